@@ -8,8 +8,8 @@ order (two small kernels over the CIGAR offsets), the FUSED range kernel (it rea
 into per-class records in LDS, the first half of the per-read walk, :436-512, and counted from there, the checkBam loop,
 :408-559), the literal kernel and the scan with findBeta2Counts + calculateSSE (:581-639).  A step ends with a device-side
 barrier: the next step's first kernel does not start before this step's last one has finished, as in a `process` run, which
-counts a read set once (``--pipelined`` drops the barrier: many samples in a row).  After the timed region the same shards are
-run the way the round timed them before the fused pass -- a LAYOUT kernel writing the records to memory, then the range kernel
+counts a read set once (``--pipelined`` drops the barrier: many samples in a row).  With ``--full``, after the timed region the
+same shards are run the way the round timed them before the fused pass -- a LAYOUT kernel writing the records to memory, then the range kernel
 over them (``roofline.two_kernels``; SPL_FUSED=0 makes that the step) -- and, as rounds 1-4 did, from the records on
 (``roofline.count_only``).
 
@@ -22,7 +22,8 @@ default for N > 1): ONE sample, its chromosomes dealt to the ranks by read count
 ``--scaling weak`` (N = 1, or asked for): every rank processes its own sample of the same shape (seed + rank).  The only
 collectives are the timing barrier and the reductions of the report.
 
-Besides the resident-step figure the line carries (rank 0): the parity of the last timed step against the oracle on the whole
+A plain run does what the line's figure needs and no more: the sample, the warm-up, the timed steps, the outputs of the last
+one when ``--dump-outputs DIR`` asks for them, the line.  With ``--full`` the line carries besides (rank 0): the parity of the last timed step against the oracle on the whole
 workload; a CPU baseline (the oracle on 1 thread and on all cores of this host; N = 1); and ``e2e`` -- the PRODUCT: BAM file ->
 decode on the GPU(s) -> reads laid out -> kernels -> .SpliSER.tsv through spliser_amd.process, wall clock of the whole call, on
 a file of constant SEQ / QUAL bytes and on one that deflates like a real library's, each with a table of the kernels' times from
@@ -49,6 +50,79 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+
+
+_GEN_STATE = None
+
+
+def _gen_batch(job):
+    """One batch of synth.Workload's reads, made in a forked worker: the reads split by chromosome, as synth._batch_job gives
+    them, and the batch's junctions already reduced to (chrom, left, right, strand, key, count) per distinct junction -- the
+    same key synth.junction_table groups by, so that the parent only merges what is distinct (the step it did on every
+    junction of the sample, on one core, took longer than the reads' generation on all of them)."""
+    from spliser_amd import synth
+    m, seed = job
+    genome, paired, nchr = _GEN_STATE
+    rb = synth.make_reads(genome, m, seed=seed, paired=paired)
+    chrom, left, right, strand = rb.junc_chrom, rb.junc_left, rb.junc_right, rb.junc_strand
+    key = (((chrom << 29 | left) << 27 | (right - left)) << 1) | (strand == ord("-")).astype(np.int64)
+    uniq, first, counts = np.unique(key, return_index=True, return_counts=True)
+    return synth.split_by_chrom(rb, nchr), (chrom[first], left[first], right[first], strand[first], uniq, counts)
+
+
+def generate_workload(name, scale, seed, workers, over=None, batch=2_500_000):
+    """synth.Workload(name, scale=scale, seed=seed, workers=workers, **over), array for array, in less time: the junction
+    table from per-batch distinct junctions (``_gen_batch``) and every chromosome's batches merged on a thread of its own.
+    np.unique(return_index) picks a key's FIRST occurrence and the batches come in order, so the table is synth.junction_table's
+    (tests/test_bench_line.py holds the two against each other)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from spliser_amd import synth
+    global _GEN_STATE
+    cfg = dict(synth.WORKLOADS[name])
+    cfg.update(over or {})
+    wl = synth.Workload.__new__(synth.Workload)
+    wl.name, wl.seed = name, cfg["seed"] if seed is None else seed
+    n_reads = int(cfg["n_reads"] * scale)
+    n_genes = max(2, int(cfg["n_genes"] * (scale if scale < 1.0 else 1.0)))
+    wl.paired = bool(cfg.get("paired"))
+    wl.genome = synth.make_genome(cfg["chroms"], n_genes, cfg["intron"], seed=wl.seed, alt_fraction=cfg.get("alt_fraction", 0.3))
+    nchr = len(wl.genome.chrom_names)
+    jobs, done = [], 0
+    while done < n_reads:
+        m = min(batch, n_reads - done)
+        jobs.append((m, wl.seed * 1000 + len(jobs)))
+        done += m
+    _GEN_STATE = (wl.genome, wl.paired, nchr)
+    try:
+        if workers > 1 and len(jobs) > 1:
+            import multiprocessing
+            with multiprocessing.get_context("fork").Pool(min(workers, len(jobs))) as pool:
+                results = pool.map(_gen_batch, jobs, chunksize=1)
+        else:
+            results = [_gen_batch(j) for j in jobs]
+    finally:
+        _GEN_STATE = None
+    per_chrom = [[sets[c] for sets, _ in results] for c in range(nchr)]
+    with ThreadPoolExecutor(max(1, min(workers, nchr))) as pool:     # (numpy's sorts and copies let go of the GIL)
+        wl.reads = list(pool.map(synth._merge_sorted, per_chrom))
+    juncs = [j for _, j in results]
+    key = np.concatenate([j[4] for j in juncs]) if juncs else np.zeros(0, np.int64)
+    if len(key) == 0:
+        z = np.zeros(0, np.int64)
+        wl.junctions = (z, z, z, np.zeros(0, np.uint8), z)
+    else:
+        _, first, inverse = np.unique(key, return_index=True, return_inverse=True)
+        counts = np.bincount(inverse.ravel(), weights=np.concatenate([j[5] for j in juncs]).astype(np.float64)).astype(np.int64)
+        wl.junctions = tuple(np.concatenate([j[k] for j in juncs])[first] for k in range(4)) + (counts,)
+    wl.n_reads = n_reads
+    return wl
+
+
+def gen_workers(world=1):
+    """Generator processes: the CPUs this process may use (its affinity, capped by its cgroup's CPU quota), shared by the ranks."""
+    nproc, quota = cpu_budget()
+    n = min(nproc, int(quota)) if quota else nproc
+    return max(1, min(32, n // max(world, 1)))
 
 
 def build_inputs(args, rank, world):
@@ -85,8 +159,7 @@ def build_inputs(args, rank, world):
         over = {} if args.alt_fraction is None else {"alt_fraction": args.alt_fraction}
         if args.genes is not None:
             over["n_genes"] = args.genes
-        wl = synth.Workload(args.workload, scale=args.scale, seed=seed, **over,
-                            workers=max(1, min(32, (os.cpu_count() or 1) // max(world, 1))))
+        wl = generate_workload(args.workload, args.scale, seed, gen_workers(world), over)
         if cache:
             wl.save(cache)
     if args.soft_clips > 0:
@@ -716,6 +789,35 @@ def resident_step(ctx, items, stranded, cryptic, steps, warmup, threads):
             "bit_exact_vs_oracle": bool(exact)}
 
 
+DUMP_LIMIT = 64 << 20   # bytes, all the files of --dump-outputs together
+DUMP_NAMES = ("beta1", "beta2_simple_reads", "double_counts", "beta2_simple", "beta2_cryptic", "beta2_weighted", "sse")
+
+
+def dump_outputs(out_dir, items, shards, counts, sses, limit=DUMP_LIMIT):
+    """What the last timed step left on the device, as a caller of the path receives it (spl_counters_download +
+    spl_sse_download): per site beta1, beta2Simple(reads), beta2Simple, beta2Cryptic, beta2Weighted, SSE, per partner edge the
+    double counts -- chromosome by chromosome in the sample's order, whichever shard a chromosome was packed into -- as
+    out_dir/<name>.npy in float64 (every counter is exact there).  Should they come to more than `limit` bytes, every array is
+    cut to the same fixed, seeded sample of its rows.  -> {name: rows written}"""
+    per = {}
+    for sh, cnt, sse in zip(shards, counts, sses):
+        for chrom, (r0, r1), (e0, e1) in zip(sh.chroms, sh.site_rows, sh.edge_rows):
+            per[chrom] = (cnt[0][r0:r1], cnt[1][r0:r1], cnt[2][e0:e1]) + tuple(a[r0:r1] for a in sse)
+    order = [c for c, _, _ in items if c in per]
+    arrays = {name: np.concatenate([per[c][k] for c in order]).astype(np.float64) if order else np.zeros(0)
+              for k, name in enumerate(DUMP_NAMES)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = limit // (8 * len(arrays)) - 64      # (room for the .npy headers)
+        for name, a in arrays.items():
+            if len(a) > keep:
+                arrays[name] = a[np.sort(np.random.default_rng(12345).choice(len(a), keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: len(a) for name, a in arrays.items()}
+
+
 def rank_pieces(items, world, rank, expected=None):
     """The pieces rank `rank` of `world` works on in a strong-scaling run, from the WHOLE sample's items [(chromosome, table, reads)]
     in file order: the sample's reads cut into `world` stretches of equal numbers (synth.strong_plan over `expected` reads per
@@ -815,10 +917,18 @@ def main():
                     "sample is loaded instead of regenerated (use under rocprofv3: no generator worker processes)")
     ap.add_argument("--copies", type=int, default=1, help="(experiment) device copies of the sample; step k works on copy "
                     "k mod copies, so that nothing a step read can still be in a cache when it is read again")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: the parity of the last timed step "
+                    "against the oracle, the CPU baseline, the other configurations' resident steps, the end-to-end and combine legs, "
+                    "the cold command lines, the roofline's extra passes (count_only, alone, two_kernels) and, N > 1, the weak-scaling "
+                    "pass and every rank's parity.  The options above that shape those parts act with --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(rank 0's counters and beta2 / SSE results, chromosome by chromosome) as DIR/<name>.npy in float64")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     rank = int(os.environ.get("RANK", "0"))
@@ -844,23 +954,23 @@ def main():
     # N > 1: rank 0's end-to-end legs (process(devices = all the node's GPUs) on ONE file, after the collectives) have a sample of
     # their own -- config 2's shape, five chromosomes: what whole-reference shares could give five GPUs at most
     wl_e2e = None
-    if args.e2e == "auto" and rank == 0 and world > 1:
+    if args.full and args.e2e == "auto" and rank == 0 and world > 1:
         small = argparse.Namespace(**vars(args))
         small.workload, small.cache, small.scaling = "arabidopsis", None, "weak"
         wl_e2e = build_inputs(small, 0, 1)
     # the e2e leg of the smaller configuration wants a sample of its own: generated now, for the same reason
     wl_small = None
-    if args.e2e == "auto" and rank == 0 and world == 1 and args.workload == "human" and args.scale == 1.0 and not args.no_small_leg:
+    if args.full and args.e2e == "auto" and rank == 0 and world == 1 and args.workload == "human" and args.scale == 1.0 and not args.no_small_leg:
         small = argparse.Namespace(**vars(args))
         small.workload, small.cache = "arabidopsis", None
         wl_small = build_inputs(small, 0, 1)
-    full_default = args.e2e == "auto" and rank == 0 and world == 1 and args.workload == "human" and args.scale == 1.0
+    full_default = args.full and args.e2e == "auto" and rank == 0 and world == 1 and args.workload == "human" and args.scale == 1.0
     # ... and so do the OTHER configurations whose resident step rides in the line (`other_steps`): config 5's shape (mouse, paired
     # flags, `fr` + cryptic: the STRANDED fused instantiation), config 2 (the small leg's sample, above), and this workload with a
     # local aligner's soft clips on three reads in ten
     others = []
     wl_mouse_e2e = None
-    if rank == 0 and world == 1 and args.workload == "human" and not args.no_other_steps and args.kernel == "ranges" and args.soft_clips == 0:
+    if args.full and rank == 0 and world == 1 and args.workload == "human" and not args.no_other_steps and args.kernel == "ranges" and args.soft_clips == 0:
         ms = argparse.Namespace(**vars(args))
         ms.workload, ms.cache, ms.stranded = "mouse_stranded", None, None
         wl_m, _, items_m, stranded_m = build_inputs(ms, 0, 1)
@@ -874,7 +984,7 @@ def main():
         from spliser_amd import synth as _synth
         clipped = [(c, arr, _synth.add_soft_clips(rd, 0.3, seed=100 + k)) for k, (c, arr, rd) in enumerate(items)]
         others.append(("%s clipped30" % args.workload, clipped, stranded, args.beta2Cryptic))
-    cmb_samples = make_combine_samples(args) if ((full_default and args.combine == "auto") or (args.combine == "on" and rank == 0 and world == 1)) else None
+    cmb_samples = make_combine_samples(args) if ((full_default and args.combine == "auto") or (args.full and args.combine == "on" and rank == 0 and world == 1)) else None
     shards = shard.pack(items, concat_reads=False)
     n_reads = sum(rd.n for _, _, rd in items)
     n_sites = sum(arr.n for _, arr, _ in items)
@@ -886,7 +996,7 @@ def main():
     # ---- the command line as users run it, BEFORE this process touches the GPU: the files of the sequence-like legs are written now
     # (host code) and `python -m spliser_amd process` runs on them as a child, a fresh interpreter each (cold_cli)
     pre_files, cold = {}, {}
-    if args.e2e == "auto" and rank == 0 and world == 1 and not args.no_cold_cli and (args.e2e_seq_mode in (None, 1)):
+    if args.full and args.e2e == "auto" and rank == 0 and world == 1 and not args.no_cold_cli and (args.e2e_seq_mode in (None, 1)):
         pre_files[args.workload] = write_e2e_files(args.workload, wl, stranded, 1)
         cold[args.workload] = cold_cli(pre_files[args.workload], stranded, args.beta2Cryptic)
         if wl_small is not None:
@@ -968,13 +1078,15 @@ def main():
     gpu_counts = [ds.counters() for ds, _, _ in dev]
     gpu_sse = [ds.sse_results() for ds, _, _ in dev]
     literal_reads = sum(dr.literal_queue_size() for _, dr, _ in dev) if args.kernel != "pairs" else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, items, shards, gpu_counts, gpu_sse)
     # outside the timed region: (a) the step as rounds 1-4 timed it -- from the records on, no layout -- for continuity
     # (roofline.count_only); (b) the range kernel with nothing beside it (a sync after every launch, so that the tail of a pass
     # is over before the next range kernel starts)
     # WEAK beside strong (N > 1, strong mode): a step of N passes over the rank's own stretch -- every GPU counts as many reads a
     # step as the one GPU of an N = 1 run does, in launches of 1/N the size -- timed the same way (barrier, MAX over ranks below)
     weak_elapsed = None
-    if dist is not None and args.scaling == "strong" and world > 1:
+    if args.full and dist is not None and args.scaling == "strong" and world > 1:
         fence()
         tw = time.perf_counter()
         for _ in range(args.steps):
@@ -996,26 +1108,28 @@ def main():
         we = torch.tensor([1.0 if same_w else 0.0], dtype=torch.float64, device=red_device)
         dist.all_reduce(we, op=dist.ReduceOp.MIN)
         weak_same = bool(we.item() > 0.5)
-    step_no[0] = 0
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(layout=False)
-    ctx.sync()
-    count_only_s = (time.perf_counter() - t1) / args.steps
-    ctx.kernel_timing_begin(5 * len(dev))
-    for _ in range(5):
-        for ds, dr, _ in dev:
-            ctx.count_launch(ds, dr, scode, 0, kflags)
-            ctx.sse_launch(ds, args.beta2Cryptic)
-            ctx.sync()
-    kernel_ms_alone = ctx.kernel_timing_collect(5 * len(dev) + 8)
+    count_only_s, kernel_ms_alone = None, []
+    if args.full:
+        step_no[0] = 0
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(layout=False)
+        ctx.sync()
+        count_only_s = (time.perf_counter() - t1) / args.steps
+        ctx.kernel_timing_begin(5 * len(dev))
+        for _ in range(5):
+            for ds, dr, _ in dev:
+                ctx.count_launch(ds, dr, scode, 0, kflags)
+                ctx.sse_launch(ds, args.beta2Cryptic)
+                ctx.sync()
+        kernel_ms_alone = ctx.kernel_timing_collect(5 * len(dev) + 8)
     info = ctx.launch_info()
     # (c) a fused pass (no records in memory: layout_bytes says 0 written) beside what it replaced: the same shards as read sets
     # with records in memory (SPL_FUSED=0), every step the layout kernel and the range kernel -- rounds 1-5's two kernels
     fused = all(b == 0 for _, b in layout_bytes) and args.kernel == "ranges"
     two_kernels = None
-    if fused:
+    if fused and args.full:
         os.environ["SPL_FUSED"] = "0"
         try:
             packed = [(ds, ctx.layout_read_segments(soa, [shift for _, shift in sh.read_segments])) for (ds, _, soa), sh in zip(dev, shards)]
@@ -1057,7 +1171,7 @@ def main():
     my_elapsed = elapsed
     if dist is not None:
         exact_rank = None
-        if strong is not None:
+        if args.full and strong is not None:
             # every rank holds its own stretch against the oracle: the PARTIAL counters of its pieces (and what findBeta2Counts +
             # calculateSSE make of them) are what the oracle gives for the same reads against the same tables
             nproc, quota = cpu_budget()
@@ -1092,7 +1206,7 @@ def main():
     e2e = None
     combine_res = None
     other_steps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         t_cpu1, want = run_oracle(items, scode, args.beta2Cryptic, 1)
         exact = True
         for sh, cnts, sses in zip(shards, gpu_counts, gpu_sse):
@@ -1245,10 +1359,11 @@ def main():
                                     "how": "the range kernel: 5 more launches after the timed region, each followed by a sync"}),
                          "path": {"what": "SURVEY 8(d)'s algorithmic bytes of a step / time of a step: every kernel of the pass (layout included) and the gaps between them",
                                   "achieved": path_gbs, "frac": path_gbs / HBM_PEAK_GBS},
-                         "count_only": {"what": ("the step without the chunk map and order kernels (they need the CIGAR offsets only)" if fused else
-                                                 "the step as rounds 1-4 timed it: from the records on (range + literal + scan), no layout"),
-                                        "ms_per_step": count_only_s * 1e3, "reads_per_sec": n_reads / count_only_s,
-                                        "path_frac": alg_bytes / count_only_s / 1e9 / HBM_PEAK_GBS},
+                         "count_only": (None if count_only_s is None else
+                                        {"what": ("the step without the chunk map and order kernels (they need the CIGAR offsets only)" if fused else
+                                                  "the step as rounds 1-4 timed it: from the records on (range + literal + scan), no layout"),
+                                         "ms_per_step": count_only_s * 1e3, "reads_per_sec": n_reads / count_only_s,
+                                         "path_frac": alg_bytes / count_only_s / 1e9 / HBM_PEAK_GBS}),
                          "hbm_actual": (None if not traffic or not kernel_ms else
                                         {"what": "the range kernel: HBM bytes per launch by the PMC counters (range_traffic) / the kernel's time: what the "
                                                  "memory system really moved, beside the algorithmic rate",

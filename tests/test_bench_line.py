@@ -4,6 +4,9 @@ import json
 import os
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -136,3 +139,79 @@ def test_the_committed_traffic_measurement_is_of_these_kernel_sources():
         if t.get("workload") == "human":
             have.append(t.get("kernel_src_sha16"))
     assert sha in have, "no profiles/*_traffic.json for the human workload was measured with the current kernel sources (%s): run tools/prof_round.sh" % sha
+
+
+def _same_workload(a, b):
+    for x, y in zip(a.junctions, b.junctions):
+        assert x.dtype == y.dtype and np.array_equal(x, y)
+    assert len(a.reads) == len(b.reads) and a.n_reads == b.n_reads and a.genome.chrom_names == b.genome.chrom_names
+    for ra, rb in zip(a.reads, b.reads):
+        for f in ("pos", "flag", "cig_off", "cigar"):
+            assert getattr(ra, f).dtype == getattr(rb, f).dtype and np.array_equal(getattr(ra, f), getattr(rb, f)), f
+        assert ra.max_end == rb.max_end
+
+
+@pytest.mark.parametrize("name,scale,over", [("arabidopsis", 0.01, {}), ("mouse_stranded", 0.002, {"n_genes": 400})])
+def test_generate_workload_is_synth_workload(name, scale, over):
+    """bench.py's sample generator (per-batch junction tables, chromosomes merged on threads) gives synth.Workload's sample, array
+    for array -- in several batches, on several worker processes, paired flags included."""
+    from spliser_amd import synth
+    want = synth.Workload(name, scale=scale, seed=7, batch=40000, workers=3, **over)
+    got = bench.generate_workload(name, scale, 7, 3, over, batch=40000)
+    assert len(want.junctions[0]) > 100
+    _same_workload(want, got)
+    _same_workload(want, bench.generate_workload(name, scale, 7, 1, over, batch=40000))
+
+
+def _dump_case():
+    from spliser_amd import sites, synth
+    wl = synth.Workload("arabidopsis", scale=0.002, seed=9, workers=1)
+    table = sites.SiteTable(is_stranded=False)
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        bed = os.path.join(tmp, "j.bed")
+        synth.write_bed(bed, wl.genome.chrom_names, wl.junctions)
+        table.add_bed(bed)
+    table.find_competitors()
+    items = [(c, table.chrom_arrays(c), wl.reads[i]) for i, c in enumerate(wl.genome.chrom_names) if table.chrom_arrays(c).n]
+    return items
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_by_chromosome(tmp_path):
+    """--dump-outputs: every array a caller of the step receives, as float64 .npy, chromosome by chromosome in the sample's order
+    whatever the shards' packing; past the size limit, the same seeded sample every time."""
+    from spliser_amd import shard
+    items = _dump_case()
+    assert len(items) > 2
+    # two packings of the same chromosomes: one shard each, in reverse order
+    for shards in (shard.pack(items, concat_reads=False), [shard.pack([it], concat_reads=False)[0] for it in reversed(items)]):
+        counts, sses = [], []
+        for sh in shards:
+            n, n_e = sh.site_rows[-1][1], sh.edge_rows[-1][1]
+            base = np.zeros(n, np.int64)
+            for chrom, (r0, r1), _ in zip(sh.chroms, sh.site_rows, sh.edge_rows):
+                base[r0:r1] = [k for k, it in enumerate(items) if it[0] == chrom][0] * 100000 + np.arange(r1 - r0)
+            ebase = np.zeros(n_e, np.int64)
+            for chrom, _, (e0, e1) in zip(sh.chroms, sh.site_rows, sh.edge_rows):
+                ebase[e0:e1] = [k for k, it in enumerate(items) if it[0] == chrom][0] * 100000 + np.arange(e1 - e0)
+            counts.append((base.astype(np.uint32), (base + 1).astype(np.uint32), ebase.astype(np.uint32)))
+            sses.append((base + 2, base + 3, base + 0.25, base + 0.5))
+        out = tmp_path / ("d%d" % len(shards))
+        rows = bench.dump_outputs(str(out), items, shards, counts, sses)
+        n_sites = sum(arr.n for _, arr, _ in items)
+        want = np.concatenate([k * 100000 + np.arange(arr.n) for k, (_, arr, _) in enumerate(items)]).astype(np.float64)
+        assert rows["beta1"] == n_sites and rows["double_counts"] == sum(int(arr.part_off[-1]) for _, arr, _ in items)
+        for name, add in zip(bench.DUMP_NAMES, (0, 1, None, 2, 3, 0.25, 0.5)):
+            a = np.load(str(out / (name + ".npy")))
+            assert a.dtype == np.float64
+            if add is not None:
+                assert np.array_equal(a, want + add), name
+    small = bench.dump_outputs(str(tmp_path / "cut"), items, shards, counts, sses, limit=8 * 7 * 200)
+    again = bench.dump_outputs(str(tmp_path / "cut2"), items, shards, counts, sses, limit=8 * 7 * 200)
+    assert small == again and max(small.values()) < n_sites
+    total = 0
+    for name in bench.DUMP_NAMES:
+        a, b = np.load(str(tmp_path / "cut" / (name + ".npy"))), np.load(str(tmp_path / "cut2" / (name + ".npy")))
+        assert np.array_equal(a, b)
+        total += os.path.getsize(str(tmp_path / "cut" / (name + ".npy")))
+    assert total <= 8 * 7 * 200

@@ -23,7 +23,8 @@ def is_fused(name):   # void spl_count_ranges_kernel<STRANDED, AGG, BIG, FUSED>(
 
 def mean(counter, sub, kernel="spl_count_ranges_kernel", fused=None):
     vals = collections.defaultdict(list)
-    for path in glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_%s_%s" % (tag, sub), "**", "*counter_collection.csv"), recursive=True):
+    out_dir = os.environ.get("OUT") or os.path.join(ROOT, "results")     # (where tools/prof_pmc.sh put the passes)
+    for path in glob.glob(os.path.join(out_dir, "pmc_%s_%s" % (tag, sub), "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(path)):
             if r["Counter_Name"] == counter and kernel in r["Kernel_Name"] and (fused is None or is_fused(r["Kernel_Name"]) == fused):
                 vals[r["Kernel_Name"]].append(float(r["Counter_Value"]))
