@@ -6,6 +6,7 @@ import pytest
 
 from conftest import golden_cases
 import helpers
+import limitcases
 from spliser_amd import native, samio, shard, sites, synth
 
 pytestmark = pytest.mark.gpu
@@ -101,38 +102,8 @@ def test_gpu_reads_with_non_consuming_ops(ctx, oracle_lib):
     """Soft clips, hard clips, insertions and padding change nothing for checkBam; the pack kernel drops them from short
     CIGARs (so that "5S95M100N50M" takes the once-spliced path).  Random decorations of spliced and unspliced reads on a
     table with rivals, against the oracle, all kernels, all strand modes."""
-    rng = np.random.default_rng(17)
-    wl = synth.Workload("arabidopsis", scale=0.004, seed=31)
-    import tempfile
-    with tempfile.TemporaryDirectory() as tmp:
-        import pathlib
-        table = _table_for(wl, pathlib.Path(tmp), True)
-    name = wl.genome.chrom_names[0]
-    arr, reads = table.chrom_arrays(name), wl.reads[0]
-    n = reads.n
-    cig_off = reads.cig_off.astype(np.int64)
-    new_ops, new_off = [], [0]
-    for i in range(n):
-        ops = reads.cigar[cig_off[i]:cig_off[i + 1]].tolist()
-        style = int(rng.integers(0, 8))
-        out = []
-        if style in (1, 3, 5):
-            out.append((int(rng.integers(1, 9)) << 4) | 5)          # leading hard clip
-        if style in (1, 2, 3):
-            out.append((int(rng.integers(1, 30)) << 4) | 4)         # leading soft clip
-        for k, op in enumerate(ops):
-            if style in (4, 5) and k == 0 and (op & 15) == 0 and (op >> 4) > 20:   # an insertion splits the first block
-                a = int(rng.integers(5, (op >> 4) - 5))
-                out += [(a << 4) | 0, (int(rng.integers(1, 4)) << 4) | 1, (((op >> 4) - a) << 4) | 0]
-            elif style == 6 and k == 0:
-                out += [op, (3 << 4) | 6]                            # padding after the first op
-            else:
-                out.append(op)
-        if style in (2, 3, 7):
-            out.append((int(rng.integers(1, 30)) << 4) | 4)         # trailing soft clip
-        new_ops += out
-        new_off.append(len(new_ops))
-    deco = native.ReadArrays(reads.pos, reads.flag, np.array(new_off, np.uint32), np.array(new_ops, np.uint32))
+    arr, rs = limitcases.non_consuming_ops_case()
+    deco = native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar)
     sites_c = native.SiteArrays.from_chrom(arr)
     for stranded in (0, 1, 2):
         want = oracle_lib.check_bam(arr.pos, arr.strand, arr.part_off, arr.part_pos, arr.comp_off, arr.comp_pos, deco.pos, deco.flag,
@@ -148,56 +119,9 @@ def test_gpu_twice_spliced_class_limits(ctx, oracle_lib):
     """The twice-spliced class packs five lengths into three words (aligned < 4096, introns < 2^28): reads on and just beyond
     those limits, with =/X blocks, soft clips, a deletion instead of an intron, in every neighbourhood (alone, in waves of
     other classes), all modes, against the oracle."""
-    rng = np.random.default_rng(23)
-    # sites: junction ends of the reads below plus alternatives sharing ends (rivals), both strands
-    base = [1000, 1100, 1400, 1500, 5000, 5100, 5400, 5600, 9000, 9050, 300000000, 300000100]
-    SHIFT = 10000   # (room in front of the first site for the 4095-base blocks)
-    pos = np.array(sorted(set(base + [1050, 1450, 5050, 5500, 9020, 1000 + 4095, 1000 + 4096 + 50])), np.int64) + SHIFT
-    n = len(pos)
-    strand = np.where(np.arange(n) % 3 == 0, ord("-"), ord("+")).astype(np.uint8)
-    # partners: a ring of mutual links over neighbours two apart gives everybody competitors
-    part = [[] for _ in range(n)]
-    for i in range(n):
-        for j in (i + 1, i + 2):
-            if j < n:
-                part[i].append(j)
-                part[j].append(i)
-    part_off = np.zeros(n + 1, np.uint32)
-    np.cumsum([len(x) for x in part], out=part_off[1:])
-    part_site = np.array([j for x in part for j in x], np.int32)
-    part_pos = pos[part_site]
-    comp = [sorted({int(pos[c]) for p_ in x for c in part[p_] if c != i}) for i, x in enumerate(part)]
-    comp_off = np.zeros(n + 1, np.uint32)
-    np.cumsum([len(x) for x in comp], out=comp_off[1:])
-    comp_pos = np.array([c for x in comp for c in x], np.int64)
-    sites_c = native.SiteArrays(pos, strand, part_off, part_pos, comp_off, comp_pos, part_site=part_site)
-
-    def rec(flag, p, *ops):
-        return (flag, p, ops)
-    M, I, D, N, S, EQ, X = 0, 1, 2, 3, 4, 7, 8
-    shapes = [
-        rec(0, 951, (50, M), (100, N), (300, M), (100, N), (60, M)),                   # 1000|1100 .. 1400|1500 ends on sites
-        rec(16, 951, (50, EQ), (100, N), (300, X), (100, N), (60, EQ)),
-        rec(99, 951, (3, S), (50, M), (100, N), (300, M), (100, N), (60, M), (7, S)),   # soft clips: same class after compaction
-        rec(0, 951, (50, M), (100, N), (300, M), (100, D), (60, M)),                    # a deletion where the second intron was
-        rec(0, 951, (50, M), (100, N), (150, M), (2, I), (150, M), (100, N), (60, M)),  # insertion splits the middle block: wide
-        rec(0, 1000 - 4094, (4095, M), (100, N), (300, M), (100, N), (60, M)),          # longest block that fits 12 bits
-        rec(0, 1000 - 4095, (4096, M), (100, N), (300, M), (100, N), (60, M)),          # one more: wide
-        rec(0, 4951, (50, M), (100, N), (300, M), (200, N), (4095, M)),
-        rec(0, 8951, (50, M), (50, N), (30, M), ((1 << 28) - 1, N), (40, M)),         # the longest intron a BAM record can hold
-        rec(147, 8951, (50, M), (50, N), (0, M), (5, N), (40, M)),                    # an empty middle block
-        rec(0, 951, (50, M), (100, N), (300, M)), rec(0, 951, (150, M)), rec(4, 1000, (50, M), (100, N), (300, M), (100, N), (60, M)),
-    ]
-    recs = []
-    for k in range(3000):                        # every shape in every neighbourhood
-        recs.append(shapes[int(rng.integers(0, len(shapes)))])
-    recs += [shapes[0]] * 300 + [shapes[7]] * 200  # and whole waves of the class
-    recs.sort(key=lambda r: r[1])
-    rpos = np.array([r[1] for r in recs], np.int64) + SHIFT
-    rflag = np.array([r[0] for r in recs], np.uint16)
-    off = np.concatenate(([0], np.cumsum([len(r[2]) for r in recs])))
-    cig = np.array([(ln << 4) | code for r in recs for ln, code in r[2]], np.uint32)
-    reads_c = native.ReadArrays(rpos, rflag, off, cig)
+    sites_c, reads_c = limitcases.twice_spliced_limits_case()
+    pos, strand, part_off, part_pos, comp_off, comp_pos = (sites_c.pos, sites_c.strand, sites_c.part_off, sites_c.part_pos,
+                                                           sites_c.comp_off, sites_c.comp_pos)
     seen = np.zeros(3, np.int64)
     for stranded in (0, 1, 2):
         for combine in (0, 1):
@@ -342,47 +266,16 @@ def test_gpu_segment_upload_equals_packed_upload(ctx, tmp_path):
 def test_gpu_long_introns_and_hot_sites(ctx, oracle_lib):
     """Skew: reads whose introns span thousands of sites (wave-cooperative path), one site hit by 200k reads
     (LDS counter contention), sites outside the LDS window (global-atomic path), unsorted reads."""
-    rng = np.random.default_rng(5)
-    n_sites = 30000
-    pos = np.sort(rng.choice(np.arange(1000, 3_000_000), n_sites, replace=False)).astype(np.int64)
-    strand = np.where(rng.random(n_sites) < 0.5, ord("+"), ord("-")).astype(np.uint8)
-    # partners: pair consecutive sites; competitors: a few
-    part_off = np.arange(n_sites + 1, dtype=np.uint32)
-    partner = np.arange(n_sites) ^ 1
-    part_pos = pos[partner]
-    comp_off = np.zeros(n_sites + 1, np.uint32)
-    has_comp = rng.random(n_sites) < 0.2
-    comp_off[1:] = np.cumsum(has_comp)
-    comp_pos = pos[(np.arange(n_sites)[has_comp] + 2) % n_sites]
-    recs = []
-    for _ in range(300):   # long introns: 10 kb .. 2.5 Mb
-        p = int(rng.integers(1000, 400000))
-        recs.append((int(rng.choice([0, 16, 99, 147])), p, "20M%dN30M" % int(rng.integers(10000, 2_500_000))))
-    hot = int(pos[1234])
-    recs += [(0, hot - 40, "100M")] * 3000
-    hot_reads = samio.ReadSet.from_records(recs)
-    # bulk: 200k unspliced reads on the hot site + random 150M reads; then shuffle a slice to break sortedness
-    bulk_pos = np.concatenate((np.full(200000, hot - 70), rng.integers(1000, 2_999_000, 300000))).astype(np.int64)
-    bulk = samio.ReadSet(bulk_pos, rng.choice([0, 16], bulk_pos.shape[0]), np.arange(bulk_pos.shape[0] + 1),
-                         np.full(bulk_pos.shape[0], 150 << 4, np.uint32))
-    allpos = np.concatenate((hot_reads.pos, bulk.pos)).astype(np.int64)
-    allflag = np.concatenate((hot_reads.flag, bulk.flag))
-    nops = np.concatenate((np.diff(hot_reads.cig_off.astype(np.int64)), np.ones(bulk.n, np.int64)))
-    ops = np.concatenate((hot_reads.cigar, bulk.cigar))
-    order = np.argsort(allpos, kind="stable")
-    order[1000:5000] = order[1000:5000][::-1]
-    src = np.concatenate(([0], np.cumsum(nops)))
-    cig = np.concatenate([ops[src[i]:src[i + 1]] for i in order])
-    off = np.concatenate(([0], np.cumsum(nops[order])))
-    sites_c = native.SiteArrays(pos, strand, part_off, part_pos, comp_off, comp_pos, part_site=partner)
-    reads_c = native.ReadArrays(allpos[order], allflag[order], off, cig)
+    sites_c, reads_c, hot_row = limitcases.long_introns_hot_sites_case()
+    pos, strand, part_off, part_pos, comp_off, comp_pos = (sites_c.pos, sites_c.strand, sites_c.part_off, sites_c.part_pos,
+                                                           sites_c.comp_off, sites_c.comp_pos)
     for stranded, flags in ((0, 0), (1, 0), (0, native.OPT_PAIR_KERNEL), (2, native.OPT_PAIR_KERNEL)):
         got = ctx.count(sites_c, reads_c, stranded, 0, flags)
         want = oracle_lib.check_bam(pos, strand, part_off, part_pos, comp_off, comp_pos, reads_c.pos, reads_c.flag,
                                     reads_c.cig_off, reads_c.cigar, stranded, 0)
         for g, w in zip(got, want):
             assert np.array_equal(g, w)
-    assert int(want[0][1234]) >= 50000
+    assert int(want[0][hot_row]) >= 50000
     # a table without part_site (or with one-way partner links) must silently take the pair kernel
     one_way = native.SiteArrays(pos, strand, part_off, part_pos, comp_off, comp_pos)
     got = ctx.count(one_way, reads_c, 1, 0)
@@ -395,25 +288,9 @@ def test_gpu_long_introns_and_hot_sites(ctx, oracle_lib):
 def test_gpu_read_with_more_ops_than_the_packed_count_holds(ctx, oracle_lib):
     """A read of 70 000 CIGAR ops (the packed op count saturates at 65 535) between ordinary reads: the kernels must find
     its true op count although the chunk-local partition moves it away from its place in the input."""
-    # the long read ends at 105 099: a walk that borrowed the ops of the next reads would run on over the site at 105 150
-    pos = np.array([150, 400, 100300, 100900, 105150, 200500], np.int64)
-    strand = np.full(6, ord("+"), np.uint8)
-    part_off = np.array([0, 1, 2, 3, 4, 4, 4], np.uint32)
-    part_pos = np.array([400, 150, 100900, 100300], np.int64)
-    part_site = np.array([1, 0, 3, 2], np.int32)
-    comp_off = np.zeros(7, np.uint32)
-    comp_pos = np.zeros(0, np.int64)
-    sites_c = native.SiteArrays(pos, strand, part_off, part_pos, comp_off, comp_pos, part_site=part_site)
-    n_pairs = 35000
-    long_ops = np.empty(2 * n_pairs, np.uint32)       # 1M 2D 1M 2D ...: 70 000 ops, 105 000 reference bases
-    long_ops[0::2] = (1 << 4) | 0
-    long_ops[1::2] = (2 << 4) | 2
-    recs_ops = [long_ops, np.array([(100 << 4) | 0], np.uint32), np.array([(50 << 4) | 0, (249 << 4) | 3, (60 << 4) | 0], np.uint32),
-                np.array([(120 << 4) | 0], np.uint32)]
-    rpos = np.array([100, 120, 101, 100250], np.int64)
-    order = np.argsort(rpos, kind="stable")
-    off = np.concatenate(([0], np.cumsum([len(recs_ops[i]) for i in order])))
-    reads_c = native.ReadArrays(rpos[order], np.zeros(4, np.uint16), off, np.concatenate([recs_ops[i] for i in order]))
+    sites_c, reads_c = limitcases.more_ops_than_the_packed_count_case()
+    pos, strand, part_off, part_pos, comp_off, comp_pos = (sites_c.pos, sites_c.strand, sites_c.part_off, sites_c.part_pos,
+                                                           sites_c.comp_off, sites_c.comp_pos)
     want = oracle_lib.check_bam(pos, strand, part_off, part_pos, comp_off, comp_pos, reads_c.pos, reads_c.flag,
                                 reads_c.cig_off, reads_c.cigar, 0, 0)
     for flags in KERNELS.values():
