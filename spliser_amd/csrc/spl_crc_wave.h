@@ -1,6 +1,6 @@
 // spl_crc_wave.h -- CRC32 (IEEE 802.3, reflected: a BGZF block's trailer, RFC 1952 section 8) of one block's payload by ONE WAVE.
 //
-// Round 4's kernel gave a block to a lane (spl_crc.h): 768 waves for a window of 49 152 blocks, every lane of a wave on a 64 KiB
+// Round 4's kernel gave a block to a lane: 768 waves for a window of 49 152 blocks, every lane of a wave on a 64 KiB
 // stretch of its own -- 64 (x 4 streams) different lines per load instruction, a serial chain of table look-ups per stream -- and
 // ran at a tenth of the memory's rate, 47-88 ms of a human file's decode.  Here the wave walks the block in ROWS of 1024 bytes,
 // lane i bytes [16 i, 16 i + 16) of every row: one coalesced 16-byte load per lane and row.  The CRC register is linear in the data

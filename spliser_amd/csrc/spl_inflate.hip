@@ -62,33 +62,6 @@ __global__ __launch_bounds__(64) void spl_inflate_copy_kernel(const spl_zblock *
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// CRC32 (IEEE, reflected) of every block's payload against the value in its trailer: one lane per block -- 768 waves for a window,
-// which leaves the CUs to the decoding kernel beside it -- and the lane's block as S streams (spl_crc.h): S chains of table
-// look-ups and S 16-byte loads in flight instead of one of each (the lane a word after the other waited 2 000 cycles a load:
-// 64 lanes on 64 different lines and nothing else to do).  Tables in LDS: slicing by four, and x^(2^k) for putting the streams'
-// registers together.  Blocks that already failed keep their status.
-template <int S>
-__global__ __launch_bounds__(64) void spl_crc32_kernel(const uint8_t *out_all, const spl_zblock *blocks, uint32_t n_blocks, uint32_t *status)
-{
-    __shared__ uint32_t table[4 * 256]; // table[k * 256 + b] = the CRC register after byte b and k zero bytes
-    __shared__ uint32_t x2n[splcrc::N_X2N];
-    for (uint32_t i = threadIdx.x; i < 256u; i += 64u) table[i] = splcrc::byte_entry(i);
-    if (threadIdx.x < (uint32_t)splcrc::N_X2N) x2n[threadIdx.x] = splcrc::x2n_entry(threadIdx.x);
-    __syncthreads();
-    for (int k = 1; k < 4; ++k) {
-        for (uint32_t i = threadIdx.x; i < 256u; i += 64u) {
-            const uint32_t c = table[(k - 1) * 256 + i];
-            table[k * 256 + i] = (c >> 8) ^ table[c & 0xffu];
-        }
-        __syncthreads();
-    }
-    const uint32_t b = blockIdx.x * 64u + threadIdx.x;
-    if (b >= n_blocks) return;
-    if (status[b] != SPL_Z_OK) return;
-    const spl_zblock zb = blocks[b];
-    if (splcrc::block<S>(out_all + zb.out, zb.out_len, table, x2n) != zb.crc) status[b] = SPL_Z_BAD_CRC;
-}
-
 // CRC32 a block per WAVE (spl_crc_wave.h, round 6): rows of 1024 bytes, a coalesced 16-byte load and twenty independent look-ups a
 // lane and row.  Workgroups of four waves share the twenty tables (20 KB of LDS: seven workgroups a CU) and stay: a wave takes
 // block after block (its number, + the grid's waves, ...), so that the tables are made once per workgroup, not per block.
@@ -413,8 +386,7 @@ extern "C" int spl_dev_launch_inflate_decode3(const uint8_t *image, const spl_zb
     if (n_blocks == 0) return 0;
     if (!work) return (int)hipErrorInvalidValue; // (nothing would be launched and the blocks' status words left as they were: an error, not a success)
     if (stride < 256u || stride > SPL_Z_TOKEN_STRIDE || (stride & 15u)) return (int)hipErrorInvalidValue;
-    // SPL_Z_WRITING_PASS=1 (A/B): every tile's tokens by a writing pass of their own, as until round 5 (now: written while the last count is taken)
-    static const uint32_t opts = getenv("SPL_Z_WRITING_PASS") ? splz::OPT_WRITING_PASS : 0u;
+    const uint32_t opts = 0u; // (a tile's tokens are written while its last count is taken; splz::OPT_WRITING_PASS, a writing pass per tile, is the host tests' fallback)
     // (measured, round 6: fewer decoding waves a CU -- 12, 9, 8 instead of the 16 that fill its LDS, by padding -- make room for the
     //  copying kernel's waves and only slow the decoder, 294 -> 345 / 412 / 468 ms a human file, the copying kernel 234 -> 215:
     //  profiles/r06n_decode_lds_pad_q2.txt)
@@ -460,12 +432,6 @@ extern "C" int spl_dev_launch_inflate(const uint8_t *image, const spl_zblock *bl
 extern "C" int spl_dev_launch_crc32(const uint8_t *out, const spl_zblock *blocks, uint32_t n_blocks, uint32_t *status, void *stream)
 {
     if (n_blocks == 0) return 0;
-    // SPL_CRC_LANES=1 (A/B): round 4's kernel, a block per lane as four streams (1.6 ms a window of 43 169 blocks alone, 2-4 in the pipeline)
-    static const bool per_lane = getenv("SPL_CRC_LANES") != nullptr;
-    if (per_lane) {
-        hipLaunchKernelGGL(spl_crc32_kernel<4>, dim3((n_blocks + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, out, blocks, n_blocks, status);
-        return (int)hipGetLastError();
-    }
     // a block per wave, four waves a workgroup, at most six workgroups per CU's worth of grid: the waves take block after block
     const uint32_t groups = std::min<uint32_t>((n_blocks + 3u) / 4u, 256u * 6u);
     hipLaunchKernelGGL(spl_crc32_wave_kernel, dim3(groups), dim3(256), 0, (hipStream_t)stream, out, blocks, n_blocks, status);

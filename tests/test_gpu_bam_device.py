@@ -258,12 +258,11 @@ def test_either_decoding_kernel_on_every_kind_of_file(ctx, tmp_path, monkeypatch
         assert _both(path, ctx, names, sets) is True
 
 
-@pytest.mark.parametrize("levels", ["0", "1", "2", "3", "4"])
+@pytest.mark.parametrize("levels", ["0", "1"])
 def test_stream_set_ups_of_the_decode(ctx, tmp_path, monkeypatch, levels):
-    """SPL_STREAM_PRIORITIES: the decode's streams at priority levels of their own and kept by the process (1, the default), all at
-    the normal level and made per call as in rounds 3-5 (0), and the variants the profile measured (2: the short kernels' stream at
-    the low level; 3: made per call; 4: the file's pieces on the context's copy stream) -- windows of a few blocks, several calls
-    in a row (the second finds the first's streams), the same reads every way."""
+    """SPL_STREAM_PRIORITIES: the decode's streams at priority levels of their own and kept by the process (1, the default), and
+    all at the normal level and made per call (0: the way where the runtime reports no priority range) -- windows of a few blocks,
+    several calls in a row (the second finds the first's streams), the same reads either way."""
     monkeypatch.setenv("SPL_STREAM_PRIORITIES", levels)
     monkeypatch.setenv("SPL_INFLATE_WINDOW_BLOCKS", "9")
     for seq_mode, level, seed in ((1, 1, 51), (2, 6, 52), (1, 1, 53)):
@@ -273,14 +272,17 @@ def test_stream_set_ups_of_the_decode(ctx, tmp_path, monkeypatch, levels):
         assert _both(path, ctx, names, sets) is True
 
 
-@pytest.mark.parametrize("bufs", [("1", "1"), ("2", "1"), ("1", "3"), ("3", "2"), ("4", "4")])
+@pytest.mark.parametrize("bufs", [("1", "1"), ("2", "1"), ("1", "3"), ("3", "2"), ("4", "4"), ("2", "2", "walk")])
 def test_windows_in_flight(ctx, tmp_path, monkeypatch, bufs):
     """A window's inflated bytes (copying kernel -> CRC32, scan, extraction) and its tokens (decoding kernel -> copying kernel) have
     buffers of their own, n_buf and n_zw of them, and every kernel waits for the reader of ITS buffer (the decoding of window
     k + n_zw for the copying of window k, the copying of window k + n_buf for the extraction of window k): any numbers of the two,
-    windows of 3 and 16 blocks on files of a few hundred, must give what the host decoder gives."""
+    windows of 3 and 16 blocks on files of a few hundred, must give what the host decoder gives.  "walk": every window's records
+    extracted by the walking kernel (SPL_EXTRACT_WALK=1), the one a window with more blocks than the placed records have room for takes."""
     monkeypatch.setenv("SPL_INFLATE_BUFFERS", bufs[0])
     monkeypatch.setenv("SPL_INFLATE_TOKEN_BUFFERS", bufs[1])
+    if len(bufs) > 2:
+        monkeypatch.setenv("SPL_EXTRACT_WALK", "1")
     for window, seq_mode, level, seed in (("3", 1, 1, 41), ("16", 2, 6, 42), ("3", 0, 6, 43)):
         monkeypatch.setenv("SPL_INFLATE_WINDOW_BLOCKS", window)
         names, sets = _random_sets(seed, 30_000, 3)
@@ -289,16 +291,13 @@ def test_windows_in_flight(ctx, tmp_path, monkeypatch, bufs):
         assert _both(path, ctx, names, sets) is True
 
 
-@pytest.mark.parametrize("late", [None, "1"])
-def test_references_complete_before_the_decoder_has_cleared_up(tmp_path, monkeypatch, late):
+def test_references_complete_before_the_decoder_has_cleared_up(tmp_path):
     """`process` counts as soon as the device decoder has made the file's references complete (spl_bam_wait_device), while the
-    decoder's thread still holds its streams, events and lists (and stands aside until the file is closed); SPL_PUBLISH_LATE=1 is
-    the order until round 4.  Either way the .SpliSER.tsv is the host decoder's, and closing the file ends the decoder's thread."""
+    decoder's thread still holds its streams, events and lists (and stands aside until the file is closed).  The .SpliSER.tsv is
+    the host decoder's, and closing the file ends the decoder's thread."""
     import threading
     from spliser_amd import synth
     from spliser_amd.process import process, wait_deferred_close
-    if late:
-        monkeypatch.setenv("SPL_PUBLISH_LATE", late)
     wl = synth.Workload("arabidopsis", scale=0.02, seed=14)
     prefix = str(tmp_path / "p")
     wl.write_inputs(prefix, bam=False)

@@ -4,7 +4,7 @@ every configuration -- a set of environment variables -- a fresh child process t
 library's own stopwatch on (spl_prof_enable) and prints the walls and the kernels' table.  Configurations run interleaved,
 `--rounds` times, so that a box's drift hits them alike.
 
-    tools/ingest_ab.py --scale 0.25 --seq-mode 2 --configs "wave:;lanes:SPL_CRC_LANES=1" --runs 4 --rounds 2
+    tools/ingest_ab.py --scale 0.25 --seq-mode 2 --configs "parent:SPLISER_HIP_LIB=/path/parent.so;new:" --runs 4 --rounds 2
 """
 import argparse
 import json
@@ -36,7 +36,7 @@ if args.child is None:
     os.makedirs(args.files, exist_ok=True)
     if not (os.path.exists(prefix + ".bam") and os.path.exists(prefix + ".n")):
         t = time.perf_counter()
-        wl = synth.Workload(args.workload, scale=args.scale, workers=max(1, min(32, os.cpu_count() or 1)))
+        wl = synth.Workload(args.workload, scale=args.scale, workers=max(1, min(16, os.cpu_count() or 1)))
         synth.write_bed(prefix + ".bed", wl.genome.chrom_names, wl.junctions)
         synth.write_gff(prefix + ".gff", wl.genome)
         native.write_bam(prefix + ".bam", wl.genome.chrom_names, wl.genome.chrom_lengths, wl.reads, level=6 if args.seq_mode == 2 else 1, threads=0, seq_mode=args.seq_mode)
