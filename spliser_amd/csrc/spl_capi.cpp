@@ -3078,7 +3078,12 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     if (err & SPL_DEV_ERR_TABLE) return spl_set_error(SPL_ERR_HIP, "junction table overflow (internal error)");
     std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hk[a] < hk[b]; }); // left, right, strand
+    // left, right, strand -- left as the signed coordinate it is: a read at POS 0 whose CIGAR opens with N has left = -1, whose
+    // key is the largest of all as an unsigned number
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const int32_t la = (int32_t)(hk[a] >> 32), lb = (int32_t)(hk[b] >> 32);
+        return la != lb ? la < lb : (uint32_t)hk[a] < (uint32_t)hk[b];
+    });
     c->junctions.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
         const unsigned long long k = hk[order[i]];
