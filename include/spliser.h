@@ -97,8 +97,8 @@ typedef struct spl_opts {
  * range kernel takes every table, combine's query tables with their one-way partner lists included (its junction table is
  * built from each row's own lists); both give identical counters. */
 #define SPL_OPT_PAIR_KERNEL 1
-/* Variant of the range kernel that merges the LDS atomics of neighbouring lanes before issuing them (same results;
- * measured never faster than the plain atomics the default uses -- kept for parity tests and experiments). */
+/* Selects nothing; defined so that ABI v1 callers that set it still build and run.  A pass with this bit set is the default
+ * pass and gives the same counters, and a read set that stays fused stays fused. */
 #define SPL_OPT_WAVE_AGGREGATION 2
 
 /* ---- library / context ------------------------------------------------------------------------ */
@@ -183,8 +183,8 @@ void spl_reads_free(spl_ctx *ctx, spl_dreads *dr);
  * device leaves (spl_bam_decode_device) and what SURVEY.md 8(d)'s "kernel-only from device-resident SoA" starts from.  A read
  * set is made from them ON THE DEVICE by spl_reads_add_soa + spl_reads_finish.  A set whose segments all lie in ONE such handle
  * stays arrays ("fused"): spl_count_launch reads them itself and makes its records in LDS (spl_kernels.hip, the FUSED range
- * kernel) -- no records in memory, no layout launch; what needs records (the pair kernel, the merging variant,
- * spl_junctions), a set of several handles or with host-packed segments, or SPL_FUSED=0, gets them from the layout kernel
+ * kernel) -- no records in memory, no layout launch; what needs records (the pair kernel, spl_junctions), a set of several
+ * handles or with host-packed segments, or SPL_FUSED=0, gets them from the layout kernel
  * (spl_devpack.hip: one launch, every read fetched and classified once).  spl_reads_relayout does again what spl_reads_finish
  * launched -- the chunks' descriptors and order, and the layout kernel where the set has records -- so that a bench.py step is
  * arrays -> counters, every step.  The handle may be freed while read sets made from it live (they share the arrays). */
@@ -210,8 +210,7 @@ int spl_pack_host(const spl_reads *reads, int n_threads, int64_t *n_chunks_out, 
  * the range kernel of the NEXT launch -- next shard, sample or step -- starts as soon as this one's is done.  The counters
  * start from zero (a clean copy of the counter region; the table keeps three).  spl_sync and the download calls wait for
  * everything; a download returns the results of the LAST pass launched on that table.  Environment, read when the context
- * is created: SPL_TAIL_STREAM=0 -- one stream; SPL_TAIL_HOST_WAIT=1 -- the call blocks while more than two passes are in
- * flight instead of putting a wait into the queue (a few percent faster when the host keeps up, idle GPU when it does not). */
+ * is created: SPL_TAIL_STREAM=0 -- one stream. */
 int spl_count_launch(spl_ctx *ctx, spl_dsites *ds, const spl_dreads *dr, const spl_opts *opts);
 /* Enqueue the beta2/SSE kernel on the counters currently held by ds (asynchronous). */
 int spl_sse_launch(spl_ctx *ctx, spl_dsites *ds, int beta2_cryptic);

@@ -40,14 +40,13 @@ namespace {
 
 // The decoder's threads stay on the NUMA node the calling thread is on: inflated data is written by some threads and walked
 // by others, and on a two-socket host every such hand-over across the sockets goes over the inter-socket link (measured on the
-// MI355X box, 2 x 64 cores: 100 M records in 1.31 s with the threads left to roam, 0.98 s on one node).  SPL_BAM_NO_PIN=1
-// turns it off.  The caller's own affinity is never changed.
+// MI355X box, 2 x 64 cores: 100 M records in 1.31 s with the threads left to roam, 0.98 s on one node).  The caller's
+// own affinity is never changed.
 struct NodeCpus {
     cpu_set_t set;
     bool valid = false;
     NodeCpus()
     {
-        if (getenv("SPL_BAM_NO_PIN")) return;
         const int cpu = sched_getcpu();
         if (cpu < 0) return;
         cpu_set_t allowed;

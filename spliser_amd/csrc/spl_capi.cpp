@@ -309,7 +309,6 @@ struct spl_ctx {
     hipStream_t tail = nullptr;
     hipEvent_t ev_range[4] = {nullptr, nullptr, nullptr, nullptr}, ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_pass = 0;       // counting passes with a tail launched so far
-    bool tail_host_wait = false;
     bool tail_pending = false; // the main stream has not been made to wait for the last tail yet
     int32_t *d_err = nullptr;               // error word of launches that are not counting passes (spl_junctions)
     // Read sets reach the device through a ring of page-locked staging buffers: the host packer (spl_pack.h) writes a piece of
@@ -329,7 +328,7 @@ struct spl_ctx {
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
     double tm_plan_s = 0, tm_emit_s = 0, tm_copy_ms = 0;
     size_t tm_bytes = 0, tm_pieces = 0;
-    int last_grid = 0, last_lds = 0, last_variant = 0;
+    int last_grid = 0, last_lds = 0;
     struct Junction { int32_t left, right; uint8_t strand; uint32_t count, anchor_left, anchor_right; };
     std::vector<Junction> junctions; // result of the last spl_junctions call, sorted
     // optional per-launch stopwatch around spl_count_kernel alone (bench.py's roofline numerator)
@@ -484,8 +483,6 @@ static int create_ctx(int device_id, void *stream, bool use_given, spl_ctx **out
         c->own_stream = true;
     }
     {
-        const char *hw = getenv("SPL_TAIL_HOST_WAIT");
-        c->tail_host_wait = hw && hw[0] == '1';
         const char *want_tail = getenv("SPL_TAIL_STREAM");
         if (!(want_tail && want_tail[0] == '0')) {
             bool ok = hipStreamCreateWithFlags(&c->tail, hipStreamNonBlocking) == hipSuccess;
@@ -965,7 +962,7 @@ static size_t stage_bytes_of(size_t mb) { const size_t huge = 2u << 20; return (
 
 // n_new page-locked staging buffers of `bytes` for `device`, made side by side, a thread each: touching 32 MiB and locking it is
 // 3-8 ms of a new process's first call, six of them one behind the other were 15-50 ms before the file's first byte was on its way
-static void make_stage_buffers(int device, size_t bytes, bool want_lock, std::vector<spl_ctx::Stage> &made, std::vector<int> &why)
+static void make_stage_buffers(int device, size_t bytes, std::vector<spl_ctx::Stage> &made, std::vector<int> &why)
 {
     const size_t huge = 2u << 20;
     const int n_new = (int)made.size();
@@ -978,7 +975,7 @@ static void make_stage_buffers(int device, size_t bytes, bool want_lock, std::ve
         memset(p, 0, bytes); // touch: the pages exist before they are locked
         st.host = (char *)p;
         st.bytes = bytes;
-        st.locked = want_lock && hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess; // (pageable works too, slower)
+        st.locked = hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess; // (pageable works too, slower)
         if (hipEventCreateWithFlags(&st.done, hipEventDisableTiming) != hipSuccess) {
             if (st.locked) (void)hipHostUnregister(p);
             free(p);
@@ -997,12 +994,11 @@ static void make_stage_buffers(int device, size_t bytes, bool want_lock, std::ve
 static int grow_stage(spl_ctx *c, int n)
 {
     const size_t bytes = stage_bytes_of(c->stage_mb);
-    const bool want_lock = !(getenv("SPL_STAGE_PAGEABLE"));
     {   // buffers a destroyed context of this process left behind (same device, same size): page-locking 96 MiB anew costs 12 ms
         std::lock_guard<std::mutex> lock(stage_pool_mu());
         std::vector<PooledStage> &pool = stage_pool();
         for (size_t k = pool.size(); k-- > 0 && (int)c->stage.size() < n;) {
-            if (pool[k].device != c->device || pool[k].st.bytes != bytes || pool[k].st.locked != want_lock) continue;
+            if (pool[k].device != c->device || pool[k].st.bytes != bytes || !pool[k].st.locked) continue;
             c->stage.push_back(pool[k].st);
             pool.erase(pool.begin() + (long)k);
         }
@@ -1011,7 +1007,7 @@ static int grow_stage(spl_ctx *c, int n)
     if (n_new <= 0) return SPL_OK;
     std::vector<spl_ctx::Stage> made((size_t)n_new);
     std::vector<int> why((size_t)n_new, SPL_OK);
-    make_stage_buffers(c->device, bytes, want_lock, made, why);
+    make_stage_buffers(c->device, bytes, made, why);
     int rc = SPL_OK;
     for (int k = 0; k < n_new; ++k) {
         if (why[(size_t)k] == SPL_OK) { c->stage.push_back(made[(size_t)k]); continue; }
@@ -2542,8 +2538,6 @@ static int64_t max_end_of(const spl_reads *r)
     return best;
 }
 
-static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceReads **out, const int64_t *max_end = nullptr);
-
 extern "C" int spl_reads_add(spl_ctx *c, spl_dreads *d, const spl_reads *reads, int32_t pos_shift) { return spl_reads_add2(c, d, reads, pos_shift, -1); }
 
 // ... known_max_end: the last base (1-based) any of the reads covers, where the caller knows it (< 0: looked for here when the
@@ -2556,20 +2550,8 @@ extern "C" int spl_reads_add2(spl_ctx *c, spl_dreads *d, const spl_reads *reads,
     int64_t max_end;
     int rc = source_of(reads, src, &max_end, "spl_reads_add");
     if (rc) return rc;
-    // SPL_RAW_UPLOAD=1 (A/B): the arrays go up as they are and the layout kernel makes the records (spl_devpack.hip), as for a BAM
-    // decoded on the device.  Not the default: a hand-over is bound by what crosses PCIe and by the copies into the staging
-    // buffers, and the records the host's threads pack on the way are two thirds of the arrays' bytes (20 M reads: 13.7 ms
-    // packed against 18.6 ms as they are, one box, profiles/r05R_pcie_rate.txt).
-    static const bool raw_upload = getenv("SPL_RAW_UPLOAD") != nullptr;
-    if (raw_upload && reads->n_reads >= 4096) {
-        DeviceReads *dev = nullptr;
-        const int64_t no_end = 0;
-        rc = upload_native(c, 1, reads, &dev, pos_shift == 0 ? &no_end : (known_max_end >= 0 ? &known_max_end : nullptr));
-        if (rc) return rc;
-        rc = add_segment_device(c, d, dev, 0, dev->n_rec, dev->n_ops, pos_shift, pos_shift != 0 ? dev->ref_max[0] : -1);
-        free_device_reads(dev); // (the read set holds them now)
-        return rc;
-    }
+    // (Measured and not kept: the arrays going up as they are, for the layout kernel to make the records -- the packed records are
+    //  two thirds of the arrays' bytes: 20 M reads, 13.7 ms packed against 18.6 ms as they are, profiles/r05R_pcie_rate.txt.)
     if (pos_shift != 0) max_end = known_max_end >= 0 ? known_max_end : max_end_of(reads);
     return add_segment(c, d, src, pos_shift, max_end);
 }
@@ -2848,18 +2830,16 @@ extern "C" int spl_count_launch(spl_ctx *c, spl_dsites *ds, const spl_dreads *dr
     // counters, difference arrays, error word and queue counters start from zero: the copy the previous pass cleared on the
     // side, or -- first pass after a pair-kernel pass -- one clearing launch
     // range kernel whenever the table allows it; the literal pair kernel otherwise or on request
-    const int variant = (o->flags & SPL_OPT_PAIR_KERNEL) ? 1 : ((o->flags & SPL_OPT_WAVE_AGGREGATION) ? 2 : 0);
-    const bool piped = c->tail != nullptr && variant != 1 && ds->region_clean[(ds->cur + 1) % 3];
+    // (SPL_OPT_WAVE_AGGREGATION selects nothing: such a pass is the default one)
+    const bool pairs = (o->flags & SPL_OPT_PAIR_KERNEL) != 0;
+    const bool piped = c->tail != nullptr && !pairs && ds->region_clean[(ds->cur + 1) % 3];
     if (piped) {
         // the tail of the pass before the last one is the last thing that read the queue buffer and wrote the counter copy
         // this pass takes (tails run in order on their stream): a wait that is over long before it is asked for
-        // The wait packet in the main queue costs 6 us between two range kernels.  SPL_TAIL_HOST_WAIT=1: the HOST waits
-        // instead (the call then blocks while more than two passes are in flight) -- 4 % faster in bench.py, and one
-        // millisecond of host jitter is one millisecond of idle GPU (1 run in 12 lost 25 % that way): not the default.
-        if (c->n_pass >= 2) {
-            if (c->tail_host_wait) HIP_TRY(hipEventSynchronize(c->ev_tail[(c->n_pass - 2) % 4]));
-            else HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_tail[(c->n_pass - 2) % 4], 0));
-        }
+        // The wait packet in the main queue costs 6 us between two range kernels.  (Measured and not kept: the HOST waiting
+        // instead -- 4 % faster in bench.py, but one millisecond of host jitter is one millisecond of idle GPU: 1 run in 12
+        // lost 25 % that way.)
+        if (c->n_pass >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_tail[(c->n_pass - 2) % 4], 0));
     } else
         HIP_TRY(join_tail(c)); // (pair kernel, first pass after one, or one stream: everything in order on the main stream)
     const int next = (ds->cur + 1) % 3;
@@ -2869,7 +2849,7 @@ extern "C" int spl_count_launch(spl_ctx *c, spl_dsites *ds, const spl_dreads *dr
     } else if (int rc0 = spl_dev_launch_clear(ds->beta1, ds->counter_bytes, c->stream)) // (in place: the copy in use)
         return spl_set_error(SPL_ERR_HIP, "clear kernel launch: %s", hipGetErrorString((hipError_t)rc0));
     if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_count_launch: the read set is not finished (spl_reads_finish)");
-    if (dr->fused && variant != 0) { const int rc0 = unfuse(c, const_cast<spl_dreads *>(dr)); if (rc0) return rc0; } // (the pair kernel and the merging variant read records)
+    if (dr->fused && pairs) { const int rc0 = unfuse(c, const_cast<spl_dreads *>(dr)); if (rc0) return rc0; } // (the pair kernel reads records)
     uint32_t *const queue = dr->queue_turn ? dr->queue_alt : dr->queue;
     dr->queue_turn ^= 1;
     dr->queued_pass = false;
@@ -2912,13 +2892,12 @@ extern "C" int spl_count_launch(spl_ctx *c, spl_dsites *ds, const spl_dreads *dr
     int64_t alg = 0;
     if (splprof::g_on.load(std::memory_order_relaxed)) (void)spl_count_algorithmic_bytes(ds, dr, &alg);
     int rc;
-    { splprof::Scope prof("spl_count_ranges_kernel", c->stream, (double)alg); rc = spl_dev_launch_count(&p, &h, variant, c->stream, &grid, &lds, timed ? (void *)c->k_ev[2 * c->k_used] : nullptr, (void *)ev_stop); }
+    { splprof::Scope prof("spl_count_ranges_kernel", c->stream, (double)alg); rc = spl_dev_launch_count(&p, &h, pairs, c->stream, &grid, &lds, timed ? (void *)c->k_ev[2 * c->k_used] : nullptr, (void *)ev_stop); }
     if (timed) c->k_used++;
     c->last_grid = grid;
     c->last_lds = lds;
-    c->last_variant = variant;
     if (rc != 0) return spl_set_error(SPL_ERR_HIP, "count kernel launch: %s", hipGetErrorString((hipError_t)rc));
-    if (variant != 1 && grid > 0) { // queued reads through the literal kernel, then difference arrays -> counters
+    if (!pairs && grid > 0) { // queued reads through the literal kernel, then difference arrays -> counters
         hipStream_t ts = c->stream;
         if (piped) {
             HIP_TRY(hipStreamWaitEvent(c->tail, ev_stop, 0));

@@ -443,48 +443,26 @@ __device__ __forceinline__ void dbk_resolve(const P &p, int32_t x, const spl_dbk
 
 typedef __attribute__((address_space(3))) int32_t spl_lds_i32; // the difference windows, typed as what they are: LDS
 
-// All 64 lanes call this together.  Lanes that add `sign` to the same key = (dpos << 2 | array) and sit next to each
-// other form a run; the first lane of each run adds sign * run-length once.  (Equal keys that are NOT adjacent make
-// several runs: still correct, just more atomics -- that only happens for unsorted input.)
-template <int NARR, bool AGG, int WIN = (NARR == 4 ? SPL_WIN_STRANDED : SPL_WIN)>
+// One +-sign at key = (dpos << 2 | array): an LDS add when dpos lies in the workgroup's window, a global atomic otherwise.
+template <int NARR, int WIN = (NARR == 4 ? SPL_WIN_STRANDED : SPL_WIN)>
 __device__ __forceinline__ void commit_key(const spl_hot_params &p, spl_lds_i32 *lds, int32_t wbase, bool valid, uint32_t key, int32_t sign)
 {
-    int32_t amount = sign;
-    bool go = valid;
-    if (AGG) {
-        const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const uint32_t k = valid ? key : 0xffffffffu;
-        // previous lane's key by a DPP wave shift (no LDS round trip); lane 0 keeps its own and is a head anyway
-        const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)k, (int)k, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-        const bool head = valid && (lane == 0 || prev != k);
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long act = __ballot(valid);
-        const unsigned long long stop = (heads | ~act) & ~((2ull << lane) - 1ull); // later lanes that end my run
-        const int len = stop ? (__ffsll((long long)stop) - 1 - lane) : (64 - lane);
-        amount = sign * len;
-        go = head;
-    }
-    if (go) {
+    if (valid) {
         const int arr = (int)(key & 3u);
         const int32_t d = (int32_t)(key >> 2);
         const uint32_t loc = (uint32_t)(d - wbase);
         // (an LDS-typed pointer: ds_add on one side, a global atomic on the other, never a flat atomic on a selected address)
-        if (loc <= (uint32_t)WIN) __hip_atomic_fetch_add(lds + (arr * (WIN + 1) + (int)loc), amount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        else atomicAdd(&p.diff[(int64_t)arr * p.diff_stride + d], amount);
+        if (loc <= (uint32_t)WIN) __hip_atomic_fetch_add(lds + (arr * (WIN + 1) + (int)loc), sign, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else atomicAdd(&p.diff[(int64_t)arr * p.diff_stride + d], sign);
     }
 }
 
 // A range of distinct positions [lo, ub) of difference array `arr`: +1 at lo, -1 at ub -- the two commit_keys of every range, with
 // what they share done once: both ends inside the workgroup's window (nearly always: the window is the chunk's) are two LDS adds
 // behind ONE test; anything else takes the two separate ways.  All 64 lanes call this together.
-template <int NARR, bool AGG, int WIN>
+template <int NARR, int WIN>
 __device__ __forceinline__ void commit_range(const spl_hot_params &p, spl_lds_i32 *lds, int32_t wbase, bool em, int32_t lo, int32_t ub, uint32_t arr)
 {
-    if (AGG) {
-        commit_key<NARR, AGG, WIN>(p, lds, wbase, em, ((uint32_t)lo << 2) | arr, 1);
-        commit_key<NARR, AGG, WIN>(p, lds, wbase, em, ((uint32_t)ub << 2) | arr, -1);
-        return;
-    }
     const uint32_t a = (uint32_t)(lo - wbase), b = (uint32_t)(ub - wbase);
     const bool inside = a <= (uint32_t)WIN && b <= (uint32_t)WIN;
     if (em && inside) {
@@ -493,8 +471,8 @@ __device__ __forceinline__ void commit_range(const spl_hot_params &p, spl_lds_i3
         __hip_atomic_fetch_add(row + (int)b, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (__any(em && !inside)) {
-        commit_key<NARR, false, WIN>(p, lds, wbase, em && !inside, ((uint32_t)lo << 2) | arr, 1);
-        commit_key<NARR, false, WIN>(p, lds, wbase, em && !inside, ((uint32_t)ub << 2) | arr, -1);
+        commit_key<NARR, WIN>(p, lds, wbase, em && !inside, ((uint32_t)lo << 2) | arr, 1);
+        commit_key<NARR, WIN>(p, lds, wbase, em && !inside, ((uint32_t)ub << 2) | arr, -1);
     }
 }
 
@@ -565,17 +543,17 @@ __device__ __forceinline__ bool rivals_inline_from(const spl_hot_params &p, spl_
         if (STRANDED && ((rv.y >> 30) != (sidx ? 2u : 1u))) continue; // strand_ok false: the ranges added nothing
         const uint32_t a_b1 = sidx, a_me = (STRANDED ? 2u : 1u) + sidx;
         if (t > l && t < r) { // flanking: not counted by `process` (:529-536)
-            commit_key<NARR, false, WIN>(p, lds, wbase, true, (td << 2) | a_me, -1);
-            commit_key<NARR, false, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, 1);
+            commit_key<NARR, WIN>(p, lds, wbase, true, (td << 2) | a_me, -1);
+            commit_key<NARR, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, 1);
         } else {
             bool cov = false;
 #pragma unroll
             for (int j = 0; j < 2; ++j) cov |= (blk_a[j] <= t) && (t + 1 <= blk_b[j]);
             if (cov) { // beta1-type (:544-556)
-                commit_key<NARR, false, WIN>(p, lds, wbase, true, (td << 2) | a_b1, -1);
-                commit_key<NARR, false, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_b1, 1);
-                commit_key<NARR, false, WIN>(p, lds, wbase, true, (td << 2) | a_me, 1);
-                commit_key<NARR, false, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, -1);
+                commit_key<NARR, WIN>(p, lds, wbase, true, (td << 2) | a_b1, -1);
+                commit_key<NARR, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_b1, 1);
+                commit_key<NARR, WIN>(p, lds, wbase, true, (td << 2) | a_me, 1);
+                commit_key<NARR, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, -1);
                 if (rv.z != 0xffffffffu) agg_add(&p.dbl[rv.z & 0x7fffffffu], 1);
                 if (rv.w != 0xffffffffu) agg_add(&p.dbl[rv.w], 1);
             }
@@ -665,14 +643,14 @@ __device__ __forceinline__ bool rivals_inline2(const spl_hot_params &p, spl_lds_
                     if (is_end && !(alpha && pp == pu)) agg_add(&p.dbl[rx.y + e2], 1);
                 }
                 if (beta1type) {
-                    commit_key<NARR, false, WIN>(p, lds, wbase, true, (td << 2) | a_b1, -1);
-                    commit_key<NARR, false, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_b1, 1);
-                    commit_key<NARR, false, WIN>(p, lds, wbase, true, (td << 2) | a_me, 1);
-                    commit_key<NARR, false, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, -1);
+                    commit_key<NARR, WIN>(p, lds, wbase, true, (td << 2) | a_b1, -1);
+                    commit_key<NARR, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_b1, 1);
+                    commit_key<NARR, WIN>(p, lds, wbase, true, (td << 2) | a_me, 1);
+                    commit_key<NARR, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, -1);
                 }
             } else if (inside >= j && strand_ok) { // flanking: the ME range counted it, `process` does not
-                commit_key<NARR, false, WIN>(p, lds, wbase, true, (td << 2) | a_me, -1);
-                commit_key<NARR, false, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, 1);
+                commit_key<NARR, WIN>(p, lds, wbase, true, (td << 2) | a_me, -1);
+                commit_key<NARR, WIN>(p, lds, wbase, true, ((td + 1u) << 2) | a_me, 1);
             }
         }
     }
@@ -706,12 +684,13 @@ __device__ __forceinline__ bool rivals_inline2(const spl_hot_params &p, spl_lds_
 // Measured (human-scale, 100 M reads a launch): 0.94-0.98 ms against 0.655-0.67 + 0.375-0.39 for layout + range.  Asking for the next
 // tile's reads before this tile is counted gained nothing (a wave's memory operations return in order: the first bucket entry
 // waits for them), 512 threads -- two reads each, eight waves counting a tile -- took 1.25 ms: profiles/r05X_fused_pass.txt.
-// Default (AGG false): plain LDS atomics, 64 VGPRs = 8 waves per SIMD (the kernel lives on how many waves are there to
-// cover each other's memory trips and barriers; the register cap costs nothing -- no scratch).  Merging the atomics of
-// neighbouring lanes first (AGG, SPL_OPT_WAVE_AGGREGATION) needs a few more registers than that cap allows and was
-// never faster in measurements, not even at 8000 reads per site; it stays as a variant for parity tests.
-template <bool STRANDED, bool AGG, bool BIG, bool FUSED>
-__global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__((amdgpu_waves_per_eu(FUSED || AGG ? 4 : 8, 8))) void spl_count_ranges_kernel(const spl_hot_params p)
+// Plain LDS atomics, 64 VGPRs = 8 waves per SIMD (the kernel lives on how many waves are there to cover each other's memory
+// trips and barriers; the register cap costs nothing -- no scratch).
+// Measured and not kept: merging the atomics of neighbouring lanes into one per run of equal keys before issuing them (a DPP
+// shift and two ballots per key) needs a few more registers than that cap allows and was never faster, not even at 8000
+// reads per site: profiles/r02g_lds_conflicts_*.txt.
+template <bool STRANDED, bool BIG, bool FUSED>
+__global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__((amdgpu_waves_per_eu(FUSED ? 4 : 8, 8))) void spl_count_ranges_kernel(const spl_hot_params p)
 {
     constexpr int NARR = STRANDED ? 4 : 2; // {beta1, ME} x {read strand +, -}
     constexpr int WIN = STRANDED ? (FUSED ? SPL_WIN_STRANDED_FUSED : SPL_WIN_STRANDED) : SPL_WIN;
@@ -920,7 +899,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         // retire in order, and the entries must not wait for the stream), in straight-line code: one place per loop body, so
         // that no pass of the compiler finds common code to move to the end of the iteration.
         // Straight-line up to the commits: lanes past the end of a run are masked, all loads of a trip issue back to
-        // back.  Control flow is wave-uniform around every commit_key (all 64 lanes reach it).
+        // back.  Control flow is wave-uniform around every commit_range (all 64 lanes reach its __any).
         uint32_t g = live ? wave : g_start[SPL_RC_RUNS]; // (a workgroup without a chunk has chunk 0's descriptor and no iteration at all)
         auto fetch_next = [&]() { if constexpr (!FUSED) fetch(g + NWAVE < g_total ? g + NWAVE : g); }; // (the last iteration asks for itself again)
         // FUSED: the records are in LDS -- nothing to ask for ahead: an iteration reads its own at its top, its run known
@@ -965,7 +944,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
                 const bool emit = i0 + j < n_run && ub > lo;
                 uint32_t arr = 0;
                 if (STRANDED) arr = (spl_read_strand(w[2 * j + 1] & 0xffffu, p.stranded) == (uint8_t)'-') ? 1u : 0u;
-                if (__any(emit)) commit_range<NARR, AGG, WIN>(p, lds, wbase, emit, lo, ub, arr);
+                if (__any(emit)) commit_range<NARR, WIN>(p, lds, wbase, emit, lo, ub, arr);
             }
         }
         // ---- once-spliced reads (aligned, N, aligned): the kinds are known, so are the arrays; three ranges
@@ -998,7 +977,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
                 auto range = [&](uint32_t arr) {
                     const int32_t lo = ua + (int32_t)nva;
                     const bool em = alive && ub > lo;
-                    if (__any(em)) commit_range<NARR, AGG, WIN>(p, lds, wbase, em, lo, ub, arr);
+                    if (__any(em)) commit_range<NARR, WIN>(p, lds, wbase, em, lo, ub, arr);
                     ua = ub; nva = nvb;
                 };
                 dbk_resolve(p, pos[j] - 1, ea[j], ua, nva);
@@ -1043,7 +1022,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
             auto range = [&](uint32_t arr) {
                 const int32_t lo = ua + (int32_t)nva;
                 const bool em = alive && ub > lo;
-                if (__any(em)) commit_range<NARR, AGG, WIN>(p, lds, wbase, em, lo, ub, arr);
+                if (__any(em)) commit_range<NARR, WIN>(p, lds, wbase, em, lo, ub, arr);
                 ua = ub; nva = nvb;
             };
             dbk_resolve(p, pos - 1, f0, ua, nva);
@@ -1129,7 +1108,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
                     const uint32_t arr = (kk == 2u ? (STRANDED ? 2u : 1u) : 0u) + sidx;
                     // junction ends: lSite is the previous boundary's position, rSite this one's
                     rival |= (kk == 2u) & ((prv | rv) != 0u);
-                    if (__any(emit)) commit_range<NARR, AGG, WIN>(p, lds, wbase, emit, lo, u, arr);
+                    if (__any(emit)) commit_range<NARR, WIN>(p, lds, wbase, emit, lo, u, arr);
                     if (kk) { pu = u; pnv = nv; prv = rv; }
                 }
                 const bool more = alive && wide && k_next < n_ops;
@@ -1832,7 +1811,7 @@ extern "C" int spl_dev_launch_clear(void *region, size_t bytes, void *stream)
 
 // ev_start / ev_stop (may be null): HIP events that take the kernel's own start and end time -- through hipExtLaunchKernelGGL,
 // i.e. without marker packets of their own in the queue (two hipEventRecord calls around a launch cost the step 3 us).
-extern "C" int spl_dev_launch_count(const spl_count_params *p, const spl_hot_params *h, int variant, void *stream, int *grid_out, int *lds_out,
+extern "C" int spl_dev_launch_count(const spl_count_params *p, const spl_hot_params *h, int pairs, void *stream, int *grid_out, int *lds_out,
                                     void *ev_start, void *ev_stop)
 {
     *grid_out = 0;
@@ -1840,33 +1819,29 @@ extern "C" int spl_dev_launch_count(const spl_count_params *p, const spl_hot_par
     if (p->n_reads <= 0 || p->n_sites <= 0) return 0;
     // grid = 8 * ceil(n_chunks / 8) so that every XCD's share has the same number of slots; the range kernel's slots are the
     // chunk order's (spl_chunk_order_kernel: whole blocks of 8 chunks per share, so a few more)
-    const uint32_t slots = variant == 1 ? ((p->n_chunks + 7u) / 8u) * 8u : h->n_chunks;
+    const uint32_t slots = pairs ? ((p->n_chunks + 7u) / 8u) * 8u : h->n_chunks;
     const uint32_t grid = slots;
     *grid_out = (int)grid;
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0 = (hipEvent_t)ev_start, e1 = (hipEvent_t)ev_stop;
-    if (variant == 1) {
+    if (pairs) {
         *lds_out = 2 * SPL_WIN * 4 + SPL_BLOCK * 5 * 4 + 4;
         if (p->stranded) hipExtLaunchKernelGGL(spl_count_pairs_kernel<true>, dim3(grid), dim3(SPL_BLOCK), 0, st, e0, e1, 0, *p);
         else hipExtLaunchKernelGGL(spl_count_pairs_kernel<false>, dim3(grid), dim3(SPL_BLOCK), 0, st, e0, e1, 0, *p);
     } else {
         const bool big = h->chunk_shift == SPL_CHUNK_BIG_SHIFT;
         *lds_out = (p->stranded ? 4 * ((h->cells ? SPL_WIN_STRANDED_FUSED : SPL_WIN_STRANDED) + 1) : 2 * (SPL_WIN + 1)) * 4 + SPL_WAVES * SPL_WAVE_READS * 2 + 4 * SPL_WAVES + 4; // difference windows + the waves' lists
-        const bool agg = (variant & 2) != 0;
-#define SPL_LAUNCH_RANGES(S, A, B) hipExtLaunchKernelGGL((spl_count_ranges_kernel<S, A, B, false>), dim3(grid), dim3(SPL_BLOCK), 0, st, e0, e1, 0, *h)
+#define SPL_LAUNCH_RANGES(S, B) hipExtLaunchKernelGGL((spl_count_ranges_kernel<S, B, false>), dim3(grid), dim3(SPL_BLOCK), 0, st, e0, e1, 0, *h)
         if (h->cells) { // the fused pass: straight from the BAM-native arrays
-            if (agg) return (int)hipErrorInvalidValue;
             *lds_out += (int)SPL_LAYOUT_SLOT(SPL_TILE_FUSED) + 2 * SPL_TILE_FUSED + (SPL_BLOCK_FUSED / 64) * SPL_WAVE_READS_FUSED * 2 - SPL_WAVES * SPL_WAVE_READS * 2;
-#define SPL_LAUNCH_FUSED(S, B) hipExtLaunchKernelGGL((spl_count_ranges_kernel<S, false, B, true>), dim3(grid), dim3(SPL_BLOCK_FUSED), 0, st, e0, e1, 0, *h)
+#define SPL_LAUNCH_FUSED(S, B) hipExtLaunchKernelGGL((spl_count_ranges_kernel<S, B, true>), dim3(grid), dim3(SPL_BLOCK_FUSED), 0, st, e0, e1, 0, *h)
             if (p->stranded) { if (big) SPL_LAUNCH_FUSED(true, true); else SPL_LAUNCH_FUSED(true, false); }
             else { if (big) SPL_LAUNCH_FUSED(false, true); else SPL_LAUNCH_FUSED(false, false); }
 #undef SPL_LAUNCH_FUSED
         } else if (p->stranded) {
-            if (agg) { if (big) SPL_LAUNCH_RANGES(true, true, true); else SPL_LAUNCH_RANGES(true, true, false); }
-            else { if (big) SPL_LAUNCH_RANGES(true, false, true); else SPL_LAUNCH_RANGES(true, false, false); }
+            if (big) SPL_LAUNCH_RANGES(true, true); else SPL_LAUNCH_RANGES(true, false);
         } else {
-            if (agg) { if (big) SPL_LAUNCH_RANGES(false, true, true); else SPL_LAUNCH_RANGES(false, true, false); }
-            else { if (big) SPL_LAUNCH_RANGES(false, false, true); else SPL_LAUNCH_RANGES(false, false, false); }
+            if (big) SPL_LAUNCH_RANGES(false, true); else SPL_LAUNCH_RANGES(false, false);
         }
 #undef SPL_LAUNCH_RANGES
     }

@@ -41,7 +41,7 @@ class spl_opts(ctypes.Structure):
 
 
 OPT_PAIR_KERNEL = 1
-OPT_WAVE_AGGREGATION = 2
+OPT_WAVE_AGGREGATION = 2   # (selects nothing: such a pass is the default one; kept for callers of ABI v1)
 
 
 EXPORTS = [

@@ -16,7 +16,6 @@ alpha / Partners / Competitors columns and the Gene column, so it follows the re
 (including the ones that look accidental) exactly.
 """
 import bisect
-import os
 
 import numpy as np
 
@@ -353,7 +352,7 @@ class SiteTable(object):
     def _keep_as_the_reference_does(self, chrom):
         """From here on this chromosome's sites live in a list in the reference's order (so far: ascending position, '+' before
         '-': what the groups hold)."""
-        if chrom in self._exact or os.environ.get("SPL_SITES_FIRST_AT_POSITION"):   # (the switch: round 4's look-ups, for tools/fuzz_reference.py's comparison)
+        if chrom in self._exact:
             return
         by_pos = self._by_pos[chrom]
         arr = []

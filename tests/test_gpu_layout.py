@@ -269,9 +269,10 @@ def test_two_read_sets_laid_out_again_and_counted_in_turn(ctx, oracle_lib):
             dr.free(); soa.free(); ds.free()
 
 
-def test_a_fused_read_set_is_laid_out_when_a_pass_needs_records(ctx, oracle_lib):
-    """A read set finished fused has no records in memory (spl_reads_layout_bytes: 0 written).  The pair kernel and spl_junctions
-    read records: the set is laid out then, once, and counts the same before and after."""
+def test_a_fused_read_set_is_laid_out_only_when_a_pass_needs_records(ctx, oracle_lib):
+    """A read set finished fused has no records in memory (spl_reads_layout_bytes: 0 written).  A pass with
+    SPL_OPT_WAVE_AGGREGATION is the default pass and leaves it fused; the pair kernel and spl_junctions read records: the set is
+    laid out then, once, and counts the same before and after."""
     arr, rs = randcase.make_case(936, False)
     big = _repeat(rs, 97)
     ocount, _ = helpers.oracle_engine(oracle_lib)
@@ -289,7 +290,11 @@ def test_a_fused_read_set_is_laid_out_when_a_pass_needs_records(ctx, oracle_lib)
             for w, g in zip(want_fr, ds.counters()):
                 assert np.array_equal(w, g)
             assert dr.layout_bytes()[1] == 0                      # (still fused)
-            ctx.count_launch(ds, dr, 0, 0, native.OPT_WAVE_AGGREGATION)   # the merging variant reads records
+            ctx.count_launch(ds, dr, 0, 0, native.OPT_WAVE_AGGREGATION)   # (selects nothing: the default pass, still fused)
+            for w, g in zip(want, ds.counters()):
+                assert np.array_equal(w, g)
+            assert dr.layout_bytes()[1] == 0
+            ctx.count_launch(ds, dr, 0, 0, native.OPT_PAIR_KERNEL)   # the pair kernel reads records
             for w, g in zip(want, ds.counters()):
                 assert np.array_equal(w, g)
             assert dr.layout_bytes()[1] > 0                       # (records in memory now)

@@ -19,6 +19,7 @@ def ctx():
     c.close()
 
 
+# (ranges_agg: SPL_OPT_WAVE_AGGREGATION selects nothing -- ABI v1 callers that set it must get the default pass and its counters)
 KERNELS = {"ranges": 0, "pairs": native.OPT_PAIR_KERNEL, "ranges_agg": native.OPT_WAVE_AGGREGATION}
 
 
@@ -151,8 +152,8 @@ def test_gpu_back_to_back_passes_on_one_table(ctx, tmp_path, oracle_lib):
         for combine in (0, 1):
             want[(stranded, combine)] = oracle_lib.check_bam(arr.pos, arr.strand, arr.part_off, arr.part_pos, arr.comp_off, arr.comp_pos,
                                                              reads.pos, reads.flag, reads.cig_off, reads.cigar, stranded, combine)
-    sequence = [(0, 0, "ranges"), (1, 0, "ranges"), (1, 0, "pairs"), (0, 0, "ranges"), (2, 1, "ranges"), (2, 1, "ranges_agg"),
-                (0, 1, "pairs"), (0, 1, "pairs"), (1, 1, "ranges"), (0, 0, "ranges_agg"), (0, 0, "ranges")]
+    sequence = [(0, 0, "ranges"), (1, 0, "ranges"), (1, 0, "pairs"), (0, 0, "ranges"), (2, 1, "ranges"), (2, 1, "ranges"),
+                (0, 1, "pairs"), (0, 1, "pairs"), (1, 1, "ranges"), (0, 0, "ranges"), (0, 0, "ranges")]
     for stranded, combine, kernel in sequence:
         ctx.count_launch(ds, dr, stranded, combine, KERNELS[kernel])
         for g, w in zip(ds.counters(), want[(stranded, combine)]):
@@ -170,14 +171,13 @@ def test_gpu_back_to_back_passes_on_one_table(ctx, tmp_path, oracle_lib):
     ds.free()
 
 
-@pytest.mark.parametrize("tail_stream", ["1", "0", "host-wait"])
+@pytest.mark.parametrize("tail_stream", ["1", "0"])
 def test_gpu_tail_stream_pipelined_passes(tmp_path, oracle_lib, monkeypatch, tail_stream):
     """The literal kernel and the scan of a pass run on a stream of their own while the next pass's range kernel is under way
     (three counter copies per table, two queue buffers per read set; SPL_TAIL_STREAM=0: everything on one stream).  Passes
     launched back to back without a download in between, on two tables and read sets taking turns, with changing modes and
     kernels: whatever is downloaded, whenever, must be the oracle's result for the last pass on that table."""
-    monkeypatch.setenv("SPL_TAIL_STREAM", "0" if tail_stream == "0" else "1")
-    monkeypatch.setenv("SPL_TAIL_HOST_WAIT", "1" if tail_stream == "host-wait" else "0")  # (who waits for the tail two passes back)
+    monkeypatch.setenv("SPL_TAIL_STREAM", tail_stream)
     wl = synth.Workload("arabidopsis", scale=0.004, seed=43)
     table = _table_for(wl, tmp_path, True)
     with native.Context(0) as piped:
@@ -210,7 +210,7 @@ def test_gpu_tail_stream_pipelined_passes(tmp_path, oracle_lib, monkeypatch, tai
         # the other kernels in between (they run on the main stream alone), the tables and read sets crossed over
         piped.count_launch(dev[0][0], dev[0][1], 1, 0, KERNELS["pairs"])
         piped.count_launch(dev[1][0], dev[1][1], 1, 0, 0)
-        piped.count_launch(dev[0][0], dev[0][1], 2, 0, KERNELS["ranges_agg"])
+        piped.count_launch(dev[0][0], dev[0][1], 2, 0, 0)
         piped.count_launch(dev[1][0], dev[1][1], 2, 0, 0)
         check(0, 2, 0, False)
         check(1, 2, 0, True)

@@ -35,10 +35,10 @@ def test_host_core_matches_oracle_on_random_cases(stranded, odd, oracle_lib):
 @pytest.mark.gpu
 @pytest.mark.parametrize("odd", [False, True])
 @pytest.mark.parametrize("stranded", [0, 1, 2])
-@pytest.mark.parametrize("kernel", ["ranges", "pairs", "ranges_agg"])
+@pytest.mark.parametrize("kernel", ["ranges", "pairs"])
 def test_gpu_matches_oracle_on_random_cases(stranded, kernel, odd, oracle_lib):
     from spliser_amd import native
-    flags = {"ranges": 0, "pairs": native.OPT_PAIR_KERNEL, "ranges_agg": native.OPT_WAVE_AGGREGATION}[kernel]
+    flags = {"ranges": 0, "pairs": native.OPT_PAIR_KERNEL}[kernel]
     with native.Context(0) as ctx:
         for seed in SEEDS:
             arr, rs = randcase.make_case(seed, bool(stranded), odd=odd)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Parity fuzzing on the GPU box: tests/randcase.py cases beyond the seeds the test suite pins, each read also repeated 70
-times (so that whole waves of every odd shape occur, not only mixed ones), range kernel (+ the aggregating variant now and
-then) against the oracle, all strand / combine modes, fused SSE included.   tools/fuzz_parity.py FIRST LAST"""
+times (so that whole waves of every odd shape occur, not only mixed ones), range kernel against the oracle, all strand /
+combine modes, fused SSE included.   tools/fuzz_parity.py FIRST LAST"""
 import os
 import sys
 import time
@@ -45,20 +45,19 @@ with native.Context(0) as ctx:
                 for combine in (0, 1):
                     want = oracle.check_bam(arr.pos, arr.strand, arr.part_off, arr.part_pos, arr.comp_off, arr.comp_pos, reads.pos,
                                             reads.flag, reads.cig_off, reads.cigar, stranded, combine)
-                    for flags in ((0, native.OPT_WAVE_AGGREGATION) if seed % 10 == 0 else (0,)):
-                        ctx.count_launch(ds, dr, stranded, combine, flags)
-                        cryptic = bool(seed & 1)
-                        ctx.sse_launch(ds, cryptic)
-                        got = ds.counters()
-                        for name, w, g in zip(("beta1", "beta2s", "dbl"), want, got):
-                            if not np.array_equal(w, g):
-                                print("MISMATCH seed %d stranded %d combine %d flags %d reads %d: %s" % (seed, stranded, combine, flags, reads.n, name))
-                                sys.exit(1)
-                        ws = oracle.beta2_sse(arr.pos, arr.part_off, arr.part_pos, arr.part_site, arr.alpha, arr.edge_cnt, *want, cryptic)
-                        for name, w, g in zip(("b2s", "b2c", "b2w", "sse"), ws, ds.sse_results()):
-                            if not np.array_equal(w, g):
-                                print("MISMATCH seed %d stranded %d combine %d flags %d reads %d: %s" % (seed, stranded, combine, flags, reads.n, name))
-                                sys.exit(1)
+                    ctx.count_launch(ds, dr, stranded, combine, 0)
+                    cryptic = bool(seed & 1)
+                    ctx.sse_launch(ds, cryptic)
+                    got = ds.counters()
+                    for name, w, g in zip(("beta1", "beta2s", "dbl"), want, got):
+                        if not np.array_equal(w, g):
+                            print("MISMATCH seed %d stranded %d combine %d reads %d: %s" % (seed, stranded, combine, reads.n, name))
+                            sys.exit(1)
+                    ws = oracle.beta2_sse(arr.pos, arr.part_off, arr.part_pos, arr.part_site, arr.alpha, arr.edge_cnt, *want, cryptic)
+                    for name, w, g in zip(("b2s", "b2c", "b2w", "sse"), ws, ds.sse_results()):
+                        if not np.array_equal(w, g):
+                            print("MISMATCH seed %d stranded %d combine %d reads %d: %s" % (seed, stranded, combine, reads.n, name))
+                            sys.exit(1)
                     n_cases += 1
                     n_reads += reads.n
                 dr.free()
