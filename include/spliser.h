@@ -183,7 +183,7 @@ void spl_reads_free(spl_ctx *ctx, spl_dreads *dr);
  * device leaves (spl_bam_decode_device) and what SURVEY.md 8(d)'s "kernel-only from device-resident SoA" starts from.  A read
  * set is made from them ON THE DEVICE by spl_reads_add_soa + spl_reads_finish.  A set whose segments all lie in ONE such handle
  * stays arrays ("fused"): spl_count_launch reads them itself and makes its records in LDS (spl_kernels.hip, the FUSED range
- * kernel) -- no records in memory, no layout launch; what needs records (the pair kernel, spl_junctions), a set of several
+ * kernel) -- no records in memory, no layout launch, and spl_junctions reads the arrays too; what needs records (the pair kernel), a set of several
  * handles or with host-packed segments, or SPL_FUSED=0, gets them from the layout kernel
  * (spl_devpack.hip: one launch, every read fetched and classified once).  spl_reads_relayout does again what spl_reads_finish
  * launched -- the chunks' descriptors and order, and the layout kernel where the set has records -- so that a bench.py step is
@@ -337,11 +337,21 @@ int spl_bam_write2(const char *path, int n_ref, const char *const *ref_names, co
  * the table of the last call, sorted by (left, right, strand), into caller arrays (any may be NULL).  stranded: 0 ->
  * strand '?', 1 = fr / 2 = rf -> '+' / '-' of the read by check_strand's rule (:374-406).  Policy knobs in the sense of
  * regtools' -a / -m / -M: a read supports a junction only if both of ITS anchors are >= min_anchor and the intron length
- * is in [min_intron, max_intron] (max_intron 0 = no upper limit); 0, 0, 0 counts every N op. */
+ * is in [min_intron, max_intron] (max_intron 0 = no upper limit); 0, 0, 0 counts every N op.  A fused set stays fused: its
+ * table comes straight from the arrays (spl_reads_layout_bytes still reports 0 record bytes afterwards). */
 int spl_junctions(spl_ctx *ctx, const spl_dreads *dr, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron,
                   int64_t *n_out);
 int spl_junctions_get(const spl_ctx *ctx, int32_t *left, int32_t *right, uint8_t *strand, uint32_t *count,
                       uint32_t *anchor_left, uint32_t *anchor_right);
+/* What the last spl_junctions call cost: the bytes of the device table it allocated and, for a fused set between
+ * spl_kernel_timing_begin and spl_kernel_timing_collect, the device time of its launches in ms (-1 = not measured). */
+int spl_junctions_stats(const spl_ctx *ctx, int64_t *table_bytes_out, float *ms_out);
+/* The per-read walk the junction kernels share, on the host (no GPU involved; test hook): every N op of the read at `pos` with
+ * the given ops (BAM form) -> left, right, both anchors and whether the read supports it under the knobs; *n_out = their
+ * number (the first `capacity` are written), *range_error_out = the walk left the coordinate space. */
+int spl_junction_walk_host(const uint32_t *ops, uint32_t n_ops, int32_t pos, int32_t min_anchor, int32_t min_intron, int32_t max_intron,
+                           int capacity, int32_t *left, int32_t *right, uint32_t *anchor_left, uint32_t *anchor_right, uint8_t *passes,
+                           int *n_out, int *range_error_out);
 
 /* ---- host helper of Step 1 ---------------------------------------------------------------------------
  * binary_gene_search (SpliSER_v0_1_8.py:118-173) for a batch of query positions against one chromosome's gene list

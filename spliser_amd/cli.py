@@ -1,9 +1,13 @@
 """Command line of the MI355X build: the sub-commands, flags and argparse dests of SpliSER v0.1.8
 (SpliSER_v0_1_8.py:1295-1361), so existing pipelines only swap the script name.
 
-Extra flags (all optional, none changes results): ``--gpus`` / ``--devices`` to shard chromosomes over
-several MI355X of one node, ``--threads`` for the BAM decode pool.  Extra sub-command: ``junctions`` writes the BED12
-junction file ``process -b`` wants from the BAM itself (the reference leaves that to regtools).
+Extra flags, all optional.  These change no result: ``--gpus`` / ``--devices`` to shard chromosomes over several MI355X
+of one node, ``--threads`` for the BAM decode pool, ``--gpuDecode`` / ``--hostDecode``, ``--keepReads``, ``--checkJunctions``,
+``--keepJunctions``.  These DO change results, and only exist where there is no junction file: ``process`` without ``-b``
+takes the junctions from the BAM itself, in the same pass, and ``--minAnchor`` / ``--minIntron`` / ``--maxIntron`` say which
+reads support a junction (regtools' -a / -m / -M; defaults 8 / 70 / 500000) -- with ``-b`` they are an error, the file has
+its own.  Extra sub-command: ``junctions`` writes that BED12 junction file on its own, for ``process -b`` here or for the
+reference (which leaves it to regtools); ``process`` without ``-b`` writes what ``junctions`` + ``process -b`` write.
 """
 import argparse
 import sys
@@ -17,7 +21,18 @@ def build_parser():
     sub = parser.add_subparsers(dest="command")
     p = sub.add_parser("process")
     p.add_argument("-B", "--BAMFile", dest="inBAM", required=True, help="The mapped RNA-seq file in BAM format")
-    p.add_argument("-b", "--bedFile", dest="inBed", required=True, help="The Tophat-style splice junction bed file")
+    p.add_argument("-b", "--bedFile", dest="inBed", required=False, default=None,
+                   help="The Tophat-style splice junction bed file; (this build only) without it the junctions are taken from the BAM "
+                        "itself, in the same pass: what `junctions` followed by `process -b` writes, from one command and one decode")
+    p.add_argument("--minAnchor", dest="minAnchor", type=int, default=None,
+                   help="(this build only, without -b; changes results) both anchors of a read must be this long to support a junction "
+                        "(regtools -a) - default: 8")
+    p.add_argument("--minIntron", dest="minIntron", type=int, default=None, help="(without -b; changes results) regtools -m - default: 70")
+    p.add_argument("--maxIntron", dest="maxIntron", type=int, default=None,
+                   help="(without -b; changes results) regtools -M, 0 = no limit - default: 500000")
+    p.add_argument("--keepJunctions", dest="keepJunctions", default=False, action="store_true",
+                   help="(this build only, without -b) also write <outputPath>.junctions.bed: the file `junctions` writes for the same "
+                        "BAM and knobs")
     p.add_argument("-o", "--outputPath", dest="outputPath", required=True,
                    help="Absolute path, including file prefix where the .SpliSER.tsv file is written")
     p.add_argument("-A", "--annotationFile", dest="annotationFile", required=False,
@@ -116,6 +131,17 @@ def main(argv=None):
     elif command in ("process", "combine", "combineShallow", "junctions") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
     if command == "process":
+        if kwargs.get("inBed") is not None:
+            given = [f for f, d in (("--minAnchor", "minAnchor"), ("--minIntron", "minIntron"), ("--maxIntron", "maxIntron")) if kwargs.get(d) is not None]
+            if kwargs.get("keepJunctions"):
+                given.append("--keepJunctions")
+            if given:
+                parser.error("%s: only without --bedFile (a junction file has its own junctions)" % ", ".join(given))
+        else:
+            if kwargs.get("checkJunctions"):
+                parser.error("--checkJunctions compares the junction file with the BAM: it requires --bedFile")
+            if any(kwargs.get(d) is not None and kwargs.get(d) < 0 for d in ("minAnchor", "minIntron", "maxIntron")):
+                parser.error("--minAnchor / --minIntron / --maxIntron must not be negative")
         from .process import process
         if __import__("os").environ.get("SPL_PROCESS_TIMING"):
             sys.stderr.write("[cli] modules of `process` imported %.4f s after main() began\n" % (timeit.default_timer() - start))

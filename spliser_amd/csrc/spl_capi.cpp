@@ -28,6 +28,8 @@
 #include "spl_device.h"
 #include "spl_error.h"
 #include "spl_pack.h"
+#include "spl_junction_walk.h"
+#include "spl_junction_fused.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -310,7 +312,8 @@ struct spl_ctx {
     hipEvent_t ev_range[4] = {nullptr, nullptr, nullptr, nullptr}, ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_pass = 0;       // counting passes with a tail launched so far
     bool tail_pending = false; // the main stream has not been made to wait for the last tail yet
-    int32_t *d_err = nullptr;               // error word of launches that are not counting passes (spl_junctions)
+    int32_t *d_err = nullptr;               // error word of launches that are not counting passes (spl_junctions); 16 bytes: the second
+                                            // eight are spl_junctions' count of the N ops it sizes a fused set's table by
     // Read sets reach the device through a ring of page-locked staging buffers: the host packer (spl_pack.h) writes a piece of
     // a segment's records into one of them while the DMA engine drains the others on a stream of their own.  Locked with
     // hipHostRegister: on this stack that costs 0.7 ms per 32 MiB where hipHostMalloc costs 5 (tools/micro/hostmem.cpp), and
@@ -331,6 +334,8 @@ struct spl_ctx {
     int last_grid = 0, last_lds = 0;
     struct Junction { int32_t left, right; uint8_t strand; uint32_t count, anchor_left, anchor_right; };
     std::vector<Junction> junctions; // result of the last spl_junctions call, sorted
+    float junction_ms = -1.0f;       // ... the device time of its launches (a fused set, kernel timing on), -1 = not measured
+    int64_t junction_table_bytes = 0; // ... and the size of the table it made
     // optional per-launch stopwatch around spl_count_kernel alone (bench.py's roofline numerator)
     std::vector<hipEvent_t> k_ev; // pairs
     int k_used = 0;
@@ -425,7 +430,7 @@ struct spl_dreads {
     uint32_t chunk_shift = SPL_CHUNK_SHIFT; // reads per chunk of this set (fixed when it is begun: spl_reads_begin_sized)
     // FUSED: every segment of the set lies in ONE set of device arrays, and the counting pass reads those arrays itself
     // (spl_count_ranges_kernel<.., FUSED>: a chunk's records made in LDS, a tile of SPL_TILE_FUSED reads at a time) -- no record slots, no
-    // layout kernel.  What needs records in memory (the pair kernel, spl_reads_junctions) lays the set out first (unfuse).
+    // layout kernel.  What needs records in memory (the pair kernel) lays the set out first (unfuse); spl_junctions reads the arrays.
     bool fused = false;
     bool finished = false;
     char *ctl = nullptr;            // chunk descriptors, costs, chunk order, the queues (allocated by spl_reads_finish)
@@ -497,7 +502,7 @@ static int create_ctx(int device_id, void *stream, bool use_given, spl_ctx **out
         }
     }
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipMalloc((void **)&c->d_err, sizeof(int32_t)) != hipSuccess) {
+        hipMalloc((void **)&c->d_err, 16) != hipSuccess) {
         spl_destroy(c);
         return spl_set_error(SPL_ERR_HIP, "context resources could not be created");
     }
@@ -3022,20 +3027,48 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     HIP_TRY(hipSetDevice(c->device));
     c->junctions.clear();
     *n_out = 0;
-    // an N op needs an aligned op on both sides: fewer than half of all ops are junctions, so a table with one slot per op
-    // (rounded up to a power of two) stays under half full
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_junctions: the read set is not finished (spl_reads_finish)");
+    // A FUSED set (all of it in one set of device arrays) is read as the arrays it is, by the chunk descriptors its finish() made:
+    // it stays fused -- no record slots, no layout launch.  Its table is sized by the N ops that pass the intron filter (a count
+    // over the chunks' ops first: an upper bound of the inserts), twice as many slots at least.  Every other set has packed
+    // records, which spl_junction_kernel reads: there an N op needs an aligned op on both sides of it in all but degenerate reads,
+    // and a table with one slot per op (rounded up to a power of two) is what the set has been given since the kernel exists.
+    const bool fused = dr->fused && dr->groups.size() == 1;
+    const spl_dreads::Group *g = fused ? &dr->groups[0] : nullptr;
+    spl_devreads src{nullptr, nullptr, nullptr, nullptr};
+    uint64_t wanted = (uint64_t)dr->n_cigar;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    c->junction_ms = -1.0f;
+    if (fused) {
+        src = spl_devreads{(const int32_t *)g->src->pos, (const uint16_t *)g->src->flag, (const uint32_t *)g->src->cig_off, (const uint32_t *)g->src->cigar};
+        unsigned long long *d_count = (unsigned long long *)(c->d_err + 2), n_pass = 0; // (the context's own word: nothing allocated per call)
+        if (c->k_on) { // (timed like the counting kernels: from the count pass to the compaction)
+            if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) { if (ev0) (void)hipEventDestroy(ev0); ev0 = ev1 = nullptr; }
+            if (ev0) (void)hipEventRecord(ev0, c->stream);
+        }
+        hipError_t qc = (hipError_t)spl_dev_launch_junctions_count(&src, g->d_chunks, g->n_chunks, (uint32_t)min_intron, (uint32_t)max_intron, d_count, c->stream);
+        if (qc == hipSuccess) qc = hipMemcpyAsync(&n_pass, d_count, 8, hipMemcpyDeviceToHost, c->stream);
+        if (qc == hipSuccess) qc = hipStreamSynchronize(c->stream);
+        if (qc != hipSuccess) { if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); } return spl_set_error(SPL_ERR_HIP, "junction count: %s", hipGetErrorString(qc)); }
+        wanted = 2ull * n_pass;
+    }
     uint64_t slots = 1024;
-    while (slots < (uint64_t)dr->n_cigar) slots <<= 1;
-    if (slots > 0x80000000ull) return spl_set_error(SPL_ERR_ARG, "read set too large for one junction table: use more shards");
+    while (slots < wanted) slots <<= 1;
+    if (slots > 0x80000000ull) { if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); } return spl_set_error(SPL_ERR_ARG, "read set too large for one junction table: use more shards"); }
     char *buf = nullptr;
     const size_t bytes = (size_t)slots * (8 + 12) * 2 + 256;
     hipError_t e = hipMalloc((void **)&buf, bytes);
-    if (e != hipSuccess) return spl_set_error(SPL_ERR_HIP, "hipMalloc(%zu) for the junction table: %s", bytes, hipGetErrorString(e));
+    if (e != hipSuccess) { if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); } return spl_set_error(SPL_ERR_HIP, "hipMalloc(%zu) for the junction table: %s", bytes, hipGetErrorString(e)); }
+    c->junction_table_bytes = (int64_t)bytes;
     unsigned long long *keys = (unsigned long long *)buf, *out_keys = keys + slots;
     uint32_t *vals = (uint32_t *)(out_keys + slots), *out_vals = vals + 3 * slots, *n_dev = out_vals + 3 * slots;
-    if (!dr->finished) { (void)hipFree(buf); return spl_set_error(SPL_ERR_ARG, "spl_junctions: the read set is not finished (spl_reads_finish)"); }
-    if (dr->fused) { const int rc0 = unfuse(c, const_cast<spl_dreads *>(dr)); if (rc0) { (void)hipFree(buf); return rc0; } } // (the junction kernel reads records)
-    int rc = spl_dev_launch_junctions(dr->meta, dr->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron,
+    int rc;
+    if (fused) {
+        rc = spl_dev_launch_junctions_fused(&src, g->src->n_rec, g->src->n_ops, g->d_chunks, g->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron,
+                                            (uint32_t)max_intron, keys, vals, (uint32_t)slots, out_keys, out_vals, n_dev, c->d_err, c->stream);
+        if (ev1) (void)hipEventRecord(ev1, c->stream);
+    } else
+        rc = spl_dev_launch_junctions(dr->meta, dr->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron,
                                       (uint32_t)max_intron, keys, vals, (uint32_t)slots, out_keys,
                                       out_vals, n_dev, c->d_err, c->stream);
     uint32_t n = 0;
@@ -3043,6 +3076,10 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     hipError_t q = rc ? (hipError_t)rc : hipMemcpyAsync(&n, n_dev, 4, hipMemcpyDeviceToHost, c->stream);
     if (q == hipSuccess) q = hipMemcpyAsync(&err, c->d_err, 4, hipMemcpyDeviceToHost, c->stream);
     if (q == hipSuccess) q = hipStreamSynchronize(c->stream);
+    if (ev0) {
+        if (q == hipSuccess && hipEventElapsedTime(&c->junction_ms, ev0, ev1) != hipSuccess) c->junction_ms = -1.0f;
+        (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+    }
     std::vector<unsigned long long> hk;
     std::vector<uint32_t> hv;
     if (q == hipSuccess && n) {
@@ -3091,6 +3128,44 @@ extern "C" int spl_junctions_get(const spl_ctx *c, int32_t *left, int32_t *right
         if (anchor_left) anchor_left[i] = j.anchor_left;
         if (anchor_right) anchor_right[i] = j.anchor_right;
     }
+    return SPL_OK;
+}
+
+// What the last spl_junctions call cost: the bytes of the table it allocated, and -- for a fused set, between
+// spl_kernel_timing_begin and _collect -- the device time from its count pass to its compaction (-1: not measured).
+extern "C" int spl_junctions_stats(const spl_ctx *c, int64_t *table_bytes_out, float *ms_out)
+{
+    if (!c) return spl_set_error(SPL_ERR_ARG, "spl_junctions_stats: null context");
+    if (table_bytes_out) *table_bytes_out = c->junction_table_bytes;
+    if (ms_out) *ms_out = c->junction_ms;
+    return SPL_OK;
+}
+
+// The walk of one read's ops that the junction kernels share (spl_junction_walk.h), on the host: no GPU involved (test hook).
+extern "C" int spl_junction_walk_host(const uint32_t *ops, uint32_t n_ops, int32_t pos, int32_t min_anchor, int32_t min_intron, int32_t max_intron,
+                                      int capacity, int32_t *left, int32_t *right, uint32_t *anchor_left, uint32_t *anchor_right, uint8_t *passes,
+                                      int *n_out, int *range_error_out)
+{
+    if ((n_ops && !ops) || !n_out) return spl_set_error(SPL_ERR_ARG, "spl_junction_walk_host: null argument");
+    if (min_anchor < 0 || min_intron < 0 || max_intron < 0) return spl_set_error(SPL_ERR_ARG, "spl_junction_walk_host: negative filter value");
+    struct HostOps { const uint32_t *p; uint32_t operator()(uint32_t k) const { return p[k]; } };
+    const spljw::Filter f{(uint32_t)min_anchor, (uint32_t)min_intron, (uint32_t)max_intron};
+    spljw::Walk w;
+    w.begin(pos);
+    spljw::Junction j;
+    int n = 0;
+    while (spljw::next(w, HostOps{ops}, n_ops, f, j)) {
+        if (n < capacity) {
+            if (left) left[n] = j.l;
+            if (right) right[n] = j.r;
+            if (anchor_left) anchor_left[n] = j.anchor_left;
+            if (anchor_right) anchor_right[n] = j.anchor_right;
+            if (passes) passes[n] = j.passes ? 1 : 0;
+        }
+        ++n;
+    }
+    *n_out = n;
+    if (range_error_out) *range_error_out = w.range_error ? 1 : 0;
     return SPL_OK;
 }
 

@@ -86,6 +86,25 @@ def build(bins, is_stranded, bed_path, q_chrom="All", q_gene="All", max_intron=0
     return table
 
 
+def build_from_arrays(bins, is_stranded, chrom_rows, q_chrom="All", q_gene="All"):
+    """``build`` for junctions that never were text (``process`` without ``-b``): ``chrom_rows`` = [(chrom, left, right, strand,
+    alpha)] -- the chromosomes in the order a BED file would name them, each one's arrays in line order, what ``read_bed_columns``
+    gives for the lines ``junctions.write_junction_bed`` writes of them.  -> FastSiteTable, or None where ``build`` returns None."""
+    if q_gene != "All":
+        return None
+    table = FastSiteTable(bins, is_stranded)
+    for chrom, _, _, _, _ in chrom_rows:          # :265-268 (also for chromosomes the -c filter drops)
+        bins.ensure_chrom(chrom)
+    for chrom, left, right, strand, alpha in chrom_rows:
+        if not (q_chrom == chrom or q_chrom == "All"):
+            continue
+        arr = _chrom(table, chrom, np.asarray(left, np.int64), np.asarray(right, np.int64), np.asarray(strand, np.uint8), np.asarray(alpha, np.int64))
+        if arr is None:
+            return None
+        table._arrays[chrom] = arr
+    return table
+
+
 def _chrom(table, chrom, left, right, strand, alpha):
     """One chromosome from its lines (arrays in line order; ``strand`` = the strand column's byte, 0 when empty)."""
     is_stranded = table.is_stranded

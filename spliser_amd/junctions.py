@@ -9,6 +9,8 @@ take it from the aligner's XS tag, which this build does not decode).
 """
 import sys
 
+import numpy as np
+
 from . import native, process as _process
 
 
@@ -24,6 +26,110 @@ def write_junction_bed(handle, chrom, table, first_number=1):
     return n
 
 
+def track_line(minAnchor, minIntron, maxIntron):
+    return 'track name=junctions description="spliser_amd junctions (a>=%d, %d<=intron<=%d)"\n' % (minAnchor, minIntron, maxIntron)
+
+
+def write_bed_file(path, chroms, tables, minAnchor, minIntron, maxIntron, log=None):
+    """The BED12 file of ``junctions``: the track line, then every chromosome of ``chroms`` that has a table, numbered through.
+    ``tables``: {chrom: table} (dicts of arrays as ``DeviceReads.junctions`` returns them).  -> the number of lines."""
+    total = 0
+    with open(path, "w") as out:
+        out.write(track_line(minAnchor, minIntron, maxIntron))
+        for chrom in chroms:
+            if chrom not in tables:
+                continue
+            n = write_junction_bed(out, chrom, tables[chrom], total + 1)
+            if log is not None:
+                log(chrom, n)
+            total += n
+    return total
+
+
+_COLUMNS = (("left", np.int32), ("right", np.int32), ("strand", np.uint8), ("count", np.uint32), ("anchor_left", np.uint32), ("anchor_right", np.uint32))
+
+
+def merge_tables(parts):
+    """Junction tables of disjoint pieces of one chromosome's reads (the shares of a decode in shares) -> the table of all of
+    them: by key (left, right, strand) the counts added, the anchors the maximum; sorted like every table, by the signed left,
+    then right, then strand."""
+    if len(parts) == 1:
+        return parts[0]
+    cat = {k: np.concatenate([np.asarray(t[k]) for t in parts]) for k, _ in _COLUMNS}
+    order = np.lexsort((cat["strand"], cat["right"], cat["left"]))
+    cat = {k: v[order] for k, v in cat.items()}
+    n = order.shape[0]
+    head = np.ones(n, bool)
+    head[1:] = (cat["left"][1:] != cat["left"][:-1]) | (cat["right"][1:] != cat["right"][:-1]) | (cat["strand"][1:] != cat["strand"][:-1])
+    starts = np.flatnonzero(head)
+    out = {k: cat[k][starts] for k in ("left", "right", "strand")}
+    if n:
+        out["count"] = np.add.reduceat(cat["count"].astype(np.int64), starts).astype(np.uint32)
+        out["anchor_left"] = np.maximum.reduceat(cat["anchor_left"], starts)
+        out["anchor_right"] = np.maximum.reduceat(cat["anchor_right"], starts)
+    else:
+        out.update({k: cat[k] for k in ("count", "anchor_left", "anchor_right")})
+    return {k: out[k].astype(dt) for k, dt in _COLUMNS}
+
+
+def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, maxIntron):
+    """The junction table of every chromosome of ``chroms`` that has reads, from an alignment source whose decode has been
+    started (``process.open_and_decode``): -> {chrom: (reads, table)}.  The reads are taken where the decode left them: after a
+    decode on the device the read sets are fused and stay so (``spl_junctions`` reads the arrays; nothing is laid out, nothing
+    decoded again by whoever counts the same reads afterwards).  A decode in shares: every device takes the table of ITS piece of
+    a chromosome, and the pieces are merged here (``merge_tables``).  A file the host's threads decode, and SAM text: the first
+    device, chromosome by chromosome as they become complete."""
+    import threading
+    is_bam = isinstance(source, native.BamFile)
+    knobs = (minAnchor, minIntron, maxIntron)
+    pieces, errors, lock = {}, [], threading.Lock()
+    on_device = is_bam and source.device_decode_started() and source.join_decoders()
+    shares = getattr(source, "shares", None) if on_device else None
+
+    def take(ctx, chrom, add):
+        with ctx.begin_reads() as dr:
+            n = add(dr)
+            if not n:
+                return
+            dr.finish()
+            table = dr.junctions(stranded, *knobs)
+        with lock:
+            pieces.setdefault(chrom, []).append((n, table))
+
+    def run(device, jobs):
+        try:
+            with native.Context(device) as ctx:
+                for chrom, add in jobs:
+                    take(ctx, chrom, add)
+        except Exception as exc:
+            with lock:
+                errors.append(exc)
+
+    if shares:
+        plans = []
+        for k, (device, names) in enumerate(shares):
+            held = [c for c in chroms if c in names and source.share_ref(k, c)[0] > 0]
+            plans.append((device, [(c, (lambda dr, k=k, c=c: dr.add_bam_share(source, k, c))) for c in held]))
+    elif is_bam:
+        plans = [(devices[0], [(c, (lambda dr, c=c: dr.add_bam(source, c))) for c in chroms])]
+    else:
+        def add_sam(dr, c):
+            rs = source.reads(c)
+            if rs is None or not rs.n:
+                return 0
+            dr.add(native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar))
+            return rs.n
+        plans = [(devices[0], [(c, (lambda dr, c=c: add_sam(dr, c))) for c in chroms])]
+    workers = [threading.Thread(target=run, args=plan) for plan in plans if plan[1]]
+    for w in workers:
+        w.start()
+    for w in workers:
+        w.join()
+    if errors:
+        raise errors[0]
+    return {c: (sum(n for n, _ in got), merge_tables([t for _, t in got])) for c, got in pieces.items()}
+
+
 def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=8, minIntron=70, maxIntron=500000,
               qChrom="All", devices=(0,), threads=0, log=None):
     """Writes ``outputPath`` (a BED12 file) and returns the number of junctions."""
@@ -31,57 +137,16 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
     stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
     if isStranded and stranded == 0:
         raise ValueError("strandedType must be 'fr' or 'rf' for a stranded library")
-    import threading
-    from . import shard
-    source = _process.open_and_decode(inBAM, tuple(devices), None, threads)   # (on the GPU with one device, like `process`)
-    is_bam = isinstance(source, native.BamFile)
-    chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
-    lengths = dict(zip(source.ref_names, source.ref_lengths)) if is_bam else {c: (source.reads(c).n if source.reads(c) is not None else 0) for c in chroms}
-    plan = shard.assign({c: int(lengths.get(c, 1)) for c in chroms}, len(devices))   # chromosomes over the devices, longest first
-    tables, errors, lock = {}, [], threading.Lock()
-
-    def run(device, mine):
-        try:
-            with native.Context(device) as ctx:
-                for chrom in [c for c in chroms if c in mine]:     # (file order: a chromosome is complete when the next begins)
-                    with ctx.begin_reads() as dr:
-                        if is_bam:
-                            n = dr.add_bam(source, chrom)
-                        else:
-                            rs = source.reads(chrom)
-                            n = rs.n if rs is not None else 0
-                            if n:
-                                dr.add(native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar))
-                        if n == 0:
-                            continue
-                        dr.finish()
-                        table = dr.junctions(stranded, minAnchor, minIntron, maxIntron)
-                    with lock:
-                        tables[chrom] = (n, table)
-        except Exception as exc:
-            with lock:
-                errors.append(exc)
-    workers = [threading.Thread(target=run, args=(dev, set(mine))) for dev, mine in zip(devices, plan)]
-    for w in workers:
-        w.start()
-    for w in workers:
-        w.join()
+    source = _process.open_and_decode(inBAM, tuple(devices), None, threads)   # (on the GPU(s), like `process`)
     try:
-        if errors:
-            raise errors[0]
-        if is_bam and not source.wait_all():
+        chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+        tables = tables_of_source(source, tuple(devices), chroms, stranded, minAnchor, minIntron, maxIntron)
+        if isinstance(source, native.BamFile) and not source.wait_all():
             raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
     finally:
         if hasattr(source, "close"):
             source.close()
-    total = 0
-    with open(outputPath, "w") as out:
-        out.write('track name=junctions description="spliser_amd junctions (a>=%d, %d<=intron<=%d)"\n' % (minAnchor, minIntron, maxIntron))
-        for chrom in chroms:
-            if chrom not in tables:
-                continue
-            n, table = tables[chrom]
-            total += write_junction_bed(out, chrom, table, total + 1)
-            log("%s: %d reads, %d junctions" % (chrom, n, len(table["left"])))
+    total = write_bed_file(outputPath, chroms, {c: t for c, (_, t) in tables.items()}, minAnchor, minIntron, maxIntron,
+                           log=lambda chrom, n: log("%s: %d reads, %d junctions" % (chrom, tables[chrom][0], n)))
     log("Junctions written:\t%d" % total)
     return total

@@ -52,7 +52,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -382,6 +382,12 @@ class DeviceReads(object):
         _check(lib().spl_reads_finish(self.ctx._h, self._h))
         return self
 
+    def junctions_stats(self):
+        """-> (bytes of the device table the last ``junctions`` call on this context allocated, device ms of its launches or -1)."""
+        b, ms = ctypes.c_int64(0), ctypes.c_float(-1.0)
+        _check(lib().spl_junctions_stats(self.ctx._h, ctypes.byref(b), ctypes.byref(ms)))
+        return b.value, ms.value
+
     def layout_bytes(self):
         """-> (bytes of BAM-native arrays the layout kernel reads, bytes of records it writes) for this read set."""
         a, b = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -698,6 +704,11 @@ class BamFile(object):
         """Why the device decoder left the file to the host threads ('' if it did not)."""
         return lib().spl_bam_decline_reason(self._h).decode("utf-8", "replace")
 
+    def device_decode_started(self):
+        """Somebody has started a decode on the device(s) (``decode_on_device_async`` / ``decode_on_devices_async``): its outcome
+        is what ``join_decoders`` waits for."""
+        return getattr(self, "_device_thread", None) is not None or bool(getattr(self, "_device_threads", None))
+
     def join_decoders(self):
         """Waits for the OUTCOME of the device decoders started by ``decode_on_device_async`` / ``decode_on_devices_async``; ->
         True when the reads are on the device(s) and every reference is complete, False when the host threads have the file (they
@@ -814,6 +825,21 @@ class _BamHandle(object):
                 lib().spl_bam_close(cls._parked.pop(key))
         for rs in views.values():
             weakref.finalize(rs.pos, gone, None)
+
+
+def junction_walk_host(ops, pos, min_anchor=0, min_intron=0, max_intron=0):
+    """The junction kernels' per-read walk on the host (``spl_junction_walk_host``): -> ([(left, right, anchor_left,
+    anchor_right, passes)], range_error)."""
+    ops = np.ascontiguousarray(ops, np.uint32)
+    cap = max(1, ops.shape[0])
+    left, right = np.empty(cap, np.int32), np.empty(cap, np.int32)
+    al, ar, ok = np.empty(cap, np.uint32), np.empty(cap, np.uint32), np.empty(cap, np.uint8)
+    n, bad = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().spl_junction_walk_host(_ptr(ops), ctypes.c_uint32(ops.shape[0]), ctypes.c_int32(int(pos)), ctypes.c_int32(int(min_anchor)),
+                                        ctypes.c_int32(int(min_intron)), ctypes.c_int32(int(max_intron)), ctypes.c_int(cap), _ptr(left), _ptr(right),
+                                        _ptr(al), _ptr(ar), _ptr(ok), ctypes.byref(n), ctypes.byref(bad)))
+    k = n.value
+    return list(zip(left[:k].tolist(), right[:k].tolist(), al[:k].tolist(), ar[:k].tolist(), [bool(x) for x in ok[:k].tolist()])), bool(bad.value)
 
 
 def pack_host(reads, threads=1):

@@ -212,7 +212,7 @@ def process_sites(table, source, q_chrom, is_stranded, stranded_type, is_beta2_c
         # the device decoder delivers every reference at once: nothing to stream chromosome by chromosome, so all chromosomes of
         # a shard are laid out as ONE read set and counted in one pass.  (Whether it did is asked when the first site table is
         # up: context and table take 10 ms that the decode's last kernels can run beside.)
-        device_decode = is_bam and (getattr(source, "_device_thread", None) is not None or getattr(source, "_device_threads", None)) and on_junctions is None
+        device_decode = is_bam and source.device_decode_started() and on_junctions is None
         whole = None
         stamps = [] if os.environ.get("SPL_PROCESS_TIMING") else None   # (where a device thread's time goes, on stderr)
 
@@ -436,10 +436,17 @@ def write_tsv(output_path, table, results, is_beta2_cryptic):
     w.close(list(results))
 
 
-def process(inBAM, inBed, outputPath, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
+def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
             isStranded=False, strandedType=None, isbeta2Cryptic=False, devices=(0,), threads=0, log=_log, checkJunctions=False,
-            gpuDecode=None, keepReads=False):
+            gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False):
     """SpliSER_v0_1_8.py:695-720, keyword-compatible with the reference's argparse dests.
+
+    ``inBed=None`` (this build only): no junction file -- the junctions are taken from the reads themselves, in this call, from
+    the one decode of the BAM: every chromosome's junction table on the GPU (``spl_junctions``; a read set decoded on the device
+    is fused and stays so), by the policy knobs ``minAnchor`` / ``minIntron`` / ``maxIntron`` (these DO change results; their
+    defaults are the ``junctions`` command's, regtools' 8 / 70 / 500000), and the site table straight from those arrays.  What
+    is written is what ``junctions`` followed by ``process -b`` on its file writes.  ``keepJunctions``: also leave
+    ``<outputPath>.junctions.bed``, the file ``junctions`` would have written.
 
     ``checkJunctions`` (this build only; changes no result): also derive every chromosome's junction table from the reads on
     the GPU and write ``<outputPath>.junctionCheck.tsv`` -- BED alpha against reads in the BAM per junction -- with a warning
@@ -453,6 +460,17 @@ def process(inBAM, inBed, outputPath, qGene="All", qChrom="All", maxIntronSize=0
     ``keepReads`` (this build only; changes no result): also leave ``<outputPath>.SpliSER.reads`` -- flag, POS and CIGAR of every
     placed record, all ``checkBam`` reads of an alignment -- which ``combine`` takes instead of decoding the BAM again, as long
     as it is still that BAM's (``readstore``)."""
+    if outputPath is None:
+        raise TypeError("process: outputPath is required")
+    knobs = None
+    if inBed is None:
+        if checkJunctions:
+            raise ValueError("checkJunctions compares a junction file with the reads: it needs inBed")
+        knobs = tuple(d if v is None else int(v) for v, d in zip((minAnchor, minIntron, maxIntron), JUNCTION_DEFAULTS))
+        if min(knobs) < 0:
+            raise ValueError("minAnchor / minIntron / maxIntron must not be negative")
+    elif not (minAnchor is None and minIntron is None and maxIntron is None) or keepJunctions:
+        raise ValueError("minAnchor / minIntron / maxIntron / keepJunctions belong to a run without inBed: a junction file has its own")
     timings = {}
     t0 = time.perf_counter()
     # The alignment file does not depend on Steps 0-2: it is decoded on native threads while the site table is built here, and
@@ -462,7 +480,14 @@ def process(inBAM, inBed, outputPath, qGene="All", qChrom="All", maxIntronSize=0
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
-        table = _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log)
+        rows_of_bam = None
+        if inBed is None:
+            def rows_of_bam():
+                t_j = time.perf_counter()
+                rows = _junction_rows(source, inBAM, outputPath if keepJunctions else None, qChrom, isStranded, strandedType, knobs, devices)
+                timings["junctions_s"] = time.perf_counter() - t_j
+                return rows
+        table = _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam)
         t1 = time.perf_counter()
         log("\n\nStep 3: Finding Beta reads")
         log("Processing sample 1 out of 1")
@@ -546,8 +571,30 @@ def process(inBAM, inBed, outputPath, qGene="All", qChrom="All", maxIntronSize=0
     return timings
 
 
-def _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log):
-    """Steps 0-2 (SpliSER_v0_1_8.py:700-712)."""
+JUNCTION_DEFAULTS = (8, 70, 500000)     # minAnchor, minIntron, maxIntron of a run without a junction file (the `junctions` command's)
+
+
+def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType, knobs, devices):
+    """A run without a junction file: every chromosome's junction table from the reads the decode leaves (``-c``: that one's) ->
+    [(chrom, table)] of the chromosomes that have a junction, in the order of the header: the lines of the file ``junctions``
+    writes, never written -- unless ``keep_prefix`` asks for it (``<prefix>.junctions.bed``, the same bytes)."""
+    from . import junctions as jn
+    stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
+    if isStranded and stranded == 0:
+        raise ValueError("strandedType must be 'fr' or 'rf' for a stranded analysis")
+    chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+    got = jn.tables_of_source(source, devices, chroms, stranded, *knobs)
+    if isinstance(source, native.BamFile) and not source.wait_all():     # (with -c too: an unsorted file's reference may be incomplete)
+        raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
+    tables = {c: t for c, (_, t) in got.items()}
+    if keep_prefix is not None:
+        jn.write_bed_file(keep_prefix + ".junctions.bed", chroms, tables, *knobs)
+    return [(c, tables[c]) for c in chroms if c in tables and len(tables[c]["left"])]
+
+
+def _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam=None):
+    """Steps 0-2 (SpliSER_v0_1_8.py:700-712).  ``rows_of_bam`` (no junction file): called after Step 0 -> [(chrom, junction
+    table)], see ``_junction_rows``."""
     log("Processing")
     log("Stranded Analysis {}".format(strandedType) if isStranded else "Unstranded Analysis")
     bins = sites.GeneBins()
@@ -559,7 +606,21 @@ def _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isSt
     log("Processing sample 1 out of 1")
     # one sample, no gene query, ordinary strands: the table follows from a few sorts (fast_sites.py, held to the
     # line-by-line builder by tests/test_fast_sites.py); anything else is built line by line
-    table = fast_sites.build(bins, isStranded, inBed, q_chrom=qChrom, q_gene=qGene, max_intron=int(maxIntronSize))
+    if rows_of_bam is not None:
+        # the junctions as arrays, in the order their lines would have: what fast_sites reads from the file, without the file
+        rows = rows_of_bam()
+        table = fast_sites.build_from_arrays(bins, isStranded, [(c, t["left"], t["right"], t["strand"], t["count"]) for c, t in rows],
+                                             q_chrom=qChrom, q_gene=qGene)
+        if table is None:       # (a gene query; a left of -1, ends that coincide: line by line, from the lines the file would hold)
+            import io
+            from . import junctions as jn
+            text, first = io.StringIO(), 1
+            for c, t in rows:
+                first += jn.write_junction_bed(text, c, t, first)
+            text.seek(0)
+            inBed = text
+    else:
+        table = fast_sites.build(bins, isStranded, inBed, q_chrom=qChrom, q_gene=qGene, max_intron=int(maxIntronSize))
     if table is None:
         table = sites.SiteTable(bins, is_stranded=isStranded)
         table.add_bed(inBed, q_chrom=qChrom, q_gene=qGene, max_intron=int(maxIntronSize))

@@ -16,6 +16,8 @@ alpha / Partners / Competitors columns and the Gene column, so it follows the re
 (including the ones that look accidental) exactly.
 """
 import bisect
+import contextlib
+import os
 
 import numpy as np
 
@@ -368,7 +370,8 @@ class SiteTable(object):
             raise ValueError("gene %r not found in the annotation (the reference dereferences None here, "
                              "SpliSER_v0_1_8.py:283)" % (q_gene,))
         max_intron = int(max_intron)
-        with open(bed_path, "r") as handle:
+        # (a path, or the lines themselves: `process` without -b hands over junctions that never were a file)
+        with (open(bed_path, "r") if isinstance(bed_path, (str, bytes, os.PathLike)) else contextlib.nullcontext(bed_path)) as handle:
             for line in handle:
                 values = line.split("\t")
                 if len(values) != 12:           # header / non-BED12 lines are skipped (:259)
