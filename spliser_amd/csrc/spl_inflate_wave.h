@@ -66,6 +66,10 @@ constexpr uint32_t FL_OK = 0, FL_EOB = 1, FL_ERR = 2;
 constexpr uint32_t EMIT_ROUNDS = SPLZ_EMIT_ROUNDS; // rounds of correction in which a corrected lane writes its tokens down at once (decode_block)
 constexpr uint32_t OPT_WRITING_PASS = 1; // decode_block: every tile's tokens by a writing pass of their own (rounds 3-5's way; A/B and tests)
 constexpr uint32_t SYM_EOB = 256, SYM_MATCH = 257, SYM_BAD = 0xffffffffu;
+// Which way a tile went, for the host harness alone (tests/hostsim/inflate_wave_host.cpp counts them): nothing, unless it is defined.
+#ifndef SPLZ_PATH
+#define SPLZ_PATH(which, taken)
+#endif
 
 // One wave's shared memory: 10120 bytes (16 waves on a CU's 160 KB).
 struct Shared {
@@ -541,6 +545,7 @@ WV_DEV uint32_t decode_block(Shared &sh, const uint8_t *image, const spl_zblock 
             const uint32_t n_valid = ~m_ok ? wv::ffs64(~m_ok) : 64u; // (the low run of ones)
             if (n_valid == 0u) return SPL_Z_OVERRUN;
             const bool valid = l < n_valid;
+            SPLZ_PATH(cut_short, wv::any(!dead && !valid));
             if (wv::any(valid && c.flag == FL_ERR)) return SPL_Z_BAD_CODE;
             eob = wv::any(valid && c.flag == FL_EOB);
             const uint32_t total = wv::readlane(cum_o, n_valid - 1u), n_t = wv::readlane(cum_t, n_valid - 1u);
@@ -549,6 +554,8 @@ WV_DEV uint32_t decode_block(Shared &sh, const uint8_t *image, const spl_zblock 
             if (in_place) {
                 // the tokens are written: each lane's to its stretch of the block's stream, sixteen bytes at a time, the last ones exactly
                 if (wv::any(valid && need > at + cum_o - c.n_out)) return SPL_Z_BAD_DISTANCE;
+                SPLZ_PATH(in_place, true);
+                SPLZ_PATH(misfit, wv::any(valid && misfit));
                 uint8_t *const dst = stream + n_tok + (cum_t - c.n_tok);
                 auto copy_out = [&](const uint8_t *from) {
                     for (uint32_t o = 0; o < c.n_tok; o += 16u) {
@@ -576,6 +583,7 @@ WV_DEV uint32_t decode_block(Shared &sh, const uint8_t *image, const spl_zblock 
             }
             // ---- the writing pass: every lane's symbols as tokens, at the lane's place in the tile's stretch of the stream
             bool bad_dist = false;
+            SPLZ_PATH(writing_pass, true);
 #ifndef SPL_EXP_NO_WRITE
             if (valid) {
                 uint32_t p = start, wr = at + cum_o - c.n_out, tp = cum_t - c.n_tok, run = 0, hdr = 0;

@@ -7,22 +7,35 @@
 
 #define WAVE_EMUL_IMPLEMENTATION
 #include "wave_emul.h"
+// which way the tiles of a block went (decode_block): tiles whose tokens were written in place, of those the ones with a lane whose
+// tokens did not fit its place and were written again, tiles cut short of a lane that was alive, tiles that took the writing pass
+enum { path_in_place, path_misfit, path_cut_short, path_writing_pass, N_PATHS };
+static uint32_t g_paths[N_PATHS];
+#define SPLZ_PATH(which, taken) do { const bool t_ = (taken); if (t_ && wv::lane() == 0) ++g_paths[path_##which]; } while (0)
 #include "../../spliser_amd/csrc/spl_inflate_wave.h"
 
-extern "C" int emul_inflate_blocks(const uint8_t *image, const spl_zblock *blocks, uint32_t n, uint8_t *out, uint32_t *status)
+// tok_cap: the token room a block is given (SPL_Z_TOKEN_STRIDE or less, a multiple of 16); paths (or null): n x 3 x N_PATHS counts,
+// per block and run (default, writing pass, TOKCAP_SMALL); tokens_out (or null): the default run's token stream of the LAST block,
+// room for SPL_Z_TOKEN_STRIDE bytes, n_tok_out its length
+extern "C" int emul_inflate_blocks_room(const uint8_t *image, const spl_zblock *blocks, uint32_t n, uint8_t *out, uint32_t *status, uint32_t tok_cap, uint32_t *paths,
+                                        uint8_t *tokens_out, uint32_t *n_tok_out)
 {
     static splz::Shared sh;
+    if (tok_cap < 256u || tok_cap > SPL_Z_TOKEN_STRIDE || (tok_cap & 15u)) return -900000;
     for (uint32_t b = 0; b < n; ++b) {
         memset(&sh, 0xEE, sizeof sh); // (nothing may depend on what the wave before left)
         static std::vector<uint8_t> tokens(SPL_Z_TOKEN_STRIDE + 256);
         memset(tokens.data(), 0xEE, tokens.size());
         uint32_t n_tok = 0;
+        memset(g_paths, 0, sizeof g_paths);
         const bool ok = wv::run_wave([&]() {
             uint32_t n = 0;
-            const uint32_t st = splz::decode_block(sh, image, blocks[b], tokens.data(), n);
+            const uint32_t st = splz::decode_block(sh, image, blocks[b], tokens.data(), n, tok_cap);
             if (wv::lane() == 0) { status[b] = st; n_tok = st == SPL_Z_OK ? n : 0u; }
         });
         if (!ok) return -1 - (int)b;
+        if (paths) memcpy(paths + (3u * b + 0u) * N_PATHS, g_paths, sizeof g_paths);
+        if (tokens_out && b == n - 1u) { memcpy(tokens_out, tokens.data(), n_tok); *n_tok_out = n_tok; }
         // ... and once more with every tile's tokens by a writing pass of their own (what a tile falls back to): the same status,
         // the same token stream, byte for byte
         {
@@ -30,12 +43,16 @@ extern "C" int emul_inflate_blocks(const uint8_t *image, const spl_zblock *block
             memset(tokens2.data(), 0xEE, tokens2.size());
             memset(&sh, 0xEE, sizeof sh);
             uint32_t st2 = 99, n2 = 0;
+            memset(g_paths, 0, sizeof g_paths);
             const bool ok2 = wv::run_wave([&]() {
                 uint32_t n = 0;
-                const uint32_t st = splz::decode_block(sh, image, blocks[b], tokens2.data(), n, SPL_Z_TOKEN_STRIDE, splz::OPT_WRITING_PASS);
+                const uint32_t st = splz::decode_block(sh, image, blocks[b], tokens2.data(), n, tok_cap, splz::OPT_WRITING_PASS);
                 if (wv::lane() == 0) { st2 = st; n2 = st == SPL_Z_OK ? n : 0u; }
             });
             if (!ok2) return -200000 - (int)b;
+            if (paths) memcpy(paths + (3u * b + 1u) * N_PATHS, g_paths, sizeof g_paths);
+            for (size_t k = tok_cap; k < tokens2.size(); ++k)
+                if (tokens2[k] != 0xEE) return -100000 - (int)b;
             if (st2 != status[b] || n2 != n_tok || (n_tok && memcmp(tokens.data(), tokens2.data(), n_tok) != 0)) return -300000 - (int)b;
         }
         // ... and once more the way the denser kernel does (spl_inflate_decode_dense_kernel: its wave's shared memory ends
@@ -46,16 +63,22 @@ extern "C" int emul_inflate_blocks(const uint8_t *image, const spl_zblock *block
             memset(tokens3.data(), 0xEE, tokens3.size());
             memset(&sh, 0xEE, sizeof sh);
             uint32_t st3 = 99, n3 = 0;
+            memset(g_paths, 0, sizeof g_paths);
             const bool ok3 = wv::run_wave([&]() {
                 uint32_t n = 0;
-                const uint32_t st = splz::decode_block<splz::TOKCAP_SMALL>(sh, image, blocks[b], tokens3.data(), n);
+                const uint32_t st = splz::decode_block<splz::TOKCAP_SMALL>(sh, image, blocks[b], tokens3.data(), n, tok_cap);
                 if (wv::lane() == 0) { st3 = st; n3 = st == SPL_Z_OK ? n : 0u; }
             });
             if (!ok3) return -400000 - (int)b;
-            if (st3 != status[b]) return -500000 - (int)b;
+            if (paths) memcpy(paths + (3u * b + 2u) * N_PATHS, g_paths, sizeof g_paths);
+            for (size_t k = tok_cap; k < tokens3.size(); ++k)
+                if (tokens3[k] != 0xEE) return -100000 - (int)b;
+            // (with the whole room the status is the same; with less, tiles cut elsewhere make other tokens, a few more or fewer, and
+            //  one kernel's may fit where the other's do not: then one of the two says SPL_Z_TOKENS, and that is all they may differ in)
+            if (st3 != status[b] && !(tok_cap < SPL_Z_TOKEN_STRIDE && (st3 == SPL_Z_TOKENS || status[b] == SPL_Z_TOKENS))) return -500000 - (int)b;
             for (uint32_t k = splz::TOKCAP_SMALL / 4u; k < splz::TOKCAP / 4u; ++k)
                 if (sh.tok[k] != 0xEEEEEEEEu) return -600000 - (int)b; // (memory the denser kernel's wave does not have)
-            if (st3 == SPL_Z_OK) {
+            if (st3 == SPL_Z_OK && status[b] == SPL_Z_OK) {
                 static std::vector<uint8_t> out3(65536 + 64);
                 static uint8_t lane_lds3[splz::COPY_LANE_BYTES];
                 memset(lane_lds3, 0xEE, sizeof lane_lds3);
@@ -67,7 +90,7 @@ extern "C" int emul_inflate_blocks(const uint8_t *image, const spl_zblock *block
                 if (made3 != made1 || (made1 == blocks[b].out_len && memcmp(out1.data(), out3.data(), made1) != 0)) return -700000 - (int)b;
             }
         }
-        for (size_t k = SPL_Z_TOKEN_STRIDE; k < tokens.size(); ++k) // (a block's room for tokens ends where the next block's begins)
+        for (size_t k = tok_cap; k < tokens.size(); ++k) // (a block's room for tokens ends where the next block's begins)
             if (tokens[k] != 0xEE) return -100000 - (int)b;
         if (status[b] == SPL_Z_OK) {
             static uint8_t lane_lds[splz::COPY_LANE_BYTES];
@@ -77,6 +100,11 @@ extern "C" int emul_inflate_blocks(const uint8_t *image, const spl_zblock *block
         }
     }
     return 0;
+}
+
+extern "C" int emul_inflate_blocks(const uint8_t *image, const spl_zblock *blocks, uint32_t n, uint8_t *out, uint32_t *status)
+{
+    return emul_inflate_blocks_room(image, blocks, n, out, status, SPL_Z_TOKEN_STRIDE, nullptr, nullptr, nullptr);
 }
 
 #ifndef EMUL_NO_MAIN

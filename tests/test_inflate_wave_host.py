@@ -11,6 +11,8 @@ import zlib
 import numpy as np
 import pytest
 
+from deflatecases import _Bits, _mixed_block  # noqa: F401  (the hand writer lives with the hand-built cases)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostsim", "inflate_wave_host.cpp")
 LIB = os.path.join(ROOT, "tests", "hostsim", "libinflate_wave_host.so")
@@ -18,15 +20,20 @@ DEPS = [SRC, os.path.join(ROOT, "tests", "hostsim", "wave_emul.h"), os.path.join
         os.path.join(ROOT, "spliser_amd", "csrc", "spl_inflate.h")]
 
 
-@pytest.fixture(scope="module")
-def emul():
+def load_emulator():
     extra = os.environ.get("SPL_EMUL_DEFINES", "").split()      # (kernel experiments: e.g. "-DSPLZ_RING=64 -DSPLZ_FIFO=128", the copying kernel's LDS per lane)
     lib_path = LIB if not extra else LIB.replace(".so", "_exp.so")
     if extra or not os.path.exists(lib_path) or any(os.path.getmtime(d) > os.path.getmtime(lib_path) for d in DEPS):
         subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wno-unknown-pragmas", "-shared", "-fPIC", "-DEMUL_NO_MAIN"] + extra + ["-o", lib_path, SRC, "-lz"])
     lib = ctypes.CDLL(lib_path)
     lib.emul_inflate_blocks.restype = ctypes.c_int
+    lib.emul_inflate_blocks_room.restype = ctypes.c_int
     return lib
+
+
+@pytest.fixture(scope="module")
+def emul():
+    return load_emulator()
 
 
 def _run(lib, streams):
@@ -108,52 +115,6 @@ def test_bgzf_blocks_of_a_bam(emul, tmp_path):
     status, got, _, _ = _run(emul, streams)
     assert not status.any()
     assert got[:-128] == b"".join(s[1] for s in streams)
-
-
-class _Bits:
-    """DEFLATE's bit order: fields LSB first, Huffman codes MSB first (RFC 1951 3.1.1)."""
-
-    def __init__(self):
-        self.buf, self.acc, self.n = bytearray(), 0, 0
-
-    def put(self, value, bits):
-        self.acc |= value << self.n
-        self.n += bits
-        while self.n >= 8:
-            self.buf.append(self.acc & 0xff)
-            self.acc >>= 8
-            self.n -= 8
-
-    def code(self, value, bits):
-        self.put(int(format(value, "0%db" % bits)[::-1], 2), bits)
-
-    def align(self):
-        if self.n:
-            self.put(0, 8 - self.n)
-
-
-def _mixed_block(n_pairs, n_stored, seed=5):
-    """One DEFLATE stream: a fixed-code section of `n_pairs` x (lone literal, match of length 3 at distance 1) -- 5 bytes of
-    tokens for 4 of output, the most a Huffman section can ask for -- then `n_stored` stored sections of ONE byte each (2 bytes of
-    tokens per byte of output).  -> (data, comp)"""
-    rng = np.random.default_rng(seed)
-    w, data = _Bits(), bytearray()
-    w.put(0, 1), w.put(1, 2)                        # not the last section, fixed code
-    for lit in rng.integers(0, 144, n_pairs):
-        w.code(0x30 + int(lit), 8)                  # literal 0..143: 8 bits, 00110000 + value
-        w.code(1, 7)                                # 257 = length 3: 7 bits, 0000001
-        w.code(0, 5)                                # distance code 0 = 1
-        data += bytes([int(lit)]) * 4
-    w.code(0, 7)                                    # 256, the section's end
-    for k, b in enumerate(rng.integers(0, 256, n_stored)):
-        w.put(1 if k == n_stored - 1 else 0, 1), w.put(0, 2)
-        w.align()
-        w.put(1, 16), w.put(0xfffe, 16), w.put(int(b), 8)
-        data.append(int(b))
-    w.align()
-    comp = bytes(w.buf)
-    assert zlib.decompress(comp, -15) == bytes(data)
-    return bytes(data), comp
 
 
 def test_stored_sections_cannot_overrun_a_blocks_token_room(emul):
