@@ -231,7 +231,8 @@ int spl_last_launch_info(const spl_ctx *ctx, int32_t *grid_out, int32_t *block_o
 /* ---- BAM ingest: replaces `samtools view` (SpliSER_v0_1_8.py:422) ------------------------------
  * The whole BGZF file is inflated and its alignment records are split per reference sequence on n_threads host threads
  * (0 = all cores up to 32).  Like `samtools view` without -F/-q every record that has a reference id is kept (secondary,
- * supplementary, duplicate, QC-fail, unmapped-but-placed ...).
+ * supplementary, duplicate, QC-fail, unmapped-but-placed ...) -- unless a read filter is set (spl_bam_set_filter below): then
+ * only the records that pass it are, as if the file had gone through `samtools view -q / -f / -F` first.
  * spl_bam_open_stream returns once the block directory and the header are read; the decode goes on on threads of its own.
  * spl_bam_wait_ref waits until reference `tid` is complete -- in a file sorted by reference that is when a record of a later
  * reference has been seen, long before the end of the file -- so that its reads can go to the GPU (spl_reads_add_bam) while
@@ -250,6 +251,16 @@ int spl_bam_open_stream(const char *path, int n_threads, spl_bam **out);
  * reference, CIGARs parked in CG tags, anything malformed) and the host threads have been started on it instead -- results and
  * error reporting are the host decoder's either way.  Waiting on a deferred file nobody decoded starts the host decode. */
 int spl_bam_open_deferred(const char *path, int n_threads, spl_bam **out);
+/* Read filter, samtools view's -q / -f / -F (the reference has none: its pipelines run samtools over the file first): of the
+ * records that have a reference and a position only those are kept with (flag & exclude_flags) == 0, (flag & require_flags) ==
+ * require_flags and MAPQ >= min_mapq -- MAPQ as a number, 255 passes every threshold.  A record that fails is never extracted,
+ * counted or handed out, on the host's decoder and the device's alike; spl_bam_n_records still counts it.  0, 0, 0 (the default)
+ * keeps everything.  To be called before anybody decodes the file or waits for it, i.e. on a file from spl_bam_open_deferred
+ * (spl_bam_open_stream and spl_bam_open start the decode themselves); later, or with min_mapq outside 0..255 or a mask outside
+ * 0..65535, it is SPL_ERR_ARG.  spl_bam_filter_counts: out2 = {records dropped by their flags, records dropped by their MAPQ
+ * alone} -- flags are tested first -- once the decode is complete (it waits for that, like spl_bam_n_records). */
+int spl_bam_set_filter(spl_bam *bam, int min_mapq, int require_flags, int exclude_flags);
+int spl_bam_filter_counts(spl_bam *bam, int64_t *out2);
 int spl_bam_decode_device(spl_ctx *ctx, spl_bam *bam, int *on_device_out);
 /* For a caller that will call spl_bam_decode_device from another thread in a moment while others may already wait for
  * references: the file is marked as taken by the device decoder now, so that those waits wait instead of starting the host
@@ -273,7 +284,8 @@ int spl_bam_reserve_device(spl_bam *bam);
  * threads decode the file (*on_device_out = 0 from that share's call; spl_bam_decoded_on_device says how it ended).  Afterwards
  * spl_bam_share_ref says what share k holds of a reference and spl_reads_add_bam_share adds exactly that to a read set on the
  * share's device.  spl_bam_share_count_host (diagnostic, no GPU): the records of share k per reference by the host's inflate and
- * a plain walk from u_lo that must arrive at u_hi -- per_tid[n_ref + 1], the last entry the records without a reference. */
+ * a plain walk from u_lo that must arrive at u_hi -- per_tid[n_ref + 1], the last entry the records without a reference; records
+ * the file's read filter drops are left out. */
 int spl_bam_share_plan(spl_bam *bam, int n_shares, int *n_out);
 int spl_bam_share_range(spl_bam *bam, int k, int *tid_lo_out, int *tid_hi_out);
 int spl_bam_share_info(spl_bam *bam, int k, int64_t *file_bytes_out, int64_t *u_lo_out, int64_t *u_hi_out, int64_t *tail_blocks_out);

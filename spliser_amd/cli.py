@@ -6,7 +6,8 @@ of one node, ``--threads`` for the BAM decode pool, ``--gpuDecode`` / ``--hostDe
 ``--keepJunctions``.  These DO change results, and only exist where there is no junction file: ``process`` without ``-b``
 takes the junctions from the BAM itself, in the same pass, and ``--minAnchor`` / ``--minIntron`` / ``--maxIntron`` say which
 reads support a junction (regtools' -a / -m / -M; defaults 8 / 70 / 500000) -- with ``-b`` they are an error, the file has
-its own.  Extra sub-command: ``junctions`` writes that BED12 junction file on its own, for ``process -b`` here or for the
+its own.  ``--minMapQ`` / ``--requireFlags`` / ``--excludeFlags`` (``process``, ``junctions``, ``combine``, ``combineShallow``) are
+samtools view's -q / -f / -F applied while the BAM is decoded: the run's results are those of the pre-filtered file.  Extra sub-command: ``junctions`` writes that BED12 junction file on its own, for ``process -b`` here or for the
 reference (which leaves it to regtools); ``process`` without ``-b`` writes what ``junctions`` + ``process -b`` write.
 """
 import argparse
@@ -63,6 +64,7 @@ def build_parser():
     p.add_argument("--keepReads", dest="keepReads", default=False, action="store_true",
                    help="(this build only) also write <outputPath>.SpliSER.reads (flag, POS, CIGAR of every read): combine takes it "
                         "instead of decoding the BAM again while it is still that BAM's")
+    _filter_flags(p)
     _engine_flags(p)
     c = sub.add_parser("combine")
     c.add_argument("-S", "--samplesFile", dest="samplesFile", required=True,
@@ -72,6 +74,7 @@ def build_parser():
     c.add_argument("--isStranded", dest="isStranded", default=False, action="store_true")
     c.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", default="fr", type=str, required=False)
     c.add_argument("--beta2Cryptic", dest="isbeta2Cryptic", default=False, action="store_true")
+    _filter_flags(c)
     _engine_flags(c)
     h = sub.add_parser("combineShallow")
     h.add_argument("-S", "--samplesFile", dest="samplesFile", required=True)
@@ -83,6 +86,7 @@ def build_parser():
     h.add_argument("-e", "--minSSE", dest="minSSE", required=False, nargs="?", default=0.00, type=float)
     h.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False)
     h.add_argument("--beta2Cryptic", dest="isbeta2Cryptic", default=False, action="store_true")
+    _filter_flags(h)
     _engine_flags(h)
     o = sub.add_parser("output")
     o.add_argument("-S", "--samplesFile", dest="samplesFile", required=True)
@@ -101,8 +105,25 @@ def build_parser():
     j.add_argument("-a", "--minAnchor", dest="minAnchor", type=int, default=8, help="both anchors of a read must be this long (regtools -a)")
     j.add_argument("-m", "--minIntron", dest="minIntron", type=int, default=70, help="regtools -m")
     j.add_argument("-M", "--maxIntron", dest="maxIntron", type=int, default=500000, help="regtools -M; 0 = no limit")
+    _filter_flags(j)
     _engine_flags(j)
     return parser
+
+
+def _flag_mask(text):
+    return int(text, 0)     # (0x900 as well as 2304, as samtools takes them)
+
+
+def _filter_flags(p):
+    p.add_argument("--minMapQ", dest="minMapQ", type=int, default=0,
+                   help="(this build only; changes results) skip alignments with MAPQ below this, 0..255 (samtools view -q; "
+                        "255 passes any threshold) - default: 0")
+    p.add_argument("--requireFlags", dest="requireFlags", type=_flag_mask, default=0,
+                   help="(this build only; changes results) keep only alignments with all of these FLAG bits set (samtools view -f; "
+                        "decimal, or hex as 0x2) - default: 0")
+    p.add_argument("--excludeFlags", dest="excludeFlags", type=_flag_mask, default=0,
+                   help="(this build only; changes results) skip alignments with any of these FLAG bits set (samtools view -F, "
+                        "e.g. 0x900: secondary and supplementary) - default: 0")
 
 
 def _engine_flags(p):
@@ -130,6 +151,13 @@ def main(argv=None):
         parser.error("--gene requires --annotationFile and --maxIntronSize")
     elif command in ("process", "combine", "combineShallow", "junctions") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
+    if command in ("process", "combine", "combineShallow", "junctions"):
+        if not 0 <= kwargs["minMapQ"] <= 255:
+            parser.error("--minMapQ must be in 0..255")
+        if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
+            parser.error("--requireFlags / --excludeFlags must be in 0..65535")
+        if kwargs["requireFlags"] & kwargs["excludeFlags"]:
+            parser.error("--requireFlags and --excludeFlags share a bit (0x%x): no read could pass" % (kwargs["requireFlags"] & kwargs["excludeFlags"]))
     if command == "process":
         if kwargs.get("inBed") is not None:
             given = [f for f, d in (("--minAnchor", "minAnchor"), ("--minIntron", "minIntron"), ("--maxIntron", "maxIntron")) if kwargs.get(d) is not None]

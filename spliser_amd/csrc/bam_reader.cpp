@@ -5,7 +5,8 @@
 // and only the three fields checkBam reads from each SAM line (flag, POS, CIGAR -- :434-437) are kept,
 // per reference sequence, as structure-of-arrays ready for spl_reads_upload().
 //
-// Like `samtools view` without -F/-q, no record is filtered by flag or MAPQ.  CIGARs of more than
+// Like `samtools view` without -F/-q, no record is filtered by flag or MAPQ -- unless the caller sets a filter
+// (spl_bam_set_filter: samtools' -q / -f / -F, the one predicate of spl_bam.h).  CIGARs of more than
 // 65535 ops stored in a CG:B,I tag behind an `<l_seq>S<rlen>N` placeholder are restored the way htslib's
 // bam_tag2cigar does, because that is what samtools would print.
 //
@@ -474,6 +475,8 @@ struct spl_bam {
     int err_code = 0;
     std::string error;
     int64_t n_records = 0;
+    spl_bam_filter filter = {0, 0, 0}; // which placed records are kept (spl_bam_set_filter; fixed once claim != 0)
+    int64_t dropped[2] = {0, 0};       // records the filter dropped: by their flags, by their MAPQ
     // ---- BAM-native arrays per reference, assembled on demand (spl_bam_reads) ----
     std::vector<RefFinal> refs_storage; // (never resized after the header: RefFinal is not copyable)
     std::vector<char> assembled;
@@ -494,7 +497,7 @@ struct spl_bam {
     std::vector<DevShare> dev_shares;
     // a decode in shares (spl_bam_share_plan): the plan, and what the shares' decoders have reported so far
     std::vector<spl_bam_share> shares;
-    struct ShareResult { bool reported = false, failed = false; void *handle = nullptr; void (*free_fn)(void *) = nullptr; std::vector<int64_t> first, n, max_end; int64_t n_records = 0; };
+    struct ShareResult { bool reported = false, failed = false; void *handle = nullptr; void (*free_fn)(void *) = nullptr; std::vector<int64_t> first, n, max_end; int64_t n_records = 0, dropped[2] = {0, 0}; };
     std::vector<ShareResult> share_results;
     bool shares_on_device = false;
     std::atomic<bool> cancel{false};       // spl_bam_cancel: whoever decodes stops at the next batch / window; nobody starts
@@ -541,8 +544,9 @@ inline const uint8_t *record_cigar(const uint8_t *r, uint32_t bs, size_t need, u
 // Extract the alignment records in [p, end); p MUST be a record boundary.  Stops at the last complete record and returns
 // the position reached (a record boundary).  Two walks: the first checks every record and sizes the parts, the second fills
 // arrays of exactly that size -- the bytes are in the caller's cache both times.
-const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, Arena &arena, std::vector<Part> &parts, int64_t &n_records,
-                               std::string &err, bool &fatal)
+// Records the filter does not keep are counted (dropped[0]: by flags, [1]: by MAPQ) and otherwise treated like records without a position.
+const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, const spl_bam_filter &filter, Arena &arena, std::vector<Part> &parts, int64_t &n_records,
+                               int64_t *dropped, std::string &err, bool &fatal)
 {
     struct Run { int32_t tid; size_t n, ops; const uint8_t *begin; };
     Run few[4];
@@ -566,7 +570,9 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
         const size_t need = 32 + (size_t)l_name + 4ull * n_cig + ((size_t)l_seq + 1) / 2 + l_seq;
         if (need > bs) { err = "corrupt record (fields exceed block_size)"; fatal = true; break; }
         n_records++;
-        if (tid >= 0 && tid < n_ref && pos0 >= 0) {
+        const int verdict = tid >= 0 && tid < n_ref && pos0 >= 0 ? spl_bam_filter_verdict(filter, le16(r + 14), r[9]) : SPL_BAM_KEPT;
+        if (verdict != SPL_BAM_KEPT) dropped[verdict - 1]++;
+        else if (tid >= 0 && tid < n_ref && pos0 >= 0) {
             (void)record_cigar(r, bs, need, l_name, l_seq, n_cig);
             if (n_runs == 0 || run_at(n_runs - 1).tid != tid) {
                 const Run fresh = {tid, 0, 0, q};
@@ -598,7 +604,7 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
             __builtin_prefetch(q + 3 * (4 + (size_t)bs));
             const uint8_t *r = q + 4;
             const int32_t tid = le32s(r), pos0 = le32s(r + 4);
-            if (tid != run.tid || pos0 < 0) continue; // (an unplaced record inside the run)
+            if (tid != run.tid || pos0 < 0 || spl_bam_filter_verdict(filter, le16(r + 14), r[9]) != SPL_BAM_KEPT) continue; // (an unplaced or filtered record inside the run)
             const uint32_t l_name = r[8], l_seq = le32(r + 16);
             uint32_t n_cig = le16(r + 12);
             const size_t need = 32 + (size_t)l_name + 4ull * n_cig + ((size_t)l_seq + 1) / 2 + l_seq;
@@ -749,7 +755,7 @@ struct BatchOut {
     std::vector<uint8_t> head, tail;
     size_t len = 0, start = 0, i0 = 0, i1 = 0; // bytes inflated, guessed first boundary; the batch's blocks
     uint64_t u0 = 0;                            // offset of the batch in the inflated stream
-    int64_t nrec = 0;
+    int64_t nrec = 0, dropped[2] = {0, 0};
     bool inflate_bad = false, parse_bad = false;
     bool known = false;                         // the first boundary is the end of the BAM header, not a guess
     bool skip = false;                          // nothing but BAM header in it
@@ -761,6 +767,7 @@ void decode_worker(spl_bam *bam)
     const uint8_t *file = (const uint8_t *)bam->map;
     BlockDir &dir = bam->dir;
     const int n_ref = bam->n_refs;
+    const spl_bam_filter filter = bam->filter; // (nobody changes it once a decoder has the file)
     const NodeCpus node; // the NUMA node this thread runs on (the opening thread's, inherited): all worker threads stay there
     auto env_num = [](const char *name, long dflt) { const char *e = getenv(name); const long v = e ? atol(e) : 0; return v > 0 ? v : dflt; };
     const size_t BATCH = (size_t)env_num("SPL_BAM_BATCH_BLOCKS", 32);
@@ -846,7 +853,7 @@ void decode_worker(spl_bam *bam)
                 o.start = (size_t)(p - buf);
                 std::string err;
                 bool fatal = false;
-                reached = (size_t)(extract_records(p, end, n_ref, arena, o.parts, o.nrec, err, fatal) - buf);
+                reached = (size_t)(extract_records(p, end, n_ref, filter, arena, o.parts, o.nrec, o.dropped, err, fatal) - buf);
                 o.parse_bad = fatal;
                 if (!o.known) o.head.assign((const uint8_t *)buf, (const uint8_t *)buf + o.start);
                 o.tail.assign((const uint8_t *)buf + reached, end);
@@ -871,10 +878,12 @@ void decode_worker(spl_bam *bam)
     size_t n_resync = 0;
     auto walk = [&](const uint8_t *p0, const uint8_t *p1, bool &fatal) { // sequential, authoritative: commits what it parses
         std::vector<Part> seq;
-        int64_t n = 0;
-        const uint8_t *r = extract_records(p0, p1, n_ref, arena_mine, seq, n, fail, fatal);
+        int64_t n = 0, drop[2] = {0, 0};
+        const uint8_t *r = extract_records(p0, p1, n_ref, filter, arena_mine, seq, n, drop, fail, fatal);
         merge_parts(bam, seq);
         bam->n_records += n;
+        bam->dropped[0] += drop[0];
+        bam->dropped[1] += drop[1];
         return r;
     };
     size_t n_batches = 0;
@@ -932,6 +941,8 @@ void decode_worker(spl_bam *bam)
         } else if (accept) {
             merge_parts(bam, o.parts);
             bam->n_records += o.nrec;
+            bam->dropped[0] += o.dropped[0];
+            bam->dropped[1] += o.dropped[1];
             carry.swap(o.tail);
         } else { // the guess did not hold: this batch again, sequentially, from the known boundary
             ++n_resync;
@@ -949,6 +960,7 @@ void decode_worker(spl_bam *bam)
         o.head.clear();
         o.tail.clear();
         o.nrec = 0;
+        o.dropped[0] = o.dropped[1] = 0;
         const double c2 = now();
         t_merge += c2 - c1;
         o.state.store(0, std::memory_order_relaxed);
@@ -1099,6 +1111,38 @@ static int open_file(const char *path, int n_threads, bool start_now, spl_bam **
 
 extern "C" int spl_bam_open_stream(const char *path, int n_threads, spl_bam **out) { return open_file(path, n_threads, true, out); }
 extern "C" int spl_bam_open_deferred(const char *path, int n_threads, spl_bam **out) { return open_file(path, n_threads, false, out); }
+
+// Which placed records the decode keeps (spl_bam.h: spl_bam_filter_verdict).  Only while nobody decodes the file or waits for it.
+extern "C" int spl_bam_set_filter(spl_bam *bam, int min_mapq, int require_flags, int exclude_flags)
+{
+    if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_filter: null argument");
+    if (min_mapq < 0 || min_mapq > 255) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_filter: min_mapq %d is not in 0..255", min_mapq);
+    if (require_flags < 0 || require_flags > 65535 || exclude_flags < 0 || exclude_flags > 65535)
+        return spl_set_error(SPL_ERR_ARG, "spl_bam_set_filter: flag masks must be in 0..65535");
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (bam->claim != 0 || bam->done)
+        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_filter: the file is being decoded (or waited for) already", bam->path.c_str());
+    bam->filter = spl_bam_filter{(uint32_t)min_mapq, (uint32_t)require_flags, (uint32_t)exclude_flags};
+    return SPL_OK;
+}
+
+spl_bam_filter spl_bam_get_filter(spl_bam *bam)
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    return bam->filter;
+}
+
+// The records the filter dropped, by flags and by MAPQ: waits for the end of the decode, like spl_bam_n_records.
+extern "C" int spl_bam_filter_counts(spl_bam *bam, int64_t *out2)
+{
+    if (!bam || !out2) return spl_set_error(SPL_ERR_ARG, "spl_bam_filter_counts: null argument");
+    (void)spl_bam_start_host(bam);
+    std::unique_lock<std::mutex> lock(bam->mu);
+    bam->cv.wait(lock, [&]() { return bam->done; });
+    out2[0] = bam->dropped[0];
+    out2[1] = bam->dropped[1];
+    return SPL_OK;
+}
 
 // (call with bam->mu held) nobody will decode a file that is being closed: whoever waits is told so
 static bool cancelled_locked(spl_bam *bam)
@@ -1293,7 +1337,7 @@ uint64_t spl_bam_header_end(const spl_bam *bam) { return bam->header_bytes; }
 int spl_bam_thread_count(const spl_bam *bam) { return bam->n_threads; }
 
 int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar, const int64_t *ref_first, const int64_t *ref_n,
-                  const int64_t *ref_max_end, int64_t n_records_total)
+                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped)
 {
     std::lock_guard<std::mutex> lock(bam->mu);
     if (bam->claim != 1) return spl_set_error(SPL_ERR_ARG, "spl_bam_adopt: the file is not claimed by the device decoder");
@@ -1321,6 +1365,8 @@ int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off,
         bam->ref_max_end[(size_t)t] = ref_max_end[t];
     }
     bam->n_records = n_records_total;
+    bam->dropped[0] = dropped[0];
+    bam->dropped[1] = dropped[1];
     bam->max_tid_seen = bam->n_refs - 1;
     bam->complete_upto = bam->n_refs;
     bam->done = true;
@@ -1532,8 +1578,10 @@ extern "C" int spl_bam_share_count_host(spl_bam *bam, int k, int64_t *per_tid)
         const uint8_t *c = buf.data() + (size_t)(u - u0);
         const uint32_t bs = le32(c);
         if (bs < 32) return spl_set_error(SPL_ERR_FORMAT, "%s: share %d: corrupt record", bam->path.c_str(), k);
-        const int32_t tid = le32s(c + 4);
-        per_tid[tid < 0 || tid >= bam->n_refs ? bam->n_refs : tid]++;
+        const int32_t tid = le32s(c + 4), pos0 = le32s(c + 8);
+        const bool placed = tid >= 0 && tid < bam->n_refs && pos0 >= 0;
+        if (!placed || spl_bam_filter_verdict(bam->filter, le16(c + 18), c[13]) == SPL_BAM_KEPT) // (a filter's records are nobody's: spl_bam_filter_counts)
+            per_tid[tid < 0 || tid >= bam->n_refs ? bam->n_refs : tid]++;
         u += 4ull + bs;
     }
     if (u != sh.u_hi) return spl_set_error(SPL_ERR_FORMAT, "%s: share %d: the walk from %llu arrives at %llu, not at the next share's first record %llu", bam->path.c_str(), k,
@@ -1550,7 +1598,7 @@ int spl_bam_share_get(spl_bam *bam, int k, spl_bam_share *out)
 }
 
 int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *), const int64_t *ref_first, const int64_t *ref_n,
-                       const int64_t *ref_max_end, int64_t n_records, int failed)
+                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, int failed)
 {
     std::unique_lock<std::mutex> lock(bam->mu);
     if (k < 0 || (size_t)k >= bam->share_results.size() || bam->share_results[(size_t)k].reported) {
@@ -1565,6 +1613,8 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
     r.free_fn = free_fn;
     r.n_records = n_records;
     if (!r.failed) {
+        r.dropped[0] = dropped[0];
+        r.dropped[1] = dropped[1];
         r.first.assign(ref_first, ref_first + bam->n_refs);
         r.n.assign(ref_n, ref_n + bam->n_refs);
         r.max_end.assign(ref_max_end, ref_max_end + bam->n_refs);
@@ -1595,7 +1645,7 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
         return SPL_OK;
     }
     bam->lazy = true;
-    int64_t n_all = 0;
+    int64_t n_all = 0, drop[2] = {0, 0};
     for (size_t s = 0; s < bam->share_results.size(); ++s) {
         spl_bam::ShareResult &x = bam->share_results[s];
         spl_bam::DevShare d;
@@ -1603,6 +1653,8 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
         x.handle = nullptr;
         bam->dev_shares.push_back(d);
         n_all += x.n_records;
+        drop[0] += x.dropped[0];
+        drop[1] += x.dropped[1];
         for (int t = 0; t < bam->n_refs; ++t) { // (a reference may have a part in several shares: file order = share order)
             if (x.n[(size_t)t] <= 0) continue;
             PendingPart *pp = new PendingPart();
@@ -1617,6 +1669,8 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
         }
     }
     bam->n_records = n_all;
+    bam->dropped[0] = drop[0];
+    bam->dropped[1] = drop[1];
     bam->max_tid_seen = bam->n_refs - 1;
     bam->complete_upto = bam->n_refs;
     bam->shares_on_device = true;

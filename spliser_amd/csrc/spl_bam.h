@@ -5,6 +5,27 @@
 #include "../../include/spliser.h"
 #include "spl_pack.h"
 
+// ---- read filters (spl_bam_set_filter): samtools view's -q / -f / -F ---------------------------------------------------
+// THE definition of which records a filter keeps: the host decoder (bam_reader.cpp) and the device's scan and walking extraction
+// (spl_inflate.hip) all call this and nothing else.  A record that has a reference and a position is kept when none of its flag
+// bits is excluded, all required ones are set, and its MAPQ -- a number: 255 passes every threshold, as in samtools -- is
+// at least min_mapq.  All zero keeps every record.
+struct spl_bam_filter { uint32_t min_mapq, require_flags, exclude_flags; };
+#if defined(__HIPCC__)
+#define SPL_BAM_HD __host__ __device__
+#else
+#define SPL_BAM_HD
+#endif
+#define SPL_BAM_KEPT 0
+#define SPL_BAM_DROP_FLAGS 1 // (flags are tested first: a record that fails both ways counts here)
+#define SPL_BAM_DROP_MAPQ 2
+SPL_BAM_HD inline int spl_bam_filter_verdict(const spl_bam_filter &f, uint32_t flag, uint32_t mapq)
+{
+    if ((flag & f.exclude_flags) != 0u || (flag & f.require_flags) != f.require_flags) return SPL_BAM_DROP_FLAGS;
+    return mapq >= f.min_mapq ? SPL_BAM_KEPT : SPL_BAM_DROP_MAPQ;
+}
+spl_bam_filter spl_bam_get_filter(spl_bam *bam);           // what the file's decoders are to apply (fixed once a decode has begun)
+
 // The reads of reference `tid` as a packer source: the decoder's own parts, in file order, nothing copied.  Waits until the
 // reference is complete (spl_bam_wait_ref).  The views stay valid until spl_bam_release_ref(tid) or spl_bam_close.
 int spl_bam_source(spl_bam *bam, int tid, splpack::Source *out, int64_t *max_end_out);
@@ -26,8 +47,9 @@ int spl_bam_thread_count(const spl_bam *bam);
 bool spl_bam_sample_density(spl_bam *bam, size_t b_lo, size_t b_hi, uint64_t *n_rec_out, uint64_t *n_ops_out, uint64_t *n_bytes_out);
 // The placed records of the whole file in file order as four malloc'ed arrays (the file takes them over and frees them with
 // free()); reference t has records [ref_first[t], ref_first[t] + ref_n[t]), cig_off holds n_total + 1 offsets into cigar.
+// dropped[2]: the records the file's filter dropped by their flags / by their MAPQ (spl_bam_filter_counts).
 int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar, const int64_t *ref_first, const int64_t *ref_n,
-                  const int64_t *ref_max_end, int64_t n_records_total);
+                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped);
 // what the device decoder keeps in device memory for the device packer: an opaque handle, freed with the file
 void spl_bam_set_device_reads(spl_bam *bam, void *handle, void (*free_fn)(void *));
 void *spl_bam_device_reads(spl_bam *bam, int tid);          // the handle that holds ALL of reference `tid` (null: none does -- no device decode, or the reference lies in several shares)
@@ -47,7 +69,7 @@ int spl_bam_share_get(spl_bam *bam, int k, spl_bam_share *out);
 // A share's decoder is done: `handle` holds its records (share-local first record per reference in ref_first), or failed != 0.
 // When the last share has reported the file is complete -- or, if one failed, everything is dropped and the host threads decode.
 int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *), const int64_t *ref_first, const int64_t *ref_n,
-                       const int64_t *ref_max_end, int64_t n_records, int failed);
+                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, int failed);
 int spl_bam_shares_on_device(spl_bam *bam);
 bool spl_bam_cancelled(const spl_bam *bam);                   // spl_bam_cancel was called: stop at the next window                  // 1: all shares reported and none failed
 // spl_bam_adopt with null arrays = the reads stay on the device; `fetch(handle, ...)` brings malloc'ed host copies when a host-side

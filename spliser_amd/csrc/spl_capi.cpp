@@ -1332,7 +1332,7 @@ static int add_segment_device(spl_ctx *c, spl_dreads *d, DeviceReads *dev, int64
 // that straddles two windows: the bytes from the first block that is not done with to the window's end are copied in front of the
 // next window's buffer (its head room), so that scan and extraction see them in one piece; the blocks are not inflated twice.
 namespace {
-struct ShareOut { DeviceReads *reads = nullptr; int64_t n_all = 0; bool to_host = false; bool more_tokens = false; };
+struct ShareOut { DeviceReads *reads = nullptr; int64_t n_all = 0, dropped[2] = {0, 0}; bool to_host = false; bool more_tokens = false; }; // (dropped: by the read filter -- flags, MAPQ)
 // What the caller of decode_share does with the share's reads, called by decode_share itself as its LAST act before it gives its
 // buffers, streams and events back -- which takes 10 ms for a large file, and whoever waits for the file's references need not.
 typedef std::function<int(ShareOut &)> Publish;
@@ -1351,7 +1351,7 @@ extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_ou
         DeviceReads *keep = res.reads;
         spl_bam_set_device_reads(bam, keep, free_device_reads);
         spl_bam_set_fetch(bam, fetch_device_reads);
-        const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.n_all);
+        const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.n_all, res.dropped);
         if (rc) spl_bam_set_device_reads(bam, nullptr, nullptr);
         if (rc == SPL_OK && on_device_out) *on_device_out = 1;
         t_pub = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
@@ -1382,7 +1382,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     ShareOut res;
     const Publish report = [&](ShareOut &res) -> int { // (a share that is done: reported at once, the last one to report completes the file)
         spl_bam_set_fetch(bam, fetch_device_reads);
-        const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.n_all, 0);
+        const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.n_all, res.dropped, 0);
         if (rc2 == SPL_OK && on_device_out) *on_device_out = 1;
         return rc2;
     };
@@ -1390,7 +1390,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     if (rc == SPL_OK && res.more_tokens) { res = ShareOut(); rc = decode_share(c, bam, &sh, res, report, true); }
     if (res.reads) return rc; // (reported: decode_share publishes the reads it has made, whatever publishing returned)
     if (getenv("SPL_BAM_TIMING")) fprintf(stderr, "[spl_bam_decode_device] share %d not done on its device (%s)\n", k, rc ? spl_last_error() : "handed to the host");
-    return spl_bam_share_done(bam, k, nullptr, free_device_reads, nullptr, nullptr, nullptr, res.n_all, 1);
+    return spl_bam_share_done(bam, k, nullptr, free_device_reads, nullptr, nullptr, nullptr, res.n_all, res.dropped, 1);
 }
 
 namespace {
@@ -1502,6 +1502,7 @@ struct ShareDecode {
     size_t fsize = 0;
     const uint8_t *const image = spl_bam_image(bam, &fsize);
     const int n_ref = spl_bam_n_ref(bam);
+    const spl_bam_filter filter = spl_bam_get_filter(bam); // (the file is claimed: nobody changes it now)
     // ---- everything the streams touch is declared before them
     DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds;
     std::vector<spl_zblock> blocks, blocks0; // (blocks0: the early windows', for their launches before the directory is complete)
@@ -1560,7 +1561,7 @@ struct ShareDecode {
     uint32_t bounds_cap = 0;
     uint64_t H = 0, expect = 0;
     size_t first = 0; // the first block that holds more than BAM header
-    int64_t n_all = 0;
+    int64_t n_all = 0, n_drop_flags = 0, n_drop_mapq = 0;
     int32_t last_tid = -1;
     size_t carry = 0;               // the first block whose records are not all extracted yet
     size_t launched = 0, copying = 0; // windows whose decoding / whose copying kernel has been put on its stream
@@ -2130,7 +2131,7 @@ struct ShareDecode {
         if (b1s > s0) {
             splprof::Scope p("spl_bam_scan_kernel", pipe.b, (double)(blocks[b1s - 1].out + blocks[b1s - 1].out_len - blocks[s0].out));
             HIP_TRY((hipError_t)spl_dev_launch_bam_scan(stream0, win_end, H, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)(b1s - s0), d_scan.as<spl_bscan>() + s0,
-                                                        more ? 1 : 0, with_recs ? d_recs.as<uint16_t>() : nullptr, pipe.b));
+                                                        more ? 1 : 0, with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags, pipe.b));
         }
         HIP_TRY(hipMemcpyAsync(status.get() + b0, d_status.as<uint32_t>() + b0, 4 * (size_t)nb, hipMemcpyDeviceToHost, pipe.b));
         if (b1s > s0) HIP_TRY(hipMemcpyAsync(scan.get() + s0, d_scan.as<spl_bscan>() + s0, sizeof(spl_bscan) * (b1s - s0), hipMemcpyDeviceToHost, pipe.b));
@@ -2179,6 +2180,8 @@ struct ShareDecode {
             if (sc.n_placed) last_tid = sc.tid_last;
             expect = sc.reached;
             n_all += sc.n_all;
+            n_drop_flags += sc.n_drop_flags;
+            n_drop_mapq += sc.n_drop_mapq;
             rec_off[b + 1] = rec_off[b] + sc.n_placed;
             op_off[b + 1] = op_off[b] + sc.n_ops;
         }
@@ -2205,7 +2208,7 @@ struct ShareDecode {
             HIP_TRY((hipError_t)spl_dev_launch_bam_extract(stream0, win_end, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)nd, d_scan.as<spl_bscan>() + s0,
                                                            d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, d_pos.as<int32_t>(), d_flag.as<uint16_t>(),
                                                            d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), d_tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
-                                                           with_recs ? d_recs.as<uint16_t>() : nullptr, pipe.b));
+                                                           with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags, pipe.b));
         }
         if (b_done < b1s && k + 1 < n_win) // what is left of this window: in front of the next one's bytes
             HIP_TRY(hipMemcpyAsync(stream0_of(k + 1) + blocks[b_done].out, stream0 + blocks[b_done].out, (size_t)(win_end - blocks[b_done].out), hipMemcpyDeviceToDevice, pipe.b));
@@ -2257,6 +2260,8 @@ struct ShareDecode {
         d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = nullptr; // (the caller owns them from here)
         res.reads = keep;
         res.n_all = n_all;
+        res.dropped[0] = n_drop_flags;
+        res.dropped[1] = n_drop_mapq;
         if (timing) fprintf(stderr, "[spl_bam_decode_device] device %d: blocks %zu..%zu, %.1f MB -> %.1f MB inflated in %zu window%s, %llu placed records of %lld: %.4f s\n", c->device, lo, hi,
                             n_bytes / 1e6, (stream_len - stream_begin) / 1e6, n_win, n_win == 1 ? "" : "s", (unsigned long long)n_rec, (long long)n_all, host_now() - t_begin);
         if (timing) {

@@ -62,6 +62,8 @@ struct spl_bscan {
     int32_t tid_first, tid_last; // of the placed records (tid_first = -1: none)
     uint32_t n_foreign;  // records starting in the block that belong to references outside [tid_lo, tid_hi): another device's
     uint32_t n_foreign_hi; // ... of those, the ones of references at or behind tid_hi (the others lie in front of tid_lo)
+    uint32_t n_drop_flags; // records that would be placed but for the read filter: dropped by their flags ...
+    uint32_t n_drop_mapq;  // ... or, their flags passing, by their MAPQ (counted in n_all, in none of n_placed, n_ops, tid_first / tid_last)
 };
 #define SPL_BS_CORRUPT 1u     // a record that contradicts itself (block_size < 32, fields beyond block_size, stream ends inside it)
 #define SPL_BS_NEEDS_HOST 2u  // a CIGAR parked in a CG tag (more than 65535 ops): the host decoder's business
@@ -79,14 +81,17 @@ extern "C" {
 // decodes a stretch of the file takes the references that begin there.
 // recs (or null): n_blocks x SPL_BS_REC_CAP 16-bit places; block b's entry j = where its j-th placed record begins, counted from
 // the block's first byte -- what lets the extraction take a block's records 64 at a time instead of walking them.
+// min_mapq, require_flags, exclude_flags: the file's read filter (spl_bam.h: spl_bam_filter_verdict; 0, 0, 0 keeps every record) --
+// the same three values go to the extraction, whose walking kernel decides about every record again.
 int spl_dev_launch_bam_scan(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks,
-                            uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, void *stream_handle);
+                            uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *stream_handle);
 // rec_off[b] / op_off[b]: index of the block's first placed record / first op in the output arrays.  cig_off gets n + 1 entries
 // (the caller sets entry 0); ref_max_end[tid] = largest last base of a read of the reference (atomicMax; zero it first).
 // recs: what the scan of THESE blocks (same first block, same order) left, or null: then a lane walks its block's records.
 int spl_dev_launch_bam_extract(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
                                const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar,
-                               int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, void *stream_handle);
+                               int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags,
+                               void *stream_handle);
 // where the reference id changes along the placed records: (index of the first record of a run, its tid) pairs, unordered
 int spl_dev_launch_bam_bounds(const int32_t *tid, const uint32_t *cig_off, uint64_t n, uint64_t *bounds, uint32_t *n_bounds, uint32_t cap, void *stream_handle);
 // image: the whole file in device memory, readable SPL_Z_IMAGE_PAD bytes past its end; out: writable 16 bytes past the last block.

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "spl_inflate.h"
+#include "spl_bam.h"
 #include "spl_wave.h"
 #include "spl_inflate_wave.h"
 #include "spl_crc.h"
@@ -114,8 +115,10 @@ __device__ __forceinline__ bool plausible_record(const uint8_t *c, const uint8_t
 
 // `stream_len` = where the inflated bytes end: the stream's end, or (more != 0) the end of the window that is inflated at the
 // moment -- a record that runs past it is then no damage but something for the next window (SPL_BS_INCOMPLETE).
+// `filter`: a record it does not keep (spl_bam.h) is counted and otherwise not placed -- what the extraction leaves is what it would
+// leave for a file without those records; the order of references (SPL_BS_UNSORTED) is the file's, and judged over all records.
 __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi,
-                                                           const spl_zblock *blocks, uint32_t n_blocks, spl_bscan *scan, uint32_t more, uint16_t *recs)
+                                                           const spl_zblock *blocks, uint32_t n_blocks, spl_bscan *scan, uint32_t more, uint16_t *recs, spl_bam_filter filter)
 {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_blocks) return;
@@ -126,6 +129,7 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
     out.start = out.reached = u1;
     out.n_all = out.n_placed = out.n_ops = 0;
     out.n_foreign = out.n_foreign_hi = 0;
+    out.n_drop_flags = out.n_drop_mapq = 0;
     out.flags = 0;
     out.tid_first = out.tid_last = -1;
     if (u1 <= header_end && !(u1 == header_end && u0 == u1)) { // BAM header bytes only (or an empty block inside them)
@@ -169,7 +173,8 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
         if (stream_len - at < 4ull + bs) { out.flags |= more ? SPL_BS_INCOMPLETE : SPL_BS_CORRUPT; break; }
         const uint8_t *r = stream + at + 4;
         const int32_t tid = (int32_t)ld32(r), pos0 = (int32_t)ld32(r + 4);
-        const uint32_t l_name = r[8], n_cig = ld16(r + 12), l_seq = ld32(r + 16);
+        const uint32_t w8 = ld32(r + 8), w12 = ld32(r + 12), l_seq = ld32(r + 16); // (l_name | MAPQ << 8 | bin << 16, n_cigar_op | FLAG << 16: two words, where the filter's fields come for nothing)
+        const uint32_t l_name = w8 & 0xffu, mapq = (w8 >> 8) & 0xffu, n_cig = w12 & 0xffffu, flag = w12 >> 16;
         const uint64_t need = 32ull + l_name + 4ull * n_cig + ((uint64_t)l_seq + 1ull) / 2ull + (uint64_t)l_seq;
         if (need > bs) { out.flags |= SPL_BS_CORRUPT; break; }
         const int32_t tid_eff = tid < 0 || tid >= n_ref ? n_ref : tid; // (records without a reference: behind all others)
@@ -177,7 +182,10 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
         last_tid = tid_eff;
         if (tid_eff < tid_lo || tid_eff >= tid_hi) { out.n_foreign++; out.n_foreign_hi += tid_eff >= tid_hi ? 1u : 0u; at += 4ull + bs; continue; }
         out.n_all++;
-        if (tid >= 0 && tid < n_ref && pos0 >= 0) {
+        const int verdict = tid >= 0 && tid < n_ref && pos0 >= 0 ? spl_bam_filter_verdict(filter, flag, mapq) : SPL_BAM_KEPT;
+        if (verdict == SPL_BAM_DROP_FLAGS) out.n_drop_flags++;
+        else if (verdict == SPL_BAM_DROP_MAPQ) out.n_drop_mapq++;
+        else if (tid >= 0 && tid < n_ref && pos0 >= 0) {
             if (n_cig > 0) {
                 const uint32_t op0 = ld32(r + 32 + l_name);
                 if ((op0 & 15u) == 4u && (op0 >> 4) == l_seq && bs > need) out.flags |= SPL_BS_NEEDS_HOST; // maybe a CG tag behind it
@@ -197,7 +205,7 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
 __global__ __launch_bounds__(64) void spl_bam_extract_kernel(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
                                                               const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out,
                                                               uint16_t *flag_out, uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out,
-                                                              unsigned long long *ref_max_end)
+                                                              unsigned long long *ref_max_end, spl_bam_filter filter)
 {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_blocks) return;
@@ -215,11 +223,11 @@ __global__ __launch_bounds__(64) void spl_bam_extract_kernel(const uint8_t *stre
     while (at < u1) {
         const uint32_t bs = h0.x;
         const int32_t tid = (int32_t)h0.y, pos0 = (int32_t)h0.z;
-        const uint32_t l_name = h0.w & 0xffu, n_cig = h1.x & 0xffffu, flag = h1.x >> 16;
+        const uint32_t l_name = h0.w & 0xffu, mapq = (h0.w >> 8) & 0xffu, n_cig = h1.x & 0xffffu, flag = h1.x >> 16;
         const uint8_t *cig = stream + at + 36 + l_name;
         at += 4ull + bs;
         if (at < u1) { __builtin_memcpy(&h0, stream + at, 16); __builtin_memcpy(&h1, stream + at + 16, 16); }
-        if (tid >= 0 && tid < n_ref && pos0 >= 0 && tid >= tid_lo && tid < tid_hi) {
+        if (tid >= 0 && tid < n_ref && pos0 >= 0 && tid >= tid_lo && tid < tid_hi && spl_bam_filter_verdict(filter, flag, mapq) == SPL_BAM_KEPT) { // (the scan's decision, made again)
             long long ref_len = 0;
             for (uint32_t k = 0; k < n_cig; ++k) {
                 const uint32_t op = ld32(cig + 4ull * k);
@@ -340,17 +348,18 @@ __global__ __launch_bounds__(256) void spl_bam_bounds_kernel(const int32_t *tid,
 }
 
 extern "C" int spl_dev_launch_bam_scan(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks,
-                                       uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, void *st)
+                                       uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *st)
 {
     if (n_blocks == 0) return 0;
     const uint32_t L = 8; // (blocks per wave: the kernel is lanes waiting for memory, a wave as slow as its slowest lane -- 1.1 ms per window of 49 152 blocks with 8, 1.7 with 64, 3.9 with 1)
-    hipLaunchKernelGGL(spl_bam_scan_kernel, dim3((n_blocks + L - 1u) / L), dim3(L), 0, (hipStream_t)st, stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, more ? 1u : 0u, recs);
+    hipLaunchKernelGGL(spl_bam_scan_kernel, dim3((n_blocks + L - 1u) / L), dim3(L), 0, (hipStream_t)st, stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, more ? 1u : 0u, recs,
+                       spl_bam_filter{min_mapq, require_flags, exclude_flags});
     return (int)hipGetLastError();
 }
 
 extern "C" int spl_dev_launch_bam_extract(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
                                           const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar,
-                                          int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, void *st)
+                                          int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *st)
 {
     if (n_blocks == 0) return 0;
     if (recs) { // (the scan of these very blocks has left the records' places: a wave per block)
@@ -360,7 +369,7 @@ extern "C" int spl_dev_launch_bam_extract(const uint8_t *stream, uint64_t stream
     }
     const uint32_t L = 64;
     hipLaunchKernelGGL(spl_bam_extract_kernel, dim3((n_blocks + L - 1u) / L), dim3(L), 0, (hipStream_t)st, stream, stream_len, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off,
-                       op_off, pos, flag, cig_off, cigar, tid, ref_max_end);
+                       op_off, pos, flag, cig_off, cigar, tid, ref_max_end, spl_bam_filter{min_mapq, require_flags, exclude_flags});
     return (int)hipGetLastError();
 }
 

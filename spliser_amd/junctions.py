@@ -131,18 +131,21 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
 
 
 def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=8, minIntron=70, maxIntron=500000,
-              qChrom="All", devices=(0,), threads=0, log=None):
-    """Writes ``outputPath`` (a BED12 file) and returns the number of junctions."""
+              qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0):
+    """Writes ``outputPath`` (a BED12 file) and returns the number of junctions.  ``minMapQ`` / ``requireFlags`` / ``excludeFlags``:
+    the read filter of ``process`` (samtools view's -q / -f / -F; changes results) -- the junctions of the reads that pass."""
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
     stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
     if isStranded and stranded == 0:
         raise ValueError("strandedType must be 'fr' or 'rf' for a stranded library")
-    source = _process.open_and_decode(inBAM, tuple(devices), None, threads)   # (on the GPU(s), like `process`)
+    filt = _process.read_filter(minMapQ, requireFlags, excludeFlags)
+    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, filt)   # (on the GPU(s), like `process`)
     try:
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
         tables = tables_of_source(source, tuple(devices), chroms, stranded, minAnchor, minIntron, maxIntron)
         if isinstance(source, native.BamFile) and not source.wait_all():
             raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
+        _process.log_filter(source, filt, log)
     finally:
         if hasattr(source, "close"):
             source.close()

@@ -50,7 +50,7 @@ EXPORTS = [
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
     "spl_soa_upload", "spl_soa_upload2", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
-    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
+    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_filter_counts", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
     "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
@@ -591,17 +591,44 @@ class BamFile(object):
     ``stream=True``: the constructor returns once the header is read and the decode goes on in the background; ``wait_ref``
     blocks until one reference is complete, ``DeviceReads.add_bam`` sends its reads to the GPU from the decoder's own buffers,
     ``wait_all`` ends the decode and tells whether the file was sorted by reference (if not, references taken early were
-    incomplete)."""
+    incomplete).
 
-    def __init__(self, path, threads=0, stream=False, defer=False):
+    ``min_mapq``, ``require_flags``, ``exclude_flags``: samtools view's -q / -f / -F (``spl_bam_set_filter``); a record that fails
+    them is never extracted, whoever decodes the file.  ``filter_counts`` says how many did."""
+
+    def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0):
         self._h = ctypes.c_void_p()
-        opener = lib().spl_bam_open_deferred if defer else (lib().spl_bam_open_stream if stream else lib().spl_bam_open)
+        self.filter = (int(min_mapq), int(require_flags), int(exclude_flags))
+        filtered = self.filter != (0, 0, 0)   # (the filter must be there before the decode starts: opened deferred, started below)
+        opener = lib().spl_bam_open_deferred if defer or filtered else (lib().spl_bam_open_stream if stream else lib().spl_bam_open)
         _check(opener(os.fsencode(path), ctypes.c_int(threads), ctypes.byref(self._h)))
+        if filtered:
+            try:
+                self.set_filter(*self.filter)
+                if not defer:
+                    _check(lib().spl_bam_start(self._h))
+                    if not stream:
+                        _check(lib().spl_bam_wait_all(self._h, None))
+            except Exception:
+                lib().spl_bam_close(self._h)
+                self._h = ctypes.c_void_p()
+                raise
         self.on_device = None    # (defer=True: set by decode_on_device)
         self.ref_names = [lib().spl_bam_ref_name(self._h, i).decode("ascii") for i in range(lib().spl_bam_n_ref(self._h))]
         self.ref_lengths = [lib().spl_bam_ref_length(self._h, i) for i in range(len(self.ref_names))]
         self._tid = {n: i for i, n in enumerate(self.ref_names)}
         self._views = {}
+
+    def set_filter(self, min_mapq=0, require_flags=0, exclude_flags=0):
+        """The read filter of a ``defer=True`` file nobody decodes yet (``spl_bam_set_filter``; an error afterwards)."""
+        _check(lib().spl_bam_set_filter(self._h, ctypes.c_int(int(min_mapq)), ctypes.c_int(int(require_flags)), ctypes.c_int(int(exclude_flags))))
+        self.filter = (int(min_mapq), int(require_flags), int(exclude_flags))
+
+    def filter_counts(self):
+        """-> (records dropped by their flags, records dropped by their MAPQ alone); waits for the end of the decode."""
+        out = (ctypes.c_int64 * 2)()
+        _check(lib().spl_bam_filter_counts(self._h, out))
+        return int(out[0]), int(out[1])
 
     def start_host_decode(self):
         """A file opened with ``defer=True``: decode on the host's threads, from now on in the background."""

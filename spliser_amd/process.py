@@ -27,26 +27,57 @@ def _log(msg):
     sys.stdout.flush()
 
 
+NO_FILTER = (0, 0, 0)
+
+
+def read_filter(minMapQ=0, requireFlags=0, excludeFlags=0):
+    """The read filter of a command (this build only; changes results), samtools view's -q / -f / -F: -> (min_mapq, require_flags,
+    exclude_flags), checked.  ``NO_FILTER`` keeps every record, as the reference does."""
+    f = (int(minMapQ or 0), int(requireFlags or 0), int(excludeFlags or 0))
+    if not 0 <= f[0] <= 255:
+        raise ValueError("minMapQ must be in 0..255")
+    if not (0 <= f[1] <= 65535 and 0 <= f[2] <= 65535):
+        raise ValueError("requireFlags / excludeFlags must be in 0..65535")
+    if f[1] & f[2]:
+        raise ValueError("requireFlags and excludeFlags share a bit (0x%x): no read could pass" % (f[1] & f[2]))
+    return f
+
+
+def log_filter(source, filt, log, name=None):
+    """One line once the decode is complete, when a filter is set: records seen, dropped by flags, dropped by MAPQ."""
+    if tuple(filt) == NO_FILTER or not hasattr(source, "filter_counts"):
+        return
+    by_flags, by_mapq = source.filter_counts()
+    log("  (read filter%s: minMapQ %d, requireFlags 0x%x, excludeFlags 0x%x: %d records seen, %d dropped by flags, %d dropped by MAPQ)"
+        % (" of " + name if name else "", filt[0], filt[1], filt[2], source.n_records, by_flags, by_mapq))
+
+
 class _SamSource(object):
     """Reads from SAM text (small inputs / fixtures)."""
 
-    def __init__(self, path):
-        self.ref_names, self._sets = samio.read_sam(path)
+    def __init__(self, path, min_mapq=0, require_flags=0, exclude_flags=0):
+        self._counts = [0, 0, 0]
+        self.ref_names, self._sets = samio.read_sam(path, min_mapq, require_flags, exclude_flags, counts=self._counts)
+        self.n_records = self._counts[0]
 
     def reads(self, chrom):
         return self._sets.get(chrom)
 
+    def filter_counts(self):
+        return self._counts[1], self._counts[2]
 
-def open_alignments(path, threads=0, stream=False, defer=False):
+
+def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER):
     """BAM (BGZF) through the native decoder; plain SAM text through the Python reader.  ``stream=True``: the BAM decoder
     returns after the header and decodes in the background (``native.BamFile``); ``defer=True``: nothing is decoded until
-    somebody asks (``BamFile.decode_on_device``, or the first wait: host threads)."""
+    somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``read_filter``: which records either keeps."""
     with open(path, "rb") as fh:
         magic = fh.read(4)
+    q, f, F = read_filter
     if magic[:2] == b"\x1f\x8b":
-        return native.BamFile(path, threads=threads, stream=stream, defer=defer)
+        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F)
     if magic[:1] == b"@" or b"\t" in open(path, "rb").readline():
-        return _SamSource(path)
+        return _SamSource(path, q, f, F)
     raise native.SpliserNativeError(-5, "%s is neither BGZF/BAM nor SAM text" % path)
 
 
@@ -63,11 +94,11 @@ def wait_deferred_close():
     return time.perf_counter() - t0
 
 
-def open_and_decode(path, devices, gpuDecode=None, threads=0):
+def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER):
     """The alignment file opened and its decode started: on the GPU(s) -- with several devices every one inflates and extracts
     the stretch of the file that holds its own references (``BamFile.decode_on_devices_async``), and counts them -- or, told so
-    (``gpuDecode=False``), on host threads.  SAM text has one reader."""
-    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False)
+    (``gpuDecode=False``), on host threads.  SAM text has one reader.  ``read_filter`` is with the source before any of them starts."""
+    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter)
     if isinstance(source, native.BamFile) and gpuDecode is not False:
         try:
             if len(devices) > 1:
@@ -438,7 +469,8 @@ def write_tsv(output_path, table, results, is_beta2_cryptic):
 
 def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
             isStranded=False, strandedType=None, isbeta2Cryptic=False, devices=(0,), threads=0, log=_log, checkJunctions=False,
-            gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False):
+            gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False,
+            minMapQ=0, requireFlags=0, excludeFlags=0):
     """SpliSER_v0_1_8.py:695-720, keyword-compatible with the reference's argparse dests.
 
     ``inBed=None`` (this build only): no junction file -- the junctions are taken from the reads themselves, in this call, from
@@ -459,9 +491,15 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
 
     ``keepReads`` (this build only; changes no result): also leave ``<outputPath>.SpliSER.reads`` -- flag, POS and CIGAR of every
     placed record, all ``checkBam`` reads of an alignment -- which ``combine`` takes instead of decoding the BAM again, as long
-    as it is still that BAM's (``readstore``)."""
+    as it is still that BAM's (``readstore``).
+
+    ``minMapQ`` / ``requireFlags`` / ``excludeFlags`` (this build only; these DO change results): samtools view's -q / -f / -F,
+    applied where the alignment file is decoded (``read_filter``; ``spl_bam_set_filter``) -- what the reference's pipelines run
+    samtools over the file for.  A read that fails is never counted, carries no junction (a run without ``inBed``,
+    ``checkJunctions``) and is not among the kept reads; the output is that of the same call on the pre-filtered file."""
     if outputPath is None:
         raise TypeError("process: outputPath is required")
+    filt = read_filter(minMapQ, requireFlags, excludeFlags)
     knobs = None
     if inBed is None:
         if checkJunctions:
@@ -476,7 +514,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     # The alignment file does not depend on Steps 0-2: it is decoded on native threads while the site table is built here, and
     # goes on decoding while Step 3 counts the chromosomes that are complete.  An unreadable file is an error here already
     # (block directory and header are read by the opening call).
-    source = open_and_decode(inBAM, devices, gpuDecode, threads)     # (the decode runs beside Steps 0-2, wherever it runs)
+    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt)     # (the decode runs beside Steps 0-2, wherever it runs)
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
@@ -513,6 +551,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
         if isinstance(source, native.BamFile) and gpuDecode is not False and source.decline_reason():
             # (said once, where the user reads it: the host's threads are several times slower than the device on files like this)
             log("  (the alignment file was decoded on host threads, not on the GPU: %s)" % source.decline_reason())
+        log_filter(source, filt, log)
         t3 = time.perf_counter()
         log("\nOutputting .tsv file")
         writer.close(list(results))
@@ -538,7 +577,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
                 t_keep = time.perf_counter()
                 kept = [(name, source.reads(name)) for name in source.ref_names]
                 t_down = time.perf_counter()
-                readstore.save(outputPath + readstore.SUFFIX, inBAM, [(name, rs) for name, rs in kept if rs is not None])
+                readstore.save(outputPath + readstore.SUFFIX, inBAM, [(name, rs) for name, rs in kept if rs is not None], read_filter=filt)
                 timings["keep_reads_s"] = time.perf_counter() - t_keep
                 if os.environ.get("SPL_PROCESS_TIMING"):
                     sys.stderr.write("[process] kept reads: down from the device %.4f s, written %.4f s\n" % (t_down - t_keep, time.perf_counter() - t_down))

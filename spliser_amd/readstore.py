@@ -6,7 +6,9 @@ The reference's ``combine`` goes back to a sample's BAM for every site the sampl
 reference, BAM-native (pos int32, flag uint16, cig_off uint32, cigar uint32: 18.8 bytes a 150 bp read, a fifth of the BAM),
 next to its ``.SpliSER.tsv``; ``combine`` takes them instead of the BAM WHEN THEY ARE THE BAM'S: the file is keyed by the BAM's
 size, its modification time and the CRC32 of its first and last 64 KiB, and anything else -- another BAM, a newer one, a
-truncated or foreign file -- is ignored and the BAM decoded as always.
+truncated or foreign file -- is ignored and the BAM decoded as always.  Reads kept under a read filter (``process --minMapQ`` /
+``--requireFlags`` / ``--excludeFlags``) are the filtered ones and say so (a ``filter`` key in the header, only then): they are
+taken by a caller that runs under the same filter and by no other.
 """
 import json
 import os
@@ -59,10 +61,16 @@ def bam_key(bam_path):
     return int(st.st_size), int(st.st_mtime_ns), crc & 0xFFFFFFFF
 
 
-def save(path, bam_path, reads_by_ref, threads=8):
+def _filter_dict(read_filter):
+    q, f, F = (int(v) for v in read_filter)
+    return {"min_mapq": q, "require_flags": f, "exclude_flags": F} if (q, f, F) != (0, 0, 0) else None
+
+
+def save(path, bam_path, reads_by_ref, threads=8, read_filter=(0, 0, 0)):
     """reads_by_ref: [(reference name, ReadSet)] in file order.  Written beside its final name and moved there whole; the arrays
     go out in pieces of 16 MB on a few threads (``os.pwrite`` leaves the interpreter's lock: one thread copies 4 GB/s into the
-    page cache, and a 20 M-read sample is 0.4 GB)."""
+    page cache, and a 20 M-read sample is 0.4 GB).  ``read_filter``: (min_mapq, require_flags, exclude_flags) the reads were
+    decoded under; noted in the header when it is one (a file of unfiltered reads is what it always was)."""
     from concurrent.futures import ThreadPoolExecutor
     import sys
     import time
@@ -71,8 +79,9 @@ def save(path, bam_path, reads_by_ref, threads=8):
     t_key = time.perf_counter()
     refs = [{"name": name, "n": int(rs.n), "ops": int(rs.cig_off[rs.n]) - int(rs.cig_off[0]) if rs.n else 0, "max_end": int(rs.max_end)}
             for name, rs in reads_by_ref]
-    head_of = lambda digest: json.dumps({"version": VERSION, "bam_size": size, "bam_mtime_ns": mtime_ns, "bam_crc32": crc, "payload_sum": digest,   # noqa: E731
-                                         "refs": refs}).encode("utf-8")
+    noted = _filter_dict(read_filter)
+    head_of = lambda digest: json.dumps(dict({"version": VERSION, "bam_size": size, "bam_mtime_ns": mtime_ns, "bam_crc32": crc, "payload_sum": digest,   # noqa: E731
+                                              "refs": refs}, **({"filter": noted} if noted else {}))).encode("utf-8")
     fixed = MAGIC + struct.pack("<II", VERSION, len(head_of("0" * 16))) + head_of("0" * 16)     # (its length does not depend on the digest)
     at = len(fixed) + (-len(fixed) % 64)
     jobs = []      # (file offset, contiguous array)
@@ -169,9 +178,9 @@ class ReadStore(object):
         self._mm = None
 
 
-def open_if_fresh(path, bam_path):
-    """-> ReadStore when ``path`` holds the reads of exactly this alignment file, None otherwise (missing, another version,
-    damaged, or the BAM has changed since)."""
+def open_if_fresh(path, bam_path, read_filter=(0, 0, 0)):
+    """-> ReadStore when ``path`` holds the reads of exactly this alignment file under exactly this read filter, None otherwise
+    (missing, another version, damaged, the BAM has changed since, or kept under another filter -- no ``filter`` key: none)."""
     if not path or not os.path.exists(path):
         return None
     try:
@@ -184,6 +193,8 @@ def open_if_fresh(path, bam_path):
                 return None
             head = json.loads(fh.read(head_len).decode("utf-8"))
             if (head.get("bam_size"), head.get("bam_mtime_ns"), head.get("bam_crc32")) != bam_key(bam_path):
+                return None
+            if head.get("filter") != _filter_dict(read_filter):
                 return None
             refs = head["refs"]
             if any(not isinstance(r.get("n"), int) or not isinstance(r.get("ops"), int) or r["n"] < 0 or r["ops"] < 0 for r in refs):

@@ -87,10 +87,13 @@ class ReadSet(object):
                    np.asarray(ops, np.int64))
 
 
-def read_sam(path):
-    """Parse SAM text -> (ref_names, {chrom: ReadSet}).  Keeps every record that has an RNAME, no flag
-    or MAPQ filtering, file order -- what ``samtools view`` (no -F/-q) would print."""
+def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None):
+    """Parse SAM text -> (ref_names, {chrom: ReadSet}).  Keeps every record that has an RNAME, file order -- what ``samtools
+    view`` would print; ``min_mapq`` / ``require_flags`` / ``exclude_flags`` are its -q / -f / -F on columns 5 and 2 (the BAM
+    decoder's rule, ``spl_bam_set_filter``: flags first, MAPQ as a number).  ``counts``: a list that gets [records seen, dropped
+    by flags, dropped by MAPQ] added to its three entries."""
     names, per = [], {}
+    seen = by_flags = by_mapq = 0
     with open(path, "r") as handle:
         for line in handle:
             if line.startswith("@"):
@@ -100,33 +103,57 @@ def read_sam(path):
                             names.append(field[3:])
                 continue
             cols = line.split("\t")
+            seen += 1
             if len(cols) < 6 or cols[2] == "*":
                 continue
+            flag = int(cols[1])
+            if int(cols[3]) >= 1:      # (a record without a position is nobody's to filter: the BAM decoder's rule)
+                if flag & exclude_flags or flag & require_flags != require_flags:
+                    by_flags += 1
+                    continue
+                if int(cols[4]) < min_mapq:
+                    by_mapq += 1
+                    continue
             rec = per.get(cols[2])
             if rec is None:
                 rec = per[cols[2]] = ([], [], [0], [])
                 if cols[2] not in names:
                     names.append(cols[2])
             rec[0].append(int(cols[3]))
-            rec[1].append(int(cols[1]))
+            rec[1].append(flag)
             rec[3].extend(cigar_ops(cols[5].strip()))
             rec[2].append(len(rec[3]))
     sets = {c: ReadSet(np.asarray(p, np.int64), np.asarray(f, np.int64), np.asarray(o, np.int64),
                        np.asarray(g, np.int64)) for c, (p, f, o, g) in per.items()}
+    if counts is not None:
+        for k, v in enumerate((seen, by_flags, by_mapq)):
+            counts[k] += v
     return names, sets
 
 
-def write_sam(path, ref_names, ref_lengths, chrom_reads):
-    """chrom_reads: list of (chrom, ReadSet) in file order."""
+def _mapq_of(mapq, k_chrom, rs):
+    """The MAPQ column of one entry of chrom_reads: 60 for every read, or the caller's array for that entry."""
+    if mapq is None:
+        return None
+    m = np.asarray(mapq[k_chrom])
+    if m.shape != (rs.n,) or (rs.n and (int(m.min()) < 0 or int(m.max()) > 255)):
+        raise ValueError("mapq: one value in 0..255 per read of every entry of chrom_reads")
+    return m
+
+
+def write_sam(path, ref_names, ref_lengths, chrom_reads, mapq=None):
+    """chrom_reads: list of (chrom, ReadSet) in file order.  mapq: per entry of chrom_reads an array of the reads' MAPQ (default:
+    60 for every read)."""
     with open(path, "w") as fh:
         fh.write("@HD\tVN:1.6\tSO:coordinate\n")
         for n, ln in zip(ref_names, ref_lengths):
             fh.write("@SQ\tSN:%s\tLN:%d\n" % (n, ln))
         i = 0
-        for chrom, rs in chrom_reads:
+        for k_chrom, (chrom, rs) in enumerate(chrom_reads):
+            mq = _mapq_of(mapq, k_chrom, rs)
             for k in range(rs.n):
                 ops = rs.cigar[rs.cig_off[k]:rs.cig_off[k + 1]]
-                fh.write("r%d\t%d\t%s\t%d\t60\t%s\t*\t0\t0\t*\t*\n" % (i, rs.flag[k], chrom, rs.pos[k], cigar_string(ops)))
+                fh.write("r%d\t%d\t%s\t%d\t%d\t%s\t*\t0\t0\t*\t*\n" % (i, rs.flag[k], chrom, rs.pos[k], 60 if mq is None else mq[k], cigar_string(ops)))
                 i += 1
 
 
@@ -162,13 +189,14 @@ def _reg2bin(beg, end):
     return 0
 
 
-def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False, unplaced=0, long_cigar_tag=False):
+def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False, unplaced=0, long_cigar_tag=False, mapq=None):
     """Write a BAM file.  chrom_reads: list of (chrom, ReadSet) in file order.
 
     with_seq       -- emit a dummy SEQ/QUAL of the query length (realistic record size) instead of '*'
     unplaced       -- append this many records without a reference (tid -1) at the end
     long_cigar_tag -- store every CIGAR with more than 3 ops the way htslib stores >65535-op CIGARs:
                       a placeholder ``<qlen>S<rlen>N`` in the record and the real ops in a CG:B,I tag
+    mapq           -- per entry of chrom_reads an array of the reads' MAPQ (default: 60 for every read)
     """
     tid_of = {n: i for i, n in enumerate(ref_names)}
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, ln) for n, ln in zip(ref_names, ref_lengths))
@@ -185,8 +213,9 @@ def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False
                 del buf[:_BGZF_BLOCK]
 
         serial = 0
-        for chrom, rs in chrom_reads:
+        for k_chrom, (chrom, rs) in enumerate(chrom_reads):
             tid = tid_of[chrom]
+            mq = _mapq_of(mapq, k_chrom, rs)
             for k in range(rs.n):
                 ops = [int(o) for o in rs.cigar[rs.cig_off[k]:rs.cig_off[k + 1]]]
                 qlen = sum(o >> 4 for o in ops if (o & 15) in (0, 1, 4, 7, 8))
@@ -205,7 +234,7 @@ def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False
                 qual = bytes([30]) * l_seq
                 flag = int(rs.flag[k])
                 end0 = pos0 + (rlen if (rlen and not flag & 4) else 1)
-                body = struct.pack("<iiBBHHHiiii", tid, pos0, len(name), 60, _reg2bin(pos0, end0), len(rec_ops), flag,
+                body = struct.pack("<iiBBHHHiiii", tid, pos0, len(name), 60 if mq is None else int(mq[k]), _reg2bin(pos0, end0), len(rec_ops), flag,
                                    l_seq, -1, -1, 0) + name + struct.pack("<%dI" % len(rec_ops), *rec_ops) + seq + qual + tags
                 buf += struct.pack("<i", len(body)) + body
                 if len(buf) >= _BGZF_BLOCK:
