@@ -32,15 +32,18 @@
 #define SPL_WAVE_ITERS 10
 #endif
 #define SPL_WAVE_READS (64 * SPL_WAVE_ITERS)
-#define SPL_TILE_FUSED_SHIFT 10           // reads per tile of a fused pass: the records of 1024 reads are 24.8 KB of LDS at most
+#define SPL_TILE_FUSED_SHIFT 10           // reads per tile of a fused pass: the stage of 1024 reads' ops is 16 KB of LDS
 #define SPL_TILE_FUSED (1 << SPL_TILE_FUSED_SHIFT)
 #define SPL_BLOCK_FUSED 256              // threads of its workgroups: four reads of a tile a thread (512 threads, two reads each, eight
                                          // waves to count a tile: 1.25 ms a launch against 0.94 -- what a wave does per tile whatever its
                                          // share of it is what the pass spends its instructions on)
-#define SPL_WAVE_READS_FUSED 512         // a wave's list entries there (4 workgroups of 39 KB on a CU)
+#define SPL_WAVE_READS_FUSED 512         // a wave's list entries there
+#define SPL_REC_BYTES_FUSED 16448        // LDS for a tile's ops, then for the records of its reads that are not simple ones (those are counted from
+                                         // registers): 16 KB + the slack behind a run's last record.  A tile that needs more is taken in halves.
+                                         // 30.1 KB of LDS a workgroup with the windows, the lists and s_idx: 5 workgroups a CU
 #define SPL_WIN 1020                     // distinct site positions a workgroup privatises in LDS (pair kernel; range kernel unstranded)
 #define SPL_WIN_STRANDED 956             // ... range kernel, stranded: 4 windows + the lists, 8 workgroups in 160 KB
-#define SPL_WIN_STRANDED_FUSED 508       // ... the fused pass, stranded: 4 windows of 2 KB beside a tile's records, 4 workgroups in 160 KB
+#define SPL_WIN_STRANDED_FUSED 508       // ... the fused pass, stranded: 4 windows of 2 KB beside a tile's records, 5 workgroups in 160 KB
 #define SPL_SERIAL_MAX 8                 // pair kernel: sites a lane classifies alone before the wave takes over
 #ifndef SPL_AGG_ROUNDS
 #define SPL_AGG_ROUNDS 2                 // distinct addresses agg_add merges across the wave before it falls back to plain atomics

@@ -476,6 +476,58 @@ __device__ __forceinline__ void commit_range(const spl_hot_params &p, spl_lds_i3
     }
 }
 
+// A bucket entry's first two words (all a boundary needs that is no junction end) at a 32-bit byte offset from the table's base:
+// see dbk_at in spl_count_ranges_kernel.
+__device__ __forceinline__ spl_dbk dbk_load2(const spl_hot_params &p, uint32_t s)
+{
+    typedef __attribute__((address_space(1))) const uint32_t gdw;
+    gdw *q = (gdw *)((__attribute__((address_space(1))) const char *)p.dbucket + (size_t)((s << 3) + (s << 2)));
+    spl_dbk e; e.first = q[0]; e.occ = q[1]; e.rival = 0u;
+    return e;
+}
+
+// The fused pass's simple reads (one aligned op, mapped, in range: run 0 of the classification), counted by the thread that
+// classified them, out of its registers (spl_layout_tile.h: tile_finish calls issue() for each of its reads right behind the
+// classification and commit() behind the ranks' barrier): two boundaries, one range, nothing else can happen -- such a read has
+// no record, no rank and no place in LDS.  A thread's 2 R bucket entries are asked for back to back and are on their way while
+// the other runs' prefix sums cross their barrier.  Slot j of a wave's threads is asked for, resolved and committed only if some
+// lane of the wave holds a simple read there (__any: wave-uniform), and only those lanes load.  Measured (profiles/
+// r08B_before_after.txt): with six reads in ten simple nearly every wave has one in every slot, so the gate saves 0.2 % of the
+// step and none of the fetched bytes over asking in every slot.  active = false (a tile taken in parts, whose simple reads were
+// counted when it was looked at in one piece): nothing is asked for or counted.
+template <bool STRANDED, int NARR, int WIN, int R>
+struct SimpleInPlace {
+    static constexpr bool in_place = true;
+    const spl_hot_params &p;
+    spl_lds_i32 *lds;
+    int32_t wbase, shift;
+    bool active;           // (workgroup-uniform)
+    spl_dbk e0[R], e1[R];  // (all that is kept from issue to commit: the record's words are the caller's, and still there)
+    __device__ __forceinline__ void issue(int j, bool is_simple, uint32_t w0, uint32_t w1)
+    {
+        if (!active || !__any(is_simple)) return; // (wave-uniform: a wave without a simple read in its slots j asks for nothing)
+        const int32_t a = (int32_t)w0 + shift, b = a + (int32_t)(w1 >> 16); // [a, b): the read's bases
+        e0[j] = e1[j] = spl_dbk{0u, 0u, 0u};
+        if (is_simple) { // (only the lanes that hold a simple read load: nothing is fetched for the others' slots)
+            e0[j] = dbk_load2(p, dbk_slot(p, a - 1));
+            e1[j] = dbk_load2(p, dbk_slot(p, b - 1));
+        }
+    }
+    __device__ __forceinline__ void commit(int j, bool is_simple, uint32_t w0, uint32_t w1)
+    {
+        if (!active || !__any(is_simple)) return; // (the same waves that asked)
+        const int32_t a = (int32_t)w0 + shift, b = a + (int32_t)(w1 >> 16);
+        int32_t ua, ub; uint32_t nva, nvb;
+        dbk_resolve(p, a - 1, e0[j], ua, nva);
+        dbk_resolve(p, b - 1, e1[j], ub, nvb);
+        const int32_t lo = ua + (int32_t)nva;
+        const bool emit = is_simple && ub > lo;
+        uint32_t arr = 0;
+        if (STRANDED) arr = (spl_read_strand(w1 & 0xffffu, p.stranded) == (uint8_t)'-') ? 1u : 0u;
+        if (__any(emit)) commit_range<NARR, WIN>(p, lds, wbase, emit, lo, ub, arr);
+    }
+};
+
 // atomicAdd(addr, delta) with delta = +1 or -1, merged over the lanes of the wave that are executing it right now
 // and target the same word: one atomic per distinct address instead of one per lane.
 __device__ __forceinline__ void agg_add(uint32_t *addr, int32_t delta)
@@ -677,20 +729,25 @@ __device__ __forceinline__ bool rivals_inline2(const spl_hot_params &p, spl_lds_
 // tile's records itself with the layout kernel's code (spl_layout_tile.h: a thread's four reads, the tile's ops through LDS,
 // classification, ranks by prefix sums) but into LDS, where the ops were, and counts them from there with the code below: the
 // records -- 12.7 bytes a read written and read again, beside 18.7 of arrays -- never go to memory, and there is no layout
-// launch.  The difference windows, the lists' front parts and the window's base belong to the chunk, not the tile.  39 KB of
-// LDS, 96 VGPRs: four workgroups a CU -- a stranded pass with windows of 508 distinct positions instead of 956 (with 956, three
-// workgroups a CU: slower than layout + range; what lies outside a window goes to the global arrays either way).  A queue entry
+// launch.  The difference windows, the lists' front parts and the window's base belong to the chunk, not the tile.  A queue entry
 // names its read by its place in the arrays (s_idx), which is where the literal kernel then reads it.
-// Measured (human-scale, 100 M reads a launch): 0.94-0.98 ms against 0.655-0.67 + 0.375-0.39 for layout + range.  Asking for the next
-// tile's reads before this tile is counted gained nothing (a wave's memory operations return in order: the first bucket entry
-// waits for them), 512 threads -- two reads each, eight waves counting a tile -- took 1.25 ms: profiles/r05X_fused_pass.txt.
+// Round 8: a SIMPLE read (run 0) has no record -- the thread that classified it counts it from its registers (SimpleInPlace: the
+// bucket entries asked for behind the classification, resolved and committed behind the ranks' barrier), so s_rec holds runs 1 .. 3
+// only: 16 KB, the ops' stage; a tile that needs more is taken in two halves.  30.1 KB of LDS, 96 VGPRs, no scratch: FIVE
+// workgroups a CU -- a stranded pass with windows of 508 distinct positions instead of 956 (what lies outside a window goes to the
+// global arrays either way).  0.858 ms a launch against 0.882 (profiles/r08B_before_after.txt); at four workgroups a CU the same
+// code is slower than the kernel it replaces (0.982 ms: profiles/experiments/r08_fused_four_workgroups.txt), and five workgroups
+// fetch 9 % more from HBM than four did (more chunks alive in one L2): 2.215 GB a launch.
+// History (round 5, records of all reads in LDS, 100 M reads a launch): 0.94-0.98 ms against 0.655-0.67 + 0.375-0.39 for layout +
+// range; asking for the next tile's reads before this tile is counted gained nothing (a wave's memory operations return in
+// order: the first bucket entry waits for them), 512 threads -- two reads each, eight waves counting a tile -- took 1.25 ms: profiles/r05X_fused_pass.txt.
 // Plain LDS atomics, 64 VGPRs = 8 waves per SIMD (the kernel lives on how many waves are there to cover each other's memory
 // trips and barriers; the register cap costs nothing -- no scratch).
 // Measured and not kept: merging the atomics of neighbouring lanes into one per run of equal keys before issuing them (a DPP
 // shift and two ballots per key) needs a few more registers than that cap allows and was never faster, not even at 8000
 // reads per site: profiles/r02g_lds_conflicts_*.txt.
 template <bool STRANDED, bool BIG, bool FUSED>
-__global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__((amdgpu_waves_per_eu(FUSED ? 4 : 8, 8))) void spl_count_ranges_kernel(const spl_hot_params p)
+__global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__((amdgpu_waves_per_eu(FUSED ? 5 : 8, 8))) void spl_count_ranges_kernel(const spl_hot_params p)
 {
     constexpr int NARR = STRANDED ? 4 : 2; // {beta1, ME} x {read strand +, -}
     constexpr int WIN = STRANDED ? (FUSED ? SPL_WIN_STRANDED_FUSED : SPL_WIN_STRANDED) : SPL_WIN;
@@ -708,7 +765,11 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     // a TILE of SPL_TILE_FUSED reads at a time, and counted from there -- they never exist in memory (a tile's reads are asked for
     // when the tile before is through: asking earlier was measured and bought nothing, profiles/r05X_fused_pass.txt).  s_rec: first the stage of the tile's ops, then its records.
     constexpr uint32_t TILE = SPL_TILE_FUSED, TILES = FUSED ? (1u << CSHIFT) / TILE : 1u;
-    constexpr uint32_t REC_BYTES = FUSED ? (uint32_t)SPL_LAYOUT_SLOT(TILE) : 16u;
+    // The simple reads have no records (SimpleInPlace): the record area is the stage of a tile's ops, 16 KB, which holds the
+    // records of a tile's other reads unless more than two thirds of its reads are twice-spliced or "other" ones.  A tile that
+    // needs more is laid out and counted in two halves (512 reads fit whatever they are), see `half` below.
+    constexpr uint32_t REC_BYTES = FUSED ? (uint32_t)SPL_REC_BYTES_FUSED : 16u, REC_ROOM = REC_BYTES - 64u; // (the slack: an iteration's last loads look 8 bytes past its run)
+    static_assert(!FUSED || (REC_ROOM >= 16u * TILE && REC_ROOM >= (TILE / 2u) * SPL_REC_OTHER), "a tile's ops, and half a tile's records whatever they are");
     __shared__ uint4 s_rec[REC_BYTES / 16u];
     __shared__ uint16_t s_idx[FUSED ? TILE : 1];   // read q of the tile's runs 1 .. 3 -> its index in the chunk's cell of the arrays
     __shared__ uint32_t s_lay[2 * NWAVE];
@@ -718,7 +779,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     __shared__ uint32_t s_qcnt[NWAVE], s_qbase;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // wave-uniform, in an SGPR
     const uint32_t seg0 = wave * SEG;
-    const uint32_t lane = (uint32_t)threadIdx.x & 63u;
+    uint32_t lane = (uint32_t)threadIdx.x & 63u; // (FUSED: taken again tile by tile, see thread_here in spl_layout_tile.h)
     uint32_t n_front = 0, n_back = 0, back_done = 0; // (back_done: entries of the back list the list pass is through with)
     // The once-spliced reads with rivals are not listed: a lane remembers WHICH of its reads they were, two bits per iteration
     // of the run (a wave has eight iterations of it at most), and the run is streamed a second time for them after the loops
@@ -741,8 +802,8 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     // are never listed).  A list that is full does not drop a read: its entries go straight into the literal queue -- one
     // returning atomic per push instead of one per workgroup, on a path that a chunk of mostly flagged spliced reads takes --,
     // and a twice-spliced read that finds the back list full is the literal kernel's (which takes any read).
-    uint32_t n_simple = 0; // (FUSED: s_idx counts from the first read that is not a simple one)
-    auto entry_of = [&](uint32_t slot) { return FUSED ? (uint32_t)((__attribute__((address_space(3))) const uint16_t *)s_idx)[(slot & 0x3fffu) - n_simple] : slot; };
+    // (FUSED: a tile's slots count its reads of runs 1 .. 3 -- the simple ones have none -- and s_idx says where in the arrays each is)
+    auto entry_of = [&](uint32_t slot) { return FUSED ? (uint32_t)((__attribute__((address_space(3))) const uint16_t *)s_idx)[slot & 0x3fffu] : slot; };
     auto push_direct = [&](bool want, uint32_t slot, unsigned long long m, uint32_t n) {
         const uint32_t shard = blockIdx.x & 7u;
         uint32_t base = 0;
@@ -765,7 +826,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         n_back += n;
     };
 
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;
     int32_t wbase = 0;
     ChunkView cv;
     // (the first two words of a bucket entry: all a boundary needs that is no junction end)
@@ -807,7 +868,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
             i = i < ch.lo ? ch.lo : (i > hi ? hi : i);
             ob[q] = q == 0u ? ch.o_lo : (q == TILES ? ch.o_hi : p.src.cig_off[i]);
         }
-        for (int j = tid; j < NARR * (WIN + 1); j += BLOCK) lds[j] = 0; // (a barrier lies between this and the first count: tile_finish has three)
+        for (int j = tid; j < NARR * (WIN + 1); j += BLOCK) lds[j] = 0; // (a barrier lies between this and the first count: tile_finish's first, behind the ops' stage)
         cv.rec = nullptr;
         cv.wide = (spl_gu32 *)(p.src.cigar + ch.seg_op0);
         cv.shift = ch.shift;
@@ -826,22 +887,36 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         if constexpr (FUSED) { const spl_u32x2 v = *(__attribute__((address_space(3))) const spl_u32x2 *)(lrec + at); return make_uint2(v.x, v.y); }
         else return ld_g2(cv.rec + (size_t)at);
     };
+    uint32_t half = 0; // FUSED: 0 = the tile in one piece; 1, 2 = its halves, one after the other (their simple reads are counted already)
     for (;;) { // the chunk's tiles (FUSED), or the chunk in one piece
     if constexpr (FUSED) {
-        const spllay::TileSpan sp = span_of(tile);
-        uint32_t n[4];
-        {
+        // The simple reads are counted by tile_finish itself, where they are classified; the records of the tile's other reads go
+        // to s_rec.  A tile whose records do not fit there (long reads, spliced reads throughout: rare in every workload) comes
+        // back with its simple reads counted and nothing written, and is laid out again half by half -- reads [lo, mid), then
+        // [mid, hi), each with its own ops, ranks, records and count, the simple reads left alone.
+        lane = spllay::thread_here() & 63u; // (what the loops below make of it is made per tile, not kept from before the first one)
+        spllay::TileSpan sp = span_of(tile);
+        if (half) {
+            int64_t mid = sp.cell0 + (int64_t)(TILE / 2u);
+            mid = mid < sp.lo ? sp.lo : (mid > sp.hi ? sp.hi : mid);
+            const uint32_t o_mid = p.src.cig_off[mid];
+            if (half == 1u) { sp.hi = mid; sp.o_hi = o_mid; } else { sp.lo = mid; sp.o_lo = o_mid; }
+        }
+        uint32_t n[4] = {0, 0, 0, 0};
+        bool fits = true;
+        if (sp.hi > sp.lo) { // (uniform; half a tile may be empty)
+            SimpleInPlace<STRANDED, NARR, WIN, RPT> simple{p, lds, wbase, ch.shift, half == 0u};
             spllay::TileLoads<(int)TILE, RPT> L;
             spllay::tile_issue<(int)TILE, RPT>(p.src, p.src_n_rec, p.src_n_ops, sp, L);
-            spllay::tile_finish<(int)TILE, RPT>(p.src, p.src_n_ops, sp, L, (spllay::lay_lds_w32 *)s_rec, (spllay::lay_lds_w32 *)s_lay,
-                                                spllay::RecordsInLds{(spllay::lay_lds_u8 *)s_rec, (spllay::lay_lds_u16 *)s_idx, tile * TILE}, n);
+            fits = spllay::tile_finish<(int)TILE, RPT>(p.src, p.src_n_ops, sp, L, (spllay::lay_lds_w32 *)s_rec, (spllay::lay_lds_w32 *)s_lay,
+                                                       spllay::RecordsInLds{(spllay::lay_lds_u8 *)s_rec, (spllay::lay_lds_u16 *)s_idx, tile * TILE}, simple, n, REC_ROOM);
         }
-        cv.start[0] = 0; cv.start[1] = n[0]; cv.start[2] = n[0] + n[1]; cv.start[3] = n[0] + n[1] + n[2]; cv.start[4] = n[0] + n[1] + n[2] + n[3];
+        if (!fits) { half = 1u; continue; } // (the workgroup as one; only a whole tile can fail to fit.  The next stage of ops is behind the ranks' barrier)
+        cv.start[0] = 0; cv.start[1] = 0; cv.start[2] = n[1]; cv.start[3] = n[1] + n[2]; cv.start[4] = n[1] + n[2] + n[3];
         cv.off[0] = 0;
-        cv.off[1] = (n[0] * SPL_REC_SIMPLE + 15u) & ~15u;
-        cv.off[2] = cv.off[1] + n[1] * SPL_REC_MNM;
+        cv.off[1] = 0;
+        cv.off[2] = n[1] * SPL_REC_MNM;
         cv.off[3] = cv.off[2] + n[2] * SPL_REC_M2;
-        n_simple = n[0];
         __syncthreads(); // the tile's records are there
     }
     // Wave-iterations of the chunk.  A wave-iteration takes 64 * K consecutive reads of ONE run, K per lane: K = 4 for simple reads
@@ -914,6 +989,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         };
         // ---- simple reads (one aligned op, mapped, in range: the packer checked all that): two boundaries, one range,
         //      nothing else can happen.  Four of them per lane.
+        if constexpr (!FUSED) // (FUSED: counted where they were classified, SimpleInPlace)
         for (; g < g_start[1]; g += NWAVE) {
             take(0u, cv.start[1], 0u, SPL_REC_SIMPLE, KS);
             const uint32_t i0 = cu_i0;
@@ -1211,12 +1287,17 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     }
     if constexpr (!FUSED) break;
     else {
-        if (tile == tile_last) break;
-        ++tile;
+        if (half == 1u) half = 2u;
+        else {
+            if (tile == tile_last) break;
+            ++tile;
+            half = 0u;
+        }
         fm_mnm = 0; it_mnm = 0; n_back = 0; back_done = 0; // (the wave's lists of the tile's own reads are through; the front list goes on)
         __syncthreads(); // everybody is through with the tile's records: the next tile's ops take their place
     }
     } // tiles
+    if constexpr (FUSED) tid = (int)spllay::thread_here(); // (likewise: the hand-over's places are made here, not in front of the tiles)
     if ((tid & 63) == 0) s_qcnt[tid >> 6] = n_front;
     __syncthreads();
     // Hand the chunk's queue over: one returning atomic per workgroup on the counter of its XCD shard (8 counters, so
@@ -1833,7 +1914,7 @@ extern "C" int spl_dev_launch_count(const spl_count_params *p, const spl_hot_par
         *lds_out = (p->stranded ? 4 * ((h->cells ? SPL_WIN_STRANDED_FUSED : SPL_WIN_STRANDED) + 1) : 2 * (SPL_WIN + 1)) * 4 + SPL_WAVES * SPL_WAVE_READS * 2 + 4 * SPL_WAVES + 4; // difference windows + the waves' lists
 #define SPL_LAUNCH_RANGES(S, B) hipExtLaunchKernelGGL((spl_count_ranges_kernel<S, B, false>), dim3(grid), dim3(SPL_BLOCK), 0, st, e0, e1, 0, *h)
         if (h->cells) { // the fused pass: straight from the BAM-native arrays
-            *lds_out += (int)SPL_LAYOUT_SLOT(SPL_TILE_FUSED) + 2 * SPL_TILE_FUSED + (SPL_BLOCK_FUSED / 64) * SPL_WAVE_READS_FUSED * 2 - SPL_WAVES * SPL_WAVE_READS * 2;
+            *lds_out += (int)SPL_REC_BYTES_FUSED + 2 * SPL_TILE_FUSED + (SPL_BLOCK_FUSED / 64) * SPL_WAVE_READS_FUSED * 2 - SPL_WAVES * SPL_WAVE_READS * 2;
 #define SPL_LAUNCH_FUSED(S, B) hipExtLaunchKernelGGL((spl_count_ranges_kernel<S, B, true>), dim3(grid), dim3(SPL_BLOCK_FUSED), 0, st, e0, e1, 0, *h)
             if (p->stranded) { if (big) SPL_LAUNCH_FUSED(true, true); else SPL_LAUNCH_FUSED(true, false); }
             else { if (big) SPL_LAUNCH_FUSED(false, true); else SPL_LAUNCH_FUSED(false, false); }

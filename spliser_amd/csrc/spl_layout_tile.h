@@ -29,6 +29,15 @@ struct StagedOps {
     lay_lds_u32 *p;
     __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return p[k]; }
 };
+// The thread's number, opaque to the compiler at this point: what a tile's steps derive from it (places in the stage, 64-bit offsets
+// of its loads) is then made where it is used, tile by tile, and not once in front of a caller's loop over its tiles and kept
+// in registers through everything the loop holds besides -- in the fused counting kernel that was six registers in scratch.
+__device__ __forceinline__ uint32_t thread_here()
+{
+    uint32_t t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+}
 // Inclusive prefix sum inside every row of 16 lanes.
 __device__ __forceinline__ uint32_t row_scan(uint32_t v)
 {
@@ -77,6 +86,14 @@ struct RecordsInLds {
     __device__ __forceinline__ void st4(uint32_t d, lay_u32x4 v) const { *(__attribute__((address_space(3))) lay_u32x4_a8 *)(rec + d) = v; }
     __device__ __forceinline__ void index(uint32_t q, uint32_t cell_index) const { idx[q] = (uint16_t)(base + cell_index); }
 };
+// What tile_finish does with a read of run 0 beyond its record.  Nothing (the layout kernel, and whoever counts from the records):
+struct SimpleAsRecords { static constexpr bool in_place = false; };
+// ... or (the fused counting kernel, spl_kernels.hip: SimpleInPlace) the read is COUNTED by the thread that classified it, from
+// the registers it stands in, and has no record at all: in_place = true,
+//   issue(j, is_simple, w0, w1)   asks for what counting the thread's read j needs (its record's two words), right behind the
+//                                 classification: the answers are on their way while the other runs are ranked;
+//   commit(j, is_simple, w0, w1)  counts it, behind the ranks' barrier and the other runs' records (all lanes of a wave together).
+// Runs 1 .. 3 then begin at offset 0 of the sink, n[0] comes back 0 and the sink's index counts from 0.
 
 // One tile of C reads -- the cell [cell0, cell0 + C) of the arrays' indexes, or the part [lo, hi) of it a segment has -- by a
 // workgroup of C / 4 threads, in two steps so that a kernel can ask for its NEXT tile's reads before it works on this one's:
@@ -84,7 +101,9 @@ struct RecordsInLds {
 //                words of them), everything asked for at once, into registers;
 //   tile_finish  the ops into s_ops (STAGE = 4 C words of LDS), classification, ranks (s_cnt: 2 words a wave), the records to
 //                `sink` -- AFTER the workgroup's last look at s_ops (a barrier lies between): the sink's memory may be s_ops itself.
-// n[r] = reads of run r; the runs begin at 0, align16(8 n0), + 16 n1, + 24 n2 (chunk_view's arithmetic).
+//                -> false, and no record written, when the records take more than `room` bytes (the caller takes the tile in parts).
+// n[r] = reads of run r; the runs begin at 0, align16(8 n0), + 16 n1, + 24 n2 (chunk_view's arithmetic).  With simple reads
+// counted in place (Simple::in_place) run 0 has no records: n[0] comes back 0 and runs 1 .. 3 begin at 0, + 16 n1, + 24 n2.
 struct TileSpan { int64_t cell0, lo, hi; uint32_t o_lo, o_hi, o_fetch_hi, seg_op0; }; // (o_fetch_hi >= o_hi: how far tile_issue may read ops)
 template <int C, int R>   // R = reads a thread: 4 (a workgroup of C / 4 threads) or 2 (C / 2)
 struct TileLoads {
@@ -100,7 +119,7 @@ __device__ __forceinline__ void tile_issue(const spl_devreads &src, int64_t n_re
     static_assert(R == 4 || R == 2, "two or four reads a thread");
     constexpr uint32_t T = C / R, STAGE = 4 * C;
     static_assert(STAGE / (4 * T) == R, "R quads of ops a thread");
-    const uint32_t t = threadIdx.x;
+    const uint32_t t = thread_here();
     const int64_t g = sp.cell0 + R * (int64_t)t; // the thread's first read
 #pragma unroll
     for (int j = 0; j < R; ++j) L.pos[j] = 0;
@@ -161,14 +180,14 @@ __device__ __forceinline__ void tile_issue(const spl_devreads &src, int64_t n_re
     }
 }
 
-template <int C, int R, class Sink>
-__device__ __forceinline__ void tile_finish(const spl_devreads &src, int64_t n_ops, const TileSpan &sp, const TileLoads<C, R> &L, lay_lds_w32 *s_ops,
-                                            lay_lds_w32 *s_cnt, const Sink sink, uint32_t (&n)[4])
+template <int C, int R, class Sink, class Simple>
+__device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_ops, const TileSpan &sp, const TileLoads<C, R> &L, lay_lds_w32 *s_ops,
+                                            lay_lds_w32 *s_cnt, const Sink sink, Simple &simple, uint32_t (&n)[4], uint32_t room = 0xffffffffu)
 {
     constexpr uint32_t T = C / R, NW = T / 64, STAGE = 4 * C; // (threads, waves, words of the op stage: 4 ops a read on average)
     static_assert(NW <= 16, "the waves' totals are summed inside one row of lanes");
     constexpr uint32_t PAD = SPL_PACK_SCAN_OPS;               // a read is classified from a stage that holds its first eight ops
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t t = thread_here(), lane = t & 63u, wave = t >> 6;
     const int64_t g = sp.cell0 + R * (int64_t)t;
     const uint32_t r0 = (uint32_t)R * t, lo_r = (uint32_t)(sp.lo - sp.cell0), hi_r = (uint32_t)(sp.hi - sp.cell0);
     const uint32_t o_hi = sp.o_hi, seg_op0 = sp.seg_op0;
@@ -278,6 +297,10 @@ __device__ __forceinline__ void tile_finish(const spl_devreads &src, int64_t n_o
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         run[j] = (runs >> (3 * j)) & 7u;
+        if constexpr (Simple::in_place) {
+            simple.issue(j, run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1]);
+            c01 += run[j] == SPL_RC_MNM ? 0x10000u : 0u;
+        } else
         c01 += run[j] == SPL_RC_SIMPLE ? 1u : (run[j] == SPL_RC_MNM ? 0x10000u : 0u);
         c23 += run[j] == SPL_RC_M2 ? 1u : (run[j] == SPL_RC_OTHER ? 0x10000u : 0u);
     }
@@ -294,6 +317,14 @@ __device__ __forceinline__ void tile_finish(const spl_devreads &src, int64_t n_o
     const uint32_t b01 = wu ? (uint32_t)__builtin_amdgcn_readlane((int)x, wu - 1u) : 0u, b23 = wu ? (uint32_t)__builtin_amdgcn_readlane((int)y, wu - 1u) : 0u;
     const uint32_t n0 = t01 & 0xffffu, n1 = t01 >> 16, n2 = t23 & 0xffffu, n3 = t23 >> 16;
     const uint32_t off1 = (n0 * SPL_REC_SIMPLE + 15u) & ~15u, off2 = off1 + n1 * SPL_REC_MNM, off3 = off2 + n2 * SPL_REC_M2;
+    n[0] = n0; n[1] = n1; n[2] = n2; n[3] = n3;
+    if (off3 + n3 * SPL_REC_OTHER > room) { // (the whole workgroup: the sink has no room for these records -- none is written)
+        if constexpr (Simple::in_place) {
+#pragma unroll
+            for (int j = 0; j < R; ++j) simple.commit(j, run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1]);
+        }
+        return false;
+    }
     // (reads of each run before this thread's: the waves below, the lanes below) -> byte offsets of the thread's next record of each run
     const uint32_t e01 = b01 + i01 - c01, e23 = b23 + i23 - c23;
     uint32_t at[4] = {(e01 & 0xffffu) * SPL_REC_SIMPLE, off1 + (e01 >> 16) * SPL_REC_MNM, off2 + (e23 & 0xffffu) * SPL_REC_M2, off3 + (e23 >> 16) * SPL_REC_OTHER};
@@ -303,8 +334,9 @@ __device__ __forceinline__ void tile_finish(const spl_devreads &src, int64_t n_o
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const uint32_t r = run[j];
-        const uint32_t d = r == SPL_RC_SIMPLE ? at[0] : (r == SPL_RC_MNM ? at[1] : (r == SPL_RC_M2 ? at[2] : at[3]));
-        if (r == SPL_RC_SIMPLE) sink.st2(d, lay_u32x2{w[j][0], w[j][1]});
+        uint32_t d = r == SPL_RC_MNM ? at[1] : (r == SPL_RC_M2 ? at[2] : at[3]);
+        if constexpr (!Simple::in_place) d = r == SPL_RC_SIMPLE ? at[0] : d; // (in place: run 0 has no place)
+        if (r == SPL_RC_SIMPLE) { if constexpr (!Simple::in_place) sink.st2(d, lay_u32x2{w[j][0], w[j][1]}); }
         else if (r < (uint32_t)SPL_RC_RUNS) {
             sink.st4(d, lay_u32x4{w[j][0], w[j][1], w[j][2], w[j][3]});
             if (r != SPL_RC_MNM) sink.st2(d + 16, lay_u32x2{w[j][4], w[j][5]});
@@ -315,12 +347,16 @@ __device__ __forceinline__ void tile_finish(const spl_devreads &src, int64_t n_o
                 q_at[2] += r == SPL_RC_OTHER ? 1u : 0u;
             }
         }
-        at[0] += r == SPL_RC_SIMPLE ? SPL_REC_SIMPLE : 0u;
+        if constexpr (!Simple::in_place) at[0] += r == SPL_RC_SIMPLE ? SPL_REC_SIMPLE : 0u;
         at[1] += r == SPL_RC_MNM ? SPL_REC_MNM : 0u;
         at[2] += r == SPL_RC_M2 ? SPL_REC_M2 : 0u;
         at[3] += r == SPL_RC_OTHER ? SPL_REC_OTHER : 0u;
     }
-    n[0] = n0; n[1] = n1; n[2] = n2; n[3] = n3;
+    if constexpr (Simple::in_place) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) simple.commit(j, run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1]);
+    }
+    return true;
 }
 
 // Both steps in a row: one chunk ch of C reads (spl_layout_kernel).  *s_first = POS of the chunk's first read in file order (valid
@@ -337,7 +373,8 @@ __device__ __forceinline__ void layout_tile(const spl_devreads &src, int64_t n_r
         const uint32_t e = (uint32_t)(sp.lo - g);
         *s_first = e == 0u ? L.pos[0] : (e == 1u ? L.pos[1] : (e == 2u ? L.pos[2] : L.pos[3]));
     }
-    tile_finish<C, 4>(src, n_ops, sp, L, s_ops, s_cnt, sink, n);
+    SimpleAsRecords as_records;
+    (void)tile_finish<C, 4>(src, n_ops, sp, L, s_ops, s_cnt, sink, as_records, n);
 }
 
 } // namespace spllay
