@@ -192,9 +192,15 @@ typedef struct spl_dsoa spl_dsoa;
 int spl_soa_upload(spl_ctx *ctx, int n_seg, const spl_reads *segs, spl_dsoa **out);
 /* ... with max_end[k] = the last base (1-based) any read of segment k covers, where the caller knows it (null, or < 0: computed) */
 int spl_soa_upload2(spl_ctx *ctx, int n_seg, const spl_reads *segs, const int64_t *max_end, spl_dsoa **out);
+/* ... and with xs[k] = a strand byte per read of segment k ('+', '-', 0 = none): a fifth device array beside flag, which
+ * spl_junctions reads with stranded = 3.  How reads the host decoded (spl_bam_aux_strand) and SAM text get there. */
+int spl_soa_upload3(spl_ctx *ctx, int n_seg, const spl_reads *segs, const int64_t *max_end, const uint8_t *const *xs, spl_dsoa **out);
 void spl_soa_free(spl_ctx *ctx, spl_dsoa *soa);
 int spl_reads_add_soa(spl_ctx *ctx, spl_dreads *dr, spl_dsoa *soa, int seg, int32_t pos_shift);
 int spl_reads_relayout(spl_ctx *ctx, spl_dreads *dr);
+/* *out = 1 when the set is fused and its arrays have the fifth one, the reads' strand bytes (a decode after
+ * spl_bam_set_aux_strand, spl_soa_upload3): what spl_junctions' stranded = 3 needs.  0 otherwise. */
+int spl_reads_has_strand(const spl_dreads *dr, int *out);
 /* What the layout moves for a finished read set: the BAM-native arrays read (10 bytes a read + 4 an op) and the records written
  * (0 while the set is fused). */
 int spl_reads_layout_bytes(spl_ctx *ctx, const spl_dreads *dr, int64_t *soa_bytes_out, int64_t *record_bytes_out);
@@ -261,6 +267,19 @@ int spl_bam_open_deferred(const char *path, int n_threads, spl_bam **out);
  * alone} -- flags are tested first -- once the decode is complete (it waits for that, like spl_bam_n_records). */
 int spl_bam_set_filter(spl_bam *bam, int min_mapq, int require_flags, int exclude_flags);
 int spl_bam_filter_counts(spl_bam *bam, int64_t *out2);
+/* The transcript strand an aligner wrote on its spliced reads for an unstranded library (XS:A:+/-: STAR --outSAMstrandField
+ * intronMotif, HISAT2, TopHat; what `regtools junctions extract -s XS` reads; the reference has no counterpart, its README sends
+ * the user to regtools).  spl_bam_set_aux_strand(bam, 1): the decode -- the device's and the host's alike -- leaves one more byte
+ * per placed read, in file order beside its FLAG: for a read whose own CIGAR holds an N op the value of the FIRST aux field XS of
+ * type A if that is '+' or '-', else 0 (no such field, another value, an area that cannot be walked to it; an XS of another type
+ * -- BWA's XS:i -- is stepped over like any field); for every other read 0, its aux area untouched.  The same rule as
+ * spl_bam_set_filter: before anybody decodes the file or waits for it, SPL_ERR_ARG afterwards.  A dropped read has no byte.
+ * spl_bam_aux_strand: borrowed view (until spl_bam_close) of the bytes of the reads spl_bam_reads hands out for `tid`, same order;
+ * *out = NULL when the file was decoded without them.  struct spl_reads is unchanged.  spl_bam_aux_strand_host: the walk itself
+ * over a caller's bytes [aux, aux + len) -> *out (test hook; no file, no GPU). */
+int spl_bam_set_aux_strand(spl_bam *bam, int on);
+int spl_bam_aux_strand(const spl_bam *bam, int tid, const uint8_t **out);
+int spl_bam_aux_strand_host(const uint8_t *aux, uint32_t len, uint8_t *out);
 int spl_bam_decode_device(spl_ctx *ctx, spl_bam *bam, int *on_device_out);
 /* For a caller that will call spl_bam_decode_device from another thread in a moment while others may already wait for
  * references: the file is marked as taken by the device decoder now, so that those waits wait instead of starting the host
@@ -347,7 +366,11 @@ int spl_bam_write2(const char *path, int n_ref, const char *const *ref_names, co
  * reads carrying each and the longest anchors on either side (reference bases of the read between the junction and the
  * previous / next N op or read end: the block sizes of a BED12 line), and returns their number; spl_junctions_get copies
  * the table of the last call, sorted by (left, right, strand), into caller arrays (any may be NULL).  stranded: 0 ->
- * strand '?', 1 = fr / 2 = rf -> '+' / '-' of the read by check_strand's rule (:374-406).  Policy knobs in the sense of
+ * strand '?', 1 = fr / 2 = rf -> '+' / '-' of the read by check_strand's rule (:374-406); 3 -> the strand byte the decode left
+ * for the read (spl_bam_set_aux_strand, spl_soa_upload3: the aligner's XS:A tag, regtools' -s XS): '+', '-', or '?' for 0, so
+ * that a junction carried by reads of all three kinds is THREE rows, each with its own count and anchors, sorted like every table
+ * ('+' < '-' < '?').  3 is for fused sets whose arrays have the bytes; on any other set it is SPL_ERR_ARG, never a table of '?'.
+ * Policy knobs in the sense of
  * regtools' -a / -m / -M: a read supports a junction only if both of ITS anchors are >= min_anchor and the intron length
  * is in [min_intron, max_intron] (max_intron 0 = no upper limit); 0, 0, 0 counts every N op.  A fused set stays fused: its
  * table comes straight from the arrays (spl_reads_layout_bytes still reports 0 record bytes afterwards). */

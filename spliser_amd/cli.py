@@ -6,7 +6,9 @@ of one node, ``--threads`` for the BAM decode pool, ``--gpuDecode`` / ``--hostDe
 ``--keepJunctions``.  These DO change results, and only exist where there is no junction file: ``process`` without ``-b``
 takes the junctions from the BAM itself, in the same pass, and ``--minAnchor`` / ``--minIntron`` / ``--maxIntron`` say which
 reads support a junction (regtools' -a / -m / -M; defaults 8 / 70 / 500000) -- with ``-b`` they are an error, the file has
-its own.  ``--minMapQ`` / ``--requireFlags`` / ``--excludeFlags`` (``process``, ``junctions``, ``combine``, ``combineShallow``) are
+its own.  ``--strandFromXS`` (``process`` without ``-b``, ``junctions``; regtools' ``-s XS``) takes a junction's strand from the
+XS:A tag the aligner wrote on its reads, for an unstranded library whose junctions are otherwise all ``?``; an alternative to
+``--isStranded``, and an error with ``-b``.  ``--minMapQ`` / ``--requireFlags`` / ``--excludeFlags`` (``process``, ``junctions``, ``combine``, ``combineShallow``) are
 samtools view's -q / -f / -F applied while the BAM is decoded: the run's results are those of the pre-filtered file.  Extra sub-command: ``junctions`` writes that BED12 junction file on its own, for ``process -b`` here or for the
 reference (which leaves it to regtools); ``process`` without ``-b`` writes what ``junctions`` + ``process -b`` write.
 """
@@ -34,6 +36,9 @@ def build_parser():
     p.add_argument("--keepJunctions", dest="keepJunctions", default=False, action="store_true",
                    help="(this build only, without -b) also write <outputPath>.junctions.bed: the file `junctions` writes for the same "
                         "BAM and knobs")
+    p.add_argument("--strandFromXS", dest="strandFromXS", default=False, action="store_true",
+                   help="(this build only, without -b; changes results) unstranded library: a junction's strand is the XS:A tag its reads "
+                        "carry (regtools -s XS) instead of '?'; not together with --isStranded")
     p.add_argument("-o", "--outputPath", dest="outputPath", required=True,
                    help="Absolute path, including file prefix where the .SpliSER.tsv file is written")
     p.add_argument("-A", "--annotationFile", dest="annotationFile", required=False,
@@ -102,6 +107,9 @@ def build_parser():
     j.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False)
     j.add_argument("--isStranded", dest="isStranded", default=False, action="store_true")
     j.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False)
+    j.add_argument("--strandFromXS", dest="strandFromXS", default=False, action="store_true",
+                   help="unstranded library: the strand column from the reads' XS:A tag (regtools -s XS) instead of '?'; not together "
+                        "with --isStranded")
     j.add_argument("-a", "--minAnchor", dest="minAnchor", type=int, default=8, help="both anchors of a read must be this long (regtools -a)")
     j.add_argument("-m", "--minIntron", dest="minIntron", type=int, default=70, help="regtools -m")
     j.add_argument("-M", "--maxIntron", dest="maxIntron", type=int, default=500000, help="regtools -M; 0 = no limit")
@@ -151,6 +159,8 @@ def main(argv=None):
         parser.error("--gene requires --annotationFile and --maxIntronSize")
     elif command in ("process", "combine", "combineShallow", "junctions") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
+    if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
+        parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
     if command in ("process", "combine", "combineShallow", "junctions"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
@@ -163,6 +173,8 @@ def main(argv=None):
             given = [f for f, d in (("--minAnchor", "minAnchor"), ("--minIntron", "minIntron"), ("--maxIntron", "maxIntron")) if kwargs.get(d) is not None]
             if kwargs.get("keepJunctions"):
                 given.append("--keepJunctions")
+            if kwargs.get("strandFromXS"):
+                given.append("--strandFromXS")
             if given:
                 parser.error("%s: only without --bedFile (a junction file has its own junctions)" % ", ".join(given))
         else:

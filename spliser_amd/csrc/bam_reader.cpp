@@ -35,6 +35,7 @@
 
 #include "../../include/spliser.h"
 #include "spl_bam.h"
+#include "spl_bam_aux.h"
 #include "spl_error.h"
 
 namespace {
@@ -314,6 +315,7 @@ struct RefReads {
     uint16_t *flag = nullptr;
     uint32_t *cig_off = nullptr; // n + 1 entries, cig_off[0] = 0: ops of read k are cigar[cig_off[k] .. cig_off[k + 1])
     uint32_t *cigar = nullptr;
+    uint8_t *xs = nullptr;       // n strand bytes beside flag, or null (spl_bam_set_aux_strand)
     size_t n = 0, n_ops = 0;
     int64_t max_end = 0;
 };
@@ -442,10 +444,11 @@ struct RefFinal {
     uint16_t *flag = nullptr;
     uint32_t *cig_off = nullptr; // n + 1
     uint32_t *cigar = nullptr;
+    uint8_t *xs = nullptr; // (spl_bam_set_aux_strand; spl_bam_aux_strand hands it out)
     RefFinal() = default;
     RefFinal(const RefFinal &) = delete;
     RefFinal &operator=(const RefFinal &) = delete;
-    ~RefFinal() { free(pos); free(flag); free(cig_off); free(cigar); }
+    ~RefFinal() { free(pos); free(flag); free(cig_off); free(cigar); free(xs); }
 };
 
 struct PendingPart {
@@ -477,6 +480,7 @@ struct spl_bam {
     int64_t n_records = 0;
     spl_bam_filter filter = {0, 0, 0}; // which placed records are kept (spl_bam_set_filter; fixed once claim != 0)
     int64_t dropped[2] = {0, 0};       // records the filter dropped: by their flags, by their MAPQ
+    bool aux_strand = false;           // a strand byte per placed read beside its flag (spl_bam_set_aux_strand; fixed once claim != 0)
     // ---- BAM-native arrays per reference, assembled on demand (spl_bam_reads) ----
     std::vector<RefFinal> refs_storage; // (never resized after the header: RefFinal is not copyable)
     std::vector<char> assembled;
@@ -491,6 +495,7 @@ struct spl_bam {
     bool lazy = false;
     bool fetching = false;     // somebody is copying a share's reads to the host right now (fetch_lazy)
     int (*dev_fetch)(void *, int32_t **, uint16_t **, uint32_t **, uint32_t **) = nullptr;
+    int (*dev_fetch_xs)(void *, uint8_t **) = nullptr; // ... and their strand bytes, where the decode left any
     // what the device decoder(s) left in device memory for the device packer (spl_capi.cpp), and how to give it back: one handle
     // for a whole-file decode, one per share otherwise
     struct DevShare { void *handle = nullptr; void (*free_fn)(void *) = nullptr; int share = -1; bool fetched = false; };
@@ -545,8 +550,10 @@ inline const uint8_t *record_cigar(const uint8_t *r, uint32_t bs, size_t need, u
 // the position reached (a record boundary).  Two walks: the first checks every record and sizes the parts, the second fills
 // arrays of exactly that size -- the bytes are in the caller's cache both times.
 // Records the filter does not keep are counted (dropped[0]: by flags, [1]: by MAPQ) and otherwise treated like records without a position.
-const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, const spl_bam_filter &filter, Arena &arena, std::vector<Part> &parts, int64_t &n_records,
-                               int64_t *dropped, std::string &err, bool &fatal)
+// want_xs: one more array per part, a strand byte per read -- the aux area of a read whose CIGAR holds an N op walked by the
+// function the device's extraction calls (spl_bam_aux.h), 0 for every other read.  A CIGAR parked in a CG tag is the read's CIGAR.
+const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, const spl_bam_filter &filter, bool want_xs, Arena &arena, std::vector<Part> &parts,
+                               int64_t &n_records, int64_t *dropped, std::string &err, bool &fatal)
 {
     struct Run { int32_t tid; size_t n, ops; const uint8_t *begin; };
     Run few[4];
@@ -596,7 +603,8 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
         rr.flag = (uint16_t *)arena.take(sizeof(uint16_t) * run.n);
         rr.cig_off = (uint32_t *)arena.take(sizeof(uint32_t) * (run.n + 1));
         rr.cigar = (uint32_t *)arena.take(sizeof(uint32_t) * std::max<size_t>(run.ops, 1));
-        if (!rr.pos || !rr.flag || !rr.cig_off || !rr.cigar) { err = "out of host memory"; fatal = true; return reached; }
+        if (want_xs) rr.xs = (uint8_t *)arena.take(std::max<size_t>(run.n, 1));
+        if (!rr.pos || !rr.flag || !rr.cig_off || !rr.cigar || (want_xs && !rr.xs)) { err = "out of host memory"; fatal = true; return reached; }
         rr.cig_off[0] = 0;
         size_t i = 0, at = 0;
         for (q = run.begin; i < run.n; q += 4 + (size_t)le32(q)) {
@@ -611,12 +619,15 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
             const uint8_t *cig = record_cigar(r, bs, need, l_name, l_seq, n_cig);
             int64_t ref_len = 0;
             uint32_t *dst = rr.cigar + at;
+            bool has_n = false;
             for (uint32_t c = 0; c < n_cig; ++c) {
                 const uint32_t op = le32(cig + 4ull * c);
                 dst[c] = op;
                 const uint32_t code = op & 15u;
                 if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) ref_len += op >> 4;
+                has_n = has_n || code == 3;
             }
+            if (want_xs) rr.xs[i] = has_n ? spl_bam_aux_strand(r + need, r + bs) : (uint8_t)0;
             at += n_cig;
             rr.pos[i] = pos0 + 1;
             rr.flag[i] = le16(r + 14);
@@ -708,7 +719,10 @@ bool assemble_ref(spl_bam *bam, int tid, std::string &err)
     dst.flag = (uint16_t *)big_alloc(sizeof(uint16_t) * (size_t)std::max<int64_t>(n, 1));
     dst.cig_off = (uint32_t *)big_alloc(sizeof(uint32_t) * (size_t)(n + 1));
     dst.cigar = (uint32_t *)big_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(g, 1));
-    if (!dst.pos || !dst.flag || !dst.cig_off || !dst.cigar) { err = "out of host memory"; return false; }
+    bool with_xs = bam->aux_strand;
+    for (const PendingPart *pt : parts) with_xs = with_xs && (pt->reads.n == 0 || pt->reads.xs != nullptr);
+    if (with_xs) dst.xs = (uint8_t *)big_alloc((size_t)std::max<int64_t>(n, 1));
+    if (!dst.pos || !dst.flag || !dst.cig_off || !dst.cigar || (with_xs && !dst.xs)) { err = "out of host memory"; return false; }
     dst.cig_off[0] = 0;
     std::vector<int64_t> read_at(parts.size() + 1, 0), op_at(parts.size() + 1, 0);
     for (size_t i = 0; i < parts.size(); ++i) {
@@ -725,6 +739,7 @@ bool assemble_ref(spl_bam *bam, int tid, std::string &err)
             if (!k) continue;
             memcpy(dst.pos + read_at[i], src.pos, sizeof(int32_t) * k);
             memcpy(dst.flag + read_at[i], src.flag, sizeof(uint16_t) * k);
+            if (with_xs) memcpy(dst.xs + read_at[i], src.xs, k);
             const uint32_t base = (uint32_t)op_at[i];
             uint32_t *off = dst.cig_off + read_at[i]; // entry j + 1 = end of read j
             const uint32_t c0 = src.cig_off[0]; // (0 for the host decoder's parts; a file-wide offset for adopted arrays)
@@ -768,6 +783,7 @@ void decode_worker(spl_bam *bam)
     BlockDir &dir = bam->dir;
     const int n_ref = bam->n_refs;
     const spl_bam_filter filter = bam->filter; // (nobody changes it once a decoder has the file)
+    const bool want_xs = bam->aux_strand;
     const NodeCpus node; // the NUMA node this thread runs on (the opening thread's, inherited): all worker threads stay there
     auto env_num = [](const char *name, long dflt) { const char *e = getenv(name); const long v = e ? atol(e) : 0; return v > 0 ? v : dflt; };
     const size_t BATCH = (size_t)env_num("SPL_BAM_BATCH_BLOCKS", 32);
@@ -853,7 +869,7 @@ void decode_worker(spl_bam *bam)
                 o.start = (size_t)(p - buf);
                 std::string err;
                 bool fatal = false;
-                reached = (size_t)(extract_records(p, end, n_ref, filter, arena, o.parts, o.nrec, o.dropped, err, fatal) - buf);
+                reached = (size_t)(extract_records(p, end, n_ref, filter, want_xs, arena, o.parts, o.nrec, o.dropped, err, fatal) - buf);
                 o.parse_bad = fatal;
                 if (!o.known) o.head.assign((const uint8_t *)buf, (const uint8_t *)buf + o.start);
                 o.tail.assign((const uint8_t *)buf + reached, end);
@@ -879,7 +895,7 @@ void decode_worker(spl_bam *bam)
     auto walk = [&](const uint8_t *p0, const uint8_t *p1, bool &fatal) { // sequential, authoritative: commits what it parses
         std::vector<Part> seq;
         int64_t n = 0, drop[2] = {0, 0};
-        const uint8_t *r = extract_records(p0, p1, n_ref, filter, arena_mine, seq, n, drop, fail, fatal);
+        const uint8_t *r = extract_records(p0, p1, n_ref, filter, want_xs, arena_mine, seq, n, drop, fail, fatal);
         merge_parts(bam, seq);
         bam->n_records += n;
         bam->dropped[0] += drop[0];
@@ -1123,6 +1139,34 @@ extern "C" int spl_bam_set_filter(spl_bam *bam, int min_mapq, int require_flags,
     if (bam->claim != 0 || bam->done)
         return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_filter: the file is being decoded (or waited for) already", bam->path.c_str());
     bam->filter = spl_bam_filter{(uint32_t)min_mapq, (uint32_t)require_flags, (uint32_t)exclude_flags};
+    return SPL_OK;
+}
+
+// A strand byte per placed read beside its flag, from the aligner's XS:A tag.  The same rule as spl_bam_set_filter: only while
+// nobody decodes the file or waits for it.
+extern "C" int spl_bam_set_aux_strand(spl_bam *bam, int on)
+{
+    if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_aux_strand: null argument");
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (bam->claim != 0 || bam->done)
+        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_aux_strand: the file is being decoded (or waited for) already", bam->path.c_str());
+    bam->aux_strand = on != 0;
+    return SPL_OK;
+}
+
+bool spl_bam_get_aux_strand(spl_bam *bam)
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    return bam->aux_strand;
+}
+
+// The walk itself on a caller's bytes (test hook; no file, no GPU): *out = '+', '-' or 0.
+extern "C" int spl_bam_aux_strand_host(const uint8_t *aux, uint32_t len, uint8_t *out)
+{
+    if ((len && !aux) || !out) return spl_set_error(SPL_ERR_ARG, "spl_bam_aux_strand_host: null argument");
+    static const uint8_t none = 0;
+    const uint8_t *p = len ? aux : &none;
+    *out = spl_bam_aux_strand(p, p + len);
     return SPL_OK;
 }
 
@@ -1723,6 +1767,11 @@ void spl_bam_set_fetch(spl_bam *bam, int (*fetch)(void *, int32_t **, uint16_t *
     std::lock_guard<std::mutex> lock(bam->mu);
     bam->dev_fetch = fetch;
 }
+void spl_bam_set_fetch_xs(spl_bam *bam, int (*fetch)(void *, uint8_t **))
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    bam->dev_fetch_xs = fetch;
+}
 
 // The host copies of reads that were adopted without them: of every share that has not brought its yet.  Called with bam->mu
 // held; the copy itself (gigabytes over PCIe) runs WITHOUT it -- whoever else wants a reference that is there already, or wants
@@ -1740,12 +1789,19 @@ static int fetch_lazy(spl_bam *bam, std::unique_lock<std::mutex> &lock)
         void *const handle = bam->dev_shares[k].handle;
         const int share = bam->dev_shares[k].share;
         int32_t *pos = nullptr; uint16_t *flag = nullptr; uint32_t *cig_off = nullptr, *cigar = nullptr;
+        uint8_t *xs = nullptr;
+        int (*const fetch_xs)(void *, uint8_t **) = bam->aux_strand ? bam->dev_fetch_xs : nullptr;
         lock.unlock();
-        const int rc = bam->dev_fetch(handle, &pos, &flag, &cig_off, &cigar);
+        int rc = bam->dev_fetch(handle, &pos, &flag, &cig_off, &cigar);
+        if (rc == SPL_OK && fetch_xs) { // (the fifth array, where the decode left one: copied with the others)
+            rc = fetch_xs(handle, &xs);
+            if (rc) { free(pos); free(flag); free(cig_off); free(cigar); }
+        }
         lock.lock();
         bam->fetching = false;
         if (rc) { bam->cv.notify_all(); return rc; }
         bam->slabs.push_back(pos); bam->slabs.push_back(flag); bam->slabs.push_back(cig_off); bam->slabs.push_back(cigar);
+        if (xs) bam->slabs.push_back(xs);
         for (int t = 0; t < bam->n_refs; ++t) {
             for (PendingPart *pp : bam->parts[(size_t)t]) {
                 if (pp->share != share) continue;
@@ -1755,6 +1811,7 @@ static int fetch_lazy(spl_bam *bam, std::unique_lock<std::mutex> &lock)
                 r.flag = flag + first;
                 r.cig_off = cig_off + first;
                 r.cigar = cigar;
+                r.xs = xs ? xs + first : nullptr;
                 r.n_ops = (size_t)(r.cig_off[r.n] - r.cig_off[0]);
             }
         }
@@ -1846,6 +1903,21 @@ extern "C" int spl_bam_reads(const spl_bam *cbam, int tid, spl_reads *out, int64
     out->cig_off = rr.cig_off;
     out->cigar = rr.cigar;
     if (max_end_out) *max_end_out = rr.max_end;
+    return SPL_OK;
+}
+
+// Borrowed view (valid until spl_bam_close) of the strand bytes of the reads spl_bam_reads hands out for `tid`, in the same order;
+// *out = null when the file was decoded without spl_bam_set_aux_strand (or the reference has no reads).
+extern "C" int spl_bam_aux_strand(const spl_bam *cbam, int tid, const uint8_t **out)
+{
+    if (!cbam || !out) return spl_set_error(SPL_ERR_ARG, "spl_bam_aux_strand: null argument");
+    *out = nullptr;
+    spl_reads r;
+    const int rc = spl_bam_reads(cbam, tid, &r, nullptr); // (assembles the reference, the fifth array with the others)
+    if (rc) return rc;
+    spl_bam *bam = const_cast<spl_bam *>(cbam);
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (r.n_reads > 0) *out = bam->refs_storage[(size_t)tid].xs;
     return SPL_OK;
 }
 

@@ -25,6 +25,7 @@ SPL_BAM_HD inline int spl_bam_filter_verdict(const spl_bam_filter &f, uint32_t f
     return mapq >= f.min_mapq ? SPL_BAM_KEPT : SPL_BAM_DROP_MAPQ;
 }
 spl_bam_filter spl_bam_get_filter(spl_bam *bam);           // what the file's decoders are to apply (fixed once a decode has begun)
+bool spl_bam_get_aux_strand(spl_bam *bam);                 // ... and whether they leave a strand byte per placed read (spl_bam_set_aux_strand)
 
 // The reads of reference `tid` as a packer source: the decoder's own parts, in file order, nothing copied.  Waits until the
 // reference is complete (spl_bam_wait_ref).  The views stay valid until spl_bam_release_ref(tid) or spl_bam_close.
@@ -75,6 +76,7 @@ bool spl_bam_cancelled(const spl_bam *bam);                   // spl_bam_cancel 
 // spl_bam_adopt with null arrays = the reads stay on the device; `fetch(handle, ...)` brings malloc'ed host copies when a host-side
 // reader asks for them (spl_bam_source, spl_bam_reads)
 void spl_bam_set_fetch(spl_bam *bam, int (*fetch)(void *, int32_t **, uint16_t **, uint32_t **, uint32_t **));
+void spl_bam_set_fetch_xs(spl_bam *bam, int (*fetch)(void *, uint8_t **)); // ... and of the strand bytes (null out = the handle has none)
 int spl_bam_start_host(spl_bam *bam);                      // decode on the host's threads unless somebody decodes already
 bool spl_bam_claim_for_device(spl_bam *bam);               // the device decoder takes the file (false: it is taken)
 void spl_bam_note_decline(spl_bam *bam, const char *why); // why the device decoder leaves the file to the host threads

@@ -1207,6 +1207,7 @@ void copy_slice(size_t k, void *arg)
 struct DeviceReads {
     int device = 0;
     void *pos = nullptr, *flag = nullptr, *cig_off = nullptr, *cigar = nullptr;
+    void *xs = nullptr; // uint8[n_rec] beside flag, or null: the reads' strand bytes (spl_bam_set_aux_strand, spl_soa_upload3)
     int64_t n_rec = 0, n_ops = 0;
     std::vector<int64_t> ref_first, ref_n, ref_max, ref_ops;
     std::atomic<int> refs{1};
@@ -1219,7 +1220,7 @@ static void free_device_reads(void *h)
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
     (void)hipSetDevice(r->device);
-    devmem::put(r->pos); devmem::put(r->flag); devmem::put(r->cig_off); devmem::put(r->cigar);
+    devmem::put(r->pos); devmem::put(r->flag); devmem::put(r->cig_off); devmem::put(r->cigar); devmem::put(r->xs);
     if (have) (void)hipSetDevice(cur);
     delete r;
 }
@@ -1280,6 +1281,24 @@ static int fetch_device_reads(void *h, int32_t **pos_out, uint16_t **flag_out, u
         return ok ? spl_set_error(SPL_ERR_HIP, "decoded reads back to the host: %s", hipGetErrorString(q)) : spl_set_error(SPL_ERR_NOMEM, "out of host memory for the decoded reads");
     }
     *pos_out = (int32_t *)arr[0].host; *flag_out = (uint16_t *)arr[1].host; *cigoff_out = (uint32_t *)arr[2].host; *cigar_out = (uint32_t *)arr[3].host;
+    return SPL_OK;
+}
+
+// ... and the fifth array, where the decode left one (spl_bam_set_aux_strand): *out = null when it did not.
+static int fetch_device_xs(void *h, uint8_t **out)
+{
+    const DeviceReads *r = (const DeviceReads *)h;
+    *out = nullptr;
+    if (!r->xs) return SPL_OK;
+    uint8_t *host = (uint8_t *)host_array((size_t)r->n_rec);
+    if (!host) return spl_set_error(SPL_ERR_NOMEM, "out of host memory for the decoded reads");
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    hipError_t q = hipSetDevice(r->device);
+    if (q == hipSuccess && r->n_rec) q = hipMemcpy(host, r->xs, (size_t)r->n_rec, hipMemcpyDeviceToHost);
+    if (have) (void)hipSetDevice(cur);
+    if (q != hipSuccess) { free(host); return spl_set_error(SPL_ERR_HIP, "decoded strand bytes back to the host: %s", hipGetErrorString(q)); }
+    *out = host;
     return SPL_OK;
 }
 
@@ -1351,6 +1370,7 @@ extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_ou
         DeviceReads *keep = res.reads;
         spl_bam_set_device_reads(bam, keep, free_device_reads);
         spl_bam_set_fetch(bam, fetch_device_reads);
+        spl_bam_set_fetch_xs(bam, fetch_device_xs);
         const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.n_all, res.dropped);
         if (rc) spl_bam_set_device_reads(bam, nullptr, nullptr);
         if (rc == SPL_OK && on_device_out) *on_device_out = 1;
@@ -1382,6 +1402,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     ShareOut res;
     const Publish report = [&](ShareOut &res) -> int { // (a share that is done: reported at once, the last one to report completes the file)
         spl_bam_set_fetch(bam, fetch_device_reads);
+        spl_bam_set_fetch_xs(bam, fetch_device_xs);
         const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.n_all, res.dropped, 0);
         if (rc2 == SPL_OK && on_device_out) *on_device_out = 1;
         return rc2;
@@ -1503,8 +1524,9 @@ struct ShareDecode {
     const uint8_t *const image = spl_bam_image(bam, &fsize);
     const int n_ref = spl_bam_n_ref(bam);
     const spl_bam_filter filter = spl_bam_get_filter(bam); // (the file is claimed: nobody changes it now)
+    const bool want_xs = spl_bam_get_aux_strand(bam);      // (likewise: a fifth array, the spliced reads' XS:A strand)
     // ---- everything the streams touch is declared before them
-    DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds;
+    DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds, d_xs;
     std::vector<spl_zblock> blocks, blocks0; // (blocks0: the early windows', for their launches before the directory is complete)
     std::unique_ptr<uint32_t[]> status;
     std::unique_ptr<spl_bscan[]> scan;
@@ -2037,7 +2059,8 @@ struct ShareDecode {
     // the extracted arrays anew, with room for want_rec records and want_ops ops
     int grow_arrays(uint64_t want_rec, uint64_t want_ops)
     {
-        DevBuf pos2, flag2, cigoff2, cigar2, tid2;
+        DevBuf pos2, flag2, cigoff2, cigar2, tid2, xs2;
+        if (want_xs) HIP_TRY(xs2.get(want_rec, pipe.b));
         HIP_TRY(pos2.get(4 * want_rec, pipe.b));
         HIP_TRY(flag2.get(2 * want_rec, pipe.b));
         HIP_TRY(cigoff2.get(4 * (want_rec + 1), pipe.b));
@@ -2049,11 +2072,13 @@ struct ShareDecode {
             HIP_TRY(hipMemcpyAsync(cigoff2.p, d_cigoff.p, 4 * (n_rec + 1), hipMemcpyDeviceToDevice, pipe.b));
             HIP_TRY(hipMemcpyAsync(cigar2.p, d_cigar.p, 4 * n_ops, hipMemcpyDeviceToDevice, pipe.b));
             HIP_TRY(hipMemcpyAsync(tid2.p, d_tid.p, 4 * n_rec, hipMemcpyDeviceToDevice, pipe.b));
+            if (want_xs && n_rec) HIP_TRY(hipMemcpyAsync(xs2.p, d_xs.p, n_rec, hipMemcpyDeviceToDevice, pipe.b));
             HIP_TRY(hipStreamSynchronize(pipe.b));
         } else {
             HIP_TRY(hipMemsetAsync(cigoff2.p, 0, 4, pipe.b));
         }
         std::swap(d_pos.p, pos2.p); std::swap(d_flag.p, flag2.p); std::swap(d_cigoff.p, cigoff2.p); std::swap(d_cigar.p, cigar2.p); std::swap(d_tid.p, tid2.p);
+        std::swap(d_xs.p, xs2.p);
         cap_rec = want_rec;
         cap_ops = want_ops;
         return SPL_OK;
@@ -2208,7 +2233,8 @@ struct ShareDecode {
             HIP_TRY((hipError_t)spl_dev_launch_bam_extract(stream0, win_end, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)nd, d_scan.as<spl_bscan>() + s0,
                                                            d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, d_pos.as<int32_t>(), d_flag.as<uint16_t>(),
                                                            d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), d_tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
-                                                           with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags, pipe.b));
+                                                           with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags,
+                                                           want_xs ? d_xs.as<uint8_t>() : nullptr, pipe.b));
         }
         if (b_done < b1s && k + 1 < n_win) // what is left of this window: in front of the next one's bytes
             HIP_TRY(hipMemcpyAsync(stream0_of(k + 1) + blocks[b_done].out, stream0 + blocks[b_done].out, (size_t)(win_end - blocks[b_done].out), hipMemcpyDeviceToDevice, pipe.b));
@@ -2257,7 +2283,8 @@ struct ShareDecode {
             keep->ref_max[(size_t)t] = (int64_t)maxend[(size_t)t];
         }
         keep->pos = d_pos.p; keep->flag = d_flag.p; keep->cig_off = d_cigoff.p; keep->cigar = d_cigar.p;
-        d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = nullptr; // (the caller owns them from here)
+        keep->xs = d_xs.p;
+        d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = d_xs.p = nullptr; // (the caller owns them from here)
         res.reads = keep;
         res.n_all = n_all;
         res.dropped[0] = n_drop_flags;
@@ -2627,7 +2654,7 @@ void max_end_slice(size_t k, void *arg)
 } // namespace
 
 // n_seg host segments as they are -> one set of device arrays (DeviceReads, one reference held by the caller).
-static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceReads **out, const int64_t *max_end)
+static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceReads **out, const int64_t *max_end, const uint8_t *const *xs = nullptr)
 {
     *out = nullptr;
     HIP_TRY(hipSetDevice(c->device));
@@ -2652,6 +2679,7 @@ static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceRea
     if (q == hipSuccess) q = devmem::get(&dev->flag, 2 * (size_t)n_rec + 64, 'b');
     if (q == hipSuccess) q = devmem::get(&dev->cig_off, 4 * ((size_t)n_rec + 1) + 64, 'b');
     if (q == hipSuccess) q = devmem::get(&dev->cigar, 4 * (size_t)n_ops + 64, 'b');
+    if (q == hipSuccess && xs) q = devmem::get(&dev->xs, (size_t)n_rec + 64, 'b');
     // The arrays go up as they are, through the context's ring of page-locked staging buffers: a piece is copied into a buffer by
     // the packing threads side by side (the CIGAR offsets moved behind the ops of the segments before theirs on the way), and is
     // on the copy stream while the next piece is copied -- a caller's pageable array straight into hipMemcpy is a third of that.
@@ -2698,6 +2726,7 @@ static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceRea
             }
             send((int32_t *)dev->pos + at, r.pos, 4 * (size_t)r.n_reads, 0u, false);
             send((uint16_t *)dev->flag + at, r.flag, 2 * (size_t)r.n_reads, 0u, false);
+            if (xs) send((uint8_t *)dev->xs + at, xs[k], (size_t)r.n_reads, 0u, false);
             if (g) send((uint32_t *)dev->cigar + op_at, r.cigar, 4 * (size_t)g, 0u, false);
             send((uint32_t *)dev->cig_off + at, r.cig_off, 4 * (size_t)r.n_reads, (uint32_t)op_at, true);
         }
@@ -2734,6 +2763,24 @@ extern "C" int spl_soa_upload2(spl_ctx *c, int n_seg, const spl_reads *segs, con
     return SPL_OK;
 }
 
+// ... xs[k]: per read of segment k its strand byte ('+', '-', 0 = none), a fifth array beside flag: what spl_junctions' stranded = 3
+// reads.  Reads the host decoded (spl_bam_aux_strand) and SAM text reach the fused junction kernel this way.
+extern "C" int spl_soa_upload3(spl_ctx *c, int n_seg, const spl_reads *segs, const int64_t *max_end, const uint8_t *const *xs, spl_dsoa **out)
+{
+    if (!c || !out || n_seg < 0 || (n_seg && !segs) || !xs) return spl_set_error(SPL_ERR_ARG, "spl_soa_upload3: null argument");
+    for (int k = 0; k < n_seg; ++k)
+        if (segs[k].n_reads > 0 && !xs[k]) return spl_set_error(SPL_ERR_ARG, "spl_soa_upload3: segment %d has no strand bytes", k);
+    *out = nullptr;
+    DeviceReads *dev = nullptr;
+    const int rc = upload_native(c, n_seg, segs, &dev, max_end, xs);
+    if (rc) return rc;
+    spl_dsoa *h = new (std::nothrow) spl_dsoa();
+    if (!h) { free_device_reads(dev); return spl_set_error(SPL_ERR_NOMEM, "out of host memory"); }
+    h->reads = dev;
+    *out = h;
+    return SPL_OK;
+}
+
 extern "C" void spl_soa_free(spl_ctx *c, spl_dsoa *soa)
 {
     if (!soa) return;
@@ -2751,6 +2798,13 @@ extern "C" int spl_reads_add_soa(spl_ctx *c, spl_dreads *d, spl_dsoa *soa, int s
     HIP_TRY(hipSetDevice(c->device));
     const size_t t = (size_t)seg;
     return add_segment_device(c, d, dev, dev->ref_first[t], dev->ref_n[t], dev->ref_ops[t], pos_shift, dev->ref_n[t] && pos_shift != 0 ? dev->ref_max[t] : -1);
+}
+
+extern "C" int spl_reads_has_strand(const spl_dreads *d, int *out)
+{
+    if (!d || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_has_strand: null argument");
+    *out = d->finished && d->fused && d->groups.size() == 1 && d->groups[0].src->xs ? 1 : 0;
+    return SPL_OK;
 }
 
 // What the layout kernel moves for this read set: the BAM-native arrays it reads (10 bytes a read and 4 an op: every input
@@ -3028,7 +3082,7 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
 {
     if (!c || !dr || !n_out) return spl_set_error(SPL_ERR_ARG, "spl_junctions: null argument");
     if (min_anchor < 0 || min_intron < 0 || max_intron < 0) return spl_set_error(SPL_ERR_ARG, "spl_junctions: negative filter value");
-    if (stranded < 0 || stranded > 2) return spl_set_error(SPL_ERR_ARG, "stranded must be 0, 1 (fr) or 2 (rf)");
+    if (stranded < 0 || stranded > 3) return spl_set_error(SPL_ERR_ARG, "stranded must be 0, 1 (fr), 2 (rf) or 3 (the reads' strand bytes)");
     HIP_TRY(hipSetDevice(c->device));
     c->junctions.clear();
     *n_out = 0;
@@ -3040,6 +3094,11 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     // and a table with one slot per op (rounded up to a power of two) is what the set has been given since the kernel exists.
     const bool fused = dr->fused && dr->groups.size() == 1;
     const spl_dreads::Group *g = fused ? &dr->groups[0] : nullptr;
+    // stranded = 3 is the fused kernel's alone, and needs the fifth array: anything else is an error, never a table of '?'
+    if (stranded == 3 && !fused)
+        return spl_set_error(SPL_ERR_ARG, "spl_junctions: stranded = 3 needs a fused read set (all of it from one device decode or one spl_soa_upload3)");
+    if (stranded == 3 && !g->src->xs)
+        return spl_set_error(SPL_ERR_ARG, "spl_junctions: stranded = 3, but the reads have no strand bytes (spl_bam_set_aux_strand before the decode, or spl_soa_upload3)");
     spl_devreads src{nullptr, nullptr, nullptr, nullptr};
     uint64_t wanted = (uint64_t)dr->n_cigar;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -3070,7 +3129,8 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     int rc;
     if (fused) {
         rc = spl_dev_launch_junctions_fused(&src, g->src->n_rec, g->src->n_ops, g->d_chunks, g->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron,
-                                            (uint32_t)max_intron, keys, vals, (uint32_t)slots, out_keys, out_vals, n_dev, c->d_err, c->stream);
+                                            (uint32_t)max_intron, keys, vals, (uint32_t)slots, out_keys, out_vals, n_dev, c->d_err,
+                                            stranded == 3 ? (const uint8_t *)g->src->xs : nullptr, c->stream);
         if (ev1) (void)hipEventRecord(ev1, c->stream);
     } else
         rc = spl_dev_launch_junctions(dr->meta, dr->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron,
@@ -3101,7 +3161,9 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     for (uint32_t i = 0; i < n; ++i) order[i] = i;
     // left, right, strand -- left as the signed coordinate it is: a read at POS 0 whose CIGAR opens with N has left = -1, whose
     // key is the largest of all as an unsigned number
+    // (stranded = 3: spljw::key3_of, whose keys compare like (left, right, strand byte) as the numbers they are)
     std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        if (stranded == 3) return hk[a] < hk[b];
         const int32_t la = (int32_t)(hk[a] >> 32), lb = (int32_t)(hk[b] >> 32);
         return la != lb ? la < lb : (uint32_t)hk[a] < (uint32_t)hk[b];
     });
@@ -3112,6 +3174,7 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
         j.left = (int32_t)(k >> 32);
         j.right = (int32_t)((k & 0xffffffffull) >> 1);
         j.strand = stranded ? ((k & 1ull) ? (uint8_t)'-' : (uint8_t)'+') : (uint8_t)'?';
+        if (stranded == 3) spljw::key3_read(k, j.left, j.right, j.strand);
         j.count = hv[3 * (size_t)order[i]];
         j.anchor_left = hv[3 * (size_t)order[i] + 1];
         j.anchor_right = hv[3 * (size_t)order[i] + 2];

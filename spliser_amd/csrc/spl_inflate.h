@@ -88,10 +88,12 @@ int spl_dev_launch_bam_scan(const uint8_t *stream, uint64_t stream_len, uint64_t
 // rec_off[b] / op_off[b]: index of the block's first placed record / first op in the output arrays.  cig_off gets n + 1 entries
 // (the caller sets entry 0); ref_max_end[tid] = largest last base of a read of the reference (atomicMax; zero it first).
 // recs: what the scan of THESE blocks (same first block, same order) left, or null: then a lane walks its block's records.
+// xs: null, or one more array beside flag -- per placed read the transcript strand of its aux area (spl_bam_aux.h), looked for
+// only where the read's own CIGAR holds an N op, 0 otherwise: the kernels' second instantiations.
 int spl_dev_launch_bam_extract(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
                                const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar,
                                int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags,
-                               void *stream_handle);
+                               uint8_t *xs, void *stream_handle);
 // where the reference id changes along the placed records: (index of the first record of a run, its tid) pairs, unordered
 int spl_dev_launch_bam_bounds(const int32_t *tid, const uint32_t *cig_off, uint64_t n, uint64_t *bounds, uint32_t *n_bounds, uint32_t cap, void *stream_handle);
 // image: the whole file in device memory, readable SPL_Z_IMAGE_PAD bytes past its end; out: writable 16 bytes past the last block.

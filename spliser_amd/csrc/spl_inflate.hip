@@ -7,6 +7,7 @@
 
 #include "spl_inflate.h"
 #include "spl_bam.h"
+#include "spl_bam_aux.h"
 #include "spl_wave.h"
 #include "spl_inflate_wave.h"
 #include "spl_crc.h"
@@ -202,10 +203,16 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
     scan[b] = out;
 }
 
-__global__ __launch_bounds__(64) void spl_bam_extract_kernel(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
-                                                              const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out,
-                                                              uint16_t *flag_out, uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out,
-                                                              unsigned long long *ref_max_end, spl_bam_filter filter)
+// Both extractions are written once, as a function with a template parameter: XS = false is the kernel a file gets that nobody
+// asked the aligner's strand tag of (spl_bam_set_aux_strand) -- not a load, a branch or an argument more than before there was
+// such a thing --, XS = true leaves one more byte per placed read: for a read whose own CIGAR holds an N op, which the op loop
+// sees anyway, the transcript strand of its aux area (spl_bam_aux.h; '+', '-' or 0); for every other read 0, without a byte of its
+// aux area being touched.  The area begins behind SEQ and QUAL -- l_seq is the second word of the h1 load -- and ends with the record.
+template <bool XS>
+__device__ __forceinline__ void bam_extract_walk(const uint8_t *stream, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
+                                                 const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out,
+                                                 uint16_t *flag_out, uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out,
+                                                 unsigned long long *ref_max_end, const spl_bam_filter &filter, uint8_t *xs_out)
 {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_blocks) return;
@@ -225,16 +232,21 @@ __global__ __launch_bounds__(64) void spl_bam_extract_kernel(const uint8_t *stre
         const int32_t tid = (int32_t)h0.y, pos0 = (int32_t)h0.z;
         const uint32_t l_name = h0.w & 0xffu, mapq = (h0.w >> 8) & 0xffu, n_cig = h1.x & 0xffffu, flag = h1.x >> 16;
         const uint8_t *cig = stream + at + 36 + l_name;
+        const uint32_t l_seq = XS ? h1.y : 0u;
         at += 4ull + bs;
         if (at < u1) { __builtin_memcpy(&h0, stream + at, 16); __builtin_memcpy(&h1, stream + at + 16, 16); }
         if (tid >= 0 && tid < n_ref && pos0 >= 0 && tid >= tid_lo && tid < tid_hi && spl_bam_filter_verdict(filter, flag, mapq) == SPL_BAM_KEPT) { // (the scan's decision, made again)
             long long ref_len = 0;
+            bool has_n = false;
             for (uint32_t k = 0; k < n_cig; ++k) {
                 const uint32_t op = ld32(cig + 4ull * k);
                 cigar[o + k] = op;
                 const uint32_t code = op & 15u;
                 if (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ref_len += (long long)(op >> 4);
+                if (XS) has_n = has_n || code == 3u;
             }
+            if (XS) // (the scan has seen to it that SEQ and QUAL end inside the record, and the record inside the stream)
+                xs_out[i] = has_n ? spl_bam_aux_strand(cig + 4ull * n_cig + ((uint64_t)l_seq + 1ull) / 2ull + (uint64_t)l_seq, cig - 32 - l_name + bs) : (uint8_t)0;
             o += n_cig;
             pos_out[i] = pos0 + 1;
             flag_out[i] = (uint16_t)flag;
@@ -254,14 +266,32 @@ __global__ __launch_bounds__(64) void spl_bam_extract_kernel(const uint8_t *stre
     if (run_tid >= 0) atomicMax(&ref_max_end[run_tid], (unsigned long long)run_end);
 }
 
+__global__ __launch_bounds__(64) void spl_bam_extract_kernel(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
+                                                              const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out,
+                                                              uint16_t *flag_out, uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out,
+                                                              unsigned long long *ref_max_end, spl_bam_filter filter)
+{
+    (void)stream_len;
+    bam_extract_walk<false>(stream, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off, op_off, pos_out, flag_out, cig_off, cigar, tid_out, ref_max_end, filter, nullptr);
+}
+
+__global__ __launch_bounds__(64) void spl_bam_extract_xs_kernel(const uint8_t *stream, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
+                                                                 const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out,
+                                                                 uint16_t *flag_out, uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out,
+                                                                 unsigned long long *ref_max_end, spl_bam_filter filter, uint8_t *xs_out)
+{
+    bam_extract_walk<true>(stream, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off, op_off, pos_out, flag_out, cig_off, cigar, tid_out, ref_max_end, filter, xs_out);
+}
+
 // Where every reference's records begin: (first record, tid | first CIGAR op << 32) per run of equal tids, in no particular order.
 // The same extraction with a WAVE per block: the scan has left where every placed record of the block begins (16 bits each), so
 // 64 records are read at once -- each lane its record's fixed fields and CIGAR, none waiting for the one before as the walk
 // above has to -- and written side by side: positions, flags and CIGAR offsets of consecutive records by consecutive lanes.
 // Where a record's ops go follows from a prefix sum over the lanes' op counts.
-__global__ __launch_bounds__(64) void spl_bam_extract_wave_kernel(const uint8_t *stream, int32_t n_ref, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
-                                                                   const uint16_t *recs, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out, uint16_t *flag_out,
-                                                                   uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end)
+template <bool XS>
+__device__ __forceinline__ void bam_extract_wave(const uint8_t *stream, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
+                                                 const uint16_t *recs, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out, uint16_t *flag_out,
+                                                 uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end, uint8_t *xs_out)
 {
     const uint32_t b = blockIdx.x;
     if (b >= n_blocks) return;
@@ -276,7 +306,7 @@ __global__ __launch_bounds__(64) void spl_bam_extract_wave_kernel(const uint8_t 
     for (uint32_t j0 = 0; j0 < n; j0 += 64u) {
         const uint32_t j = j0 + l;
         const bool have = j < n;
-        uint32_t n_cig = 0, l_name = 0, flag = 0;
+        uint32_t n_cig = 0, l_name = 0, flag = 0, bs = 0, l_seq = 0;
         int32_t tid = -1, pos0 = 0;
         const uint8_t *r = stream;
         if (have) {
@@ -286,6 +316,7 @@ __global__ __launch_bounds__(64) void spl_bam_extract_wave_kernel(const uint8_t 
             __builtin_memcpy(&h1, r + 16, 16);
             tid = (int32_t)h0.y; pos0 = (int32_t)h0.z;
             l_name = h0.w & 0xffu; n_cig = h1.x & 0xffffu; flag = h1.x >> 16;
+            if (XS) { bs = h0.x; l_seq = h1.y; }
         }
         // ops of the records before mine in this round
         uint32_t incl = n_cig;
@@ -299,13 +330,16 @@ __global__ __launch_bounds__(64) void spl_bam_extract_wave_kernel(const uint8_t 
         if (have) {
             const uint8_t *cig = r + 36 + l_name;
             long long ref_len = 0;
+            bool has_n = false;
             for (uint32_t k = 0; k < n_cig; ++k) {
                 const uint32_t op = ld32(cig + 4ull * k);
                 cigar[o + k] = op;
                 const uint32_t code = op & 15u;
                 if (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ref_len += (long long)(op >> 4);
+                if (XS) has_n = has_n || code == 3u;
             }
             const uint64_t i = i0 + j;
+            if (XS) xs_out[i] = has_n ? spl_bam_aux_strand(cig + 4ull * n_cig + ((uint64_t)l_seq + 1ull) / 2ull + (uint64_t)l_seq, r + 4 + bs) : (uint8_t)0;
             pos_out[i] = pos0 + 1;
             flag_out[i] = (uint16_t)flag;
             tid_out[i] = tid;
@@ -337,6 +371,21 @@ __global__ __launch_bounds__(64) void spl_bam_extract_wave_kernel(const uint8_t 
     }
 }
 
+__global__ __launch_bounds__(64) void spl_bam_extract_wave_kernel(const uint8_t *stream, int32_t n_ref, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
+                                                                   const uint16_t *recs, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out, uint16_t *flag_out,
+                                                                   uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end)
+{
+    (void)n_ref;
+    bam_extract_wave<false>(stream, blocks, n_blocks, scan, recs, rec_off, op_off, pos_out, flag_out, cig_off, cigar, tid_out, ref_max_end, nullptr);
+}
+
+__global__ __launch_bounds__(64) void spl_bam_extract_wave_xs_kernel(const uint8_t *stream, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
+                                                                      const uint16_t *recs, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out, uint16_t *flag_out,
+                                                                      uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end, uint8_t *xs_out)
+{
+    bam_extract_wave<true>(stream, blocks, n_blocks, scan, recs, rec_off, op_off, pos_out, flag_out, cig_off, cigar, tid_out, ref_max_end, xs_out);
+}
+
 __global__ __launch_bounds__(256) void spl_bam_bounds_kernel(const int32_t *tid, const uint32_t *cig_off, uint64_t n, uint64_t *bounds, uint32_t *n_bounds, uint32_t cap)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -359,9 +408,18 @@ extern "C" int spl_dev_launch_bam_scan(const uint8_t *stream, uint64_t stream_le
 
 extern "C" int spl_dev_launch_bam_extract(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
                                           const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar,
-                                          int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *st)
+                                          int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, uint8_t *xs, void *st)
 {
     if (n_blocks == 0) return 0;
+    if (xs) { // (spl_bam_set_aux_strand: the instantiations that walk a spliced read's aux area)
+        if (recs)
+            hipLaunchKernelGGL(spl_bam_extract_wave_xs_kernel, dim3(n_blocks), dim3(64), 0, (hipStream_t)st, stream, blocks, n_blocks, scan, recs, rec_off, op_off, pos, flag, cig_off, cigar, tid,
+                               ref_max_end, xs);
+        else
+            hipLaunchKernelGGL(spl_bam_extract_xs_kernel, dim3((n_blocks + 63u) / 64u), dim3(64), 0, (hipStream_t)st, stream, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off, op_off, pos, flag,
+                               cig_off, cigar, tid, ref_max_end, spl_bam_filter{min_mapq, require_flags, exclude_flags}, xs);
+        return (int)hipGetLastError();
+    }
     if (recs) { // (the scan of these very blocks has left the records' places: a wave per block)
         hipLaunchKernelGGL(spl_bam_extract_wave_kernel, dim3(n_blocks), dim3(64), 0, (hipStream_t)st, stream, n_ref, blocks, n_blocks, scan, recs, rec_off, op_off, pos, flag, cig_off, cigar,
                            tid, ref_max_end);

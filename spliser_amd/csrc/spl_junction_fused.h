@@ -18,7 +18,7 @@ int spl_dev_launch_junctions_count(const spl_devreads *src, const spl_layout_chu
 int spl_dev_launch_junctions_fused(const spl_devreads *src, int64_t n_rec, int64_t n_ops, const spl_layout_chunk *chunks, uint32_t n_chunks,
                                    int stranded, uint32_t min_anchor, uint32_t min_intron, uint32_t max_intron, unsigned long long *keys,
                                    uint32_t *vals, uint32_t n_slots, unsigned long long *out_keys, uint32_t *out_vals, uint32_t *n_out,
-                                   int32_t *err, void *stream);
+                                   int32_t *err, const uint8_t *xs, void *stream); // xs: the reads' strand bytes, with stranded = 3 and only then
 #ifdef __cplusplus
 }
 #endif

@@ -87,5 +87,25 @@ SPL_JW_HD unsigned long long key_of(int32_t l, int32_t r, unsigned long long str
     return ((unsigned long long)(uint32_t)l << 32) | ((unsigned long long)(uint32_t)r << 1) | strand_bit;
 }
 
+// The key of a table whose strand comes from the reads' own bytes (spl_junctions, stranded = 3): THREE strand values -- 0 '+',
+// 1 '-', 2 '?' -- need two bits, which key_of does not have beside 32 bits of l and 31 of r.  They are found by storing l + 1 and
+// r + 1, 31 bits each: a walked read has POS >= 0 and every cursor it reaches is <= SPL_COORD_MAX = 2^31 - 67 (beyond it the
+// walk ends with range_error, which the kernel turns into SPL_DEV_ERR_RANGE), so -1 <= l, r <= 2^31 - 68 and both sums fit.  A
+// coordinate below -1 -- only a segment moved by a negative shift could make one -- is refused by the kernel with the same
+// SPL_DEV_ERR_RANGE before it gets here.  Keys compare like (l, r, strand byte): '+' < '-' < '?'; none is ~0, the empty slot.
+// The tables of stranded = 0 / 1 / 2 keep key_of.
+SPL_JW_HD unsigned long long key3_of(int32_t l, int32_t r, unsigned long long strand_code)
+{
+    return ((unsigned long long)(uint32_t)(l + 1) << 33) | ((unsigned long long)(uint32_t)(r + 1) << 2) | strand_code;
+}
+SPL_JW_HD bool key3_fits(int32_t l, int32_t r) { return l >= -1 && r >= -1; }
+SPL_JW_HD void key3_read(unsigned long long key, int32_t &l, int32_t &r, uint8_t &strand)
+{
+    l = (int32_t)(uint32_t)(key >> 33) - 1;
+    r = (int32_t)(uint32_t)((key >> 2) & 0x7fffffffull) - 1;
+    const uint32_t s = (uint32_t)(key & 3ull);
+    strand = s == 0u ? (uint8_t)'+' : s == 1u ? (uint8_t)'-' : (uint8_t)'?';
+}
+
 } // namespace spljw
 #endif

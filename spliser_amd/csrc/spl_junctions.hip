@@ -76,9 +76,14 @@ struct StagedOrGlobalOps { // a listed read's ops: in the stage (LDS) when all o
     __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return staged ? lds[k] : glob[k]; }
 };
 
+// XS (spl_junctions, stranded = 3): the strand of a junction is the byte the decode left for its read (spl_bam_set_aux_strand: '+',
+// '-' or 0 -> '?'), so the table has up to three rows a junction (spljw::key3_of).  `xs` is an argument of this kernel's own --
+// spl_devreads is the range kernels' argument too -- and is read for a LISTED read only, into bits 16.. of the list entry's flag
+// word, which the 16-bit FLAG leaves free.  XS = false is the kernel of stranded = 0 / 1 / 2 as it was.
+template <bool XS>
 __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl_devreads src, int64_t n_rec, int64_t n_ops_total, const spl_layout_chunk *chunks,
                                                                       int stranded, uint32_t min_anchor, uint32_t min_intron, uint32_t max_intron,
-                                                                      unsigned long long *keys, uint32_t *vals, uint32_t mask, int32_t *err)
+                                                                      unsigned long long *keys, uint32_t *vals, uint32_t mask, int32_t *err, const uint8_t *xs)
 {
     __shared__ uint32_t s_stage[SPL_JSTAGE];
     __shared__ uint4 s_list[SPL_JTILE];   // {POS + shift, flag, first op, number of ops} of the listed reads
@@ -137,6 +142,7 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
             pos = src.pos[i];
             fl = src.flag[i];
             listed = !(fl & 4u) && pos >= 0; // unmapped and unplaced records carry no junctions
+            if (XS && listed) fl |= (uint32_t)xs[i] << 16;
         }
         // the list: lanes with a read to walk, in tile order
         const unsigned long long bal = __ballot(listed);
@@ -153,7 +159,9 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
             uint4 rd = make_uint4(0u, 0u, 0u, 0u);
             if (e < total) rd = s_list[e];
             const uint32_t r_ops = e < total ? rd.w : 0u;
-            const unsigned long long sbit = (stranded && spl_read_strand(rd.y, stranded) == (uint8_t)'-') ? 1ull : 0ull;
+            unsigned long long sbit;
+            if (XS) { const uint32_t x = rd.y >> 16; sbit = x == (uint32_t)'+' ? 0ull : x == (uint32_t)'-' ? 1ull : 2ull; }
+            else sbit = (stranded && spl_read_strand(rd.y, stranded) == (uint8_t)'-') ? 1ull : 0ull;
             StagedOrGlobalOps ops;
             ops.staged = (uint64_t)rd.z + rd.w <= ws + SPL_JSTAGE;
             ops.lds = (const lds_u32 *)s_stage + (ops.staged ? rd.z - (uint32_t)ws : 0u);
@@ -173,7 +181,9 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
                     if (has_n) atomicOr(err, SPL_DEV_ERR_RANGE);
                     w.range_error = false;
                 }
-                junction_merge_insert(have, have ? spljw::key_of(j.l, j.r, sbit) : ~0ull, j.anchor_left, j.anchor_right, lane, keys, vals, mask, err);
+                if (XS && have && !spljw::key3_fits(j.l, j.r)) { atomicOr(err, SPL_DEV_ERR_RANGE); have = false; }
+                junction_merge_insert(have, have ? (XS ? spljw::key3_of(j.l, j.r, sbit) : spljw::key_of(j.l, j.r, sbit)) : ~0ull, j.anchor_left, j.anchor_right, lane, keys, vals, mask,
+                                      err);
             }
         }
         __syncthreads(); // (the stage and the list are the next tile's)
@@ -230,17 +240,21 @@ extern "C" int spl_dev_launch_junctions_count(const spl_devreads *src, const spl
 extern "C" int spl_dev_launch_junctions_fused(const spl_devreads *src, int64_t n_rec, int64_t n_ops, const spl_layout_chunk *chunks, uint32_t n_chunks,
                                               int stranded, uint32_t min_anchor, uint32_t min_intron, uint32_t max_intron,
                                               unsigned long long *keys, uint32_t *vals, uint32_t n_slots, unsigned long long *out_keys,
-                                              uint32_t *out_vals, uint32_t *n_out, int32_t *err, void *stream)
+                                              uint32_t *out_vals, uint32_t *n_out, int32_t *err, const uint8_t *xs, void *stream)
 {
+    if ((stranded == 3) != (xs != nullptr)) return (int)hipErrorInvalidValue; // (mode 3 and the reads' strand bytes come together)
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)n_slots * 8, st);
     if (e == hipSuccess) e = hipMemsetAsync(vals, 0, (size_t)n_slots * 12, st);
     if (e == hipSuccess) e = hipMemsetAsync(n_out, 0, 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(err, 0, 4, st);
     if (e != hipSuccess) return (int)e;
-    if (n_chunks > 0)
-        hipLaunchKernelGGL(spl_junction_fused_kernel, dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron,
-                           max_intron, keys, vals, n_slots - 1u, err);
+    if (n_chunks > 0 && xs)
+        hipLaunchKernelGGL(spl_junction_fused_kernel<true>, dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron,
+                           max_intron, keys, vals, n_slots - 1u, err, xs);
+    else if (n_chunks > 0)
+        hipLaunchKernelGGL(spl_junction_fused_kernel<false>, dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron,
+                           max_intron, keys, vals, n_slots - 1u, err, (const uint8_t *)nullptr);
     hipLaunchKernelGGL(spl_junction_fused_compact_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, st, keys, vals, n_slots, out_keys, out_vals, n_out);
     return (int)hipGetLastError();
 }

@@ -4,8 +4,11 @@ Not part of SpliSER v0.1.8: its README (README.md:41) sends the user to ``regtoo
 table comes from ``spl_junctions`` (one insert per N op into a device hash table, see spl_kernels.hip); the line layout is
 the one findAlphaCounts reads (SpliSER_v0_1_8.py:259-277): ``leftpos = chromStart + blockSizes[0]``, ``rightpos =
 chromEnd - blockSizes[1]``, ``alpha = score``, strand in column 6.  Defaults of the policy knobs are regtools' (-a 8 -m 70
--M 500000); strand is the read strand by check_strand's rule for a stranded library and ``?`` otherwise (regtools can also
-take it from the aligner's XS tag, which this build does not decode).
+-M 500000); strand is the read strand by check_strand's rule for a stranded library and ``?`` otherwise -- or, with
+``strandFromXS`` (regtools' ``-s XS``, its mode for unstranded libraries), the value of the XS:A tag the aligner wrote on the read
+(STAR --outSAMstrandField intronMotif, HISAT2, TopHat): the decode leaves a strand byte per spliced read (``spl_bam_set_aux_strand``)
+and ``spl_junctions`` keys its table by it (mode 3), so that a junction carried by ``+``-tagged, ``-``-tagged and untagged reads
+is three lines.  An XS of another type (BWA's XS:i) or another value counts as no tag: ``?``.
 """
 import sys
 
@@ -72,14 +75,27 @@ def merge_tables(parts):
     return {k: out[k].astype(dt) for k, dt in _COLUMNS}
 
 
-def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, maxIntron):
+def log_xs_tally(tally, log):
+    """What a user of ``strandFromXS`` needs to learn first: whether the aligner wrote the tag at all."""
+    log("  (strand from XS: junction-supporting reads tagged +: %d, tagged -: %d, without a usable XS:A tag: %d)" % tuple(tally))
+    if tally[0] + tally[1] == 0 and tally[2]:
+        log("  (no spliced read carries XS:A:+/-: was the file aligned with STAR --outSAMstrandField intronMotif, HISAT2 or TopHat?)")
+
+
+def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, maxIntron, tally=None):
     """The junction table of every chromosome of ``chroms`` that has reads, from an alignment source whose decode has been
     started (``process.open_and_decode``): -> {chrom: (reads, table)}.  The reads are taken where the decode left them: after a
     decode on the device the read sets are fused and stay so (``spl_junctions`` reads the arrays; nothing is laid out, nothing
     decoded again by whoever counts the same reads afterwards).  A decode in shares: every device takes the table of ITS piece of
     a chromosome, and the pieces are merged here (``merge_tables``).  A file the host's threads decode, and SAM text: the first
-    device, chromosome by chromosome as they become complete."""
+    device, chromosome by chromosome as they become complete.  ``stranded`` = ``native.STRAND_FROM_XS``: the source must have been
+    opened with ``aux_strand`` -- the device decode's sets have the strand bytes, host-decoded reads and SAM text go up with
+    theirs as arrays (``spl_soa_upload3``: that mode is the fused kernel's).  ``tally``: a list whose three entries get the
+    junction-supporting reads by strand (+, -, ?) added: the sums of the tables' counts."""
     import threading
+    from_xs = stranded == native.STRAND_FROM_XS
+    if from_xs and not getattr(source, "aux_strand", False):
+        raise ValueError("strand from XS: the alignment source was opened without aux_strand")
     is_bam = isinstance(source, native.BamFile)
     knobs = (minAnchor, minIntron, maxIntron)
     pieces, errors, lock = {}, [], threading.Lock()
@@ -96,11 +112,27 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
         with lock:
             pieces.setdefault(chrom, []).append((n, table))
 
+    def take_arrays(ctx, chrom, rs):       # (strand from XS, reads on the host: up as five arrays, a fused set of their own)
+        if rs is None or not rs.n:
+            return
+        if rs.xs is None:
+            raise native.SpliserNativeError(-1, "%s: reads without strand bytes" % chrom)
+        with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, xs=rs.xs)], [rs.max_end], with_strand=True) as soa:
+            with ctx.begin_reads() as dr:
+                dr.add_soa(soa, 0)
+                dr.finish()
+                table = dr.junctions(stranded, *knobs)
+        with lock:
+            pieces.setdefault(chrom, []).append((rs.n, table))
+
     def run(device, jobs):
         try:
             with native.Context(device) as ctx:
                 for chrom, add in jobs:
-                    take(ctx, chrom, add)
+                    if add is None:
+                        take_arrays(ctx, chrom, source.reads(chrom))
+                    else:
+                        take(ctx, chrom, add)
         except Exception as exc:
             with lock:
                 errors.append(exc)
@@ -110,6 +142,8 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
         for k, (device, names) in enumerate(shares):
             held = [c for c in chroms if c in names and source.share_ref(k, c)[0] > 0]
             plans.append((device, [(c, (lambda dr, k=k, c=c: dr.add_bam_share(source, k, c))) for c in held]))
+    elif from_xs and not on_device:
+        plans = [(devices[0], [(c, None) for c in chroms])]
     elif is_bam:
         plans = [(devices[0], [(c, (lambda dr, c=c: dr.add_bam(source, c))) for c in chroms])]
     else:
@@ -127,25 +161,39 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
         w.join()
     if errors:
         raise errors[0]
+    if tally is not None:
+        for got in pieces.values():
+            for _, t in got:
+                for k, byte in enumerate(b"+-?"):
+                    tally[k] += int(t["count"][t["strand"] == byte].sum())
     return {c: (sum(n for n, _ in got), merge_tables([t for _, t in got])) for c, got in pieces.items()}
 
 
 def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=8, minIntron=70, maxIntron=500000,
-              qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0):
+              qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False):
     """Writes ``outputPath`` (a BED12 file) and returns the number of junctions.  ``minMapQ`` / ``requireFlags`` / ``excludeFlags``:
-    the read filter of ``process`` (samtools view's -q / -f / -F; changes results) -- the junctions of the reads that pass."""
+    the read filter of ``process`` (samtools view's -q / -f / -F; changes results) -- the junctions of the reads that pass.
+    ``strandFromXS``: for an unstranded library, the strand column from the reads' XS:A tag (regtools' ``-s XS``) instead of ``?``;
+    an alternative to ``isStranded``."""
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
     stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
     if isStranded and stranded == 0:
         raise ValueError("strandedType must be 'fr' or 'rf' for a stranded library")
+    if strandFromXS and isStranded:
+        raise ValueError("strandFromXS and isStranded are alternatives: the strand of the tag, or the strand of the read")
+    if strandFromXS:
+        stranded = native.STRAND_FROM_XS
     filt = _process.read_filter(minMapQ, requireFlags, excludeFlags)
-    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, filt)   # (on the GPU(s), like `process`)
+    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, filt, aux_strand=bool(strandFromXS))   # (on the GPU(s), like `process`)
     try:
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
-        tables = tables_of_source(source, tuple(devices), chroms, stranded, minAnchor, minIntron, maxIntron)
+        tally = [0, 0, 0] if strandFromXS else None
+        tables = tables_of_source(source, tuple(devices), chroms, stranded, minAnchor, minIntron, maxIntron, tally=tally)
         if isinstance(source, native.BamFile) and not source.wait_all():
             raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
         _process.log_filter(source, filt, log)
+        if strandFromXS:
+            log_xs_tally(tally, log)
     finally:
         if hasattr(source, "close"):
             source.close()

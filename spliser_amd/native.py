@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SPLISER_HIP_LIB") or os.path.join(HERE, "libspliser_h
 CSRC = os.path.join(HERE, "csrc")
 
 STRANDED_CODE = {None: 0, False: 0, "": 0, "fr": 1, "rf": 2}
+STRAND_FROM_XS = 3   # spl_junctions' fourth mode: a junction's strand is its read's strand byte (the aligner's XS:A tag)
 
 
 class SpliserNativeError(RuntimeError):
@@ -48,9 +49,9 @@ EXPORTS = [
     "spl_abi_version", "spl_last_error", "spl_device_count", "spl_trim", "spl_create", "spl_create_on_stream", "spl_destroy",
     "spl_sync", "spl_pass_barrier", "spl_timer_begin", "spl_timer_end", "spl_kernel_timing_begin", "spl_kernel_timing_collect", "spl_prof_enable", "spl_prof_report", "spl_count", "spl_sse", "spl_sites_upload", "spl_sites_free",
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
-    "spl_soa_upload", "spl_soa_upload2", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes",
+    "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_reads_has_strand", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
-    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_filter_counts", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
+    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
     "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
@@ -151,7 +152,10 @@ class SiteArrays(object):
 
 
 class ReadArrays(object):
-    def __init__(self, pos, flag, cig_off, cigar):
+    """``xs``: None, or a strand byte per read ('+', '-', 0) for ``Context.upload_soa`` (``spl_soa_upload3``); no other call reads it."""
+
+    def __init__(self, pos, flag, cig_off, cigar, xs=None):
+        self.xs = None if xs is None else _arr(xs, np.uint8)
         self.pos = _to_i32(pos, "read position")
         self.flag = _arr(flag, np.uint16)
         self.cig_off = _arr(cig_off, np.uint32)
@@ -159,6 +163,8 @@ class ReadArrays(object):
         self.n = int(self.pos.shape[0])
         if self.cig_off.shape[0] != self.n + 1:
             raise ValueError("cig_off must have n_reads + 1 entries")
+        if self.xs is not None and self.xs.shape[0] != self.n:
+            raise ValueError("xs must have n_reads entries")
         self.c = spl_reads(self.n, _ptr(self.pos), _ptr(self.flag), _ptr(self.cig_off), _ptr(self.cigar))
 
 
@@ -245,17 +251,24 @@ class Context(object):
         _check(lib().spl_reads_upload_segments(self._h, ctypes.c_int(n), segs, shifts, ctypes.byref(h)))
         return DeviceReads(self, h, total)
 
-    def upload_soa(self, segments, max_ends=None):
+    def upload_soa(self, segments, max_ends=None, with_strand=False):
         """segments: [ReadArrays-like with .c] -> the BAM-native arrays as they are, laid end to end in device memory
         (``spl_soa_upload``): what a decode on the device leaves.  Read sets are laid out from them by the layout kernel
-        (``DeviceReads.add_soa`` + ``finish``; ``relayout``).  ``max_ends``: per segment the last base its reads cover, if known."""
+        (``DeviceReads.add_soa`` + ``finish``; ``relayout``).  ``max_ends``: per segment the last base its reads cover, if known.
+        ``with_strand``: every segment's ``xs`` goes up as a fifth array (``spl_soa_upload3``), for ``junctions(STRAND_FROM_XS)``."""
         n = len(segments)
         segs = (spl_reads * max(n, 1))()
         for k, reads in enumerate(segments):
             segs[k] = reads.c
         h = ctypes.c_void_p()
         ends = None if max_ends is None else (ctypes.c_int64 * max(n, 1))(*[int(v) if v is not None else -1 for v in max_ends])
-        _check(lib().spl_soa_upload2(self._h, ctypes.c_int(n), segs, ends, ctypes.byref(h)))
+        if with_strand:
+            if any(r.xs is None for r in segments):
+                raise ValueError("upload_soa(with_strand=True): every segment needs its xs array")
+            xs = (ctypes.c_void_p * max(n, 1))(*[r.xs.ctypes.data for r in segments])
+            _check(lib().spl_soa_upload3(self._h, ctypes.c_int(n), segs, ends, xs, ctypes.byref(h)))
+        else:
+            _check(lib().spl_soa_upload2(self._h, ctypes.c_int(n), segs, ends, ctypes.byref(h)))
         return DeviceSoA(self, h, [r.n for r in segments])
 
     def layout_read_segments(self, soa, shifts):
@@ -382,6 +395,13 @@ class DeviceReads(object):
         _check(lib().spl_reads_finish(self.ctx._h, self._h))
         return self
 
+    def has_strand(self):
+        """True when the (finished) set is fused and its device arrays include the reads' strand bytes: what
+        ``junctions(STRAND_FROM_XS)`` needs (a decode after ``BamFile.set_aux_strand``, ``upload_soa(with_strand=True)``)."""
+        out = ctypes.c_int(0)
+        _check(lib().spl_reads_has_strand(self._h, ctypes.byref(out)))
+        return bool(out.value)
+
     def junctions_stats(self):
         """-> (bytes of the device table the last ``junctions`` call on this context allocated, device ms of its launches or -1)."""
         b, ms = ctypes.c_int64(0), ctypes.c_float(-1.0)
@@ -411,7 +431,8 @@ class DeviceReads(object):
 
     def junctions(self, stranded=0, min_anchor=0, min_intron=0, max_intron=0):
         """Junction table of this read set, computed on the device (``spl_junctions``): dict of arrays left, right,
-        strand (bytes '+', '-' or '?'), count, anchor_left, anchor_right, sorted by (left, right, strand)."""
+        strand (bytes '+', '-' or '?'), count, anchor_left, anchor_right, sorted by (left, right, strand).  ``stranded``: 0, 1
+        (fr), 2 (rf) or ``STRAND_FROM_XS``: the reads' strand bytes, up to three rows a junction (``has_strand`` sets only)."""
         n = ctypes.c_int64(0)
         _check(lib().spl_junctions(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int32(int(min_anchor)),
                                    ctypes.c_int32(int(min_intron)), ctypes.c_int32(int(max_intron)), ctypes.byref(n)))
@@ -596,15 +617,18 @@ class BamFile(object):
     ``min_mapq``, ``require_flags``, ``exclude_flags``: samtools view's -q / -f / -F (``spl_bam_set_filter``); a record that fails
     them is never extracted, whoever decodes the file.  ``filter_counts`` says how many did."""
 
-    def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0):
+    def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False):
         self._h = ctypes.c_void_p()
         self.filter = (int(min_mapq), int(require_flags), int(exclude_flags))
-        filtered = self.filter != (0, 0, 0)   # (the filter must be there before the decode starts: opened deferred, started below)
+        self.aux_strand = False
+        filtered = self.filter != (0, 0, 0) or bool(aux_strand)   # (both must be there before the decode starts: opened deferred, started below)
         opener = lib().spl_bam_open_deferred if defer or filtered else (lib().spl_bam_open_stream if stream else lib().spl_bam_open)
         _check(opener(os.fsencode(path), ctypes.c_int(threads), ctypes.byref(self._h)))
         if filtered:
             try:
                 self.set_filter(*self.filter)
+                if aux_strand:
+                    self.set_aux_strand(True)
                 if not defer:
                     _check(lib().spl_bam_start(self._h))
                     if not stream:
@@ -623,6 +647,13 @@ class BamFile(object):
         """The read filter of a ``defer=True`` file nobody decodes yet (``spl_bam_set_filter``; an error afterwards)."""
         _check(lib().spl_bam_set_filter(self._h, ctypes.c_int(int(min_mapq)), ctypes.c_int(int(require_flags)), ctypes.c_int(int(exclude_flags))))
         self.filter = (int(min_mapq), int(require_flags), int(exclude_flags))
+
+    def set_aux_strand(self, on=True):
+        """A ``defer=True`` file nobody decodes yet: the decode -- whoever does it -- also leaves a strand byte per placed read, the
+        aligner's XS:A tag of the spliced ones (``spl_bam_set_aux_strand``; an error afterwards).  ``reads(chrom).xs`` has them,
+        a read set of the device decode ``has_strand()``."""
+        _check(lib().spl_bam_set_aux_strand(self._h, ctypes.c_int(1 if on else 0)))
+        self.aux_strand = bool(on)
 
     def filter_counts(self):
         """-> (records dropped by their flags, records dropped by their MAPQ alone); waits for the end of the decode."""
@@ -804,6 +835,11 @@ class BamFile(object):
         rs.cig_off = cig_off
         rs.cigar = view(r.cigar, n_cig, np.uint32) if n_cig else np.zeros(0, np.uint32)
         rs.max_end = me.value
+        rs.xs = None
+        if self.aux_strand:
+            xp = ctypes.c_void_p()
+            _check(lib().spl_bam_aux_strand(self._h, ctypes.c_int(tid), ctypes.byref(xp)))
+            rs.xs = view(xp.value, n, np.uint8) if xp.value else None
         self._views[chrom] = rs
         return rs
 
@@ -852,6 +888,15 @@ class _BamHandle(object):
                 lib().spl_bam_close(cls._parked.pop(key))
         for rs in views.values():
             weakref.finalize(rs.pos, gone, None)
+
+
+def aux_strand_host(aux):
+    """The decoders' walk over one record's aux area on the host (``spl_bam_aux_strand_host``): bytes -> ``'+'``, ``'-'`` or 0 as
+    an int."""
+    buf = np.frombuffer(bytes(aux), np.uint8)
+    out = ctypes.c_uint8(0)
+    _check(lib().spl_bam_aux_strand_host(_ptr(buf) if buf.size else None, ctypes.c_uint32(int(buf.size)), ctypes.byref(out)))
+    return out.value
 
 
 def junction_walk_host(ops, pos, min_anchor=0, min_intron=0, max_intron=0):

@@ -55,9 +55,10 @@ def log_filter(source, filt, log, name=None):
 class _SamSource(object):
     """Reads from SAM text (small inputs / fixtures)."""
 
-    def __init__(self, path, min_mapq=0, require_flags=0, exclude_flags=0):
+    def __init__(self, path, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False):
         self._counts = [0, 0, 0]
-        self.ref_names, self._sets = samio.read_sam(path, min_mapq, require_flags, exclude_flags, counts=self._counts)
+        self.aux_strand = bool(aux_strand)
+        self.ref_names, self._sets = samio.read_sam(path, min_mapq, require_flags, exclude_flags, counts=self._counts, aux_strand=aux_strand)
         self.n_records = self._counts[0]
 
     def reads(self, chrom):
@@ -67,17 +68,18 @@ class _SamSource(object):
         return self._counts[1], self._counts[2]
 
 
-def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER):
+def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER, aux_strand=False):
     """BAM (BGZF) through the native decoder; plain SAM text through the Python reader.  ``stream=True``: the BAM decoder
     returns after the header and decodes in the background (``native.BamFile``); ``defer=True``: nothing is decoded until
-    somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``read_filter``: which records either keeps."""
+    somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``read_filter``: which records either keeps.
+    ``aux_strand``: either also leaves a strand byte per read, the XS:A tag of the spliced ones (``--strandFromXS``)."""
     with open(path, "rb") as fh:
         magic = fh.read(4)
     q, f, F = read_filter
     if magic[:2] == b"\x1f\x8b":
-        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F)
+        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=aux_strand)
     if magic[:1] == b"@" or b"\t" in open(path, "rb").readline():
-        return _SamSource(path, q, f, F)
+        return _SamSource(path, q, f, F, aux_strand)
     raise native.SpliserNativeError(-5, "%s is neither BGZF/BAM nor SAM text" % path)
 
 
@@ -94,11 +96,12 @@ def wait_deferred_close():
     return time.perf_counter() - t0
 
 
-def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER):
+def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER, aux_strand=False):
     """The alignment file opened and its decode started: on the GPU(s) -- with several devices every one inflates and extracts
     the stretch of the file that holds its own references (``BamFile.decode_on_devices_async``), and counts them -- or, told so
-    (``gpuDecode=False``), on host threads.  SAM text has one reader.  ``read_filter`` is with the source before any of them starts."""
-    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter)
+    (``gpuDecode=False``), on host threads.  SAM text has one reader.  ``read_filter`` is with the source before any of them starts,
+    and so is ``aux_strand`` (``BamFile.set_aux_strand``: a strand byte per read for ``--strandFromXS``)."""
+    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter, aux_strand=aux_strand)
     if isinstance(source, native.BamFile) and gpuDecode is not False:
         try:
             if len(devices) > 1:
@@ -470,8 +473,12 @@ def write_tsv(output_path, table, results, is_beta2_cryptic):
 def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
             isStranded=False, strandedType=None, isbeta2Cryptic=False, devices=(0,), threads=0, log=_log, checkJunctions=False,
             gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False,
-            minMapQ=0, requireFlags=0, excludeFlags=0):
+            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False):
     """SpliSER_v0_1_8.py:695-720, keyword-compatible with the reference's argparse dests.
+
+    ``strandFromXS`` (this build only, without ``inBed``, an unstranded library; changes results): a junction's strand is the
+    XS:A tag the aligner wrote on the reads that carry it (regtools' ``-s XS``) instead of ``?`` -- ``junctions(strandFromXS=True)``
+    followed by ``process -b`` on its file, from one decode.
 
     ``inBed=None`` (this build only): no junction file -- the junctions are taken from the reads themselves, in this call, from
     the one decode of the BAM: every chromosome's junction table on the GPU (``spl_junctions``; a read set decoded on the device
@@ -507,14 +514,16 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
         knobs = tuple(d if v is None else int(v) for v, d in zip((minAnchor, minIntron, maxIntron), JUNCTION_DEFAULTS))
         if min(knobs) < 0:
             raise ValueError("minAnchor / minIntron / maxIntron must not be negative")
-    elif not (minAnchor is None and minIntron is None and maxIntron is None) or keepJunctions:
-        raise ValueError("minAnchor / minIntron / maxIntron / keepJunctions belong to a run without inBed: a junction file has its own")
+    elif not (minAnchor is None and minIntron is None and maxIntron is None) or keepJunctions or strandFromXS:
+        raise ValueError("minAnchor / minIntron / maxIntron / keepJunctions / strandFromXS belong to a run without inBed: a junction file has its own")
+    if strandFromXS and isStranded:
+        raise ValueError("strandFromXS and isStranded are alternatives: the strand of the tag, or the strand of the read")
     timings = {}
     t0 = time.perf_counter()
     # The alignment file does not depend on Steps 0-2: it is decoded on native threads while the site table is built here, and
     # goes on decoding while Step 3 counts the chromosomes that are complete.  An unreadable file is an error here already
     # (block directory and header are read by the opening call).
-    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt)     # (the decode runs beside Steps 0-2, wherever it runs)
+    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt, aux_strand=bool(strandFromXS))     # (the decode runs beside Steps 0-2, wherever it runs)
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
@@ -522,7 +531,8 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
         if inBed is None:
             def rows_of_bam():
                 t_j = time.perf_counter()
-                rows = _junction_rows(source, inBAM, outputPath if keepJunctions else None, qChrom, isStranded, strandedType, knobs, devices)
+                rows = _junction_rows(source, inBAM, outputPath if keepJunctions else None, qChrom, isStranded, strandedType, knobs, devices,
+                                      strandFromXS=strandFromXS, log=log)
                 timings["junctions_s"] = time.perf_counter() - t_j
                 return rows
         table = _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam)
@@ -613,7 +623,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
 JUNCTION_DEFAULTS = (8, 70, 500000)     # minAnchor, minIntron, maxIntron of a run without a junction file (the `junctions` command's)
 
 
-def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType, knobs, devices):
+def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType, knobs, devices, strandFromXS=False, log=None):
     """A run without a junction file: every chromosome's junction table from the reads the decode leaves (``-c``: that one's) ->
     [(chrom, table)] of the chromosomes that have a junction, in the order of the header: the lines of the file ``junctions``
     writes, never written -- unless ``keep_prefix`` asks for it (``<prefix>.junctions.bed``, the same bytes)."""
@@ -621,10 +631,15 @@ def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType,
     stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
     if isStranded and stranded == 0:
         raise ValueError("strandedType must be 'fr' or 'rf' for a stranded analysis")
+    if strandFromXS:
+        stranded = native.STRAND_FROM_XS
     chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
-    got = jn.tables_of_source(source, devices, chroms, stranded, *knobs)
+    tally = [0, 0, 0] if strandFromXS else None
+    got = jn.tables_of_source(source, devices, chroms, stranded, *knobs, tally=tally)
     if isinstance(source, native.BamFile) and not source.wait_all():     # (with -c too: an unsorted file's reference may be incomplete)
         raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
+    if strandFromXS and log is not None:
+        jn.log_xs_tally(tally, log)
     tables = {c: t for c, (_, t) in got.items()}
     if keep_prefix is not None:
         jn.write_bed_file(keep_prefix + ".junctions.bed", chroms, tables, *knobs)

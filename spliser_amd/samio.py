@@ -34,10 +34,13 @@ def cigar_string(ops):
 
 
 class ReadSet(object):
-    """Reads of one chromosome in file order (SoA).  ``pos`` is 1-based (SAM POS)."""
-    __slots__ = ("pos", "flag", "cig_off", "cigar", "max_end")
+    """Reads of one chromosome in file order (SoA).  ``pos`` is 1-based (SAM POS).  ``xs``: None, or a strand byte per read
+    (``'+'``, ``'-'``, 0) from the aligner's XS:A tag where the reader was asked for it (``read_sam(aux_strand=True)``,
+    ``native.BamFile.set_aux_strand``)."""
+    __slots__ = ("pos", "flag", "cig_off", "cigar", "max_end", "xs")
 
-    def __init__(self, pos, flag, cig_off, cigar, max_end=None):
+    def __init__(self, pos, flag, cig_off, cigar, max_end=None, xs=None):
+        self.xs = None if xs is None else np.ascontiguousarray(xs, dtype=np.uint8)
         self.pos = np.ascontiguousarray(pos, dtype=np.int32)
         self.flag = np.ascontiguousarray(flag, dtype=np.uint16)
         self.cig_off = np.ascontiguousarray(cig_off, dtype=np.uint32)
@@ -87,11 +90,23 @@ class ReadSet(object):
                    np.asarray(ops, np.int64))
 
 
-def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None):
+def sam_aux_strand(cigar, optional):
+    """The strand byte of one SAM line by the BAM decoder's rule (``spl_bam_set_aux_strand``): 0 unless the CIGAR holds an N op;
+    else the value of the first optional column ``XS:A:`` if it is ``+`` or ``-`` (an ``XS:i:`` is another field), else 0."""
+    if "N" not in cigar:
+        return 0
+    for field in optional:
+        if field.startswith("XS:A:"):
+            v = field[5:].rstrip("\n")
+            return ord(v) if v in ("+", "-") else 0
+    return 0
+
+
+def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None, aux_strand=False):
     """Parse SAM text -> (ref_names, {chrom: ReadSet}).  Keeps every record that has an RNAME, file order -- what ``samtools
     view`` would print; ``min_mapq`` / ``require_flags`` / ``exclude_flags`` are its -q / -f / -F on columns 5 and 2 (the BAM
     decoder's rule, ``spl_bam_set_filter``: flags first, MAPQ as a number).  ``counts``: a list that gets [records seen, dropped
-    by flags, dropped by MAPQ] added to its three entries."""
+    by flags, dropped by MAPQ] added to its three entries.  ``aux_strand``: every ReadSet gets ``xs`` (``sam_aux_strand``)."""
     names, per = [], {}
     seen = by_flags = by_mapq = 0
     with open(path, "r") as handle:
@@ -116,15 +131,17 @@ def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None):
                     continue
             rec = per.get(cols[2])
             if rec is None:
-                rec = per[cols[2]] = ([], [], [0], [])
+                rec = per[cols[2]] = ([], [], [0], [], [])
                 if cols[2] not in names:
                     names.append(cols[2])
             rec[0].append(int(cols[3]))
             rec[1].append(flag)
             rec[3].extend(cigar_ops(cols[5].strip()))
             rec[2].append(len(rec[3]))
+            if aux_strand:
+                rec[4].append(sam_aux_strand(cols[5], cols[11:]))
     sets = {c: ReadSet(np.asarray(p, np.int64), np.asarray(f, np.int64), np.asarray(o, np.int64),
-                       np.asarray(g, np.int64)) for c, (p, f, o, g) in per.items()}
+                       np.asarray(g, np.int64), xs=np.asarray(x, np.uint8) if aux_strand else None) for c, (p, f, o, g, x) in per.items()}
     if counts is not None:
         for k, v in enumerate((seen, by_flags, by_mapq)):
             counts[k] += v
@@ -189,7 +206,7 @@ def _reg2bin(beg, end):
     return 0
 
 
-def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False, unplaced=0, long_cigar_tag=False, mapq=None):
+def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False, unplaced=0, long_cigar_tag=False, mapq=None, tags=None):
     """Write a BAM file.  chrom_reads: list of (chrom, ReadSet) in file order.
 
     with_seq       -- emit a dummy SEQ/QUAL of the query length (realistic record size) instead of '*'
@@ -197,7 +214,11 @@ def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False
     long_cigar_tag -- store every CIGAR with more than 3 ops the way htslib stores >65535-op CIGARs:
                       a placeholder ``<qlen>S<rlen>N`` in the record and the real ops in a CG:B,I tag
     mapq           -- per entry of chrom_reads an array of the reads' MAPQ (default: 60 for every read)
+    tags           -- per entry of chrom_reads a list of raw aux bytes per read (``b"XSA+"``, ...), appended to the record as
+                      they are, behind the CG tag where there is one (default: no tags of the caller's)
     """
+    if tags is not None and (len(tags) != len(chrom_reads) or any(len(t) != rs.n for t, (_, rs) in zip(tags, chrom_reads))):
+        raise ValueError("tags: one bytes object per read of every entry of chrom_reads")
     tid_of = {n: i for i, n in enumerate(ref_names)}
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, ln) for n, ln in zip(ref_names, ref_lengths))
     head = [b"BAM\x01", struct.pack("<i", len(text)), text.encode("ascii"), struct.pack("<i", len(ref_names))]
@@ -223,19 +244,19 @@ def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False
                 name = ("r%d" % serial).encode("ascii") + b"\x00"
                 serial += 1
                 pos0 = int(rs.pos[k]) - 1
-                tags = b""
+                aux = b""
                 rec_ops = ops
                 l_seq = qlen if with_seq else 0
                 if long_cigar_tag and len(ops) > 3:
                     rec_ops = [(qlen << 4) | 4, (rlen << 4) | 3]   # htslib: <l_seq>S<rlen>N placeholder
-                    tags = b"NMC\x00" + b"CGBI" + struct.pack("<i", len(ops)) + struct.pack("<%dI" % len(ops), *ops)
+                    aux = b"NMC\x00" + b"CGBI" + struct.pack("<i", len(ops)) + struct.pack("<%dI" % len(ops), *ops)
                     l_seq = qlen
                 seq = bytes([0x11]) * ((l_seq + 1) // 2)
                 qual = bytes([30]) * l_seq
                 flag = int(rs.flag[k])
                 end0 = pos0 + (rlen if (rlen and not flag & 4) else 1)
                 body = struct.pack("<iiBBHHHiiii", tid, pos0, len(name), 60 if mq is None else int(mq[k]), _reg2bin(pos0, end0), len(rec_ops), flag,
-                                   l_seq, -1, -1, 0) + name + struct.pack("<%dI" % len(rec_ops), *rec_ops) + seq + qual + tags
+                                   l_seq, -1, -1, 0) + name + struct.pack("<%dI" % len(rec_ops), *rec_ops) + seq + qual + aux + (bytes(tags[k_chrom][k]) if tags is not None else b"")
                 buf += struct.pack("<i", len(body)) + body
                 if len(buf) >= _BGZF_BLOCK:
                     flush()
