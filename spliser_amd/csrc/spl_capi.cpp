@@ -2175,15 +2175,20 @@ struct ShareDecode {
         return extract(k, s0, b_done, b1s, win_end, with_recs);
     }
 
-    // Which of the window's blocks are done with: all whose records end inside it.  A block near the window's end may have
-    // looked for its first record, or walked its last one, into bytes that are not there yet: it is told by its flag, or
-    // -- within reach of the end -- by anything being wrong with it, and is looked at again with the next window.  b_done: the
-    // first block that is not; the blocks in front of it are walked on the host (the chain, the prefix sums).  Returns what is wrong
+    // Which of the window's blocks are done with: all whose records end inside it.  A block may have walked its last record, or
+    // looked for its first one, into bytes that are not there yet.  The walk says so by its flag.  The guess cannot: where the
+    // window ends its chain is as long as the bytes allow, and bytes inside a record that look like a record -- of whatever size,
+    // so anywhere in the window, not only near its end -- are taken for a start without the successors that would have told.  Such
+    // a block is known by where it begins: not where the chain of the blocks before it arrived (and whatever else is wrong with it
+    // may come of that).  It is looked at again with the next window, as long as there is one and there is room for it; a start that
+    // is wrong with all the bytes there stays wrong, and is then what the file is declined for.  A block that begins where it must
+    // has read nothing the window's end could have changed: what is wrong with it is wrong with the file.  b_done: the first block
+    // that is not done with; the blocks in front of it are walked on the host (the chain, the prefix sums).  Returns what is wrong
     // with the file, if anything is.
     const char *records_done(size_t s0, size_t b1s, size_t b1, uint64_t win_end, size_t &b_done)
     {
         const bool more = b1 < n_blocks;
-        const uint64_t reach = b1s > s0 ? std::min<uint64_t>((win_end - blocks[s0].out) / 2, ((uint64_t)5 << 18)) : 0;
+        const char *held = nullptr; // what is wrong with the block that waits for the next window, if anything is
         b_done = std::max(b1s, s0);
         for (size_t b = s0; b < b1s; ++b) {
             spl_bscan &sc = scan[b];
@@ -2200,7 +2205,7 @@ struct ShareDecode {
             else if (sc.flags & SPL_BS_UNSORTED) wrong = "not sorted by reference";
             else if (sc.start != expect) wrong = "a guessed record boundary did not hold";
             else if (sc.n_placed && sc.tid_first < last_tid) wrong = "not sorted by reference";
-            if ((sc.flags & SPL_BS_INCOMPLETE) || (wrong && more && blocks[b].out + reach >= win_end)) { b_done = b; break; }
+            if ((sc.flags & SPL_BS_INCOMPLETE) || (wrong && more && sc.start != expect)) { b_done = b; held = (sc.flags & SPL_BS_INCOMPLETE) ? nullptr : wrong; break; }
             if (wrong) return wrong;
             if (sc.n_placed) last_tid = sc.tid_last;
             expect = sc.reached;
@@ -2211,7 +2216,7 @@ struct ShareDecode {
             op_off[b + 1] = op_off[b] + sc.n_ops;
         }
         if (b_done < b1s && b1 == n_blocks) return last_share ? "the file ends inside a record" : "a record runs past the blocks behind a share";
-        if (b_done < b1s && win_end - blocks[b_done].out > HEAD) return "a record larger than the room between two windows";
+        if (b_done < b1s && win_end - blocks[b_done].out > HEAD) return held ? held : "a record larger than the room between two windows";
         if (op_off[b_done] > 0xfffffff0ull) return "more than 2^32 CIGAR operations";
         return nullptr;
     }
