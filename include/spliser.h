@@ -278,6 +278,24 @@ int spl_bam_filter_counts(spl_bam *bam, int64_t *out2);
  * *out = NULL when the file was decoded without them.  struct spl_reads is unchanged.  spl_bam_aux_strand_host: the walk itself
  * over a caller's bytes [aux, aux + len) -> *out (test hook; no file, no GPU). */
 int spl_bam_set_aux_strand(spl_bam *bam, int on);
+/* Library size without a second pass over the file (the reference's README sends the user to `samtools flagstat` for the
+ * Library_size column of the diffSpliSER target file; the reference has no counterpart).  spl_bam_set_flagstat(bam, 1): the
+ * decode -- the device's and the host's alike, whole or in shares -- also counts samtools flagstat's sixteen categories, each for
+ * QC-passed and QC-failed records (FLAG 0x200), over EVERY record of the file: placed or not, with a reference or without.  Under
+ * a read filter a record counts only if it passes the filter, which for this purpose is applied to every record (as `samtools
+ * view -q 10` drops an unmapped record of MAPQ 0); spl_bam_filter_counts keeps its meaning and its values.  The same rule as
+ * spl_bam_set_filter: before anybody decodes the file or waits for it, SPL_ERR_ARG afterwards.  Off by default, and nothing of
+ * the decode changes while it is off.
+ * spl_bam_flagstat: out32[2 * c + q] = records of category c that passed (q = 0) / failed (q = 1) quality control, once the decode
+ * is complete (it waits for that); SPL_ERR_ARG when counting was not switched on.  Categories, a record being PRIMARY when
+ * neither 0x100 nor 0x800 is set: 0 total, 1 primary, 2 secondary (0x100), 3 supplementary (0x800 without 0x100), 4 duplicates
+ * (0x400), 5 primary duplicates, 6 mapped (not 0x4), 7 primary mapped, 8 paired in sequencing (primary and 0x1), 9 read1 (8 and
+ * 0x40), 10 read2 (8 and 0x80), 11 properly paired (8, 0x2, not 0x4), 12 with itself and mate mapped (8, not 0x4, not 0x8),
+ * 13 singletons (8, 0x8, not 0x4), 14 with mate mapped to a different chr (12 and next_refID != refID), 15 ... and MAPQ >= 5.
+ * spl_flagstat_add_host: the definition itself on one record's fields, added to inout32 (test hook; no file, no GPU). */
+int spl_bam_set_flagstat(spl_bam *bam, int on);
+int spl_bam_flagstat(spl_bam *bam, int64_t *out32);
+int spl_flagstat_add_host(uint32_t flag, int32_t tid, int32_t next_tid, uint32_t mapq, int64_t *inout32);
 int spl_bam_aux_strand(const spl_bam *bam, int tid, const uint8_t **out);
 int spl_bam_aux_strand_host(const uint8_t *aux, uint32_t len, uint8_t *out);
 int spl_bam_decode_device(spl_ctx *ctx, spl_bam *bam, int *on_device_out);

@@ -11,6 +11,11 @@ XS:A tag the aligner wrote on its reads, for an unstranded library whose junctio
 ``--isStranded``, and an error with ``-b``.  ``--minMapQ`` / ``--requireFlags`` / ``--excludeFlags`` (``process``, ``junctions``, ``combine``, ``combineShallow``) are
 samtools view's -q / -f / -F applied while the BAM is decoded: the run's results are those of the pre-filtered file.  Extra sub-command: ``junctions`` writes that BED12 junction file on its own, for ``process -b`` here or for the
 reference (which leaves it to regtools); ``process`` without ``-b`` writes what ``junctions`` + ``process -b`` write.
+``process --flagstat`` also writes ``<outputPath>.flagstat.txt``, samtools flagstat's sixteen lines counted by the decode the
+command does anyway, over the whole file whatever ``-c`` / ``-g`` say, and logs the library size (the ``Library_size`` column of
+the diffSpliSER target file, for which the reference's README sends the user to ``samtools flagstat``); it changes no result.
+Extra sub-command ``flagstat -B x.bam -o PATH`` writes those lines alone (the filter and engine flags, ``--gpuDecode`` /
+``--hostDecode``).  Under a read filter the counters are the pre-filtered file's.
 """
 import argparse
 import sys
@@ -69,8 +74,18 @@ def build_parser():
     p.add_argument("--keepReads", dest="keepReads", default=False, action="store_true",
                    help="(this build only) also write <outputPath>.SpliSER.reads (flag, POS, CIGAR of every read): combine takes it "
                         "instead of decoding the BAM again while it is still that BAM's")
+    p.add_argument("--flagstat", dest="flagstat", default=False, action="store_true",
+                   help="(this build only) also write <outputPath>.flagstat.txt: samtools flagstat's counters of the whole BAM, from "
+                        "the decode this command does anyway, and log the library size (mapped reads); changes no result")
     _filter_flags(p)
     _engine_flags(p)
+    f = sub.add_parser("flagstat", help="(this build only) samtools flagstat's counters of a BAM, counted while it is decoded on the GPU")
+    f.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    f.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="path of the text file to write")
+    f.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
+    f.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    _filter_flags(f)
+    _engine_flags(f)
     c = sub.add_parser("combine")
     c.add_argument("-S", "--samplesFile", dest="samplesFile", required=True,
                    help="three-column .tsv: sample name, path of its .SpliSER.tsv, path of its BAM")
@@ -161,7 +176,7 @@ def main(argv=None):
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -201,6 +216,9 @@ def main(argv=None):
     elif command == "junctions":
         from .junctions import junctions
         junctions(devices=devices, threads=threads, **kwargs)
+    elif command == "flagstat":
+        from .flagstat import flagstat
+        flagstat(devices=devices, threads=threads, **kwargs)
     else:
         parser.error("sub-command %r is not part of this build yet" % command)
     print("Total runtime (s): \t" + str(timeit.default_timer() - start))

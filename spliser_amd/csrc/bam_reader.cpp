@@ -36,6 +36,7 @@
 #include "../../include/spliser.h"
 #include "spl_bam.h"
 #include "spl_bam_aux.h"
+#include "spl_flagstat.h"
 #include "spl_error.h"
 
 namespace {
@@ -481,6 +482,8 @@ struct spl_bam {
     spl_bam_filter filter = {0, 0, 0}; // which placed records are kept (spl_bam_set_filter; fixed once claim != 0)
     int64_t dropped[2] = {0, 0};       // records the filter dropped: by their flags, by their MAPQ
     bool aux_strand = false;           // a strand byte per placed read beside its flag (spl_bam_set_aux_strand; fixed once claim != 0)
+    bool flagstat = false;             // the decode counts the flagstat categories (spl_bam_set_flagstat; fixed once claim != 0)
+    int64_t fstat[2 * SPL_FS_CATEGORIES] = {0}; // ... over every record the filter keeps, placed or not: [2 c + q] (spl_flagstat.h)
     // ---- BAM-native arrays per reference, assembled on demand (spl_bam_reads) ----
     std::vector<RefFinal> refs_storage; // (never resized after the header: RefFinal is not copyable)
     std::vector<char> assembled;
@@ -502,7 +505,7 @@ struct spl_bam {
     std::vector<DevShare> dev_shares;
     // a decode in shares (spl_bam_share_plan): the plan, and what the shares' decoders have reported so far
     std::vector<spl_bam_share> shares;
-    struct ShareResult { bool reported = false, failed = false; void *handle = nullptr; void (*free_fn)(void *) = nullptr; std::vector<int64_t> first, n, max_end; int64_t n_records = 0, dropped[2] = {0, 0}; };
+    struct ShareResult { bool reported = false, failed = false; void *handle = nullptr; void (*free_fn)(void *) = nullptr; std::vector<int64_t> first, n, max_end; int64_t n_records = 0, dropped[2] = {0, 0}, fstat[2 * SPL_FS_CATEGORIES] = {0}; };
     std::vector<ShareResult> share_results;
     bool shares_on_device = false;
     std::atomic<bool> cancel{false};       // spl_bam_cancel: whoever decodes stops at the next batch / window; nobody starts
@@ -552,8 +555,10 @@ inline const uint8_t *record_cigar(const uint8_t *r, uint32_t bs, size_t need, u
 // Records the filter does not keep are counted (dropped[0]: by flags, [1]: by MAPQ) and otherwise treated like records without a position.
 // want_xs: one more array per part, a strand byte per read -- the aux area of a read whose CIGAR holds an N op walked by the
 // function the device's extraction calls (spl_bam_aux.h), 0 for every other read.  A CIGAR parked in a CG tag is the read's CIGAR.
+// fstat (or null): the flagstat counters, [2 c + q], of EVERY record walked that the filter keeps -- without a reference or a
+// position too, where `dropped` has placeable records only (spl_flagstat.h: the one definition, the device's scan's as well).
 const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, const spl_bam_filter &filter, bool want_xs, Arena &arena, std::vector<Part> &parts,
-                               int64_t &n_records, int64_t *dropped, std::string &err, bool &fatal)
+                               int64_t &n_records, int64_t *dropped, int64_t *fstat, std::string &err, bool &fatal)
 {
     struct Run { int32_t tid; size_t n, ops; const uint8_t *begin; };
     Run few[4];
@@ -577,6 +582,7 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
         const size_t need = 32 + (size_t)l_name + 4ull * n_cig + ((size_t)l_seq + 1) / 2 + l_seq;
         if (need > bs) { err = "corrupt record (fields exceed block_size)"; fatal = true; break; }
         n_records++;
+        if (fstat && spl_bam_filter_verdict(filter, le16(r + 14), r[9]) == SPL_BAM_KEPT) spl_flagstat_add(fstat, le16(r + 14), tid, le32s(r + 20), r[9]);
         const int verdict = tid >= 0 && tid < n_ref && pos0 >= 0 ? spl_bam_filter_verdict(filter, le16(r + 14), r[9]) : SPL_BAM_KEPT;
         if (verdict != SPL_BAM_KEPT) dropped[verdict - 1]++;
         else if (tid >= 0 && tid < n_ref && pos0 >= 0) {
@@ -771,6 +777,7 @@ struct BatchOut {
     size_t len = 0, start = 0, i0 = 0, i1 = 0; // bytes inflated, guessed first boundary; the batch's blocks
     uint64_t u0 = 0;                            // offset of the batch in the inflated stream
     int64_t nrec = 0, dropped[2] = {0, 0};
+    int64_t fstat[2 * SPL_FS_CATEGORIES] = {0}; // (spl_bam_set_flagstat: the batch's counters, added to the file's when the batch is committed)
     bool inflate_bad = false, parse_bad = false;
     bool known = false;                         // the first boundary is the end of the BAM header, not a guess
     bool skip = false;                          // nothing but BAM header in it
@@ -784,6 +791,7 @@ void decode_worker(spl_bam *bam)
     const int n_ref = bam->n_refs;
     const spl_bam_filter filter = bam->filter; // (nobody changes it once a decoder has the file)
     const bool want_xs = bam->aux_strand;
+    const bool want_stat = bam->flagstat;
     const NodeCpus node; // the NUMA node this thread runs on (the opening thread's, inherited): all worker threads stay there
     auto env_num = [](const char *name, long dflt) { const char *e = getenv(name); const long v = e ? atol(e) : 0; return v > 0 ? v : dflt; };
     const size_t BATCH = (size_t)env_num("SPL_BAM_BATCH_BLOCKS", 32);
@@ -869,7 +877,7 @@ void decode_worker(spl_bam *bam)
                 o.start = (size_t)(p - buf);
                 std::string err;
                 bool fatal = false;
-                reached = (size_t)(extract_records(p, end, n_ref, filter, want_xs, arena, o.parts, o.nrec, o.dropped, err, fatal) - buf);
+                reached = (size_t)(extract_records(p, end, n_ref, filter, want_xs, arena, o.parts, o.nrec, o.dropped, want_stat ? o.fstat : nullptr, err, fatal) - buf);
                 o.parse_bad = fatal;
                 if (!o.known) o.head.assign((const uint8_t *)buf, (const uint8_t *)buf + o.start);
                 o.tail.assign((const uint8_t *)buf + reached, end);
@@ -894,12 +902,13 @@ void decode_worker(spl_bam *bam)
     size_t n_resync = 0;
     auto walk = [&](const uint8_t *p0, const uint8_t *p1, bool &fatal) { // sequential, authoritative: commits what it parses
         std::vector<Part> seq;
-        int64_t n = 0, drop[2] = {0, 0};
-        const uint8_t *r = extract_records(p0, p1, n_ref, filter, want_xs, arena_mine, seq, n, drop, fail, fatal);
+        int64_t n = 0, drop[2] = {0, 0}, fs[2 * SPL_FS_CATEGORIES] = {0};
+        const uint8_t *r = extract_records(p0, p1, n_ref, filter, want_xs, arena_mine, seq, n, drop, want_stat ? fs : nullptr, fail, fatal);
         merge_parts(bam, seq);
         bam->n_records += n;
         bam->dropped[0] += drop[0];
         bam->dropped[1] += drop[1];
+        for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] += fs[c];
         return r;
     };
     size_t n_batches = 0;
@@ -959,6 +968,7 @@ void decode_worker(spl_bam *bam)
             bam->n_records += o.nrec;
             bam->dropped[0] += o.dropped[0];
             bam->dropped[1] += o.dropped[1];
+            for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] += o.fstat[c];
             carry.swap(o.tail);
         } else { // the guess did not hold: this batch again, sequentially, from the known boundary
             ++n_resync;
@@ -977,6 +987,7 @@ void decode_worker(spl_bam *bam)
         o.tail.clear();
         o.nrec = 0;
         o.dropped[0] = o.dropped[1] = 0;
+        for (int64_t &x : o.fstat) x = 0;
         const double c2 = now();
         t_merge += c2 - c1;
         o.state.store(0, std::memory_order_relaxed);
@@ -1158,6 +1169,48 @@ bool spl_bam_get_aux_strand(spl_bam *bam)
 {
     std::lock_guard<std::mutex> lock(bam->mu);
     return bam->aux_strand;
+}
+
+// The flagstat counters, counted by whoever decodes the file.  The same rule as spl_bam_set_filter: only while nobody decodes the
+// file or waits for it.
+extern "C" int spl_bam_set_flagstat(spl_bam *bam, int on)
+{
+    if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_flagstat: null argument");
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (bam->claim != 0 || bam->done)
+        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_flagstat: the file is being decoded (or waited for) already", bam->path.c_str());
+    bam->flagstat = on != 0;
+    return SPL_OK;
+}
+
+bool spl_bam_get_flagstat(spl_bam *bam)
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    return bam->flagstat;
+}
+
+// The counters: waits for the end of the decode, like spl_bam_filter_counts; the decode's error is the call's.
+extern "C" int spl_bam_flagstat(spl_bam *bam, int64_t *out32)
+{
+    if (!bam || !out32) return spl_set_error(SPL_ERR_ARG, "spl_bam_flagstat: null argument");
+    {
+        std::lock_guard<std::mutex> lock(bam->mu);
+        if (!bam->flagstat) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_flagstat: counting was not switched on (spl_bam_set_flagstat)", bam->path.c_str());
+    }
+    (void)spl_bam_start_host(bam);
+    std::unique_lock<std::mutex> lock(bam->mu);
+    bam->cv.wait(lock, [&]() { return bam->done; });
+    if (bam->err_code) return spl_set_error(bam->err_code, "%s", bam->error.c_str());
+    for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) out32[c] = bam->fstat[c];
+    return SPL_OK;
+}
+
+// The definition itself on one record's fields (test hook; no file, no GPU).
+extern "C" int spl_flagstat_add_host(uint32_t flag, int32_t tid, int32_t next_tid, uint32_t mapq, int64_t *inout32)
+{
+    if (!inout32) return spl_set_error(SPL_ERR_ARG, "spl_flagstat_add_host: null argument");
+    spl_flagstat_add(inout32, flag, tid, next_tid, mapq);
+    return SPL_OK;
 }
 
 // The walk itself on a caller's bytes (test hook; no file, no GPU): *out = '+', '-' or 0.
@@ -1381,7 +1434,7 @@ uint64_t spl_bam_header_end(const spl_bam *bam) { return bam->header_bytes; }
 int spl_bam_thread_count(const spl_bam *bam) { return bam->n_threads; }
 
 int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar, const int64_t *ref_first, const int64_t *ref_n,
-                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped)
+                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped, const int64_t *flagstat)
 {
     std::lock_guard<std::mutex> lock(bam->mu);
     if (bam->claim != 1) return spl_set_error(SPL_ERR_ARG, "spl_bam_adopt: the file is not claimed by the device decoder");
@@ -1411,6 +1464,7 @@ int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off,
     bam->n_records = n_records_total;
     bam->dropped[0] = dropped[0];
     bam->dropped[1] = dropped[1];
+    for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] = flagstat ? flagstat[c] : 0;
     bam->max_tid_seen = bam->n_refs - 1;
     bam->complete_upto = bam->n_refs;
     bam->done = true;
@@ -1642,7 +1696,7 @@ int spl_bam_share_get(spl_bam *bam, int k, spl_bam_share *out)
 }
 
 int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *), const int64_t *ref_first, const int64_t *ref_n,
-                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, int failed)
+                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, const int64_t *flagstat, int failed)
 {
     std::unique_lock<std::mutex> lock(bam->mu);
     if (k < 0 || (size_t)k >= bam->share_results.size() || bam->share_results[(size_t)k].reported) {
@@ -1659,6 +1713,7 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
     if (!r.failed) {
         r.dropped[0] = dropped[0];
         r.dropped[1] = dropped[1];
+        for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) r.fstat[c] = flagstat ? flagstat[c] : 0;
         r.first.assign(ref_first, ref_first + bam->n_refs);
         r.n.assign(ref_n, ref_n + bam->n_refs);
         r.max_end.assign(ref_max_end, ref_max_end + bam->n_refs);
@@ -1689,7 +1744,7 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
         return SPL_OK;
     }
     bam->lazy = true;
-    int64_t n_all = 0, drop[2] = {0, 0};
+    int64_t n_all = 0, drop[2] = {0, 0}, fs[2 * SPL_FS_CATEGORIES] = {0};
     for (size_t s = 0; s < bam->share_results.size(); ++s) {
         spl_bam::ShareResult &x = bam->share_results[s];
         spl_bam::DevShare d;
@@ -1699,6 +1754,7 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
         n_all += x.n_records;
         drop[0] += x.dropped[0];
         drop[1] += x.dropped[1];
+        for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) fs[c] += x.fstat[c];
         for (int t = 0; t < bam->n_refs; ++t) { // (a reference may have a part in several shares: file order = share order)
             if (x.n[(size_t)t] <= 0) continue;
             PendingPart *pp = new PendingPart();
@@ -1715,6 +1771,7 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
     bam->n_records = n_all;
     bam->dropped[0] = drop[0];
     bam->dropped[1] = drop[1];
+    for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] = fs[c];
     bam->max_tid_seen = bam->n_refs - 1;
     bam->complete_upto = bam->n_refs;
     bam->shares_on_device = true;

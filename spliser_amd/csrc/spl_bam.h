@@ -26,6 +26,7 @@ SPL_BAM_HD inline int spl_bam_filter_verdict(const spl_bam_filter &f, uint32_t f
 }
 spl_bam_filter spl_bam_get_filter(spl_bam *bam);           // what the file's decoders are to apply (fixed once a decode has begun)
 bool spl_bam_get_aux_strand(spl_bam *bam);                 // ... and whether they leave a strand byte per placed read (spl_bam_set_aux_strand)
+bool spl_bam_get_flagstat(spl_bam *bam);                   // ... and whether they count the flagstat categories (spl_bam_set_flagstat, spl_flagstat.h)
 
 // The reads of reference `tid` as a packer source: the decoder's own parts, in file order, nothing copied.  Waits until the
 // reference is complete (spl_bam_wait_ref).  The views stay valid until spl_bam_release_ref(tid) or spl_bam_close.
@@ -48,9 +49,10 @@ int spl_bam_thread_count(const spl_bam *bam);
 bool spl_bam_sample_density(spl_bam *bam, size_t b_lo, size_t b_hi, uint64_t *n_rec_out, uint64_t *n_ops_out, uint64_t *n_bytes_out);
 // The placed records of the whole file in file order as four malloc'ed arrays (the file takes them over and frees them with
 // free()); reference t has records [ref_first[t], ref_first[t] + ref_n[t]), cig_off holds n_total + 1 offsets into cigar.
-// dropped[2]: the records the file's filter dropped by their flags / by their MAPQ (spl_bam_filter_counts).
+// dropped[2]: the records the file's filter dropped by their flags / by their MAPQ (spl_bam_filter_counts).  flagstat: the 32
+// counters of spl_bam_flagstat over every record of the file, or null (nobody asked: spl_bam_get_flagstat).
 int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar, const int64_t *ref_first, const int64_t *ref_n,
-                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped);
+                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped, const int64_t *flagstat);
 // what the device decoder keeps in device memory for the device packer: an opaque handle, freed with the file
 void spl_bam_set_device_reads(spl_bam *bam, void *handle, void (*free_fn)(void *));
 void *spl_bam_device_reads(spl_bam *bam, int tid);          // the handle that holds ALL of reference `tid` (null: none does -- no device decode, or the reference lies in several shares)
@@ -68,9 +70,11 @@ struct spl_bam_share { uint64_t block_lo, block_hi; int32_t tid_lo, tid_hi; uint
 // file; later calls return the first plan.
 int spl_bam_share_get(spl_bam *bam, int k, spl_bam_share *out);
 // A share's decoder is done: `handle` holds its records (share-local first record per reference in ref_first), or failed != 0.
-// When the last share has reported the file is complete -- or, if one failed, everything is dropped and the host threads decode.
+// When the last share has reported the file is complete -- or, if one failed, everything is dropped and the host threads decode
+// (and count: the shares' flagstat counters go with their reads).  flagstat: the share's 32 counters -- of the records that BEGIN
+// in its own blocks, so that the shares' add up to the file's -- or null.
 int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *), const int64_t *ref_first, const int64_t *ref_n,
-                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, int failed);
+                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, const int64_t *flagstat, int failed);
 int spl_bam_shares_on_device(spl_bam *bam);
 bool spl_bam_cancelled(const spl_bam *bam);                   // spl_bam_cancel was called: stop at the next window                  // 1: all shares reported and none failed
 // spl_bam_adopt with null arrays = the reads stay on the device; `fetch(handle, ...)` brings malloc'ed host copies when a host-side

@@ -24,6 +24,7 @@
 #include "../../include/spliser.h"
 #include "spl_bam.h"
 #include "spl_inflate.h"
+#include "spl_flagstat.h"
 #include "spl_devpack.h"
 #include "spl_device.h"
 #include "spl_error.h"
@@ -1351,7 +1352,11 @@ static int add_segment_device(spl_ctx *c, spl_dreads *d, DeviceReads *dev, int64
 // that straddles two windows: the bytes from the first block that is not done with to the window's end are copied in front of the
 // next window's buffer (its head room), so that scan and extraction see them in one piece; the blocks are not inflated twice.
 namespace {
-struct ShareOut { DeviceReads *reads = nullptr; int64_t n_all = 0, dropped[2] = {0, 0}; bool to_host = false; bool more_tokens = false; }; // (dropped: by the read filter -- flags, MAPQ)
+struct ShareOut { // (dropped: by the read filter -- flags, MAPQ; flagstat: the share's counters, spl_flagstat.h, zeros when nobody asked)
+    DeviceReads *reads = nullptr;
+    int64_t n_all = 0, dropped[2] = {0, 0}, flagstat[2 * SPL_FS_CATEGORIES] = {0};
+    bool to_host = false; bool more_tokens = false;
+};
 // What the caller of decode_share does with the share's reads, called by decode_share itself as its LAST act before it gives its
 // buffers, streams and events back -- which takes 10 ms for a large file, and whoever waits for the file's references need not.
 typedef std::function<int(ShareOut &)> Publish;
@@ -1371,7 +1376,7 @@ extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_ou
         spl_bam_set_device_reads(bam, keep, free_device_reads);
         spl_bam_set_fetch(bam, fetch_device_reads);
         spl_bam_set_fetch_xs(bam, fetch_device_xs);
-        const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.n_all, res.dropped);
+        const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.n_all, res.dropped, res.flagstat);
         if (rc) spl_bam_set_device_reads(bam, nullptr, nullptr);
         if (rc == SPL_OK && on_device_out) *on_device_out = 1;
         t_pub = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
@@ -1403,7 +1408,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     const Publish report = [&](ShareOut &res) -> int { // (a share that is done: reported at once, the last one to report completes the file)
         spl_bam_set_fetch(bam, fetch_device_reads);
         spl_bam_set_fetch_xs(bam, fetch_device_xs);
-        const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.n_all, res.dropped, 0);
+        const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.n_all, res.dropped, res.flagstat, 0);
         if (rc2 == SPL_OK && on_device_out) *on_device_out = 1;
         return rc2;
     };
@@ -1411,7 +1416,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     if (rc == SPL_OK && res.more_tokens) { res = ShareOut(); rc = decode_share(c, bam, &sh, res, report, true); }
     if (res.reads) return rc; // (reported: decode_share publishes the reads it has made, whatever publishing returned)
     if (getenv("SPL_BAM_TIMING")) fprintf(stderr, "[spl_bam_decode_device] share %d not done on its device (%s)\n", k, rc ? spl_last_error() : "handed to the host");
-    return spl_bam_share_done(bam, k, nullptr, free_device_reads, nullptr, nullptr, nullptr, res.n_all, res.dropped, 1);
+    return spl_bam_share_done(bam, k, nullptr, free_device_reads, nullptr, nullptr, nullptr, res.n_all, res.dropped, nullptr, 1); // (a share the host takes: its counters go, the host decoder counts the file)
 }
 
 namespace {
@@ -1525,8 +1530,9 @@ struct ShareDecode {
     const int n_ref = spl_bam_n_ref(bam);
     const spl_bam_filter filter = spl_bam_get_filter(bam); // (the file is claimed: nobody changes it now)
     const bool want_xs = spl_bam_get_aux_strand(bam);      // (likewise: a fifth array, the spliced reads' XS:A strand)
+    const bool want_stat = spl_bam_get_flagstat(bam);      // (likewise: the scan counts the flagstat categories per block, a kernel adds up the accepted blocks')
     // ---- everything the streams touch is declared before them
-    DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds, d_xs;
+    DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds, d_xs, d_fstat, d_fsum;
     std::vector<spl_zblock> blocks, blocks0; // (blocks0: the early windows', for their launches before the directory is complete)
     std::unique_ptr<uint32_t[]> status;
     std::unique_ptr<spl_bscan[]> scan;
@@ -1534,6 +1540,7 @@ struct ShareDecode {
     std::vector<unsigned long long> maxend;
     std::vector<uint64_t> bounds;
     uint32_t n_bounds = 0;
+    unsigned long long fsum[2 * SPL_FS_CATEGORIES] = {0};
     Pipe pipe{c};
     // ---- the share: which blocks, which bytes of the file (plan)
     int walk_rc = SPL_OK;
@@ -2023,6 +2030,10 @@ struct ShareDecode {
         bounds_cap = (uint32_t)std::max(n_ref, 1) * 4u + 64u;
         HIP_TRY(d_bounds.get(16 * (size_t)bounds_cap, c->copy));
         HIP_TRY(d_nbounds.get(4, c->copy));
+        if (want_stat) { // (64 bytes a block of the share's own, never downloaded; the 32 sums)
+            HIP_TRY(d_fstat.get(4 * (size_t)SPL_FS_CATEGORIES * n_own, c->copy));
+            HIP_TRY(d_fsum.get(sizeof(fsum), c->copy));
+        }
         t_bufs = host_now() - t_begin;
         status.reset(new (std::nothrow) uint32_t[n_blocks]); // (four arrays the device fills window by window: not zeroed first, that was 10 ms of a large file's start)
         scan.reset(new (std::nothrow) spl_bscan[n_blocks]);
@@ -2034,6 +2045,7 @@ struct ShareDecode {
         HIP_TRY(hipMemsetAsync(d_status.p, 0xff, 4 * n_blocks, pipe.b));
         HIP_TRY(hipMemsetAsync(d_maxend.p, 0, 8 * (size_t)std::max(n_ref, 1), pipe.b));
         HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, pipe.b));
+        if (want_stat) HIP_TRY(hipMemsetAsync(d_fsum.p, 0, sizeof(fsum), pipe.b));
         HIP_TRY(hipEventRecord(pipe.setup, pipe.b));
         // (what the early windows' kernels said about their blocks goes to its place among the file's when they have said it: the loop, behind the window's copying kernel)
         HIP_TRY(hipStreamWaitEvent(pipe.a, pipe.setup, 0));
@@ -2155,8 +2167,9 @@ struct ShareDecode {
         const bool with_recs = b1s > s0 && b1s - s0 <= recs_blocks && !getenv("SPL_EXTRACT_WALK");
         if (b1s > s0) {
             splprof::Scope p("spl_bam_scan_kernel", pipe.b, (double)(blocks[b1s - 1].out + blocks[b1s - 1].out_len - blocks[s0].out));
-            HIP_TRY((hipError_t)spl_dev_launch_bam_scan(stream0, win_end, H, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)(b1s - s0), d_scan.as<spl_bscan>() + s0,
-                                                        more ? 1 : 0, with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags, pipe.b));
+            HIP_TRY((hipError_t)spl_dev_launch_bam_scan2(stream0, win_end, H, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)(b1s - s0), d_scan.as<spl_bscan>() + s0,
+                                                         more ? 1 : 0, with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags, pipe.b,
+                                                         want_stat ? d_fstat.as<uint32_t>() + (size_t)SPL_FS_CATEGORIES * s0 : nullptr));
         }
         HIP_TRY(hipMemcpyAsync(status.get() + b0, d_status.as<uint32_t>() + b0, 4 * (size_t)nb, hipMemcpyDeviceToHost, pipe.b));
         if (b1s > s0) HIP_TRY(hipMemcpyAsync(scan.get() + s0, d_scan.as<spl_bscan>() + s0, sizeof(spl_bscan) * (b1s - s0), hipMemcpyDeviceToHost, pipe.b));
@@ -2241,6 +2254,10 @@ struct ShareDecode {
                                                            with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags,
                                                            want_xs ? d_xs.as<uint8_t>() : nullptr, pipe.b));
         }
+        if (want_stat && b_done > s0) { // the counters of the blocks that are done with, each once: a block that waits for the next window is scanned, and counted, again
+            splprof::Scope p("spl_bam_flagstat_reduce_kernel", pipe.b, 4.0 * SPL_FS_CATEGORIES * (double)(b_done - s0));
+            HIP_TRY((hipError_t)spl_dev_launch_bam_flagstat_reduce(d_fstat.as<uint32_t>() + (size_t)SPL_FS_CATEGORIES * s0, (uint32_t)(b_done - s0), d_fsum.as<unsigned long long>(), pipe.b));
+        }
         if (b_done < b1s && k + 1 < n_win) // what is left of this window: in front of the next one's bytes
             HIP_TRY(hipMemcpyAsync(stream0_of(k + 1) + blocks[b_done].out, stream0 + blocks[b_done].out, (size_t)(win_end - blocks[b_done].out), hipMemcpyDeviceToDevice, pipe.b));
         HIP_TRY(hipEventRecord(pipe.freed[k % (size_t)n_buf], pipe.b));
@@ -2262,6 +2279,7 @@ struct ShareDecode {
         HIP_TRY(hipMemcpyAsync(maxend.data(), d_maxend.p, 8 * maxend.size(), hipMemcpyDeviceToHost, pipe.b));
         HIP_TRY(hipMemcpyAsync(bounds.data(), d_bounds.p, 16 * (size_t)bounds_cap, hipMemcpyDeviceToHost, pipe.b));
         HIP_TRY(hipMemcpyAsync(&n_bounds, d_nbounds.p, 4, hipMemcpyDeviceToHost, pipe.b));
+        if (want_stat) HIP_TRY(hipMemcpyAsync(fsum, d_fsum.p, sizeof(fsum), hipMemcpyDeviceToHost, pipe.b));
         HIP_TRY(hipStreamSynchronize(pipe.b));
         join_readers();
         for (hipError_t e : errs) HIP_TRY(e);
@@ -2294,6 +2312,7 @@ struct ShareDecode {
         res.n_all = n_all;
         res.dropped[0] = n_drop_flags;
         res.dropped[1] = n_drop_mapq;
+        for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.flagstat[q] = (int64_t)fsum[q];
         if (timing) fprintf(stderr, "[spl_bam_decode_device] device %d: blocks %zu..%zu, %.1f MB -> %.1f MB inflated in %zu window%s, %llu placed records of %lld: %.4f s\n", c->device, lo, hi,
                             n_bytes / 1e6, (stream_len - stream_begin) / 1e6, n_win, n_win == 1 ? "" : "s", (unsigned long long)n_rec, (long long)n_all, host_now() - t_begin);
         if (timing) {
@@ -2315,7 +2334,7 @@ struct ShareDecode {
         d_image.release();
         for (int k = 0; k < NBUF; ++k) { d_stream[k].release(); d_zwork[k].release(); }
         d_blocks0.release(); d_status0.release(); d_recs.release(); d_blocks.release(); d_status.release(); d_scan.release(); d_recoff.release(); d_opoff.release();
-        d_tid.release(); d_maxend.release(); d_bounds.release(); d_nbounds.release();
+        d_tid.release(); d_maxend.release(); d_bounds.release(); d_nbounds.release(); d_fstat.release(); d_fsum.release();
         const int told = publish(res);
         // ... and not at once: 500 events and five streams destroyed are 10 ms of the HIP runtime's locks, which the thread that was
         // told above needs now -- for the layout kernels, the chunk order's upload, the counting launches (its 9 ms took 17 beside

@@ -85,6 +85,16 @@ extern "C" {
 // the same three values go to the extraction, whose walking kernel decides about every record again.
 int spl_dev_launch_bam_scan(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks,
                             uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *stream_handle);
+// ... with the flagstat counters (spl_flagstat.h): fstat = null, or n_blocks x 16 words -- block b's entry c = the records that begin
+// in the block, that the filter keeps (judged for every record, placed or not) and that belong to category c, QC-passed ones in
+// the low half and QC-failed ones (FLAG 0x200) in the high half; zeros for a block of BAM header bytes.  Null selects the kernel
+// above, unchanged; the pointer comes last, behind the stream, so that spl_dev_launch_bam_scan's callers need not know of it.
+int spl_dev_launch_bam_scan2(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks,
+                             uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *stream_handle,
+                             uint32_t *fstat);
+// sums[2 c + q] += the QC-passed (q = 0) / QC-failed (q = 1) halves of entry c of fstat's n_blocks blocks: 32 counters of 64 bits
+// (zero them first; 32 atomics per workgroup).  The caller passes the blocks whose scan it has accepted, each once.
+int spl_dev_launch_bam_flagstat_reduce(const uint32_t *fstat, uint32_t n_blocks, unsigned long long *sums, void *stream_handle);
 // rec_off[b] / op_off[b]: index of the block's first placed record / first op in the output arrays.  cig_off gets n + 1 entries
 // (the caller sets entry 0); ref_max_end[tid] = largest last base of a read of the reference (atomicMax; zero it first).
 // recs: what the scan of THESE blocks (same first block, same order) left, or null: then a lane walks its block's records.

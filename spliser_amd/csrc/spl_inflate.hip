@@ -8,6 +8,7 @@
 #include "spl_inflate.h"
 #include "spl_bam.h"
 #include "spl_bam_aux.h"
+#include "spl_flagstat.h"
 #include "spl_wave.h"
 #include "spl_inflate_wave.h"
 #include "spl_crc.h"
@@ -118,11 +119,23 @@ __device__ __forceinline__ bool plausible_record(const uint8_t *c, const uint8_t
 // moment -- a record that runs past it is then no damage but something for the next window (SPL_BS_INCOMPLETE).
 // `filter`: a record it does not keep (spl_bam.h) is counted and otherwise not placed -- what the extraction leaves is what it would
 // leave for a file without those records; the order of references (SPL_BS_UNSORTED) is the file's, and judged over all records.
-__global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi,
-                                                           const spl_zblock *blocks, uint32_t n_blocks, spl_bscan *scan, uint32_t more, uint16_t *recs, spl_bam_filter filter)
+//
+// Written once, with a template parameter, as the extraction is: STAT = false is the scan of a file nobody asked the flagstat
+// counters of (spl_bam_set_flagstat) -- not a load, a branch or an argument more than before there was such a thing.  STAT = true
+// also counts every record it walks -- placed, dropped from the extraction, without a reference, another share's: all that go into
+// n_all or n_foreign -- into the sixteen categories of spl_flagstat.h, if the filter keeps it (judged for EVERY record here: a
+// pre-filtered file has lost its unmapped reads of MAPQ 0 too), and leaves the block's counters in fstat[16 b ..]: sixteen words
+// that live in the lane's registers meanwhile, nothing atomic.  Per block, not summed: a block whose scan the host does not
+// accept (records_done, spl_capi.cpp) is scanned again with the next window, and only what the last scan left counts
+// (spl_bam_flagstat_reduce_kernel adds the accepted blocks').
+template <bool STAT>
+__device__ __forceinline__ void bam_scan_block(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi,
+                                               const spl_zblock *blocks, uint32_t n_blocks, spl_bscan *scan, uint32_t more, uint16_t *recs, const spl_bam_filter &filter, uint32_t *fstat)
 {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_blocks) return;
+    uint32_t fs[SPL_FS_CATEGORIES] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    u32x4 *const fs_out = STAT ? reinterpret_cast<u32x4 *>(fstat + (size_t)b * SPL_FS_CATEGORIES) : nullptr;
     const uint64_t u0 = blocks[b].out, u1 = u0 + blocks[b].out_len;
     uint16_t *const mine = recs ? recs + (size_t)b * SPL_BS_REC_CAP : nullptr; // where this block's placed records begin, for the extraction
     const uint8_t *const end = stream + stream_len;
@@ -136,6 +149,7 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
     if (u1 <= header_end && !(u1 == header_end && u0 == u1)) { // BAM header bytes only (or an empty block inside them)
         out.start = out.reached = u1 < header_end ? u1 : header_end;
         scan[b] = out;
+        if (STAT) { const u32x4 zero = {0u, 0u, 0u, 0u}; fs_out[0] = zero; fs_out[1] = zero; fs_out[2] = zero; fs_out[3] = zero; }
         return;
     }
     uint64_t at = u0;
@@ -181,6 +195,7 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
         const int32_t tid_eff = tid < 0 || tid >= n_ref ? n_ref : tid; // (records without a reference: behind all others)
         if (tid_eff < last_tid) out.flags |= SPL_BS_UNSORTED; // (every record counts here, a neighbour's too: the shares are cut on this order)
         last_tid = tid_eff;
+        if (STAT && spl_bam_filter_verdict(filter, flag, mapq) == SPL_BAM_KEPT) spl_flagstat_add_packed(fs, flag, tid, (int32_t)ld32(r + 20), mapq); // (next_refID: in the line the five loads above have brought)
         if (tid_eff < tid_lo || tid_eff >= tid_hi) { out.n_foreign++; out.n_foreign_hi += tid_eff >= tid_hi ? 1u : 0u; at += 4ull + bs; continue; }
         out.n_all++;
         const int verdict = tid >= 0 && tid < n_ref && pos0 >= 0 ? spl_bam_filter_verdict(filter, flag, mapq) : SPL_BAM_KEPT;
@@ -201,6 +216,61 @@ __global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream,
     }
     out.reached = at;
     scan[b] = out;
+    if (STAT) {
+#pragma unroll
+        for (uint32_t k = 0; k < SPL_FS_CATEGORIES / 4u; ++k) { const u32x4 v = {fs[4u * k], fs[4u * k + 1u], fs[4u * k + 2u], fs[4u * k + 3u]}; fs_out[k] = v; }
+    }
+}
+
+__global__ __launch_bounds__(64) void spl_bam_scan_kernel(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi,
+                                                           const spl_zblock *blocks, uint32_t n_blocks, spl_bscan *scan, uint32_t more, uint16_t *recs, spl_bam_filter filter)
+{
+    bam_scan_block<false>(stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, more, recs, filter, nullptr);
+}
+
+__global__ __launch_bounds__(64) void spl_bam_scan_stat_kernel(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi,
+                                                                const spl_zblock *blocks, uint32_t n_blocks, spl_bscan *scan, uint32_t more, uint16_t *recs, spl_bam_filter filter,
+                                                                uint32_t *fstat)
+{
+    bam_scan_block<true>(stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, more, recs, filter, fstat);
+}
+
+// The flagstat counters of the blocks whose scan the host has accepted, added up: fstat = n_blocks x 16 words as the scan left them,
+// sums = 32 counters, [2 c + q] (q = 1: QC-failed), which only ever grow.  Wave64.  Lane i of the grid takes word i, i + the
+// grid's lanes, ...: sixteen consecutive lanes the sixteen words of one block, a wave four blocks with one coalesced load, and
+// as the grid's lanes are a multiple of 16 a lane stays with category lane & 15 and keeps the two halves of its words apart in
+// two 64-bit accumulators.  The four lanes of a wave that hold a category are added (lane ^ 16, lane ^ 32), the waves of the
+// workgroup in LDS, and 32 lanes of the workgroup add its sums to the file's: 32 atomics a workgroup, however many blocks.
+constexpr uint32_t FS_REDUCE_LANES = 256u;
+__device__ __forceinline__ unsigned long long fs_shfl64(unsigned long long v, uint32_t src)
+{
+    return (unsigned long long)wv::shfl((uint32_t)v, src) | (unsigned long long)wv::shfl((uint32_t)(v >> 32), src) << 32;
+}
+__global__ __launch_bounds__(FS_REDUCE_LANES) void spl_bam_flagstat_reduce_kernel(const uint32_t *fstat, uint32_t n_blocks, unsigned long long *sums)
+{
+    static_assert(FS_REDUCE_LANES % 64u == 0u && 64u % SPL_FS_CATEGORIES == 0u, "a lane keeps its category along the grid's stride");
+    __shared__ unsigned long long part[FS_REDUCE_LANES / 64u][2u * SPL_FS_CATEGORIES];
+    const uint64_t n_words = (uint64_t)n_blocks * SPL_FS_CATEGORIES, stride = (uint64_t)gridDim.x * FS_REDUCE_LANES;
+    unsigned long long pass = 0ull, fail = 0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * FS_REDUCE_LANES + threadIdx.x; i < n_words; i += stride) {
+        const uint32_t v = fstat[i];
+        pass += v & 0xffffu;
+        fail += v >> 16;
+    }
+    const uint32_t lane = wv::lane(), wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t s = 16u; s < 64u; s <<= 1) { // (every lane of the wave is here: the loop above has no exit of its own)
+        pass += fs_shfl64(pass, lane ^ s);
+        fail += fs_shfl64(fail, lane ^ s);
+    }
+    if (lane < SPL_FS_CATEGORIES) { part[wave][2u * lane] = pass; part[wave][2u * lane + 1u] = fail; }
+    wv::sync();
+    if (threadIdx.x < 2u * SPL_FS_CATEGORIES) {
+        unsigned long long t = 0ull;
+#pragma unroll
+        for (uint32_t w = 0; w < FS_REDUCE_LANES / 64u; ++w) t += part[w][threadIdx.x];
+        if (t) atomicAdd(&sums[threadIdx.x], t);
+    }
 }
 
 // Both extractions are written once, as a function with a template parameter: XS = false is the kernel a file gets that nobody
@@ -396,13 +466,32 @@ __global__ __launch_bounds__(256) void spl_bam_bounds_kernel(const int32_t *tid,
     }
 }
 
-extern "C" int spl_dev_launch_bam_scan(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks,
-                                       uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *st)
+extern "C" int spl_dev_launch_bam_scan2(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks,
+                                        uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *st, uint32_t *fstat)
 {
     if (n_blocks == 0) return 0;
     const uint32_t L = 8; // (blocks per wave: the kernel is lanes waiting for memory, a wave as slow as its slowest lane -- 1.1 ms per window of 49 152 blocks with 8, 1.7 with 64, 3.9 with 1)
-    hipLaunchKernelGGL(spl_bam_scan_kernel, dim3((n_blocks + L - 1u) / L), dim3(L), 0, (hipStream_t)st, stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, more ? 1u : 0u, recs,
-                       spl_bam_filter{min_mapq, require_flags, exclude_flags});
+    if (fstat) // (spl_bam_set_flagstat: the instantiation that counts what it walks)
+        hipLaunchKernelGGL(spl_bam_scan_stat_kernel, dim3((n_blocks + L - 1u) / L), dim3(L), 0, (hipStream_t)st, stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan,
+                           more ? 1u : 0u, recs, spl_bam_filter{min_mapq, require_flags, exclude_flags}, fstat);
+    else
+        hipLaunchKernelGGL(spl_bam_scan_kernel, dim3((n_blocks + L - 1u) / L), dim3(L), 0, (hipStream_t)st, stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, more ? 1u : 0u, recs,
+                           spl_bam_filter{min_mapq, require_flags, exclude_flags});
+    return (int)hipGetLastError();
+}
+
+extern "C" int spl_dev_launch_bam_scan(const uint8_t *stream, uint64_t stream_len, uint64_t header_end, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks,
+                                       uint32_t n_blocks, spl_bscan *scan, int more, uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, void *st)
+{
+    return spl_dev_launch_bam_scan2(stream, stream_len, header_end, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, more, recs, min_mapq, require_flags, exclude_flags, st, nullptr);
+}
+
+extern "C" int spl_dev_launch_bam_flagstat_reduce(const uint32_t *fstat, uint32_t n_blocks, unsigned long long *sums, void *st)
+{
+    if (n_blocks == 0) return 0;
+    // (a workgroup takes sixteen blocks a turn; no more workgroups than two a CU: what is left is the loop's)
+    const uint32_t groups = std::min<uint32_t>((n_blocks + FS_REDUCE_LANES / SPL_FS_CATEGORIES - 1u) / (FS_REDUCE_LANES / SPL_FS_CATEGORIES), 512u);
+    hipLaunchKernelGGL(spl_bam_flagstat_reduce_kernel, dim3(groups), dim3(FS_REDUCE_LANES), 0, (hipStream_t)st, fstat, n_blocks, sums);
     return (int)hipGetLastError();
 }
 

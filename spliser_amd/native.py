@@ -51,7 +51,7 @@ EXPORTS = [
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
     "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_reads_has_strand", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
-    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
+    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
     "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
@@ -615,13 +615,17 @@ class BamFile(object):
     incomplete).
 
     ``min_mapq``, ``require_flags``, ``exclude_flags``: samtools view's -q / -f / -F (``spl_bam_set_filter``); a record that fails
-    them is never extracted, whoever decodes the file.  ``filter_counts`` says how many did."""
+    them is never extracted, whoever decodes the file.  ``filter_counts`` says how many did.
 
-    def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False):
+    ``flagstat``: whoever decodes the file also counts samtools flagstat's categories over all its records
+    (``spl_bam_set_flagstat``); ``flagstat()`` has them."""
+
+    def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False, flagstat=False):
         self._h = ctypes.c_void_p()
         self.filter = (int(min_mapq), int(require_flags), int(exclude_flags))
         self.aux_strand = False
-        filtered = self.filter != (0, 0, 0) or bool(aux_strand)   # (both must be there before the decode starts: opened deferred, started below)
+        self.counts_flagstat = False
+        filtered = self.filter != (0, 0, 0) or bool(aux_strand) or bool(flagstat)   # (all must be there before the decode starts: opened deferred, started below)
         opener = lib().spl_bam_open_deferred if defer or filtered else (lib().spl_bam_open_stream if stream else lib().spl_bam_open)
         _check(opener(os.fsencode(path), ctypes.c_int(threads), ctypes.byref(self._h)))
         if filtered:
@@ -629,6 +633,8 @@ class BamFile(object):
                 self.set_filter(*self.filter)
                 if aux_strand:
                     self.set_aux_strand(True)
+                if flagstat:
+                    self.set_flagstat(True)
                 if not defer:
                     _check(lib().spl_bam_start(self._h))
                     if not stream:
@@ -654,6 +660,20 @@ class BamFile(object):
         a read set of the device decode ``has_strand()``."""
         _check(lib().spl_bam_set_aux_strand(self._h, ctypes.c_int(1 if on else 0)))
         self.aux_strand = bool(on)
+
+    def set_flagstat(self, on=True):
+        """A ``defer=True`` file nobody decodes yet: the decode -- whoever does it -- also counts the flagstat categories
+        (``spl_bam_set_flagstat``; an error afterwards)."""
+        _check(lib().spl_bam_set_flagstat(self._h, ctypes.c_int(1 if on else 0)))
+        self.counts_flagstat = bool(on)
+
+    def flagstat(self):
+        """-> int64 array (16, 2): per category of samtools flagstat (``FLAGSTAT_LABELS``) the QC-passed and the QC-failed records
+        of the file -- of those the read filter keeps, when one is set; waits for the end of the decode.  An error for a file
+        opened without ``flagstat=True``."""
+        out = (ctypes.c_int64 * 32)()
+        _check(lib().spl_bam_flagstat(self._h, out))
+        return np.array(out[:], np.int64).reshape(16, 2)
 
     def filter_counts(self):
         """-> (records dropped by their flags, records dropped by their MAPQ alone); waits for the end of the decode."""
@@ -888,6 +908,21 @@ class _BamHandle(object):
                 lib().spl_bam_close(cls._parked.pop(key))
         for rs in views.values():
             weakref.finalize(rs.pos, gone, None)
+
+
+FLAGSTAT_LABELS = ("in total (QC-passed reads + QC-failed reads)", "primary", "secondary", "supplementary", "duplicates", "primary duplicates", "mapped",
+                   "primary mapped", "paired in sequencing", "read1", "read2", "properly paired", "with itself and mate mapped", "singletons",
+                   "with mate mapped to a different chr", "with mate mapped to a different chr (mapQ>=5)")
+
+
+def flagstat_add_host(flag, tid, next_tid, mapq, counters=None):
+    """The decoders' counting of one record on the host (``spl_flagstat_add_host``): adds to ``counters`` (int64, (16, 2); made when
+    None) and returns them."""
+    if counters is None:
+        counters = np.zeros((16, 2), np.int64)
+    assert counters.dtype == np.int64 and counters.shape == (16, 2) and counters.flags.c_contiguous
+    _check(lib().spl_flagstat_add_host(ctypes.c_uint32(int(flag)), ctypes.c_int32(int(tid)), ctypes.c_int32(int(next_tid)), ctypes.c_uint32(int(mapq)), _ptr(counters)))
+    return counters
 
 
 def aux_strand_host(aux):

@@ -68,16 +68,19 @@ class _SamSource(object):
         return self._counts[1], self._counts[2]
 
 
-def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER, aux_strand=False):
+def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER, aux_strand=False, flagstat=False):
     """BAM (BGZF) through the native decoder; plain SAM text through the Python reader.  ``stream=True``: the BAM decoder
     returns after the header and decodes in the background (``native.BamFile``); ``defer=True``: nothing is decoded until
     somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``read_filter``: which records either keeps.
-    ``aux_strand``: either also leaves a strand byte per read, the XS:A tag of the spliced ones (``--strandFromXS``)."""
+    ``aux_strand``: either also leaves a strand byte per read, the XS:A tag of the spliced ones (``--strandFromXS``).
+    ``flagstat``: the BAM decoder also counts the flagstat categories (``--flagstat``; SAM text has no such counters: an error)."""
     with open(path, "rb") as fh:
         magic = fh.read(4)
     q, f, F = read_filter
     if magic[:2] == b"\x1f\x8b":
-        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=aux_strand)
+        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=aux_strand, flagstat=flagstat)
+    if flagstat:
+        raise native.SpliserNativeError(-5, "%s: flagstat counters are counted while a BAM file is decoded; this is not one" % path)
     if magic[:1] == b"@" or b"\t" in open(path, "rb").readline():
         return _SamSource(path, q, f, F, aux_strand)
     raise native.SpliserNativeError(-5, "%s is neither BGZF/BAM nor SAM text" % path)
@@ -96,12 +99,13 @@ def wait_deferred_close():
     return time.perf_counter() - t0
 
 
-def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER, aux_strand=False):
+def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER, aux_strand=False, flagstat=False):
     """The alignment file opened and its decode started: on the GPU(s) -- with several devices every one inflates and extracts
     the stretch of the file that holds its own references (``BamFile.decode_on_devices_async``), and counts them -- or, told so
     (``gpuDecode=False``), on host threads.  SAM text has one reader.  ``read_filter`` is with the source before any of them starts,
-    and so is ``aux_strand`` (``BamFile.set_aux_strand``: a strand byte per read for ``--strandFromXS``)."""
-    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter, aux_strand=aux_strand)
+    and so is ``aux_strand`` (``BamFile.set_aux_strand``: a strand byte per read for ``--strandFromXS``), and ``flagstat``
+    (``BamFile.set_flagstat``: the decoders count the flagstat categories)."""
+    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter, aux_strand=aux_strand, flagstat=flagstat)
     if isinstance(source, native.BamFile) and gpuDecode is not False:
         try:
             if len(devices) > 1:
@@ -473,8 +477,13 @@ def write_tsv(output_path, table, results, is_beta2_cryptic):
 def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
             isStranded=False, strandedType=None, isbeta2Cryptic=False, devices=(0,), threads=0, log=_log, checkJunctions=False,
             gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False,
-            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False):
+            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, flagstat=False):
     """SpliSER_v0_1_8.py:695-720, keyword-compatible with the reference's argparse dests.
+
+    ``flagstat`` (this build only; changes no result): also write ``<outputPath>.flagstat.txt`` -- samtools flagstat's sixteen
+    lines, counted by the decode this call does anyway (``flagstat.py``), over the WHOLE file whatever ``qChrom`` / ``qGene`` say
+    (a library's size is the library's), of the records the read filter keeps when one is set -- and log the library size, the
+    number the diffSpliSER target file asks for.
 
     ``strandFromXS`` (this build only, without ``inBed``, an unstranded library; changes results): a junction's strand is the
     XS:A tag the aligner wrote on the reads that carry it (regtools' ``-s XS``) instead of ``?`` -- ``junctions(strandFromXS=True)``
@@ -523,7 +532,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     # The alignment file does not depend on Steps 0-2: it is decoded on native threads while the site table is built here, and
     # goes on decoding while Step 3 counts the chromosomes that are complete.  An unreadable file is an error here already
     # (block directory and header are read by the opening call).
-    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt, aux_strand=bool(strandFromXS))     # (the decode runs beside Steps 0-2, wherever it runs)
+    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt, aux_strand=bool(strandFromXS), flagstat=bool(flagstat))     # (the decode runs beside Steps 0-2, wherever it runs)
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
@@ -562,6 +571,9 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
             # (said once, where the user reads it: the host's threads are several times slower than the device on files like this)
             log("  (the alignment file was decoded on host threads, not on the GPU: %s)" % source.decline_reason())
         log_filter(source, filt, log)
+        if flagstat:      # (the whole file is decoded by now, or will be in a moment: -c / -g do not make the decode any shorter)
+            from . import flagstat as _flagstat
+            _flagstat.write_and_log(outputPath + _flagstat.SUFFIX, source.flagstat(), log)
         t3 = time.perf_counter()
         log("\nOutputting .tsv file")
         writer.close(list(results))
