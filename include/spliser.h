@@ -296,6 +296,28 @@ int spl_bam_set_aux_strand(spl_bam *bam, int on);
 int spl_bam_set_flagstat(spl_bam *bam, int on);
 int spl_bam_flagstat(spl_bam *bam, int64_t *out32);
 int spl_flagstat_add_host(uint32_t flag, int32_t tid, int32_t next_tid, uint32_t mapq, int64_t *inout32);
+/* No `samtools sort` in front of the decode (the reference reads through `samtools view BAM region`, SpliSER_v0_1_8.py:422, which
+ * needs the index of a coordinate-sorted file; STAR's and HISAT2's own output is not sorted).  spl_bam_set_any_order(bam, 1): the
+ * file's records may come in ANY order, and after the decode -- the device's and the host's alike -- every reference's reads are
+ * handed out sorted by (POS, place in the file), to every consumer: spl_bam_reads, spl_reads_add_bam, spl_bam_aux_strand, the
+ * junction tables.  spl_bam_wait_all then reports *sorted_out = 1 whatever the file's order was, spl_bam_wait_ref returns at the
+ * end of the decode only (a reference of such a file is complete no earlier), and the device decoder does not hand the file to the
+ * host for its order.  A file whose reference ids never go down is left exactly as it is without the switch, bytes and order (one
+ * sorted by reference but not by POS inside a reference too).  On the device the placed records' arrays are sorted by a stable
+ * radix sort of (reference id << 32 | POS) between the last extraction and the bounds kernel (csrc/spl_sort.hip); the host decoder
+ * orders each reference's reads with a stable index sort; both leave the same arrays.  The order of reads with equal
+ * coordinates is the file's, not `samtools sort`'s tie order: no result depends on it.  The same rule as spl_bam_set_filter:
+ * before anybody decodes the file or waits for it, SPL_ERR_ARG afterwards.  Off by default, and nothing of the decode changes
+ * while it is off.  A decode in shares (spl_bam_share_plan) cuts the file on the order of references: not for such a file.
+ * spl_bam_any_order_sorted: once the decode is complete (it waits for that), *n_sorted_out = the reads that were put in order
+ * (0: the file was in order already) and *on_device_out = 1 when the device's sort did it, 0 when the host threads did.
+ * spl_sort_keys_device: the device's sort itself on a caller's keys (test hook; no file): uploads n keys (n < 2^32 - 16), runs
+ * exactly the passes the decode runs for keys of key_bits bits (1..64: the digits of the low word from bit 0, those of the high
+ * word from bit 32, 8 bits a pass) and downloads the permutation -- perm_out[i] = index of the key that comes i-th, equal keys in
+ * the order they came in. */
+int spl_bam_set_any_order(spl_bam *bam, int on);
+int spl_bam_any_order_sorted(spl_bam *bam, int64_t *n_sorted_out, int *on_device_out);
+int spl_sort_keys_device(spl_ctx *ctx, const uint64_t *keys, int64_t n, int key_bits, uint32_t *perm_out);
 int spl_bam_aux_strand(const spl_bam *bam, int tid, const uint8_t **out);
 int spl_bam_aux_strand_host(const uint8_t *aux, uint32_t len, uint8_t *out);
 int spl_bam_decode_device(spl_ctx *ctx, spl_bam *bam, int *on_device_out);

@@ -16,6 +16,8 @@ command does anyway, over the whole file whatever ``-c`` / ``-g`` say, and logs 
 the diffSpliSER target file, for which the reference's README sends the user to ``samtools flagstat``); it changes no result.
 Extra sub-command ``flagstat -B x.bam -o PATH`` writes those lines alone (the filter and engine flags, ``--gpuDecode`` /
 ``--hostDecode``).  Under a read filter the counters are the pre-filtered file's.
+``--anyOrder`` (``process``, ``junctions``, ``flagstat``; changes no result): the BAM may be in any record order, e.g. the aligner's
+own output -- its reads are coordinate-sorted on the GPU after the decode instead of by ``samtools sort`` beforehand.
 """
 import argparse
 import sys
@@ -77,6 +79,7 @@ def build_parser():
     p.add_argument("--flagstat", dest="flagstat", default=False, action="store_true",
                    help="(this build only) also write <outputPath>.flagstat.txt: samtools flagstat's counters of the whole BAM, from "
                         "the decode this command does anyway, and log the library size (mapped reads); changes no result")
+    p.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(p)
     _engine_flags(p)
     f = sub.add_parser("flagstat", help="(this build only) samtools flagstat's counters of a BAM, counted while it is decoded on the GPU")
@@ -84,6 +87,7 @@ def build_parser():
     f.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="path of the text file to write")
     f.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
     f.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    f.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(f)
     _engine_flags(f)
     c = sub.add_parser("combine")
@@ -128,6 +132,7 @@ def build_parser():
     j.add_argument("-a", "--minAnchor", dest="minAnchor", type=int, default=8, help="both anchors of a read must be this long (regtools -a)")
     j.add_argument("-m", "--minIntron", dest="minIntron", type=int, default=70, help="regtools -m")
     j.add_argument("-M", "--maxIntron", dest="maxIntron", type=int, default=500000, help="regtools -M; 0 = no limit")
+    j.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(j)
     _engine_flags(j)
     return parser
@@ -147,6 +152,10 @@ def _filter_flags(p):
     p.add_argument("--excludeFlags", dest="excludeFlags", type=_flag_mask, default=0,
                    help="(this build only; changes results) skip alignments with any of these FLAG bits set (samtools view -F, "
                         "e.g. 0x900: secondary and supplementary) - default: 0")
+
+
+ANY_ORDER_HELP = ("(this build only; changes no result) the BAM may be in any record order, e.g. as the aligner wrote it: its reads are "
+                  "coordinate-sorted on the GPU after the decode instead of by samtools sort beforehand")
 
 
 def _engine_flags(p):

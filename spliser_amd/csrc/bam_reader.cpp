@@ -20,6 +20,7 @@
 #include <math.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -483,6 +484,9 @@ struct spl_bam {
     int64_t dropped[2] = {0, 0};       // records the filter dropped: by their flags, by their MAPQ
     bool aux_strand = false;           // a strand byte per placed read beside its flag (spl_bam_set_aux_strand; fixed once claim != 0)
     bool flagstat = false;             // the decode counts the flagstat categories (spl_bam_set_flagstat; fixed once claim != 0)
+    bool any_order = false;            // the records may come in any order: whoever decodes hands every reference's reads out sorted by (POS, place in the file) (spl_bam_set_any_order; fixed once claim != 0)
+    int64_t n_sorted = 0;              // ... the reads that were put in order for it (0: the file was in order already) ...
+    int sorted_on_device = 0;          // ... and by whom: the device decoder's sort (1) or the host threads (0)
     int64_t fstat[2 * SPL_FS_CATEGORIES] = {0}; // ... over every record the filter keeps, placed or not: [2 c + q] (spl_flagstat.h)
     // ---- BAM-native arrays per reference, assembled on demand (spl_bam_reads) ----
     std::vector<RefFinal> refs_storage; // (never resized after the header: RefFinal is not copyable)
@@ -708,6 +712,94 @@ void merge_parts(spl_bam *bam, std::vector<Part> &parts)
     }
     if (bam->max_tid_seen > bam->complete_upto) bam->complete_upto = bam->max_tid_seen;
     if (bam->complete_upto != before) bam->cv.notify_all();
+}
+
+// spl_bam_set_any_order on the host decoder, for a file that was found out of order (call with bam->mu held, before `done`):
+// every reference's parts -- file order -- become ONE part whose reads are ordered by (POS, place in the file), FLAG, CIGAR and the
+// strand bytes permuted alike: the arrays the device's sort (spl_sort.hip) leaves for the same file.  A stable index sort per
+// reference, the references side by side.  (The parts' own arrays stay in their slabs until the file is closed.)
+bool order_parts(spl_bam *bam, std::string &err)
+{
+    struct Done { PendingPart *part = nullptr; void *arr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool failed = false; };
+    std::vector<Done> done((size_t)bam->n_refs);
+    std::atomic<int> next(0);
+    std::atomic<bool> too_many(false);
+    auto work = [&]() {
+        for (;;) {
+            const int tid = next.fetch_add(1);
+            if (tid >= bam->n_refs) break;
+            const std::vector<PendingPart *> &parts = bam->parts[(size_t)tid];
+            size_t n = 0, g = 0;
+            bool with_xs = bam->aux_strand;
+            for (const PendingPart *pt : parts) { n += pt->reads.n; g += pt->reads.n_ops; with_xs = with_xs && (pt->reads.n == 0 || pt->reads.xs != nullptr); }
+            if (n == 0) continue;
+            Done &d = done[(size_t)tid];
+            if (g > 0xfffffff0ull) { too_many.store(true); d.failed = true; continue; }
+            // where read k of the reference (file order) lies: its part and its place there
+            std::vector<uint32_t> part_of(n), order(n);
+            std::vector<size_t> first(parts.size() + 1, 0);
+            std::vector<int32_t> pos_at(n);
+            size_t at = 0;
+            for (size_t i = 0; i < parts.size(); ++i) {
+                const RefReads &r = parts[i]->reads;
+                first[i] = at;
+                for (size_t j = 0; j < r.n; ++j) { part_of[at + j] = (uint32_t)i; pos_at[at + j] = r.pos[j]; }
+                at += r.n;
+            }
+            first[parts.size()] = at;
+            for (size_t k = 0; k < n; ++k) order[k] = (uint32_t)k;
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return pos_at[a] < pos_at[b]; });
+            int32_t *pos = (int32_t *)big_alloc(sizeof(int32_t) * n);
+            uint16_t *flag = (uint16_t *)big_alloc(sizeof(uint16_t) * n);
+            uint32_t *cig_off = (uint32_t *)big_alloc(sizeof(uint32_t) * (n + 1));
+            uint32_t *cigar = (uint32_t *)big_alloc(sizeof(uint32_t) * std::max<size_t>(g, 1));
+            uint8_t *xs = with_xs ? (uint8_t *)big_alloc(n) : nullptr;
+            d.arr[0] = pos; d.arr[1] = flag; d.arr[2] = cig_off; d.arr[3] = cigar; d.arr[4] = xs;
+            if (!pos || !flag || !cig_off || !cigar || (with_xs && !xs)) { d.failed = true; continue; }
+            uint32_t o = 0;
+            cig_off[0] = 0;
+            for (size_t k = 0; k < n; ++k) {
+                const RefReads &r = parts[part_of[order[k]]]->reads;
+                const size_t j = order[k] - first[part_of[order[k]]];
+                pos[k] = r.pos[j];
+                flag[k] = r.flag[j];
+                if (with_xs) xs[k] = r.xs[j];
+                const uint32_t a = r.cig_off[j], b = r.cig_off[j + 1];
+                if (b > a) memcpy(cigar + o, r.cigar + a, sizeof(uint32_t) * (b - a));
+                o += b - a;
+                cig_off[k + 1] = o;
+            }
+            PendingPart *pp = new PendingPart();
+            pp->tid = tid;
+            pp->reads.pos = pos; pp->reads.flag = flag; pp->reads.cig_off = cig_off; pp->reads.cigar = cigar; pp->reads.xs = xs;
+            pp->reads.n = n; pp->reads.n_ops = g; pp->reads.max_end = bam->ref_max_end[(size_t)tid];
+            d.part = pp;
+        }
+    };
+    const int nt = std::max(1, std::min(std::min(bam->n_threads, 16), bam->n_refs));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto &th : pool) th.join();
+    bool failed = false;
+    for (const Done &d : done) failed = failed || d.failed;
+    if (failed) {
+        for (Done &d : done) { delete d.part; for (void *a : d.arr) free(a); }
+        err = too_many.load() ? "more than 2^32 CIGAR operations on one reference" : "out of host memory";
+        return false;
+    }
+    int64_t n_sorted = 0;
+    for (int tid = 0; tid < bam->n_refs; ++tid) {
+        Done &d = done[(size_t)tid];
+        if (!d.part) continue;
+        for (void *a : d.arr) if (a) bam->slabs.push_back(a);
+        for (PendingPart *old : bam->parts[(size_t)tid]) delete old;
+        bam->parts[(size_t)tid].assign(1, d.part);
+        n_sorted += (int64_t)d.part->reads.n;
+    }
+    bam->n_sorted = n_sorted;
+    bam->sorted_on_device = 0;
+    return true;
 }
 
 // BAM-native arrays of one reference (spl_bam_reads): one exact-size allocation per array, copied from the parts.
@@ -1015,6 +1107,10 @@ void decode_worker(spl_bam *bam)
     {
         std::lock_guard<std::mutex> lock(bam->mu);
         if (!fail.empty() && !bam->err_code) { bam->error = bam->path + ": " + fail; bam->err_code = SPL_ERR_FORMAT; }
+        if (bam->any_order && bam->out_of_order && !bam->err_code) { // (spl_bam_set_any_order: nobody has been handed a reference yet, spl_bam_wait_ref)
+            std::string why;
+            if (!order_parts(bam, why)) { bam->error = bam->path + ": " + why; bam->err_code = SPL_ERR_NOMEM; }
+        }
         bam->complete_upto = bam->n_refs;
         bam->done = true;
     }
@@ -1187,6 +1283,45 @@ bool spl_bam_get_flagstat(spl_bam *bam)
 {
     std::lock_guard<std::mutex> lock(bam->mu);
     return bam->flagstat;
+}
+
+// The file's records may come in any order: whoever decodes it hands every reference's reads out sorted by (POS, place in the
+// file).  The same rule as spl_bam_set_filter: only while nobody decodes the file or waits for it.
+extern "C" int spl_bam_set_any_order(spl_bam *bam, int on)
+{
+    if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_any_order: null argument");
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (bam->claim != 0 || bam->done)
+        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_any_order: the file is being decoded (or waited for) already", bam->path.c_str());
+    bam->any_order = on != 0;
+    return SPL_OK;
+}
+
+bool spl_bam_get_any_order(spl_bam *bam)
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    return bam->any_order;
+}
+
+// (the device decoder, before it hands its arrays over: it has sorted n reads)
+void spl_bam_note_sorted(spl_bam *bam, int64_t n)
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    bam->n_sorted = n;
+    bam->sorted_on_device = n > 0 ? 1 : 0;
+}
+
+// What spl_bam_set_any_order came to: waits for the end of the decode, like spl_bam_filter_counts; the decode's error is the call's.
+extern "C" int spl_bam_any_order_sorted(spl_bam *bam, int64_t *n_sorted_out, int *on_device_out)
+{
+    if (!bam || !n_sorted_out || !on_device_out) return spl_set_error(SPL_ERR_ARG, "spl_bam_any_order_sorted: null argument");
+    (void)spl_bam_start_host(bam);
+    std::unique_lock<std::mutex> lock(bam->mu);
+    bam->cv.wait(lock, [&]() { return bam->done; });
+    if (bam->err_code) return spl_set_error(bam->err_code, "%s", bam->error.c_str());
+    *n_sorted_out = bam->n_sorted;
+    *on_device_out = bam->sorted_on_device;
+    return SPL_OK;
 }
 
 // The counters: waits for the end of the decode, like spl_bam_filter_counts; the decode's error is the call's.
@@ -1574,6 +1709,7 @@ extern "C" int spl_bam_share_plan(spl_bam *bam, int n_shares, int *n_out)
     {
         std::lock_guard<std::mutex> lock(bam->mu);
         if (!bam->shares.empty()) { if (n_out) *n_out = (int)bam->shares.size(); return SPL_OK; }
+        if (bam->any_order) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_share_plan: shares are cut on the order of references, which a file opened with spl_bam_set_any_order need not have", bam->path.c_str());
     }
     int rc = spl_bam_walk_all(bam);
     if (rc) return rc;
@@ -1889,7 +2025,7 @@ extern "C" int spl_bam_wait_ref(spl_bam *bam, int tid, int64_t *n_reads_out, int
     if (tid < 0 || tid >= bam->n_refs) return spl_set_error(SPL_ERR_ARG, "tid %d out of range", tid);
     (void)spl_bam_start_host(bam); // (a deferred file nobody has decoded yet: on the host then)
     std::unique_lock<std::mutex> lock(bam->mu);
-    bam->cv.wait(lock, [&]() { return bam->done || tid < bam->complete_upto; });
+    bam->cv.wait(lock, [&]() { return bam->done || (!bam->any_order && tid < bam->complete_upto); }); // (spl_bam_set_any_order: a reference is complete, and in order, at the end only)
     const int rc = decode_status(bam);
     if (rc) return rc;
     if (n_reads_out) *n_reads_out = bam->ref_reads[(size_t)tid];
@@ -1903,7 +2039,7 @@ extern "C" int spl_bam_wait_all(spl_bam *bam, int *sorted_out)
     (void)spl_bam_start_host(bam);
     std::unique_lock<std::mutex> lock(bam->mu);
     bam->cv.wait(lock, [&]() { return bam->done; });
-    if (sorted_out) *sorted_out = bam->out_of_order ? 0 : 1;
+    if (sorted_out) *sorted_out = bam->out_of_order && !bam->any_order ? 0 : 1; // (spl_bam_set_any_order: the reads are handed out in order whatever the file's was)
     return decode_status(bam);
 }
 

@@ -27,6 +27,8 @@ SPL_BAM_HD inline int spl_bam_filter_verdict(const spl_bam_filter &f, uint32_t f
 spl_bam_filter spl_bam_get_filter(spl_bam *bam);           // what the file's decoders are to apply (fixed once a decode has begun)
 bool spl_bam_get_aux_strand(spl_bam *bam);                 // ... and whether they leave a strand byte per placed read (spl_bam_set_aux_strand)
 bool spl_bam_get_flagstat(spl_bam *bam);                   // ... and whether they count the flagstat categories (spl_bam_set_flagstat, spl_flagstat.h)
+bool spl_bam_get_any_order(spl_bam *bam);                  // ... and whether the records may come in any order (spl_bam_set_any_order): the decoder puts them in order
+void spl_bam_note_sorted(spl_bam *bam, int64_t n);         // (the device decoder, before spl_bam_adopt: it has sorted n reads -- spl_bam_any_order_sorted)
 
 // The reads of reference `tid` as a packer source: the decoder's own parts, in file order, nothing copied.  Waits until the
 // reference is complete (spl_bam_wait_ref).  The views stay valid until spl_bam_release_ref(tid) or spl_bam_close.

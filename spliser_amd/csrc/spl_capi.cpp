@@ -24,6 +24,7 @@
 #include "../../include/spliser.h"
 #include "spl_bam.h"
 #include "spl_inflate.h"
+#include "spl_sort.h"
 #include "spl_flagstat.h"
 #include "spl_devpack.h"
 #include "spl_device.h"
@@ -1356,6 +1357,7 @@ struct ShareOut { // (dropped: by the read filter -- flags, MAPQ; flagstat: the 
     DeviceReads *reads = nullptr;
     int64_t n_all = 0, dropped[2] = {0, 0}, flagstat[2 * SPL_FS_CATEGORIES] = {0};
     bool to_host = false; bool more_tokens = false;
+    int64_t n_sorted = 0; // (spl_bam_set_any_order: the records the device's sort put in order; 0: they were)
 };
 // What the caller of decode_share does with the share's reads, called by decode_share itself as its LAST act before it gives its
 // buffers, streams and events back -- which takes 10 ms for a large file, and whoever waits for the file's references need not.
@@ -1373,6 +1375,7 @@ extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_ou
     double t_pub = 0;
     const Publish adopt = [&](ShareOut &res) -> int {
         DeviceReads *keep = res.reads;
+        spl_bam_note_sorted(bam, res.n_sorted);
         spl_bam_set_device_reads(bam, keep, free_device_reads);
         spl_bam_set_fetch(bam, fetch_device_reads);
         spl_bam_set_fetch_xs(bam, fetch_device_xs);
@@ -1531,8 +1534,10 @@ struct ShareDecode {
     const spl_bam_filter filter = spl_bam_get_filter(bam); // (the file is claimed: nobody changes it now)
     const bool want_xs = spl_bam_get_aux_strand(bam);      // (likewise: a fifth array, the spliced reads' XS:A strand)
     const bool want_stat = spl_bam_get_flagstat(bam);      // (likewise: the scan counts the flagstat categories per block, a kernel adds up the accepted blocks')
+    const bool any_order = !share && spl_bam_get_any_order(bam); // (likewise: the records may come in any order -- sorted behind the last extraction, sort_records; the whole file only)
     // ---- everything the streams touch is declared before them
     DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds, d_xs, d_fstat, d_fsum;
+    DevBuf d_sortkeys[2], d_sortperm[2], d_sortwork, d_pos2, d_flag2, d_cigoff2, d_cigar2, d_tid2, d_xs2; // (spl_bam_set_any_order: got only when the sort runs)
     std::vector<spl_zblock> blocks, blocks0; // (blocks0: the early windows', for their launches before the directory is complete)
     std::unique_ptr<uint32_t[]> status;
     std::unique_ptr<spl_bscan[]> scan;
@@ -2215,9 +2220,9 @@ struct ShareDecode {
             if (sc.flags & SPL_BS_CORRUPT) wrong = "a record contradicts itself";
             else if (sc.flags & SPL_BS_NO_START) wrong = "no record boundary found near a block";
             else if (sc.flags & SPL_BS_NEEDS_HOST) wrong = "a CIGAR parked in a CG tag";
-            else if (sc.flags & SPL_BS_UNSORTED) wrong = "not sorted by reference";
+            else if ((sc.flags & SPL_BS_UNSORTED) && !any_order) wrong = "not sorted by reference";
             else if (sc.start != expect) wrong = "a guessed record boundary did not hold";
-            else if (sc.n_placed && sc.tid_first < last_tid) wrong = "not sorted by reference";
+            else if (sc.n_placed && sc.tid_first < last_tid && !any_order) wrong = "not sorted by reference";
             if ((sc.flags & SPL_BS_INCOMPLETE) || (wrong && more && sc.start != expect)) { b_done = b; held = (sc.flags & SPL_BS_INCOMPLETE) ? nullptr : wrong; break; }
             if (wrong) return wrong;
             if (sc.n_placed) last_tid = sc.tid_last;
@@ -2265,6 +2270,61 @@ struct ShareDecode {
         return SPL_OK;
     }
 
+    // ---- spl_bam_set_any_order, a file whose references do not come in order: the extracted arrays sorted by (reference id, POS,
+    // place in the file) on stream B.  Keys (id << 32 | POS) with the record's index as payload go through the passes of the stable
+    // radix sort (spl_sort.hip), least significant digit first, over the digits that can differ only: POS is at most the largest end
+    // any reference's reads have (d_maxend), the id below n_ref.  Then the arrays are gathered by the permutation -- the op counts
+    // in their new order scanned into the new cig_off, the CIGAR words copied run by run -- and take the unsorted ones' places.
+    // Scratch: two key and two payload buffers (24 bytes a record in all) and the arrays a second time; all given back in release_and_publish.
+    uint64_t n_sorted = 0;
+    double sort_ms = 0, sort_room_ms = 0, sort_bytes = 0; // (sort_room_ms: of sort_ms, giving the decode's buffers back and looking at what is free)
+    uint32_t sort_passes = 0, sort_pos_bits = 0, sort_tid_bits = 0;
+    int sort_records()
+    {
+        if (n_rec > 0xfffffff0ull) return to_host("more than 2^32 placed records in a file that is not in coordinate order");
+        const double t0 = host_now();
+        unsigned long long top = 1;
+        for (unsigned long long e : maxend) top = std::max(top, e);
+        while (sort_pos_bits < 31u && (top >> sort_pos_bits)) ++sort_pos_bits; // (POS is kept 1-based in 31 bits, and no read ends in front of its POS)
+        while (sort_tid_bits < 31u && ((uint64_t)std::max(n_ref - 1, 1) >> sort_tid_bits)) ++sort_tid_bits;
+        uint32_t shifts[8];
+        sort_passes = spl_dev_sort_passes(sort_pos_bits, sort_tid_bits, shifts);
+        // the decode's own buffers are done with (every window is extracted, stream B has been waited for): their room first
+        d_image.release();
+        for (int k = 0; k < NBUF; ++k) { d_stream[k].release(); d_zwork[k].release(); }
+        d_recs.release();
+        const size_t n = (size_t)n_rec, work_bytes = spl_dev_sort_work_bytes(n_rec);
+        const double need = 24.0 * (double)n + (double)work_bytes + (want_xs ? 15.0 : 14.0) * (double)n + 4.0 * (double)n_ops + 4096.0;
+        HIP_TRY(look_at_free());
+        if (need + slack > (double)free_b) return to_host("not enough device memory to sort the records");
+        const double t_room = host_now();
+        for (int k = 0; k < 2; ++k) { HIP_TRY(d_sortkeys[k].get(8 * n, pipe.b)); HIP_TRY(d_sortperm[k].get(4 * n, pipe.b)); }
+        HIP_TRY(d_sortwork.get(work_bytes, pipe.b));
+        HIP_TRY(d_pos2.get(4 * n, pipe.b)); HIP_TRY(d_flag2.get(2 * n, pipe.b)); HIP_TRY(d_cigoff2.get(4 * (n + 1), pipe.b));
+        HIP_TRY(d_cigar2.get(4 * (size_t)n_ops, pipe.b)); HIP_TRY(d_tid2.get(4 * n, pipe.b));
+        if (want_xs) HIP_TRY(d_xs2.get(n, pipe.b));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_make_keys(d_tid.as<int32_t>(), d_pos.as<int32_t>(), n_rec, d_sortkeys[0].as<uint64_t>(), pipe.b));
+        int cur = 0;
+        for (uint32_t k = 0; k < sort_passes; ++k, cur ^= 1)
+            HIP_TRY((hipError_t)spl_dev_launch_sort_pass(d_sortkeys[cur].as<uint64_t>(), k ? d_sortperm[cur].as<uint32_t>() : nullptr, n_rec, shifts[k], d_sortkeys[cur ^ 1].as<uint64_t>(),
+                                                         d_sortperm[cur ^ 1].as<uint32_t>(), d_sortwork.p, pipe.b));
+        const uint32_t *perm = d_sortperm[cur].as<uint32_t>();
+        HIP_TRY((hipError_t)spl_dev_launch_sort_gather(perm, d_sortkeys[cur].as<uint64_t>(), n_rec, d_pos.as<int32_t>(), d_flag.as<uint16_t>(), want_xs ? d_xs.as<uint8_t>() : nullptr,
+                                                       d_cigoff.as<uint32_t>(), d_pos2.as<int32_t>(), d_flag2.as<uint16_t>(), want_xs ? d_xs2.as<uint8_t>() : nullptr, d_tid2.as<int32_t>(),
+                                                       d_cigoff2.as<uint32_t>(), pipe.b));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_cigoff2.as<uint32_t>() + 1, n_rec, d_sortwork.p, pipe.b)); // (n_ops < 2^32: records_done)
+        HIP_TRY((hipError_t)spl_dev_launch_sort_cigar(perm, n_rec, d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), d_cigoff2.as<uint32_t>(), d_cigar2.as<uint32_t>(), pipe.b));
+        HIP_TRY(hipStreamSynchronize(pipe.b));
+        std::swap(d_pos.p, d_pos2.p); std::swap(d_flag.p, d_flag2.p); std::swap(d_cigoff.p, d_cigoff2.p); std::swap(d_cigar.p, d_cigar2.p); std::swap(d_tid.p, d_tid2.p);
+        std::swap(d_xs.p, d_xs2.p);
+        n_sorted = n_rec;
+        sort_ms = 1e3 * (host_now() - t0);
+        sort_room_ms = 1e3 * (t_room - t0);
+        // (make_keys 16; a pass 8 + 8 + 12 and the payloads it reads; gather 12 + 8 and the fields twice; scan 12; the CIGARs' offsets 20, their words twice)
+        sort_bytes = (double)n * (16.0 + 28.0 * sort_passes + 4.0 * (sort_passes - 1) + 20.0 + 2.0 * (want_xs ? 15.0 : 14.0) + 12.0 + 20.0) + 8.0 * (double)n_ops;
+        return SPL_OK;
+    }
+
     // ---- stage: the end of the chain, where each reference's records are (bounds kernel) -> the DeviceReads in res
     int finish()
     {
@@ -2273,21 +2333,39 @@ struct ShareDecode {
         if (!last_share && expect != sh.u_hi) return to_host("a share's records do not end where the next share's begin");
         if (last_share && expect != stream_len) return to_host("the file ends inside a record");
         if (!cap_rec) { const int rc = make_room(0, 0, 1.0); if (rc) return rc; } // (a share without a record of its own)
-        HIP_TRY((hipError_t)spl_dev_launch_bam_bounds(d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), n_rec, d_bounds.as<uint64_t>(), d_nbounds.as<uint32_t>(), bounds_cap, pipe.b));
         maxend.assign((size_t)std::max(n_ref, 1), 0);
-        bounds.assign(2 * (size_t)bounds_cap, 0);
         HIP_TRY(hipMemcpyAsync(maxend.data(), d_maxend.p, 8 * maxend.size(), hipMemcpyDeviceToHost, pipe.b));
-        HIP_TRY(hipMemcpyAsync(bounds.data(), d_bounds.p, 16 * (size_t)bounds_cap, hipMemcpyDeviceToHost, pipe.b));
-        HIP_TRY(hipMemcpyAsync(&n_bounds, d_nbounds.p, 4, hipMemcpyDeviceToHost, pipe.b));
         if (want_stat) HIP_TRY(hipMemcpyAsync(fsum, d_fsum.p, sizeof(fsum), hipMemcpyDeviceToHost, pipe.b));
-        HIP_TRY(hipStreamSynchronize(pipe.b));
-        join_readers();
-        for (hipError_t e : errs) HIP_TRY(e);
-        if (n_bounds > bounds_cap) return to_host("not sorted by reference");
         struct Run { uint64_t first; int32_t tid; uint32_t op; };
         std::vector<Run> runs;
-        for (uint32_t k = 0; k < n_bounds; ++k) runs.push_back(Run{bounds[2 * k], (int32_t)(uint32_t)bounds[2 * k + 1], (uint32_t)(bounds[2 * k + 1] >> 32)});
-        std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.first < b.first; });
+        // where each reference's records are, and whether the references come in order (every run's id above the one before)
+        auto find_runs = [&](bool &in_order) -> int {
+            HIP_TRY((hipError_t)spl_dev_launch_bam_bounds(d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), n_rec, d_bounds.as<uint64_t>(), d_nbounds.as<uint32_t>(), bounds_cap, pipe.b));
+            bounds.assign(2 * (size_t)bounds_cap, 0);
+            HIP_TRY(hipMemcpyAsync(bounds.data(), d_bounds.p, 16 * (size_t)bounds_cap, hipMemcpyDeviceToHost, pipe.b));
+            HIP_TRY(hipMemcpyAsync(&n_bounds, d_nbounds.p, 4, hipMemcpyDeviceToHost, pipe.b));
+            HIP_TRY(hipStreamSynchronize(pipe.b));
+            runs.clear();
+            in_order = n_bounds <= bounds_cap;
+            if (!in_order) return SPL_OK;
+            for (uint32_t k = 0; k < n_bounds; ++k) runs.push_back(Run{bounds[2 * k], (int32_t)(uint32_t)bounds[2 * k + 1], (uint32_t)(bounds[2 * k + 1] >> 32)});
+            std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.first < b.first; });
+            for (size_t k = 0; k < runs.size() && in_order; ++k) in_order = runs[k].tid >= 0 && runs[k].tid < n_ref && !(k && runs[k].tid <= runs[k - 1].tid);
+            return SPL_OK;
+        };
+        bool in_order = false;
+        int rc_runs = find_runs(in_order);
+        if (rc_runs) return rc_runs;
+        join_readers();
+        for (hipError_t e : errs) HIP_TRY(e);
+        if (!in_order && any_order) { // (spl_bam_set_any_order: the arrays sorted by (reference, POS, place in the file), then the runs of the sorted ones)
+            rc_runs = sort_records();
+            if (rc_runs) return rc_runs;
+            HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, pipe.b));
+            rc_runs = find_runs(in_order);
+            if (rc_runs) return rc_runs;
+        }
+        if (!in_order) return to_host("not sorted by reference");
         const size_t nr = (size_t)std::max(n_ref, 1);
         // The records stay where they are, BAM-native in device memory: a read set on this device is laid out from them by kernels
         // (spl_devpack.hip), and the host gets copies only if somebody asks the file for them (fetch_device_reads).
@@ -2298,7 +2376,6 @@ struct ShareDecode {
         keep->ref_first.assign(nr, 0); keep->ref_n.assign(nr, 0); keep->ref_max.assign(nr, 0); keep->ref_ops.assign(nr, 0);
         for (size_t k = 0; k < runs.size(); ++k) {
             const int32_t t = runs[k].tid;
-            if (t < 0 || t >= n_ref || (k && t <= runs[k - 1].tid)) { delete keep; return to_host("not sorted by reference"); }
             const bool last = k + 1 == runs.size();
             keep->ref_first[(size_t)t] = (int64_t)runs[k].first;
             keep->ref_n[(size_t)t] = (int64_t)((last ? n_rec : runs[k + 1].first) - runs[k].first);
@@ -2310,11 +2387,15 @@ struct ShareDecode {
         d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = d_xs.p = nullptr; // (the caller owns them from here)
         res.reads = keep;
         res.n_all = n_all;
+        res.n_sorted = (int64_t)n_sorted;
         res.dropped[0] = n_drop_flags;
         res.dropped[1] = n_drop_mapq;
         for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.flagstat[q] = (int64_t)fsum[q];
         if (timing) fprintf(stderr, "[spl_bam_decode_device] device %d: blocks %zu..%zu, %.1f MB -> %.1f MB inflated in %zu window%s, %llu placed records of %lld: %.4f s\n", c->device, lo, hi,
                             n_bytes / 1e6, (stream_len - stream_begin) / 1e6, n_win, n_win == 1 ? "" : "s", (unsigned long long)n_rec, (long long)n_all, host_now() - t_begin);
+        if (timing && n_sorted)
+            fprintf(stderr, "[spl_bam_decode_device] device %d: not in coordinate order: %llu records sorted in %.3f ms (%.3f of them before the scratch memory was asked for), %u passes (%u bits of POS, %u of the reference id), %.1f MB read and written\n",
+                    c->device, (unsigned long long)n_sorted, sort_ms, sort_room_ms, sort_passes, sort_pos_bits, sort_tid_bits, sort_bytes / 1e6);
         if (timing) {
             fprintf(stderr, "[spl_bam_decode_device] device %d: staging buffers at %.4f s, the ring's memory %.4f, streams and events %.4f, the first window's buffers %.4f, its kernels on their streams %.4f\n",
                     c->device, t_stage, t_image, t_pipe, t_early_bufs, t_early);
@@ -2335,6 +2416,8 @@ struct ShareDecode {
         for (int k = 0; k < NBUF; ++k) { d_stream[k].release(); d_zwork[k].release(); }
         d_blocks0.release(); d_status0.release(); d_recs.release(); d_blocks.release(); d_status.release(); d_scan.release(); d_recoff.release(); d_opoff.release();
         d_tid.release(); d_maxend.release(); d_bounds.release(); d_nbounds.release(); d_fstat.release(); d_fsum.release();
+        for (int k = 0; k < 2; ++k) { d_sortkeys[k].release(); d_sortperm[k].release(); }
+        d_sortwork.release(); d_pos2.release(); d_flag2.release(); d_cigoff2.release(); d_cigar2.release(); d_tid2.release(); d_xs2.release();
         const int told = publish(res);
         // ... and not at once: 500 events and five streams destroyed are 10 ms of the HIP runtime's locks, which the thread that was
         // told above needs now -- for the layout kernels, the chunk order's upload, the counting launches (its 9 ms took 17 beside
@@ -2357,6 +2440,29 @@ static int decode_share(spl_ctx *c, spl_bam *bam, const spl_bam_share *share, Sh
     if (rc == SPL_OK) rc = d.finish();
     if (rc == SPL_OK) return d.release_and_publish(publish);
     return rc == STOPPED ? SPL_OK : rc;
+}
+
+// The device's sort on a caller's keys (test hook): exactly the launches sort_records makes for keys of key_bits bits.
+extern "C" int spl_sort_keys_device(spl_ctx *c, const uint64_t *keys, int64_t n, int key_bits, uint32_t *perm_out)
+{
+    if (!c || n < 0 || (n && (!keys || !perm_out))) return spl_set_error(SPL_ERR_ARG, "spl_sort_keys_device: null argument");
+    if (key_bits < 1 || key_bits > 64) return spl_set_error(SPL_ERR_ARG, "spl_sort_keys_device: key_bits %d is not in 1..64", key_bits);
+    if ((uint64_t)n > 0xfffffff0ull) return spl_set_error(SPL_ERR_ARG, "spl_sort_keys_device: more than 2^32 keys");
+    if (n == 0) return SPL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t shifts[8];
+    const uint32_t n_pass = spl_dev_sort_passes((uint32_t)std::min(key_bits, 32), (uint32_t)std::max(key_bits - 32, 0), shifts);
+    DevBuf d_keys[2], d_perm[2], d_work;
+    for (int k = 0; k < 2; ++k) { HIP_TRY(d_keys[k].get(8 * (size_t)n, c->stream)); HIP_TRY(d_perm[k].get(4 * (size_t)n, c->stream)); }
+    HIP_TRY(d_work.get(spl_dev_sort_work_bytes((uint64_t)n), c->stream));
+    HIP_TRY(hipMemcpyAsync(d_keys[0].p, keys, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    int cur = 0;
+    for (uint32_t k = 0; k < n_pass; ++k, cur ^= 1)
+        HIP_TRY((hipError_t)spl_dev_launch_sort_pass(d_keys[cur].as<uint64_t>(), k ? d_perm[cur].as<uint32_t>() : nullptr, (uint64_t)n, shifts[k], d_keys[cur ^ 1].as<uint64_t>(),
+                                                     d_perm[cur ^ 1].as<uint32_t>(), d_work.p, c->stream));
+    HIP_TRY(hipMemcpyAsync(perm_out, d_perm[cur].p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPL_OK;
 }
 
 // What a read set's device segments need between the arrays and the counters, on the context's main stream, nothing for the host

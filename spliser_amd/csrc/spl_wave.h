@@ -28,6 +28,7 @@ WV_DEV uint32_t readlane(uint32_t v, uint32_t uniform_lane) { return (uint32_t)_
 WV_DEV void sync() { __syncthreads(); }
 WV_DEV uint32_t lds_max(uint32_t *p, uint32_t v) { return atomicMax(p, v); }
 WV_DEV uint32_t lds_or(uint32_t *p, uint32_t v) { return atomicOr(p, v); }
+WV_DEV uint32_t lds_add(uint32_t *p, uint32_t v) { return atomicAdd(p, v); }
 WV_DEV uint32_t popc64(uint64_t m) { return (uint32_t)__popcll(m); }
 WV_DEV uint32_t ffs64(uint64_t m) { return (uint32_t)__ffsll((long long)m) - 1u; } // index of the lowest set bit (m != 0)
 WV_DEV uint32_t brev32(uint32_t v) { return __brev(v); }

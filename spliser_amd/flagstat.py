@@ -42,18 +42,21 @@ def write_and_log(path, counts, log):
     log("Library size: %d mapped reads (%d primary)" % (int(counts[MAPPED][0]), int(counts[PRIMARY_MAPPED][0])))
 
 
-def flagstat(inBAM, outputPath, devices=(0,), threads=0, gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, log=None):
+def flagstat(inBAM, outputPath, devices=(0,), threads=0, gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, log=None, anyOrder=False):
     """Writes ``outputPath`` (the sixteen lines) and returns the counters, (16, 2).  ``minMapQ`` / ``requireFlags`` /
     ``excludeFlags``: the read filter of ``process`` -- the counters of the pre-filtered file.  ``gpuDecode``: as for ``process``.
+    ``anyOrder``: the BAM may be in any record order and stays on the GPU all the same (``process``); the counters do not depend on it.
 
     The decode is the NORMAL one with its reads dropped: the blocks are inflated, scanned and their records extracted as for
     ``process``, and nothing is counted against sites.  A decode that stops after the scan would save the extraction kernel's
     share of the decode (about a tenth of it) at the price of a second path through the window loop; it is not arranged."""
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
     filt = _process.read_filter(minMapQ, requireFlags, excludeFlags)
-    source = _process.open_and_decode(inBAM, tuple(devices), gpuDecode, threads, filt, flagstat=True)
+    source = _process.open_and_decode(inBAM, tuple(devices), gpuDecode, threads, filt, flagstat=True, any_order=bool(anyOrder), log=log)
     try:
         counts = source.flagstat()
+        if anyOrder:
+            _process.log_any_order(source, log)
         if gpuDecode is not False and source.decline_reason():
             log("  (the alignment file was decoded on host threads, not on the GPU: %s)" % source.decline_reason())
         _process.log_filter(source, filt, log)

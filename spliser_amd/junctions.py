@@ -170,11 +170,12 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
 
 
 def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=8, minIntron=70, maxIntron=500000,
-              qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False):
+              qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, anyOrder=False):
     """Writes ``outputPath`` (a BED12 file) and returns the number of junctions.  ``minMapQ`` / ``requireFlags`` / ``excludeFlags``:
     the read filter of ``process`` (samtools view's -q / -f / -F; changes results) -- the junctions of the reads that pass.
     ``strandFromXS``: for an unstranded library, the strand column from the reads' XS:A tag (regtools' ``-s XS``) instead of ``?``;
-    an alternative to ``isStranded``."""
+    an alternative to ``isStranded``.  ``anyOrder`` (changes no result): the BAM may be in any record order -- its reads are
+    coordinate-sorted on the GPU after the decode instead of by ``samtools sort`` beforehand (``process``)."""
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
     stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
     if isStranded and stranded == 0:
@@ -184,9 +185,11 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
     if strandFromXS:
         stranded = native.STRAND_FROM_XS
     filt = _process.read_filter(minMapQ, requireFlags, excludeFlags)
-    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, filt, aux_strand=bool(strandFromXS))   # (on the GPU(s), like `process`)
+    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, filt, aux_strand=bool(strandFromXS), any_order=bool(anyOrder), log=log)   # (on the GPU(s), like `process`)
     try:
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+        if anyOrder:
+            _process.log_any_order(source, log)
         tally = [0, 0, 0] if strandFromXS else None
         tables = tables_of_source(source, tuple(devices), chroms, stranded, minAnchor, minIntron, maxIntron, tally=tally)
         if isinstance(source, native.BamFile) and not source.wait_all():

@@ -51,7 +51,7 @@ EXPORTS = [
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
     "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_reads_has_strand", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
-    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
+    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
     "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
@@ -618,14 +618,20 @@ class BamFile(object):
     them is never extracted, whoever decodes the file.  ``filter_counts`` says how many did.
 
     ``flagstat``: whoever decodes the file also counts samtools flagstat's categories over all its records
-    (``spl_bam_set_flagstat``); ``flagstat()`` has them."""
+    (``spl_bam_set_flagstat``); ``flagstat()`` has them.
 
-    def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False, flagstat=False):
+    ``any_order``: the file's records may come in any order, e.g. as the aligner wrote them -- whoever decodes the file hands
+    every reference's reads out sorted by (POS, place in the file) (``spl_bam_set_any_order``), ``wait_all`` says True and
+    ``wait_ref`` returns at the end of the decode; ``any_order_sorted()`` says what that took."""
+
+    def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False, flagstat=False,
+                 any_order=False):
         self._h = ctypes.c_void_p()
         self.filter = (int(min_mapq), int(require_flags), int(exclude_flags))
         self.aux_strand = False
         self.counts_flagstat = False
-        filtered = self.filter != (0, 0, 0) or bool(aux_strand) or bool(flagstat)   # (all must be there before the decode starts: opened deferred, started below)
+        self.any_order = False
+        filtered = self.filter != (0, 0, 0) or bool(aux_strand) or bool(flagstat) or bool(any_order)   # (all must be there before the decode starts: opened deferred, started below)
         opener = lib().spl_bam_open_deferred if defer or filtered else (lib().spl_bam_open_stream if stream else lib().spl_bam_open)
         _check(opener(os.fsencode(path), ctypes.c_int(threads), ctypes.byref(self._h)))
         if filtered:
@@ -635,6 +641,8 @@ class BamFile(object):
                     self.set_aux_strand(True)
                 if flagstat:
                     self.set_flagstat(True)
+                if any_order:
+                    self.set_any_order(True)
                 if not defer:
                     _check(lib().spl_bam_start(self._h))
                     if not stream:
@@ -666,6 +674,19 @@ class BamFile(object):
         (``spl_bam_set_flagstat``; an error afterwards)."""
         _check(lib().spl_bam_set_flagstat(self._h, ctypes.c_int(1 if on else 0)))
         self.counts_flagstat = bool(on)
+
+    def set_any_order(self, on=True):
+        """A ``defer=True`` file nobody decodes yet: its records may come in any order, and the decode -- whoever does it -- hands
+        every reference's reads out sorted by (POS, place in the file) (``spl_bam_set_any_order``; an error afterwards)."""
+        _check(lib().spl_bam_set_any_order(self._h, ctypes.c_int(1 if on else 0)))
+        self.any_order = bool(on)
+
+    def any_order_sorted(self):
+        """-> (reads that were put in order -- 0 when the file was in order already --, True when the GPU's sort did it and False
+        when the host threads did); waits for the end of the decode (``spl_bam_any_order_sorted``)."""
+        n, dev = ctypes.c_int64(0), ctypes.c_int(0)
+        _check(lib().spl_bam_any_order_sorted(self._h, ctypes.byref(n), ctypes.byref(dev)))
+        return int(n.value), bool(dev.value)
 
     def flagstat(self):
         """-> int64 array (16, 2): per category of samtools flagstat (``FLAGSTAT_LABELS``) the QC-passed and the QC-failed records
@@ -913,6 +934,16 @@ class _BamHandle(object):
 FLAGSTAT_LABELS = ("in total (QC-passed reads + QC-failed reads)", "primary", "secondary", "supplementary", "duplicates", "primary duplicates", "mapped",
                    "primary mapped", "paired in sequencing", "read1", "read2", "properly paired", "with itself and mate mapped", "singletons",
                    "with mate mapped to a different chr", "with mate mapped to a different chr (mapQ>=5)")
+
+
+def sort_keys_device(ctx, keys, key_bits):
+    """The device's stable radix sort on ``keys`` (uint64) -- exactly the passes the decode of an ``any_order`` file runs for keys of
+    ``key_bits`` bits (``spl_sort_keys_device``) -> the permutation, uint32: entry i = index of the key that comes i-th, equal keys
+    in the order they came in."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    perm = np.zeros(len(keys), np.uint32)
+    _check(lib().spl_sort_keys_device(ctx._h, _ptr(keys) if len(keys) else None, ctypes.c_int64(len(keys)), ctypes.c_int(int(key_bits)), _ptr(perm) if len(keys) else None))
+    return perm
 
 
 def flagstat_add_host(flag, tid, next_tid, mapq, counters=None):

@@ -68,17 +68,18 @@ class _SamSource(object):
         return self._counts[1], self._counts[2]
 
 
-def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER, aux_strand=False, flagstat=False):
+def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER, aux_strand=False, flagstat=False, any_order=False):
     """BAM (BGZF) through the native decoder; plain SAM text through the Python reader.  ``stream=True``: the BAM decoder
     returns after the header and decodes in the background (``native.BamFile``); ``defer=True``: nothing is decoded until
     somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``read_filter``: which records either keeps.
     ``aux_strand``: either also leaves a strand byte per read, the XS:A tag of the spliced ones (``--strandFromXS``).
-    ``flagstat``: the BAM decoder also counts the flagstat categories (``--flagstat``; SAM text has no such counters: an error)."""
+    ``flagstat``: the BAM decoder also counts the flagstat categories (``--flagstat``; SAM text has no such counters: an error).
+    ``any_order``: the BAM's records may come in any order (``--anyOrder``; SAM text is read whole and per reference anyway)."""
     with open(path, "rb") as fh:
         magic = fh.read(4)
     q, f, F = read_filter
     if magic[:2] == b"\x1f\x8b":
-        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=aux_strand, flagstat=flagstat)
+        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=aux_strand, flagstat=flagstat, any_order=any_order)
     if flagstat:
         raise native.SpliserNativeError(-5, "%s: flagstat counters are counted while a BAM file is decoded; this is not one" % path)
     if magic[:1] == b"@" or b"\t" in open(path, "rb").readline():
@@ -99,16 +100,23 @@ def wait_deferred_close():
     return time.perf_counter() - t0
 
 
-def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER, aux_strand=False, flagstat=False):
+def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER, aux_strand=False, flagstat=False, any_order=False, log=None):
     """The alignment file opened and its decode started: on the GPU(s) -- with several devices every one inflates and extracts
     the stretch of the file that holds its own references (``BamFile.decode_on_devices_async``), and counts them -- or, told so
     (``gpuDecode=False``), on host threads.  SAM text has one reader.  ``read_filter`` is with the source before any of them starts,
     and so is ``aux_strand`` (``BamFile.set_aux_strand``: a strand byte per read for ``--strandFromXS``), and ``flagstat``
-    (``BamFile.set_flagstat``: the decoders count the flagstat categories)."""
-    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter, aux_strand=aux_strand, flagstat=flagstat)
+    (``BamFile.set_flagstat``: the decoders count the flagstat categories), and ``any_order`` (``BamFile.set_any_order``: the
+    records may come in any order, the decoder sorts them).  A file in any order is decoded whole on the first device -- shares
+    are cut on the order of references --, whichever devices count its chromosomes afterwards."""
+    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter, aux_strand=aux_strand, flagstat=flagstat,
+                             any_order=any_order)
     if isinstance(source, native.BamFile) and gpuDecode is not False:
         try:
-            if len(devices) > 1:
+            if len(devices) > 1 and any_order:
+                if log is not None:
+                    log("  (--anyOrder: the alignment file is decoded whole on device %d, not in shares over %d devices)" % (devices[0], len(devices)))
+                source.decode_on_device_async(devices[0])
+            elif len(devices) > 1:
                 source.decode_on_devices_async(list(devices))
             else:
                 source.decode_on_device_async(devices[0])
@@ -116,6 +124,14 @@ def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FIL
             source.close()
             raise
     return source
+
+
+def log_any_order(source, log):
+    """``--anyOrder``: one line when the file was not in coordinate order (waits for the end of the decode), nothing when it was."""
+    if isinstance(source, native.BamFile) and source.any_order:
+        n, on_gpu = source.any_order_sorted()
+        if n:
+            log("  (the alignment file is not in coordinate order: %d reads sorted %s)" % (n, "on the GPU" if on_gpu else "on host threads"))
 
 
 class _Replan(Exception):
@@ -477,8 +493,13 @@ def write_tsv(output_path, table, results, is_beta2_cryptic):
 def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
             isStranded=False, strandedType=None, isbeta2Cryptic=False, devices=(0,), threads=0, log=_log, checkJunctions=False,
             gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False,
-            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, flagstat=False):
+            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, flagstat=False, anyOrder=False):
     """SpliSER_v0_1_8.py:695-720, keyword-compatible with the reference's argparse dests.
+
+    ``anyOrder`` (this build only; changes no result): the BAM may be in any record order, e.g. as the aligner wrote it -- its reads
+    are coordinate-sorted on the GPU after the decode (``spl_bam_set_any_order``) instead of by ``samtools sort`` beforehand.  The
+    whole file is waited for before Step 3 (a reference of such a file is complete only at its end), nothing is counted twice, and
+    a run without ``inBed`` takes the file as well.  A file that is in order is decoded and counted exactly as without the flag.
 
     ``flagstat`` (this build only; changes no result): also write ``<outputPath>.flagstat.txt`` -- samtools flagstat's sixteen
     lines, counted by the decode this call does anyway (``flagstat.py``), over the WHOLE file whatever ``qChrom`` / ``qGene`` say
@@ -532,7 +553,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     # The alignment file does not depend on Steps 0-2: it is decoded on native threads while the site table is built here, and
     # goes on decoding while Step 3 counts the chromosomes that are complete.  An unreadable file is an error here already
     # (block directory and header are read by the opening call).
-    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt, aux_strand=bool(strandFromXS), flagstat=bool(flagstat))     # (the decode runs beside Steps 0-2, wherever it runs)
+    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt, aux_strand=bool(strandFromXS), flagstat=bool(flagstat), any_order=bool(anyOrder), log=log)     # (the decode runs beside Steps 0-2, wherever it runs)
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
@@ -550,6 +571,9 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
         log("Processing sample 1 out of 1")
         writer = _TsvWriter(outputPath, table, isbeta2Cryptic)
         jrows = {}
+        if anyOrder and isinstance(source, native.BamFile):     # (a reference of a file in any order is complete, and in order, at the file's end only)
+            source.wait_all()
+            log_any_order(source, log)
         try:
             results = process_sites(table, source, qChrom, isStranded, strandedType, isbeta2Cryptic, devices=devices, log=log,
                                     timings=timings, on_result=writer.add, on_tables=writer.expect,
