@@ -22,7 +22,8 @@ from ast import literal_eval
 
 import numpy as np
 
-from . import native
+from . import native, process as _process, readstore
+from .process import DecodeOptions
 
 HEADER = ("Sample\tRegion\tSite\tStrand\tGene\tSSE\talpha_count\tbeta1_count\tbeta2Simple_count\tbeta2Cryptic_count\t"
           "beta2_weighted\tPartners\tCompetitors\n")
@@ -234,7 +235,7 @@ class _QueryTable(object):
         return self._arrays[chrom]
 
 
-def fill_gaps(merged, bam_paths, is_stranded, stranded_type, devices=(0,), threads=0, log=_log, kept_reads=None, read_filter=(0, 0, 0)):
+def fill_gaps(merged, bam_paths, is_stranded, stranded_type, devices=(0,), threads=0, log=_log, kept_reads=None, options=DecodeOptions()):
     """Answer every (site, sample) query of ``merge_sites``'s result on the GPUs (``fill_tables``).
     -> {(site index, sample idx): (beta1, beta2Simple)}"""
     tables = {idx: _QueryTable(qs) for idx, qs in gap_queries(merged).items()}
@@ -245,21 +246,20 @@ def fill_gaps(merged, bam_paths, is_stranded, stranded_type, devices=(0,), threa
         with lock:
             for si, x, y in zip(site, beta1.tolist(), b2.tolist()):
                 results[(int(si), idx)] = (int(x), int(y))
-    fill_tables(tables, take, bam_paths, is_stranded, stranded_type, devices=devices, threads=threads, log=log, kept_reads=kept_reads, read_filter=read_filter)
+    fill_tables(tables, take, bam_paths, is_stranded, stranded_type, devices=devices, threads=threads, log=log, kept_reads=kept_reads, options=options)
     return results
 
 
-def open_kept_reads(kept_reads, bam_paths, read_filter=(0, 0, 0)):
+def open_kept_reads(kept_reads, bam_paths, options=DecodeOptions()):
     """The samples' kept reads (``process --keepReads``), opened on a few threads while the caller does something else (the walk
     over the sample files does not need them; opening one maps 0.4 GB and checks it against its checksum): -> a function
     ``idx -> ReadStore or None`` that waits for that sample's.  Samples without such a file, with a stale one or one kept under
     another read filter give None."""
     from concurrent.futures import ThreadPoolExecutor
-    from . import readstore
     if not kept_reads:
         return lambda idx: None
     pool = ThreadPoolExecutor(max_workers=3)
-    futures = {idx: pool.submit(readstore.open_if_fresh, path, bam_paths[idx], read_filter) for idx, path in enumerate(kept_reads) if path}
+    futures = {idx: pool.submit(readstore.open_if_fresh, path, bam_paths[idx], options.read_filter) for idx, path in enumerate(kept_reads) if path}
     pool.shutdown(wait=False)
 
     def get(idx):
@@ -270,15 +270,14 @@ def open_kept_reads(kept_reads, bam_paths, read_filter=(0, 0, 0)):
 
 
 def fill_tables(tables, take, bam_paths, is_stranded, stranded_type, devices=(0,), threads=0, log=_log, kept_reads=None, opened=None,
-                read_filter=(0, 0, 0)):
+                options=DecodeOptions()):
     """Answer the query tables ``{sample idx: table}`` on the GPUs.  Each sample's BAM is decoded once, in the background (on
     the GPU when the call has one device, like ``process``); its chromosomes are dealt to the devices
     (``process.process_sites``: one context per device, a chromosome goes to its GPU as soon as the decoder has it complete) and
     counted in ``combine_mode`` (a flanking read counts toward beta2Simple, :529-536); several samples are in flight at a time,
     each starting on another device.  ``take(idx, merged-site indexes, beta1, beta2Simple)`` gets a region's answers.
-    ``read_filter``: every sample's decode runs under it, and only reads kept under it are taken instead."""
+    ``options``: every sample's decode runs under them, and only reads kept under their read filter are taken instead."""
     from concurrent.futures import ThreadPoolExecutor
-    from . import process as _process, readstore
     devices = tuple(devices)
 
     def one(idx):
@@ -288,18 +287,18 @@ def fill_tables(tables, take, bam_paths, is_stranded, stranded_type, devices=(0,
         if opened is not None:
             source = opened(idx)          # (opened while the files were walked: open_kept_reads)
         else:
-            source = readstore.open_if_fresh(kept_reads[idx], bam_paths[idx], read_filter) if kept_reads and kept_reads[idx] else None
+            source = readstore.open_if_fresh(kept_reads[idx], bam_paths[idx], options.read_filter) if kept_reads and kept_reads[idx] else None
         if source is not None:
             log("  ({}: reads kept by process, {} not decoded again)".format(os.path.basename(kept_reads[idx]), os.path.basename(bam_paths[idx])))
         else:
-            source = _process.open_and_decode(bam_paths[idx], devs, None, threads, read_filter)   # (on the sample's first device when it has one device)
+            source = _process.open_and_decode(bam_paths[idx], devs, None, threads, options)   # (on the sample's first device when it has one device)
         try:
             out = _process.process_sites(table, source, "All", is_stranded, stranded_type, False, devices=devs, combine_mode=1,
                                          log=lambda m: None)
             if isinstance(source, native.BamFile) and not source.wait_all():   # not sorted by reference: again, from the whole decode
                 out = _process.process_sites(table, source, "All", is_stranded, stranded_type, False, devices=devs, combine_mode=1,
                                              log=lambda m: None)
-            _process.log_filter(source, read_filter, log, os.path.basename(bam_paths[idx]))
+            _process.log_filter(source, options.read_filter, log, os.path.basename(bam_paths[idx]))
         finally:
             if hasattr(source, "close"):
                 source.close()
@@ -389,15 +388,13 @@ def combine(samplesFile, outputPath, qGene="All", isStranded=False, strandedType
     The walk over the files runs on columns in the native library (``native.Combine``); files its parsers do not take -- and
     ``native_walk=False`` or SPL_COMBINE_PYTHON=1 -- are walked by the Python statement of the same loop below."""
     t_all = time.perf_counter()
-    from . import process as _proc
-    filt = _proc.read_filter(minMapQ, requireFlags, excludeFlags)
-    _proc.wait_deferred_close()       # (`process --keepReads` calls of this very interpreter may still be writing what this call is about to look for)
+    options = DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags))
+    _process.wait_deferred_close()       # (`process --keepReads` calls of this very interpreter may still be writing what this call is about to look for)
     log("Combining samples...")
     titles, tsvs, bams = read_samples_file(samplesFile, strict=shallow is None)
     if native_walk is None:
         native_walk = not os.environ.get("SPL_COMBINE_PYTHON")
     # what `process --keepReads` may have left beside each sample's .SpliSER.tsv (taken only if it is still its BAM's: readstore)
-    from . import readstore
     kept = None if os.environ.get("SPL_IGNORE_KEPT_READS") else [readstore.path_for_tsv(p) for p in tsvs]
     tm = None
     if native_walk:
@@ -414,15 +411,15 @@ def combine(samplesFile, outputPath, qGene="All", isStranded=False, strandedType
             if exc.code != -5:
                 raise
         if walk is not None:
-            tm = _combine_native(walk, time.perf_counter() - t_open, titles, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept, filt)
+            tm = _combine_native(walk, time.perf_counter() - t_open, titles, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept, options)
     if tm is None:
-        tm = _combine_python(titles, tsvs, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept, filt)
+        tm = _combine_python(titles, tsvs, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept, options)
     if tm:
         tm["total_s"] = time.perf_counter() - t_all
     return tm
 
 
-def _combine_native(walk, t_parse, titles, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept=None, read_filter=(0, 0, 0)):
+def _combine_native(walk, t_parse, titles, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept=None, options=DecodeOptions()):
     with walk:
         log("Establishing order of genomic regions.")
         chroms = region_order_from_runs(walk.region_runs())
@@ -434,7 +431,7 @@ def _combine_native(walk, t_parse, titles, bams, outputPath, qGene, isStranded, 
             walk.keep_gene(qGene)
         log("Iterating through files in parallel, to interleave lines and fill gaps.")
         t0 = time.perf_counter()
-        opened = open_kept_reads(kept, bams, read_filter)      # (beside the walk: the gap fill finds the samples' kept reads open)
+        opened = open_kept_reads(kept, bams, options)      # (beside the walk: the gap fill finds the samples' kept reads open)
         for pos, seen in walk.merge(chroms, isStranded, qGene, shallow):
             log("Skipped site {} for insufficient evidence, only {} samples with Site using minimum reads".format(pos, seen))
         tables = {}
@@ -448,7 +445,7 @@ def _combine_native(walk, t_parse, titles, bams, outputPath, qGene, isStranded, 
         n_gap_sites = walk.n_gap_sites
         t0 = time.perf_counter()
         if tables:
-            fill_tables(tables, walk.answers, bams, isStranded, strandedType, devices=devices, threads=threads, log=log, kept_reads=kept, opened=opened, read_filter=read_filter)
+            fill_tables(tables, walk.answers, bams, isStranded, strandedType, devices=devices, threads=threads, log=log, kept_reads=kept, opened=opened, options=options)
         if hasattr(opened, "close"):
             opened.close()
         t_fill = time.perf_counter() - t0
@@ -461,7 +458,7 @@ def _combine_native(walk, t_parse, titles, bams, outputPath, qGene, isStranded, 
                 queries=n_queries)
 
 
-def _combine_python(titles, tsvs, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept=None, read_filter=(0, 0, 0)):
+def _combine_python(titles, tsvs, bams, outputPath, qGene, isStranded, strandedType, isbeta2Cryptic, devices, threads, log, shallow, kept=None, options=DecodeOptions()):
     t0 = time.perf_counter()
     rows = [_parse_tsv(p) for p in tsvs]
     t_parse = time.perf_counter() - t0
@@ -479,7 +476,7 @@ def _combine_python(titles, tsvs, bams, outputPath, qGene, isStranded, strandedT
     n_gap_sites = sum(1 for m in merged if m.queries)
     t_merge = time.perf_counter() - t0
     t0 = time.perf_counter()
-    results = fill_gaps(merged, bams, isStranded, strandedType, devices=devices, threads=threads, log=log, kept_reads=kept, read_filter=read_filter) if n_gap_sites else {}
+    results = fill_gaps(merged, bams, isStranded, strandedType, devices=devices, threads=threads, log=log, kept_reads=kept, options=options) if n_gap_sites else {}
     t_fill = time.perf_counter() - t0
     t0 = time.perf_counter()
     write_combined(outputPath + ".combined.tsv", merged, titles, results, isbeta2Cryptic)

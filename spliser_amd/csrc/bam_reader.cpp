@@ -38,6 +38,7 @@
 #include "spl_bam.h"
 #include "spl_bam_aux.h"
 #include "spl_flagstat.h"
+static_assert(SPL_BAM_N_FSTAT == 2 * SPL_FS_CATEGORIES, "spl_bam_totals::fstat holds every flagstat counter");
 #include "spl_error.h"
 
 namespace {
@@ -479,15 +480,8 @@ struct spl_bam {
     bool done = false;
     int err_code = 0;
     std::string error;
-    int64_t n_records = 0;
-    spl_bam_filter filter = {0, 0, 0}; // which placed records are kept (spl_bam_set_filter; fixed once claim != 0)
-    int64_t dropped[2] = {0, 0};       // records the filter dropped: by their flags, by their MAPQ
-    bool aux_strand = false;           // a strand byte per placed read beside its flag (spl_bam_set_aux_strand; fixed once claim != 0)
-    bool flagstat = false;             // the decode counts the flagstat categories (spl_bam_set_flagstat; fixed once claim != 0)
-    bool any_order = false;            // the records may come in any order: whoever decodes hands every reference's reads out sorted by (POS, place in the file) (spl_bam_set_any_order; fixed once claim != 0)
-    int64_t n_sorted = 0;              // ... the reads that were put in order for it (0: the file was in order already) ...
-    int sorted_on_device = 0;          // ... and by whom: the device decoder's sort (1) or the host threads (0)
-    int64_t fstat[2 * SPL_FS_CATEGORIES] = {0}; // ... over every record the filter keeps, placed or not: [2 c + q] (spl_flagstat.h)
+    spl_bam_decode_opts opts; // what the decoders are to do (the spl_bam_set_* setters; fixed once claim != 0)
+    spl_bam_totals totals;    // ... and what they counted (complete when `done`)
     // ---- BAM-native arrays per reference, assembled on demand (spl_bam_reads) ----
     std::vector<RefFinal> refs_storage; // (never resized after the header: RefFinal is not copyable)
     std::vector<char> assembled;
@@ -509,7 +503,7 @@ struct spl_bam {
     std::vector<DevShare> dev_shares;
     // a decode in shares (spl_bam_share_plan): the plan, and what the shares' decoders have reported so far
     std::vector<spl_bam_share> shares;
-    struct ShareResult { bool reported = false, failed = false; void *handle = nullptr; void (*free_fn)(void *) = nullptr; std::vector<int64_t> first, n, max_end; int64_t n_records = 0, dropped[2] = {0, 0}, fstat[2 * SPL_FS_CATEGORIES] = {0}; };
+    struct ShareResult { bool reported = false, failed = false; void *handle = nullptr; void (*free_fn)(void *) = nullptr; std::vector<int64_t> first, n, max_end; spl_bam_totals totals; };
     std::vector<ShareResult> share_results;
     bool shares_on_device = false;
     std::atomic<bool> cancel{false};       // spl_bam_cancel: whoever decodes stops at the next batch / window; nobody starts
@@ -557,13 +551,18 @@ inline const uint8_t *record_cigar(const uint8_t *r, uint32_t bs, size_t need, u
 // the position reached (a record boundary).  Two walks: the first checks every record and sizes the parts, the second fills
 // arrays of exactly that size -- the bytes are in the caller's cache both times.
 // Records the filter does not keep are counted (dropped[0]: by flags, [1]: by MAPQ) and otherwise treated like records without a position.
-// want_xs: one more array per part, a strand byte per read -- the aux area of a read whose CIGAR holds an N op walked by the
+// opts.aux_strand: one more array per part, a strand byte per read -- the aux area of a read whose CIGAR holds an N op walked by the
 // function the device's extraction calls (spl_bam_aux.h), 0 for every other read.  A CIGAR parked in a CG tag is the read's CIGAR.
-// fstat (or null): the flagstat counters, [2 c + q], of EVERY record walked that the filter keeps -- without a reference or a
+// opts.flagstat: the flagstat counters, [2 c + q], of EVERY record walked that the filter keeps -- without a reference or a
 // position too, where `dropped` has placeable records only (spl_flagstat.h: the one definition, the device's scan's as well).
-const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, const spl_bam_filter &filter, bool want_xs, Arena &arena, std::vector<Part> &parts,
-                               int64_t &n_records, int64_t *dropped, int64_t *fstat, std::string &err, bool &fatal)
+// What is counted is ADDED to `out`.
+const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, const spl_bam_decode_opts &opts, Arena &arena, std::vector<Part> &parts, spl_bam_totals &out,
+                               std::string &err, bool &fatal)
 {
+    const spl_bam_filter &filter = opts.filter; // (plain values for the two walks: nothing of `opts` is looked up per record)
+    const bool want_xs = opts.aux_strand;
+    int64_t &n_records = out.n_records;
+    int64_t *const dropped = out.dropped, *const fstat = opts.flagstat ? out.fstat : nullptr;
     struct Run { int32_t tid; size_t n, ops; const uint8_t *begin; };
     Run few[4];
     std::vector<Run> many; // (more than four changes of reference in one stretch: an unsorted file)
@@ -730,7 +729,7 @@ bool order_parts(spl_bam *bam, std::string &err)
             if (tid >= bam->n_refs) break;
             const std::vector<PendingPart *> &parts = bam->parts[(size_t)tid];
             size_t n = 0, g = 0;
-            bool with_xs = bam->aux_strand;
+            bool with_xs = bam->opts.aux_strand;
             for (const PendingPart *pt : parts) { n += pt->reads.n; g += pt->reads.n_ops; with_xs = with_xs && (pt->reads.n == 0 || pt->reads.xs != nullptr); }
             if (n == 0) continue;
             Done &d = done[(size_t)tid];
@@ -797,8 +796,8 @@ bool order_parts(spl_bam *bam, std::string &err)
         bam->parts[(size_t)tid].assign(1, d.part);
         n_sorted += (int64_t)d.part->reads.n;
     }
-    bam->n_sorted = n_sorted;
-    bam->sorted_on_device = 0;
+    bam->totals.n_sorted = n_sorted;
+    bam->totals.sorted_on_device = 0;
     return true;
 }
 
@@ -817,7 +816,7 @@ bool assemble_ref(spl_bam *bam, int tid, std::string &err)
     dst.flag = (uint16_t *)big_alloc(sizeof(uint16_t) * (size_t)std::max<int64_t>(n, 1));
     dst.cig_off = (uint32_t *)big_alloc(sizeof(uint32_t) * (size_t)(n + 1));
     dst.cigar = (uint32_t *)big_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(g, 1));
-    bool with_xs = bam->aux_strand;
+    bool with_xs = bam->opts.aux_strand;
     for (const PendingPart *pt : parts) with_xs = with_xs && (pt->reads.n == 0 || pt->reads.xs != nullptr);
     if (with_xs) dst.xs = (uint8_t *)big_alloc((size_t)std::max<int64_t>(n, 1));
     if (!dst.pos || !dst.flag || !dst.cig_off || !dst.cigar || (with_xs && !dst.xs)) { err = "out of host memory"; return false; }
@@ -868,8 +867,7 @@ struct BatchOut {
     std::vector<uint8_t> head, tail;
     size_t len = 0, start = 0, i0 = 0, i1 = 0; // bytes inflated, guessed first boundary; the batch's blocks
     uint64_t u0 = 0;                            // offset of the batch in the inflated stream
-    int64_t nrec = 0, dropped[2] = {0, 0};
-    int64_t fstat[2 * SPL_FS_CATEGORIES] = {0}; // (spl_bam_set_flagstat: the batch's counters, added to the file's when the batch is committed)
+    spl_bam_totals totals;                      // (the batch's: added to the file's when the batch is committed)
     bool inflate_bad = false, parse_bad = false;
     bool known = false;                         // the first boundary is the end of the BAM header, not a guess
     bool skip = false;                          // nothing but BAM header in it
@@ -881,9 +879,7 @@ void decode_worker(spl_bam *bam)
     const uint8_t *file = (const uint8_t *)bam->map;
     BlockDir &dir = bam->dir;
     const int n_ref = bam->n_refs;
-    const spl_bam_filter filter = bam->filter; // (nobody changes it once a decoder has the file)
-    const bool want_xs = bam->aux_strand;
-    const bool want_stat = bam->flagstat;
+    const spl_bam_decode_opts opts = bam->opts; // (nobody changes them once a decoder has the file)
     const NodeCpus node; // the NUMA node this thread runs on (the opening thread's, inherited): all worker threads stay there
     auto env_num = [](const char *name, long dflt) { const char *e = getenv(name); const long v = e ? atol(e) : 0; return v > 0 ? v : dflt; };
     const size_t BATCH = (size_t)env_num("SPL_BAM_BATCH_BLOCKS", 32);
@@ -969,7 +965,7 @@ void decode_worker(spl_bam *bam)
                 o.start = (size_t)(p - buf);
                 std::string err;
                 bool fatal = false;
-                reached = (size_t)(extract_records(p, end, n_ref, filter, want_xs, arena, o.parts, o.nrec, o.dropped, want_stat ? o.fstat : nullptr, err, fatal) - buf);
+                reached = (size_t)(extract_records(p, end, n_ref, opts, arena, o.parts, o.totals, err, fatal) - buf);
                 o.parse_bad = fatal;
                 if (!o.known) o.head.assign((const uint8_t *)buf, (const uint8_t *)buf + o.start);
                 o.tail.assign((const uint8_t *)buf + reached, end);
@@ -994,13 +990,10 @@ void decode_worker(spl_bam *bam)
     size_t n_resync = 0;
     auto walk = [&](const uint8_t *p0, const uint8_t *p1, bool &fatal) { // sequential, authoritative: commits what it parses
         std::vector<Part> seq;
-        int64_t n = 0, drop[2] = {0, 0}, fs[2 * SPL_FS_CATEGORIES] = {0};
-        const uint8_t *r = extract_records(p0, p1, n_ref, filter, want_xs, arena_mine, seq, n, drop, want_stat ? fs : nullptr, fail, fatal);
+        spl_bam_totals t;
+        const uint8_t *r = extract_records(p0, p1, n_ref, opts, arena_mine, seq, t, fail, fatal);
         merge_parts(bam, seq);
-        bam->n_records += n;
-        bam->dropped[0] += drop[0];
-        bam->dropped[1] += drop[1];
-        for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] += fs[c];
+        bam->totals.add(t);
         return r;
     };
     size_t n_batches = 0;
@@ -1057,10 +1050,7 @@ void decode_worker(spl_bam *bam)
         if (handled) {
         } else if (accept) {
             merge_parts(bam, o.parts);
-            bam->n_records += o.nrec;
-            bam->dropped[0] += o.dropped[0];
-            bam->dropped[1] += o.dropped[1];
-            for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] += o.fstat[c];
+            bam->totals.add(o.totals);
             carry.swap(o.tail);
         } else { // the guess did not hold: this batch again, sequentially, from the known boundary
             ++n_resync;
@@ -1077,9 +1067,7 @@ void decode_worker(spl_bam *bam)
         o.parts.clear();
         o.head.clear();
         o.tail.clear();
-        o.nrec = 0;
-        o.dropped[0] = o.dropped[1] = 0;
-        for (int64_t &x : o.fstat) x = 0;
+        o.totals = spl_bam_totals();
         const double c2 = now();
         t_merge += c2 - c1;
         o.state.store(0, std::memory_order_relaxed);
@@ -1107,7 +1095,7 @@ void decode_worker(spl_bam *bam)
     {
         std::lock_guard<std::mutex> lock(bam->mu);
         if (!fail.empty() && !bam->err_code) { bam->error = bam->path + ": " + fail; bam->err_code = SPL_ERR_FORMAT; }
-        if (bam->any_order && bam->out_of_order && !bam->err_code) { // (spl_bam_set_any_order: nobody has been handed a reference yet, spl_bam_wait_ref)
+        if (opts.any_order && bam->out_of_order && !bam->err_code) { // (spl_bam_set_any_order: nobody has been handed a reference yet, spl_bam_wait_ref)
             std::string why;
             if (!order_parts(bam, why)) { bam->error = bam->path + ": " + why; bam->err_code = SPL_ERR_NOMEM; }
         }
@@ -1235,108 +1223,77 @@ static int open_file(const char *path, int n_threads, bool start_now, spl_bam **
 extern "C" int spl_bam_open_stream(const char *path, int n_threads, spl_bam **out) { return open_file(path, n_threads, true, out); }
 extern "C" int spl_bam_open_deferred(const char *path, int n_threads, spl_bam **out) { return open_file(path, n_threads, false, out); }
 
-// Which placed records the decode keeps (spl_bam.h: spl_bam_filter_verdict).  Only while nobody decodes the file or waits for it.
+// ---- the decode switches (spl_bam.h: spl_bam_decode_opts).  One rule for all of them: only while nobody decodes the file or
+// waits for it.  A setter checks its own argument, then changes its field under this guard.
+template <class Set> static int set_opt(spl_bam *bam, const char *who, Set set)
+{
+    if (!bam) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (bam->claim != 0 || bam->done) return spl_set_error(SPL_ERR_ARG, "%s: %s: the file is being decoded (or waited for) already", bam->path.c_str(), who);
+    set(bam->opts);
+    return SPL_OK;
+}
+
+// Which placed records the decode keeps (spl_bam.h: spl_bam_filter_verdict).
 extern "C" int spl_bam_set_filter(spl_bam *bam, int min_mapq, int require_flags, int exclude_flags)
 {
     if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_filter: null argument");
     if (min_mapq < 0 || min_mapq > 255) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_filter: min_mapq %d is not in 0..255", min_mapq);
     if (require_flags < 0 || require_flags > 65535 || exclude_flags < 0 || exclude_flags > 65535)
         return spl_set_error(SPL_ERR_ARG, "spl_bam_set_filter: flag masks must be in 0..65535");
-    std::lock_guard<std::mutex> lock(bam->mu);
-    if (bam->claim != 0 || bam->done)
-        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_filter: the file is being decoded (or waited for) already", bam->path.c_str());
-    bam->filter = spl_bam_filter{(uint32_t)min_mapq, (uint32_t)require_flags, (uint32_t)exclude_flags};
-    return SPL_OK;
+    return set_opt(bam, "spl_bam_set_filter", [&](spl_bam_decode_opts &o) { o.filter = spl_bam_filter{(uint32_t)min_mapq, (uint32_t)require_flags, (uint32_t)exclude_flags}; });
 }
+// A strand byte per placed read beside its flag, from the aligner's XS:A tag.
+extern "C" int spl_bam_set_aux_strand(spl_bam *bam, int on) { return set_opt(bam, "spl_bam_set_aux_strand", [&](spl_bam_decode_opts &o) { o.aux_strand = on != 0; }); }
+// The flagstat counters, counted by whoever decodes the file.
+extern "C" int spl_bam_set_flagstat(spl_bam *bam, int on) { return set_opt(bam, "spl_bam_set_flagstat", [&](spl_bam_decode_opts &o) { o.flagstat = on != 0; }); }
+// The file's records may come in any order: whoever decodes it hands every reference's reads out sorted by (POS, place in the file).
+extern "C" int spl_bam_set_any_order(spl_bam *bam, int on) { return set_opt(bam, "spl_bam_set_any_order", [&](spl_bam_decode_opts &o) { o.any_order = on != 0; }); }
 
-// A strand byte per placed read beside its flag, from the aligner's XS:A tag.  The same rule as spl_bam_set_filter: only while
-// nobody decodes the file or waits for it.
-extern "C" int spl_bam_set_aux_strand(spl_bam *bam, int on)
-{
-    if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_aux_strand: null argument");
-    std::lock_guard<std::mutex> lock(bam->mu);
-    if (bam->claim != 0 || bam->done)
-        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_aux_strand: the file is being decoded (or waited for) already", bam->path.c_str());
-    bam->aux_strand = on != 0;
-    return SPL_OK;
-}
-
-bool spl_bam_get_aux_strand(spl_bam *bam)
+spl_bam_decode_opts spl_bam_get_opts(spl_bam *bam)
 {
     std::lock_guard<std::mutex> lock(bam->mu);
-    return bam->aux_strand;
+    return bam->opts;
 }
 
-// The flagstat counters, counted by whoever decodes the file.  The same rule as spl_bam_set_filter: only while nobody decodes the
-// file or waits for it.
-extern "C" int spl_bam_set_flagstat(spl_bam *bam, int on)
+// The end of the decode, for whoever asks what it counted: the host threads decode if nobody does yet.  Returns with bam->mu held.
+static std::unique_lock<std::mutex> wait_for_end(spl_bam *bam)
 {
-    if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_flagstat: null argument");
-    std::lock_guard<std::mutex> lock(bam->mu);
-    if (bam->claim != 0 || bam->done)
-        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_flagstat: the file is being decoded (or waited for) already", bam->path.c_str());
-    bam->flagstat = on != 0;
-    return SPL_OK;
+    (void)spl_bam_start_host(bam);
+    std::unique_lock<std::mutex> lock(bam->mu);
+    bam->cv.wait(lock, [&]() { return bam->done; });
+    return lock;
 }
 
-bool spl_bam_get_flagstat(spl_bam *bam)
-{
-    std::lock_guard<std::mutex> lock(bam->mu);
-    return bam->flagstat;
-}
-
-// The file's records may come in any order: whoever decodes it hands every reference's reads out sorted by (POS, place in the
-// file).  The same rule as spl_bam_set_filter: only while nobody decodes the file or waits for it.
-extern "C" int spl_bam_set_any_order(spl_bam *bam, int on)
-{
-    if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_set_any_order: null argument");
-    std::lock_guard<std::mutex> lock(bam->mu);
-    if (bam->claim != 0 || bam->done)
-        return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_set_any_order: the file is being decoded (or waited for) already", bam->path.c_str());
-    bam->any_order = on != 0;
-    return SPL_OK;
-}
-
-bool spl_bam_get_any_order(spl_bam *bam)
-{
-    std::lock_guard<std::mutex> lock(bam->mu);
-    return bam->any_order;
-}
-
-// (the device decoder, before it hands its arrays over: it has sorted n reads)
-void spl_bam_note_sorted(spl_bam *bam, int64_t n)
-{
-    std::lock_guard<std::mutex> lock(bam->mu);
-    bam->n_sorted = n;
-    bam->sorted_on_device = n > 0 ? 1 : 0;
-}
-
-// What spl_bam_set_any_order came to: waits for the end of the decode, like spl_bam_filter_counts; the decode's error is the call's.
+// What spl_bam_set_any_order came to; the decode's error is the call's.
 extern "C" int spl_bam_any_order_sorted(spl_bam *bam, int64_t *n_sorted_out, int *on_device_out)
 {
     if (!bam || !n_sorted_out || !on_device_out) return spl_set_error(SPL_ERR_ARG, "spl_bam_any_order_sorted: null argument");
-    (void)spl_bam_start_host(bam);
-    std::unique_lock<std::mutex> lock(bam->mu);
-    bam->cv.wait(lock, [&]() { return bam->done; });
+    const std::unique_lock<std::mutex> lock = wait_for_end(bam);
     if (bam->err_code) return spl_set_error(bam->err_code, "%s", bam->error.c_str());
-    *n_sorted_out = bam->n_sorted;
-    *on_device_out = bam->sorted_on_device;
+    *n_sorted_out = bam->totals.n_sorted;
+    *on_device_out = bam->totals.sorted_on_device;
     return SPL_OK;
 }
 
-// The counters: waits for the end of the decode, like spl_bam_filter_counts; the decode's error is the call's.
+// The counters; the decode's error is the call's.
 extern "C" int spl_bam_flagstat(spl_bam *bam, int64_t *out32)
 {
     if (!bam || !out32) return spl_set_error(SPL_ERR_ARG, "spl_bam_flagstat: null argument");
-    {
-        std::lock_guard<std::mutex> lock(bam->mu);
-        if (!bam->flagstat) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_flagstat: counting was not switched on (spl_bam_set_flagstat)", bam->path.c_str());
-    }
-    (void)spl_bam_start_host(bam);
-    std::unique_lock<std::mutex> lock(bam->mu);
-    bam->cv.wait(lock, [&]() { return bam->done; });
+    if (!spl_bam_get_opts(bam).flagstat) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_flagstat: counting was not switched on (spl_bam_set_flagstat)", bam->path.c_str());
+    const std::unique_lock<std::mutex> lock = wait_for_end(bam);
     if (bam->err_code) return spl_set_error(bam->err_code, "%s", bam->error.c_str());
-    for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) out32[c] = bam->fstat[c];
+    for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) out32[c] = bam->totals.fstat[c];
+    return SPL_OK;
+}
+
+// The records the filter dropped, by flags and by MAPQ.  (Like spl_bam_n_records, it does not report the decode's error.)
+extern "C" int spl_bam_filter_counts(spl_bam *bam, int64_t *out2)
+{
+    if (!bam || !out2) return spl_set_error(SPL_ERR_ARG, "spl_bam_filter_counts: null argument");
+    const std::unique_lock<std::mutex> lock = wait_for_end(bam);
+    out2[0] = bam->totals.dropped[0];
+    out2[1] = bam->totals.dropped[1];
     return SPL_OK;
 }
 
@@ -1355,24 +1312,6 @@ extern "C" int spl_bam_aux_strand_host(const uint8_t *aux, uint32_t len, uint8_t
     static const uint8_t none = 0;
     const uint8_t *p = len ? aux : &none;
     *out = spl_bam_aux_strand(p, p + len);
-    return SPL_OK;
-}
-
-spl_bam_filter spl_bam_get_filter(spl_bam *bam)
-{
-    std::lock_guard<std::mutex> lock(bam->mu);
-    return bam->filter;
-}
-
-// The records the filter dropped, by flags and by MAPQ: waits for the end of the decode, like spl_bam_n_records.
-extern "C" int spl_bam_filter_counts(spl_bam *bam, int64_t *out2)
-{
-    if (!bam || !out2) return spl_set_error(SPL_ERR_ARG, "spl_bam_filter_counts: null argument");
-    (void)spl_bam_start_host(bam);
-    std::unique_lock<std::mutex> lock(bam->mu);
-    bam->cv.wait(lock, [&]() { return bam->done; });
-    out2[0] = bam->dropped[0];
-    out2[1] = bam->dropped[1];
     return SPL_OK;
 }
 
@@ -1569,7 +1508,7 @@ uint64_t spl_bam_header_end(const spl_bam *bam) { return bam->header_bytes; }
 int spl_bam_thread_count(const spl_bam *bam) { return bam->n_threads; }
 
 int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar, const int64_t *ref_first, const int64_t *ref_n,
-                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped, const int64_t *flagstat)
+                  const int64_t *ref_max_end, const spl_bam_totals &totals)
 {
     std::lock_guard<std::mutex> lock(bam->mu);
     if (bam->claim != 1) return spl_set_error(SPL_ERR_ARG, "spl_bam_adopt: the file is not claimed by the device decoder");
@@ -1596,10 +1535,7 @@ int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off,
         bam->ref_reads[(size_t)t] = ref_n[t];
         bam->ref_max_end[(size_t)t] = ref_max_end[t];
     }
-    bam->n_records = n_records_total;
-    bam->dropped[0] = dropped[0];
-    bam->dropped[1] = dropped[1];
-    for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] = flagstat ? flagstat[c] : 0;
+    bam->totals = totals;
     bam->max_tid_seen = bam->n_refs - 1;
     bam->complete_upto = bam->n_refs;
     bam->done = true;
@@ -1709,7 +1645,7 @@ extern "C" int spl_bam_share_plan(spl_bam *bam, int n_shares, int *n_out)
     {
         std::lock_guard<std::mutex> lock(bam->mu);
         if (!bam->shares.empty()) { if (n_out) *n_out = (int)bam->shares.size(); return SPL_OK; }
-        if (bam->any_order) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_share_plan: shares are cut on the order of references, which a file opened with spl_bam_set_any_order need not have", bam->path.c_str());
+        if (bam->opts.any_order) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_share_plan: shares are cut on the order of references, which a file opened with spl_bam_set_any_order need not have", bam->path.c_str());
     }
     int rc = spl_bam_walk_all(bam);
     if (rc) return rc;
@@ -1814,7 +1750,7 @@ extern "C" int spl_bam_share_count_host(spl_bam *bam, int k, int64_t *per_tid)
         if (bs < 32) return spl_set_error(SPL_ERR_FORMAT, "%s: share %d: corrupt record", bam->path.c_str(), k);
         const int32_t tid = le32s(c + 4), pos0 = le32s(c + 8);
         const bool placed = tid >= 0 && tid < bam->n_refs && pos0 >= 0;
-        if (!placed || spl_bam_filter_verdict(bam->filter, le16(c + 18), c[13]) == SPL_BAM_KEPT) // (a filter's records are nobody's: spl_bam_filter_counts)
+        if (!placed || spl_bam_filter_verdict(bam->opts.filter, le16(c + 18), c[13]) == SPL_BAM_KEPT) // (a filter's records are nobody's: spl_bam_filter_counts)
             per_tid[tid < 0 || tid >= bam->n_refs ? bam->n_refs : tid]++;
         u += 4ull + bs;
     }
@@ -1832,7 +1768,7 @@ int spl_bam_share_get(spl_bam *bam, int k, spl_bam_share *out)
 }
 
 int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *), const int64_t *ref_first, const int64_t *ref_n,
-                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, const int64_t *flagstat, int failed)
+                       const int64_t *ref_max_end, const spl_bam_totals &totals, int failed)
 {
     std::unique_lock<std::mutex> lock(bam->mu);
     if (k < 0 || (size_t)k >= bam->share_results.size() || bam->share_results[(size_t)k].reported) {
@@ -1845,11 +1781,9 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
     r.failed = failed != 0;
     r.handle = handle;
     r.free_fn = free_fn;
-    r.n_records = n_records;
+    r.totals.n_records = totals.n_records;
     if (!r.failed) {
-        r.dropped[0] = dropped[0];
-        r.dropped[1] = dropped[1];
-        for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) r.fstat[c] = flagstat ? flagstat[c] : 0;
+        r.totals = totals;
         r.first.assign(ref_first, ref_first + bam->n_refs);
         r.n.assign(ref_n, ref_n + bam->n_refs);
         r.max_end.assign(ref_max_end, ref_max_end + bam->n_refs);
@@ -1880,17 +1814,14 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
         return SPL_OK;
     }
     bam->lazy = true;
-    int64_t n_all = 0, drop[2] = {0, 0}, fs[2 * SPL_FS_CATEGORIES] = {0};
+    spl_bam_totals sum;
     for (size_t s = 0; s < bam->share_results.size(); ++s) {
         spl_bam::ShareResult &x = bam->share_results[s];
         spl_bam::DevShare d;
         d.handle = x.handle; d.free_fn = x.free_fn; d.share = (int)s;
         x.handle = nullptr;
         bam->dev_shares.push_back(d);
-        n_all += x.n_records;
-        drop[0] += x.dropped[0];
-        drop[1] += x.dropped[1];
-        for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) fs[c] += x.fstat[c];
+        sum.add(x.totals);
         for (int t = 0; t < bam->n_refs; ++t) { // (a reference may have a part in several shares: file order = share order)
             if (x.n[(size_t)t] <= 0) continue;
             PendingPart *pp = new PendingPart();
@@ -1904,10 +1835,7 @@ int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *
             bam->ref_max_end[(size_t)t] = std::max(bam->ref_max_end[(size_t)t], x.max_end[(size_t)t]);
         }
     }
-    bam->n_records = n_all;
-    bam->dropped[0] = drop[0];
-    bam->dropped[1] = drop[1];
-    for (int c = 0; c < 2 * SPL_FS_CATEGORIES; ++c) bam->fstat[c] = fs[c];
+    bam->totals = sum;
     bam->max_tid_seen = bam->n_refs - 1;
     bam->complete_upto = bam->n_refs;
     bam->shares_on_device = true;
@@ -1983,7 +1911,7 @@ static int fetch_lazy(spl_bam *bam, std::unique_lock<std::mutex> &lock)
         const int share = bam->dev_shares[k].share;
         int32_t *pos = nullptr; uint16_t *flag = nullptr; uint32_t *cig_off = nullptr, *cigar = nullptr;
         uint8_t *xs = nullptr;
-        int (*const fetch_xs)(void *, uint8_t **) = bam->aux_strand ? bam->dev_fetch_xs : nullptr;
+        int (*const fetch_xs)(void *, uint8_t **) = bam->opts.aux_strand ? bam->dev_fetch_xs : nullptr;
         lock.unlock();
         int rc = bam->dev_fetch(handle, &pos, &flag, &cig_off, &cigar);
         if (rc == SPL_OK && fetch_xs) { // (the fifth array, where the decode left one: copied with the others)
@@ -2025,7 +1953,7 @@ extern "C" int spl_bam_wait_ref(spl_bam *bam, int tid, int64_t *n_reads_out, int
     if (tid < 0 || tid >= bam->n_refs) return spl_set_error(SPL_ERR_ARG, "tid %d out of range", tid);
     (void)spl_bam_start_host(bam); // (a deferred file nobody has decoded yet: on the host then)
     std::unique_lock<std::mutex> lock(bam->mu);
-    bam->cv.wait(lock, [&]() { return bam->done || (!bam->any_order && tid < bam->complete_upto); }); // (spl_bam_set_any_order: a reference is complete, and in order, at the end only)
+    bam->cv.wait(lock, [&]() { return bam->done || (!bam->opts.any_order && tid < bam->complete_upto); }); // (spl_bam_set_any_order: a reference is complete, and in order, at the end only)
     const int rc = decode_status(bam);
     if (rc) return rc;
     if (n_reads_out) *n_reads_out = bam->ref_reads[(size_t)tid];
@@ -2039,7 +1967,7 @@ extern "C" int spl_bam_wait_all(spl_bam *bam, int *sorted_out)
     (void)spl_bam_start_host(bam);
     std::unique_lock<std::mutex> lock(bam->mu);
     bam->cv.wait(lock, [&]() { return bam->done; });
-    if (sorted_out) *sorted_out = bam->out_of_order && !bam->any_order ? 0 : 1; // (spl_bam_set_any_order: the reads are handed out in order whatever the file's was)
+    if (sorted_out) *sorted_out = bam->out_of_order && !bam->opts.any_order ? 0 : 1; // (spl_bam_set_any_order: the reads are handed out in order whatever the file's was)
     return decode_status(bam);
 }
 
@@ -2067,11 +1995,8 @@ extern "C" int64_t spl_bam_ref_length(const spl_bam *bam, int tid)
 extern "C" int64_t spl_bam_n_records(const spl_bam *bam)
 {
     if (!bam) return 0;
-    spl_bam *b = const_cast<spl_bam *>(bam);
-    (void)spl_bam_start_host(b);
-    std::unique_lock<std::mutex> lock(b->mu);
-    b->cv.wait(lock, [&]() { return b->done; });
-    return b->n_records;
+    const std::unique_lock<std::mutex> lock = wait_for_end(const_cast<spl_bam *>(bam));
+    return bam->totals.n_records;
 }
 
 extern "C" int spl_bam_reads(const spl_bam *cbam, int tid, spl_reads *out, int64_t *max_end_out)

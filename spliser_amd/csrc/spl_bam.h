@@ -24,11 +24,36 @@ SPL_BAM_HD inline int spl_bam_filter_verdict(const spl_bam_filter &f, uint32_t f
     if ((flag & f.exclude_flags) != 0u || (flag & f.require_flags) != f.require_flags) return SPL_BAM_DROP_FLAGS;
     return mapq >= f.min_mapq ? SPL_BAM_KEPT : SPL_BAM_DROP_MAPQ;
 }
-spl_bam_filter spl_bam_get_filter(spl_bam *bam);           // what the file's decoders are to apply (fixed once a decode has begun)
-bool spl_bam_get_aux_strand(spl_bam *bam);                 // ... and whether they leave a strand byte per placed read (spl_bam_set_aux_strand)
-bool spl_bam_get_flagstat(spl_bam *bam);                   // ... and whether they count the flagstat categories (spl_bam_set_flagstat, spl_flagstat.h)
-bool spl_bam_get_any_order(spl_bam *bam);                  // ... and whether the records may come in any order (spl_bam_set_any_order): the decoder puts them in order
-void spl_bam_note_sorted(spl_bam *bam, int64_t n);         // (the device decoder, before spl_bam_adopt: it has sorted n reads -- spl_bam_any_order_sorted)
+
+// ---- what a decoder is asked to do, and what it counted -----------------------------------------------------------------
+// The file's decode switches, one record: set through spl_bam_set_filter / _aux_strand / _flagstat / _any_order while nobody
+// decodes the file, fixed from then on.  A decoder takes ONE copy (spl_bam_get_opts) before its first record.  A new switch is
+// one field here, one setter body (bam_reader.cpp) and one field of process.DecodeOptions.
+struct spl_bam_decode_opts {
+    spl_bam_filter filter = {0, 0, 0}; // which placed records are kept
+    bool aux_strand = false;           // a strand byte per placed read beside its flag, from the aligner's XS:A tag
+    bool flagstat = false;             // count the flagstat categories (spl_flagstat.h)
+    bool any_order = false;            // the records may come in any order: the decoder hands every reference's reads out sorted by (POS, place in the file)
+};
+spl_bam_decode_opts spl_bam_get_opts(spl_bam *bam);
+// What a decode counted, of a batch, a share or the whole file -- they add up.  dropped: the placed records the filter dropped by
+// their flags / by their MAPQ (spl_bam_filter_counts).  fstat: the counters of spl_bam_flagstat, [2 c + q], over every record the
+// filter keeps; zeros when nobody asked.  n_sorted: the reads put in order for any_order (0: the file was in order), by the
+// device's sort (sorted_on_device = 1) or the host threads (0).
+#define SPL_BAM_N_FSTAT 32 // 2 * SPL_FS_CATEGORIES of spl_flagstat.h, which includes this header: bam_reader.cpp asserts the two agree
+struct spl_bam_totals {
+    int64_t n_records = 0, dropped[2] = {0, 0}, fstat[SPL_BAM_N_FSTAT] = {0}, n_sorted = 0;
+    int sorted_on_device = 0;
+    void add(const spl_bam_totals &o)
+    {
+        n_records += o.n_records;
+        dropped[0] += o.dropped[0];
+        dropped[1] += o.dropped[1];
+        for (int c = 0; c < SPL_BAM_N_FSTAT; ++c) fstat[c] += o.fstat[c];
+        n_sorted += o.n_sorted;
+        sorted_on_device |= o.sorted_on_device;
+    }
+};
 
 // The reads of reference `tid` as a packer source: the decoder's own parts, in file order, nothing copied.  Waits until the
 // reference is complete (spl_bam_wait_ref).  The views stay valid until spl_bam_release_ref(tid) or spl_bam_close.
@@ -51,10 +76,9 @@ int spl_bam_thread_count(const spl_bam *bam);
 bool spl_bam_sample_density(spl_bam *bam, size_t b_lo, size_t b_hi, uint64_t *n_rec_out, uint64_t *n_ops_out, uint64_t *n_bytes_out);
 // The placed records of the whole file in file order as four malloc'ed arrays (the file takes them over and frees them with
 // free()); reference t has records [ref_first[t], ref_first[t] + ref_n[t]), cig_off holds n_total + 1 offsets into cigar.
-// dropped[2]: the records the file's filter dropped by their flags / by their MAPQ (spl_bam_filter_counts).  flagstat: the 32
-// counters of spl_bam_flagstat over every record of the file, or null (nobody asked: spl_bam_get_flagstat).
+// totals: what the decode counted over the whole file.
 int spl_bam_adopt(spl_bam *bam, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar, const int64_t *ref_first, const int64_t *ref_n,
-                  const int64_t *ref_max_end, int64_t n_records_total, const int64_t *dropped, const int64_t *flagstat);
+                  const int64_t *ref_max_end, const spl_bam_totals &totals);
 // what the device decoder keeps in device memory for the device packer: an opaque handle, freed with the file
 void spl_bam_set_device_reads(spl_bam *bam, void *handle, void (*free_fn)(void *));
 void *spl_bam_device_reads(spl_bam *bam, int tid);          // the handle that holds ALL of reference `tid` (null: none does -- no device decode, or the reference lies in several shares)
@@ -73,10 +97,10 @@ struct spl_bam_share { uint64_t block_lo, block_hi; int32_t tid_lo, tid_hi; uint
 int spl_bam_share_get(spl_bam *bam, int k, spl_bam_share *out);
 // A share's decoder is done: `handle` holds its records (share-local first record per reference in ref_first), or failed != 0.
 // When the last share has reported the file is complete -- or, if one failed, everything is dropped and the host threads decode
-// (and count: the shares' flagstat counters go with their reads).  flagstat: the share's 32 counters -- of the records that BEGIN
-// in its own blocks, so that the shares' add up to the file's -- or null.
+// (and count: the shares' totals go with their reads).  totals: of the records that BEGIN in the share's own blocks, so that the
+// shares' add up to the file's.
 int spl_bam_share_done(spl_bam *bam, int k, void *handle, void (*free_fn)(void *), const int64_t *ref_first, const int64_t *ref_n,
-                       const int64_t *ref_max_end, int64_t n_records, const int64_t *dropped, const int64_t *flagstat, int failed);
+                       const int64_t *ref_max_end, const spl_bam_totals &totals, int failed);
 int spl_bam_shares_on_device(spl_bam *bam);
 bool spl_bam_cancelled(const spl_bam *bam);                   // spl_bam_cancel was called: stop at the next window                  // 1: all shares reported and none failed
 // spl_bam_adopt with null arrays = the reads stay on the device; `fetch(handle, ...)` brings malloc'ed host copies when a host-side

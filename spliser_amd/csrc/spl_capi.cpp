@@ -1353,11 +1353,10 @@ static int add_segment_device(spl_ctx *c, spl_dreads *d, DeviceReads *dev, int64
 // that straddles two windows: the bytes from the first block that is not done with to the window's end are copied in front of the
 // next window's buffer (its head room), so that scan and extraction see them in one piece; the blocks are not inflated twice.
 namespace {
-struct ShareOut { // (dropped: by the read filter -- flags, MAPQ; flagstat: the share's counters, spl_flagstat.h, zeros when nobody asked)
+struct ShareOut {
     DeviceReads *reads = nullptr;
-    int64_t n_all = 0, dropped[2] = {0, 0}, flagstat[2 * SPL_FS_CATEGORIES] = {0};
+    spl_bam_totals totals; // (what the share counted, spl_bam.h: filled with `reads`, zeros until then)
     bool to_host = false; bool more_tokens = false;
-    int64_t n_sorted = 0; // (spl_bam_set_any_order: the records the device's sort put in order; 0: they were)
 };
 // What the caller of decode_share does with the share's reads, called by decode_share itself as its LAST act before it gives its
 // buffers, streams and events back -- which takes 10 ms for a large file, and whoever waits for the file's references need not.
@@ -1375,11 +1374,10 @@ extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_ou
     double t_pub = 0;
     const Publish adopt = [&](ShareOut &res) -> int {
         DeviceReads *keep = res.reads;
-        spl_bam_note_sorted(bam, res.n_sorted);
         spl_bam_set_device_reads(bam, keep, free_device_reads);
         spl_bam_set_fetch(bam, fetch_device_reads);
         spl_bam_set_fetch_xs(bam, fetch_device_xs);
-        const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.n_all, res.dropped, res.flagstat);
+        const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.totals);
         if (rc) spl_bam_set_device_reads(bam, nullptr, nullptr);
         if (rc == SPL_OK && on_device_out) *on_device_out = 1;
         t_pub = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
@@ -1411,7 +1409,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     const Publish report = [&](ShareOut &res) -> int { // (a share that is done: reported at once, the last one to report completes the file)
         spl_bam_set_fetch(bam, fetch_device_reads);
         spl_bam_set_fetch_xs(bam, fetch_device_xs);
-        const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.n_all, res.dropped, res.flagstat, 0);
+        const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.totals, 0);
         if (rc2 == SPL_OK && on_device_out) *on_device_out = 1;
         return rc2;
     };
@@ -1419,7 +1417,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     if (rc == SPL_OK && res.more_tokens) { res = ShareOut(); rc = decode_share(c, bam, &sh, res, report, true); }
     if (res.reads) return rc; // (reported: decode_share publishes the reads it has made, whatever publishing returned)
     if (getenv("SPL_BAM_TIMING")) fprintf(stderr, "[spl_bam_decode_device] share %d not done on its device (%s)\n", k, rc ? spl_last_error() : "handed to the host");
-    return spl_bam_share_done(bam, k, nullptr, free_device_reads, nullptr, nullptr, nullptr, res.n_all, res.dropped, nullptr, 1); // (a share the host takes: its counters go, the host decoder counts the file)
+    return spl_bam_share_done(bam, k, nullptr, free_device_reads, nullptr, nullptr, nullptr, res.totals, 1); // (a share the host takes: its counters go, the host decoder counts the file)
 }
 
 namespace {
@@ -1531,10 +1529,10 @@ struct ShareDecode {
     size_t fsize = 0;
     const uint8_t *const image = spl_bam_image(bam, &fsize);
     const int n_ref = spl_bam_n_ref(bam);
-    const spl_bam_filter filter = spl_bam_get_filter(bam); // (the file is claimed: nobody changes it now)
-    const bool want_xs = spl_bam_get_aux_strand(bam);      // (likewise: a fifth array, the spliced reads' XS:A strand)
-    const bool want_stat = spl_bam_get_flagstat(bam);      // (likewise: the scan counts the flagstat categories per block, a kernel adds up the accepted blocks')
-    const bool any_order = !share && spl_bam_get_any_order(bam); // (likewise: the records may come in any order -- sorted behind the last extraction, sort_records; the whole file only)
+    const spl_bam_decode_opts opts = spl_bam_get_opts(bam); // (the file is claimed: nobody changes them now)
+    const bool want_xs = opts.aux_strand;            // (a fifth array, the spliced reads' XS:A strand)
+    const bool want_stat = opts.flagstat;            // (the scan counts the flagstat categories per block, a kernel adds up the accepted blocks')
+    const bool any_order = !share && opts.any_order; // (the records may come in any order -- sorted behind the last extraction, sort_records; the whole file only)
     // ---- everything the streams touch is declared before them
     DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds, d_xs, d_fstat, d_fsum;
     DevBuf d_sortkeys[2], d_sortperm[2], d_sortwork, d_pos2, d_flag2, d_cigoff2, d_cigar2, d_tid2, d_xs2; // (spl_bam_set_any_order: got only when the sort runs)
@@ -2173,7 +2171,7 @@ struct ShareDecode {
         if (b1s > s0) {
             splprof::Scope p("spl_bam_scan_kernel", pipe.b, (double)(blocks[b1s - 1].out + blocks[b1s - 1].out_len - blocks[s0].out));
             HIP_TRY((hipError_t)spl_dev_launch_bam_scan2(stream0, win_end, H, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)(b1s - s0), d_scan.as<spl_bscan>() + s0,
-                                                         more ? 1 : 0, with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags, pipe.b,
+                                                         more ? 1 : 0, with_recs ? d_recs.as<uint16_t>() : nullptr, opts.filter.min_mapq, opts.filter.require_flags, opts.filter.exclude_flags, pipe.b,
                                                          want_stat ? d_fstat.as<uint32_t>() + (size_t)SPL_FS_CATEGORIES * s0 : nullptr));
         }
         HIP_TRY(hipMemcpyAsync(status.get() + b0, d_status.as<uint32_t>() + b0, 4 * (size_t)nb, hipMemcpyDeviceToHost, pipe.b));
@@ -2256,7 +2254,7 @@ struct ShareDecode {
             HIP_TRY((hipError_t)spl_dev_launch_bam_extract(stream0, win_end, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)nd, d_scan.as<spl_bscan>() + s0,
                                                            d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, d_pos.as<int32_t>(), d_flag.as<uint16_t>(),
                                                            d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), d_tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
-                                                           with_recs ? d_recs.as<uint16_t>() : nullptr, filter.min_mapq, filter.require_flags, filter.exclude_flags,
+                                                           with_recs ? d_recs.as<uint16_t>() : nullptr, opts.filter.min_mapq, opts.filter.require_flags, opts.filter.exclude_flags,
                                                            want_xs ? d_xs.as<uint8_t>() : nullptr, pipe.b));
         }
         if (want_stat && b_done > s0) { // the counters of the blocks that are done with, each once: a block that waits for the next window is scanned, and counted, again
@@ -2386,11 +2384,12 @@ struct ShareDecode {
         keep->xs = d_xs.p;
         d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = d_xs.p = nullptr; // (the caller owns them from here)
         res.reads = keep;
-        res.n_all = n_all;
-        res.n_sorted = (int64_t)n_sorted;
-        res.dropped[0] = n_drop_flags;
-        res.dropped[1] = n_drop_mapq;
-        for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.flagstat[q] = (int64_t)fsum[q];
+        res.totals.n_records = n_all;
+        res.totals.n_sorted = (int64_t)n_sorted;
+        res.totals.sorted_on_device = n_sorted ? 1 : 0;
+        res.totals.dropped[0] = n_drop_flags;
+        res.totals.dropped[1] = n_drop_mapq;
+        for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.totals.fstat[q] = (int64_t)fsum[q];
         if (timing) fprintf(stderr, "[spl_bam_decode_device] device %d: blocks %zu..%zu, %.1f MB -> %.1f MB inflated in %zu window%s, %llu placed records of %lld: %.4f s\n", c->device, lo, hi,
                             n_bytes / 1e6, (stream_len - stream_begin) / 1e6, n_win, n_win == 1 ? "" : "s", (unsigned long long)n_rec, (long long)n_all, host_now() - t_begin);
         if (timing && n_sorted)

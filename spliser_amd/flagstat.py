@@ -51,15 +51,15 @@ def flagstat(inBAM, outputPath, devices=(0,), threads=0, gpuDecode=None, minMapQ
     ``process``, and nothing is counted against sites.  A decode that stops after the scan would save the extraction kernel's
     share of the decode (about a tenth of it) at the price of a second path through the window loop; it is not arranged."""
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
-    filt = _process.read_filter(minMapQ, requireFlags, excludeFlags)
-    source = _process.open_and_decode(inBAM, tuple(devices), gpuDecode, threads, filt, flagstat=True, any_order=bool(anyOrder), log=log)
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), flagstat=True, any_order=bool(anyOrder))
+    source = _process.open_and_decode(inBAM, tuple(devices), gpuDecode, threads, options, log=log)
     try:
         counts = source.flagstat()
         if anyOrder:
             _process.log_any_order(source, log)
         if gpuDecode is not False and source.decline_reason():
             log("  (the alignment file was decoded on host threads, not on the GPU: %s)" % source.decline_reason())
-        _process.log_filter(source, filt, log)
+        _process.log_filter(source, options.read_filter, log)
     finally:
         source.close()
     write_and_log(outputPath, counts, log)

@@ -184,8 +184,8 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
         raise ValueError("strandFromXS and isStranded are alternatives: the strand of the tag, or the strand of the read")
     if strandFromXS:
         stranded = native.STRAND_FROM_XS
-    filt = _process.read_filter(minMapQ, requireFlags, excludeFlags)
-    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, filt, aux_strand=bool(strandFromXS), any_order=bool(anyOrder), log=log)   # (on the GPU(s), like `process`)
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), aux_strand=bool(strandFromXS), any_order=bool(anyOrder))
+    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, options, log=log)   # (on the GPU(s), like `process`)
     try:
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
         if anyOrder:
@@ -194,7 +194,7 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
         tables = tables_of_source(source, tuple(devices), chroms, stranded, minAnchor, minIntron, maxIntron, tally=tally)
         if isinstance(source, native.BamFile) and not source.wait_all():
             raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
-        _process.log_filter(source, filt, log)
+        _process.log_filter(source, options.read_filter, log)
         if strandFromXS:
             log_xs_tally(tally, log)
     finally:

@@ -627,22 +627,19 @@ class BamFile(object):
     def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False, flagstat=False,
                  any_order=False):
         self._h = ctypes.c_void_p()
-        self.filter = (int(min_mapq), int(require_flags), int(exclude_flags))
-        self.aux_strand = False
-        self.counts_flagstat = False
-        self.any_order = False
-        filtered = self.filter != (0, 0, 0) or bool(aux_strand) or bool(flagstat) or bool(any_order)   # (all must be there before the decode starts: opened deferred, started below)
-        opener = lib().spl_bam_open_deferred if defer or filtered else (lib().spl_bam_open_stream if stream else lib().spl_bam_open)
+        self.filter, self.aux_strand, self.counts_flagstat, self.any_order = (0, 0, 0), False, False, False
+        # what was asked for must be there before the decode starts: such a file is opened deferred, set up and started below
+        options = [(self.set_filter, (int(min_mapq), int(require_flags), int(exclude_flags)), (0, 0, 0)),
+                   (self.set_aux_strand, (bool(aux_strand),), (False,)),
+                   (self.set_flagstat, (bool(flagstat),), (False,)),
+                   (self.set_any_order, (bool(any_order),), (False,))]
+        asked = [(setter, args) for setter, args, default in options if args != default]
+        opener = lib().spl_bam_open_deferred if defer or asked else (lib().spl_bam_open_stream if stream else lib().spl_bam_open)
         _check(opener(os.fsencode(path), ctypes.c_int(threads), ctypes.byref(self._h)))
-        if filtered:
+        if asked:
             try:
-                self.set_filter(*self.filter)
-                if aux_strand:
-                    self.set_aux_strand(True)
-                if flagstat:
-                    self.set_flagstat(True)
-                if any_order:
-                    self.set_any_order(True)
+                for setter, args in asked:
+                    setter(*args)
                 if not defer:
                     _check(lib().spl_bam_start(self._h))
                     if not stream:

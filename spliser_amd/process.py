@@ -12,6 +12,7 @@ Deliberate deviations from the reference, all on the failure side (SURVEY.md sec
   * ``-g GENE`` with a gene that is not in the annotation is an error here; the reference crashes with
     AttributeError at :283.
 """
+import collections
 import os
 import sys
 import threading
@@ -43,6 +44,14 @@ def read_filter(minMapQ=0, requireFlags=0, excludeFlags=0):
     return f
 
 
+# What a command asks of the decode of its alignment file, one immutable record from the command's keywords down to where the file
+# is opened (``open_alignments``): ``read_filter`` as above; ``aux_strand``: a strand byte per read, the XS:A tag of the spliced ones
+# (``--strandFromXS``); ``flagstat``: the decode counts the flagstat categories (``--flagstat``); ``any_order``: the BAM's records
+# may come in any order, the decoder sorts them (``--anyOrder``).  ``DecodeOptions()`` is what no flag gives.  A new decode switch
+# is one field here (and one in csrc/spl_bam.h's spl_bam_decode_opts, one setter).
+DecodeOptions = collections.namedtuple("DecodeOptions", "read_filter aux_strand flagstat any_order", defaults=(NO_FILTER, False, False, False))
+
+
 def log_filter(source, filt, log, name=None):
     """One line once the decode is complete, when a filter is set: records seen, dropped by flags, dropped by MAPQ."""
     if tuple(filt) == NO_FILTER or not hasattr(source, "filter_counts"):
@@ -55,10 +64,10 @@ def log_filter(source, filt, log, name=None):
 class _SamSource(object):
     """Reads from SAM text (small inputs / fixtures)."""
 
-    def __init__(self, path, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False):
+    def __init__(self, path, options=DecodeOptions()):
         self._counts = [0, 0, 0]
-        self.aux_strand = bool(aux_strand)
-        self.ref_names, self._sets = samio.read_sam(path, min_mapq, require_flags, exclude_flags, counts=self._counts, aux_strand=aux_strand)
+        self.aux_strand = bool(options.aux_strand)
+        self.ref_names, self._sets = samio.read_sam(path, *options.read_filter, counts=self._counts, aux_strand=options.aux_strand)
         self.n_records = self._counts[0]
 
     def reads(self, chrom):
@@ -68,22 +77,21 @@ class _SamSource(object):
         return self._counts[1], self._counts[2]
 
 
-def open_alignments(path, threads=0, stream=False, defer=False, read_filter=NO_FILTER, aux_strand=False, flagstat=False, any_order=False):
+def open_alignments(path, threads=0, stream=False, defer=False, options=DecodeOptions()):
     """BAM (BGZF) through the native decoder; plain SAM text through the Python reader.  ``stream=True``: the BAM decoder
     returns after the header and decodes in the background (``native.BamFile``); ``defer=True``: nothing is decoded until
-    somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``read_filter``: which records either keeps.
-    ``aux_strand``: either also leaves a strand byte per read, the XS:A tag of the spliced ones (``--strandFromXS``).
-    ``flagstat``: the BAM decoder also counts the flagstat categories (``--flagstat``; SAM text has no such counters: an error).
-    ``any_order``: the BAM's records may come in any order (``--anyOrder``; SAM text is read whole and per reference anyway)."""
+    somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``options`` (``DecodeOptions``): what either
+    reader is to do -- SAM text has no flagstat counters (an error) and is read whole and per reference whatever its order."""
     with open(path, "rb") as fh:
         magic = fh.read(4)
-    q, f, F = read_filter
     if magic[:2] == b"\x1f\x8b":
-        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=aux_strand, flagstat=flagstat, any_order=any_order)
-    if flagstat:
+        q, f, F = options.read_filter
+        return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=options.aux_strand,
+                              flagstat=options.flagstat, any_order=options.any_order)
+    if options.flagstat:
         raise native.SpliserNativeError(-5, "%s: flagstat counters are counted while a BAM file is decoded; this is not one" % path)
     if magic[:1] == b"@" or b"\t" in open(path, "rb").readline():
-        return _SamSource(path, q, f, F, aux_strand)
+        return _SamSource(path, options)
     raise native.SpliserNativeError(-5, "%s is neither BGZF/BAM nor SAM text" % path)
 
 
@@ -100,19 +108,16 @@ def wait_deferred_close():
     return time.perf_counter() - t0
 
 
-def open_and_decode(path, devices, gpuDecode=None, threads=0, read_filter=NO_FILTER, aux_strand=False, flagstat=False, any_order=False, log=None):
+def open_and_decode(path, devices, gpuDecode=None, threads=0, options=DecodeOptions(), log=None):
     """The alignment file opened and its decode started: on the GPU(s) -- with several devices every one inflates and extracts
     the stretch of the file that holds its own references (``BamFile.decode_on_devices_async``), and counts them -- or, told so
-    (``gpuDecode=False``), on host threads.  SAM text has one reader.  ``read_filter`` is with the source before any of them starts,
-    and so is ``aux_strand`` (``BamFile.set_aux_strand``: a strand byte per read for ``--strandFromXS``), and ``flagstat``
-    (``BamFile.set_flagstat``: the decoders count the flagstat categories), and ``any_order`` (``BamFile.set_any_order``: the
-    records may come in any order, the decoder sorts them).  A file in any order is decoded whole on the first device -- shares
-    are cut on the order of references --, whichever devices count its chromosomes afterwards."""
-    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, read_filter=read_filter, aux_strand=aux_strand, flagstat=flagstat,
-                             any_order=any_order)
+    (``gpuDecode=False``), on host threads.  SAM text has one reader.  ``options`` (``DecodeOptions``) are with the source before
+    any of them starts.  A file in any order is decoded whole on the first device -- shares are cut on the order of references --,
+    whichever devices count its chromosomes afterwards."""
+    source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, options=options)
     if isinstance(source, native.BamFile) and gpuDecode is not False:
         try:
-            if len(devices) > 1 and any_order:
+            if len(devices) > 1 and options.any_order:
                 if log is not None:
                     log("  (--anyOrder: the alignment file is decoded whole on device %d, not in shares over %d devices)" % (devices[0], len(devices)))
                 source.decode_on_device_async(devices[0])
@@ -536,7 +541,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     ``checkJunctions``) and is not among the kept reads; the output is that of the same call on the pre-filtered file."""
     if outputPath is None:
         raise TypeError("process: outputPath is required")
-    filt = read_filter(minMapQ, requireFlags, excludeFlags)
+    options = DecodeOptions(read_filter(minMapQ, requireFlags, excludeFlags), bool(strandFromXS), bool(flagstat), bool(anyOrder))
     knobs = None
     if inBed is None:
         if checkJunctions:
@@ -553,7 +558,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     # The alignment file does not depend on Steps 0-2: it is decoded on native threads while the site table is built here, and
     # goes on decoding while Step 3 counts the chromosomes that are complete.  An unreadable file is an error here already
     # (block directory and header are read by the opening call).
-    source = open_and_decode(inBAM, devices, gpuDecode, threads, filt, aux_strand=bool(strandFromXS), flagstat=bool(flagstat), any_order=bool(anyOrder), log=log)     # (the decode runs beside Steps 0-2, wherever it runs)
+    source = open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)     # (the decode runs beside Steps 0-2, wherever it runs)
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
@@ -594,7 +599,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
         if isinstance(source, native.BamFile) and gpuDecode is not False and source.decline_reason():
             # (said once, where the user reads it: the host's threads are several times slower than the device on files like this)
             log("  (the alignment file was decoded on host threads, not on the GPU: %s)" % source.decline_reason())
-        log_filter(source, filt, log)
+        log_filter(source, options.read_filter, log)
         if flagstat:      # (the whole file is decoded by now, or will be in a moment: -c / -g do not make the decode any shorter)
             from . import flagstat as _flagstat
             _flagstat.write_and_log(outputPath + _flagstat.SUFFIX, source.flagstat(), log)
@@ -623,7 +628,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
                 t_keep = time.perf_counter()
                 kept = [(name, source.reads(name)) for name in source.ref_names]
                 t_down = time.perf_counter()
-                readstore.save(outputPath + readstore.SUFFIX, inBAM, [(name, rs) for name, rs in kept if rs is not None], read_filter=filt)
+                readstore.save(outputPath + readstore.SUFFIX, inBAM, [(name, rs) for name, rs in kept if rs is not None], read_filter=options.read_filter)
                 timings["keep_reads_s"] = time.perf_counter() - t_keep
                 if os.environ.get("SPL_PROCESS_TIMING"):
                     sys.stderr.write("[process] kept reads: down from the device %.4f s, written %.4f s\n" % (t_down - t_keep, time.perf_counter() - t_down))

@@ -126,7 +126,7 @@ def test_sam_text_follows_the_same_rule(case, seed, filt, stranded, tmp_path):
     c = F.Case(case, seed, filt)
     path = str(tmp_path / "x.sam")
     samio.write_sam(path, c.names, c.lengths, c.x, mapq=c.mapq)
-    src = proc.open_alignments(path, read_filter=c.filt)
+    src = proc.open_alignments(path, options=proc.DecodeOptions(read_filter=c.filt))
     for chrom, sub in c.x_kept:
         F.same_reads(src.reads(chrom), sub, chrom)
     assert src.filter_counts() == (c.by_flags, c.by_mapq) and src.n_records == c.n_all
