@@ -428,6 +428,35 @@ int spl_junction_walk_host(const uint32_t *ops, uint32_t n_ops, int32_t pos, int
                            int capacity, int32_t *left, int32_t *right, uint32_t *anchor_left, uint32_t *anchor_right, uint8_t *passes,
                            int *n_out, int *range_error_out);
 
+/* ---- strandedness of the library (what the pipeline otherwise asks the user for) -----------------------------------------
+ * Replaces a manual step: the reference's README tells the user to open the BAM in IGV, colour the reads by first-in-pair and
+ * compare them with a junction, to learn whether the library is unstranded, "fr" or "rf" -- "a common place to trip up": a wrong
+ * answer does not fail, it gives no beta1 counts, or half the sites without a gene.  The reference has no counterpart.
+ * spl_strand_tally counts, on the device, over the BAM-native arrays of a FUSED read set, how every read's strand compares with
+ * two independent sources of its transcript's strand.  The rule (csrc/spl_strand_rule.h), per read the set holds:
+ *   eligible    (flag & (0x4 | 0x100 | 0x200 | 0x800)) == 0;
+ *   mate class  the branch check_strand takes (:374-406): 0 unpaired (!(flag & 1)), 1 first (flag & 1 and flag & 0x40), 2 second
+ *               (every other paired read);
+ *   fr strand   check_strand's '+' / '-' for "fr"; the "rf" strand is the opposite, so "agrees under rf" is "disagrees under fr";
+ *   tag evidence         the read's strand byte when it is '+' or '-' (spl_bam_set_aux_strand: the aligner's XS:A tag on spliced
+ *                        reads; spl_soa_upload3); a set without the fifth array has none;
+ *   annotation evidence  from a strand cover map of the set's coordinate space: ascending int32 cover_start[n_cover] with uint8
+ *                        cover_code[n_cover], code[k] holding for positions start[k] <= p < start[k + 1] (the last entry to
+ *                        +infinity; 0 below start[0]); 0 = no gene, 1 = only '+' genes, 2 = only '-' genes, 3 = both.  With
+ *                        ref_len = the sum of the lengths of the read's M, D, N, = and X ops and k = the last entry with start[k] <=
+ *                        POS, the read has evidence when ref_len >= 1, POS + ref_len - 1 < start[k + 1] (or k is the last entry)
+ *                        and code[k] is 1 ('+') or 2 ('-'): the whole span, introns included, lies in one stretch covered by
+ *                        genes of one strand only.  Arithmetic in int64.
+ * out14[0] = reads seen, [1] = eligible reads, [2 + 2 m + d] = eligible reads of mate class m with tag evidence, d = 0 when the fr
+ * strand equals the evidence and 1 when it does not, [8 + 2 m + d] = the same for annotation evidence.  out14 is overwritten; the
+ * call synchronises; integer sums, exact and the same for the reads in any order.  The CIGAR is read only when there is a map; a
+ * map of any size is taken (its top level is searched in LDS, the rest where it is); a set without a single read gives fourteen zeros.  SPL_ERR_ARG: a set that is not fused; a set
+ * without strand bytes and n_cover == 0 (nothing to tally); a map that is not strictly ascending.
+ * spl_strand_rule_host: the same rule for one read on the host, added to inout14 (test hook; no file, no GPU). */
+int spl_strand_tally(spl_ctx *ctx, const spl_dreads *dr, int64_t n_cover, const int32_t *cover_start, const uint8_t *cover_code, int64_t *out14);
+int spl_strand_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, uint8_t xs, int64_t n_cover, const int32_t *cover_start,
+                         const uint8_t *cover_code, int64_t *inout14);
+
 /* ---- host helper of Step 1 ---------------------------------------------------------------------------
  * binary_gene_search (SpliSER_v0_1_8.py:118-173) for a batch of query positions against one chromosome's gene list
  * (in list order), probe for probe like the reference.  Strand bytes are '+', '-' or 0 for anything else;

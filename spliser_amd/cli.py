@@ -16,7 +16,12 @@ command does anyway, over the whole file whatever ``-c`` / ``-g`` say, and logs 
 the diffSpliSER target file, for which the reference's README sends the user to ``samtools flagstat``); it changes no result.
 Extra sub-command ``flagstat -B x.bam -o PATH`` writes those lines alone (the filter and engine flags, ``--gpuDecode`` /
 ``--hostDecode``).  Under a read filter the counters are the pre-filtered file's.
-``--anyOrder`` (``process``, ``junctions``, ``flagstat``; changes no result): the BAM may be in any record order, e.g. the aligner's
+``-s auto`` (``process``, ``junctions``) infers the library's strandedness from the BAM itself -- every read's strand tallied on the
+GPU against the XS:A tag of the spliced reads and, with ``-A``, against the strand of the genes it lies in -- and goes on as if the
+verdict had been typed: ``--isStranded -s fr``, ``--isStranded -s rf``, or neither; ``process`` leaves the tally in
+``<outputPath>.strandedness.txt``.  No verdict is an error.  Extra sub-command ``strandedness -B x.bam [-A genes.gff] [-o report.txt]``
+writes that tally and the verdict alone (what the reference's README has the user find out in IGV).
+``--anyOrder`` (``process``, ``junctions``, ``flagstat``, ``strandedness``; changes no result): the BAM may be in any record order, e.g. the aligner's
 own output -- its reads are coordinate-sorted on the GPU after the decode instead of by ``samtools sort`` beforehand.
 """
 import argparse
@@ -61,7 +66,9 @@ def build_parser():
                    help="optional: required with --gene, the max intron size used in aligning the bam file")
     p.add_argument("--isStranded", dest="isStranded", default=False, action="store_true")
     p.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
-                   help='optional: strand specificity of the library, "rf" (first-strand) or "fr" (second-strand)')
+                   help='optional: strand specificity of the library, "rf" (first-strand) or "fr" (second-strand); (this build only) "auto": '
+                        "inferred from the BAM -- " + AUTO_HELP)
+    p.add_argument("--minEvidence", dest="minEvidence", type=int, default=None, help=MIN_EVIDENCE_HELP)
     p.add_argument("--beta2Cryptic", dest="isbeta2Cryptic", default=False, action="store_true",
                    help="optional: weight the utilisation of competing splice sites into SSE (legacy)")
     p.add_argument("--checkJunctions", dest="checkJunctions", default=False, action="store_true",
@@ -125,7 +132,9 @@ def build_parser():
     j.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="path of the BED12 file to write")
     j.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False)
     j.add_argument("--isStranded", dest="isStranded", default=False, action="store_true")
-    j.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False)
+    j.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
+                   help='"fr" or "rf"; "auto": inferred from the BAM\'s XS:A tags -- ' + AUTO_HELP)
+    j.add_argument("--minEvidence", dest="minEvidence", type=int, default=None, help=MIN_EVIDENCE_HELP)
     j.add_argument("--strandFromXS", dest="strandFromXS", default=False, action="store_true",
                    help="unstranded library: the strand column from the reads' XS:A tag (regtools -s XS) instead of '?'; not together "
                         "with --isStranded")
@@ -135,6 +144,19 @@ def build_parser():
     j.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(j)
     _engine_flags(j)
+    s = sub.add_parser("strandedness", help="(this build only) is the library unstranded, fr or rf?  Tallied from the BAM on the GPU: " + AUTO_HELP)
+    s.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    s.add_argument("-A", "--annotationFile", dest="annotationFile", required=False,
+                   help="optional: gff3 or gtf file; reads that lie in a stretch covered by genes of one strand only are held against that strand")
+    s.add_argument("-t", "--annotationType", dest="aType", nargs="?", default="gene", type=str, required=False)
+    s.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False, help="optional: tally one chromosome only")
+    s.add_argument("-o", "--outputPath", dest="outputPath", required=False, default=None, help="optional: path of the tab-separated report to write")
+    s.add_argument("--minEvidence", dest="minEvidence", type=int, default=1000, help=MIN_EVIDENCE_HELP)
+    s.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
+    s.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    s.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _filter_flags(s)
+    _engine_flags(s)
     return parser
 
 
@@ -153,6 +175,11 @@ def _filter_flags(p):
                    help="(this build only; changes results) skip alignments with any of these FLAG bits set (samtools view -F, "
                         "e.g. 0x900: secondary and supplementary) - default: 0")
 
+
+AUTO_HELP = ("every read's strand is held against the XS:A tag of the spliced reads and, with -A, against the strand of the genes it lies in; per "
+             "source >= 90%% of the reads agreeing with fr means fr, <= 10%% rf, 40..60%% unstranded, anything else (or two sources that differ) "
+             "undetermined: a stated policy, not a measurement")
+MIN_EVIDENCE_HELP = "(-s auto, strandedness) reads with evidence a source needs to be heard - default: 1000"
 
 ANY_ORDER_HELP = ("(this build only; changes no result) the BAM may be in any record order, e.g. as the aligner wrote it: its reads are "
                   "coordinate-sorted on the GPU after the decode instead of by samtools sort beforehand")
@@ -183,9 +210,13 @@ def main(argv=None):
         parser.error("--gene requires --annotationFile and --maxIntronSize")
     elif command in ("process", "combine", "combineShallow", "junctions") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
+    if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":
+        parser.error("-s auto and --strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
+    if command in ("process", "junctions", "strandedness") and kwargs.get("minEvidence") is not None and kwargs["minEvidence"] < 0:
+        parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions", "flagstat"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -225,6 +256,9 @@ def main(argv=None):
     elif command == "junctions":
         from .junctions import junctions
         junctions(devices=devices, threads=threads, **kwargs)
+    elif command == "strandedness":
+        from .strandedness import strandedness
+        strandedness(devices=devices, threads=threads, **kwargs)
     elif command == "flagstat":
         from .flagstat import flagstat
         flagstat(devices=devices, threads=threads, **kwargs)

@@ -32,6 +32,8 @@
 #include "spl_pack.h"
 #include "spl_junction_walk.h"
 #include "spl_junction_fused.h"
+#include "spl_strand.h"
+#include "spl_strand_rule.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -3335,6 +3337,61 @@ extern "C" int spl_junctions_stats(const spl_ctx *c, int64_t *table_bytes_out, f
     if (!c) return spl_set_error(SPL_ERR_ARG, "spl_junctions_stats: null context");
     if (table_bytes_out) *table_bytes_out = c->junction_table_bytes;
     if (ms_out) *ms_out = c->junction_ms;
+    return SPL_OK;
+}
+
+// ---- strandedness of the library (spl_strand.hip; the rule is spl_strand_rule.h) ------------------------------------------
+// Read strand against evidence strand over a fused set's arrays: one launch per segment, 14 sums in device memory, down and added.
+extern "C" int spl_strand_tally(spl_ctx *c, const spl_dreads *dr, int64_t n_cover, const int32_t *cover_start, const uint8_t *cover_code, int64_t *out14)
+{
+    if (!c || !dr || !out14 || n_cover < 0 || (n_cover && (!cover_start || !cover_code))) return spl_set_error(SPL_ERR_ARG, "spl_strand_tally: null argument");
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_strand_tally: the read set is not finished (spl_reads_finish)");
+    for (int64_t k = 1; k < n_cover; ++k)
+        if (cover_start[k] <= cover_start[k - 1]) return spl_set_error(SPL_ERR_ARG, "spl_strand_tally: the cover map is not strictly ascending at entry %lld", (long long)k);
+    if (dr->segs.empty()) { // (a set without a read has no arrays to be fused of, and nothing to say)
+        memset(out14, 0, 8 * SPL_STRAND_COUNTERS);
+        return SPL_OK;
+    }
+    if (!(dr->fused && dr->groups.size() == 1))
+        return spl_set_error(SPL_ERR_ARG, "spl_strand_tally needs a fused read set (all of it from one device decode or one spl_soa_upload)");
+    const spl_dreads::Group &g = dr->groups[0];
+    if (!g.src->xs && n_cover == 0)
+        return spl_set_error(SPL_ERR_ARG, "spl_strand_tally: nothing to tally: the reads have no strand bytes (spl_bam_set_aux_strand, spl_soa_upload3) and there is no cover map");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf d_out, d_start, d_code;
+    HIP_TRY(d_out.get(8 * SPL_STRAND_COUNTERS, c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * SPL_STRAND_COUNTERS, c->stream));
+    if (n_cover) {
+        HIP_TRY(d_start.get(4 * (size_t)n_cover, c->stream));
+        HIP_TRY(d_code.get((size_t)n_cover, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_start.p, cover_start, 4 * (size_t)n_cover, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_code.p, cover_code, (size_t)n_cover, hipMemcpyHostToDevice, c->stream));
+    }
+    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+    for (const spl_dreads::Segment &seg : dr->segs) {
+        const spl_layout_seg &ls = g.segs[seg.group_seg];
+        if (ls.n_reads <= 0) continue;
+        // bytes: what the launch must read at least -- FLAG and the strand byte; with a map POS and the CIGAR offsets too, and the ops
+        const double bytes = n_cover ? (double)ls.n_reads * (g.src->xs ? 11.0 : 10.0) + 4.0 * (double)seg.n_ops : 3.0 * (double)ls.n_reads;
+        splprof::Scope prof("spl_strand_tally_kernel", c->stream, bytes);
+        const int rc = spl_dev_launch_strand_tally(&src, (const uint8_t *)g.src->xs, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, n_cover, d_start.as<int32_t>(),
+                                                   d_code.as<uint8_t>(), d_out.as<unsigned long long>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "strand tally kernel launch: %s", hipGetErrorString((hipError_t)rc));
+    }
+    HIP_TRY(hipMemcpyAsync(out14, d_out.p, 8 * SPL_STRAND_COUNTERS, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPL_OK;
+}
+
+// The rule itself for one read, added to inout14: no GPU involved (test hook).
+extern "C" int spl_strand_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, uint8_t xs, int64_t n_cover, const int32_t *cover_start,
+                                    const uint8_t *cover_code, int64_t *inout14)
+{
+    if (!inout14 || (n_ops && !ops) || n_cover < 0 || (n_cover && (!cover_start || !cover_code))) return spl_set_error(SPL_ERR_ARG, "spl_strand_rule_host: null argument");
+    for (int64_t k = 1; k < n_cover; ++k)
+        if (cover_start[k] <= cover_start[k - 1]) return spl_set_error(SPL_ERR_ARG, "spl_strand_rule_host: the cover map is not strictly ascending at entry %lld", (long long)k);
+    const uint32_t bits = spl_strand_read_bits(flag, (int64_t)pos, ops, n_ops, xs, n_cover, cover_start, cover_code);
+    for (int k = 0; k < SPL_STRAND_COUNTERS; ++k) inout14[k] += (bits >> k) & 1u;
     return SPL_OK;
 }
 

@@ -170,23 +170,32 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
 
 
 def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=8, minIntron=70, maxIntron=500000,
-              qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, anyOrder=False):
-    """Writes ``outputPath`` (a BED12 file) and returns the number of junctions.  ``minMapQ`` / ``requireFlags`` / ``excludeFlags``:
+              qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, anyOrder=False,
+              minEvidence=None):
+    """Writes ``outputPath`` (a BED12 file) and returns the number of junctions.  ``strandedType="auto"``: the library's strandedness
+    is inferred first, from the reads' XS:A tags (``strandedness.py``), and the call goes on as if the verdict had been passed.  ``minMapQ`` / ``requireFlags`` / ``excludeFlags``:
     the read filter of ``process`` (samtools view's -q / -f / -F; changes results) -- the junctions of the reads that pass.
     ``strandFromXS``: for an unstranded library, the strand column from the reads' XS:A tag (regtools' ``-s XS``) instead of ``?``;
     an alternative to ``isStranded``.  ``anyOrder`` (changes no result): the BAM may be in any record order -- its reads are
     coordinate-sorted on the GPU after the decode instead of by ``samtools sort`` beforehand (``process``)."""
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
-    stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
-    if isStranded and stranded == 0:
+    auto = strandedType == "auto"
+    if auto and strandFromXS:
+        raise ValueError("strandedType 'auto' and strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
+    stranded = 0 if auto else native.STRANDED_CODE[strandedType] if isStranded else 0
+    if isStranded and stranded == 0 and not auto:
         raise ValueError("strandedType must be 'fr' or 'rf' for a stranded library")
     if strandFromXS and isStranded:
         raise ValueError("strandFromXS and isStranded are alternatives: the strand of the tag, or the strand of the read")
     if strandFromXS:
         stranded = native.STRAND_FROM_XS
-    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), aux_strand=bool(strandFromXS), any_order=bool(anyOrder))
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), aux_strand=bool(strandFromXS or auto), any_order=bool(anyOrder))
     source = _process.open_and_decode(inBAM, tuple(devices), None, threads, options, log=log)   # (on the GPU(s), like `process`)
     try:
+        if auto:     # (the library's strandedness from the reads' XS:A tags -- this command has no annotation --, then as if it had been typed)
+            from . import strandedness as _strandedness
+            isStranded, strandedType = _strandedness.resolve_auto(source, devices, isStranded, None, _strandedness.MIN_EVIDENCE if minEvidence is None else int(minEvidence), log)
+            stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
         if anyOrder:
             _process.log_any_order(source, log)

@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -441,6 +441,17 @@ class DeviceReads(object):
                    count=np.empty(n, np.uint32), anchor_left=np.empty(n, np.uint32), anchor_right=np.empty(n, np.uint32))
         _check(lib().spl_junctions_get(self.ctx._h, _ptr(out["left"]), _ptr(out["right"]), _ptr(out["strand"]), _ptr(out["count"]),
                                        _ptr(out["anchor_left"]), _ptr(out["anchor_right"])))
+        return out
+
+    def strand_tally(self, cover=None):
+        """Read strand against evidence strand over this (finished, fused) set, on the device (``spl_strand_tally``): -> int64[14]
+        -- reads seen, eligible reads, then per mate class (unpaired, first, second) the reads whose fr strand agrees / disagrees
+        with their strand byte (``has_strand`` sets) and, from index 8, with the strand cover map.  ``cover``: ``(start, code)`` in the
+        set's coordinates (``strandedness.cover_map``) or None."""
+        start, code = _cover_arrays(cover)
+        out = np.zeros(14, np.int64)
+        _check(lib().spl_strand_tally(self.ctx._h, self._h, ctypes.c_int64(start.shape[0]), _ptr(start) if start.shape[0] else None,
+                                      _ptr(code) if code.shape[0] else None, _ptr(out)))
         return out
 
     def free(self):
@@ -960,6 +971,29 @@ def aux_strand_host(aux):
     out = ctypes.c_uint8(0)
     _check(lib().spl_bam_aux_strand_host(_ptr(buf) if buf.size else None, ctypes.c_uint32(int(buf.size)), ctypes.byref(out)))
     return out.value
+
+
+def _cover_arrays(cover):
+    if cover is None:
+        return np.zeros(0, np.int32), np.zeros(0, np.uint8)
+    start, code = _arr(cover[0], np.int32), _arr(cover[1], np.uint8)
+    if start.ndim != 1 or start.shape != code.shape:
+        raise ValueError("a cover map is two arrays of one length: start (int32) and code (uint8)")
+    return start, code
+
+
+def strand_rule_host(flag, pos, ops, xs=0, cover=None, counters=None):
+    """The strandedness rule for one read on the host (``spl_strand_rule_host``): adds to ``counters`` (int64[14]; made when None)
+    and returns them."""
+    if counters is None:
+        counters = np.zeros(14, np.int64)
+    assert counters.dtype == np.int64 and counters.shape == (14,) and counters.flags.c_contiguous
+    ops = np.ascontiguousarray(ops, np.uint32)
+    start, code = _cover_arrays(cover)
+    _check(lib().spl_strand_rule_host(ctypes.c_uint32(int(flag)), ctypes.c_int32(int(pos)), _ptr(ops) if ops.shape[0] else None, ctypes.c_uint32(ops.shape[0]),
+                                      ctypes.c_uint8(int(xs)), ctypes.c_int64(start.shape[0]), _ptr(start) if start.shape[0] else None,
+                                      _ptr(code) if code.shape[0] else None, _ptr(counters)))
+    return counters
 
 
 def junction_walk_host(ops, pos, min_anchor=0, min_intron=0, max_intron=0):

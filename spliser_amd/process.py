@@ -498,8 +498,16 @@ def write_tsv(output_path, table, results, is_beta2_cryptic):
 def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
             isStranded=False, strandedType=None, isbeta2Cryptic=False, devices=(0,), threads=0, log=_log, checkJunctions=False,
             gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False,
-            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, flagstat=False, anyOrder=False):
+            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, flagstat=False, anyOrder=False, minEvidence=None):
     """SpliSER_v0_1_8.py:695-720, keyword-compatible with the reference's argparse dests.
+
+    ``strandedType="auto"`` (this build only): the library's strandedness is inferred from the file itself (``strandedness.py``): the
+    decode also leaves the spliced reads' XS:A strand bytes, the whole decode is waited for (as for ``anyOrder``), every read's
+    strand is tallied on the GPU against its tag and -- with ``annotationFile`` -- against the strand of the genes it lies in, and
+    the call goes on exactly as if the caller had passed the verdict: ``isStranded=True`` with ``fr`` or ``rf``, or neither for an
+    unstranded library.  The report is logged and written to ``<outputPath>.strandedness.txt``.  No verdict, or ``unstranded``
+    where ``isStranded`` was passed, is an error (``strandedness.Undetermined``) before anything else is written.  ``minEvidence``:
+    the reads with evidence a source needs to be heard (default 1000).
 
     ``anyOrder`` (this build only; changes no result): the BAM may be in any record order, e.g. as the aligner wrote it -- its reads
     are coordinate-sorted on the GPU after the decode (``spl_bam_set_any_order``) instead of by ``samtools sort`` beforehand.  The
@@ -541,7 +549,10 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     ``checkJunctions``) and is not among the kept reads; the output is that of the same call on the pre-filtered file."""
     if outputPath is None:
         raise TypeError("process: outputPath is required")
-    options = DecodeOptions(read_filter(minMapQ, requireFlags, excludeFlags), bool(strandFromXS), bool(flagstat), bool(anyOrder))
+    auto = strandedType == "auto"
+    if auto and strandFromXS:
+        raise ValueError("strandedType 'auto' and strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
+    options = DecodeOptions(read_filter(minMapQ, requireFlags, excludeFlags), bool(strandFromXS or auto), bool(flagstat), bool(anyOrder))
     knobs = None
     if inBed is None:
         if checkJunctions:
@@ -562,6 +573,18 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
+        bins = None
+        if auto:
+            from . import strandedness as _strandedness
+            t_s = time.perf_counter()
+            if annotationFile is not None:
+                log("\n\nStep 0: Creating Genes from Annotation...")
+                bins = sites.GeneBins.from_annotation(annotationFile, aType, "All", log=log)
+            isStranded, strandedType = _strandedness.resolve_auto(source, devices, isStranded, bins, _strandedness.MIN_EVIDENCE if minEvidence is None else int(minEvidence),
+                                                                  log, outputPath + ".strandedness.txt")
+            if qGene != "All":
+                bins = None       # (a gene query keeps that gene's bins only: Step 0 reads the file for itself)
+            timings["strandedness_s"] = time.perf_counter() - t_s
         rows_of_bam = None
         if inBed is None:
             def rows_of_bam():
@@ -570,7 +593,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
                                       strandFromXS=strandFromXS, log=log)
                 timings["junctions_s"] = time.perf_counter() - t_j
                 return rows
-        table = _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam)
+        table = _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam, bins=bins)
         t1 = time.perf_counter()
         log("\n\nStep 3: Finding Beta reads")
         log("Processing sample 1 out of 1")
@@ -687,13 +710,15 @@ def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType,
     return [(c, tables[c]) for c in chroms if c in tables and len(tables[c]["left"])]
 
 
-def _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam=None):
+def _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam=None, bins=None):
     """Steps 0-2 (SpliSER_v0_1_8.py:700-712).  ``rows_of_bam`` (no junction file): called after Step 0 -> [(chrom, junction
-    table)], see ``_junction_rows``."""
+    table)], see ``_junction_rows``.  ``bins``: Step 0's genes, where the caller has read the annotation already (``-s auto``)."""
     log("Processing")
     log("Stranded Analysis {}".format(strandedType) if isStranded else "Unstranded Analysis")
-    bins = sites.GeneBins()
-    if annotationFile is not None:
+    have_bins = bins is not None
+    if not have_bins:
+        bins = sites.GeneBins()
+    if annotationFile is not None and not have_bins:
         log("\n\nStep 0: Creating Genes from Annotation...")
         bins = sites.GeneBins.from_annotation(annotationFile, aType, qGene, log=log)
     log("\n\nPreparing Splice Site Arrays")
