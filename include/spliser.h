@@ -380,6 +380,22 @@ void spl_bam_cancel(spl_bam *bam);
  * words (not sorted by reference, a CIGAR parked in a CG tag, a block that did not inflate, not enough device memory, ...).  The
  * pointer is good while the file is open.  (The reference has no counterpart: samtools reads whatever it is given, :422.) */
 const char *spl_bam_decline_reason(spl_bam *bam);
+/* SAM TEXT behind the same object, as the aligner writes it (HISAT2 always, STAR by default): no `samtools view -b` in front.
+ * spl_sam_open maps the file, reads the header on the host (@SQ SN / LN, in order: the reference ids) and starts nothing: a
+ * deferred file, to which the four spl_bam_set_* setters, spl_bam_decode_device and every consumer apply unchanged (wait_ref /
+ * wait_all, spl_reads_add_bam, spl_bam_reads, spl_bam_aux_strand, spl_bam_flagstat, spl_bam_filter_counts, spl_bam_n_records,
+ * spl_bam_any_order_sorted).  spl_bam_decode_device parses the text on the GPU: line starts by a wave per 16 KiB, then a lane per
+ * line, windows of SPL_SAM_WINDOW_BYTES (default 256 MiB) going up while the one before is parsed; without that call, or where
+ * the device cannot (memory, a HIP error), one host thread parses it.  Either way by ONE strict rule (csrc/spl_sam_line.h), and
+ * always as spl_bam_set_any_order: lines in any order, sorted on the GPU when reference ids or POS ever go down.  A file with a
+ * line the rule does not take is declined as a whole: the decode ends with SPL_ERR_FORMAT, spl_bam_decline_reason says
+ * "line N <why>" (1-based, header lines counted), and the caller reads the file by other means (process.py: samio.read_sam, as
+ * before).  A line longer than SPL_SAM_WINDOW_BYTES, its newline counted, is such a line for both decoders.  SPL_ERR_FORMAT from
+ * spl_sam_open itself: gzip/BGZF data, no @SQ line, an @SQ line without SN and LN, a repeated name, a line that begins "@SQ" and
+ * is no @SQ line, a carriage return in the header.  n_threads is kept and unused: the host parser is one thread.  spl_bam_share_plan, spl_bam_sample and spl_bam_compression_ratio are SPL_ERR_ARG on such a file; spl_bam_open* keep
+ * refusing text.  Not read: gzip'd or BGZF-compressed SAM, CRAM, a pipe; no decode in shares.  spl_bam_is_text: 1 for such a file. */
+int spl_sam_open(const char *path, int n_threads, spl_bam **out);
+int spl_bam_is_text(const spl_bam *bam);
 void spl_bam_close(spl_bam *bam);
 int spl_bam_n_ref(const spl_bam *bam);
 const char *spl_bam_ref_name(const spl_bam *bam, int tid);

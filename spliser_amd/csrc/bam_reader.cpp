@@ -38,6 +38,7 @@
 #include "spl_bam.h"
 #include "spl_bam_aux.h"
 #include "spl_flagstat.h"
+#include "spl_sam_line.h"
 static_assert(SPL_BAM_N_FSTAT == 2 * SPL_FS_CATEGORIES, "spl_bam_totals::fstat holds every flagstat counter");
 #include "spl_error.h"
 
@@ -513,8 +514,18 @@ struct spl_bam {
     uint64_t header_bytes = 0; // magic, text and reference dictionary: the first record starts here in the inflated stream
     std::string path;
     std::string decline_reason; // why the device decoder handed the file to the host threads, if it did
+    // ---- SAM text (spl_sam_open): where the alignment lines begin, the header lines in front of them, the names' look-up table
+    bool is_text = false;
+    uint64_t text_begin = 0, header_lines = 0;
+    std::vector<uint32_t> sam_slots, sam_name_off;
+    std::vector<uint8_t> sam_blob;
     ~spl_bam();
 };
+
+static void sam_host_worker(spl_bam *bam); // (SAM text's decode on the host, at the end of this file)
+namespace { void decode_worker(spl_bam *bam); }
+// (call with bam->mu held) the file's decode on the host, on the file's own thread
+static void start_worker(spl_bam *bam) { bam->worker = std::thread(bam->is_text ? sam_host_worker : decode_worker, bam); }
 
 spl_bam::~spl_bam()
 {
@@ -1334,7 +1345,7 @@ int spl_bam_start_host(spl_bam *bam)
 {
     if (!bam) return spl_set_error(SPL_ERR_ARG, "spl_bam_start_host: null argument");
     std::lock_guard<std::mutex> lock(bam->mu);
-    if (bam->claim == 0 && !cancelled_locked(bam)) { bam->claim = 2; bam->worker = std::thread(decode_worker, bam); }
+    if (bam->claim == 0 && !cancelled_locked(bam)) { bam->claim = 2; start_worker(bam); }
     bam->cv.notify_all(); // (spl_bam_wait_device)
     return SPL_OK;
 }
@@ -1374,7 +1385,7 @@ extern "C" const char *spl_bam_decline_reason(spl_bam *bam)
 int spl_bam_device_gives_up(spl_bam *bam)
 {
     std::lock_guard<std::mutex> lock(bam->mu);
-    if (bam->claim == 1 && !cancelled_locked(bam)) { bam->claim = 2; bam->worker = std::thread(decode_worker, bam); }
+    if (bam->claim == 1 && !cancelled_locked(bam)) { bam->claim = 2; start_worker(bam); }
     bam->cv.notify_all(); // (spl_bam_wait_device)
     return SPL_OK;
 }
@@ -1433,6 +1444,7 @@ extern "C" int spl_bam_start(spl_bam *bam)
 extern "C" int spl_bam_compression_ratio(spl_bam *bam, double *ratio_out)
 {
     if (!bam || !ratio_out) return spl_set_error(SPL_ERR_ARG, "spl_bam_compression_ratio: null argument");
+    if (bam->is_text) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_compression_ratio: SAM text has no BGZF blocks (text)", bam->path.c_str());
     *ratio_out = 0.0;
     {
         std::lock_guard<std::mutex> lock(bam->mu);
@@ -1630,6 +1642,7 @@ bool spl_bam_sample_density(spl_bam *bam, size_t b_lo, size_t b_hi, uint64_t *n_
 extern "C" int spl_bam_sample(spl_bam *bam, int64_t *out3)
 {
     if (!bam || !out3) return spl_set_error(SPL_ERR_ARG, "spl_bam_sample: null argument");
+    if (bam->is_text) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_sample: SAM text has no BGZF blocks (text)", bam->path.c_str());
     const int rc = spl_bam_walk_all(bam);
     if (rc) return rc;
     uint64_t n_rec = 0, n_ops = 0, n_bytes = 0;
@@ -1642,6 +1655,7 @@ extern "C" int spl_bam_sample(spl_bam *bam, int64_t *out3)
 extern "C" int spl_bam_share_plan(spl_bam *bam, int n_shares, int *n_out)
 {
     if (!bam || n_shares < 1) return spl_set_error(SPL_ERR_ARG, "spl_bam_share_plan: bad argument");
+    if (bam->is_text) return spl_set_error(SPL_ERR_ARG, "%s: spl_bam_share_plan: SAM text has no BGZF blocks (text)", bam->path.c_str());
     {
         std::lock_guard<std::mutex> lock(bam->mu);
         if (!bam->shares.empty()) { if (n_out) *n_out = (int)bam->shares.size(); return SPL_OK; }
@@ -2355,4 +2369,259 @@ extern "C" int spl_bam_write(const char *path, int n_ref, const char *const *ref
                              const spl_reads *per_ref, int level, int n_threads)
 {
     return spl_bam_write2(path, n_ref, ref_names, ref_lengths, per_ref, level, n_threads, 0);
+}
+
+// ---- SAM text behind the same object ---------------------------------------------------------------------------------------
+// spl_sam_open maps the file and reads the header here; the alignment lines are parsed by the device (spl_capi.cpp: SamDecode)
+// or, where it cannot (no device memory, a HIP error) or nobody asked it to, by sam_host_worker below -- the same rule, line by
+// line (spl_sam_line.h), the same arrays and counters.  Replaces `samtools view -b` in front of the BAM decoder.
+extern "C" int spl_bam_is_text(const spl_bam *bam) { return bam && bam->is_text ? 1 : 0; }
+
+bool spl_bam_text(const spl_bam *bam, uint64_t *begin_out, uint64_t *header_lines_out, spl_sam_names *names_out, size_t *blob_bytes_out)
+{
+    if (!bam->is_text) return false;
+    if (begin_out) *begin_out = bam->text_begin;
+    if (header_lines_out) *header_lines_out = bam->header_lines;
+    if (names_out) *names_out = spl_sam_names{bam->sam_slots.data(), bam->sam_name_off.data(), bam->sam_blob.data(), (uint32_t)bam->sam_slots.size(), bam->n_refs};
+    if (blob_bytes_out) *blob_bytes_out = bam->sam_blob.size();
+    return true;
+}
+
+size_t spl_sam_window_bytes()
+{
+    size_t bytes = (size_t)256 << 20;
+    if (const char *e = getenv("SPL_SAM_WINDOW_BYTES")) { const long long v = atoll(e); if (v >= 64) bytes = (size_t)std::min<long long>(v, 1ll << 30); }
+    return bytes;
+}
+
+void spl_sam_fail(spl_bam *bam, uint64_t line_no, uint32_t reason)
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (bam->done) return;
+    if (bam->decline_reason.empty()) bam->decline_reason = "line " + std::to_string(line_no) + " " + spl_sam_reason_text(reason);
+    bam->err_code = SPL_ERR_FORMAT;
+    bam->error = bam->path + ": " + bam->decline_reason + " (not SAM text as spl_sam_open's decoders read it: csrc/spl_sam_line.h)";
+    bam->claim = 2;
+    bam->complete_upto = bam->n_refs;
+    bam->done = true;
+    bam->cv.notify_all();
+}
+
+extern "C" int spl_sam_open(const char *path, int n_threads, spl_bam **out)
+{
+    if (!path || !out) return spl_set_error(SPL_ERR_ARG, "spl_sam_open: null argument");
+    *out = nullptr;
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return spl_set_error(SPL_ERR_IO, "cannot open %s", path);
+    struct FdGuard { int fd; ~FdGuard() { if (fd >= 0) close(fd); } } fd_guard{fd};
+    struct stat st;
+    if (fstat(fd, &st) != 0 || st.st_size <= 0) return spl_set_error(SPL_ERR_IO, "cannot stat %s (or empty file)", path);
+    const size_t fsize = (size_t)st.st_size;
+    void *map = mmap(nullptr, fsize, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (map == MAP_FAILED) return spl_set_error(SPL_ERR_IO, "mmap failed for %s", path);
+    madvise(map, fsize, MADV_SEQUENTIAL);
+    spl_bam *bam = new (std::nothrow) spl_bam();
+    if (!bam) { munmap(map, fsize); return spl_set_error(SPL_ERR_NOMEM, "out of host memory"); }
+    bam->map = map; // (the object owns the mapping and the file from here: `delete bam` gives both back)
+    bam->fsize = fsize;
+    bam->path = path;
+    bam->fd = fd_guard.fd;
+    fd_guard.fd = -1;
+    bam->is_text = true;
+    bam->opts.any_order = true; // (the Python reader takes the lines in any order: so do this file's decoders)
+    if (n_threads <= 0) n_threads = (int)std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
+    bam->n_threads = n_threads;
+    const uint8_t *file = (const uint8_t *)map;
+    auto refuse = [&](const char *why) { delete bam; return spl_set_error(SPL_ERR_FORMAT, "%s: %s", path, why); };
+    if (fsize >= 2 && file[0] == 0x1f && file[1] == 0x8b) return refuse("gzip or BGZF data, not SAM text (spl_bam_open reads BAM; compressed SAM is not read)");
+    // the header: every line that begins with '@', at the top; @SQ lines give the references, in order
+    size_t at = 0;
+    while (at < fsize && file[at] == '@') {
+        const uint8_t *nl = (const uint8_t *)memchr(file + at, '\n', fsize - at);
+        const size_t stop = nl ? (size_t)(nl - file) : fsize;
+        if (memchr(file + at, '\r', stop - at)) return refuse("a carriage return in the header");
+        // (read_sam takes SN: fields from every line that begins "@SQ", whatever follows: such a line that is not an @SQ line is its business)
+        if (stop - at >= 3 && memcmp(file + at, "@SQ", 3) == 0 && (stop - at == 3 || file[at + 3] != '\t')) return refuse("a header line that begins @SQ and is no @SQ line");
+        if (stop - at >= 4 && memcmp(file + at, "@SQ\t", 4) == 0) {
+            std::string name;
+            int64_t len = -1;
+            int n_sn = 0;
+            for (size_t f = at + 4; f <= stop;) {
+                const uint8_t *tab = (const uint8_t *)memchr(file + f, '\t', stop - f);
+                const size_t g = tab ? (size_t)(tab - file) : stop;
+                if (g - f >= 3 && memcmp(file + f, "SN:", 3) == 0) { name.assign((const char *)file + f + 3, g - f - 3); ++n_sn; }
+                if (g - f >= 3 && memcmp(file + f, "LN:", 3) == 0) {
+                    uint64_t v = 0;
+                    if (spl_sam_number(file + f + 3, file + g, 10, 2147483647u, &v)) len = (int64_t)v;
+                }
+                f = g + 1;
+            }
+            if (n_sn != 1 || name.empty() || len < 0) return refuse("an @SQ line without one SN and an LN in digits");
+            bam->ref_names.push_back(name);
+            bam->ref_lengths.push_back(len);
+        }
+        bam->header_lines++;
+        at = nl ? stop + 1 : fsize;
+    }
+    if (bam->ref_names.empty()) return refuse("SAM text without @SQ lines (or not SAM text)");
+    const size_t n_ref = bam->ref_names.size();
+    bam->text_begin = at;
+    bam->n_refs = (int)n_ref;
+    bam->refs_storage = std::vector<RefFinal>(n_ref);
+    bam->assembled.assign(n_ref, 0);
+    bam->parts.assign(n_ref, std::vector<PendingPart *>());
+    bam->ref_max_end.assign(n_ref, 0);
+    bam->ref_reads.assign(n_ref, 0);
+    // the names' look-up table (spl_sam_line.h: spl_sam_names)
+    size_t n_slots = 4;
+    while (n_slots < 2 * n_ref) n_slots *= 2;
+    bam->sam_slots.assign(n_slots, 0);
+    bam->sam_name_off.assign(n_ref + 1, 0);
+    for (size_t t = 0; t < n_ref; ++t) {
+        const std::string &nm = bam->ref_names[t];
+        bam->sam_blob.insert(bam->sam_blob.end(), nm.begin(), nm.end());
+        if (bam->sam_blob.size() > 0xfffffff0ull) return refuse("reference names beyond 2^32 bytes");
+        bam->sam_name_off[t + 1] = (uint32_t)bam->sam_blob.size();
+    }
+    if (bam->sam_blob.empty()) bam->sam_blob.push_back(0);
+    const spl_sam_names table = {bam->sam_slots.data(), bam->sam_name_off.data(), bam->sam_blob.data(), (uint32_t)n_slots, (int32_t)n_ref};
+    for (size_t t = 0; t < n_ref; ++t) {
+        const uint8_t *p = bam->sam_blob.data() + bam->sam_name_off[t], *e = bam->sam_blob.data() + bam->sam_name_off[t + 1];
+        if (spl_sam_lookup(table, p, e, -1) >= 0) return refuse("two @SQ lines with the same SN");
+        uint32_t s = spl_sam_hash(p, e) & (uint32_t)(n_slots - 1);
+        while (bam->sam_slots[s]) s = (s + 1u) & (uint32_t)(n_slots - 1);
+        bam->sam_slots[s] = (uint32_t)t + 1u;
+    }
+    *out = bam;
+    return SPL_OK;
+}
+
+// The host parser: the alignment lines one by one through the rule, the kept ones' fields into vectors in file order; then every
+// reference's reads -- in file order, or, when reference ids or POS ever went down, by a stable sort on (id, POS): what the
+// device's sort leaves -- into one part of exact-size arrays, as order_parts makes them.  One thread: this is what runs where
+// the device cannot, and what makes the rule testable without one.
+static void sam_host_worker(spl_bam *bam)
+{
+    const uint8_t *file = (const uint8_t *)bam->map;
+    const uint8_t *p = file + bam->text_begin, *const end = file + bam->fsize;
+    const spl_bam_decode_opts opts = bam->opts;
+    const spl_sam_names names = {bam->sam_slots.data(), bam->sam_name_off.data(), bam->sam_blob.data(), (uint32_t)bam->sam_slots.size(), bam->n_refs};
+    const size_t n_ref = (size_t)bam->n_refs;
+    std::vector<int32_t> tid_v, pos_v;
+    std::vector<uint16_t> flag_v;
+    std::vector<uint8_t> xs_v;
+    std::vector<uint64_t> off_v(1, 0);
+    std::vector<uint32_t> cigar_v;
+    std::vector<int64_t> end_v;
+    spl_bam_totals totals;
+    uint64_t line_no = bam->header_lines;
+    const size_t max_line = spl_sam_window_bytes();
+    int32_t last_tid = -1, last_pos = 0;
+    bool unordered = false;
+    auto fail = [&](const std::string &why, int code) {
+        std::lock_guard<std::mutex> lock(bam->mu);
+        bam->err_code = code;
+        bam->error = bam->path + ": " + why;
+        bam->complete_upto = bam->n_refs;
+        bam->done = true;
+        bam->cv.notify_all();
+    };
+    try {
+        while (p < end) {
+            const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
+            const uint8_t *stop = nl ? nl : end;
+            ++line_no;
+            if ((line_no & 0xffffu) == 0 && bam->cancel.load(std::memory_order_acquire)) { fail("closed before it was decoded", SPL_ERR_IO); return; }
+            if ((size_t)(stop - p) + (nl ? 1u : 0u) > max_line) { spl_sam_fail(bam, line_no, SPL_SAM_LONG_LINE); return; } // (the device's windows hold no such line)
+            spl_sam_line ln;
+            spl_sam_parse_line(p, stop, names, last_tid, opts.filter, opts.aux_strand, &ln);
+            if (ln.reason != SPL_SAM_OK) { spl_sam_fail(bam, line_no, ln.reason); return; }
+            totals.n_records++;
+            if (opts.flagstat && ln.verdict == SPL_BAM_KEPT) spl_flagstat_add(totals.fstat, ln.flag, ln.tid, ln.next_tid, ln.mapq);
+            if (ln.placed && ln.verdict != SPL_BAM_KEPT) totals.dropped[ln.verdict - 1]++;
+            else if (ln.placed) {
+                if (ln.tid < last_tid || (ln.tid == last_tid && ln.pos < last_pos)) unordered = true;
+                last_tid = ln.tid;
+                last_pos = ln.pos;
+                const size_t at = cigar_v.size();
+                if (at + ln.n_ops > 0xfffffff0ull || tid_v.size() >= 0xfffffff0ull) { spl_sam_fail(bam, line_no, SPL_SAM_TOO_MANY); return; }
+                cigar_v.resize(at + ln.n_ops);
+                uint32_t n = 0;
+                int64_t ref_len = 0;
+                bool has_n = false;
+                (void)spl_sam_cigar(p + ln.cigar_at, p + ln.cigar_at + ln.cigar_len, cigar_v.data() + at, &n, &ref_len, &has_n);
+                tid_v.push_back(ln.tid);
+                pos_v.push_back(ln.pos);
+                flag_v.push_back((uint16_t)ln.flag);
+                xs_v.push_back(ln.xs);
+                end_v.push_back(ln.end);
+                off_v.push_back(cigar_v.size());
+            }
+            p = nl ? nl + 1 : end;
+        }
+        const size_t n = tid_v.size();
+        std::vector<uint32_t> order(n);
+        for (size_t k = 0; k < n; ++k) order[k] = (uint32_t)k;
+        if (unordered)
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return tid_v[a] != tid_v[b] ? tid_v[a] < tid_v[b] : pos_v[a] < pos_v[b]; });
+        // (in order, a reference's reads are one run of the file; sorted, one run of `order`)
+        std::vector<PendingPart *> made(n_ref, nullptr);
+        std::vector<void *> slabs;
+        bool nomem = false;
+        for (size_t k = 0; k < n && !nomem;) {
+            const int32_t tid = tid_v[order[k]];
+            size_t k1 = k, g = 0;
+            while (k1 < n && tid_v[order[k1]] == tid) { g += (size_t)(off_v[order[k1] + 1] - off_v[order[k1]]); ++k1; }
+            const size_t m = k1 - k;
+            int32_t *pos = (int32_t *)big_alloc(sizeof(int32_t) * m);
+            uint16_t *flag = (uint16_t *)big_alloc(sizeof(uint16_t) * m);
+            uint32_t *cig_off = (uint32_t *)big_alloc(sizeof(uint32_t) * (m + 1));
+            uint32_t *cigar = (uint32_t *)big_alloc(sizeof(uint32_t) * std::max<size_t>(g, 1));
+            uint8_t *xs = opts.aux_strand ? (uint8_t *)big_alloc(m) : nullptr;
+            for (void *a : {(void *)pos, (void *)flag, (void *)cig_off, (void *)cigar, (void *)xs}) if (a) slabs.push_back(a);
+            if (!pos || !flag || !cig_off || !cigar || (opts.aux_strand && !xs)) { nomem = true; break; }
+            PendingPart *pp = new PendingPart();
+            made[(size_t)tid] = pp;
+            pp->tid = tid;
+            RefReads &r = pp->reads;
+            r.pos = pos; r.flag = flag; r.cig_off = cig_off; r.cigar = cigar; r.xs = xs; r.n = m; r.n_ops = g;
+            uint32_t o = 0;
+            cig_off[0] = 0;
+            for (size_t j = 0; j < m; ++j) {
+                const size_t i = order[k + j];
+                pos[j] = pos_v[i];
+                flag[j] = flag_v[i];
+                if (xs) xs[j] = xs_v[i];
+                const size_t a = (size_t)off_v[i], b = (size_t)off_v[i + 1];
+                if (b > a) memcpy(cigar + o, cigar_v.data() + a, sizeof(uint32_t) * (b - a));
+                o += (uint32_t)(b - a);
+                cig_off[j + 1] = o;
+                if (end_v[i] > r.max_end) r.max_end = end_v[i];
+            }
+            k = k1;
+        }
+        if (nomem) {
+            for (PendingPart *pp : made) delete pp;
+            for (void *a : slabs) free(a);
+            fail("out of host memory", SPL_ERR_NOMEM);
+            return;
+        }
+        totals.n_sorted = unordered ? (int64_t)n : 0;
+        totals.sorted_on_device = 0;
+        std::lock_guard<std::mutex> lock(bam->mu);
+        for (void *a : slabs) bam->slabs.push_back(a);
+        for (size_t t = 0; t < n_ref; ++t) {
+            if (!made[t]) continue;
+            bam->parts[t].push_back(made[t]);
+            bam->ref_reads[t] = (int64_t)made[t]->reads.n;
+            bam->ref_max_end[t] = made[t]->reads.max_end;
+        }
+        bam->totals = totals;
+        bam->max_tid_seen = bam->n_refs - 1;
+        bam->complete_upto = bam->n_refs;
+        bam->done = true;
+        bam->cv.notify_all();
+    } catch (const std::bad_alloc &) {
+        fail("out of host memory", SPL_ERR_NOMEM);
+    }
 }

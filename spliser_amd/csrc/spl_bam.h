@@ -113,4 +113,18 @@ void spl_bam_note_decline(spl_bam *bam, const char *why); // why the device deco
 int spl_bam_device_gives_up(spl_bam *bam);                 // ... and hands it to the host threads after all
 void spl_bam_linger(spl_bam *bam, double seconds);       // a decoder with only its clearing up left: until spl_bam_cancel, `seconds` at most
 
+// ---- SAM text behind the same object (spl_sam_open; the line's rule: spl_sam_line.h) -------------------------------------
+// false: the file is BGZF/BAM.  true: the alignment lines are the mapping's bytes [*begin_out, file size) (spl_bam_image), in front of
+// them `*header_lines_out` header lines; names_out: the header's reference names as the rule looks them up (host memory, the file's),
+// blob_bytes_out: the bytes of all names.  Null outputs are skipped.
+struct spl_sam_names;
+bool spl_bam_text(const spl_bam *bam, uint64_t *begin_out, uint64_t *header_lines_out, spl_sam_names *names_out, size_t *blob_bytes_out);
+// The rule declines the file at line `line_no` (1-based, header lines counted) for `reason` (SPL_SAM_*): the decode ends with
+// SPL_ERR_FORMAT and spl_bam_decline_reason says "line N <reason>" -- whoever opened the file reads it as it was read before this
+// decoder existed.  For the decoder that has the file (the device's, claim 1, or the host parser).
+void spl_sam_fail(spl_bam *bam, uint64_t line_no, uint32_t reason);
+// SPL_SAM_WINDOW_BYTES (64 .. 2^30; default 256 MiB): the bytes of text the device parses at a time, and for BOTH decoders the
+// longest line, its newline counted, that the rule takes (SPL_SAM_LONG_LINE)
+size_t spl_sam_window_bytes();
+
 #endif

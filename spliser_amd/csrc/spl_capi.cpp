@@ -25,6 +25,8 @@
 #include "spl_bam.h"
 #include "spl_inflate.h"
 #include "spl_sort.h"
+#include "spl_sam.h"
+#include "spl_sam_line.h"
 #include "spl_flagstat.h"
 #include "spl_devpack.h"
 #include "spl_device.h"
@@ -1365,6 +1367,7 @@ struct ShareOut {
 typedef std::function<int(ShareOut &)> Publish;
 }
 static int decode_share(spl_ctx *c, spl_bam *bam, const spl_bam_share *share, ShareOut &res, const Publish &publish, bool all_token_room = false);
+static int decode_text(spl_ctx *c, spl_bam *bam, ShareOut &res, const Publish &publish); // (SAM text, spl_sam_open: behind decode_share below)
 
 extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_out)
 {
@@ -1385,7 +1388,7 @@ extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_ou
         t_pub = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
         return rc;
     };
-    int rc = decode_share(c, bam, nullptr, res, adopt);
+    int rc = spl_bam_text(bam, nullptr, nullptr, nullptr, nullptr) ? decode_text(c, bam, res, adopt) : decode_share(c, bam, nullptr, res, adopt);
     if (rc == SPL_OK && res.more_tokens) { res = ShareOut(); rc = decode_share(c, bam, nullptr, res, adopt, true); }
     // whatever went wrong on the way (device memory, a HIP error, a file this path does not take): the file must not be left
     // without a decoder -- the host threads take it (a no-op when the arrays were adopted); spl_last_error keeps the reason
@@ -1423,6 +1426,57 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
 }
 
 namespace {
+// The sort of the extracted arrays by (reference id, POS, place in the file), for both decoders (ShareDecode::sort_records, SamDecode):
+// keys (id << 32 | POS) with the record's index as payload through the passes of the stable radix sort (spl_sort.hip), least
+// significant digit first, over the digits that can differ only -- POS is at most `top`, the largest end any read has, the id
+// below n_ref; then the arrays gathered by the permutation, the op counts in their new order scanned into the new cig_off, the
+// CIGAR words copied run by run.  The sorted arrays take the unsorted ones' places (the DevBuf pointers are swapped); the scratch
+// -- two key and two payload buffers, the arrays a second time -- stays here until release().
+struct RecordSort {
+    DevBuf keys[2], perm[2], work, pos2, flag2, cigoff2, cigar2, tid2, xs2;
+    uint32_t passes = 0, pos_bits = 0, tid_bits = 0, shifts[8] = {0};
+    void plan(unsigned long long top, int n_ref)
+    {
+        while (pos_bits < 31u && (top >> pos_bits)) ++pos_bits; // (POS is kept 1-based in 31 bits, and no read ends in front of its POS)
+        while (tid_bits < 31u && ((uint64_t)std::max(n_ref - 1, 1) >> tid_bits)) ++tid_bits;
+        passes = spl_dev_sort_passes(pos_bits, tid_bits, shifts);
+    }
+    static double bytes_needed(uint64_t n_rec, uint64_t n_ops, bool want_xs)
+    {
+        return 24.0 * (double)n_rec + (double)spl_dev_sort_work_bytes(n_rec) + (want_xs ? 15.0 : 14.0) * (double)n_rec + 4.0 * (double)n_ops + 4096.0;
+    }
+    // (after plan) n_ops < 2^32 and n_rec <= 0xfffffff0 are the caller's to have seen; waits for the stream before it swaps
+    int run(hipStream_t st, uint64_t n_rec, uint64_t n_ops, bool want_xs, DevBuf &d_pos, DevBuf &d_flag, DevBuf &d_cigoff, DevBuf &d_cigar, DevBuf &d_tid, DevBuf &d_xs)
+    {
+        const size_t n = (size_t)n_rec;
+        for (int k = 0; k < 2; ++k) { HIP_TRY(keys[k].get(8 * n, st)); HIP_TRY(perm[k].get(4 * n, st)); }
+        HIP_TRY(work.get(spl_dev_sort_work_bytes(n_rec), st));
+        HIP_TRY(pos2.get(4 * n, st)); HIP_TRY(flag2.get(2 * n, st)); HIP_TRY(cigoff2.get(4 * (n + 1), st));
+        HIP_TRY(cigar2.get(4 * (size_t)n_ops, st)); HIP_TRY(tid2.get(4 * n, st));
+        if (want_xs) HIP_TRY(xs2.get(n, st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_make_keys(d_tid.as<int32_t>(), d_pos.as<int32_t>(), n_rec, keys[0].as<uint64_t>(), st));
+        int cur = 0;
+        for (uint32_t k = 0; k < passes; ++k, cur ^= 1)
+            HIP_TRY((hipError_t)spl_dev_launch_sort_pass(keys[cur].as<uint64_t>(), k ? perm[cur].as<uint32_t>() : nullptr, n_rec, shifts[k], keys[cur ^ 1].as<uint64_t>(),
+                                                         perm[cur ^ 1].as<uint32_t>(), work.p, st));
+        const uint32_t *order = perm[cur].as<uint32_t>();
+        HIP_TRY((hipError_t)spl_dev_launch_sort_gather(order, keys[cur].as<uint64_t>(), n_rec, d_pos.as<int32_t>(), d_flag.as<uint16_t>(), want_xs ? d_xs.as<uint8_t>() : nullptr,
+                                                       d_cigoff.as<uint32_t>(), pos2.as<int32_t>(), flag2.as<uint16_t>(), want_xs ? xs2.as<uint8_t>() : nullptr, tid2.as<int32_t>(),
+                                                       cigoff2.as<uint32_t>(), st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(cigoff2.as<uint32_t>() + 1, n_rec, work.p, st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_cigar(order, n_rec, d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), cigoff2.as<uint32_t>(), cigar2.as<uint32_t>(), st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::swap(d_pos.p, pos2.p); std::swap(d_flag.p, flag2.p); std::swap(d_cigoff.p, cigoff2.p); std::swap(d_cigar.p, cigar2.p); std::swap(d_tid.p, tid2.p);
+        std::swap(d_xs.p, xs2.p);
+        return SPL_OK;
+    }
+    void release()
+    {
+        for (int k = 0; k < 2; ++k) { keys[k].release(); perm[k].release(); }
+        work.release(); pos2.release(); flag2.release(); cigoff2.release(); cigar2.release(); tid2.release(); xs2.release();
+    }
+};
+
 constexpr int NBUF = 4; // (at most: n_buf byte buffers and n_zw token buffers are used, ShareDecode::buffers)
 
 // The decode's streams -- A, B, C and the upload's -- and their events; waits for everything on them on the way out, whichever way that is.
@@ -1537,7 +1591,7 @@ struct ShareDecode {
     const bool any_order = !share && opts.any_order; // (the records may come in any order -- sorted behind the last extraction, sort_records; the whole file only)
     // ---- everything the streams touch is declared before them
     DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds, d_xs, d_fstat, d_fsum;
-    DevBuf d_sortkeys[2], d_sortperm[2], d_sortwork, d_pos2, d_flag2, d_cigoff2, d_cigar2, d_tid2, d_xs2; // (spl_bam_set_any_order: got only when the sort runs)
+    RecordSort sorter; // (spl_bam_set_any_order: its scratch is got only when the sort runs)
     std::vector<spl_zblock> blocks, blocks0; // (blocks0: the early windows', for their launches before the directory is complete)
     std::unique_ptr<uint32_t[]> status;
     std::unique_ptr<spl_bscan[]> scan;
@@ -2270,58 +2324,30 @@ struct ShareDecode {
         return SPL_OK;
     }
 
-    // ---- spl_bam_set_any_order, a file whose references do not come in order: the extracted arrays sorted by (reference id, POS,
-    // place in the file) on stream B.  Keys (id << 32 | POS) with the record's index as payload go through the passes of the stable
-    // radix sort (spl_sort.hip), least significant digit first, over the digits that can differ only: POS is at most the largest end
-    // any reference's reads have (d_maxend), the id below n_ref.  Then the arrays are gathered by the permutation -- the op counts
-    // in their new order scanned into the new cig_off, the CIGAR words copied run by run -- and take the unsorted ones' places.
-    // Scratch: two key and two payload buffers (24 bytes a record in all) and the arrays a second time; all given back in release_and_publish.
+    // ---- spl_bam_set_any_order, a file whose references do not come in order: the extracted arrays sorted on stream B (RecordSort
+    // above has the method); its scratch is given back in release_and_publish.
     uint64_t n_sorted = 0;
     double sort_ms = 0, sort_room_ms = 0, sort_bytes = 0; // (sort_room_ms: of sort_ms, giving the decode's buffers back and looking at what is free)
-    uint32_t sort_passes = 0, sort_pos_bits = 0, sort_tid_bits = 0;
     int sort_records()
     {
         if (n_rec > 0xfffffff0ull) return to_host("more than 2^32 placed records in a file that is not in coordinate order");
         const double t0 = host_now();
         unsigned long long top = 1;
         for (unsigned long long e : maxend) top = std::max(top, e);
-        while (sort_pos_bits < 31u && (top >> sort_pos_bits)) ++sort_pos_bits; // (POS is kept 1-based in 31 bits, and no read ends in front of its POS)
-        while (sort_tid_bits < 31u && ((uint64_t)std::max(n_ref - 1, 1) >> sort_tid_bits)) ++sort_tid_bits;
-        uint32_t shifts[8];
-        sort_passes = spl_dev_sort_passes(sort_pos_bits, sort_tid_bits, shifts);
+        sorter.plan(top, n_ref);
         // the decode's own buffers are done with (every window is extracted, stream B has been waited for): their room first
         d_image.release();
         for (int k = 0; k < NBUF; ++k) { d_stream[k].release(); d_zwork[k].release(); }
         d_recs.release();
-        const size_t n = (size_t)n_rec, work_bytes = spl_dev_sort_work_bytes(n_rec);
-        const double need = 24.0 * (double)n + (double)work_bytes + (want_xs ? 15.0 : 14.0) * (double)n + 4.0 * (double)n_ops + 4096.0;
         HIP_TRY(look_at_free());
-        if (need + slack > (double)free_b) return to_host("not enough device memory to sort the records");
+        if (RecordSort::bytes_needed(n_rec, n_ops, want_xs) + slack > (double)free_b) return to_host("not enough device memory to sort the records");
         const double t_room = host_now();
-        for (int k = 0; k < 2; ++k) { HIP_TRY(d_sortkeys[k].get(8 * n, pipe.b)); HIP_TRY(d_sortperm[k].get(4 * n, pipe.b)); }
-        HIP_TRY(d_sortwork.get(work_bytes, pipe.b));
-        HIP_TRY(d_pos2.get(4 * n, pipe.b)); HIP_TRY(d_flag2.get(2 * n, pipe.b)); HIP_TRY(d_cigoff2.get(4 * (n + 1), pipe.b));
-        HIP_TRY(d_cigar2.get(4 * (size_t)n_ops, pipe.b)); HIP_TRY(d_tid2.get(4 * n, pipe.b));
-        if (want_xs) HIP_TRY(d_xs2.get(n, pipe.b));
-        HIP_TRY((hipError_t)spl_dev_launch_sort_make_keys(d_tid.as<int32_t>(), d_pos.as<int32_t>(), n_rec, d_sortkeys[0].as<uint64_t>(), pipe.b));
-        int cur = 0;
-        for (uint32_t k = 0; k < sort_passes; ++k, cur ^= 1)
-            HIP_TRY((hipError_t)spl_dev_launch_sort_pass(d_sortkeys[cur].as<uint64_t>(), k ? d_sortperm[cur].as<uint32_t>() : nullptr, n_rec, shifts[k], d_sortkeys[cur ^ 1].as<uint64_t>(),
-                                                         d_sortperm[cur ^ 1].as<uint32_t>(), d_sortwork.p, pipe.b));
-        const uint32_t *perm = d_sortperm[cur].as<uint32_t>();
-        HIP_TRY((hipError_t)spl_dev_launch_sort_gather(perm, d_sortkeys[cur].as<uint64_t>(), n_rec, d_pos.as<int32_t>(), d_flag.as<uint16_t>(), want_xs ? d_xs.as<uint8_t>() : nullptr,
-                                                       d_cigoff.as<uint32_t>(), d_pos2.as<int32_t>(), d_flag2.as<uint16_t>(), want_xs ? d_xs2.as<uint8_t>() : nullptr, d_tid2.as<int32_t>(),
-                                                       d_cigoff2.as<uint32_t>(), pipe.b));
-        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_cigoff2.as<uint32_t>() + 1, n_rec, d_sortwork.p, pipe.b)); // (n_ops < 2^32: records_done)
-        HIP_TRY((hipError_t)spl_dev_launch_sort_cigar(perm, n_rec, d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), d_cigoff2.as<uint32_t>(), d_cigar2.as<uint32_t>(), pipe.b));
-        HIP_TRY(hipStreamSynchronize(pipe.b));
-        std::swap(d_pos.p, d_pos2.p); std::swap(d_flag.p, d_flag2.p); std::swap(d_cigoff.p, d_cigoff2.p); std::swap(d_cigar.p, d_cigar2.p); std::swap(d_tid.p, d_tid2.p);
-        std::swap(d_xs.p, d_xs2.p);
+        { const int rc = sorter.run(pipe.b, n_rec, n_ops, want_xs, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_xs); if (rc) return rc; } // (n_ops < 2^32: records_done)
         n_sorted = n_rec;
         sort_ms = 1e3 * (host_now() - t0);
         sort_room_ms = 1e3 * (t_room - t0);
         // (make_keys 16; a pass 8 + 8 + 12 and the payloads it reads; gather 12 + 8 and the fields twice; scan 12; the CIGARs' offsets 20, their words twice)
-        sort_bytes = (double)n * (16.0 + 28.0 * sort_passes + 4.0 * (sort_passes - 1) + 20.0 + 2.0 * (want_xs ? 15.0 : 14.0) + 12.0 + 20.0) + 8.0 * (double)n_ops;
+        sort_bytes = (double)n_rec * (16.0 + 28.0 * sorter.passes + 4.0 * (sorter.passes - 1) + 20.0 + 2.0 * (want_xs ? 15.0 : 14.0) + 12.0 + 20.0) + 8.0 * (double)n_ops;
         return SPL_OK;
     }
 
@@ -2396,7 +2422,7 @@ struct ShareDecode {
                             n_bytes / 1e6, (stream_len - stream_begin) / 1e6, n_win, n_win == 1 ? "" : "s", (unsigned long long)n_rec, (long long)n_all, host_now() - t_begin);
         if (timing && n_sorted)
             fprintf(stderr, "[spl_bam_decode_device] device %d: not in coordinate order: %llu records sorted in %.3f ms (%.3f of them before the scratch memory was asked for), %u passes (%u bits of POS, %u of the reference id), %.1f MB read and written\n",
-                    c->device, (unsigned long long)n_sorted, sort_ms, sort_room_ms, sort_passes, sort_pos_bits, sort_tid_bits, sort_bytes / 1e6);
+                    c->device, (unsigned long long)n_sorted, sort_ms, sort_room_ms, sorter.passes, sorter.pos_bits, sorter.tid_bits, sort_bytes / 1e6);
         if (timing) {
             fprintf(stderr, "[spl_bam_decode_device] device %d: staging buffers at %.4f s, the ring's memory %.4f, streams and events %.4f, the first window's buffers %.4f, its kernels on their streams %.4f\n",
                     c->device, t_stage, t_image, t_pipe, t_early_bufs, t_early);
@@ -2417,8 +2443,7 @@ struct ShareDecode {
         for (int k = 0; k < NBUF; ++k) { d_stream[k].release(); d_zwork[k].release(); }
         d_blocks0.release(); d_status0.release(); d_recs.release(); d_blocks.release(); d_status.release(); d_scan.release(); d_recoff.release(); d_opoff.release();
         d_tid.release(); d_maxend.release(); d_bounds.release(); d_nbounds.release(); d_fstat.release(); d_fsum.release();
-        for (int k = 0; k < 2; ++k) { d_sortkeys[k].release(); d_sortperm[k].release(); }
-        d_sortwork.release(); d_pos2.release(); d_flag2.release(); d_cigoff2.release(); d_cigar2.release(); d_tid2.release(); d_xs2.release();
+        sorter.release();
         const int told = publish(res);
         // ... and not at once: 500 events and five streams destroyed are 10 ms of the HIP runtime's locks, which the thread that was
         // told above needs now -- for the layout kernels, the chunk order's upload, the counting launches (its 9 ms took 17 beside
@@ -2441,6 +2466,369 @@ static int decode_share(spl_ctx *c, spl_bam *bam, const spl_bam_share *share, Sh
     if (rc == SPL_OK) rc = d.finish();
     if (rc == SPL_OK) return d.release_and_publish(publish);
     return rc == STOPPED ? SPL_OK : rc;
+}
+
+// ---- SAM text (spl_sam_open): the same five arrays from the text an aligner writes --------------------------------------
+// Windows of SPL_SAM_WINDOW_BYTES (default 256 MiB) of whole lines -- the host cuts a window behind its last '\n', which it finds
+// in the mapping: text needs no room for an unfinished line, and a line longer than a window declines the file -- go up
+// through the context's staging ring on the copy stream, from a thread of this call, into two device buffers, while the window
+// before is parsed on a stream of its own: line starts (count, prefix sum, fill), the scan (the rule, a lane per line), prefix sums
+// of kept lines and ops, the extraction.  The host waits twice a window, for the number of lines and for the kept lines' and ops'
+// totals (the output arrays are sized from the first window's density and regrown, device to device, when a later one needs
+// more).  Behind the last window: the sort when reference ids or POS ever went down (text is always spl_bam_set_any_order),
+// where each reference's records are, the totals, and the same hand-over as the BAM decode's.  A line the rule does not take ends
+// the decode with the file declined (spl_sam_fail); everything else that goes wrong leaves the file to the host parser.
+namespace {
+struct SamDecode {
+    spl_ctx *const c;
+    spl_bam *const bam;
+    ShareOut &res;
+    const bool timing = getenv("SPL_BAM_TIMING") != nullptr;
+    static double host_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    const double t_begin = host_now();
+    size_t fsize = 0;
+    const uint8_t *const image = spl_bam_image(bam, &fsize);
+    const int n_ref = spl_bam_n_ref(bam);
+    const spl_bam_decode_opts opts = spl_bam_get_opts(bam);
+    const bool want_xs = opts.aux_strand, want_stat = opts.flagstat;
+    uint64_t begin = 0, header_lines = 0;
+    spl_sam_names host_names{}, dev_names{};
+    size_t blob_bytes = 0;
+    // ---- everything the streams touch is declared before them
+    DevBuf d_text[2], d_slots, d_nameoff, d_blob, d_chunks, d_lines, d_kept, d_nops, d_ltid, d_fstat, d_fsum, d_counts, d_work, d_maxend, d_bounds, d_nbounds;
+    DevBuf d_pos, d_flag, d_tid, d_cigoff, d_cigar, d_xs;
+    RecordSort sorter;
+    size_t cap_chunks = 0, cap_lines = 0, cap_work = 0;
+    uint64_t cap_rec = 0, cap_ops = 0, n_rec = 0, n_ops = 0, n_lines_all = 0, n_drop_flags = 0, n_drop_mapq = 0, n_sorted = 0;
+    struct Streams {
+        hipStream_t k = nullptr;
+        hipEvent_t up[2] = {nullptr, nullptr};
+        ~Streams()
+        {
+            if (k) { (void)hipStreamSynchronize(k); (void)hipStreamDestroy(k); }
+            for (hipEvent_t e : up) if (e) (void)hipEventDestroy(e);
+        }
+    } st;
+    // ---- the windows and the thread that sends them
+    struct Window { uint64_t lo, hi; };
+    std::vector<Window> windows;
+    size_t win_bytes = (size_t)256 << 20;
+    std::mutex mu;
+    std::condition_variable cv;
+    size_t n_sent = 0, n_parsed = 0; // windows whose copies are queued (their event recorded) / whose buffer is free again
+    bool stop = false;
+    hipError_t up_err = hipSuccess;
+    std::thread uploader;
+
+    SamDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : c(ctx), bam(b), res(r) {}
+    ~SamDecode()
+    {
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            stop = true;
+        }
+        cv.notify_all();
+        if (uploader.joinable()) uploader.join();
+        if (c->copy) (void)hipStreamSynchronize(c->copy);
+        for (spl_ctx::Stage &sg : c->stage) sg.busy = false;
+    }
+
+    // The file cut into windows of whole lines.  A line longer than a window (its newline counted) fits none: the windows end in
+    // front of it, and the file is declined there once the lines before it have been found good -- the first line the rule does
+    // not take is the one that is reported, as by the host parser, which declines the same line by the same measure.
+    bool long_line = false;
+    int plan()
+    {
+        (void)spl_bam_text(bam, &begin, &header_lines, &host_names, &blob_bytes);
+        win_bytes = spl_sam_window_bytes();
+        for (uint64_t lo = begin; lo < fsize;) {
+            uint64_t hi = std::min<uint64_t>(fsize, lo + win_bytes);
+            if (hi < fsize) {
+                const void *nl = memrchr(image + lo, '\n', (size_t)(hi - lo));
+                if (!nl) { long_line = true; break; }
+                hi = (uint64_t)((const uint8_t *)nl - image) + 1;
+            }
+            windows.push_back(Window{lo, hi});
+            lo = hi;
+        }
+        return SPL_OK;
+    }
+
+    size_t buf_bytes() const { return win_bytes + 16 + SPL_SAM_PAD; } // (a window begins up to 15 bytes behind its buffer's first byte)
+
+    int set_up()
+    {
+        HIP_TRY(hipStreamCreateWithFlags(&st.k, hipStreamNonBlocking));
+        for (hipEvent_t &e : st.up) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        { const int rc = ensure_stage(c, 3); if (rc) return rc; }
+        for (int k = 0; k < (windows.size() > 1 ? 2 : 1); ++k) HIP_TRY(d_text[k].get(buf_bytes(), st.k));
+        const size_t nr = (size_t)std::max(n_ref, 1);
+        HIP_TRY(d_slots.get(4 * (size_t)host_names.n_slots, st.k)); HIP_TRY(d_nameoff.get(4 * (nr + 1), st.k)); HIP_TRY(d_blob.get(std::max<size_t>(blob_bytes, 1), st.k));
+        HIP_TRY(d_counts.get(sizeof(spl_sam_counts), st.k)); HIP_TRY(d_maxend.get(8 * nr, st.k)); HIP_TRY(d_fsum.get(8 * 2 * SPL_FS_CATEGORIES, st.k));
+        HIP_TRY(d_bounds.get(16 * (nr + 1), st.k)); HIP_TRY(d_nbounds.get(4, st.k));
+        HIP_TRY(hipMemcpyAsync(d_slots.p, host_names.slots, 4 * (size_t)host_names.n_slots, hipMemcpyHostToDevice, st.k));
+        HIP_TRY(hipMemcpyAsync(d_nameoff.p, host_names.name_off, 4 * (nr + 1), hipMemcpyHostToDevice, st.k));
+        HIP_TRY(hipMemcpyAsync(d_blob.p, host_names.blob, std::max<size_t>(blob_bytes, 1), hipMemcpyHostToDevice, st.k));
+        HIP_TRY(hipMemsetAsync(d_counts.p, 0, sizeof(spl_sam_counts), st.k));
+        HIP_TRY(hipMemsetAsync(d_maxend.p, 0, 8 * nr, st.k));
+        HIP_TRY(hipMemsetAsync(d_fsum.p, 0, 8 * 2 * SPL_FS_CATEGORIES, st.k));
+        HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, st.k));
+        HIP_TRY(hipStreamSynchronize(st.k)); // (the names' host memory is the file's; the copies above are done with it here)
+        dev_names = spl_sam_names{d_slots.as<uint32_t>(), d_nameoff.as<uint32_t>(), d_blob.as<uint8_t>(), host_names.n_slots, host_names.n};
+        uploader = std::thread([this]() { send_windows(); });
+        return SPL_OK;
+    }
+
+    // (the uploader's thread) window w into buffer w % 2 once window w - 2 is parsed, piece by piece through the staging ring
+    void send_windows()
+    {
+        hipError_t q = hipSetDevice(c->device);
+        for (size_t w = 0; w < windows.size() && q == hipSuccess; ++w) {
+            {
+                std::unique_lock<std::mutex> lock(mu);
+                cv.wait(lock, [&]() { return stop || w < n_parsed + 2; });
+                if (stop) return;
+            }
+            const uint64_t from = windows[w].lo & ~(uint64_t)15, bytes = windows[w].hi - from;
+            char *const dst = d_text[w % 2].as<char>();
+            for (uint64_t done = 0; done < bytes && q == hipSuccess;) {
+                spl_ctx::Stage &sg = c->stage[c->stage_next];
+                c->stage_next = (c->stage_next + 1) % c->stage.size();
+                if (sg.busy) { q = hipEventSynchronize(sg.done); sg.busy = false; if (q != hipSuccess) break; }
+                const size_t n = (size_t)std::min<uint64_t>(bytes - done, sg.bytes);
+                CopyJob job{sg.host, (const char *)image + from + done, n, (n + 7) / 8, spl_bam_fd(bam), (size_t)(from + done)};
+                splpack::parallel_for((n + job.per - 1) / std::max<size_t>(job.per, 1), 8, copy_slice, &job);
+                q = hipMemcpyAsync(dst + done, sg.host, n, hipMemcpyHostToDevice, c->copy);
+                if (q == hipSuccess) { q = hipEventRecord(sg.done, c->copy); sg.busy = true; }
+                done += n;
+            }
+            if (q == hipSuccess) q = hipEventRecord(st.up[w % 2], c->copy);
+            std::lock_guard<std::mutex> lock(mu);
+            if (q == hipSuccess) n_sent = w + 1;
+            else up_err = q;
+            cv.notify_all();
+        }
+        if (q != hipSuccess) {
+            std::lock_guard<std::mutex> lock(mu);
+            up_err = q;
+            cv.notify_all();
+        }
+    }
+
+    template <class T> hipError_t regrow(DevBuf &b, size_t old_n, size_t new_n)
+    {
+        DevBuf fresh;
+        hipError_t q = fresh.get(sizeof(T) * new_n, st.k);
+        if (q == hipSuccess && b.p && old_n) q = hipMemcpyAsync(fresh.p, b.p, sizeof(T) * old_n, hipMemcpyDeviceToDevice, st.k);
+        if (q == hipSuccess) q = hipStreamSynchronize(st.k);
+        if (q == hipSuccess) std::swap(b.p, fresh.p);
+        return q; // (fresh's destructor gives the old array back)
+    }
+    // room for the records and ops of this window behind the ones there are; the first time from the window's density over the file
+    int make_room(uint64_t more_rec, uint64_t more_ops, uint64_t win_len, uint64_t bytes_left)
+    {
+        const uint64_t need_rec = n_rec + more_rec, need_ops = n_ops + more_ops;
+        if (need_rec <= cap_rec && need_ops <= cap_ops && cap_rec) return SPL_OK;
+        const double scale = 1.0 + 1.1 * (double)bytes_left / (double)std::max<uint64_t>(win_len, 1); // (this window, and the rest at its density and a tenth)
+        const uint64_t want_rec = std::max<uint64_t>(need_rec, n_rec + (uint64_t)((double)more_rec * scale)) + 1024, want_ops = std::max<uint64_t>(need_ops, n_ops + (uint64_t)((double)more_ops * scale)) + 1024;
+        if (need_rec > cap_rec || !cap_rec) {
+            HIP_TRY(regrow<int32_t>(d_pos, (size_t)n_rec, (size_t)want_rec)); HIP_TRY(regrow<uint16_t>(d_flag, (size_t)n_rec, (size_t)want_rec)); HIP_TRY(regrow<int32_t>(d_tid, (size_t)n_rec, (size_t)want_rec));
+            HIP_TRY(regrow<uint32_t>(d_cigoff, cap_rec ? (size_t)n_rec + 1 : 0, (size_t)want_rec + 1));
+            if (want_xs) HIP_TRY(regrow<uint8_t>(d_xs, (size_t)n_rec, (size_t)want_rec));
+            if (!cap_rec) { HIP_TRY(hipMemsetAsync(d_cigoff.p, 0, 4, st.k)); }
+            cap_rec = want_rec;
+        }
+        if (need_ops > cap_ops || !d_cigar.p) {
+            HIP_TRY(regrow<uint32_t>(d_cigar, (size_t)n_ops, (size_t)want_ops));
+            cap_ops = want_ops;
+        }
+        return SPL_OK;
+    }
+
+    uint64_t bad_line = 0; uint32_t bad_reason = 0; // (a window's scan found a line the rule does not take)
+
+    int parse_window(size_t w)
+    {
+        {
+            std::unique_lock<std::mutex> lock(mu);
+            cv.wait(lock, [&]() { return n_sent > w || up_err != hipSuccess; });
+            HIP_TRY(up_err);
+        }
+        if (spl_bam_cancelled(bam)) return spl_set_error(SPL_ERR_IO, "closed before it was decoded");
+        const Window win = windows[w];
+        const uint64_t base = win.lo & ~(uint64_t)15;
+        const uint8_t *const text = d_text[w % 2].as<uint8_t>() - base;
+        const uint64_t last_end = image[win.hi - 1] == '\n' ? win.hi - 1 : win.hi;
+        HIP_TRY(hipStreamWaitEvent(st.k, st.up[w % 2], 0));
+        // ---- line starts
+        const uint32_t n_chunks = spl_sam_chunks(win.lo, win.hi);
+        if (n_chunks > cap_chunks) { d_chunks.release(); HIP_TRY(d_chunks.get(4 * (size_t)n_chunks, st.k)); cap_chunks = n_chunks; }
+        auto work_for = [&](uint64_t n) -> hipError_t {
+            const size_t need = spl_dev_sort_work_bytes(n);
+            if (need <= cap_work) return hipSuccess;
+            d_work.release();
+            cap_work = 0;
+            const hipError_t q = d_work.get(need, st.k);
+            if (q == hipSuccess) cap_work = need;
+            return q;
+        };
+        HIP_TRY(work_for(n_chunks));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_line_count(text, win.lo, win.hi, d_chunks.as<uint32_t>(), st.k));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_chunks.as<uint32_t>(), n_chunks, d_work.p, st.k));
+        uint32_t n_lines = 0;
+        HIP_TRY(hipMemcpyAsync(&n_lines, d_chunks.as<uint32_t>() + (n_chunks - 1), 4, hipMemcpyDeviceToHost, st.k));
+        HIP_TRY(hipStreamSynchronize(st.k));
+        if (n_lines > cap_lines) {
+            d_lines.release(); d_kept.release(); d_nops.release(); d_ltid.release(); d_fstat.release();
+            cap_lines = 0;
+            const size_t n = (size_t)n_lines + (size_t)n_lines / 8;
+            HIP_TRY(d_lines.get(4 * n, st.k)); HIP_TRY(d_kept.get(4 * n, st.k)); HIP_TRY(d_nops.get(4 * n, st.k)); HIP_TRY(d_ltid.get(4 * n, st.k));
+            if (want_stat) HIP_TRY(d_fstat.get(4 * SPL_FS_CATEGORIES * ((n + 63) / 64), st.k));
+            cap_lines = n;
+        }
+        HIP_TRY(work_for(n_lines));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_line_fill(text, win.lo, win.hi, d_chunks.as<uint32_t>(), d_lines.as<uint32_t>(), st.k));
+        // ---- the rule, a lane per line
+        static const unsigned long long none = ~0ull;
+        HIP_TRY(hipMemcpyAsync(d_counts.p, &none, 8, hipMemcpyHostToDevice, st.k));
+        HIP_TRY(hipMemsetAsync(d_counts.as<char>() + 8, 0, 8, st.k)); // (the two drop counters; `unordered` and `overflow` stay)
+        HIP_TRY((hipError_t)spl_dev_launch_sam_scan(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
+                                                    opts.filter.exclude_flags, want_xs ? 1 : 0, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(),
+                                                    want_stat ? d_fstat.as<uint32_t>() : nullptr, d_counts.as<spl_sam_counts>(), st.k));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_kept.as<uint32_t>(), n_lines, d_work.p, st.k));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_nops.as<uint32_t>(), n_lines, d_work.p, st.k)); // (below 2^32 a window: a window is below 2^30 bytes, an op two bytes at least)
+        spl_sam_counts counts;
+        uint32_t kept_w = 0, ops_w = 0;
+        HIP_TRY(hipMemcpyAsync(&counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st.k));
+        if (n_lines) {
+            HIP_TRY(hipMemcpyAsync(&kept_w, d_kept.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st.k));
+            HIP_TRY(hipMemcpyAsync(&ops_w, d_nops.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st.k));
+        }
+        HIP_TRY(hipStreamSynchronize(st.k));
+        if (counts.first_bad != none) {
+            bad_line = header_lines + n_lines_all + (counts.first_bad >> 8) + 1;
+            bad_reason = (uint32_t)(counts.first_bad & 0xffu);
+            return STOPPED;
+        }
+        if (n_rec + kept_w > 0xfffffff0ull || n_ops + ops_w > 0xfffffff0ull) { // (cig_off is 32 bits wide, and so is the sort's payload)
+            bad_line = header_lines + n_lines_all + n_lines;
+            bad_reason = SPL_SAM_TOO_MANY;
+            return STOPPED;
+        }
+        n_drop_flags += counts.n_drop_flags;
+        n_drop_mapq += counts.n_drop_mapq;
+        if (want_stat) HIP_TRY((hipError_t)spl_dev_launch_bam_flagstat_reduce(d_fstat.as<uint32_t>(), (n_lines + 63u) / 64u, d_fsum.as<unsigned long long>(), st.k));
+        // ---- the kept lines' fields behind the ones there are
+        { const int rc = make_room(kept_w, ops_w, win.hi - win.lo, fsize - win.hi); if (rc) return rc; }
+        HIP_TRY((hipError_t)spl_dev_launch_sam_extract(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
+                                                       opts.filter.exclude_flags, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(), n_rec, n_ops, cap_rec, cap_ops,
+                                                       d_pos.as<int32_t>(), d_flag.as<uint16_t>(), d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(),
+                                                       want_xs ? d_xs.as<uint8_t>() : nullptr, d_maxend.as<unsigned long long>(), d_counts.as<spl_sam_counts>(), st.k));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_order(d_tid.as<int32_t>(), d_pos.as<int32_t>(), n_rec, kept_w, d_counts.as<spl_sam_counts>(), st.k));
+        HIP_TRY(hipStreamSynchronize(st.k)); // (the window's buffer is free for the window after the next)
+        n_rec += kept_w;
+        n_ops += ops_w;
+        n_lines_all += n_lines;
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            n_parsed = w + 1;
+        }
+        cv.notify_all();
+        return SPL_OK;
+    }
+
+    // the window buffers and the per-line arrays are done with behind the last window: their room first, for the sort and for whoever is told next
+    void release_buffers()
+    {
+        for (DevBuf &b : d_text) b.release();
+        d_chunks.release(); d_lines.release(); d_kept.release(); d_nops.release(); d_ltid.release(); d_fstat.release(); d_work.release();
+    }
+    std::vector<unsigned long long> maxend;
+    int sort_records()
+    {
+        unsigned long long top = 1;
+        for (unsigned long long e : maxend) top = std::max(top, e);
+        sorter.plan(top, n_ref);
+        release_buffers();
+        const int rc = sorter.run(st.k, n_rec, n_ops, want_xs, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_xs); // (n_rec and n_ops below 2^32 - 16: parse_window)
+        if (rc == SPL_OK) n_sorted = n_rec;
+        return rc;
+    }
+
+    int finish()
+    {
+        if (!cap_rec) { const int rc = make_room(0, 0, 1, 0); if (rc) return rc; } // (a file without a placed record)
+        const size_t nr = (size_t)std::max(n_ref, 1);
+        const uint32_t bounds_cap = (uint32_t)nr + 1u;
+        maxend.assign(nr, 0);
+        spl_sam_counts counts;
+        unsigned long long fsum[2 * SPL_FS_CATEGORIES] = {0};
+        HIP_TRY(hipMemcpyAsync(maxend.data(), d_maxend.p, 8 * nr, hipMemcpyDeviceToHost, st.k));
+        HIP_TRY(hipMemcpyAsync(&counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st.k));
+        if (want_stat) HIP_TRY(hipMemcpyAsync(fsum, d_fsum.p, sizeof(fsum), hipMemcpyDeviceToHost, st.k));
+        HIP_TRY(hipStreamSynchronize(st.k));
+        if (counts.overflow) return spl_set_error(SPL_ERR_HIP, "the SAM extraction disagreed with its scan (%u)", counts.overflow);
+        if (counts.unordered) { const int rc = sort_records(); if (rc) return rc; }
+        // where each reference's records are (their ids go up now)
+        std::vector<uint64_t> bounds(2 * (size_t)bounds_cap, 0);
+        uint32_t n_bounds = 0;
+        HIP_TRY((hipError_t)spl_dev_launch_bam_bounds(d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), n_rec, d_bounds.as<uint64_t>(), d_nbounds.as<uint32_t>(), bounds_cap, st.k));
+        HIP_TRY(hipMemcpyAsync(bounds.data(), d_bounds.p, 16 * (size_t)bounds_cap, hipMemcpyDeviceToHost, st.k));
+        HIP_TRY(hipMemcpyAsync(&n_bounds, d_nbounds.p, 4, hipMemcpyDeviceToHost, st.k));
+        HIP_TRY(hipStreamSynchronize(st.k));
+        if (n_bounds > bounds_cap) return spl_set_error(SPL_ERR_HIP, "the SAM records' reference ids do not go up behind the sort");
+        struct Run { uint64_t first; int32_t tid; uint32_t op; };
+        std::vector<Run> runs;
+        for (uint32_t k = 0; k < n_bounds; ++k) runs.push_back(Run{bounds[2 * k], (int32_t)(uint32_t)bounds[2 * k + 1], (uint32_t)(bounds[2 * k + 1] >> 32)});
+        std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.first < b.first; });
+        for (size_t k = 0; k < runs.size(); ++k)
+            if (runs[k].tid < 0 || runs[k].tid >= n_ref || (k && runs[k].tid <= runs[k - 1].tid)) return spl_set_error(SPL_ERR_HIP, "the SAM records' reference ids do not go up behind the sort");
+        DeviceReads *keep = new (std::nothrow) DeviceReads();
+        if (!keep) return spl_set_error(SPL_ERR_NOMEM, "out of host memory");
+        keep->device = c->device;
+        keep->n_rec = (int64_t)n_rec; keep->n_ops = (int64_t)n_ops;
+        keep->ref_first.assign(nr, 0); keep->ref_n.assign(nr, 0); keep->ref_max.assign(nr, 0); keep->ref_ops.assign(nr, 0);
+        for (size_t k = 0; k < runs.size(); ++k) {
+            const size_t t = (size_t)runs[k].tid;
+            const bool last = k + 1 == runs.size();
+            keep->ref_first[t] = (int64_t)runs[k].first;
+            keep->ref_n[t] = (int64_t)((last ? n_rec : runs[k + 1].first) - runs[k].first);
+            keep->ref_ops[t] = (int64_t)((last ? n_ops : (uint64_t)runs[k + 1].op) - runs[k].op);
+            keep->ref_max[t] = (int64_t)maxend[t];
+        }
+        keep->pos = d_pos.p; keep->flag = d_flag.p; keep->cig_off = d_cigoff.p; keep->cigar = d_cigar.p; keep->xs = d_xs.p;
+        d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = d_xs.p = nullptr; // (the caller owns them from here)
+        res.reads = keep;
+        res.totals.n_records = (int64_t)n_lines_all;
+        res.totals.n_sorted = (int64_t)n_sorted;
+        res.totals.sorted_on_device = n_sorted ? 1 : 0;
+        res.totals.dropped[0] = (int64_t)n_drop_flags;
+        res.totals.dropped[1] = (int64_t)n_drop_mapq;
+        for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.totals.fstat[q] = (int64_t)fsum[q];
+        if (timing)
+            fprintf(stderr, "[spl_bam_decode_device] device %d: SAM text, %.1f MB in %zu window%s, %llu lines, %llu placed records%s: %.4f s\n", c->device, (fsize - begin) / 1e6, windows.size(),
+                    windows.size() == 1 ? "" : "s", (unsigned long long)n_lines_all, (unsigned long long)n_rec, n_sorted ? ", sorted" : "", host_now() - t_begin);
+        return SPL_OK;
+    }
+};
+} // namespace
+
+static int decode_text(spl_ctx *c, spl_bam *bam, ShareOut &res, const Publish &publish)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    SamDecode d(c, bam, res);
+    int rc = d.plan();
+    if (rc == SPL_OK) rc = d.set_up();
+    for (size_t w = 0; w < d.windows.size() && rc == SPL_OK; ++w) rc = d.parse_window(w);
+    if (rc == STOPPED) { spl_sam_fail(bam, d.bad_line, d.bad_reason); return SPL_OK; }
+    if (rc == SPL_OK && d.long_line) { spl_sam_fail(bam, d.header_lines + d.n_lines_all + 1, SPL_SAM_LONG_LINE); return SPL_OK; }
+    if (rc == SPL_OK) rc = d.finish();
+    if (rc != SPL_OK) return rc;
+    // as ShareDecode::release_and_publish: the decode's buffers go back to the pool before the waiters are told (a failed
+    // hand-over frees the reads itself: spl_bam_decode_device's `adopt`)
+    d.release_buffers();
+    d.sorter.release();
+    return publish(res);
 }
 
 // The device's sort on a caller's keys (test hook): exactly the launches sort_records makes for keys of key_bits bits.

@@ -78,19 +78,31 @@ class _SamSource(object):
 
 
 def open_alignments(path, threads=0, stream=False, defer=False, options=DecodeOptions()):
-    """BAM (BGZF) through the native decoder; plain SAM text through the Python reader.  ``stream=True``: the BAM decoder
+    """BAM (BGZF) through the native decoder; plain SAM text through the Python reader, or -- ``defer=True``, a decode that may use
+    the GPU -- as a ``native.SamFile``.  ``stream=True``: the BAM decoder
     returns after the header and decodes in the background (``native.BamFile``); ``defer=True``: nothing is decoded until
     somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``options`` (``DecodeOptions``): what either
-    reader is to do -- SAM text has no flagstat counters (an error) and is read whole and per reference whatever its order."""
+    reader is to do -- the Python reader has no flagstat counters (an error); SAM text is read whole and per reference whatever its
+    order."""
     with open(path, "rb") as fh:
         magic = fh.read(4)
     if magic[:2] == b"\x1f\x8b":
         q, f, F = options.read_filter
         return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=options.aux_strand,
                               flagstat=options.flagstat, any_order=options.any_order)
+    is_sam = magic[:1] == b"@" or b"\t" in open(path, "rb").readline()
+    if is_sam and defer:
+        # the aligner's text parsed natively (on the GPU by ``SamFile.decode_on_device``): counters, kept reads and all.  A header
+        # the native reader does not take (no @SQ / LN, a repeated name) is the Python reader's, as any SAM text was
+        try:
+            q, f, F = options.read_filter
+            return native.SamFile(path, threads=threads, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=options.aux_strand, flagstat=options.flagstat)
+        except native.SpliserNativeError as exc:
+            if exc.code != -5:
+                raise
     if options.flagstat:
         raise native.SpliserNativeError(-5, "%s: flagstat counters are counted while a BAM file is decoded; this is not one" % path)
-    if magic[:1] == b"@" or b"\t" in open(path, "rb").readline():
+    if is_sam:
         return _SamSource(path, options)
     raise native.SpliserNativeError(-5, "%s is neither BGZF/BAM nor SAM text" % path)
 
@@ -115,6 +127,8 @@ def open_and_decode(path, devices, gpuDecode=None, threads=0, options=DecodeOpti
     any of them starts.  A file in any order is decoded whole on the first device -- shares are cut on the order of references --,
     whichever devices count its chromosomes afterwards."""
     source = open_alignments(path, threads=threads, stream=True, defer=gpuDecode is not False, options=options)
+    if isinstance(source, native.SamFile):
+        return _decode_sam_text(source, path, devices, options, log)
     if isinstance(source, native.BamFile) and gpuDecode is not False:
         try:
             if len(devices) > 1 and options.any_order:
@@ -129,6 +143,38 @@ def open_and_decode(path, devices, gpuDecode=None, threads=0, options=DecodeOpti
             source.close()
             raise
     return source
+
+
+def _decode_sam_text(source, path, devices, options, log):
+    """SAM text parsed on the first device, here and now: whether the strict rule takes the file is known at its end only, and a
+    file it declines is read by the Python reader exactly as before (or refused as before: flagstat).  -> the source to go on with."""
+    try:
+        if len(devices) > 1 and log is not None:
+            # (text is always read as under --anyOrder: the line that flag's decode says)
+            log("  (--anyOrder: the alignment file is decoded whole on device %d, not in shares over %d devices)" % (devices[0], len(devices)))
+        try:
+            ctx = native.Context(devices[0])
+        except native.SpliserNativeError:      # (no context to be had: the host thread parses, by the same rule -- as a BAM goes to the host threads then)
+            source.start_host_decode()
+        else:
+            with ctx:
+                source.decode_on_device(ctx)
+        why = source.declined()
+    except BaseException:
+        source.close()
+        raise
+    if not why:
+        if log is not None:
+            log("  (SAM text: %d lines parsed %s)" % (source.n_records, "on the GPU" if source.on_device else "on host threads"))
+            if not options.any_order:      # (text is always taken in any order; with --anyOrder the command says the line itself)
+                log_any_order(source, log)
+        return source
+    source.close()
+    if log is not None:
+        log("  (SAM text: %s: read by the Python reader)" % why)
+    if options.flagstat:
+        raise native.SpliserNativeError(-5, "%s: flagstat counters are counted while a BAM file is decoded; this is not one" % path)
+    return _SamSource(path, options)
 
 
 def log_any_order(source, log):
@@ -569,7 +615,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     # The alignment file does not depend on Steps 0-2: it is decoded on native threads while the site table is built here, and
     # goes on decoding while Step 3 counts the chromosomes that are complete.  An unreadable file is an error here already
     # (block directory and header are read by the opening call).
-    source = open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)     # (the decode runs beside Steps 0-2, wherever it runs)
+    source = open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)     # (a BAM's decode runs beside Steps 0-2, wherever it runs; SAM text is parsed here and now)
     keep = None      # (--keepReads: what the closing thread does first)
     try:
         t_open = time.perf_counter()
