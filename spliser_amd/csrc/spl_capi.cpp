@@ -443,6 +443,8 @@ struct spl_dreads {
     spl_chunk_meta *meta = nullptr;
     uint32_t *cost = nullptr;
     uint32_t *chunk_order = nullptr; // slot of an XCD share -> chunk, longest first (0xffffffff: none)
+    spl_fused_slot *by_chunk = nullptr; // the fused counting kernel's descriptor of every chunk (spl_layout_map_kernel) ...
+    spl_fused_slot *slots = nullptr;    // ... and the same in slot order, one per slot (spl_chunk_order_kernel)
     uint32_t *queue = nullptr; // reads the range kernel hands to the literal kernel (the counters are with the site table)
     uint32_t *queue_alt = nullptr;     // ... and the buffer the NEXT pass writes while this pass's literal kernel still reads
     uint32_t *queue_total = nullptr;   // entries the last pass queued (written by its literal kernel)
@@ -2868,13 +2870,13 @@ static int launch_layout(spl_ctx *c, spl_dreads *d)
         lp.n_rec = g.src->n_rec; lp.n_ops = g.src->n_ops;
         lp.chunks = g.d_chunks; lp.rec_base = (uint8_t *)g.slab; lp.meta = d->meta;
         // (the chunks' descriptors hold offsets read from the arrays: made anew whenever the layout runs)
-        const int rc0 = spl_dev_launch_layout_map(&lp.src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->cost, c->stream);
+        const int rc0 = spl_dev_launch_layout_map(&lp.src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->cost, d->by_chunk, c->stream);
         if (rc0) return spl_set_error(SPL_ERR_HIP, "layout map kernel launch: %s", hipGetErrorString((hipError_t)rc0));
         lps.push_back(lp);
     }
     if (d->n_chunks) {
         splprof::Scope prof("spl_chunk_order_kernel", c->stream, 8.0 * (double)d->n_chunks);
-        const int rc = spl_dev_launch_chunk_order(d->cost, d->n_chunks, chunk, d->chunk_order, c->stream);
+        const int rc = spl_dev_launch_chunk_order(d->cost, d->n_chunks, chunk, d->chunk_order, d->by_chunk, d->slots, c->stream);
         if (rc) return spl_set_error(SPL_ERR_HIP, "chunk order kernel launch: %s", hipGetErrorString((hipError_t)rc));
     }
     size_t gi = 0;
@@ -2928,6 +2930,7 @@ static int finish_reads(spl_ctx *c, spl_dreads *d)
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
     const size_t o_meta = take(sizeof(spl_chunk_meta) * std::max<size_t>(n, 1)), o_cost = take(4 * std::max<size_t>(n, 1)), o_order = take(4 * std::max<size_t>(d->n_slots, 1));
+    const size_t o_by_chunk = take(sizeof(spl_fused_slot) * std::max<size_t>(n, 1)), o_slots = take(sizeof(spl_fused_slot) * std::max<size_t>(d->n_slots, 1));
     const size_t o_total = take(4);
     const size_t o_queue = take(4 * 8 * shard_cap), o_queue_alt = take(c->tail ? 4 * 8 * shard_cap : 0);
     hipError_t e = devmem::get((void **)&d->ctl, std::max<size_t>(off, 256), 'c');
@@ -2935,6 +2938,8 @@ static int finish_reads(spl_ctx *c, spl_dreads *d)
     d->meta = (spl_chunk_meta *)(d->ctl + o_meta);
     d->cost = (uint32_t *)(d->ctl + o_cost);
     d->chunk_order = (uint32_t *)(d->ctl + o_order);
+    d->by_chunk = (spl_fused_slot *)(d->ctl + o_by_chunk);
+    d->slots = (spl_fused_slot *)(d->ctl + o_slots);
     d->queue_total = (uint32_t *)(d->ctl + o_total);
     d->queue = (uint32_t *)(d->ctl + o_queue);
     d->queue_alt = c->tail ? (uint32_t *)(d->ctl + o_queue_alt) : d->queue;
@@ -3459,6 +3464,7 @@ extern "C" int spl_count_launch(spl_ctx *c, spl_dsites *ds, const spl_dreads *dr
     if (dr->fused) {
         const spl_dreads::Group &g = dr->groups[0];
         h.cells = g.d_chunks;
+        h.slots = dr->slots;
         h.src = spl_devreads{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
         h.src_n_rec = g.src->n_rec; h.src_n_ops = g.src->n_ops;
     }

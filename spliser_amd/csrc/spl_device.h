@@ -32,8 +32,7 @@
 #define SPL_WAVE_ITERS 10
 #endif
 #define SPL_WAVE_READS (64 * SPL_WAVE_ITERS)
-#define SPL_TILE_FUSED_SHIFT 10           // reads per tile of a fused pass: the stage of 1024 reads' ops is 16 KB of LDS
-#define SPL_TILE_FUSED (1 << SPL_TILE_FUSED_SHIFT)
+// (SPL_TILE_FUSED, the reads per tile of a fused pass: spl_devpack.h, beside the descriptor that holds the tiles' boundaries)
 #define SPL_BLOCK_FUSED 256              // threads of its workgroups: four reads of a tile a thread (512 threads, two reads each, eight
                                          // waves to count a tile: 1.25 ms a launch against 0.94 -- what a wave does per tile whatever its
                                          // share of it is what the pass spends its instructions on)
@@ -140,6 +139,7 @@ struct spl_hot_params {
     // the FUSED instantiation (reads counted straight from the BAM-native arrays, see spl_count_ranges_kernel): the chunks are
     // cells of the grid over the arrays' indexes; chunk_meta is not looked at
     const spl_layout_chunk *cells; // [chunks] (spl_devpack.h; made by spl_layout_map_kernel)
+    const spl_fused_slot *slots; // [n_chunks] what a workgroup needs of its chunk, in slot order (spl_chunk_order_kernel)
     spl_devreads src;
     int64_t src_n_rec, src_n_ops;
 };

@@ -42,6 +42,27 @@ struct spl_layout_chunk {
     uint32_t flat;             // its index in the read set's flat chunk list
 };
 
+// What a workgroup of the FUSED counting kernel needs to know about its chunk (spl_kernels.hip), one per SLOT of that kernel's
+// grid and in slot order, 64 bytes on a 64-byte boundary: ONE scalar load where the workgroup had the chunk order, the chunk's
+// descriptor and then the arrays themselves (the CIGAR offsets at its tiles' boundaries, its first POS) to go through before it
+// could ask for its first read.  Made per chunk by spl_layout_map_kernel, put in slot order by spl_chunk_order_kernel.
+#define SPL_TILE_FUSED_SHIFT 10           // reads per tile of a fused pass: the stage of 1024 reads' ops is 16 KB of LDS
+#define SPL_TILE_FUSED (1 << SPL_TILE_FUSED_SHIFT)
+#define SPL_FUSED_TILES_MAX 4             // (a chunk of SPL_CHUNK_BIG reads)
+#define SPL_SLOT_EMPTY 0xffffffffu
+struct alignas(64) spl_fused_slot {
+    int64_t lo;                // index of the chunk's first read in the arrays
+    uint32_t chunk;            // its number in the launch's chunks (queue entries name it); SPL_SLOT_EMPTY: a slot without a chunk
+    uint32_t n;                // reads
+    int32_t shift;
+    uint32_t seg_op0;
+    int32_t pos0;              // POS of its first read, as the arrays have it (no shift)
+    uint32_t unused0;
+    uint32_t ob[SPL_FUSED_TILES_MAX + 1]; // cig_off at the tiles' boundaries, clamped to the chunk: ob[0] = o_lo, ob[tiles ..] = o_hi
+    uint32_t unused1[3];
+};
+static_assert(sizeof(spl_fused_slot) == 64, "one scalar load of sixteen words");
+
 struct spl_layout_params {
     spl_devreads src;
     int64_t n_rec;             // reads in the arrays (cig_off has n_rec + 1 entries): no load goes beyond them
@@ -62,14 +83,15 @@ static inline uint32_t spl_order_per(uint32_t n_chunks) { return ((n_chunks + 7u
 extern "C" {
 #endif
 // chunks[k] = the launch's k-th chunk (which segment's, where its reads and ops lie), cost[its flat index] = what it will cost the
-// range kernel, roughly, from its numbers of reads and ops (device arrays; chunk = reads per chunk)
+// range kernel, roughly, from its numbers of reads and ops (device arrays; chunk = reads per chunk); by_chunk[its flat index] =
+// the fused kernel's descriptor of it
 int spl_dev_launch_layout_map(const spl_devreads *src, const spl_layout_seg *segs, uint32_t n_segs, uint32_t n_chunks, uint32_t chunk, spl_layout_chunk *chunks, uint32_t *cost,
-                              void *stream);
+                              spl_fused_slot *by_chunk, void *stream);
 // the layout itself: one workgroup per chunk of the launch (chunk = reads per chunk, 2048 or 4096)
 int spl_dev_launch_layout(const spl_layout_params *p, uint32_t n_dev_chunks, uint32_t chunk, void *stream, void *ev_start, void *ev_stop);
 // cost[n_chunks] -> order[8 * spl_order_per(n_chunks)]: the range kernel's slots, XCD share by XCD share, longest chunk first;
-// 0xffffffff = an empty slot
-int spl_dev_launch_chunk_order(const uint32_t *cost, uint32_t n_chunks, uint32_t chunk, uint32_t *order, void *stream);
+// 0xffffffff = an empty slot; slots[the same] = by_chunk[order[slot]], or a descriptor marked SPL_SLOT_EMPTY
+int spl_dev_launch_chunk_order(const uint32_t *cost, uint32_t n_chunks, uint32_t chunk, uint32_t *order, const spl_fused_slot *by_chunk, spl_fused_slot *slots, void *stream);
 #ifdef __cplusplus
 }
 #endif

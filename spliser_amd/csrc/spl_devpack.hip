@@ -31,7 +31,7 @@ using namespace spllay;
 // and weighs 2, a once-spliced one three and 5, a twice-spliced one five and 9: (3 ops + reads) / 2), so that the chunk order can be
 // made BEFORE the records are (spl_chunk_order_kernel) and nothing stands between the layout kernel and the range kernel.
 __global__ __launch_bounds__(256) void spl_layout_map_kernel(const spl_devreads src, const spl_layout_seg *segs, uint32_t n_segs, uint32_t n_chunks, uint32_t chunk,
-                                                             spl_layout_chunk *chunks, uint32_t *cost)
+                                                             spl_layout_chunk *chunks, uint32_t *cost, spl_fused_slot *by_chunk)
 {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= n_chunks) return;
@@ -51,6 +51,20 @@ __global__ __launch_bounds__(256) void spl_layout_map_kernel(const spl_devreads 
     c.flat = s.chunk0 + (k - s.dev0);
     chunks[k] = c;
     cost[c.flat] = (3u * (c.o_hi - c.o_lo) + c.n) / 2u;
+    // the fused counting kernel's view of the chunk: the offsets at its tiles' boundaries (cell c0's tile q begins at c0 + q TILE,
+    // clamped to the chunk's reads) and its first POS -- a load of pos and at most three more of cig_off here, a thread per
+    // chunk, instead of two dependent trips in front of every workgroup's first tile there
+    spl_fused_slot f;
+    f.lo = c.lo; f.chunk = c.flat; f.n = c.n; f.shift = c.shift; f.seg_op0 = c.seg_op0;
+    f.pos0 = c.n ? src.pos[c.lo] : 0;
+    f.unused0 = 0; f.unused1[0] = f.unused1[1] = f.unused1[2] = 0;
+    const uint32_t tiles = chunk >> SPL_TILE_FUSED_SHIFT; // (0 for a chunk size the fused pass does not take: boundaries o_lo, o_hi ...)
+    for (uint32_t q = 0; q <= SPL_FUSED_TILES_MAX; ++q) {
+        int64_t i = c0 + (int64_t)q * SPL_TILE_FUSED;
+        i = i < c.lo ? c.lo : (i > hi ? hi : i);
+        f.ob[q] = q == 0u ? c.o_lo : (q >= tiles ? c.o_hi : src.cig_off[i]);
+    }
+    by_chunk[c.flat] = f;
 }
 
 template <int C>
@@ -82,7 +96,8 @@ __global__ __launch_bounds__(C / 4) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 // spread over all eight; neighbouring chunks, which share lines of the position index, still go to one L2 together), and inside
 // an XCD's share they go longest first by the cost estimate (a counting sort on cost / 16; equal keys in any order).  One
 // workgroup per XCD share; slots past a share's chunks hold 0xffffffff.
-__global__ __launch_bounds__(1024) void spl_chunk_order_kernel(const uint32_t *cost, uint32_t n, uint32_t per, uint32_t *order)
+__global__ __launch_bounds__(1024) void spl_chunk_order_kernel(const uint32_t *cost, uint32_t n, uint32_t per, uint32_t *order, const spl_fused_slot *by_chunk,
+                                                               spl_fused_slot *slots)
 {
     constexpr uint32_t NB = 4096;
     __shared__ uint32_t s_hist[NB];
@@ -113,18 +128,31 @@ __global__ __launch_bounds__(1024) void spl_chunk_order_kernel(const uint32_t *c
     s_hist[4 * t] = before; s_hist[4 * t + 1] = before + h0; s_hist[4 * t + 2] = before + h0 + h1; s_hist[4 * t + 3] = before + h0 + h1 + h2;
     __syncthreads();
     uint32_t *const mine = order + (size_t)x * per;
+    spl_fused_slot *const mine_slots = slots + (size_t)x * per; // (the fused kernel's descriptors go where their chunks go)
     for (uint32_t e = t; e < per; e += 1024u) {
         const uint32_t j = chunk_of(e);
-        if (j < n) mine[atomicAdd(&s_hist[key_of(cost[j])], 1u)] = j;
+        if (j < n) {
+            const uint32_t dst = atomicAdd(&s_hist[key_of(cost[j])], 1u);
+            mine[dst] = j;
+            const uint4 *from = (const uint4 *)(by_chunk + j);
+            uint4 *to = (uint4 *)(mine_slots + dst);
+            const uint4 a = from[0], b = from[1], c = from[2], d = from[3];
+            to[0] = a; to[1] = b; to[2] = c; to[3] = d;
+        }
     }
-    for (uint32_t s = total + t; s < per; s += 1024u) mine[s] = 0xffffffffu;
+    for (uint32_t s = total + t; s < per; s += 1024u) {
+        mine[s] = 0xffffffffu;
+        uint4 *to = (uint4 *)(mine_slots + s);
+        to[0] = make_uint4(0u, 0u, SPL_SLOT_EMPTY, 0u); // (lo, lo, chunk, n)
+        to[1] = to[2] = to[3] = make_uint4(0u, 0u, 0u, 0u);
+    }
 }
 
 extern "C" int spl_dev_launch_layout_map(const spl_devreads *src, const spl_layout_seg *segs, uint32_t n_segs, uint32_t n_chunks, uint32_t chunk, spl_layout_chunk *chunks,
-                                         uint32_t *cost, void *stream)
+                                         uint32_t *cost, spl_fused_slot *by_chunk, void *stream)
 {
     if (!n_segs || !n_chunks) return 0;
-    hipLaunchKernelGGL(spl_layout_map_kernel, dim3((n_chunks + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, *src, segs, n_segs, n_chunks, chunk, chunks, cost);
+    hipLaunchKernelGGL(spl_layout_map_kernel, dim3((n_chunks + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, *src, segs, n_segs, n_chunks, chunk, chunks, cost, by_chunk);
     return (int)hipGetLastError();
 }
 
@@ -139,10 +167,11 @@ extern "C" int spl_dev_launch_layout(const spl_layout_params *p, uint32_t n_dev_
     return (int)hipGetLastError();
 }
 
-extern "C" int spl_dev_launch_chunk_order(const uint32_t *cost, uint32_t n_chunks, uint32_t chunk, uint32_t *order, void *stream)
+extern "C" int spl_dev_launch_chunk_order(const uint32_t *cost, uint32_t n_chunks, uint32_t chunk, uint32_t *order, const spl_fused_slot *by_chunk, spl_fused_slot *slots,
+                                          void *stream)
 {
     if (!n_chunks) return 0;
     (void)chunk; // (the map kernel's estimate, (3 ops + reads) / 2, has no bound of its own for long-read chunks: the order kernel's key_of clamps it to its 4096 keys)
-    hipLaunchKernelGGL(spl_chunk_order_kernel, dim3(8), dim3(1024), 0, (hipStream_t)stream, cost, n_chunks, spl_order_per(n_chunks), order);
+    hipLaunchKernelGGL(spl_chunk_order_kernel, dim3(8), dim3(1024), 0, (hipStream_t)stream, cost, n_chunks, spl_order_per(n_chunks), order, by_chunk, slots);
     return (int)hipGetLastError();
 }

@@ -500,9 +500,28 @@ struct SimpleInPlace {
     static constexpr bool in_place = true;
     const spl_hot_params &p;
     spl_lds_i32 *lds;
-    int32_t wbase, shift;
+    int32_t &wbase;        // the caller's window base: resolved here (staged) on the chunk's first tile, see below
+    int32_t shift;
     bool active;           // (workgroup-uniform)
+    // The bucket entry of the chunk's first POS - 1 (x_first) is asked for right behind the first tile's reads (ask_base: a scalar
+    // load -- the position index is read-only for the kernel's lifetime -- so nothing waits for it there and no vector register
+    // holds it), and resolved behind the barrier that follows the tile's stage, the first point that needs wbase (staged).
+    bool &wbase_pending;   // (workgroup-uniform)
+    const int32_t x_first;
+    uint32_t first_first = 0, first_occ = 0;
     spl_dbk e0[R], e1[R];  // (all that is kept from issue to commit: the record's words are the caller's, and still there)
+    __device__ __forceinline__ void ask_base()
+    {
+        if (wbase_pending) {
+            typedef __attribute__((address_space(4))) const uint32_t spl_cdw;
+            spl_cdw *const q = (spl_cdw *)((__attribute__((address_space(4))) const char *)(uintptr_t)p.dbucket + (size_t)dbk_slot(p, x_first) * sizeof(spl_dbk));
+            first_first = q[0]; first_occ = q[1];
+        }
+    }
+    __device__ __forceinline__ void staged()
+    {
+        if (wbase_pending) { uint32_t nv; dbk_resolve(p, x_first, spl_dbk{first_first, first_occ, 0u}, wbase, nv); wbase_pending = false; }
+    }
     __device__ __forceinline__ void issue(int j, bool is_simple, uint32_t w0, uint32_t w1)
     {
         if (!active || !__any(is_simple)) return; // (wave-uniform: a wave without a simple read in its slots j asks for nothing)
@@ -738,6 +757,12 @@ __device__ __forceinline__ bool rivals_inline2(const spl_hot_params &p, spl_lds_
 // global arrays either way).  0.858 ms a launch against 0.882 (profiles/r08B_before_after.txt); at four workgroups a CU the same
 // code is slower than the kernel it replaces (0.982 ms: profiles/experiments/r08_fused_four_workgroups.txt), and five workgroups
 // fetch 9 % more from HBM than four did (more chunks alive in one L2): 2.215 GB a launch.
+// Round 13: the workgroup's uniform state.  One 64-byte descriptor per slot of the grid (spl_fused_slot, spl_devpack.h) is all the
+// prologue loads -- the chunk order, the chunk's cell, the CIGAR offsets at its tile boundaries and its first POS were three
+// dependent trips in front of the first tile's reads --, the descriptor and the argument block are read where they are used
+// (slot_here, params_here) instead of being held, spilled, across the tile loop, and the window's base is asked for behind the first
+// tile's loads: 13-19 spilled SGPRs against 57-65, none reloaded in a tile's straight-line blocks; 0.798 ms a launch against 0.850
+// (profiles/r13_before_after.txt, r13_uniform_state.txt).
 // History (round 5, records of all reads in LDS, 100 M reads a launch): 0.94-0.98 ms against 0.655-0.67 + 0.375-0.39 for layout +
 // range; asking for the next tile's reads before this tile is counted gained nothing (a wave's memory operations return in
 // order: the first bucket entry waits for them), 512 threads -- two reads each, eight waves counting a tile -- took 1.25 ms: profiles/r05X_fused_pass.txt.
@@ -747,8 +772,30 @@ __device__ __forceinline__ bool rivals_inline2(const spl_hot_params &p, spl_lds_
 // shift and two ballots per key) needs a few more registers than that cap allows and was never faster, not even at 8000
 // reads per site: profiles/r02g_lds_conflicts_*.txt.
 template <bool STRANDED, bool BIG, bool FUSED>
-__global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__((amdgpu_waves_per_eu(FUSED ? 5 : 8, 8))) void spl_count_ranges_kernel(const spl_hot_params p)
+__global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__((amdgpu_waves_per_eu(FUSED ? 5 : 8, 8))) void spl_count_ranges_kernel(const spl_hot_params p_in)
 {
+    // FUSED: the argument block is read WHERE its members are used -- `p` is made anew (params_here: scalar loads from the kernel's
+    // argument segment through a pointer the compiler cannot see through) in front of every stage of a tile, so that no member
+    // lives longer than the stage that uses it.  Read once at the kernel's entry, the block's fifty scalar registers were held
+    // across the tile loop at the price of a spill each: a VALU lane write at the entry and a lane read, with its hazard
+    // fillers, at every use -- in the blocks that hold a tile's loads, the classification and every run loop's iteration.  A
+    // scalar load from the argument segment costs no VALU instruction.
+    spl_hot_params p = p_in;
+    [[maybe_unused]] auto params_here = [&]() {
+        if constexpr (FUSED) {
+            typedef __attribute__((address_space(4))) const spl_hot_params spl_cparams;
+            uint64_t a = (uint64_t)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr(); // (the kernel's one argument lies at its start)
+            asm volatile("" : "+s"(a));
+            spl_cparams *const c = (spl_cparams *)a;
+            p.n_chunks = c->n_chunks; p.chunk_shift = c->chunk_shift; p.chunk_meta = c->chunk_meta; p.chunk_order = c->chunk_order; p.part_pos = c->part_pos;
+            p.dbucket = c->dbucket; p.n_dbuckets = c->n_dbuckets; p.dbase = c->dbase; p.n_dpos = c->n_dpos; p.stranded = c->stranded;
+            p.diff = c->diff; p.diff_stride = c->diff_stride; p.jhash = c->jhash; p.jhash_mask = c->jhash_mask; p.jrivals = c->jrivals;
+            p.dbl = c->dbl; p.combine_mode = c->combine_mode; p.queue = c->queue; p.queue_n = c->queue_n; p.queue_cap = c->queue_cap; p.err = c->err;
+            p.cells = c->cells; p.slots = c->slots;
+            p.src.pos = c->src.pos; p.src.flag = c->src.flag; p.src.cig_off = c->src.cig_off; p.src.cigar = c->src.cigar;
+            p.src_n_rec = c->src_n_rec; p.src_n_ops = c->src_n_ops;
+        }
+    };
     constexpr int NARR = STRANDED ? 4 : 2; // {beta1, ME} x {read strand +, -}
     constexpr int WIN = STRANDED ? (FUSED ? SPL_WIN_STRANDED_FUSED : SPL_WIN_STRANDED) : SPL_WIN;
     __shared__ int32_t lds_words[NARR * (WIN + 1)];
@@ -794,8 +841,21 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     // (Measured and not kept, round 4: workgroups that STAY and take chunk after chunk of their XCD's share from a counter, as
     // many as the chip holds -- to fill the eighth of the workgroup slots that stand empty between a workgroup's end and its
     // successor's first records: 0.443 ms a launch against 0.39, with ten registers in scratch for the loop around the body.)
+    // FUSED: everything uniform a workgroup needs of its chunk is its slot's descriptor (spl_fused_slot, 64 bytes in slot order:
+    // one scalar load, no trip through chunk_order, cells and the arrays), and it is read WHERE it is used -- through a pointer
+    // the compiler cannot see through, so that a tile's boundaries or the chunk's first index are sixteen words of the scalar
+    // cache away and not scalar registers held, and spilled to VGPR lanes, across everything the tile loop holds besides.
     const uint32_t chunk_slot = my_chunk();
-    const uint32_t ordered = chunk_slot < p.n_chunks ? p.chunk_order[chunk_slot] : 0xffffffffu; // (p.n_chunks: the SLOTS; a share's last ones may be empty)
+    typedef __attribute__((address_space(4))) const spl_fused_slot spl_cslot;
+    auto slot_here = [&]() {
+        uint64_t a = (uint64_t)(uintptr_t)(p.slots + chunk_slot);
+        asm volatile("" : "+s"(a));
+        return (spl_cslot *)a;
+    };
+    uint32_t ordered = 0xffffffffu;
+    if (chunk_slot < p.n_chunks) { // (p.n_chunks: the SLOTS; a share's last ones may be empty)
+        if constexpr (FUSED) ordered = slot_here()->chunk; else ordered = p.chunk_order[chunk_slot];
+    }
     const bool live = ordered != 0xffffffffu;
     const uint32_t chunk = live ? ordered : 0u;
     // A segment holds what a wave lists in all but pathological chunks (SEG entries for the ~1000 reads a wave walks; simple reads
@@ -838,45 +898,41 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     auto dbk2 = [&](uint32_t s) { spl_gdw *q = dbk_at(s); spl_dbk e; e.first = q[0]; e.occ = q[1]; e.rival = 0u; return e; };
     auto dbk3 = [&](uint32_t s) { spl_gdw *q = dbk_at(s); spl_dbk e; e.first = q[0]; e.occ = q[1]; e.rival = q[2]; return e; };
     // ---- FUSED: the chunk's tiles.  Tile k is the part [lo, hi) of the chunk in cell [g0 + k TILE, + TILE) of the arrays' indexes.
-    spl_layout_chunk ch;
+    // The part of tile k's cell the chunk has, relative to the cell, and its ops: the boundaries' offsets are the descriptor's
+    // (ob[k], ob[k + 1]: a scalar load with a uniform index).
     uint32_t tile = 0, tile_last = 0;
-    uint32_t ob[TILES + 1]; // cig_off at the tiles' boundaries
+    static_assert(!FUSED || TILES <= SPL_FUSED_TILES_MAX, "the descriptor's boundaries");
     auto span_of = [&](uint32_t k) {
-        const int64_t g0 = ch.lo & ~(int64_t)((1u << CSHIFT) - 1u), hi = ch.lo + ch.n;
+        spl_cslot *const d = slot_here();
+        const uint32_t first_r = (uint32_t)d->lo & ((1u << CSHIFT) - 1u), end_r = first_r + d->n; // the chunk's reads, from the chunk's cell (of 1 << CSHIFT reads) on
+        const uint32_t t0 = k * TILE;
         spllay::TileSpan sp;
-        sp.cell0 = g0 + (int64_t)k * TILE;
-        sp.lo = sp.cell0 > ch.lo ? sp.cell0 : ch.lo;
-        sp.hi = sp.cell0 + TILE < hi ? sp.cell0 + TILE : hi;
-        uint32_t a = ob[0], b = ob[1];
-#pragma unroll
-        for (uint32_t q = 1; q < TILES; ++q) { a = k == q ? ob[q] : a; b = k == q ? ob[q + 1] : b; }
-        sp.o_lo = a; sp.o_hi = b; sp.o_fetch_hi = ch.o_hi; sp.seg_op0 = ch.seg_op0;
+        sp.cell0 = (d->lo & ~(int64_t)((1u << CSHIFT) - 1u)) + (int64_t)t0;
+        sp.lo_r = first_r > t0 ? first_r - t0 : 0u;
+        sp.hi_r = end_r - t0 < TILE ? end_r - t0 : TILE; // (end_r > t0: k <= tile_last)
+        sp.o_lo = d->ob[k]; sp.o_hi = d->ob[k + 1u]; sp.o_fetch_hi = d->ob[TILES]; sp.seg_op0 = d->seg_op0;
         return sp;
     };
+    bool wbase_pending = FUSED; // (the window's base: asked for behind the first tile's reads, resolved behind that tile's stage -- SimpleInPlace)
     if constexpr (FUSED) {
         if (!live) return; // (the whole workgroup: before any barrier)
-        ch = p.cells[chunk];
-        const int64_t g0 = ch.lo & ~(int64_t)((1u << CSHIFT) - 1u), hi = ch.lo + ch.n;
-        tile = (uint32_t)((ch.lo - g0) >> SPL_TILE_FUSED_SHIFT);
-        tile_last = (uint32_t)((hi - 1 - g0) >> SPL_TILE_FUSED_SHIFT);
-        // (the window's base: the bucket entry of the chunk's first POS is asked for now, beside the arrays)
-        const int32_t fp0 = p.src.pos[ch.lo] + ch.shift;
-        const spl_dbk e_first = p.dbucket[dbk_slot(p, fp0 - 1)];
-#pragma unroll
-        for (uint32_t q = 0; q <= TILES; ++q) {
-            int64_t i = g0 + (int64_t)q * TILE;
-            i = i < ch.lo ? ch.lo : (i > hi ? hi : i);
-            ob[q] = q == 0u ? ch.o_lo : (q == TILES ? ch.o_hi : p.src.cig_off[i]);
-        }
-        for (int j = tid; j < NARR * (WIN + 1); j += BLOCK) lds[j] = 0; // (a barrier lies between this and the first count: tile_finish's first, behind the ops' stage)
+        spl_cslot *const d = slot_here();
+        const uint32_t first_r = (uint32_t)d->lo & ((1u << CSHIFT) - 1u);
+        tile = first_r >> SPL_TILE_FUSED_SHIFT;
+        tile_last = (first_r + d->n - 1u) >> SPL_TILE_FUSED_SHIFT;
         cv.rec = nullptr;
-        cv.wide = (spl_gu32 *)(p.src.cigar + ch.seg_op0);
-        cv.shift = ch.shift;
-        cv.first_pos = fp0 - ch.shift;
-        { uint32_t nv; dbk_resolve(p, fp0 - 1, e_first, wbase, nv); }
+        cv.wide = nullptr; // (the segment's ops: made where a WIDE read is walked, from the descriptor)
+        cv.shift = d->shift;
+        cv.first_pos = 0; // (the descriptor's pos0, read where the window's base is asked for)
+        for (int j = tid; j < NARR * (WIN + 1); j += BLOCK) lds[j] = 0; // (a barrier lies between this and the first count: tile_finish's first, behind the ops' stage)
     } else {
         cv = chunk_view(p.chunk_meta + chunk);
     }
+    // the ops of the chunk's segment, where a WIDE read's index counts from (FUSED: a place in the arrays, from the descriptor)
+    auto wide_ops = [&]() {
+        if constexpr (FUSED) return (spl_gu32 *)(p.src.cigar + slot_here()->seg_op0);
+        else return cv.wide;
+    };
     // a record's 16 / 8 bytes at a byte offset of the chunk's record area
     typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
     auto ld_r4 = [&](uint32_t at) {
@@ -890,6 +946,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     uint32_t half = 0; // FUSED: 0 = the tile in one piece; 1, 2 = its halves, one after the other (their simple reads are counted already)
     for (;;) { // the chunk's tiles (FUSED), or the chunk in one piece
     if constexpr (FUSED) {
+        params_here();
         // The simple reads are counted by tile_finish itself, where they are classified; the records of the tile's other reads go
         // to s_rec.  A tile whose records do not fit there (long reads, spliced reads throughout: rare in every workload) comes
         // back with its simple reads counted and nothing written, and is laid out again half by half -- reads [lo, mid), then
@@ -897,17 +954,18 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         lane = spllay::thread_here() & 63u; // (what the loops below make of it is made per tile, not kept from before the first one)
         spllay::TileSpan sp = span_of(tile);
         if (half) {
-            int64_t mid = sp.cell0 + (int64_t)(TILE / 2u);
-            mid = mid < sp.lo ? sp.lo : (mid > sp.hi ? sp.hi : mid);
-            const uint32_t o_mid = p.src.cig_off[mid];
-            if (half == 1u) { sp.hi = mid; sp.o_hi = o_mid; } else { sp.lo = mid; sp.o_lo = o_mid; }
+            uint32_t mid = TILE / 2u;
+            mid = mid < sp.lo_r ? sp.lo_r : (mid > sp.hi_r ? sp.hi_r : mid);
+            const uint32_t o_mid = p.src.cig_off[sp.cell0 + (int64_t)mid];
+            if (half == 1u) { sp.hi_r = mid; sp.o_hi = o_mid; } else { sp.lo_r = mid; sp.o_lo = o_mid; }
         }
         uint32_t n[4] = {0, 0, 0, 0};
         bool fits = true;
-        if (sp.hi > sp.lo) { // (uniform; half a tile may be empty)
-            SimpleInPlace<STRANDED, NARR, WIN, RPT> simple{p, lds, wbase, ch.shift, half == 0u};
+        if (sp.hi_r > sp.lo_r) { // (uniform; half a tile may be empty)
+            SimpleInPlace<STRANDED, NARR, WIN, RPT> simple{p, lds, wbase, cv.shift, half == 0u, wbase_pending, wbase_pending ? slot_here()->pos0 + cv.shift - 1 : 0};
             spllay::TileLoads<(int)TILE, RPT> L;
             spllay::tile_issue<(int)TILE, RPT>(p.src, p.src_n_rec, p.src_n_ops, sp, L);
+            simple.ask_base();
             fits = spllay::tile_finish<(int)TILE, RPT>(p.src, p.src_n_ops, sp, L, (spllay::lay_lds_w32 *)s_rec, (spllay::lay_lds_w32 *)s_lay,
                                                        spllay::RecordsInLds{(spllay::lay_lds_u8 *)s_rec, (spllay::lay_lds_u16 *)s_idx, tile * TILE}, simple, n, REC_ROOM);
         }
@@ -918,6 +976,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         cv.off[2] = n[1] * SPL_REC_MNM;
         cv.off[3] = cv.off[2] + n[2] * SPL_REC_M2;
         __syncthreads(); // the tile's records are there
+        params_here();
     }
     // Wave-iterations of the chunk.  A wave-iteration takes 64 * K consecutive reads of ONE run, K per lane: K = 4 for simple reads
     // (32 bytes of records per lane), 2 for once-spliced ones (32 bytes), 1 for the rest (24 bytes).  Run r has iters[r]
@@ -1075,6 +1134,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         }
         // ---- twice-spliced reads (aligned, N, aligned, N, aligned; the record holds the five lengths): six boundaries,
         //      five ranges.  One read per lane.
+        params_here();
         for (; g < g_start[3]; g += NWAVE) {
             take(g_start[2], cv.start[3] - cv.start[2], cv.off[2], SPL_REC_M2, 1u);
             const uint32_t i0 = cu_i0;
@@ -1122,6 +1182,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
                 push_back(flagged && !p.combine_mode, slot | (fl1 << 14) | (fl2 << 15)); // which junction must be in the table
             }
         }
+        params_here();
         for (; g < g_total; g += NWAVE) {
             take(g_start[3], cv.start[4] - cv.start[3], cv.off[3], SPL_REC_OTHER, 1u);
             const uint32_t i0 = cu_i0;
@@ -1191,7 +1252,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
                 if (!__any(more)) break;
                 mine = more;
 #pragma unroll
-                for (int k = 0; k < SPL_INLINE_OPS; ++k) op[k] = (more && k_next + (uint32_t)k < n_ops) ? cv.wide[o0 + k_next + (uint32_t)k] : 0xfu;
+                for (int k = 0; k < SPL_INLINE_OPS; ++k) op[k] = (more && k_next + (uint32_t)k < n_ops) ? wide_ops()[o0 + k_next + (uint32_t)k] : 0xfu;
                 k_next += (uint32_t)SPL_INLINE_OPS;
             }
             fetch_next(); // (this path asks late: its batches of bucket entries need the registers, and it is the rare one)
@@ -1201,6 +1262,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
             const bool flagged = !literal && alive && rival;
             if (__any(literal || flagged)) push_front(literal || flagged, slot);
         }
+        params_here();
         // Once- and twice-spliced reads with rivals, the wave's own, lanes dense: the junction table says which sites of the read's
         // window are affected and how (rivals_inline); what it cannot decide joins the literal list.  The list is read
         // from its growing end, so the front list can only ever grow into entries that are done with.
@@ -1230,6 +1292,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         }
         // Once-spliced reads with rivals: the run once more, for the lanes that marked a read of theirs (fm_mnm).  An iteration's
         // records are asked for while the one before is worked on; what an iteration then waits for is its reads' table slots.
+        params_here();
         if (__any(fm_mnm != 0u)) {
             const uint32_t n_run = cv.start[2] - cv.start[1];
             auto fetch_mnm = [&](uint32_t g2) {
@@ -1297,6 +1360,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         __syncthreads(); // everybody is through with the tile's records: the next tile's ops take their place
     }
     } // tiles
+    params_here();
     if constexpr (FUSED) tid = (int)spllay::thread_here(); // (likewise: the hand-over's places are made here, not in front of the tiles)
     if ((tid & 63) == 0) s_qcnt[tid >> 6] = n_front;
     __syncthreads();

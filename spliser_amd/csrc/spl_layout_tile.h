@@ -92,7 +92,8 @@ struct SimpleAsRecords { static constexpr bool in_place = false; };
 // the registers it stands in, and has no record at all: in_place = true,
 //   issue(j, is_simple, w0, w1)   asks for what counting the thread's read j needs (its record's two words), right behind the
 //                                 classification: the answers are on their way while the other runs are ranked;
-//   commit(j, is_simple, w0, w1)  counts it, behind the ranks' barrier and the other runs' records (all lanes of a wave together).
+//   commit(j, is_simple, w0, w1)  counts it, behind the ranks' barrier and the other runs' records (all lanes of a wave together);
+//   staged()                      is called once a tile behind the barrier that follows the ops' stage, before any issue().
 // Runs 1 .. 3 then begin at offset 0 of the sink, n[0] comes back 0 and the sink's index counts from 0.
 
 // One tile of C reads -- the cell [cell0, cell0 + C) of the arrays' indexes, or the part [lo, hi) of it a segment has -- by a
@@ -104,7 +105,25 @@ struct SimpleAsRecords { static constexpr bool in_place = false; };
 //                -> false, and no record written, when the records take more than `room` bytes (the caller takes the tile in parts).
 // n[r] = reads of run r; the runs begin at 0, align16(8 n0), + 16 n1, + 24 n2 (chunk_view's arithmetic).  With simple reads
 // counted in place (Simple::in_place) run 0 has no records: n[0] comes back 0 and runs 1 .. 3 begin at 0, + 16 n1, + 24 n2.
-struct TileSpan { int64_t cell0, lo, hi; uint32_t o_lo, o_hi, o_fetch_hi, seg_op0; }; // (o_fetch_hi >= o_hi: how far tile_issue may read ops)
+// A thread's places are 32-bit and relative: reads count from the cell's first (lo_r, hi_r: the part of the cell), ops from the
+// window's first word.  The cell's and the window's base addresses are uniform -- made once a tile on the scalar side -- and every
+// load is "scalar base + 32-bit lane offset"; a 64-bit index per lane was a v_lshl_add_u64 per load and a 64-bit compare per guard.
+struct TileSpan { int64_t cell0; uint32_t lo_r, hi_r; uint32_t o_lo, o_hi, o_fetch_hi, seg_op0; }; // (o_fetch_hi >= o_hi: how far tile_issue may read ops)
+typedef __attribute__((address_space(1))) const char lay_gchar; // (global, typed: see lay_lds_w32)
+template <class V>
+__device__ __forceinline__ V ld_at(lay_gchar *base, uint32_t byte_off) { return *(__attribute__((address_space(1))) const V *)(base + (size_t)byte_off); }
+// words [rel, rel + 4) of the window that begins at `win`, of which n_win exist in the array (n_win >= rel + 1)
+__device__ __forceinline__ lay_u32x4 ld_ops_quad(lay_gchar *win, uint32_t rel, uint32_t n_win)
+{
+    lay_u32x4 v = lay_u32x4{0u, 0u, 0u, 0u};
+    if (rel + 4u <= n_win) v = ld_at<lay_u32x4>(win, 4u * rel);
+    else {
+        v.x = ld_at<uint32_t>(win, 4u * rel);
+        if (rel + 1u < n_win) v.y = ld_at<uint32_t>(win, 4u * rel + 4u);
+        if (rel + 2u < n_win) v.z = ld_at<uint32_t>(win, 4u * rel + 8u);
+    }
+    return v;
+}
 template <int C, int R>   // R = reads a thread: 4 (a workgroup of C / 4 threads) or 2 (C / 2)
 struct TileLoads {
     int32_t pos[R];
@@ -120,33 +139,48 @@ __device__ __forceinline__ void tile_issue(const spl_devreads &src, int64_t n_re
     constexpr uint32_t T = C / R, STAGE = 4 * C;
     static_assert(STAGE / (4 * T) == R, "R quads of ops a thread");
     const uint32_t t = thread_here();
-    const int64_t g = sp.cell0 + R * (int64_t)t; // the thread's first read
+    lay_gchar *const pos_c = (lay_gchar *)(src.pos + sp.cell0), *const flag_c = (lay_gchar *)(src.flag + sp.cell0), *const co_c = (lay_gchar *)(src.cig_off + sp.cell0); // the cell's (uniform)
 #pragma unroll
     for (int j = 0; j < R; ++j) L.pos[j] = 0;
 #pragma unroll
     for (int j = 0; j <= R; ++j) L.co[j] = 0;
 #pragma unroll
     for (int j = 0; j < R / 2; ++j) L.fw[j] = 0;
+    // The ops FIRST: the reads' loads below end in a branch whose arms are joined through register moves, which wait for what they
+    // move -- behind the ops' loads that wait covers one trip with everything in flight; in front of them it was a trip of its own.
+    // (the window [ws, ws + STAGE) of the ops: what of it may be read -- up to o_fetch_hi -- and what of it the array has, both
+    //  counted from ws: ws <= o_lo <= o_fetch_hi <= n_ops)
+    const uint32_t ws = sp.o_lo & ~3u;
+    lay_gchar *const win = (lay_gchar *)(src.cigar + ws);
+    const uint32_t end_r = sp.o_fetch_hi - ws < STAGE ? sp.o_fetch_hi - ws : STAGE;
+    const int64_t ops_left = n_ops - (int64_t)ws;
+    const uint32_t n_win = ops_left < (int64_t)(STAGE + 4u) ? (uint32_t)ops_left : STAGE + 4u;
+#pragma unroll
+    for (uint32_t q = 0; q < (uint32_t)R; ++q) {
+        const uint32_t rel = 4u * (t + q * T);
+        L.v[q] = lay_u32x4{0u, 0u, 0u, 0u};
+        if (rel < end_r) L.v[q] = ld_ops_quad(win, rel, n_win);
+    }
     // (places in the cell are 32-bit: the span's bounds relative to the cell are uniform, a thread's reads R t .. R t + R - 1)
-    const uint32_t r0 = (uint32_t)R * t, lo_r = (uint32_t)(sp.lo - sp.cell0), hi_r = (uint32_t)(sp.hi - sp.cell0);
+    const uint32_t r0 = (uint32_t)R * t, lo_r = sp.lo_r, hi_r = sp.hi_r;
     const int64_t left = n_rec - sp.cell0;
     const uint32_t rec_r = left < (int64_t)C ? (uint32_t)left : (uint32_t)C; // reads the arrays have from the cell's first on, at most C
     const bool mine = r0 + R > lo_r && r0 < hi_r; // (a partial cell's threads outside the segment load nothing)
     if (mine) {
         if (r0 + R <= rec_r) {
             if constexpr (R == 4) {
-                const lay_u32x4 pv = *(const lay_u32x4 *)(src.pos + g);
-                const lay_u32x2 fv = *(const lay_u32x2 *)(src.flag + g);
-                const lay_u32x4 cv = *(const lay_u32x4 *)(src.cig_off + g);
-                L.co[4] = src.cig_off[g + 4];
+                const lay_u32x4 pv = ld_at<lay_u32x4>(pos_c, 4u * r0);
+                const lay_u32x2 fv = ld_at<lay_u32x2>(flag_c, 2u * r0);
+                const lay_u32x4 cv = ld_at<lay_u32x4>(co_c, 4u * r0);
+                L.co[4] = ld_at<uint32_t>(co_c, 4u * r0 + 16u);
                 L.pos[0] = (int32_t)pv.x; L.pos[1] = (int32_t)pv.y; L.pos[2] = (int32_t)pv.z; L.pos[3] = (int32_t)pv.w;
                 L.fw[0] = fv.x; L.fw[1] = fv.y;
                 L.co[0] = cv.x; L.co[1] = cv.y; L.co[2] = cv.z; L.co[3] = cv.w;
             } else {
-                const lay_u32x2 pv = *(const lay_u32x2 *)(src.pos + g);
-                L.fw[0] = *(const uint32_t *)(src.flag + g);
-                const lay_u32x2 cv = *(const lay_u32x2 *)(src.cig_off + g);
-                L.co[2] = src.cig_off[g + 2];
+                const lay_u32x2 pv = ld_at<lay_u32x2>(pos_c, 4u * r0);
+                L.fw[0] = ld_at<uint32_t>(flag_c, 2u * r0);
+                const lay_u32x2 cv = ld_at<lay_u32x2>(co_c, 4u * r0);
+                L.co[2] = ld_at<uint32_t>(co_c, 4u * r0 + 8u);
                 L.pos[0] = (int32_t)pv.x; L.pos[1] = (int32_t)pv.y;
                 L.co[0] = cv.x; L.co[1] = cv.y;
             }
@@ -154,28 +188,13 @@ __device__ __forceinline__ void tile_issue(const spl_devreads &src, int64_t n_re
             uint32_t f[R];
 #pragma unroll
             for (int j = 0; j < R; ++j) {
-                const int64_t i = g + j;
+                const uint32_t i = r0 + (uint32_t)j; // (< C: inside the arrays if and only if below rec_r)
                 f[j] = 0;
-                if (i < n_rec) { L.pos[j] = src.pos[i]; f[j] = src.flag[i]; L.co[j] = src.cig_off[i]; L.co[j + 1] = src.cig_off[i + 1]; }
+                if (i < rec_r) { L.pos[j] = ld_at<int32_t>(pos_c, 4u * i); f[j] = ld_at<uint16_t>(flag_c, 2u * i); L.co[j] = ld_at<uint32_t>(co_c, 4u * i); L.co[j + 1] = ld_at<uint32_t>(co_c, 4u * i + 4u); }
                 else L.co[j + 1] = L.co[j];
             }
 #pragma unroll
             for (int j = 0; j < R / 2; ++j) L.fw[j] = f[2 * j] | (f[2 * j + 1] << 16);
-        }
-    }
-    const uint64_t ws = sp.o_lo & ~3u;
-    const uint64_t o_end = (uint64_t)sp.o_fetch_hi < ws + STAGE ? (uint64_t)sp.o_fetch_hi : ws + STAGE;
-#pragma unroll
-    for (uint32_t q = 0; q < (uint32_t)R; ++q) {
-        const uint64_t at = ws + 4ull * (t + q * T);
-        L.v[q] = lay_u32x4{0u, 0u, 0u, 0u};
-        if (at < o_end) {
-            if (at + 4 <= (uint64_t)n_ops) L.v[q] = *(const lay_u32x4 *)(src.cigar + at);
-            else {
-                L.v[q].x = src.cigar[at];
-                if (at + 1 < (uint64_t)n_ops) L.v[q].y = src.cigar[at + 1];
-                if (at + 2 < (uint64_t)n_ops) L.v[q].z = src.cigar[at + 2];
-            }
         }
     }
 }
@@ -188,8 +207,7 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
     static_assert(NW <= 16, "the waves' totals are summed inside one row of lanes");
     constexpr uint32_t PAD = SPL_PACK_SCAN_OPS;               // a read is classified from a stage that holds its first eight ops
     const uint32_t t = thread_here(), lane = t & 63u, wave = t >> 6;
-    const int64_t g = sp.cell0 + R * (int64_t)t;
-    const uint32_t r0 = (uint32_t)R * t, lo_r = (uint32_t)(sp.lo - sp.cell0), hi_r = (uint32_t)(sp.hi - sp.cell0);
+    const uint32_t r0 = (uint32_t)R * t, lo_r = sp.lo_r, hi_r = sp.hi_r;
     const uint32_t o_hi = sp.o_hi, seg_op0 = sp.seg_op0;
     int32_t pos[R];
     uint32_t flag[R], co[R + 1];
@@ -200,29 +218,26 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
     // The tile's ops into LDS, 16 bytes a lane and load, a WINDOW of STAGE words at a time: one window for all but long-read
     // CIGARs (more than four ops a read on average), whose tiles take several -- a read is classified from the window that
     // holds its first eight ops (more are never looked at: such a read is WIDE, its ops stay where they are).
-    auto fill = [&](uint64_t ws) {
-        const uint64_t o_end = (uint64_t)o_hi < ws + STAGE ? (uint64_t)o_hi : ws + STAGE;
+    auto fill = [&](uint32_t ws) { // (a later window: ws < o_hi <= n_ops)
+        lay_gchar *const win = (lay_gchar *)(src.cigar + ws);
+        const uint32_t end_r = o_hi - ws < STAGE ? o_hi - ws : STAGE;
+        const int64_t ops_left = n_ops - (int64_t)ws;
+        const uint32_t n_win = ops_left < (int64_t)(STAGE + 4u) ? (uint32_t)ops_left : STAGE + 4u;
         lay_u32x4 v[R];
 #pragma unroll
         for (uint32_t q = 0; q < (uint32_t)R; ++q) {
-            const uint64_t at = ws + 4ull * (t + q * T);
+            const uint32_t rel = 4u * (t + q * T);
             v[q] = lay_u32x4{0u, 0u, 0u, 0u};
-            if (at < o_end) {
-                if (at + 4 <= (uint64_t)n_ops) v[q] = *(const lay_u32x4 *)(src.cigar + at);
-                else {
-                    v[q].x = src.cigar[at];
-                    if (at + 1 < (uint64_t)n_ops) v[q].y = src.cigar[at + 1];
-                    if (at + 2 < (uint64_t)n_ops) v[q].z = src.cigar[at + 2];
-                }
-            }
+            if (rel < end_r) v[q] = ld_ops_quad(win, rel, n_win);
         }
 #pragma unroll
         for (uint32_t q = 0; q < (uint32_t)R; ++q) *(__attribute__((address_space(3))) lay_u32x4 *)(s_ops + 4u * (t + q * T)) = v[q];
     };
-    uint64_t ws = sp.o_lo & ~3u;
+    uint32_t ws = sp.o_lo & ~3u; // (the window's first op; every comparison below is relative to it: ws <= o_hi, and ws + STAGE may pass 2^32)
 #pragma unroll
     for (uint32_t q = 0; q < (uint32_t)R; ++q) *(__attribute__((address_space(3))) lay_u32x4 *)(s_ops + 4u * (t + q * T)) = L.v[q];
     __syncthreads();
+    if constexpr (Simple::in_place) simple.staged(); // (the first point at which the caller's window base is needed: see SimpleInPlace)
 
     // ---- classify: four records in registers.  Straight-line, no branch, the four reads' chains side by side: in the fused kernel
     // the three plain shapes from the op codes alone (classify_plain), then -- a wave that has anything else -- every class of
@@ -234,7 +249,7 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const bool valid = r0 + (uint32_t)j >= lo_r && r0 + (uint32_t)j < hi_r;
-        const uint32_t rel0 = co[j] - (uint32_t)ws;
+        const uint32_t rel0 = co[j] - ws;
         const bool inside = rel0 + PAD <= STAGE;
         lay_lds_u32 *o = (lay_lds_u32 *)s_ops + (inside ? rel0 : 0u);
         splrec::Rec r;
@@ -254,7 +269,7 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
     if (Sink::clip_tier && __any(pend != 0u)) {
 #pragma unroll
         for (int j = 0; j < R; ++j) {
-            const uint32_t rel0 = co[j] - (uint32_t)ws;
+            const uint32_t rel0 = co[j] - ws;
             const bool inside = rel0 + PAD <= STAGE;
             splrec::Rec r;
             const bool fast = splrec::classify_clipped(pos[j], flag[j], StagedOps{(lay_lds_u32 *)s_ops + (inside ? rel0 : 0u)}, co[j + 1] - co[j], co[j] - seg_op0, r);
@@ -273,7 +288,8 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
                 if ((pend >> j) & 1u) {
                     // (the read's offsets come from memory again, its POS and flag out of the record's first words: nothing but the
                     //  records stays in registers across this branch, which most waves never take)
-                    const uint32_t c0 = src.cig_off[g + j], c1 = src.cig_off[g + j + 1], rel0 = c0 - (uint32_t)ws;
+                    lay_gchar *const co_c = (lay_gchar *)(src.cig_off + sp.cell0);
+                    const uint32_t c0 = ld_at<uint32_t>(co_c, 4u * (r0 + (uint32_t)j)), c1 = ld_at<uint32_t>(co_c, 4u * (r0 + (uint32_t)j) + 4u), rel0 = c0 - ws;
                     if (rel0 + PAD <= STAGE) {
                         splrec::Rec r;
                         splrec::classify_lean((int32_t)w[j][0], w[j][1] & 0xffffu, StagedOps{(lay_lds_u32 *)s_ops + rel0}, c1 - c0, c0 - seg_op0, r);
@@ -286,7 +302,7 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (ws + STAGE >= (uint64_t)o_hi + PAD) break; // (wave-uniform: the chunk's ops, and eight words behind them, were in this window)
+        if (o_hi - ws + PAD <= STAGE) break; // (wave-uniform: the chunk's ops, and eight words behind them, were in this window)
         ws += STAGE - PAD;
         __syncthreads();
         fill(ws);
@@ -365,12 +381,13 @@ template <int C, class Sink>
 __device__ __forceinline__ void layout_tile(const spl_devreads &src, int64_t n_rec, int64_t n_ops, const spl_layout_chunk &ch, lay_lds_w32 *s_ops,
                                             lay_lds_w32 *s_cnt, lay_lds_i32 *s_first, const Sink sink, uint32_t (&n)[4])
 {
-    const TileSpan sp{ch.lo & ~(int64_t)(C - 1), ch.lo, ch.lo + ch.n, ch.o_lo, ch.o_hi, ch.o_hi, ch.seg_op0};
+    const int64_t cell0 = ch.lo & ~(int64_t)(C - 1);
+    const TileSpan sp{cell0, (uint32_t)(ch.lo - cell0), (uint32_t)(ch.lo - cell0) + ch.n, ch.o_lo, ch.o_hi, ch.o_hi, ch.seg_op0};
     TileLoads<C, 4> L;
     tile_issue<C, 4>(src, n_rec, n_ops, sp, L);
-    const int64_t g = sp.cell0 + 4 * (int64_t)threadIdx.x;
-    if (sp.lo >= g && sp.lo < g + 4) { // (a record's first word is its read's POS, whatever its class)
-        const uint32_t e = (uint32_t)(sp.lo - g);
+    const uint32_t r0 = 4u * threadIdx.x;
+    if (sp.lo_r >= r0 && sp.lo_r < r0 + 4u) { // (a record's first word is its read's POS, whatever its class)
+        const uint32_t e = sp.lo_r - r0;
         *s_first = e == 0u ? L.pos[0] : (e == 1u ? L.pos[1] : (e == 2u ? L.pos[2] : L.pos[3]));
     }
     SimpleAsRecords as_records;
