@@ -391,11 +391,27 @@ const char *spl_bam_decline_reason(spl_bam *bam);
  * line the rule does not take is declined as a whole: the decode ends with SPL_ERR_FORMAT, spl_bam_decline_reason says
  * "line N <why>" (1-based, header lines counted), and the caller reads the file by other means (process.py: samio.read_sam, as
  * before).  A line longer than SPL_SAM_WINDOW_BYTES, its newline counted, is such a line for both decoders.  SPL_ERR_FORMAT from
- * spl_sam_open itself: gzip/BGZF data, no @SQ line, an @SQ line without SN and LN, a repeated name, a line that begins "@SQ" and
- * is no @SQ line, a carriage return in the header.  n_threads is kept and unused: the host parser is one thread.  spl_bam_share_plan, spl_bam_sample and spl_bam_compression_ratio are SPL_ERR_ARG on such a file; spl_bam_open* keep
- * refusing text.  Not read: gzip'd or BGZF-compressed SAM, CRAM, a pipe; no decode in shares.  spl_bam_is_text: 1 for such a file. */
+ * spl_sam_open itself: gzip/BGZF data that is no SAM text (a BAM, anything else), no @SQ line, an @SQ line without SN and LN, a
+ * repeated name, a line that begins "@SQ" and is no @SQ line, a carriage return in the header.  n_threads is kept and unused: the
+ * host parser is one thread.  spl_bam_share_plan, spl_bam_sample and spl_bam_compression_ratio are SPL_ERR_ARG on such a file;
+ * spl_bam_open* keep refusing text, compressed or not.  spl_bam_is_text: 1 for such a file.
+ * COMPRESSED TEXT, the form such files have on disk: a file that begins 1f 8b is taken when its inflated content is SAM text.  The
+ * host inflates as far as the header's end; line numbers and every offset are those of the inflated text.  BGZF (bgzip, samtools
+ * view -O sam: the block walk takes the whole file, EOF marker included -- without one SPL_ERR_IO, as for a BAM):
+ * spl_bam_decode_device sends the file's blocks up and inflates them there, a block per wave, in windows of whole blocks, and
+ * parses the text where it lies; the bytes behind a window's last newline are carried to the front of the next window on the
+ * device.  Plain gzip (anything else zlib takes, several members too): one host thread inflates and the text goes up to the same
+ * parser.  Every line of at most SPL_SAM_WINDOW_BYTES is taken wherever blocks and windows cut it; line numbers in a decline are
+ * the plain text's.  Without a device decode, or where it gives up (a block that does not inflate, a wrong CRC32, memory), one host
+ * thread inflates in pieces and parses, holding a line and a piece of the text at a time; damaged data ends the decode with
+ * SPL_ERR_FORMAT.  spl_bam_text_compression: 0 plain text (or no text), 1 BGZF, 2 gzip.  spl_bam_text_blocks: the BGZF blocks a
+ * device decode of the file inflated.
+ * Not read: CRAM, a pipe; no decode in shares.  (process.open_alignments sends a compressed file to spl_sam_open only when it
+ * inflates to an '@': compressed text without a header is not read by the commands.) */
 int spl_sam_open(const char *path, int n_threads, spl_bam **out);
 int spl_bam_is_text(const spl_bam *bam);
+int spl_bam_text_compression(const spl_bam *bam);
+int64_t spl_bam_text_blocks(const spl_bam *bam);
 void spl_bam_close(spl_bam *bam);
 int spl_bam_n_ref(const spl_bam *bam);
 const char *spl_bam_ref_name(const spl_bam *bam, int tid);

@@ -23,6 +23,10 @@ verdict had been typed: ``--isStranded -s fr``, ``--isStranded -s rf``, or neith
 writes that tally and the verdict alone (what the reference's README has the user find out in IGV).
 ``--anyOrder`` (``process``, ``junctions``, ``flagstat``, ``strandedness``; changes no result): the BAM may be in any record order, e.g. the aligner's
 own output -- its reads are coordinate-sorted on the GPU after the decode instead of by ``samtools sort`` beforehand.
+``-B`` (every command that has it) also takes SAM text as the aligner writes it, and that text compressed -- BGZF (``bgzip``,
+``samtools view -O sam``) or gzip (``aligner | gzip``): what the file inflates to says which, no flag.  The text is parsed on the GPU;
+BGZF is inflated there too, plain gzip by one host thread; a file the strict rule declines is read by the Python reader.
+Not read: CRAM, a pipe, and compressed text that has no ``@`` header line (uncompressed, the Python reader still takes that).
 """
 import argparse
 import sys
@@ -35,7 +39,7 @@ def build_parser():
     parser = argparse.ArgumentParser(description="SpliSER - Splice Site Strength Estimates from RNA-seq (MI355X build)")
     sub = parser.add_subparsers(dest="command")
     p = sub.add_parser("process")
-    p.add_argument("-B", "--BAMFile", dest="inBAM", required=True, help="The mapped RNA-seq file in BAM format")
+    p.add_argument("-B", "--BAMFile", dest="inBAM", required=True, help="The mapped RNA-seq file in BAM format (this build: or SAM text, plain or compressed as BGZF or gzip; compressed text needs its @ header)")
     p.add_argument("-b", "--bedFile", dest="inBed", required=False, default=None,
                    help="The Tophat-style splice junction bed file; (this build only) without it the junctions are taken from the BAM "
                         "itself, in the same pass: what `junctions` followed by `process -b` writes, from one command and one decode")

@@ -39,6 +39,7 @@
 #include "spl_bam_aux.h"
 #include "spl_flagstat.h"
 #include "spl_sam_line.h"
+#include "spl_sam_zhost.h"
 static_assert(SPL_BAM_N_FSTAT == 2 * SPL_FS_CATEGORIES, "spl_bam_totals::fstat holds every flagstat counter");
 #include "spl_error.h"
 
@@ -516,7 +517,9 @@ struct spl_bam {
     std::string decline_reason; // why the device decoder handed the file to the host threads, if it did
     // ---- SAM text (spl_sam_open): where the alignment lines begin, the header lines in front of them, the names' look-up table
     bool is_text = false;
-    uint64_t text_begin = 0, header_lines = 0;
+    int text_z = 0;             // SPL_TEXT_*: plain text, BGZF (the block directory is walked when the file is opened) or plain gzip
+    uint64_t text_begin = 0, header_lines = 0; // (text_begin: in the inflated stream, for a compressed file)
+    std::atomic<int64_t> text_blocks{0};       // BGZF blocks a device decoder has inflated (spl_bam_text_blocks)
     std::vector<uint32_t> sam_slots, sam_name_off;
     std::vector<uint8_t> sam_blob;
     ~spl_bam();
@@ -2376,6 +2379,9 @@ extern "C" int spl_bam_write(const char *path, int n_ref, const char *const *ref
 // or, where it cannot (no device memory, a HIP error) or nobody asked it to, by sam_host_worker below -- the same rule, line by
 // line (spl_sam_line.h), the same arrays and counters.  Replaces `samtools view -b` in front of the BAM decoder.
 extern "C" int spl_bam_is_text(const spl_bam *bam) { return bam && bam->is_text ? 1 : 0; }
+extern "C" int spl_bam_text_compression(const spl_bam *bam) { return bam && bam->is_text ? bam->text_z : 0; }
+extern "C" int64_t spl_bam_text_blocks(const spl_bam *bam) { return bam ? bam->text_blocks.load() : 0; }
+void spl_bam_note_text_blocks(spl_bam *bam, int64_t n) { bam->text_blocks.store(n); }
 
 bool spl_bam_text(const spl_bam *bam, uint64_t *begin_out, uint64_t *header_lines_out, spl_sam_names *names_out, size_t *blob_bytes_out)
 {
@@ -2416,7 +2422,7 @@ extern "C" int spl_sam_open(const char *path, int n_threads, spl_bam **out)
     struct FdGuard { int fd; ~FdGuard() { if (fd >= 0) close(fd); } } fd_guard{fd};
     struct stat st;
     if (fstat(fd, &st) != 0 || st.st_size <= 0) return spl_set_error(SPL_ERR_IO, "cannot stat %s (or empty file)", path);
-    const size_t fsize = (size_t)st.st_size;
+    size_t fsize = (size_t)st.st_size;
     void *map = mmap(nullptr, fsize, PROT_READ, MAP_PRIVATE, fd, 0);
     if (map == MAP_FAILED) return spl_set_error(SPL_ERR_IO, "mmap failed for %s", path);
     madvise(map, fsize, MADV_SEQUENTIAL);
@@ -2431,9 +2437,34 @@ extern "C" int spl_sam_open(const char *path, int n_threads, spl_bam **out)
     bam->opts.any_order = true; // (the Python reader takes the lines in any order: so do this file's decoders)
     if (n_threads <= 0) n_threads = (int)std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
     bam->n_threads = n_threads;
-    const uint8_t *file = (const uint8_t *)map;
     auto refuse = [&](const char *why) { delete bam; return spl_set_error(SPL_ERR_FORMAT, "%s: %s", path, why); };
-    if (fsize >= 2 && file[0] == 0x1f && file[1] == 0x8b) return refuse("gzip or BGZF data, not SAM text (spl_bam_open reads BAM; compressed SAM is not read)");
+    // Compressed text (gzip's magic): the host inflates from the start until the header has ended -- a line begins with something
+    // other than '@', or the data ends --, and the header is read from those bytes; every offset from here on is one in the
+    // inflated stream.  Which kind it is: BGZF when the block walk takes the whole file, plain gzip otherwise.
+    std::vector<uint8_t> head;
+    const bool packed = fsize >= 2 && ((const uint8_t *)map)[0] == 0x1f && ((const uint8_t *)map)[1] == 0x8b;
+    if (packed) {
+        splsamz::Inflater z;
+        if (!z.begin((const uint8_t *)map, fsize)) return refuse("zlib's inflate could not be started");
+        size_t seen = 0;
+        for (bool ended = false; !ended;) {
+            const size_t old = head.size(), step = 65536;
+            head.resize(old + step);
+            head.resize(old + z.read(head.data() + old, step));
+            if (head.size() >= 4 && memcmp(head.data(), "BAM\1", 4) == 0) return refuse("gzip or BGZF data that holds a BAM file, not SAM text (spl_bam_open reads BAM)");
+            while (seen < head.size() && head[seen] == '@') {
+                const uint8_t *nl = (const uint8_t *)memchr(head.data() + seen, '\n', head.size() - seen);
+                if (!nl) break;
+                seen = (size_t)(nl - head.data()) + 1;
+            }
+            if (seen < head.size() && head[seen] != '@') ended = true;
+            else if (z.status == 1) ended = true;
+            else if (z.status == -1) return refuse("gzip data that does not inflate as far as a SAM header's end (neither BAM nor SAM text)");
+        }
+    }
+    const uint8_t *const file = packed ? head.data() : (const uint8_t *)map;
+    const size_t fsize_map = fsize;
+    if (packed) fsize = head.size(); // (the header's loop below reads the inflated bytes; the mapping's size is back behind it)
     // the header: every line that begins with '@', at the top; @SQ lines give the references, in order
     size_t at = 0;
     while (at < fsize && file[at] == '@') {
@@ -2464,6 +2495,17 @@ extern "C" int spl_sam_open(const char *path, int n_threads, spl_bam **out)
         at = nl ? stop + 1 : fsize;
     }
     if (bam->ref_names.empty()) return refuse("SAM text without @SQ lines (or not SAM text)");
+    fsize = fsize_map;
+    if (packed) {
+        bam->dir.chunks.assign(fsize / 28 / BlockDir::CHUNK + 2, nullptr);
+        walk_blocks(bam->dir, (const uint8_t *)map, fsize, path, 0);
+        if (bam->dir.state.load() == 1) bam->text_z = SPL_TEXT_BGZF;
+        else if (bam->dir.err_code == SPL_ERR_IO) { // (every block walked and no EOF marker behind them: truncated, as for a BAM)
+            const std::string text = bam->dir.error;
+            delete bam;
+            return spl_set_error(SPL_ERR_IO, "%s", text.c_str());
+        } else bam->text_z = SPL_TEXT_GZIP;
+    }
     const size_t n_ref = bam->ref_names.size();
     bam->text_begin = at;
     bam->n_refs = (int)n_ref;
@@ -2503,7 +2545,6 @@ extern "C" int spl_sam_open(const char *path, int n_threads, spl_bam **out)
 static void sam_host_worker(spl_bam *bam)
 {
     const uint8_t *file = (const uint8_t *)bam->map;
-    const uint8_t *p = file + bam->text_begin, *const end = file + bam->fsize;
     const spl_bam_decode_opts opts = bam->opts;
     const spl_sam_names names = {bam->sam_slots.data(), bam->sam_name_off.data(), bam->sam_blob.data(), (uint32_t)bam->sam_slots.size(), bam->n_refs};
     const size_t n_ref = (size_t)bam->n_refs;
@@ -2527,15 +2568,14 @@ static void sam_host_worker(spl_bam *bam)
         bam->cv.notify_all();
     };
     try {
-        while (p < end) {
-            const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
-            const uint8_t *stop = nl ? nl : end;
+        // one line through the rule -> false: the decode has ended (declined, or closed)
+        auto take_line = [&](const uint8_t *p, const uint8_t *stop, bool nl) -> bool {
             ++line_no;
-            if ((line_no & 0xffffu) == 0 && bam->cancel.load(std::memory_order_acquire)) { fail("closed before it was decoded", SPL_ERR_IO); return; }
-            if ((size_t)(stop - p) + (nl ? 1u : 0u) > max_line) { spl_sam_fail(bam, line_no, SPL_SAM_LONG_LINE); return; } // (the device's windows hold no such line)
+            if ((line_no & 0xffffu) == 0 && bam->cancel.load(std::memory_order_acquire)) { fail("closed before it was decoded", SPL_ERR_IO); return false; }
+            if ((size_t)(stop - p) + (nl ? 1u : 0u) > max_line) { spl_sam_fail(bam, line_no, SPL_SAM_LONG_LINE); return false; } // (the device's windows hold no such line)
             spl_sam_line ln;
             spl_sam_parse_line(p, stop, names, last_tid, opts.filter, opts.aux_strand, &ln);
-            if (ln.reason != SPL_SAM_OK) { spl_sam_fail(bam, line_no, ln.reason); return; }
+            if (ln.reason != SPL_SAM_OK) { spl_sam_fail(bam, line_no, ln.reason); return false; }
             totals.n_records++;
             if (opts.flagstat && ln.verdict == SPL_BAM_KEPT) spl_flagstat_add(totals.fstat, ln.flag, ln.tid, ln.next_tid, ln.mapq);
             if (ln.placed && ln.verdict != SPL_BAM_KEPT) totals.dropped[ln.verdict - 1]++;
@@ -2544,7 +2584,7 @@ static void sam_host_worker(spl_bam *bam)
                 last_tid = ln.tid;
                 last_pos = ln.pos;
                 const size_t at = cigar_v.size();
-                if (at + ln.n_ops > 0xfffffff0ull || tid_v.size() >= 0xfffffff0ull) { spl_sam_fail(bam, line_no, SPL_SAM_TOO_MANY); return; }
+                if (at + ln.n_ops > 0xfffffff0ull || tid_v.size() >= 0xfffffff0ull) { spl_sam_fail(bam, line_no, SPL_SAM_TOO_MANY); return false; }
                 cigar_v.resize(at + ln.n_ops);
                 uint32_t n = 0;
                 int64_t ref_len = 0;
@@ -2557,7 +2597,24 @@ static void sam_host_worker(spl_bam *bam)
                 end_v.push_back(ln.end);
                 off_v.push_back(cigar_v.size());
             }
-            p = nl ? nl + 1 : end;
+            return true;
+        };
+        if (bam->text_z == SPL_TEXT_PLAIN) {
+            const uint8_t *p = file + bam->text_begin, *const end = file + bam->fsize;
+            while (p < end) {
+                const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
+                if (!take_line(p, nl ? nl : end, nl != nullptr)) return;
+                p = nl ? nl + 1 : end;
+            }
+        } else {
+            // a compressed file: inflated in pieces on this thread, the lines cut from the pieces with a carried partial line
+            // (spl_sam_zhost.h: one buffer of a line's length and a piece, never the file)
+            splsamz::Inflater z;
+            splsamz::Lines lines;
+            if (!z.begin(file, bam->fsize)) { fail("zlib's inflate could not be started", SPL_ERR_NOMEM); return; }
+            const int rc = lines.walk(z, bam->text_begin, max_line, take_line);
+            if (rc == 1) return; // (take_line has said why)
+            if (rc == -1) { fail("gzip data that does not inflate, or a member's CRC32 or length is wrong (corrupt or truncated file)", SPL_ERR_FORMAT); return; }
         }
         const size_t n = tid_v.size();
         std::vector<uint32_t> order(n);

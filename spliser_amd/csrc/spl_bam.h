@@ -117,6 +117,13 @@ void spl_bam_linger(spl_bam *bam, double seconds);       // a decoder with only 
 // false: the file is BGZF/BAM.  true: the alignment lines are the mapping's bytes [*begin_out, file size) (spl_bam_image), in front of
 // them `*header_lines_out` header lines; names_out: the header's reference names as the rule looks them up (host memory, the file's),
 // blob_bytes_out: the bytes of all names.  Null outputs are skipped.
+// spl_bam_text_compression's values.  A compressed file's offsets (*begin_out below) are offsets in the INFLATED stream, and its
+// mapping (spl_bam_image) holds the compressed bytes: BGZF blocks, all in the block directory (spl_bam_block_count / _get: walked
+// by spl_sam_open), or gzip members for splsamz::Inflater (spl_sam_zhost.h).
+#define SPL_TEXT_PLAIN 0
+#define SPL_TEXT_BGZF 1
+#define SPL_TEXT_GZIP 2
+void spl_bam_note_text_blocks(spl_bam *bam, int64_t n);    // the BGZF blocks a device decoder inflated (spl_bam_text_blocks)
 struct spl_sam_names;
 bool spl_bam_text(const spl_bam *bam, uint64_t *begin_out, uint64_t *header_lines_out, spl_sam_names *names_out, size_t *blob_bytes_out);
 // The rule declines the file at line `line_no` (1-based, header lines counted) for `reason` (SPL_SAM_*): the decode ends with

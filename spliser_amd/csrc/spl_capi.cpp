@@ -27,6 +27,7 @@
 #include "spl_sort.h"
 #include "spl_sam.h"
 #include "spl_sam_line.h"
+#include "spl_sam_zhost.h"
 #include "spl_flagstat.h"
 #include "spl_devpack.h"
 #include "spl_device.h"
@@ -2470,6 +2471,39 @@ static int decode_share(spl_ctx *c, spl_bam *bam, const spl_bam_share *share, Sh
     return rc == STOPPED ? SPL_OK : rc;
 }
 
+// `bytes` bytes to `dst` on the device through the context's staging ring on the copy stream, for the one thread of a call that
+// sends: take the next pinned buffer, wait while its last copy is under way, have it filled -- fill(host, room, done) -> the bytes
+// it put there, at most `room`; 0 ends the sending early --, queue the copy, record the buffer's event.  *sent_out: the bytes queued.
+namespace {
+template <class Fill> hipError_t ring_send(spl_ctx *c, char *dst, uint64_t bytes, Fill &&fill, uint64_t *sent_out = nullptr)
+{
+    hipError_t q = hipSuccess;
+    uint64_t done = 0;
+    while (done < bytes && q == hipSuccess) {
+        spl_ctx::Stage &sg = c->stage[c->stage_next];
+        c->stage_next = (c->stage_next + 1) % c->stage.size();
+        if (sg.busy) { q = hipEventSynchronize(sg.done); sg.busy = false; if (q != hipSuccess) break; }
+        const size_t n = fill(sg.host, (size_t)std::min<uint64_t>(bytes - done, sg.bytes), done);
+        if (!n) break;
+        q = hipMemcpyAsync(dst + done, sg.host, n, hipMemcpyHostToDevice, c->copy);
+        if (q == hipSuccess) { q = hipEventRecord(sg.done, c->copy); sg.busy = true; }
+        done += n;
+    }
+    if (sent_out) *sent_out = done;
+    return q;
+}
+// ... filled from the file: `room` bytes from file offset file_off + done, eight threads a piece (copy_slice)
+struct FileFill {
+    const uint8_t *image; int fd; uint64_t file_off;
+    size_t operator()(char *host, size_t room, uint64_t done) const
+    {
+        CopyJob job{host, (const char *)image + file_off + done, room, (room + 7) / 8, fd, (size_t)(file_off + done)};
+        splpack::parallel_for((room + job.per - 1) / std::max<size_t>(job.per, 1), 8, copy_slice, &job);
+        return room;
+    }
+};
+} // namespace
+
 // ---- SAM text (spl_sam_open): the same five arrays from the text an aligner writes --------------------------------------
 // Windows of SPL_SAM_WINDOW_BYTES (default 256 MiB) of whole lines -- the host cuts a window behind its last '\n', which it finds
 // in the mapping: text needs no room for an unfinished line, and a line longer than a window declines the file -- go up
@@ -2497,7 +2531,7 @@ struct SamDecode {
     spl_sam_names host_names{}, dev_names{};
     size_t blob_bytes = 0;
     // ---- everything the streams touch is declared before them
-    DevBuf d_text[2], d_slots, d_nameoff, d_blob, d_chunks, d_lines, d_kept, d_nops, d_ltid, d_fstat, d_fsum, d_counts, d_work, d_maxend, d_bounds, d_nbounds;
+    DevBuf d_text[2], d_slots, d_nameoff, d_blob, d_chunks, d_lines, d_kept, d_nops, d_ltid, d_fstat, d_fsum, d_counts, d_work, d_maxend, d_bounds, d_nbounds, d_long;
     DevBuf d_pos, d_flag, d_tid, d_cigoff, d_cigar, d_xs;
     RecordSort sorter;
     size_t cap_chunks = 0, cap_lines = 0, cap_work = 0;
@@ -2515,6 +2549,9 @@ struct SamDecode {
     struct Window { uint64_t lo, hi; };
     std::vector<Window> windows;
     size_t win_bytes = (size_t)256 << 20;
+    uint64_t text_bytes = 0;  // (SPL_BAM_TIMING's line: the bytes of text, the windows they came in, and what kind of file)
+    size_t n_windows = 0;
+    const char *what = "SAM text";
     std::mutex mu;
     std::condition_variable cv;
     size_t n_sent = 0, n_parsed = 0; // windows whose copies are queued (their event recorded) / whose buffer is free again
@@ -2553,6 +2590,8 @@ struct SamDecode {
             windows.push_back(Window{lo, hi});
             lo = hi;
         }
+        text_bytes = fsize - begin;
+        n_windows = windows.size();
         return SPL_OK;
     }
 
@@ -2560,10 +2599,21 @@ struct SamDecode {
 
     int set_up()
     {
+        { const int rc = set_up_streams(); if (rc) return rc; }
+        for (int k = 0; k < (windows.size() > 1 ? 2 : 1); ++k) HIP_TRY(d_text[k].get(buf_bytes(), st.k));
+        { const int rc = set_up_names(); if (rc) return rc; }
+        uploader = std::thread([this]() { send_windows(); });
+        return SPL_OK;
+    }
+    // (the parts of set_up that do not depend on where the text comes from: SamZDecode's too)
+    int set_up_streams()
+    {
         HIP_TRY(hipStreamCreateWithFlags(&st.k, hipStreamNonBlocking));
         for (hipEvent_t &e : st.up) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        { const int rc = ensure_stage(c, 3); if (rc) return rc; }
-        for (int k = 0; k < (windows.size() > 1 ? 2 : 1); ++k) HIP_TRY(d_text[k].get(buf_bytes(), st.k));
+        return ensure_stage(c, 3);
+    }
+    int set_up_names()
+    {
         const size_t nr = (size_t)std::max(n_ref, 1);
         HIP_TRY(d_slots.get(4 * (size_t)host_names.n_slots, st.k)); HIP_TRY(d_nameoff.get(4 * (nr + 1), st.k)); HIP_TRY(d_blob.get(std::max<size_t>(blob_bytes, 1), st.k));
         HIP_TRY(d_counts.get(sizeof(spl_sam_counts), st.k)); HIP_TRY(d_maxend.get(8 * nr, st.k)); HIP_TRY(d_fsum.get(8 * 2 * SPL_FS_CATEGORIES, st.k));
@@ -2577,7 +2627,6 @@ struct SamDecode {
         HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, st.k));
         HIP_TRY(hipStreamSynchronize(st.k)); // (the names' host memory is the file's; the copies above are done with it here)
         dev_names = spl_sam_names{d_slots.as<uint32_t>(), d_nameoff.as<uint32_t>(), d_blob.as<uint8_t>(), host_names.n_slots, host_names.n};
-        uploader = std::thread([this]() { send_windows(); });
         return SPL_OK;
     }
 
@@ -2592,18 +2641,7 @@ struct SamDecode {
                 if (stop) return;
             }
             const uint64_t from = windows[w].lo & ~(uint64_t)15, bytes = windows[w].hi - from;
-            char *const dst = d_text[w % 2].as<char>();
-            for (uint64_t done = 0; done < bytes && q == hipSuccess;) {
-                spl_ctx::Stage &sg = c->stage[c->stage_next];
-                c->stage_next = (c->stage_next + 1) % c->stage.size();
-                if (sg.busy) { q = hipEventSynchronize(sg.done); sg.busy = false; if (q != hipSuccess) break; }
-                const size_t n = (size_t)std::min<uint64_t>(bytes - done, sg.bytes);
-                CopyJob job{sg.host, (const char *)image + from + done, n, (n + 7) / 8, spl_bam_fd(bam), (size_t)(from + done)};
-                splpack::parallel_for((n + job.per - 1) / std::max<size_t>(job.per, 1), 8, copy_slice, &job);
-                q = hipMemcpyAsync(dst + done, sg.host, n, hipMemcpyHostToDevice, c->copy);
-                if (q == hipSuccess) { q = hipEventRecord(sg.done, c->copy); sg.busy = true; }
-                done += n;
-            }
+            q = ring_send(c, d_text[w % 2].as<char>(), bytes, FileFill{image, spl_bam_fd(bam), from});
             if (q == hipSuccess) q = hipEventRecord(st.up[w % 2], c->copy);
             std::lock_guard<std::mutex> lock(mu);
             if (q == hipSuccess) n_sent = w + 1;
@@ -2658,10 +2696,25 @@ struct SamDecode {
         }
         if (spl_bam_cancelled(bam)) return spl_set_error(SPL_ERR_IO, "closed before it was decoded");
         const Window win = windows[w];
-        const uint64_t base = win.lo & ~(uint64_t)15;
-        const uint8_t *const text = d_text[w % 2].as<uint8_t>() - base;
+        const uint8_t *const text = d_text[w % 2].as<uint8_t>() - (win.lo & ~(uint64_t)15);
         const uint64_t last_end = image[win.hi - 1] == '\n' ? win.hi - 1 : win.hi;
         HIP_TRY(hipStreamWaitEvent(st.k, st.up[w % 2], 0));
+        { const int rc = parse_range(text, win, last_end, fsize - win.hi, 0); if (rc) return rc; }
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            n_parsed = w + 1;
+        }
+        cv.notify_all();
+        return SPL_OK;
+    }
+
+    // The lines of bytes [win.lo, win.hi) of the text (whole lines; `text` indexed with offsets into the whole text, spl_sam.h) behind
+    // the ones there are: the stream's work and its two waits.  bytes_left: the text still to come, for the arrays' room.  max_line:
+    // 0, or the longest line the rule takes -- a caller whose windows may hold a longer one (SamZDecode: a carried piece in front
+    // of new text) has the lines measured, and the first one too long declines the file unless a line in front of it does.
+    int parse_range(const uint8_t *text, const Window win, uint64_t last_end, uint64_t bytes_left, size_t max_line)
+    {
+        const uint64_t base = win.lo & ~(uint64_t)15;
         // ---- line starts
         const uint32_t n_chunks = spl_sam_chunks(win.lo, win.hi);
         if (n_chunks > cap_chunks) { d_chunks.release(); HIP_TRY(d_chunks.get(4 * (size_t)n_chunks, st.k)); cap_chunks = n_chunks; }
@@ -2690,6 +2743,14 @@ struct SamDecode {
         }
         HIP_TRY(work_for(n_lines));
         HIP_TRY((hipError_t)spl_dev_launch_sam_line_fill(text, win.lo, win.hi, d_chunks.as<uint32_t>(), d_lines.as<uint32_t>(), st.k));
+        uint32_t first_long = ~0u;
+        if (max_line) {
+            static const uint32_t no_line = ~0u;
+            if (!d_long.p) HIP_TRY(d_long.get(4, st.k));
+            HIP_TRY(hipMemcpyAsync(d_long.p, &no_line, 4, hipMemcpyHostToDevice, st.k));
+            HIP_TRY((hipError_t)spl_dev_launch_sam_long_line(d_lines.as<uint32_t>(), n_lines, (uint32_t)(win.hi - base), (uint32_t)std::min<size_t>(max_line, 0xffffffffu), d_long.as<uint32_t>(), st.k));
+            HIP_TRY(hipMemcpyAsync(&first_long, d_long.p, 4, hipMemcpyDeviceToHost, st.k)); // (back with the scan's counters: no wait of its own)
+        }
         // ---- the rule, a lane per line
         static const unsigned long long none = ~0ull;
         HIP_TRY(hipMemcpyAsync(d_counts.p, &none, 8, hipMemcpyHostToDevice, st.k));
@@ -2707,6 +2768,11 @@ struct SamDecode {
             HIP_TRY(hipMemcpyAsync(&ops_w, d_nops.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st.k));
         }
         HIP_TRY(hipStreamSynchronize(st.k));
+        if (first_long != ~0u && (counts.first_bad == none || first_long <= (counts.first_bad >> 8))) { // (the host parser measures a line before it reads it)
+            bad_line = header_lines + n_lines_all + first_long + 1;
+            bad_reason = SPL_SAM_LONG_LINE;
+            return STOPPED;
+        }
         if (counts.first_bad != none) {
             bad_line = header_lines + n_lines_all + (counts.first_bad >> 8) + 1;
             bad_reason = (uint32_t)(counts.first_bad & 0xffu);
@@ -2721,7 +2787,7 @@ struct SamDecode {
         n_drop_mapq += counts.n_drop_mapq;
         if (want_stat) HIP_TRY((hipError_t)spl_dev_launch_bam_flagstat_reduce(d_fstat.as<uint32_t>(), (n_lines + 63u) / 64u, d_fsum.as<unsigned long long>(), st.k));
         // ---- the kept lines' fields behind the ones there are
-        { const int rc = make_room(kept_w, ops_w, win.hi - win.lo, fsize - win.hi); if (rc) return rc; }
+        { const int rc = make_room(kept_w, ops_w, win.hi - win.lo, bytes_left); if (rc) return rc; }
         HIP_TRY((hipError_t)spl_dev_launch_sam_extract(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
                                                        opts.filter.exclude_flags, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(), n_rec, n_ops, cap_rec, cap_ops,
                                                        d_pos.as<int32_t>(), d_flag.as<uint16_t>(), d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(),
@@ -2731,11 +2797,6 @@ struct SamDecode {
         n_rec += kept_w;
         n_ops += ops_w;
         n_lines_all += n_lines;
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            n_parsed = w + 1;
-        }
-        cv.notify_all();
         return SPL_OK;
     }
 
@@ -2808,16 +2869,296 @@ struct SamDecode {
         res.totals.dropped[1] = (int64_t)n_drop_mapq;
         for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.totals.fstat[q] = (int64_t)fsum[q];
         if (timing)
-            fprintf(stderr, "[spl_bam_decode_device] device %d: SAM text, %.1f MB in %zu window%s, %llu lines, %llu placed records%s: %.4f s\n", c->device, (fsize - begin) / 1e6, windows.size(),
-                    windows.size() == 1 ? "" : "s", (unsigned long long)n_lines_all, (unsigned long long)n_rec, n_sorted ? ", sorted" : "", host_now() - t_begin);
+            fprintf(stderr, "[spl_bam_decode_device] device %d: %s, %.1f MB in %zu window%s, %llu lines, %llu placed records%s: %.4f s\n", c->device, what, text_bytes / 1e6, n_windows,
+                    n_windows == 1 ? "" : "s", (unsigned long long)n_lines_all, (unsigned long long)n_rec, n_sorted ? ", sorted" : "", host_now() - t_begin);
+        return SPL_OK;
+    }
+};
+
+// ---- compressed SAM text (spl_sam_open on gzip's magic): inflated on the device, parsed in the same pass -------------------------
+// SamDecode with another source of text.  BGZF: a window is a run of whole blocks -- it closes at SPL_SAM_WINDOW_BYTES of inflated
+// text or at Z_BLOCK_CAP blocks --, whose compressed bytes go up through the staging ring on the copy stream and are inflated by
+// spl_inflate.hip's three kernels (decode, copy, CRC32) at the worst-case token stride; only the file crosses the link.  Plain
+// gzip: one DEFLATE stream is nothing to split across waves, so this call's thread inflates it with zlib into the staging ring and
+// the text goes up.  Either way the window's text ends where its last block (or piece) ends, not at a newline.  THE JOIN: a
+// window's lines are bytes [lo, hi), lo = where the window before ended its lines, hi = behind the last '\n' of the new text
+// (spl_sam_last_newline_kernel); the bytes behind hi are copied, device to device, to the front of the next window's buffer, to
+// addresses that equal their stream offsets modulo 16 -- each buffer has a window's room for them in front of the new text, so every
+// line of at most a window is whole in one buffer wherever blocks and windows cut it.  An unfinished line that has outgrown a window
+// ends the windows as SamDecode's plan does (long_line); a line too long INSIDE a buffer -- carry and new text are a window each --
+// is found by spl_sam_long_line_kernel.
+// The producing thread (upload, inflate, last newline, carry) is a window ahead of the parsing one and waits once a window, for the
+// blocks' status words and the newline's place: three host waits a window with parse_range's two.  A block that did not inflate,
+// or whose CRC32 is wrong, ends the call before anything of its window is parsed, and the host parser says what is wrong with the file.
+constexpr uint32_t Z_BLOCK_CAP = 13000; // (x SPL_Z_TOKEN_STRIDE = 1.07e9 bytes of token room: below 1 GiB)
+static_assert((uint64_t)Z_BLOCK_CAP * SPL_Z_TOKEN_STRIDE < (1ull << 30), "a window's token room stays below 1 GiB");
+
+struct SamZDecode : SamDecode {
+    const int kind = spl_bam_text_compression(bam);
+    DevBuf d_image[2], d_zb[2], d_zstatus[2], d_zwork, d_nl;
+    struct ZStreams {
+        hipStream_t z = nullptr;
+        hipEvent_t t[4] = {nullptr, nullptr, nullptr, nullptr}; // (SPL_BAM_TIMING: around a window's upload and around its inflate)
+        ~ZStreams()
+        {
+            if (z) { (void)hipStreamSynchronize(z); (void)hipStreamDestroy(z); }
+            for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
+        }
+    } zs;
+    struct Ready { uint64_t lo, hi, last_end, left; const uint8_t *text; uint64_t n_blocks; };
+    std::vector<Ready> ready;             // (under mu) window w's lines, once n_sent > w
+    bool produced_all = false, z_bad = false; // (under mu) no more windows will come / a block did not inflate
+    std::vector<size_t> win_at;           // BGZF: window w is blocks [win_at[w], win_at[w + 1])
+    std::vector<spl_zblock> zlist[2];
+    std::vector<uint32_t> zstatus;
+    uint64_t total_u = 0;                 // BGZF: the inflated stream's length
+    size_t most_blocks = 0, most_bytes = 0;
+    size_t carry_room = 0;
+    double t_upload = 0, t_inflate = 0, t_parse = 0;
+    uint64_t n_blocks_done = 0;
+
+    SamZDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : SamDecode(ctx, b, r) {}
+    ~SamZDecode()
+    {
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            stop = true;
+        }
+        cv.notify_all();
+        if (uploader.joinable()) uploader.join(); // (before this object's buffers and stream go: the thread works on them)
+    }
+
+    int plan_z()
+    {
+        (void)spl_bam_text(bam, &begin, &header_lines, &host_names, &blob_bytes);
+        win_bytes = spl_sam_window_bytes();
+        carry_room = ((win_bytes + 15) & ~(size_t)15) + 16;
+        what = kind == SPL_TEXT_BGZF ? "SAM text, BGZF" : "SAM text, gzip";
+        if (kind != SPL_TEXT_BGZF) return SPL_OK;
+        const size_t n_all = spl_bam_block_count(bam);
+        if (n_all > 0xfffffff0ull) return spl_set_error(SPL_ERR_FORMAT, "more than 2^32 BGZF blocks");
+        spl_bam_block_info bi;
+        size_t b = 0;
+        for (; b < n_all; ++b) { // the blocks of nothing but header are the opening call's
+            spl_bam_block_get(bam, b, &bi);
+            if (bi.uoff + bi.isize > begin) break;
+        }
+        if (n_all) { spl_bam_block_get(bam, n_all - 1, &bi); total_u = bi.uoff + bi.isize; }
+        while (b < n_all) {
+            win_at.push_back(b);
+            spl_bam_block_info first;
+            spl_bam_block_get(bam, b, &first);
+            size_t e = b;
+            for (; e < n_all && e - b < Z_BLOCK_CAP; ++e) {
+                spl_bam_block_get(bam, e, &bi);
+                if (e > b && bi.uoff + bi.isize - first.uoff > win_bytes) break;
+            }
+            spl_bam_block_get(bam, e - 1, &bi);
+            most_blocks = std::max(most_blocks, e - b);
+            most_bytes = std::max(most_bytes, (size_t)(bi.data_off + bi.data_len - first.data_off));
+            b = e;
+        }
+        if (!win_at.empty()) win_at.push_back(n_all);
+        return SPL_OK;
+    }
+
+    // a buffer: a window's room for carried bytes, up to 15 bytes so that addresses equal stream offsets modulo 16, the new text (a
+    // window of it, or the one block that is more), and what the kernels' 16-byte loads may read behind it
+    size_t zbuf_bytes() const { return carry_room + 16 + win_bytes + 65536 + 16 + SPL_SAM_PAD; }
+
+    int set_up_z()
+    {
+        { const int rc = set_up_streams(); if (rc) return rc; }
+        HIP_TRY(hipStreamCreateWithFlags(&zs.z, hipStreamNonBlocking));
+        if (timing) for (hipEvent_t &e : zs.t) HIP_TRY(hipEventCreate(&e));
+        for (DevBuf &b : d_text) HIP_TRY(b.get(zbuf_bytes(), st.k));
+        HIP_TRY(d_nl.get(8, st.k));
+        if (kind == SPL_TEXT_BGZF && most_blocks) {
+            for (int k = 0; k < (win_at.size() > 2 ? 2 : 1); ++k) {
+                HIP_TRY(d_image[k].get(most_bytes + SPL_Z_IMAGE_PAD, st.k));
+                HIP_TRY(d_zb[k].get(sizeof(spl_zblock) * most_blocks, st.k));
+                HIP_TRY(d_zstatus[k].get(4 * most_blocks, st.k));
+            }
+            HIP_TRY(d_zwork.get(spl_dev_inflate_work_bytes((uint32_t)most_blocks), st.k));
+            zstatus.resize(most_blocks);
+        }
+        { const int rc = set_up_names(); if (rc) return rc; }
+        uploader = std::thread([this]() { produce(); });
+        return SPL_OK;
+    }
+
+    // BGZF window w: its blocks' bytes up, the three kernels behind them; the new text is [S, *E_out) of `text`
+    hipError_t fill_bgzf(size_t w, uint8_t *text, uint64_t *E_out, bool *last_out)
+    {
+        const size_t b0 = win_at[w], b1 = win_at[w + 1], n = b1 - b0, k = w % 2;
+        spl_bam_block_info first, bi;
+        spl_bam_block_get(bam, b0, &first);
+        std::vector<spl_zblock> &list = zlist[k];
+        list.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            spl_bam_block_get(bam, b0 + i, &bi);
+            list[i].in = bi.data_off - first.data_off; list[i].out = bi.uoff; list[i].in_len = bi.data_len; list[i].out_len = bi.isize; list[i].crc = bi.crc; list[i].pad = 0;
+        }
+        *E_out = bi.uoff + bi.isize;
+        *last_out = w + 2 == win_at.size();
+        hipError_t q = hipSuccess;
+        if (timing) q = hipEventRecord(zs.t[0], c->copy);
+        if (q == hipSuccess) q = ring_send(c, d_image[k].as<char>(), bi.data_off + bi.data_len - first.data_off, FileFill{image, spl_bam_fd(bam), first.data_off});
+        if (q == hipSuccess) q = hipEventRecord(timing ? zs.t[1] : st.up[k], c->copy);
+        if (q == hipSuccess) q = hipStreamWaitEvent(zs.z, timing ? zs.t[1] : st.up[k], 0);
+        if (q == hipSuccess && timing) q = hipEventRecord(zs.t[2], zs.z);
+        if (q == hipSuccess) q = hipMemcpyAsync(d_zb[k].p, list.data(), sizeof(spl_zblock) * n, hipMemcpyHostToDevice, zs.z);
+        if (q == hipSuccess) q = hipMemsetAsync(d_zstatus[k].p, 0xff, 4 * n, zs.z);
+        if (q == hipSuccess) q = (hipError_t)spl_dev_launch_inflate_decode(d_image[k].as<uint8_t>(), d_zb[k].as<spl_zblock>(), (uint32_t)n, d_zstatus[k].as<uint32_t>(), d_zwork.p, zs.z);
+        if (q == hipSuccess) q = (hipError_t)spl_dev_launch_inflate_copy(d_zb[k].as<spl_zblock>(), (uint32_t)n, text, d_zstatus[k].as<uint32_t>(), d_zwork.p, zs.z);
+        if (q == hipSuccess) q = (hipError_t)spl_dev_launch_crc32(text, d_zb[k].as<spl_zblock>(), (uint32_t)n, d_zstatus[k].as<uint32_t>(), zs.z);
+        if (q == hipSuccess && timing) q = hipEventRecord(zs.t[3], zs.z);
+        if (q == hipSuccess) q = hipMemcpyAsync(zstatus.data(), d_zstatus[k].p, 4 * n, hipMemcpyDeviceToHost, zs.z);
+        return q;
+    }
+
+    // gzip: up to a window of text from the host's inflate, piece by piece through the staging ring
+    splsamz::Inflater gz;
+    hipError_t fill_gzip(size_t w, uint8_t *text, uint64_t S, uint64_t *E_out, bool *last_out)
+    {
+        uint64_t done = 0;
+        hipError_t q = ring_send(c, (char *)text + S, win_bytes, [&](char *host, size_t room, uint64_t) { return gz.status == 0 ? gz.read((uint8_t *)host, room) : (size_t)0; }, &done);
+        if (q == hipSuccess) q = hipEventRecord(st.up[w % 2], c->copy);
+        if (q == hipSuccess) q = hipStreamWaitEvent(zs.z, st.up[w % 2], 0);
+        *E_out = S + done;
+        *last_out = gz.status != 0;
+        return q;
+    }
+
+    void produce()
+    {
+        hipError_t q = hipSetDevice(c->device);
+        bool bad = false;
+        uint64_t lo = begin, S = begin;
+        const uint8_t *prev = nullptr;
+        if (kind == SPL_TEXT_BGZF) {
+            if (win_at.empty()) { std::lock_guard<std::mutex> lock(mu); produced_all = true; cv.notify_all(); return; }
+            spl_bam_block_info bi;
+            spl_bam_block_get(bam, win_at[0], &bi);
+            S = bi.uoff;
+        } else {
+            // the header's bytes are inflated once more and dropped: the text that goes up begins with the first line
+            bad = !gz.begin(image, fsize);
+            std::vector<uint8_t> drop(65536);
+            for (uint64_t left = begin; left && !bad;) {
+                const size_t n = gz.read(drop.data(), (size_t)std::min<uint64_t>(left, drop.size()));
+                left -= n;
+                if (left && gz.status != 0) bad = true;
+            }
+        }
+        for (size_t w = 0; q == hipSuccess && !bad; ++w) {
+            {
+                std::unique_lock<std::mutex> lock(mu);
+                cv.wait(lock, [&]() { return stop || w < n_parsed + 2; });
+                if (stop) return;
+            }
+            uint8_t *const text = d_text[w % 2].as<uint8_t>() + carry_room + (S & 15u) - S; // (stream offset s lies at text + s: the same modulo 16)
+            uint64_t E = S;
+            bool last = false;
+            unsigned long long nl = 0;
+            if (S > lo) q = hipMemcpyAsync(text + lo, prev + lo, (size_t)(S - lo), hipMemcpyDeviceToDevice, zs.z); // the carry: at most a window (checked below, a window ago)
+            if (q == hipSuccess) q = kind == SPL_TEXT_BGZF ? fill_bgzf(w, text, &E, &last) : fill_gzip(w, text, S, &E, &last);
+            const uint64_t from = std::max(S, lo); // (the first window's first block may begin with the header's end)
+            if (q == hipSuccess) q = hipMemsetAsync(d_nl.p, 0, 8, zs.z);
+            if (q == hipSuccess) q = (hipError_t)spl_dev_launch_sam_last_newline(text, from, E, d_nl.as<unsigned long long>(), zs.z);
+            if (q == hipSuccess) q = hipMemcpyAsync(&nl, d_nl.p, 8, hipMemcpyDeviceToHost, zs.z);
+            if (q == hipSuccess) q = hipStreamSynchronize(zs.z); // the producer's one wait a window
+            if (q != hipSuccess) break;
+            if (timing && kind == SPL_TEXT_BGZF) {
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, zs.t[0], zs.t[1]) == hipSuccess) t_upload += ms / 1e3;
+                if (hipEventElapsedTime(&ms, zs.t[2], zs.t[3]) == hipSuccess) t_inflate += ms / 1e3;
+            }
+            if (kind == SPL_TEXT_BGZF) {
+                const size_t n = win_at[w + 1] - win_at[w];
+                for (size_t i = 0; i < n && !bad; ++i) bad = zstatus[i] != SPL_Z_OK;
+            } else bad = gz.status == -1;
+            if (bad) break;
+            const uint64_t hi = last ? E : (nl ? (uint64_t)nl : lo);
+            const uint64_t last_end = hi > lo && nl == hi ? hi - 1 : hi;
+            uint64_t left = 0;
+            if (kind == SPL_TEXT_BGZF) left = total_u - hi;
+            else if (!last && gz.consumed()) left = (uint64_t)((double)(E - begin) / (double)gz.consumed() * (double)(fsize - gz.consumed()));
+            const bool too_long = !last && E - hi > win_bytes; // an unfinished line that no window will hold
+            {
+                std::lock_guard<std::mutex> lock(mu);
+                ready.push_back(Ready{lo, hi, last_end, left, text, kind == SPL_TEXT_BGZF ? (uint64_t)(win_at[w + 1] - win_at[w]) : 0});
+                n_sent = w + 1;
+                if (last || too_long) produced_all = true;
+                if (too_long) long_line = true;
+            }
+            cv.notify_all();
+            if (last || too_long) return;
+            lo = hi;
+            prev = text;
+            S = E;
+        }
+        std::lock_guard<std::mutex> lock(mu);
+        if (q != hipSuccess) up_err = q;
+        else z_bad = true;
+        cv.notify_all();
+    }
+
+    int parse_all()
+    {
+        for (size_t w = 0;; ++w) {
+            Ready r;
+            {
+                std::unique_lock<std::mutex> lock(mu);
+                cv.wait(lock, [&]() { return n_sent > w || produced_all || z_bad || up_err != hipSuccess; });
+                if (n_sent <= w) { // (what was sent is parsed first: its blocks were good)
+                    HIP_TRY(up_err);
+                    if (z_bad) return spl_set_error(SPL_ERR_FORMAT, "compressed SAM text: a block did not inflate, or its CRC32 is wrong");
+                    break;
+                }
+                r = ready[w];
+            }
+            if (spl_bam_cancelled(bam)) return spl_set_error(SPL_ERR_IO, "closed before it was decoded");
+            n_blocks_done += r.n_blocks; // (inflated, checked and handed over: what spl_bam_text_blocks says, a decline included)
+            spl_bam_note_text_blocks(bam, (int64_t)n_blocks_done);
+            const double t0 = host_now();
+            if (r.hi > r.lo) { const int rc = parse_range(r.text, Window{r.lo, r.hi}, r.last_end, r.left, win_bytes); if (rc) return rc; }
+            t_parse += host_now() - t0;
+            ++n_windows;
+            text_bytes += r.hi - r.lo;
+            {
+                std::lock_guard<std::mutex> lock(mu);
+                n_parsed = w + 1;
+            }
+            cv.notify_all();
+        }
+        if (timing)
+            fprintf(stderr, "[spl_bam_decode_device] device %d: %s: upload %.4f s, inflate %.4f s (%llu blocks), parse %.4f s (the producing thread's stages overlap the parsing one's)\n", c->device, what,
+                    t_upload, t_inflate, (unsigned long long)n_blocks_done, t_parse);
         return SPL_OK;
     }
 };
 } // namespace
 
+static int decode_ztext(spl_ctx *c, spl_bam *bam, ShareOut &res, const Publish &publish)
+{
+    SamZDecode d(c, bam, res);
+    int rc = d.plan_z();
+    if (rc == SPL_OK) rc = d.set_up_z();
+    if (rc == SPL_OK) rc = d.parse_all();
+    if (rc == STOPPED) { spl_sam_fail(bam, d.bad_line, d.bad_reason); return SPL_OK; }
+    if (rc == SPL_OK && d.long_line) { spl_sam_fail(bam, d.header_lines + d.n_lines_all + 1, SPL_SAM_LONG_LINE); return SPL_OK; }
+    if (rc == SPL_OK) rc = d.finish();
+    if (rc != SPL_OK) return rc;
+    d.release_buffers();
+    d.sorter.release();
+    return publish(res);
+}
+
 static int decode_text(spl_ctx *c, spl_bam *bam, ShareOut &res, const Publish &publish)
 {
     HIP_TRY(hipSetDevice(c->device));
+    if (spl_bam_text_compression(bam) != SPL_TEXT_PLAIN) return decode_ztext(c, bam, res, publish);
     SamDecode d(c, bam, res);
     int rc = d.plan();
     if (rc == SPL_OK) rc = d.set_up();

@@ -58,6 +58,16 @@ int spl_dev_launch_sam_extract(const uint8_t *text, uint64_t base, const uint32_
                                uint8_t *xs, unsigned long long *ref_max_end, struct spl_sam_counts *counts, void *stream);
 // counts->unordered = 1 when (tid, pos) of any record in [first, first + n), first > 0: or of record first, is below its predecessor's
 int spl_dev_launch_sam_order(const int32_t *tid, const int32_t *pos, uint64_t first, uint64_t n, struct spl_sam_counts *counts, void *stream);
+// ---- for text that arrives without regard to lines (compressed SAM, spl_capi.cpp: SamZDecode) --------------------------------
+// The inflated bytes of a window end where its last BGZF block ends.  *last (zero it first) = the offset behind the last '\n' of
+// [lo, hi), unchanged where there is none: the window's lines end there, the bytes behind go to the front of the next window.
+// `text` as above: indexed with offsets into the whole stream, address and offset equal modulo 16, readable in
+// [lo & ~15, (hi + 15) & ~15).
+int spl_dev_launch_sam_last_newline(const uint8_t *text, uint64_t lo, uint64_t hi, unsigned long long *last, void *stream);
+// *first_long (set it to ~0 first) = the first of the window's lines that is longer than max_line bytes, its newline counted --
+// such a line may lie INSIDE a window whose front is a carried piece (carry and new text are a window each).  end_off: where the
+// last line ends, from the window's base, its newline counted if it has one.
+int spl_dev_launch_sam_long_line(const uint32_t *line_start, uint32_t n_lines, uint32_t end_off, uint32_t max_line, uint32_t *first_long, void *stream);
 #ifdef __cplusplus
 }
 #endif

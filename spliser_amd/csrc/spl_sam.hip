@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "spl_sam.h"
 #include "spl_sam_line.h"
 #include "spl_flagstat.h"
@@ -201,7 +203,55 @@ __global__ __launch_bounds__(256) void spl_sam_order_kernel(const int32_t *tid, 
     if (t1 < t0 || (t1 == t0 && pos[r] < pos[r - 1])) atomicOr(&counts->unordered, 1u);
 }
 
+// ---- the join behind an inflate (spl_sam.h): where the text that has arrived ends in a whole line, and lines too long for the rule
+// The last '\n' of [lo, hi): a lane per sixteen bytes (the same aligned load and the same test as the line starts'), the wave's
+// largest, one atomicMax a wave that has any.  *last = that byte's offset + 1, left as it was (the caller's 0) where there is none.
+__global__ __launch_bounds__(256) void spl_sam_last_newline_kernel(const uint8_t *text, uint64_t lo, uint64_t hi, unsigned long long *last)
+{
+    const uint64_t base = lo & ~(uint64_t)15, hi16 = (hi + 15u) & ~(uint64_t)15;
+    unsigned long long mine = 0;
+    for (uint64_t at = base + ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 16u; at < hi16; at += (uint64_t)gridDim.x * 256u * 16u) {
+        const uint4 w = *(const uint4 *)(text + at);
+        uint32_t nl = newline_bits(w.x) | newline_bits(w.y) << 4 | newline_bits(w.z) << 8 | newline_bits(w.w) << 12;
+        if (at < lo) nl &= ~((1u << (uint32_t)(lo - at)) - 1u);              // (lo - at < 16: at >= base)
+        if (at + 16u > hi) nl &= (1u << (uint32_t)(hi - at)) - 1u;           // (hi - at in 1 .. 15: at < hi16)
+        if (nl) mine = at + (31u - (uint32_t)__clz((int)nl)) + 1u;           // (offsets go up along the loop: the last word with one wins)
+    }
+    for (uint32_t s = 32u; s; s >>= 1) {
+        const unsigned long long other = (unsigned long long)wv::shfl((uint32_t)mine, wv::lane() ^ s) | (unsigned long long)wv::shfl((uint32_t)(mine >> 32), wv::lane() ^ s) << 32;
+        mine = other > mine ? other : mine;
+    }
+    if (wv::lane() == 0 && mine) atomicMax(last, mine);
+}
+
+// *first_long = the smallest i whose line is longer than max_line, its newline counted (atomicMin; the caller sets ~0 first).
+// Line i is [line_start[i], line_start[i + 1]), the last one ends at end_off (all from the window's base): a last line without a
+// newline counts its bytes, as the host parser counts them.
+__global__ __launch_bounds__(256) void spl_sam_long_line_kernel(const uint32_t *line_start, uint32_t n_lines, uint32_t end_off, uint32_t max_line, uint32_t *first_long)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_lines) return;
+    const uint32_t len = (i + 1u < n_lines ? line_start[i + 1u] : end_off) - line_start[i];
+    if (len > max_line) atomicMin(first_long, i);
+}
+
 } // namespace
+
+extern "C" int spl_dev_launch_sam_last_newline(const uint8_t *text, uint64_t lo, uint64_t hi, unsigned long long *last, void *st)
+{
+    if (hi <= lo) return 0;
+    const uint64_t words = (((hi + 15u) & ~(uint64_t)15) - (lo & ~(uint64_t)15)) / 16u;
+    const uint32_t groups = (uint32_t)std::min<uint64_t>((words + 255u) / 256u, 256u * 8u); // (eight workgroups a CU's worth of grid; the loop takes the rest)
+    hipLaunchKernelGGL(spl_sam_last_newline_kernel, dim3(groups), dim3(256), 0, (hipStream_t)st, text, lo, hi, last);
+    return (int)hipGetLastError();
+}
+
+extern "C" int spl_dev_launch_sam_long_line(const uint32_t *line_start, uint32_t n_lines, uint32_t end_off, uint32_t max_line, uint32_t *first_long, void *st)
+{
+    if (!n_lines) return 0;
+    hipLaunchKernelGGL(spl_sam_long_line_kernel, dim3((n_lines + 255u) / 256u), dim3(256), 0, (hipStream_t)st, line_start, n_lines, end_off, max_line, first_long);
+    return (int)hipGetLastError();
+}
 
 extern "C" uint32_t spl_sam_chunks(uint64_t lo, uint64_t hi)
 {

@@ -51,7 +51,7 @@ EXPORTS = [
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
     "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_reads_has_strand", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
-    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_close",
+    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
     "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
@@ -84,6 +84,7 @@ def lib():
         L.spl_bam_decline_reason.restype = ctypes.c_char_p
         L.spl_bam_ref_length.restype = ctypes.c_int64
         L.spl_bam_n_records.restype = ctypes.c_int64
+        L.spl_bam_text_blocks.restype = ctypes.c_int64
         for name in ("spl_destroy", "spl_sites_free", "spl_reads_free", "spl_soa_free", "spl_bam_close", "spl_text_close", "spl_combine_close"):
             getattr(L, name).restype = None
         for name in ("spl_combine_rows", "spl_combine_region_runs", "spl_combine_n_sites", "spl_combine_n_gap_sites", "spl_combine_skipped"):
@@ -926,7 +927,8 @@ class SamFile(BamFile):
     deferred whatever ``stream`` / ``defer`` say: ``decode_on_device`` parses it on the GPU, and without that call the first
     wait parses it on a host thread -- by the same strict rule (csrc/spl_sam_line.h), always as ``any_order``.  A file with a
     line the rule does not take is DECLINED: waiting for it raises (code -5) and ``decline_reason()`` says ``line N <why>``;
-    ``samio.read_sam`` reads such a file as before (``process.open_and_decode`` does that)."""
+    ``samio.read_sam`` reads such a file as before (``process.open_and_decode`` does that).  The text may be compressed, as BGZF
+    (``bgzip``, ``samtools view -O sam,level=6``) or as plain gzip (``gzip``, several members too): ``compression`` says which."""
 
     def __init__(self, path, threads=0, stream=False, defer=True, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False, flagstat=False,
                  any_order=True):
@@ -937,6 +939,19 @@ class SamFile(BamFile):
     @staticmethod
     def _opener(deferred, stream):
         return lib().spl_sam_open
+
+    COMPRESSION = ("", "BGZF", "gzip")
+
+    @property
+    def compression(self):
+        """'' for plain text, 'BGZF' or 'gzip' for compressed text (``spl_bam_text_compression``): BGZF is inflated on the GPU, block
+        by block, plain gzip by one host thread -- parsed on the GPU either way (``decode_on_device``)."""
+        return self.COMPRESSION[lib().spl_bam_text_compression(self._h)]
+
+    @property
+    def blocks_inflated(self):
+        """The BGZF blocks a device decode of this file inflated (0: none did, or the file is not BGZF)."""
+        return int(lib().spl_bam_text_blocks(self._h))
 
     def declined(self):
         """Waits for the end of the decode; -> '' when the rule took every line, else ``line N <why>``.  Other failures raise."""

@@ -13,10 +13,12 @@ Deliberate deviations from the reference, all on the failure side (SURVEY.md sec
     AttributeError at :283.
 """
 import collections
+import gzip
 import os
 import sys
 import threading
 import time
+import zlib
 
 import numpy as np
 
@@ -78,7 +80,8 @@ class _SamSource(object):
 
 
 def open_alignments(path, threads=0, stream=False, defer=False, options=DecodeOptions()):
-    """BAM (BGZF) through the native decoder; plain SAM text through the Python reader, or -- ``defer=True``, a decode that may use
+    """BAM (BGZF) through the native decoder; SAM text -- plain, or compressed as BGZF or gzip, told from a BAM by the first bytes its
+    first member inflates to -- through the Python reader, or -- ``defer=True``, a decode that may use
     the GPU -- as a ``native.SamFile``.  ``stream=True``: the BAM decoder
     returns after the header and decodes in the background (``native.BamFile``); ``defer=True``: nothing is decoded until
     somebody asks (``BamFile.decode_on_device``, or the first wait: host threads).  ``options`` (``DecodeOptions``): what either
@@ -86,11 +89,18 @@ def open_alignments(path, threads=0, stream=False, defer=False, options=DecodeOp
     order."""
     with open(path, "rb") as fh:
         magic = fh.read(4)
-    if magic[:2] == b"\x1f\x8b":
+    packed_text = False
+    if magic[:2] == b"\x1f\x8b":      # gzip's magic: a BAM, or compressed SAM text -- what the first member inflates to says which
+        try:
+            with gzip.open(path, "rb") as fh:
+                packed_text = fh.read(1) == b"@"
+        except (OSError, EOFError, zlib.error):
+            pass                        # (not even a first member: the BAM reader finds the words for it)
+    if magic[:2] == b"\x1f\x8b" and not packed_text:
         q, f, F = options.read_filter
         return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=options.aux_strand,
                               flagstat=options.flagstat, any_order=options.any_order)
-    is_sam = magic[:1] == b"@" or b"\t" in open(path, "rb").readline()
+    is_sam = packed_text or magic[:1] == b"@" or b"\t" in open(path, "rb").readline()
     if is_sam and defer:
         # the aligner's text parsed natively (on the GPU by ``SamFile.decode_on_device``): counters, kept reads and all.  A header
         # the native reader does not take (no @SQ / LN, a repeated name) is the Python reader's, as any SAM text was
@@ -163,15 +173,22 @@ def _decode_sam_text(source, path, devices, options, log):
     except BaseException:
         source.close()
         raise
+    kind = source.compression       # '' / 'BGZF' / 'gzip'
+    tag = "SAM text, %s" % kind if kind else "SAM text"
     if not why:
         if log is not None:
-            log("  (SAM text: %d lines parsed %s)" % (source.n_records, "on the GPU" if source.on_device else "on host threads"))
+            where = "on the GPU" if source.on_device else "on host threads"
+            if kind == "BGZF" and source.on_device:
+                where += ", %d blocks inflated there" % source.blocks_inflated
+            elif kind == "gzip" and source.on_device:
+                where += ", inflated on one host thread"
+            log("  (%s: %d lines parsed %s)" % (tag, source.n_records, where))
             if not options.any_order:      # (text is always taken in any order; with --anyOrder the command says the line itself)
                 log_any_order(source, log)
         return source
     source.close()
     if log is not None:
-        log("  (SAM text: %s: read by the Python reader)" % why)
+        log("  (%s: %s: read by the Python reader)" % (tag, why))
     if options.flagstat:
         raise native.SpliserNativeError(-5, "%s: flagstat counters are counted while a BAM file is decoded; this is not one" % path)
     return _SamSource(path, options)

@@ -5,10 +5,11 @@ line ``samtools view`` prints (flag, POS, CIGAR -- SpliSER_v0_1_8.py:434-437) as
 (``include/spliser.h``: ``spl_reads``).  Production input is BAM, decoded by the native reader in
 ``csrc/bam_reader.cpp`` (see ``native.BamFile``).  This module adds
 
-  * ``read_sam``   -- a plain SAM-text reader (small inputs, fixtures; ``samtools view`` accepts SAM too),
+  * ``read_sam``   -- a plain SAM-text reader (small inputs, fixtures; ``samtools view`` accepts SAM too), gzip'd or BGZF text too,
   * ``write_bam``  -- a spec-conformant BGZF/BAM writer used to make test and synthetic BAM files
                       (the image has no samtools/htslib), and ``write_sam`` for their text twins.
 """
+import gzip
 import re
 import struct
 import zlib
@@ -103,13 +104,15 @@ def sam_aux_strand(cigar, optional):
 
 
 def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None, aux_strand=False):
-    """Parse SAM text -> (ref_names, {chrom: ReadSet}).  Keeps every record that has an RNAME, file order -- what ``samtools
+    """Parse SAM text (plain, or compressed as gzip / BGZF) -> (ref_names, {chrom: ReadSet}).  Keeps every record that has an RNAME, file order -- what ``samtools
     view`` would print; ``min_mapq`` / ``require_flags`` / ``exclude_flags`` are its -q / -f / -F on columns 5 and 2 (the BAM
     decoder's rule, ``spl_bam_set_filter``: flags first, MAPQ as a number).  ``counts``: a list that gets [records seen, dropped
     by flags, dropped by MAPQ] added to its three entries.  ``aux_strand``: every ReadSet gets ``xs`` (``sam_aux_strand``)."""
     names, per = [], {}
     seen = by_flags = by_mapq = 0
-    with open(path, "r") as handle:
+    with open(path, "rb") as handle:
+        packed = handle.read(2) == b"\x1f\x8b"      # (gzip, or BGZF, which is gzip in many members)
+    with (gzip.open(path, "rt") if packed else open(path, "r")) as handle:      # (both translate newlines alike: a carriage return ends a line)
         for line in handle:
             if line.startswith("@"):
                 if line.startswith("@SQ"):

@@ -8,12 +8,19 @@ pseudo-random SEQ and QUAL of the read's length, an ``NH:i`` / ``XS:A`` tail (``
 rate: 60 bytes a read instead of ~300) -- and as a ``seq-like`` BAM.  Printed: seconds from ``spl_bam_decode_device`` until every
 reference is complete (best of three after a warm-up, a fresh object each), GB/s of text beside the link's floor (text bytes at
 the project's PCIe figure, 56 GB/s), the same call on the BAM, and for files of at most 2 M reads the Python reader's seconds for
-the same file (``samio.read_sam``: what `-B x.sam` ran before this decoder).  The files are written once and removed at the end."""
+the same file (``samio.read_sam``: what `-B x.sam` ran before this decoder).  The files are written once and removed at the end.
+
+The same text is also written COMPRESSED, the way it lies on disk: as BGZF at level 6 with payloads of 0xff00 bytes (``bgzip``,
+``samtools view -O sam,level=6``) and as gzip (members of 256 MiB of text, level 6, deflated side by side: the host's inflate reads
+them as one stream).  Per form: seconds and GB/s of INFLATED text, against the plain text's figure of the same run and the BAM's;
+for the BGZF leg one more call under ``SPL_BAM_TIMING`` gives the decoder's own split -- upload, inflate, parse."""
 import argparse
+import multiprocessing
 import os
 import sys
 import tempfile
 import time
+import zlib
 
 import numpy as np
 
@@ -59,6 +66,59 @@ def write_sam_like_an_aligner(path, names, lengths, read_sets, seed=1, piece=1_0
     return n_lines
 
 
+def _bgzf_piece(args):
+    path, at, n = args
+    with open(path, "rb") as fh:
+        fh.seek(at)
+        text = fh.read(n)
+    return b"".join(samio._bgzf_block(text[k:k + 0xff00], 6) for k in range(0, len(text), 0xff00))
+
+
+def _gzip_piece(args):
+    path, at, n = args
+    with open(path, "rb") as fh:
+        fh.seek(at)
+        text = fh.read(n)
+    comp = zlib.compressobj(6, zlib.DEFLATED, 31)
+    return comp.compress(text) + comp.flush()
+
+
+def write_compressed(sam, bgzf_path, gzip_path, workers=15):
+    """The text of ``sam`` as BGZF (level 6, payloads of 0xff00 bytes, the EOF marker) and as gzip (a member per 256 MiB of text).
+    The workers are fresh processes (``spawn``), and ``main`` calls this before it opens its context: none of them ever sees the GPU."""
+    size = os.path.getsize(sam)
+    with multiprocessing.get_context("spawn").Pool(workers) as pool:
+        step = 0xff00 * 256
+        with open(bgzf_path, "wb") as fh:
+            for piece in pool.imap(_bgzf_piece, [(sam, at, step) for at in range(0, size, step)], chunksize=4):
+                fh.write(piece)
+            fh.write(samio._BGZF_EOF)
+        step = 256 << 20
+        with open(gzip_path, "wb") as fh:
+            for piece in pool.imap(_gzip_piece, [(sam, at, step) for at in range(0, size, step)]):
+                fh.write(piece)
+
+
+def timing_split(make, ctx):
+    """One more decode under SPL_BAM_TIMING, the library's stderr caught: -> its lines about this decode."""
+    sys.stderr.flush()
+    keep = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        os.environ["SPL_BAM_TIMING"] = "1"
+        try:
+            src = make()
+            src.decode_on_device(ctx)
+            src.wait_all()
+            src.close()
+        finally:
+            del os.environ["SPL_BAM_TIMING"]
+            os.dup2(keep, 2)
+            os.close(keep)
+        tmp.seek(0)
+        return [line for line in tmp.read().decode("utf-8", "replace").split("\n") if "SAM text" in line]
+
+
 def best_of(make, ctx, runs=3):
     """A warm-up, then the best of ``runs``: seconds of decode_on_device on a fresh object -> (seconds, records, taken on the device)."""
     best, n, on = None, 0, False
@@ -88,34 +148,51 @@ def main():
         print(msg, flush=True)
         out.append(msg)
     work = args.dir or tempfile.mkdtemp(prefix="sam_rate_")
-    with native.Context(args.device) as ctx:
-        for n_reads in [int(v) for v in args.reads.split(",")]:
-            sam, bam = os.path.join(work, "s%d.sam" % n_reads), os.path.join(work, "s%d.bam" % n_reads)
-            free = os.statvfs(work).f_bavail * os.statvfs(work).f_frsize
-            if free < 450 * n_reads:
-                say("%d reads: skipped, %s has %.1f GB free and the two files need about %.1f" % (n_reads, work, free / 1e9, 450 * n_reads / 1e9))
-                continue
-            t = time.perf_counter()
-            wl = synth.Workload("arabidopsis", n_reads=n_reads, seed=5)
-            names, lengths = wl.genome.chrom_names, wl.genome.chrom_lengths
-            n_lines = write_sam_like_an_aligner(sam, names, lengths, wl.reads)
-            native.write_bam(bam, names, lengths, wl.reads, seq_mode=1)
-            text_bytes, bam_bytes = os.path.getsize(sam), os.path.getsize(bam)
-            say("%d reads: SAM %.3f GB (%.0f B a line), BAM %.3f GB, written in %.0f s" % (n_lines, text_bytes / 1e9, text_bytes / n_lines, bam_bytes / 1e9, time.perf_counter() - t))
+    for n_reads in [int(v) for v in args.reads.split(",")]:
+        sam, bam = os.path.join(work, "s%d.sam" % n_reads), os.path.join(work, "s%d.bam" % n_reads)
+        bgz, gzp = sam + ".bgzf.gz", sam + ".gz"
+        free = os.statvfs(work).f_bavail * os.statvfs(work).f_frsize
+        if free < 600 * n_reads:
+            say("%d reads: skipped, %s has %.1f GB free and the four files need about %.1f" % (n_reads, work, free / 1e9, 600 * n_reads / 1e9))
+            continue
+        # ---- the four files first, with no context open: the compressing workers are started while this process has no GPU
+        t = time.perf_counter()
+        wl = synth.Workload("arabidopsis", n_reads=n_reads, seed=5)
+        names, lengths = wl.genome.chrom_names, wl.genome.chrom_lengths
+        n_lines = write_sam_like_an_aligner(sam, names, lengths, wl.reads)
+        native.write_bam(bam, names, lengths, wl.reads, seq_mode=1)
+        text_bytes, bam_bytes = os.path.getsize(sam), os.path.getsize(bam)
+        say("%d reads: SAM %.3f GB (%.0f B a line), BAM %.3f GB, written in %.0f s" % (n_lines, text_bytes / 1e9, text_bytes / n_lines, bam_bytes / 1e9, time.perf_counter() - t))
+        t = time.perf_counter()
+        write_compressed(sam, bgz, gzp)
+        say("  the text compressed: BGZF (level 6, payloads of 0xff00) %.3f GB = 1/%.2f of the text, gzip %.3f GB; written in %.0f s"
+            % (os.path.getsize(bgz) / 1e9, text_bytes / os.path.getsize(bgz), os.path.getsize(gzp) / 1e9, time.perf_counter() - t))
+        del wl
+        with native.Context(args.device) as ctx:
             t_sam, n_sam, on_sam = best_of(lambda: native.SamFile(sam), ctx)
             floor = text_bytes / (LINK_GBS * 1e9)
             say("  SAM text on the %s: %.4f s until the references are complete = %.2f GB/s of text, %.1f M lines/s; the link's floor at %.0f GB/s is %.4f s (x%.2f)"
                 % ("GPU" if on_sam else "HOST (declined or no memory)", t_sam, text_bytes / t_sam / 1e9, n_sam / t_sam / 1e6, LINK_GBS, floor, t_sam / floor))
+            t_of = {}
+            for form, path in (("BGZF", bgz), ("gzip", gzp)):
+                t_z, n_z, on_z = best_of(lambda: native.SamFile(path), ctx)
+                t_of[form] = t_z
+                say("  SAM text, %s, on the %s: %.4f s = %.2f GB/s of inflated text (x%.2f of the plain text's time, file bytes at the link's rate: %.4f s); %d records: %s"
+                    % (form, "GPU" if on_z else "HOST", t_z, text_bytes / t_z / 1e9, t_z / t_sam, os.path.getsize(path) / (LINK_GBS * 1e9), n_z, n_z == n_sam))
+            for line in timing_split(lambda: native.SamFile(bgz), ctx):
+                say("    " + line)
             t_bam, n_bam, on_bam = best_of(lambda: native.BamFile(bam, defer=True), ctx)
             say("  BAM of the same reads on the %s: %.4f s (%.2f GB/s of file); %d records both ways: %s" % ("GPU" if on_bam else "HOST", t_bam, bam_bytes / t_bam / 1e9, n_bam,
                                                                                                           n_bam == n_sam))
-            if n_reads <= 2_000_000:
+        if n_reads <= 2_000_000:
+            for what, path, t_gpu in (("the plain text", sam, t_sam), ("the BGZF text", bgz, t_of["BGZF"]), ("the gzip text", gzp, t_of["gzip"])):
                 t = time.perf_counter()
-                samio.read_sam(sam)
+                samio.read_sam(path)
                 t_py = time.perf_counter() - t
-                say("  the Python reader (samio.read_sam, what -B x.sam ran before): %.2f s = %.0f k lines/s (x%.0f)" % (t_py, n_lines / t_py / 1e3, t_py / t_sam))
-            os.remove(sam)
-            os.remove(bam)
+                say("  the Python reader (samio.read_sam, what -B ran before) on %s: %.2f s = %.0f k lines/s (x%.1f of the GPU's time for that file)"
+                    % (what, t_py, n_lines / t_py / 1e3, t_py / t_gpu))
+        for path in (sam, bam, bgz, gzp):
+            os.remove(path)
     if args.out:
         with open(args.out, "w") as fh:
             fh.write("\n".join(out) + "\n")
