@@ -489,6 +489,19 @@ int spl_strand_tally(spl_ctx *ctx, const spl_dreads *dr, int64_t n_cover, const 
 int spl_strand_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, uint8_t xs, int64_t n_cover, const int32_t *cover_start,
                          const uint8_t *cover_code, int64_t *inout14);
 
+/* ---- the fused counting kernel's rule for simple reads, on the host (test hook; no file, no GPU) ---------------------------
+ * A simple read (one aligned op) with bases [a, b), a = pos + shift, b = a + len, counts for the sites t with t and t + 1 both under it: the
+ * distinct positions [lo, ub), lo = number of site positions <= a - 1, ub = number of site positions < b - 1.  The kernel asks one
+ * question for the simple reads of a thread together: with a_min the least a and b_max the greatest b among them, the thread is
+ * FLAGGED when ub(b_max) > lo(a_min); a thread that is not flagged has no simple read with a range.  A flagged thread's simple
+ * reads are then looked at one by one.  site_pos: n_pos >= 1 strictly ascending positions in [0, 2^31 - 67] (the shard coordinate space); the reads of
+ * thread t are [t * reads_per_thread, (t + 1) * reads_per_thread) of pos / len / is_simple, in any order of position.
+ * flagged[n_threads]; emits / lo / ub[n_threads * reads_per_thread]: for a flagged thread's simple reads the range and whether it
+ * is not empty, 0 for every other read.  SPL_ERR_RANGE: a simple read outside that space. */
+int spl_simple_span_host(const int32_t *site_pos, int64_t n_pos, int64_t n_threads, int reads_per_thread, const int32_t *pos,
+                         const uint16_t *len, const uint8_t *is_simple, int32_t shift, uint8_t *flagged, uint8_t *emits, int32_t *lo,
+                         int32_t *ub);
+
 /* ---- host helper of Step 1 ---------------------------------------------------------------------------
  * binary_gene_search (SpliSER_v0_1_8.py:118-173) for a batch of query positions against one chromosome's gene list
  * (in list order), probe for probe like the reference.  Strand bytes are '+', '-' or 0 for anything else;

@@ -37,6 +37,7 @@
 #include "spl_junction_fused.h"
 #include "spl_strand.h"
 #include "spl_strand_rule.h"
+#include "spl_simple_span.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -4127,6 +4128,59 @@ extern "C" int spl_strand_rule_host(uint32_t flag, int32_t pos, const uint32_t *
         if (cover_start[k] <= cover_start[k - 1]) return spl_set_error(SPL_ERR_ARG, "spl_strand_rule_host: the cover map is not strictly ascending at entry %lld", (long long)k);
     const uint32_t bits = spl_strand_read_bits(flag, (int64_t)pos, ops, n_ops, xs, n_cover, cover_start, cover_code);
     for (int k = 0; k < SPL_STRAND_COUNTERS; ++k) inout14[k] += (bits >> k) & 1u;
+    return SPL_OK;
+}
+
+// The fused range kernel's rule for a thread's simple reads (spl_simple_span.h) on the host, over a position index built here the
+// way spl_sites_upload lays it out and spl_build_dbuckets_kernel fills it: no GPU involved (test hook).
+extern "C" int spl_simple_span_host(const int32_t *site_pos, int64_t n_pos, int64_t n_threads, int reads_per_thread, const int32_t *pos,
+                                    const uint16_t *len, const uint8_t *is_simple, int32_t shift, uint8_t *flagged, uint8_t *emits, int32_t *lo,
+                                    int32_t *ub)
+{
+    if (!site_pos || n_pos < 1 || n_threads < 0 || reads_per_thread < 1 || (n_threads && (!pos || !len || !is_simple || !flagged || !emits || !lo || !ub)))
+        return spl_set_error(SPL_ERR_ARG, "spl_simple_span_host: null or empty argument");
+    for (int64_t k = 0; k < n_pos; ++k)
+        if (site_pos[k] < 0 || site_pos[k] > SPL_COORD_MAX || (k && site_pos[k] <= site_pos[k - 1]))
+            return spl_set_error(SPL_ERR_ARG, "spl_simple_span_host: site positions must ascend strictly inside [0, %d]", SPL_COORD_MAX);
+    const int64_t n_reads = n_threads * (int64_t)reads_per_thread;
+    for (int64_t i = 0; i < n_reads; ++i)
+        if (is_simple[i] && ((int64_t)pos[i] + shift < 0 || (int64_t)pos[i] + shift + (int64_t)len[i] > (int64_t)SPL_COORD_MAX))
+            return spl_set_error(SPL_ERR_RANGE, "spl_simple_span_host: read %lld lies outside [0, %d]", (long long)i, SPL_COORD_MAX);
+    // the index: one empty bucket in front of the first site and one behind the last (spl_sites_upload), entries as the device makes them
+    const int64_t first = site_pos[0], last = site_pos[n_pos - 1];
+    const int32_t dbase = first >= 64 ? (int32_t)(first - 64) : -64;
+    const uint32_t n_dbuckets = (uint32_t)((last - (int64_t)dbase) >> 5) + 2;
+    std::vector<uint32_t> b_first(n_dbuckets), b_occ(n_dbuckets, 0u);
+    {
+        int64_t k = 0;
+        for (uint32_t b = 0; b < n_dbuckets; ++b) {
+            const int64_t start = (int64_t)dbase + ((int64_t)b << 5);
+            while (k < n_pos && site_pos[k] < start) ++k;
+            b_first[b] = (uint32_t)k;
+            for (int64_t j = k; j < n_pos && site_pos[j] < start + 32; ++j) b_occ[b] |= 1u << (site_pos[j] - start);
+        }
+    }
+    auto entry = [&](int32_t x, uint32_t &f, uint32_t &o) { const uint32_t s = spl_dbk_slot_of(dbase, n_dbuckets, x); f = b_first[s]; o = b_occ[s]; };
+    for (int64_t t = 0; t < n_threads; ++t) {
+        const int64_t r0 = t * (int64_t)reads_per_thread;
+        spl_simple_span span;
+        spl_span_begin(span);
+        for (int j = 0; j < reads_per_thread; ++j) spl_span_take(span, is_simple[r0 + j] != 0, (uint32_t)pos[r0 + j], (uint32_t)len[r0 + j] << 16, shift);
+        uint32_t f0 = 0, o0 = 0, f1 = 0, o1 = 0;
+        if (spl_span_any(span)) { entry(span.a_min - 1, f0, o0); entry(span.b_max - 1, f1, o1); }
+        const bool fl = spl_span_flagged(dbase, span, f0, o0, f1, o1);
+        flagged[t] = fl ? 1 : 0;
+        for (int j = 0; j < reads_per_thread; ++j) {
+            const int64_t i = r0 + j;
+            emits[i] = 0; lo[i] = 0; ub[i] = 0;
+            if (!fl || !is_simple[i]) continue; // (what the kernel lists: a flagged thread's simple reads, each looked at on its own)
+            int32_t a, b;
+            spl_simple_bases((uint32_t)pos[i], (uint32_t)len[i] << 16, shift, a, b);
+            entry(a - 1, f0, o0);
+            entry(b - 1, f1, o1);
+            emits[i] = spl_simple_range(dbase, a, b, f0, o0, f1, o1, lo[i], ub[i]) ? 1 : 0;
+        }
+    }
     return SPL_OK;
 }
 

@@ -39,7 +39,14 @@
 #define SPL_WAVE_READS_FUSED 512         // a wave's list entries there
 #define SPL_REC_BYTES_FUSED 16448        // LDS for a tile's ops, then for the records of its reads that are not simple ones (those are counted from
                                          // registers): 16 KB + the slack behind a run's last record.  A tile that needs more is taken in halves.
-                                         // 30.1 KB of LDS a workgroup with the windows, the lists and s_idx: 5 workgroups a CU
+                                         // 31.1 KB of LDS a workgroup with the windows, the lists and s_idx: 5 workgroups a CU
+#define SPL_SIMPLE_LIST_FUSED 32         // a wave's list of simple reads to look at one by one (SimpleInPlace: the reads of the threads whose
+                                         // span holds a site), 8 bytes each: 1 KB a workgroup, 31 840 B in all.  LDS is handed out in granules
+                                         // of 1280 bytes (128 a CU): five workgroups a CU need 25 granules or fewer = 32 000 B, not 32 768 --
+                                         // 48 entries (32 352 B, 26 granules) left four, and the launch took 0.906 ms against 0.802
+#define SPL_SIMPLE_DENSE_FUSED 16        // flagged threads of a wave above which their simple reads are taken slot by slot, not through the list:
+                                         // 16 threads list at most 64 reads = two drains (a memory trip each) where slot by slot is one trip of
+                                         // eight gathers a thread and about three drains' worth of instructions
 #define SPL_WIN 1020                     // distinct site positions a workgroup privatises in LDS (pair kernel; range kernel unstranded)
 #define SPL_WIN_STRANDED 956             // ... range kernel, stranded: 4 windows + the lists, 8 workgroups in 160 KB
 #define SPL_WIN_STRANDED_FUSED 508       // ... the fused pass, stranded: 4 windows of 2 KB beside a tile's records, 5 workgroups in 160 KB

@@ -31,6 +31,7 @@
 #include "spl_classify.h"
 #include "spl_device.h"
 #include "spl_layout_tile.h"
+#include "spl_simple_span.h"
 
 namespace {
 
@@ -416,21 +417,15 @@ template <class P>
 __device__ __forceinline__ uint32_t dbk_slot(const P &p, int32_t x)
 {
     // the table starts with empty buckets before the first site (dbase >= -64) and ends with an empty bucket whose first
-    // dpos is n_dpos, so clamping the index is all the range handling there is; x - dbase cannot wrap because
-    // coordinates stay <= SPL_COORD_MAX = 2^31 - 67
-    int32_t b = (x - p.dbase) >> 5;
-    b = b < 0 ? 0 : b;
-    const int32_t last = (int32_t)p.n_dbuckets - 1;
-    return (uint32_t)(b > last ? last : b);
+    // dpos is n_dpos, so clamping the index is all the range handling there is (spl_simple_span.h: the arithmetic, shared with the host)
+    return spl_dbk_slot_of(p.dbase, p.n_dbuckets, x);
 }
 
 // For x outside the table the clamped entry is an empty bucket: count 0, not a site, not flagged, whatever the bit index says.
 template <class P>
 __device__ __forceinline__ void dbk_resolve(const P &p, int32_t x, const spl_dbk &e, int32_t &u, uint32_t &nv)
 {
-    const uint32_t bit = (uint32_t)(x - p.dbase) & 31u;
-    u = (int32_t)(e.first + (uint32_t)__popc(e.occ & ((1u << bit) - 1u)));
-    nv = (e.occ >> bit) & 1u;
+    spl_dbk_resolve_at(p.dbase, x, e.first, e.occ, u, nv);
 }
 
 // The same with the bucket's mask of flagged positions: rv = x is an end of a junction that has rivals.
@@ -486,20 +481,42 @@ __device__ __forceinline__ spl_dbk dbk_load2(const spl_hot_params &p, uint32_t s
     return e;
 }
 
-// The fused pass's simple reads (one aligned op, mapped, in range: run 0 of the classification), counted by the thread that
-// classified them, out of its registers (spl_layout_tile.h: tile_finish calls issue() for each of its reads right behind the
-// classification and commit() behind the ranks' barrier): two boundaries, one range, nothing else can happen -- such a read has
-// no record, no rank and no place in LDS.  A thread's 2 R bucket entries are asked for back to back and are on their way while
-// the other runs' prefix sums cross their barrier.  Slot j of a wave's threads is asked for, resolved and committed only if some
-// lane of the wave holds a simple read there (__any: wave-uniform), and only those lanes load.  Measured (profiles/
-// r08B_before_after.txt): with six reads in ten simple nearly every wave has one in every slot, so the gate saves 0.2 % of the
-// step and none of the fetched bytes over asking in every slot.  active = false (a tile taken in parts, whose simple reads were
-// counted when it was looked at in one piece): nothing is asked for or counted.
+// The waves' lists of simple reads to look at one by one (SimpleInPlace), SPL_SIMPLE_LIST_FUSED entries of two record words a
+// wave: LDS of the fused instantiations only, which is why it is declared here and not among the kernel's other arrays.
+template <int NWAVE>
+__device__ __forceinline__ __attribute__((address_space(3))) spl_u32x2 *simple_lists()
+{
+    __shared__ spl_u32x2 s_simple[NWAVE * SPL_SIMPLE_LIST_FUSED];
+    return (__attribute__((address_space(3))) spl_u32x2 *)s_simple;
+}
+
+// The fused pass's simple reads (one aligned op, mapped, in range: run 0 of the classification), counted by the wave that
+// classified them, out of its registers (spl_layout_tile.h: tile_finish calls ask() right behind the classification and count()
+// behind the ranks' barrier): two boundaries, one range, nothing else can happen -- such a read has no record, no rank and no
+// place in the record area.  Very few of them count for anything (three in a hundred on the human-scale sample: a site must lie
+// strictly inside the read), so a thread asks ONE question for all its simple reads -- the span test of spl_simple_span.h: the
+// bucket entries of its least start - 1 and its greatest end - 1, two loads that are on their way while the other runs' prefix
+// sums cross their barrier, and four registers kept across it where a pair of entries a read was sixteen.  A thread whose span
+// holds no site is done.  The simple reads of the others (FLAGGED: two or three threads of a wave) are compacted: their two record
+// words go to the wave's list in LDS (SPL_SIMPLE_LIST_FUSED entries; ballot and mbcnt, the fill count a wave-uniform register, no
+// atomics, only the owning wave touches it -- push_back's idiom), and the wave then takes the list one read a lane: two bucket
+// places, two gathers, two resolves, one commit_range with all lanes in it.  The list is the chunk's, not the tile's: it is
+// drained when it is full (what does not fit goes in behind the drain: no read is dropped) and behind the chunk's last tile, so
+// the drain's memory trip -- nothing else is in flight behind the barrier to hide it -- comes once for 32 listed reads; drained
+// tile by tile the pass was no faster than with eight gathers a thread (profiles/r14_before_after.txt).  A wave with more than SPL_SIMPLE_DENSE_FUSED flagged threads (sites every few bases: up to 256
+// listed reads, a memory trip per 32 of them) takes its flagged threads' reads slot by slot instead, the eight gathers of a
+// thread in one trip, which is what every wave did before round 14.  active = false (a tile taken in parts, whose simple reads
+// were counted when it was looked at in one piece): nothing is asked for or counted.
 template <bool STRANDED, int NARR, int WIN, int R>
 struct SimpleInPlace {
     static constexpr bool in_place = true;
+    static constexpr uint32_t CAP = SPL_SIMPLE_LIST_FUSED, DENSE = SPL_SIMPLE_DENSE_FUSED;
+    static_assert(CAP >= 1 && CAP <= 64, "the list is drained one entry a lane");
+    typedef __attribute__((address_space(3))) spl_u32x2 lds_pair;
     const spl_hot_params &p;
     spl_lds_i32 *lds;
+    lds_pair *lists;       // CAP entries a wave
+    uint32_t &n_list;      // the wave's fill count, the caller's: it lives as long as the chunk (wave-uniform)
     int32_t &wbase;        // the caller's window base: resolved here (staged) on the chunk's first tile, see below
     int32_t shift;
     bool active;           // (workgroup-uniform)
@@ -509,7 +526,8 @@ struct SimpleInPlace {
     bool &wbase_pending;   // (workgroup-uniform)
     const int32_t x_first;
     uint32_t first_first = 0, first_occ = 0;
-    spl_dbk e0[R], e1[R];  // (all that is kept from issue to commit: the record's words are the caller's, and still there)
+    spl_simple_span span = {0, 0}; // (all that is kept from ask to count, with the two entries' words: the records' words are the caller's, and still there)
+    spl_dbk es0 = {0u, 0u, 0u}, es1 = {0u, 0u, 0u};
     __device__ __forceinline__ void ask_base()
     {
         if (wbase_pending) {
@@ -522,28 +540,98 @@ struct SimpleInPlace {
     {
         if (wbase_pending) { uint32_t nv; dbk_resolve(p, x_first, spl_dbk{first_first, first_occ, 0u}, wbase, nv); wbase_pending = false; }
     }
-    __device__ __forceinline__ void issue(int j, bool is_simple, uint32_t w0, uint32_t w1)
+    // run[j], w[j]: the run and the record words of the thread's read j (run 0 = simple)
+    __device__ __forceinline__ void ask(const uint32_t (&run)[R], const uint32_t (&w)[R][6])
     {
-        if (!active || !__any(is_simple)) return; // (wave-uniform: a wave without a simple read in its slots j asks for nothing)
-        const int32_t a = (int32_t)w0 + shift, b = a + (int32_t)(w1 >> 16); // [a, b): the read's bases
-        e0[j] = e1[j] = spl_dbk{0u, 0u, 0u};
-        if (is_simple) { // (only the lanes that hold a simple read load: nothing is fetched for the others' slots)
-            e0[j] = dbk_load2(p, dbk_slot(p, a - 1));
-            e1[j] = dbk_load2(p, dbk_slot(p, b - 1));
+        if (!active) return;
+        spl_span_begin(span);
+#pragma unroll
+        for (int j = 0; j < R; ++j) spl_span_take(span, run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1], shift);
+        es0 = es1 = spl_dbk{0u, 0u, 0u};
+        if (spl_span_any(span)) { // (only the lanes that hold a simple read load)
+            es0 = dbk_load2(p, dbk_slot(p, span.a_min - 1));
+            es1 = dbk_load2(p, dbk_slot(p, span.b_max - 1));
         }
     }
-    __device__ __forceinline__ void commit(int j, bool is_simple, uint32_t w0, uint32_t w1)
+    // One read a lane, its entries there: all 64 lanes together.
+    __device__ __forceinline__ void count_one(const spl_hot_params &q, bool has, uint32_t w0, uint32_t w1, const spl_dbk &e0, const spl_dbk &e1)
     {
-        if (!active || !__any(is_simple)) return; // (the same waves that asked)
-        const int32_t a = (int32_t)w0 + shift, b = a + (int32_t)(w1 >> 16);
-        int32_t ua, ub; uint32_t nva, nvb;
-        dbk_resolve(p, a - 1, e0[j], ua, nva);
-        dbk_resolve(p, b - 1, e1[j], ub, nvb);
-        const int32_t lo = ua + (int32_t)nva;
-        const bool emit = is_simple && ub > lo;
+        int32_t a, b, lo, ub;
+        spl_simple_bases(w0, w1, shift, a, b);
+        const bool emit = spl_simple_range(q.dbase, a, b, e0.first, e0.occ, e1.first, e1.occ, lo, ub) && has;
         uint32_t arr = 0;
-        if (STRANDED) arr = (spl_read_strand(w1 & 0xffffu, p.stranded) == (uint8_t)'-') ? 1u : 0u;
-        if (__any(emit)) commit_range<NARR, WIN>(p, lds, wbase, emit, lo, ub, arr);
+        if (STRANDED) arr = (spl_read_strand(w1 & 0xffffu, q.stranded) == (uint8_t)'-') ? 1u : 0u;
+        if (__any(emit)) commit_range<NARR, WIN>(q, lds, wbase, emit, lo, ub, arr);
+    }
+    __device__ __forceinline__ void ask_one(const spl_hot_params &q, bool has, uint32_t w0, uint32_t w1, spl_dbk &e0, spl_dbk &e1)
+    {
+        int32_t a, b;
+        spl_simple_bases(w0, w1, shift, a, b);
+        e0 = e1 = spl_dbk{0u, 0u, 0u};
+        if (has) {
+            e0 = dbk_load2(q, dbk_slot(q, a - 1));
+            e1 = dbk_load2(q, dbk_slot(q, b - 1));
+        }
+    }
+    // (the wave's list: its place is made where it is used, not held in a scalar register from the tile's top on)
+    __device__ __forceinline__ lds_pair *my_list() const { return lists + (uint32_t)__builtin_amdgcn_readfirstlane((int)(spllay::thread_here() >> 6)) * CAP; }
+    // The list's first n entries (n <= CAP, wave-uniform), one a lane.
+    __device__ __forceinline__ void drain(const spl_hot_params &q, lds_pair *list, uint32_t n)
+    {
+        const uint32_t lane = (uint32_t)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const bool has = lane < n;
+        const spl_u32x2 e = list[has ? lane : 0u];
+        spl_dbk e0, e1;
+        ask_one(q, has, e.x, e.y, e0, e1);
+        count_one(q, has, e.x, e.y, e0, e1);
+    }
+    __device__ __forceinline__ void count(const uint32_t (&run)[R], const uint32_t (&w)[R][6])
+    {
+        if (!active) return;
+        const spl_hot_params &q = p;
+        const bool flagged = spl_span_flagged(q.dbase, span, es0.first, es0.occ, es1.first, es1.occ);
+        const unsigned long long fm = __ballot(flagged);
+        if (!fm) return; // (wave-uniform, like every branch below)
+        if ((uint32_t)__popcll(fm) > DENSE) { // slot by slot: a thread's gathers in one trip
+            spl_dbk e0[R], e1[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) ask_one(q, flagged && run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1], e0[j], e1[j]);
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const bool want = flagged && run[j] == SPL_RC_SIMPLE;
+                if (__any(want)) count_one(q, want, w[j][0], w[j][1], e0[j], e1[j]);
+            }
+            return;
+        }
+        // Every listed read's place in the wave's order (slot 0's reads first, by lane; then slot 1's ...): the fill counts are
+        // wave-uniform, the ranks come from mbcnt.  The list takes CAP of them at a time -- nearly always all there are.
+        uint32_t at[R], total = 0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const bool want = flagged && run[j] == SPL_RC_SIMPLE;
+            const unsigned long long m = __ballot(want);
+            at[j] = want ? total + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) : 0xffffffffu;
+            total += (uint32_t)__popcll(m);
+        }
+        // The list goes on from tile to tile (n_list: the caller's, wave-uniform) and is drained when it is full -- and once more
+        // behind the chunk's last tile (finish) --, so the drain's memory trip and its instructions come once for CAP reads and
+        // not once a tile for the four or five a wave lists there.
+        lds_pair *const list = my_list();
+        for (uint32_t done = 0;;) { // (`done` of this tile's `total` are in the list or through it)
+            const uint32_t room = CAP - n_list;
+#pragma unroll
+            for (int j = 0; j < R; ++j)
+                if (at[j] - done < room) list[n_list + (at[j] - done)] = spl_u32x2{w[j][0], w[j][1]}; // (unsigned: neither the reads behind this pass nor those before it, nor 0xffffffff)
+            if (total - done <= room) { n_list += total - done; break; }
+            drain(q, list, CAP); // (no read is dropped: what did not fit goes in now)
+            n_list = 0; done += room;
+        }
+    }
+    // Behind the chunk's last tile, in front of the barrier that precedes the windows' way to memory: what the list still holds.
+    __device__ __forceinline__ void finish()
+    {
+        if (n_list) drain(p, my_list(), n_list);
+        n_list = 0;
     }
 };
 
@@ -943,6 +1031,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         if constexpr (FUSED) { const spl_u32x2 v = *(__attribute__((address_space(3))) const spl_u32x2 *)(lrec + at); return make_uint2(v.x, v.y); }
         else return ld_g2(cv.rec + (size_t)at);
     };
+    [[maybe_unused]] uint32_t n_simple = 0; // FUSED: entries in the wave's list of simple reads (SimpleInPlace; wave-uniform)
     uint32_t half = 0; // FUSED: 0 = the tile in one piece; 1, 2 = its halves, one after the other (their simple reads are counted already)
     for (;;) { // the chunk's tiles (FUSED), or the chunk in one piece
     if constexpr (FUSED) {
@@ -962,7 +1051,7 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
         uint32_t n[4] = {0, 0, 0, 0};
         bool fits = true;
         if (sp.hi_r > sp.lo_r) { // (uniform; half a tile may be empty)
-            SimpleInPlace<STRANDED, NARR, WIN, RPT> simple{p, lds, wbase, cv.shift, half == 0u, wbase_pending, wbase_pending ? slot_here()->pos0 + cv.shift - 1 : 0};
+            SimpleInPlace<STRANDED, NARR, WIN, RPT> simple{p, lds, simple_lists<NWAVE>(), n_simple, wbase, cv.shift, half == 0u, wbase_pending, wbase_pending ? slot_here()->pos0 + cv.shift - 1 : 0};
             spllay::TileLoads<(int)TILE, RPT> L;
             spllay::tile_issue<(int)TILE, RPT>(p.src, p.src_n_rec, p.src_n_ops, sp, L);
             simple.ask_base();
@@ -1361,6 +1450,10 @@ __global__ __launch_bounds__(FUSED ? SPL_BLOCK_FUSED : SPL_BLOCK) __attribute__(
     }
     } // tiles
     params_here();
+    if constexpr (FUSED) { // (the simple reads still listed: counted before the windows go to memory)
+        bool no_base = false;
+        SimpleInPlace<STRANDED, NARR, WIN, RPT>{p, lds, simple_lists<NWAVE>(), n_simple, wbase, cv.shift, false, no_base, 0}.finish();
+    }
     if constexpr (FUSED) tid = (int)spllay::thread_here(); // (likewise: the hand-over's places are made here, not in front of the tiles)
     if ((tid & 63) == 0) s_qcnt[tid >> 6] = n_front;
     __syncthreads();

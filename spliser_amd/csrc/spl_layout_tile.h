@@ -90,10 +90,10 @@ struct RecordsInLds {
 struct SimpleAsRecords { static constexpr bool in_place = false; };
 // ... or (the fused counting kernel, spl_kernels.hip: SimpleInPlace) the read is COUNTED by the thread that classified it, from
 // the registers it stands in, and has no record at all: in_place = true,
-//   issue(j, is_simple, w0, w1)   asks for what counting the thread's read j needs (its record's two words), right behind the
-//                                 classification: the answers are on their way while the other runs are ranked;
-//   commit(j, is_simple, w0, w1)  counts it, behind the ranks' barrier and the other runs' records (all lanes of a wave together);
-//   staged()                      is called once a tile behind the barrier that follows the ops' stage, before any issue().
+//   ask(run, w)      asks for what counting the thread's reads of run 0 needs (run[j], w[j]: read j's run and record words), right
+//                    behind the classification: the answers are on their way while the other runs are ranked;
+//   count(run, w)    counts them, behind the ranks' barrier and the other runs' records (all lanes of a wave together);
+//   staged()         is called once a tile behind the barrier that follows the ops' stage, before ask().
 // Runs 1 .. 3 then begin at offset 0 of the sink, n[0] comes back 0 and the sink's index counts from 0.
 
 // One tile of C reads -- the cell [cell0, cell0 + C) of the arrays' indexes, or the part [lo, hi) of it a segment has -- by a
@@ -313,13 +313,11 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         run[j] = (runs >> (3 * j)) & 7u;
-        if constexpr (Simple::in_place) {
-            simple.issue(j, run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1]);
-            c01 += run[j] == SPL_RC_MNM ? 0x10000u : 0u;
-        } else
-        c01 += run[j] == SPL_RC_SIMPLE ? 1u : (run[j] == SPL_RC_MNM ? 0x10000u : 0u);
+        if constexpr (Simple::in_place) c01 += run[j] == SPL_RC_MNM ? 0x10000u : 0u;
+        else c01 += run[j] == SPL_RC_SIMPLE ? 1u : (run[j] == SPL_RC_MNM ? 0x10000u : 0u);
         c23 += run[j] == SPL_RC_M2 ? 1u : (run[j] == SPL_RC_OTHER ? 0x10000u : 0u);
     }
+    if constexpr (Simple::in_place) simple.ask(run, w);
 
     // ---- ranks: prefix sums over the lanes (DPP: row shifts, then the rows' totals broadcast), the waves' totals through LDS
     const uint32_t i01 = wave_scan(c01), i23 = wave_scan(c23);
@@ -334,13 +332,8 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
     const uint32_t n0 = t01 & 0xffffu, n1 = t01 >> 16, n2 = t23 & 0xffffu, n3 = t23 >> 16;
     const uint32_t off1 = (n0 * SPL_REC_SIMPLE + 15u) & ~15u, off2 = off1 + n1 * SPL_REC_MNM, off3 = off2 + n2 * SPL_REC_M2;
     n[0] = n0; n[1] = n1; n[2] = n2; n[3] = n3;
-    if (off3 + n3 * SPL_REC_OTHER > room) { // (the whole workgroup: the sink has no room for these records -- none is written)
-        if constexpr (Simple::in_place) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) simple.commit(j, run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1]);
-        }
-        return false;
-    }
+    const bool fits = off3 + n3 * SPL_REC_OTHER <= room; // (the whole workgroup.  No room in the sink for these records: none is written)
+    if (fits) {
     // (reads of each run before this thread's: the waves below, the lanes below) -> byte offsets of the thread's next record of each run
     const uint32_t e01 = b01 + i01 - c01, e23 = b23 + i23 - c23;
     uint32_t at[4] = {(e01 & 0xffffu) * SPL_REC_SIMPLE, off1 + (e01 >> 16) * SPL_REC_MNM, off2 + (e23 & 0xffffu) * SPL_REC_M2, off3 + (e23 >> 16) * SPL_REC_OTHER};
@@ -368,11 +361,9 @@ __device__ __forceinline__ bool tile_finish(const spl_devreads &src, int64_t n_o
         at[2] += r == SPL_RC_M2 ? SPL_REC_M2 : 0u;
         at[3] += r == SPL_RC_OTHER ? SPL_REC_OTHER : 0u;
     }
-    if constexpr (Simple::in_place) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) simple.commit(j, run[j] == SPL_RC_SIMPLE, w[j][0], w[j][1]);
     }
-    return true;
+    if constexpr (Simple::in_place) simple.count(run, w); // (whether the records fit or not: a tile that is taken in parts has its simple reads counted here)
+    return fits;
 }
 
 // Both steps in a row: one chunk ch of C reads (spl_layout_kernel).  *s_first = POS of the chunk's first read in file order (valid

@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_simple_span_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -1042,6 +1042,24 @@ def strand_rule_host(flag, pos, ops, xs=0, cover=None, counters=None):
                                       ctypes.c_uint8(int(xs)), ctypes.c_int64(start.shape[0]), _ptr(start) if start.shape[0] else None,
                                       _ptr(code) if code.shape[0] else None, _ptr(counters)))
     return counters
+
+
+def simple_span_host(site_pos, pos, length, is_simple, shift=0, reads_per_thread=4):
+    """The fused range kernel's rule for a thread's simple reads on the host (``spl_simple_span_host``).  ``pos``, ``length``
+    (1 .. 65535) and ``is_simple`` hold ``reads_per_thread`` reads a thread.  -> (flagged[threads], emits, lo, ub [reads]): whether
+    the span of a thread's simple reads holds a site, and for a flagged thread's simple reads their ranges of distinct positions
+    (0 for every other read)."""
+    site_pos = _arr(site_pos, np.int32)
+    pos, length, is_simple = _arr(pos, np.int32), _arr(length, np.uint16), _arr(is_simple, np.uint8)
+    n = pos.shape[0]
+    if n % reads_per_thread or length.shape[0] != n or is_simple.shape[0] != n:
+        raise ValueError("pos, length and is_simple hold reads_per_thread reads a thread")
+    n_threads = n // reads_per_thread
+    flagged, emits = np.zeros(n_threads, np.uint8), np.zeros(n, np.uint8)
+    lo, ub = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    _check(lib().spl_simple_span_host(_ptr(site_pos), ctypes.c_int64(site_pos.shape[0]), ctypes.c_int64(n_threads), ctypes.c_int(reads_per_thread),
+                                      _ptr(pos), _ptr(length), _ptr(is_simple), ctypes.c_int32(int(shift)), _ptr(flagged), _ptr(emits), _ptr(lo), _ptr(ub)))
+    return flagged.astype(bool), emits.astype(bool), lo, ub
 
 
 def junction_walk_host(ops, pos, min_anchor=0, min_intron=0, max_intron=0):
