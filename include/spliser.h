@@ -489,6 +489,42 @@ int spl_strand_tally(spl_ctx *ctx, const spl_dreads *dr, int64_t n_cover, const 
 int spl_strand_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, uint8_t xs, int64_t n_cover, const int32_t *cover_start,
                          const uint8_t *cover_code, int64_t *inout14);
 
+/* ---- per-base coverage (what the pipeline otherwise needs a sorted, indexed BAM and a second tool for) ------------------------
+ * Replaces a manual step: the reference's README sends the user to IGV whenever something looks wrong, and IGV wants a
+ * coordinate-sorted, indexed BAM, or a coverage track from `bedtools genomecov -bg -split` / deepTools `bamCoverage`.  The
+ * reference has no counterpart.  spl_coverage computes, on the device, over the BAM-native arrays of a FUSED read set taken as
+ * the reads of ONE reference of `length` bases, the per-base read depth of one track as runs.  The rule (csrc/spl_coverage_rule.h):
+ *   eligible    (flag & 0x4) == 0, POS >= 1 and at least one op: secondary, supplementary, duplicate and QC-failed reads count,
+ *               as in bedtools genomecov (narrow them with the decode's read filter: spl_bam_set_filter);
+ *   track       stranded = 0: one track, strand = 0.  stranded = 1 (fr) / 2 (rf): the read belongs to the track check_strand's
+ *               rule gives it (:374-406), and strand = '+' or '-' says which track is computed;
+ *   walk        from the 0-based p = POS - 1 + the segment's shift, in int64: M, = and X cover [p, p + len) and advance; D and N
+ *               advance without covering (a deletion is a gap, as an intron is: genomecov's -split); I, S, H, P and the op codes
+ *               above 8 do nothing, nor does an op of length zero; covering ops that abut (10M2I5M) are ONE block;
+ *   clipping    blocks are clipped to [0, length); a read that loses a base that way is "past the end", a read left without a
+ *               covered base does not contribute.
+ * The result: runs (start, end, depth), 0-based and half-open, ascending, maximal (the depth differs from both neighbours'), only
+ * depth > 0; the depth is an exact uint32 (sums mod 2^32: exact below 2^32 reads over a base), the same for the reads in any
+ * order.  Parity with bedtools / deepTools is intended and not pinned by a test.  The call synchronises.  SPL_ERR_ARG: a set that
+ * is not fused; length outside 1 .. 2^31 - 2; stranded outside 0..2; a strand that does not fit stranded.  A set without a single
+ * read gives no run.
+ * spl_coverage_totals: out5 = runs, reads seen (the whole set's, whatever the track), reads that contributed to this track, reads
+ * past the end, covered bases (= the sum of (end - start) * depth over the runs).  spl_coverage_download: the runs into caller
+ * arrays of `runs` entries (any may be NULL).  spl_coverage_free: NULL is allowed.
+ * spl_coverage_rule_host: the same rule for one read on the host (test hook; no file, no GPU): its clipped blocks on the track,
+ * *n_out of them (the first `capacity` are written), *past_end_out = it lost a base to the clipping.
+ * spl_bedgraph_append: n runs of one chromosome appended to `path` as "chrom\tstart\tend\tvalue\n" lines; value = the depth as an
+ * integer or, with per_million_of = N > 0, the text Python's repr(depth * 1000000 / N) gives.  No GPU involved. */
+typedef struct spl_cov spl_cov;
+int spl_coverage(spl_ctx *ctx, const spl_dreads *dr, int64_t length, int stranded, int strand /* 0, '+', '-' */, spl_cov **out);
+int spl_coverage_totals(const spl_cov *cov, int64_t *out5);
+int spl_coverage_download(spl_ctx *ctx, const spl_cov *cov, int32_t *start, int32_t *end, uint32_t *depth);
+void spl_coverage_free(spl_ctx *ctx, spl_cov *cov);
+int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int64_t length, int stranded, int strand,
+                           int capacity, int64_t *blk_start, int64_t *blk_end, int *n_out, int *past_end_out);
+int spl_bedgraph_append(const char *path, const char *chrom, int64_t n, const int32_t *start, const int32_t *end, const uint32_t *depth,
+                        int64_t per_million_of /* 0: integers */);
+
 /* ---- the fused counting kernel's rule for simple reads, on the host (test hook; no file, no GPU) ---------------------------
  * A simple read (one aligned op) with bases [a, b), a = pos + shift, b = a + len, counts for the sites t with t and t + 1 both under it: the
  * distinct positions [lo, ub), lo = number of site positions <= a - 1, ub = number of site positions < b - 1.  The kernel asks one

@@ -26,6 +26,9 @@ own output -- its reads are coordinate-sorted on the GPU after the decode instea
 ``-B`` (every command that has it) also takes SAM text as the aligner writes it, and that text compressed -- BGZF (``bgzip``,
 ``samtools view -O sam``) or gzip (``aligner | gzip``): what the file inflates to says which, no flag.  The text is parsed on the GPU;
 BGZF is inflated there too, plain gzip by one host thread; a file the strict rule declines is read by the Python reader.
+Extra sub-command ``coverage -B x.bam -o PREFIX [-c CHROM] [--isStranded -s fr|rf] [--perMillion]`` writes ``PREFIX.bedgraph`` (stranded:
+``PREFIX.plus.bedgraph`` and ``PREFIX.minus.bedgraph``): per-base read depth in runs, reduced on the GPU from the decode -- the
+coverage track of the look at the alignments the reference's README asks for, without a sorted, indexed BAM (``coverage.py``).
 Not read: CRAM, a pipe, and compressed text that has no ``@`` header line (uncompressed, the Python reader still takes that).
 """
 import argparse
@@ -161,6 +164,22 @@ def build_parser():
     s.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(s)
     _engine_flags(s)
+    v = sub.add_parser("coverage", help="(this build only) per-base read depth of the alignment file as a bedGraph, reduced on the GPU from the decode: "
+                                        "no sorted, indexed BAM needed to look at the data")
+    v.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    v.add_argument("-o", "--outputPath", dest="outputPath", required=True,
+                   help="output prefix: .bedgraph is appended, or .plus.bedgraph and .minus.bedgraph with --isStranded")
+    v.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False, help="optional: one chromosome only")
+    v.add_argument("--isStranded", dest="isStranded", default=False, action="store_true", help="one track per strand of the reads (check_strand's rule)")
+    v.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
+                   help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
+    v.add_argument("--perMillion", dest="perMillion", default=False, action="store_true",
+                   help="values per million mapped reads: depth * 1000000 / the library size --flagstat logs (under the filters)")
+    v.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
+    v.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    v.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _filter_flags(v)
+    _engine_flags(v)
     return parser
 
 
@@ -212,15 +231,19 @@ def main(argv=None):
         print(kwargs.get("qGene"))
         print(kwargs.get("annotationFile"))
         parser.error("--gene requires --annotationFile and --maxIntronSize")
-    elif command in ("process", "combine", "combineShallow", "junctions") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
+    elif command in ("process", "combine", "combineShallow", "junctions", "coverage") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
+    if command == "coverage" and kwargs.get("strandedType") == "auto":
+        parser.error("coverage: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
+    if command == "coverage" and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
+        parser.error("coverage: --strandedType/-s must be fr or rf")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":
         parser.error("-s auto and --strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
     if command in ("process", "junctions", "strandedness") and kwargs.get("minEvidence") is not None and kwargs["minEvidence"] < 0:
         parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -263,6 +286,9 @@ def main(argv=None):
     elif command == "strandedness":
         from .strandedness import strandedness
         strandedness(devices=devices, threads=threads, **kwargs)
+    elif command == "coverage":
+        from .coverage import coverage
+        coverage(devices=devices, threads=threads, **kwargs)
     elif command == "flagstat":
         from .flagstat import flagstat
         flagstat(devices=devices, threads=threads, **kwargs)

@@ -37,6 +37,8 @@
 #include "spl_junction_fused.h"
 #include "spl_strand.h"
 #include "spl_strand_rule.h"
+#include "spl_coverage.h"
+#include "spl_coverage_rule.h"
 #include "spl_simple_span.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
@@ -4128,6 +4130,141 @@ extern "C" int spl_strand_rule_host(uint32_t flag, int32_t pos, const uint32_t *
         if (cover_start[k] <= cover_start[k - 1]) return spl_set_error(SPL_ERR_ARG, "spl_strand_rule_host: the cover map is not strictly ascending at entry %lld", (long long)k);
     const uint32_t bits = spl_strand_read_bits(flag, (int64_t)pos, ops, n_ops, xs, n_cover, cover_start, cover_code);
     for (int k = 0; k < SPL_STRAND_COUNTERS; ++k) inout14[k] += (bits >> k) & 1u;
+    return SPL_OK;
+}
+
+// ---- per-base coverage (spl_coverage.hip; the rule is spl_coverage_rule.h) ---------------------------------------------------
+// The runs of one track: what spl_coverage leaves on the host, and what it counted.
+struct spl_cov {
+    std::vector<int32_t> start, end;
+    std::vector<uint32_t> depth;
+    int64_t totals[5] = {0, 0, 0, 0, 0}; // runs, reads seen, reads that contributed, reads past the end, covered bases
+};
+
+// mark per segment into one zeroed difference array, compact (count, scan, emit), scan of the deltas; the boundaries come down and
+// those with a depth of zero are dropped here.
+extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, spl_cov **out)
+{
+    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_coverage: null argument");
+    *out = nullptr;
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_coverage: the read set is not finished (spl_reads_finish)");
+    if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_coverage: length must be in 1 .. 2^31 - 2, not %lld", (long long)length);
+    if (stranded < 0 || stranded > 2) return spl_set_error(SPL_ERR_ARG, "spl_coverage: stranded must be 0 (one track), 1 (fr) or 2 (rf)");
+    if (!spl_cov_args_fit(stranded, strand))
+        return spl_set_error(SPL_ERR_ARG, "spl_coverage: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2");
+    std::unique_ptr<spl_cov> cov(new spl_cov());
+    if (dr->segs.empty()) { // (a set without a read has no arrays to be fused of, and covers nothing)
+        *out = cov.release();
+        return SPL_OK;
+    }
+    if (!(dr->fused && dr->groups.size() == 1))
+        return spl_set_error(SPL_ERR_ARG, "spl_coverage needs a fused read set (all of it from one device decode or one spl_soa_upload)");
+    const spl_dreads::Group &g = dr->groups[0];
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t n_tiles = (length + SPL_COV_POS_TILE - 1) / SPL_COV_POS_TILE;
+    const size_t diff_bytes = 4 * (size_t)spl_dev_cov_diff_words(length);
+    DevBuf d_diff, d_out, d_tiles, d_work, d_pos, d_delta;
+    HIP_TRY(d_diff.get(diff_bytes, c->stream));
+    HIP_TRY(d_out.get(8 * (SPL_COV_COUNTERS + 1), c->stream));
+    HIP_TRY(d_tiles.get(4 * (size_t)n_tiles, c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * (SPL_COV_COUNTERS + 1), c->stream));
+    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+    {
+        double bytes = (double)diff_bytes; // what mark must move at least: the array cleared, 10 bytes a read and its ops
+        for (const spl_dreads::Segment &seg : dr->segs) bytes += 10.0 * (double)seg.n_reads + 4.0 * (double)seg.n_ops;
+        splprof::Scope prof("spl_cov_mark_kernel", c->stream, bytes);
+        HIP_TRY(hipMemsetAsync(d_diff.p, 0, diff_bytes, c->stream));
+        for (const spl_dreads::Segment &seg : dr->segs) {
+            const spl_layout_seg &ls = g.segs[seg.group_seg];
+            if (ls.n_reads <= 0) continue;
+            const int rc = spl_dev_launch_cov_mark(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, length, stranded, strand, d_diff.as<uint32_t>(),
+                                                   d_out.as<unsigned long long>(), c->stream);
+            if (rc) return spl_set_error(SPL_ERR_HIP, "coverage mark kernel launch: %s", hipGetErrorString((hipError_t)rc));
+        }
+    }
+    uint32_t n_bound = 0;
+    {
+        splprof::Scope prof("spl_cov_compact", c->stream, 2.0 * 4.0 * (double)length); // (the array read twice; the boundaries are few beside it)
+        int rc = spl_dev_launch_cov_count(d_diff.as<uint32_t>(), length, d_tiles.as<uint32_t>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "coverage count kernel launch: %s", hipGetErrorString((hipError_t)rc));
+        HIP_TRY(d_work.get(spl_dev_sort_work_bytes((uint64_t)n_tiles), c->stream));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_tiles.as<uint32_t>(), (uint64_t)n_tiles, d_work.p, c->stream));
+        HIP_TRY(hipMemcpyAsync(&n_bound, d_tiles.as<uint32_t>() + (n_tiles - 1), 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream)); // (the buffers below are sized from the count)
+        if (n_bound) {
+            HIP_TRY(d_pos.get(4 * (size_t)n_bound, c->stream));
+            HIP_TRY(d_delta.get(4 * (size_t)n_bound, c->stream));
+            rc = spl_dev_launch_cov_emit(d_diff.as<uint32_t>(), length, d_tiles.as<uint32_t>(), d_pos.as<int32_t>(), d_delta.as<uint32_t>(), (int64_t)n_bound, c->stream);
+            if (rc) return spl_set_error(SPL_ERR_HIP, "coverage emit kernel launch: %s", hipGetErrorString((hipError_t)rc));
+        }
+    }
+    std::vector<int32_t> h_pos(n_bound);
+    std::vector<uint32_t> h_depth(n_bound);
+    if (n_bound) {
+        {
+            splprof::Scope prof("spl_cov_scan", c->stream, 2.0 * 4.0 * (double)n_bound);
+            if (spl_dev_sort_work_bytes(n_bound) > spl_dev_sort_work_bytes((uint64_t)n_tiles)) { d_work.release(); HIP_TRY(d_work.get(spl_dev_sort_work_bytes(n_bound), c->stream)); }
+            HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_delta.as<uint32_t>(), n_bound, d_work.p, c->stream)); // delta -> the depth behind each boundary
+        }
+        HIP_TRY(hipMemcpyAsync(h_pos.data(), d_pos.p, 4 * (size_t)n_bound, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h_depth.data(), d_delta.p, 4 * (size_t)n_bound, hipMemcpyDeviceToHost, c->stream));
+    }
+    unsigned long long sums[SPL_COV_COUNTERS + 1] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(sums, d_out.p, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    size_t n_runs = 0;
+    for (uint32_t k = 0; k < n_bound; ++k) n_runs += h_depth[k] != 0u;
+    cov->start.reserve(n_runs); cov->end.reserve(n_runs); cov->depth.reserve(n_runs);
+    for (uint32_t k = 0; k < n_bound; ++k) {
+        if (h_depth[k] == 0u) continue;
+        cov->start.push_back(h_pos[k]);
+        cov->end.push_back(k + 1 < n_bound ? h_pos[k + 1] : (int32_t)length);
+        cov->depth.push_back(h_depth[k]);
+    }
+    cov->totals[0] = (int64_t)n_runs;
+    for (int k = 0; k < SPL_COV_COUNTERS + 1; ++k) cov->totals[k + 1] = (int64_t)sums[k];
+    *out = cov.release();
+    return SPL_OK;
+}
+
+extern "C" int spl_coverage_totals(const spl_cov *cov, int64_t *out5)
+{
+    if (!cov || !out5) return spl_set_error(SPL_ERR_ARG, "spl_coverage_totals: null argument");
+    memcpy(out5, cov->totals, sizeof cov->totals);
+    return SPL_OK;
+}
+
+extern "C" int spl_coverage_download(spl_ctx *c, const spl_cov *cov, int32_t *start, int32_t *end, uint32_t *depth)
+{
+    if (!c || !cov) return spl_set_error(SPL_ERR_ARG, "spl_coverage_download: null argument");
+    const size_t n = cov->start.size(); // (the runs are on the host already: spl_coverage dropped the zero-depth boundaries there)
+    if (n && start) memcpy(start, cov->start.data(), 4 * n);
+    if (n && end) memcpy(end, cov->end.data(), 4 * n);
+    if (n && depth) memcpy(depth, cov->depth.data(), 4 * n);
+    return SPL_OK;
+}
+
+extern "C" void spl_coverage_free(spl_ctx *, spl_cov *cov) { delete cov; }
+
+// The rule itself for one read: its clipped blocks on the track, no GPU involved (test hook).
+extern "C" int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int64_t length, int stranded, int strand, int capacity,
+                                      int64_t *blk_start, int64_t *blk_end, int *n_out, int *past_end_out)
+{
+    if ((n_ops && !ops) || !n_out || capacity < 0 || (capacity && (!blk_start || !blk_end))) return spl_set_error(SPL_ERR_ARG, "spl_coverage_rule_host: null argument");
+    if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_coverage_rule_host: length must be in 1 .. 2^31 - 2");
+    if (!spl_cov_args_fit(stranded, strand)) return spl_set_error(SPL_ERR_ARG, "spl_coverage_rule_host: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2");
+    struct HostOps { const uint32_t *p; uint32_t operator()(uint32_t k) const { return p[k]; } };
+    struct Keep {
+        int capacity, n; int64_t *s, *e;
+        void operator()(int64_t a, int64_t b) { if (n < capacity) { s[n] = a; e[n] = b; } ++n; }
+    } keep{capacity, 0, blk_start, blk_end};
+    uint32_t bits = 0;
+    if (spl_cov_eligible(flag, (int64_t)pos, n_ops) && spl_cov_on_track(flag, stranded, strand)) {
+        int64_t covered = 0;
+        bits = spl_cov_walk(HostOps{ops}, n_ops, (int64_t)pos - 1 + (int64_t)shift, length, keep, &covered);
+    }
+    *n_out = keep.n;
+    if (past_end_out) *past_end_out = (bits & SPL_COV_PAST_END) ? 1 : 0;
     return SPL_OK;
 }
 

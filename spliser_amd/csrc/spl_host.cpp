@@ -208,6 +208,35 @@ extern "C" int spl_tsv_append(const char *path, const char *chrom, int64_t n_sit
     return spl_tsv_append_many(path, 1, &r, cryptic);
 }
 
+// ---- bedGraph lines (the `coverage` command) ---------------------------------------------------------------------------------
+// n runs of one chromosome appended to a file: "chrom\tstart\tend\tvalue\n", value the depth as an integer, or -- per_million_of
+// = N > 0 -- what Python's repr(depth * 1000000 / N) gives: depth * 10^6 is below 2^53, so the one division is the double's.
+extern "C" int spl_bedgraph_append(const char *path, const char *chrom, int64_t n, const int32_t *start, const int32_t *end, const uint32_t *depth, int64_t per_million_of)
+{
+    if (!path || !chrom || n < 0 || per_million_of < 0 || (n && (!start || !end || !depth))) return spl_set_error(SPL_ERR_ARG, "spl_bedgraph_append: bad argument");
+    FILE *f = fopen(path, "ab");
+    if (!f) return spl_set_error(SPL_ERR_IO, "cannot open %s for appending", path);
+    const size_t chrom_len = strlen(chrom);
+    std::string out;
+    bool ok = true;
+    char num[64];
+    for (int64_t i = 0; i < n && ok; ++i) {
+        out.append(chrom, chrom_len);
+        out.push_back('\t');
+        out.append(num, fmt_int(num, (int64_t)start[i]));
+        out.push_back('\t');
+        out.append(num, fmt_int(num, (int64_t)end[i]));
+        out.push_back('\t');
+        if (per_million_of) out.append(num, splfmt::fmt_repr(num, (double)((uint64_t)depth[i] * 1000000ull) / (double)per_million_of));
+        else out.append(num, fmt_int(num, (int64_t)depth[i]));
+        out.push_back('\n');
+        if (out.size() >= (1u << 20)) { ok = fwrite(out.data(), 1, out.size(), f) == out.size(); out.clear(); }
+    }
+    if (ok && !out.empty()) ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+    if (fclose(f) != 0) ok = false;
+    return ok ? SPL_OK : spl_set_error(SPL_ERR_IO, "write error on %s", path);
+}
+
 // ---- Steps 0-1 text input: the BED12 junction file and the gene lines of the annotation, as columns ---------------------
 // What findAlphaCounts reads from a line (SpliSER_v0_1_8.py:257-277) and what createGenes keeps of a gene line (:81-87, with
 // HTSeq's conventions: start = column 4 - 1, end = column 5, name = value of the first attribute).  Files of this kind have

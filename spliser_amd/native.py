@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_simple_span_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_simple_span_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -85,7 +85,7 @@ def lib():
         L.spl_bam_ref_length.restype = ctypes.c_int64
         L.spl_bam_n_records.restype = ctypes.c_int64
         L.spl_bam_text_blocks.restype = ctypes.c_int64
-        for name in ("spl_destroy", "spl_sites_free", "spl_reads_free", "spl_soa_free", "spl_bam_close", "spl_text_close", "spl_combine_close"):
+        for name in ("spl_destroy", "spl_sites_free", "spl_reads_free", "spl_soa_free", "spl_bam_close", "spl_text_close", "spl_combine_close", "spl_coverage_free"):
             getattr(L, name).restype = None
         for name in ("spl_combine_rows", "spl_combine_region_runs", "spl_combine_n_sites", "spl_combine_n_gap_sites", "spl_combine_skipped"):
             getattr(L, name).restype = ctypes.c_int64
@@ -454,6 +454,24 @@ class DeviceReads(object):
         _check(lib().spl_strand_tally(self.ctx._h, self._h, ctypes.c_int64(start.shape[0]), _ptr(start) if start.shape[0] else None,
                                       _ptr(code) if code.shape[0] else None, _ptr(out)))
         return out
+
+    def coverage(self, length, stranded=0, strand=0):
+        """Per-base read depth of this (finished, fused) set, taken as the reads of one reference of ``length`` bases, on the device
+        (``spl_coverage``): -> (start int32, end int32, depth uint32, totals) -- the runs, 0-based and half-open, ascending, maximal,
+        depth > 0 only; ``totals``: dict of runs, reads_seen, contributed, past_end, covered_bases.  ``stranded``: 0, 1 (fr) or 2
+        (rf); ``strand``: 0 with ``stranded=0``, else ``'+'`` or ``'-'`` (a character or its code): the track."""
+        strand = ord(strand) if isinstance(strand, (str, bytes)) else int(strand)
+        h = ctypes.c_void_p()
+        _check(lib().spl_coverage(self.ctx._h, self._h, ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.byref(h)))
+        try:
+            t = np.zeros(5, np.int64)
+            _check(lib().spl_coverage_totals(h, _ptr(t)))
+            n = int(t[0])
+            start, end, depth = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.uint32)
+            _check(lib().spl_coverage_download(self.ctx._h, h, _ptr(start), _ptr(end), _ptr(depth)))
+        finally:
+            lib().spl_coverage_free(self.ctx._h, h)
+        return start, end, depth, dict(zip(COVERAGE_TOTALS, t.tolist()))
 
     def free(self):
         if self._h:
@@ -1042,6 +1060,34 @@ def strand_rule_host(flag, pos, ops, xs=0, cover=None, counters=None):
                                       ctypes.c_uint8(int(xs)), ctypes.c_int64(start.shape[0]), _ptr(start) if start.shape[0] else None,
                                       _ptr(code) if code.shape[0] else None, _ptr(counters)))
     return counters
+
+
+COVERAGE_TOTALS = ("runs", "reads_seen", "contributed", "past_end", "covered_bases")
+
+
+def coverage_rule_host(flag, pos, ops, length, shift=0, stranded=0, strand=0):
+    """The coverage rule for one read on the host (``spl_coverage_rule_host``): -> ([(start, end)] its clipped blocks on the track,
+    whether it lost a base to the clipping)."""
+    ops = np.ascontiguousarray(ops, np.uint32)
+    strand = ord(strand) if isinstance(strand, (str, bytes)) else int(strand)
+    cap = max(1, ops.shape[0])
+    s, e = np.empty(cap, np.int64), np.empty(cap, np.int64)
+    n, past = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().spl_coverage_rule_host(ctypes.c_uint32(int(flag)), ctypes.c_int32(int(pos)), _ptr(ops) if ops.shape[0] else None, ctypes.c_uint32(ops.shape[0]),
+                                        ctypes.c_int32(int(shift)), ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.c_int(cap),
+                                        _ptr(s), _ptr(e), ctypes.byref(n), ctypes.byref(past)))
+    return list(zip(s[:n.value].tolist(), e[:n.value].tolist())), bool(past.value)
+
+
+def bedgraph_append(path, chrom, start, end, depth, per_million_of=0):
+    """Runs of one chromosome appended to a bedGraph file (``spl_bedgraph_append``): ``chrom\tstart\tend\tvalue`` lines, the value
+    the depth or, with ``per_million_of=N``, what ``repr(depth * 1000000 / N)`` gives."""
+    start, end, depth = _arr(start, np.int32), _arr(end, np.int32), _arr(depth, np.uint32)
+    n = start.shape[0]
+    if end.shape[0] != n or depth.shape[0] != n:
+        raise ValueError("start, end and depth are three arrays of one length")
+    _check(lib().spl_bedgraph_append(os.fsencode(path), chrom.encode("utf-8"), ctypes.c_int64(n), _ptr(start) if n else None, _ptr(end) if n else None,
+                                     _ptr(depth) if n else None, ctypes.c_int64(int(per_million_of))))
 
 
 def simple_span_host(site_pos, pos, length, is_simple, shift=0, reads_per_thread=4):
