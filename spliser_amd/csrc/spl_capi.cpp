@@ -328,10 +328,17 @@ struct spl_ctx {
     // a segment's records into one of them while the DMA engine drains the others on a stream of their own.  Locked with
     // hipHostRegister: on this stack that costs 0.7 ms per 32 MiB where hipHostMalloc costs 5 (tools/micro/hostmem.cpp), and
     // copies run at 50...55 GB/s from pieces of this size (20 GB/s from 8 MiB pieces).
-    struct Stage { char *host = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; bool busy = false, locked = false; };
+    // A buffer's cycle: next_stage(), wait() while its last copy is under way, fill it, queue its copies, mark() it behind them.
+    struct Stage {
+        char *host = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; bool busy = false, locked = false;
+        hipError_t wait() { const bool was = busy; busy = false; return was ? hipEventSynchronize(done) : hipSuccess; }
+        hipError_t mark(hipStream_t s) { busy = true; return hipEventRecord(done, s); }
+    };
     size_t stage_mb = 32; // size of a staging buffer (set when the ring is made)
     std::vector<Stage> stage;
     size_t stage_next = 0;
+    Stage &next_stage() { Stage &st = stage[stage_next]; stage_next = (stage_next + 1) % stage.size(); return st; }
+    void stages_idle() { for (Stage &st : stage) st.busy = false; } // (behind a wait for the copy stream)
     hipStream_t copy = nullptr;
     hipEvent_t ev_copy = nullptr;
     int pack_threads = 1;
@@ -872,18 +879,11 @@ extern "C" int spl_sites_upload(spl_ctx *c, const spl_sites *s, spl_dsites **out
     // call), this way the copy engine runs at its 50 GB/s while the next buffer is being filled.
     hipError_t r = hipSuccess;
     if (ensure_stage(c) != SPL_OK) r = hipErrorOutOfMemory;
-    size_t fill = 0;        // bytes used of the current staging buffer
-    bool open_buf = false;  // the current buffer has copies in flight that no event covers yet
-    auto next_buffer = [&]() -> hipError_t {
-        hipError_t q = hipSuccess;
-        if (open_buf) {
-            spl_ctx::Stage &cur = c->stage[c->stage_next];
-            q = hipEventRecord(cur.done, c->copy);
-            cur.busy = true;
-            c->stage_next = (c->stage_next + 1) % c->stage.size();
-            open_buf = false;
-        }
-        fill = 0;
+    spl_ctx::Stage *st = nullptr; // the staging buffer being packed: its copies are in flight, no event covers them yet
+    size_t fill = 0;              // bytes used of it
+    auto next_buffer = [&]() -> hipError_t { // (the current one is done with)
+        const hipError_t q = st ? st->mark(c->copy) : hipSuccess;
+        st = nullptr;
         return q;
     };
     auto up = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
@@ -891,14 +891,17 @@ extern "C" int spl_sites_upload(spl_ctx *c, const spl_sites *s, spl_dsites **out
         const char *from = (const char *)src;
         char *to = (char *)dst;
         while (bytes) {
-            spl_ctx::Stage *st = &c->stage[c->stage_next];
-            if (fill + 64 > st->bytes) { const hipError_t q = next_buffer(); if (q != hipSuccess) return q; st = &c->stage[c->stage_next]; }
-            if (fill == 0 && st->busy) { const hipError_t q = hipEventSynchronize(st->done); st->busy = false; if (q != hipSuccess) return q; }
+            if (st && fill + 64 > st->bytes) { const hipError_t q = next_buffer(); if (q != hipSuccess) return q; }
+            if (!st) {
+                st = &c->next_stage();
+                fill = 0;
+                const hipError_t q = st->wait();
+                if (q != hipSuccess) return q;
+            }
             const size_t n = std::min(bytes, st->bytes - fill);
             memcpy(st->host + fill, from, n);
             const hipError_t q = hipMemcpyAsync(to, st->host + fill, n, hipMemcpyHostToDevice, c->copy);
             if (q != hipSuccess) return q;
-            open_buf = true;
             fill = (fill + n + 63) & ~(size_t)63;
             from += n; to += n; bytes -= n;
         }
@@ -1056,6 +1059,55 @@ static void free_stage(spl_ctx *c)
     c->copy = nullptr;
 }
 
+// `bytes` bytes to `dst` on the device through the context's staging ring on the copy stream, for the one thread of a call that
+// sends: take the next pinned buffer, wait while its last copy is under way, have it filled -- fill(host, room, done) -> the bytes
+// it put there, at most `room`; 0 ends the sending early --, queue the copy, record the buffer's event.  *sent_out: the bytes queued.
+namespace {
+template <class Fill> hipError_t ring_send(spl_ctx *c, char *dst, uint64_t bytes, Fill &&fill, uint64_t *sent_out = nullptr)
+{
+    hipError_t q = hipSuccess;
+    uint64_t done = 0;
+    while (done < bytes && q == hipSuccess) {
+        spl_ctx::Stage &sg = c->next_stage();
+        q = sg.wait();
+        if (q != hipSuccess) break;
+        const size_t n = fill(sg.host, (size_t)std::min<uint64_t>(bytes - done, sg.bytes), done);
+        if (!n) break;
+        q = hipMemcpyAsync(dst + done, sg.host, n, hipMemcpyHostToDevice, c->copy);
+        if (q == hipSuccess) q = sg.mark(c->copy);
+        done += n;
+    }
+    if (sent_out) *sent_out = done;
+    return q;
+}
+// A stretch of the file into a staging buffer: pread when the file is open (the page cache's bytes straight into the pinned
+// buffer; copying out of the mapping instead faults 4 KiB pages into this process's page tables, a million of them for a
+// 3.6 GB file, and every other run of a loop took 0.4 s longer for it), the mapping otherwise.
+struct CopyJob { char *dst; const char *src; size_t n, per; int fd; size_t file_off; };
+void copy_slice(size_t k, void *arg)
+{
+    const CopyJob &j = *(const CopyJob *)arg;
+    size_t a = k * j.per;
+    const size_t b = std::min(j.n, a + j.per);
+    while (j.fd >= 0 && a < b) {
+        const ssize_t got = pread(j.fd, j.dst + a, b - a, (off_t)(j.file_off + a));
+        if (got <= 0) break; // (whatever is left comes from the mapping)
+        a += (size_t)got;
+    }
+    if (a < b) memcpy(j.dst + a, j.src + a, b - a);
+}
+// ... ring_send's filling from the file: `room` bytes from file offset file_off + done, eight threads a piece (copy_slice)
+struct FileFill {
+    const uint8_t *image; int fd; uint64_t file_off;
+    size_t operator()(char *host, size_t room, uint64_t done) const
+    {
+        CopyJob job{host, (const char *)image + file_off + done, room, (room + 7) / 8, fd, (size_t)(file_off + done)};
+        splpack::parallel_for((room + job.per - 1) / std::max<size_t>(job.per, 1), 8, copy_slice, &job);
+        return room;
+    }
+};
+} // namespace
+
 namespace {
 struct EmitJob {
     const splpack::Source *src;
@@ -1107,9 +1159,9 @@ static int add_segment(spl_ctx *c, spl_dreads *d, const splpack::Source &src, in
     auto wide_end = [&](size_t k) { return k + 1 < n_chunks ? plan.chunks[k + 1].wide_off : plan.n_wide; };
     hipError_t q = hipSuccess;
     for (size_t c0 = 0; c0 < n_chunks && q == hipSuccess;) {
-        spl_ctx::Stage &st = c->stage[c->stage_next];
-        c->stage_next = (c->stage_next + 1) % c->stage.size();
-        if (st.busy) { q = hipEventSynchronize(st.done); st.busy = false; if (q != hipSuccess) break; }
+        spl_ctx::Stage &st = c->next_stage();
+        q = st.wait();
+        if (q != hipSuccess) break;
         const uint64_t r0 = plan.chunks[c0].rec_off, w0 = plan.chunks[c0].wide_off;
         size_t c1 = c0;
         auto need = [&](size_t k) { return align_up((size_t)(rec_end(k) - r0)) + 4 * (size_t)(wide_end(k) - w0); };
@@ -1128,7 +1180,7 @@ static int add_segment(spl_ctx *c, spl_dreads *d, const splpack::Source &src, in
         if (q == hipSuccess && wide_span)
             q = hipMemcpyAsync(seg.slab + rec_al + 4 * w0, host + align_up(rec_span), 4 * wide_span, hipMemcpyHostToDevice, c->copy);
         if (q == hipSuccess && !big.empty()) q = hipStreamSynchronize(c->copy);
-        else if (q == hipSuccess) { q = hipEventRecord(st.done, c->copy); st.busy = true; }
+        else if (q == hipSuccess) q = st.mark(c->copy);
         if (q == hipSuccess && c->stage_timing) {
             float ms = 0;
             (void)hipEventRecord(c->ev_t1, c->copy);
@@ -1195,22 +1247,6 @@ struct DevBuf {
     hipError_t get(size_t bytes, hipStream_t) { return devmem::get(&p, bytes ? bytes : 16, 'b'); }
     template <class T> T *as() const { return (T *)p; }
 };
-// A stretch of the file into a staging buffer: pread when the file is open (the page cache's bytes straight into the pinned
-// buffer; copying out of the mapping instead faults 4 KiB pages into this process's page tables, a million of them for a
-// 3.6 GB file, and every other run of a loop took 0.4 s longer for it), the mapping otherwise.
-struct CopyJob { char *dst; const char *src; size_t n, per; int fd; size_t file_off; };
-void copy_slice(size_t k, void *arg)
-{
-    const CopyJob &j = *(const CopyJob *)arg;
-    size_t a = k * j.per;
-    const size_t b = std::min(j.n, a + j.per);
-    while (j.fd >= 0 && a < b) {
-        const ssize_t got = pread(j.fd, j.dst + a, b - a, (off_t)(j.file_off + a));
-        if (got <= 0) break; // (whatever is left comes from the mapping)
-        a += (size_t)got;
-    }
-    if (a < b) memcpy(j.dst + a, j.src + a, b - a);
-}
 } // namespace
 
 // What spl_bam_decode_device leaves on the device (and what spl_soa_upload brings up): placed records, BAM-native, and where each
@@ -1235,6 +1271,110 @@ static void free_device_reads(void *h)
     devmem::put(r->pos); devmem::put(r->flag); devmem::put(r->cig_off); devmem::put(r->cigar); devmem::put(r->xs);
     if (have) (void)hipSetDevice(cur);
     delete r;
+}
+
+// What a decoder's extraction writes, window by window: the five arrays of a DeviceReads and the records' reference ids beside
+// them, with the room they have and what is used of it.  Both decoders (ShareDecode, SamDecode) grow them here, RecordSort swaps
+// its sorted copy in, and find_runs / hand_over make the DeviceReads of them.
+struct RecordArrays {
+    DevBuf pos, flag, cig_off, cigar, tid, xs; // (xs only where want_xs)
+    uint64_t cap_rec = 0, cap_ops = 0, n_rec = 0, n_ops = 0;
+    bool want_xs = false;
+    struct Run { uint64_t first; int32_t tid; uint32_t op; }; // a reference's records: the first one, the id, its first op
+
+    // Room for want_rec records and want_ops ops, each limit raised only where it rises: an array at a time anew, what is there
+    // (n_rec records, n_rec + 1 offsets, n_ops ops) moved device to device on `st`, which is waited for behind every move -- the
+    // old array goes back to the pool behind that wait.  The first reservation moves nothing and waits for nothing.
+    int reserve(uint64_t want_rec, uint64_t want_ops, hipStream_t st)
+    {
+        auto grow = [&](DevBuf &b, size_t elem, uint64_t n, uint64_t used) -> int {
+            DevBuf fresh;
+            HIP_TRY(fresh.get(elem * (size_t)n, st));
+            if (b.p && used) {
+                HIP_TRY(hipMemcpyAsync(fresh.p, b.p, elem * (size_t)used, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+            std::swap(b.p, fresh.p);
+            return SPL_OK; // (fresh's destructor gives the old array back)
+        };
+        if (want_rec > cap_rec) {
+            const bool first = !cig_off.p;
+            int rc = grow(pos, 4, want_rec, n_rec);
+            if (rc == SPL_OK) rc = grow(flag, 2, want_rec, n_rec);
+            if (rc == SPL_OK) rc = grow(tid, 4, want_rec, n_rec);
+            if (rc == SPL_OK) rc = grow(cig_off, 4, want_rec + 1, n_rec + 1);
+            if (rc == SPL_OK && want_xs) rc = grow(xs, 1, want_rec, n_rec);
+            if (rc) return rc;
+            if (first) HIP_TRY(hipMemsetAsync(cig_off.p, 0, 4, st));
+            cap_rec = want_rec;
+        }
+        if (want_ops > cap_ops) {
+            const int rc = grow(cigar, 4, want_ops, n_ops);
+            if (rc) return rc;
+            cap_ops = want_ops;
+        }
+        return SPL_OK;
+    }
+    void swap(RecordArrays &o)
+    {
+        std::swap(pos.p, o.pos.p); std::swap(flag.p, o.flag.p); std::swap(cig_off.p, o.cig_off.p); std::swap(cigar.p, o.cigar.p); std::swap(tid.p, o.tid.p); std::swap(xs.p, o.xs.p);
+        std::swap(cap_rec, o.cap_rec); std::swap(cap_ops, o.cap_ops);
+    }
+    void release() { pos.release(); flag.release(); cig_off.release(); cigar.release(); tid.release(); xs.release(); cap_rec = cap_ops = 0; }
+
+    // Where each reference's records are (the bounds kernel on `st`, waited for), sorted by their first record, and whether the
+    // references come in order: no more runs than bounds_cap, every id in [0, n_ref) and above the one before.
+    int find_runs(int n_ref, const DevBuf &d_bounds, const DevBuf &d_nbounds, uint32_t bounds_cap, hipStream_t st, std::vector<Run> &runs, bool &in_order)
+    {
+        std::vector<uint64_t> bounds(2 * (size_t)bounds_cap, 0);
+        uint32_t n_bounds = 0;
+        HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, st));
+        HIP_TRY((hipError_t)spl_dev_launch_bam_bounds(tid.as<int32_t>(), cig_off.as<uint32_t>(), n_rec, d_bounds.as<uint64_t>(), d_nbounds.as<uint32_t>(), bounds_cap, st));
+        HIP_TRY(hipMemcpyAsync(bounds.data(), d_bounds.p, 16 * (size_t)bounds_cap, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&n_bounds, d_nbounds.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        runs.clear();
+        in_order = n_bounds <= bounds_cap;
+        if (!in_order) return SPL_OK;
+        for (uint32_t k = 0; k < n_bounds; ++k) runs.push_back(Run{bounds[2 * k], (int32_t)(uint32_t)bounds[2 * k + 1], (uint32_t)(bounds[2 * k + 1] >> 32)});
+        std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.first < b.first; });
+        for (size_t k = 0; k < runs.size() && in_order; ++k) in_order = runs[k].tid >= 0 && runs[k].tid < n_ref && !(k && runs[k].tid <= runs[k - 1].tid);
+        return SPL_OK;
+    }
+    // The records stay where they are, BAM-native in device memory: a read set on this device is laid out from them by kernels
+    // (spl_devpack.hip), and the host gets copies only if somebody asks the file for them (fetch_device_reads).  The five arrays
+    // are the DeviceReads' from here (null: out of host memory); tid stays behind.
+    DeviceReads *hand_over(int device, int n_ref, const std::vector<Run> &runs, const std::vector<unsigned long long> &maxend)
+    {
+        DeviceReads *keep = new (std::nothrow) DeviceReads();
+        if (!keep) return nullptr;
+        const size_t nr = (size_t)std::max(n_ref, 1);
+        keep->device = device;
+        keep->n_rec = (int64_t)n_rec; keep->n_ops = (int64_t)n_ops;
+        keep->ref_first.assign(nr, 0); keep->ref_n.assign(nr, 0); keep->ref_max.assign(nr, 0); keep->ref_ops.assign(nr, 0);
+        for (size_t k = 0; k < runs.size(); ++k) {
+            const size_t t = (size_t)runs[k].tid;
+            const bool last = k + 1 == runs.size();
+            keep->ref_first[t] = (int64_t)runs[k].first;
+            keep->ref_n[t] = (int64_t)((last ? n_rec : runs[k + 1].first) - runs[k].first);
+            keep->ref_ops[t] = (int64_t)((last ? n_ops : (uint64_t)runs[k + 1].op) - runs[k].op);
+            keep->ref_max[t] = (int64_t)maxend[t];
+        }
+        keep->pos = pos.p; keep->flag = flag.p; keep->cig_off = cig_off.p; keep->cigar = cigar.p; keep->xs = xs.p;
+        pos.p = flag.p = cig_off.p = cigar.p = xs.p = nullptr;
+        return keep;
+    }
+};
+
+// A decode's totals record (spl_bam.h), filled with its reads: the records it saw, how many it sorted, what the filters dropped, flagstat's sums.
+static void fill_totals(spl_bam_totals &t, int64_t n_records, uint64_t n_sorted, int64_t drop_flags, int64_t drop_mapq, const unsigned long long *fsum)
+{
+    t.n_records = n_records;
+    t.n_sorted = (int64_t)n_sorted;
+    t.sorted_on_device = n_sorted ? 1 : 0;
+    t.dropped[0] = drop_flags;
+    t.dropped[1] = drop_mapq;
+    for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) t.fstat[q] = (int64_t)fsum[q];
 }
 
 static void *host_array(size_t bytes) // (2 MiB-aligned, huge pages asked for: tens to hundreds of MB that are written once, front to back)
@@ -1436,10 +1576,11 @@ namespace {
 // keys (id << 32 | POS) with the record's index as payload through the passes of the stable radix sort (spl_sort.hip), least
 // significant digit first, over the digits that can differ only -- POS is at most `top`, the largest end any read has, the id
 // below n_ref; then the arrays gathered by the permutation, the op counts in their new order scanned into the new cig_off, the
-// CIGAR words copied run by run.  The sorted arrays take the unsorted ones' places (the DevBuf pointers are swapped); the scratch
-// -- two key and two payload buffers, the arrays a second time -- stays here until release().
+// CIGAR words copied run by run.  The sorted arrays take the unsorted ones' places (RecordArrays::swap); the scratch -- two key
+// and two payload buffers, the arrays a second time -- stays here until release().
 struct RecordSort {
-    DevBuf keys[2], perm[2], work, pos2, flag2, cigoff2, cigar2, tid2, xs2;
+    DevBuf keys[2], perm[2], work;
+    RecordArrays sorted;
     uint32_t passes = 0, pos_bits = 0, tid_bits = 0, shifts[8] = {0};
     void plan(unsigned long long top, int n_ref)
     {
@@ -1452,34 +1593,37 @@ struct RecordSort {
         return 24.0 * (double)n_rec + (double)spl_dev_sort_work_bytes(n_rec) + (want_xs ? 15.0 : 14.0) * (double)n_rec + 4.0 * (double)n_ops + 4096.0;
     }
     // (after plan) n_ops < 2^32 and n_rec <= 0xfffffff0 are the caller's to have seen; waits for the stream before it swaps
-    int run(hipStream_t st, uint64_t n_rec, uint64_t n_ops, bool want_xs, DevBuf &d_pos, DevBuf &d_flag, DevBuf &d_cigoff, DevBuf &d_cigar, DevBuf &d_tid, DevBuf &d_xs)
+    int run(hipStream_t st, RecordArrays &a)
     {
+        const uint64_t n_rec = a.n_rec;
+        const bool want_xs = a.want_xs;
         const size_t n = (size_t)n_rec;
         for (int k = 0; k < 2; ++k) { HIP_TRY(keys[k].get(8 * n, st)); HIP_TRY(perm[k].get(4 * n, st)); }
         HIP_TRY(work.get(spl_dev_sort_work_bytes(n_rec), st));
-        HIP_TRY(pos2.get(4 * n, st)); HIP_TRY(flag2.get(2 * n, st)); HIP_TRY(cigoff2.get(4 * (n + 1), st));
-        HIP_TRY(cigar2.get(4 * (size_t)n_ops, st)); HIP_TRY(tid2.get(4 * n, st));
-        if (want_xs) HIP_TRY(xs2.get(n, st));
-        HIP_TRY((hipError_t)spl_dev_launch_sort_make_keys(d_tid.as<int32_t>(), d_pos.as<int32_t>(), n_rec, keys[0].as<uint64_t>(), st));
+        HIP_TRY(sorted.pos.get(4 * n, st)); HIP_TRY(sorted.flag.get(2 * n, st)); HIP_TRY(sorted.cig_off.get(4 * (n + 1), st));
+        HIP_TRY(sorted.cigar.get(4 * (size_t)a.n_ops, st)); HIP_TRY(sorted.tid.get(4 * n, st));
+        if (want_xs) HIP_TRY(sorted.xs.get(n, st));
+        sorted.cap_rec = n_rec; sorted.cap_ops = a.n_ops;
+        HIP_TRY((hipError_t)spl_dev_launch_sort_make_keys(a.tid.as<int32_t>(), a.pos.as<int32_t>(), n_rec, keys[0].as<uint64_t>(), st));
         int cur = 0;
         for (uint32_t k = 0; k < passes; ++k, cur ^= 1)
             HIP_TRY((hipError_t)spl_dev_launch_sort_pass(keys[cur].as<uint64_t>(), k ? perm[cur].as<uint32_t>() : nullptr, n_rec, shifts[k], keys[cur ^ 1].as<uint64_t>(),
                                                          perm[cur ^ 1].as<uint32_t>(), work.p, st));
         const uint32_t *order = perm[cur].as<uint32_t>();
-        HIP_TRY((hipError_t)spl_dev_launch_sort_gather(order, keys[cur].as<uint64_t>(), n_rec, d_pos.as<int32_t>(), d_flag.as<uint16_t>(), want_xs ? d_xs.as<uint8_t>() : nullptr,
-                                                       d_cigoff.as<uint32_t>(), pos2.as<int32_t>(), flag2.as<uint16_t>(), want_xs ? xs2.as<uint8_t>() : nullptr, tid2.as<int32_t>(),
-                                                       cigoff2.as<uint32_t>(), st));
-        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(cigoff2.as<uint32_t>() + 1, n_rec, work.p, st));
-        HIP_TRY((hipError_t)spl_dev_launch_sort_cigar(order, n_rec, d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), cigoff2.as<uint32_t>(), cigar2.as<uint32_t>(), st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_gather(order, keys[cur].as<uint64_t>(), n_rec, a.pos.as<int32_t>(), a.flag.as<uint16_t>(), want_xs ? a.xs.as<uint8_t>() : nullptr,
+                                                       a.cig_off.as<uint32_t>(), sorted.pos.as<int32_t>(), sorted.flag.as<uint16_t>(), want_xs ? sorted.xs.as<uint8_t>() : nullptr,
+                                                       sorted.tid.as<int32_t>(), sorted.cig_off.as<uint32_t>(), st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(sorted.cig_off.as<uint32_t>() + 1, n_rec, work.p, st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_cigar(order, n_rec, a.cig_off.as<uint32_t>(), a.cigar.as<uint32_t>(), sorted.cig_off.as<uint32_t>(), sorted.cigar.as<uint32_t>(), st));
         HIP_TRY(hipStreamSynchronize(st));
-        std::swap(d_pos.p, pos2.p); std::swap(d_flag.p, flag2.p); std::swap(d_cigoff.p, cigoff2.p); std::swap(d_cigar.p, cigar2.p); std::swap(d_tid.p, tid2.p);
-        std::swap(d_xs.p, xs2.p);
+        a.swap(sorted);
         return SPL_OK;
     }
     void release()
     {
         for (int k = 0; k < 2; ++k) { keys[k].release(); perm[k].release(); }
-        work.release(); pos2.release(); flag2.release(); cigoff2.release(); cigar2.release(); tid2.release(); xs2.release();
+        work.release();
+        sorted.release();
     }
 };
 
@@ -1596,15 +1740,14 @@ struct ShareDecode {
     const bool want_stat = opts.flagstat;            // (the scan counts the flagstat categories per block, a kernel adds up the accepted blocks')
     const bool any_order = !share && opts.any_order; // (the records may come in any order -- sorted behind the last extraction, sort_records; the whole file only)
     // ---- everything the streams touch is declared before them
-    DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_maxend, d_bounds, d_nbounds, d_xs, d_fstat, d_fsum;
+    DevBuf d_image, d_stream[NBUF], d_zwork[NBUF], d_blocks0, d_status0, d_recs, d_blocks, d_status, d_scan, d_recoff, d_opoff, d_maxend, d_bounds, d_nbounds, d_fstat, d_fsum;
+    RecordArrays arrays; // (what the extraction writes: POS, FLAG, CIGARs, reference ids and, where wanted, the strand bytes)
     RecordSort sorter; // (spl_bam_set_any_order: its scratch is got only when the sort runs)
     std::vector<spl_zblock> blocks, blocks0; // (blocks0: the early windows', for their launches before the directory is complete)
     std::unique_ptr<uint32_t[]> status;
     std::unique_ptr<spl_bscan[]> scan;
     std::unique_ptr<uint64_t[]> rec_off, op_off;
     std::vector<unsigned long long> maxend;
-    std::vector<uint64_t> bounds;
-    uint32_t n_bounds = 0;
     unsigned long long fsum[2 * SPL_FS_CATEGORIES] = {0};
     Pipe pipe{c};
     // ---- the share: which blocks, which bytes of the file (plan)
@@ -1622,7 +1765,6 @@ struct ShareDecode {
     size_t win_bytes_cap = (size_t)-1; // a window ends where its blocks' bytes in the file would exceed this (so that four windows fit the ring)
     double per_block_file = 65536.0;
     uint32_t max_block_file = 0, tok_stride = SPL_Z_TOKEN_STRIDE, k1_flags = 0; // (max_block_file: the most bytes of file any block known so far has)
-    uint64_t cap_rec = 0, cap_ops = 0, n_rec = 0, n_ops = 0;
     // ---- the readers
     std::vector<hipError_t> errs;
     std::vector<std::atomic<int>> sent; // piece k's copy and event are in the copy stream's queue (or will never be: errs)
@@ -1661,7 +1803,7 @@ struct ShareDecode {
     size_t launched = 0, copying = 0; // windows whose decoding / whose copying kernel has been put on its stream
     std::vector<double> t_win; // (SPL_BAM_TIMING: when each window's scan was back on the host)
 
-    ShareDecode(spl_ctx *ctx, spl_bam *b, const spl_bam_share *s, ShareOut &out, bool all_room) : c(ctx), bam(b), share(s), res(out), all_token_room(all_room) {}
+    ShareDecode(spl_ctx *ctx, spl_bam *b, const spl_bam_share *s, ShareOut &out, bool all_room) : c(ctx), bam(b), share(s), res(out), all_token_room(all_room) { arrays.want_xs = want_xs; }
     ~ShareDecode()
     {
         if (walker.joinable()) walker.join();
@@ -1735,13 +1877,13 @@ struct ShareDecode {
                 if (stop_upload.load(std::memory_order_acquire)) errs[t] = hipErrorNotReady; // (the call is on its way out: nobody waits for this piece)
                 else errs[t] = hipStreamWaitEvent(up, pipe.dec[w], 0);
             }
-            if (errs[t] == hipSuccess && st.busy) { errs[t] = hipEventSynchronize(st.done); st.busy = false; }
+            if (errs[t] == hipSuccess) errs[t] = st.wait();
             if (errs[t] == hipSuccess) {
                 const size_t off = k * piece, n = std::min(piece + TAIL, n_bytes - off);
                 CopyJob job{st.host, (const char *)image + byte_lo + off, n, n, fd, byte_lo + off};
                 copy_slice(0, &job);
                 errs[t] = hipMemcpyAsync(d_image.as<char>() + (k % ring) * slot, st.host, n, hipMemcpyHostToDevice, up);
-                if (errs[t] == hipSuccess) { errs[t] = hipEventRecord(st.done, up); st.busy = true; }
+                if (errs[t] == hipSuccess) errs[t] = st.mark(up);
                 if (errs[t] == hipSuccess) errs[t] = hipEventCreateWithFlags(&pipe.piece[k], hipEventDisableTiming); // (piece k is this reader's alone; whoever waits for it looks after sent[k])
                 if (errs[t] == hipSuccess) errs[t] = hipEventRecord(pipe.piece[k], up);
             }
@@ -1922,7 +2064,7 @@ struct ShareDecode {
     // of the first launch, and make_room below finds the room there -- or grows it, as before, where the sample was wrong.
     int early_room(size_t b_lo, size_t b_hi, double inflated_bytes)
     {
-        if (cap_rec) return SPL_OK;
+        if (arrays.cap_rec) return SPL_OK;
         uint64_t s_rec = 0, s_ops = 0, s_bytes = 0;
         if (!spl_bam_sample_density(bam, b_lo, b_hi, &s_rec, &s_ops, &s_bytes)) return SPL_OK;
         const double scale = 1.25 * inflated_bytes / (double)s_bytes;
@@ -1933,7 +2075,7 @@ struct ShareDecode {
         const uint64_t want_ops = (uint64_t)std::min((double)s_ops * scale_ops, inflated_bytes / 4.0) + 1024;
         HIP_TRY(look_at_free());
         if ((double)(14 * want_rec + 4 * want_ops) > (double)free_b / 3.0) return SPL_OK; // (a guess must not be what the windows' buffers go without)
-        const int rc = grow_arrays(want_rec, want_ops);
+        const int rc = arrays.reserve(want_rec, want_ops, pipe.b);
         if (rc) return rc;
         used_b += (size_t)(14 * want_rec + 4 * want_ops);
         if (timing) fprintf(stderr, "[spl_bam_decode_device] device %d: room for %llu records and %llu CIGAR ops from %llu records in %.1f KB on the host\n", c->device,
@@ -2109,7 +2251,6 @@ struct ShareDecode {
         HIP_TRY(hipMemcpyAsync(d_blocks.p, blocks.data(), sizeof(spl_zblock) * n_blocks, hipMemcpyHostToDevice, pipe.b));
         HIP_TRY(hipMemsetAsync(d_status.p, 0xff, 4 * n_blocks, pipe.b));
         HIP_TRY(hipMemsetAsync(d_maxend.p, 0, 8 * (size_t)std::max(n_ref, 1), pipe.b));
-        HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, pipe.b));
         if (want_stat) HIP_TRY(hipMemsetAsync(d_fsum.p, 0, sizeof(fsum), pipe.b));
         HIP_TRY(hipEventRecord(pipe.setup, pipe.b));
         // (what the early windows' kernels said about their blocks goes to its place among the file's when they have said it: the loop, behind the window's copying kernel)
@@ -2123,42 +2264,17 @@ struct ShareDecode {
     }
 
     // the extracted arrays: as large as the first window says the share will need and a fifth more, larger when that was wrong
+    // (RecordArrays::reserve: the limit that was hit is raised, the records' or the ops')
     int make_room(uint64_t need_rec, uint64_t need_ops, double part_done)
     {
+        const uint64_t cap_rec = arrays.cap_rec, cap_ops = arrays.cap_ops;
         if (need_rec <= cap_rec && need_ops <= cap_ops && cap_rec) return SPL_OK;
         const double scale = 1.2 / std::max(part_done, 1e-6); // (a fifth more than the windows so far say: growing later means fresh memory and moving what is there)
         if (timing && cap_rec) fprintf(stderr, "[spl_bam_decode_device] device %d: the extracted arrays grow (%llu records and %llu ops needed %.0f %% into the stretch, room for %llu and %llu)\n",
                                        c->device, (unsigned long long)need_rec, (unsigned long long)need_ops, 100.0 * part_done, (unsigned long long)cap_rec, (unsigned long long)cap_ops);
         const uint64_t want_rec = std::max<uint64_t>(need_rec, (uint64_t)((double)need_rec * scale)) + 1024;
         const uint64_t want_ops = std::max<uint64_t>(need_ops, (uint64_t)((double)need_ops * scale)) + 1024;
-        return grow_arrays(want_rec, want_ops);
-    }
-    // the extracted arrays anew, with room for want_rec records and want_ops ops
-    int grow_arrays(uint64_t want_rec, uint64_t want_ops)
-    {
-        DevBuf pos2, flag2, cigoff2, cigar2, tid2, xs2;
-        if (want_xs) HIP_TRY(xs2.get(want_rec, pipe.b));
-        HIP_TRY(pos2.get(4 * want_rec, pipe.b));
-        HIP_TRY(flag2.get(2 * want_rec, pipe.b));
-        HIP_TRY(cigoff2.get(4 * (want_rec + 1), pipe.b));
-        HIP_TRY(cigar2.get(4 * want_ops, pipe.b));
-        HIP_TRY(tid2.get(4 * want_rec, pipe.b));
-        if (cap_rec) { // what the windows so far have left (n_rec records, n_ops ops) moves
-            HIP_TRY(hipMemcpyAsync(pos2.p, d_pos.p, 4 * n_rec, hipMemcpyDeviceToDevice, pipe.b));
-            HIP_TRY(hipMemcpyAsync(flag2.p, d_flag.p, 2 * n_rec, hipMemcpyDeviceToDevice, pipe.b));
-            HIP_TRY(hipMemcpyAsync(cigoff2.p, d_cigoff.p, 4 * (n_rec + 1), hipMemcpyDeviceToDevice, pipe.b));
-            HIP_TRY(hipMemcpyAsync(cigar2.p, d_cigar.p, 4 * n_ops, hipMemcpyDeviceToDevice, pipe.b));
-            HIP_TRY(hipMemcpyAsync(tid2.p, d_tid.p, 4 * n_rec, hipMemcpyDeviceToDevice, pipe.b));
-            if (want_xs && n_rec) HIP_TRY(hipMemcpyAsync(xs2.p, d_xs.p, n_rec, hipMemcpyDeviceToDevice, pipe.b));
-            HIP_TRY(hipStreamSynchronize(pipe.b));
-        } else {
-            HIP_TRY(hipMemsetAsync(cigoff2.p, 0, 4, pipe.b));
-        }
-        std::swap(d_pos.p, pos2.p); std::swap(d_flag.p, flag2.p); std::swap(d_cigoff.p, cigoff2.p); std::swap(d_cigar.p, cigar2.p); std::swap(d_tid.p, tid2.p);
-        std::swap(d_xs.p, xs2.p);
-        cap_rec = want_rec;
-        cap_ops = want_ops;
-        return SPL_OK;
+        return arrays.reserve(need_rec > cap_rec || !cap_rec ? want_rec : 0, need_ops > cap_ops || !cap_rec ? want_ops : 0, pipe.b);
     }
 
     // ---- stage: the window loop
@@ -2306,18 +2422,18 @@ struct ShareDecode {
         if (b_done > s0) {
             const int rc = make_room(rec_off[b_done], op_off[b_done], (double)(blocks[b_done - 1].out + blocks[b_done - 1].out_len - stream_begin) / (double)std::max<uint64_t>(stream_len - stream_begin, 1));
             if (rc) return rc;
-            n_rec = rec_off[b_done];
-            n_ops = op_off[b_done];
+            arrays.n_rec = rec_off[b_done];
+            arrays.n_ops = op_off[b_done];
             const size_t nd = b_done - s0;
             HIP_TRY(hipMemcpyAsync(d_recoff.as<uint64_t>() + s0, rec_off.get() + s0, 8 * nd, hipMemcpyHostToDevice, pipe.b));
             HIP_TRY(hipMemcpyAsync(d_opoff.as<uint64_t>() + s0, op_off.get() + s0, 8 * nd, hipMemcpyHostToDevice, pipe.b));
             HIP_TRY(hipMemcpyAsync(d_scan.as<spl_bscan>() + s0, scan.get() + s0, sizeof(spl_bscan) * nd, hipMemcpyHostToDevice, pipe.b));
             splprof::Scope p("spl_bam_extract_kernel", pipe.b, (double)(blocks[b_done - 1].out + blocks[b_done - 1].out_len - blocks[s0].out));
             HIP_TRY((hipError_t)spl_dev_launch_bam_extract(stream0, win_end, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)nd, d_scan.as<spl_bscan>() + s0,
-                                                           d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, d_pos.as<int32_t>(), d_flag.as<uint16_t>(),
-                                                           d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(), d_tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
+                                                           d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(),
+                                                           arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(), arrays.tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
                                                            with_recs ? d_recs.as<uint16_t>() : nullptr, opts.filter.min_mapq, opts.filter.require_flags, opts.filter.exclude_flags,
-                                                           want_xs ? d_xs.as<uint8_t>() : nullptr, pipe.b));
+                                                           want_xs ? arrays.xs.as<uint8_t>() : nullptr, pipe.b));
         }
         if (want_stat && b_done > s0) { // the counters of the blocks that are done with, each once: a block that waits for the next window is scanned, and counted, again
             splprof::Scope p("spl_bam_flagstat_reduce_kernel", pipe.b, 4.0 * SPL_FS_CATEGORIES * (double)(b_done - s0));
@@ -2336,6 +2452,7 @@ struct ShareDecode {
     double sort_ms = 0, sort_room_ms = 0, sort_bytes = 0; // (sort_room_ms: of sort_ms, giving the decode's buffers back and looking at what is free)
     int sort_records()
     {
+        const uint64_t n_rec = arrays.n_rec, n_ops = arrays.n_ops;
         if (n_rec > 0xfffffff0ull) return to_host("more than 2^32 placed records in a file that is not in coordinate order");
         const double t0 = host_now();
         unsigned long long top = 1;
@@ -2348,7 +2465,7 @@ struct ShareDecode {
         HIP_TRY(look_at_free());
         if (RecordSort::bytes_needed(n_rec, n_ops, want_xs) + slack > (double)free_b) return to_host("not enough device memory to sort the records");
         const double t_room = host_now();
-        { const int rc = sorter.run(pipe.b, n_rec, n_ops, want_xs, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_xs); if (rc) return rc; } // (n_ops < 2^32: records_done)
+        { const int rc = sorter.run(pipe.b, arrays); if (rc) return rc; } // (n_ops < 2^32: records_done)
         n_sorted = n_rec;
         sort_ms = 1e3 * (host_now() - t0);
         sort_room_ms = 1e3 * (t_room - t0);
@@ -2364,66 +2481,28 @@ struct ShareDecode {
         // every record that begins in the share's own blocks has been walked: the walk must have arrived where the next share's begins
         if (!last_share && expect != sh.u_hi) return to_host("a share's records do not end where the next share's begin");
         if (last_share && expect != stream_len) return to_host("the file ends inside a record");
-        if (!cap_rec) { const int rc = make_room(0, 0, 1.0); if (rc) return rc; } // (a share without a record of its own)
+        if (!arrays.cap_rec) { const int rc = make_room(0, 0, 1.0); if (rc) return rc; } // (a share without a record of its own)
         maxend.assign((size_t)std::max(n_ref, 1), 0);
         HIP_TRY(hipMemcpyAsync(maxend.data(), d_maxend.p, 8 * maxend.size(), hipMemcpyDeviceToHost, pipe.b));
         if (want_stat) HIP_TRY(hipMemcpyAsync(fsum, d_fsum.p, sizeof(fsum), hipMemcpyDeviceToHost, pipe.b));
-        struct Run { uint64_t first; int32_t tid; uint32_t op; };
-        std::vector<Run> runs;
         // where each reference's records are, and whether the references come in order (every run's id above the one before)
-        auto find_runs = [&](bool &in_order) -> int {
-            HIP_TRY((hipError_t)spl_dev_launch_bam_bounds(d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), n_rec, d_bounds.as<uint64_t>(), d_nbounds.as<uint32_t>(), bounds_cap, pipe.b));
-            bounds.assign(2 * (size_t)bounds_cap, 0);
-            HIP_TRY(hipMemcpyAsync(bounds.data(), d_bounds.p, 16 * (size_t)bounds_cap, hipMemcpyDeviceToHost, pipe.b));
-            HIP_TRY(hipMemcpyAsync(&n_bounds, d_nbounds.p, 4, hipMemcpyDeviceToHost, pipe.b));
-            HIP_TRY(hipStreamSynchronize(pipe.b));
-            runs.clear();
-            in_order = n_bounds <= bounds_cap;
-            if (!in_order) return SPL_OK;
-            for (uint32_t k = 0; k < n_bounds; ++k) runs.push_back(Run{bounds[2 * k], (int32_t)(uint32_t)bounds[2 * k + 1], (uint32_t)(bounds[2 * k + 1] >> 32)});
-            std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.first < b.first; });
-            for (size_t k = 0; k < runs.size() && in_order; ++k) in_order = runs[k].tid >= 0 && runs[k].tid < n_ref && !(k && runs[k].tid <= runs[k - 1].tid);
-            return SPL_OK;
-        };
+        std::vector<RecordArrays::Run> runs;
         bool in_order = false;
-        int rc_runs = find_runs(in_order);
+        int rc_runs = arrays.find_runs(n_ref, d_bounds, d_nbounds, bounds_cap, pipe.b, runs, in_order);
         if (rc_runs) return rc_runs;
         join_readers();
         for (hipError_t e : errs) HIP_TRY(e);
         if (!in_order && any_order) { // (spl_bam_set_any_order: the arrays sorted by (reference, POS, place in the file), then the runs of the sorted ones)
             rc_runs = sort_records();
             if (rc_runs) return rc_runs;
-            HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, pipe.b));
-            rc_runs = find_runs(in_order);
+            rc_runs = arrays.find_runs(n_ref, d_bounds, d_nbounds, bounds_cap, pipe.b, runs, in_order);
             if (rc_runs) return rc_runs;
         }
         if (!in_order) return to_host("not sorted by reference");
-        const size_t nr = (size_t)std::max(n_ref, 1);
-        // The records stay where they are, BAM-native in device memory: a read set on this device is laid out from them by kernels
-        // (spl_devpack.hip), and the host gets copies only if somebody asks the file for them (fetch_device_reads).
-        DeviceReads *keep = new (std::nothrow) DeviceReads();
-        if (!keep) return spl_set_error(SPL_ERR_NOMEM, "out of host memory");
-        keep->device = c->device;
-        keep->n_rec = (int64_t)n_rec; keep->n_ops = (int64_t)n_ops;
-        keep->ref_first.assign(nr, 0); keep->ref_n.assign(nr, 0); keep->ref_max.assign(nr, 0); keep->ref_ops.assign(nr, 0);
-        for (size_t k = 0; k < runs.size(); ++k) {
-            const int32_t t = runs[k].tid;
-            const bool last = k + 1 == runs.size();
-            keep->ref_first[(size_t)t] = (int64_t)runs[k].first;
-            keep->ref_n[(size_t)t] = (int64_t)((last ? n_rec : runs[k + 1].first) - runs[k].first);
-            keep->ref_ops[(size_t)t] = (int64_t)((last ? n_ops : (uint64_t)runs[k + 1].op) - runs[k].op);
-            keep->ref_max[(size_t)t] = (int64_t)maxend[(size_t)t];
-        }
-        keep->pos = d_pos.p; keep->flag = d_flag.p; keep->cig_off = d_cigoff.p; keep->cigar = d_cigar.p;
-        keep->xs = d_xs.p;
-        d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = d_xs.p = nullptr; // (the caller owns them from here)
-        res.reads = keep;
-        res.totals.n_records = n_all;
-        res.totals.n_sorted = (int64_t)n_sorted;
-        res.totals.sorted_on_device = n_sorted ? 1 : 0;
-        res.totals.dropped[0] = n_drop_flags;
-        res.totals.dropped[1] = n_drop_mapq;
-        for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.totals.fstat[q] = (int64_t)fsum[q];
+        res.reads = arrays.hand_over(c->device, n_ref, runs, maxend); // (the caller owns the five arrays from here)
+        if (!res.reads) return spl_set_error(SPL_ERR_NOMEM, "out of host memory");
+        fill_totals(res.totals, n_all, n_sorted, n_drop_flags, n_drop_mapq, fsum);
+        const uint64_t n_rec = arrays.n_rec;
         if (timing) fprintf(stderr, "[spl_bam_decode_device] device %d: blocks %zu..%zu, %.1f MB -> %.1f MB inflated in %zu window%s, %llu placed records of %lld: %.4f s\n", c->device, lo, hi,
                             n_bytes / 1e6, (stream_len - stream_begin) / 1e6, n_win, n_win == 1 ? "" : "s", (unsigned long long)n_rec, (long long)n_all, host_now() - t_begin);
         if (timing && n_sorted)
@@ -2448,7 +2527,7 @@ struct ShareDecode {
         d_image.release();
         for (int k = 0; k < NBUF; ++k) { d_stream[k].release(); d_zwork[k].release(); }
         d_blocks0.release(); d_status0.release(); d_recs.release(); d_blocks.release(); d_status.release(); d_scan.release(); d_recoff.release(); d_opoff.release();
-        d_tid.release(); d_maxend.release(); d_bounds.release(); d_nbounds.release(); d_fstat.release(); d_fsum.release();
+        arrays.tid.release(); d_maxend.release(); d_bounds.release(); d_nbounds.release(); d_fstat.release(); d_fsum.release();
         sorter.release();
         const int told = publish(res);
         // ... and not at once: 500 events and five streams destroyed are 10 ms of the HIP runtime's locks, which the thread that was
@@ -2473,39 +2552,6 @@ static int decode_share(spl_ctx *c, spl_bam *bam, const spl_bam_share *share, Sh
     if (rc == SPL_OK) return d.release_and_publish(publish);
     return rc == STOPPED ? SPL_OK : rc;
 }
-
-// `bytes` bytes to `dst` on the device through the context's staging ring on the copy stream, for the one thread of a call that
-// sends: take the next pinned buffer, wait while its last copy is under way, have it filled -- fill(host, room, done) -> the bytes
-// it put there, at most `room`; 0 ends the sending early --, queue the copy, record the buffer's event.  *sent_out: the bytes queued.
-namespace {
-template <class Fill> hipError_t ring_send(spl_ctx *c, char *dst, uint64_t bytes, Fill &&fill, uint64_t *sent_out = nullptr)
-{
-    hipError_t q = hipSuccess;
-    uint64_t done = 0;
-    while (done < bytes && q == hipSuccess) {
-        spl_ctx::Stage &sg = c->stage[c->stage_next];
-        c->stage_next = (c->stage_next + 1) % c->stage.size();
-        if (sg.busy) { q = hipEventSynchronize(sg.done); sg.busy = false; if (q != hipSuccess) break; }
-        const size_t n = fill(sg.host, (size_t)std::min<uint64_t>(bytes - done, sg.bytes), done);
-        if (!n) break;
-        q = hipMemcpyAsync(dst + done, sg.host, n, hipMemcpyHostToDevice, c->copy);
-        if (q == hipSuccess) { q = hipEventRecord(sg.done, c->copy); sg.busy = true; }
-        done += n;
-    }
-    if (sent_out) *sent_out = done;
-    return q;
-}
-// ... filled from the file: `room` bytes from file offset file_off + done, eight threads a piece (copy_slice)
-struct FileFill {
-    const uint8_t *image; int fd; uint64_t file_off;
-    size_t operator()(char *host, size_t room, uint64_t done) const
-    {
-        CopyJob job{host, (const char *)image + file_off + done, room, (room + 7) / 8, fd, (size_t)(file_off + done)};
-        splpack::parallel_for((room + job.per - 1) / std::max<size_t>(job.per, 1), 8, copy_slice, &job);
-        return room;
-    }
-};
-} // namespace
 
 // ---- SAM text (spl_sam_open): the same five arrays from the text an aligner writes --------------------------------------
 // Windows of SPL_SAM_WINDOW_BYTES (default 256 MiB) of whole lines -- the host cuts a window behind its last '\n', which it finds
@@ -2535,10 +2581,10 @@ struct SamDecode {
     size_t blob_bytes = 0;
     // ---- everything the streams touch is declared before them
     DevBuf d_text[2], d_slots, d_nameoff, d_blob, d_chunks, d_lines, d_kept, d_nops, d_ltid, d_fstat, d_fsum, d_counts, d_work, d_maxend, d_bounds, d_nbounds, d_long;
-    DevBuf d_pos, d_flag, d_tid, d_cigoff, d_cigar, d_xs;
+    RecordArrays arrays;
     RecordSort sorter;
     size_t cap_chunks = 0, cap_lines = 0, cap_work = 0;
-    uint64_t cap_rec = 0, cap_ops = 0, n_rec = 0, n_ops = 0, n_lines_all = 0, n_drop_flags = 0, n_drop_mapq = 0, n_sorted = 0;
+    uint64_t n_lines_all = 0, n_drop_flags = 0, n_drop_mapq = 0, n_sorted = 0;
     struct Streams {
         hipStream_t k = nullptr;
         hipEvent_t up[2] = {nullptr, nullptr};
@@ -2562,7 +2608,7 @@ struct SamDecode {
     hipError_t up_err = hipSuccess;
     std::thread uploader;
 
-    SamDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : c(ctx), bam(b), res(r) {}
+    SamDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : c(ctx), bam(b), res(r) { arrays.want_xs = want_xs; }
     ~SamDecode()
     {
         {
@@ -2572,7 +2618,7 @@ struct SamDecode {
         cv.notify_all();
         if (uploader.joinable()) uploader.join();
         if (c->copy) (void)hipStreamSynchronize(c->copy);
-        for (spl_ctx::Stage &sg : c->stage) sg.busy = false;
+        c->stages_idle();
     }
 
     // The file cut into windows of whole lines.  A line longer than a window (its newline counted) fits none: the windows end in
@@ -2627,7 +2673,6 @@ struct SamDecode {
         HIP_TRY(hipMemsetAsync(d_counts.p, 0, sizeof(spl_sam_counts), st.k));
         HIP_TRY(hipMemsetAsync(d_maxend.p, 0, 8 * nr, st.k));
         HIP_TRY(hipMemsetAsync(d_fsum.p, 0, 8 * 2 * SPL_FS_CATEGORIES, st.k));
-        HIP_TRY(hipMemsetAsync(d_nbounds.p, 0, 4, st.k));
         HIP_TRY(hipStreamSynchronize(st.k)); // (the names' host memory is the file's; the copies above are done with it here)
         dev_names = spl_sam_names{d_slots.as<uint32_t>(), d_nameoff.as<uint32_t>(), d_blob.as<uint8_t>(), host_names.n_slots, host_names.n};
         return SPL_OK;
@@ -2658,34 +2703,16 @@ struct SamDecode {
         }
     }
 
-    template <class T> hipError_t regrow(DevBuf &b, size_t old_n, size_t new_n)
-    {
-        DevBuf fresh;
-        hipError_t q = fresh.get(sizeof(T) * new_n, st.k);
-        if (q == hipSuccess && b.p && old_n) q = hipMemcpyAsync(fresh.p, b.p, sizeof(T) * old_n, hipMemcpyDeviceToDevice, st.k);
-        if (q == hipSuccess) q = hipStreamSynchronize(st.k);
-        if (q == hipSuccess) std::swap(b.p, fresh.p);
-        return q; // (fresh's destructor gives the old array back)
-    }
     // room for the records and ops of this window behind the ones there are; the first time from the window's density over the file
+    // (RecordArrays::reserve: the limit that was hit is raised, the records' or the ops')
     int make_room(uint64_t more_rec, uint64_t more_ops, uint64_t win_len, uint64_t bytes_left)
     {
+        const uint64_t n_rec = arrays.n_rec, n_ops = arrays.n_ops, cap_rec = arrays.cap_rec, cap_ops = arrays.cap_ops;
         const uint64_t need_rec = n_rec + more_rec, need_ops = n_ops + more_ops;
         if (need_rec <= cap_rec && need_ops <= cap_ops && cap_rec) return SPL_OK;
         const double scale = 1.0 + 1.1 * (double)bytes_left / (double)std::max<uint64_t>(win_len, 1); // (this window, and the rest at its density and a tenth)
         const uint64_t want_rec = std::max<uint64_t>(need_rec, n_rec + (uint64_t)((double)more_rec * scale)) + 1024, want_ops = std::max<uint64_t>(need_ops, n_ops + (uint64_t)((double)more_ops * scale)) + 1024;
-        if (need_rec > cap_rec || !cap_rec) {
-            HIP_TRY(regrow<int32_t>(d_pos, (size_t)n_rec, (size_t)want_rec)); HIP_TRY(regrow<uint16_t>(d_flag, (size_t)n_rec, (size_t)want_rec)); HIP_TRY(regrow<int32_t>(d_tid, (size_t)n_rec, (size_t)want_rec));
-            HIP_TRY(regrow<uint32_t>(d_cigoff, cap_rec ? (size_t)n_rec + 1 : 0, (size_t)want_rec + 1));
-            if (want_xs) HIP_TRY(regrow<uint8_t>(d_xs, (size_t)n_rec, (size_t)want_rec));
-            if (!cap_rec) { HIP_TRY(hipMemsetAsync(d_cigoff.p, 0, 4, st.k)); }
-            cap_rec = want_rec;
-        }
-        if (need_ops > cap_ops || !d_cigar.p) {
-            HIP_TRY(regrow<uint32_t>(d_cigar, (size_t)n_ops, (size_t)want_ops));
-            cap_ops = want_ops;
-        }
-        return SPL_OK;
+        return arrays.reserve(need_rec > cap_rec || !cap_rec ? want_rec : 0, need_ops > cap_ops || !cap_rec ? want_ops : 0, st.k);
     }
 
     uint64_t bad_line = 0; uint32_t bad_reason = 0; // (a window's scan found a line the rule does not take)
@@ -2781,7 +2808,7 @@ struct SamDecode {
             bad_reason = (uint32_t)(counts.first_bad & 0xffu);
             return STOPPED;
         }
-        if (n_rec + kept_w > 0xfffffff0ull || n_ops + ops_w > 0xfffffff0ull) { // (cig_off is 32 bits wide, and so is the sort's payload)
+        if (arrays.n_rec + kept_w > 0xfffffff0ull || arrays.n_ops + ops_w > 0xfffffff0ull) { // (cig_off is 32 bits wide, and so is the sort's payload)
             bad_line = header_lines + n_lines_all + n_lines;
             bad_reason = SPL_SAM_TOO_MANY;
             return STOPPED;
@@ -2792,13 +2819,13 @@ struct SamDecode {
         // ---- the kept lines' fields behind the ones there are
         { const int rc = make_room(kept_w, ops_w, win.hi - win.lo, bytes_left); if (rc) return rc; }
         HIP_TRY((hipError_t)spl_dev_launch_sam_extract(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
-                                                       opts.filter.exclude_flags, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(), n_rec, n_ops, cap_rec, cap_ops,
-                                                       d_pos.as<int32_t>(), d_flag.as<uint16_t>(), d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), d_cigar.as<uint32_t>(),
-                                                       want_xs ? d_xs.as<uint8_t>() : nullptr, d_maxend.as<unsigned long long>(), d_counts.as<spl_sam_counts>(), st.k));
-        HIP_TRY((hipError_t)spl_dev_launch_sam_order(d_tid.as<int32_t>(), d_pos.as<int32_t>(), n_rec, kept_w, d_counts.as<spl_sam_counts>(), st.k));
+                                                       opts.filter.exclude_flags, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(), arrays.n_rec, arrays.n_ops, arrays.cap_rec, arrays.cap_ops,
+                                                       arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(), arrays.tid.as<int32_t>(), arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(),
+                                                       want_xs ? arrays.xs.as<uint8_t>() : nullptr, d_maxend.as<unsigned long long>(), d_counts.as<spl_sam_counts>(), st.k));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_order(arrays.tid.as<int32_t>(), arrays.pos.as<int32_t>(), arrays.n_rec, kept_w, d_counts.as<spl_sam_counts>(), st.k));
         HIP_TRY(hipStreamSynchronize(st.k)); // (the window's buffer is free for the window after the next)
-        n_rec += kept_w;
-        n_ops += ops_w;
+        arrays.n_rec += kept_w;
+        arrays.n_ops += ops_w;
         n_lines_all += n_lines;
         return SPL_OK;
     }
@@ -2816,16 +2843,15 @@ struct SamDecode {
         for (unsigned long long e : maxend) top = std::max(top, e);
         sorter.plan(top, n_ref);
         release_buffers();
-        const int rc = sorter.run(st.k, n_rec, n_ops, want_xs, d_pos, d_flag, d_cigoff, d_cigar, d_tid, d_xs); // (n_rec and n_ops below 2^32 - 16: parse_window)
-        if (rc == SPL_OK) n_sorted = n_rec;
+        const int rc = sorter.run(st.k, arrays); // (n_rec and n_ops below 2^32 - 16: parse_window)
+        if (rc == SPL_OK) n_sorted = arrays.n_rec;
         return rc;
     }
 
     int finish()
     {
-        if (!cap_rec) { const int rc = make_room(0, 0, 1, 0); if (rc) return rc; } // (a file without a placed record)
+        if (!arrays.cap_rec) { const int rc = make_room(0, 0, 1, 0); if (rc) return rc; } // (a file without a placed record)
         const size_t nr = (size_t)std::max(n_ref, 1);
-        const uint32_t bounds_cap = (uint32_t)nr + 1u;
         maxend.assign(nr, 0);
         spl_sam_counts counts;
         unsigned long long fsum[2 * SPL_FS_CATEGORIES] = {0};
@@ -2836,41 +2862,14 @@ struct SamDecode {
         if (counts.overflow) return spl_set_error(SPL_ERR_HIP, "the SAM extraction disagreed with its scan (%u)", counts.overflow);
         if (counts.unordered) { const int rc = sort_records(); if (rc) return rc; }
         // where each reference's records are (their ids go up now)
-        std::vector<uint64_t> bounds(2 * (size_t)bounds_cap, 0);
-        uint32_t n_bounds = 0;
-        HIP_TRY((hipError_t)spl_dev_launch_bam_bounds(d_tid.as<int32_t>(), d_cigoff.as<uint32_t>(), n_rec, d_bounds.as<uint64_t>(), d_nbounds.as<uint32_t>(), bounds_cap, st.k));
-        HIP_TRY(hipMemcpyAsync(bounds.data(), d_bounds.p, 16 * (size_t)bounds_cap, hipMemcpyDeviceToHost, st.k));
-        HIP_TRY(hipMemcpyAsync(&n_bounds, d_nbounds.p, 4, hipMemcpyDeviceToHost, st.k));
-        HIP_TRY(hipStreamSynchronize(st.k));
-        if (n_bounds > bounds_cap) return spl_set_error(SPL_ERR_HIP, "the SAM records' reference ids do not go up behind the sort");
-        struct Run { uint64_t first; int32_t tid; uint32_t op; };
-        std::vector<Run> runs;
-        for (uint32_t k = 0; k < n_bounds; ++k) runs.push_back(Run{bounds[2 * k], (int32_t)(uint32_t)bounds[2 * k + 1], (uint32_t)(bounds[2 * k + 1] >> 32)});
-        std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.first < b.first; });
-        for (size_t k = 0; k < runs.size(); ++k)
-            if (runs[k].tid < 0 || runs[k].tid >= n_ref || (k && runs[k].tid <= runs[k - 1].tid)) return spl_set_error(SPL_ERR_HIP, "the SAM records' reference ids do not go up behind the sort");
-        DeviceReads *keep = new (std::nothrow) DeviceReads();
-        if (!keep) return spl_set_error(SPL_ERR_NOMEM, "out of host memory");
-        keep->device = c->device;
-        keep->n_rec = (int64_t)n_rec; keep->n_ops = (int64_t)n_ops;
-        keep->ref_first.assign(nr, 0); keep->ref_n.assign(nr, 0); keep->ref_max.assign(nr, 0); keep->ref_ops.assign(nr, 0);
-        for (size_t k = 0; k < runs.size(); ++k) {
-            const size_t t = (size_t)runs[k].tid;
-            const bool last = k + 1 == runs.size();
-            keep->ref_first[t] = (int64_t)runs[k].first;
-            keep->ref_n[t] = (int64_t)((last ? n_rec : runs[k + 1].first) - runs[k].first);
-            keep->ref_ops[t] = (int64_t)((last ? n_ops : (uint64_t)runs[k + 1].op) - runs[k].op);
-            keep->ref_max[t] = (int64_t)maxend[t];
-        }
-        keep->pos = d_pos.p; keep->flag = d_flag.p; keep->cig_off = d_cigoff.p; keep->cigar = d_cigar.p; keep->xs = d_xs.p;
-        d_pos.p = d_flag.p = d_cigoff.p = d_cigar.p = d_xs.p = nullptr; // (the caller owns them from here)
-        res.reads = keep;
-        res.totals.n_records = (int64_t)n_lines_all;
-        res.totals.n_sorted = (int64_t)n_sorted;
-        res.totals.sorted_on_device = n_sorted ? 1 : 0;
-        res.totals.dropped[0] = (int64_t)n_drop_flags;
-        res.totals.dropped[1] = (int64_t)n_drop_mapq;
-        for (int q = 0; q < 2 * SPL_FS_CATEGORIES; ++q) res.totals.fstat[q] = (int64_t)fsum[q];
+        std::vector<RecordArrays::Run> runs;
+        bool in_order = false;
+        { const int rc = arrays.find_runs(n_ref, d_bounds, d_nbounds, (uint32_t)nr + 1u, st.k, runs, in_order); if (rc) return rc; }
+        if (!in_order) return spl_set_error(SPL_ERR_HIP, "the SAM records' reference ids do not go up behind the sort");
+        res.reads = arrays.hand_over(c->device, n_ref, runs, maxend); // (the caller owns the five arrays from here)
+        if (!res.reads) return spl_set_error(SPL_ERR_NOMEM, "out of host memory");
+        fill_totals(res.totals, (int64_t)n_lines_all, n_sorted, (int64_t)n_drop_flags, (int64_t)n_drop_mapq, fsum);
+        const uint64_t n_rec = arrays.n_rec;
         if (timing)
             fprintf(stderr, "[spl_bam_decode_device] device %d: %s, %.1f MB in %zu window%s, %llu lines, %llu placed records%s: %.4f s\n", c->device, what, text_bytes / 1e6, n_windows,
                     n_windows == 1 ? "" : "s", (unsigned long long)n_lines_all, (unsigned long long)n_rec, n_sorted ? ", sorted" : "", host_now() - t_begin);
@@ -3318,7 +3317,7 @@ static int finish_reads(spl_ctx *c, spl_dreads *d)
     }
     // (everything the host-packed segments queued on the copy stream is over with this; the vectors above die at return)
     if (q == hipSuccess && c->copy && (host_segs || !c->stage.empty())) q = hipStreamSynchronize(c->copy);
-    for (spl_ctx::Stage &st : c->stage) st.busy = false;
+    c->stages_idle();
     if (q != hipSuccess) return spl_set_error(SPL_ERR_HIP, "read set upload: %s", hipGetErrorString(q));
     // segments on the device: record slots, the segment list and the chunk -> segment map of every group
     const uint32_t chunk = 1u << d->chunk_shift;
@@ -3564,19 +3563,15 @@ static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceRea
         for (size_t i = 0; i < (b - a) / 4; ++i) out[i] = in[i] + pc.add;
     };
     auto send = [&](void *dst_dev, const void *src, size_t bytes, uint32_t add, bool offsets) {
-        for (size_t done = 0; done < bytes && q == hipSuccess;) {
-            spl_ctx::Stage &st = c->stage[c->stage_next];
-            c->stage_next = (c->stage_next + 1) % c->stage.size();
-            if (st.busy) { q = hipEventSynchronize(st.done); st.busy = false; if (q != hipSuccess) break; }
-            const size_t n = std::min(bytes - done, st.bytes / 64 * 64);
-            Piece pc{st.host, (const char *)src + done, n, add, offsets, 0};
+        if (q != hipSuccess) return;
+        q = ring_send(c, (char *)dst_dev, bytes, [&](char *host, size_t room, uint64_t done) {
+            const size_t n = done + room < bytes ? room / 64 * 64 : room; // (a piece that is not the array's last: whole 64-byte lines)
+            Piece pc{host, (const char *)src + done, n, add, offsets, 0};
             const size_t slices = std::max<size_t>(1, std::min<size_t>((size_t)c->pack_threads * 2, n >> 16));
             pc.per = ((n + slices - 1) / slices + 63) / 64 * 64;
             splpack::parallel_for(slices, c->pack_threads, slice, &pc);
-            q = hipMemcpyAsync((char *)dst_dev + done, st.host, n, hipMemcpyHostToDevice, c->copy);
-            if (q == hipSuccess) { q = hipEventRecord(st.done, c->copy); st.busy = true; }
-            done += n;
-        }
+            return n;
+        });
     };
     int64_t at = 0, op_at = 0;
     for (int k = 0; k < n_seg && q == hipSuccess; ++k) {
@@ -3604,7 +3599,7 @@ static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceRea
     const uint32_t last = (uint32_t)op_at;
     if (q == hipSuccess) q = hipMemcpyAsync((uint32_t *)dev->cig_off + at, &last, 4, hipMemcpyHostToDevice, c->copy);
     if (q == hipSuccess) q = hipStreamSynchronize(c->copy);
-    for (spl_ctx::Stage &st : c->stage) st.busy = false;
+    c->stages_idle();
     if (q != hipSuccess) {
         free_device_reads(dev);
         return spl_set_error(SPL_ERR_HIP, "reads to the device: %s", hipGetErrorString(q));

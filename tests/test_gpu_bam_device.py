@@ -1,6 +1,8 @@
 """BAM decode on the device (spl_bam_decode_device: BGZF inflate, CRC32, record scan and extraction as HIP kernels) against the
 host decoder on the same files: identical arrays per reference, identical record counts -- and the files the device path does
 not take (unsorted, CG-tag CIGARs, damaged) end up with the host decoder, whose results and errors are the contract."""
+import re
+
 import numpy as np
 import pytest
 
@@ -242,6 +244,69 @@ def test_inflate_windows_of_a_few_blocks(ctx, tmp_path, monkeypatch, window):
     dev.decode_on_device(ctx)      # (a megabyte is 17 blocks: the record's bytes travel from window to window in the room in
     _same(dev.reads("c0"), want)   #  front of each; what counts is the result)
     dev.close()
+
+
+def _stretches(stretches):
+    """Two references' reads from (ops a read, reads, bases an aligned block) stretches in file order: a one-op read is one
+    match, a read of more ops a soft clip and matches with introns between them (so that the writer gives it an XS tag)."""
+    kinds = [(n_ops, q) for n_ops, count, q in stretches for _ in range(count)]
+    sets = []
+    for part in (kinds[:len(kinds) // 2], kinds[len(kinds) // 2:]):
+        ops = [[(q << 4) | 0] if n_ops == 1 else [(3 << 4) | 4] + [(q << 4) | 0 if j % 2 == 0 else (100 << 4) | 3 for j in range(n_ops - 1)]
+               for n_ops, q in part]
+        cig_off = np.concatenate(([0], np.cumsum([len(o) for o in ops]))).astype(np.uint32)
+        flag = np.where(np.arange(len(part)) % 3 == 0, 16, 0).astype(np.uint16)
+        sets.append(samio.ReadSet((100 + 7 * np.arange(len(part))).astype(np.int32), flag, cig_off, np.array([x for o in ops for x in o], np.uint32)))
+    return sets
+
+
+@pytest.mark.parametrize("limit,stretches", [
+    ("ops", [(1, 3000, 1), (1, 1000, 2600), (12, 8000, 1)]),
+    ("records", [(12, 8000, 150), (1, 4000, 4)]),
+])
+def test_the_extracted_arrays_grow_at_either_limit(ctx, tmp_path, monkeypatch, capfd, limit, stretches):
+    """The extracted arrays' first room comes from what the host sees of the file at three places (the first blocks, a third and
+    two thirds in), a quarter more for the records and six tenths more for the ops; a window that needs more than that raises the
+    limit it hit, the records' arrays or the op array, each array moved on its own.  Two files of 12 000 reads on two references
+    that mislead the sample, windows of two blocks, the strand bytes wanted so that the sixth array moves too:
+    "ops": the first third of the reads have one op, the rest twelve.  The one-op reads are 3 000 short ones, which the first
+    place sees, and 1 000 of 2 600 bases, which fill the file past the other two; the twelve-op reads behind them are what the
+    sample never saw: room for some 27 000 ops where the file has 100 000, for 21 000 records where it has 12 000.
+    "records": the twelve-op reads first, 900 bases each, the one-op reads of four bases behind the last place: room for some
+    11 400 records where the file has 12 000, for 160 000 ops where it has 100 000.
+    What the host decoder gives, array by array, and the decode must say that the arrays grew."""
+    monkeypatch.setenv("SPL_INFLATE_WINDOW_BLOCKS", "2")
+    monkeypatch.setenv("SPL_BAM_TIMING", "1")
+    names = ["c0", "c1"]
+    sets = _stretches(stretches)
+    path = str(tmp_path / "g.bam")
+    native.write_bam(path, names, [10 ** 8] * 2, sets, level=1, threads=3, seq_mode=2)
+    host = native.BamFile(path, threads=2, defer=True)
+    host.set_aux_strand(True)
+    host.start_host_decode()
+    dev = native.BamFile(path, threads=2, defer=True)
+    dev.set_aux_strand(True)
+    capfd.readouterr()
+    assert dev.decode_on_device(ctx) is True, dev.decline_reason()
+    said = capfd.readouterr().err
+    print(said)
+    try:
+        assert dev.n_records == host.n_records == 12000
+        for c, rs in zip(names, sets):
+            d, h = dev.reads(c), host.reads(c)
+            _same(h, rs)
+            _same(d, h)
+            assert h.xs is not None and np.any(h.xs != h.xs[0])     # (both strands' bytes, and reads without one)
+            assert np.array_equal(d.xs, h.xs), (c, np.flatnonzero(d.xs != h.xs)[:10])
+            assert dev.wait_ref(c) == host.wait_ref(c)
+    finally:
+        host.close()
+        dev.close()
+    grown = [line for line in said.splitlines() if "the extracted arrays grow" in line]
+    assert grown, said
+    for line in grown:      # (the limit this file is about was hit, and only that one)
+        need_rec, need_ops, room_rec, room_ops = (int(x) for x in re.search(r"grow \((\d+) records and (\d+) ops needed .* room for (\d+) and (\d+)\)", line).groups())
+        assert (need_ops > room_ops and need_rec <= room_rec) if limit == "ops" else (need_rec > room_rec and need_ops <= room_ops), line
 
 
 @pytest.mark.parametrize("dense", ["0", "1"])
