@@ -538,6 +538,19 @@ int spl_simple_span_host(const int32_t *site_pos, int64_t n_pos, int64_t n_threa
                          const uint16_t *len, const uint8_t *is_simple, int32_t shift, uint8_t *flagged, uint8_t *emits, int32_t *lo,
                          int32_t *ub);
 
+/* ---- the position index of an uploaded site table, read back (test hooks; no product path calls them) ----------------------
+ * The index every counting kernel finds its sites through: one entry per 32-base bucket counted from dbase, bucket b beginning at
+ * start = dbase + 32 b -- first: the number of distinct site positions below start; occ: bit k set when start + k is a site
+ * position; rival: bit k set when start + k is an end of a junction that has rivals (a partner or competitor position of a row
+ * that has both lists; not necessarily a site).  dbase = lo - 64 (-64 when lo < 64) and n_dbuckets = ((hi - dbase) >> 5) + 2, lo
+ * and hi the least and the greatest of the site and flagged positions; a table without rows has no buckets.
+ * spl_sites_index_info: any output may be NULL.  spl_sites_index_download: buckets [first_bucket, first_bucket + count) into out,
+ * three words a bucket (first, occ, rival); it waits for the context's stream first.  SPL_ERR_ARG: a null argument,
+ * first_bucket + count > n_dbuckets. */
+int spl_sites_index_info(const spl_dsites *ds, int32_t *dbase, uint32_t *n_dbuckets, int32_t *n_dpos);
+int spl_sites_index_download(spl_ctx *ctx, const spl_dsites *ds, uint32_t first_bucket, uint32_t count,
+                             uint32_t *out /* 3 words a bucket: first, occ, rival */);
+
 /* ---- host helper of Step 1 ---------------------------------------------------------------------------
  * binary_gene_search (SpliSER_v0_1_8.py:118-173) for a batch of query positions against one chromosome's gene list
  * (in list order), probe for probe like the reference.  Strand bytes are '+', '-' or 0 for anything else;

@@ -4316,6 +4316,29 @@ extern "C" int spl_simple_span_host(const int32_t *site_pos, int64_t n_pos, int6
     return SPL_OK;
 }
 
+// The position index of an uploaded table as spl_build_dbuckets_kernel left it, read back (test hooks: no product path calls them).
+extern "C" int spl_sites_index_info(const spl_dsites *ds, int32_t *dbase, uint32_t *n_dbuckets, int32_t *n_dpos)
+{
+    if (!ds) return spl_set_error(SPL_ERR_ARG, "spl_sites_index_info: null argument");
+    if (dbase) *dbase = ds->dbase;
+    if (n_dbuckets) *n_dbuckets = ds->n_dbuckets;
+    if (n_dpos) *n_dpos = ds->n_dpos;
+    return SPL_OK;
+}
+
+extern "C" int spl_sites_index_download(spl_ctx *c, const spl_dsites *ds, uint32_t first_bucket, uint32_t count, uint32_t *out)
+{
+    static_assert(sizeof(spl_dbk) == 12, "a bucket entry is three words");
+    if (!c || !ds || !out) return spl_set_error(SPL_ERR_ARG, "spl_sites_index_download: null argument");
+    if ((uint64_t)first_bucket + (uint64_t)count > (uint64_t)ds->n_dbuckets)
+        return spl_set_error(SPL_ERR_ARG, "spl_sites_index_download: buckets [%u, %llu) of %u", first_bucket,
+                             (unsigned long long)first_bucket + count, ds->n_dbuckets);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (count) HIP_TRY(hipMemcpy(out, ds->dbucket + first_bucket, sizeof(spl_dbk) * (size_t)count, hipMemcpyDeviceToHost));
+    return SPL_OK;
+}
+
 // The walk of one read's ops that the junction kernels share (spl_junction_walk.h), on the host: no GPU involved (test hook).
 extern "C" int spl_junction_walk_host(const uint32_t *ops, uint32_t n_ops, int32_t pos, int32_t min_anchor, int32_t min_intron, int32_t max_intron,
                                       int capacity, int32_t *left, int32_t *right, uint32_t *anchor_left, uint32_t *anchor_right, uint8_t *passes,

@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_simple_span_host", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -351,6 +351,20 @@ class DeviceSites(object):
              np.zeros(max(n, 1), np.float64)]
         _check(lib().spl_sse_download(self.ctx._h, self._h, _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3])))
         return tuple(a[:n] for a in o)
+
+    def position_index(self, first=0, count=None):
+        """The table's position index as the device holds it (test hook: ``spl_sites_index_info`` / ``spl_sites_index_download``)
+        -> (dbase, n_dbuckets, n_dpos, uint32[count, 3]: first, occ, rival of buckets [first, first + count)); ``count`` None: all
+        buckets from ``first`` on."""
+        dbase, n_dbuckets, n_dpos = ctypes.c_int32(0), ctypes.c_uint32(0), ctypes.c_int32(0)
+        _check(lib().spl_sites_index_info(self._h, ctypes.byref(dbase), ctypes.byref(n_dbuckets), ctypes.byref(n_dpos)))
+        first = int(first)
+        count = max(n_dbuckets.value - first, 0) if count is None else int(count)
+        if first < 0 or count < 0 or first >= 1 << 32 or count >= 1 << 32:
+            raise ValueError("position_index: first and count must fit uint32")
+        out = np.zeros((max(count, 1), 3), np.uint32)
+        _check(lib().spl_sites_index_download(self.ctx._h, self._h, ctypes.c_uint32(first), ctypes.c_uint32(count), _ptr(out)))
+        return dbase.value, n_dbuckets.value, n_dpos.value, out[:count]
 
     def free(self):
         if self._h:
