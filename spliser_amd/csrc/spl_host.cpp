@@ -242,8 +242,8 @@ extern "C" int spl_bedgraph_append(const char *path, const char *chrom, int64_t 
 // HTSeq's conventions: start = column 4 - 1, end = column 5, name = value of the first attribute).  Files of this kind have
 // 10^5 lines; line by line in Python that is a fifth of a second, here it is a few milliseconds.  Anything these parsers are
 // not sure to read the way Python's str.split / int() would -- a number that is not a plain decimal integer, a strand
-// column longer than one byte, a lone carriage return, bytes outside ASCII where they would matter -- makes the call fail with
-// SPL_ERR_FORMAT, and the caller takes its line-by-line path, which then says what Python says.
+// column longer than one byte, a lone carriage return, a NUL or a byte outside ASCII anywhere in the file -- makes the call fail
+// with SPL_ERR_FORMAT, and the caller takes its line-by-line path, which then says what Python says.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -284,7 +284,19 @@ struct Mapped {
     ~Mapped() { if (p) munmap((void *)p, n); }
 };
 
+// The blanks int() takes around the digits of an ASCII text ...
 inline bool is_space(char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\v' || ch == '\f'; }
+// ... and what str.strip() strips of one: the "separator" controls 0x1c-0x1f too (int("5\x1f") is a ValueError, "x\x1f".strip() is "x").
+inline bool is_str_space(char ch) { return is_space(ch) || (ch >= 0x1c && ch <= 0x1f); }
+
+// A NUL ends the C strings the names are handed out as, and bytes outside ASCII are text only if Python's decoder says so: a file
+// that holds either, in whatever column or line, is Python's to read (the .SpliSER.tsv parser of spl_combine.cpp does the same).
+bool plain_ascii(const char *p, size_t n)
+{
+    unsigned high = 0, nul = 0;
+    for (size_t i = 0; i < n; ++i) { high |= (unsigned char)p[i]; nul |= p[i] == 0; }
+    return !(high & 0x80u) && !nul;
+}
 
 // Python's int(text) for the texts that occur in these files: optional blanks, optional sign, decimal digits, optional blanks.
 bool py_int(const char *s, const char *e, int64_t *out)
@@ -322,6 +334,7 @@ extern "C" int spl_bed_open(const char *path, spl_textfile **out)
     *out = nullptr;
     Mapped f(path);
     if (!f.ok) return spl_set_error(SPL_ERR_IO, "cannot read %s", path);
+    if (!plain_ascii(f.p, f.n)) return spl_set_error(SPL_ERR_FORMAT, "%s holds a NUL or a byte outside ASCII", path);
     spl_textfile *t = new spl_textfile();
     std::map<std::string, int32_t> ids;
     const char *p = f.p, *end = f.p + f.n;
@@ -352,7 +365,7 @@ extern "C" int spl_bed_open(const char *path, spl_textfile **out)
                 return spl_set_error(SPL_ERR_FORMAT, "%s: line %lld holds a number that is not a plain integer", path, (long long)line_no);
             }
             const size_t sl = (size_t)(fe(5) - field[5]);
-            if (sl > 1 || (sl == 1 && (unsigned char)field[5][0] >= 128)) { delete t; return spl_set_error(SPL_ERR_FORMAT, "%s: line %lld has a strand column of more than one character", path, (long long)line_no); }
+            if (sl > 1) { delete t; return spl_set_error(SPL_ERR_FORMAT, "%s: line %lld has a strand column of more than one character", path, (long long)line_no); }
             t->chrom.push_back(chrom_id(t, ids, field[0], fe(0)));
             t->a.push_back(start + b0);   // :275
             t->b.push_back(stop - b1);    // :276
@@ -372,6 +385,7 @@ extern "C" int spl_gff_open(const char *path, spl_textfile **out)
     *out = nullptr;
     Mapped f(path);
     if (!f.ok) return spl_set_error(SPL_ERR_IO, "cannot read %s", path);
+    if (!plain_ascii(f.p, f.n)) return spl_set_error(SPL_ERR_FORMAT, "%s holds a NUL or a byte outside ASCII", path);
     spl_textfile *t = new spl_textfile();
     t->name_off.push_back(0);
     std::map<std::string, int32_t> ids;
@@ -385,7 +399,7 @@ extern "C" int spl_gff_open(const char *path, spl_textfile **out)
         if (le > p && le[-1] == '\r') --le;
         if (memchr(p, '\r', (size_t)(le - p))) return fail("holds a carriage return");
         bool blank = true;
-        for (const char *q = p; q < le && blank; ++q) blank = is_space(*q);
+        for (const char *q = p; q < le && blank; ++q) blank = is_str_space(*q);
         if (!(le == p || *p == '#' || blank)) {
             std::vector<const char *> field;
             field.push_back(p);
@@ -397,22 +411,21 @@ extern "C" int spl_gff_open(const char *path, spl_textfile **out)
                 int64_t c4, c5;
                 if (!py_int(field[3], fe(3), &c4) || !py_int(field[4], fe(4), &c5)) return fail("holds a coordinate that is not a plain integer");
                 const size_t sl = (size_t)(fe(6) - field[6]);
-                if (sl != 1 || (unsigned char)field[6][0] >= 128) return fail("has a strand column that is not one character");
+                if (sl != 1) return fail("has a strand column that is not one character");
                 // name = value of the first attribute (HTSeq), quotes stripped: sites.py _first_attribute
                 const char *s = field[8], *e = fe(8);
-                for (const char *q = s; q < e; ++q) if ((unsigned char)*q >= 128) return fail("has non-ASCII attributes");
-                while (s < e && is_space(*s)) ++s;
-                while (e > s && is_space(e[-1])) --e;
+                while (s < e && is_str_space(*s)) ++s;
+                while (e > s && is_str_space(e[-1])) --e;
                 const char *semi = (const char *)memchr(s, ';', (size_t)(e - s));
                 if (semi) e = semi;
-                while (s < e && is_space(*s)) ++s;
-                while (e > s && is_space(e[-1])) --e;
+                while (s < e && is_str_space(*s)) ++s;
+                while (e > s && is_str_space(e[-1])) --e;
                 const char *eq = (const char *)memchr(s, '=', (size_t)(e - s));
                 const char *sp = (const char *)memchr(s, ' ', (size_t)(e - s));
                 if (eq) s = eq + 1;
                 else if (sp) s = sp + 1;
-                while (s < e && is_space(*s)) ++s;
-                while (e > s && is_space(e[-1])) --e;
+                while (s < e && is_str_space(*s)) ++s;
+                while (e > s && is_str_space(e[-1])) --e;
                 while (s < e && *s == '"') ++s;
                 while (e > s && e[-1] == '"') --e;
                 t->chrom.push_back(chrom_id(t, ids, field[0], fe(0)));

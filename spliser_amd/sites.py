@@ -103,6 +103,20 @@ class GeneBins(object):
                 [g.name for g in genes])
 
     @classmethod
+    def from_columns(cls, cols):
+        """The bins of the gene lines ``native.read_gff_genes`` read (all genes, file order)."""
+        bins = cls()
+        bins._columns = {}
+        for k, chrom in enumerate(cols.chrom_names):
+            rows = np.flatnonzero(cols.chrom == k)
+            order = rows[np.argsort(cols.left[rows], kind="stable")]   # = bisect.insort by left, later lines after equal ones
+            bins._chroms.add(chrom)
+            bins.chrom_index.append(chrom)
+            bins._columns[chrom] = (cols.left[order], cols.right[order], cols.strand[order], [cols.names[i] for i in order.tolist()])
+        bins.n_created = int(cols.chrom.shape[0])
+        return bins
+
+    @classmethod
     def from_annotation(cls, path, a_type="gene", q_gene="All", log=None):
         """createGenes.  ``a_type`` is accepted and ignored exactly like the reference does
         (it tests ``line.type == 'gene'`` literally, SpliSER_v0_1_8.py:82).  Coordinates follow
@@ -116,14 +130,7 @@ class GeneBins(object):
             except Exception:
                 cols = None
             if cols is not None:
-                bins._columns = {}
-                for k, chrom in enumerate(cols.chrom_names):
-                    rows = np.flatnonzero(cols.chrom == k)
-                    order = rows[np.argsort(cols.left[rows], kind="stable")]   # = bisect.insort by left, later lines after equal ones
-                    bins._chroms.add(chrom)
-                    bins.chrom_index.append(chrom)
-                    bins._columns[chrom] = (cols.left[order], cols.right[order], cols.strand[order], [cols.names[i] for i in order.tolist()])
-                bins.n_created = int(cols.chrom.shape[0])
+                bins = cls.from_columns(cols)
                 if log:
                     log("%d Genes created in %d bins" % (bins.n_created, len(bins.chrom_index)))
                 return bins

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers
+import textcases
 from spliser_amd import combine as cmb
 from spliser_amd import native
 
@@ -180,13 +181,7 @@ def test_files_the_native_parser_leaves_to_python(tmp_path):
 
 def test_str_of_a_float_like_python():
     L = native.lib()
-    rng = np.random.default_rng(7)
-    vals = [0.0, -0.0, 2.0, 0.33333, 12.5, 1e16, 1e15, 9999999999999998.0, 1.5e-5, 1e-4, 9.999e-5, 1e22, 5e-324, 1.7976931348623157e308,
-            0.1 + 0.2, 100.0, 123456.789, float("inf"), float("-inf")]
-    vals += (rng.integers(0, 10 ** 7, 3000) / 1e5).tolist()                      # what "{0:.5f}" of process leaves, summed or not
-    vals += (rng.integers(0, 10 ** 7, 500) / 1e5 + rng.integers(0, 10 ** 7, 500) / 1e5).tolist()
-    vals += np.exp(rng.uniform(-60, 60, 3000)).tolist()
-    vals += rng.standard_normal(500).tolist()
+    vals = textcases.repr_values()          # (shared with the sanitizer driver, test_native_sanitizers.py)
     buf = ctypes.create_string_buffer(64)
     for x in vals:
         assert L.spl_fmt_repr(ctypes.c_double(x), buf) == 0

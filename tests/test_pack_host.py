@@ -7,6 +7,7 @@ import pytest
 
 from spliser_amd import native, samio, synth
 from tests import randcase
+import textcases
 
 COORD_MAX = 2147483581
 CHUNK = 2048
@@ -108,11 +109,7 @@ def check(reads, threads=3):
 
 
 def test_pack_corner_cigars():
-    recs = [(0, 100, "50M"), (16, 100, "50="), (0, 100, "20M100N30M"), (0, 100, "5S20M100N30M3S"), (0, 100, "20M100N30M50N40M"),
-            (0, 100, "2H20M2I100N30M50N40M1P"), (4, 100, "50M"), (0, 100, "*"), (0, 100, "10S"), (0, 100, "10M5D10M"),
-            (0, 100, "10M0N10M"), (0, 100, "10M5N5N10M"), (0, 100, "10N20M"), (0, 100, "20M10N"), (0, 100, "70000M"),
-            (0, 100, "70000M10N5M"), (0, 100, "5M10N70000M"), (0, 100, "5M10N5M10N70000M"), (0, 100, "1M1N1M1N1M1N1M"),
-            (0, 100, "1M1I1M1I1M1I1M1I1M"), (0, 100, "1M1D" * 10), (1024, 2147483000, "1000M"), (0, 2147483000, "100M")]
+    recs = textcases.PACK_CORNER_RECORDS    # (shared with the sanitizer driver, test_native_sanitizers.py)
     reads = samio.ReadSet.from_records(recs)
     desc = check(reads, threads=1)
     assert desc[0]["n"].tolist() == [3, 4, 2, len(recs) - 9]

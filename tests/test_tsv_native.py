@@ -5,6 +5,7 @@ import pytest
 
 from conftest import golden_cases
 import helpers
+import textcases
 from spliser_amd import native, samio, sites, tsv
 
 
@@ -84,7 +85,6 @@ def test_fixed_point_text_matches_python_format():
     """spl_fmt_fixed (the writer's "%.3f" / "%.5f") against Python's format over ratios of small integers (what SSE values are --
     exact ties like 1/16 included), random doubles, powers of two, tiny and large values."""
     import ctypes
-    import random
     lib = native.lib()
     lib.spl_fmt_fixed.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_char_p]
     buf = ctypes.create_string_buffer(64)
@@ -93,13 +93,7 @@ def test_fixed_point_text_matches_python_format():
         assert lib.spl_fmt_fixed(x, d, buf) == 0
         return buf.value.decode()
 
-    rnd = random.Random(7)
-    values = [0.0, 1.0, 0.5, 0.0625, 0.1875, 0.0005, 0.00049999999999999, 0.9995, 0.99949999999999994, 2.5e-5, 5e-324, 1e-310,
-              123456789.123456, 8.9e12, 4503599627370496.0, 1e40, 0.000005, 0.0000049999]
-    values += [2.0 ** -k for k in range(0, 80)] + [(2 * k + 1) / 2.0 ** 12 for k in range(0, 2048, 7)]
-    values += [a / b for a in range(0, 60) for b in range(1, 60)]
-    values += [rnd.random() for _ in range(20000)] + [rnd.random() * 10 ** rnd.randint(-8, 12) for _ in range(20000)]
-    values += [rnd.randint(0, 10 ** 6) / 10 ** rnd.randint(1, 7) for _ in range(20000)]   # decimal-looking values next to ties
+    values = textcases.fixed_values()       # (shared with the sanitizer driver, test_native_sanitizers.py)
     for x in values:
         for d in (3, 5, 0, 6):
             assert got(x, d) == ("{0:.%df}" % d).format(x), (x, d)
