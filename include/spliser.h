@@ -525,6 +525,36 @@ int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint
 int spl_bedgraph_append(const char *path, const char *chrom, int64_t n, const int32_t *start, const int32_t *end, const uint32_t *depth,
                         int64_t per_million_of /* 0: integers */);
 
+/* ---- per-gene read counts (what the pipeline otherwise leaves to a second pass by another program) ---------------------------
+ * Replaces `htseq-count` / `featureCounts` over the file this library has just decoded: the diffSpliSER analysis is an edgeR
+ * analysis, and the gene's expression belongs beside a change in SSE.  The reference has no counterpart.  spl_gene_count counts,
+ * on the device, over the BAM-native arrays of a FUSED read set, the reads of every gene.  The rule (csrc/spl_genecount_rule.h):
+ *   gene map    of the set's coordinate space: ascending int32 start[n] with uint32 code[n], code[k] holding for the 0-based
+ *               positions start[k] <= p < start[k + 1] (the last entry to +infinity; 0 below start[0]); 0 = no feature, g + 1 = only
+ *               features of gene g (0 <= g < n_genes), 0xFFFFFFFF = features of two or more genes.  A map of 0 entries is valid;
+ *   maps        stranded = 0: map a serves every read.  stranded = 1 (fr) / 2 (rf): map a serves the reads check_strand's rule
+ *               (:374-406) calls '+', map b those it calls '-';
+ *   eligible    (flag & (0x4 | 0x100 | 0x200 | 0x800)) == 0, POS >= 1 and at least one op; duplicates count.  Every other read
+ *               the set holds is "not counted";
+ *   blocks      spl_coverage's walk from the 0-based p = POS - 1 + the segment's shift, in int64: M, = and X cover, D and N are
+ *               gaps, covering ops that abut are one block; nothing is clipped to a length;
+ *   gene set    the union, over every stretch of the read's map that a block overlaps by a base or more, of the stretch's code:
+ *               empty = "no feature", exactly one gene = one more read of that gene, anything else = "ambiguous" (htseq-count
+ *               --mode union --nonunique none and featureCounts' default, per READ: a paired fragment adds up to two).
+ * inout[0 .. n_genes) += the genes' reads, inout[n_genes] += no feature, [n_genes + 1] += ambiguous, [n_genes + 2] += not counted:
+ * what is ADDED sums to the reads of the set.  The call synchronises; integer sums, exact and the same for the reads in any order
+ * (one atomic per run of equal results in a wave: a gene that takes every read is no slower).  Parity with htseq-count /
+ * featureCounts is intended and not pinned by a test.  A set without a single read adds nothing.  SPL_ERR_ARG: null arguments; a
+ * set that is not fused; stranded outside 0..2; a start that is not strictly ascending; a code above n_genes that is not
+ * 0xFFFFFFFF; n_genes above 0xFFFFFFF0.  The context stays usable after a refusal.
+ * spl_gene_count_rule_host: the same rule for one read on the host (test hook; no file, no GPU): *result_out = the gene's index,
+ * -1 no feature, -2 ambiguous, -3 not counted. */
+int spl_gene_count(spl_ctx *ctx, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b,
+                   const int32_t *b_start, const uint32_t *b_code, int64_t n_genes, int64_t *inout /* n_genes + 3 */);
+int spl_gene_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int stranded, int64_t n_a,
+                             const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
+                             int64_t n_genes, int64_t *result_out);
+
 /* ---- the fused counting kernel's rule for simple reads, on the host (test hook; no file, no GPU) ---------------------------
  * A simple read (one aligned op) with bases [a, b), a = pos + shift, b = a + len, counts for the sites t with t and t + 1 both under it: the
  * distinct positions [lo, ub), lo = number of site positions <= a - 1, ub = number of site positions < b - 1.  The kernel asks one

@@ -29,6 +29,9 @@ BGZF is inflated there too, plain gzip by one host thread; a file the strict rul
 Extra sub-command ``coverage -B x.bam -o PREFIX [-c CHROM] [--isStranded -s fr|rf] [--perMillion]`` writes ``PREFIX.bedgraph`` (stranded:
 ``PREFIX.plus.bedgraph`` and ``PREFIX.minus.bedgraph``): per-base read depth in runs, reduced on the GPU from the decode -- the
 coverage track of the look at the alignments the reference's README asks for, without a sorted, indexed BAM (``coverage.py``).
+Extra sub-command ``genecounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [-c CHROM] [--isStranded -s fr|rf]`` writes
+``PREFIX.genecounts.tsv``: reads per gene, assigned on the GPU from the decode by htseq-count's ``--mode union --nonunique none`` per
+read -- the two-column file ``edgeR::readDGE`` reads, without a second pass over the BAM by another program (``genecounts.py``).
 Not read: CRAM, a pipe, and compressed text that has no ``@`` header line (uncompressed, the Python reader still takes that).
 """
 import argparse
@@ -180,6 +183,24 @@ def build_parser():
     v.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(v)
     _engine_flags(v)
+    n = sub.add_parser("genecounts", help="(this build only) reads per gene as htseq-count's two-column file, assigned on the GPU from the decode "
+                                          "(--mode union --nonunique none, per read): no second pass over the BAM by another program")
+    n.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    n.add_argument("-A", "--annotationFile", dest="annotationFile", required=False, default=None, help="gff3 or gtf file matching the reference genome used for alignment (required)")
+    n.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="output prefix: .genecounts.tsv is appended")
+    n.add_argument("-t", "--annotationType", dest="aType", nargs="?", default="exon", type=str, required=False,
+                   help="the feature type (column 3) whose lines are a gene's features - default: exon")
+    n.add_argument("--idAttr", dest="idAttr", default="gene_id", type=str, required=False, help="the attribute (column 9) that names a feature's gene - default: gene_id")
+    n.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False,
+                   help="optional: the reads of one chromosome only, and the genes with a feature on it")
+    n.add_argument("--isStranded", dest="isStranded", default=False, action="store_true", help="a read counts for the features of its strand only (check_strand's rule)")
+    n.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
+                   help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
+    n.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
+    n.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    n.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _filter_flags(n)
+    _engine_flags(n)
     return parser
 
 
@@ -231,19 +252,25 @@ def main(argv=None):
         print(kwargs.get("qGene"))
         print(kwargs.get("annotationFile"))
         parser.error("--gene requires --annotationFile and --maxIntronSize")
-    elif command in ("process", "combine", "combineShallow", "junctions", "coverage") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
+    elif command in ("process", "combine", "combineShallow", "junctions", "coverage", "genecounts") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
     if command == "coverage" and kwargs.get("strandedType") == "auto":
         parser.error("coverage: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
     if command == "coverage" and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
         parser.error("coverage: --strandedType/-s must be fr or rf")
+    if command == "genecounts" and kwargs.get("annotationFile") is None:
+        parser.error("genecounts: --annotationFile/-A is required: the genes are its features")
+    if command == "genecounts" and kwargs.get("strandedType") == "auto":
+        parser.error("genecounts: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
+    if command == "genecounts" and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
+        parser.error("genecounts: --strandedType/-s must be fr or rf")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":
         parser.error("-s auto and --strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
     if command in ("process", "junctions", "strandedness") and kwargs.get("minEvidence") is not None and kwargs["minEvidence"] < 0:
         parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -289,6 +316,9 @@ def main(argv=None):
     elif command == "coverage":
         from .coverage import coverage
         coverage(devices=devices, threads=threads, **kwargs)
+    elif command == "genecounts":
+        from .genecounts import genecounts
+        genecounts(devices=devices, threads=threads, **kwargs)
     elif command == "flagstat":
         from .flagstat import flagstat
         flagstat(devices=devices, threads=threads, **kwargs)

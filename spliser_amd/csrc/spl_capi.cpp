@@ -39,6 +39,8 @@
 #include "spl_strand_rule.h"
 #include "spl_coverage.h"
 #include "spl_coverage_rule.h"
+#include "spl_genecount.h"
+#include "spl_genecount_rule.h"
 #include "spl_simple_span.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
@@ -4260,6 +4262,84 @@ extern "C" int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t
     }
     *n_out = keep.n;
     if (past_end_out) *past_end_out = (bits & SPL_COV_PAST_END) ? 1 : 0;
+    return SPL_OK;
+}
+
+// ---- per-gene read counts (spl_genecount.hip; the rule is spl_genecount_rule.h) -----------------------------------------------
+namespace {
+// 0, or SPL_ERR_ARG with the message set: the two maps as spl_gene_count and its host hook take them.
+int gene_maps_fit(const char *who, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, int64_t n_genes)
+{
+    if (n_a < 0 || (n_a && (!a_start || !a_code)) || n_b < 0 || (n_b && (!b_start || !b_code))) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
+    if (stranded < 0 || stranded > 2) return spl_set_error(SPL_ERR_ARG, "%s: stranded must be 0 (one map), 1 (fr) or 2 (rf)", who);
+    if (n_genes < 0 || n_genes > (int64_t)SPL_GENE_INDEX_MAX) return spl_set_error(SPL_ERR_ARG, "%s: n_genes must be in 0 .. %u", who, SPL_GENE_INDEX_MAX);
+    const int64_t n[2] = {n_a, n_b};
+    const int32_t *const start[2] = {a_start, b_start};
+    const uint32_t *const code[2] = {a_code, b_code};
+    for (int m = 0; m < 2; ++m) {
+        int why = 0;
+        const int64_t k = spl_gene_map_flaw(n[m], start[m], code[m], n_genes, &why);
+        if (k < 0) continue;
+        if (why == 0) return spl_set_error(SPL_ERR_ARG, "%s: gene map %c is not strictly ascending at entry %lld", who, "ab"[m], (long long)k);
+        return spl_set_error(SPL_ERR_ARG, "%s: gene map %c has code %u at entry %lld, beyond the %lld genes", who, "ab"[m], code[m][k], (long long)k, (long long)n_genes);
+    }
+    return SPL_OK;
+}
+} // namespace
+
+// Every read's gene over a fused set's arrays: one launch per segment, n_genes + 3 sums in device memory, down and added to inout.
+extern "C" int spl_gene_count(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
+                              const uint32_t *b_code, int64_t n_genes, int64_t *inout)
+{
+    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_gene_count: null argument");
+    if (const int rc = gene_maps_fit("spl_gene_count", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_gene_count: the read set is not finished (spl_reads_finish)");
+    if (dr->segs.empty()) return SPL_OK; // (a set without a read has no arrays to be fused of, and adds nothing)
+    if (!(dr->fused && dr->groups.size() == 1))
+        return spl_set_error(SPL_ERR_ARG, "spl_gene_count needs a fused read set (all of it from one device decode or one spl_soa_upload)");
+    const spl_dreads::Group &g = dr->groups[0];
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n_out = (size_t)n_genes + SPL_GENE_SPECIALS;
+    DevBuf d_out, d_as, d_ac, d_bs, d_bc;
+    HIP_TRY(d_out.get(8 * n_out, c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
+    if (n_a) {
+        HIP_TRY(d_as.get(4 * (size_t)n_a, c->stream));
+        HIP_TRY(d_ac.get(4 * (size_t)n_a, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_as.p, a_start, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_ac.p, a_code, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
+    }
+    if (n_b) {
+        HIP_TRY(d_bs.get(4 * (size_t)n_b, c->stream));
+        HIP_TRY(d_bc.get(4 * (size_t)n_b, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bs.p, b_start, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bc.p, b_code, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
+    }
+    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+    for (const spl_dreads::Segment &seg : dr->segs) {
+        const spl_layout_seg &ls = g.segs[seg.group_seg];
+        if (ls.n_reads <= 0) continue;
+        // bytes: what the launch must read at least -- FLAG, POS and the two CIGAR offsets of a read, and its ops
+        splprof::Scope prof("spl_gene_count_kernel", c->stream, 10.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
+        const int rc = spl_dev_launch_gene_count(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_as.as<int32_t>(), d_ac.as<uint32_t>(), n_b,
+                                                 d_bs.as<int32_t>(), d_bc.as<uint32_t>(), (uint32_t)n_genes, d_out.as<unsigned long long>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "gene count kernel launch: %s", hipGetErrorString((hipError_t)rc));
+    }
+    std::vector<unsigned long long> sums(n_out, 0ull);
+    HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
+    return SPL_OK;
+}
+
+// The rule itself for one read: no GPU involved (test hook).  *result_out: the gene's index, -1 no feature, -2 ambiguous, -3 not counted.
+extern "C" int spl_gene_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int stranded, int64_t n_a, const int32_t *a_start,
+                                        const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, int64_t n_genes, int64_t *result_out)
+{
+    if (!result_out || (n_ops && !ops)) return spl_set_error(SPL_ERR_ARG, "spl_gene_count_rule_host: null argument");
+    if (const int rc = gene_maps_fit("spl_gene_count_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
+    const uint32_t r = spl_gene_read_result(flag, (int64_t)pos, ops, n_ops, (int64_t)shift, stranded, spl_gene_map_flat{n_a, a_start, a_code}, spl_gene_map_flat{n_b, b_start, b_code});
+    *result_out = r == SPL_GENE_NO_FEATURE ? -1 : r == SPL_GENE_AMBIGUOUS ? -2 : r == SPL_GENE_NOT_COUNTED ? -3 : (int64_t)r;
     return SPL_OK;
 }
 

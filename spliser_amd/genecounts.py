@@ -1,0 +1,275 @@
+"""``genecounts`` -- reads per gene, from the decode of the alignment file: the expression beside a change in SSE, without a second
+pass over the BAM by another program.
+
+Not part of SpliSER v0.1.8.  The diffSpliSER analysis is an edgeR analysis, and whoever reads a change in SSE wants the gene's
+expression beside it, from the same session; that has meant ``htseq-count`` or ``featureCounts`` over the file this build has just
+decoded -- minutes to hours of CPU, and ``htseq-count`` wants the sorted file ``--anyOrder`` exists to spare.  The decode leaves POS,
+FLAG and CIGAR of every read on the device, and ``spl_gene_count`` assigns every read there (the rule: include/spliser.h,
+csrc/spl_genecount_rule.h).  ``<out>.genecounts.tsv`` is htseq-count's two-column file, which ``edgeR::readDGE`` reads (it drops the
+``__`` rows).
+
+The rule.  A feature is a line of the GFF / GTF whose column 3 is ``-t`` (default ``exon``); its gene is the value of ``--idAttr``
+(default ``gene_id``); a gene is all features with one id, wherever they lie.  A read counts when it is mapped, primary, QC-passed
+and not supplementary, duplicates included; its aligned blocks (M, = and X; D and N are gaps) are held against the features: no
+gene under any base -> ``__no_feature``, one gene -> that gene, more -> ``__ambiguous``; every other read -> ``__not_counted``.
+With ``--isStranded -s fr|rf`` a read sees only the features of its strand (and those without one).  This is htseq-count's
+``--mode union --nonunique none``, and featureCounts' default, applied per READ: a paired fragment adds up to two.  Fragment counting
+needs mate pairing, which the decode does not keep: out of scope.  Parity with htseq-count and featureCounts is intended and
+unpinned (neither is on the build machine): the yardstick is this statement of the rule, restated in tests/genecases.py.
+"""
+import sys
+
+import numpy as np
+
+from . import native, process as _process
+
+SUFFIX = ".genecounts.tsv"
+STRANDED = {"fr": 1, "rf": 2}
+MANY = native.GENE_MANY
+SPECIALS = native.GENE_SPECIALS
+COORD_MAX = 2147483581              # the bound ``strandedness.cover_map`` enforces on a map's 1-based positions
+
+
+class Features(object):
+    """The features of an annotation: ``ids`` -- the gene ids, sorted, a gene's index is its place there --, ``chroms`` -- the
+    chromosomes in the order they first appear --, and per chromosome four arrays ``(left int64, right int64, strand uint8, gene
+    int64)``: 0-based half-open ``[column 4 - 1, column 5)``, the strand byte of column 7, the gene's index."""
+
+    def __init__(self, ids, chroms, by_chrom):
+        self.ids, self.chroms, self.by_chrom = ids, chroms, by_chrom
+
+    def arrays(self, chrom):
+        empty = np.zeros(0, np.int64)
+        return self.by_chrom.get(chrom, (empty, empty, np.zeros(0, np.uint8), empty))
+
+    def genes_on(self, chrom):
+        """Sorted indices of the genes with a feature on ``chrom`` (features without a base included: they are features)."""
+        return np.unique(self.arrays(chrom)[3])
+
+
+def attribute(text, key):
+    """The value of attribute ``key`` in column 9, GTF form ``key "value";`` or GFF3 form ``key=value;``, quotes stripped; None when
+    it is not there."""
+    for field in text.split(";"):
+        field = field.strip()
+        if not field.startswith(key):
+            continue
+        rest = field[len(key):]
+        if rest[:1] == "=":
+            value = rest[1:].strip()
+        elif rest[:1] in (" ", "\t"):
+            value = rest.strip()
+        else:
+            continue                    # (a longer key that begins alike: gene_id_version)
+        if len(value) >= 2 and value[0] == value[-1] == '"':
+            value = value[1:-1]
+        return value
+    return None
+
+
+def read_features(path, aType="exon", idAttr="gene_id"):
+    """The plain reader: every non-comment line with at least 9 columns whose column 3 equals ``aType``.  A line of the type
+    without ``idAttr`` is an error that names the line number.  -> Features (features with ``right <= left`` are kept here and
+    ignored by ``gene_maps``)."""
+    rows, names = {}, {}
+    with open(path) as fh:
+        for number, line in enumerate(fh, 1):
+            if line.startswith("#"):
+                continue
+            cols = line.rstrip("\r\n").split("\t")
+            if len(cols) < 9 or cols[2] != aType:
+                continue
+            gene = attribute(cols[8], idAttr)
+            if gene is None:
+                raise native.SpliserNativeError(-5, "%s: line %d: a %s feature without the attribute %s" % (path, number, aType, idAttr))
+            try:
+                left, right = int(cols[3]) - 1, int(cols[4])
+            except ValueError:
+                raise native.SpliserNativeError(-5, "%s: line %d: columns 4 and 5 are not numbers" % (path, number))
+            names.setdefault(gene, None)
+            rows.setdefault(cols[0], []).append((left, right, ord(cols[6][0]) if cols[6] else 0, gene))
+    ids = sorted(names)
+    index = {g: k for k, g in enumerate(ids)}
+    by_chrom = {}
+    for chrom, r in rows.items():
+        by_chrom[chrom] = (np.array([x[0] for x in r], np.int64), np.array([x[1] for x in r], np.int64), np.array([x[2] for x in r], np.uint8),
+                           np.array([index[x[3]] for x in r], np.int64))
+    return Features(ids, list(rows), by_chrom)
+
+
+def gene_map(left, right, gene):
+    """The gene map of one selection of features: -> (start int32, code uint32), ascending; code[k] holds for the 0-based positions
+    start[k] <= p < start[k + 1] (the last to the end; 0 below start[0]): 0 no feature, g + 1 only gene g, ``MANY`` two genes or
+    more; an entry only where the code changes.  A sweep: each gene's features are merged first (overlapping exons of one gene are
+    one gene), then every merged interval is an event pair carrying +-1 and +-(g + 1); where the depth is 1 the running sum is the code."""
+    left, right, gene = np.asarray(left, np.int64), np.asarray(right, np.int64), np.asarray(gene, np.int64)
+    keep = right > left
+    left, right, gene = left[keep], right[keep], gene[keep]
+    if not left.shape[0]:
+        return np.zeros(0, np.int32), np.zeros(0, np.uint32)
+    if int(right.max()) + 1 > COORD_MAX:
+        raise native.SpliserNativeError(-6, "a gene ends beyond the int32 coordinate space")
+    # merge per gene: sorted by (gene, left), a merged interval begins where left exceeds every right before it in the gene -- the
+    # running maximum is kept per gene by lifting gene g's coordinates by g * big
+    order = np.lexsort((left, gene))
+    left, right, gene = left[order], right[order], gene[order]
+    low = min(int(left.min()), 0)
+    big = int(right.max()) - low + 1
+    reach = np.maximum.accumulate(gene * big + (right - low))
+    first = np.ones(left.shape[0], bool)
+    first[1:] = gene[1:] * big + (left[1:] - low) > reach[:-1]
+    begins = np.flatnonzero(first)
+    ends = np.concatenate((begins[1:], [left.shape[0]])) - 1
+    m_left, m_right, m_gene = left[begins], reach[ends] - gene[ends] * big + low, gene[begins]
+    at = np.concatenate((m_left, m_right))
+    step = np.concatenate((np.ones(m_left.shape[0], np.int64), -np.ones(m_left.shape[0], np.int64)))
+    points = np.unique(at)
+    slot = np.searchsorted(points, at)
+    depth, total = np.zeros(points.shape[0], np.int64), np.zeros(points.shape[0], np.int64)
+    np.add.at(depth, slot, step)
+    np.add.at(total, slot, step * (np.concatenate((m_gene, m_gene)) + 1))
+    depth, total = np.cumsum(depth), np.cumsum(total)
+    code = np.where(depth == 0, 0, np.where(depth == 1, total, MANY)).astype(np.uint32)
+    change = np.ones(points.shape[0], bool)
+    change[1:] = code[1:] != code[:-1]
+    change[0] = code[0] != 0
+    return points[change].astype(np.int32), code[change]
+
+
+def gene_maps(left, right, strand, gene, stranded=False):
+    """The gene maps of one chromosome's features: -> (map a, map b).  Unstranded: map a of all features, map b None.  Stranded: map a
+    (the ``+`` reads') holds the features whose strand is not ``-``, map b those whose strand is not ``+``; a ``.`` is in both."""
+    left, right, strand, gene = np.asarray(left, np.int64), np.asarray(right, np.int64), np.asarray(strand, np.uint8), np.asarray(gene, np.int64)
+    if not stranded:
+        return gene_map(left, right, gene), None
+    plus, minus = strand != 45, strand != 43
+    return gene_map(left[plus], right[plus], gene[plus]), gene_map(left[minus], right[minus], gene[minus])
+
+
+def maps_of(features, chroms, stranded=False):
+    """{chrom: (map a, map b)} of the chromosomes of ``chroms`` that have a feature."""
+    out = {}
+    for chrom in chroms:
+        if chrom in features.by_chrom:
+            out[chrom] = gene_maps(*features.arrays(chrom), stranded=bool(stranded))
+    return out
+
+
+def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None):
+    """``spl_gene_count`` over every chromosome of ``chroms`` -> int64[n_genes + 3], the sums: the genes' reads, then no feature,
+    ambiguous, not counted.  On the plan of ``strandedness.tally_of_source``: a file decoded on the device is counted per chromosome
+    where it lies (the sets stay fused); after a decode in shares every device counts its piece and the host adds -- counts add over
+    reads; host-decoded reads and the Python reader's go up as four arrays (``upload_soa``), a fused set of their own.  ``maps``:
+    {chrom: (map a, map b)} (``maps_of``); a chromosome without one has no feature.  ``per_chrom``: a dict that gets, per chromosome
+    with reads, int64[4]: counted, no feature, ambiguous, not counted."""
+    import threading
+    is_bam = isinstance(source, native.BamFile)
+    n_genes = int(n_genes)
+    total, errors, lock = np.zeros(n_genes + 3, np.int64), [], threading.Lock()
+    on_device = is_bam and source.join_decoders()      # (however the device decode was started; False: the host threads have the file)
+    shares = getattr(source, "shares", None) if on_device else None
+
+    def count(dr, chrom):
+        a, b = maps.get(chrom, (None, None))
+        t = dr.gene_counts(n_genes, a, b, stranded)
+        with lock:
+            total[:] += t
+            if per_chrom is not None:
+                row = per_chrom.setdefault(chrom, np.zeros(4, np.int64))
+                row += [int(t[:n_genes].sum()), int(t[n_genes]), int(t[n_genes + 1]), int(t[n_genes + 2])]
+
+    def run(device, jobs):
+        try:
+            with native.Context(device) as ctx:
+                for chrom, add in jobs:
+                    if add is None:
+                        rs = source.reads(chrom)
+                        if rs is None or not rs.n:
+                            continue
+                        with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar)], [getattr(rs, "max_end", None)]) as soa:
+                            with ctx.begin_reads() as dr:
+                                dr.add_soa(soa, 0)
+                                dr.finish()
+                                count(dr, chrom)
+                    else:
+                        with ctx.begin_reads() as dr:
+                            if add(dr):
+                                dr.finish()
+                                count(dr, chrom)
+        except Exception as exc:
+            with lock:
+                errors.append(exc)
+
+    if shares:
+        plans = []
+        for k, (device, names) in enumerate(shares):
+            held = [c for c in chroms if c in names and source.share_ref(k, c)[0] > 0]
+            plans.append((device, [(c, (lambda dr, k=k, c=c: dr.add_bam_share(source, k, c))) for c in held]))
+    elif on_device:
+        plans = [(devices[0], [(c, (lambda dr, c=c: dr.add_bam(source, c))) for c in chroms])]
+    else:
+        plans = [(devices[0], [(c, None) for c in chroms])]
+    workers = [threading.Thread(target=run, args=plan) for plan in plans if plan[1]]
+    for w in workers:
+        w.start()
+    for w in workers:
+        w.join()
+    if errors:
+        raise errors[0]
+    return total
+
+
+def write_counts(path, ids, counts, only=None):
+    """``id\\tcount\\n`` for every gene in the order of ``ids`` (``only``: just the genes with these indices), zeros included, then the
+    three ``__`` rows.  -> the number of gene rows."""
+    n = len(ids)
+    rows = range(n) if only is None else [int(k) for k in only]
+    with open(path, "w") as fh:
+        for k in rows:
+            fh.write("%s\t%d\n" % (ids[k], int(counts[k])))
+        for k, name in enumerate(SPECIALS):
+            fh.write("%s\t%d\n" % (name, int(counts[n + k])))
+    return len(rows)
+
+
+def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id", qChrom="All", isStranded=False, strandedType=None, devices=(0,), threads=0, log=None,
+               gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False):
+    """The ``genecounts`` command: one decode, the annotation read meanwhile, ``<outputPath>.genecounts.tsv``.  ``qChrom``: the reads
+    of that chromosome, and the genes with a feature on it.  -> int64[n_genes + 3], the counts written."""
+    import timeit
+    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    if annotationFile is None:
+        raise ValueError("genecounts: an annotation file (-A) is required")
+    if isStranded and strandedType not in STRANDED:
+        raise ValueError("genecounts: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
+    stranded = STRANDED[strandedType] if isStranded else 0
+    devices = tuple(devices)
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder))
+    source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
+    try:
+        t0 = timeit.default_timer()
+        features = read_features(annotationFile, aType, idAttr)
+        n_genes = len(features.ids)
+        log("Annotation: %d %s features of %d genes on %d chromosomes (read in %.3f s)" % (sum(v[0].shape[0] for v in features.by_chrom.values()), aType, n_genes,
+                                                                                            len(features.chroms), timeit.default_timer() - t0))
+        if isinstance(source, native.BamFile):
+            source.wait_all()      # (every reference is complete at the end of the file, whatever its order)
+        if anyOrder:
+            _process.log_any_order(source, log)
+        chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+        maps = maps_of(features, chroms, stranded)
+        per_chrom = {}
+        counts = counts_of_source(source, devices, chroms, maps, n_genes, stranded, per_chrom)
+        for chrom in chroms:
+            if chrom in per_chrom:
+                log("  %s: %d reads counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom,) + tuple(int(v) for v in per_chrom[chrom])))
+        _process.log_filter(source, options.read_filter, log)
+    finally:
+        if hasattr(source, "close"):
+            source.close()
+    only = None if qChrom == "All" else features.genes_on(qChrom)
+    path = outputPath + SUFFIX
+    n_rows = write_counts(path, features.ids, counts, only)
+    log("%s: %d genes, %d reads counted, %d without a feature, %d ambiguous, %d not counted" % (path, n_rows, int(counts[:n_genes].sum()), int(counts[n_genes]),
+                                                                                               int(counts[n_genes + 1]), int(counts[n_genes + 2])))
+    return counts

@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -486,6 +486,22 @@ class DeviceReads(object):
         finally:
             lib().spl_coverage_free(self.ctx._h, h)
         return start, end, depth, dict(zip(COVERAGE_TOTALS, t.tolist()))
+
+    def gene_counts(self, n_genes, map_a, map_b=None, stranded=0, out=None):
+        """Per-gene read counts of this (finished, fused) set, on the device (``spl_gene_count``): ADDS to ``out`` (int64[n_genes + 3];
+        made when None) and returns it -- the genes' reads, then no feature, ambiguous, not counted.  ``map_a`` / ``map_b``: gene maps
+        ``(start int32, code uint32)`` in the set's coordinates (``genecounts.gene_maps``) or None; ``stranded``: 0 (``map_a`` serves
+        every read), 1 (fr) or 2 (rf): ``map_a`` serves the ``+`` reads, ``map_b`` the ``-`` reads."""
+        n_genes = int(n_genes)
+        if out is None:
+            out = np.zeros(max(n_genes, 0) + 3, np.int64)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.shape == (n_genes + 3,) and out.flags.c_contiguous):
+            raise ValueError("gene counts are a contiguous int64 array of n_genes + 3 entries")
+        (a_start, a_code), (b_start, b_code) = _gene_map_arrays(map_a), _gene_map_arrays(map_b)
+        _check(lib().spl_gene_count(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]), _ptr(a_start) if a_start.shape[0] else None,
+                                    _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
+                                    _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_genes), _ptr(out)))
+        return out
 
     def free(self):
         if self._h:
@@ -1074,6 +1090,32 @@ def strand_rule_host(flag, pos, ops, xs=0, cover=None, counters=None):
                                       ctypes.c_uint8(int(xs)), ctypes.c_int64(start.shape[0]), _ptr(start) if start.shape[0] else None,
                                       _ptr(code) if code.shape[0] else None, _ptr(counters)))
     return counters
+
+
+GENE_MANY = 0xFFFFFFFF                 # a gene map's code where two or more genes cover a position
+GENE_SPECIALS = ("__no_feature", "__ambiguous", "__not_counted")      # the three counters behind the genes'
+
+
+def _gene_map_arrays(gene_map):
+    if gene_map is None:
+        return np.zeros(0, np.int32), np.zeros(0, np.uint32)
+    start, code = _arr(gene_map[0], np.int32), _arr(gene_map[1], np.uint32)
+    if start.ndim != 1 or start.shape != code.shape:
+        raise ValueError("a gene map is two arrays of one length: start (int32) and code (uint32)")
+    return start, code
+
+
+def gene_count_rule_host(flag, pos, ops, n_genes, map_a, map_b=None, stranded=0, shift=0):
+    """The gene-count rule for one read on the host (``spl_gene_count_rule_host``): -> the gene's index, -1 no feature, -2 ambiguous,
+    -3 not counted."""
+    ops = np.ascontiguousarray(ops, np.uint32)
+    (a_start, a_code), (b_start, b_code) = _gene_map_arrays(map_a), _gene_map_arrays(map_b)
+    out = ctypes.c_int64(0)
+    _check(lib().spl_gene_count_rule_host(ctypes.c_uint32(int(flag)), ctypes.c_int32(int(pos)), _ptr(ops) if ops.shape[0] else None, ctypes.c_uint32(ops.shape[0]),
+                                          ctypes.c_int32(int(shift)), ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]), _ptr(a_start) if a_start.shape[0] else None,
+                                          _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
+                                          _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(int(n_genes)), ctypes.byref(out)))
+    return out.value
 
 
 COVERAGE_TOTALS = ("runs", "reads_seen", "contributed", "past_end", "covered_bases")
