@@ -204,6 +204,13 @@ int spl_reads_has_strand(const spl_dreads *dr, int *out);
 /* What the layout moves for a finished read set: the BAM-native arrays read (10 bytes a read + 4 an op) and the records written
  * (0 while the set is fused). */
 int spl_reads_layout_bytes(spl_ctx *ctx, const spl_dreads *dr, int64_t *soa_bytes_out, int64_t *record_bytes_out);
+/* The range kernel's slots of a finished read set as the last spl_reads_finish / spl_reads_relayout left them, read back (test
+ * hook; no product path calls it; waits for the layout).  *n_slots_out = 8 shares of equal length, *n_chunks_out chunks among
+ * them; any output may be NULL.  order_out: uint32[n_slots], the chunk of every slot (0xffffffff: none).  A fused set also has
+ * slots_out: n_slots descriptors of 64 bytes, and chunks_out: n_chunks descriptors of 32 bytes (spl_fused_slot, spl_layout_chunk
+ * of spl_devpack.h); asked of any other set they are an error. */
+int spl_reads_slots_download(spl_ctx *ctx, const spl_dreads *dr, int64_t *n_chunks_out, int64_t *n_slots_out, int *fused_out,
+                             uint32_t *order_out, void *slots_out, void *chunks_out);
 /* ... and the durations of the layout kernel's launches since spl_kernel_timing_begin (call before spl_kernel_timing_collect) */
 int spl_layout_timing_collect(spl_ctx *ctx, float *ms_out, int capacity, int *n_out);
 /* The host packer alone (no GPU involved; diagnostic and test hook): sizes of what an upload of `reads` would send, and --

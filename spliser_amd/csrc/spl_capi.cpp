@@ -456,8 +456,7 @@ struct spl_dreads {
     spl_chunk_meta *meta = nullptr;
     uint32_t *cost = nullptr;
     uint32_t *chunk_order = nullptr; // slot of an XCD share -> chunk, longest first (0xffffffff: none)
-    spl_fused_slot *by_chunk = nullptr; // the fused counting kernel's descriptor of every chunk (spl_layout_map_kernel) ...
-    spl_fused_slot *slots = nullptr;    // ... and the same in slot order, one per slot (spl_chunk_order_kernel)
+    spl_fused_slot *slots = nullptr;    // the fused counting kernel's descriptor of its chunk, one per slot (spl_chunk_slots_kernel)
     uint32_t *queue = nullptr; // reads the range kernel hands to the literal kernel (the counters are with the site table)
     uint32_t *queue_alt = nullptr;     // ... and the buffer the NEXT pass writes while this pass's literal kernel still reads
     uint32_t *queue_total = nullptr;   // entries the last pass queued (written by its literal kernel)
@@ -3202,12 +3201,21 @@ extern "C" int spl_sort_keys_device(spl_ctx *c, const uint64_t *keys, int64_t n,
 }
 
 // What a read set's device segments need between the arrays and the counters, on the context's main stream, nothing for the host
-// to wait for: per group the chunks' descriptors and cost estimates (from their numbers of reads and ops), the chunk order of the
-// range kernel from the costs (host-packed chunks' are up already), then the layout kernel per group -- the records and the
-// chunks' spl_chunk_meta -- and the range kernel can follow it directly.
+// to wait for.  A fused set: ONE launch for the chunks' descriptors, the chunk order of the range kernel and that kernel's slots.
+// Any other: per group the chunks' descriptors and cost estimates (from their numbers of reads and ops), the chunk order from
+// the costs (host-packed chunks' are up already), then the layout kernel per group -- the records and the chunks' spl_chunk_meta
+// -- and the range kernel can follow it directly.
 static int launch_layout(spl_ctx *c, spl_dreads *d)
 {
     const uint32_t chunk = 1u << d->chunk_shift;
+    if (d->fused) { // (one group holds every chunk: its descriptors, their order and the counting pass's slots in ONE launch; that pass makes its records itself)
+        spl_dreads::Group &g = d->groups[0];
+        const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+        splprof::Scope prof("spl_chunk_slots_kernel", c->stream, 104.0 * (double)d->n_chunks);
+        const int rc = spl_dev_launch_chunk_slots(&src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->chunk_order, d->slots, c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "chunk slots kernel launch: %s", hipGetErrorString((hipError_t)rc));
+        return SPL_OK;
+    }
     std::vector<spl_layout_params> lps;
     for (spl_dreads::Group &g : d->groups) {
         spl_layout_params lp;
@@ -3215,17 +3223,16 @@ static int launch_layout(spl_ctx *c, spl_dreads *d)
         lp.n_rec = g.src->n_rec; lp.n_ops = g.src->n_ops;
         lp.chunks = g.d_chunks; lp.rec_base = (uint8_t *)g.slab; lp.meta = d->meta;
         // (the chunks' descriptors hold offsets read from the arrays: made anew whenever the layout runs)
-        const int rc0 = spl_dev_launch_layout_map(&lp.src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->cost, d->by_chunk, c->stream);
+        const int rc0 = spl_dev_launch_layout_map(&lp.src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->cost, c->stream);
         if (rc0) return spl_set_error(SPL_ERR_HIP, "layout map kernel launch: %s", hipGetErrorString((hipError_t)rc0));
         lps.push_back(lp);
     }
     if (d->n_chunks) {
-        splprof::Scope prof("spl_chunk_order_kernel", c->stream, 8.0 * (double)d->n_chunks);
-        const int rc = spl_dev_launch_chunk_order(d->cost, d->n_chunks, chunk, d->chunk_order, d->by_chunk, d->slots, c->stream);
+        splprof::Scope prof("spl_chunk_slots_kernel", c->stream, 8.0 * (double)d->n_chunks);
+        const int rc = spl_dev_launch_chunk_order(d->cost, d->n_chunks, d->chunk_order, c->stream);
         if (rc) return spl_set_error(SPL_ERR_HIP, "chunk order kernel launch: %s", hipGetErrorString((hipError_t)rc));
     }
     size_t gi = 0;
-    if (d->fused) return SPL_OK; // (the counting pass makes its records itself)
     for (spl_dreads::Group &g : d->groups) {
         const spl_layout_params &lp = lps[gi++];
         int64_t n_reads = 0, n_ops = 0;
@@ -3275,7 +3282,7 @@ static int finish_reads(spl_ctx *c, spl_dreads *d)
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
     const size_t o_meta = take(sizeof(spl_chunk_meta) * std::max<size_t>(n, 1)), o_cost = take(4 * std::max<size_t>(n, 1)), o_order = take(4 * std::max<size_t>(d->n_slots, 1));
-    const size_t o_by_chunk = take(sizeof(spl_fused_slot) * std::max<size_t>(n, 1)), o_slots = take(sizeof(spl_fused_slot) * std::max<size_t>(d->n_slots, 1));
+    const size_t o_slots = take(sizeof(spl_fused_slot) * std::max<size_t>(d->n_slots, 1));
     const size_t o_total = take(4);
     const size_t o_queue = take(4 * 8 * shard_cap), o_queue_alt = take(c->tail ? 4 * 8 * shard_cap : 0);
     hipError_t e = devmem::get((void **)&d->ctl, std::max<size_t>(off, 256), 'c');
@@ -3283,7 +3290,6 @@ static int finish_reads(spl_ctx *c, spl_dreads *d)
     d->meta = (spl_chunk_meta *)(d->ctl + o_meta);
     d->cost = (uint32_t *)(d->ctl + o_cost);
     d->chunk_order = (uint32_t *)(d->ctl + o_order);
-    d->by_chunk = (spl_fused_slot *)(d->ctl + o_by_chunk);
     d->slots = (spl_fused_slot *)(d->ctl + o_slots);
     d->queue_total = (uint32_t *)(d->ctl + o_total);
     d->queue = (uint32_t *)(d->ctl + o_queue);
@@ -3669,6 +3675,26 @@ extern "C" int spl_reads_has_strand(const spl_dreads *d, int *out)
 {
     if (!d || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_has_strand: null argument");
     *out = d->finished && d->fused && d->groups.size() == 1 && d->groups[0].src->xs ? 1 : 0;
+    return SPL_OK;
+}
+
+// The range kernel's chunk order, the fused pass's slots and the chunks' descriptors of a finished read set as the last layout
+// left them, read back (test hook: no product path calls it).  Waits for the layout.
+extern "C" int spl_reads_slots_download(spl_ctx *c, const spl_dreads *d, int64_t *n_chunks_out, int64_t *n_slots_out, int *fused_out, uint32_t *order_out, void *slots_out,
+                                        void *chunks_out)
+{
+    if (!c || !d) return spl_set_error(SPL_ERR_ARG, "spl_reads_slots_download: null argument");
+    if (!d->finished) return spl_set_error(SPL_ERR_ARG, "spl_reads_slots_download: the read set is not finished (spl_reads_finish)");
+    if (n_chunks_out) *n_chunks_out = (int64_t)d->n_chunks;
+    if (n_slots_out) *n_slots_out = (int64_t)d->n_slots;
+    if (fused_out) *fused_out = d->fused ? 1 : 0;
+    if (!d->n_chunks || (!order_out && !slots_out && !chunks_out)) return SPL_OK;
+    if ((slots_out || chunks_out) && !d->fused) return spl_set_error(SPL_ERR_ARG, "spl_reads_slots_download: only a fused read set has slots and one list of chunk descriptors");
+    HIP_TRY(hipSetDevice(c->device));
+    if (order_out) HIP_TRY(hipMemcpyAsync(order_out, d->chunk_order, 4 * (size_t)d->n_slots, hipMemcpyDeviceToHost, c->stream));
+    if (slots_out) HIP_TRY(hipMemcpyAsync(slots_out, d->slots, sizeof(spl_fused_slot) * (size_t)d->n_slots, hipMemcpyDeviceToHost, c->stream));
+    if (chunks_out) HIP_TRY(hipMemcpyAsync(chunks_out, d->groups[0].d_chunks, sizeof(spl_layout_chunk) * (size_t)d->n_chunks, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SPL_OK;
 }
 

@@ -145,8 +145,8 @@ struct spl_hot_params {
     int32_t *err;
     // the FUSED instantiation (reads counted straight from the BAM-native arrays, see spl_count_ranges_kernel): the chunks are
     // cells of the grid over the arrays' indexes; chunk_meta is not looked at
-    const spl_layout_chunk *cells; // [chunks] (spl_devpack.h; made by spl_layout_map_kernel)
-    const spl_fused_slot *slots; // [n_chunks] what a workgroup needs of its chunk, in slot order (spl_chunk_order_kernel)
+    const spl_layout_chunk *cells; // [chunks] (spl_devpack.h; made by spl_chunk_slots_kernel)
+    const spl_fused_slot *slots; // [n_chunks] what a workgroup needs of its chunk, in slot order (spl_chunk_slots_kernel)
     spl_devreads src;
     int64_t src_n_rec, src_n_ops;
 };

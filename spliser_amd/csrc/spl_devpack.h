@@ -31,8 +31,9 @@ struct spl_layout_seg {
 #define SPL_LAYOUT_SLOT(chunk_reads) ((size_t)(chunk_reads) * SPL_REC_OTHER + 256u)
 
 // What a workgroup of the layout kernel needs to know about its chunk, in ONE scalar load (made from the segments and the
-// arrays' CIGAR offsets by spl_layout_map_kernel: a workgroup that first had to look its segment up, then the offsets of its
-// first and last read, had three memory trips behind it before its first op was asked for).
+// arrays' CIGAR offsets by spl_chunk_slots_kernel, or by spl_layout_map_kernel for a set that is not fused: a workgroup that first
+// had to look its segment up, then the offsets of its first and last read, had three memory trips behind it before its first op
+// was asked for).
 struct spl_layout_chunk {
     int64_t lo;                // index of the chunk's first read in the arrays (its cell of the grid: lo & ~(chunk - 1))
     uint32_t n;                // reads
@@ -45,7 +46,7 @@ struct spl_layout_chunk {
 // What a workgroup of the FUSED counting kernel needs to know about its chunk (spl_kernels.hip), one per SLOT of that kernel's
 // grid and in slot order, 64 bytes on a 64-byte boundary: ONE scalar load where the workgroup had the chunk order, the chunk's
 // descriptor and then the arrays themselves (the CIGAR offsets at its tiles' boundaries, its first POS) to go through before it
-// could ask for its first read.  Made per chunk by spl_layout_map_kernel, put in slot order by spl_chunk_order_kernel.
+// could ask for its first read.  Made per chunk by spl_chunk_slots_kernel, and written by it to the chunk's slot.
 #define SPL_TILE_FUSED_SHIFT 10           // reads per tile of a fused pass: the stage of 1024 reads' ops is 16 KB of LDS
 #define SPL_TILE_FUSED (1 << SPL_TILE_FUSED_SHIFT)
 #define SPL_FUSED_TILES_MAX 4             // (a chunk of SPL_CHUNK_BIG reads)
@@ -78,20 +79,27 @@ static inline uint32_t spl_layout_seg_chunks(int64_t first, int64_t n_reads, uin
 }
 // Slots per XCD share of the range kernel's grid for n chunks (blocks of 8 consecutive chunks dealt round-robin to the eight).
 static inline uint32_t spl_order_per(uint32_t n_chunks) { return ((n_chunks + 7u) / 8u + 7u) / 8u * 8u; }
+// (the most chunks a set can have: a share's members are numbered in 32 bits, and so are the chunks they stand for)
+#define SPL_ORDER_CHUNKS_MAX 0xfff00000u
 
 #ifdef __cplusplus
 extern "C" {
 #endif
-// chunks[k] = the launch's k-th chunk (which segment's, where its reads and ops lie), cost[its flat index] = what it will cost the
-// range kernel, roughly, from its numbers of reads and ops (device arrays; chunk = reads per chunk); by_chunk[its flat index] =
-// the fused kernel's descriptor of it
+// A group of a read set that is not fused: chunks[k] = the group's k-th chunk (which segment's, where its reads and ops lie),
+// cost[its flat index] = what it will cost the range kernel, roughly, from its numbers of reads and ops (device arrays; chunk =
+// reads per chunk, a power of two)
 int spl_dev_launch_layout_map(const spl_devreads *src, const spl_layout_seg *segs, uint32_t n_segs, uint32_t n_chunks, uint32_t chunk, spl_layout_chunk *chunks, uint32_t *cost,
-                              spl_fused_slot *by_chunk, void *stream);
+                              void *stream);
 // the layout itself: one workgroup per chunk of the launch (chunk = reads per chunk, 2048 or 4096)
 int spl_dev_launch_layout(const spl_layout_params *p, uint32_t n_dev_chunks, uint32_t chunk, void *stream, void *ev_start, void *ev_stop);
-// cost[n_chunks] -> order[8 * spl_order_per(n_chunks)]: the range kernel's slots, XCD share by XCD share, longest chunk first;
-// 0xffffffff = an empty slot; slots[the same] = by_chunk[order[slot]], or a descriptor marked SPL_SLOT_EMPTY
-int spl_dev_launch_chunk_order(const uint32_t *cost, uint32_t n_chunks, uint32_t chunk, uint32_t *order, const spl_fused_slot *by_chunk, spl_fused_slot *slots, void *stream);
+// A fused read set (all n_chunks chunks of its flat list are the segments' of ONE group), one launch: chunks[k] as above,
+// order[8 * spl_order_per(n_chunks)] = the range kernel's slots, XCD share by XCD share, longest chunk first (equal keys, cost / 16,
+// by chunk number); 0xffffffff = an empty slot; slots[the same] = the fused kernel's descriptor of chunk order[slot], or one marked
+// SPL_SLOT_EMPTY
+int spl_dev_launch_chunk_slots(const spl_devreads *src, const spl_layout_seg *segs, uint32_t n_segs, uint32_t n_chunks, uint32_t chunk, spl_layout_chunk *chunks, uint32_t *order,
+                               spl_fused_slot *slots, void *stream);
+// cost[n_chunks] -> order[8 * spl_order_per(n_chunks)], the same order from costs that are in memory (a set that is not fused)
+int spl_dev_launch_chunk_order(const uint32_t *cost, uint32_t n_chunks, uint32_t *order, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 // spl_junctions.hip -- the junction table of a FUSED read set (`process` without -b and the `junctions` command
 // after a decode on the device): straight from the BAM-native arrays pos / flag / cig_off / cigar, driven by the chunk descriptors
-// spl_layout_map_kernel writes when the set is finished -- no records in memory, no layout launch.  The table, its key, its hash
+// spl_chunk_slots_kernel writes when the set is finished -- no records in memory, no layout launch.  The table, its key, its hash
 // and its compaction are spl_junction_kernel's (spl_kernels.hip: the same table from packed records); the per-read walk is
 // spl_junction_walk.h, which the host compiles too.
 #include <hip/hip_runtime.h>
@@ -54,7 +54,7 @@ __device__ __forceinline__ void junction_merge_insert(bool have, unsigned long l
 }
 
 // ---- the same table from a FUSED read set: straight from pos / flag / cig_off / cigar, driven by the chunk descriptors of
-// spl_layout_map_kernel (first read, number of reads, shift) -- no records, no layout launch.
+// spl_chunk_slots_kernel (first read, number of reads, shift) -- no records, no layout launch.
 //
 // One workgroup per chunk, a TILE of 256 reads at a time (a read a lane):
 //   1. the lane's two cig_off words give its op count before anything else is touched: with min_anchor > 0 a read of fewer than

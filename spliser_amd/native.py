@@ -49,7 +49,7 @@ EXPORTS = [
     "spl_abi_version", "spl_last_error", "spl_device_count", "spl_trim", "spl_create", "spl_create_on_stream", "spl_destroy",
     "spl_sync", "spl_pass_barrier", "spl_timer_begin", "spl_timer_end", "spl_kernel_timing_begin", "spl_kernel_timing_collect", "spl_prof_enable", "spl_prof_report", "spl_count", "spl_sse", "spl_sites_upload", "spl_sites_free",
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
-    "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_reads_has_strand", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes",
+    "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_reads_has_strand", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes", "spl_reads_slots_download",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
@@ -428,6 +428,22 @@ class DeviceReads(object):
         a, b = ctypes.c_int64(0), ctypes.c_int64(0)
         _check(lib().spl_reads_layout_bytes(self.ctx._h, self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def slots(self):
+        """The range kernel's slots of this (finished) set as the last layout left them (test hook: ``spl_reads_slots_download``) ->
+        dict: ``fused``; ``order`` uint32[8, per], the chunk of every slot of every XCD share (0xffffffff: none); for a fused set
+        also ``slots`` uint8[8, per, 64] and ``chunks`` uint8[n_chunks, 32], the descriptors as bytes (``spl_devpack.h``)."""
+        n, ns, fused = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
+        _check(lib().spl_reads_slots_download(self.ctx._h, self._h, ctypes.byref(n), ctypes.byref(ns), ctypes.byref(fused), None, None, None))
+        n, ns, fused = n.value, ns.value, bool(fused.value)
+        order = np.zeros(max(ns, 1), np.uint32)
+        slots = np.zeros((max(ns, 1), 64), np.uint8) if fused else None
+        chunks = np.zeros((max(n, 1), 32), np.uint8) if fused else None
+        _check(lib().spl_reads_slots_download(self.ctx._h, self._h, None, None, None, _ptr(order), _ptr(slots), _ptr(chunks)))
+        out = dict(fused=fused, order=order[:ns].reshape(8, ns // 8))
+        if fused:
+            out.update(slots=slots[:ns].reshape(8, ns // 8, 64), chunks=chunks[:n])
+        return out
 
     def relayout(self):
         """The layout kernel once more, into the same records (segments that were laid out on the device)."""
