@@ -562,6 +562,46 @@ int spl_gene_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, ui
                              const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
                              int64_t n_genes, int64_t *result_out);
 
+/* ---- per-exon-bin read counts (what the pipeline otherwise leaves to a second pass by another program) -----------------------
+ * Replaces `featureCounts -f -O` / `dexseq_count.py` over the file this library has just decoded: whoever looks at a change in
+ * splice-site strength also asks about exon usage (edgeR::diffSpliceDGE, DEXSeq), which needs reads per exon counting bin.  The
+ * reference has no counterpart.  spl_exon_count counts, on the device, over the BAM-native arrays of a FUSED read set, the reads
+ * of every bin of one chromosome.  The rule (csrc/spl_exoncount_rule.h):
+ *   features    and selections are spl_gene_count's: a feature is an interval [left, right) of one gene, those with right <= left
+ *               are ignored; unstranded, map a is made of all of a chromosome's features; stranded, map a of those whose strand is
+ *               not '-', map b of those whose strand is not '+' (a '.' is in both);
+ *   bins        for one selection, cut the chromosome at every left and every right of its features, and take a piece between two
+ *               consecutive cuts: covered by no feature = code 0; by features of exactly one gene g = the BIN (g, start, end); by
+ *               features of two or more genes = shared, code 0xFFFFFFFF, and no bin.  Two abutting exons of one gene are two bins;
+ *               the same exon in two transcripts is one; the same (gene, start, end) out of both maps is one.  A chromosome's bins
+ *               are numbered 0 .. n_bins - 1 in the order (start, end, gene) over the distinct triples of both maps;
+ *   bin map     the shape of a gene map: ascending int32 start[n] with uint32 code[n], 0 = none, b + 1 = bin b, 0xFFFFFFFF =
+ *               shared, an entry only where the code changes; bin_gene[n_bins] = every bin's gene, only ever compared for equality;
+ *   a read      eligibility, map and blocks are spl_gene_count's (nothing clipped).  Its hit stretches are the stretches of its
+ *               map that a block overlaps by a base or more, each taken ONCE however many of its blocks overlap it;
+ *   verdict     any hit stretch shared, or two hit stretches with bins of different genes = "ambiguous", and NO bin is
+ *               incremented; no hit stretch with a bin = "no feature"; otherwise "counted", and every hit stretch's bin gets + 1;
+ *               every other read of the set is "not counted".
+ * This is DEXSeq's counting (dexseq_count.py: reads with bins of more than one gene are _ambiguous) and `featureCounts -f -O`
+ * restricted to reads of one gene, applied per READ: counting is per read, and a paired fragment adds up to two per bin.  Fragment
+ * counting needs mate pairing, which the decode does not keep: out of scope.  Parity with DEXSeq / featureCounts is intended and
+ * unpinned: it is not pinned by a test, neither tool being where this is built.  By construction a read's verdict is the one
+ * spl_gene_count gives it on the gene maps of the same features.
+ * inout[0 .. n_bins) += the bins' reads, inout[n_bins] += counted reads, [n_bins + 1] += no feature, [n_bins + 2] += ambiguous,
+ * [n_bins + 3] += not counted: the last four ADDED sum to the reads of the set.  Bins are the chromosome's own: a call moves
+ * n_bins + 4 words.  The call synchronises; integer sums, exact and the same for the reads in any order (one atomic per run of equal
+ * bins in a wave and round).  SPL_ERR_ARG: spl_gene_count's own refusals; a code above n_bins that is not 0xFFFFFFFF; n_bins above
+ * 0xFFFFFFF0; a null bin_gene with n_bins > 0.  The context stays usable after a refusal.
+ * spl_exon_count_rule_host: the same rule for one read on the host (test hook; no file, no GPU): *verdict_out = 0 counted, -1 no
+ * feature, -2 ambiguous, -3 not counted; bins_out[0 .. cap) = a counted read's bins in the order of their stretches, *n_hits_out =
+ * their number, also beyond cap; any other verdict has no hit. */
+int spl_exon_count(spl_ctx *ctx, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b,
+                   const int32_t *b_start, const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *inout /* n_bins + 4 */);
+int spl_exon_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int stranded, int64_t n_a,
+                             const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
+                             int64_t n_bins, const uint32_t *bin_gene, int64_t *verdict_out, int64_t *bins_out, int64_t cap,
+                             int64_t *n_hits_out);
+
 /* ---- the fused counting kernel's rule for simple reads, on the host (test hook; no file, no GPU) ---------------------------
  * A simple read (one aligned op) with bases [a, b), a = pos + shift, b = a + len, counts for the sites t with t and t + 1 both under it: the
  * distinct positions [lo, ub), lo = number of site positions <= a - 1, ub = number of site positions < b - 1.  The kernel asks one

@@ -32,6 +32,10 @@ coverage track of the look at the alignments the reference's README asks for, wi
 Extra sub-command ``genecounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [-c CHROM] [--isStranded -s fr|rf]`` writes
 ``PREFIX.genecounts.tsv``: reads per gene, assigned on the GPU from the decode by htseq-count's ``--mode union --nonunique none`` per
 read -- the two-column file ``edgeR::readDGE`` reads, without a second pass over the BAM by another program (``genecounts.py``).
+Extra sub-command ``exoncounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [-c CHROM] [--isStranded -s fr|rf]`` writes
+``PREFIX.exonbins.tsv`` and ``PREFIX.exoncounts.tsv``: reads per exon counting bin, counted on the GPU from the decode by DEXSeq's rule
+(``featureCounts -f -O`` restricted to reads of one gene) per read -- what ``edgeR::diffSpliceDGE`` needs, without a second pass over
+the BAM by another program (``exoncounts.py``).
 Not read: CRAM, a pipe, and compressed text that has no ``@`` header line (uncompressed, the Python reader still takes that).
 """
 import argparse
@@ -201,6 +205,24 @@ def build_parser():
     n.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(n)
     _engine_flags(n)
+    x = sub.add_parser("exoncounts", help="(this build only) reads per exon counting bin for edgeR::diffSpliceDGE / DEXSeq, counted on the GPU from the decode "
+                                          "(dexseq_count.py's rule, featureCounts -f -O for reads of one gene; per read): no second pass over the BAM by another program")
+    x.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    x.add_argument("-A", "--annotationFile", dest="annotationFile", required=False, default=None, help="gff3 or gtf file matching the reference genome used for alignment (required)")
+    x.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="output prefix: .exonbins.tsv and .exoncounts.tsv are appended")
+    x.add_argument("-t", "--annotationType", dest="aType", nargs="?", default="exon", type=str, required=False,
+                   help="the feature type (column 3) whose lines are a gene's features - default: exon")
+    x.add_argument("--idAttr", dest="idAttr", default="gene_id", type=str, required=False, help="the attribute (column 9) that names a feature's gene - default: gene_id")
+    x.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False,
+                   help="optional: the reads of one chromosome only, and the bins on it (under the ids they have in the whole annotation)")
+    x.add_argument("--isStranded", dest="isStranded", default=False, action="store_true", help="a read counts for the features of its strand only (check_strand's rule)")
+    x.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
+                   help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
+    x.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
+    x.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    x.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _filter_flags(x)
+    _engine_flags(x)
     return parser
 
 
@@ -252,25 +274,25 @@ def main(argv=None):
         print(kwargs.get("qGene"))
         print(kwargs.get("annotationFile"))
         parser.error("--gene requires --annotationFile and --maxIntronSize")
-    elif command in ("process", "combine", "combineShallow", "junctions", "coverage", "genecounts") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
+    elif command in ("process", "combine", "combineShallow", "junctions", "coverage", "genecounts", "exoncounts") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
     if command == "coverage" and kwargs.get("strandedType") == "auto":
         parser.error("coverage: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
     if command == "coverage" and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
         parser.error("coverage: --strandedType/-s must be fr or rf")
-    if command == "genecounts" and kwargs.get("annotationFile") is None:
-        parser.error("genecounts: --annotationFile/-A is required: the genes are its features")
-    if command == "genecounts" and kwargs.get("strandedType") == "auto":
-        parser.error("genecounts: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
-    if command == "genecounts" and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
-        parser.error("genecounts: --strandedType/-s must be fr or rf")
+    if command in ("genecounts", "exoncounts") and kwargs.get("annotationFile") is None:
+        parser.error("%s: --annotationFile/-A is required: the genes are its features" % command)
+    if command in ("genecounts", "exoncounts") and kwargs.get("strandedType") == "auto":
+        parser.error("%s: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf" % command)
+    if command in ("genecounts", "exoncounts") and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
+        parser.error("%s: --strandedType/-s must be fr or rf" % command)
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":
         parser.error("-s auto and --strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
     if command in ("process", "junctions", "strandedness") and kwargs.get("minEvidence") is not None and kwargs["minEvidence"] < 0:
         parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts", "exoncounts"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -319,6 +341,9 @@ def main(argv=None):
     elif command == "genecounts":
         from .genecounts import genecounts
         genecounts(devices=devices, threads=threads, **kwargs)
+    elif command == "exoncounts":
+        from .exoncounts import exoncounts
+        exoncounts(devices=devices, threads=threads, **kwargs)
     elif command == "flagstat":
         from .flagstat import flagstat
         flagstat(devices=devices, threads=threads, **kwargs)

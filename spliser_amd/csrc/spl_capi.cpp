@@ -41,6 +41,8 @@
 #include "spl_coverage_rule.h"
 #include "spl_genecount.h"
 #include "spl_genecount_rule.h"
+#include "spl_exoncount.h"
+#include "spl_exoncount_rule.h"
 #include "spl_simple_span.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
@@ -4366,6 +4368,75 @@ extern "C" int spl_gene_count_rule_host(uint32_t flag, int32_t pos, const uint32
     if (const int rc = gene_maps_fit("spl_gene_count_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
     const uint32_t r = spl_gene_read_result(flag, (int64_t)pos, ops, n_ops, (int64_t)shift, stranded, spl_gene_map_flat{n_a, a_start, a_code}, spl_gene_map_flat{n_b, b_start, b_code});
     *result_out = r == SPL_GENE_NO_FEATURE ? -1 : r == SPL_GENE_AMBIGUOUS ? -2 : r == SPL_GENE_NOT_COUNTED ? -3 : (int64_t)r;
+    return SPL_OK;
+}
+
+// ---- per-exon-bin read counts (spl_exoncount.hip; the rule is spl_exoncount_rule.h) --------------------------------------------
+namespace {
+// 0, or SPL_ERR_ARG with the message set: the bins and the two bin maps as spl_exon_count and its host hook take them.
+int exon_maps_fit(const char *who, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, int64_t n_bins,
+                  const uint32_t *bin_gene)
+{
+    if (n_bins < 0 || n_bins > (int64_t)SPL_GENE_INDEX_MAX) return spl_set_error(SPL_ERR_ARG, "%s: n_bins must be in 0 .. %u", who, SPL_GENE_INDEX_MAX);
+    if (n_bins && !bin_gene) return spl_set_error(SPL_ERR_ARG, "%s: null argument (the bins' genes)", who);
+    return gene_maps_fit(who, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins); // (a bin map is a gene map whose codes are bins')
+}
+} // namespace
+
+// Every read's bins over a fused set's arrays: one launch per segment, n_bins + 4 sums in device memory, down and added to inout.
+extern "C" int spl_exon_count(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
+                              const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *inout)
+{
+    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_exon_count: null argument");
+    if (const int rc = exon_maps_fit("spl_exon_count", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_exon_count: the read set is not finished (spl_reads_finish)");
+    if (dr->segs.empty()) return SPL_OK; // (a set without a read has no arrays to be fused of, and adds nothing)
+    if (!(dr->fused && dr->groups.size() == 1))
+        return spl_set_error(SPL_ERR_ARG, "spl_exon_count needs a fused read set (all of it from one device decode or one spl_soa_upload)");
+    const spl_dreads::Group &g = dr->groups[0];
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n_out = (size_t)n_bins + SPL_EXON_VERDICTS;
+    DevBuf d_out, d_gene, d_map[4];
+    HIP_TRY(d_out.get(8 * n_out, c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
+    if (n_bins) {
+        HIP_TRY(d_gene.get(4 * (size_t)n_bins, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_gene.p, bin_gene, 4 * (size_t)n_bins, hipMemcpyHostToDevice, c->stream));
+    }
+    const void *const host[4] = {a_start, a_code, b_start, b_code};
+    const int64_t entries[4] = {n_a, n_a, n_b, n_b};
+    for (int m = 0; m < 4; ++m) {
+        if (!entries[m]) continue;
+        HIP_TRY(d_map[m].get(4 * (size_t)entries[m], c->stream));
+        HIP_TRY(hipMemcpyAsync(d_map[m].p, host[m], 4 * (size_t)entries[m], hipMemcpyHostToDevice, c->stream));
+    }
+    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+    for (const spl_dreads::Segment &seg : dr->segs) {
+        const spl_layout_seg &ls = g.segs[seg.group_seg];
+        if (ls.n_reads <= 0) continue;
+        // bytes: what the launch must read at least -- FLAG, POS and the two CIGAR offsets of a read, and its ops (once: the second walk's are cached)
+        splprof::Scope prof("spl_exon_count_kernel", c->stream, 10.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
+        const int rc = spl_dev_launch_exon_count(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_map[0].as<int32_t>(), d_map[1].as<uint32_t>(), n_b,
+                                                 d_map[2].as<int32_t>(), d_map[3].as<uint32_t>(), (uint32_t)n_bins, d_gene.as<uint32_t>(), d_out.as<unsigned long long>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "exon count kernel launch: %s", hipGetErrorString((hipError_t)rc));
+    }
+    std::vector<unsigned long long> sums(n_out, 0ull);
+    HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
+    return SPL_OK;
+}
+
+// The rule itself for one read: no GPU involved (test hook).  *verdict_out: 0 counted, -1 no feature, -2 ambiguous, -3 not counted.
+extern "C" int spl_exon_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int stranded, int64_t n_a, const int32_t *a_start,
+                                        const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *verdict_out,
+                                        int64_t *bins_out, int64_t cap, int64_t *n_hits_out)
+{
+    if (!verdict_out || !n_hits_out || (n_ops && !ops) || cap < 0 || (cap && !bins_out)) return spl_set_error(SPL_ERR_ARG, "spl_exon_count_rule_host: null argument");
+    if (const int rc = exon_maps_fit("spl_exon_count_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
+    const uint32_t v = spl_exon_read_result(flag, (int64_t)pos, ops, n_ops, (int64_t)shift, stranded, spl_gene_map_flat{n_a, a_start, a_code}, spl_gene_map_flat{n_b, b_start, b_code}, bin_gene,
+                                            bins_out, cap, n_hits_out);
+    *verdict_out = -(int64_t)v;
     return SPL_OK;
 }
 

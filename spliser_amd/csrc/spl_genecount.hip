@@ -23,6 +23,7 @@
 #include "spl_genecount.h"
 #include "spl_genecount_rule.h"
 #include "spl_genecount_wave.h"
+#include "spl_genemap_dev.h" // DevMap, DevOps, levels
 
 static_assert(splgene::NO_FEATURE == SPL_GENE_NO_FEATURE && splgene::AMBIGUOUS == SPL_GENE_AMBIGUOUS && splgene::NOT_COUNTED == SPL_GENE_NOT_COUNTED &&
                   splgene::IDLE == SPL_GENE_IDLE && splgene::SPECIALS == SPL_GENE_SPECIALS,
@@ -30,30 +31,6 @@ static_assert(splgene::NO_FEATURE == SPL_GENE_NO_FEATURE && splgene::AMBIGUOUS =
 static_assert(SPL_GENE_TILE % 64 == 0, "whole waves: splgene::wave_count is called by all 64 lanes");
 
 namespace {
-
-// A gene map as a workgroup has it: the top level in LDS, the entries in global memory.
-struct DevMap {
-    const int32_t *top; // LDS
-    uint32_t n_top, stride;
-    int64_t n;
-    const int32_t *start;
-    const uint32_t *code;
-    __device__ __forceinline__ int64_t size() const { return n; }
-    __device__ __forceinline__ int64_t find(int64_t pos) const
-    {
-        const int64_t j = spl_cover_find(top, 0, n_top, pos);
-        if (j < 0) return -1;
-        const int64_t lo = j * stride, hi = lo + stride < n ? lo + stride : n;
-        return spl_cover_find(start, lo, hi, pos); // (start[lo] <= pos: the answer is lo at least)
-    }
-    __device__ __forceinline__ int64_t start_at(int64_t k) const { return (int64_t)start[k]; }
-    __device__ __forceinline__ uint32_t code_at(int64_t k) const { return code[k]; }
-};
-
-struct DevOps {
-    const uint32_t *p;
-    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return p[k]; }
-};
 
 __global__ __launch_bounds__(SPL_GENE_TILE) void spl_gene_count_kernel(const spl_devreads src, int64_t n_ops_total, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a,
                                                                         const int32_t *a_start, const uint32_t *a_code, uint32_t a_stride, uint32_t a_top, int64_t n_b,
@@ -92,12 +69,6 @@ __global__ __launch_bounds__(SPL_GENE_TILE) void spl_gene_count_kernel(const spl
     if (t < SPL_GENE_SPECIALS && s_sum[t]) atomicAdd(&counts[(int64_t)n_genes + t], (unsigned long long)s_sum[t]);
 }
 
-void levels(int64_t n, uint32_t *stride, uint32_t *n_top)
-{
-    *stride = n ? (uint32_t)((n + SPL_GENE_TOP - 1) / SPL_GENE_TOP) : 1u;
-    *n_top = n ? (uint32_t)((n + *stride - 1) / *stride) : 0u;
-}
-
 } // namespace
 
 extern "C" uint32_t spl_dev_gene_grid(int64_t n)
@@ -114,8 +85,8 @@ extern "C" int spl_dev_launch_gene_count(const spl_devreads *src, int64_t n_rec,
         (n_b && (!b_start || !b_code)))
         return (int)hipErrorInvalidValue;
     uint32_t a_stride, a_top, b_stride, b_top;
-    levels(n_a, &a_stride, &a_top);
-    levels(n_b, &b_stride, &b_top);
+    levels(n_a, SPL_GENE_TOP, &a_stride, &a_top);
+    levels(n_b, SPL_GENE_TOP, &b_stride, &b_top);
     hipLaunchKernelGGL(spl_gene_count_kernel, dim3(spl_dev_gene_grid(n)), dim3(SPL_GENE_TILE), 0, (hipStream_t)stream, *src, n_ops, first, n, shift, stranded, n_a, a_start, a_code, a_stride,
                        a_top, n_b, b_start, b_code, b_stride, b_top, n_genes, counts);
     return (int)hipGetLastError();

@@ -20,16 +20,25 @@ namespace splgene {
 constexpr uint32_t NO_FEATURE = 0xFFFFFFFCu, AMBIGUOUS = 0xFFFFFFFDu, NOT_COUNTED = 0xFFFFFFFEu, IDLE = 0xFFFFFFFFu; // (= SPL_GENE_* of spl_genecount_rule.h)
 constexpr uint32_t SPECIALS = 3u;
 
+// Called by all 64 lanes.  The runs of equal values in lane order: -> whether this lane is a run's head; length: the lanes of the
+// run from this lane on (the whole run's for its head).  (spl_exoncount_wave.h counts its rounds of bins with it too.)
+WV_DEV bool wave_run(uint32_t value, uint32_t &length)
+{
+    const uint32_t lane = wv::lane();
+    const uint32_t before = wv::shfl_up(value, 1u); // (lane 0 gets its own back: it is a head whatever it holds)
+    const uint64_t heads = wv::ballot(lane == 0u || before != value);
+    const uint64_t above = lane < 63u ? heads >> (lane + 1u) : 0ull; // the heads behind this lane, the next one in bit 0
+    length = above ? wv::ffs64(above) + 1u : 64u - lane;
+    return ((heads >> lane) & 1ull) != 0ull;
+}
+
 // Called by all 64 lanes.  result: this lane's; counts: n_genes 64-bit words in device memory; mine: lane c's running sum of
 // special counter c (c < SPECIALS).  A gene result at or beyond n_genes is counted nowhere (there is none: said for the memory's sake).
 WV_DEV void wave_count(uint32_t result, uint32_t n_genes, uint64_t *counts, uint32_t &mine)
 {
     const uint32_t lane = wv::lane();
-    const uint32_t before = wv::shfl_up(result, 1u); // (lane 0 gets its own back: it is a head whatever it holds)
-    const uint64_t heads = wv::ballot(lane == 0u || before != result);
-    const uint64_t above = lane < 63u ? heads >> (lane + 1u) : 0ull; // the heads behind this lane, the next one in bit 0
-    const uint32_t length = above ? wv::ffs64(above) + 1u : 64u - lane;
-    if (((heads >> lane) & 1ull) && result < n_genes) wv::mem_add64(&counts[result], (uint64_t)length);
+    uint32_t length;
+    if (wave_run(result, length) && result < n_genes) wv::mem_add64(&counts[result], (uint64_t)length);
 #pragma unroll
     for (uint32_t c = 0; c < SPECIALS; ++c) {
         const uint64_t b = wv::ballot(result == NO_FEATURE + c);

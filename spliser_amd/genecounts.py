@@ -97,6 +97,22 @@ def read_features(path, aType="exon", idAttr="gene_id"):
     return Features(ids, list(rows), by_chrom)
 
 
+def merged_per_gene(left, right, gene):
+    """Each gene's features (all with ``right > left``, int64 arrays, at least one) merged: overlapping or abutting exons of one gene
+    are one interval.  -> (left, right, gene) of the merged intervals.  Sorted by (gene, left), a merged interval begins where left
+    exceeds every right before it in the gene -- the running maximum is kept per gene by lifting gene g's coordinates by g * big."""
+    order = np.lexsort((left, gene))
+    left, right, gene = left[order], right[order], gene[order]
+    low = min(int(left.min()), 0)
+    big = int(right.max()) - low + 1
+    reach = np.maximum.accumulate(gene * big + (right - low))
+    first = np.ones(left.shape[0], bool)
+    first[1:] = gene[1:] * big + (left[1:] - low) > reach[:-1]
+    begins = np.flatnonzero(first)
+    ends = np.concatenate((begins[1:], [left.shape[0]])) - 1
+    return left[begins], reach[ends] - gene[ends] * big + low, gene[begins]
+
+
 def gene_map(left, right, gene):
     """The gene map of one selection of features: -> (start int32, code uint32), ascending; code[k] holds for the 0-based positions
     start[k] <= p < start[k + 1] (the last to the end; 0 below start[0]): 0 no feature, g + 1 only gene g, ``MANY`` two genes or
@@ -109,18 +125,7 @@ def gene_map(left, right, gene):
         return np.zeros(0, np.int32), np.zeros(0, np.uint32)
     if int(right.max()) + 1 > COORD_MAX:
         raise native.SpliserNativeError(-6, "a gene ends beyond the int32 coordinate space")
-    # merge per gene: sorted by (gene, left), a merged interval begins where left exceeds every right before it in the gene -- the
-    # running maximum is kept per gene by lifting gene g's coordinates by g * big
-    order = np.lexsort((left, gene))
-    left, right, gene = left[order], right[order], gene[order]
-    low = min(int(left.min()), 0)
-    big = int(right.max()) - low + 1
-    reach = np.maximum.accumulate(gene * big + (right - low))
-    first = np.ones(left.shape[0], bool)
-    first[1:] = gene[1:] * big + (left[1:] - low) > reach[:-1]
-    begins = np.flatnonzero(first)
-    ends = np.concatenate((begins[1:], [left.shape[0]])) - 1
-    m_left, m_right, m_gene = left[begins], reach[ends] - gene[ends] * big + low, gene[begins]
+    m_left, m_right, m_gene = merged_per_gene(left, right, gene)
     at = np.concatenate((m_left, m_right))
     step = np.concatenate((np.ones(m_left.shape[0], np.int64), -np.ones(m_left.shape[0], np.int64)))
     points = np.unique(at)
@@ -155,28 +160,17 @@ def maps_of(features, chroms, stranded=False):
     return out
 
 
-def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None):
-    """``spl_gene_count`` over every chromosome of ``chroms`` -> int64[n_genes + 3], the sums: the genes' reads, then no feature,
-    ambiguous, not counted.  On the plan of ``strandedness.tally_of_source``: a file decoded on the device is counted per chromosome
-    where it lies (the sets stay fused); after a decode in shares every device counts its piece and the host adds -- counts add over
-    reads; host-decoded reads and the Python reader's go up as four arrays (``upload_soa``), a fused set of their own.  ``maps``:
-    {chrom: (map a, map b)} (``maps_of``); a chromosome without one has no feature.  ``per_chrom``: a dict that gets, per chromosome
-    with reads, int64[4]: counted, no feature, ambiguous, not counted."""
+def over_fused_sets(source, devices, chroms, visit):
+    """The plan both counting commands run a source by (``strandedness.tally_of_source``'s): ``visit(dr, chrom)`` for a finished, fused
+    read set per chromosome of ``chroms`` -- called from one thread per device, so it guards what it adds to.  A file decoded on the
+    device is visited per chromosome where it lies (the sets stay fused); after a decode in shares every device visits its piece of a
+    chromosome -- what the visits add must add over reads; host-decoded reads and the Python reader's go up as four arrays
+    (``upload_soa``), a fused set of their own.  The first exception of a visit is raised when all have ended."""
     import threading
     is_bam = isinstance(source, native.BamFile)
-    n_genes = int(n_genes)
-    total, errors, lock = np.zeros(n_genes + 3, np.int64), [], threading.Lock()
+    errors, lock = [], threading.Lock()
     on_device = is_bam and source.join_decoders()      # (however the device decode was started; False: the host threads have the file)
     shares = getattr(source, "shares", None) if on_device else None
-
-    def count(dr, chrom):
-        a, b = maps.get(chrom, (None, None))
-        t = dr.gene_counts(n_genes, a, b, stranded)
-        with lock:
-            total[:] += t
-            if per_chrom is not None:
-                row = per_chrom.setdefault(chrom, np.zeros(4, np.int64))
-                row += [int(t[:n_genes].sum()), int(t[n_genes]), int(t[n_genes + 1]), int(t[n_genes + 2])]
 
     def run(device, jobs):
         try:
@@ -190,12 +184,12 @@ def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chr
                             with ctx.begin_reads() as dr:
                                 dr.add_soa(soa, 0)
                                 dr.finish()
-                                count(dr, chrom)
+                                visit(dr, chrom)
                     else:
                         with ctx.begin_reads() as dr:
                             if add(dr):
                                 dr.finish()
-                                count(dr, chrom)
+                                visit(dr, chrom)
         except Exception as exc:
             with lock:
                 errors.append(exc)
@@ -216,6 +210,27 @@ def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chr
         w.join()
     if errors:
         raise errors[0]
+
+
+def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None):
+    """``spl_gene_count`` over every chromosome of ``chroms`` -> int64[n_genes + 3], the sums: the genes' reads, then no feature,
+    ambiguous, not counted.  On the plan of ``over_fused_sets``: counts add over reads, so the pieces of a decode in shares are counted
+    where they lie and the host adds.  ``maps``: {chrom: (map a, map b)} (``maps_of``); a chromosome without one has no feature.
+    ``per_chrom``: a dict that gets, per chromosome with reads, int64[4]: counted, no feature, ambiguous, not counted."""
+    import threading
+    n_genes = int(n_genes)
+    total, lock = np.zeros(n_genes + 3, np.int64), threading.Lock()
+
+    def count(dr, chrom):
+        a, b = maps.get(chrom, (None, None))
+        t = dr.gene_counts(n_genes, a, b, stranded)
+        with lock:
+            total[:] += t
+            if per_chrom is not None:
+                row = per_chrom.setdefault(chrom, np.zeros(4, np.int64))
+                row += [int(t[:n_genes].sum()), int(t[n_genes]), int(t[n_genes + 1]), int(t[n_genes + 2])]
+
+    over_fused_sets(source, devices, chroms, count)
     return total
 
 
