@@ -602,6 +602,51 @@ int spl_exon_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, ui
                              int64_t n_bins, const uint32_t *bin_gene, int64_t *verdict_out, int64_t *bins_out, int64_t cap,
                              int64_t *n_hits_out);
 
+/* ---- intron depth (what the pipeline otherwise needs IRFinder or iREAD and a sorted BAM for) ------------------------------------
+ * Replaces a second tool over the file this library has just decoded: how deeply every annotated intron is covered, beside the
+ * change in SSE at its donor.  The reference has no counterpart.  The rule (csrc/spl_intron_rule.h; the command builds the
+ * introns and their pieces: spliser_amd/intronretention.py):
+ *   features    genecounts': the lines of type -t, their gene the value of --idAttr; unstranded ONE selection of all features
+ *               with right > left, track '.'; stranded, selection a = the features whose strand is not '-', measured on the '+'
+ *               track, selection b = those whose strand is not '+', on the '-' track;
+ *   introns     per selection, chromosome and gene: the gene's features merged (overlapping or abutting ones are one interval);
+ *               every gap [s, e), 0-based and half-open, between two consecutive merged intervals is an intron (gene, s, e,
+ *               track); a gene of '.' features gives the same (gene, s, e) on both tracks, two rows;
+ *   pieces      the intron minus the union of ALL features of its selection, of any gene, clipped to [0, length): sorted,
+ *               disjoint [ps, pe); L = the sum of their lengths, which may be 0;
+ *   depth       spl_coverage's on the intron's track (eligibility, walk, -split gaps and clipping of csrc/spl_coverage_rule.h).
+ *               With D the ascending multiset of the depth at each of the L measurable bases and t = trim_percent (0..49):
+ *               lo = (L * t) / 100, hi = L - lo, depth_n = hi - lo, depth_sum = the sum of D[lo .. hi), covered = #{d > 0}:
+ *               int64, exact while depth_sum < 2^63, the same for the reads in any order; t = 0 is the plain sum;
+ *   splicing    from the junction table of the same set (spl_junctions with knobs 0, 0, 0 and the command's `stranded`; under a
+ *               stranded run only rows of the intron's track): an intron [s, e) is the junction left == s, right == e;
+ *               splice_left = the counts of the junctions with left == s, splice_right of those with right == e, splice_exact
+ *               of the one with both;
+ *   IR ratio    depth = depth_sum / depth_n; IRratio = depth / (depth + max(splice_left, splice_right)); NA where depth_n == 0
+ *               or the denominator is 0.
+ * This is IRFinder's published measure (a trimmed mean over max-side splicing) as this project restates it; IRFinder is not on
+ * the build machine: parity with it is intended and unpinned.
+ * spl_intron_depth: runs spl_coverage's stages on the device over a FUSED, finished read set taken as the reads of ONE reference
+ * of `length` bases, keeps their boundaries there, and takes the four numbers of every intron from them with one kernel
+ * (csrc/spl_intron.hip); only `out` comes down: 4 per intron, L, covered, depth_n, depth_sum.  Intron i has the pieces
+ * piece_off[i] .. piece_off[i + 1] of (piece_start, piece_end).  Pieces of different introns may overlap.  A set without a read:
+ * every intron is L, 0, depth_n, 0.  SPL_ERR_ARG (the context stays usable): spl_coverage's refusals; a null argument;
+ * trim_percent outside 0..49; piece_off not non-decreasing from 0; a piece with end <= start or outside [0, length]; pieces of
+ * ONE intron not strictly ascending and disjoint.  n_introns = 0 is valid.
+ * spl_intron_depth_runs: the same kernel and checks over a caller's boundaries, which are uploaded (test hook; no reads, no
+ * file): bound_pos strictly ascending (else SPL_ERR_ARG), bound_depth[k] holds from bound_pos[k] to bound_pos[k + 1], the last to
+ * the end, 0 before the first; n_bound = 0 is valid.
+ * spl_intron_depth_host: the rule for ONE intron on the host by another method -- (depth, bases) pairs collected, sorted and
+ * walked (test hook; no GPU): out4 = L, covered, depth_n, depth_sum. */
+int spl_intron_depth(spl_ctx *ctx, const spl_dreads *dr, int64_t length, int stranded, int strand /* 0, '+', '-' */, int64_t n_introns,
+                     const int64_t *piece_off /* n_introns + 1 */, const int32_t *piece_start, const int32_t *piece_end, int trim_percent,
+                     int64_t *out /* 4 per intron */);
+int spl_intron_depth_runs(spl_ctx *ctx, int64_t n_bound, const int32_t *bound_pos, const uint32_t *bound_depth, int64_t length,
+                          int64_t n_introns, const int64_t *piece_off, const int32_t *piece_start, const int32_t *piece_end,
+                          int trim_percent, int64_t *out);
+int spl_intron_depth_host(int64_t n_bound, const int32_t *bound_pos, const uint32_t *bound_depth, int64_t n_pieces,
+                          const int32_t *piece_start, const int32_t *piece_end, int trim_percent, int64_t *out4);
+
 /* ---- the fused counting kernel's rule for simple reads, on the host (test hook; no file, no GPU) ---------------------------
  * A simple read (one aligned op) with bases [a, b), a = pos + shift, b = a + len, counts for the sites t with t and t + 1 both under it: the
  * distinct positions [lo, ub), lo = number of site positions <= a - 1, ub = number of site positions < b - 1.  The kernel asks one

@@ -36,6 +36,9 @@ Extra sub-command ``exoncounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAt
 ``PREFIX.exonbins.tsv`` and ``PREFIX.exoncounts.tsv``: reads per exon counting bin, counted on the GPU from the decode by DEXSeq's rule
 (``featureCounts -f -O`` restricted to reads of one gene) per read -- what ``edgeR::diffSpliceDGE`` needs, without a second pass over
 the BAM by another program (``exoncounts.py``).
+Extra sub-command ``intronretention -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [--trimPercent 30] [-c CHROM] [--isStranded
+-s fr|rf]`` writes ``PREFIX.introns.tsv``: per annotated intron the trimmed depth of its measurable bases, the splice counts at its ends and
+the IR ratio, taken on the GPU from the decode -- IRFinder's measure, without a sorted BAM and a second tool (``intronretention.py``).
 Not read: CRAM, a pipe, and compressed text that has no ``@`` header line (uncompressed, the Python reader still takes that).
 """
 import argparse
@@ -223,6 +226,26 @@ def build_parser():
     x.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     _filter_flags(x)
     _engine_flags(x)
+    i = sub.add_parser("intronretention", help="(this build only) per annotated intron the trimmed depth, the splice counts and the IR ratio, taken on the GPU from the "
+                                               "decode (IRFinder's measure): no sorted BAM, no second pass over the file by another program")
+    i.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    i.add_argument("-A", "--annotationFile", dest="annotationFile", required=False, default=None, help="gff3 or gtf file matching the reference genome used for alignment (required)")
+    i.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="output prefix: .introns.tsv is appended")
+    i.add_argument("-t", "--annotationType", dest="aType", nargs="?", default="exon", type=str, required=False,
+                   help="the feature type (column 3) whose lines are a gene's features - default: exon")
+    i.add_argument("--idAttr", dest="idAttr", default="gene_id", type=str, required=False, help="the attribute (column 9) that names a feature's gene - default: gene_id")
+    i.add_argument("--trimPercent", dest="trimPercent", default=30, type=int, required=False,
+                   help="percent of an intron's measurable bases left out at either end of their sorted depths, 0..49 (0: the plain mean) - default: 30")
+    i.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False,
+                   help="optional: the introns of one chromosome only (under the ids they have in the whole annotation)")
+    i.add_argument("--isStranded", dest="isStranded", default=False, action="store_true", help="an intron is measured on the track of its strand (check_strand's rule)")
+    i.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
+                   help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
+    i.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
+    i.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    i.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _filter_flags(i)
+    _engine_flags(i)
     return parser
 
 
@@ -274,25 +297,27 @@ def main(argv=None):
         print(kwargs.get("qGene"))
         print(kwargs.get("annotationFile"))
         parser.error("--gene requires --annotationFile and --maxIntronSize")
-    elif command in ("process", "combine", "combineShallow", "junctions", "coverage", "genecounts", "exoncounts") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
+    elif command in ("process", "combine", "combineShallow", "junctions", "coverage", "genecounts", "exoncounts", "intronretention") and kwargs.get("isStranded") is True and kwargs.get("strandedType") is None:
         parser.error("--isStranded requires parameter --strandedType/-s as fr or rf")
     if command == "coverage" and kwargs.get("strandedType") == "auto":
         parser.error("coverage: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
     if command == "coverage" and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
         parser.error("coverage: --strandedType/-s must be fr or rf")
-    if command in ("genecounts", "exoncounts") and kwargs.get("annotationFile") is None:
+    if command in ("genecounts", "exoncounts", "intronretention") and kwargs.get("annotationFile") is None:
         parser.error("%s: --annotationFile/-A is required: the genes are its features" % command)
-    if command in ("genecounts", "exoncounts") and kwargs.get("strandedType") == "auto":
+    if command in ("genecounts", "exoncounts", "intronretention") and kwargs.get("strandedType") == "auto":
         parser.error("%s: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf" % command)
-    if command in ("genecounts", "exoncounts") and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
+    if command in ("genecounts", "exoncounts", "intronretention") and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
         parser.error("%s: --strandedType/-s must be fr or rf" % command)
+    if command == "intronretention" and not 0 <= kwargs["trimPercent"] <= 49:
+        parser.error("intronretention: --trimPercent must be in 0..49")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":
         parser.error("-s auto and --strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
     if command in ("process", "junctions", "strandedness") and kwargs.get("minEvidence") is not None and kwargs["minEvidence"] < 0:
         parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts", "exoncounts"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts", "exoncounts", "intronretention"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -344,6 +369,9 @@ def main(argv=None):
     elif command == "exoncounts":
         from .exoncounts import exoncounts
         exoncounts(devices=devices, threads=threads, **kwargs)
+    elif command == "intronretention":
+        from .intronretention import intronretention
+        intronretention(devices=devices, threads=threads, **kwargs)
     elif command == "flagstat":
         from .flagstat import flagstat
         flagstat(devices=devices, threads=threads, **kwargs)

@@ -29,11 +29,11 @@ def tracks_of(stranded):
     return [(SUFFIX_PLUS, "+"), (SUFFIX_MINUS, "-")] if stranded else [(SUFFIX, 0)]
 
 
-def runs_of_source(source, device, chroms, stranded=0):
-    """``spl_coverage`` over every chromosome of ``chroms`` in turn, every track of it: yields (chrom, length, [(start, end, depth,
-    totals) per track]).  On the plan of ``strandedness.tally_of_source``, one device: a file decoded on the device is covered per
-    chromosome where it lies (one fused set a chromosome, shift 0); host-decoded reads and the Python reader's go up as four
-    arrays, a fused set of their own.  ``length``: the header's LN; a source without lengths uses the reads' ``max_end``."""
+def sets_of_source(source, device, chroms):
+    """A finished, fused read set per chromosome of ``chroms`` that has a read, each in turn: yields (chrom, length, dr).  On the
+    plan of ``strandedness.tally_of_source``, one device: a file decoded on the device is visited per chromosome where it lies (one
+    fused set a chromosome, shift 0); host-decoded reads and the Python reader's go up as four arrays, a fused set of their own.
+    ``length``: the header's LN; a source without lengths uses the reads' ``max_end``."""
     is_bam = isinstance(source, native.BamFile)
     on_device = is_bam and source.join_decoders()      # (False: the host threads have the file)
     lengths = dict(zip(source.ref_names, source.ref_lengths)) if getattr(source, "ref_lengths", None) else {}
@@ -45,7 +45,7 @@ def runs_of_source(source, device, chroms, stranded=0):
                     if not dr.add_bam(source, chrom):
                         continue
                     dr.finish()
-                    yield chrom, length, [dr.coverage(length, stranded, strand) for _, strand in tracks_of(stranded)]
+                    yield chrom, length, dr
                 continue
             rs = source.reads(chrom)
             if rs is None or not rs.n:
@@ -58,7 +58,14 @@ def runs_of_source(source, device, chroms, stranded=0):
                 with ctx.begin_reads() as dr:
                     dr.add_soa(soa, 0)
                     dr.finish()
-                    yield chrom, length, [dr.coverage(length, stranded, strand) for _, strand in tracks_of(stranded)]
+                    yield chrom, length, dr
+
+
+def runs_of_source(source, device, chroms, stranded=0):
+    """``spl_coverage`` over every chromosome of ``chroms`` in turn (``sets_of_source``), every track of it: yields (chrom, length,
+    [(start, end, depth, totals) per track])."""
+    for chrom, length, dr in sets_of_source(source, device, chroms):
+        yield chrom, length, [dr.coverage(length, stranded, strand) for _, strand in tracks_of(stranded)]
 
 
 def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=None, perMillion=False, devices=(0,), threads=0, log=None, gpuDecode=None,

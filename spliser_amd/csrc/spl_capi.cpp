@@ -43,6 +43,8 @@
 #include "spl_genecount_rule.h"
 #include "spl_exoncount.h"
 #include "spl_exoncount_rule.h"
+#include "spl_intron.h"
+#include "spl_intron_rule.h"
 #include "spl_simple_span.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
@@ -4166,29 +4168,35 @@ struct spl_cov {
     int64_t totals[5] = {0, 0, 0, 0, 0}; // runs, reads seen, reads that contributed, reads past the end, covered bases
 };
 
-// mark per segment into one zeroed difference array, compact (count, scan, emit), scan of the deltas; the boundaries come down and
-// those with a depth of zero are dropped here.
-extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, spl_cov **out)
+namespace {
+// What the coverage stages leave on the device: n_bound boundaries, ascending in pos; delta holds the depth from each to the next
+// (0 before the first); out: the mark kernel's four sums.
+struct CovStages {
+    DevBuf diff, out, tiles, work, pos, delta;
+    uint32_t n_bound = 0;
+};
+
+// 0, or the refusal of a call that covers a read set (`who`: its name).
+int cov_refusal(const char *who, const spl_dreads *dr, int64_t length, int stranded, int strand)
 {
-    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_coverage: null argument");
-    *out = nullptr;
-    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_coverage: the read set is not finished (spl_reads_finish)");
-    if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_coverage: length must be in 1 .. 2^31 - 2, not %lld", (long long)length);
-    if (stranded < 0 || stranded > 2) return spl_set_error(SPL_ERR_ARG, "spl_coverage: stranded must be 0 (one track), 1 (fr) or 2 (rf)");
-    if (!spl_cov_args_fit(stranded, strand))
-        return spl_set_error(SPL_ERR_ARG, "spl_coverage: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2");
-    std::unique_ptr<spl_cov> cov(new spl_cov());
-    if (dr->segs.empty()) { // (a set without a read has no arrays to be fused of, and covers nothing)
-        *out = cov.release();
-        return SPL_OK;
-    }
-    if (!(dr->fused && dr->groups.size() == 1))
-        return spl_set_error(SPL_ERR_ARG, "spl_coverage needs a fused read set (all of it from one device decode or one spl_soa_upload)");
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "%s: the read set is not finished (spl_reads_finish)", who);
+    if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "%s: length must be in 1 .. 2^31 - 2, not %lld", who, (long long)length);
+    if (stranded < 0 || stranded > 2) return spl_set_error(SPL_ERR_ARG, "%s: stranded must be 0 (one track), 1 (fr) or 2 (rf)", who);
+    if (!spl_cov_args_fit(stranded, strand)) return spl_set_error(SPL_ERR_ARG, "%s: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2", who);
+    if (!dr->segs.empty() && !(dr->fused && dr->groups.size() == 1))
+        return spl_set_error(SPL_ERR_ARG, "%s needs a fused read set (all of it from one device decode or one spl_soa_upload)", who);
+    return SPL_OK;
+}
+
+// The three stages over a fused set with a read: mark per segment into one zeroed difference array, compact (count, scan, emit),
+// scan of the deltas.  The stream has been waited for once (the buffers are sized from the count); the scan may still run.
+int cov_stages(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, CovStages &s)
+{
+    DevBuf &d_diff = s.diff, &d_out = s.out, &d_tiles = s.tiles, &d_work = s.work, &d_pos = s.pos, &d_delta = s.delta;
     const spl_dreads::Group &g = dr->groups[0];
     HIP_TRY(hipSetDevice(c->device));
     const int64_t n_tiles = (length + SPL_COV_POS_TILE - 1) / SPL_COV_POS_TILE;
     const size_t diff_bytes = 4 * (size_t)spl_dev_cov_diff_words(length);
-    DevBuf d_diff, d_out, d_tiles, d_work, d_pos, d_delta;
     HIP_TRY(d_diff.get(diff_bytes, c->stream));
     HIP_TRY(d_out.get(8 * (SPL_COV_COUNTERS + 1), c->stream));
     HIP_TRY(d_tiles.get(4 * (size_t)n_tiles, c->stream));
@@ -4223,14 +4231,34 @@ extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, in
             if (rc) return spl_set_error(SPL_ERR_HIP, "coverage emit kernel launch: %s", hipGetErrorString((hipError_t)rc));
         }
     }
+    if (n_bound) {
+        splprof::Scope prof("spl_cov_scan", c->stream, 2.0 * 4.0 * (double)n_bound);
+        if (spl_dev_sort_work_bytes(n_bound) > spl_dev_sort_work_bytes((uint64_t)n_tiles)) { d_work.release(); HIP_TRY(d_work.get(spl_dev_sort_work_bytes(n_bound), c->stream)); }
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_delta.as<uint32_t>(), n_bound, d_work.p, c->stream)); // delta -> the depth behind each boundary
+    }
+    s.n_bound = n_bound;
+    return SPL_OK;
+}
+} // namespace
+
+// The stages (cov_stages); the boundaries come down and those with a depth of zero are dropped here.
+extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, spl_cov **out)
+{
+    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_coverage: null argument");
+    *out = nullptr;
+    if (const int rc = cov_refusal("spl_coverage", dr, length, stranded, strand)) return rc;
+    std::unique_ptr<spl_cov> cov(new spl_cov());
+    if (dr->segs.empty()) { // (a set without a read has no arrays to be fused of, and covers nothing)
+        *out = cov.release();
+        return SPL_OK;
+    }
+    CovStages st;
+    if (const int rc = cov_stages(c, dr, length, stranded, strand, st)) return rc;
+    const uint32_t n_bound = st.n_bound;
+    DevBuf &d_out = st.out, &d_pos = st.pos, &d_delta = st.delta;
     std::vector<int32_t> h_pos(n_bound);
     std::vector<uint32_t> h_depth(n_bound);
     if (n_bound) {
-        {
-            splprof::Scope prof("spl_cov_scan", c->stream, 2.0 * 4.0 * (double)n_bound);
-            if (spl_dev_sort_work_bytes(n_bound) > spl_dev_sort_work_bytes((uint64_t)n_tiles)) { d_work.release(); HIP_TRY(d_work.get(spl_dev_sort_work_bytes(n_bound), c->stream)); }
-            HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_delta.as<uint32_t>(), n_bound, d_work.p, c->stream)); // delta -> the depth behind each boundary
-        }
         HIP_TRY(hipMemcpyAsync(h_pos.data(), d_pos.p, 4 * (size_t)n_bound, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(h_depth.data(), d_delta.p, 4 * (size_t)n_bound, hipMemcpyDeviceToHost, c->stream));
     }
@@ -4290,6 +4318,131 @@ extern "C" int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t
     }
     *n_out = keep.n;
     if (past_end_out) *past_end_out = (bits & SPL_COV_PAST_END) ? 1 : 0;
+    return SPL_OK;
+}
+
+// ---- intron depth (spl_intron.hip; the rule is spl_intron_rule.h) ---------------------------------------------------------------
+namespace {
+// 0, or SPL_ERR_ARG with the message set: the introns' pieces as spl_intron_depth and spl_intron_depth_runs take them.
+int intron_args_fit(const char *who, int64_t length, int64_t n_introns, const int64_t *piece_off, const int32_t *piece_start, const int32_t *piece_end, int trim_percent,
+                    const int64_t *out)
+{
+    if (n_introns < 0 || !piece_off || (n_introns && !out)) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
+    if (n_introns > 0xfffffff0ll) return spl_set_error(SPL_ERR_ARG, "%s: more than 2^32 introns", who);
+    if (trim_percent < 0 || trim_percent > SPL_INTRON_TRIM_MAX) return spl_set_error(SPL_ERR_ARG, "%s: trim_percent must be in 0 .. %d, not %d", who, SPL_INTRON_TRIM_MAX, trim_percent);
+    if (piece_off[0] != 0) return spl_set_error(SPL_ERR_ARG, "%s: piece_off does not begin at 0", who);
+    for (int64_t i = 0; i < n_introns; ++i)
+        if (piece_off[i + 1] < piece_off[i]) return spl_set_error(SPL_ERR_ARG, "%s: piece_off decreases at intron %lld", who, (long long)i);
+    if (piece_off[n_introns] && (!piece_start || !piece_end)) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
+    for (int64_t i = 0; i < n_introns; ++i) {
+        int why = 0;
+        const int64_t k = spl_intron_piece_flaw(piece_start, piece_end, piece_off[i], piece_off[i + 1], length, &why);
+        if (k < 0) continue;
+        if (why == 0) return spl_set_error(SPL_ERR_ARG, "%s: piece %lld (intron %lld) ends at or before its start", who, (long long)k, (long long)i);
+        if (why == 1) return spl_set_error(SPL_ERR_ARG, "%s: piece %lld (intron %lld) is outside [0, %lld]", who, (long long)k, (long long)i, (long long)length);
+        return spl_set_error(SPL_ERR_ARG, "%s: the pieces of intron %lld are not strictly ascending and disjoint at piece %lld", who, (long long)i, (long long)k);
+    }
+    return SPL_OK;
+}
+
+// The kernel over boundaries that are on the device (checked or made there), the pieces going up and `out` coming down: the long
+// introns by a team each, then the others by a wave each.
+int intron_launch(spl_ctx *c, const int32_t *d_pos, const uint32_t *d_depth, int64_t n_bound, int64_t n_introns, const int64_t *piece_off, const int32_t *piece_start,
+                  const int32_t *piece_end, int trim_percent, int64_t *out)
+{
+    if (n_introns == 0) return SPL_OK;
+    const int64_t n_pieces = piece_off[n_introns];
+    std::vector<uint32_t> items((size_t)n_introns); // the long introns first, then the others
+    int64_t n_long = 0;
+    {
+        std::vector<uint32_t> rest;
+        rest.reserve((size_t)n_introns);
+        for (int64_t i = 0; i < n_introns; ++i) {
+            int64_t bases = 0;
+            for (int64_t k = piece_off[i]; k < piece_off[i + 1]; ++k) bases += (int64_t)piece_end[k] - (int64_t)piece_start[k];
+            if (bases >= SPL_INTRON_LONG_BASES) items[(size_t)n_long++] = (uint32_t)i;
+            else rest.push_back((uint32_t)i);
+        }
+        std::copy(rest.begin(), rest.end(), items.begin() + n_long);
+    }
+    DevBuf d_off, d_start, d_end, d_items, d_out;
+    HIP_TRY(d_off.get(8 * (size_t)(n_introns + 1), c->stream));
+    HIP_TRY(d_start.get(4 * (size_t)n_pieces, c->stream));
+    HIP_TRY(d_end.get(4 * (size_t)n_pieces, c->stream));
+    HIP_TRY(d_items.get(4 * (size_t)n_introns, c->stream));
+    HIP_TRY(d_out.get(8 * (size_t)SPL_INTRON_OUT * (size_t)n_introns, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_off.p, piece_off, 8 * (size_t)(n_introns + 1), hipMemcpyHostToDevice, c->stream));
+    if (n_pieces) {
+        HIP_TRY(hipMemcpyAsync(d_start.p, piece_start, 4 * (size_t)n_pieces, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_end.p, piece_end, 4 * (size_t)n_pieces, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(d_items.p, items.data(), 4 * (size_t)n_introns, hipMemcpyHostToDevice, c->stream));
+    {
+        // what the kernel must move at least: an intron's offset, item and results, a piece's ends, and every boundary once
+        splprof::Scope prof("spl_intron_kernel", c->stream, 44.0 * (double)n_introns + 8.0 * (double)n_pieces + 8.0 * (double)n_bound);
+        int rc = spl_dev_launch_intron(SPL_INTRON_TEAM, d_pos, d_depth, n_bound, d_off.as<int64_t>(), d_start.as<int32_t>(), d_end.as<int32_t>(), d_items.as<uint32_t>(), n_long, trim_percent,
+                                       d_out.as<int64_t>(), c->stream);
+        if (!rc)
+            rc = spl_dev_launch_intron(64, d_pos, d_depth, n_bound, d_off.as<int64_t>(), d_start.as<int32_t>(), d_end.as<int32_t>(), d_items.as<uint32_t>() + n_long, n_introns - n_long,
+                                       trim_percent, d_out.as<int64_t>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "intron depth kernel launch: %s", hipGetErrorString((hipError_t)rc));
+    }
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, 8 * (size_t)SPL_INTRON_OUT * (size_t)n_introns, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPL_OK;
+}
+} // namespace
+
+extern "C" int spl_intron_depth(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, int64_t n_introns, const int64_t *piece_off, const int32_t *piece_start,
+                                const int32_t *piece_end, int trim_percent, int64_t *out)
+{
+    if (!c || !dr) return spl_set_error(SPL_ERR_ARG, "spl_intron_depth: null argument");
+    if (const int rc = cov_refusal("spl_intron_depth", dr, length, stranded, strand)) return rc;
+    if (const int rc = intron_args_fit("spl_intron_depth", length, n_introns, piece_off, piece_start, piece_end, trim_percent, out)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    CovStages st; // (a set without a read has no arrays to be fused of: no boundary, a depth of 0 everywhere)
+    if (!dr->segs.empty())
+        if (const int rc = cov_stages(c, dr, length, stranded, strand, st)) return rc;
+    return intron_launch(c, st.pos.as<int32_t>(), st.delta.as<uint32_t>(), (int64_t)st.n_bound, n_introns, piece_off, piece_start, piece_end, trim_percent, out);
+}
+
+// The same kernel over a caller's boundaries (test hook): checked here, uploaded, no reads and no file.
+extern "C" int spl_intron_depth_runs(spl_ctx *c, int64_t n_bound, const int32_t *bound_pos, const uint32_t *bound_depth, int64_t length, int64_t n_introns, const int64_t *piece_off,
+                                     const int32_t *piece_start, const int32_t *piece_end, int trim_percent, int64_t *out)
+{
+    if (!c || n_bound < 0 || (n_bound && (!bound_pos || !bound_depth))) return spl_set_error(SPL_ERR_ARG, "spl_intron_depth_runs: null argument");
+    if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_intron_depth_runs: length must be in 1 .. 2^31 - 2, not %lld", (long long)length);
+    if (const int rc = intron_args_fit("spl_intron_depth_runs", length, n_introns, piece_off, piece_start, piece_end, trim_percent, out)) return rc;
+    if (const int64_t k = spl_intron_bound_flaw(n_bound, bound_pos); k >= 0)
+        return spl_set_error(SPL_ERR_ARG, "spl_intron_depth_runs: the boundaries are not strictly ascending at entry %lld", (long long)k);
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf d_pos, d_depth;
+    if (n_bound) {
+        HIP_TRY(d_pos.get(4 * (size_t)n_bound, c->stream));
+        HIP_TRY(d_depth.get(4 * (size_t)n_bound, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_pos.p, bound_pos, 4 * (size_t)n_bound, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_depth.p, bound_depth, 4 * (size_t)n_bound, hipMemcpyHostToDevice, c->stream));
+    }
+    return intron_launch(c, d_pos.as<int32_t>(), d_depth.as<uint32_t>(), n_bound, n_introns, piece_off, piece_start, piece_end, trim_percent, out);
+}
+
+// The rule itself for one intron on the host, by sorting (test hook; no GPU involved).
+extern "C" int spl_intron_depth_host(int64_t n_bound, const int32_t *bound_pos, const uint32_t *bound_depth, int64_t n_pieces, const int32_t *piece_start, const int32_t *piece_end,
+                                     int trim_percent, int64_t *out4)
+{
+    if (!out4 || n_bound < 0 || (n_bound && (!bound_pos || !bound_depth)) || n_pieces < 0 || (n_pieces && (!piece_start || !piece_end)))
+        return spl_set_error(SPL_ERR_ARG, "spl_intron_depth_host: null argument");
+    if (trim_percent < 0 || trim_percent > SPL_INTRON_TRIM_MAX)
+        return spl_set_error(SPL_ERR_ARG, "spl_intron_depth_host: trim_percent must be in 0 .. %d, not %d", SPL_INTRON_TRIM_MAX, trim_percent);
+    int why = 0;
+    if (const int64_t k = spl_intron_piece_flaw(piece_start, piece_end, 0, n_pieces, SPL_COV_LENGTH_MAX, &why); k >= 0)
+        return spl_set_error(SPL_ERR_ARG, why == 0   ? "spl_intron_depth_host: piece %lld ends at or before its start"
+                                          : why == 1 ? "spl_intron_depth_host: piece %lld is outside [0, 2^31 - 2]"
+                                                     : "spl_intron_depth_host: the pieces are not strictly ascending and disjoint at piece %lld",
+                             (long long)k);
+    if (const int64_t k = spl_intron_bound_flaw(n_bound, bound_pos); k >= 0)
+        return spl_set_error(SPL_ERR_ARG, "spl_intron_depth_host: the boundaries are not strictly ascending at entry %lld", (long long)k);
+    spl_intron_depth_of(n_bound, bound_pos, bound_depth, n_pieces, piece_start, piece_end, trim_percent, out4);
     return SPL_OK;
 }
 

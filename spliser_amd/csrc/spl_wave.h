@@ -29,6 +29,7 @@ WV_DEV void sync() { __syncthreads(); }
 WV_DEV uint32_t lds_max(uint32_t *p, uint32_t v) { return atomicMax(p, v); }
 WV_DEV uint32_t lds_or(uint32_t *p, uint32_t v) { return atomicOr(p, v); }
 WV_DEV uint32_t lds_add(uint32_t *p, uint32_t v) { return atomicAdd(p, v); }
+WV_DEV void lds_add64(uint64_t *p, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
 // a 64-bit sum in device memory whose value nobody waits for
 WV_DEV void mem_add64(uint64_t *p, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
 WV_DEV uint32_t popc64(uint64_t m) { return (uint32_t)__popcll(m); }

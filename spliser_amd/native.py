@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -534,6 +534,20 @@ class DeviceReads(object):
         _check(lib().spl_exon_count(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]), _ptr(a_start) if a_start.shape[0] else None,
                                     _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
                                     _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_bins), _ptr(bin_gene) if n_bins else None, _ptr(out)))
+        return out
+
+    def intron_depth(self, length, piece_off, piece_start, piece_end, trim_percent=30, stranded=0, strand=0):
+        """The trimmed depth of introns over this (finished, fused) set, taken as the reads of one reference of ``length`` bases, on
+        the device (``spl_intron_depth``): -> int64[n_introns, 4] -- measurable bases L, covered bases, depth_n, depth_sum.  Intron i
+        has the pieces ``piece_off[i] .. piece_off[i + 1]`` of ``(piece_start, piece_end)``, 0-based and half-open, disjoint and
+        ascending within an intron; ``stranded`` / ``strand``: the track, as for ``coverage``."""
+        strand = ord(strand) if isinstance(strand, (str, bytes)) else int(strand)
+        off, start, end = _arr(piece_off, np.int64), _arr(piece_start, np.int32), _arr(piece_end, np.int32)
+        n = max(int(off.shape[0]) - 1, 0)
+        out = np.zeros((n, 4), np.int64)
+        _check(lib().spl_intron_depth(self.ctx._h, self._h, ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.c_int64(n),
+                                      _ptr(off) if off.shape[0] else None, _ptr(start) if start.shape[0] else None, _ptr(end) if end.shape[0] else None,
+                                      ctypes.c_int(int(trim_percent)), _ptr(out) if n else None))
         return out
 
     def free(self):
@@ -1166,6 +1180,33 @@ def exon_count_rule_host(flag, pos, ops, bin_gene, map_a, map_b=None, stranded=0
                                           _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(bin_gene.shape[0]), _ptr(bin_gene) if bin_gene.shape[0] else None,
                                           ctypes.byref(verdict), _ptr(bins), ctypes.c_int64(int(cap)), ctypes.byref(n_hits)))
     return verdict.value, bins[:min(int(cap), n_hits.value)].tolist(), n_hits.value
+
+
+INTRON_LONG_BASES = 16384   # csrc/spl_intron.h's SPL_INTRON_LONG_BASES: an intron of this many measurable bases or more has a team of its own
+
+
+def intron_depth_runs(ctx, bound_pos, bound_depth, length, piece_off, piece_start, piece_end, trim_percent=30):
+    """``spl_intron_depth``'s kernel over a caller's boundaries (``spl_intron_depth_runs``: test hook) -> int64[n_introns, 4].
+    ``bound_pos`` strictly ascending; ``bound_depth[k]`` holds from ``bound_pos[k]`` to the next one, 0 before the first."""
+    pos, depth = _arr(bound_pos, np.int32), _arr(bound_depth, np.uint32)
+    off, start, end = _arr(piece_off, np.int64), _arr(piece_start, np.int32), _arr(piece_end, np.int32)
+    n = max(int(off.shape[0]) - 1, 0)
+    out = np.zeros((n, 4), np.int64)
+    _check(lib().spl_intron_depth_runs(ctx._h, ctypes.c_int64(pos.shape[0]), _ptr(pos) if pos.shape[0] else None, _ptr(depth) if depth.shape[0] else None,
+                                       ctypes.c_int64(int(length)), ctypes.c_int64(n), _ptr(off) if off.shape[0] else None, _ptr(start) if start.shape[0] else None,
+                                       _ptr(end) if end.shape[0] else None, ctypes.c_int(int(trim_percent)), _ptr(out) if n else None))
+    return out
+
+
+def intron_depth_host(bound_pos, bound_depth, piece_start, piece_end, trim_percent=30):
+    """The intron rule for ONE intron on the host, by sorting (``spl_intron_depth_host``: test hook, no GPU) -> [L, covered, depth_n,
+    depth_sum]."""
+    pos, depth = _arr(bound_pos, np.int32), _arr(bound_depth, np.uint32)
+    start, end = _arr(piece_start, np.int32), _arr(piece_end, np.int32)
+    out = np.zeros(4, np.int64)
+    _check(lib().spl_intron_depth_host(ctypes.c_int64(pos.shape[0]), _ptr(pos) if pos.shape[0] else None, _ptr(depth) if depth.shape[0] else None, ctypes.c_int64(start.shape[0]),
+                                       _ptr(start) if start.shape[0] else None, _ptr(end) if end.shape[0] else None, ctypes.c_int(int(trim_percent)), _ptr(out)))
+    return out.tolist()
 
 
 COVERAGE_TOTALS = ("runs", "reads_seen", "contributed", "past_end", "covered_bases")
