@@ -195,12 +195,19 @@ int spl_soa_upload2(spl_ctx *ctx, int n_seg, const spl_reads *segs, const int64_
 /* ... and with xs[k] = a strand byte per read of segment k ('+', '-', 0 = none): a fifth device array beside flag, which
  * spl_junctions reads with stranded = 3.  How reads the host decoded (spl_bam_aux_strand) and SAM text get there. */
 int spl_soa_upload3(spl_ctx *ctx, int n_seg, const spl_reads *segs, const int64_t *max_end, const uint8_t *const *xs, spl_dsoa **out);
+/* ... and with name_key[k] = a name key per read of segment k (0 = no name; the key: "mates and fragments" below): a further
+ * device array beside flag, which spl_mate_table and spl_gene_count_fragments read.  xs may be null: no strand bytes. */
+int spl_soa_upload4(spl_ctx *ctx, int n_seg, const spl_reads *segs, const int64_t *max_end, const uint8_t *const *xs, const uint64_t *const *name_key,
+                    spl_dsoa **out);
 void spl_soa_free(spl_ctx *ctx, spl_dsoa *soa);
 int spl_reads_add_soa(spl_ctx *ctx, spl_dreads *dr, spl_dsoa *soa, int seg, int32_t pos_shift);
 int spl_reads_relayout(spl_ctx *ctx, spl_dreads *dr);
 /* *out = 1 when the set is fused and its arrays have the fifth one, the reads' strand bytes (a decode after
  * spl_bam_set_aux_strand, spl_soa_upload3): what spl_junctions' stranded = 3 needs.  0 otherwise. */
 int spl_reads_has_strand(const spl_dreads *dr, int *out);
+/* *out = 1 when the set is fused and its arrays have the reads' name keys (a decode after spl_bam_set_mate_keys, spl_soa_upload4):
+ * what spl_mate_table needs.  0 otherwise. */
+int spl_reads_has_mate_keys(const spl_dreads *dr, int *out);
 /* What the layout moves for a finished read set: the BAM-native arrays read (10 bytes a read + 4 an op) and the records written
  * (0 while the set is fused). */
 int spl_reads_layout_bytes(spl_ctx *ctx, const spl_dreads *dr, int64_t *soa_bytes_out, int64_t *record_bytes_out);
@@ -285,6 +292,16 @@ int spl_bam_filter_counts(spl_bam *bam, int64_t *out2);
  * *out = NULL when the file was decoded without them.  struct spl_reads is unchanged.  spl_bam_aux_strand_host: the walk itself
  * over a caller's bytes [aux, aux + len) -> *out (test hook; no file, no GPU). */
 int spl_bam_set_aux_strand(spl_bam *bam, int on);
+/* Which two records are mates (what fragment counting needs: "mates and fragments" below).  spl_bam_set_mate_keys(bam, 1): the
+ * decode -- the device's and the host's, of BAM and of SAM text alike -- leaves one more array per placed read, in file order
+ * beside its FLAG and carried through the sort of spl_bam_set_any_order: the 64-bit key of its name (BAM: the l_read_name - 1
+ * bytes 36 bytes into the record, walked no further than the record's end; SAM: column 1), 0 for an empty name and for `*`.  The
+ * same rule as spl_bam_set_filter: before anybody decodes the file or waits for it, SPL_ERR_ARG afterwards.  Without the switch
+ * the decode is what it was: the kernels that hash names are instantiations of their own.  spl_bam_mate_keys: borrowed view (until
+ * spl_bam_close) of the keys of the reads spl_bam_reads hands out for `tid`, same order; *out = NULL when the file was decoded
+ * without them.  spl_reads_add_bam picks the keys up where they are on the device; host arrays bring theirs with spl_soa_upload4. */
+int spl_bam_set_mate_keys(spl_bam *bam, int on);
+int spl_bam_mate_keys(const spl_bam *bam, int tid, const uint64_t **out);
 /* Library size without a second pass over the file (the reference's README sends the user to `samtools flagstat` for the
  * Library_size column of the diffSpliSER target file; the reference has no counterpart).  spl_bam_set_flagstat(bam, 1): the
  * decode -- the device's and the host's alike, whole or in shares -- also counts samtools flagstat's sixteen categories, each for
@@ -547,7 +564,8 @@ int spl_bedgraph_append(const char *path, const char *chrom, int64_t n, const in
  *               gaps, covering ops that abut are one block; nothing is clipped to a length;
  *   gene set    the union, over every stretch of the read's map that a block overlaps by a base or more, of the stretch's code:
  *               empty = "no feature", exactly one gene = one more read of that gene, anything else = "ambiguous" (htseq-count
- *               --mode union --nonunique none and featureCounts' default, per READ: a paired fragment adds up to two).
+ *               --mode union --nonunique none and featureCounts' default, per READ: a paired fragment adds up to two;
+ *               spl_gene_count_fragments, below, counts a fragment once).
  * inout[0 .. n_genes) += the genes' reads, inout[n_genes] += no feature, [n_genes + 1] += ambiguous, [n_genes + 2] += not counted:
  * what is ADDED sums to the reads of the set.  The call synchronises; integer sums, exact and the same for the reads in any order
  * (one atomic per run of equal results in a wave: a gene that takes every read is no slower).  Parity with htseq-count /
@@ -561,6 +579,48 @@ int spl_gene_count(spl_ctx *ctx, const spl_dreads *dr, int stranded, int64_t n_a
 int spl_gene_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int stranded, int64_t n_a,
                              const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
                              int64_t n_genes, int64_t *result_out);
+
+/* ---- mates and fragments (paired-end libraries: count a fragment once) ----------------------------------------------------------
+ * Replaces the name-sorted pass of `htseq-count` / `featureCounts -p --countReadPairs`, which count FRAGMENTS of a paired-end
+ * library.  The reference has no counterpart.  The rule is csrc/spl_mate_rule.h, which the kernels and the host hooks compile alike:
+ *   name key    64 bits of the QNAME as the file has it (BAM: l_read_name - 1 bytes, SAM: column 1): FNV-1a over the bytes (from
+ *               0xcbf29ce484222325, per byte h = (h ^ b) * 0x100000001b3), then h ^= h >> 33, h *= 0xff51afd7ed558ccd, h ^= h >> 33,
+ *               h *= 0xc4ceb9fe1a85ec53, h ^= h >> 33, mod 2^64.  An empty name and `*` have key 0, "no name"; another name whose
+ *               hash is 0 has key 1.  A decode leaves the keys beside FLAG when asked to (spl_bam_set_mate_keys);
+ *   pairable    a read that is eligible as for spl_gene_count, has flag 0x1, exactly one of 0x40 and 0x80, and a key that is not 0;
+ *   group       the pairable reads of ONE SEGMENT (a chromosome's reads) whose keys agree in their upper 63 bits;
+ *   mates       within a group, in the segment's order, the j-th first read (0x40) and the j-th second read (0x80); every other
+ *               read has no mate.  A group is one first and one second read unless a name occurs twice or two names' 63 bits
+ *               collide: then two fragments of one chromosome may swap mates.  For n distinct names on a chromosome about
+ *               n^2 / 2^64 colliding pairs are expected, 5e-6 for 10 M names (derived, not measured);
+ *   fragment    a read that is not eligible is "not counted", one per read.  An eligible read whose mate has a lower index adds
+ *               nothing.  Every other eligible read folds its blocks over the map of its own strand and, if it has a mate, the
+ *               mate's blocks over the map of the mate's strand (by the mate's own flag) into one gene set: empty = "no feature", one
+ *               gene = that gene, else "ambiguous".  What is added sums to the reads minus the pairs.
+ * Deliberate differences from the tools: a pair split over two chromosomes, or with one mate filtered out of the decode, counts as
+ * two single-end fragments; names are compared by 63 hash bits.  Parity with htseq-count / featureCounts -p is intended and not
+ * pinned by a test; the yardstick is tests/matecases.py.
+ * spl_mate_table: the table of segment `seg` -- counted over the segments that have reads, in the order they were added; a set
+ * without a read has none and gives three zeros -- of a finished, FUSED read set whose arrays have name keys, made on the device at the
+ * first call (for every segment: the pairable reads compacted to (key with bit 0 = the kind, index), eight stable passes of the
+ * radix sort of spl_sort.hip, then per element three binary searches: O(n log n) whatever the groups; scratch 2 x 12 bytes a
+ * pairable read of the largest segment) and kept with the set, 4 bytes a read.  host_out (or null): a word per read of the
+ * segment, the mate's index within the segment or 0xFFFFFFFF; the table is symmetric.  counts (or null): [0] pairable reads, [1]
+ * reads with a mate (twice the pairs), [2] pairable reads without a mate whose flag has 0x8 clear (a mapped mate that was not
+ * found on the chromosome).  SPL_ERR_ARG: a set that is not finished or not fused, or whose arrays have no name keys; no such segment.
+ * spl_gene_count_fragments: spl_gene_count's arguments and output, counted per fragment by that table.
+ * Test hooks, no GPU: spl_name_key_host (the key of len bytes), spl_mate_table_host (the table of one segment's host arrays: the
+ * pair stage's body as the kernel runs it, behind a stable sort on the host), spl_gene_fragment_rule_host (per read of one
+ * segment's host arrays and its table: the gene's index, -1 no feature, -2 ambiguous, -3 not counted, -4 nothing: the leader counts). */
+int spl_mate_table(spl_ctx *ctx, const spl_dreads *dr, int seg, uint32_t *host_out /* the segment's reads, or null */, int64_t *counts /* 3, or null */);
+int spl_gene_count_fragments(spl_ctx *ctx, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b,
+                             const int32_t *b_start, const uint32_t *b_code, int64_t n_genes, int64_t *inout /* n_genes + 3 */);
+int spl_name_key_host(const uint8_t *bytes, int64_t len, uint64_t *out);
+int spl_mate_table_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint64_t *name_key, uint32_t *mate_out,
+                        int64_t *counts /* 3, or null */);
+int spl_gene_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint32_t *mate,
+                                int32_t shift, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
+                                const uint32_t *b_code, int64_t n_genes, int64_t *results_out /* n_reads */);
 
 /* ---- per-exon-bin read counts (what the pipeline otherwise leaves to a second pass by another program) -----------------------
  * Replaces `featureCounts -f -O` / `dexseq_count.py` over the file this library has just decoded: whoever looks at a change in
@@ -584,7 +644,8 @@ int spl_gene_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, ui
  *               every other read of the set is "not counted".
  * This is DEXSeq's counting (dexseq_count.py: reads with bins of more than one gene are _ambiguous) and `featureCounts -f -O`
  * restricted to reads of one gene, applied per READ: counting is per read, and a paired fragment adds up to two per bin.  Fragment
- * counting needs mate pairing, which the decode does not keep: out of scope.  Parity with DEXSeq / featureCounts is intended and
+ * counting is out of scope here: the bins of a read are committed each bin once, and a fragment needs that across both mates'
+ * walks; the mate table of "mates and fragments" above is what a follow-up would use.  Parity with DEXSeq / featureCounts is intended and
  * unpinned: it is not pinned by a test, neither tool being where this is built.  By construction a read's verdict is the one
  * spl_gene_count gives it on the gene maps of the same features.
  * inout[0 .. n_bins) += the bins' reads, inout[n_bins] += counted reads, [n_bins + 1] += no feature, [n_bins + 2] += ambiguous,

@@ -32,6 +32,7 @@ coverage track of the look at the alignments the reference's README asks for, wi
 Extra sub-command ``genecounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [-c CHROM] [--isStranded -s fr|rf]`` writes
 ``PREFIX.genecounts.tsv``: reads per gene, assigned on the GPU from the decode by htseq-count's ``--mode union --nonunique none`` per
 read -- the two-column file ``edgeR::readDGE`` reads, without a second pass over the BAM by another program (``genecounts.py``).
+``--fragments``: a paired-end fragment counts once -- the decode keeps a key of every read's name, the GPU pairs the mates.
 Extra sub-command ``exoncounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [-c CHROM] [--isStranded -s fr|rf]`` writes
 ``PREFIX.exonbins.tsv`` and ``PREFIX.exoncounts.tsv``: reads per exon counting bin, counted on the GPU from the decode by DEXSeq's rule
 (``featureCounts -f -O`` restricted to reads of one gene) per read -- what ``edgeR::diffSpliceDGE`` needs, without a second pass over
@@ -206,6 +207,9 @@ def build_parser():
     n.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
     n.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
     n.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    n.add_argument("--fragments", dest="fragments", default=False, action="store_true",
+                   help="paired-end: mates are paired on the GPU by a key of their names and a fragment counts once, by both mates' blocks "
+                        "(htseq-count's and featureCounts -p --countReadPairs' way); a pair split over two chromosomes or by the read filter counts as two")
     _filter_flags(n)
     _engine_flags(n)
     x = sub.add_parser("exoncounts", help="(this build only) reads per exon counting bin for edgeR::diffSpliceDGE / DEXSeq, counted on the GPU from the decode "
@@ -224,6 +228,8 @@ def build_parser():
     x.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
     x.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
     x.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    x.add_argument("--fragments", dest="fragments", default=False, action="store_true",
+                   help="(refused: exon bins are counted per read; `genecounts --fragments` counts a paired-end fragment once per gene)")
     _filter_flags(x)
     _engine_flags(x)
     i = sub.add_parser("intronretention", help="(this build only) per annotated intron the trimmed depth, the splice counts and the IR ratio, taken on the GPU from the "
@@ -309,6 +315,9 @@ def main(argv=None):
         parser.error("%s: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf" % command)
     if command in ("genecounts", "exoncounts", "intronretention") and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
         parser.error("%s: --strandedType/-s must be fr or rf" % command)
+    if command == "exoncounts" and kwargs.pop("fragments", False):
+        parser.error("exoncounts: --fragments is not taken here: a read's bins are committed each bin once, and a fragment needs that across both mates' walks; "
+                     "`genecounts --fragments` counts a fragment once per gene")
     if command == "intronretention" and not 0 <= kwargs["trimPercent"] <= 49:
         parser.error("intronretention: --trimPercent must be in 0..49")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":

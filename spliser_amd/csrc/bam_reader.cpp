@@ -321,6 +321,7 @@ struct RefReads {
     uint32_t *cig_off = nullptr; // n + 1 entries, cig_off[0] = 0: ops of read k are cigar[cig_off[k] .. cig_off[k + 1])
     uint32_t *cigar = nullptr;
     uint8_t *xs = nullptr;       // n strand bytes beside flag, or null (spl_bam_set_aux_strand)
+    uint64_t *name_key = nullptr; // n name keys beside flag, or null (spl_bam_set_mate_keys)
     size_t n = 0, n_ops = 0;
     int64_t max_end = 0;
 };
@@ -450,10 +451,11 @@ struct RefFinal {
     uint32_t *cig_off = nullptr; // n + 1
     uint32_t *cigar = nullptr;
     uint8_t *xs = nullptr; // (spl_bam_set_aux_strand; spl_bam_aux_strand hands it out)
+    uint64_t *name_key = nullptr; // (spl_bam_set_mate_keys; spl_bam_mate_keys hands it out)
     RefFinal() = default;
     RefFinal(const RefFinal &) = delete;
     RefFinal &operator=(const RefFinal &) = delete;
-    ~RefFinal() { free(pos); free(flag); free(cig_off); free(cigar); free(xs); }
+    ~RefFinal() { free(pos); free(flag); free(cig_off); free(cigar); free(xs); free(name_key); }
 };
 
 struct PendingPart {
@@ -499,6 +501,7 @@ struct spl_bam {
     bool fetching = false;     // somebody is copying a share's reads to the host right now (fetch_lazy)
     int (*dev_fetch)(void *, int32_t **, uint16_t **, uint32_t **, uint32_t **) = nullptr;
     int (*dev_fetch_xs)(void *, uint8_t **) = nullptr; // ... and their strand bytes, where the decode left any
+    int (*dev_fetch_keys)(void *, uint64_t **) = nullptr; // ... and their name keys, where the decode left any
     // what the device decoder(s) left in device memory for the device packer (spl_capi.cpp), and how to give it back: one handle
     // for a whole-file decode, one per share otherwise
     struct DevShare { void *handle = nullptr; void (*free_fn)(void *) = nullptr; int share = -1; bool fetched = false; };
@@ -574,7 +577,7 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
                                std::string &err, bool &fatal)
 {
     const spl_bam_filter &filter = opts.filter; // (plain values for the two walks: nothing of `opts` is looked up per record)
-    const bool want_xs = opts.aux_strand;
+    const bool want_xs = opts.aux_strand, want_keys = opts.mate_keys;
     int64_t &n_records = out.n_records;
     int64_t *const dropped = out.dropped, *const fstat = opts.flagstat ? out.fstat : nullptr;
     struct Run { int32_t tid; size_t n, ops; const uint8_t *begin; };
@@ -627,7 +630,8 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
         rr.cig_off = (uint32_t *)arena.take(sizeof(uint32_t) * (run.n + 1));
         rr.cigar = (uint32_t *)arena.take(sizeof(uint32_t) * std::max<size_t>(run.ops, 1));
         if (want_xs) rr.xs = (uint8_t *)arena.take(std::max<size_t>(run.n, 1));
-        if (!rr.pos || !rr.flag || !rr.cig_off || !rr.cigar || (want_xs && !rr.xs)) { err = "out of host memory"; fatal = true; return reached; }
+        if (want_keys) rr.name_key = (uint64_t *)arena.take(sizeof(uint64_t) * std::max<size_t>(run.n, 1));
+        if (!rr.pos || !rr.flag || !rr.cig_off || !rr.cigar || (want_xs && !rr.xs) || (want_keys && !rr.name_key)) { err = "out of host memory"; fatal = true; return reached; }
         rr.cig_off[0] = 0;
         size_t i = 0, at = 0;
         for (q = run.begin; i < run.n; q += 4 + (size_t)le32(q)) {
@@ -651,6 +655,7 @@ const uint8_t *extract_records(const uint8_t *p, const uint8_t *end, int n_ref, 
                 has_n = has_n || code == 3;
             }
             if (want_xs) rr.xs[i] = has_n ? spl_bam_aux_strand(r + need, r + bs) : (uint8_t)0;
+            if (want_keys) rr.name_key[i] = spl_name_key_bam(r + 32, l_name, r + bs);
             at += n_cig;
             rr.pos[i] = pos0 + 1;
             rr.flag[i] = le16(r + 14);
@@ -733,7 +738,7 @@ void merge_parts(spl_bam *bam, std::vector<Part> &parts)
 // reference, the references side by side.  (The parts' own arrays stay in their slabs until the file is closed.)
 bool order_parts(spl_bam *bam, std::string &err)
 {
-    struct Done { PendingPart *part = nullptr; void *arr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool failed = false; };
+    struct Done { PendingPart *part = nullptr; void *arr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool failed = false; };
     std::vector<Done> done((size_t)bam->n_refs);
     std::atomic<int> next(0);
     std::atomic<bool> too_many(false);
@@ -743,8 +748,12 @@ bool order_parts(spl_bam *bam, std::string &err)
             if (tid >= bam->n_refs) break;
             const std::vector<PendingPart *> &parts = bam->parts[(size_t)tid];
             size_t n = 0, g = 0;
-            bool with_xs = bam->opts.aux_strand;
-            for (const PendingPart *pt : parts) { n += pt->reads.n; g += pt->reads.n_ops; with_xs = with_xs && (pt->reads.n == 0 || pt->reads.xs != nullptr); }
+            bool with_xs = bam->opts.aux_strand, with_keys = bam->opts.mate_keys;
+            for (const PendingPart *pt : parts) {
+                n += pt->reads.n; g += pt->reads.n_ops;
+                with_xs = with_xs && (pt->reads.n == 0 || pt->reads.xs != nullptr);
+                with_keys = with_keys && (pt->reads.n == 0 || pt->reads.name_key != nullptr);
+            }
             if (n == 0) continue;
             Done &d = done[(size_t)tid];
             if (g > 0xfffffff0ull) { too_many.store(true); d.failed = true; continue; }
@@ -767,8 +776,9 @@ bool order_parts(spl_bam *bam, std::string &err)
             uint32_t *cig_off = (uint32_t *)big_alloc(sizeof(uint32_t) * (n + 1));
             uint32_t *cigar = (uint32_t *)big_alloc(sizeof(uint32_t) * std::max<size_t>(g, 1));
             uint8_t *xs = with_xs ? (uint8_t *)big_alloc(n) : nullptr;
-            d.arr[0] = pos; d.arr[1] = flag; d.arr[2] = cig_off; d.arr[3] = cigar; d.arr[4] = xs;
-            if (!pos || !flag || !cig_off || !cigar || (with_xs && !xs)) { d.failed = true; continue; }
+            uint64_t *name_key = with_keys ? (uint64_t *)big_alloc(sizeof(uint64_t) * n) : nullptr;
+            d.arr[0] = pos; d.arr[1] = flag; d.arr[2] = cig_off; d.arr[3] = cigar; d.arr[4] = xs; d.arr[5] = name_key;
+            if (!pos || !flag || !cig_off || !cigar || (with_xs && !xs) || (with_keys && !name_key)) { d.failed = true; continue; }
             uint32_t o = 0;
             cig_off[0] = 0;
             for (size_t k = 0; k < n; ++k) {
@@ -777,6 +787,7 @@ bool order_parts(spl_bam *bam, std::string &err)
                 pos[k] = r.pos[j];
                 flag[k] = r.flag[j];
                 if (with_xs) xs[k] = r.xs[j];
+                if (with_keys) name_key[k] = r.name_key[j];
                 const uint32_t a = r.cig_off[j], b = r.cig_off[j + 1];
                 if (b > a) memcpy(cigar + o, r.cigar + a, sizeof(uint32_t) * (b - a));
                 o += b - a;
@@ -784,7 +795,7 @@ bool order_parts(spl_bam *bam, std::string &err)
             }
             PendingPart *pp = new PendingPart();
             pp->tid = tid;
-            pp->reads.pos = pos; pp->reads.flag = flag; pp->reads.cig_off = cig_off; pp->reads.cigar = cigar; pp->reads.xs = xs;
+            pp->reads.pos = pos; pp->reads.flag = flag; pp->reads.cig_off = cig_off; pp->reads.cigar = cigar; pp->reads.xs = xs; pp->reads.name_key = name_key;
             pp->reads.n = n; pp->reads.n_ops = g; pp->reads.max_end = bam->ref_max_end[(size_t)tid];
             d.part = pp;
         }
@@ -833,7 +844,10 @@ bool assemble_ref(spl_bam *bam, int tid, std::string &err)
     bool with_xs = bam->opts.aux_strand;
     for (const PendingPart *pt : parts) with_xs = with_xs && (pt->reads.n == 0 || pt->reads.xs != nullptr);
     if (with_xs) dst.xs = (uint8_t *)big_alloc((size_t)std::max<int64_t>(n, 1));
-    if (!dst.pos || !dst.flag || !dst.cig_off || !dst.cigar || (with_xs && !dst.xs)) { err = "out of host memory"; return false; }
+    bool with_keys = bam->opts.mate_keys;
+    for (const PendingPart *pt : parts) with_keys = with_keys && (pt->reads.n == 0 || pt->reads.name_key != nullptr);
+    if (with_keys) dst.name_key = (uint64_t *)big_alloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(n, 1));
+    if (!dst.pos || !dst.flag || !dst.cig_off || !dst.cigar || (with_xs && !dst.xs) || (with_keys && !dst.name_key)) { err = "out of host memory"; return false; }
     dst.cig_off[0] = 0;
     std::vector<int64_t> read_at(parts.size() + 1, 0), op_at(parts.size() + 1, 0);
     for (size_t i = 0; i < parts.size(); ++i) {
@@ -851,6 +865,7 @@ bool assemble_ref(spl_bam *bam, int tid, std::string &err)
             memcpy(dst.pos + read_at[i], src.pos, sizeof(int32_t) * k);
             memcpy(dst.flag + read_at[i], src.flag, sizeof(uint16_t) * k);
             if (with_xs) memcpy(dst.xs + read_at[i], src.xs, k);
+            if (with_keys) memcpy(dst.name_key + read_at[i], src.name_key, sizeof(uint64_t) * k);
             const uint32_t base = (uint32_t)op_at[i];
             uint32_t *off = dst.cig_off + read_at[i]; // entry j + 1 = end of read j
             const uint32_t c0 = src.cig_off[0]; // (0 for the host decoder's parts; a file-wide offset for adopted arrays)
@@ -1259,6 +1274,7 @@ extern "C" int spl_bam_set_filter(spl_bam *bam, int min_mapq, int require_flags,
 }
 // A strand byte per placed read beside its flag, from the aligner's XS:A tag.
 extern "C" int spl_bam_set_aux_strand(spl_bam *bam, int on) { return set_opt(bam, "spl_bam_set_aux_strand", [&](spl_bam_decode_opts &o) { o.aux_strand = on != 0; }); }
+extern "C" int spl_bam_set_mate_keys(spl_bam *bam, int on) { return set_opt(bam, "spl_bam_set_mate_keys", [&](spl_bam_decode_opts &o) { o.mate_keys = on != 0; }); }
 // The flagstat counters, counted by whoever decodes the file.
 extern "C" int spl_bam_set_flagstat(spl_bam *bam, int on) { return set_opt(bam, "spl_bam_set_flagstat", [&](spl_bam_decode_opts &o) { o.flagstat = on != 0; }); }
 // The file's records may come in any order: whoever decodes it hands every reference's reads out sorted by (POS, place in the file).
@@ -1910,6 +1926,11 @@ void spl_bam_set_fetch_xs(spl_bam *bam, int (*fetch)(void *, uint8_t **))
     std::lock_guard<std::mutex> lock(bam->mu);
     bam->dev_fetch_xs = fetch;
 }
+void spl_bam_set_fetch_keys(spl_bam *bam, int (*fetch)(void *, uint64_t **))
+{
+    std::lock_guard<std::mutex> lock(bam->mu);
+    bam->dev_fetch_keys = fetch;
+}
 
 // The host copies of reads that were adopted without them: of every share that has not brought its yet.  Called with bam->mu
 // held; the copy itself (gigabytes over PCIe) runs WITHOUT it -- whoever else wants a reference that is there already, or wants
@@ -1929,17 +1950,24 @@ static int fetch_lazy(spl_bam *bam, std::unique_lock<std::mutex> &lock)
         int32_t *pos = nullptr; uint16_t *flag = nullptr; uint32_t *cig_off = nullptr, *cigar = nullptr;
         uint8_t *xs = nullptr;
         int (*const fetch_xs)(void *, uint8_t **) = bam->opts.aux_strand ? bam->dev_fetch_xs : nullptr;
+        uint64_t *keys = nullptr;
+        int (*const fetch_keys)(void *, uint64_t **) = bam->opts.mate_keys ? bam->dev_fetch_keys : nullptr;
         lock.unlock();
         int rc = bam->dev_fetch(handle, &pos, &flag, &cig_off, &cigar);
         if (rc == SPL_OK && fetch_xs) { // (the fifth array, where the decode left one: copied with the others)
             rc = fetch_xs(handle, &xs);
             if (rc) { free(pos); free(flag); free(cig_off); free(cigar); }
         }
+        if (rc == SPL_OK && fetch_keys) { // (and the name keys)
+            rc = fetch_keys(handle, &keys);
+            if (rc) { free(pos); free(flag); free(cig_off); free(cigar); free(xs); xs = nullptr; }
+        }
         lock.lock();
         bam->fetching = false;
         if (rc) { bam->cv.notify_all(); return rc; }
         bam->slabs.push_back(pos); bam->slabs.push_back(flag); bam->slabs.push_back(cig_off); bam->slabs.push_back(cigar);
         if (xs) bam->slabs.push_back(xs);
+        if (keys) bam->slabs.push_back(keys);
         for (int t = 0; t < bam->n_refs; ++t) {
             for (PendingPart *pp : bam->parts[(size_t)t]) {
                 if (pp->share != share) continue;
@@ -1950,6 +1978,7 @@ static int fetch_lazy(spl_bam *bam, std::unique_lock<std::mutex> &lock)
                 r.cig_off = cig_off + first;
                 r.cigar = cigar;
                 r.xs = xs ? xs + first : nullptr;
+                r.name_key = keys ? keys + first : nullptr;
                 r.n_ops = (size_t)(r.cig_off[r.n] - r.cig_off[0]);
             }
         }
@@ -2053,6 +2082,21 @@ extern "C" int spl_bam_aux_strand(const spl_bam *cbam, int tid, const uint8_t **
     spl_bam *bam = const_cast<spl_bam *>(cbam);
     std::lock_guard<std::mutex> lock(bam->mu);
     if (r.n_reads > 0) *out = bam->refs_storage[(size_t)tid].xs;
+    return SPL_OK;
+}
+
+// Borrowed view (valid until spl_bam_close) of the name keys of the reads spl_bam_reads hands out for `tid`, in the same order;
+// *out = null when the file was decoded without spl_bam_set_mate_keys (or the reference has no reads).
+extern "C" int spl_bam_mate_keys(const spl_bam *cbam, int tid, const uint64_t **out)
+{
+    if (!cbam || !out) return spl_set_error(SPL_ERR_ARG, "spl_bam_mate_keys: null argument");
+    *out = nullptr;
+    spl_reads r;
+    const int rc = spl_bam_reads(cbam, tid, &r, nullptr); // (assembles the reference, the keys with the other arrays)
+    if (rc) return rc;
+    spl_bam *bam = const_cast<spl_bam *>(cbam);
+    std::lock_guard<std::mutex> lock(bam->mu);
+    if (r.n_reads > 0) *out = bam->refs_storage[(size_t)tid].name_key;
     return SPL_OK;
 }
 
@@ -2554,6 +2598,7 @@ static void sam_host_worker(spl_bam *bam)
     std::vector<uint64_t> off_v(1, 0);
     std::vector<uint32_t> cigar_v;
     std::vector<int64_t> end_v;
+    std::vector<uint64_t> key_v; // (spl_bam_set_mate_keys)
     spl_bam_totals totals;
     uint64_t line_no = bam->header_lines;
     const size_t max_line = spl_sam_window_bytes();
@@ -2594,6 +2639,7 @@ static void sam_host_worker(spl_bam *bam)
                 pos_v.push_back(ln.pos);
                 flag_v.push_back((uint16_t)ln.flag);
                 xs_v.push_back(ln.xs);
+                if (opts.mate_keys) key_v.push_back(spl_name_key_sam(p, stop));
                 end_v.push_back(ln.end);
                 off_v.push_back(cigar_v.size());
             }
@@ -2635,13 +2681,14 @@ static void sam_host_worker(spl_bam *bam)
             uint32_t *cig_off = (uint32_t *)big_alloc(sizeof(uint32_t) * (m + 1));
             uint32_t *cigar = (uint32_t *)big_alloc(sizeof(uint32_t) * std::max<size_t>(g, 1));
             uint8_t *xs = opts.aux_strand ? (uint8_t *)big_alloc(m) : nullptr;
-            for (void *a : {(void *)pos, (void *)flag, (void *)cig_off, (void *)cigar, (void *)xs}) if (a) slabs.push_back(a);
-            if (!pos || !flag || !cig_off || !cigar || (opts.aux_strand && !xs)) { nomem = true; break; }
+            uint64_t *keys = opts.mate_keys ? (uint64_t *)big_alloc(sizeof(uint64_t) * m) : nullptr;
+            for (void *a : {(void *)pos, (void *)flag, (void *)cig_off, (void *)cigar, (void *)xs, (void *)keys}) if (a) slabs.push_back(a);
+            if (!pos || !flag || !cig_off || !cigar || (opts.aux_strand && !xs) || (opts.mate_keys && !keys)) { nomem = true; break; }
             PendingPart *pp = new PendingPart();
             made[(size_t)tid] = pp;
             pp->tid = tid;
             RefReads &r = pp->reads;
-            r.pos = pos; r.flag = flag; r.cig_off = cig_off; r.cigar = cigar; r.xs = xs; r.n = m; r.n_ops = g;
+            r.pos = pos; r.flag = flag; r.cig_off = cig_off; r.cigar = cigar; r.xs = xs; r.name_key = keys; r.n = m; r.n_ops = g;
             uint32_t o = 0;
             cig_off[0] = 0;
             for (size_t j = 0; j < m; ++j) {
@@ -2649,6 +2696,7 @@ static void sam_host_worker(spl_bam *bam)
                 pos[j] = pos_v[i];
                 flag[j] = flag_v[i];
                 if (xs) xs[j] = xs_v[i];
+                if (keys) keys[j] = key_v[i];
                 const size_t a = (size_t)off_v[i], b = (size_t)off_v[i + 1];
                 if (b > a) memcpy(cigar + o, cigar_v.data() + a, sizeof(uint32_t) * (b - a));
                 o += (uint32_t)(b - a);

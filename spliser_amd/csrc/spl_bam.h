@@ -33,6 +33,7 @@ struct spl_bam_decode_opts {
     spl_bam_filter filter = {0, 0, 0}; // which placed records are kept
     bool aux_strand = false;           // a strand byte per placed read beside its flag, from the aligner's XS:A tag
     bool flagstat = false;             // count the flagstat categories (spl_flagstat.h)
+    bool mate_keys = false;            // a name key per placed read beside its flag (spl_mate_rule.h), for mate pairing
     bool any_order = false;            // the records may come in any order: the decoder hands every reference's reads out sorted by (POS, place in the file)
 };
 spl_bam_decode_opts spl_bam_get_opts(spl_bam *bam);
@@ -107,6 +108,7 @@ bool spl_bam_cancelled(const spl_bam *bam);                   // spl_bam_cancel 
 // reader asks for them (spl_bam_source, spl_bam_reads)
 void spl_bam_set_fetch(spl_bam *bam, int (*fetch)(void *, int32_t **, uint16_t **, uint32_t **, uint32_t **));
 void spl_bam_set_fetch_xs(spl_bam *bam, int (*fetch)(void *, uint8_t **)); // ... and of the strand bytes (null out = the handle has none)
+void spl_bam_set_fetch_keys(spl_bam *bam, int (*fetch)(void *, uint64_t **)); // ... and of the name keys (null out = the handle has none)
 int spl_bam_start_host(spl_bam *bam);                      // decode on the host's threads unless somebody decodes already
 bool spl_bam_claim_for_device(spl_bam *bam);               // the device decoder takes the file (false: it is taken)
 void spl_bam_note_decline(spl_bam *bam, const char *why); // why the device decoder leaves the file to the host threads

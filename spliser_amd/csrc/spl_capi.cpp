@@ -41,6 +41,8 @@
 #include "spl_coverage_rule.h"
 #include "spl_genecount.h"
 #include "spl_genecount_rule.h"
+#include "spl_mate_rule.h"
+#include "spl_mates.h"
 #include "spl_exoncount.h"
 #include "spl_exoncount_rule.h"
 #include "spl_intron.h"
@@ -468,6 +470,10 @@ struct spl_dreads {
     mutable int queue_turn = 0;        // which of the two the next pass takes
     mutable bool queued_pass = false;  // the last counting pass over this read set had a literal kernel
     mutable int64_t tail_pass = -1;    // the context's pass number of the last counting pass over this set that has a tail on the tail stream
+    // The mate table of a fused set whose arrays have name keys (spl_mate_table): made on first use, kept with the set.  One word a
+    // read of the arrays, a segment's at its reads' places, the mate as an index within the segment; three counters a segment.
+    mutable uint32_t *mates = nullptr;
+    mutable std::vector<int64_t> mate_counts;
 };
 
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
@@ -1261,6 +1267,7 @@ struct DeviceReads {
     int device = 0;
     void *pos = nullptr, *flag = nullptr, *cig_off = nullptr, *cigar = nullptr;
     void *xs = nullptr; // uint8[n_rec] beside flag, or null: the reads' strand bytes (spl_bam_set_aux_strand, spl_soa_upload3)
+    void *name_key = nullptr; // uint64[n_rec] beside flag, or null: the reads' name keys (spl_bam_set_mate_keys, spl_soa_upload4)
     int64_t n_rec = 0, n_ops = 0;
     std::vector<int64_t> ref_first, ref_n, ref_max, ref_ops;
     std::atomic<int> refs{1};
@@ -1273,7 +1280,7 @@ static void free_device_reads(void *h)
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
     (void)hipSetDevice(r->device);
-    devmem::put(r->pos); devmem::put(r->flag); devmem::put(r->cig_off); devmem::put(r->cigar); devmem::put(r->xs);
+    devmem::put(r->pos); devmem::put(r->flag); devmem::put(r->cig_off); devmem::put(r->cigar); devmem::put(r->xs); devmem::put(r->name_key);
     if (have) (void)hipSetDevice(cur);
     delete r;
 }
@@ -1282,9 +1289,9 @@ static void free_device_reads(void *h)
 // them, with the room they have and what is used of it.  Both decoders (ShareDecode, SamDecode) grow them here, RecordSort swaps
 // its sorted copy in, and find_runs / hand_over make the DeviceReads of them.
 struct RecordArrays {
-    DevBuf pos, flag, cig_off, cigar, tid, xs; // (xs only where want_xs)
+    DevBuf pos, flag, cig_off, cigar, tid, xs, name_key; // (xs only where want_xs, name_key only where want_keys)
     uint64_t cap_rec = 0, cap_ops = 0, n_rec = 0, n_ops = 0;
-    bool want_xs = false;
+    bool want_xs = false, want_keys = false;
     struct Run { uint64_t first; int32_t tid; uint32_t op; }; // a reference's records: the first one, the id, its first op
 
     // Room for want_rec records and want_ops ops, each limit raised only where it rises: an array at a time anew, what is there
@@ -1309,6 +1316,7 @@ struct RecordArrays {
             if (rc == SPL_OK) rc = grow(tid, 4, want_rec, n_rec);
             if (rc == SPL_OK) rc = grow(cig_off, 4, want_rec + 1, n_rec + 1);
             if (rc == SPL_OK && want_xs) rc = grow(xs, 1, want_rec, n_rec);
+            if (rc == SPL_OK && want_keys) rc = grow(name_key, 8, want_rec, n_rec);
             if (rc) return rc;
             if (first) HIP_TRY(hipMemsetAsync(cig_off.p, 0, 4, st));
             cap_rec = want_rec;
@@ -1322,10 +1330,10 @@ struct RecordArrays {
     }
     void swap(RecordArrays &o)
     {
-        std::swap(pos.p, o.pos.p); std::swap(flag.p, o.flag.p); std::swap(cig_off.p, o.cig_off.p); std::swap(cigar.p, o.cigar.p); std::swap(tid.p, o.tid.p); std::swap(xs.p, o.xs.p);
+        std::swap(pos.p, o.pos.p); std::swap(flag.p, o.flag.p); std::swap(cig_off.p, o.cig_off.p); std::swap(cigar.p, o.cigar.p); std::swap(tid.p, o.tid.p); std::swap(xs.p, o.xs.p); std::swap(name_key.p, o.name_key.p);
         std::swap(cap_rec, o.cap_rec); std::swap(cap_ops, o.cap_ops);
     }
-    void release() { pos.release(); flag.release(); cig_off.release(); cigar.release(); tid.release(); xs.release(); cap_rec = cap_ops = 0; }
+    void release() { pos.release(); flag.release(); cig_off.release(); cigar.release(); tid.release(); xs.release(); name_key.release(); cap_rec = cap_ops = 0; }
 
     // Where each reference's records are (the bounds kernel on `st`, waited for), sorted by their first record, and whether the
     // references come in order: no more runs than bounds_cap, every id in [0, n_ref) and above the one before.
@@ -1365,8 +1373,8 @@ struct RecordArrays {
             keep->ref_ops[t] = (int64_t)((last ? n_ops : (uint64_t)runs[k + 1].op) - runs[k].op);
             keep->ref_max[t] = (int64_t)maxend[t];
         }
-        keep->pos = pos.p; keep->flag = flag.p; keep->cig_off = cig_off.p; keep->cigar = cigar.p; keep->xs = xs.p;
-        pos.p = flag.p = cig_off.p = cigar.p = xs.p = nullptr;
+        keep->pos = pos.p; keep->flag = flag.p; keep->cig_off = cig_off.p; keep->cigar = cigar.p; keep->xs = xs.p; keep->name_key = name_key.p;
+        pos.p = flag.p = cig_off.p = cigar.p = xs.p = name_key.p = nullptr;
         return keep;
     }
 };
@@ -1459,6 +1467,24 @@ static int fetch_device_xs(void *h, uint8_t **out)
     return SPL_OK;
 }
 
+// ... and the name keys, where the decode left them (spl_bam_set_mate_keys): *out = null when it did not.
+static int fetch_device_keys(void *h, uint64_t **out)
+{
+    const DeviceReads *r = (const DeviceReads *)h;
+    *out = nullptr;
+    if (!r->name_key) return SPL_OK;
+    uint64_t *host = (uint64_t *)host_array(8 * (size_t)r->n_rec);
+    if (!host) return spl_set_error(SPL_ERR_NOMEM, "out of host memory for the decoded reads");
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    hipError_t q = hipSetDevice(r->device);
+    if (q == hipSuccess && r->n_rec) q = hipMemcpy(host, r->name_key, 8 * (size_t)r->n_rec, hipMemcpyDeviceToHost);
+    if (have) (void)hipSetDevice(cur);
+    if (q != hipSuccess) { free(host); return spl_set_error(SPL_ERR_HIP, "decoded name keys back to the host: %s", hipGetErrorString(q)); }
+    *out = host;
+    return SPL_OK;
+}
+
 // One more segment of a read set from reads that are on the device already, BAM-native (add_segment is the host's version):
 // only noted here -- the layout kernel runs once for all such segments when the read set is finished (finish_reads).
 static int add_segment_device(spl_ctx *c, spl_dreads *d, DeviceReads *dev, int64_t first, int64_t n_reads, int64_t n_ops, int32_t shift, int64_t max_end)
@@ -1533,6 +1559,7 @@ extern "C" int spl_bam_decode_device(spl_ctx *c, spl_bam *bam, int *on_device_ou
         spl_bam_set_device_reads(bam, keep, free_device_reads);
         spl_bam_set_fetch(bam, fetch_device_reads);
         spl_bam_set_fetch_xs(bam, fetch_device_xs);
+        spl_bam_set_fetch_keys(bam, fetch_device_keys);
         const int rc = spl_bam_adopt(bam, nullptr, nullptr, nullptr, nullptr, keep->ref_first.data(), keep->ref_n.data(), keep->ref_max.data(), res.totals);
         if (rc) spl_bam_set_device_reads(bam, nullptr, nullptr);
         if (rc == SPL_OK && on_device_out) *on_device_out = 1;
@@ -1565,6 +1592,7 @@ extern "C" int spl_bam_decode_device_share(spl_ctx *c, spl_bam *bam, int k, int 
     const Publish report = [&](ShareOut &res) -> int { // (a share that is done: reported at once, the last one to report completes the file)
         spl_bam_set_fetch(bam, fetch_device_reads);
         spl_bam_set_fetch_xs(bam, fetch_device_xs);
+        spl_bam_set_fetch_keys(bam, fetch_device_keys);
         const int rc2 = spl_bam_share_done(bam, k, res.reads, free_device_reads, res.reads->ref_first.data(), res.reads->ref_n.data(), res.reads->ref_max.data(), res.totals, 0);
         if (rc2 == SPL_OK && on_device_out) *on_device_out = 1;
         return rc2;
@@ -1593,9 +1621,9 @@ struct RecordSort {
         while (tid_bits < 31u && ((uint64_t)std::max(n_ref - 1, 1) >> tid_bits)) ++tid_bits;
         passes = spl_dev_sort_passes(pos_bits, tid_bits, shifts);
     }
-    static double bytes_needed(uint64_t n_rec, uint64_t n_ops, bool want_xs)
+    static double bytes_needed(uint64_t n_rec, uint64_t n_ops, bool want_xs, bool want_keys = false)
     {
-        return 24.0 * (double)n_rec + (double)spl_dev_sort_work_bytes(n_rec) + (want_xs ? 15.0 : 14.0) * (double)n_rec + 4.0 * (double)n_ops + 4096.0;
+        return 24.0 * (double)n_rec + (double)spl_dev_sort_work_bytes(n_rec) + ((want_xs ? 15.0 : 14.0) + (want_keys ? 8.0 : 0.0)) * (double)n_rec + 4.0 * (double)n_ops + 4096.0;
     }
     // (after plan) n_ops < 2^32 and n_rec <= 0xfffffff0 are the caller's to have seen; waits for the stream before it swaps
     int run(hipStream_t st, RecordArrays &a)
@@ -1608,6 +1636,7 @@ struct RecordSort {
         HIP_TRY(sorted.pos.get(4 * n, st)); HIP_TRY(sorted.flag.get(2 * n, st)); HIP_TRY(sorted.cig_off.get(4 * (n + 1), st));
         HIP_TRY(sorted.cigar.get(4 * (size_t)a.n_ops, st)); HIP_TRY(sorted.tid.get(4 * n, st));
         if (want_xs) HIP_TRY(sorted.xs.get(n, st));
+        if (a.want_keys) HIP_TRY(sorted.name_key.get(8 * n, st));
         sorted.cap_rec = n_rec; sorted.cap_ops = a.n_ops;
         HIP_TRY((hipError_t)spl_dev_launch_sort_make_keys(a.tid.as<int32_t>(), a.pos.as<int32_t>(), n_rec, keys[0].as<uint64_t>(), st));
         int cur = 0;
@@ -1618,6 +1647,7 @@ struct RecordSort {
         HIP_TRY((hipError_t)spl_dev_launch_sort_gather(order, keys[cur].as<uint64_t>(), n_rec, a.pos.as<int32_t>(), a.flag.as<uint16_t>(), want_xs ? a.xs.as<uint8_t>() : nullptr,
                                                        a.cig_off.as<uint32_t>(), sorted.pos.as<int32_t>(), sorted.flag.as<uint16_t>(), want_xs ? sorted.xs.as<uint8_t>() : nullptr,
                                                        sorted.tid.as<int32_t>(), sorted.cig_off.as<uint32_t>(), st));
+        if (a.want_keys) HIP_TRY((hipError_t)spl_dev_launch_gather_u64(order, n_rec, a.name_key.as<uint64_t>(), sorted.name_key.as<uint64_t>(), st));
         HIP_TRY((hipError_t)spl_dev_launch_sort_scan(sorted.cig_off.as<uint32_t>() + 1, n_rec, work.p, st));
         HIP_TRY((hipError_t)spl_dev_launch_sort_cigar(order, n_rec, a.cig_off.as<uint32_t>(), a.cigar.as<uint32_t>(), sorted.cig_off.as<uint32_t>(), sorted.cigar.as<uint32_t>(), st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1742,6 +1772,7 @@ struct ShareDecode {
     const int n_ref = spl_bam_n_ref(bam);
     const spl_bam_decode_opts opts = spl_bam_get_opts(bam); // (the file is claimed: nobody changes them now)
     const bool want_xs = opts.aux_strand;            // (a fifth array, the spliced reads' XS:A strand)
+    const bool want_keys = opts.mate_keys;           // (one more, the reads' name keys)
     const bool want_stat = opts.flagstat;            // (the scan counts the flagstat categories per block, a kernel adds up the accepted blocks')
     const bool any_order = !share && opts.any_order; // (the records may come in any order -- sorted behind the last extraction, sort_records; the whole file only)
     // ---- everything the streams touch is declared before them
@@ -1808,7 +1839,7 @@ struct ShareDecode {
     size_t launched = 0, copying = 0; // windows whose decoding / whose copying kernel has been put on its stream
     std::vector<double> t_win; // (SPL_BAM_TIMING: when each window's scan was back on the host)
 
-    ShareDecode(spl_ctx *ctx, spl_bam *b, const spl_bam_share *s, ShareOut &out, bool all_room) : c(ctx), bam(b), share(s), res(out), all_token_room(all_room) { arrays.want_xs = want_xs; }
+    ShareDecode(spl_ctx *ctx, spl_bam *b, const spl_bam_share *s, ShareOut &out, bool all_room) : c(ctx), bam(b), share(s), res(out), all_token_room(all_room) { arrays.want_xs = want_xs; arrays.want_keys = want_keys; }
     ~ShareDecode()
     {
         if (walker.joinable()) walker.join();
@@ -2434,11 +2465,18 @@ struct ShareDecode {
             HIP_TRY(hipMemcpyAsync(d_opoff.as<uint64_t>() + s0, op_off.get() + s0, 8 * nd, hipMemcpyHostToDevice, pipe.b));
             HIP_TRY(hipMemcpyAsync(d_scan.as<spl_bscan>() + s0, scan.get() + s0, sizeof(spl_bscan) * nd, hipMemcpyHostToDevice, pipe.b));
             splprof::Scope p("spl_bam_extract_kernel", pipe.b, (double)(blocks[b_done - 1].out + blocks[b_done - 1].out_len - blocks[s0].out));
-            HIP_TRY((hipError_t)spl_dev_launch_bam_extract(stream0, win_end, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)nd, d_scan.as<spl_bscan>() + s0,
-                                                           d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(),
-                                                           arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(), arrays.tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
-                                                           with_recs ? d_recs.as<uint16_t>() : nullptr, opts.filter.min_mapq, opts.filter.require_flags, opts.filter.exclude_flags,
-                                                           want_xs ? arrays.xs.as<uint8_t>() : nullptr, pipe.b));
+            if (want_keys) // (spl_bam_set_mate_keys: the extractions' instantiations that hash the names)
+                HIP_TRY((hipError_t)spl_dev_launch_bam_extract_keys(stream0, win_end, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)nd, d_scan.as<spl_bscan>() + s0,
+                                                                    d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(),
+                                                                    arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(), arrays.tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
+                                                                    with_recs ? d_recs.as<uint16_t>() : nullptr, opts.filter.min_mapq, opts.filter.require_flags,
+                                                                    opts.filter.exclude_flags, want_xs ? arrays.xs.as<uint8_t>() : nullptr, arrays.name_key.as<uint64_t>(), pipe.b));
+            else
+                HIP_TRY((hipError_t)spl_dev_launch_bam_extract(stream0, win_end, n_ref, 0, n_ref + 1, d_blocks.as<spl_zblock>() + s0, (uint32_t)nd, d_scan.as<spl_bscan>() + s0,
+                                                               d_recoff.as<uint64_t>() + s0, d_opoff.as<uint64_t>() + s0, arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(),
+                                                               arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(), arrays.tid.as<int32_t>(), d_maxend.as<unsigned long long>(),
+                                                               with_recs ? d_recs.as<uint16_t>() : nullptr, opts.filter.min_mapq, opts.filter.require_flags, opts.filter.exclude_flags,
+                                                               want_xs ? arrays.xs.as<uint8_t>() : nullptr, pipe.b));
         }
         if (want_stat && b_done > s0) { // the counters of the blocks that are done with, each once: a block that waits for the next window is scanned, and counted, again
             splprof::Scope p("spl_bam_flagstat_reduce_kernel", pipe.b, 4.0 * SPL_FS_CATEGORIES * (double)(b_done - s0));
@@ -2468,7 +2506,7 @@ struct ShareDecode {
         for (int k = 0; k < NBUF; ++k) { d_stream[k].release(); d_zwork[k].release(); }
         d_recs.release();
         HIP_TRY(look_at_free());
-        if (RecordSort::bytes_needed(n_rec, n_ops, want_xs) + slack > (double)free_b) return to_host("not enough device memory to sort the records");
+        if (RecordSort::bytes_needed(n_rec, n_ops, want_xs, want_keys) + slack > (double)free_b) return to_host("not enough device memory to sort the records");
         const double t_room = host_now();
         { const int rc = sorter.run(pipe.b, arrays); if (rc) return rc; } // (n_ops < 2^32: records_done)
         n_sorted = n_rec;
@@ -2580,7 +2618,7 @@ struct SamDecode {
     const uint8_t *const image = spl_bam_image(bam, &fsize);
     const int n_ref = spl_bam_n_ref(bam);
     const spl_bam_decode_opts opts = spl_bam_get_opts(bam);
-    const bool want_xs = opts.aux_strand, want_stat = opts.flagstat;
+    const bool want_xs = opts.aux_strand, want_stat = opts.flagstat, want_keys = opts.mate_keys;
     uint64_t begin = 0, header_lines = 0;
     spl_sam_names host_names{}, dev_names{};
     size_t blob_bytes = 0;
@@ -2613,7 +2651,7 @@ struct SamDecode {
     hipError_t up_err = hipSuccess;
     std::thread uploader;
 
-    SamDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : c(ctx), bam(b), res(r) { arrays.want_xs = want_xs; }
+    SamDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : c(ctx), bam(b), res(r) { arrays.want_xs = want_xs; arrays.want_keys = want_keys; }
     ~SamDecode()
     {
         {
@@ -2823,10 +2861,17 @@ struct SamDecode {
         if (want_stat) HIP_TRY((hipError_t)spl_dev_launch_bam_flagstat_reduce(d_fstat.as<uint32_t>(), (n_lines + 63u) / 64u, d_fsum.as<unsigned long long>(), st.k));
         // ---- the kept lines' fields behind the ones there are
         { const int rc = make_room(kept_w, ops_w, win.hi - win.lo, bytes_left); if (rc) return rc; }
-        HIP_TRY((hipError_t)spl_dev_launch_sam_extract(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
-                                                       opts.filter.exclude_flags, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(), arrays.n_rec, arrays.n_ops, arrays.cap_rec, arrays.cap_ops,
-                                                       arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(), arrays.tid.as<int32_t>(), arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(),
-                                                       want_xs ? arrays.xs.as<uint8_t>() : nullptr, d_maxend.as<unsigned long long>(), d_counts.as<spl_sam_counts>(), st.k));
+        if (want_keys) // (spl_bam_set_mate_keys: the instantiation that hashes column 1)
+            HIP_TRY((hipError_t)spl_dev_launch_sam_extract_keys(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
+                                                                opts.filter.exclude_flags, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(), arrays.n_rec, arrays.n_ops,
+                                                                arrays.cap_rec, arrays.cap_ops, arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(), arrays.tid.as<int32_t>(),
+                                                                arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(), want_xs ? arrays.xs.as<uint8_t>() : nullptr,
+                                                                arrays.name_key.as<uint64_t>(), d_maxend.as<unsigned long long>(), d_counts.as<spl_sam_counts>(), st.k));
+        else
+            HIP_TRY((hipError_t)spl_dev_launch_sam_extract(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
+                                                           opts.filter.exclude_flags, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(), arrays.n_rec, arrays.n_ops, arrays.cap_rec, arrays.cap_ops,
+                                                           arrays.pos.as<int32_t>(), arrays.flag.as<uint16_t>(), arrays.tid.as<int32_t>(), arrays.cig_off.as<uint32_t>(), arrays.cigar.as<uint32_t>(),
+                                                           want_xs ? arrays.xs.as<uint8_t>() : nullptr, d_maxend.as<unsigned long long>(), d_counts.as<spl_sam_counts>(), st.k));
         HIP_TRY((hipError_t)spl_dev_launch_sam_order(arrays.tid.as<int32_t>(), arrays.pos.as<int32_t>(), arrays.n_rec, kept_w, d_counts.as<spl_sam_counts>(), st.k));
         HIP_TRY(hipStreamSynchronize(st.k)); // (the window's buffer is free for the window after the next)
         arrays.n_rec += kept_w;
@@ -3533,7 +3578,8 @@ void max_end_slice(size_t k, void *arg)
 } // namespace
 
 // n_seg host segments as they are -> one set of device arrays (DeviceReads, one reference held by the caller).
-static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceReads **out, const int64_t *max_end, const uint8_t *const *xs = nullptr)
+static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceReads **out, const int64_t *max_end, const uint8_t *const *xs = nullptr,
+                         const uint64_t *const *name_key = nullptr)
 {
     *out = nullptr;
     HIP_TRY(hipSetDevice(c->device));
@@ -3559,6 +3605,7 @@ static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceRea
     if (q == hipSuccess) q = devmem::get(&dev->cig_off, 4 * ((size_t)n_rec + 1) + 64, 'b');
     if (q == hipSuccess) q = devmem::get(&dev->cigar, 4 * (size_t)n_ops + 64, 'b');
     if (q == hipSuccess && xs) q = devmem::get(&dev->xs, (size_t)n_rec + 64, 'b');
+    if (q == hipSuccess && name_key) q = devmem::get(&dev->name_key, 8 * (size_t)n_rec + 64, 'b');
     // The arrays go up as they are, through the context's ring of page-locked staging buffers: a piece is copied into a buffer by
     // the packing threads side by side (the CIGAR offsets moved behind the ops of the segments before theirs on the way), and is
     // on the copy stream while the next piece is copied -- a caller's pageable array straight into hipMemcpy is a third of that.
@@ -3602,6 +3649,7 @@ static int upload_native(spl_ctx *c, int n_seg, const spl_reads *segs, DeviceRea
             send((int32_t *)dev->pos + at, r.pos, 4 * (size_t)r.n_reads, 0u, false);
             send((uint16_t *)dev->flag + at, r.flag, 2 * (size_t)r.n_reads, 0u, false);
             if (xs) send((uint8_t *)dev->xs + at, xs[k], (size_t)r.n_reads, 0u, false);
+            if (name_key) send((uint64_t *)dev->name_key + at, name_key[k], 8 * (size_t)r.n_reads, 0u, false);
             if (g) send((uint32_t *)dev->cigar + op_at, r.cigar, 4 * (size_t)g, 0u, false);
             send((uint32_t *)dev->cig_off + at, r.cig_off, 4 * (size_t)r.n_reads, (uint32_t)op_at, true);
         }
@@ -3656,6 +3704,26 @@ extern "C" int spl_soa_upload3(spl_ctx *c, int n_seg, const spl_reads *segs, con
     return SPL_OK;
 }
 
+// ... name_key[k]: per read of segment k its name key (spl_mate_rule.h; 0 = no name), a further array beside flag: what
+// spl_mate_table reads.  xs as for spl_soa_upload3, or null: no strand bytes.
+extern "C" int spl_soa_upload4(spl_ctx *c, int n_seg, const spl_reads *segs, const int64_t *max_end, const uint8_t *const *xs, const uint64_t *const *name_key, spl_dsoa **out)
+{
+    if (!c || !out || n_seg < 0 || (n_seg && !segs) || !name_key) return spl_set_error(SPL_ERR_ARG, "spl_soa_upload4: null argument");
+    for (int k = 0; k < n_seg; ++k) {
+        if (segs[k].n_reads > 0 && xs && !xs[k]) return spl_set_error(SPL_ERR_ARG, "spl_soa_upload4: segment %d has no strand bytes", k);
+        if (segs[k].n_reads > 0 && !name_key[k]) return spl_set_error(SPL_ERR_ARG, "spl_soa_upload4: segment %d has no name keys", k);
+    }
+    *out = nullptr;
+    DeviceReads *dev = nullptr;
+    const int rc = upload_native(c, n_seg, segs, &dev, max_end, xs, name_key);
+    if (rc) return rc;
+    spl_dsoa *h = new (std::nothrow) spl_dsoa();
+    if (!h) { free_device_reads(dev); return spl_set_error(SPL_ERR_NOMEM, "out of host memory"); }
+    h->reads = dev;
+    *out = h;
+    return SPL_OK;
+}
+
 extern "C" void spl_soa_free(spl_ctx *c, spl_dsoa *soa)
 {
     if (!soa) return;
@@ -3679,6 +3747,13 @@ extern "C" int spl_reads_has_strand(const spl_dreads *d, int *out)
 {
     if (!d || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_has_strand: null argument");
     *out = d->finished && d->fused && d->groups.size() == 1 && d->groups[0].src->xs ? 1 : 0;
+    return SPL_OK;
+}
+
+extern "C" int spl_reads_has_mate_keys(const spl_dreads *d, int *out)
+{
+    if (!d || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_has_mate_keys: null argument");
+    *out = d->finished && d->fused && d->groups.size() == 1 && d->groups[0].src->name_key ? 1 : 0;
     return SPL_OK;
 }
 
@@ -3752,6 +3827,7 @@ extern "C" void spl_reads_free(spl_ctx *c, spl_dreads *d)
     for (spl_dreads::Segment &seg : d->segs) devmem::put(seg.slab);
     for (spl_dreads::Group &g : d->groups) { devmem::put(g.slab); devmem::put(g.d_segs); free_device_reads(g.src); }
     devmem::put(d->ctl);
+    devmem::put(d->mates);
     delete d;
 }
 
@@ -4521,6 +4597,201 @@ extern "C" int spl_gene_count_rule_host(uint32_t flag, int32_t pos, const uint32
     if (const int rc = gene_maps_fit("spl_gene_count_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
     const uint32_t r = spl_gene_read_result(flag, (int64_t)pos, ops, n_ops, (int64_t)shift, stranded, spl_gene_map_flat{n_a, a_start, a_code}, spl_gene_map_flat{n_b, b_start, b_code});
     *result_out = r == SPL_GENE_NO_FEATURE ? -1 : r == SPL_GENE_AMBIGUOUS ? -2 : r == SPL_GENE_NOT_COUNTED ? -3 : (int64_t)r;
+    return SPL_OK;
+}
+
+// ---- mates and fragments (spl_mates.hip, spl_genecount.hip; the rule is spl_mate_rule.h) ---------------------------------------
+namespace {
+// The mate table of every segment of a finished, fused set whose arrays have name keys, made once (dr->mates, dr->mate_counts).
+int mates_of(spl_ctx *c, const spl_dreads *dr, const char *who)
+{
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "%s: the read set is not finished (spl_reads_finish)", who);
+    if (dr->segs.empty()) return SPL_OK;
+    if (!(dr->fused && dr->groups.size() == 1)) return spl_set_error(SPL_ERR_ARG, "%s needs a fused read set (all of it from one device decode or one spl_soa_upload)", who);
+    const spl_dreads::Group &g = dr->groups[0];
+    if (!g.src->name_key)
+        return spl_set_error(SPL_ERR_ARG, "%s: the reads have no name keys (spl_bam_set_mate_keys before the decode, or spl_soa_upload4)", who);
+    if (dr->mates) return SPL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int64_t most = 0;
+    for (const spl_dreads::Segment &seg : dr->segs) most = std::max<int64_t>(most, g.segs[seg.group_seg].n_reads);
+    if (most > 0xfffffff0LL) return spl_set_error(SPL_ERR_ARG, "%s: a segment of more than 2^32 reads", who);
+    void *table = nullptr;
+    HIP_TRY(devmem::get(&table, 4 * (size_t)std::max<int64_t>(g.src->n_rec, 1) + 64, 'b'));
+    struct Put { void *p; ~Put() { devmem::put(p); } } keep{table};
+    HIP_TRY(hipMemsetAsync(table, 0xff, 4 * (size_t)std::max<int64_t>(g.src->n_rec, 1), c->stream));
+    DevBuf d_counts, d_work, d_keys[2], d_index[2];
+    std::vector<unsigned long long> counts(SPL_MATE_COUNTERS * dr->segs.size(), 0ull);
+    HIP_TRY(d_counts.get(8 * counts.size(), c->stream));
+    HIP_TRY(hipMemsetAsync(d_counts.p, 0, 8 * counts.size(), c->stream));
+    HIP_TRY(d_work.get(spl_dev_sort_work_bytes((uint64_t)std::max<int64_t>(most, 1)), c->stream));
+    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+    const uint64_t *name_key = (const uint64_t *)g.src->name_key;
+    uint64_t cap = 0; // elements the two pairs of scratch arrays hold
+    for (size_t k = 0; k < dr->segs.size(); ++k) {
+        const spl_layout_seg &ls = g.segs[dr->segs[k].group_seg];
+        const int64_t n = ls.n_reads;
+        if (n <= 0) continue;
+        uint32_t *mate = (uint32_t *)table + ls.first;
+        unsigned long long *seg_counts = d_counts.as<unsigned long long>() + SPL_MATE_COUNTERS * k;
+        uint32_t n_pairable = 0;
+        {
+            // bytes: FLAG, POS, the two CIGAR offsets and the key of a read, and its mark
+            splprof::Scope prof("spl_mate_compact", c->stream, 30.0 * (double)n);
+            HIP_TRY((hipError_t)spl_dev_launch_mate_mark(&src, name_key, g.src->n_rec, ls.first, n, mate, c->stream));
+            HIP_TRY((hipError_t)spl_dev_launch_sort_scan(mate, (uint64_t)n, d_work.p, c->stream));
+            HIP_TRY(hipMemcpyAsync(&n_pairable, mate + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if ((int64_t)n_pairable > n) return spl_set_error(SPL_ERR_HIP, "%s: the scan of the pairable reads went wrong", who);
+            if (n_pairable > cap) {
+                for (int q = 0; q < 2; ++q) {
+                    d_keys[q].release(); d_index[q].release();
+                    HIP_TRY(d_keys[q].get(8 * (size_t)n_pairable, c->stream));
+                    HIP_TRY(d_index[q].get(4 * (size_t)n_pairable, c->stream));
+                }
+                cap = n_pairable;
+            }
+            if (n_pairable)
+                HIP_TRY((hipError_t)spl_dev_launch_mate_compact(&src, name_key, g.src->n_rec, ls.first, n, mate, d_keys[0].as<uint64_t>(), d_index[0].as<uint32_t>(), c->stream));
+            HIP_TRY(hipMemsetAsync(mate, 0xff, 4 * (size_t)n, c->stream));
+        }
+        counts[SPL_MATE_COUNTERS * k] = n_pairable;
+        if (!n_pairable) continue;
+        {
+            splprof::Scope prof("spl_mate_sort", c->stream, 8.0 * 2.0 * 12.0 * (double)n_pairable);
+            for (uint32_t pass = 0; pass < 8u; ++pass) { // (an even number: the sorted elements end where they began)
+                const int a = (int)(pass & 1u), b = a ^ 1;
+                HIP_TRY((hipError_t)spl_dev_launch_sort_pass(d_keys[a].as<uint64_t>(), d_index[a].as<uint32_t>(), n_pairable, 8u * pass, d_keys[b].as<uint64_t>(), d_index[b].as<uint32_t>(),
+                                                             d_work.p, c->stream));
+            }
+        }
+        {
+            splprof::Scope prof("spl_mate_pair_kernel", c->stream, 16.0 * (double)n_pairable);
+            HIP_TRY((hipError_t)spl_dev_launch_mate_pair(d_keys[0].as<uint64_t>(), d_index[0].as<uint32_t>(), (int64_t)n_pairable, src.flag + ls.first, n, mate, seg_counts, c->stream));
+        }
+    }
+    std::vector<unsigned long long> got(counts.size(), 0ull);
+    HIP_TRY(hipMemcpyAsync(got.data(), d_counts.p, 8 * got.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dr->mate_counts.assign(counts.size(), 0);
+    for (size_t k = 0; k < counts.size(); ++k) dr->mate_counts[k] = (int64_t)(k % SPL_MATE_COUNTERS == 0 ? counts[k] : got[k]);
+    dr->mates = (uint32_t *)table;
+    keep.p = nullptr;
+    return SPL_OK;
+}
+} // namespace
+
+// The mate table of segment `seg` (counted over the segments that have reads, in the order they were added) of a finished, fused read set with name keys: host_out (or null) gets a word per read of the
+// segment, counts (or null) the three counters of spl_mates.h.  The table is made at the first call and kept with the set.
+extern "C" int spl_mate_table(spl_ctx *c, const spl_dreads *dr, int seg, uint32_t *host_out, int64_t *counts)
+{
+    if (!c || !dr) return spl_set_error(SPL_ERR_ARG, "spl_mate_table: null argument");
+    if (const int rc = mates_of(c, dr, "spl_mate_table")) return rc;
+    if (dr->segs.empty() && seg >= 0) { // (a set without a read has no segment and no table)
+        if (counts) for (int k = 0; k < SPL_MATE_COUNTERS; ++k) counts[k] = 0;
+        return SPL_OK;
+    }
+    if (seg < 0 || (size_t)seg >= dr->segs.size()) return spl_set_error(SPL_ERR_ARG, "spl_mate_table: no segment %d", seg);
+    const spl_layout_seg &ls = dr->groups[0].segs[dr->segs[(size_t)seg].group_seg];
+    if (counts) for (int k = 0; k < SPL_MATE_COUNTERS; ++k) counts[k] = dr->mate_counts[SPL_MATE_COUNTERS * (size_t)seg + (size_t)k];
+    if (host_out && ls.n_reads > 0) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMemcpyAsync(host_out, dr->mates + ls.first, 4 * (size_t)ls.n_reads, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return SPL_OK;
+}
+
+// spl_gene_count per fragment: the arguments are spl_gene_count's; the set must have name keys.
+extern "C" int spl_gene_count_fragments(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
+                                        const uint32_t *b_code, int64_t n_genes, int64_t *inout)
+{
+    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_gene_count_fragments: null argument");
+    if (const int rc = gene_maps_fit("spl_gene_count_fragments", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
+    if (const int rc = mates_of(c, dr, "spl_gene_count_fragments")) return rc;
+    if (dr->segs.empty()) return SPL_OK;
+    const spl_dreads::Group &g = dr->groups[0];
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n_out = (size_t)n_genes + SPL_GENE_SPECIALS;
+    DevBuf d_out, d_as, d_ac, d_bs, d_bc;
+    HIP_TRY(d_out.get(8 * n_out, c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
+    if (n_a) {
+        HIP_TRY(d_as.get(4 * (size_t)n_a, c->stream));
+        HIP_TRY(d_ac.get(4 * (size_t)n_a, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_as.p, a_start, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_ac.p, a_code, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
+    }
+    if (n_b) {
+        HIP_TRY(d_bs.get(4 * (size_t)n_b, c->stream));
+        HIP_TRY(d_bc.get(4 * (size_t)n_b, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bs.p, b_start, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_bc.p, b_code, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
+    }
+    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+    for (const spl_dreads::Segment &seg : dr->segs) {
+        const spl_layout_seg &ls = g.segs[seg.group_seg];
+        if (ls.n_reads <= 0) continue;
+        // bytes: the per-read launch's, and a read's word of the mate table
+        splprof::Scope prof("spl_gene_count_fragments_kernel", c->stream, 14.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
+        const int rc = spl_dev_launch_gene_count_fragments(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_as.as<int32_t>(), d_ac.as<uint32_t>(), n_b,
+                                                           d_bs.as<int32_t>(), d_bc.as<uint32_t>(), (uint32_t)n_genes, dr->mates + ls.first, d_out.as<unsigned long long>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "gene count kernel launch (fragments): %s", hipGetErrorString((hipError_t)rc));
+    }
+    std::vector<unsigned long long> sums(n_out, 0ull);
+    HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
+    return SPL_OK;
+}
+
+// The key of a name: no GPU involved (test hook).
+extern "C" int spl_name_key_host(const uint8_t *bytes, int64_t len, uint64_t *out)
+{
+    if (!out || len < 0 || (len && !bytes)) return spl_set_error(SPL_ERR_ARG, "spl_name_key_host: null argument");
+    *out = spl_name_key(bytes, (uint64_t)len);
+    return SPL_OK;
+}
+
+// The mate table of one segment's host arrays by the rule header: the compaction and a stable sort here, the pair stage's body as the
+// kernel runs it.  No GPU involved (test hook).  counts: the three counters, or null.
+extern "C" int spl_mate_table_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint64_t *name_key, uint32_t *mate_out, int64_t *counts)
+{
+    if (n_reads < 0 || n_reads > 0xfffffff0LL || (n_reads && (!pos || !flag || !cig_off || !name_key || !mate_out))) return spl_set_error(SPL_ERR_ARG, "spl_mate_table_host: null argument");
+    std::vector<std::pair<uint64_t, uint32_t>> el;
+    for (int64_t r = 0; r < n_reads; ++r) {
+        mate_out[r] = SPL_MATE_NONE;
+        const uint32_t n_ops = cig_off[r + 1] > cig_off[r] ? cig_off[r + 1] - cig_off[r] : 0u;
+        if (spl_mate_pairable(flag[r], (int64_t)pos[r], n_ops, name_key[r])) el.push_back({spl_mate_sort_key(name_key[r], flag[r]), (uint32_t)r});
+    }
+    std::stable_sort(el.begin(), el.end(), [](const std::pair<uint64_t, uint32_t> &a, const std::pair<uint64_t, uint32_t> &b) { return a.first < b.first; });
+    std::vector<uint64_t> keys(el.size());
+    std::vector<uint32_t> index(el.size());
+    for (size_t j = 0; j < el.size(); ++j) { keys[j] = el[j].first; index[j] = el[j].second; }
+    int64_t paired = 0, lonely = 0;
+    for (size_t j = 0; j < el.size(); ++j) {
+        if (spl_mate_pair_element(keys.data(), index.data(), (int64_t)el.size(), (int64_t)j, mate_out, n_reads)) ++paired;
+        else if (!(flag[index[j]] & 0x8u)) ++lonely;
+    }
+    if (counts) { counts[0] = (int64_t)el.size(); counts[1] = paired; counts[2] = lonely; }
+    return SPL_OK;
+}
+
+// The fragment rule for every read of one segment's host arrays with its mate table: no GPU involved (test hook).  results_out[r]:
+// the gene's index, -1 no feature, -2 ambiguous, -3 not counted, -4 nothing (the read's leader counts the fragment).
+extern "C" int spl_gene_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint32_t *mate, int32_t shift,
+                                           int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
+                                           int64_t n_genes, int64_t *results_out)
+{
+    if (n_reads < 0 || (n_reads && (!pos || !flag || !cig_off || !mate || !results_out))) return spl_set_error(SPL_ERR_ARG, "spl_gene_fragment_rule_host: null argument");
+    if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_gene_fragment_rule_host: cigar is null");
+    if (const int rc = gene_maps_fit("spl_gene_fragment_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
+    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    const spl_gene_map_flat map_a{n_a, a_start, a_code}, map_b{n_b, b_start, b_code};
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const uint32_t v = spl_gene_fragment_result<spl_gene_ops_ptr>(reads, 0, n_reads, r, mate, (int64_t)shift, stranded, map_a, map_b);
+        results_out[r] = v == SPL_GENE_NO_FEATURE ? -1 : v == SPL_GENE_AMBIGUOUS ? -2 : v == SPL_GENE_NOT_COUNTED ? -3 : v == SPL_GENE_IDLE ? -4 : (int64_t)v;
+    }
     return SPL_OK;
 }
 

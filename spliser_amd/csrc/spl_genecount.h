@@ -23,6 +23,11 @@ uint32_t spl_dev_gene_grid(int64_t n);
 // 2 (rf): map a the '+' reads, map b the '-' reads.  n_rec / n_ops: the arrays' sizes, beyond which nothing is loaded.
 int spl_dev_launch_gene_count(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a, const int32_t *a_start,
                               const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, uint32_t n_genes, unsigned long long *counts, void *stream);
+// The same per FRAGMENT (spl_mate_rule.h): mate[r] = the mate of read first + r as an index within [0, n), or 0xFFFFFFFF (device
+// memory, n words: spl_mates.hip); a read whose mate has a lower index adds nothing.
+int spl_dev_launch_gene_count_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a,
+                                        const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, uint32_t n_genes,
+                                        const uint32_t *mate, unsigned long long *counts, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include "spl_genecount_rule.h"
 #include "spl_genecount_wave.h"
 #include "spl_genemap_dev.h" // DevMap, DevOps, levels
+#include "spl_mate_rule.h"   // the fragment's rule
 
 static_assert(splgene::NO_FEATURE == SPL_GENE_NO_FEATURE && splgene::AMBIGUOUS == SPL_GENE_AMBIGUOUS && splgene::NOT_COUNTED == SPL_GENE_NOT_COUNTED &&
                   splgene::IDLE == SPL_GENE_IDLE && splgene::SPECIALS == SPL_GENE_SPECIALS,
@@ -69,6 +70,36 @@ __global__ __launch_bounds__(SPL_GENE_TILE) void spl_gene_count_kernel(const spl
     if (t < SPL_GENE_SPECIALS && s_sum[t]) atomicAdd(&counts[(int64_t)n_genes + t], (unsigned long long)s_sum[t]);
 }
 
+// Fragments (spl_gene_count_fragments): the same launch over the segment with its mate table (spl_mates.hip) beside the arrays.
+// A lane whose read leads a fragment walks its own ops and then its mate's, wherever that read lies in the segment; the mate's lane
+// stays silent (SPL_GENE_IDLE), so the histogram is the per-read kernel's.  The rule is spl_gene_fragment_result.
+__global__ __launch_bounds__(SPL_GENE_TILE) void spl_gene_count_fragments_kernel(const spl_devreads src, int64_t n_ops_total, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a,
+                                                                                  const int32_t *a_start, const uint32_t *a_code, uint32_t a_stride, uint32_t a_top, int64_t n_b,
+                                                                                  const int32_t *b_start, const uint32_t *b_code, uint32_t b_stride, uint32_t b_top, uint32_t n_genes,
+                                                                                  const uint32_t *mate, unsigned long long *counts)
+{
+    __shared__ int32_t s_top[2 * SPL_GENE_TOP];
+    __shared__ uint32_t s_sum[SPL_GENE_SPECIALS];
+    const uint32_t t = threadIdx.x;
+    const uint32_t lane = wv::lane();
+    for (uint32_t j = t; j < a_top; j += SPL_GENE_TILE) s_top[j] = a_start[(int64_t)j * a_stride];
+    for (uint32_t j = t; j < b_top; j += SPL_GENE_TILE) s_top[SPL_GENE_TOP + j] = b_start[(int64_t)j * b_stride];
+    if (t < SPL_GENE_SPECIALS) s_sum[t] = 0u;
+    __syncthreads();
+    const DevMap map_a{s_top, a_top, a_stride, n_a, a_start, a_code}, map_b{s_top + SPL_GENE_TOP, b_top, b_stride, n_b, b_start, b_code};
+    const spl_mate_reads reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
+    uint32_t mine = 0; // (as in the per-read kernel)
+    for (int64_t base = (int64_t)blockIdx.x * SPL_GENE_TILE; base < n; base += (int64_t)gridDim.x * SPL_GENE_TILE) { // (uniform over the workgroup)
+        const int64_t r = base + t;
+        uint32_t result = SPL_GENE_IDLE;
+        if (r < n) result = spl_gene_fragment_result<DevOps>(reads, first, n, r, mate, (int64_t)shift, stranded, map_a, map_b);
+        splgene::wave_count(result, n_genes, reinterpret_cast<uint64_t *>(counts), mine);
+    }
+    if (lane < SPL_GENE_SPECIALS && mine) atomicAdd(&s_sum[lane], mine);
+    __syncthreads();
+    if (t < SPL_GENE_SPECIALS && s_sum[t]) atomicAdd(&counts[(int64_t)n_genes + t], (unsigned long long)s_sum[t]);
+}
+
 } // namespace
 
 extern "C" uint32_t spl_dev_gene_grid(int64_t n)
@@ -89,5 +120,21 @@ extern "C" int spl_dev_launch_gene_count(const spl_devreads *src, int64_t n_rec,
     levels(n_b, SPL_GENE_TOP, &b_stride, &b_top);
     hipLaunchKernelGGL(spl_gene_count_kernel, dim3(spl_dev_gene_grid(n)), dim3(SPL_GENE_TILE), 0, (hipStream_t)stream, *src, n_ops, first, n, shift, stranded, n_a, a_start, a_code, a_stride,
                        a_top, n_b, b_start, b_code, b_stride, b_top, n_genes, counts);
+    return (int)hipGetLastError();
+}
+
+extern "C" int spl_dev_launch_gene_count_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a,
+                                                   const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, uint32_t n_genes,
+                                                   const uint32_t *mate, unsigned long long *counts, void *stream)
+{
+    if (n <= 0) return 0;
+    if (!src || !counts || !mate || first < 0 || first + n > n_rec || stranded < 0 || stranded > 2 || n_genes > SPL_GENE_INDEX_MAX || n_a < 0 || (n_a && (!a_start || !a_code)) || n_b < 0 ||
+        (n_b && (!b_start || !b_code)))
+        return (int)hipErrorInvalidValue;
+    uint32_t a_stride, a_top, b_stride, b_top;
+    levels(n_a, SPL_GENE_TOP, &a_stride, &a_top);
+    levels(n_b, SPL_GENE_TOP, &b_stride, &b_top);
+    hipLaunchKernelGGL(spl_gene_count_fragments_kernel, dim3(spl_dev_gene_grid(n)), dim3(SPL_GENE_TILE), 0, (hipStream_t)stream, *src, n_ops, first, n, shift, stranded, n_a, a_start, a_code,
+                       a_stride, a_top, n_b, b_start, b_code, b_stride, b_top, n_genes, mate, counts);
     return (int)hipGetLastError();
 }

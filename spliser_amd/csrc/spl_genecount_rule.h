@@ -79,6 +79,18 @@ SPL_HD uint32_t spl_gene_of_blocks(const Ops &ops, uint32_t n_ops, int64_t p, co
     return fold.set == 0u ? SPL_GENE_NO_FEATURE : fold.set == SPL_GENE_MANY ? SPL_GENE_AMBIGUOUS : fold.set - 1u;
 }
 
+// The form that CONTINUES a set (a fragment's: spl_mate_rule.h): `set` as a fold has it -> the set with these blocks folded in.
+template <class Ops, class Map>
+SPL_HD uint32_t spl_gene_set_add_blocks(uint32_t set, const Ops &ops, uint32_t n_ops, int64_t p, const Map &map)
+{
+    spl_gene_fold<Map> fold{map, set};
+    int64_t covered = 0;
+    (void)spl_cov_walk(ops, n_ops, p, SPL_GENE_NO_LENGTH, fold, &covered);
+    return fold.set;
+}
+// What a finished set comes to.
+SPL_HD uint32_t spl_gene_result_of_set(uint32_t set) { return set == 0u ? SPL_GENE_NO_FEATURE : set == SPL_GENE_MANY ? SPL_GENE_AMBIGUOUS : set - 1u; }
+
 // Map b serves this read (stranded = 1 / 2 and a '-' read); map a every other.
 SPL_HD bool spl_gene_uses_b(uint32_t flag, int stranded) { return stranded != 0 && spl_read_strand(flag, stranded) == (uint8_t)'-'; }
 

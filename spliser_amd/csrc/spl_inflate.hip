@@ -8,6 +8,9 @@
 #include "spl_inflate.h"
 #include "spl_bam.h"
 #include "spl_bam_aux.h"
+#define SPL_MATE_KEY_ONLY // (the name key alone)
+#include "spl_mate_rule.h"
+#undef SPL_MATE_KEY_ONLY
 #include "spl_flagstat.h"
 #include "spl_wave.h"
 #include "spl_inflate_wave.h"
@@ -278,11 +281,14 @@ __global__ __launch_bounds__(FS_REDUCE_LANES) void spl_bam_flagstat_reduce_kerne
 // such a thing --, XS = true leaves one more byte per placed read: for a read whose own CIGAR holds an N op, which the op loop
 // sees anyway, the transcript strand of its aux area (spl_bam_aux.h; '+', '-' or 0); for every other read 0, without a byte of its
 // aux area being touched.  The area begins behind SEQ and QUAL -- l_seq is the second word of the h1 load -- and ends with the record.
-template <bool XS>
+// KEY (spl_bam_set_mate_keys) is the same bargain for the reads' names: KEY = false is the kernel as it was, KEY = true leaves the
+// name key of spl_mate_rule.h per placed read -- the l_read_name - 1 bytes that begin 36 bytes into the record, behind block_size,
+// walked byte by byte and no further than the record's end.
+template <bool XS, bool KEY = false>
 __device__ __forceinline__ void bam_extract_walk(const uint8_t *stream, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
                                                  const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out,
                                                  uint16_t *flag_out, uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out,
-                                                 unsigned long long *ref_max_end, const spl_bam_filter &filter, uint8_t *xs_out)
+                                                 unsigned long long *ref_max_end, const spl_bam_filter &filter, uint8_t *xs_out, uint64_t *key_out = nullptr)
 {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_blocks) return;
@@ -317,6 +323,7 @@ __device__ __forceinline__ void bam_extract_walk(const uint8_t *stream, int32_t 
             }
             if (XS) // (the scan has seen to it that SEQ and QUAL end inside the record, and the record inside the stream)
                 xs_out[i] = has_n ? spl_bam_aux_strand(cig + 4ull * n_cig + ((uint64_t)l_seq + 1ull) / 2ull + (uint64_t)l_seq, cig - 32 - l_name + bs) : (uint8_t)0;
+            if (KEY) key_out[i] = spl_name_key_bam(cig - l_name, l_name, cig - 32 - l_name + bs);
             o += n_cig;
             pos_out[i] = pos0 + 1;
             flag_out[i] = (uint16_t)flag;
@@ -358,10 +365,10 @@ __global__ __launch_bounds__(64) void spl_bam_extract_xs_kernel(const uint8_t *s
 // 64 records are read at once -- each lane its record's fixed fields and CIGAR, none waiting for the one before as the walk
 // above has to -- and written side by side: positions, flags and CIGAR offsets of consecutive records by consecutive lanes.
 // Where a record's ops go follows from a prefix sum over the lanes' op counts.
-template <bool XS>
+template <bool XS, bool KEY = false>
 __device__ __forceinline__ void bam_extract_wave(const uint8_t *stream, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan,
                                                  const uint16_t *recs, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out, uint16_t *flag_out,
-                                                 uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end, uint8_t *xs_out)
+                                                 uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end, uint8_t *xs_out, uint64_t *key_out = nullptr)
 {
     const uint32_t b = blockIdx.x;
     if (b >= n_blocks) return;
@@ -387,6 +394,7 @@ __device__ __forceinline__ void bam_extract_wave(const uint8_t *stream, const sp
             tid = (int32_t)h0.y; pos0 = (int32_t)h0.z;
             l_name = h0.w & 0xffu; n_cig = h1.x & 0xffffu; flag = h1.x >> 16;
             if (XS) { bs = h0.x; l_seq = h1.y; }
+            if (KEY) bs = h0.x;
         }
         // ops of the records before mine in this round
         uint32_t incl = n_cig;
@@ -410,6 +418,7 @@ __device__ __forceinline__ void bam_extract_wave(const uint8_t *stream, const sp
             }
             const uint64_t i = i0 + j;
             if (XS) xs_out[i] = has_n ? spl_bam_aux_strand(cig + 4ull * n_cig + ((uint64_t)l_seq + 1ull) / 2ull + (uint64_t)l_seq, r + 4 + bs) : (uint8_t)0;
+            if (KEY) key_out[i] = spl_name_key_bam(r + SPL_MATE_NAME_OFFSET, l_name, r + 4 + bs);
             pos_out[i] = pos0 + 1;
             flag_out[i] = (uint16_t)flag;
             tid_out[i] = tid;
@@ -454,6 +463,24 @@ __global__ __launch_bounds__(64) void spl_bam_extract_wave_xs_kernel(const uint8
                                                                       uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end, uint8_t *xs_out)
 {
     bam_extract_wave<true>(stream, blocks, n_blocks, scan, recs, rec_off, op_off, pos_out, flag_out, cig_off, cigar, tid_out, ref_max_end, xs_out);
+}
+
+// ... and the instantiations that leave the name keys (spl_bam_set_mate_keys), with the strand bytes or without
+template <bool XS>
+__global__ __launch_bounds__(64) void spl_bam_extract_keys_kernel(const uint8_t *stream, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
+                                                                   const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out, uint16_t *flag_out,
+                                                                   uint32_t *cig_off, uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end, spl_bam_filter filter,
+                                                                   uint8_t *xs_out, uint64_t *key_out)
+{
+    bam_extract_walk<XS, true>(stream, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off, op_off, pos_out, flag_out, cig_off, cigar, tid_out, ref_max_end, filter, xs_out, key_out);
+}
+
+template <bool XS>
+__global__ __launch_bounds__(64) void spl_bam_extract_wave_keys_kernel(const uint8_t *stream, const spl_zblock *blocks, uint32_t n_blocks, const spl_bscan *scan, const uint16_t *recs,
+                                                                        const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos_out, uint16_t *flag_out, uint32_t *cig_off,
+                                                                        uint32_t *cigar, int32_t *tid_out, unsigned long long *ref_max_end, uint8_t *xs_out, uint64_t *key_out)
+{
+    bam_extract_wave<XS, true>(stream, blocks, n_blocks, scan, recs, rec_off, op_off, pos_out, flag_out, cig_off, cigar, tid_out, ref_max_end, xs_out, key_out);
 }
 
 __global__ __launch_bounds__(256) void spl_bam_bounds_kernel(const int32_t *tid, const uint32_t *cig_off, uint64_t n, uint64_t *bounds, uint32_t *n_bounds, uint32_t cap)
@@ -517,6 +544,33 @@ extern "C" int spl_dev_launch_bam_extract(const uint8_t *stream, uint64_t stream
     const uint32_t L = 64;
     hipLaunchKernelGGL(spl_bam_extract_kernel, dim3((n_blocks + L - 1u) / L), dim3(L), 0, (hipStream_t)st, stream, stream_len, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off,
                        op_off, pos, flag, cig_off, cigar, tid, ref_max_end, spl_bam_filter{min_mapq, require_flags, exclude_flags});
+    return (int)hipGetLastError();
+}
+
+extern "C" int spl_dev_launch_bam_extract_keys(const uint8_t *stream, uint64_t stream_len, int32_t n_ref, int32_t tid_lo, int32_t tid_hi, const spl_zblock *blocks, uint32_t n_blocks,
+                                               const spl_bscan *scan, const uint64_t *rec_off, const uint64_t *op_off, int32_t *pos, uint16_t *flag, uint32_t *cig_off, uint32_t *cigar,
+                                               int32_t *tid, unsigned long long *ref_max_end, const uint16_t *recs, uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags,
+                                               uint8_t *xs, uint64_t *name_key, void *st)
+{
+    if (!name_key)
+        return spl_dev_launch_bam_extract(stream, stream_len, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off, op_off, pos, flag, cig_off, cigar, tid, ref_max_end, recs, min_mapq,
+                                          require_flags, exclude_flags, xs, st);
+    if (n_blocks == 0) return 0;
+    const spl_bam_filter filter{min_mapq, require_flags, exclude_flags};
+    if (recs) {
+        if (xs)
+            hipLaunchKernelGGL(spl_bam_extract_wave_keys_kernel<true>, dim3(n_blocks), dim3(64), 0, (hipStream_t)st, stream, blocks, n_blocks, scan, recs, rec_off, op_off, pos, flag, cig_off,
+                               cigar, tid, ref_max_end, xs, name_key);
+        else
+            hipLaunchKernelGGL(spl_bam_extract_wave_keys_kernel<false>, dim3(n_blocks), dim3(64), 0, (hipStream_t)st, stream, blocks, n_blocks, scan, recs, rec_off, op_off, pos, flag, cig_off,
+                               cigar, tid, ref_max_end, xs, name_key);
+    } else if (xs) {
+        hipLaunchKernelGGL(spl_bam_extract_keys_kernel<true>, dim3((n_blocks + 63u) / 64u), dim3(64), 0, (hipStream_t)st, stream, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off, op_off,
+                           pos, flag, cig_off, cigar, tid, ref_max_end, filter, xs, name_key);
+    } else {
+        hipLaunchKernelGGL(spl_bam_extract_keys_kernel<false>, dim3((n_blocks + 63u) / 64u), dim3(64), 0, (hipStream_t)st, stream, n_ref, tid_lo, tid_hi, blocks, n_blocks, scan, rec_off, op_off,
+                           pos, flag, cig_off, cigar, tid, ref_max_end, filter, xs, name_key);
+    }
     return (int)hipGetLastError();
 }
 

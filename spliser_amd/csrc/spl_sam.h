@@ -56,6 +56,12 @@ int spl_dev_launch_sam_extract(const uint8_t *text, uint64_t base, const uint32_
                                uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, const uint32_t *kept_end, const uint32_t *ops_end, const int32_t *line_tid,
                                uint64_t rec0, uint64_t op0, uint64_t cap_rec, uint64_t cap_ops, int32_t *pos, uint16_t *flag, int32_t *tid, uint32_t *cig_off, uint32_t *cigar,
                                uint8_t *xs, unsigned long long *ref_max_end, struct spl_sam_counts *counts, void *stream);
+// ... and with name_key: null (the call above), or one more array beside flag -- per kept line the key of its column 1
+// (spl_name_key_sam): the kernel's instantiation for spl_bam_set_mate_keys.
+int spl_dev_launch_sam_extract_keys(const uint8_t *text, uint64_t base, const uint32_t *line_start, uint32_t n_lines, uint64_t last_end, const struct spl_sam_names *names,
+                                    uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, const uint32_t *kept_end, const uint32_t *ops_end, const int32_t *line_tid,
+                                    uint64_t rec0, uint64_t op0, uint64_t cap_rec, uint64_t cap_ops, int32_t *pos, uint16_t *flag, int32_t *tid, uint32_t *cig_off, uint32_t *cigar,
+                                    uint8_t *xs, uint64_t *name_key, unsigned long long *ref_max_end, struct spl_sam_counts *counts, void *stream);
 // counts->unordered = 1 when (tid, pos) of any record in [first, first + n), first > 0: or of record first, is below its predecessor's
 int spl_dev_launch_sam_order(const int32_t *tid, const int32_t *pos, uint64_t first, uint64_t n, struct spl_sam_counts *counts, void *stream);
 // ---- for text that arrives without regard to lines (compressed SAM, spl_capi.cpp: SamZDecode) --------------------------------

@@ -142,11 +142,13 @@ __global__ __launch_bounds__(SPL_SAM_SCAN_LANES) void spl_sam_scan_kernel(const 
     }
 }
 
-__global__ __launch_bounds__(SPL_SAM_SCAN_LANES) void spl_sam_extract_kernel(const uint8_t *text, uint64_t base, const uint32_t *line_start, uint32_t n_lines, uint64_t last_end,
-                                                                              spl_sam_names names, spl_bam_filter filter, const uint32_t *kept_end, const uint32_t *ops_end,
-                                                                              const int32_t *line_tid, uint64_t rec0, uint64_t op0, uint64_t cap_rec, uint64_t cap_ops, int32_t *pos,
-                                                                              uint16_t *flag, int32_t *tid, uint32_t *cig_off, uint32_t *cigar, uint8_t *xs,
-                                                                              unsigned long long *ref_max_end, spl_sam_counts *counts)
+// (Written once with a template parameter, as the BAM extractions are: KEY = false is the kernel a file gets that nobody asked the
+//  name keys of -- spl_bam_set_mate_keys --, not a load, a branch or an argument more; KEY = true leaves the key of column 1 per read.)
+template <bool KEY>
+__device__ __forceinline__ void sam_extract_lines(const uint8_t *text, uint64_t base, const uint32_t *line_start, uint32_t n_lines, uint64_t last_end, const spl_sam_names &names,
+                                                  const spl_bam_filter &filter, const uint32_t *kept_end, const uint32_t *ops_end, const int32_t *line_tid, uint64_t rec0, uint64_t op0,
+                                                  uint64_t cap_rec, uint64_t cap_ops, int32_t *pos, uint16_t *flag, int32_t *tid, uint32_t *cig_off, uint32_t *cigar, uint8_t *xs,
+                                                  unsigned long long *ref_max_end, spl_sam_counts *counts, uint64_t *name_key)
 {
     const uint32_t i = blockIdx.x * SPL_SAM_SCAN_LANES + threadIdx.x;
     int32_t my_tid = -1;
@@ -172,6 +174,7 @@ __global__ __launch_bounds__(SPL_SAM_SCAN_LANES) void spl_sam_extract_kernel(con
                 flag[r] = (uint16_t)ln.flag;
                 tid[r] = ln.tid;
                 if (xs) xs[r] = ln.xs;
+                if (KEY) name_key[r] = spl_name_key_sam(p, end);
                 cig_off[r + 1u] = (uint32_t)(op0 + o1);
                 my_tid = ln.tid;
                 my_end = (long long)ln.end;
@@ -193,6 +196,26 @@ __global__ __launch_bounds__(SPL_SAM_SCAN_LANES) void spl_sam_extract_kernel(con
         if (wv::lane() == lead) atomicMax(&ref_max_end[t], (unsigned long long)m);
         if (mine) my_tid = -1;
     }
+}
+
+__global__ __launch_bounds__(SPL_SAM_SCAN_LANES) void spl_sam_extract_kernel(const uint8_t *text, uint64_t base, const uint32_t *line_start, uint32_t n_lines, uint64_t last_end,
+                                                                              spl_sam_names names, spl_bam_filter filter, const uint32_t *kept_end, const uint32_t *ops_end,
+                                                                              const int32_t *line_tid, uint64_t rec0, uint64_t op0, uint64_t cap_rec, uint64_t cap_ops, int32_t *pos,
+                                                                              uint16_t *flag, int32_t *tid, uint32_t *cig_off, uint32_t *cigar, uint8_t *xs,
+                                                                              unsigned long long *ref_max_end, spl_sam_counts *counts)
+{
+    sam_extract_lines<false>(text, base, line_start, n_lines, last_end, names, filter, kept_end, ops_end, line_tid, rec0, op0, cap_rec, cap_ops, pos, flag, tid, cig_off, cigar, xs,
+                             ref_max_end, counts, nullptr);
+}
+
+__global__ __launch_bounds__(SPL_SAM_SCAN_LANES) void spl_sam_extract_keys_kernel(const uint8_t *text, uint64_t base, const uint32_t *line_start, uint32_t n_lines, uint64_t last_end,
+                                                                                   spl_sam_names names, spl_bam_filter filter, const uint32_t *kept_end, const uint32_t *ops_end,
+                                                                                   const int32_t *line_tid, uint64_t rec0, uint64_t op0, uint64_t cap_rec, uint64_t cap_ops, int32_t *pos,
+                                                                                   uint16_t *flag, int32_t *tid, uint32_t *cig_off, uint32_t *cigar, uint8_t *xs,
+                                                                                   unsigned long long *ref_max_end, spl_sam_counts *counts, uint64_t *name_key)
+{
+    sam_extract_lines<true>(text, base, line_start, n_lines, last_end, names, filter, kept_end, ops_end, line_tid, rec0, op0, cap_rec, cap_ops, pos, flag, tid, cig_off, cigar, xs,
+                            ref_max_end, counts, name_key);
 }
 
 __global__ __launch_bounds__(256) void spl_sam_order_kernel(const int32_t *tid, const int32_t *pos, uint64_t first, uint64_t n, spl_sam_counts *counts)
@@ -295,6 +318,21 @@ extern "C" int spl_dev_launch_sam_extract(const uint8_t *text, uint64_t base, co
     hipLaunchKernelGGL(spl_sam_extract_kernel, dim3((n_lines + SPL_SAM_SCAN_LANES - 1u) / SPL_SAM_SCAN_LANES), dim3(SPL_SAM_SCAN_LANES), 0, (hipStream_t)st, text, base, line_start,
                        n_lines, last_end, *names, spl_bam_filter{min_mapq, require_flags, exclude_flags}, kept_end, ops_end, line_tid, rec0, op0, cap_rec, cap_ops, pos, flag, tid,
                        cig_off, cigar, xs, ref_max_end, counts);
+    return (int)hipGetLastError();
+}
+
+extern "C" int spl_dev_launch_sam_extract_keys(const uint8_t *text, uint64_t base, const uint32_t *line_start, uint32_t n_lines, uint64_t last_end, const spl_sam_names *names,
+                                               uint32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, const uint32_t *kept_end, const uint32_t *ops_end,
+                                               const int32_t *line_tid, uint64_t rec0, uint64_t op0, uint64_t cap_rec, uint64_t cap_ops, int32_t *pos, uint16_t *flag, int32_t *tid,
+                                               uint32_t *cig_off, uint32_t *cigar, uint8_t *xs, uint64_t *name_key, unsigned long long *ref_max_end, spl_sam_counts *counts, void *st)
+{
+    if (!name_key)
+        return spl_dev_launch_sam_extract(text, base, line_start, n_lines, last_end, names, min_mapq, require_flags, exclude_flags, kept_end, ops_end, line_tid, rec0, op0, cap_rec,
+                                          cap_ops, pos, flag, tid, cig_off, cigar, xs, ref_max_end, counts, st);
+    if (!n_lines) return 0;
+    hipLaunchKernelGGL(spl_sam_extract_keys_kernel, dim3((n_lines + SPL_SAM_SCAN_LANES - 1u) / SPL_SAM_SCAN_LANES), dim3(SPL_SAM_SCAN_LANES), 0, (hipStream_t)st, text, base, line_start,
+                       n_lines, last_end, *names, spl_bam_filter{min_mapq, require_flags, exclude_flags}, kept_end, ops_end, line_tid, rec0, op0, cap_rec, cap_ops, pos, flag, tid,
+                       cig_off, cigar, xs, ref_max_end, counts, name_key);
     return (int)hipGetLastError();
 }
 

@@ -19,6 +19,8 @@
 //   filter  spl_bam_filter_verdict on FLAG and MAPQ, flags first (spl_bam.h)
 //   strand  samio.sam_aux_strand: 0 unless the CIGAR holds an N; else the value of the first column from the 12th on that begins
 //           "XS:A:", if that value is exactly '+' or '-' followed by TAB or the line's end, else 0 ("XS:i:" is another field)
+//   name    where the decode was asked for name keys (spl_bam_set_mate_keys): spl_name_key_sam of the line, the key of column 1 --
+//           the bytes from the line's start to its first TAB -- by spl_mate_rule.h, taken by the caller for a line it extracts
 //
 // No byte at or beyond `end` is ever read: every load is preceded by the comparison that allows it.
 #ifndef SPL_SAM_LINE_H
@@ -26,6 +28,9 @@
 #include <stdint.h>
 
 #include "spl_bam.h"
+#define SPL_MATE_KEY_ONLY // (the name key alone: spl_name_key_sam, column 1 of a line the rule has taken)
+#include "spl_mate_rule.h"
+#undef SPL_MATE_KEY_ONLY
 
 // why a line (a file) is declined; 0 = the line is taken
 #define SPL_SAM_OK 0u

@@ -14,7 +14,8 @@ by features of two genes or more is shared and no bin.  Two abutting exons of on
 transcripts is one.  A read that ``genecounts`` gives to a gene adds one to EVERY bin one of its aligned blocks overlaps (each bin
 once, however many of its blocks lie in it); a read it calls ambiguous adds to no bin.  This is DEXSeq's counting
 (``dexseq_count.py``) and ``featureCounts -f -O`` restricted to reads of one gene, applied per READ: a paired fragment adds up to
-two per bin.  Fragment counting needs mate pairing, which the decode does not keep: out of scope.  Parity with DEXSeq and
+two per bin.  Fragment counting is out of scope here: a read's bins are committed each bin once, and a fragment needs that across both mates'
+walks -- the mate table of ``genecounts --fragments`` (``spl_mate_table``) is what a follow-up would use.  Parity with DEXSeq and
 featureCounts is intended and unpinned (neither is on the build machine): the yardstick is this statement of the rule, restated in
 tests/exoncases.py.
 """

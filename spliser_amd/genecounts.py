@@ -13,9 +13,21 @@ The rule.  A feature is a line of the GFF / GTF whose column 3 is ``-t`` (defaul
 and not supplementary, duplicates included; its aligned blocks (M, = and X; D and N are gaps) are held against the features: no
 gene under any base -> ``__no_feature``, one gene -> that gene, more -> ``__ambiguous``; every other read -> ``__not_counted``.
 With ``--isStranded -s fr|rf`` a read sees only the features of its strand (and those without one).  This is htseq-count's
-``--mode union --nonunique none``, and featureCounts' default, applied per READ: a paired fragment adds up to two.  Fragment counting
-needs mate pairing, which the decode does not keep: out of scope.  Parity with htseq-count and featureCounts is intended and
-unpinned (neither is on the build machine): the yardstick is this statement of the rule, restated in tests/genecases.py.
+``--mode union --nonunique none``, and featureCounts' default, applied per READ: a paired fragment adds up to two.  Parity with
+htseq-count and featureCounts is intended and unpinned (neither is on the build machine): the yardstick is this statement of the rule,
+restated in tests/genecases.py.
+
+``--fragments`` counts a paired-end library as htseq-count and ``featureCounts -p --countReadPairs`` do, a FRAGMENT once.  The decode
+then keeps a 64-bit key of every read's name (``mate_keys``), the mate table is built on the GPU per chromosome (``spl_mate_table``:
+the pairable reads sorted by key, mates found by binary search) and ``spl_gene_count_fragments`` holds both mates' blocks against the
+features, each mate on the map of its own strand: no gene -> ``__no_feature``, one -> that gene, more -> ``__ambiguous``.  A read is
+pairable when it counts at all, is paired (0x1), is first or second in its pair (one of 0x40 / 0x80) and has a name; among the pairable
+reads of one chromosome with one name the j-th first and the j-th second read are mates.  The rows then sum to reads minus pairs.
+Deliberate differences from the tools: a pair split over two chromosomes, or with one mate filtered out (``--minMapQ``, the flag
+filters), counts as two single-end fragments; names are compared by a 63-bit hash (two fragments of a chromosome may swap mates
+where two names collide: about n^2 / 2^64 pairs for n names, 5e-6 for 10 M).  Parity with htseq-count and ``featureCounts -p`` is
+intended and unpinned: the yardstick is tests/matecases.py.  With several devices the file is decoded and counted on the first
+one: mates can lie either side of a share's cut.
 """
 import sys
 
@@ -160,12 +172,13 @@ def maps_of(features, chroms, stranded=False):
     return out
 
 
-def over_fused_sets(source, devices, chroms, visit):
+def over_fused_sets(source, devices, chroms, visit, with_keys=False):
     """The plan both counting commands run a source by (``strandedness.tally_of_source``'s): ``visit(dr, chrom)`` for a finished, fused
     read set per chromosome of ``chroms`` -- called from one thread per device, so it guards what it adds to.  A file decoded on the
     device is visited per chromosome where it lies (the sets stay fused); after a decode in shares every device visits its piece of a
     chromosome -- what the visits add must add over reads; host-decoded reads and the Python reader's go up as four arrays
-    (``upload_soa``), a fused set of their own.  The first exception of a visit is raised when all have ended."""
+    (``upload_soa``), a fused set of their own -- ``with_keys``: with their name keys, which the source must have.  The first exception
+    of a visit is raised when all have ended."""
     import threading
     is_bam = isinstance(source, native.BamFile)
     errors, lock = [], threading.Lock()
@@ -180,7 +193,10 @@ def over_fused_sets(source, devices, chroms, visit):
                         rs = source.reads(chrom)
                         if rs is None or not rs.n:
                             continue
-                        with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar)], [getattr(rs, "max_end", None)]) as soa:
+                        if with_keys and getattr(rs, "name_key", None) is None:
+                            raise native.SpliserNativeError(-1, "the reads of %s were decoded without name keys (mate_keys)" % chrom)
+                        arrays = native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, name_key=rs.name_key if with_keys else None)
+                        with ctx.upload_soa([arrays], [getattr(rs, "max_end", None)], with_keys=with_keys) as soa:
                             with ctx.begin_reads() as dr:
                                 dr.add_soa(soa, 0)
                                 dr.finish()
@@ -212,26 +228,44 @@ def over_fused_sets(source, devices, chroms, visit):
         raise errors[0]
 
 
-def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None):
+def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None, fragments=False, mates=None):
     """``spl_gene_count`` over every chromosome of ``chroms`` -> int64[n_genes + 3], the sums: the genes' reads, then no feature,
     ambiguous, not counted.  On the plan of ``over_fused_sets``: counts add over reads, so the pieces of a decode in shares are counted
     where they lie and the host adds.  ``maps``: {chrom: (map a, map b)} (``maps_of``); a chromosome without one has no feature.
-    ``per_chrom``: a dict that gets, per chromosome with reads, int64[4]: counted, no feature, ambiguous, not counted."""
+    ``per_chrom``: a dict that gets, per chromosome with reads, int64[4]: counted, no feature, ambiguous, not counted.
+    ``fragments``: ``spl_gene_count_fragments`` -- a pair of mates counts once; the source was decoded with ``mate_keys`` and not in
+    shares (an error otherwise).  ``mates``: a dict that then gets, per chromosome with reads, int64[4]: reads, pairable reads, reads
+    with a mate, pairable reads without one whose flag says the mate is mapped."""
     import threading
     n_genes = int(n_genes)
     total, lock = np.zeros(n_genes + 3, np.int64), threading.Lock()
+    if fragments and not getattr(source, "mate_keys", False):
+        raise native.SpliserNativeError(-1, "fragment counting needs a source decoded with name keys (DecodeOptions.mate_keys)")
+    if fragments and getattr(source, "shares", None):
+        raise native.SpliserNativeError(-1, "fragment counting needs the file decoded on one device: mates can lie either side of a share's cut")
 
     def count(dr, chrom):
         a, b = maps.get(chrom, (None, None))
-        t = dr.gene_counts(n_genes, a, b, stranded)
+        t = dr.gene_counts(n_genes, a, b, stranded, fragments=fragments)
+        stats = dr.mate_table(0)[1] if fragments and mates is not None else None
         with lock:
+            if stats is not None:
+                row = mates.setdefault(chrom, np.zeros(4, np.int64))
+                row += [dr.n, stats["pairable"], stats["paired"], stats["unpaired_mate_mapped"]]
             total[:] += t
             if per_chrom is not None:
                 row = per_chrom.setdefault(chrom, np.zeros(4, np.int64))
                 row += [int(t[:n_genes].sum()), int(t[n_genes]), int(t[n_genes + 1]), int(t[n_genes + 2])]
 
-    over_fused_sets(source, devices, chroms, count)
+    over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments))
     return total
+
+
+def mates_line(row):
+    """reads, pairable, paired, unpaired with a mapped mate -> the log's words."""
+    reads, pairable, paired, lonely = (int(v) for v in row)
+    return ("%d reads, %d pairable, %d pairs, %d pairable reads without a mate on their chromosome (%d of them with a mapped mate by their flag)"
+            % (reads, pairable, paired // 2, pairable - paired, lonely))
 
 
 def write_counts(path, ids, counts, only=None):
@@ -248,9 +282,10 @@ def write_counts(path, ids, counts, only=None):
 
 
 def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id", qChrom="All", isStranded=False, strandedType=None, devices=(0,), threads=0, log=None,
-               gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False):
+               gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False, fragments=False):
     """The ``genecounts`` command: one decode, the annotation read meanwhile, ``<outputPath>.genecounts.tsv``.  ``qChrom``: the reads
-    of that chromosome, and the genes with a feature on it.  -> int64[n_genes + 3], the counts written."""
+    of that chromosome, and the genes with a feature on it.  ``fragments``: a pair of mates counts once (the module's text); the
+    file's format is the same.  -> int64[n_genes + 3], the counts written."""
     import timeit
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
     if annotationFile is None:
@@ -259,7 +294,10 @@ def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
         raise ValueError("genecounts: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
     stranded = STRANDED[strandedType] if isStranded else 0
     devices = tuple(devices)
-    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder))
+    if fragments and len(devices) > 1:
+        log("  (--fragments: the alignment file is decoded and counted on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
+        devices = devices[:1]
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(fragments))
     source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
     try:
         t0 = timeit.default_timer()
@@ -273,11 +311,16 @@ def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
             _process.log_any_order(source, log)
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
         maps = maps_of(features, chroms, stranded)
-        per_chrom = {}
-        counts = counts_of_source(source, devices, chroms, maps, n_genes, stranded, per_chrom)
+        per_chrom, mates = {}, ({} if fragments else None)
+        counts = counts_of_source(source, devices, chroms, maps, n_genes, stranded, per_chrom, fragments=bool(fragments), mates=mates)
+        what = "fragments" if fragments else "reads"
         for chrom in chroms:
             if chrom in per_chrom:
-                log("  %s: %d reads counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom,) + tuple(int(v) for v in per_chrom[chrom])))
+                log("  %s: %d %s counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom, int(per_chrom[chrom][0]), what) + tuple(int(v) for v in per_chrom[chrom][1:])))
+            if fragments and chrom in mates:
+                log("  %s: %s" % (chrom, mates_line(mates[chrom])))
+        if fragments:
+            log("  mates: %s" % mates_line(sum(mates.values(), np.zeros(4, np.int64))))
         _process.log_filter(source, options.read_filter, log)
     finally:
         if hasattr(source, "close"):
@@ -285,6 +328,6 @@ def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
     only = None if qChrom == "All" else features.genes_on(qChrom)
     path = outputPath + SUFFIX
     n_rows = write_counts(path, features.ids, counts, only)
-    log("%s: %d genes, %d reads counted, %d without a feature, %d ambiguous, %d not counted" % (path, n_rows, int(counts[:n_genes].sum()), int(counts[n_genes]),
-                                                                                               int(counts[n_genes + 1]), int(counts[n_genes + 2])))
+    log("%s: %d genes, %d %s counted, %d without a feature, %d ambiguous, %d not counted" % (path, n_rows, int(counts[:n_genes].sum()), "fragments" if fragments else "reads",
+                                                                                             int(counts[n_genes]), int(counts[n_genes + 1]), int(counts[n_genes + 2])))
     return counts

@@ -49,11 +49,11 @@ EXPORTS = [
     "spl_abi_version", "spl_last_error", "spl_device_count", "spl_trim", "spl_create", "spl_create_on_stream", "spl_destroy",
     "spl_sync", "spl_pass_barrier", "spl_timer_begin", "spl_timer_end", "spl_kernel_timing_begin", "spl_kernel_timing_collect", "spl_prof_enable", "spl_prof_report", "spl_count", "spl_sse", "spl_sites_upload", "spl_sites_free",
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
-    "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_reads_has_strand", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes", "spl_reads_slots_download",
+    "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_soa_upload4", "spl_reads_has_strand", "spl_reads_has_mate_keys", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes", "spl_reads_slots_download",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
-    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
+    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_set_mate_keys", "spl_bam_mate_keys", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -153,10 +153,12 @@ class SiteArrays(object):
 
 
 class ReadArrays(object):
-    """``xs``: None, or a strand byte per read ('+', '-', 0) for ``Context.upload_soa`` (``spl_soa_upload3``); no other call reads it."""
+    """``xs``: None, or a strand byte per read ('+', '-', 0) for ``Context.upload_soa`` (``spl_soa_upload3``); ``name_key``: None, or a
+    name key per read (uint64, 0 = no name) for ``Context.upload_soa`` (``spl_soa_upload4``); no other call reads them."""
 
-    def __init__(self, pos, flag, cig_off, cigar, xs=None):
+    def __init__(self, pos, flag, cig_off, cigar, xs=None, name_key=None):
         self.xs = None if xs is None else _arr(xs, np.uint8)
+        self.name_key = None if name_key is None else _arr(name_key, np.uint64)
         self.pos = _to_i32(pos, "read position")
         self.flag = _arr(flag, np.uint16)
         self.cig_off = _arr(cig_off, np.uint32)
@@ -166,6 +168,8 @@ class ReadArrays(object):
             raise ValueError("cig_off must have n_reads + 1 entries")
         if self.xs is not None and self.xs.shape[0] != self.n:
             raise ValueError("xs must have n_reads entries")
+        if self.name_key is not None and self.name_key.shape[0] != self.n:
+            raise ValueError("name_key must have n_reads entries")
         self.c = spl_reads(self.n, _ptr(self.pos), _ptr(self.flag), _ptr(self.cig_off), _ptr(self.cigar))
 
 
@@ -252,21 +256,28 @@ class Context(object):
         _check(lib().spl_reads_upload_segments(self._h, ctypes.c_int(n), segs, shifts, ctypes.byref(h)))
         return DeviceReads(self, h, total)
 
-    def upload_soa(self, segments, max_ends=None, with_strand=False):
+    def upload_soa(self, segments, max_ends=None, with_strand=False, with_keys=False):
         """segments: [ReadArrays-like with .c] -> the BAM-native arrays as they are, laid end to end in device memory
         (``spl_soa_upload``): what a decode on the device leaves.  Read sets are laid out from them by the layout kernel
         (``DeviceReads.add_soa`` + ``finish``; ``relayout``).  ``max_ends``: per segment the last base its reads cover, if known.
-        ``with_strand``: every segment's ``xs`` goes up as a fifth array (``spl_soa_upload3``), for ``junctions(STRAND_FROM_XS)``."""
+        ``with_strand``: every segment's ``xs`` goes up as a fifth array (``spl_soa_upload3``), for ``junctions(STRAND_FROM_XS)``.
+        ``with_keys``: every segment's ``name_key`` goes up beside it (``spl_soa_upload4``), for ``mate_table`` and
+        ``gene_counts(fragments=True)``."""
         n = len(segments)
         segs = (spl_reads * max(n, 1))()
         for k, reads in enumerate(segments):
             segs[k] = reads.c
         h = ctypes.c_void_p()
         ends = None if max_ends is None else (ctypes.c_int64 * max(n, 1))(*[int(v) if v is not None else -1 for v in max_ends])
-        if with_strand:
-            if any(r.xs is None for r in segments):
-                raise ValueError("upload_soa(with_strand=True): every segment needs its xs array")
-            xs = (ctypes.c_void_p * max(n, 1))(*[r.xs.ctypes.data for r in segments])
+        if with_strand and any(r.xs is None for r in segments):
+            raise ValueError("upload_soa(with_strand=True): every segment needs its xs array")
+        xs = (ctypes.c_void_p * max(n, 1))(*[r.xs.ctypes.data for r in segments]) if with_strand else None
+        if with_keys:
+            if any(getattr(r, "name_key", None) is None for r in segments):
+                raise ValueError("upload_soa(with_keys=True): every segment needs its name_key array")
+            keys = (ctypes.c_void_p * max(n, 1))(*[r.name_key.ctypes.data for r in segments])
+            _check(lib().spl_soa_upload4(self._h, ctypes.c_int(n), segs, ends, xs, keys, ctypes.byref(h)))
+        elif with_strand:
             _check(lib().spl_soa_upload3(self._h, ctypes.c_int(n), segs, ends, xs, ctypes.byref(h)))
         else:
             _check(lib().spl_soa_upload2(self._h, ctypes.c_int(n), segs, ends, ctypes.byref(h)))
@@ -417,6 +428,23 @@ class DeviceReads(object):
         _check(lib().spl_reads_has_strand(self._h, ctypes.byref(out)))
         return bool(out.value)
 
+    def has_mate_keys(self):
+        """True when the (finished) set is fused and its device arrays include the reads' name keys: what ``mate_table`` and
+        ``gene_counts(fragments=True)`` need (a decode with ``mate_keys``, ``upload_soa(with_keys=True)``)."""
+        out = ctypes.c_int(0)
+        _check(lib().spl_reads_has_mate_keys(self._h, ctypes.byref(out)))
+        return bool(out.value)
+
+    def mate_table(self, seg, n_reads=None):
+        """The mate table of segment ``seg`` of this (finished, fused) set with name keys, made on the device (``spl_mate_table``) ->
+        (mate uint32[reads of the segment]: the mate's index within the segment or 0xFFFFFFFF, counts: dict of pairable, paired,
+        unpaired_mate_mapped).  ``seg`` counts the segments that have reads, in the order they were added.  ``n_reads``: the
+        segment's reads (asked of nobody: the caller added it); None: counts only."""
+        counts = np.zeros(3, np.int64)
+        mate = None if n_reads is None else np.empty(max(int(n_reads), 1), np.uint32)
+        _check(lib().spl_mate_table(self.ctx._h, self._h, ctypes.c_int(int(seg)), _ptr(mate), _ptr(counts)))
+        return (None if mate is None else mate[:int(n_reads)]), dict(zip(MATE_COUNTS, counts.tolist()))
+
     def junctions_stats(self):
         """-> (bytes of the device table the last ``junctions`` call on this context allocated, device ms of its launches or -1)."""
         b, ms = ctypes.c_int64(0), ctypes.c_float(-1.0)
@@ -503,20 +531,22 @@ class DeviceReads(object):
             lib().spl_coverage_free(self.ctx._h, h)
         return start, end, depth, dict(zip(COVERAGE_TOTALS, t.tolist()))
 
-    def gene_counts(self, n_genes, map_a, map_b=None, stranded=0, out=None):
+    def gene_counts(self, n_genes, map_a, map_b=None, stranded=0, out=None, fragments=False):
         """Per-gene read counts of this (finished, fused) set, on the device (``spl_gene_count``): ADDS to ``out`` (int64[n_genes + 3];
         made when None) and returns it -- the genes' reads, then no feature, ambiguous, not counted.  ``map_a`` / ``map_b``: gene maps
         ``(start int32, code uint32)`` in the set's coordinates (``genecounts.gene_maps``) or None; ``stranded``: 0 (``map_a`` serves
-        every read), 1 (fr) or 2 (rf): ``map_a`` serves the ``+`` reads, ``map_b`` the ``-`` reads."""
+        every read), 1 (fr) or 2 (rf): ``map_a`` serves the ``+`` reads, ``map_b`` the ``-`` reads.  ``fragments``: a pair of mates
+        (``mate_table``) counts once, by both mates' blocks (``spl_gene_count_fragments``; the set needs name keys)."""
         n_genes = int(n_genes)
         if out is None:
             out = np.zeros(max(n_genes, 0) + 3, np.int64)
         if not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.shape == (n_genes + 3,) and out.flags.c_contiguous):
             raise ValueError("gene counts are a contiguous int64 array of n_genes + 3 entries")
         (a_start, a_code), (b_start, b_code) = _gene_map_arrays(map_a), _gene_map_arrays(map_b)
-        _check(lib().spl_gene_count(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]), _ptr(a_start) if a_start.shape[0] else None,
-                                    _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
-                                    _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_genes), _ptr(out)))
+        entry = lib().spl_gene_count_fragments if fragments else lib().spl_gene_count
+        _check(entry(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]), _ptr(a_start) if a_start.shape[0] else None,
+                    _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
+                    _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_genes), _ptr(out)))
         return out
 
     def exon_counts(self, bin_gene, map_a, map_b=None, stranded=0, out=None):
@@ -732,14 +762,15 @@ class BamFile(object):
     ``wait_ref`` returns at the end of the decode; ``any_order_sorted()`` says what that took."""
 
     def __init__(self, path, threads=0, stream=False, defer=False, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False, flagstat=False,
-                 any_order=False):
+                 any_order=False, mate_keys=False):
         self._h = ctypes.c_void_p()
-        self.filter, self.aux_strand, self.counts_flagstat, self.any_order = (0, 0, 0), False, False, False
+        self.filter, self.aux_strand, self.counts_flagstat, self.any_order, self.mate_keys = (0, 0, 0), False, False, False, False
         # what was asked for must be there before the decode starts: such a file is opened deferred, set up and started below
         options = [(self.set_filter, (int(min_mapq), int(require_flags), int(exclude_flags)), (0, 0, 0)),
                    (self.set_aux_strand, (bool(aux_strand),), (False,)),
                    (self.set_flagstat, (bool(flagstat),), (False,)),
-                   (self.set_any_order, (bool(any_order),), (False,))]
+                   (self.set_any_order, (bool(any_order),), (False,)),
+                   (self.set_mate_keys, (bool(mate_keys),), (False,))]
         asked = [(setter, args) for setter, args, default in options if args != default]
         opener = self._opener(defer or bool(asked), stream)
         _check(opener(os.fsencode(path), ctypes.c_int(threads), ctypes.byref(self._h)))
@@ -776,6 +807,13 @@ class BamFile(object):
         a read set of the device decode ``has_strand()``."""
         _check(lib().spl_bam_set_aux_strand(self._h, ctypes.c_int(1 if on else 0)))
         self.aux_strand = bool(on)
+
+    def set_mate_keys(self, on=True):
+        """A ``defer=True`` file nobody decodes yet: the decode -- whoever does it -- also leaves a name key per placed read
+        (``spl_bam_set_mate_keys``; an error afterwards): which two records are mates.  ``reads(chrom).name_key`` has them, a read
+        set of the device decode ``has_mate_keys()``."""
+        _check(lib().spl_bam_set_mate_keys(self._h, ctypes.c_int(1 if on else 0)))
+        self.mate_keys = bool(on)
 
     def set_flagstat(self, on=True):
         """A ``defer=True`` file nobody decodes yet: the decode -- whoever does it -- also counts the flagstat categories
@@ -989,6 +1027,11 @@ class BamFile(object):
             xp = ctypes.c_void_p()
             _check(lib().spl_bam_aux_strand(self._h, ctypes.c_int(tid), ctypes.byref(xp)))
             rs.xs = view(xp.value, n, np.uint8) if xp.value else None
+        rs.name_key = None
+        if self.mate_keys:
+            kp = ctypes.c_void_p()
+            _check(lib().spl_bam_mate_keys(self._h, ctypes.c_int(tid), ctypes.byref(kp)))
+            rs.name_key = view(kp.value, n, np.uint64) if kp.value else None
         self._views[chrom] = rs
         return rs
 
@@ -1026,9 +1069,9 @@ class SamFile(BamFile):
     (``bgzip``, ``samtools view -O sam,level=6``) or as plain gzip (``gzip``, several members too): ``compression`` says which."""
 
     def __init__(self, path, threads=0, stream=False, defer=True, min_mapq=0, require_flags=0, exclude_flags=0, aux_strand=False, flagstat=False,
-                 any_order=True):
+                 any_order=True, mate_keys=False):
         BamFile.__init__(self, path, threads=threads, stream=True, defer=True, min_mapq=min_mapq, require_flags=require_flags, exclude_flags=exclude_flags,
-                         aux_strand=aux_strand, flagstat=flagstat)
+                         aux_strand=aux_strand, flagstat=flagstat, mate_keys=mate_keys)
         self.any_order = True     # (the native side's default for text, whatever was passed)
 
     @staticmethod
@@ -1163,6 +1206,45 @@ def gene_count_rule_host(flag, pos, ops, n_genes, map_a, map_b=None, stranded=0,
                                           _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
                                           _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(int(n_genes)), ctypes.byref(out)))
     return out.value
+
+
+MATE_NONE = 0xFFFFFFFF                 # a mate table's word for a read without a mate
+MATE_COUNTS = ("pairable", "paired", "unpaired_mate_mapped")          # spl_mate_table's three counters (paired: twice the pairs)
+
+
+def name_key_host(name):
+    """The name key of ``name`` (bytes) by the library's rule header (``spl_name_key_host``): 0 = no name."""
+    name = bytes(name)
+    buf = (ctypes.c_uint8 * max(len(name), 1)).from_buffer_copy(name.ljust(1, b"\0"))
+    out = ctypes.c_uint64(0)
+    _check(lib().spl_name_key_host(buf, ctypes.c_int64(len(name)), ctypes.byref(out)))
+    return out.value
+
+
+def mate_table_host(reads, name_key):
+    """The mate table of one segment's host arrays (``ReadArrays``-like) by the rule header on the host (``spl_mate_table_host``) ->
+    (mate uint32[n], counts dict)."""
+    name_key = _arr(name_key, np.uint64)
+    if name_key.shape[0] != reads.n:
+        raise ValueError("name_key must have n_reads entries")
+    mate, counts = np.empty(max(reads.n, 1), np.uint32), np.zeros(3, np.int64)
+    _check(lib().spl_mate_table_host(ctypes.c_int64(reads.n), _ptr(reads.pos), _ptr(reads.flag), _ptr(reads.cig_off), _ptr(name_key), _ptr(mate), _ptr(counts)))
+    return mate[:reads.n], dict(zip(MATE_COUNTS, counts.tolist()))
+
+
+def gene_fragment_rule_host(reads, mate, n_genes, map_a, map_b=None, stranded=0, shift=0):
+    """The fragment rule for every read of one segment's host arrays with its mate table (``spl_gene_fragment_rule_host``) ->
+    int64[n]: the gene's index, -1 no feature, -2 ambiguous, -3 not counted, -4 nothing (the read's leader counts the fragment)."""
+    mate = _arr(mate, np.uint32)
+    if mate.shape[0] != reads.n:
+        raise ValueError("mate must have n_reads entries")
+    (a_start, a_code), (b_start, b_code) = _gene_map_arrays(map_a), _gene_map_arrays(map_b)
+    out = np.zeros(max(reads.n, 1), np.int64)
+    _check(lib().spl_gene_fragment_rule_host(ctypes.c_int64(reads.n), _ptr(reads.pos), _ptr(reads.flag), _ptr(reads.cig_off), _ptr(reads.cigar) if reads.cigar.shape[0] else None,
+                                             _ptr(mate), ctypes.c_int32(int(shift)), ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]),
+                                             _ptr(a_start) if a_start.shape[0] else None, _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]),
+                                             _ptr(b_start) if b_start.shape[0] else None, _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(int(n_genes)), _ptr(out)))
+    return out[:reads.n]
 
 
 EXON_SPECIALS = ("__no_feature", "__ambiguous", "__not_counted")      # the rows behind the bins' (the counted reads are no row)

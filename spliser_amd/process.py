@@ -49,9 +49,10 @@ def read_filter(minMapQ=0, requireFlags=0, excludeFlags=0):
 # What a command asks of the decode of its alignment file, one immutable record from the command's keywords down to where the file
 # is opened (``open_alignments``): ``read_filter`` as above; ``aux_strand``: a strand byte per read, the XS:A tag of the spliced ones
 # (``--strandFromXS``); ``flagstat``: the decode counts the flagstat categories (``--flagstat``); ``any_order``: the BAM's records
-# may come in any order, the decoder sorts them (``--anyOrder``).  ``DecodeOptions()`` is what no flag gives.  A new decode switch
+# may come in any order, the decoder sorts them (``--anyOrder``); ``mate_keys``: a name key per read, which says which two records
+# are mates (``genecounts --fragments``).  ``DecodeOptions()`` is what no flag gives.  A new decode switch
 # is one field here (and one in csrc/spl_bam.h's spl_bam_decode_opts, one setter).
-DecodeOptions = collections.namedtuple("DecodeOptions", "read_filter aux_strand flagstat any_order", defaults=(NO_FILTER, False, False, False))
+DecodeOptions = collections.namedtuple("DecodeOptions", "read_filter aux_strand flagstat any_order mate_keys", defaults=(NO_FILTER, False, False, False, False))
 
 
 def log_filter(source, filt, log, name=None):
@@ -69,7 +70,8 @@ class _SamSource(object):
     def __init__(self, path, options=DecodeOptions()):
         self._counts = [0, 0, 0]
         self.aux_strand = bool(options.aux_strand)
-        self.ref_names, self._sets = samio.read_sam(path, *options.read_filter, counts=self._counts, aux_strand=options.aux_strand)
+        self.mate_keys = bool(options.mate_keys)
+        self.ref_names, self._sets = samio.read_sam(path, *options.read_filter, counts=self._counts, aux_strand=options.aux_strand, mate_keys=options.mate_keys)
         self.n_records = self._counts[0]
 
     def reads(self, chrom):
@@ -99,14 +101,15 @@ def open_alignments(path, threads=0, stream=False, defer=False, options=DecodeOp
     if magic[:2] == b"\x1f\x8b" and not packed_text:
         q, f, F = options.read_filter
         return native.BamFile(path, threads=threads, stream=stream, defer=defer, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=options.aux_strand,
-                              flagstat=options.flagstat, any_order=options.any_order)
+                              flagstat=options.flagstat, any_order=options.any_order, mate_keys=options.mate_keys)
     is_sam = packed_text or magic[:1] == b"@" or b"\t" in open(path, "rb").readline()
     if is_sam and defer:
         # the aligner's text parsed natively (on the GPU by ``SamFile.decode_on_device``): counters, kept reads and all.  A header
         # the native reader does not take (no @SQ / LN, a repeated name) is the Python reader's, as any SAM text was
         try:
             q, f, F = options.read_filter
-            return native.SamFile(path, threads=threads, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=options.aux_strand, flagstat=options.flagstat)
+            return native.SamFile(path, threads=threads, min_mapq=q, require_flags=f, exclude_flags=F, aux_strand=options.aux_strand, flagstat=options.flagstat,
+                                  mate_keys=options.mate_keys)
         except native.SpliserNativeError as exc:
             if exc.code != -5:
                 raise

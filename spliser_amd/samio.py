@@ -16,7 +16,7 @@ import zlib
 
 import numpy as np
 
-__all__ = ["ReadSet", "read_sam", "write_bam", "write_sam", "cigar_ops", "cigar_string", "OP_CODES"]
+__all__ = ["ReadSet", "read_sam", "write_bam", "write_sam", "cigar_ops", "cigar_string", "name_key", "OP_CODES"]
 
 OP_CODES = "MIDNSHP=XB"
 _CIGAR_RE = re.compile(r"(\d+)([MIDNSHP=XB])")
@@ -34,14 +34,36 @@ def cigar_string(ops):
     return "".join("%d%s" % (int(o) >> 4, OP_CODES[int(o) & 15]) for o in ops) or "*"
 
 
+_MASK64 = (1 << 64) - 1
+
+
+def name_key(name):
+    """The name key of a QNAME (bytes) by the library's rule (``csrc/spl_mate_rule.h``): FNV-1a over the bytes, then a 64-bit
+    finisher; 0 for an empty name and for ``*`` ("no name"), 1 for another name whose hash comes to 0."""
+    name = bytes(name)
+    if name == b"" or name == b"*":
+        return 0
+    h = 0xcbf29ce484222325
+    for b in name:
+        h = ((h ^ b) * 0x100000001b3) & _MASK64
+    h ^= h >> 33
+    h = (h * 0xff51afd7ed558ccd) & _MASK64
+    h ^= h >> 33
+    h = (h * 0xc4ceb9fe1a85ec53) & _MASK64
+    h ^= h >> 33
+    return h or 1
+
+
 class ReadSet(object):
     """Reads of one chromosome in file order (SoA).  ``pos`` is 1-based (SAM POS).  ``xs``: None, or a strand byte per read
     (``'+'``, ``'-'``, 0) from the aligner's XS:A tag where the reader was asked for it (``read_sam(aux_strand=True)``,
-    ``native.BamFile.set_aux_strand``)."""
-    __slots__ = ("pos", "flag", "cig_off", "cigar", "max_end", "xs")
+    ``native.BamFile.set_aux_strand``).  ``name_key``: None, or the reads' name keys (uint64; ``name_key``) where the reader was
+    asked for them (``read_sam(mate_keys=True)``, a decode with ``mate_keys``)."""
+    __slots__ = ("pos", "flag", "cig_off", "cigar", "max_end", "xs", "name_key")
 
-    def __init__(self, pos, flag, cig_off, cigar, max_end=None, xs=None):
+    def __init__(self, pos, flag, cig_off, cigar, max_end=None, xs=None, name_key=None):
         self.xs = None if xs is None else np.ascontiguousarray(xs, dtype=np.uint8)
+        self.name_key = None if name_key is None else np.ascontiguousarray(name_key, dtype=np.uint64)
         self.pos = np.ascontiguousarray(pos, dtype=np.int32)
         self.flag = np.ascontiguousarray(flag, dtype=np.uint16)
         self.cig_off = np.ascontiguousarray(cig_off, dtype=np.uint32)
@@ -72,7 +94,7 @@ class ReadSet(object):
             return ReadSet.empty()
         o0, o1 = int(self.cig_off[lo]), int(self.cig_off[hi])
         off = self.cig_off[lo:hi + 1] if o0 == 0 else (self.cig_off[lo:hi + 1].astype(np.int64) - o0).astype(np.uint32)
-        return ReadSet(self.pos[lo:hi], self.flag[lo:hi], off, self.cigar[o0:o1], max_end=self.max_end)
+        return ReadSet(self.pos[lo:hi], self.flag[lo:hi], off, self.cigar[o0:o1], max_end=self.max_end, name_key=None if self.name_key is None else self.name_key[lo:hi])
 
     @classmethod
     def empty(cls):
@@ -103,16 +125,18 @@ def sam_aux_strand(cigar, optional):
     return 0
 
 
-def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None, aux_strand=False):
+def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None, aux_strand=False, mate_keys=False):
     """Parse SAM text (plain, or compressed as gzip / BGZF) -> (ref_names, {chrom: ReadSet}).  Keeps every record that has an RNAME, file order -- what ``samtools
     view`` would print; ``min_mapq`` / ``require_flags`` / ``exclude_flags`` are its -q / -f / -F on columns 5 and 2 (the BAM
     decoder's rule, ``spl_bam_set_filter``: flags first, MAPQ as a number).  ``counts``: a list that gets [records seen, dropped
-    by flags, dropped by MAPQ] added to its three entries.  ``aux_strand``: every ReadSet gets ``xs`` (``sam_aux_strand``)."""
+    by flags, dropped by MAPQ] added to its three entries.  ``aux_strand``: every ReadSet gets ``xs`` (``sam_aux_strand``).  ``mate_keys``: every
+    ReadSet gets ``name_key``, the key of column 1 as the file's bytes have it (the text is then read byte for byte, as Latin-1)."""
     names, per = [], {}
     seen = by_flags = by_mapq = 0
     with open(path, "rb") as handle:
         packed = handle.read(2) == b"\x1f\x8b"      # (gzip, or BGZF, which is gzip in many members)
-    with (gzip.open(path, "rt") if packed else open(path, "r")) as handle:      # (both translate newlines alike: a carriage return ends a line)
+    enc = dict(encoding="latin-1") if mate_keys else {}
+    with (gzip.open(path, "rt", **enc) if packed else open(path, "r", **enc)) as handle:      # (both translate newlines alike: a carriage return ends a line)
         for line in handle:
             if line.startswith("@"):
                 if line.startswith("@SQ"):
@@ -134,7 +158,7 @@ def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None, au
                     continue
             rec = per.get(cols[2])
             if rec is None:
-                rec = per[cols[2]] = ([], [], [0], [], [])
+                rec = per[cols[2]] = ([], [], [0], [], [], [])
                 if cols[2] not in names:
                     names.append(cols[2])
             rec[0].append(int(cols[3]))
@@ -143,8 +167,11 @@ def read_sam(path, min_mapq=0, require_flags=0, exclude_flags=0, counts=None, au
             rec[2].append(len(rec[3]))
             if aux_strand:
                 rec[4].append(sam_aux_strand(cols[5], cols[11:]))
+            if mate_keys:
+                rec[5].append(name_key(cols[0].encode("latin-1")))
     sets = {c: ReadSet(np.asarray(p, np.int64), np.asarray(f, np.int64), np.asarray(o, np.int64),
-                       np.asarray(g, np.int64), xs=np.asarray(x, np.uint8) if aux_strand else None) for c, (p, f, o, g, x) in per.items()}
+                       np.asarray(g, np.int64), xs=np.asarray(x, np.uint8) if aux_strand else None, name_key=np.asarray(k, np.uint64) if mate_keys else None)
+            for c, (p, f, o, g, x, k) in per.items()}
     if counts is not None:
         for k, v in enumerate((seen, by_flags, by_mapq)):
             counts[k] += v
@@ -161,10 +188,18 @@ def _mapq_of(mapq, k_chrom, rs):
     return m
 
 
-def write_sam(path, ref_names, ref_lengths, chrom_reads, mapq=None):
+def _names_of(names, chrom_reads):
+    if names is not None and (len(names) != len(chrom_reads) or any(len(t) != rs.n for t, (_, rs) in zip(names, chrom_reads))):
+        raise ValueError("names: one bytes object per read of every entry of chrom_reads")
+    return names
+
+
+def write_sam(path, ref_names, ref_lengths, chrom_reads, mapq=None, names=None):
     """chrom_reads: list of (chrom, ReadSet) in file order.  mapq: per entry of chrom_reads an array of the reads' MAPQ (default:
-    60 for every read)."""
-    with open(path, "w") as fh:
+    60 for every read).  names: per entry of chrom_reads a list of the reads' QNAMEs as bytes, written as they are (default:
+    ``r<serial>``)."""
+    names = _names_of(names, chrom_reads)
+    with open(path, "w", **(dict(encoding="latin-1", newline="\n") if names is not None else {})) as fh:
         fh.write("@HD\tVN:1.6\tSO:coordinate\n")
         for n, ln in zip(ref_names, ref_lengths):
             fh.write("@SQ\tSN:%s\tLN:%d\n" % (n, ln))
@@ -173,7 +208,8 @@ def write_sam(path, ref_names, ref_lengths, chrom_reads, mapq=None):
             mq = _mapq_of(mapq, k_chrom, rs)
             for k in range(rs.n):
                 ops = rs.cigar[rs.cig_off[k]:rs.cig_off[k + 1]]
-                fh.write("r%d\t%d\t%s\t%d\t%d\t%s\t*\t0\t0\t*\t*\n" % (i, rs.flag[k], chrom, rs.pos[k], 60 if mq is None else mq[k], cigar_string(ops)))
+                qname = "r%d" % i if names is None else bytes(names[k_chrom][k]).decode("latin-1")
+                fh.write("%s\t%d\t%s\t%d\t%d\t%s\t*\t0\t0\t*\t*\n" % (qname, rs.flag[k], chrom, rs.pos[k], 60 if mq is None else mq[k], cigar_string(ops)))
                 i += 1
 
 
@@ -209,7 +245,7 @@ def _reg2bin(beg, end):
     return 0
 
 
-def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False, unplaced=0, long_cigar_tag=False, mapq=None, tags=None):
+def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False, unplaced=0, long_cigar_tag=False, mapq=None, tags=None, names=None):
     """Write a BAM file.  chrom_reads: list of (chrom, ReadSet) in file order.
 
     with_seq       -- emit a dummy SEQ/QUAL of the query length (realistic record size) instead of '*'
@@ -219,7 +255,10 @@ def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False
     mapq           -- per entry of chrom_reads an array of the reads' MAPQ (default: 60 for every read)
     tags           -- per entry of chrom_reads a list of raw aux bytes per read (``b"XSA+"``, ...), appended to the record as
                       they are, behind the CG tag where there is one (default: no tags of the caller's)
+    names          -- per entry of chrom_reads a list of the reads' QNAMEs as bytes, at most 254 each, without the NUL (default:
+                      ``r<serial>``)
     """
+    names = _names_of(names, chrom_reads)
     if tags is not None and (len(tags) != len(chrom_reads) or any(len(t) != rs.n for t, (_, rs) in zip(tags, chrom_reads))):
         raise ValueError("tags: one bytes object per read of every entry of chrom_reads")
     tid_of = {n: i for i, n in enumerate(ref_names)}
@@ -244,7 +283,9 @@ def write_bam(path, ref_names, ref_lengths, chrom_reads, level=1, with_seq=False
                 ops = [int(o) for o in rs.cigar[rs.cig_off[k]:rs.cig_off[k + 1]]]
                 qlen = sum(o >> 4 for o in ops if (o & 15) in (0, 1, 4, 7, 8))
                 rlen = sum(o >> 4 for o in ops if (o & 15) in (0, 2, 3, 7, 8))
-                name = ("r%d" % serial).encode("ascii") + b"\x00"
+                name = (("r%d" % serial).encode("ascii") if names is None else bytes(names[k_chrom][k])) + b"\x00"
+                if len(name) > 255:
+                    raise ValueError("a QNAME has at most 254 bytes")
                 serial += 1
                 pos0 = int(rs.pos[k]) - 1
                 aux = b""
