@@ -109,6 +109,13 @@ int spl_device_count(int *n_out);
  * in the same process -- fresh device memory costs 30 ms per GB on this stack -- up to half of what was free on the device when it
  * first asked (SPL_DEV_CACHE_GB overrides).  spl_trim returns all of it to the driver: device_id, or -1 for every device. */
 int spl_trim(int device_id);
+/* Test hooks on that pool.  spl_devmem_stats: since the process began, out[0] buffers handed out, out[1] those of them that were
+ * served from the pool, out[2] those that were poisoned (SPL_DEV_POISON=1 fills every buffer with 0xA5 as it is handed out),
+ * out[3] the bytes the pool holds now.  spl_devmem_probe takes a buffer of `bytes` from the pool under `tag` the way the library
+ * takes its own, copies its whole capacity (at most `room` bytes) to host_out as it was handed over, reports the capacity in
+ * *cap_out and gives the buffer back. */
+int spl_devmem_stats(int64_t out[4]);
+int spl_devmem_probe(spl_ctx *ctx, int64_t bytes, int tag, uint8_t *host_out, int64_t room, int64_t *cap_out);
 int spl_create(int device_id, spl_ctx **out);
 /* Same, but work is enqueued on a caller-provided hipStream_t (e.g. torch's current stream). */
 int spl_create_on_stream(int device_id, void *hip_stream, spl_ctx **out);

@@ -92,6 +92,7 @@ struct Held { int device; void *p; size_t bytes; };
 static std::mutex &mu() { static std::mutex m; return m; }
 static std::vector<Held> &held() { static std::vector<Held> *v = new std::vector<Held>(); return *v; }
 static std::vector<Held> &lent() { static std::vector<Held> *v = new std::vector<Held>(); return *v; }
+static int64_t n_handed = 0, n_from_pool = 0, n_poisoned = 0; // (under mu(): what spl_devmem_stats reports)
 static size_t limit(int device)
 {
     static const long long env = []() { const char *e = getenv("SPL_DEV_CACHE_GB"); return e ? (long long)std::max(0, atoi(e)) << 30 : -1LL; }();
@@ -140,13 +141,14 @@ static hipError_t get(void **out, size_t bytes, char tag = 'x')
     bytes = (std::max<size_t>(bytes, 1) + gran - 1) / gran * gran;
     void *p = nullptr;
     size_t cap = bytes;
+    bool from_pool = false;
     {
         std::lock_guard<std::mutex> lock(mu());
         std::vector<Held> &v = held();
         size_t best = v.size();
         for (size_t k = 0; k < v.size(); ++k)
             if (v[k].device == device && v[k].bytes >= bytes && v[k].bytes <= 2 * bytes && (best == v.size() || v[k].bytes < v[best].bytes)) best = k;
-        if (best < v.size()) { p = v[best].p; cap = v[best].bytes; v.erase(v.begin() + (long)best); }
+        if (best < v.size()) { p = v[best].p; cap = v[best].bytes; from_pool = true; v.erase(v.begin() + (long)best); }
     }
     if (!p) {
         static const bool timing = getenv("SPL_DEV_TIMING") != nullptr; // (diagnostic: what the driver took for memory the pool did not have)
@@ -158,7 +160,13 @@ static hipError_t get(void **out, size_t bytes, char tag = 'x')
             fprintf(stderr, "[devmem] hipMalloc of %.1f MB ('%c') on device %d: %.2f ms; the pool holds %.1f MB\n", (double)bytes / 1e6, tag, device,
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3, (double)held_bytes(device) / 1e6);
     }
-    { std::lock_guard<std::mutex> lock(mu()); lent().push_back(Held{device, p, cap}); }
+    {
+        std::lock_guard<std::mutex> lock(mu());
+        lent().push_back(Held{device, p, cap});
+        ++n_handed;
+        if (from_pool) ++n_from_pool;
+        if (poison) ++n_poisoned;
+    }
     if (poison) { // (and done before anybody's stream touches the buffer: a memset on the null stream does not wait for, or hold up, the others)
         e = hipMemset(p, 0xA5, cap);
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -166,6 +174,12 @@ static hipError_t get(void **out, size_t bytes, char tag = 'x')
     }
     *out = p;
     return hipSuccess;
+}
+static size_t capacity_of(void *p)
+{
+    std::lock_guard<std::mutex> lock(mu());
+    for (const Held &h : lent()) if (h.p == p) return h.bytes;
+    return 0;
 }
 static void put(void *p)
 {
@@ -580,6 +594,37 @@ extern "C" int spl_sync(spl_ctx *c)
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(join_tail(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPL_OK;
+}
+
+// Test hooks on the device memory pool (devmem above).  spl_devmem_stats: since the process began, the buffers handed out, those of
+// them that came from the pool, those that were poisoned (SPL_DEV_POISON), and the bytes the pool holds now, over every device.
+extern "C" int spl_devmem_stats(int64_t out[4])
+{
+    if (!out) return spl_set_error(SPL_ERR_ARG, "spl_devmem_stats: null output");
+    std::lock_guard<std::mutex> lock(devmem::mu());
+    out[0] = devmem::n_handed;
+    out[1] = devmem::n_from_pool;
+    out[2] = devmem::n_poisoned;
+    out[3] = 0;
+    for (const devmem::Held &h : devmem::held()) out[3] += (int64_t)h.bytes;
+    return SPL_OK;
+}
+
+// spl_devmem_probe: a buffer of `bytes` taken from the pool under `tag` exactly as the product takes its own, its whole capacity (at
+// most `room` bytes of it) copied to host_out as the pool handed it over, the capacity reported, and the buffer given back.
+extern "C" int spl_devmem_probe(spl_ctx *c, int64_t bytes, int tag, uint8_t *host_out, int64_t room, int64_t *cap_out)
+{
+    if (!c || bytes < 0 || room < 0 || (room > 0 && !host_out)) return spl_set_error(SPL_ERR_ARG, "spl_devmem_probe: bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    void *p = nullptr;
+    HIP_TRY(devmem::get(&p, (size_t)bytes, (char)tag));
+    const size_t cap = devmem::capacity_of(p);
+    const size_t n = std::min<size_t>(cap, (size_t)room);
+    const hipError_t e = n ? hipMemcpy(host_out, p, n, hipMemcpyDeviceToHost) : hipSuccess;
+    devmem::put(p);
+    if (e != hipSuccess) return spl_set_error(SPL_ERR_HIP, "spl_devmem_probe: %s", hipGetErrorString(e));
+    if (cap_out) *cap_out = (int64_t)cap;
     return SPL_OK;
 }
 

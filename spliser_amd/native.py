@@ -46,7 +46,7 @@ OPT_WAVE_AGGREGATION = 2   # (selects nothing: such a pass is the default one; k
 
 
 EXPORTS = [
-    "spl_abi_version", "spl_last_error", "spl_device_count", "spl_trim", "spl_create", "spl_create_on_stream", "spl_destroy",
+    "spl_abi_version", "spl_last_error", "spl_device_count", "spl_trim", "spl_devmem_stats", "spl_devmem_probe", "spl_create", "spl_create_on_stream", "spl_destroy",
     "spl_sync", "spl_pass_barrier", "spl_timer_begin", "spl_timer_end", "spl_kernel_timing_begin", "spl_kernel_timing_collect", "spl_prof_enable", "spl_prof_report", "spl_count", "spl_sse", "spl_sites_upload", "spl_sites_free",
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
     "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_soa_upload4", "spl_reads_has_strand", "spl_reads_has_mate_keys", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes", "spl_reads_slots_download",
@@ -729,6 +729,27 @@ def trim(device=-1):
     _check(lib().spl_trim(ctypes.c_int(device)))
 
 
+DEVMEM_STATS = ("handed_out", "from_pool", "poisoned", "held_bytes")
+
+
+def devmem_stats():
+    """The device memory pool since the process began (``spl_devmem_stats``, a test hook) -> dict of handed_out, from_pool, poisoned
+    (buffers) and held_bytes (what the pool holds now)."""
+    out = np.zeros(4, np.int64)
+    _check(lib().spl_devmem_stats(_ptr(out)))
+    return dict(zip(DEVMEM_STATS, out.tolist()))
+
+
+def devmem_probe(ctx, n_bytes, tag="x", room=None):
+    """A buffer of ``n_bytes`` taken from the pool under ``tag`` as the library takes its own, and given back
+    (``spl_devmem_probe``, a test hook) -> (its bytes as it was handed over: uint8[min(capacity, room)], its capacity)."""
+    room = int(n_bytes) + (4 << 20) if room is None else int(room)
+    host = np.zeros(max(room, 1), np.uint8)
+    cap = ctypes.c_int64(0)
+    _check(lib().spl_devmem_probe(ctx._h, ctypes.c_int64(int(n_bytes)), ctypes.c_int(ord(tag)), _ptr(host), ctypes.c_int64(room), ctypes.byref(cap)))
+    return host[:min(cap.value, room)], cap.value
+
+
 def prof_enable(on=True):
     """The library's own stopwatch over all its kernels, process-wide (``spl_prof_enable``): clears what was recorded."""
     _check(lib().spl_prof_enable(ctypes.c_int(1 if on else 0)))
@@ -1115,14 +1136,18 @@ class _BamHandle(object):
         import weakref
         key = handle.value
         cls._parked[key] = handle
-        left = [len(views)]
+        # (every array of every read set, not one of them: a caller that keeps the flags, the strand bytes or the name keys and
+        # lets POS go still reads the native object's memory)
+        live = [a for rs in views.values() for a in (rs.pos, rs.flag, rs.cig_off, rs.cigar, getattr(rs, "xs", None), getattr(rs, "name_key", None))
+                if a is not None]
+        left = [len(live)]
 
         def gone(_):
             left[0] -= 1
             if left[0] == 0:
                 lib().spl_bam_close(cls._parked.pop(key))
-        for rs in views.values():
-            weakref.finalize(rs.pos, gone, None)
+        for a in live:
+            weakref.finalize(a, gone, None)
 
 
 FLAGSTAT_LABELS = ("in total (QC-passed reads + QC-failed reads)", "primary", "secondary", "supplementary", "duplicates", "primary duplicates", "mapped",
