@@ -650,9 +650,8 @@ int spl_gene_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint1
  *               incremented; no hit stretch with a bin = "no feature"; otherwise "counted", and every hit stretch's bin gets + 1;
  *               every other read of the set is "not counted".
  * This is DEXSeq's counting (dexseq_count.py: reads with bins of more than one gene are _ambiguous) and `featureCounts -f -O`
- * restricted to reads of one gene, applied per READ: counting is per read, and a paired fragment adds up to two per bin.  Fragment
- * counting is out of scope here: the bins of a read are committed each bin once, and a fragment needs that across both mates'
- * walks; the mate table of "mates and fragments" above is what a follow-up would use.  Parity with DEXSeq / featureCounts is intended and
+ * restricted to reads of one gene, applied per READ: counting is per read, and a paired fragment adds up to two per bin
+ * (spl_exon_count_fragments, below, counts a fragment once per bin).  Parity with DEXSeq / featureCounts is intended and
  * unpinned: it is not pinned by a test, neither tool being where this is built.  By construction a read's verdict is the one
  * spl_gene_count gives it on the gene maps of the same features.
  * inout[0 .. n_bins) += the bins' reads, inout[n_bins] += counted reads, [n_bins + 1] += no feature, [n_bins + 2] += ambiguous,
@@ -662,13 +661,40 @@ int spl_gene_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint1
  * 0xFFFFFFF0; a null bin_gene with n_bins > 0.  The context stays usable after a refusal.
  * spl_exon_count_rule_host: the same rule for one read on the host (test hook; no file, no GPU): *verdict_out = 0 counted, -1 no
  * feature, -2 ambiguous, -3 not counted; bins_out[0 .. cap) = a counted read's bins in the order of their stretches, *n_hits_out =
- * their number, also beyond cap; any other verdict has no hit. */
+ * their number, also beyond cap; any other verdict has no hit.
+ * PER FRAGMENT (csrc/spl_exonfragment_rule.h; DEXSeq's paired counting, `featureCounts -f -O -p --countReadPairs`).  Mates, pairable
+ * reads, groups and the leader are those of "mates and fragments" above; eligibility, maps, blocks, hit stretches and bins are
+ * unchanged.  A read that is not eligible is "not counted", one per read.  An eligible read whose mate has a lower index in the
+ * segment is silent: it adds nothing and enters no counter.  Every other eligible read is a fragment's leader, or a read without
+ * a mate: its hit stretches are its own, over the map of its own strand, and, if it has a mate, the mate's, over the map of the
+ * mate's strand (by the mate's own flag).  The verdict is taken over the UNION of both reads' hit stretches: any stretch shared,
+ * or two stretches with bins of different genes = "ambiguous", and NO bin is incremented; no stretch with a bin = "no feature";
+ * otherwise "counted", and every DISTINCT bin of the union gets + 1 -- a bin both mates hit counts once, whether they saw it
+ * through the same map or through the two maps of a stranded run (a `.` feature).  The four verdict counters ADDED sum to the
+ * reads minus the pairs; a fragment's verdict is the one spl_gene_count_fragments gives it on the gene maps of the same features.
+ * How a bin is given once with nothing stored per read: one read's bins ascend strictly in bin number on either map (bins are
+ * numbered over both maps), so a fragment's are the two-way merge of its reads' walks, equal heads given once.  The deliberate
+ * differences from the tools are spl_gene_count_fragments' own (a pair split over chromosomes or by a filter counts as two
+ * single-end fragments; names are compared by 63 hash bits); parity is intended and unpinned, the yardstick is
+ * tests/exonfragcases.py.
+ * spl_exon_count_fragments: spl_exon_count's arguments, output and refusals, and spl_mate_table's: SPL_ERR_ARG for a set without
+ * name keys, not fused or not finished.  The mate table is made at the first call that needs it and kept with the set.
+ * spl_exon_fragment_rule_host: the rule for every read of one segment's host arrays with its mate table (test hook; no GPU):
+ * verdict_out[r] = 0 counted, -1 no feature, -2 ambiguous, -3 not counted, -4 silent; n_hits_out[r] = a counted leader's distinct
+ * bins, all of them; bins_out[0 .. cap) = the counted leaders' merged bins, ascending within a fragment, one fragment after the
+ * other in read order, as far as cap reaches.  A mate index at or beyond n_reads, or equal to r, means no mate. */
 int spl_exon_count(spl_ctx *ctx, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b,
                    const int32_t *b_start, const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *inout /* n_bins + 4 */);
 int spl_exon_count_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int stranded, int64_t n_a,
                              const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
                              int64_t n_bins, const uint32_t *bin_gene, int64_t *verdict_out, int64_t *bins_out, int64_t cap,
                              int64_t *n_hits_out);
+int spl_exon_count_fragments(spl_ctx *ctx, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b,
+                             const int32_t *b_start, const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *inout /* n_bins + 4 */);
+int spl_exon_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint32_t *mate,
+                                int32_t shift, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
+                                const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *verdict_out /* n_reads */,
+                                int64_t *n_hits_out /* n_reads */, int64_t *bins_out, int64_t cap);
 
 /* ---- intron depth (what the pipeline otherwise needs IRFinder or iREAD and a sorted BAM for) ------------------------------------
  * Replaces a second tool over the file this library has just decoded: how deeply every annotated intron is covered, beside the

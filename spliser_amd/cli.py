@@ -36,7 +36,8 @@ read -- the two-column file ``edgeR::readDGE`` reads, without a second pass over
 Extra sub-command ``exoncounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [-c CHROM] [--isStranded -s fr|rf]`` writes
 ``PREFIX.exonbins.tsv`` and ``PREFIX.exoncounts.tsv``: reads per exon counting bin, counted on the GPU from the decode by DEXSeq's rule
 (``featureCounts -f -O`` restricted to reads of one gene) per read -- what ``edgeR::diffSpliceDGE`` needs, without a second pass over
-the BAM by another program (``exoncounts.py``).
+the BAM by another program (``exoncounts.py``).  ``--countReadPairs``: a paired-end fragment adds one to every distinct bin under either
+mate -- mates paired on the GPU as for ``genecounts --fragments``, whose spelling is refused here.
 Extra sub-command ``intronretention -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [--trimPercent 30] [-c CHROM] [--isStranded
 -s fr|rf]`` writes ``PREFIX.introns.tsv``: per annotated intron the trimmed depth of its measurable bases, the splice counts at its ends and
 the IR ratio, taken on the GPU from the decode -- IRFinder's measure, without a sorted BAM and a second tool (``intronretention.py``).
@@ -213,7 +214,8 @@ def build_parser():
     _filter_flags(n)
     _engine_flags(n)
     x = sub.add_parser("exoncounts", help="(this build only) reads per exon counting bin for edgeR::diffSpliceDGE / DEXSeq, counted on the GPU from the decode "
-                                          "(dexseq_count.py's rule, featureCounts -f -O for reads of one gene; per read): no second pass over the BAM by another program")
+                                          "(dexseq_count.py's rule, featureCounts -f -O for reads of one gene; per read, per fragment with --countReadPairs): no second pass over the BAM "
+                                          "by another program")
     x.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
     x.add_argument("-A", "--annotationFile", dest="annotationFile", required=False, default=None, help="gff3 or gtf file matching the reference genome used for alignment (required)")
     x.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="output prefix: .exonbins.tsv and .exoncounts.tsv are appended")
@@ -229,7 +231,12 @@ def build_parser():
     x.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
     x.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
     x.add_argument("--fragments", dest="fragments", default=False, action="store_true",
-                   help="(refused: exon bins are counted per read; `genecounts --fragments` counts a paired-end fragment once per gene)")
+                   help="(refused: `genecounts --fragments`' spelling; here the switch is --countReadPairs)")
+    # (default SUPPRESS: without the switch the parsed arguments are what they were, key for key)
+    x.add_argument("--countReadPairs", dest="countReadPairs", default=argparse.SUPPRESS, action="store_true",
+                   help="paired-end: mates are paired on the GPU by a key of their names (as for `genecounts --fragments`) and a fragment adds one to every "
+                        "distinct bin under either mate, a bin both mates overlap once (DEXSeq's and featureCounts -f -O -p --countReadPairs' way); a pair split "
+                        "over two chromosomes or by the read filter counts as two")
     _filter_flags(x)
     _engine_flags(x)
     i = sub.add_parser("intronretention", help="(this build only) per annotated intron the trimmed depth, the splice counts and the IR ratio, taken on the GPU from the "
@@ -316,8 +323,7 @@ def main(argv=None):
     if command in ("genecounts", "exoncounts", "intronretention") and kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
         parser.error("%s: --strandedType/-s must be fr or rf" % command)
     if command == "exoncounts" and kwargs.pop("fragments", False):
-        parser.error("exoncounts: --fragments is not taken here: a read's bins are committed each bin once, and a fragment needs that across both mates' walks; "
-                     "`genecounts --fragments` counts a fragment once per gene")
+        parser.error("exoncounts: --fragments is `genecounts --fragments`' spelling; here the switch is --countReadPairs")
     if command == "intronretention" and not 0 <= kwargs["trimPercent"] <= 49:
         parser.error("intronretention: --trimPercent must be in 0..49")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":

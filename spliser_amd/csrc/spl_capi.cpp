@@ -45,6 +45,7 @@
 #include "spl_mates.h"
 #include "spl_exoncount.h"
 #include "spl_exoncount_rule.h"
+#include "spl_exonfragment_rule.h"
 #include "spl_intron.h"
 #include "spl_intron_rule.h"
 #include "spl_simple_span.h"
@@ -4906,6 +4907,71 @@ extern "C" int spl_exon_count_rule_host(uint32_t flag, int32_t pos, const uint32
     const uint32_t v = spl_exon_read_result(flag, (int64_t)pos, ops, n_ops, (int64_t)shift, stranded, spl_gene_map_flat{n_a, a_start, a_code}, spl_gene_map_flat{n_b, b_start, b_code}, bin_gene,
                                             bins_out, cap, n_hits_out);
     *verdict_out = -(int64_t)v;
+    return SPL_OK;
+}
+
+// spl_exon_count per fragment (the rule is spl_exonfragment_rule.h): the arguments are spl_exon_count's; the set must have name keys.
+extern "C" int spl_exon_count_fragments(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
+                                        const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *inout)
+{
+    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_exon_count_fragments: null argument");
+    if (const int rc = exon_maps_fit("spl_exon_count_fragments", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
+    if (const int rc = mates_of(c, dr, "spl_exon_count_fragments")) return rc;
+    if (dr->segs.empty()) return SPL_OK;
+    const spl_dreads::Group &g = dr->groups[0];
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n_out = (size_t)n_bins + SPL_EXON_VERDICTS;
+    DevBuf d_out, d_gene, d_map[4];
+    HIP_TRY(d_out.get(8 * n_out, c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
+    if (n_bins) {
+        HIP_TRY(d_gene.get(4 * (size_t)n_bins, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_gene.p, bin_gene, 4 * (size_t)n_bins, hipMemcpyHostToDevice, c->stream));
+    }
+    const void *const host[4] = {a_start, a_code, b_start, b_code};
+    const int64_t entries[4] = {n_a, n_a, n_b, n_b};
+    for (int m = 0; m < 4; ++m) {
+        if (!entries[m]) continue;
+        HIP_TRY(d_map[m].get(4 * (size_t)entries[m], c->stream));
+        HIP_TRY(hipMemcpyAsync(d_map[m].p, host[m], 4 * (size_t)entries[m], hipMemcpyHostToDevice, c->stream));
+    }
+    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
+    for (const spl_dreads::Segment &seg : dr->segs) {
+        const spl_layout_seg &ls = g.segs[seg.group_seg];
+        if (ls.n_reads <= 0) continue;
+        // bytes: the per-read launch's, and a read's word of the mate table
+        splprof::Scope prof("spl_exon_count_fragments_kernel", c->stream, 14.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
+        const int rc = spl_dev_launch_exon_count_fragments(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_map[0].as<int32_t>(), d_map[1].as<uint32_t>(), n_b,
+                                                           d_map[2].as<int32_t>(), d_map[3].as<uint32_t>(), (uint32_t)n_bins, d_gene.as<uint32_t>(), dr->mates + ls.first,
+                                                           d_out.as<unsigned long long>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "exon count kernel launch (fragments): %s", hipGetErrorString((hipError_t)rc));
+    }
+    std::vector<unsigned long long> sums(n_out, 0ull);
+    HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
+    return SPL_OK;
+}
+
+// The fragment rule for every read of one segment's host arrays with its mate table: no GPU involved (test hook).  verdict_out[r]:
+// 0 counted, -1 no feature, -2 ambiguous, -3 not counted, -4 silent (the read's leader counts the fragment); n_hits_out[r]: a counted
+// leader's distinct bins (all of them); bins_out[0 .. cap): the counted leaders' merged bins, one after the other in read order.
+extern "C" int spl_exon_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint32_t *mate, int32_t shift,
+                                           int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
+                                           int64_t n_bins, const uint32_t *bin_gene, int64_t *verdict_out, int64_t *n_hits_out, int64_t *bins_out, int64_t cap)
+{
+    if (n_reads < 0 || (n_reads && (!pos || !flag || !cig_off || !mate || !verdict_out || !n_hits_out)) || cap < 0 || (cap && !bins_out))
+        return spl_set_error(SPL_ERR_ARG, "spl_exon_fragment_rule_host: null argument");
+    if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_exon_fragment_rule_host: cigar is null");
+    if (const int rc = exon_maps_fit("spl_exon_fragment_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
+    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    const spl_gene_map_flat map_a{n_a, a_start, a_code}, map_b{n_b, b_start, b_code};
+    int64_t used = 0;
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const uint32_t v = spl_exon_fragment_result(reads, n_reads, r, mate, (int64_t)shift, stranded, map_a, map_b, bin_gene, bins_out ? bins_out + used : nullptr, cap - used, &n_hits_out[r]);
+        verdict_out[r] = -(int64_t)v;
+        used = std::min<int64_t>(cap, used + n_hits_out[r]);
+    }
     return SPL_OK;
 }
 

@@ -25,6 +25,11 @@ uint32_t spl_dev_exon_grid(int64_t n);
 int spl_dev_launch_exon_count(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a, const int32_t *a_start,
                               const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, uint32_t n_bins, const uint32_t *bin_gene, unsigned long long *counts,
                               void *stream);
+// The same per FRAGMENT (spl_exonfragment_rule.h): mate = the segment's mate table in device memory, n words, indexes relative to
+// `first`; a pair of mates adds one to every distinct bin of both reads, and one to one verdict counter.
+int spl_dev_launch_exon_count_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a, const int32_t *a_start,
+                                        const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, uint32_t n_bins, const uint32_t *bin_gene,
+                                        const uint32_t *mate, unsigned long long *counts, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -14,10 +14,22 @@ by features of two genes or more is shared and no bin.  Two abutting exons of on
 transcripts is one.  A read that ``genecounts`` gives to a gene adds one to EVERY bin one of its aligned blocks overlaps (each bin
 once, however many of its blocks lie in it); a read it calls ambiguous adds to no bin.  This is DEXSeq's counting
 (``dexseq_count.py``) and ``featureCounts -f -O`` restricted to reads of one gene, applied per READ: a paired fragment adds up to
-two per bin.  Fragment counting is out of scope here: a read's bins are committed each bin once, and a fragment needs that across both mates'
-walks -- the mate table of ``genecounts --fragments`` (``spl_mate_table``) is what a follow-up would use.  Parity with DEXSeq and
-featureCounts is intended and unpinned (neither is on the build machine): the yardstick is this statement of the rule, restated in
-tests/exoncases.py.
+two per bin.  Parity with DEXSeq and featureCounts is intended and unpinned (neither is on the build machine): the yardstick is
+this statement of the rule, restated in tests/exoncases.py.
+
+``--countReadPairs`` (featureCounts' word; ``--fragments`` is ``genecounts``' spelling and is refused here) counts a paired-end
+library as DEXSeq and ``featureCounts -f -O -p --countReadPairs`` do, a FRAGMENT once per bin.  Mates are ``genecounts
+--fragments``': the decode keeps a 64-bit key of every read's name, the mate table is built on the GPU per chromosome
+(``spl_mate_table``), and ``spl_exon_count_fragments`` holds both mates against the bins, each mate on the map of its own strand.
+A read that is not eligible is not counted; an eligible read whose mate lies before it in the chromosome's reads is silent; every
+other eligible read leads its fragment (or has no mate).  The verdict is taken over both mates' hit stretches together: a shared
+piece under either, or bins of two genes, is ambiguous and NO bin moves; no bin at all is no feature; otherwise every DISTINCT bin
+under either mate gets one -- a bin both mates overlap counts once, also when a stranded run showed it to them through different
+maps (a ``.`` feature).  One read's bins ascend in bin number, so the kernel merges the two mates' walks and gives equal heads once;
+nothing is stored per read.  The rows then sum to reads minus pairs, and a fragment's verdict is ``genecounts --fragments``' on the
+same features.  The deliberate differences from the tools are that command's: a pair split over two chromosomes or by a filter
+counts as two single-end fragments, and names are compared by a 63-bit hash.  Parity is intended and unpinned; the yardstick is
+tests/exonfragcases.py.  With several devices the file is decoded and counted on the first one.
 """
 import sys
 
@@ -115,20 +127,30 @@ class Bins(object):
         return np.flatnonzero(self.chrom == self.chroms.index(chrom)) if chrom in self.chroms else np.zeros(0, np.int64)
 
 
-def counts_of_source(source, devices, chroms, bins, stranded=0, per_chrom=None):
+def counts_of_source(source, devices, chroms, bins, stranded=0, per_chrom=None, fragments=False, mates=None):
     """``spl_exon_count`` over every chromosome of ``chroms`` -> ({chrom: int64[n_bins] the bins' reads}, int64[4] the reads counted,
     without a feature, ambiguous, not counted), on the plan of ``genecounts.over_fused_sets``.  A chromosome without a feature has
     no bin, and every eligible read on it is without a feature.  ``per_chrom``: a dict that gets, per chromosome with reads, its
-    int64[4]."""
+    int64[4].  ``fragments``: ``spl_exon_count_fragments`` -- a pair of mates counts once per bin; the source was decoded with
+    ``mate_keys`` and not in shares (an error otherwise).  ``mates``: a dict that then gets, per chromosome with reads, int64[4] as
+    ``genecounts.counts_of_source`` fills it."""
     import threading
     per_bin, total, lock = {}, np.zeros(4, np.int64), threading.Lock()
     nothing = (None, None, np.zeros(0, np.uint32))
+    if fragments and not getattr(source, "mate_keys", False):
+        raise native.SpliserNativeError(-1, "fragment counting needs a source decoded with name keys (DecodeOptions.mate_keys)")
+    if fragments and getattr(source, "shares", None):
+        raise native.SpliserNativeError(-1, "fragment counting needs the file decoded on one device: mates can lie either side of a share's cut")
 
     def count(dr, chrom):
         a, b, bin_gene = bins.by_chrom.get(chrom, nothing)
-        t = dr.exon_counts(bin_gene, a, b, stranded)
+        t = dr.exon_counts(bin_gene, a, b, stranded, fragments=fragments)
+        stats = dr.mate_table(0)[1] if fragments and mates is not None else None
         n = bin_gene.shape[0]
         with lock:
+            if stats is not None:
+                row = mates.setdefault(chrom, np.zeros(4, np.int64))
+                row += [dr.n, stats["pairable"], stats["paired"], stats["unpaired_mate_mapped"]]
             if chrom in per_bin:
                 per_bin[chrom] += t[:n]
             else:
@@ -138,7 +160,7 @@ def counts_of_source(source, devices, chroms, bins, stranded=0, per_chrom=None):
                 row = per_chrom.setdefault(chrom, np.zeros(4, np.int64))
                 row += t[n:]
 
-    _gc.over_fused_sets(source, devices, chroms, count)
+    _gc.over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments))
     return per_bin, total
 
 
@@ -173,10 +195,11 @@ def write_counts(path, bins, rows, counts, verdicts):
 
 
 def exoncounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id", qChrom="All", isStranded=False, strandedType=None, devices=(0,), threads=0, log=None,
-               gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False):
+               gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False, countReadPairs=False):
     """The ``exoncounts`` command: one decode, the annotation read and cut into bins meanwhile, ``<outputPath>.exonbins.tsv`` and
     ``<outputPath>.exoncounts.tsv``.  ``qChrom``: the reads of that chromosome, and the bins on it, under the ids they have in the
-    whole annotation.  -> (the rows' counts, int64[4]: counted, no feature, ambiguous, not counted)."""
+    whole annotation.  ``countReadPairs``: a pair of mates counts once per bin (the module's text); the files' format is the same.
+    -> (the rows' counts, int64[4]: counted, no feature, ambiguous, not counted)."""
     import timeit
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
     if annotationFile is None:
@@ -185,7 +208,10 @@ def exoncounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
         raise ValueError("exoncounts: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
     stranded = _gc.STRANDED[strandedType] if isStranded else 0
     devices = tuple(devices)
-    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder))
+    if countReadPairs and len(devices) > 1:
+        log("  (--countReadPairs: the alignment file is decoded and counted on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
+        devices = devices[:1]
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(countReadPairs))
     source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
     try:
         t0 = timeit.default_timer()
@@ -199,11 +225,16 @@ def exoncounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
         if anyOrder:
             _process.log_any_order(source, log)
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
-        per_chrom = {}
-        per_bin, verdicts = counts_of_source(source, devices, chroms, bins, stranded, per_chrom)
+        per_chrom, mates = {}, ({} if countReadPairs else None)
+        per_bin, verdicts = counts_of_source(source, devices, chroms, bins, stranded, per_chrom, fragments=bool(countReadPairs), mates=mates)
+        what = "fragments" if countReadPairs else "reads"
         for chrom in chroms:
             if chrom in per_chrom:
-                log("  %s: %d reads counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom,) + tuple(int(v) for v in per_chrom[chrom])))
+                log("  %s: %d %s counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom, int(per_chrom[chrom][0]), what) + tuple(int(v) for v in per_chrom[chrom][1:])))
+            if countReadPairs and chrom in mates:
+                log("  %s: %s" % (chrom, _gc.mates_line(mates[chrom])))
+        if countReadPairs:
+            log("  mates: %s" % _gc.mates_line(sum(mates.values(), np.zeros(4, np.int64))))
         _process.log_filter(source, options.read_filter, log)
     finally:
         if hasattr(source, "close"):
@@ -212,5 +243,6 @@ def exoncounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
     counts = row_counts(bins, per_bin, rows)
     write_bins(outputPath + BINS_SUFFIX, bins, rows)
     write_counts(outputPath + COUNTS_SUFFIX, bins, rows, counts, verdicts)
-    log("%s: %d bins, %d reads counted, %d without a feature, %d ambiguous, %d not counted" % ((outputPath + COUNTS_SUFFIX, len(rows)) + tuple(int(v) for v in verdicts)))
+    log("%s: %d bins, %d %s counted, %d without a feature, %d ambiguous, %d not counted" % ((outputPath + COUNTS_SUFFIX, len(rows), int(verdicts[0]), "fragments" if countReadPairs else "reads")
+                                                                                           + tuple(int(v) for v in verdicts[1:])))
     return counts, verdicts

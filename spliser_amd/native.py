@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_set_mate_keys", "spl_bam_mate_keys", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -549,11 +549,12 @@ class DeviceReads(object):
                     _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_genes), _ptr(out)))
         return out
 
-    def exon_counts(self, bin_gene, map_a, map_b=None, stranded=0, out=None):
+    def exon_counts(self, bin_gene, map_a, map_b=None, stranded=0, out=None, fragments=False):
         """Per-exon-bin read counts of this (finished, fused) set, on the device (``spl_exon_count``): ADDS to ``out``
         (int64[n_bins + 4]; made when None) and returns it -- the bins' reads, then the reads counted, without a feature, ambiguous,
         not counted.  ``bin_gene``: every bin's gene (uint32[n_bins]); ``map_a`` / ``map_b``: bin maps ``(start int32, code uint32)``
-        in the set's coordinates (``exoncounts.exon_maps``) or None; ``stranded`` as for ``gene_counts``."""
+        in the set's coordinates (``exoncounts.exon_maps``) or None; ``stranded`` as for ``gene_counts``.  ``fragments``: a pair of
+        mates (``mate_table``) adds one to every distinct bin of both reads (``spl_exon_count_fragments``; the set needs name keys)."""
         bin_gene = _arr(bin_gene, np.uint32)
         n_bins = int(bin_gene.shape[0])
         if out is None:
@@ -561,9 +562,10 @@ class DeviceReads(object):
         if not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.shape == (n_bins + 4,) and out.flags.c_contiguous):
             raise ValueError("exon counts are a contiguous int64 array of n_bins + 4 entries")
         (a_start, a_code), (b_start, b_code) = _gene_map_arrays(map_a), _gene_map_arrays(map_b)
-        _check(lib().spl_exon_count(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]), _ptr(a_start) if a_start.shape[0] else None,
-                                    _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
-                                    _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_bins), _ptr(bin_gene) if n_bins else None, _ptr(out)))
+        entry = lib().spl_exon_count_fragments if fragments else lib().spl_exon_count
+        _check(entry(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]), _ptr(a_start) if a_start.shape[0] else None,
+                     _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]), _ptr(b_start) if b_start.shape[0] else None,
+                     _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_bins), _ptr(bin_gene) if n_bins else None, _ptr(out)))
         return out
 
     def intron_depth(self, length, piece_off, piece_start, piece_end, trim_percent=30, stranded=0, strand=0):
@@ -1287,6 +1289,25 @@ def exon_count_rule_host(flag, pos, ops, bin_gene, map_a, map_b=None, stranded=0
                                           _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(bin_gene.shape[0]), _ptr(bin_gene) if bin_gene.shape[0] else None,
                                           ctypes.byref(verdict), _ptr(bins), ctypes.c_int64(int(cap)), ctypes.byref(n_hits)))
     return verdict.value, bins[:min(int(cap), n_hits.value)].tolist(), n_hits.value
+
+
+def exon_fragment_rule_host(reads, mate, bin_gene, map_a, map_b=None, stranded=0, shift=0, cap=4096):
+    """The exon-bin fragment rule for every read of one segment's host arrays with its mate table (``spl_exon_fragment_rule_host``)
+    -> (verdict int64[n], n_hits int64[n], bins int64[min(cap, sum of n_hits)]): 0 counted, -1 no feature, -2 ambiguous, -3 not
+    counted, -4 silent (the read's leader counts the fragment); a counted leader's number of distinct bins, also beyond ``cap``; the
+    counted leaders' merged bins, one fragment after the other in read order, as far as ``cap`` reaches."""
+    mate, bin_gene = _arr(mate, np.uint32), _arr(bin_gene, np.uint32)
+    if mate.shape[0] != reads.n:
+        raise ValueError("mate must have n_reads entries")
+    (a_start, a_code), (b_start, b_code) = _gene_map_arrays(map_a), _gene_map_arrays(map_b)
+    verdict, n_hits, bins = np.zeros(max(reads.n, 1), np.int64), np.zeros(max(reads.n, 1), np.int64), np.zeros(max(int(cap), 1), np.int64)
+    _check(lib().spl_exon_fragment_rule_host(ctypes.c_int64(reads.n), _ptr(reads.pos), _ptr(reads.flag), _ptr(reads.cig_off), _ptr(reads.cigar) if reads.cigar.shape[0] else None,
+                                             _ptr(mate), ctypes.c_int32(int(shift)), ctypes.c_int(int(stranded)), ctypes.c_int64(a_start.shape[0]),
+                                             _ptr(a_start) if a_start.shape[0] else None, _ptr(a_code) if a_code.shape[0] else None, ctypes.c_int64(b_start.shape[0]),
+                                             _ptr(b_start) if b_start.shape[0] else None, _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(bin_gene.shape[0]),
+                                             _ptr(bin_gene) if bin_gene.shape[0] else None, _ptr(verdict), _ptr(n_hits), _ptr(bins), ctypes.c_int64(int(cap))))
+    verdict, n_hits = verdict[:reads.n], n_hits[:reads.n]
+    return verdict, n_hits, bins[:min(int(cap), int(n_hits.sum()))]
 
 
 INTRON_LONG_BASES = 16384   # csrc/spl_intron.h's SPL_INTRON_LONG_BASES: an intron of this many measurable bases or more has a team of its own
