@@ -629,6 +629,18 @@ int spl_gene_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint1
                                 int32_t shift, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
                                 const uint32_t *b_code, int64_t n_genes, int64_t *results_out /* n_reads */);
 
+/* ---- the lanes of the counting passes (test hook, no GPU) ----------------------------------------------------------------------
+ * Which stream a counting pass runs on and which recorded events it waits for is a rule of its own (csrc/spl_lanes.h; INTEGRATION.md,
+ * "streams"), which spl_reads_relayout, spl_count_launch, spl_pass_barrier and the joins of every other entry point follow.
+ * spl_lanes_plan_host runs that rule over a sequence of calls and hands back what each of them would queue.  calls: four int32 a call,
+ * kind, a, b, c -- 0 relayout(set a, fused b), 1 count(table a, set b, piped c: the range kernel on a clean counter copy), 2 barrier,
+ * 3 a download (join, the host waits), 4 other work on the main stream (a: behind a join).  out: 6 + 4 * 12 int64 a call -- the lane,
+ * piped, the number of ops, how many of them stand behind the call's own launches, how many (before those) between the range kernel
+ * and the tail, the tail's stream, then per op (1 wait / 2 record, the stream: 0 main, 1 second lane, 2 tail, the event's kind: 1 a
+ * pass's range kernel, 2 a tail on the tail stream, 3 a marker on the main stream, 4 on the second lane, 5 a tail on the second lane,
+ * its number).  two_lanes / tail_stream / callers_stream: the context's streams.  At most 64 tables and 64 sets. */
+int spl_lanes_plan_host(int two_lanes, int tail_stream, int callers_stream, int n_tables, int n_sets, int64_t n_calls, const int32_t *calls, int64_t *out);
+
 /* ---- per-exon-bin read counts (what the pipeline otherwise leaves to a second pass by another program) -----------------------
  * Replaces `featureCounts -f -O` / `dexseq_count.py` over the file this library has just decoded: whoever looks at a change in
  * splice-site strength also asks about exon usage (edgeR::diffSpliceDGE, DEXSeq), which needs reads per exon counting bin.  The

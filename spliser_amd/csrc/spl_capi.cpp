@@ -42,6 +42,7 @@
 #include "spl_genecount.h"
 #include "spl_genecount_rule.h"
 #include "spl_mate_rule.h"
+#include "spl_lanes.h"
 #include "spl_mates.h"
 #include "spl_exoncount.h"
 #include "spl_exoncount_rule.h"
@@ -336,15 +337,18 @@ struct spl_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // The tail of a counting pass (literal kernel, scan + SSE) runs on a stream of its own, so that the range kernel of the
     // NEXT pass -- of the next shard, sample or step -- starts as soon as this pass's range kernel is done: the tail is a
-    // few thousand waves waiting on memory and fits next to it.  Pass n's tail waits for ev_range[n % 4]; pass n's range
-    // kernel waits for ev_tail[(n - 2) % 4], the tail that last read the queue buffer and cleared the counter copy it is
-    // about to use (three counter copies per site table, two queue buffers per read set).  SPL_TAIL_STREAM=0 when the context
-    // is created: one stream.  (A cross-queue dependency still costs ~11 us between two range kernels on this stack, which
-    // leaves 4...9 % of the 20 % there is to gain: DESIGN.md section 6.)
-    hipStream_t tail = nullptr;
-    hipEvent_t ev_range[4] = {nullptr, nullptr, nullptr, nullptr}, ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t n_pass = 0;       // counting passes with a tail launched so far
-    bool tail_pending = false; // the main stream has not been made to wait for the last tail yet
+    // few thousand waves waiting on memory and fits next to it.  And a re-laid-out read set's slots kernel and range kernel run
+    // on a second LANE, a stream beside the main one, when the range kernel before them was another set's: the shards of a
+    // sample share nothing and count side by side.  Which lane a pass takes and which events it waits for -- every table and
+    // every read set remembers the range kernel and the tails that last touched it (three counter copies per site table, two
+    // queue buffers per read set) -- is spl_lanes.h's rule; pass n's events are ev_range / ev_tail[n % SPL_LANE_RING].
+    // SPL_TAIL_STREAM=0 when the context is created: one stream for everything.  (A cross-queue dependency costs ~6-11 us
+    // where a kernel stands behind it: DESIGN.md section 6.)
+    hipStream_t tail = nullptr, lane = nullptr;
+    hipEvent_t ev_range[SPL_LANE_RING] = {}, ev_tail[SPL_LANE_RING] = {}, ev_stail[SPL_LANE_RING] = {}, ev_main[4] = {}, ev_side[4] = {}; // (ev_tail / ev_stail: of the tails on the tail stream / on the second lane, each kind numbered by itself)
+    hipEvent_t range_used[SPL_LANE_RING] = {}; // the stop event pass n's range kernel recorded: ev_range[n % ..], or the stopwatch's
+    spl_lanes lanes = spl_lanes();
+    hipStream_t lane_stream(int s) const { return s == SPL_LANE_SIDE ? lane : s == SPL_LANE_TAIL ? tail : stream; }
     int32_t *d_err = nullptr;               // error word of launches that are not counting passes (spl_junctions); 16 bytes: the second
                                             // eight are spl_junctions' count of the N ops it sizes a fused set's table by
     // Read sets reach the device through a ring of page-locked staging buffers: the host packer (spl_pack.h) writes a piece of
@@ -436,6 +440,7 @@ struct spl_dsites {
     double *sse_cryptic = nullptr;      // SSE with --beta2Cryptic, written next to `sse` by the fused scan kernel
     bool sse_fused = false;             // the last counting pass computed beta2 / SSE (both settings) already
     const double *sse_view = nullptr;   // what spl_sse_download hands out
+    spl_lane_table lane_state = spl_lane_table(); // the range kernel and the tails that last touched this table (spl_lanes.h)
 };
 
 struct DeviceReads;
@@ -484,7 +489,7 @@ struct spl_dreads {
     uint32_t queue_cap = 0;
     mutable int queue_turn = 0;        // which of the two the next pass takes
     mutable bool queued_pass = false;  // the last counting pass over this read set had a literal kernel
-    mutable int64_t tail_pass = -1;    // the context's pass number of the last counting pass over this set that has a tail on the tail stream
+    mutable spl_lane_set lane_state = spl_lane_set(); // the set's lane and the tails that last touched it (spl_lanes.h)
     // The mate table of a fused set whose arrays have name keys (spl_mate_table): made on first use, kept with the set.  One word a
     // read of the arrays, a segment's at its reads' places, the mate as an index within the segment; three counters a segment.
     mutable uint32_t *mates = nullptr;
@@ -535,17 +540,28 @@ static int create_ctx(int device_id, void *stream, bool use_given, spl_ctx **out
     {
         const char *want_tail = getenv("SPL_TAIL_STREAM");
         if (!(want_tail && want_tail[0] == '0')) {
-            bool ok = hipStreamCreateWithFlags(&c->tail, hipStreamNonBlocking) == hipSuccess;
-            for (int i = 0; i < 4 && ok; ++i)
+            // (the lane is made right behind the main stream and the tail, at their priority level: the runtime deals a new
+            //  stream the least used of its hardware queues of that level -- four, with the caller's -- and two streams on one
+            //  queue run one behind the other: see Pipe::make)
+            bool ok = hipStreamCreateWithFlags(&c->tail, hipStreamNonBlocking) == hipSuccess &&
+                      hipStreamCreateWithFlags(&c->lane, hipStreamNonBlocking) == hipSuccess;
+            for (int i = 0; i < SPL_LANE_RING && ok; ++i)
                 // (no system-scope fences: what these events order is read on this device only)
                 ok = hipEventCreate(&c->ev_range[i]) == hipSuccess && // (a kernel's stop event: hipExtLaunchKernelGGL)
-                     hipEventCreateWithFlags(&c->ev_tail[i], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
+                     hipEventCreateWithFlags(&c->ev_tail[i], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess &&
+                     hipEventCreateWithFlags(&c->ev_stail[i], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
+            for (int i = 0; i < 4 && ok; ++i)
+                ok = hipEventCreateWithFlags(&c->ev_main[i], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess &&
+                     hipEventCreateWithFlags(&c->ev_side[i], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
             if (!ok) { // one stream it is
+                (void)hipGetLastError();
                 if (c->tail) (void)hipStreamDestroy(c->tail);
-                c->tail = nullptr;
+                if (c->lane) (void)hipStreamDestroy(c->lane);
+                c->tail = c->lane = nullptr;
             }
         }
     }
+    spl_lanes_init(&c->lanes, c->lane != nullptr, c->tail != nullptr, !c->own_stream);
     if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipMalloc((void **)&c->d_err, 16) != hipSuccess) {
         spl_destroy(c);
@@ -560,17 +576,31 @@ extern "C" int spl_create_on_stream(int device_id, void *hip_stream, spl_ctx **o
 
 static void free_stage(spl_ctx *c);
 
+// The host waits for the context's three streams (an object goes: whatever may still read it is over).
+static void sync_streams(spl_ctx *c)
+{
+    if (c->lane) (void)hipStreamSynchronize(c->lane);
+    if (c->tail) (void)hipStreamSynchronize(c->tail);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    spl_lanes_host_synced(&c->lanes);
+}
+
 extern "C" void spl_destroy(spl_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->tail) (void)hipStreamSynchronize(c->tail);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 4; ++i) {
+    sync_streams(c);
+    for (int i = 0; i < SPL_LANE_RING; ++i) {
         if (c->ev_range[i]) (void)hipEventDestroy(c->ev_range[i]);
         if (c->ev_tail[i]) (void)hipEventDestroy(c->ev_tail[i]);
+        if (c->ev_stail[i]) (void)hipEventDestroy(c->ev_stail[i]);
+    }
+    for (int i = 0; i < 4; ++i) {
+        if (c->ev_main[i]) (void)hipEventDestroy(c->ev_main[i]);
+        if (c->ev_side[i]) (void)hipEventDestroy(c->ev_side[i]);
     }
     if (c->tail) (void)hipStreamDestroy(c->tail);
+    if (c->lane) (void)hipStreamDestroy(c->lane);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->k_ev) (void)hipEventDestroy(e);
@@ -581,12 +611,45 @@ extern "C" void spl_destroy(spl_ctx *c)
     delete c;
 }
 
-// Everything queued on the main stream after this call runs after the tails of all counting passes launched so far.
+// What spl_lanes.h's rule asked for, in its order: waits and markers.
+static hipError_t run_plan(spl_ctx *c, const spl_lane_plan &p, int part = 0) // (part 1: what stands before the call's own launches, 2: between the range kernel and the tail, 3: behind them)
+{
+    if (p.n_ops > SPL_LANE_MAX_OPS) return hipErrorUnknown;
+    const int mid = p.n_ops - p.n_after - p.n_mid, after = p.n_ops - p.n_after;
+    for (int k = part == 2 ? mid : part == 3 ? after : 0; k < (part == 1 ? mid : part == 2 ? after : p.n_ops); ++k) {
+        const spl_lane_op &o = p.ops[k];
+        hipEvent_t ev = o.kind == SPL_LEV_RANGE ? c->range_used[o.seq % SPL_LANE_RING] : o.kind == SPL_LEV_TAIL ? c->ev_tail[o.seq % SPL_LANE_RING]
+                      : o.kind == SPL_LEV_STAIL ? c->ev_stail[o.seq % SPL_LANE_RING] : o.kind == SPL_LEV_MAIN ? c->ev_main[o.seq % 4] : c->ev_side[o.seq % 4];
+        const hipError_t e = o.op == SPL_LOP_WAIT ? hipStreamWaitEvent(c->lane_stream(o.stream), ev, 0) : hipEventRecord(ev, c->lane_stream(o.stream));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// Everything queued on the main stream after this call runs after everything launched so far: the tails of all counting passes
+// and whatever is on the second lane.
 static hipError_t join_tail(spl_ctx *c)
 {
-    if (!c->tail || !c->tail_pending) return hipSuccess;
-    c->tail_pending = false;
-    return hipStreamWaitEvent(c->stream, c->ev_tail[(c->n_pass - 1) % 4], 0);
+    spl_lane_plan p;
+    spl_lanes_join(&c->lanes, &p);
+    return run_plan(c, p);
+}
+
+// The same for an entry point that queues work of its own on the main stream behind it: the second lane's next launch stands
+// behind that work.
+static hipError_t join_for_main_work(spl_ctx *c, bool joined = true)
+{
+    spl_lane_plan p;
+    spl_lanes_main_work(&c->lanes, joined ? 1 : 0, &p);
+    return run_plan(c, p);
+}
+
+// The host has waited for the main stream behind a join.
+static hipError_t sync_main(spl_ctx *c)
+{
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) spl_lanes_host_synced(&c->lanes);
+    return e;
 }
 
 extern "C" int spl_sync(spl_ctx *c)
@@ -594,7 +657,7 @@ extern "C" int spl_sync(spl_ctx *c)
     if (!c) return spl_set_error(SPL_ERR_ARG, "spl_sync: null context");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(join_tail(c));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(sync_main(c));
     return SPL_OK;
 }
 
@@ -635,7 +698,9 @@ extern "C" int spl_pass_barrier(spl_ctx *c)
 {
     if (!c) return spl_set_error(SPL_ERR_ARG, "spl_pass_barrier: null context");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(join_tail(c));
+    spl_lane_plan p;
+    spl_lanes_barrier(&c->lanes, &p);
+    HIP_TRY(run_plan(c, p));
     return SPL_OK;
 }
 
@@ -643,6 +708,7 @@ extern "C" int spl_timer_begin(spl_ctx *c)
 {
     if (!c) return spl_set_error(SPL_ERR_ARG, "spl_timer_begin: null context");
     HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(join_tail(c)); // (the stretch begins behind whatever either lane still holds)
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
     return SPL_OK;
 }
@@ -654,6 +720,7 @@ extern "C" int spl_timer_end(spl_ctx *c, float *ms)
     HIP_TRY(join_tail(c));
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
     HIP_TRY(hipEventSynchronize(c->ev1));
+    spl_lanes_host_synced(&c->lanes);
     HIP_TRY(hipEventElapsedTime(ms, c->ev0, c->ev1));
     return SPL_OK;
 }
@@ -684,7 +751,8 @@ extern "C" int spl_layout_timing_collect(spl_ctx *c, float *ms_out, int capacity
 {
     if (!c || !n_out || (capacity > 0 && !ms_out)) return spl_set_error(SPL_ERR_ARG, "spl_layout_timing_collect: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(join_tail(c)); // (a launch's events are recorded on its own lane)
+    HIP_TRY(sync_main(c));
     const int n = std::min(c->l_used, capacity);
     for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], c->l_ev[2 * i], c->l_ev[2 * i + 1]));
     *n_out = n;
@@ -695,7 +763,8 @@ extern "C" int spl_kernel_timing_collect(spl_ctx *c, float *ms_out, int capacity
 {
     if (!c || !n_out || (capacity > 0 && !ms_out)) return spl_set_error(SPL_ERR_ARG, "spl_kernel_timing_collect: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(join_tail(c)); // (a launch's events are recorded on its own lane)
+    HIP_TRY(sync_main(c));
     const int n = std::min(c->k_used, capacity);
     for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&ms_out[i], c->k_ev[2 * i], c->k_ev[2 * i + 1]));
     *n_out = n;
@@ -999,8 +1068,7 @@ extern "C" void spl_sites_free(spl_ctx *c, spl_dsites *d)
 {
     if (!d) return;
     if (c) (void)hipSetDevice(c->device);
-    if (c && c->tail) (void)hipStreamSynchronize(c->tail); // (a tail may still be reading these buffers; hipFree itself waits
-    if (c && c->stream) (void)hipStreamSynchronize(c->stream); //  for the device, this makes it independent of that)
+    if (c) sync_streams(c); // (a tail or a lane may still be using these buffers; hipFree itself waits for the device, this makes it independent of that)
     devmem::put(d->slab);
     delete d;
 }
@@ -3295,19 +3363,19 @@ extern "C" int spl_sort_keys_device(spl_ctx *c, const uint64_t *keys, int64_t n,
     return SPL_OK;
 }
 
-// What a read set's device segments need between the arrays and the counters, on the context's main stream, nothing for the host
-// to wait for.  A fused set: ONE launch for the chunks' descriptors, the chunk order of the range kernel and that kernel's slots.
+// What a read set's device segments need between the arrays and the counters, on the stream given (the main stream, or the set's
+// lane), nothing for the host to wait for.  A fused set: ONE launch for the chunks' descriptors, the chunk order of the range kernel and that kernel's slots.
 // Any other: per group the chunks' descriptors and cost estimates (from their numbers of reads and ops), the chunk order from
 // the costs (host-packed chunks' are up already), then the layout kernel per group -- the records and the chunks' spl_chunk_meta
 // -- and the range kernel can follow it directly.
-static int launch_layout(spl_ctx *c, spl_dreads *d)
+static int launch_layout(spl_ctx *c, spl_dreads *d, hipStream_t st)
 {
     const uint32_t chunk = 1u << d->chunk_shift;
     if (d->fused) { // (one group holds every chunk: its descriptors, their order and the counting pass's slots in ONE launch; that pass makes its records itself)
         spl_dreads::Group &g = d->groups[0];
         const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
-        splprof::Scope prof("spl_chunk_slots_kernel", c->stream, 104.0 * (double)d->n_chunks);
-        const int rc = spl_dev_launch_chunk_slots(&src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->chunk_order, d->slots, c->stream);
+        splprof::Scope prof("spl_chunk_slots_kernel", st, 104.0 * (double)d->n_chunks);
+        const int rc = spl_dev_launch_chunk_slots(&src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->chunk_order, d->slots, st);
         if (rc) return spl_set_error(SPL_ERR_HIP, "chunk slots kernel launch: %s", hipGetErrorString((hipError_t)rc));
         return SPL_OK;
     }
@@ -3318,13 +3386,13 @@ static int launch_layout(spl_ctx *c, spl_dreads *d)
         lp.n_rec = g.src->n_rec; lp.n_ops = g.src->n_ops;
         lp.chunks = g.d_chunks; lp.rec_base = (uint8_t *)g.slab; lp.meta = d->meta;
         // (the chunks' descriptors hold offsets read from the arrays: made anew whenever the layout runs)
-        const int rc0 = spl_dev_launch_layout_map(&lp.src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->cost, c->stream);
+        const int rc0 = spl_dev_launch_layout_map(&lp.src, g.d_segs, (uint32_t)g.segs.size(), g.n_chunks, chunk, g.d_chunks, d->cost, st);
         if (rc0) return spl_set_error(SPL_ERR_HIP, "layout map kernel launch: %s", hipGetErrorString((hipError_t)rc0));
         lps.push_back(lp);
     }
     if (d->n_chunks) {
-        splprof::Scope prof("spl_chunk_slots_kernel", c->stream, 8.0 * (double)d->n_chunks);
-        const int rc = spl_dev_launch_chunk_order(d->cost, d->n_chunks, d->chunk_order, c->stream);
+        splprof::Scope prof("spl_chunk_slots_kernel", st, 8.0 * (double)d->n_chunks);
+        const int rc = spl_dev_launch_chunk_order(d->cost, d->n_chunks, d->chunk_order, st);
         if (rc) return spl_set_error(SPL_ERR_HIP, "chunk order kernel launch: %s", hipGetErrorString((hipError_t)rc));
     }
     size_t gi = 0;
@@ -3336,8 +3404,8 @@ static int launch_layout(spl_ctx *c, spl_dreads *d)
         const bool timed = c->k_on && (size_t)(2 * c->l_used + 1) < c->l_ev.size();
         int rc;
         { // (bytes: the arrays read once, 10 bytes a read and 4 an op)
-            splprof::Scope prof("spl_layout_kernel", c->stream, 10.0 * (double)n_reads + 4.0 * (double)n_ops);
-            rc = spl_dev_launch_layout(&lp, g.n_chunks, chunk, c->stream, timed ? (void *)c->l_ev[2 * c->l_used] : nullptr, timed ? (void *)c->l_ev[2 * c->l_used + 1] : nullptr);
+            splprof::Scope prof("spl_layout_kernel", st, 10.0 * (double)n_reads + 4.0 * (double)n_ops);
+            rc = spl_dev_launch_layout(&lp, g.n_chunks, chunk, st, timed ? (void *)c->l_ev[2 * c->l_used] : nullptr, timed ? (void *)c->l_ev[2 * c->l_used + 1] : nullptr);
         }
         if (timed) c->l_used++;
         if (rc) return spl_set_error(SPL_ERR_HIP, "layout kernel launch: %s", hipGetErrorString((hipError_t)rc));
@@ -3424,6 +3492,7 @@ static int finish_reads(spl_ctx *c, spl_dreads *d)
     if (q != hipSuccess) return spl_set_error(SPL_ERR_HIP, "read set upload: %s", hipGetErrorString(q));
     // segments on the device: record slots, the segment list and the chunk -> segment map of every group
     const uint32_t chunk = 1u << d->chunk_shift;
+    HIP_TRY(join_for_main_work(c, false)); // (a new set's first layout: on the main stream behind nothing but what is there; should the set go to the second lane later, that lane stands behind this)
     for (spl_dreads::Group &g : d->groups) {
         const size_t seg_bytes = align_up(sizeof(spl_layout_seg) * g.segs.size());
         e = d->fused ? hipSuccess : devmem::get((void **)&g.slab, SPL_LAYOUT_SLOT(chunk) * (size_t)g.n_chunks + 256, 'R');
@@ -3432,7 +3501,7 @@ static int finish_reads(spl_ctx *c, spl_dreads *d)
         g.d_chunks = (spl_layout_chunk *)((char *)g.d_segs + seg_bytes);
         HIP_TRY(hipMemcpyAsync(g.d_segs, g.segs.data(), sizeof(spl_layout_seg) * g.segs.size(), hipMemcpyHostToDevice, c->stream)); // (g.segs lives as long as the read set)
     }
-    const int rc = launch_layout(c, d);
+    const int rc = launch_layout(c, d, c->stream);
     if (rc) return rc;
     if (c->stage_timing)
         fprintf(stderr, "[spl_reads_finish] %zu chunks (%zu group(s) laid out on the device): control block (%.1f MB) at %.4f s, launched %.4f\n", n, d->groups.size(), off / 1e6,
@@ -3456,7 +3525,7 @@ static int unfuse(spl_ctx *c, spl_dreads *d)
     }
     if (rc == SPL_OK) {
         d->fused = false;
-        rc = launch_layout(c, d);
+        rc = launch_layout(c, d, c->stream);
     }
     if (rc != SPL_OK) {
         d->fused = true;
@@ -3473,11 +3542,13 @@ extern "C" int spl_reads_relayout(spl_ctx *c, spl_dreads *d)
     if (!d->finished) return spl_set_error(SPL_ERR_ARG, "spl_reads_relayout: the read set is not finished (spl_reads_finish)");
     if (d->groups.empty()) return spl_set_error(SPL_ERR_ARG, "spl_reads_relayout: no segment of this read set was laid out on the device");
     HIP_TRY(hipSetDevice(c->device));
-    // The literal kernel of the last pass over THIS set reads the records this rewrites: wait for that tail, not for all of them
-    // (another shard's tail may run beside this layout).  Pass q's range kernel waited for tail q - 2, so a tail three passes
-    // back and more is over as far as the main stream is concerned.
-    if (c->tail && d->tail_pass >= 0 && (uint64_t)d->tail_pass + 3 > c->n_pass) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_tail[d->tail_pass % 4], 0));
-    return launch_layout(c, d);
+    // The literal kernel of the last pass over THIS set reads what this rewrites: wait for that tail, not for all of them
+    // (another shard's tail may run beside this layout).  A fused set goes to the lane the last range kernel is not on, where
+    // its range kernel follows it: spl_lanes.h.
+    spl_lane_plan p;
+    spl_lanes_relayout(&c->lanes, &d->lane_state, d->fused ? 1 : 0, &p);
+    HIP_TRY(run_plan(c, p));
+    return launch_layout(c, d, c->lane_stream(p.lane));
 }
 
 static int source_of(const spl_reads *r, splpack::Source &src, int64_t *max_end, const char *who)
@@ -3816,10 +3887,11 @@ extern "C" int spl_reads_slots_download(spl_ctx *c, const spl_dreads *d, int64_t
     if (!d->n_chunks || (!order_out && !slots_out && !chunks_out)) return SPL_OK;
     if ((slots_out || chunks_out) && !d->fused) return spl_set_error(SPL_ERR_ARG, "spl_reads_slots_download: only a fused read set has slots and one list of chunk descriptors");
     HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(join_tail(c)); // (the slots kernel may have run on the second lane)
     if (order_out) HIP_TRY(hipMemcpyAsync(order_out, d->chunk_order, 4 * (size_t)d->n_slots, hipMemcpyDeviceToHost, c->stream));
     if (slots_out) HIP_TRY(hipMemcpyAsync(slots_out, d->slots, sizeof(spl_fused_slot) * (size_t)d->n_slots, hipMemcpyDeviceToHost, c->stream));
     if (chunks_out) HIP_TRY(hipMemcpyAsync(chunks_out, d->groups[0].d_chunks, sizeof(spl_layout_chunk) * (size_t)d->n_chunks, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(sync_main(c));
     return SPL_OK;
 }
 
@@ -3868,8 +3940,8 @@ extern "C" void spl_reads_free(spl_ctx *c, spl_dreads *d)
     if (!d) return;
     if (c) (void)hipSetDevice(c->device);
     if (c && c->copy) (void)hipStreamSynchronize(c->copy);
-    if (c && c->tail) (void)hipStreamSynchronize(c->tail); // (a tail may still be reading these buffers; hipFree itself waits
-    if (c && c->stream) (void)hipStreamSynchronize(c->stream); //  for the device, this makes it independent of that)
+    if (c) sync_streams(c); // (a tail or a lane may still be using these buffers; hipFree itself waits for the device, this makes it independent of that)
+    if (c && c->lanes.range_set == &d->lane_state) c->lanes.range_set = nullptr;
     for (spl_dreads::Segment &seg : d->segs) devmem::put(seg.slab);
     for (spl_dreads::Group &g : d->groups) { devmem::put(g.slab); devmem::put(g.d_segs); free_device_reads(g.src); }
     devmem::put(d->ctl);
@@ -3914,22 +3986,27 @@ extern "C" int spl_count_launch(spl_ctx *c, spl_dsites *ds, const spl_dreads *dr
     // (SPL_OPT_WAVE_AGGREGATION selects nothing: such a pass is the default one)
     const bool pairs = (o->flags & SPL_OPT_PAIR_KERNEL) != 0;
     const bool piped = c->tail != nullptr && !pairs && ds->region_clean[(ds->cur + 1) % 3];
-    if (piped) {
-        // the tail of the pass before the last one is the last thing that read the queue buffer and wrote the counter copy
-        // this pass takes (tails run in order on their stream): a wait that is over long before it is asked for
-        // The wait packet in the main queue costs 6 us between two range kernels.  (Measured and not kept: the HOST waiting
-        // instead -- 4 % faster in bench.py, but one millisecond of host jitter is one millisecond of idle GPU: 1 run in 12
-        // lost 25 % that way.)
-        if (c->n_pass >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_tail[(c->n_pass - 2) % 4], 0));
-    } else
-        HIP_TRY(join_tail(c)); // (pair kernel, first pass after one, or one stream: everything in order on the main stream)
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_count_launch: the read set is not finished (spl_reads_finish)");
+    // Piped: the range kernel on the read set's lane, behind the events the rule names (spl_lanes.h) -- the last range kernel on
+    // this table; the tail two passes back on the table, which cleared the counter copy this pass takes, and on the set, which
+    // read the queue buffer it writes -- of which only those are waited for that the lane does not stand behind already.  A
+    // wait packet costs 6 us where a range kernel stands behind it.  (Measured and not kept: the HOST waiting instead -- 4 %
+    // faster in bench.py, but one millisecond of host jitter is one millisecond of idle GPU: 1 run in 12 lost 25 % that way.)
+    // Otherwise (pair kernel, first pass after one, or one stream): the main stream behind everything, all in order on it.
+    spl_lane_plan plan;
+    spl_lanes_count(&c->lanes, &ds->lane_state, &dr->lane_state, piped ? 1 : 0, &plan);
+    HIP_TRY(run_plan(c, plan, 1));
+    struct Behind { spl_ctx *c; const spl_lane_plan &p; ~Behind() { (void)run_plan(c, p, 3); } } behind{c, plan}; // (however this call ends)
+    // the tail's stream (the tail stream; the second lane itself for a pass on it) and the event recorded behind the tail
+    const hipStream_t tail_s = piped ? c->lane_stream(plan.tail_stream) : c->stream;
+    const hipEvent_t ev_tail = !piped ? nullptr : plan.tail_stream == SPL_LANE_SIDE ? c->ev_stail[plan.tail_seq % SPL_LANE_RING] : c->ev_tail[plan.tail_seq % SPL_LANE_RING];
+    const hipStream_t ls = c->lane_stream(piped ? plan.lane : SPL_LANE_MAIN);
     const int next = (ds->cur + 1) % 3;
     if (ds->region_clean[next]) {
         ds->point_at(next);
         ds->region_clean[next] = false;
     } else if (int rc0 = spl_dev_launch_clear(ds->beta1, ds->counter_bytes, c->stream)) // (in place: the copy in use)
         return spl_set_error(SPL_ERR_HIP, "clear kernel launch: %s", hipGetErrorString((hipError_t)rc0));
-    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_count_launch: the read set is not finished (spl_reads_finish)");
     if (dr->fused && pairs) { const int rc0 = unfuse(c, const_cast<spl_dreads *>(dr)); if (rc0) return rc0; } // (the pair kernel reads records)
     uint32_t *const queue = dr->queue_turn ? dr->queue_alt : dr->queue;
     dr->queue_turn ^= 1;
@@ -3970,20 +4047,27 @@ extern "C" int spl_count_launch(spl_ctx *c, spl_dsites *ds, const spl_dreads *dr
     const bool timed = c->k_on && (size_t)(2 * c->k_used + 1) < c->k_ev.size();
     // (with the tail on its own stream that stream waits for the range kernel's OWN stop event: a marker packet behind the
     //  kernel -- hipEventRecord -- holds the main queue up for ~18 us when another queue depends on it)
-    hipEvent_t ev_stop = timed ? c->k_ev[2 * c->k_used + 1] : (piped ? c->ev_range[c->n_pass % 4] : nullptr);
+    hipEvent_t ev_stop = timed ? c->k_ev[2 * c->k_used + 1] : (piped ? c->ev_range[plan.pass % SPL_LANE_RING] : nullptr);
+    if (piped) c->range_used[plan.pass % SPL_LANE_RING] = ev_stop;
     int64_t alg = 0;
     if (splprof::g_on.load(std::memory_order_relaxed)) (void)spl_count_algorithmic_bytes(ds, dr, &alg);
     int rc;
-    { splprof::Scope prof("spl_count_ranges_kernel", c->stream, (double)alg); rc = spl_dev_launch_count(&p, &h, pairs, c->stream, &grid, &lds, timed ? (void *)c->k_ev[2 * c->k_used] : nullptr, (void *)ev_stop); }
+    { splprof::Scope prof("spl_count_ranges_kernel", ls, (double)alg); rc = spl_dev_launch_count(&p, &h, pairs, ls, &grid, &lds, timed ? (void *)c->k_ev[2 * c->k_used] : nullptr, (void *)ev_stop); }
     if (timed) c->k_used++;
     c->last_grid = grid;
     c->last_lds = lds;
     if (rc != 0) return spl_set_error(SPL_ERR_HIP, "count kernel launch: %s", hipGetErrorString((hipError_t)rc));
+    if (piped && grid <= 0) { // (nothing to launch: the events the rule has handed out are recorded all the same)
+        HIP_TRY(hipEventRecord(ev_stop, ls));
+        if (plan.tail_stream == SPL_LANE_TAIL) HIP_TRY(hipStreamWaitEvent(c->tail, ev_stop, 0));
+        HIP_TRY(run_plan(c, plan, 2));
+        HIP_TRY(hipEventRecord(ev_tail, tail_s));
+    }
     if (!pairs && grid > 0) { // queued reads through the literal kernel, then difference arrays -> counters
-        hipStream_t ts = c->stream;
+        const hipStream_t ts = tail_s;
         if (piped) {
-            HIP_TRY(hipStreamWaitEvent(c->tail, ev_stop, 0));
-            ts = c->tail;
+            if (plan.tail_stream == SPL_LANE_TAIL) HIP_TRY(hipStreamWaitEvent(c->tail, ev_stop, 0));
+            HIP_TRY(run_plan(c, plan, 2)); // (the tails before it on this table and on this set, where another stream ran them)
         }
         // the copy to clear: with the tail on its own stream the one after next (the next pass may be running by then),
         // otherwise the next one
@@ -4014,12 +4098,7 @@ extern "C" int spl_count_launch(spl_ctx *c, spl_dsites *ds, const spl_dreads *dr
         rc = spl_dev_launch_scan(&q, ts);
         if (rc != 0) return spl_set_error(SPL_ERR_HIP, "scan kernel launch: %s", hipGetErrorString((hipError_t)rc));
         ds->sse_fused = q.with_sse != 0;
-        if (piped) {
-            HIP_TRY(hipEventRecord(c->ev_tail[c->n_pass % 4], c->tail));
-            dr->tail_pass = (int64_t)c->n_pass;
-            c->n_pass++;
-            c->tail_pending = true;
-        }
+        if (piped) HIP_TRY(hipEventRecord(ev_tail, ts));
     }
     return SPL_OK;
 }
@@ -4034,7 +4113,7 @@ extern "C" int spl_sse_launch(spl_ctx *c, spl_dsites *ds, int cryptic)
         return SPL_OK;
     }
     ds->sse_view = ds->sse;
-    HIP_TRY(join_tail(c));
+    HIP_TRY(join_for_main_work(c));
     spl_sse_params p;
     memset(&p, 0, sizeof(p));
     p.n_sites = ds->n_sites; p.site_pos = ds->pos; p.part_off = ds->part_off; p.part_pos = ds->part_pos; p.part_site = ds->part_site;
@@ -4051,7 +4130,7 @@ static int check_device_error(spl_ctx *c, const spl_dsites *ds)
     int32_t err = 0;
     HIP_TRY(join_tail(c));
     HIP_TRY(hipMemcpyAsync(&err, ds->err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(sync_main(c));
     if (err & SPL_DEV_ERR_TABLE) return spl_set_error(SPL_ERR_HIP, "a wave's list of reads overflowed in the range kernel (internal error: results discarded)");
     if (err & SPL_DEV_ERR_RANGE)
         return spl_set_error(SPL_ERR_RANGE, "a read starts below 0 or ends beyond coordinate %d: split the shard (spliser_amd/shard.py)", SPL_COORD_MAX);
@@ -4081,7 +4160,7 @@ extern "C" int spl_sse_download(spl_ctx *c, const spl_dsites *ds, int64_t *b2s, 
         if (b2w) HIP_TRY(hipMemcpyAsync(b2w, ds->b2_weighted, n, hipMemcpyDeviceToHost, c->stream));
         if (sse) HIP_TRY(hipMemcpyAsync(sse, ds->sse_view, n, hipMemcpyDeviceToHost, c->stream));
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(sync_main(c));
     return SPL_OK;
 }
 
@@ -4105,6 +4184,7 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     c->junctions.clear();
     *n_out = 0;
     if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_junctions: the read set is not finished (spl_reads_finish)");
+    HIP_TRY(join_for_main_work(c)); // (the chunk descriptors it reads are the slots kernel's, which may have run on the second lane)
     // A FUSED set (all of it in one set of device arrays) is read as the arrays it is, by the chunk descriptors its finish() made:
     // it stays fused -- no record slots, no layout launch.  Its table is sized by the N ops that pass the intron filter (a count
     // over the chunks' ops first: an upper bound of the inserts), twice as many slots at least.  Every other set has packed
@@ -4801,6 +4881,14 @@ extern "C" int spl_name_key_host(const uint8_t *bytes, int64_t len, uint64_t *ou
 
 // The mate table of one segment's host arrays by the rule header: the compaction and a stable sort here, the pair stage's body as the
 // kernel runs it.  No GPU involved (test hook).  counts: the three counters, or null.
+extern "C" int spl_lanes_plan_host(int two_lanes, int tail_stream, int callers_stream, int n_tables, int n_sets, int64_t n_calls, const int32_t *calls, int64_t *out)
+{
+    if (n_calls < 0 || (n_calls && (!calls || !out))) return spl_set_error(SPL_ERR_ARG, "spl_lanes_plan_host: null argument");
+    if (spl_lanes_plan(two_lanes, tail_stream, callers_stream, n_tables, n_sets, n_calls, calls, out) != 0)
+        return spl_set_error(SPL_ERR_ARG, "spl_lanes_plan_host: a call of an unknown kind, or a table or set out of range (64 of each at most)");
+    return SPL_OK;
+}
+
 extern "C" int spl_mate_table_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint64_t *name_key, uint32_t *mate_out, int64_t *counts)
 {
     if (n_reads < 0 || n_reads > 0xfffffff0LL || (n_reads && (!pos || !flag || !cig_off || !name_key || !mate_out))) return spl_set_error(SPL_ERR_ARG, "spl_mate_table_host: null argument");
@@ -5088,7 +5176,7 @@ extern "C" int spl_literal_queue_size(spl_ctx *c, const spl_dreads *dr, int64_t 
     uint32_t total = 0; // (a word of the read set's own, written by the literal kernel of its last pass)
     HIP_TRY(join_tail(c));
     HIP_TRY(hipMemcpyAsync(&total, dr->queue_total, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(sync_main(c));
     *n_out = total;
     return SPL_OK;
 }
@@ -5125,8 +5213,8 @@ extern "C" int spl_sse(spl_ctx *c, const spl_sites *s, const uint32_t *beta1, co
     spl_dsites *ds = nullptr;
     int rc = spl_sites_upload(c, s, &ds);
     if (rc != SPL_OK) return rc;
-    hipError_t e = hipSuccess;
-    if (ds->n_sites) {
+    hipError_t e = join_for_main_work(c, false); // (a new table: behind nothing)
+    if (e == hipSuccess && ds->n_sites) {
         e = hipMemcpyAsync(ds->beta1, beta1, 4 * ds->n_sites, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(ds->beta2s, b2s_reads, 4 * ds->n_sites, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess && ds->n_part && dbl) e = hipMemcpyAsync(ds->dbl, dbl, 4 * ds->n_part, hipMemcpyHostToDevice, c->stream);
