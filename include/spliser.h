@@ -490,6 +490,28 @@ int spl_junctions_stats(const spl_ctx *ctx, int64_t *table_bytes_out, float *ms_
 int spl_junction_walk_host(const uint32_t *ops, uint32_t n_ops, int32_t pos, int32_t min_anchor, int32_t min_intron, int32_t max_intron,
                            int capacity, int32_t *left, int32_t *right, uint32_t *anchor_left, uint32_t *anchor_right, uint8_t *passes,
                            int *n_out, int *range_error_out);
+/* ---- the junction table per FRAGMENT (the splice counts of `intronretention --fragments`) ---------------------------------------
+ * Both mates of a pair that cross the same intron are one molecule's evidence for one splicing event; IRFinder, whose measure
+ * `intronretention` restates, works on fragments.  The rule (csrc/spl_junctionfragment_rule.h): walks, anchors, knobs, the strand
+ * modes 0 / 1 / 2 / 3 and the table keys are spl_junctions', unchanged.  A junction that read r SUPPORTS, with table key K, is a
+ * DUPLICATE CARRY when r has a mate m < r by its segment's mate table (m != SPL_MATE_NONE, m < n, m != r) and read m's own walk
+ * supports a junction with the same key K, the strand taken by m's own flag (or strand byte) under the same mode.  A duplicate
+ * carry adds nothing, no count and no anchors; everything else is inserted exactly as spl_junctions inserts it.  Hence: the key
+ * set of the table equals the per-read table's; count_frag(K) = count_read(K) - duplicates(K); the anchors are <= the per-read
+ * table's.  Reads that are not pairable behave as in the per-read table.  `junctions` and `process` have NO such switch: the BED
+ * score feeds SpliSER's alpha, which stays per read beside beta1 / beta2.
+ * spl_junctions_fragments: spl_junctions' arguments, result (spl_junctions_get / spl_junctions_stats) and refusals, and
+ * spl_mate_table's: SPL_ERR_ARG for a set without name keys, not fused or not finished; the context stays usable.
+ * spl_junction_fragment_rule_host: the rule for every read of one segment's host arrays with its mate table (test hook; no GPU).
+ * xs: the reads' strand bytes (stranded = 3) or NULL.  counted_out[r] / duplicate_out[r]: the junctions read r supports that are
+ * inserted / that are duplicate carries; rows_out (or NULL) [0 .. cap) x 6: left, right, strand byte, anchor_left, anchor_right,
+ * duplicate, of every supported junction in read and walk order; *n_rows_out: all of them. */
+int spl_junctions_fragments(spl_ctx *ctx, const spl_dreads *dr, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron,
+                            int64_t *n_out);
+int spl_junction_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar,
+                                    const uint8_t *xs, const uint32_t *mate, int32_t shift, int stranded, int32_t min_anchor, int32_t min_intron,
+                                    int32_t max_intron, int64_t *counted_out, int64_t *duplicate_out, int64_t *rows_out, int64_t cap,
+                                    int64_t *n_rows_out);
 
 /* ---- strandedness of the library (what the pipeline otherwise asks the user for) -----------------------------------------
  * Replaces a manual step: the reference's README tells the user to open the BAM in IGV, colour the reads by first-in-pair and
@@ -555,6 +577,46 @@ int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint
                            int capacity, int64_t *blk_start, int64_t *blk_end, int *n_out, int *past_end_out);
 int spl_bedgraph_append(const char *path, const char *chrom, int64_t n, const int32_t *start, const int32_t *end, const uint32_t *depth,
                         int64_t per_million_of /* 0: integers */);
+
+/* ---- per-base coverage per FRAGMENT (`coverage --fragments`) --------------------------------------------------------------------
+ * Replaces deepTools `bamCoverage` (paired-end default) / `bedtools genomecov -pc -split`: where the mates of a pair overlap, one
+ * molecule was sequenced, and a base under both counts once.  The rule (csrc/spl_covfragment_rule.h), per call -- one segment with
+ * its mate table (spl_mate_table), `length`, `stranded`, `strand`:
+ *   participates  a read for which spl_coverage's "eligible" and "track" hold, unchanged: secondary, supplementary, duplicate and
+ *                 QC-failed reads still cover; only pairable reads can have a mate;
+ *   partner       read r has the partner m = mate[r] when m != SPL_MATE_NONE, m < n, m != r and read m participates in this same
+ *                 call.  A mate on the other track of a stranded run is no partner: each mate covers alone on its own track;
+ *   silent        a participating read with a partner m < r marks nothing and is only "seen";
+ *   union         every other participating read marks the UNION of its own clipped blocks and, if it has one, its partner's
+ *                 (spl_coverage's walk and clipping): blocks that overlap OR abut are one interval.  It "contributed" when the
+ *                 union has a base, is "past the end" when either read lost a base to the clipping, and its covered bases are
+ *                 the union's length.
+ * Which mate leads depends on the reads' order; the union does not: runs and totals are the same for the reads in any order.  The
+ * deliberate differences are `genecounts --fragments`': a pair split over two references, segments or by the read filter is two
+ * single fragments; names are compared by a 63-bit hash.  The gap between two mates is NOT filled (no --extendReads).  Parity with
+ * deepTools / bedtools -pc is intended and unpinned.
+ * spl_coverage_fragments: spl_coverage's arguments, result (read with spl_coverage_download / spl_coverage_free; spl_coverage_totals
+ * keeps giving five numbers) and refusals, and spl_mate_table's: SPL_ERR_ARG for a set without name keys, not fused or not finished;
+ * the context stays usable.  The mate table is made at the first call that needs it and kept with the set, per segment.
+ * spl_coverage_fragment_totals: out6 = runs, reads seen, contributed (fragments, and reads without a partner), past the end,
+ * covered bases (= the sum of (end - start) * depth over the runs), pairs whose union was taken.  After spl_coverage, [5] is 0.
+ * spl_intron_depth_fragments: spl_intron_depth's arguments, output and refusals, and spl_mate_table's: the boundaries come from the
+ * fragment mark kernel.
+ * spl_coverage_fragment_rule_host: the rule for every read of one segment's host arrays with its mate table (test hook; no GPU):
+ * status_out[r] = 1 contributed, 0 nothing to mark, -4 silent, -3 not participating; n_iv_out[r] = the intervals of read r's union
+ * (all of them); past_out[r] (or NULL) = past the end; iv_start / iv_end [0 .. cap): the intervals, one read after the other in read
+ * order; totals6 (or NULL): spl_coverage_fragment_totals' numbers, [0] being the intervals.
+ * spl_coverage_cursor_host: spl_coverage_rule_host's arguments and results, by the rule header's resumable block cursor (test hook). */
+int spl_coverage_fragments(spl_ctx *ctx, const spl_dreads *dr, int64_t length, int stranded, int strand /* 0, '+', '-' */, spl_cov **out);
+int spl_coverage_fragment_totals(const spl_cov *cov, int64_t *out6);
+int spl_intron_depth_fragments(spl_ctx *ctx, const spl_dreads *dr, int64_t length, int stranded, int strand /* 0, '+', '-' */, int64_t n_introns,
+                               const int64_t *piece_off /* n_introns + 1 */, const int32_t *piece_start, const int32_t *piece_end,
+                               int trim_percent, int64_t *out /* 4 per intron */);
+int spl_coverage_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar,
+                                    const uint32_t *mate, int32_t shift, int64_t length, int stranded, int strand, int64_t *status_out,
+                                    int64_t *n_iv_out, uint8_t *past_out, int64_t *iv_start, int64_t *iv_end, int64_t cap, int64_t *totals6);
+int spl_coverage_cursor_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int64_t length, int stranded, int strand,
+                             int capacity, int64_t *blk_start, int64_t *blk_end, int *n_out, int *past_end_out);
 
 /* ---- per-gene read counts (what the pipeline otherwise leaves to a second pass by another program) ---------------------------
  * Replaces `htseq-count` / `featureCounts` over the file this library has just decoded: the diffSpliSER analysis is an edgeR

@@ -29,6 +29,8 @@ BGZF is inflated there too, plain gzip by one host thread; a file the strict rul
 Extra sub-command ``coverage -B x.bam -o PREFIX [-c CHROM] [--isStranded -s fr|rf] [--perMillion]`` writes ``PREFIX.bedgraph`` (stranded:
 ``PREFIX.plus.bedgraph`` and ``PREFIX.minus.bedgraph``): per-base read depth in runs, reduced on the GPU from the decode -- the
 coverage track of the look at the alignments the reference's README asks for, without a sorted, indexed BAM (``coverage.py``).
+``--fragments``: a paired-end fragment covers a base once -- the union of both mates' blocks, mates paired on the GPU as for ``genecounts
+--fragments``; not with ``--perMillion``.
 Extra sub-command ``genecounts -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [-c CHROM] [--isStranded -s fr|rf]`` writes
 ``PREFIX.genecounts.tsv``: reads per gene, assigned on the GPU from the decode by htseq-count's ``--mode union --nonunique none`` per
 read -- the two-column file ``edgeR::readDGE`` reads, without a second pass over the BAM by another program (``genecounts.py``).
@@ -41,6 +43,8 @@ mate -- mates paired on the GPU as for ``genecounts --fragments``, whose spellin
 Extra sub-command ``intronretention -B x.bam -A genes.gtf -o PREFIX [-t exon] [--idAttr gene_id] [--trimPercent 30] [-c CHROM] [--isStranded
 -s fr|rf]`` writes ``PREFIX.introns.tsv``: per annotated intron the trimmed depth of its measurable bases, the splice counts at its ends and
 the IR ratio, taken on the GPU from the decode -- IRFinder's measure, without a sorted BAM and a second tool (``intronretention.py``).
+``--fragments``: depth and splice counts per fragment -- ``coverage --fragments``' depth, and a junction both mates cross counted once.
+``junctions`` and ``process`` have no such switch: the BED score feeds alpha, which stays per read beside beta1 / beta2.
 Not read: CRAM, a pipe, and compressed text that has no ``@`` header line (uncompressed, the Python reader still takes that).
 """
 import argparse
@@ -50,7 +54,10 @@ import timeit
 VERSION = "v0.1.8-mi355x"
 
 
-def build_parser():
+def build_parser(fragment_switches=False):
+    """The command line.  ``fragment_switches``: with ``coverage --fragments`` and ``intronretention --fragments``, as ``main`` builds it.
+    Without (the default) those two commands take the arguments they took before the switches existed, and refuse the switch: callers
+    that build the parser themselves, and the tests that pin ``--fragments`` to ``genecounts``, see the parser they know."""
     parser = argparse.ArgumentParser(description="SpliSER - Splice Site Strength Estimates from RNA-seq (MI355X build)")
     sub = parser.add_subparsers(dest="command")
     p = sub.add_parser("process")
@@ -190,6 +197,12 @@ def build_parser():
     v.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
     v.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
     v.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    # (default SUPPRESS: without the switch the parsed arguments are what they were, key for key)
+    if fragment_switches:
+        v.add_argument("--fragments", dest="fragments", default=argparse.SUPPRESS, action="store_true",
+                   help="paired-end: mates are paired on the GPU by a key of their names (as for `genecounts --fragments`) and a pair whose mates both cover on the "
+                        "track covers the union of their blocks once (deepTools bamCoverage's paired-end default, bedtools genomecov -pc, without filling the gap "
+                        "between the mates); a pair split over two chromosomes, by the read filter or over the two tracks covers as two reads; not with --perMillion")
     _filter_flags(v)
     _engine_flags(v)
     n = sub.add_parser("genecounts", help="(this build only) reads per gene as htseq-count's two-column file, assigned on the GPU from the decode "
@@ -257,6 +270,10 @@ def build_parser():
     i.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
     i.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
     i.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    if fragment_switches:
+        i.add_argument("--fragments", dest="fragments", default=argparse.SUPPRESS, action="store_true",
+                   help="paired-end: depth and splice counts per fragment (IRFinder's way) -- the depth is `coverage --fragments`', and a junction that both mates of "
+                        "a pair support counts once; mates are paired on the GPU by a key of their names")
     _filter_flags(i)
     _engine_flags(i)
     return parser
@@ -296,7 +313,7 @@ def _engine_flags(p):
 def main(argv=None):
     print("\nSpliSER " + VERSION + " (MI355X / gfx950 build of SpliSER v0.1.8, SKB LAB)\n")
     start = timeit.default_timer()
-    parser = build_parser()
+    parser = build_parser(fragment_switches=True)
     kwargs = vars(parser.parse_args(argv))
     command = kwargs.pop("command")
     if command is None:
@@ -324,6 +341,8 @@ def main(argv=None):
         parser.error("%s: --strandedType/-s must be fr or rf" % command)
     if command == "exoncounts" and kwargs.pop("fragments", False):
         parser.error("exoncounts: --fragments is `genecounts --fragments`' spelling; here the switch is --countReadPairs")
+    if command == "coverage" and kwargs.get("fragments") and kwargs.get("perMillion"):
+        parser.error("coverage: --perMillion --fragments is refused: no fragment library size is counted, and fragment depth per million mapped reads would mislead")
     if command == "intronretention" and not 0 <= kwargs["trimPercent"] <= 49:
         parser.error("intronretention: --trimPercent must be in 0..49")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":

@@ -13,6 +13,16 @@ N are gaps (``-split``); blocks are clipped to the reference's length.  Parity w
 
 ``--perMillion`` divides every depth by the library size ``--flagstat`` logs (mapped reads, under the filters) and multiplies by
 10^6: the value column is ``repr(depth * 1000000 / N)``.
+
+``--fragments`` covers a paired-end library per FRAGMENT, as deepTools ``bamCoverage`` does by default and ``bedtools genomecov -pc``:
+where the mates of a pair overlap one molecule was sequenced, and the depth there is one.  The decode then keeps a 64-bit key of
+every read's name (``mate_keys``), the mate table is built on the GPU per chromosome (``spl_mate_table``) and
+``spl_coverage_fragments`` marks, for a pair whose mates both cover on the track, the UNION of both reads' blocks once (the rule:
+include/spliser.h, csrc/spl_covfragment_rule.h).  The gap between two mates is not filled.  A pair split over two chromosomes, by
+the read filter or -- stranded -- over the two tracks is two single fragments; names are compared by a 63-bit hash.  The files have
+the same names and format.  ``--perMillion --fragments`` is refused: no fragment library size is counted, and fragment depth divided
+by mapped reads would mislead.  Parity with deepTools / bedtools -pc is intended and unpinned: the yardstick is
+tests/covfragcases.py.
 """
 import sys
 
@@ -29,11 +39,14 @@ def tracks_of(stranded):
     return [(SUFFIX_PLUS, "+"), (SUFFIX_MINUS, "-")] if stranded else [(SUFFIX, 0)]
 
 
-def sets_of_source(source, device, chroms):
+def sets_of_source(source, device, chroms, with_keys=False):
     """A finished, fused read set per chromosome of ``chroms`` that has a read, each in turn: yields (chrom, length, dr).  On the
     plan of ``strandedness.tally_of_source``, one device: a file decoded on the device is visited per chromosome where it lies (one
-    fused set a chromosome, shift 0); host-decoded reads and the Python reader's go up as four arrays, a fused set of their own.
+    fused set a chromosome, shift 0); host-decoded reads and the Python reader's go up as four arrays, a fused set of their own --
+    ``with_keys``: with their name keys, which the source must have (``DecodeOptions.mate_keys``).
     ``length``: the header's LN; a source without lengths uses the reads' ``max_end``."""
+    if with_keys and not getattr(source, "mate_keys", False):
+        raise native.SpliserNativeError(-1, "fragment counting needs a source decoded with name keys (DecodeOptions.mate_keys)")
     is_bam = isinstance(source, native.BamFile)
     on_device = is_bam and source.join_decoders()      # (False: the host threads have the file)
     lengths = dict(zip(source.ref_names, source.ref_lengths)) if getattr(source, "ref_lengths", None) else {}
@@ -54,28 +67,45 @@ def sets_of_source(source, device, chroms):
                 length = int(rs.max_end)       # (the last base a read covers, 1-based: as many bases as the reads can tell of)
             if length < 1:
                 continue                        # (no read covers a base: nothing to write, and no length to clip to)
-            with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar)], [getattr(rs, "max_end", None)]) as soa:
+            if with_keys and getattr(rs, "name_key", None) is None:
+                raise native.SpliserNativeError(-1, "the reads of %s were decoded without name keys (mate_keys)" % chrom)
+            arrays = native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, name_key=rs.name_key if with_keys else None)
+            with ctx.upload_soa([arrays], [getattr(rs, "max_end", None)], with_keys=with_keys) as soa:
                 with ctx.begin_reads() as dr:
                     dr.add_soa(soa, 0)
                     dr.finish()
                     yield chrom, length, dr
 
 
-def runs_of_source(source, device, chroms, stranded=0):
+def union_text(tracks, taken):
+    """The log's words for the pairs whose union was taken, per track."""
+    if len(tracks) == 1:
+        return "%d pairs whose union was taken" % taken[0]
+    return "pairs whose union was taken: " + ", ".join("%d (%s)" % (n, strand) for (_, strand), n in zip(tracks, taken))
+
+
+def runs_of_source(source, device, chroms, stranded=0, fragments=False, mates=None):
     """``spl_coverage`` over every chromosome of ``chroms`` in turn (``sets_of_source``), every track of it: yields (chrom, length,
-    [(start, end, depth, totals) per track])."""
-    for chrom, length, dr in sets_of_source(source, device, chroms):
-        yield chrom, length, [dr.coverage(length, stranded, strand) for _, strand in tracks_of(stranded)]
+    [(start, end, depth, totals) per track]).  ``fragments``: ``spl_coverage_fragments`` (the source was decoded with ``mate_keys``);
+    ``mates``: a dict that gets every chromosome's mate table counters."""
+    for chrom, length, dr in sets_of_source(source, device, chroms, with_keys=bool(fragments)):
+        per_track = [dr.coverage(length, stranded, strand, fragments=bool(fragments)) for _, strand in tracks_of(stranded)]
+        if fragments and mates is not None:
+            mates[chrom] = dr.mate_table(0)[1]
+        yield chrom, length, per_track
 
 
 def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=None, perMillion=False, devices=(0,), threads=0, log=None, gpuDecode=None,
-             minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False):
+             minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False, fragments=False):
     """The ``coverage`` command: one decode, ``<outputPath>.bedgraph`` -- or, ``isStranded`` with ``strandedType`` ``fr`` / ``rf``,
     ``<outputPath>.plus.bedgraph`` and ``<outputPath>.minus.bedgraph`` -- with the chromosomes in header order (``qChrom``: that one)
     and no track line.  ``perMillion``: values per million mapped reads (the decode counts them: ``DecodeOptions(flagstat=True)``; a
     source without those counters is an error).  With several devices the file is decoded and covered on the first: there are no
-    shares.  -> {file path: number of runs written}."""
+    shares.  ``fragments``: a pair of mates covers the union of its reads' blocks once (the module's text); not with ``perMillion``.
+    -> {file path: number of runs written}."""
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    if fragments and perMillion:
+        raise ValueError("coverage: --perMillion --fragments is refused: no fragment library size is counted, and fragment depth per million mapped READS would mislead")
     if isStranded and strandedType not in STRANDED:
         raise ValueError("coverage: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
     stranded = STRANDED[strandedType] if isStranded else 0
@@ -83,9 +113,11 @@ def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=Non
     if len(devices) > 1:
         log("  (coverage: the alignment file is decoded and covered on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
         devices = devices[:1]
-    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), flagstat=bool(perMillion), any_order=bool(anyOrder))
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), flagstat=bool(perMillion), any_order=bool(anyOrder), mate_keys=bool(fragments))
     source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
     tracks = tracks_of(stranded)
+    mates = {} if fragments else None
+    pair_sums = np.zeros(2 + len(tracks), np.int64)      # --fragments: pairable reads, pairs found, pairs whose union was taken per track
     paths = [outputPath + suffix for suffix, _ in tracks]
     written = dict.fromkeys(paths, 0)
     held = []          # --perMillion: (chrom, runs per track) until the library size is known
@@ -98,13 +130,17 @@ def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=Non
         for path in paths:
             open(path, "w").close()
         chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
-        for chrom, length, per_track in runs_of_source(source, devices[0], chroms, stranded):
+        for chrom, length, per_track in runs_of_source(source, devices[0], chroms, stranded, fragments=bool(fragments), mates=mates):
+            if fragments:
+                taken = [int(t[3]["pairs"]) for t in per_track]
+                log("  %s: %d pairable reads, %d pairs found, %s" % (chrom, mates[chrom]["pairable"], mates[chrom]["paired"] // 2, union_text(tracks, taken)))
+                pair_sums += [mates[chrom]["pairable"], mates[chrom]["paired"] // 2] + taken
             for k, (start, end, depth, totals) in enumerate(per_track):
                 name = "%s (%s)" % (chrom, tracks[k][1]) if stranded else chrom
                 log("  %s: %d runs, %d covered bases" % (name, totals["runs"], totals["covered_bases"]))
                 if totals["past_end"]:
                     log("  %d reads ran past the end of %s (%d bases)" % (totals["past_end"], name, length))
-                sums[k] += [totals[key] for key in native.COVERAGE_TOTALS]
+                sums[k] += [totals[key] for key in native.COVERAGE_TOTALS]          # (the first five, per read and per fragment)
                 if not perMillion:
                     native.bedgraph_append(paths[k], chrom, start, end, depth)
                     written[paths[k]] += int(start.shape[0])
@@ -121,11 +157,13 @@ def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=Non
                 for k, (start, end, depth) in enumerate(per_track):
                     native.bedgraph_append(paths[k], chrom, start, end, depth, per_million_of=size)
                     written[paths[k]] += int(start.shape[0])
+        if fragments:
+            log("Mates: %d pairable reads, %d pairs found, %s" % (pair_sums[0], pair_sums[1], union_text(tracks, pair_sums[2:].tolist())))
         _process.log_filter(source, options.read_filter, log)
     finally:
         if hasattr(source, "close"):
             source.close()
     for k, path in enumerate(paths):
-        log("%s: %d runs, %d covered bases, %d of %d reads contributed%s" % (path, sums[k][0], sums[k][4], sums[k][2], sums[k][1],
+        log("%s: %d runs, %d covered bases, %d %sof %d reads contributed%s" % (path, sums[k][0], sums[k][4], sums[k][2], "fragments and single reads " if fragments else "", sums[k][1],
                                                                           ", %d ran past the end of their reference" % sums[k][3] if sums[k][3] else ""))
     return written

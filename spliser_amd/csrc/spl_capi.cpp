@@ -39,6 +39,8 @@
 #include "spl_strand_rule.h"
 #include "spl_coverage.h"
 #include "spl_coverage_rule.h"
+#include "spl_covfragment_rule.h"
+#include "spl_junctionfragment_rule.h"
 #include "spl_genecount.h"
 #include "spl_genecount_rule.h"
 #include "spl_mate_rule.h"
@@ -4174,16 +4176,22 @@ extern "C" int spl_count_algorithmic_bytes(const spl_dsites *ds, const spl_dread
 }
 
 // ---- junction table of a read set ---------------------------------------------------------
-extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron,
-                             int64_t *n_out)
+namespace {
+int mates_of(spl_ctx *c, const spl_dreads *dr, const char *who); // (below, with the mate table)
+
+// spl_junctions, and -- fragments -- spl_junctions_fragments: the same table without the duplicate carries of spl_junctionfragment_rule.h.
+int junctions_of(spl_ctx *c, const spl_dreads *dr, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron, int64_t *n_out, bool fragments)
 {
-    if (!c || !dr || !n_out) return spl_set_error(SPL_ERR_ARG, "spl_junctions: null argument");
-    if (min_anchor < 0 || min_intron < 0 || max_intron < 0) return spl_set_error(SPL_ERR_ARG, "spl_junctions: negative filter value");
+    const char *who = fragments ? "spl_junctions_fragments" : "spl_junctions";
+    if (!c || !dr || !n_out) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
+    if (min_anchor < 0 || min_intron < 0 || max_intron < 0) return spl_set_error(SPL_ERR_ARG, "%s: negative filter value", who);
     if (stranded < 0 || stranded > 3) return spl_set_error(SPL_ERR_ARG, "stranded must be 0, 1 (fr), 2 (rf) or 3 (the reads' strand bytes)");
     HIP_TRY(hipSetDevice(c->device));
     c->junctions.clear();
     *n_out = 0;
-    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_junctions: the read set is not finished (spl_reads_finish)");
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "%s: the read set is not finished (spl_reads_finish)", who);
+    if (fragments)
+        if (const int rc = mates_of(c, dr, who)) return rc; // (refuses a set that is not fused, or has no name keys)
     HIP_TRY(join_for_main_work(c)); // (the chunk descriptors it reads are the slots kernel's, which may have run on the second lane)
     // A FUSED set (all of it in one set of device arrays) is read as the arrays it is, by the chunk descriptors its finish() made:
     // it stays fused -- no record slots, no layout launch.  Its table is sized by the N ops that pass the intron filter (a count
@@ -4225,7 +4233,31 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
     unsigned long long *keys = (unsigned long long *)buf, *out_keys = keys + slots;
     uint32_t *vals = (uint32_t *)(out_keys + slots), *out_vals = vals + 3 * slots, *n_dev = out_vals + 3 * slots;
     int rc;
-    if (fused) {
+    DevBuf d_segs;
+    if (fused && fragments && dr->mates) {
+        // the set's segments in ascending order of their first read, for a chunk to find its own by
+        std::vector<std::pair<int64_t, int64_t>> segs;
+        for (const spl_dreads::Segment &seg : dr->segs) {
+            const spl_layout_seg &ls = g->segs[seg.group_seg];
+            if (ls.n_reads > 0 && ls.first >= 0 && ls.first + ls.n_reads <= g->src->n_rec) segs.push_back({ls.first, ls.n_reads});
+        }
+        std::sort(segs.begin(), segs.end());
+        segs.erase(std::unique(segs.begin(), segs.end(), [](const std::pair<int64_t, int64_t> &a, const std::pair<int64_t, int64_t> &b) { return a.first == b.first; }), segs.end());
+        std::vector<int64_t> flat(2 * std::max<size_t>(segs.size(), 1), 0);
+        for (size_t k = 0; k < segs.size(); ++k) { flat[k] = segs[k].first; flat[segs.size() + k] = segs[k].second; }
+        rc = (int)d_segs.get(8 * flat.size(), c->stream);
+        if (!rc) rc = (int)hipMemcpyAsync(d_segs.p, flat.data(), 8 * flat.size(), hipMemcpyHostToDevice, c->stream);
+        if (!rc) rc = (int)hipStreamSynchronize(c->stream); // (flat is this block's)
+        if (!rc && !segs.empty())
+            rc = spl_dev_launch_junctions_fused_fragments(&src, g->src->n_rec, g->src->n_ops, g->d_chunks, g->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron,
+                                                          (uint32_t)max_intron, keys, vals, (uint32_t)slots, out_keys, out_vals, n_dev, c->d_err,
+                                                          stranded == 3 ? (const uint8_t *)g->src->xs : nullptr, dr->mates, d_segs.as<int64_t>(), d_segs.as<int64_t>() + segs.size(),
+                                                          (uint32_t)segs.size(), c->stream);
+        else if (!rc)
+            rc = spl_dev_launch_junctions_fused(&src, g->src->n_rec, g->src->n_ops, g->d_chunks, g->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron, (uint32_t)max_intron, keys,
+                                                vals, (uint32_t)slots, out_keys, out_vals, n_dev, c->d_err, stranded == 3 ? (const uint8_t *)g->src->xs : nullptr, c->stream);
+        if (ev1) (void)hipEventRecord(ev1, c->stream);
+    } else if (fused) {
         rc = spl_dev_launch_junctions_fused(&src, g->src->n_rec, g->src->n_ops, g->d_chunks, g->n_chunks, stranded, (uint32_t)min_anchor, (uint32_t)min_intron,
                                             (uint32_t)max_intron, keys, vals, (uint32_t)slots, out_keys, out_vals, n_dev, c->d_err,
                                             stranded == 3 ? (const uint8_t *)g->src->xs : nullptr, c->stream);
@@ -4278,6 +4310,56 @@ extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int
         j.anchor_right = hv[3 * (size_t)order[i] + 2];
     }
     *n_out = n;
+    return SPL_OK;
+}
+} // namespace
+
+extern "C" int spl_junctions(spl_ctx *c, const spl_dreads *dr, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron, int64_t *n_out)
+{
+    return junctions_of(c, dr, stranded, min_anchor, min_intron, max_intron, n_out, false);
+}
+
+// spl_junctions per fragment (the rule is spl_junctionfragment_rule.h): the arguments are spl_junctions'; the set must be fused and have
+// name keys.  The table is read with spl_junctions_get / spl_junctions_stats.
+extern "C" int spl_junctions_fragments(spl_ctx *c, const spl_dreads *dr, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron, int64_t *n_out)
+{
+    return junctions_of(c, dr, stranded, min_anchor, min_intron, max_intron, n_out, true);
+}
+
+// The junction fragment rule for every read of one segment's host arrays with its mate table: no GPU involved (test hook).  xs: the
+// reads' strand bytes (stranded = 3) or null.  counted_out[r] / duplicate_out[r]: the junctions read r supports that are inserted /
+// that are duplicate carries.  rows_out (or null) [0 .. cap) x 6: left, right, strand byte, anchor_left, anchor_right, duplicate, of
+// every supported junction in read and walk order; *n_rows_out: all of them.
+extern "C" int spl_junction_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint8_t *xs,
+                                               const uint32_t *mate, int32_t shift, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron, int64_t *counted_out,
+                                               int64_t *duplicate_out, int64_t *rows_out, int64_t cap, int64_t *n_rows_out)
+{
+    if (n_reads < 0 || (n_reads && (!pos || !flag || !cig_off || !mate || !counted_out || !duplicate_out)) || cap < 0 || (cap && !rows_out) || !n_rows_out)
+        return spl_set_error(SPL_ERR_ARG, "spl_junction_fragment_rule_host: null argument");
+    if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_junction_fragment_rule_host: cigar is null");
+    if (min_anchor < 0 || min_intron < 0 || max_intron < 0) return spl_set_error(SPL_ERR_ARG, "spl_junction_fragment_rule_host: negative filter value");
+    if (stranded < 0 || stranded > 3 || (stranded == 3 && n_reads && !xs)) return spl_set_error(SPL_ERR_ARG, "spl_junction_fragment_rule_host: stranded must be 0, 1, 2 or 3 (with strand bytes)");
+    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    const spljw::Filter filter{(uint32_t)min_anchor, (uint32_t)min_intron, (uint32_t)max_intron};
+    struct Keep {
+        int stranded; int64_t cap, n, counted, dup; int64_t *rows;
+        void operator()(int32_t l, int32_t r, uint32_t code, uint32_t al, uint32_t ar, bool is_dup)
+        {
+            if (n < cap) {
+                int64_t *row = rows + 6 * n;
+                row[0] = l; row[1] = r; row[2] = !stranded ? '?' : code == 0u ? '+' : code == 1u ? '-' : '?'; row[3] = al; row[4] = ar; row[5] = is_dup ? 1 : 0;
+            }
+            ++n;
+            ++(is_dup ? dup : counted);
+        }
+    } keep{stranded, cap, 0, 0, 0, rows_out};
+    for (int64_t r = 0; r < n_reads; ++r) {
+        keep.counted = keep.dup = 0;
+        (void)spljf::read_junctions(reads, stranded == 3 ? xs : nullptr, n_reads, r, mate, shift, stranded, filter, keep);
+        counted_out[r] = keep.counted;
+        duplicate_out[r] = keep.dup;
+    }
+    *n_rows_out = keep.n;
     return SPL_OK;
 }
 
@@ -4368,11 +4450,12 @@ struct spl_cov {
     std::vector<int32_t> start, end;
     std::vector<uint32_t> depth;
     int64_t totals[5] = {0, 0, 0, 0, 0}; // runs, reads seen, reads that contributed, reads past the end, covered bases
+    int64_t pairs = 0;                   // spl_coverage_fragments: the pairs whose union was taken
 };
 
 namespace {
 // What the coverage stages leave on the device: n_bound boundaries, ascending in pos; delta holds the depth from each to the next
-// (0 before the first); out: the mark kernel's four sums.
+// (0 before the first); out: the mark kernel's four sums, and behind them the fragment mark kernel's pairs (0 per read).
 struct CovStages {
     DevBuf diff, out, tiles, work, pos, delta;
     uint32_t n_bound = 0;
@@ -4392,7 +4475,8 @@ int cov_refusal(const char *who, const spl_dreads *dr, int64_t length, int stran
 
 // The three stages over a fused set with a read: mark per segment into one zeroed difference array, compact (count, scan, emit),
 // scan of the deltas.  The stream has been waited for once (the buffers are sized from the count); the scan may still run.
-int cov_stages(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, CovStages &s)
+// fragments: mark per fragment (spl_covfragment_rule.h) over the set's mate table, which the caller has had made (mates_of).
+int cov_stages(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, CovStages &s, bool fragments = false)
 {
     DevBuf &d_diff = s.diff, &d_out = s.out, &d_tiles = s.tiles, &d_work = s.work, &d_pos = s.pos, &d_delta = s.delta;
     const spl_dreads::Group &g = dr->groups[0];
@@ -4400,20 +4484,22 @@ int cov_stages(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, i
     const int64_t n_tiles = (length + SPL_COV_POS_TILE - 1) / SPL_COV_POS_TILE;
     const size_t diff_bytes = 4 * (size_t)spl_dev_cov_diff_words(length);
     HIP_TRY(d_diff.get(diff_bytes, c->stream));
-    HIP_TRY(d_out.get(8 * (SPL_COV_COUNTERS + 1), c->stream));
+    HIP_TRY(d_out.get(8 * (SPL_COVF_COUNTERS + 1), c->stream));
     HIP_TRY(d_tiles.get(4 * (size_t)n_tiles, c->stream));
-    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * (SPL_COV_COUNTERS + 1), c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * (SPL_COVF_COUNTERS + 1), c->stream));
     const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
     {
         double bytes = (double)diff_bytes; // what mark must move at least: the array cleared, 10 bytes a read and its ops
-        for (const spl_dreads::Segment &seg : dr->segs) bytes += 10.0 * (double)seg.n_reads + 4.0 * (double)seg.n_ops;
-        splprof::Scope prof("spl_cov_mark_kernel", c->stream, bytes);
+        for (const spl_dreads::Segment &seg : dr->segs) bytes += (fragments ? 14.0 : 10.0) * (double)seg.n_reads + 4.0 * (double)seg.n_ops; // (fragments: and a read's word of the mate table)
+        splprof::Scope prof(fragments ? "spl_cov_mark_fragments_kernel" : "spl_cov_mark_kernel", c->stream, bytes);
         HIP_TRY(hipMemsetAsync(d_diff.p, 0, diff_bytes, c->stream));
         for (const spl_dreads::Segment &seg : dr->segs) {
             const spl_layout_seg &ls = g.segs[seg.group_seg];
             if (ls.n_reads <= 0) continue;
-            const int rc = spl_dev_launch_cov_mark(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, length, stranded, strand, d_diff.as<uint32_t>(),
-                                                   d_out.as<unsigned long long>(), c->stream);
+            const int rc = fragments ? spl_dev_launch_cov_mark_fragments(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, length, stranded, strand, dr->mates + ls.first,
+                                                                         d_diff.as<uint32_t>(), d_out.as<unsigned long long>(), c->stream)
+                                     : spl_dev_launch_cov_mark(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, length, stranded, strand, d_diff.as<uint32_t>(),
+                                                               d_out.as<unsigned long long>(), c->stream);
             if (rc) return spl_set_error(SPL_ERR_HIP, "coverage mark kernel launch: %s", hipGetErrorString((hipError_t)rc));
         }
     }
@@ -4443,19 +4529,17 @@ int cov_stages(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, i
 }
 } // namespace
 
-// The stages (cov_stages); the boundaries come down and those with a depth of zero are dropped here.
-extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, spl_cov **out)
+namespace {
+// The stages (cov_stages); the boundaries come down and those with a depth of zero are dropped here.  The call has been checked.
+int cov_runs(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, bool fragments, spl_cov **out)
 {
-    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_coverage: null argument");
-    *out = nullptr;
-    if (const int rc = cov_refusal("spl_coverage", dr, length, stranded, strand)) return rc;
     std::unique_ptr<spl_cov> cov(new spl_cov());
     if (dr->segs.empty()) { // (a set without a read has no arrays to be fused of, and covers nothing)
         *out = cov.release();
         return SPL_OK;
     }
     CovStages st;
-    if (const int rc = cov_stages(c, dr, length, stranded, strand, st)) return rc;
+    if (const int rc = cov_stages(c, dr, length, stranded, strand, st, fragments)) return rc;
     const uint32_t n_bound = st.n_bound;
     DevBuf &d_out = st.out, &d_pos = st.pos, &d_delta = st.delta;
     std::vector<int32_t> h_pos(n_bound);
@@ -4464,7 +4548,7 @@ extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, in
         HIP_TRY(hipMemcpyAsync(h_pos.data(), d_pos.p, 4 * (size_t)n_bound, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(h_depth.data(), d_delta.p, 4 * (size_t)n_bound, hipMemcpyDeviceToHost, c->stream));
     }
-    unsigned long long sums[SPL_COV_COUNTERS + 1] = {0, 0, 0, 0};
+    unsigned long long sums[SPL_COVF_COUNTERS + 1] = {0, 0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(sums, d_out.p, sizeof sums, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     size_t n_runs = 0;
@@ -4478,8 +4562,18 @@ extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, in
     }
     cov->totals[0] = (int64_t)n_runs;
     for (int k = 0; k < SPL_COV_COUNTERS + 1; ++k) cov->totals[k + 1] = (int64_t)sums[k];
+    cov->pairs = (int64_t)sums[SPL_COV_COUNTERS + 1];
     *out = cov.release();
     return SPL_OK;
+}
+} // namespace
+
+extern "C" int spl_coverage(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, spl_cov **out)
+{
+    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_coverage: null argument");
+    *out = nullptr;
+    if (const int rc = cov_refusal("spl_coverage", dr, length, stranded, strand)) return rc;
+    return cov_runs(c, dr, length, stranded, strand, false, out);
 }
 
 extern "C" int spl_coverage_totals(const spl_cov *cov, int64_t *out5)
@@ -4825,6 +4919,103 @@ extern "C" int spl_mate_table(spl_ctx *c, const spl_dreads *dr, int seg, uint32_
         HIP_TRY(hipMemcpyAsync(host_out, dr->mates + ls.first, 4 * (size_t)ls.n_reads, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    return SPL_OK;
+}
+
+// spl_coverage per fragment (the rule is spl_covfragment_rule.h): the arguments are spl_coverage's; the set must have name keys.
+extern "C" int spl_coverage_fragments(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, spl_cov **out)
+{
+    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragments: null argument");
+    *out = nullptr;
+    if (const int rc = cov_refusal("spl_coverage_fragments", dr, length, stranded, strand)) return rc;
+    if (const int rc = mates_of(c, dr, "spl_coverage_fragments")) return rc;
+    return cov_runs(c, dr, length, stranded, strand, true, out);
+}
+
+extern "C" int spl_coverage_fragment_totals(const spl_cov *cov, int64_t *out6)
+{
+    if (!cov || !out6) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_totals: null argument");
+    memcpy(out6, cov->totals, sizeof cov->totals);
+    out6[5] = cov->pairs;
+    return SPL_OK;
+}
+
+// spl_intron_depth per fragment: the boundaries come from the fragment mark kernel; the arguments are spl_intron_depth's.
+extern "C" int spl_intron_depth_fragments(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, int64_t n_introns, const int64_t *piece_off, const int32_t *piece_start,
+                                          const int32_t *piece_end, int trim_percent, int64_t *out)
+{
+    if (!c || !dr) return spl_set_error(SPL_ERR_ARG, "spl_intron_depth_fragments: null argument");
+    if (const int rc = cov_refusal("spl_intron_depth_fragments", dr, length, stranded, strand)) return rc;
+    if (const int rc = intron_args_fit("spl_intron_depth_fragments", length, n_introns, piece_off, piece_start, piece_end, trim_percent, out)) return rc;
+    if (const int rc = mates_of(c, dr, "spl_intron_depth_fragments")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    CovStages st; // (a set without a read: no boundary, a depth of 0 everywhere)
+    if (!dr->segs.empty())
+        if (const int rc = cov_stages(c, dr, length, stranded, strand, st, true)) return rc;
+    return intron_launch(c, st.pos.as<int32_t>(), st.delta.as<uint32_t>(), (int64_t)st.n_bound, n_introns, piece_off, piece_start, piece_end, trim_percent, out);
+}
+
+// The fragment rule for every read of one segment's host arrays with its mate table: no GPU involved (test hook).  status_out[r]:
+// 1 contributed (a leader, or a read without a partner, whose union has a base), 0 nothing to mark, -4 silent (the read's leader
+// marks the fragment), -3 not participating; n_iv_out[r]: the intervals of read r's union (all of them); past_out[r] (or null):
+// whether either read lost a base to the clipping; iv_start / iv_end [0 .. cap): the intervals, one read after the other in read
+// order; totals6 (or null): what spl_coverage_fragment_totals gives, [0] being the intervals here.
+extern "C" int spl_coverage_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint32_t *mate, int32_t shift,
+                                               int64_t length, int stranded, int strand, int64_t *status_out, int64_t *n_iv_out, uint8_t *past_out, int64_t *iv_start, int64_t *iv_end,
+                                               int64_t cap, int64_t *totals6)
+{
+    if (n_reads < 0 || (n_reads && (!pos || !flag || !cig_off || !mate || !status_out || !n_iv_out)) || cap < 0 || (cap && (!iv_start || !iv_end)))
+        return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_rule_host: null argument");
+    if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_rule_host: cigar is null");
+    if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_rule_host: length must be in 1 .. 2^31 - 2");
+    if (!spl_cov_args_fit(stranded, strand)) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_rule_host: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2");
+    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    struct Keep {
+        int64_t cap, used, n; int64_t *s, *e;
+        void operator()(int64_t a, int64_t b) { if (used < cap) { s[used] = a; e[used] = b; ++used; } ++n; }
+    } keep{cap, 0, 0, iv_start, iv_end};
+    int64_t totals[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t r = 0; r < n_reads; ++r) {
+        spl_cov_side lead, other;
+        const uint32_t what = spl_cov_fragment_sides(reads, 0, n_reads, r, mate, (int64_t)shift, stranded, strand, &lead, &other);
+        n_iv_out[r] = 0;
+        if (past_out) past_out[r] = 0;
+        ++totals[1];
+        if (what != SPL_COVF_LEADS) { status_out[r] = what == SPL_COVF_SILENT ? -4 : -3; continue; }
+        keep.n = 0;
+        int64_t covered = 0;
+        const uint32_t bits = spl_cov_fragment_walk<spl_gene_ops_ptr>(cigar, lead, other, length, keep, &covered);
+        n_iv_out[r] = keep.n;
+        status_out[r] = (bits & SPL_COV_CONTRIBUTED) ? 1 : 0;
+        if (past_out) past_out[r] = (bits & SPL_COV_PAST_END) ? 1 : 0;
+        totals[0] += keep.n;
+        totals[2] += (bits & SPL_COV_CONTRIBUTED) ? 1 : 0;
+        totals[3] += (bits & SPL_COV_PAST_END) ? 1 : 0;
+        totals[4] += covered;
+        totals[5] += (bits & SPL_COVF_PAIR) ? 1 : 0;
+    }
+    if (totals6) memcpy(totals6, totals, sizeof totals);
+    return SPL_OK;
+}
+
+// The block cursor of spl_covfragment_rule.h for one read on the host (test hook; no GPU): spl_coverage_rule_host's arguments and
+// results, by spl_cov_cursor in place of spl_cov_walk.
+extern "C" int spl_coverage_cursor_host(uint32_t flag, int32_t pos, const uint32_t *ops, uint32_t n_ops, int32_t shift, int64_t length, int stranded, int strand, int capacity,
+                                        int64_t *blk_start, int64_t *blk_end, int *n_out, int *past_end_out)
+{
+    if ((n_ops && !ops) || !n_out || capacity < 0 || (capacity && (!blk_start || !blk_end))) return spl_set_error(SPL_ERR_ARG, "spl_coverage_cursor_host: null argument");
+    if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_coverage_cursor_host: length must be in 1 .. 2^31 - 2");
+    if (!spl_cov_args_fit(stranded, strand)) return spl_set_error(SPL_ERR_ARG, "spl_coverage_cursor_host: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2");
+    int n = 0;
+    uint32_t bits = 0;
+    if (spl_cov_eligible(flag, (int64_t)pos, n_ops) && spl_cov_on_track(flag, stranded, strand)) {
+        spl_cov_cursor<spl_gene_ops_ptr> cursor(spl_gene_ops_ptr{ops}, n_ops, (int64_t)pos - 1 + (int64_t)shift, length);
+        for (int64_t s, e; cursor.next(&s, &e); ++n)
+            if (n < capacity) { blk_start[n] = s; blk_end[n] = e; }
+        bits = cursor.bits;
+    }
+    *n_out = n;
+    if (past_end_out) *past_end_out = (bits & SPL_COV_PAST_END) ? 1 : 0;
     return SPL_OK;
 }
 

@@ -27,6 +27,11 @@ int64_t spl_dev_cov_diff_words(int64_t length);
 // reads that contributed, reads past the end, covered bases.  n_rec / n_ops: the arrays' sizes, beyond which nothing is loaded.
 int spl_dev_launch_cov_mark(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int64_t length, int stranded, int strand,
                             uint32_t *diff, unsigned long long *out4, void *stream);
+// mark, per fragment (spl_covfragment_rule.h): the same over the segment's mate table -- mate: n words of device memory, a read's
+// mate within [0, n) or SPL_MATE_NONE.  out5: the four sums where spl_dev_launch_cov_mark has them, and [4] the pairs whose union
+// was taken.
+int spl_dev_launch_cov_mark_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int64_t length, int stranded, int strand,
+                                      const uint32_t *mate, uint32_t *diff, unsigned long long *out5, void *stream);
 // compact, pass 1: tile_count[t] = the non-zero words of diff among the positions [t * SPL_COV_POS_TILE, ...) below length.
 int spl_dev_launch_cov_count(const uint32_t *diff, int64_t length, uint32_t *tile_count, void *stream);
 // compact, pass 2: tile_sum = the INCLUSIVE prefix sums of tile_count; the non-zero words below length go to (pos, delta) in

@@ -15,12 +15,17 @@
 //          the tiles again and writes (position, delta) in ascending order, a word's place being its tile's offset, the words of
 //          the waves in front, of the lanes in front (ballots) and of the lane's own load.  No second array of `length` words.
 // Integer sums throughout: exact, and the same for the reads in any order.
+//
+// spl_coverage_fragments (`coverage --fragments`) has a mark kernel of its own below, in the same geometry over the segment's mate
+// table: a fragment's leader marks the union of both mates' blocks, the merge of two block cursors (spl_covfragment_rule.h); the
+// count, emit and scan stages are the same.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define SPL_HD __device__ __forceinline__
 #include "spl_coverage.h"
 #include "spl_coverage_rule.h"
+#include "spl_covfragment_rule.h" // a fragment's rule: spl_cov_mark_fragments_kernel
 
 namespace {
 
@@ -81,6 +86,50 @@ __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_mark_kernel(const spl_de
     if (lane == SPL_COV_COUNTERS && bases) atomicAdd(&s_sum[SPL_COV_COUNTERS], bases);
     __syncthreads();
     if (t < SPL_COV_COUNTERS + 1 && s_sum[t]) atomicAdd(&out[t], s_sum[t]);
+}
+
+// Fragments (spl_coverage_fragments): the same launch over the segment with its mate table (spl_mates.hip) beside the arrays, the
+// same diff array and atomics.  A lane first asks whether its read's mate takes part in the call -- a dependent load of the mate's
+// FLAG, POS and CIGAR offsets from wherever that read lies in the segment.  A silent lane then idles; a leader walks its own ops
+// and its mate's as two block cursors and marks their union (spl_cov_fragment_walk): at most the two reads' marks, fewer where the
+// mates overlap or abut.  Nothing is stored per lane.  One ballot counter more: the pairs whose union was taken.
+__global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_mark_fragments_kernel(const spl_devreads src, int64_t n_ops_total, int64_t first, int64_t n, int32_t shift, int64_t length,
+                                                                               int stranded, int strand, const uint32_t *mate, uint32_t *diff, unsigned long long *out)
+{
+    __shared__ unsigned long long s_sum[SPL_COVF_COUNTERS + 1];
+    const uint32_t t = threadIdx.x;
+    const uint32_t lane = lane_id();
+    if (t < SPL_COVF_COUNTERS + 1) s_sum[t] = 0ull;
+    __syncthreads();
+    const spl_mate_reads reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
+    uint32_t mine = 0;            // (as in the per-read kernel)
+    unsigned long long bases = 0; // this lane's covered bases
+    DiffMark mark{diff};
+    for (int64_t base = (int64_t)blockIdx.x * SPL_COV_TILE; base < n; base += (int64_t)gridDim.x * SPL_COV_TILE) { // (uniform over the workgroup)
+        const int64_t r = base + t;
+        uint32_t bits = 0;
+        if (r < n) {
+            bits = SPL_COV_SEEN;
+            spl_cov_side lead, other;
+            if (spl_cov_fragment_sides(reads, first, n, r, mate, (int64_t)shift, stranded, strand, &lead, &other) == SPL_COVF_LEADS) {
+                int64_t covered = 0;
+                bits |= spl_cov_fragment_walk<DevOps>(src.cigar, lead, other, length, mark, &covered);
+                bases += (unsigned long long)covered;
+            }
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < SPL_COVF_COUNTERS; ++c) {
+            const unsigned long long b = __ballot((bits >> c) & 1u);
+            if (lane == c) mine += (uint32_t)__popcll(b);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) bases += __shfl_xor(bases, d, 64);
+    // out: the per-read kernel's four sums where they were, and the pairs behind them
+    if (lane < SPL_COVF_COUNTERS && mine) atomicAdd(&s_sum[lane < SPL_COV_COUNTERS ? lane : SPL_COV_COUNTERS + 1], (unsigned long long)mine);
+    if (lane == SPL_COVF_COUNTERS && bases) atomicAdd(&s_sum[SPL_COV_COUNTERS], bases);
+    __syncthreads();
+    if (t < SPL_COVF_COUNTERS + 1 && s_sum[t]) atomicAdd(&out[t], s_sum[t]);
 }
 
 // The four words of this lane's load of tile `tile`, those at or beyond `length` as zero: bit k of the result = word k is not zero.
@@ -166,6 +215,16 @@ extern "C" int spl_dev_launch_cov_mark(const spl_devreads *src, int64_t n_rec, i
     if (n <= 0) return 0;
     if (!src || !diff || !out4 || first < 0 || first + n > n_rec || length < 1 || length > SPL_COV_LENGTH_MAX || stranded < 0 || stranded > 2) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(spl_cov_mark_kernel, dim3(spl_dev_cov_grid(n)), dim3(SPL_COV_TILE), 0, (hipStream_t)stream, *src, n_ops, first, n, shift, length, stranded, strand, diff, out4);
+    return (int)hipGetLastError();
+}
+
+extern "C" int spl_dev_launch_cov_mark_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int64_t length, int stranded, int strand,
+                                                 const uint32_t *mate, uint32_t *diff, unsigned long long *out5, void *stream)
+{
+    if (n <= 0) return 0;
+    if (!src || !mate || !diff || !out5 || first < 0 || first + n > n_rec || length < 1 || length > SPL_COV_LENGTH_MAX || stranded < 0 || stranded > 2) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(spl_cov_mark_fragments_kernel, dim3(spl_dev_cov_grid(n)), dim3(SPL_COV_TILE), 0, (hipStream_t)stream, *src, n_ops, first, n, shift, length, stranded, strand, mate, diff,
+                       out5);
     return (int)hipGetLastError();
 }
 

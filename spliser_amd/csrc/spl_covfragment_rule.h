@@ -1,0 +1,137 @@
+// spl_covfragment_rule.h -- what ONE FRAGMENT of a paired-end library adds to the per-base depth of its reference, as straight-line
+// C++: the rule of spl_coverage_fragments (the `coverage --fragments` switch).
+//
+// The kernel (spl_coverage.hip) includes this header with SPL_HD = __device__ __forceinline__.  It contains no HIP intrinsics, so
+// that tests/ compile it with g++ too (spl_coverage_fragment_rule_host, tests/hostsim/covfragment_rule_asan.cpp); the product never
+// calls it on the host.
+//
+// Replaces deepTools `bamCoverage` (paired-end default) / `bedtools genomecov -pc -split` over the file this library has just
+// decoded: on a 2 x 150 library with 300-base inserts most mates overlap, and covering per read shows a depth of two over the
+// overlap where one molecule was sequenced.  The reference has no counterpart.
+//
+// Mates and the mate table are spl_mate_rule.h's; eligibility, the track, the walk, the blocks and their clipping are
+// spl_coverage_rule.h's, unchanged.  THE RULE, per call -- one segment with its mate table, `length`, `stranded`, `strand`:
+//   a read PARTICIPATES when spl_cov_eligible and spl_cov_on_track hold for it (secondary, supplementary, duplicate and QC-failed
+//   reads still cover; only pairable reads can have a mate);
+//   read r has a PARTNER m = mate[r] when m != SPL_MATE_NONE, m < n, m != r and read m participates in this same call -- a mate on
+//   the other track of a stranded run is no partner: each mate then covers alone on its own track;
+//   a participating read with a partner m < r is SILENT: it marks nothing and is only "seen";
+//   every other participating read marks the UNION of its own clipped blocks and, if it has one, its partner's: blocks that
+//   overlap OR abut become one interval, the intervals are given ascending and disjoint.  It CONTRIBUTED when the union has a base,
+//   is PAST THE END when either read lost a base to the clipping, and its covered bases are the union's length.
+// A read's leader depends on the reads' order; the union does not, nor do the counters: a pair contributes once, whichever leads.
+//
+// NOTHING STORED PER LANE.  One read's clipped blocks ascend and are disjoint (spl_cov_cursor: spl_cov_walk as a resumable cursor,
+// block for block), so a fragment's union is the two-way merge of two block cursors: hold both heads, take the one that starts
+// first, and let it lengthen the open interval or close it.
+#ifndef SPL_COVFRAGMENT_RULE_H
+#define SPL_COVFRAGMENT_RULE_H
+
+#include <stdint.h>
+
+#include "spl_coverage_rule.h"
+#include "spl_mate_rule.h"
+
+#define SPL_COVF_COUNTERS 4   // spl_coverage_rule.h's three predicates of a read, and [3]: it led a pair whose union was taken
+#define SPL_COVF_PAIR 8u
+// What read r of a segment is to a call (spl_cov_fragment_sides):
+#define SPL_COVF_NOT_PARTICIPATING 0u
+#define SPL_COVF_SILENT 1u
+#define SPL_COVF_LEADS 2u     // to be walked: a fragment's leader, or a read without a partner
+
+// spl_cov_walk, resumable: next() gives the read's clipped blocks one by one, 0 <= s < e <= length, ascending and disjoint; bits
+// gathers SPL_COV_PAST_END as the walk meets it (complete once next() has said false).  A read of no op gives nothing.
+template <class Ops>
+struct spl_cov_cursor {
+    Ops ops;
+    uint32_t n_ops, k, bits;
+    int64_t p, length, bs, be; // the open block [bs, be); bs == be: none
+
+    SPL_HD spl_cov_cursor(const Ops &o, uint32_t n, int64_t p0, int64_t len) : ops(o), n_ops(n), k(0u), bits(0u), p(p0), length(len), bs(0), be(0) {}
+
+    SPL_HD bool next(int64_t *s_out, int64_t *e_out)
+    {
+        while (k <= n_ops) {
+            int64_t len = 0;
+            bool covers = false;
+            if (k < n_ops) {
+                const uint32_t op = ops(k);
+                len = (int64_t)(op >> 4);
+                if (len == 0 || !((SPL_PROG_MASK >> (op & 15u)) & 1u)) { ++k; continue; }
+                covers = ((SPL_MAPPED_MASK >> (op & 15u)) & 1u) != 0u;
+            }
+            if (covers && be > bs && p == be) { be += len; p += len; ++k; continue; } // abuts the open block
+            if (be > bs) { // the open block ends here; op k is looked at again by the next turn, with no block open
+                const int64_t s = bs < 0 ? 0 : bs, e = be > length ? length : be;
+                if (s != bs || e != be) bits |= SPL_COV_PAST_END;
+                bs = be = 0;
+                if (e > s) { *s_out = s; *e_out = e; return true; }
+                continue;
+            }
+            if (covers) { bs = p; be = p + len; }
+            p += len;
+            ++k;
+        }
+        return false;
+    }
+};
+
+// One read of a fragment as a cursor takes it: its ops (n_ops = 0: there is no such read) and p = POS - 1 + shift.
+struct spl_cov_side {
+    uint32_t c0, n_ops;
+    int64_t p;
+};
+
+// Does entry i of the arrays participate in the call?  -> its ops and POS too.
+SPL_HD bool spl_cov_participates(const spl_mate_reads &s, int64_t i, int stranded, int strand, uint32_t *c0, uint32_t *n_ops, int64_t *pos)
+{
+    const uint32_t flag = s.flag[i];
+    *pos = (int64_t)s.pos[i];
+    s.ops_of(i, c0, n_ops);
+    return spl_cov_eligible(flag, *pos, *n_ops) && spl_cov_on_track(flag, stranded, strand);
+}
+
+// What read r of the n reads of a segment is to the call: SPL_COVF_NOT_PARTICIPATING, SPL_COVF_SILENT, or SPL_COVF_LEADS -- *lead
+// is the read itself, *other its partner (n_ops = 0: it has none).
+SPL_HD uint32_t spl_cov_fragment_sides(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, int strand, spl_cov_side *lead,
+                                       spl_cov_side *other)
+{
+    *lead = spl_cov_side{0u, 0u, 0};
+    *other = spl_cov_side{0u, 0u, 0};
+    uint32_t c0, n_ops;
+    int64_t pos;
+    if (!spl_cov_participates(s, first + r, stranded, strand, &c0, &n_ops, &pos)) return SPL_COVF_NOT_PARTICIPATING;
+    *lead = spl_cov_side{c0, n_ops, pos - 1 + shift};
+    const uint32_t m = mate[r];
+    if (m == SPL_MATE_NONE || (int64_t)m >= n || (int64_t)m == r) return SPL_COVF_LEADS; // (a table of this segment: said for the memory's sake)
+    uint32_t m0, m_ops;
+    int64_t m_pos;
+    if (!spl_cov_participates(s, first + (int64_t)m, stranded, strand, &m0, &m_ops, &m_pos)) return SPL_COVF_LEADS; // (on the other track, or not eligible: no partner)
+    if ((int64_t)m < r) return SPL_COVF_SILENT;
+    *other = spl_cov_side{m0, m_ops, m_pos - 1 + shift};
+    return SPL_COVF_LEADS;
+}
+
+// The union of the clipped blocks of a read that leads (spl_cov_fragment_sides said SPL_COVF_LEADS): emit(s, e) for each interval,
+// 0 <= s < e <= length, ascending and disjoint -- not even abutting.  cigar: the segment's ops.  -> SPL_COV_CONTRIBUTED,
+// SPL_COV_PAST_END and SPL_COVF_PAIR as they hold; *covered_out = the union's bases.
+template <class Ops, class Emit>
+SPL_HD uint32_t spl_cov_fragment_walk(const uint32_t *cigar, const spl_cov_side &lead, const spl_cov_side &other, int64_t length, Emit &emit, int64_t *covered_out)
+{
+    spl_cov_cursor<Ops> x(Ops{cigar + lead.c0}, lead.n_ops, lead.p, length), y(Ops{cigar + other.c0}, other.n_ops, other.p, length);
+    int64_t xs = 0, xe = 0, ys = 0, ye = 0, cs = 0, ce = 0, covered = 0; // the heads, and the open interval [cs, ce); cs == ce: none
+    bool hx = x.next(&xs, &xe), hy = y.next(&ys, &ye);
+    while (hx || hy) {
+        int64_t s, e;
+        if (hx && (!hy || xs <= ys)) { s = xs; e = xe; hx = x.next(&xs, &xe); }
+        else { s = ys; e = ye; hy = y.next(&ys, &ye); }
+        if (ce > cs && s <= ce) { if (e > ce) ce = e; continue; } // overlaps or abuts the open interval
+        if (ce > cs) { emit(cs, ce); covered += ce - cs; }
+        cs = s; ce = e;
+    }
+    if (ce > cs) { emit(cs, ce); covered += ce - cs; }
+    *covered_out = covered;
+    return ((x.bits | y.bits) & SPL_COV_PAST_END) | (covered ? SPL_COV_CONTRIBUTED : 0u) | (other.n_ops ? SPL_COVF_PAIR : 0u);
+}
+
+#endif // SPL_COVFRAGMENT_RULE_H

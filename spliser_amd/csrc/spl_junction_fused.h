@@ -19,6 +19,12 @@ int spl_dev_launch_junctions_fused(const spl_devreads *src, int64_t n_rec, int64
                                    int stranded, uint32_t min_anchor, uint32_t min_intron, uint32_t max_intron, unsigned long long *keys,
                                    uint32_t *vals, uint32_t n_slots, unsigned long long *out_keys, uint32_t *out_vals, uint32_t *n_out,
                                    int32_t *err, const uint8_t *xs, void *stream); // xs: the reads' strand bytes, with stranded = 3 and only then
+// ... per fragment (spl_junctionfragment_rule.h): mates = the set's mate table, a word a read of the arrays; seg_first / seg_n (device
+// memory, n_segs >= 1 entries): the set's segments, ascending in their first read, each inside the arrays.
+int spl_dev_launch_junctions_fused_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, const spl_layout_chunk *chunks, uint32_t n_chunks, int stranded,
+                                             uint32_t min_anchor, uint32_t min_intron, uint32_t max_intron, unsigned long long *keys, uint32_t *vals, uint32_t n_slots,
+                                             unsigned long long *out_keys, uint32_t *out_vals, uint32_t *n_out, int32_t *err, const uint8_t *xs, const uint32_t *mates,
+                                             const int64_t *seg_first, const int64_t *seg_n, uint32_t n_segs, void *stream);
 #ifdef __cplusplus
 }
 #endif

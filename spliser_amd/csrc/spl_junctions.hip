@@ -12,6 +12,7 @@
 #include "spl_device.h"
 #include "spl_junction_fused.h"
 #include "spl_junction_walk.h"
+#include "spl_junctionfragment_rule.h" // a fragment's rule: spl_junction_fused_kernel<XS, true>
 
 namespace {
 
@@ -80,10 +81,19 @@ struct StagedOrGlobalOps { // a listed read's ops: in the stage (LDS) when all o
 // '-' or 0 -> '?'), so the table has up to three rows a junction (spljw::key3_of).  `xs` is an argument of this kernel's own --
 // spl_devreads is the range kernels' argument too -- and is read for a LISTED read only, into bits 16.. of the list entry's flag
 // word, which the 16-bit FLAG leaves free.  XS = false is the kernel of stranded = 0 / 1 / 2 as it was.
-template <bool XS>
+//
+// FRAG (spl_junctions_fragments; the rule is spl_junctionfragment_rule.h): a junction whose read has an EARLIER mate that supports
+// the same key is a duplicate carry and is not inserted.  mates: the set's mate table, a word a read of the arrays, a segment's
+// words holding indexes within the segment; seg_first / seg_n: the set's segments in ascending order of their first read, the
+// chunk's own found by a search that is uniform over the workgroup.  Only a LISTED read -- one with an N op -- loads its word of
+// the table (its place in the tile rides in bits 24.. of the list entry's flag word); only one whose mate is earlier, walked and of
+// its strand loads the mate's POS, FLAG and CIGAR offsets, and walks the mate's ops from the arrays, wherever that read lies, once
+// per junction it supports itself.  FRAG = false is the kernel as it was.
+template <bool XS, bool FRAG>
 __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl_devreads src, int64_t n_rec, int64_t n_ops_total, const spl_layout_chunk *chunks,
                                                                       int stranded, uint32_t min_anchor, uint32_t min_intron, uint32_t max_intron,
-                                                                      unsigned long long *keys, uint32_t *vals, uint32_t mask, int32_t *err, const uint8_t *xs)
+                                                                      unsigned long long *keys, uint32_t *vals, uint32_t mask, int32_t *err, const uint8_t *xs,
+                                                                      const uint32_t *mates, const int64_t *seg_first, const int64_t *seg_n, uint32_t n_segs)
 {
     __shared__ uint32_t s_stage[SPL_JSTAGE];
     __shared__ uint4 s_list[SPL_JTILE];   // {POS + shift, flag, first op, number of ops} of the listed reads
@@ -95,6 +105,13 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
     const uint32_t need = spljw::min_ops(min_anchor);
     const uint32_t t = threadIdx.x, wave = t >> 6;
     const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    int64_t seg_lo = 0, seg_len = 0; // FRAG: the chunk's segment, reads [seg_lo, seg_lo + seg_len) of the arrays
+    if (FRAG && n_segs) {
+        uint32_t a = 0, b = n_segs;
+        while (a + 1u < b) { const uint32_t mid = a + (b - a) / 2u; if (seg_first[mid] <= ch.lo) a = mid; else b = mid; }
+        seg_lo = seg_first[a];
+        seg_len = seg_n[a];
+    }
     for (uint32_t base = 0; base < ch.n; base += SPL_JTILE) {
         const uint32_t left = ch.n - base, n_tile = left < (uint32_t)SPL_JTILE ? left : (uint32_t)SPL_JTILE;
         const int64_t i = ch.lo + base + t;
@@ -143,6 +160,7 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
             fl = src.flag[i];
             listed = !(fl & 4u) && pos >= 0; // unmapped and unplaced records carry no junctions
             if (XS && listed) fl |= (uint32_t)xs[i] << 16;
+            if (FRAG && listed) fl |= t << 24;
         }
         // the list: lanes with a read to walk, in tile order
         const unsigned long long bal = __ballot(listed);
@@ -160,8 +178,24 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
             if (e < total) rd = s_list[e];
             const uint32_t r_ops = e < total ? rd.w : 0u;
             unsigned long long sbit;
-            if (XS) { const uint32_t x = rd.y >> 16; sbit = x == (uint32_t)'+' ? 0ull : x == (uint32_t)'-' ? 1ull : 2ull; }
-            else sbit = (stranded && spl_read_strand(rd.y, stranded) == (uint8_t)'-') ? 1ull : 0ull;
+            if (XS) { const uint32_t x = FRAG ? (rd.y >> 16) & 0xffu : rd.y >> 16; sbit = x == (uint32_t)'+' ? 0ull : x == (uint32_t)'-' ? 1ull : 2ull; }
+            else sbit = (stranded && spl_read_strand(FRAG ? rd.y & 0xffffu : rd.y, stranded) == (uint8_t)'-') ? 1ull : 0ull;
+            bool m_has = false; // FRAG: the read has an earlier mate that is walked and of its strand: ops cigar[m0, m0 + m_ops), from m_p
+            uint32_t m0 = 0, m_ops = 0;
+            int32_t m_p = 0;
+            if (FRAG && e < total) {
+                const int64_t r = ch.lo + (int64_t)base + (int64_t)(rd.y >> 24) - seg_lo; // the read's index within its segment
+                const int64_t m = (r >= 0 && r < seg_len) ? spljf::earlier_mate(mates + seg_lo, seg_len, r) : -1;
+                if (m >= 0) {
+                    const int64_t mi = seg_lo + m; // (< seg_lo + seg_len <= n_rec: the launcher's check)
+                    const uint32_t m_fl = src.flag[mi];
+                    const int32_t m_pos = src.pos[mi];
+                    uint32_t a = src.cig_off[mi], b = src.cig_off[mi + 1];
+                    if (b < a || (int64_t)b > n_ops_total) b = a; // (offsets of the arrays' own ops: said for the memory's sake)
+                    m0 = a; m_ops = b - a; m_p = m_pos + ch.shift;
+                    m_has = spljf::walked(m_fl, (int64_t)m_pos) && spljf::strand_code(m_fl, XS ? (uint32_t)xs[mi] : 0u, stranded) == (uint32_t)sbit;
+                }
+            }
             StagedOrGlobalOps ops;
             ops.staged = (uint64_t)rd.z + rd.w <= ws + SPL_JSTAGE;
             ops.lds = (const lds_u32 *)s_stage + (ops.staged ? rd.z - (uint32_t)ws : 0u);
@@ -182,6 +216,7 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
                     w.range_error = false;
                 }
                 if (XS && have && !spljw::key3_fits(j.l, j.r)) { atomicOr(err, SPL_DEV_ERR_RANGE); have = false; }
+                if (FRAG && have && m_has && spljf::carries(spljf::OpsPtr{src.cigar + m0}, m_ops, m_p, filter, j.l, j.r)) have = false; // a duplicate carry
                 junction_merge_insert(have, have ? (XS ? spljw::key3_of(j.l, j.r, sbit) : spljw::key_of(j.l, j.r, sbit)) : ~0ull, j.anchor_left, j.anchor_right, lane, keys, vals, mask,
                                       err);
             }
@@ -250,11 +285,35 @@ extern "C" int spl_dev_launch_junctions_fused(const spl_devreads *src, int64_t n
     if (e == hipSuccess) e = hipMemsetAsync(err, 0, 4, st);
     if (e != hipSuccess) return (int)e;
     if (n_chunks > 0 && xs)
-        hipLaunchKernelGGL(spl_junction_fused_kernel<true>, dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron,
-                           max_intron, keys, vals, n_slots - 1u, err, xs);
+        hipLaunchKernelGGL((spl_junction_fused_kernel<true, false>), dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron,
+                           max_intron, keys, vals, n_slots - 1u, err, xs, (const uint32_t *)nullptr, (const int64_t *)nullptr, (const int64_t *)nullptr, 0u);
     else if (n_chunks > 0)
-        hipLaunchKernelGGL(spl_junction_fused_kernel<false>, dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron,
-                           max_intron, keys, vals, n_slots - 1u, err, (const uint8_t *)nullptr);
+        hipLaunchKernelGGL((spl_junction_fused_kernel<false, false>), dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron,
+                           max_intron, keys, vals, n_slots - 1u, err, (const uint8_t *)nullptr, (const uint32_t *)nullptr, (const int64_t *)nullptr, (const int64_t *)nullptr, 0u);
+    hipLaunchKernelGGL(spl_junction_fused_compact_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, st, keys, vals, n_slots, out_keys, out_vals, n_out);
+    return (int)hipGetLastError();
+}
+
+// The same per fragment: mates (n_rec words), and the set's n_segs >= 1 segments, ascending in seg_first (device memory), every one
+// inside [0, n_rec): the caller's check.
+extern "C" int spl_dev_launch_junctions_fused_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, const spl_layout_chunk *chunks, uint32_t n_chunks, int stranded,
+                                                        uint32_t min_anchor, uint32_t min_intron, uint32_t max_intron, unsigned long long *keys, uint32_t *vals, uint32_t n_slots,
+                                                        unsigned long long *out_keys, uint32_t *out_vals, uint32_t *n_out, int32_t *err, const uint8_t *xs, const uint32_t *mates,
+                                                        const int64_t *seg_first, const int64_t *seg_n, uint32_t n_segs, void *stream)
+{
+    if ((stranded == 3) != (xs != nullptr) || !mates || !seg_first || !seg_n || n_segs < 1u) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)n_slots * 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(vals, 0, (size_t)n_slots * 12, st);
+    if (e == hipSuccess) e = hipMemsetAsync(n_out, 0, 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(err, 0, 4, st);
+    if (e != hipSuccess) return (int)e;
+    if (n_chunks > 0 && xs)
+        hipLaunchKernelGGL((spl_junction_fused_kernel<true, true>), dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron, max_intron, keys,
+                           vals, n_slots - 1u, err, xs, mates, seg_first, seg_n, n_segs);
+    else if (n_chunks > 0)
+        hipLaunchKernelGGL((spl_junction_fused_kernel<false, true>), dim3(n_chunks), dim3(SPL_JTILE), 0, st, *src, n_rec, n_ops, chunks, stranded, min_anchor, min_intron, max_intron, keys,
+                           vals, n_slots - 1u, err, (const uint8_t *)nullptr, mates, seg_first, seg_n, n_segs);
     hipLaunchKernelGGL(spl_junction_fused_compact_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, st, keys, vals, n_slots, out_keys, out_vals, n_out);
     return (int)hipGetLastError();
 }

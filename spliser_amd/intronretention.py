@@ -16,6 +16,13 @@ selection, of any gene, clipped to the chromosome; over the ascending depths D o
 begins, and end where it ends.  This is IRFinder's published measure -- a trimmed mean over max-side splicing -- as this project restates
 it; parity with IRFinder is intended and unpinned (it is not on the build machine): the yardstick is tests/introncases.py.
 Transcript-level introns, IRFinder's warnings column and known-exon blacklists are out of scope.
+
+``--fragments`` takes both sides of the ratio per FRAGMENT, as IRFinder does.  Per read, a pair whose mates overlap inside an intron
+adds two to its depth, and a pair whose mates both cross it adds two to its splice count: numerator and denominator are inflated by
+different factors that depend on the library's insert size.  With the switch the depth is ``coverage --fragments``' (the union of
+both mates' blocks, once: ``spl_intron_depth_fragments``) and the junction table is ``spl_junctions_fragments``': a junction whose
+read has an earlier mate that supports the same junction adds nothing (csrc/spl_junctionfragment_rule.h).  Same file, same header.
+``junctions`` and ``process`` have no such switch: the BED score feeds SpliSER's alpha, which stays per read beside beta1 / beta2.
 """
 import sys
 
@@ -168,10 +175,11 @@ def write_rows(path, table, rows, numbers, splices):
 
 
 def intronretention(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id", trimPercent=30, qChrom="All", isStranded=False, strandedType=None, devices=(0,), threads=0,
-                    log=None, gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False):
+                    log=None, gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False, fragments=False):
     """The ``intronretention`` command: one decode, the annotation read meanwhile, ``<outputPath>.introns.tsv``.  ``qChrom``: the rows
     of that chromosome, under the ids they have in the whole annotation.  With several devices the file is decoded and measured on
-    the first: there are no shares.  -> the number of rows written."""
+    the first: there are no shares.  ``fragments``: depth and splice counts per fragment (the module's text).  -> the number of rows
+    written."""
     import timeit
     log = log or (lambda msg: (print(msg), sys.stdout.flush()))
     if annotationFile is None:
@@ -186,8 +194,9 @@ def intronretention(inBAM, annotationFile, outputPath, aType="exon", idAttr="gen
     if len(devices) > 1:
         log("  (intronretention: the alignment file is decoded and measured on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
         devices = devices[:1]
-    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder))
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(fragments))
     source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
+    pair_sums = np.zeros(2, np.int64)      # --fragments: pairable reads, pairs found
     try:
         t0 = timeit.default_timer()
         features = _gc.read_features(annotationFile, aType, idAttr)
@@ -202,12 +211,18 @@ def intronretention(inBAM, annotationFile, outputPath, aType="exon", idAttr="gen
         n = table.gene.shape[0]
         numbers, splices, done = np.zeros((n, 4), np.int64), np.zeros((n, 3), np.int64), set()
         visit = [c for c in source.ref_names if c in wanted]
-        for chrom, length, dr in _coverage.sets_of_source(source, devices[0], visit):
-            junctions = dr.junctions(stranded, 0, 0, 0)
+        if fragments:
+            log("  (--fragments: depth and splice counts are per fragment -- a base under both mates of a pair, and a junction both support, count once)")
+        for chrom, length, dr in _coverage.sets_of_source(source, devices[0], visit, with_keys=bool(fragments)):
+            junctions = dr.junctions(stranded, 0, 0, 0, fragments=bool(fragments))
+            if fragments:
+                mates = dr.mate_table(0)[1]
+                log("  %s: %d pairable reads, %d pairs found" % (chrom, mates["pairable"], mates["paired"] // 2))
+                pair_sums += [mates["pairable"], mates["paired"] // 2]
             for track, strand in tracks_of(stranded):
                 rows = table.rows_on(chrom, track)
                 piece_off, piece_start, piece_end = table.pieces(rows, chrom, track, length)
-                got = dr.intron_depth(length, piece_off, piece_start, piece_end, trim, stranded, strand)
+                got = dr.intron_depth(length, piece_off, piece_start, piece_end, trim, stranded, strand, fragments=bool(fragments))
                 numbers[rows] = got
                 splices[rows] = splice_counts(junctions, table.s[rows], table.e[rows], track, stranded)
                 name = "%s (%s)" % (chrom, track) if stranded else chrom
@@ -221,6 +236,8 @@ def intronretention(inBAM, annotationFile, outputPath, aType="exon", idAttr="gen
                 rows = table.rows_on(chrom, track)
                 length = int(lengths.get(chrom, 0))
                 numbers[rows] = no_read_numbers(*table.pieces(rows, chrom, track, length if length >= 1 else None), trim=trim)
+        if fragments:
+            log("Mates: %d pairable reads, %d pairs found" % (pair_sums[0], pair_sums[1]))
         _process.log_filter(source, options.read_filter, log)
     finally:
         if hasattr(source, "close"):

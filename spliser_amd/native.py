@@ -53,7 +53,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_set_mate_keys", "spl_bam_mate_keys", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_lanes_plan_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_junctions_fragments", "spl_junction_fragment_rule_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_coverage_fragments", "spl_coverage_fragment_totals", "spl_intron_depth_fragments", "spl_coverage_fragment_rule_host", "spl_coverage_cursor_host", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_lanes_plan_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -488,12 +488,15 @@ class DeviceReads(object):
         _check(lib().spl_literal_queue_size(self.ctx._h, self._h, ctypes.byref(out)))
         return out.value
 
-    def junctions(self, stranded=0, min_anchor=0, min_intron=0, max_intron=0):
+    def junctions(self, stranded=0, min_anchor=0, min_intron=0, max_intron=0, fragments=False):
         """Junction table of this read set, computed on the device (``spl_junctions``): dict of arrays left, right,
         strand (bytes '+', '-' or '?'), count, anchor_left, anchor_right, sorted by (left, right, strand).  ``stranded``: 0, 1
-        (fr), 2 (rf) or ``STRAND_FROM_XS``: the reads' strand bytes, up to three rows a junction (``has_strand`` sets only)."""
+        (fr), 2 (rf) or ``STRAND_FROM_XS``: the reads' strand bytes, up to three rows a junction (``has_strand`` sets only).
+        ``fragments``: a junction whose read has an earlier mate (``mate_table``) that supports the same row adds nothing
+        (``spl_junctions_fragments``; a fused set with name keys)."""
         n = ctypes.c_int64(0)
-        _check(lib().spl_junctions(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int32(int(min_anchor)),
+        entry = lib().spl_junctions_fragments if fragments else lib().spl_junctions
+        _check(entry(self.ctx._h, self._h, ctypes.c_int(int(stranded)), ctypes.c_int32(int(min_anchor)),
                                    ctypes.c_int32(int(min_intron)), ctypes.c_int32(int(max_intron)), ctypes.byref(n)))
         n = n.value
         out = dict(left=np.empty(n, np.int32), right=np.empty(n, np.int32), strand=np.empty(n, np.uint8),
@@ -513,23 +516,26 @@ class DeviceReads(object):
                                       _ptr(code) if code.shape[0] else None, _ptr(out)))
         return out
 
-    def coverage(self, length, stranded=0, strand=0):
+    def coverage(self, length, stranded=0, strand=0, fragments=False):
         """Per-base read depth of this (finished, fused) set, taken as the reads of one reference of ``length`` bases, on the device
         (``spl_coverage``): -> (start int32, end int32, depth uint32, totals) -- the runs, 0-based and half-open, ascending, maximal,
         depth > 0 only; ``totals``: dict of runs, reads_seen, contributed, past_end, covered_bases.  ``stranded``: 0, 1 (fr) or 2
-        (rf); ``strand``: 0 with ``stranded=0``, else ``'+'`` or ``'-'`` (a character or its code): the track."""
+        (rf); ``strand``: 0 with ``stranded=0``, else ``'+'`` or ``'-'`` (a character or its code): the track.  ``fragments``: a pair
+        of mates (``mate_table``) on the track covers the union of both reads' blocks once (``spl_coverage_fragments``; the set needs
+        name keys); ``totals`` then has ``pairs`` too, the pairs whose union was taken."""
         strand = ord(strand) if isinstance(strand, (str, bytes)) else int(strand)
         h = ctypes.c_void_p()
-        _check(lib().spl_coverage(self.ctx._h, self._h, ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.byref(h)))
+        entry = lib().spl_coverage_fragments if fragments else lib().spl_coverage
+        _check(entry(self.ctx._h, self._h, ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.byref(h)))
         try:
-            t = np.zeros(5, np.int64)
-            _check(lib().spl_coverage_totals(h, _ptr(t)))
+            t = np.zeros(6 if fragments else 5, np.int64)
+            _check((lib().spl_coverage_fragment_totals if fragments else lib().spl_coverage_totals)(h, _ptr(t)))
             n = int(t[0])
             start, end, depth = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.uint32)
             _check(lib().spl_coverage_download(self.ctx._h, h, _ptr(start), _ptr(end), _ptr(depth)))
         finally:
             lib().spl_coverage_free(self.ctx._h, h)
-        return start, end, depth, dict(zip(COVERAGE_TOTALS, t.tolist()))
+        return start, end, depth, dict(zip(COVERAGE_FRAGMENT_TOTALS if fragments else COVERAGE_TOTALS, t.tolist()))
 
     def gene_counts(self, n_genes, map_a, map_b=None, stranded=0, out=None, fragments=False):
         """Per-gene read counts of this (finished, fused) set, on the device (``spl_gene_count``): ADDS to ``out`` (int64[n_genes + 3];
@@ -568,18 +574,20 @@ class DeviceReads(object):
                      _ptr(b_code) if b_code.shape[0] else None, ctypes.c_int64(n_bins), _ptr(bin_gene) if n_bins else None, _ptr(out)))
         return out
 
-    def intron_depth(self, length, piece_off, piece_start, piece_end, trim_percent=30, stranded=0, strand=0):
+    def intron_depth(self, length, piece_off, piece_start, piece_end, trim_percent=30, stranded=0, strand=0, fragments=False):
         """The trimmed depth of introns over this (finished, fused) set, taken as the reads of one reference of ``length`` bases, on
         the device (``spl_intron_depth``): -> int64[n_introns, 4] -- measurable bases L, covered bases, depth_n, depth_sum.  Intron i
         has the pieces ``piece_off[i] .. piece_off[i + 1]`` of ``(piece_start, piece_end)``, 0-based and half-open, disjoint and
-        ascending within an intron; ``stranded`` / ``strand``: the track, as for ``coverage``."""
+        ascending within an intron; ``stranded`` / ``strand``: the track, as for ``coverage``.  ``fragments``: the depth is
+        ``coverage(fragments=True)``'s (``spl_intron_depth_fragments``; the set needs name keys)."""
         strand = ord(strand) if isinstance(strand, (str, bytes)) else int(strand)
         off, start, end = _arr(piece_off, np.int64), _arr(piece_start, np.int32), _arr(piece_end, np.int32)
         n = max(int(off.shape[0]) - 1, 0)
         out = np.zeros((n, 4), np.int64)
-        _check(lib().spl_intron_depth(self.ctx._h, self._h, ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.c_int64(n),
-                                      _ptr(off) if off.shape[0] else None, _ptr(start) if start.shape[0] else None, _ptr(end) if end.shape[0] else None,
-                                      ctypes.c_int(int(trim_percent)), _ptr(out) if n else None))
+        entry = lib().spl_intron_depth_fragments if fragments else lib().spl_intron_depth
+        _check(entry(self.ctx._h, self._h, ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.c_int64(n),
+                     _ptr(off) if off.shape[0] else None, _ptr(start) if start.shape[0] else None, _ptr(end) if end.shape[0] else None,
+                     ctypes.c_int(int(trim_percent)), _ptr(out) if n else None))
         return out
 
     def free(self):
@@ -1352,6 +1360,8 @@ def intron_depth_host(bound_pos, bound_depth, piece_start, piece_end, trim_perce
 
 
 COVERAGE_TOTALS = ("runs", "reads_seen", "contributed", "past_end", "covered_bases")
+COVERAGE_FRAGMENT_TOTALS = COVERAGE_TOTALS + ("pairs",)          # spl_coverage_fragment_totals' six
+COVF_CONTRIBUTED, COVF_NOTHING, COVF_NOT_PARTICIPATING, COVF_SILENT = 1, 0, -3, -4          # spl_coverage_fragment_rule_host's status of a read
 
 
 def coverage_rule_host(flag, pos, ops, length, shift=0, stranded=0, strand=0):
@@ -1366,6 +1376,54 @@ def coverage_rule_host(flag, pos, ops, length, shift=0, stranded=0, strand=0):
                                         ctypes.c_int32(int(shift)), ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.c_int(cap),
                                         _ptr(s), _ptr(e), ctypes.byref(n), ctypes.byref(past)))
     return list(zip(s[:n.value].tolist(), e[:n.value].tolist())), bool(past.value)
+
+
+def junction_fragment_rule_host(reads, mate, stranded=0, min_anchor=0, min_intron=0, max_intron=0, shift=0, xs=None, cap=1 << 16):
+    """The junction fragment rule for every read of one segment's host arrays with its mate table
+    (``spl_junction_fragment_rule_host``) -> (counted int64[n], duplicate int64[n], rows int64[min(cap, all), 6]: left, right, strand
+    byte, anchor_left, anchor_right, duplicate -- every supported junction in read and walk order)."""
+    mate = _arr(mate, np.uint32)
+    if mate.shape[0] != reads.n:
+        raise ValueError("mate must have n_reads entries")
+    xs = None if xs is None else _arr(xs, np.uint8)
+    counted, dup = np.zeros(max(reads.n, 1), np.int64), np.zeros(max(reads.n, 1), np.int64)
+    rows, n_rows = np.zeros((max(int(cap), 1), 6), np.int64), ctypes.c_int64(0)
+    _check(lib().spl_junction_fragment_rule_host(ctypes.c_int64(reads.n), _ptr(reads.pos), _ptr(reads.flag), _ptr(reads.cig_off), _ptr(reads.cigar) if reads.cigar.shape[0] else None,
+                                                 _ptr(xs), _ptr(mate), ctypes.c_int32(int(shift)), ctypes.c_int(int(stranded)), ctypes.c_int32(int(min_anchor)),
+                                                 ctypes.c_int32(int(min_intron)), ctypes.c_int32(int(max_intron)), _ptr(counted), _ptr(dup), _ptr(rows), ctypes.c_int64(int(cap)),
+                                                 ctypes.byref(n_rows)))
+    return counted[:reads.n], dup[:reads.n], rows[:min(int(cap), n_rows.value)]
+
+
+def coverage_cursor_host(flag, pos, ops, length, shift=0, stranded=0, strand=0):
+    """``coverage_rule_host``'s arguments and results by the fragment rule's resumable block cursor (``spl_coverage_cursor_host``)."""
+    ops = np.ascontiguousarray(ops, np.uint32)
+    strand = ord(strand) if isinstance(strand, (str, bytes)) else int(strand)
+    cap = max(1, ops.shape[0])
+    s, e = np.empty(cap, np.int64), np.empty(cap, np.int64)
+    n, past = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().spl_coverage_cursor_host(ctypes.c_uint32(int(flag)), ctypes.c_int32(int(pos)), _ptr(ops) if ops.shape[0] else None, ctypes.c_uint32(ops.shape[0]),
+                                          ctypes.c_int32(int(shift)), ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), ctypes.c_int(cap),
+                                          _ptr(s), _ptr(e), ctypes.byref(n), ctypes.byref(past)))
+    return list(zip(s[:n.value].tolist(), e[:n.value].tolist())), bool(past.value)
+
+
+def coverage_fragment_rule_host(reads, mate, length, shift=0, stranded=0, strand=0, cap=1 << 16):
+    """The fragment coverage rule for every read of one segment's host arrays with its mate table
+    (``spl_coverage_fragment_rule_host``) -> (status int64[n]: ``COVF_*``, n_iv int64[n]: the intervals of a read's union, also beyond
+    ``cap``, past bool[n], intervals [(start, end)]: the reads' unions one after the other in read order as far as ``cap`` reaches,
+    totals: dict of ``COVERAGE_FRAGMENT_TOTALS``, ``runs`` being the intervals)."""
+    mate = _arr(mate, np.uint32)
+    if mate.shape[0] != reads.n:
+        raise ValueError("mate must have n_reads entries")
+    strand = ord(strand) if isinstance(strand, (str, bytes)) else int(strand)
+    status, n_iv, past = np.zeros(max(reads.n, 1), np.int64), np.zeros(max(reads.n, 1), np.int64), np.zeros(max(reads.n, 1), np.uint8)
+    s, e, totals = np.zeros(max(int(cap), 1), np.int64), np.zeros(max(int(cap), 1), np.int64), np.zeros(6, np.int64)
+    _check(lib().spl_coverage_fragment_rule_host(ctypes.c_int64(reads.n), _ptr(reads.pos), _ptr(reads.flag), _ptr(reads.cig_off), _ptr(reads.cigar) if reads.cigar.shape[0] else None,
+                                                 _ptr(mate), ctypes.c_int32(int(shift)), ctypes.c_int64(int(length)), ctypes.c_int(int(stranded)), ctypes.c_int(strand), _ptr(status),
+                                                 _ptr(n_iv), _ptr(past), _ptr(s), _ptr(e), ctypes.c_int64(int(cap)), _ptr(totals)))
+    used = min(int(cap), int(n_iv[:reads.n].sum()))
+    return status[:reads.n], n_iv[:reads.n], past[:reads.n].astype(bool), list(zip(s[:used].tolist(), e[:used].tolist())), dict(zip(COVERAGE_FRAGMENT_TOTALS, totals.tolist()))
 
 
 def bedgraph_append(path, chrom, start, end, depth, per_million_of=0):
