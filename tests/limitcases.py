@@ -183,8 +183,10 @@ def concat(segments):
 
 
 def read_class(ops, flag=0):
-    """The packer's run of a read (spl_pack.h) for the CIGARs the cases here use: 0 simple, 1 once-spliced, 2 twice-spliced,
-    3 everything else (flag 0x4, indels, clips, blocks of 2^16 or more, twice-spliced blocks of 2^12 or more)."""
+    """The packer's run of a read (spl_pack.h) inside the coordinate space whose CIGAR holds M, N, = and X ops only: 0 simple,
+    1 once-spliced (first block below 2^16; the intron and the second block are full words), 2 twice-spliced (all three blocks
+    below 2^16), 3 everything else (flag 0x4, longer blocks, more junctions).  Any other op makes it 3 here, which is the
+    packer's answer for indels and for CIGARs of more than SPL_PACK_SCAN_OPS ops and what the cases here need of clips."""
     if flag & 4 or any(c not in (M, N, EQ, X) for _, c in ops):
         return 3
     shape = "".join("N" if c == N else "A" for _, c in ops)
@@ -194,7 +196,7 @@ def read_class(ops, flag=0):
     if shape == "ANA":
         return 1 if blocks[0] < 1 << 16 else 3
     if shape == "ANANA":
-        return 2 if max(blocks) < 1 << 12 else 3
+        return 2 if max(blocks) < 1 << 16 else 3
     return 3
 
 
@@ -264,8 +266,9 @@ def non_consuming_ops_case():
 
 
 def twice_spliced_limits_case():
-    """The twice-spliced class packs five lengths into three words (aligned < 4096, introns < 2^28): reads on and just beyond those
-    limits, with =/X blocks, soft clips, a deletion instead of an intron, in every neighbourhood.  -> (SiteArrays, ReadArrays)."""
+    """The twice-spliced class packs five lengths into four words (aligned < 65536, introns whatever a BAM record holds, < 2^28):
+    blocks of 4095 and 4096 bases (the limit of an earlier, 12-bit layout; classcases.py has the 16-bit one), the longest intron,
+    =/X blocks, soft clips, a deletion instead of an intron, in every neighbourhood.  -> (SiteArrays, ReadArrays)."""
     rng = np.random.default_rng(23)
     # sites: junction ends of the reads below plus alternatives sharing ends (rivals), both strands
     base = [1000, 1100, 1400, 1500, 5000, 5100, 5400, 5600, 9000, 9050, 300000000, 300000100]
@@ -298,8 +301,8 @@ def twice_spliced_limits_case():
         rec(99, 951, (3, S), (50, M), (100, N), (300, M), (100, N), (60, M), (7, S)),   # soft clips: same class after compaction
         rec(0, 951, (50, M), (100, N), (300, M), (100, D), (60, M)),                    # a deletion where the second intron was
         rec(0, 951, (50, M), (100, N), (150, M), (2, I), (150, M), (100, N), (60, M)),  # insertion splits the middle block: wide
-        rec(0, 1000 - 4094, (4095, M), (100, N), (300, M), (100, N), (60, M)),          # longest block that fits 12 bits
-        rec(0, 1000 - 4095, (4096, M), (100, N), (300, M), (100, N), (60, M)),          # one more: wide
+        rec(0, 1000 - 4094, (4095, M), (100, N), (300, M), (100, N), (60, M)),          # a block of 12 bits
+        rec(0, 1000 - 4095, (4096, M), (100, N), (300, M), (100, N), (60, M)),          # one more: the same class
         rec(0, 4951, (50, M), (100, N), (300, M), (200, N), (4095, M)),
         rec(0, 8951, (50, M), (50, N), (30, M), ((1 << 28) - 1, N), (40, M)),         # the longest intron a BAM record can hold
         rec(147, 8951, (50, M), (50, N), (0, M), (5, N), (40, M)),                    # an empty middle block
@@ -398,7 +401,7 @@ def parity_cases():
     arr, deco = non_consuming_ops_case()
     out.append(Case("non_consuming_ops", Table.from_chrom(arr), [(deco, 0)], "S/H/I/P around spliced reads"))
     s, r = twice_spliced_limits_case()
-    out.append(Case("twice_spliced_class_limits", _table_of(s), [(_readset(r), 0)], "12-bit blocks, 28-bit introns"))
+    out.append(Case("twice_spliced_class_limits", _table_of(s), [(_readset(r), 0)], "blocks of 4095 and 4096 bases (well inside 16 bits), 28-bit introns"))
     s, r, hot = long_introns_hot_sites_case()
     out.append(Case("long_introns_and_hot_sites", _table_of(s), [(_readset(r), 0)], "200k reads on one site, unsorted",
                     modes=[(0, 0), (1, 0), (2, 1)], hot_row=hot))
@@ -624,7 +627,7 @@ def overflow_case(which, n=CHUNK_BIG):
             L, R = juncs[0]
             recs.append((f, L - 40, [(41, M), (R - L, N), (int(rng.integers(10, 80)), M)]))
             continue
-        L2, R2 = juncs[k + 1]                               # (the middle block stays below 2^12)
+        L2, R2 = juncs[k + 1]                               # (the middle block is 1500 bases: far inside the class)
         twice = (f, L - 30, [(31, M), (R - L, N), (L2 - R, M), (R2 - L2, N), (int(rng.integers(5, 60)), M)])
         literal = (f | 4, R - 10, [(int(rng.integers(20, 90)), M)])
         if which == "twice":
