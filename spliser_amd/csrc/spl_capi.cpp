@@ -4179,6 +4179,13 @@ extern "C" int spl_count_algorithmic_bytes(const spl_dsites *ds, const spl_dread
 namespace {
 int mates_of(spl_ctx *c, const spl_dreads *dr, const char *who); // (below, with the mate table)
 
+// 0, or the refusal of a call (`who`: its name) that reads a set's arrays where the decode left them: a set with a read must be fused.
+int fused_refusal(const char *who, const spl_dreads *dr)
+{
+    if (dr->segs.empty() || (dr->fused && dr->groups.size() == 1)) return SPL_OK; // (a set without a read has no arrays to be fused of)
+    return spl_set_error(SPL_ERR_ARG, "%s needs a fused read set (all of it from one device decode or one spl_soa_upload)", who);
+}
+
 // spl_junctions, and -- fragments -- spl_junctions_fragments: the same table without the duplicate carries of spl_junctionfragment_rule.h.
 int junctions_of(spl_ctx *c, const spl_dreads *dr, int stranded, int32_t min_anchor, int32_t min_intron, int32_t max_intron, int64_t *n_out, bool fragments)
 {
@@ -4401,8 +4408,7 @@ extern "C" int spl_strand_tally(spl_ctx *c, const spl_dreads *dr, int64_t n_cove
         memset(out14, 0, 8 * SPL_STRAND_COUNTERS);
         return SPL_OK;
     }
-    if (!(dr->fused && dr->groups.size() == 1))
-        return spl_set_error(SPL_ERR_ARG, "spl_strand_tally needs a fused read set (all of it from one device decode or one spl_soa_upload)");
+    if (const int rc = fused_refusal("spl_strand_tally", dr)) return rc;
     const spl_dreads::Group &g = dr->groups[0];
     if (!g.src->xs && n_cover == 0)
         return spl_set_error(SPL_ERR_ARG, "spl_strand_tally: nothing to tally: the reads have no strand bytes (spl_bam_set_aux_strand, spl_soa_upload3) and there is no cover map");
@@ -4468,9 +4474,7 @@ int cov_refusal(const char *who, const spl_dreads *dr, int64_t length, int stran
     if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "%s: length must be in 1 .. 2^31 - 2, not %lld", who, (long long)length);
     if (stranded < 0 || stranded > 2) return spl_set_error(SPL_ERR_ARG, "%s: stranded must be 0 (one track), 1 (fr) or 2 (rf)", who);
     if (!spl_cov_args_fit(stranded, strand)) return spl_set_error(SPL_ERR_ARG, "%s: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2", who);
-    if (!dr->segs.empty() && !(dr->fused && dr->groups.size() == 1))
-        return spl_set_error(SPL_ERR_ARG, "%s needs a fused read set (all of it from one device decode or one spl_soa_upload)", who);
-    return SPL_OK;
+    return fused_refusal(who, dr);
 }
 
 // The three stages over a fused set with a read: mark per segment into one zeroed difference array, compact (count, scan, emit),
@@ -4762,51 +4766,84 @@ int gene_maps_fit(const char *who, int stranded, int64_t n_a, const int32_t *a_s
     }
     return SPL_OK;
 }
-} // namespace
 
-// Every read's gene over a fused set's arrays: one launch per segment, n_genes + 3 sums in device memory, down and added to inout.
-extern "C" int spl_gene_count(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
-                              const uint32_t *b_code, int64_t n_genes, int64_t *inout)
+// One segment of a counting call as a launcher takes it: the arrays and the segment's place in them, the maps (and, for the exon
+// counts, the bins' genes) in device memory, the segment's mate table (null per read), the sums.
+struct CountSegment {
+    const spl_devreads *src;
+    int64_t n_rec, n_ops, first, n;
+    int32_t shift;
+    const spl_count_maps *maps;
+    const uint32_t *bin_gene, *mate;
+    unsigned long long *sums;
+    void *stream;
+};
+
+// The counting calls' one body, over the segments of a finished, fused set: n_out sums in device memory, cleared; the maps (and
+// bin_gene's n_bins words, if any) up; launch(segment) for every segment with a read, under the profiler's scope `kernel` -- bytes:
+// what the launch must read at least, FLAG, POS and the two CIGAR offsets of a read and its ops (once: a second walk's are cached),
+// per fragment a read's word of the mate table too; the sums down and added to inout.  fragments: the set's mate table is made
+// first (mates_of).  what: the launch as an error names it.  The caller has checked its own arguments.
+template <class Launch>
+int count_segments(spl_ctx *c, const spl_dreads *dr, const char *who, const spl_count_maps &maps, int64_t n_bins, const uint32_t *bin_gene, size_t n_out, bool fragments, const char *kernel,
+                   const char *what, int64_t *inout, Launch launch)
 {
-    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_gene_count: null argument");
-    if (const int rc = gene_maps_fit("spl_gene_count", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
-    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_gene_count: the read set is not finished (spl_reads_finish)");
+    if (fragments) {
+        if (const int rc = mates_of(c, dr, who)) return rc;
+    } else {
+        if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "%s: the read set is not finished (spl_reads_finish)", who);
+        if (const int rc = fused_refusal(who, dr)) return rc;
+    }
     if (dr->segs.empty()) return SPL_OK; // (a set without a read has no arrays to be fused of, and adds nothing)
-    if (!(dr->fused && dr->groups.size() == 1))
-        return spl_set_error(SPL_ERR_ARG, "spl_gene_count needs a fused read set (all of it from one device decode or one spl_soa_upload)");
     const spl_dreads::Group &g = dr->groups[0];
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n_out = (size_t)n_genes + SPL_GENE_SPECIALS;
-    DevBuf d_out, d_as, d_ac, d_bs, d_bc;
+    DevBuf d_out, d_words[5];
     HIP_TRY(d_out.get(8 * n_out, c->stream));
     HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
-    if (n_a) {
-        HIP_TRY(d_as.get(4 * (size_t)n_a, c->stream));
-        HIP_TRY(d_ac.get(4 * (size_t)n_a, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_as.p, a_start, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_ac.p, a_code, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
+    const void *const host[5] = {maps.a.start, maps.a.code, maps.b.start, maps.b.code, bin_gene};
+    const int64_t words[5] = {maps.a.n, maps.a.n, maps.b.n, maps.b.n, n_bins};
+    for (int k = 0; k < 5; ++k) {
+        if (!words[k]) continue; // (its pointer stays null)
+        HIP_TRY(d_words[k].get(4 * (size_t)words[k], c->stream));
+        HIP_TRY(hipMemcpyAsync(d_words[k].p, host[k], 4 * (size_t)words[k], hipMemcpyHostToDevice, c->stream));
     }
-    if (n_b) {
-        HIP_TRY(d_bs.get(4 * (size_t)n_b, c->stream));
-        HIP_TRY(d_bc.get(4 * (size_t)n_b, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bs.p, b_start, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bc.p, b_code, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
-    }
+    const spl_count_maps d_maps{{maps.a.n, d_words[0].as<int32_t>(), d_words[1].as<uint32_t>(), 0u, 0u}, {maps.b.n, d_words[2].as<int32_t>(), d_words[3].as<uint32_t>(), 0u, 0u}};
     const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
     for (const spl_dreads::Segment &seg : dr->segs) {
         const spl_layout_seg &ls = g.segs[seg.group_seg];
         if (ls.n_reads <= 0) continue;
-        // bytes: what the launch must read at least -- FLAG, POS and the two CIGAR offsets of a read, and its ops
-        splprof::Scope prof("spl_gene_count_kernel", c->stream, 10.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
-        const int rc = spl_dev_launch_gene_count(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_as.as<int32_t>(), d_ac.as<uint32_t>(), n_b,
-                                                 d_bs.as<int32_t>(), d_bc.as<uint32_t>(), (uint32_t)n_genes, d_out.as<unsigned long long>(), c->stream);
-        if (rc) return spl_set_error(SPL_ERR_HIP, "gene count kernel launch: %s", hipGetErrorString((hipError_t)rc));
+        splprof::Scope prof(kernel, c->stream, (fragments ? 14.0 : 10.0) * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
+        const int rc = launch(CountSegment{&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, &d_maps, d_words[4].as<uint32_t>(), fragments ? dr->mates + ls.first : nullptr,
+                                           d_out.as<unsigned long long>(), c->stream});
+        if (rc) return spl_set_error(SPL_ERR_HIP, "%s kernel launch%s: %s", what, fragments ? " (fragments)" : "", hipGetErrorString((hipError_t)rc));
     }
     std::vector<unsigned long long> sums(n_out, 0ull);
     HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
     return SPL_OK;
+}
+
+// spl_gene_count and -- fragments -- spl_gene_count_fragments: n_genes + 3 sums.
+int gene_count(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
+               int64_t n_genes, int64_t *inout, bool fragments)
+{
+    const char *who = fragments ? "spl_gene_count_fragments" : "spl_gene_count";
+    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
+    if (const int rc = gene_maps_fit(who, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
+    return count_segments(c, dr, who, spl_count_maps{{n_a, a_start, a_code, 0u, 0u}, {n_b, b_start, b_code, 0u, 0u}}, 0, nullptr, (size_t)n_genes + SPL_GENE_SPECIALS, fragments,
+                          fragments ? "spl_gene_count_fragments_kernel" : "spl_gene_count_kernel", "gene count", inout, [&](const CountSegment &s) {
+                              return fragments ? spl_dev_launch_gene_count_fragments(s.src, s.n_rec, s.n_ops, s.first, s.n, s.shift, stranded, s.maps, (uint32_t)n_genes, s.mate, s.sums, s.stream)
+                                               : spl_dev_launch_gene_count(s.src, s.n_rec, s.n_ops, s.first, s.n, s.shift, stranded, s.maps, (uint32_t)n_genes, s.sums, s.stream);
+                          });
+}
+} // namespace
+
+// Every read's gene over a fused set's arrays: one launch per segment, n_genes + 3 sums in device memory, down and added to inout.
+extern "C" int spl_gene_count(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
+                              const uint32_t *b_code, int64_t n_genes, int64_t *inout)
+{
+    return gene_count(c, dr, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes, inout, false);
 }
 
 // The rule itself for one read: no GPU involved (test hook).  *result_out: the gene's index, -1 no feature, -2 ambiguous, -3 not counted.
@@ -4827,7 +4864,7 @@ int mates_of(spl_ctx *c, const spl_dreads *dr, const char *who)
 {
     if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "%s: the read set is not finished (spl_reads_finish)", who);
     if (dr->segs.empty()) return SPL_OK;
-    if (!(dr->fused && dr->groups.size() == 1)) return spl_set_error(SPL_ERR_ARG, "%s needs a fused read set (all of it from one device decode or one spl_soa_upload)", who);
+    if (const int rc = fused_refusal(who, dr)) return rc;
     const spl_dreads::Group &g = dr->groups[0];
     if (!g.src->name_key)
         return spl_set_error(SPL_ERR_ARG, "%s: the reads have no name keys (spl_bam_set_mate_keys before the decode, or spl_soa_upload4)", who);
@@ -5023,43 +5060,7 @@ extern "C" int spl_coverage_cursor_host(uint32_t flag, int32_t pos, const uint32
 extern "C" int spl_gene_count_fragments(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
                                         const uint32_t *b_code, int64_t n_genes, int64_t *inout)
 {
-    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_gene_count_fragments: null argument");
-    if (const int rc = gene_maps_fit("spl_gene_count_fragments", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
-    if (const int rc = mates_of(c, dr, "spl_gene_count_fragments")) return rc;
-    if (dr->segs.empty()) return SPL_OK;
-    const spl_dreads::Group &g = dr->groups[0];
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n_out = (size_t)n_genes + SPL_GENE_SPECIALS;
-    DevBuf d_out, d_as, d_ac, d_bs, d_bc;
-    HIP_TRY(d_out.get(8 * n_out, c->stream));
-    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
-    if (n_a) {
-        HIP_TRY(d_as.get(4 * (size_t)n_a, c->stream));
-        HIP_TRY(d_ac.get(4 * (size_t)n_a, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_as.p, a_start, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_ac.p, a_code, 4 * (size_t)n_a, hipMemcpyHostToDevice, c->stream));
-    }
-    if (n_b) {
-        HIP_TRY(d_bs.get(4 * (size_t)n_b, c->stream));
-        HIP_TRY(d_bc.get(4 * (size_t)n_b, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bs.p, b_start, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_bc.p, b_code, 4 * (size_t)n_b, hipMemcpyHostToDevice, c->stream));
-    }
-    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
-    for (const spl_dreads::Segment &seg : dr->segs) {
-        const spl_layout_seg &ls = g.segs[seg.group_seg];
-        if (ls.n_reads <= 0) continue;
-        // bytes: the per-read launch's, and a read's word of the mate table
-        splprof::Scope prof("spl_gene_count_fragments_kernel", c->stream, 14.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
-        const int rc = spl_dev_launch_gene_count_fragments(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_as.as<int32_t>(), d_ac.as<uint32_t>(), n_b,
-                                                           d_bs.as<int32_t>(), d_bc.as<uint32_t>(), (uint32_t)n_genes, dr->mates + ls.first, d_out.as<unsigned long long>(), c->stream);
-        if (rc) return spl_set_error(SPL_ERR_HIP, "gene count kernel launch (fragments): %s", hipGetErrorString((hipError_t)rc));
-    }
-    std::vector<unsigned long long> sums(n_out, 0ull);
-    HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
-    return SPL_OK;
+    return gene_count(c, dr, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes, inout, true);
 }
 
 // The key of a name: no GPU involved (test hook).
@@ -5130,50 +5131,28 @@ int exon_maps_fit(const char *who, int stranded, int64_t n_a, const int32_t *a_s
     if (n_bins && !bin_gene) return spl_set_error(SPL_ERR_ARG, "%s: null argument (the bins' genes)", who);
     return gene_maps_fit(who, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins); // (a bin map is a gene map whose codes are bins')
 }
+
+// spl_exon_count and -- fragments -- spl_exon_count_fragments: n_bins + 4 sums (count_segments, above).
+int exon_count(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code,
+               int64_t n_bins, const uint32_t *bin_gene, int64_t *inout, bool fragments)
+{
+    const char *who = fragments ? "spl_exon_count_fragments" : "spl_exon_count";
+    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
+    if (const int rc = exon_maps_fit(who, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
+    return count_segments(c, dr, who, spl_count_maps{{n_a, a_start, a_code, 0u, 0u}, {n_b, b_start, b_code, 0u, 0u}}, n_bins, bin_gene, (size_t)n_bins + SPL_EXON_VERDICTS, fragments,
+                          fragments ? "spl_exon_count_fragments_kernel" : "spl_exon_count_kernel", "exon count", inout, [&](const CountSegment &s) {
+                              return fragments ? spl_dev_launch_exon_count_fragments(s.src, s.n_rec, s.n_ops, s.first, s.n, s.shift, stranded, s.maps, (uint32_t)n_bins, s.bin_gene, s.mate, s.sums,
+                                                                                     s.stream)
+                                               : spl_dev_launch_exon_count(s.src, s.n_rec, s.n_ops, s.first, s.n, s.shift, stranded, s.maps, (uint32_t)n_bins, s.bin_gene, s.sums, s.stream);
+                          });
+}
 } // namespace
 
 // Every read's bins over a fused set's arrays: one launch per segment, n_bins + 4 sums in device memory, down and added to inout.
 extern "C" int spl_exon_count(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
                               const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *inout)
 {
-    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_exon_count: null argument");
-    if (const int rc = exon_maps_fit("spl_exon_count", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
-    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_exon_count: the read set is not finished (spl_reads_finish)");
-    if (dr->segs.empty()) return SPL_OK; // (a set without a read has no arrays to be fused of, and adds nothing)
-    if (!(dr->fused && dr->groups.size() == 1))
-        return spl_set_error(SPL_ERR_ARG, "spl_exon_count needs a fused read set (all of it from one device decode or one spl_soa_upload)");
-    const spl_dreads::Group &g = dr->groups[0];
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n_out = (size_t)n_bins + SPL_EXON_VERDICTS;
-    DevBuf d_out, d_gene, d_map[4];
-    HIP_TRY(d_out.get(8 * n_out, c->stream));
-    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
-    if (n_bins) {
-        HIP_TRY(d_gene.get(4 * (size_t)n_bins, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_gene.p, bin_gene, 4 * (size_t)n_bins, hipMemcpyHostToDevice, c->stream));
-    }
-    const void *const host[4] = {a_start, a_code, b_start, b_code};
-    const int64_t entries[4] = {n_a, n_a, n_b, n_b};
-    for (int m = 0; m < 4; ++m) {
-        if (!entries[m]) continue;
-        HIP_TRY(d_map[m].get(4 * (size_t)entries[m], c->stream));
-        HIP_TRY(hipMemcpyAsync(d_map[m].p, host[m], 4 * (size_t)entries[m], hipMemcpyHostToDevice, c->stream));
-    }
-    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
-    for (const spl_dreads::Segment &seg : dr->segs) {
-        const spl_layout_seg &ls = g.segs[seg.group_seg];
-        if (ls.n_reads <= 0) continue;
-        // bytes: what the launch must read at least -- FLAG, POS and the two CIGAR offsets of a read, and its ops (once: the second walk's are cached)
-        splprof::Scope prof("spl_exon_count_kernel", c->stream, 10.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
-        const int rc = spl_dev_launch_exon_count(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_map[0].as<int32_t>(), d_map[1].as<uint32_t>(), n_b,
-                                                 d_map[2].as<int32_t>(), d_map[3].as<uint32_t>(), (uint32_t)n_bins, d_gene.as<uint32_t>(), d_out.as<unsigned long long>(), c->stream);
-        if (rc) return spl_set_error(SPL_ERR_HIP, "exon count kernel launch: %s", hipGetErrorString((hipError_t)rc));
-    }
-    std::vector<unsigned long long> sums(n_out, 0ull);
-    HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
-    return SPL_OK;
+    return exon_count(c, dr, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene, inout, false);
 }
 
 // The rule itself for one read: no GPU involved (test hook).  *verdict_out: 0 counted, -1 no feature, -2 ambiguous, -3 not counted.
@@ -5193,43 +5172,7 @@ extern "C" int spl_exon_count_rule_host(uint32_t flag, int32_t pos, const uint32
 extern "C" int spl_exon_count_fragments(spl_ctx *c, const spl_dreads *dr, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
                                         const uint32_t *b_code, int64_t n_bins, const uint32_t *bin_gene, int64_t *inout)
 {
-    if (!c || !dr || !inout) return spl_set_error(SPL_ERR_ARG, "spl_exon_count_fragments: null argument");
-    if (const int rc = exon_maps_fit("spl_exon_count_fragments", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
-    if (const int rc = mates_of(c, dr, "spl_exon_count_fragments")) return rc;
-    if (dr->segs.empty()) return SPL_OK;
-    const spl_dreads::Group &g = dr->groups[0];
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t n_out = (size_t)n_bins + SPL_EXON_VERDICTS;
-    DevBuf d_out, d_gene, d_map[4];
-    HIP_TRY(d_out.get(8 * n_out, c->stream));
-    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * n_out, c->stream));
-    if (n_bins) {
-        HIP_TRY(d_gene.get(4 * (size_t)n_bins, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_gene.p, bin_gene, 4 * (size_t)n_bins, hipMemcpyHostToDevice, c->stream));
-    }
-    const void *const host[4] = {a_start, a_code, b_start, b_code};
-    const int64_t entries[4] = {n_a, n_a, n_b, n_b};
-    for (int m = 0; m < 4; ++m) {
-        if (!entries[m]) continue;
-        HIP_TRY(d_map[m].get(4 * (size_t)entries[m], c->stream));
-        HIP_TRY(hipMemcpyAsync(d_map[m].p, host[m], 4 * (size_t)entries[m], hipMemcpyHostToDevice, c->stream));
-    }
-    const spl_devreads src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar};
-    for (const spl_dreads::Segment &seg : dr->segs) {
-        const spl_layout_seg &ls = g.segs[seg.group_seg];
-        if (ls.n_reads <= 0) continue;
-        // bytes: the per-read launch's, and a read's word of the mate table
-        splprof::Scope prof("spl_exon_count_fragments_kernel", c->stream, 14.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops);
-        const int rc = spl_dev_launch_exon_count_fragments(&src, g.src->n_rec, g.src->n_ops, ls.first, ls.n_reads, ls.shift, stranded, n_a, d_map[0].as<int32_t>(), d_map[1].as<uint32_t>(), n_b,
-                                                           d_map[2].as<int32_t>(), d_map[3].as<uint32_t>(), (uint32_t)n_bins, d_gene.as<uint32_t>(), dr->mates + ls.first,
-                                                           d_out.as<unsigned long long>(), c->stream);
-        if (rc) return spl_set_error(SPL_ERR_HIP, "exon count kernel launch (fragments): %s", hipGetErrorString((hipError_t)rc));
-    }
-    std::vector<unsigned long long> sums(n_out, 0ull);
-    HIP_TRY(hipMemcpyAsync(sums.data(), d_out.p, 8 * n_out, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k < n_out; ++k) inout[k] += (int64_t)sums[k];
-    return SPL_OK;
+    return exon_count(c, dr, stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene, inout, true);
 }
 
 // The fragment rule for every read of one segment's host arrays with its mate table: no GPU involved (test hook).  verdict_out[r]:

@@ -9,16 +9,16 @@
 // decoded: on a 2 x 150 library with 300-base inserts most mates overlap, and covering per read shows a depth of two over the
 // overlap where one molecule was sequenced.  The reference has no counterpart.
 //
-// Mates and the mate table are spl_mate_rule.h's; eligibility, the track, the walk, the blocks and their clipping are
+// Mates, the mate table and A FRAGMENT'S SIDES -- which read is out, which is silent, which leads -- are spl_mate_rule.h's
+// (spl_fragment_sides; here a mate must take part too); eligibility, the track, the walk, the blocks and their clipping are
 // spl_coverage_rule.h's, unchanged.  THE RULE, per call -- one segment with its mate table, `length`, `stranded`, `strand`:
-//   a read PARTICIPATES when spl_cov_eligible and spl_cov_on_track hold for it (secondary, supplementary, duplicate and QC-failed
-//   reads still cover; only pairable reads can have a mate);
-//   read r has a PARTNER m = mate[r] when m != SPL_MATE_NONE, m < n, m != r and read m participates in this same call -- a mate on
-//   the other track of a stranded run is no partner: each mate then covers alone on its own track;
-//   a participating read with a partner m < r is SILENT: it marks nothing and is only "seen";
-//   every other participating read marks the UNION of its own clipped blocks and, if it has one, its partner's: blocks that
-//   overlap OR abut become one interval, the intervals are given ascending and disjoint.  It CONTRIBUTED when the union has a base,
-//   is PAST THE END when either read lost a base to the clipping, and its covered bases are the union's length.
+//   a read TAKES PART when spl_cov_eligible and spl_cov_on_track hold for it (secondary, supplementary, duplicate and QC-failed
+//   reads still cover; only pairable reads can have a mate).  A mate on the other track of a stranded run is no partner: each
+//   mate then covers alone on its own track;
+//   a silent read marks nothing and is only "seen";
+//   a leader marks the UNION of its own clipped blocks and, if it has one, its partner's: blocks that overlap OR abut become one
+//   interval, the intervals are given ascending and disjoint.  It CONTRIBUTED when the union has a base, is PAST THE END when
+//   either read lost a base to the clipping, and its covered bases are the union's length.
 // A read's leader depends on the reads' order; the union does not, nor do the counters: a pair contributes once, whichever leads.
 //
 // NOTHING STORED PER LANE.  One read's clipped blocks ascend and are disjoint (spl_cov_cursor: spl_cov_walk as a resumable cursor,
@@ -34,10 +34,10 @@
 
 #define SPL_COVF_COUNTERS 4   // spl_coverage_rule.h's three predicates of a read, and [3]: it led a pair whose union was taken
 #define SPL_COVF_PAIR 8u
-// What read r of a segment is to a call (spl_cov_fragment_sides):
-#define SPL_COVF_NOT_PARTICIPATING 0u
-#define SPL_COVF_SILENT 1u
-#define SPL_COVF_LEADS 2u     // to be walked: a fragment's leader, or a read without a partner
+// What read r of a segment is to a call (spl_cov_fragment_sides): spl_mate_rule.h's answers under the coverage's names.
+#define SPL_COVF_NOT_PARTICIPATING SPL_FRAG_OUT
+#define SPL_COVF_SILENT SPL_FRAG_SILENT
+#define SPL_COVF_LEADS SPL_FRAG_LEADS // to be walked: a fragment's leader, or a read without a partner
 
 // spl_cov_walk, resumable: next() gives the read's clipped blocks one by one, 0 <= s < e <= length, ascending and disjoint; bits
 // gathers SPL_COV_PAST_END as the walk meets it (complete once next() has said false).  A read of no op gives nothing.
@@ -76,40 +76,21 @@ struct spl_cov_cursor {
     }
 };
 
-// One read of a fragment as a cursor takes it: its ops (n_ops = 0: there is no such read) and p = POS - 1 + shift.
-struct spl_cov_side {
-    uint32_t c0, n_ops;
-    int64_t p;
+// The coverage's predicate: a read takes part when it is eligible and on the call's track.
+struct spl_cov_takes {
+    int stranded, strand;
+    SPL_HD bool operator()(uint32_t flag, int64_t pos, uint32_t n_ops) const { return spl_cov_eligible(flag, pos, n_ops) && spl_cov_on_track(flag, stranded, strand); }
 };
 
-// Does entry i of the arrays participate in the call?  -> its ops and POS too.
-SPL_HD bool spl_cov_participates(const spl_mate_reads &s, int64_t i, int stranded, int strand, uint32_t *c0, uint32_t *n_ops, int64_t *pos)
-{
-    const uint32_t flag = s.flag[i];
-    *pos = (int64_t)s.pos[i];
-    s.ops_of(i, c0, n_ops);
-    return spl_cov_eligible(flag, *pos, *n_ops) && spl_cov_on_track(flag, stranded, strand);
-}
+// One read of a fragment as a cursor takes it: spl_mate_rule.h's side.
+typedef spl_frag_side spl_cov_side;
 
-// What read r of the n reads of a segment is to the call: SPL_COVF_NOT_PARTICIPATING, SPL_COVF_SILENT, or SPL_COVF_LEADS -- *lead
-// is the read itself, *other its partner (n_ops = 0: it has none).
+// What read r of the n reads of a segment is to the call: SPL_COVF_NOT_PARTICIPATING, SPL_COVF_SILENT or SPL_COVF_LEADS
+// (spl_fragment_sides; a mate that does not take part is no partner).
 SPL_HD uint32_t spl_cov_fragment_sides(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, int strand, spl_cov_side *lead,
                                        spl_cov_side *other)
 {
-    *lead = spl_cov_side{0u, 0u, 0};
-    *other = spl_cov_side{0u, 0u, 0};
-    uint32_t c0, n_ops;
-    int64_t pos;
-    if (!spl_cov_participates(s, first + r, stranded, strand, &c0, &n_ops, &pos)) return SPL_COVF_NOT_PARTICIPATING;
-    *lead = spl_cov_side{c0, n_ops, pos - 1 + shift};
-    const uint32_t m = mate[r];
-    if (m == SPL_MATE_NONE || (int64_t)m >= n || (int64_t)m == r) return SPL_COVF_LEADS; // (a table of this segment: said for the memory's sake)
-    uint32_t m0, m_ops;
-    int64_t m_pos;
-    if (!spl_cov_participates(s, first + (int64_t)m, stranded, strand, &m0, &m_ops, &m_pos)) return SPL_COVF_LEADS; // (on the other track, or not eligible: no partner)
-    if ((int64_t)m < r) return SPL_COVF_SILENT;
-    *other = spl_cov_side{m0, m_ops, m_pos - 1 + shift};
-    return SPL_COVF_LEADS;
+    return spl_fragment_sides<true>(s, first, n, r, mate, shift, spl_cov_takes{stranded, strand}, lead, other);
 }
 
 // The union of the clipped blocks of a read that leads (spl_cov_fragment_sides said SPL_COVF_LEADS): emit(s, e) for each interval,

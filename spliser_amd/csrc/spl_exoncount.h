@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "spl_devpack.h"
+#include "spl_genecount.h" // spl_count_maps: a bin map is a gene map whose codes are bins'
 
 #define SPL_EXON_TILE 256       // reads a workgroup takes per grid-stride step, a read a lane
 #define SPL_EXON_GRID_MAX 1024  // workgroups a launch has at most (four a CU); the rest is grid-stride
@@ -18,18 +19,15 @@ extern "C" {
 // Workgroups of a launch over n reads.
 uint32_t spl_dev_exon_grid(int64_t n);
 // Adds what reads [first, first + n) of the arrays come to to counts (device memory, n_bins + 4 words of 64 bits: the bins, then
-// counted, no feature, ambiguous, not counted; the caller clears it).  (n_a, a_start, a_code) / (n_b, b_start, b_code): the bin maps
-// in device memory, in the coordinates of POS - 1 + shift, either may have no entry; bin_gene: n_bins genes in device memory;
+// counted, no feature, ambiguous, not counted; the caller clears it).  maps: the bin maps; bin_gene: n_bins genes in device memory;
 // stranded = 0: map a serves every read, 1 (fr) / 2 (rf): map a the '+' reads, map b the '-' reads.  n_rec / n_ops: the arrays'
 // sizes, beyond which nothing is loaded.
-int spl_dev_launch_exon_count(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a, const int32_t *a_start,
-                              const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, uint32_t n_bins, const uint32_t *bin_gene, unsigned long long *counts,
-                              void *stream);
+int spl_dev_launch_exon_count(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, const spl_count_maps *maps, uint32_t n_bins,
+                              const uint32_t *bin_gene, unsigned long long *counts, void *stream);
 // The same per FRAGMENT (spl_exonfragment_rule.h): mate = the segment's mate table in device memory, n words, indexes relative to
 // `first`; a pair of mates adds one to every distinct bin of both reads, and one to one verdict counter.
-int spl_dev_launch_exon_count_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, int64_t n_a, const int32_t *a_start,
-                                        const uint32_t *a_code, int64_t n_b, const int32_t *b_start, const uint32_t *b_code, uint32_t n_bins, const uint32_t *bin_gene,
-                                        const uint32_t *mate, unsigned long long *counts, void *stream);
+int spl_dev_launch_exon_count_fragments(const spl_devreads *src, int64_t n_rec, int64_t n_ops, int64_t first, int64_t n, int32_t shift, int stranded, const spl_count_maps *maps,
+                                        uint32_t n_bins, const uint32_t *bin_gene, const uint32_t *mate, unsigned long long *counts, void *stream);
 #ifdef __cplusplus
 }
 #endif

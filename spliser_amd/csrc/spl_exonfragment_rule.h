@@ -9,19 +9,17 @@
 // library has just decoded: on a 2 x 150 library with 300-base inserts most fragments' mates overlap in an exon, and counting per
 // read adds two to that exon's bin where both tools add one.  The reference has no counterpart.
 //
-// Mates, pairable reads, groups and the LEADER are spl_mate_rule.h's; eligibility, maps, blocks, hit stretches and bins are
+// Mates, pairable reads, groups and A FRAGMENT'S SIDES -- which read is out, which is silent, which leads -- are spl_mate_rule.h's
+// (spl_fragment_sides with spl_gene_eligible, by the table's word); eligibility, maps, blocks, hit stretches and bins are
 // spl_exoncount_rule.h's.  THE RULE, per read r of a segment with its mate table:
-//   a read that is not eligible is NOT COUNTED, one per read;
-//   an eligible read whose mate has a lower index in the segment is SILENT: it adds nothing and enters no counter;
-//   every other eligible read is a fragment's leader, or a read without a mate.  Its hit stretches are its own, over the map of
-//   its own strand, and -- if it has a mate -- the mate's, over the map of the mate's strand, by the mate's own flag (as in
-//   spl_gene_fragment_result).  VERDICT over the union of both reads' hit stretches: any stretch shared, or two stretches with bins
-//   of different genes -> AMBIGUOUS, and NO bin is incremented; no stretch with a bin -> NO FEATURE; otherwise COUNTED, and every
-//   DISTINCT bin of the union gets +1: a bin both mates hit counts once, whether the mates saw it through the same map or through
-//   the two maps of a stranded run (a `.` feature).
+//   a read that is out is NOT COUNTED, one per read; a silent read adds nothing and enters no counter;
+//   a leader's hit stretches are its own, over the map of its own strand, and -- if it has a mate -- the mate's, over the map of
+//   the mate's strand, by the mate's own flag (as in spl_gene_fragment_result).  VERDICT over the union of both reads' hit
+//   stretches: any stretch shared, or two stretches with bins of different genes -> AMBIGUOUS, and NO bin is incremented; no
+//   stretch with a bin -> NO FEATURE; otherwise COUNTED, and every DISTINCT bin of the union gets +1: a bin both mates hit counts
+//   once, whether the mates saw it through the same map or through the two maps of a stranded run (a `.` feature).
 // The four verdict counters ADDED sum to the reads minus the pairs.  By construction a fragment's verdict is the one
-// spl_gene_count_fragments gives it on the gene maps of the same features.  A mate index at or beyond n, or equal to r, means no
-// mate (a table of this segment: said for the memory's sake).
+// spl_gene_count_fragments gives it on the gene maps of the same features.
 //
 // EACH BIN ONCE, WITH NOTHING STORED PER LANE.  A chromosome's bins are numbered in the order (start, end, gene) over both maps, and
 // a map's stretches are disjoint and ascend: the bins ONE read's walk gives (spl_exon_next_bin) ascend strictly in bin number, on
@@ -46,29 +44,18 @@ struct spl_exon_side {
     bool on_b;
 };
 
-// What read r of the n reads of a segment is: SPL_EXON_NOT_COUNTED, SPL_EXON_IDLE (silent: its leader counts the fragment), or
-// SPL_EXON_COUNTED -- to be walked: *lead is the read itself, *other its mate (n_ops = 0: it has none).
+// What read r of the n reads of a segment is (spl_fragment_sides, by the table's word): SPL_EXON_NOT_COUNTED, SPL_EXON_IDLE (silent:
+// its leader counts the fragment), or SPL_EXON_COUNTED -- to be walked: *lead is the read itself, *other its mate (n_ops = 0: it
+// has none).  A side's map is settled here, from its read's own flag.
 SPL_HD uint32_t spl_exon_fragment_sides(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, spl_exon_side *lead,
                                         spl_exon_side *other)
 {
-    *lead = spl_exon_side{0u, 0u, 0, false};
-    *other = spl_exon_side{0u, 0u, 0, false};
-    const int64_t i = first + r;
-    const uint32_t flag = s.flag[i];
-    const int64_t pos = (int64_t)s.pos[i];
-    uint32_t c0, n_ops;
-    s.ops_of(i, &c0, &n_ops);
-    if (!spl_gene_eligible(flag, pos, n_ops)) return SPL_EXON_NOT_COUNTED;
-    const uint32_t m = mate[r];
-    const bool has_mate = m != SPL_MATE_NONE && (int64_t)m < n && (int64_t)m != r; // (a table of this segment: said for the memory's sake)
-    if (has_mate && (int64_t)m < r) return SPL_EXON_IDLE;
-    *lead = spl_exon_side{c0, n_ops, pos - 1 + shift, spl_gene_uses_b(flag, stranded)};
-    if (has_mate) {
-        const int64_t im = first + (int64_t)m;
-        uint32_t m0, m_ops;
-        s.ops_of(im, &m0, &m_ops);
-        *other = spl_exon_side{m0, m_ops, (int64_t)s.pos[im] - 1 + shift, spl_gene_uses_b(s.flag[im], stranded)};
-    }
+    spl_frag_side x, y;
+    const uint32_t what = spl_fragment_sides<false>(s, first, n, r, mate, shift, spl_gene_takes{}, &x, &y);
+    *lead = *other = spl_exon_side{0u, 0u, 0, false};
+    if (what != SPL_FRAG_LEADS) return what == SPL_FRAG_SILENT ? SPL_EXON_IDLE : SPL_EXON_NOT_COUNTED;
+    *lead = spl_exon_side{x.c0, x.n_ops, x.p, spl_gene_uses_b(x.flag, stranded)};
+    if (y.n_ops) *other = spl_exon_side{y.c0, y.n_ops, y.p, spl_gene_uses_b(y.flag, stranded)};
     return SPL_EXON_COUNTED;
 }
 

@@ -1,5 +1,6 @@
-// spl_mate_rule.h -- which two reads of a chromosome are MATES, and which gene a FRAGMENT counts for, as straight-line C++: the
-// rule of spl_mate_table (spl_mates.hip) and of spl_gene_count_fragments (spl_genecount.hip).
+// spl_mate_rule.h -- which two reads of a chromosome are MATES, what a read is to a per-fragment call (A FRAGMENT'S SIDES: the
+// gene, exon and coverage rules all ask it here), and which gene a FRAGMENT counts for, as straight-line C++: the rule of
+// spl_mate_table (spl_mates.hip) and of spl_gene_count_fragments (spl_genecount.hip).
 //
 // The kernels include this header with SPL_HD = __device__ __forceinline__.  It contains no HIP intrinsics, so that tests/ compile
 // it with g++ too (spl_name_key_host, spl_mate_table_host, spl_gene_fragment_rule_host, tests/hostsim/mate_rule_asan.cpp); the
@@ -27,11 +28,20 @@
 // first reads of a group stand before its second reads.  For the element at place j the group's start, its first second-kind
 // element and its end are three binary searches; the partner's place is an offset.  Nothing is linear in a group's length.
 //
-// A FRAGMENT'S GENE.  A read that is not eligible is NOT COUNTED, one per read.  An eligible read whose mate has a lower index adds
-// nothing: its LEADER counts the fragment.  Every other eligible read folds its blocks over the map of its own strand
-// (spl_gene_uses_b of its own flag) and, if it has a mate, the mate's blocks over the map of the mate's strand, by the mate's own
-// flag, into the same gene set: empty -> NO FEATURE, one gene -> that gene, else AMBIGUOUS.  (Under fr, flags 99 and 147 land on
-// the same map; a pair whose mates' strands disagree looks at both maps, as htseq-count does.)  The rows sum to reads - pairs.
+// A FRAGMENT'S SIDES (spl_fragment_sides): what read r of a segment is to a per-fragment call, asked ONCE for every such command.
+// A read that does not TAKE PART in the call (the caller's predicate: spl_gene_eligible for the gene and exon counts; eligible and
+// on the track for the coverage) is OUT.  A read that takes part and whose mate has a lower index is SILENT: its LEADER does the
+// fragment's work.  Every other read that takes part LEADS, with its mate as the second side if it has one.  A mate index that is
+// SPL_MATE_NONE, at or beyond n, or r itself means no mate (a table of this segment: said for the memory's sake).  ONE POLICY differs
+// between the commands: the counts take the table's word -- pairable reads are eligible ones, so "silent" is decided before the
+// mate is looked at -- while the coverage wants the mate to take part in this same call, and a mate that does not (on the other
+// track of a stranded run) is no partner: the read then leads alone.
+//
+// A FRAGMENT'S GENE.  A read that is out is NOT COUNTED, one per read; a silent read adds nothing.  A leader folds its blocks over
+// the map of its own strand (spl_gene_uses_b of its own flag) and, if it has a mate, the mate's blocks over the map of the mate's
+// strand, by the mate's own flag, into the same gene set: empty -> NO FEATURE, one gene -> that gene, else AMBIGUOUS.  (Under fr,
+// flags 99 and 147 land on the same map; a pair whose mates' strands disagree looks at both maps, as htseq-count does.)  The rows
+// sum to reads - pairs.
 #ifndef SPL_MATE_RULE_KEY_H
 #define SPL_MATE_RULE_KEY_H
 
@@ -140,7 +150,15 @@ SPL_HD bool spl_mate_pair_element(const uint64_t *keys, const uint32_t *index, i
     return true;
 }
 
-// ---- a fragment's gene -------------------------------------------------------------------------------------------------------------
+// ---- a fragment's sides, and its gene ---------------------------------------------------------------------------------------------
+// One read of a fragment as a walk takes it: its ops (n_ops = 0: there is no such read), p = POS - 1 + shift, and its FLAG (which
+// map serves it: spl_gene_uses_b).
+struct spl_frag_side {
+    uint32_t c0, n_ops;
+    int64_t p;
+    uint32_t flag;
+};
+
 // The arrays of a segment as the rule reads them: read r of the segment is entry first + r; mate[] is the segment's table.
 struct spl_mate_reads {
     const int32_t *pos;
@@ -154,7 +172,47 @@ struct spl_mate_reads {
         if (b < a || (int64_t)b > n_ops_total) b = a; // (offsets of the arrays' own ops: said for the memory's sake)
         *c0 = a; *n = b - a;
     }
+    // Entry i as a side; -> whether it takes part: takes(flag, POS, n_ops).
+    template <class Takes>
+    SPL_HD bool side_of(int64_t i, int64_t shift, const Takes &takes, spl_frag_side *out) const
+    {
+        const int64_t p1 = (int64_t)pos[i];
+        out->flag = flag[i];
+        ops_of(i, &out->c0, &out->n_ops);
+        out->p = p1 - 1 + shift;
+        return takes(out->flag, p1, out->n_ops);
+    }
 };
+
+#define SPL_FRAG_OUT 0u
+#define SPL_FRAG_SILENT 1u
+#define SPL_FRAG_LEADS 2u // to be walked
+
+// The counts' predicate.
+struct spl_gene_takes {
+    SPL_HD bool operator()(uint32_t flag, int64_t pos, uint32_t n_ops) const { return spl_gene_eligible(flag, pos, n_ops); }
+};
+
+// What read r of the n reads of a segment is to a call.  *lead: the read itself when it takes part (n_ops = 0: it is out); *other:
+// a leader's mate (n_ops = 0: it has none).  MateMustTake: the policy above -- false, the table's word; true, a mate that does
+// not take part is no partner.
+template <bool MateMustTake, class Takes>
+SPL_HD uint32_t spl_fragment_sides(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, const Takes &takes, spl_frag_side *lead,
+                                   spl_frag_side *other)
+{
+    const spl_frag_side none{0u, 0u, 0, 0u};
+    *lead = *other = none;
+    spl_frag_side me, its = none;
+    if (!s.side_of(first + r, shift, takes, &me)) return SPL_FRAG_OUT;
+    *lead = me;
+    const uint32_t m = mate[r];
+    bool has_mate = m != SPL_MATE_NONE && (int64_t)m < n && (int64_t)m != r; // (a table of this segment: said for the memory's sake)
+    if (MateMustTake && has_mate) has_mate = s.side_of(first + (int64_t)m, shift, takes, &its);
+    if (has_mate && (int64_t)m < r) return SPL_FRAG_SILENT;
+    if (!MateMustTake && has_mate) (void)s.side_of(first + (int64_t)m, shift, takes, &its); // (a read that is silent by the table's word never looks at its mate)
+    if (has_mate) *other = its;
+    return SPL_FRAG_LEADS;
+}
 
 // What read r of the n reads of a segment adds: a gene, SPL_GENE_NO_FEATURE, SPL_GENE_AMBIGUOUS, SPL_GENE_NOT_COUNTED -- or
 // SPL_GENE_IDLE: nothing, its leader counts the fragment.  Ops: made from a pointer to the read's first op.
@@ -162,23 +220,11 @@ template <class Ops, class Map>
 SPL_HD uint32_t spl_gene_fragment_result(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, const Map &map_a,
                                          const Map &map_b)
 {
-    const int64_t i = first + r;
-    const uint32_t flag = s.flag[i];
-    const int64_t pos = (int64_t)s.pos[i];
-    uint32_t c0, n_ops;
-    s.ops_of(i, &c0, &n_ops);
-    if (!spl_gene_eligible(flag, pos, n_ops)) return SPL_GENE_NOT_COUNTED;
-    const uint32_t m = mate[r];
-    const bool has_mate = m != SPL_MATE_NONE && (int64_t)m < n && (int64_t)m != r; // (a table of this segment: said for the memory's sake)
-    if (has_mate && (int64_t)m < r) return SPL_GENE_IDLE;
-    uint32_t set = spl_gene_set_add_blocks(0u, Ops{s.cigar + c0}, n_ops, pos - 1 + shift, spl_gene_uses_b(flag, stranded) ? map_b : map_a);
-    if (has_mate) {
-        const int64_t im = first + (int64_t)m;
-        const uint32_t mflag = s.flag[im];
-        uint32_t m0, m_ops;
-        s.ops_of(im, &m0, &m_ops);
-        set = spl_gene_set_add_blocks(set, Ops{s.cigar + m0}, m_ops, (int64_t)s.pos[im] - 1 + shift, spl_gene_uses_b(mflag, stranded) ? map_b : map_a);
-    }
+    spl_frag_side lead, other;
+    const uint32_t what = spl_fragment_sides<false>(s, first, n, r, mate, shift, spl_gene_takes{}, &lead, &other);
+    if (what != SPL_FRAG_LEADS) return what == SPL_FRAG_SILENT ? SPL_GENE_IDLE : SPL_GENE_NOT_COUNTED;
+    uint32_t set = spl_gene_set_add_blocks(0u, Ops{s.cigar + lead.c0}, lead.n_ops, lead.p, spl_gene_uses_b(lead.flag, stranded) ? map_b : map_a);
+    if (other.n_ops) set = spl_gene_set_add_blocks(set, Ops{s.cigar + other.c0}, other.n_ops, other.p, spl_gene_uses_b(other.flag, stranded) ? map_b : map_a);
     return spl_gene_result_of_set(set);
 }
 
