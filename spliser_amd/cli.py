@@ -118,9 +118,7 @@ def build_parser(fragment_switches=False):
     f = sub.add_parser("flagstat", help="(this build only) samtools flagstat's counters of a BAM, counted while it is decoded on the GPU")
     f.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
     f.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="path of the text file to write")
-    f.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
-    f.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
-    f.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _decode_flags(f)
     _filter_flags(f)
     _engine_flags(f)
     c = sub.add_parser("combine")
@@ -178,9 +176,7 @@ def build_parser(fragment_switches=False):
     s.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False, help="optional: tally one chromosome only")
     s.add_argument("-o", "--outputPath", dest="outputPath", required=False, default=None, help="optional: path of the tab-separated report to write")
     s.add_argument("--minEvidence", dest="minEvidence", type=int, default=1000, help=MIN_EVIDENCE_HELP)
-    s.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
-    s.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
-    s.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _decode_flags(s)
     _filter_flags(s)
     _engine_flags(s)
     v = sub.add_parser("coverage", help="(this build only) per-base read depth of the alignment file as a bedGraph, reduced on the GPU from the decode: "
@@ -194,9 +190,7 @@ def build_parser(fragment_switches=False):
                    help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
     v.add_argument("--perMillion", dest="perMillion", default=False, action="store_true",
                    help="values per million mapped reads: depth * 1000000 / the library size --flagstat logs (under the filters)")
-    v.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
-    v.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
-    v.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _decode_flags(v)
     # (default SUPPRESS: without the switch the parsed arguments are what they were, key for key)
     if fragment_switches:
         v.add_argument("--fragments", dest="fragments", default=argparse.SUPPRESS, action="store_true",
@@ -218,9 +212,7 @@ def build_parser(fragment_switches=False):
     n.add_argument("--isStranded", dest="isStranded", default=False, action="store_true", help="a read counts for the features of its strand only (check_strand's rule)")
     n.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
                    help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
-    n.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
-    n.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
-    n.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _decode_flags(n)
     n.add_argument("--fragments", dest="fragments", default=False, action="store_true",
                    help="paired-end: mates are paired on the GPU by a key of their names and a fragment counts once, by both mates' blocks "
                         "(htseq-count's and featureCounts -p --countReadPairs' way); a pair split over two chromosomes or by the read filter counts as two")
@@ -240,9 +232,7 @@ def build_parser(fragment_switches=False):
     x.add_argument("--isStranded", dest="isStranded", default=False, action="store_true", help="a read counts for the features of its strand only (check_strand's rule)")
     x.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
                    help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
-    x.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
-    x.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
-    x.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _decode_flags(x)
     x.add_argument("--fragments", dest="fragments", default=False, action="store_true",
                    help="(refused: `genecounts --fragments`' spelling; here the switch is --countReadPairs)")
     # (default SUPPRESS: without the switch the parsed arguments are what they were, key for key)
@@ -267,9 +257,7 @@ def build_parser(fragment_switches=False):
     i.add_argument("--isStranded", dest="isStranded", default=False, action="store_true", help="an intron is measured on the track of its strand (check_strand's rule)")
     i.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
                    help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
-    i.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
-    i.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
-    i.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    _decode_flags(i)
     if fragment_switches:
         i.add_argument("--fragments", dest="fragments", default=argparse.SUPPRESS, action="store_true",
                    help="paired-end: depth and splice counts per fragment (IRFinder's way) -- the depth is `coverage --fragments`', and a junction that both mates of "
@@ -281,6 +269,12 @@ def build_parser(fragment_switches=False):
 
 def _flag_mask(text):
     return int(text, 0)     # (0x900 as well as 2304, as samtools takes them)
+
+
+def _decode_flags(p):
+    p.add_argument("--gpuDecode", dest="gpuDecode", default=None, action="store_true", help="decode on the GPU whatever the file looks like (as for process)")
+    p.add_argument("--hostDecode", dest="gpuDecode", action="store_false", help="decode the BAM on host threads")
+    p.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
 
 
 def _filter_flags(p):

@@ -292,16 +292,13 @@ def fill_tables(tables, take, bam_paths, is_stranded, stranded_type, devices=(0,
             log("  ({}: reads kept by process, {} not decoded again)".format(os.path.basename(kept_reads[idx]), os.path.basename(bam_paths[idx])))
         else:
             source = _process.open_and_decode(bam_paths[idx], devs, None, threads, options)   # (on the sample's first device when it has one device)
-        try:
+        with _process.closing(source):
             out = _process.process_sites(table, source, "All", is_stranded, stranded_type, False, devices=devs, combine_mode=1,
                                          log=lambda m: None)
             if isinstance(source, native.BamFile) and not source.wait_all():   # not sorted by reference: again, from the whole decode
                 out = _process.process_sites(table, source, "All", is_stranded, stranded_type, False, devices=devs, combine_mode=1,
                                              log=lambda m: None)
             _process.log_filter(source, options.read_filter, log, os.path.basename(bam_paths[idx]))
-        finally:
-            if hasattr(source, "close"):
-                source.close()
         for chrom, (_, r) in out.items():
             take(idx, table.site_index[chrom], r["beta1"], r["beta2s_reads"])
 

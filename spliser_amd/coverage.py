@@ -24,14 +24,11 @@ the same names and format.  ``--perMillion --fragments`` is refused: no fragment
 by mapped reads would mislead.  Parity with deepTools / bedtools -pc is intended and unpinned: the yardstick is
 tests/covfragcases.py.
 """
-import sys
-
 import numpy as np
 
-from . import native, process as _process
+from . import native, process as _process, readsets
 
 SUFFIX, SUFFIX_PLUS, SUFFIX_MINUS = ".bedgraph", ".plus.bedgraph", ".minus.bedgraph"
-STRANDED = {"fr": 1, "rf": 2}
 
 
 def tracks_of(stranded):
@@ -40,41 +37,30 @@ def tracks_of(stranded):
 
 
 def sets_of_source(source, device, chroms, with_keys=False):
-    """A finished, fused read set per chromosome of ``chroms`` that has a read, each in turn: yields (chrom, length, dr).  On the
-    plan of ``strandedness.tally_of_source``, one device: a file decoded on the device is visited per chromosome where it lies (one
-    fused set a chromosome, shift 0); host-decoded reads and the Python reader's go up as four arrays, a fused set of their own --
-    ``with_keys``: with their name keys, which the source must have (``DecodeOptions.mate_keys``).
-    ``length``: the header's LN; a source without lengths uses the reads' ``max_end``."""
-    if with_keys and not getattr(source, "mate_keys", False):
-        raise native.SpliserNativeError(-1, "fragment counting needs a source decoded with name keys (DecodeOptions.mate_keys)")
-    is_bam = isinstance(source, native.BamFile)
-    on_device = is_bam and source.join_decoders()      # (False: the host threads have the file)
+    """A finished, fused read set per chromosome of ``chroms`` that has a read, each in turn: yields (chrom, length, dr); the set is
+    freed when the next one is asked for.  On the plan of ``readsets``, one device and the calling thread: a file decoded on the
+    device is visited per chromosome where it lies (one fused set a chromosome, shift 0); reads on the host go up as four arrays, a
+    fused set of their own -- ``with_keys``: with their name keys, which the source must have (``DecodeOptions.mate_keys``).
+    ``length``: the header's LN; a source without lengths uses the reads' ``max_end``, and a chromosome of it no read of which covers
+    a base is skipped (its set has gone up by then: it holds no covering read, and nothing is written of it)."""
+    if with_keys:
+        readsets.check_fragment_source(source)
     lengths = dict(zip(source.ref_names, source.ref_lengths)) if getattr(source, "ref_lengths", None) else {}
+    plans = readsets.plans_of(source, (device,), chroms)
+    if len(plans) != 1:
+        raise native.SpliserNativeError(-1, "the read sets are visited on one device in turn: this file was decoded in %d shares" % len(plans))
+    entries = plans[0][1]
     with native.Context(device) as ctx:
-        for chrom in chroms:
-            length = int(lengths.get(chrom, 0))
-            if on_device:
-                with ctx.begin_reads() as dr:
-                    if not dr.add_bam(source, chrom):
-                        continue
-                    dr.finish()
-                    yield chrom, length, dr
-                continue
-            rs = source.reads(chrom)
-            if rs is None or not rs.n:
-                continue
-            if length < 1:
-                length = int(rs.max_end)       # (the last base a read covers, 1-based: as many bases as the reads can tell of)
-            if length < 1:
-                continue                        # (no read covers a base: nothing to write, and no length to clip to)
-            if with_keys and getattr(rs, "name_key", None) is None:
-                raise native.SpliserNativeError(-1, "the reads of %s were decoded without name keys (mate_keys)" % chrom)
-            arrays = native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, name_key=rs.name_key if with_keys else None)
-            with ctx.upload_soa([arrays], [getattr(rs, "max_end", None)], with_keys=with_keys) as soa:
-                with ctx.begin_reads() as dr:
-                    dr.add_soa(soa, 0)
-                    dr.finish()
-                    yield chrom, length, dr
+        for chrom, add in entries:
+            with readsets.fused_set(ctx, source, chrom, add, with_keys=with_keys) as dr:
+                if dr is None:
+                    continue
+                length = int(lengths.get(chrom, 0))
+                if add is None and length < 1:
+                    length = int(source.reads(chrom).max_end)       # (the last base a read covers, 1-based: as many bases as the reads can tell of)
+                    if length < 1:
+                        continue                                    # (no read covers a base: nothing to write, and no length to clip to)
+                yield chrom, length, dr
 
 
 def union_text(tracks, taken):
@@ -103,18 +89,12 @@ def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=Non
     source without those counters is an error).  With several devices the file is decoded and covered on the first: there are no
     shares.  ``fragments``: a pair of mates covers the union of its reads' blocks once (the module's text); not with ``perMillion``.
     -> {file path: number of runs written}."""
-    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    log = _process.logger(log)
     if fragments and perMillion:
         raise ValueError("coverage: --perMillion --fragments is refused: no fragment library size is counted, and fragment depth per million mapped READS would mislead")
-    if isStranded and strandedType not in STRANDED:
-        raise ValueError("coverage: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
-    stranded = STRANDED[strandedType] if isStranded else 0
-    devices = tuple(devices)
-    if len(devices) > 1:
-        log("  (coverage: the alignment file is decoded and covered on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
-        devices = devices[:1]
+    stranded = _process.stranded_code("coverage", isStranded, strandedType)
+    devices = _process.one_device(devices, log, "coverage: the alignment file is decoded and covered")
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), flagstat=bool(perMillion), any_order=bool(anyOrder), mate_keys=bool(fragments))
-    source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
     tracks = tracks_of(stranded)
     mates = {} if fragments else None
     pair_sums = np.zeros(2 + len(tracks), np.int64)      # --fragments: pairable reads, pairs found, pairs whose union was taken per track
@@ -122,15 +102,11 @@ def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=Non
     written = dict.fromkeys(paths, 0)
     held = []          # --perMillion: (chrom, runs per track) until the library size is known
     sums = np.zeros((len(tracks), 5), np.int64)
-    try:
-        if isinstance(source, native.BamFile):
-            source.wait_all()      # (every reference is complete at the end of the file, whatever its order)
-        if anyOrder:
-            _process.log_any_order(source, log)
+    with _process.decoding(inBAM, devices, gpuDecode, threads, options, log=log) as source:
+        _process.wait_decoded(source, anyOrder, log)
         for path in paths:
             open(path, "w").close()
-        chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
-        for chrom, length, per_track in runs_of_source(source, devices[0], chroms, stranded, fragments=bool(fragments), mates=mates):
+        for chrom, length, per_track in runs_of_source(source, devices[0], _process.chroms_of(source, qChrom), stranded, fragments=bool(fragments), mates=mates):
             if fragments:
                 taken = [int(t[3]["pairs"]) for t in per_track]
                 log("  %s: %d pairable reads, %d pairs found, %s" % (chrom, mates[chrom]["pairable"], mates[chrom]["paired"] // 2, union_text(tracks, taken)))
@@ -160,9 +136,6 @@ def coverage(inBAM, outputPath, qChrom="All", isStranded=False, strandedType=Non
         if fragments:
             log("Mates: %d pairable reads, %d pairs found, %s" % (pair_sums[0], pair_sums[1], union_text(tracks, pair_sums[2:].tolist())))
         _process.log_filter(source, options.read_filter, log)
-    finally:
-        if hasattr(source, "close"):
-            source.close()
     for k, path in enumerate(paths):
         log("%s: %d runs, %d covered bases, %d %sof %d reads contributed%s" % (path, sums[k][0], sums[k][4], sums[k][2], "fragments and single reads " if fragments else "", sums[k][1],
                                                                           ", %d ran past the end of their reference" % sums[k][3] if sums[k][3] else ""))

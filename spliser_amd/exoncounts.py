@@ -31,11 +31,12 @@ same features.  The deliberate differences from the tools are that command's: a 
 counts as two single-end fragments, and names are compared by a 63-bit hash.  Parity is intended and unpinned; the yardstick is
 tests/exonfragcases.py.  With several devices the file is decoded and counted on the first one.
 """
-import sys
+import threading
+import timeit
 
 import numpy as np
 
-from . import genecounts as _gc, native, process as _process
+from . import genecounts as _gc, native, process as _process, readsets, shard
 
 BINS_SUFFIX, COUNTS_SUFFIX = ".exonbins.tsv", ".exoncounts.tsv"
 SHARED = native.GENE_MANY
@@ -50,7 +51,7 @@ def _pieces(left, right, gene):
     left, right, gene = left[keep], right[keep], gene[keep]
     if not left.shape[0]:
         return np.zeros(0, np.int64), np.zeros(0, np.int64)
-    if int(right.max()) + 1 > _gc.COORD_MAX:
+    if int(right.max()) + 1 > shard.COORD_MAX:
         raise native.SpliserNativeError(-6, "a gene ends beyond the int32 coordinate space")
     cuts = np.unique(np.concatenate((left, right)))
     m_left, m_right, m_gene = _gc.merged_per_gene(left, right, gene)
@@ -129,38 +130,31 @@ class Bins(object):
 
 def counts_of_source(source, devices, chroms, bins, stranded=0, per_chrom=None, fragments=False, mates=None):
     """``spl_exon_count`` over every chromosome of ``chroms`` -> ({chrom: int64[n_bins] the bins' reads}, int64[4] the reads counted,
-    without a feature, ambiguous, not counted), on the plan of ``genecounts.over_fused_sets``.  A chromosome without a feature has
+    without a feature, ambiguous, not counted), on the plan of ``readsets.over_fused_sets``.  A chromosome without a feature has
     no bin, and every eligible read on it is without a feature.  ``per_chrom``: a dict that gets, per chromosome with reads, its
     int64[4].  ``fragments``: ``spl_exon_count_fragments`` -- a pair of mates counts once per bin; the source was decoded with
     ``mate_keys`` and not in shares (an error otherwise).  ``mates``: a dict that then gets, per chromosome with reads, int64[4] as
     ``genecounts.counts_of_source`` fills it."""
-    import threading
     per_bin, total, lock = {}, np.zeros(4, np.int64), threading.Lock()
     nothing = (None, None, np.zeros(0, np.uint32))
-    if fragments and not getattr(source, "mate_keys", False):
-        raise native.SpliserNativeError(-1, "fragment counting needs a source decoded with name keys (DecodeOptions.mate_keys)")
-    if fragments and getattr(source, "shares", None):
-        raise native.SpliserNativeError(-1, "fragment counting needs the file decoded on one device: mates can lie either side of a share's cut")
+    if fragments:
+        readsets.check_fragment_source(source)
 
     def count(dr, chrom):
         a, b, bin_gene = bins.by_chrom.get(chrom, nothing)
         t = dr.exon_counts(bin_gene, a, b, stranded, fragments=fragments)
-        stats = dr.mate_table(0)[1] if fragments and mates is not None else None
+        row = _gc.mate_row(dr) if fragments and mates is not None else None
         n = bin_gene.shape[0]
         with lock:
-            if stats is not None:
-                row = mates.setdefault(chrom, np.zeros(4, np.int64))
-                row += [dr.n, stats["pairable"], stats["paired"], stats["unpaired_mate_mapped"]]
+            _gc.add_row(mates, chrom, row)
             if chrom in per_bin:
                 per_bin[chrom] += t[:n]
             else:
                 per_bin[chrom] = t[:n].copy()
             total[:] += t[n:]
-            if per_chrom is not None:
-                row = per_chrom.setdefault(chrom, np.zeros(4, np.int64))
-                row += t[n:]
+            _gc.add_row(per_chrom, chrom, t[n:])
 
-    _gc.over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments))
+    readsets.over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments))
     return per_bin, total
 
 
@@ -200,45 +194,24 @@ def exoncounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
     ``<outputPath>.exoncounts.tsv``.  ``qChrom``: the reads of that chromosome, and the bins on it, under the ids they have in the
     whole annotation.  ``countReadPairs``: a pair of mates counts once per bin (the module's text); the files' format is the same.
     -> (the rows' counts, int64[4]: counted, no feature, ambiguous, not counted)."""
-    import timeit
-    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    log = _process.logger(log)
     if annotationFile is None:
         raise ValueError("exoncounts: an annotation file (-A) is required")
-    if isStranded and strandedType not in _gc.STRANDED:
-        raise ValueError("exoncounts: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
-    stranded = _gc.STRANDED[strandedType] if isStranded else 0
-    devices = tuple(devices)
-    if countReadPairs and len(devices) > 1:
-        log("  (--countReadPairs: the alignment file is decoded and counted on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
-        devices = devices[:1]
+    stranded = _process.stranded_code("exoncounts", isStranded, strandedType)
+    devices = _process.one_device(devices, log, "--countReadPairs: the alignment file is decoded and counted") if countReadPairs else tuple(devices)
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(countReadPairs))
-    source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
-    try:
+    with _process.decoding(inBAM, devices, gpuDecode, threads, options, log=log) as source:
         t0 = timeit.default_timer()
         features = _gc.read_features(annotationFile, aType, idAttr)
         bins = Bins(features, stranded)
-        log("Annotation: %d %s features of %d genes on %d chromosomes (read in %.3f s)" % (sum(v[0].shape[0] for v in features.by_chrom.values()), aType, len(features.ids),
-                                                                                            len(features.chroms), timeit.default_timer() - t0))
+        _gc.log_annotation(features, aType, t0, log)
         log("Bins: %d exon counting bins" % bins.n)
-        if isinstance(source, native.BamFile):
-            source.wait_all()      # (every reference is complete at the end of the file, whatever its order)
-        if anyOrder:
-            _process.log_any_order(source, log)
-        chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+        _process.wait_decoded(source, anyOrder, log)
+        chroms = _process.chroms_of(source, qChrom)
         per_chrom, mates = {}, ({} if countReadPairs else None)
         per_bin, verdicts = counts_of_source(source, devices, chroms, bins, stranded, per_chrom, fragments=bool(countReadPairs), mates=mates)
-        what = "fragments" if countReadPairs else "reads"
-        for chrom in chroms:
-            if chrom in per_chrom:
-                log("  %s: %d %s counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom, int(per_chrom[chrom][0]), what) + tuple(int(v) for v in per_chrom[chrom][1:])))
-            if countReadPairs and chrom in mates:
-                log("  %s: %s" % (chrom, _gc.mates_line(mates[chrom])))
-        if countReadPairs:
-            log("  mates: %s" % _gc.mates_line(sum(mates.values(), np.zeros(4, np.int64))))
+        _gc.log_verdicts(chroms, per_chrom, mates, log)
         _process.log_filter(source, options.read_filter, log)
-    finally:
-        if hasattr(source, "close"):
-            source.close()
     rows = bins.rows_on(None if qChrom == "All" else qChrom)
     counts = row_counts(bins, per_bin, rows)
     write_bins(outputPath + BINS_SUFFIX, bins, rows)

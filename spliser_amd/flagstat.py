@@ -9,8 +9,6 @@ record of the file, placed or not; under a read filter, the records of the pre-f
 The text is samtools' layout as of 1.13, restated from its documentation; parity with the tool itself is not pinned by a test
 (DESIGN.md section 9): the definition of the counters is ``spl_flagstat.h``.
 """
-import sys
-
 from . import native, process as _process
 
 SUFFIX = ".flagstat.txt"
@@ -50,17 +48,14 @@ def flagstat(inBAM, outputPath, devices=(0,), threads=0, gpuDecode=None, minMapQ
     The decode is the NORMAL one with its reads dropped: the blocks are inflated, scanned and their records extracted as for
     ``process``, and nothing is counted against sites.  A decode that stops after the scan would save the extraction kernel's
     share of the decode (about a tenth of it) at the price of a second path through the window loop; it is not arranged."""
-    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    log = _process.logger(log)
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), flagstat=True, any_order=bool(anyOrder))
-    source = _process.open_and_decode(inBAM, tuple(devices), gpuDecode, threads, options, log=log)
-    try:
+    with _process.decoding(inBAM, devices, gpuDecode, threads, options, log=log) as source:
         counts = source.flagstat()
         if anyOrder:
             _process.log_any_order(source, log)
         if gpuDecode is not False and source.decline_reason():
             log("  (the alignment file was decoded on host threads, not on the GPU: %s)" % source.decline_reason())
         _process.log_filter(source, options.read_filter, log)
-    finally:
-        source.close()
     write_and_log(outputPath, counts, log)
     return counts

@@ -29,17 +29,17 @@ where two names collide: about n^2 / 2^64 pairs for n names, 5e-6 for 10 M).  Pa
 intended and unpinned: the yardstick is tests/matecases.py.  With several devices the file is decoded and counted on the first
 one: mates can lie either side of a share's cut.
 """
-import sys
+import threading
+import timeit
 
 import numpy as np
 
-from . import native, process as _process
+from . import native, process as _process, readsets
+from .shard import COORD_MAX        # (the bound ``strandedness.cover_map`` enforces on a map's 1-based positions)
 
 SUFFIX = ".genecounts.tsv"
-STRANDED = {"fr": 1, "rf": 2}
 MANY = native.GENE_MANY
 SPECIALS = native.GENE_SPECIALS
-COORD_MAX = 2147483581              # the bound ``strandedness.cover_map`` enforces on a map's 1-based positions
 
 
 class Features(object):
@@ -172,92 +172,44 @@ def maps_of(features, chroms, stranded=False):
     return out
 
 
-def over_fused_sets(source, devices, chroms, visit, with_keys=False):
-    """The plan both counting commands run a source by (``strandedness.tally_of_source``'s): ``visit(dr, chrom)`` for a finished, fused
-    read set per chromosome of ``chroms`` -- called from one thread per device, so it guards what it adds to.  A file decoded on the
-    device is visited per chromosome where it lies (the sets stay fused); after a decode in shares every device visits its piece of a
-    chromosome -- what the visits add must add over reads; host-decoded reads and the Python reader's go up as four arrays
-    (``upload_soa``), a fused set of their own -- ``with_keys``: with their name keys, which the source must have.  The first exception
-    of a visit is raised when all have ended."""
-    import threading
-    is_bam = isinstance(source, native.BamFile)
-    errors, lock = [], threading.Lock()
-    on_device = is_bam and source.join_decoders()      # (however the device decode was started; False: the host threads have the file)
-    shares = getattr(source, "shares", None) if on_device else None
+def mate_row(dr):
+    """-> the row a read set adds to ``mates``: reads, pairable reads, reads with a mate, pairable reads without one whose flag says
+    the mate is mapped (``spl_mate_table``)."""
+    stats = dr.mate_table(0)[1]
+    return [dr.n, stats["pairable"], stats["paired"], stats["unpaired_mate_mapped"]]
 
-    def run(device, jobs):
-        try:
-            with native.Context(device) as ctx:
-                for chrom, add in jobs:
-                    if add is None:
-                        rs = source.reads(chrom)
-                        if rs is None or not rs.n:
-                            continue
-                        if with_keys and getattr(rs, "name_key", None) is None:
-                            raise native.SpliserNativeError(-1, "the reads of %s were decoded without name keys (mate_keys)" % chrom)
-                        arrays = native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, name_key=rs.name_key if with_keys else None)
-                        with ctx.upload_soa([arrays], [getattr(rs, "max_end", None)], with_keys=with_keys) as soa:
-                            with ctx.begin_reads() as dr:
-                                dr.add_soa(soa, 0)
-                                dr.finish()
-                                visit(dr, chrom)
-                    else:
-                        with ctx.begin_reads() as dr:
-                            if add(dr):
-                                dr.finish()
-                                visit(dr, chrom)
-        except Exception as exc:
-            with lock:
-                errors.append(exc)
 
-    if shares:
-        plans = []
-        for k, (device, names) in enumerate(shares):
-            held = [c for c in chroms if c in names and source.share_ref(k, c)[0] > 0]
-            plans.append((device, [(c, (lambda dr, k=k, c=c: dr.add_bam_share(source, k, c))) for c in held]))
-    elif on_device:
-        plans = [(devices[0], [(c, (lambda dr, c=c: dr.add_bam(source, c))) for c in chroms])]
-    else:
-        plans = [(devices[0], [(c, None) for c in chroms])]
-    workers = [threading.Thread(target=run, args=plan) for plan in plans if plan[1]]
-    for w in workers:
-        w.start()
-    for w in workers:
-        w.join()
-    if errors:
-        raise errors[0]
+def add_row(rows, chrom, row):
+    """``rows[chrom] += row`` (int64[4]) where both are kept; under the caller's lock."""
+    if rows is not None and row is not None:
+        got = rows.setdefault(chrom, np.zeros(4, np.int64))
+        got += row
 
 
 def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None, fragments=False, mates=None):
     """``spl_gene_count`` over every chromosome of ``chroms`` -> int64[n_genes + 3], the sums: the genes' reads, then no feature,
-    ambiguous, not counted.  On the plan of ``over_fused_sets``: counts add over reads, so the pieces of a decode in shares are counted
-    where they lie and the host adds.  ``maps``: {chrom: (map a, map b)} (``maps_of``); a chromosome without one has no feature.
+    ambiguous, not counted.  On the plan of ``readsets.over_fused_sets``: counts add over reads, so the pieces of a decode in shares are
+    counted where they lie and the host adds.  ``maps``: {chrom: (map a, map b)} (``maps_of``); a chromosome without one has no feature.
     ``per_chrom``: a dict that gets, per chromosome with reads, int64[4]: counted, no feature, ambiguous, not counted.
     ``fragments``: ``spl_gene_count_fragments`` -- a pair of mates counts once; the source was decoded with ``mate_keys`` and not in
     shares (an error otherwise).  ``mates``: a dict that then gets, per chromosome with reads, int64[4]: reads, pairable reads, reads
     with a mate, pairable reads without one whose flag says the mate is mapped."""
-    import threading
     n_genes = int(n_genes)
     total, lock = np.zeros(n_genes + 3, np.int64), threading.Lock()
-    if fragments and not getattr(source, "mate_keys", False):
-        raise native.SpliserNativeError(-1, "fragment counting needs a source decoded with name keys (DecodeOptions.mate_keys)")
-    if fragments and getattr(source, "shares", None):
-        raise native.SpliserNativeError(-1, "fragment counting needs the file decoded on one device: mates can lie either side of a share's cut")
+    if fragments:
+        readsets.check_fragment_source(source)
 
     def count(dr, chrom):
         a, b = maps.get(chrom, (None, None))
         t = dr.gene_counts(n_genes, a, b, stranded, fragments=fragments)
-        stats = dr.mate_table(0)[1] if fragments and mates is not None else None
+        row = mate_row(dr) if fragments and mates is not None else None
+        verdicts = [int(t[:n_genes].sum()), int(t[n_genes]), int(t[n_genes + 1]), int(t[n_genes + 2])] if per_chrom is not None else None
         with lock:
-            if stats is not None:
-                row = mates.setdefault(chrom, np.zeros(4, np.int64))
-                row += [dr.n, stats["pairable"], stats["paired"], stats["unpaired_mate_mapped"]]
+            add_row(mates, chrom, row)
             total[:] += t
-            if per_chrom is not None:
-                row = per_chrom.setdefault(chrom, np.zeros(4, np.int64))
-                row += [int(t[:n_genes].sum()), int(t[n_genes]), int(t[n_genes + 1]), int(t[n_genes + 2])]
+            add_row(per_chrom, chrom, verdicts)
 
-    over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments))
+    readsets.over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments))
     return total
 
 
@@ -266,6 +218,24 @@ def mates_line(row):
     reads, pairable, paired, lonely = (int(v) for v in row)
     return ("%d reads, %d pairable, %d pairs, %d pairable reads without a mate on their chromosome (%d of them with a mapped mate by their flag)"
             % (reads, pairable, paired // 2, pairable - paired, lonely))
+
+
+def log_annotation(features, aType, t0, log, more=""):
+    """The line a command says once its annotation is read (``more``: what the command made of it)."""
+    log("Annotation: %d %s features of %d genes on %d chromosomes%s (read in %.3f s)" % (sum(v[0].shape[0] for v in features.by_chrom.values()), aType, len(features.ids),
+                                                                                          len(features.chroms), more, timeit.default_timer() - t0))
+
+
+def log_verdicts(chroms, per_chrom, mates, log):
+    """Per chromosome with reads its verdict line -- and, ``mates`` not None (fragments were counted), its mates line, then their sum."""
+    what = "reads" if mates is None else "fragments"
+    for chrom in chroms:
+        if chrom in per_chrom:
+            log("  %s: %d %s counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom, int(per_chrom[chrom][0]), what) + tuple(int(v) for v in per_chrom[chrom][1:])))
+        if mates is not None and chrom in mates:
+            log("  %s: %s" % (chrom, mates_line(mates[chrom])))
+    if mates is not None:
+        log("  mates: %s" % mates_line(sum(mates.values(), np.zeros(4, np.int64))))
 
 
 def write_counts(path, ids, counts, only=None):
@@ -286,45 +256,24 @@ def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
     """The ``genecounts`` command: one decode, the annotation read meanwhile, ``<outputPath>.genecounts.tsv``.  ``qChrom``: the reads
     of that chromosome, and the genes with a feature on it.  ``fragments``: a pair of mates counts once (the module's text); the
     file's format is the same.  -> int64[n_genes + 3], the counts written."""
-    import timeit
-    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    log = _process.logger(log)
     if annotationFile is None:
         raise ValueError("genecounts: an annotation file (-A) is required")
-    if isStranded and strandedType not in STRANDED:
-        raise ValueError("genecounts: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
-    stranded = STRANDED[strandedType] if isStranded else 0
-    devices = tuple(devices)
-    if fragments and len(devices) > 1:
-        log("  (--fragments: the alignment file is decoded and counted on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
-        devices = devices[:1]
+    stranded = _process.stranded_code("genecounts", isStranded, strandedType)
+    devices = _process.one_device(devices, log, "--fragments: the alignment file is decoded and counted") if fragments else tuple(devices)
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(fragments))
-    source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
-    try:
+    with _process.decoding(inBAM, devices, gpuDecode, threads, options, log=log) as source:
         t0 = timeit.default_timer()
         features = read_features(annotationFile, aType, idAttr)
         n_genes = len(features.ids)
-        log("Annotation: %d %s features of %d genes on %d chromosomes (read in %.3f s)" % (sum(v[0].shape[0] for v in features.by_chrom.values()), aType, n_genes,
-                                                                                            len(features.chroms), timeit.default_timer() - t0))
-        if isinstance(source, native.BamFile):
-            source.wait_all()      # (every reference is complete at the end of the file, whatever its order)
-        if anyOrder:
-            _process.log_any_order(source, log)
-        chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+        log_annotation(features, aType, t0, log)
+        _process.wait_decoded(source, anyOrder, log)
+        chroms = _process.chroms_of(source, qChrom)
         maps = maps_of(features, chroms, stranded)
         per_chrom, mates = {}, ({} if fragments else None)
         counts = counts_of_source(source, devices, chroms, maps, n_genes, stranded, per_chrom, fragments=bool(fragments), mates=mates)
-        what = "fragments" if fragments else "reads"
-        for chrom in chroms:
-            if chrom in per_chrom:
-                log("  %s: %d %s counted, %d without a feature, %d ambiguous, %d not counted" % ((chrom, int(per_chrom[chrom][0]), what) + tuple(int(v) for v in per_chrom[chrom][1:])))
-            if fragments and chrom in mates:
-                log("  %s: %s" % (chrom, mates_line(mates[chrom])))
-        if fragments:
-            log("  mates: %s" % mates_line(sum(mates.values(), np.zeros(4, np.int64))))
+        log_verdicts(chroms, per_chrom, mates, log)
         _process.log_filter(source, options.read_filter, log)
-    finally:
-        if hasattr(source, "close"):
-            source.close()
     only = None if qChrom == "All" else features.genes_on(qChrom)
     path = outputPath + SUFFIX
     n_rows = write_counts(path, features.ids, counts, only)

@@ -24,14 +24,13 @@ both mates' blocks, once: ``spl_intron_depth_fragments``) and the junction table
 read has an earlier mate that supports the same junction adds nothing (csrc/spl_junctionfragment_rule.h).  Same file, same header.
 ``junctions`` and ``process`` have no such switch: the BED score feeds SpliSER's alpha, which stays per read beside beta1 / beta2.
 """
-import sys
+import timeit
 
 import numpy as np
 
-from . import coverage as _coverage, genecounts as _gc, native, process as _process
+from . import coverage as _coverage, genecounts as _gc, native, process as _process, shard
 
 SUFFIX = ".introns.tsv"
-STRANDED = _gc.STRANDED
 HEADER = ("id", "gene", "chrom", "start", "end", "strand", "measurable", "covered", "depth_n", "depth_sum", "depth", "splice_left", "splice_right", "splice_exact", "IRratio")
 PLUS, MINUS = 43, 45
 
@@ -59,7 +58,7 @@ def introns_of(left, right, gene):
     empty = np.zeros(0, np.int64)
     if not left.shape[0]:
         return empty, empty, empty
-    if int(right.max()) + 1 > _gc.COORD_MAX:
+    if int(right.max()) + 1 > shard.COORD_MAX:
         raise native.SpliserNativeError(-6, "a feature ends beyond the int32 coordinate space")
     m_left, m_right, m_gene = _gc.merged_per_gene(left, right, gene)
     same = m_gene[1:] == m_gene[:-1]
@@ -180,34 +179,23 @@ def intronretention(inBAM, annotationFile, outputPath, aType="exon", idAttr="gen
     of that chromosome, under the ids they have in the whole annotation.  With several devices the file is decoded and measured on
     the first: there are no shares.  ``fragments``: depth and splice counts per fragment (the module's text).  -> the number of rows
     written."""
-    import timeit
-    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    log = _process.logger(log)
     if annotationFile is None:
         raise ValueError("intronretention: an annotation file (-A) is required")
-    if isStranded and strandedType not in STRANDED:
-        raise ValueError("intronretention: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)")
+    stranded = _process.stranded_code("intronretention", isStranded, strandedType)
     trim = int(trimPercent)
     if not 0 <= trim <= 49:
         raise ValueError("intronretention: --trimPercent must be in 0..49")
-    stranded = STRANDED[strandedType] if isStranded else 0
-    devices = tuple(devices)
-    if len(devices) > 1:
-        log("  (intronretention: the alignment file is decoded and measured on device %d alone, not in shares over %d devices)" % (devices[0], len(devices)))
-        devices = devices[:1]
+    devices = _process.one_device(devices, log, "intronretention: the alignment file is decoded and measured")
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(fragments))
-    source = _process.open_and_decode(inBAM, devices, gpuDecode, threads, options, log=log)
     pair_sums = np.zeros(2, np.int64)      # --fragments: pairable reads, pairs found
-    try:
+    with _process.decoding(inBAM, devices, gpuDecode, threads, options, log=log) as source:
         t0 = timeit.default_timer()
         features = _gc.read_features(annotationFile, aType, idAttr)
         table = Table(features, bool(stranded))
-        log("Annotation: %d %s features of %d genes on %d chromosomes, %d introns (read in %.3f s)" % (sum(v[0].shape[0] for v in features.by_chrom.values()), aType, len(features.ids),
-                                                                                                        len(features.chroms), table.gene.shape[0], timeit.default_timer() - t0))
-        if isinstance(source, native.BamFile):
-            source.wait_all()      # (every reference is complete at the end of the file, whatever its order)
-        if anyOrder:
-            _process.log_any_order(source, log)
-        wanted = [c for c in table.chroms if qChrom == c or qChrom == "All"]
+        _gc.log_annotation(features, aType, t0, log, ", %d introns" % table.gene.shape[0])
+        _process.wait_decoded(source, anyOrder, log)
+        wanted = list(table.chroms) if qChrom == "All" else [c for c in table.chroms if c == qChrom]
         n = table.gene.shape[0]
         numbers, splices, done = np.zeros((n, 4), np.int64), np.zeros((n, 3), np.int64), set()
         visit = [c for c in source.ref_names if c in wanted]
@@ -239,9 +227,6 @@ def intronretention(inBAM, annotationFile, outputPath, aType="exon", idAttr="gen
         if fragments:
             log("Mates: %d pairable reads, %d pairs found" % (pair_sums[0], pair_sums[1]))
         _process.log_filter(source, options.read_filter, log)
-    finally:
-        if hasattr(source, "close"):
-            source.close()
     keep = np.flatnonzero(np.isin(table.chrom, [table.chroms.index(c) for c in wanted]))
     path = outputPath + SUFFIX
     written = write_rows(path, table, keep, numbers[keep], splices[keep])

@@ -10,11 +10,11 @@ chromEnd - blockSizes[1]``, ``alpha = score``, strand in column 6.  Defaults of 
 and ``spl_junctions`` keys its table by it (mode 3), so that a junction carried by ``+``-tagged, ``-``-tagged and untagged reads
 is three lines.  An XS of another type (BWA's XS:i) or another value counts as no tag: ``?``.
 """
-import sys
+import threading
 
 import numpy as np
 
-from . import native, process as _process
+from . import native, process as _process, readsets
 
 
 def write_junction_bed(handle, chrom, table, first_number=1):
@@ -84,83 +84,41 @@ def log_xs_tally(tally, log):
 
 def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, maxIntron, tally=None):
     """The junction table of every chromosome of ``chroms`` that has reads, from an alignment source whose decode has been
-    started (``process.open_and_decode``): -> {chrom: (reads, table)}.  The reads are taken where the decode left them: after a
-    decode on the device the read sets are fused and stay so (``spl_junctions`` reads the arrays; nothing is laid out, nothing
-    decoded again by whoever counts the same reads afterwards).  A decode in shares: every device takes the table of ITS piece of
-    a chromosome, and the pieces are merged here (``merge_tables``).  A file the host's threads decode, and SAM text: the first
-    device, chromosome by chromosome as they become complete.  ``stranded`` = ``native.STRAND_FROM_XS``: the source must have been
-    opened with ``aux_strand`` -- the device decode's sets have the strand bytes, host-decoded reads and SAM text go up with
-    theirs as arrays (``spl_soa_upload3``: that mode is the fused kernel's).  ``tally``: a list whose three entries get the
+    started (``process.open_and_decode``): -> {chrom: (reads, table)}.  On the plan of ``readsets``: after a decode on the device
+    the read sets are fused and stay so (``spl_junctions`` reads the arrays; nothing is laid out, nothing decoded again by whoever
+    counts the same reads afterwards); after a decode in shares every device takes the table of ITS piece of a chromosome, and the
+    pieces are merged here (``merge_tables``).  Reads on the host -- a file the host's threads decode, SAM text -- are this
+    function's own case: they go to the first device unfused (``add_bam`` / ``add``), chromosome by chromosome AS THEY BECOME COMPLETE,
+    not after the whole file (``process`` without ``-b`` counts on behind them).  ``stranded`` = ``native.STRAND_FROM_XS``: the source
+    must have been opened with ``aux_strand`` -- the device decode's sets have the strand bytes, reads on the host go up with theirs
+    as arrays, by the plan (``spl_soa_upload3``: that mode is the fused kernel's).  ``tally``: a list whose three entries get the
     junction-supporting reads by strand (+, -, ?) added: the sums of the tables' counts."""
-    import threading
     from_xs = stranded == native.STRAND_FROM_XS
     if from_xs and not getattr(source, "aux_strand", False):
         raise ValueError("strand from XS: the alignment source was opened without aux_strand")
-    is_bam = isinstance(source, native.BamFile)
-    knobs = (minAnchor, minIntron, maxIntron)
-    pieces, errors, lock = {}, [], threading.Lock()
-    on_device = is_bam and source.device_decode_started() and source.join_decoders()
-    shares = getattr(source, "shares", None) if on_device else None
+    pieces, lock = {}, threading.Lock()
 
-    def take(ctx, chrom, add):
-        with ctx.begin_reads() as dr:
-            n = add(dr)
-            if not n:
+    def add_host(dr, chrom):
+        if isinstance(source, native.BamFile):
+            return dr.add_bam(source, chrom)
+        rs = source.reads(chrom)
+        if rs is None or not rs.n:
+            return 0
+        dr.add(native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar))
+        return rs.n
+
+    def job(ctx, chrom, add):
+        if add is None and not from_xs:
+            def add(dr):
+                return add_host(dr, chrom)
+        with readsets.fused_set(ctx, source, chrom, add, with_strand=from_xs) as dr:
+            if dr is None:
                 return
-            dr.finish()
-            table = dr.junctions(stranded, *knobs)
+            n, table = dr.n, dr.junctions(stranded, minAnchor, minIntron, maxIntron)
         with lock:
             pieces.setdefault(chrom, []).append((n, table))
 
-    def take_arrays(ctx, chrom, rs):       # (strand from XS, reads on the host: up as five arrays, a fused set of their own)
-        if rs is None or not rs.n:
-            return
-        if rs.xs is None:
-            raise native.SpliserNativeError(-1, "%s: reads without strand bytes" % chrom)
-        with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, xs=rs.xs)], [rs.max_end], with_strand=True) as soa:
-            with ctx.begin_reads() as dr:
-                dr.add_soa(soa, 0)
-                dr.finish()
-                table = dr.junctions(stranded, *knobs)
-        with lock:
-            pieces.setdefault(chrom, []).append((rs.n, table))
-
-    def run(device, jobs):
-        try:
-            with native.Context(device) as ctx:
-                for chrom, add in jobs:
-                    if add is None:
-                        take_arrays(ctx, chrom, source.reads(chrom))
-                    else:
-                        take(ctx, chrom, add)
-        except Exception as exc:
-            with lock:
-                errors.append(exc)
-
-    if shares:
-        plans = []
-        for k, (device, names) in enumerate(shares):
-            held = [c for c in chroms if c in names and source.share_ref(k, c)[0] > 0]
-            plans.append((device, [(c, (lambda dr, k=k, c=c: dr.add_bam_share(source, k, c))) for c in held]))
-    elif from_xs and not on_device:
-        plans = [(devices[0], [(c, None) for c in chroms])]
-    elif is_bam:
-        plans = [(devices[0], [(c, (lambda dr, c=c: dr.add_bam(source, c))) for c in chroms])]
-    else:
-        def add_sam(dr, c):
-            rs = source.reads(c)
-            if rs is None or not rs.n:
-                return 0
-            dr.add(native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar))
-            return rs.n
-        plans = [(devices[0], [(c, (lambda dr, c=c: add_sam(dr, c))) for c in chroms])]
-    workers = [threading.Thread(target=run, args=plan) for plan in plans if plan[1]]
-    for w in workers:
-        w.start()
-    for w in workers:
-        w.join()
-    if errors:
-        raise errors[0]
+    readsets.run_plans(readsets.plans_of(source, devices, chroms), job)
     if tally is not None:
         for got in pieces.values():
             for _, t in got:
@@ -178,7 +136,7 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
     ``strandFromXS``: for an unstranded library, the strand column from the reads' XS:A tag (regtools' ``-s XS``) instead of ``?``;
     an alternative to ``isStranded``.  ``anyOrder`` (changes no result): the BAM may be in any record order -- its reads are
     coordinate-sorted on the GPU after the decode instead of by ``samtools sort`` beforehand (``process``)."""
-    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    log = _process.logger(log)
     auto = strandedType == "auto"
     if auto and strandFromXS:
         raise ValueError("strandedType 'auto' and strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
@@ -190,13 +148,12 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
     if strandFromXS:
         stranded = native.STRAND_FROM_XS
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), aux_strand=bool(strandFromXS or auto), any_order=bool(anyOrder))
-    source = _process.open_and_decode(inBAM, tuple(devices), None, threads, options, log=log)   # (on the GPU(s), like `process`)
-    try:
+    with _process.decoding(inBAM, devices, None, threads, options, log=log) as source:   # (on the GPU(s), like `process`)
         if auto:     # (the library's strandedness from the reads' XS:A tags -- this command has no annotation --, then as if it had been typed)
             from . import strandedness as _strandedness
             isStranded, strandedType = _strandedness.resolve_auto(source, devices, isStranded, None, _strandedness.MIN_EVIDENCE if minEvidence is None else int(minEvidence), log)
             stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
-        chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+        chroms = _process.chroms_of(source, qChrom)
         if anyOrder:
             _process.log_any_order(source, log)
         tally = [0, 0, 0] if strandFromXS else None
@@ -206,9 +163,6 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
         _process.log_filter(source, options.read_filter, log)
         if strandFromXS:
             log_xs_tally(tally, log)
-    finally:
-        if hasattr(source, "close"):
-            source.close()
     total = write_bed_file(outputPath, chroms, {c: t for c, (_, t) in tables.items()}, minAnchor, minIntron, maxIntron,
                            log=lambda chrom, n: log("%s: %d reads, %d junctions" % (chrom, tables[chrom][0], n)))
     log("Junctions written:\t%d" % total)

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SPLISER_HIP_LIB") or os.path.join(HERE, "libspliser_h
 CSRC = os.path.join(HERE, "csrc")
 
 STRANDED_CODE = {None: 0, False: 0, "": 0, "fr": 1, "rf": 2}
+COORD_MAX = 2147483581   # csrc/spl_pack.h's SPL_COORD_MAX: read ends and site positions stay at or below it (``shard.COORD_MAX`` is this)
 STRAND_FROM_XS = 3   # spl_junctions' fourth mode: a junction's strand is its read's strand byte (the aligner's XS:A tag)
 
 
@@ -115,7 +116,7 @@ def _arr(a, dt):
 
 def _to_i32(a, what):
     a = np.asarray(a)
-    if a.size and (a.max() > 2147483581 or a.min() < -2147483648):
+    if a.size and (a.max() > COORD_MAX or a.min() < -2147483648):
         raise SpliserNativeError(-6, "%s exceeds the int32 shard coordinate space; split the shard" % what)
     return _arr(a, np.int32)
 

@@ -13,6 +13,7 @@ Deliberate deviations from the reference, all on the failure side (SURVEY.md sec
     AttributeError at :283.
 """
 import collections
+import contextlib
 import gzip
 import os
 import sys
@@ -203,6 +204,56 @@ def log_any_order(source, log):
         n, on_gpu = source.any_order_sorted()
         if n:
             log("  (the alignment file is not in coordinate order: %d reads sorted %s)" % (n, "on the GPU" if on_gpu else "on host threads"))
+
+
+# ---- the frame of a command around its decode: what every command says and does alike ------------------------------------------
+def logger(log):
+    """A command's ``log``: the caller's, or a print that is flushed line by line."""
+    return log or _log
+
+
+def chroms_of(source, qChrom):
+    """The references of the source a command visits, in header order: all, or the one ``-c`` names."""
+    return [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+
+
+def stranded_code(command, isStranded, strandedType):
+    """-> 0, 1 (fr) or 2 (rf) of ``native.STRANDED_CODE`` for a command that takes no ``auto``."""
+    code = native.STRANDED_CODE.get(strandedType, 0) if isStranded else 0
+    if isStranded and not code:
+        raise ValueError("%s: --isStranded needs -s fr or -s rf (the `strandedness` command tells which)" % command)
+    return code
+
+
+def one_device(devices, log, text):
+    """A command (or switch) that has no shares: -> the first device alone, said when several were given."""
+    devices = tuple(devices)
+    if len(devices) > 1:
+        log("  (%s on device %d alone, not in shares over %d devices)" % (text, devices[0], len(devices)))
+    return devices[:1]
+
+
+@contextlib.contextmanager
+def closing(source):
+    """An alignment source for the length of a ``with``: closed on the way out, whatever happened (the Python reader's has nothing to close)."""
+    try:
+        yield source
+    finally:
+        if hasattr(source, "close"):
+            source.close()
+
+
+def decoding(path, devices, gpuDecode=None, threads=0, options=DecodeOptions(), log=None):
+    """``open_and_decode`` for the length of a ``with``."""
+    return closing(open_and_decode(path, tuple(devices), gpuDecode, threads, options, log=log))
+
+
+def wait_decoded(source, anyOrder, log):
+    """Waits for the end of the decode (every reference is complete at the end of the file, whatever its order), then ``--anyOrder``'s line."""
+    if isinstance(source, native.BamFile):
+        source.wait_all()
+    if anyOrder:
+        log_any_order(source, log)
 
 
 class _Replan(Exception):
@@ -763,7 +814,7 @@ def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType,
         raise ValueError("strandedType must be 'fr' or 'rf' for a stranded analysis")
     if strandFromXS:
         stranded = native.STRAND_FROM_XS
-    chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+    chroms = chroms_of(source, qChrom)
     tally = [0, 0, 0] if strandFromXS else None
     got = jn.tables_of_source(source, devices, chroms, stranded, *knobs, tally=tally)
     if isinstance(source, native.BamFile) and not source.wait_all():     # (with -c too: an unsorted file's reference may be incomplete)

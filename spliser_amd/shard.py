@@ -17,7 +17,7 @@ import numpy as np
 
 from . import native
 
-COORD_MAX = 2147483581
+COORD_MAX = native.COORD_MAX
 GAP = 1024
 
 

@@ -12,11 +12,11 @@ The decision is a stated policy, not a measurement, in integers: per source (tag
 verdict of the sources that are not ``none``.  Parity with RSeQC's ``infer_experiment.py`` is unpinned (it is not on the build
 machine): the yardstick is this statement of the rule.
 """
-import sys
+import threading
 
 import numpy as np
 
-from . import native, process as _process
+from . import native, process as _process, readsets, shard
 
 MIN_EVIDENCE = 1000
 SOURCES = (("tags", 2), ("annotation", 8))      # name, first counter
@@ -56,7 +56,7 @@ def cover_map(left, right, strand):
     change = np.ones(points.shape[0], bool)
     change[1:] = code[1:] != code[:-1]
     change[0] = code[0] != 0
-    if points[change].shape[0] and points[change].max() > 2147483581:
+    if points[change].shape[0] and points[change].max() > shard.COORD_MAX:
         raise native.SpliserNativeError(-6, "a gene ends beyond the int32 coordinate space")
     return points[change].astype(np.int32), code[change]
 
@@ -74,20 +74,15 @@ def covers_of(bins, chroms):
 
 def tally_of_source(source, devices, chroms, covers=None, spliced=None):
     """``spl_strand_tally`` over every chromosome of ``chroms``, from an alignment source whose decode has been started with
-    ``aux_strand`` (``process.open_and_decode``) -> int64[14], the sums.  On the plan of ``junctions.tables_of_source``: a file
-    decoded on the device is tallied per chromosome where it lies (the sets stay fused); after a decode in shares every device
-    tallies its piece and the host adds the 14 numbers; host-decoded reads and SAM text go up as five arrays
-    (``upload_soa(..., with_strand=True)``), a fused set of their own.  ``covers``: {chrom: (start, code)} (``covers_of``) or None.
+    ``aux_strand`` (``process.open_and_decode``) -> int64[14], the sums.  On the plan of ``readsets.over_fused_sets``: the tally adds
+    over reads, so after a decode in shares every device tallies its piece and the host adds the 14 numbers; reads on the host go
+    up with their strand bytes.  ``covers``: {chrom: (start, code)} (``covers_of``) or None.
     ``spliced``: a list whose entry 0 gets the junction-carrying reads of the sets WITHOUT any tag evidence added (what the hint
     about the aligner's options needs)."""
-    import threading
     if not getattr(source, "aux_strand", False):
         raise ValueError("strandedness: the alignment source was opened without aux_strand")
     covers = covers or {}
-    is_bam = isinstance(source, native.BamFile)
-    total, errors, lock = np.zeros(14, np.int64), [], threading.Lock()
-    on_device = is_bam and source.join_decoders()      # (however the device decode was started; False: the host threads have the file)
-    shares = getattr(source, "shares", None) if on_device else None
+    total, lock = np.zeros(14, np.int64), threading.Lock()
 
     def tally(dr, chrom):
         t = dr.strand_tally(covers.get(chrom))
@@ -99,46 +94,7 @@ def tally_of_source(source, devices, chroms, covers=None, spliced=None):
             if spliced is not None:
                 spliced[0] += n_spliced
 
-    def run(device, jobs):
-        try:
-            with native.Context(device) as ctx:
-                for chrom, add in jobs:
-                    if add is None:
-                        rs = source.reads(chrom)
-                        if rs is None or not rs.n:
-                            continue
-                        if rs.xs is None:
-                            raise native.SpliserNativeError(-1, "%s: reads without strand bytes" % chrom)
-                        with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, xs=rs.xs)], [getattr(rs, "max_end", None)], with_strand=True) as soa:
-                            with ctx.begin_reads() as dr:
-                                dr.add_soa(soa, 0)
-                                dr.finish()
-                                tally(dr, chrom)
-                    else:
-                        with ctx.begin_reads() as dr:
-                            if add(dr):
-                                dr.finish()
-                                tally(dr, chrom)
-        except Exception as exc:
-            with lock:
-                errors.append(exc)
-
-    if shares:
-        plans = []
-        for k, (device, names) in enumerate(shares):
-            held = [c for c in chroms if c in names and source.share_ref(k, c)[0] > 0]
-            plans.append((device, [(c, (lambda dr, k=k, c=c: dr.add_bam_share(source, k, c))) for c in held]))
-    elif on_device:
-        plans = [(devices[0], [(c, (lambda dr, c=c: dr.add_bam(source, c))) for c in chroms])]
-    else:
-        plans = [(devices[0], [(c, None) for c in chroms])]
-    workers = [threading.Thread(target=run, args=plan) for plan in plans if plan[1]]
-    for w in workers:
-        w.start()
-    for w in workers:
-        w.join()
-    if errors:
-        raise errors[0]
+    readsets.over_fused_sets(source, devices, chroms, tally, with_strand=True)
     return total
 
 
@@ -195,7 +151,7 @@ def infer(source, devices, bins=None, qChrom="All", minEvidence=MIN_EVIDENCE, lo
     (``qChrom``: that one) with the cover maps of ``bins`` when there are any -> (verdict, report text, tally).  Logs the report."""
     if isinstance(source, native.BamFile):
         source.wait_all()      # (every reference is complete at the end of the file, whatever its order)
-    chroms = [c for c in source.ref_names if qChrom == c or qChrom == "All"]
+    chroms = _process.chroms_of(source, qChrom)
     covers = covers_of(bins, chroms) if bins is not None else {}
     spliced = [0]
     tally = tally_of_source(source, tuple(devices), chroms, covers, spliced=spliced)
@@ -229,20 +185,16 @@ def strandedness(inBAM, annotationFile=None, aType="gene", qChrom="All", outputP
     """The ``strandedness`` command: one decode with ``aux_strand``, the tally, the report -- logged, and written to ``outputPath``
     when given.  -> (verdict, tally).  Whatever the verdict, it is a result, not an error."""
     from . import sites
-    log = log or (lambda msg: (print(msg), sys.stdout.flush()))
+    log = _process.logger(log)
     if int(minEvidence) < 0:
         raise ValueError("minEvidence must not be negative")
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), aux_strand=True, any_order=bool(anyOrder))
-    source = _process.open_and_decode(inBAM, tuple(devices), gpuDecode, threads, options, log=log)
-    try:
+    with _process.decoding(inBAM, devices, gpuDecode, threads, options, log=log) as source:
         bins = sites.GeneBins.from_annotation(annotationFile, aType, "All", log=log) if annotationFile is not None else None
         if anyOrder:
             _process.log_any_order(source, log)
         verdict, text, tally = infer(source, devices, bins, qChrom, int(minEvidence), log)
         _process.log_filter(source, options.read_filter, log)
-    finally:
-        if hasattr(source, "close"):
-            source.close()
     if outputPath is not None:
         with open(outputPath, "w") as fh:
             fh.write(text)
