@@ -841,6 +841,53 @@ int spl_sites_index_info(const spl_dsites *ds, int32_t *dbase, uint32_t *n_dbuck
 int spl_sites_index_download(spl_ctx *ctx, const spl_dsites *ds, uint32_t first_bucket, uint32_t count,
                              uint32_t *out /* 3 words a bucket: first, occ, rival */);
 
+/* ---- junction strand from the genome's splice motifs (what the pipeline otherwise needs the aligner's XS:A tag for) ----------
+ * For a file whose aligner was not asked for the tag (STAR writes it only with --outSAMstrandField intronMotif; BWA, minimap2 and
+ * GSNAP never do) the strand of a junction is in the genome: the intron's first and last two bases.  The reference has no
+ * counterpart: it reads the strand a BED line says.  The rule (csrc/spl_motif_rule.h; the yardstick is tests/motifcases.py):
+ *   base codes   four bits: A = 1, C = 2, G = 4, T = 8 in either letter case, every other byte 0.
+ *   FASTA        a line that begins with '>' opens a sequence, its name the bytes behind '>' up to the first space, tab, CR or the
+ *                line's end; every other line is a sequence line, each byte of it a base except one CR directly in front of the
+ *                newline.  Any line lengths, empty lines skipped, a last line without a newline taken, a sequence of no bases
+ *                legal.  SPL_ERR_FORMAT, the message naming the 1-based line ("line N"): bytes before the first '>', an empty name,
+ *                a repeated name, no sequence; and a file that begins 1f 8b (pass the uncompressed FASTA the aligner's index was
+ *                built from).  Plain text only, no .fai.
+ *   motif code   of a junction (left, right) in spl_junctions' site convention: donor pair = bases left + 1, left + 2, acceptor
+ *                pair = bases right - 1, right; 1 GT..AG, 2 CT..AC, 3 GC..AG, 4 CT..GC, 5 AT..AC, 6 GT..AT (column 5 of STAR's
+ *                SJ.out.tab), 0 everything else: a pair with a 0 base, right - left < 4, a pair outside [1, length].  Odd codes are
+ *                '+', even ones that are not 0 are '-'.
+ *   read strand  over ALL N ops of the read (the walk of csrc/spl_junction_walk.h with the knobs 0, 0, 0): '+' with a '+' code and
+ *                no '-' code, '-' for the mirror case, 0 otherwise; 0 for a read that is unmapped (0x4), has POS < 1, no CIGAR or
+ *                no N op.  STAR's intronMotif, except that reads of inconsistent motifs stay and count under '?'.
+ * spl_genome_open maps the file and sends it up through the staging ring in windows of whole lines of about window_bytes (0 = the
+ * SAM text's SPL_SAM_WINDOW_BYTES, 256 MiB; a test cuts them at 64 KiB), the window before being packed meanwhile: only the file
+ * crosses the link.  STORED FORM: two codes a byte, base p (1-based) of a sequence in nibble p - 1 from the sequence's first byte,
+ * the low nibble first; every sequence starts on a 16-byte boundary.  spl_genome_name: the pointer is good while the handle is.
+ * spl_genome_bases: bases first + 1 .. first + n of sequence i, a code a byte (test hook).  spl_genome_stats: the file's bytes, the
+ * store's bytes, the device time of the copies and of the kernels.  spl_genome_free: while nothing uses the handle.
+ * spl_genome_pack_host: the same rule on the host, no GPU -- the three counts are always written; name_off[n_seq + 1] / names (end
+ * to end) / length[n_seq] / codes (a code a byte, end to end) where given and cap_seq, cap_names, cap_codes are enough.
+ * spl_reads_motif_strand OVERWRITES the strand byte of every read of a FUSED set whose arrays have the bytes
+ * (spl_reads_has_strand; anything else is SPL_ERR_ARG, as spl_junctions' stranded = 3) by the rule, against sequence `seq`, the
+ * reads' POS moved by their segment's shift; the set stays fused.  tally_out[12]: junction walks by code 0 .. 6, then reads given
+ * '+', '-', conflicting, spliced without a canonical junction, with a pair outside the sequence.  The call synchronises.
+ * spl_motif_read_strand_host: the rule over host arrays and a sequence with a code a byte (test hook; offsets beyond n_ops_total
+ * are an empty CIGAR).  spl_junction_motifs: code_out[i] for row i of a junction table; _host the same without a GPU. */
+typedef struct spl_genome spl_genome;
+int spl_genome_open(spl_ctx *ctx, const char *fasta_path, int64_t window_bytes, spl_genome **out);
+int spl_genome_n(const spl_genome *g);
+int spl_genome_name(const spl_genome *g, int i, const char **name_out, int64_t *length_out);
+int spl_genome_bases(const spl_ctx *ctx, const spl_genome *g, int i, int64_t first, int64_t n, uint8_t *codes_out);
+int spl_genome_stats(const spl_genome *g, int64_t *text_bytes, int64_t *device_bytes, float *upload_ms, float *pack_ms);
+void spl_genome_free(spl_ctx *ctx, spl_genome *g);
+int spl_genome_pack_host(const uint8_t *text, int64_t len, int64_t *n_seq_out, int64_t *name_bytes_out, int64_t *n_codes_out, int64_t cap_seq,
+                         int64_t cap_names, int64_t cap_codes, int64_t *name_off, uint8_t *names, int64_t *length, uint8_t *codes);
+int spl_reads_motif_strand(spl_ctx *ctx, spl_dreads *dr, const spl_genome *g, int seq, int64_t *tally_out);
+int spl_motif_read_strand_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar,
+                               int64_t n_ops_total, int32_t shift, const uint8_t *codes, int64_t length, uint8_t *strand_out, int64_t *tally_out);
+int spl_junction_motifs(spl_ctx *ctx, const spl_genome *g, int seq, int64_t n, const int32_t *left, const int32_t *right, uint8_t *code_out);
+int spl_junction_motifs_host(const uint8_t *codes, int64_t length, int64_t n, const int32_t *left, const int32_t *right, uint8_t *code_out);
+
 /* ---- host helper of Step 1 ---------------------------------------------------------------------------
  * binary_gene_search (SpliSER_v0_1_8.py:118-173) for a batch of query positions against one chromosome's gene list
  * (in list order), probe for probe like the reference.  Strand bytes are '+', '-' or 0 for anything else;

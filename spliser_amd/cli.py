@@ -8,7 +8,10 @@ takes the junctions from the BAM itself, in the same pass, and ``--minAnchor`` /
 reads support a junction (regtools' -a / -m / -M; defaults 8 / 70 / 500000) -- with ``-b`` they are an error, the file has
 its own.  ``--strandFromXS`` (``process`` without ``-b``, ``junctions``; regtools' ``-s XS``) takes a junction's strand from the
 XS:A tag the aligner wrote on its reads, for an unstranded library whose junctions are otherwise all ``?``; an alternative to
-``--isStranded``, and an error with ``-b``.  ``--minMapQ`` / ``--requireFlags`` / ``--excludeFlags`` (``process``, ``junctions``, ``combine``, ``combineShallow``) are
+``--isStranded``, and an error with ``-b``.  ``--genome FASTA`` (the same two commands) sends the genome the reads were aligned to
+to the GPU; ``--strandFromMotif`` then takes the strand from the splice motifs of each read's junctions (GT..AG and its kin), for a
+file whose aligner wrote no XS:A -- an alternative to ``--isStranded``, ``--strandFromXS`` and ``-s auto`` --, and ``--canonicalOnly``
+drops the junctions whose motif is none of the six.  ``--minMapQ`` / ``--requireFlags`` / ``--excludeFlags`` (``process``, ``junctions``, ``combine``, ``combineShallow``) are
 samtools view's -q / -f / -F applied while the BAM is decoded: the run's results are those of the pre-filtered file.  Extra sub-command: ``junctions`` writes that BED12 junction file on its own, for ``process -b`` here or for the
 reference (which leaves it to regtools); ``process`` without ``-b`` writes what ``junctions`` + ``process -b`` write.
 ``process --flagstat`` also writes ``<outputPath>.flagstat.txt``, samtools flagstat's sixteen lines counted by the decode the
@@ -77,6 +80,16 @@ def build_parser(fragment_switches=False):
     p.add_argument("--strandFromXS", dest="strandFromXS", default=False, action="store_true",
                    help="(this build only, without -b; changes results) unstranded library: a junction's strand is the XS:A tag its reads "
                         "carry (regtools -s XS) instead of '?'; not together with --isStranded")
+    p.add_argument("--genome", dest="genome", default=None, metavar="FASTA",
+                   help="(this build only, without -b) the uncompressed FASTA the aligner's index was built from: it goes to the GPU as base codes, for "
+                        "--strandFromMotif and --canonicalOnly")
+    p.add_argument("--strandFromMotif", dest="strandFromMotif", default=False, action="store_true",
+                   help="(needs --genome; changes results) a junction's strand from the splice motifs of its reads' junctions in the genome "
+                        "(GT..AG and its kin), as STAR --outSAMstrandField intronMotif would have tagged them, for a file without XS:A tags; "
+                        "an alternative to --isStranded, --strandFromXS and -s auto")
+    p.add_argument("--canonicalOnly", dest="canonicalOnly", default=False, action="store_true",
+                   help="(needs --genome; changes results) junctions whose motif is none of GT..AG, GC..AG, AT..AC or their reverse complements "
+                        "are dropped")
     p.add_argument("-o", "--outputPath", dest="outputPath", required=True,
                    help="Absolute path, including file prefix where the .SpliSER.tsv file is written")
     p.add_argument("-A", "--annotationFile", dest="annotationFile", required=False,
@@ -162,6 +175,16 @@ def build_parser(fragment_switches=False):
     j.add_argument("--strandFromXS", dest="strandFromXS", default=False, action="store_true",
                    help="unstranded library: the strand column from the reads' XS:A tag (regtools -s XS) instead of '?'; not together "
                         "with --isStranded")
+    j.add_argument("--genome", dest="genome", default=None, metavar="FASTA",
+                   help="(this build only) the uncompressed FASTA the aligner's index was built from: it goes to the GPU as base codes, for "
+                        "--strandFromMotif and --canonicalOnly")
+    j.add_argument("--strandFromMotif", dest="strandFromMotif", default=False, action="store_true",
+                   help="(needs --genome; changes results) a junction's strand from the splice motifs of its reads' junctions in the genome "
+                        "(GT..AG and its kin), as STAR --outSAMstrandField intronMotif would have tagged them, for a file without XS:A tags; "
+                        "an alternative to --isStranded, --strandFromXS and -s auto")
+    j.add_argument("--canonicalOnly", dest="canonicalOnly", default=False, action="store_true",
+                   help="(needs --genome; changes results) junctions whose motif is none of GT..AG, GC..AG, AT..AC or their reverse complements "
+                        "are dropped")
     j.add_argument("-a", "--minAnchor", dest="minAnchor", type=int, default=8, help="both anchors of a read must be this long (regtools -a)")
     j.add_argument("-m", "--minIntron", dest="minIntron", type=int, default=70, help="regtools -m")
     j.add_argument("-M", "--maxIntron", dest="maxIntron", type=int, default=500000, help="regtools -M; 0 = no limit")
@@ -341,6 +364,23 @@ def main(argv=None):
         parser.error("intronretention: --trimPercent must be in 0..49")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("strandedType") == "auto":
         parser.error("-s auto and --strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
+    if command in ("process", "junctions"):
+        for flag in ("strandFromMotif", "canonicalOnly"):
+            if kwargs.get(flag) and kwargs.get("genome") is None:
+                parser.error("--%s needs --genome: the FASTA the reads were aligned to" % flag)
+        for other, name in (("isStranded", "--isStranded"), ("strandFromXS", "--strandFromXS")):
+            if kwargs.get("strandFromMotif") and kwargs.get(other):
+                parser.error("--strandFromMotif and %s are alternatives: one source for a junction's strand" % name)
+        if kwargs.get("strandFromMotif") and kwargs.get("strandedType") == "auto":
+            parser.error("--strandFromMotif and -s auto are alternatives: one source for a junction's strand")
+        if kwargs.get("genome") is not None:
+            try:
+                with open(kwargs["genome"], "rb") as fh:
+                    magic = fh.read(2)
+            except OSError as exc:
+                parser.error("--genome %s: %s" % (kwargs["genome"], exc.strerror))
+            if magic == b"\x1f\x8b":
+                parser.error("--genome %s is compressed: pass the uncompressed FASTA the aligner's index was built from" % kwargs["genome"])
     if command in ("process", "junctions", "strandedness") and kwargs.get("minEvidence") is not None and kwargs["minEvidence"] < 0:
         parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
@@ -359,6 +399,7 @@ def main(argv=None):
                 given.append("--keepJunctions")
             if kwargs.get("strandFromXS"):
                 given.append("--strandFromXS")
+            given.extend(f for f, d in (("--genome", "genome"), ("--strandFromMotif", "strandFromMotif"), ("--canonicalOnly", "canonicalOnly")) if kwargs.get(d))
             if given:
                 parser.error("%s: only without --bedFile (a junction file has its own junctions)" % ", ".join(given))
         else:

@@ -3,11 +3,14 @@
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
 
+#include <fcntl.h>
 #include <sys/mman.h>
+#include <sys/stat.h>
 
 #include <algorithm>
 #include <atomic>
 #include <unistd.h>
+#include <cerrno>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -19,6 +22,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/spliser.h"
@@ -52,6 +56,9 @@
 #include "spl_intron.h"
 #include "spl_intron_rule.h"
 #include "spl_simple_span.h"
+#include "spl_genome.h"
+#include "spl_motif.h"
+#include "spl_motif_rule.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -5358,4 +5365,458 @@ extern "C" int spl_sse(spl_ctx *c, const spl_sites *s, const uint32_t *beta1, co
     if (rc == SPL_OK) rc = spl_sse_download(c, ds, b2s, b2c, b2w, sse);
     spl_sites_free(c, ds);
     return rc;
+}
+
+// ---- the genome on the device (spl_genome.hip; the rule is spl_motif_rule.h) ----------------------------------------------------
+// A FASTA's sequences as base codes, two a byte (spl_genome.h: the stored form).  The file is mapped and goes up through the
+// staging ring in windows of whole lines -- cut by the host at the last newline a window's bytes hold, as the plain SAM text's
+// are (a longer line gets a window of its own) --, window w + 1 is sent before window w's launches are queued, so the copy engine
+// works while the kernels do.  Per window: spl_sam.hip's line starts, classify, two prefix sums, headers; the headers come down (a
+// few dozen for a genome), the host closes the sequences they end, checks the names and gives every piece of a sequence its
+// place; the pack kernel stores.  A sequence that spans windows is joined in the one 16-byte word two windows share (spl_genome.h).
+struct spl_genome {
+    int device = 0;
+    void *store = nullptr;
+    uint64_t cap = 0, used = 0;
+    std::vector<std::string> names;
+    std::vector<int64_t> length;
+    std::vector<uint64_t> dst;
+    int64_t text_bytes = 0;
+    float upload_ms = 0, pack_ms = 0;
+};
+
+namespace {
+const char *fasta_reason(int r)
+{
+    switch (r) {
+    case SPL_FASTA_BEFORE_HEADER: return "bytes before the first '>'";
+    case SPL_FASTA_EMPTY_NAME: return "a sequence without a name";
+    case SPL_FASTA_REPEATED_NAME: return "a sequence name for the second time";
+    case SPL_FASTA_NO_SEQUENCE: return "the file has no sequence";
+    case SPL_FASTA_GZIP: return "compressed data (1f 8b): pass the uncompressed FASTA the aligner's index was built from";
+    default: return "not FASTA";
+    }
+}
+
+struct GenomeLoad {
+    spl_ctx *const c;
+    spl_genome *const g;
+    const char *const path;
+    const uint8_t *image = nullptr;
+    size_t fsize = 0;
+    int fd = -1;
+    struct Window { uint64_t lo, hi; };
+    std::vector<Window> windows;
+    DevBuf d_text[2], d_chunks, d_lines, d_nb, d_hdr, d_headers, d_segs, d_counts, d_work, d_store;
+    size_t cap_chunks = 0, cap_lines = 0, cap_work = 0, cap_headers = 0, cap_segs = 0;
+    hipEvent_t up[2] = {nullptr, nullptr};
+    std::vector<hipEvent_t> ev; // per window: copy begin, copy end, kernels begin, kernels end
+    // the sequence that is open: its bases so far, where it lies
+    bool seq_open = false;
+    uint64_t cur_len = 0, cur_dst = 0, lines_before = 0;
+    uint64_t stored = 0; // the store's bytes that launches have written: where the window before ended (at most g->cap; g->used runs ahead of it inside a window)
+    std::unordered_set<std::string> seen;
+    std::vector<spl_genome_header> headers;
+    std::vector<spl_genome_segment> segs;
+
+    GenomeLoad(spl_ctx *ctx, spl_genome *gen, const char *p) : c(ctx), g(gen), path(p) {}
+    ~GenomeLoad()
+    {
+        if (c->copy) (void)hipStreamSynchronize(c->copy);
+        (void)hipStreamSynchronize(c->stream);
+        c->stages_idle();
+        for (hipEvent_t e : up) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (image) munmap((void *)image, fsize);
+        if (fd >= 0) close(fd);
+    }
+
+    int bad(int reason, uint64_t line) { return spl_set_error(SPL_ERR_FORMAT, "%s: line %llu: %s", path, (unsigned long long)line, fasta_reason(reason)); }
+
+    int map()
+    {
+        fd = ::open(path, O_RDONLY);
+        if (fd < 0) return spl_set_error(SPL_ERR_IO, "%s: %s", path, strerror(errno));
+        struct stat sb;
+        if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return spl_set_error(SPL_ERR_IO, "%s: not a regular file", path);
+        fsize = (size_t)sb.st_size;
+        if (fsize == 0) return bad(SPL_FASTA_NO_SEQUENCE, 1);
+        void *m = mmap(nullptr, fsize, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m == MAP_FAILED) return spl_set_error(SPL_ERR_IO, "%s: mmap: %s", path, strerror(errno));
+        image = (const uint8_t *)m;
+        if (fsize >= 2 && image[0] == 0x1f && image[1] == 0x8b) return bad(SPL_FASTA_GZIP, 1);
+        return SPL_OK;
+    }
+
+    int plan(size_t win_bytes)
+    {
+        for (uint64_t lo = 0; lo < fsize;) {
+            uint64_t hi = std::min<uint64_t>(fsize, lo + win_bytes);
+            if (hi < fsize) {
+                const void *nl = memrchr(image + lo, '\n', (size_t)(hi - lo));
+                if (!nl) nl = memchr(image + hi, '\n', fsize - hi); // (a line longer than a window: a window of its own)
+                hi = nl ? (uint64_t)((const uint8_t *)nl - image) + 1 : fsize;
+            }
+            if (hi - lo > 0xffffff00ull) return spl_set_error(SPL_ERR_FORMAT, "%s: a line of more than 4 GiB", path);
+            windows.push_back(Window{lo, hi});
+            lo = hi;
+        }
+        return SPL_OK;
+    }
+
+    hipError_t send(size_t w)
+    {
+        const uint64_t from = windows[w].lo & ~(uint64_t)15, bytes = windows[w].hi - from;
+        hipError_t q = hipEventRecord(ev[4 * w], c->copy);
+        if (q == hipSuccess) q = ring_send(c, d_text[w % 2].as<char>(), bytes, FileFill{image, fd, from});
+        if (q == hipSuccess) q = hipEventRecord(ev[4 * w + 1], c->copy);
+        if (q == hipSuccess) q = hipEventRecord(up[w % 2], c->copy);
+        return q;
+    }
+
+    bool name_seen(const std::string &s)
+    {
+        return !seen.insert(s).second;
+    }
+
+    int room(uint64_t need)
+    {
+        if (need <= g->cap) return SPL_OK;
+        const uint64_t want = align_up((size_t)std::max<uint64_t>(need + need / 4, 4096), 256);
+        DevBuf fresh;
+        HIP_TRY(fresh.get((size_t)want, c->stream));
+        // (what the windows before have stored, no more: g->used is already this window's, beyond the old store's end where it grows)
+        if (d_store.p && stored) HIP_TRY(hipMemcpyAsync(fresh.p, d_store.p, (size_t)std::min<uint64_t>(stored, g->cap), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        d_store.release();
+        d_store.p = fresh.p; fresh.p = nullptr;
+        g->cap = want;
+        return SPL_OK;
+    }
+
+    int window(size_t w)
+    {
+        hipStream_t st = c->stream;
+        const Window win = windows[w];
+        const uint64_t base = win.lo & ~(uint64_t)15;
+        const uint8_t *const text = d_text[w % 2].as<uint8_t>() - base;
+        const uint64_t last_end = image[win.hi - 1] == '\n' ? win.hi - 1 : win.hi;
+        HIP_TRY(hipStreamWaitEvent(st, up[w % 2], 0));
+        HIP_TRY(hipEventRecord(ev[4 * w + 2], st));
+        auto work_for = [&](uint64_t n) -> hipError_t {
+            const size_t need = spl_dev_sort_work_bytes(n);
+            if (need <= cap_work) return hipSuccess;
+            d_work.release(); cap_work = 0;
+            const hipError_t q = d_work.get(need, st);
+            if (q == hipSuccess) cap_work = need;
+            return q;
+        };
+        // ---- line starts
+        const uint32_t n_chunks = spl_sam_chunks(win.lo, win.hi);
+        if (n_chunks > cap_chunks) { d_chunks.release(); cap_chunks = 0; HIP_TRY(d_chunks.get(4 * (size_t)n_chunks, st)); cap_chunks = n_chunks; }
+        HIP_TRY(work_for(n_chunks));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_line_count(text, win.lo, win.hi, d_chunks.as<uint32_t>(), st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_chunks.as<uint32_t>(), n_chunks, d_work.p, st));
+        uint32_t n_lines = 0;
+        HIP_TRY(hipMemcpyAsync(&n_lines, d_chunks.as<uint32_t>() + (n_chunks - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_lines > cap_lines) {
+            d_lines.release(); d_nb.release(); d_hdr.release(); cap_lines = 0;
+            const size_t n = (size_t)n_lines + (size_t)n_lines / 8;
+            HIP_TRY(d_lines.get(4 * n, st)); HIP_TRY(d_nb.get(4 * n, st)); HIP_TRY(d_hdr.get(4 * n, st));
+            cap_lines = n;
+        }
+        HIP_TRY(work_for(n_lines));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_line_fill(text, win.lo, win.hi, d_chunks.as<uint32_t>(), d_lines.as<uint32_t>(), st));
+        // ---- what every line is, and the sums
+        static const unsigned long long none = ~0ull;
+        HIP_TRY(hipMemcpyAsync(d_counts.p, &none, 8, hipMemcpyHostToDevice, st));
+        HIP_TRY((hipError_t)spl_dev_launch_genome_classify(text, base, d_lines.as<uint32_t>(), n_lines, last_end, win.hi, d_nb.as<uint32_t>(), d_hdr.as<uint32_t>(),
+                                                           d_counts.as<spl_genome_counts>(), st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_nb.as<uint32_t>(), n_lines, d_work.p, st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_hdr.as<uint32_t>(), n_lines, d_work.p, st));
+        uint32_t n_bases = 0, n_hdr = 0;
+        HIP_TRY(hipMemcpyAsync(&n_bases, d_nb.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&n_hdr, d_hdr.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_hdr > cap_headers) { d_headers.release(); cap_headers = 0; HIP_TRY(d_headers.get(sizeof(spl_genome_header) * (size_t)n_hdr, st)); cap_headers = n_hdr; }
+        HIP_TRY((hipError_t)spl_dev_launch_genome_headers(text, base, d_lines.as<uint32_t>(), n_lines, last_end, win.hi, d_nb.as<uint32_t>(), d_hdr.as<uint32_t>(), seq_open ? 1 : 0,
+                                                          d_headers.as<spl_genome_header>(), d_counts.as<spl_genome_counts>(), st));
+        headers.resize(n_hdr);
+        spl_genome_counts counts;
+        if (n_hdr) HIP_TRY(hipMemcpyAsync(headers.data(), d_headers.p, sizeof(spl_genome_header) * (size_t)n_hdr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        // ---- the sequences the headers end and begin; every piece of a sequence in this window is a segment
+        const uint64_t bad_line = counts.first_bad == none ? ~0ull : (counts.first_bad >> 8);
+        segs.clear();
+        uint32_t wb = 0;
+        auto piece = [&](uint32_t upto) {
+            const uint32_t n = upto - wb;
+            if (seq_open && n) { segs.push_back(spl_genome_segment{cur_dst, cur_len, wb, n, 0u, 0u}); cur_len += n; g->length.back() = (int64_t)cur_len; }
+            wb = upto;
+        };
+        for (const spl_genome_header &h : headers) {
+            if ((uint64_t)h.line > bad_line) break; // (the first line the rule declines is the one that is reported)
+            piece(h.bases_before);
+            const std::string name((const char *)image + h.name_at, h.name_len);
+            if (h.name_len && name_seen(name)) return bad(SPL_FASTA_REPEATED_NAME, lines_before + h.line + 1);
+            if (seq_open) g->used = cur_dst + 16u * ((cur_len + 31u) / 32u);
+            seq_open = true;
+            cur_len = 0;
+            cur_dst = g->used;
+            g->names.push_back(name); g->length.push_back(0); g->dst.push_back(cur_dst);
+        }
+        if (bad_line != ~0ull) return bad((int)(counts.first_bad & 0xffu), lines_before + bad_line + 1);
+        piece(n_bases);
+        uint32_t n_groups = 0;
+        for (spl_genome_segment &s : segs) { s.group_first = n_groups; n_groups += (uint32_t)((s.seq_first + s.n + 31u) / 32u - s.seq_first / 32u); }
+        const uint64_t end = seq_open ? cur_dst + 16u * ((cur_len + 31u) / 32u) : 0;
+        { const int rc = room(end); if (rc) return rc; }
+        if (!segs.empty()) {
+            if (segs.size() > cap_segs) { d_segs.release(); cap_segs = 0; HIP_TRY(d_segs.get(sizeof(spl_genome_segment) * (segs.size() + segs.size() / 8), st)); cap_segs = segs.size() + segs.size() / 8; }
+            HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), sizeof(spl_genome_segment) * segs.size(), hipMemcpyHostToDevice, st));
+            splprof::Scope prof("spl_genome_pack_kernel", st, 1.5 * (double)n_bases); // a byte read and half a byte written a base
+            HIP_TRY((hipError_t)spl_dev_launch_genome_pack(text, base, d_lines.as<uint32_t>(), n_lines, d_nb.as<uint32_t>(), d_segs.as<spl_genome_segment>(), (uint32_t)segs.size(),
+                                                           n_groups, d_store.as<uint8_t>(), g->cap, st));
+        }
+        HIP_TRY(hipEventRecord(ev[4 * w + 3], st));
+        HIP_TRY(hipStreamSynchronize(st)); // (the window's buffer is free for the window after the next; the segments' host memory too)
+        g->used = end > g->used ? end : g->used;
+        stored = g->used;
+        lines_before += n_lines;
+        return SPL_OK;
+    }
+
+    int run(int64_t window_bytes)
+    {
+        { const int rc = map(); if (rc) return rc; }
+        { const int rc = plan(window_bytes > 0 ? (size_t)std::max<int64_t>(window_bytes, 64) : spl_sam_window_bytes()); if (rc) return rc; }
+        HIP_TRY(hipSetDevice(c->device));
+        { const int rc = ensure_stage(c, 3); if (rc) return rc; }
+        for (hipEvent_t &e : up) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ev.assign(4 * windows.size(), nullptr);
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+        uint64_t widest = 0;
+        for (const Window &w : windows) widest = std::max(widest, w.hi - (w.lo & ~(uint64_t)15));
+        for (int k = 0; k < (windows.size() > 1 ? 2 : 1); ++k) HIP_TRY(d_text[k].get((size_t)widest + 16 + SPL_SAM_PAD, c->stream));
+        HIP_TRY(d_counts.get(sizeof(spl_genome_counts), c->stream));
+        { const int rc = room((uint64_t)fsize / 2 + 4096); if (rc) return rc; }
+        HIP_TRY(send(0));
+        for (size_t w = 0; w < windows.size(); ++w) {
+            if (w + 1 < windows.size()) HIP_TRY(send(w + 1)); // (its buffer is free: window w - 1 was waited for)
+            const int rc = window(w);
+            if (rc) return rc;
+        }
+        if (g->names.empty()) return bad(SPL_FASTA_NO_SEQUENCE, lines_before ? lines_before : 1);
+        for (size_t w = 0; w < windows.size(); ++w) {
+            float a = 0, b = 0;
+            HIP_TRY(hipEventElapsedTime(&a, ev[4 * w], ev[4 * w + 1]));
+            HIP_TRY(hipEventElapsedTime(&b, ev[4 * w + 2], ev[4 * w + 3]));
+            g->upload_ms += a; g->pack_ms += b;
+        }
+        g->text_bytes = (int64_t)fsize;
+        g->device = c->device;
+        g->store = d_store.p; d_store.p = nullptr; // (the handle owns it from here)
+        return SPL_OK;
+    }
+};
+} // namespace
+
+extern "C" int spl_genome_open(spl_ctx *c, const char *fasta_path, int64_t window_bytes, spl_genome **out)
+{
+    if (!c || !fasta_path || !out || window_bytes < 0) return spl_set_error(SPL_ERR_ARG, "spl_genome_open: bad argument");
+    *out = nullptr;
+    spl_genome *g = new (std::nothrow) spl_genome();
+    if (!g) return spl_set_error(SPL_ERR_NOMEM, "out of host memory");
+    int rc;
+    {
+        GenomeLoad load(c, g, fasta_path);
+        rc = load.run(window_bytes);
+    }
+    if (rc != SPL_OK) { delete g; return rc; }
+    *out = g;
+    return SPL_OK;
+}
+
+extern "C" int spl_genome_n(const spl_genome *g) { return g ? (int)g->names.size() : 0; }
+
+extern "C" int spl_genome_name(const spl_genome *g, int i, const char **name_out, int64_t *length_out)
+{
+    if (!g || i < 0 || (size_t)i >= g->names.size()) return spl_set_error(SPL_ERR_ARG, "spl_genome_name: no such sequence");
+    if (name_out) *name_out = g->names[(size_t)i].c_str();
+    if (length_out) *length_out = g->length[(size_t)i];
+    return SPL_OK;
+}
+
+extern "C" int spl_genome_bases(const spl_ctx *c, const spl_genome *g, int i, int64_t first, int64_t n, uint8_t *codes_out)
+{
+    if (!c || !g || i < 0 || (size_t)i >= g->names.size() || first < 0 || n < 0 || first + n > g->length[(size_t)i] || (n && !codes_out))
+        return spl_set_error(SPL_ERR_ARG, "spl_genome_bases: bad argument");
+    if (c->device != g->device) return spl_set_error(SPL_ERR_ARG, "spl_genome_bases: the genome lies on device %d", g->device);
+    if (!n) return SPL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t b0 = (uint64_t)first / 2, b1 = ((uint64_t)(first + n) + 1) / 2;
+    std::vector<uint8_t> bytes((size_t)(b1 - b0));
+    HIP_TRY(hipMemcpy(bytes.data(), (const uint8_t *)g->store + g->dst[(size_t)i] + b0, bytes.size(), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < n; ++k) {
+        const uint64_t p = (uint64_t)(first + k);
+        codes_out[k] = (uint8_t)(bytes[(size_t)(p / 2 - b0)] >> (4 * (p & 1u)) & 15u);
+    }
+    return SPL_OK;
+}
+
+extern "C" int spl_genome_stats(const spl_genome *g, int64_t *text_bytes, int64_t *device_bytes, float *upload_ms, float *pack_ms)
+{
+    if (!g) return spl_set_error(SPL_ERR_ARG, "spl_genome_stats: null argument");
+    if (text_bytes) *text_bytes = g->text_bytes;
+    if (device_bytes) *device_bytes = (int64_t)g->used;
+    if (upload_ms) *upload_ms = g->upload_ms;
+    if (pack_ms) *pack_ms = g->pack_ms;
+    return SPL_OK;
+}
+
+extern "C" void spl_genome_free(spl_ctx *c, spl_genome *g)
+{
+    if (!g) return;
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    (void)hipSetDevice(g->device);
+    if (c && c->stream) (void)hipStreamSynchronize(c->stream);
+    else (void)hipDeviceSynchronize(); // (no context to say which stream used it last: every stream of the device)
+    devmem::put(g->store);
+    if (have) (void)hipSetDevice(cur);
+    delete g;
+}
+
+// The same rule on the host, no GPU (test hook and yardstick): the sequences of `len` bytes of FASTA text.  The three counts are
+// always written; names (the names' bytes end to end, name_off[n_seq + 1] into them), length[n_seq] and codes (a code a byte, the
+// sequences end to end) where they are given and their room -- cap_seq, cap_names, cap_codes -- is enough, else SPL_ERR_ARG.
+extern "C" int spl_genome_pack_host(const uint8_t *text, int64_t len, int64_t *n_seq_out, int64_t *name_bytes_out, int64_t *n_codes_out, int64_t cap_seq, int64_t cap_names,
+                                    int64_t cap_codes, int64_t *name_off, uint8_t *names, int64_t *length, uint8_t *codes)
+{
+    if (len < 0 || (len && !text) || !n_seq_out || !name_bytes_out || !n_codes_out) return spl_set_error(SPL_ERR_ARG, "spl_genome_pack_host: bad argument");
+    struct Sink {
+        std::vector<std::string> names;
+        std::unordered_set<std::string> seen;
+        std::vector<int64_t> length;
+        std::vector<uint8_t> codes;
+        bool header(const uint8_t *p, uint64_t n, int64_t)
+        {
+            std::string s((const char *)p, (size_t)n);
+            if (!seen.insert(s).second) return false;
+            names.push_back(s); length.push_back(0);
+            return true;
+        }
+        void bases(const uint8_t *p, uint64_t n)
+        {
+            for (uint64_t k = 0; k < n; ++k) codes.push_back((uint8_t)splmotif::base_code(p[k]));
+            length.back() += (int64_t)n;
+        }
+    } sink;
+    int64_t bad_line = 0;
+    const int reason = splmotif::fasta_scan(text, len, sink, &bad_line);
+    if (reason != SPL_FASTA_OK) return spl_set_error(SPL_ERR_FORMAT, "FASTA text: line %lld: %s", (long long)bad_line, fasta_reason(reason));
+    size_t name_bytes = 0;
+    for (const std::string &s : sink.names) name_bytes += s.size();
+    *n_seq_out = (int64_t)sink.names.size(); *name_bytes_out = (int64_t)name_bytes; *n_codes_out = (int64_t)sink.codes.size();
+    if (!name_off && !names && !length && !codes) return SPL_OK;
+    if (cap_seq < *n_seq_out || cap_names < *name_bytes_out || cap_codes < *n_codes_out) return spl_set_error(SPL_ERR_ARG, "spl_genome_pack_host: not enough room");
+    size_t at = 0;
+    for (size_t k = 0; k < sink.names.size(); ++k) {
+        if (name_off) name_off[k] = (int64_t)at;
+        if (names) memcpy(names + at, sink.names[k].data(), sink.names[k].size());
+        if (length) length[k] = sink.length[k];
+        at += sink.names[k].size();
+    }
+    if (name_off) name_off[sink.names.size()] = (int64_t)at;
+    if (codes && !sink.codes.empty()) memcpy(codes, sink.codes.data(), sink.codes.size());
+    return SPL_OK;
+}
+
+// ---- the reads' strand bytes from the splice motifs (spl_motif.hip) --------------------------------------------------------------
+extern "C" int spl_reads_motif_strand(spl_ctx *c, spl_dreads *dr, const spl_genome *g, int seq, int64_t *tally_out)
+{
+    if (!c || !dr || !g || !tally_out) return spl_set_error(SPL_ERR_ARG, "spl_reads_motif_strand: null argument");
+    if (seq < 0 || (size_t)seq >= g->names.size()) return spl_set_error(SPL_ERR_ARG, "spl_reads_motif_strand: no such sequence");
+    if (c->device != g->device) return spl_set_error(SPL_ERR_ARG, "spl_reads_motif_strand: the genome lies on device %d", g->device);
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_reads_motif_strand: the read set is not finished (spl_reads_finish)");
+    memset(tally_out, 0, 8 * SPL_MOTIF_TALLY);
+    if (dr->segs.empty()) return SPL_OK;
+    if (const int rc = fused_refusal("spl_reads_motif_strand", dr)) return rc;
+    const spl_dreads::Group &grp = dr->groups[0];
+    if (!grp.src->xs) return spl_set_error(SPL_ERR_ARG, "spl_reads_motif_strand: the reads have no strand bytes to write (spl_bam_set_aux_strand, spl_soa_upload3)");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf d_out;
+    HIP_TRY(d_out.get(8 * SPL_MOTIF_TALLY, c->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, 8 * SPL_MOTIF_TALLY, c->stream));
+    const spl_devreads src{(const int32_t *)grp.src->pos, (const uint16_t *)grp.src->flag, (const uint32_t *)grp.src->cig_off, (const uint32_t *)grp.src->cigar};
+    const uint8_t *packed = (const uint8_t *)g->store + g->dst[(size_t)seq];
+    for (const spl_dreads::Segment &seg : dr->segs) {
+        const spl_layout_seg &ls = grp.segs[seg.group_seg];
+        if (ls.n_reads <= 0) continue;
+        splprof::Scope prof("spl_motif_strand_kernel", c->stream, 9.0 * (double)ls.n_reads + 4.0 * (double)seg.n_ops); // the offsets, the ops, the byte written
+        const int rc = spl_dev_launch_motif_strand(&src, (uint8_t *)grp.src->xs, grp.src->n_rec, grp.src->n_ops, ls.first, ls.n_reads, ls.shift, packed, g->length[(size_t)seq],
+                                                   d_out.as<unsigned long long>(), c->stream);
+        if (rc) return spl_set_error(SPL_ERR_HIP, "motif strand kernel launch: %s", hipGetErrorString((hipError_t)rc));
+    }
+    HIP_TRY(hipMemcpyAsync(tally_out, d_out.p, 8 * SPL_MOTIF_TALLY, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPL_OK;
+}
+
+namespace {
+struct HostOps {
+    const uint32_t *p;
+    uint32_t operator()(uint32_t k) const { return p[k]; }
+};
+} // namespace
+
+// The rule over host arrays and a sequence with a code a byte: no GPU involved (test hook).
+extern "C" int spl_motif_read_strand_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, int64_t n_ops_total, int32_t shift,
+                                          const uint8_t *codes, int64_t length, uint8_t *strand_out, int64_t *tally_out)
+{
+    if (n_reads < 0 || n_ops_total < 0 || length < 0 || (n_reads && (!pos || !flag || !cig_off || !strand_out)) || (n_ops_total && !cigar) || (length && !codes) || !tally_out)
+        return spl_set_error(SPL_ERR_ARG, "spl_motif_read_strand_host: bad argument");
+    memset(tally_out, 0, 8 * SPL_MOTIF_TALLY);
+    for (int64_t i = 0; i < n_reads; ++i) {
+        uint32_t c0, c1;
+        splmotif::ops_span(cig_off, i, n_ops_total, c0, c1);
+        splmotif::ReadMotifs m;
+        splmotif::read_motifs((uint32_t)flag[i], (int64_t)pos[i] + shift, HostOps{cigar + c0}, c1 - c0, splmotif::BytePairs{codes}, length, m);
+        strand_out[i] = m.strand;
+        for (int k = 0; k < 7; ++k) tally_out[k] += m.walks[k];
+        if (m.cls) tally_out[m.cls] += 1;
+        if (m.outside) tally_out[11] += 1;
+    }
+    return SPL_OK;
+}
+
+// code_out[i] = the motif code of junction (left[i], right[i]) of sequence `seq`: a lane a row.
+extern "C" int spl_junction_motifs(spl_ctx *c, const spl_genome *g, int seq, int64_t n, const int32_t *left, const int32_t *right, uint8_t *code_out)
+{
+    if (!c || !g || n < 0 || (n && (!left || !right || !code_out))) return spl_set_error(SPL_ERR_ARG, "spl_junction_motifs: bad argument");
+    if (seq < 0 || (size_t)seq >= g->names.size()) return spl_set_error(SPL_ERR_ARG, "spl_junction_motifs: no such sequence");
+    if (c->device != g->device) return spl_set_error(SPL_ERR_ARG, "spl_junction_motifs: the genome lies on device %d", g->device);
+    if (!n) return SPL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf d_l, d_r, d_c;
+    HIP_TRY(d_l.get(4 * (size_t)n, c->stream)); HIP_TRY(d_r.get(4 * (size_t)n, c->stream)); HIP_TRY(d_c.get((size_t)n, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_l.p, left, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_r.p, right, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    const int rc = spl_dev_launch_junction_motifs(d_l.as<int32_t>(), d_r.as<int32_t>(), n, (const uint8_t *)g->store + g->dst[(size_t)seq], g->length[(size_t)seq], d_c.as<uint8_t>(), c->stream);
+    if (rc) return spl_set_error(SPL_ERR_HIP, "junction motifs kernel launch: %s", hipGetErrorString((hipError_t)rc));
+    HIP_TRY(hipMemcpyAsync(code_out, d_c.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPL_OK;
+}
+
+extern "C" int spl_junction_motifs_host(const uint8_t *codes, int64_t length, int64_t n, const int32_t *left, const int32_t *right, uint8_t *code_out)
+{
+    if (length < 0 || n < 0 || (length && !codes) || (n && (!left || !right || !code_out))) return spl_set_error(SPL_ERR_ARG, "spl_junction_motifs_host: bad argument");
+    for (int64_t i = 0; i < n; ++i) {
+        bool outside = false;
+        code_out[i] = (uint8_t)splmotif::junction_code(splmotif::BytePairs{codes}, length, (int64_t)left[i], (int64_t)right[i], outside);
+    }
+    return SPL_OK;
 }

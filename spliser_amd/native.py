@@ -54,7 +54,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_set_mate_keys", "spl_bam_mate_keys", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_junctions_fragments", "spl_junction_fragment_rule_host", "spl_strand_tally", "spl_strand_rule_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_coverage_fragments", "spl_coverage_fragment_totals", "spl_intron_depth_fragments", "spl_coverage_fragment_rule_host", "spl_coverage_cursor_host", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_lanes_plan_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_junctions_fragments", "spl_junction_fragment_rule_host", "spl_strand_tally", "spl_strand_rule_host", "spl_genome_open", "spl_genome_n", "spl_genome_name", "spl_genome_bases", "spl_genome_stats", "spl_genome_free", "spl_genome_pack_host", "spl_reads_motif_strand", "spl_motif_read_strand_host", "spl_junction_motifs", "spl_junction_motifs_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_coverage_fragments", "spl_coverage_fragment_totals", "spl_intron_depth_fragments", "spl_coverage_fragment_rule_host", "spl_coverage_cursor_host", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_lanes_plan_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -86,7 +86,7 @@ def lib():
         L.spl_bam_ref_length.restype = ctypes.c_int64
         L.spl_bam_n_records.restype = ctypes.c_int64
         L.spl_bam_text_blocks.restype = ctypes.c_int64
-        for name in ("spl_destroy", "spl_sites_free", "spl_reads_free", "spl_soa_free", "spl_bam_close", "spl_text_close", "spl_combine_close", "spl_coverage_free"):
+        for name in ("spl_destroy", "spl_sites_free", "spl_reads_free", "spl_soa_free", "spl_bam_close", "spl_text_close", "spl_combine_close", "spl_coverage_free", "spl_genome_free"):
             getattr(L, name).restype = None
         for name in ("spl_combine_rows", "spl_combine_region_runs", "spl_combine_n_sites", "spl_combine_n_gap_sites", "spl_combine_skipped"):
             getattr(L, name).restype = ctypes.c_int64
@@ -504,6 +504,13 @@ class DeviceReads(object):
                    count=np.empty(n, np.uint32), anchor_left=np.empty(n, np.uint32), anchor_right=np.empty(n, np.uint32))
         _check(lib().spl_junctions_get(self.ctx._h, _ptr(out["left"]), _ptr(out["right"]), _ptr(out["strand"]), _ptr(out["count"]),
                                        _ptr(out["anchor_left"]), _ptr(out["anchor_right"])))
+        return out
+
+    def motif_strand(self, genome, seq):
+        """OVERWRITES the strand byte of every read of this (finished, fused, ``has_strand``) set by the splice motifs of sequence
+        ``seq`` (an index or a name) of ``genome`` (``spl_reads_motif_strand``) -> int64[12], ``MOTIF_TALLY``'s counters."""
+        out = np.zeros(12, np.int64)
+        _check(lib().spl_reads_motif_strand(self.ctx._h, self._h, genome._h, ctypes.c_int(genome.index(seq)), _ptr(out)))
         return out
 
     def strand_tally(self, cover=None):
@@ -1184,6 +1191,114 @@ def flagstat_add_host(flag, tid, next_tid, mapq, counters=None):
     assert counters.dtype == np.int64 and counters.shape == (16, 2) and counters.flags.c_contiguous
     _check(lib().spl_flagstat_add_host(ctypes.c_uint32(int(flag)), ctypes.c_int32(int(tid)), ctypes.c_int32(int(next_tid)), ctypes.c_uint32(int(mapq)), _ptr(counters)))
     return counters
+
+
+MOTIF_TALLY = ("walks_none", "walks_GT_AG", "walks_CT_AC", "walks_GC_AG", "walks_CT_GC", "walks_AT_AC", "walks_GT_AT",
+               "reads_plus", "reads_minus", "reads_conflicting", "reads_no_canonical", "reads_outside")
+
+
+class Genome(object):
+    """A FASTA's sequences as base codes in device memory (``spl_genome_open``): ``names``, ``lengths``; ``window_bytes``: 0 = the
+    default windows.  ``free()`` while nothing uses it.  The store belongs to the device, not to the context that loaded it:
+    ``detach()`` lets go of that context, after which every context of the device may use the handle (``junction_motifs(ctx=...)``,
+    ``DeviceReads.motif_strand``) and ``free()`` waits for the whole device instead of for one stream."""
+
+    def __init__(self, ctx, path, window_bytes=0):
+        self.ctx, self._h = ctx, ctypes.c_void_p()
+        _check(lib().spl_genome_open(ctx._h, os.fsencode(path), ctypes.c_int64(int(window_bytes)), ctypes.byref(self._h)))
+        self.names, self.lengths = [], []
+        for i in range(lib().spl_genome_n(self._h)):
+            name, length = ctypes.c_char_p(), ctypes.c_int64(0)
+            _check(lib().spl_genome_name(self._h, ctypes.c_int(i), ctypes.byref(name), ctypes.byref(length)))
+            self.names.append(name.value.decode("utf-8", "surrogateescape"))
+            self.lengths.append(length.value)
+        self._index = {n: i for i, n in enumerate(self.names)}
+
+    def index(self, seq):
+        if isinstance(seq, str):
+            if seq not in self._index:
+                raise KeyError("%s is not in the FASTA" % seq)
+            return self._index[seq]
+        return int(seq)
+
+    def __contains__(self, name):
+        return name in self._index
+
+    def length(self, seq):
+        return self.lengths[self.index(seq)]
+
+    def bases(self, seq, first=0, n=None):
+        """Test hook: bases first + 1 .. first + n of a sequence, a code a byte (``spl_genome_bases``)."""
+        i = self.index(seq)
+        n = self.lengths[i] - first if n is None else n
+        out = np.zeros(max(n, 1), np.uint8)
+        _check(lib().spl_genome_bases(self.ctx._h, self._h, ctypes.c_int(i), ctypes.c_int64(int(first)), ctypes.c_int64(int(n)), _ptr(out)))
+        return out[:n]
+
+    def stats(self):
+        """-> dict: text_bytes, device_bytes, upload_ms, pack_ms (device time of the copies / of the kernels)."""
+        t, d, u, k = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_float(0), ctypes.c_float(0)
+        _check(lib().spl_genome_stats(self._h, ctypes.byref(t), ctypes.byref(d), ctypes.byref(u), ctypes.byref(k)))
+        return dict(text_bytes=t.value, device_bytes=d.value, upload_ms=u.value, pack_ms=k.value)
+
+    def junction_motifs(self, seq, left, right, ctx=None):
+        """The motif codes of the rows (left, right) of a junction table of sequence ``seq`` (``spl_junction_motifs``) -> uint8[n].
+        ``ctx``: another context of the genome's device than the one that loaded it."""
+        left, right = _arr(left, np.int32), _arr(right, np.int32)
+        out = np.zeros(max(left.shape[0], 1), np.uint8)
+        _check(lib().spl_junction_motifs((ctx or self.ctx)._h, self._h, ctypes.c_int(self.index(seq)), ctypes.c_int64(left.shape[0]), _ptr(left), _ptr(right), _ptr(out)))
+        return out[:left.shape[0]]
+
+    def detach(self):
+        self.ctx = None
+        return self
+
+    def free(self):
+        if self._h:
+            lib().spl_genome_free(self.ctx._h if self.ctx is not None else None, self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def genome_pack_host(text):
+    """The FASTA rule on the host (``spl_genome_pack_host``): bytes -> [(name bytes, codes uint8[length])]."""
+    buf = np.frombuffer(bytes(text), np.uint8)
+    n, nb, nc = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    args = (_ptr(buf) if buf.size else None, ctypes.c_int64(buf.size), ctypes.byref(n), ctypes.byref(nb), ctypes.byref(nc))
+    _check(lib().spl_genome_pack_host(*args, ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), None, None, None, None))
+    off, names = np.zeros(n.value + 1, np.int64), np.zeros(max(nb.value, 1), np.uint8)
+    length, codes = np.zeros(max(n.value, 1), np.int64), np.zeros(max(nc.value, 1), np.uint8)
+    _check(lib().spl_genome_pack_host(*args, ctypes.c_int64(n.value), ctypes.c_int64(nb.value), ctypes.c_int64(nc.value), _ptr(off), _ptr(names), _ptr(length), _ptr(codes)))
+    out, at = [], 0
+    for k in range(n.value):
+        out.append((names[off[k]:off[k + 1]].tobytes(), codes[at:at + length[k]].copy()))
+        at += int(length[k])
+    return out
+
+
+def motif_read_strand_host(reads, codes, shift=0):
+    """The motif rule over host arrays (``spl_motif_read_strand_host``): ``reads`` with pos, flag, cig_off, cigar; ``codes``: the
+    sequence, a code a byte -> (strand uint8[n], tally int64[12])."""
+    pos, flag = _arr(reads.pos, np.int32), _arr(reads.flag, np.uint16)
+    cig_off, cigar, codes = _arr(reads.cig_off, np.uint32), _arr(reads.cigar, np.uint32), _arr(codes, np.uint8)
+    n = pos.shape[0]
+    strand, tally = np.zeros(max(n, 1), np.uint8), np.zeros(12, np.int64)
+    _check(lib().spl_motif_read_strand_host(ctypes.c_int64(n), _ptr(pos), _ptr(flag), _ptr(cig_off), _ptr(cigar) if cigar.size else None, ctypes.c_int64(cigar.shape[0]),
+                                            ctypes.c_int32(int(shift)), _ptr(codes) if codes.size else None, ctypes.c_int64(codes.shape[0]), _ptr(strand), _ptr(tally)))
+    return strand[:n], tally
+
+
+def junction_motifs_host(codes, left, right):
+    """The motif codes of junctions (left, right) over a sequence with a code a byte (``spl_junction_motifs_host``) -> uint8[n]."""
+    codes, left, right = _arr(codes, np.uint8), _arr(left, np.int32), _arr(right, np.int32)
+    out = np.zeros(max(left.shape[0], 1), np.uint8)
+    _check(lib().spl_junction_motifs_host(_ptr(codes) if codes.size else None, ctypes.c_int64(codes.shape[0]), ctypes.c_int64(left.shape[0]), _ptr(left), _ptr(right), _ptr(out)))
+    return out[:left.shape[0]]
 
 
 def aux_strand_host(aux):

@@ -615,8 +615,15 @@ def write_tsv(output_path, table, results, is_beta2_cryptic):
 def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIntronSize=0, annotationFile=None, aType="gene",
             isStranded=False, strandedType=None, isbeta2Cryptic=False, devices=(0,), threads=0, log=_log, checkJunctions=False,
             gpuDecode=None, keepReads=False, minAnchor=None, minIntron=None, maxIntron=None, keepJunctions=False,
-            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, flagstat=False, anyOrder=False, minEvidence=None):
+            minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, flagstat=False, anyOrder=False, minEvidence=None,
+            genome=None, strandFromMotif=False, canonicalOnly=False):
     """SpliSER_v0_1_8.py:695-720, keyword-compatible with the reference's argparse dests.
+
+    ``genome`` / ``strandFromMotif`` / ``canonicalOnly`` (this build only, without ``inBed``; these change results): the uncompressed
+    FASTA the reads were aligned to goes to the GPU as base codes; ``strandFromMotif`` takes a junction's strand from the splice motifs
+    of its reads' junctions -- what STAR's ``--outSAMstrandField intronMotif`` would have tagged, for a file without tags; the run goes
+    on as under ``strandFromXS``, to which, like ``isStranded`` and ``strandedType="auto"``, it is an alternative --; ``canonicalOnly``
+    drops the junctions whose motif is none of the six before the site table is made (``junctions.py``).
 
     ``strandedType="auto"`` (this build only): the library's strandedness is inferred from the file itself (``strandedness.py``): the
     decode also leaves the spliced reads' XS:A strand bytes, the whole decode is waited for (as for ``anyOrder``), every read's
@@ -669,7 +676,11 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
     auto = strandedType == "auto"
     if auto and strandFromXS:
         raise ValueError("strandedType 'auto' and strandFromXS are alternatives: the tag tells the library's strandedness, or the junctions' strands")
-    options = DecodeOptions(read_filter(minMapQ, requireFlags, excludeFlags), bool(strandFromXS or auto), bool(flagstat), bool(anyOrder))
+    from . import junctions as _jn
+    if inBed is not None and (genome is not None or strandFromMotif or canonicalOnly):
+        raise ValueError("genome / strandFromMotif / canonicalOnly belong to a run without inBed: a junction file has its own strands and junctions")
+    _jn.check_motif_options(genome, strandFromMotif, canonicalOnly, isStranded, strandFromXS, auto)
+    options = DecodeOptions(read_filter(minMapQ, requireFlags, excludeFlags), bool(strandFromXS or strandFromMotif or auto), bool(flagstat), bool(anyOrder))
     knobs = None
     if inBed is None:
         if checkJunctions:
@@ -707,7 +718,7 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
             def rows_of_bam():
                 t_j = time.perf_counter()
                 rows = _junction_rows(source, inBAM, outputPath if keepJunctions else None, qChrom, isStranded, strandedType, knobs, devices,
-                                      strandFromXS=strandFromXS, log=log)
+                                      strandFromXS=strandFromXS, log=log, genome=genome, strandFromMotif=strandFromMotif, canonicalOnly=canonicalOnly)
                 timings["junctions_s"] = time.perf_counter() - t_j
                 return rows
         table = _site_table(inBed, qGene, qChrom, maxIntronSize, annotationFile, aType, isStranded, strandedType, log, rows_of_bam, bins=bins)
@@ -804,7 +815,8 @@ def process(inBAM, inBed=None, outputPath=None, qGene="All", qChrom="All", maxIn
 JUNCTION_DEFAULTS = (8, 70, 500000)     # minAnchor, minIntron, maxIntron of a run without a junction file (the `junctions` command's)
 
 
-def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType, knobs, devices, strandFromXS=False, log=None):
+def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType, knobs, devices, strandFromXS=False, log=None, genome=None, strandFromMotif=False,
+                   canonicalOnly=False):
     """A run without a junction file: every chromosome's junction table from the reads the decode leaves (``-c``: that one's) ->
     [(chrom, table)] of the chromosomes that have a junction, in the order of the header: the lines of the file ``junctions``
     writes, never written -- unless ``keep_prefix`` asks for it (``<prefix>.junctions.bed``, the same bytes)."""
@@ -812,16 +824,25 @@ def _junction_rows(source, inBAM, keep_prefix, qChrom, isStranded, strandedType,
     stranded = native.STRANDED_CODE[strandedType] if isStranded else 0
     if isStranded and stranded == 0:
         raise ValueError("strandedType must be 'fr' or 'rf' for a stranded analysis")
-    if strandFromXS:
+    if strandFromXS or strandFromMotif:
         stranded = native.STRAND_FROM_XS
     chroms = chroms_of(source, qChrom)
     tally = [0, 0, 0] if strandFromXS else None
-    got = jn.tables_of_source(source, devices, chroms, stranded, *knobs, tally=tally)
-    if isinstance(source, native.BamFile) and not source.wait_all():     # (with -c too: an unsorted file's reference may be incomplete)
-        raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
-    if strandFromXS and log is not None:
-        jn.log_xs_tally(tally, log)
-    tables = {c: t for c, (_, t) in got.items()}
+    fasta = jn.GenomeOnDevices(genome) if genome is not None else None
+    try:
+        got = jn.tables_of_source(source, devices, chroms, stranded, *knobs, tally=tally, motif=fasta if strandFromMotif else None)
+        if isinstance(source, native.BamFile) and not source.wait_all():     # (with -c too: an unsorted file's reference may be incomplete)
+            raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
+        if strandFromXS and log is not None:
+            jn.log_xs_tally(tally, log)
+        if strandFromMotif and log is not None:
+            jn.log_motif_tally(fasta.tally, log)
+        tables = {c: t for c, (_, t) in got.items()}
+        if canonicalOnly:
+            tables = jn.drop_noncanonical(tables, chroms, fasta, source, tuple(devices), log if log is not None else (lambda *a: None))
+    finally:
+        if fasta is not None:
+            fasta.close()
     if keep_prefix is not None:
         jn.write_bed_file(keep_prefix + ".junctions.bed", chroms, tables, *knobs)
     return [(c, tables[c]) for c in chroms if c in tables and len(tables[c]["left"])]
