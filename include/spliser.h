@@ -345,10 +345,22 @@ int spl_flagstat_add_host(uint32_t flag, int32_t tid, int32_t next_tid, uint32_t
  * spl_sort_keys_device: the device's sort itself on a caller's keys (test hook; no file): uploads n keys (n < 2^32 - 16), runs
  * exactly the passes the decode runs for keys of key_bits bits (1..64: the digits of the low word from bit 0, those of the high
  * word from bit 32, 8 bits a pass) and downloads the permutation -- perm_out[i] = index of the key that comes i-th, equal keys in
- * the order they came in. */
+ * the order they came in.
+ * spl_text_windows_host (test hook, no GPU): how the device's text sources cut a mapped text into windows of whole lines
+ * (csrc/spl_text_windows.h) -- bytes [begin, len) of `text` into windows of at most win_bytes that end behind a newline, the last
+ * one with the text; rule 0 (SAM text): a line that fits no window ends the plan in front of it, *long_line_out = 1; rule 1
+ * (FASTA): it gets a window of its own.  *n_out = the windows, always written; cuts[2k], cuts[2k + 1] = window k's first byte and
+ * the byte behind its last where cap >= *n_out, SPL_ERR_ARG otherwise.
+ * spl_text_line_index (test hook): the line starts the device's text sources find (csrc/spl_sam.h) in windows [lo[w], hi[w]) of a
+ * host text, 0 <= lo < hi <= len, ONE index object over all of them in the order given, its buffers kept, reused and regrown as a
+ * decode's are.  n_lines_out[w] = window w's lines, room_out[w] = the lines the index had room for behind it; starts_out = every
+ * window's line starts end to end, as offsets from lo[w] & ~15 (cap_starts of them at most, SPL_ERR_ARG otherwise). */
 int spl_bam_set_any_order(spl_bam *bam, int on);
 int spl_bam_any_order_sorted(spl_bam *bam, int64_t *n_sorted_out, int *on_device_out);
 int spl_sort_keys_device(spl_ctx *ctx, const uint64_t *keys, int64_t n, int key_bits, uint32_t *perm_out);
+int spl_text_windows_host(const uint8_t *text, int64_t len, int64_t begin, int64_t win_bytes, int rule, int64_t cap, int64_t *cuts, int64_t *n_out, int *long_line_out);
+int spl_text_line_index(spl_ctx *ctx, const uint8_t *text, int64_t len, int64_t n_windows, const int64_t *lo, const int64_t *hi, int64_t cap_starts, int64_t *n_lines_out,
+                        int64_t *room_out, uint32_t *starts_out);
 int spl_bam_aux_strand(const spl_bam *bam, int tid, const uint8_t **out);
 int spl_bam_aux_strand_host(const uint8_t *aux, uint32_t len, uint8_t *out);
 int spl_bam_decode_device(spl_ctx *ctx, spl_bam *bam, int *on_device_out);

@@ -32,6 +32,7 @@
 #include "spl_sam.h"
 #include "spl_sam_line.h"
 #include "spl_sam_zhost.h"
+#include "spl_text_windows.h"
 #include "spl_flagstat.h"
 #include "spl_devpack.h"
 #include "spl_device.h"
@@ -1376,10 +1377,79 @@ static hipError_t create(Kept &k)
 
 struct DevBuf {
     void *p = nullptr;
+    size_t room = 0; // the bytes ensure() last asked for (0 for a buffer that get() made)
     ~DevBuf() { devmem::put(p); }
-    void release() { devmem::put(p); p = nullptr; }
+    void release() { devmem::put(p); p = nullptr; room = 0; }
     hipError_t get(size_t bytes, hipStream_t) { return devmem::get(&p, bytes ? bytes : 16, 'b'); }
+    // (a buffer kept between uses, its contents not) nothing to do while `bytes` fit; else the old buffer goes back FIRST -- the pool
+    // may hand the same block out again -- and a get that fails leaves no room behind
+    hipError_t ensure(size_t bytes, hipStream_t st)
+    {
+        if (bytes <= room) return hipSuccess;
+        release();
+        const hipError_t q = get(bytes, st);
+        if (q == hipSuccess) room = bytes;
+        return q;
+    }
     template <class T> T *as() const { return (T *)p; }
+};
+
+// A fresh buffer of `bytes` in b's place with the first `used` bytes of the old one, moved device to device on `st`, which is
+// waited for behind the move: the old buffer goes back to the pool behind that wait.  Nothing there, or nothing used: no move, no wait.
+static int regrow(DevBuf &b, size_t bytes, size_t used, hipStream_t st)
+{
+    DevBuf fresh; // (its destructor gives the old buffer back)
+    HIP_TRY(fresh.get(bytes, st));
+    if (b.p && used) { HIP_TRY(hipMemcpyAsync(fresh.p, b.p, used, hipMemcpyDeviceToDevice, st)); HIP_TRY(hipStreamSynchronize(st)); }
+    std::swap(b.p, fresh.p);
+    return SPL_OK;
+}
+
+// ---- what the device's text sources share (SamDecode, SamZDecode, GenomeLoad): spl_text_windows.h cuts a mapped text into windows
+// of whole lines, send_window brings one up, LineIndex finds its lines, and the source's own rule, a lane per line, leaves the
+// first line it declines as a FirstBad.
+using spltext::Window;
+// `win` of a mapped file into `dst` from lo rounded down to 16 (spl_sam.h: addresses and file offsets are equal modulo 16), piece by
+// piece through the context's staging ring on the copy stream; `done` is recorded behind the last piece.
+static hipError_t send_window(spl_ctx *c, const uint8_t *image, int fd, const Window &win, DevBuf &dst, hipEvent_t done)
+{
+    const uint64_t from = win.lo & ~(uint64_t)15;
+    const hipError_t q = ring_send(c, dst.as<char>(), win.hi - from, FileFill{image, fd, from});
+    return q == hipSuccess ? hipEventRecord(done, c->copy) : q;
+}
+
+// Where the lines of a window begin (spl_sam.h: `text` indexed with whole-file offsets, whole lines in [lo, hi), hi > lo): a count a
+// chunk, the prefix sum, the fill.  One object serves a source's windows in turn and keeps its buffers between them; they grow when
+// a window needs more, the chunks and the scan's work to the size asked for, the lines by an eighth more.
+struct LineIndex {
+    DevBuf d_chunks, d_lines, d_work;
+    uint32_t n_lines = 0; // of the last window
+    size_t room() const { return d_lines.room / 4; } // the lines d_lines has room for: the callers' per-line arrays are sized by it, so they regrow with it
+    hipError_t scan_work(uint64_t n, hipStream_t st) { return d_work.ensure(spl_dev_sort_work_bytes(n), st); }
+    // One host wait, for the number of lines; the fill is queued behind it.  The caller then sizes its per-line arrays by room() and
+    // asks for scan_work(n_lines), the scan's work buffer for its own sums over the lines, behind them: the order the pool has always been asked in.
+    int find(const uint8_t *text, uint64_t lo, uint64_t hi, hipStream_t st)
+    {
+        const uint32_t n_chunks = spl_sam_chunks(lo, hi);
+        HIP_TRY(d_chunks.ensure(4 * (size_t)n_chunks, st));
+        HIP_TRY(scan_work(n_chunks, st));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_line_count(text, lo, hi, d_chunks.as<uint32_t>(), st));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_chunks.as<uint32_t>(), n_chunks, d_work.p, st));
+        HIP_TRY(hipMemcpyAsync(&n_lines, d_chunks.as<uint32_t>() + (n_chunks - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_lines > room()) HIP_TRY(d_lines.ensure(4 * ((size_t)n_lines + (size_t)n_lines / 8), st));
+        HIP_TRY((hipError_t)spl_dev_launch_sam_line_fill(text, lo, hi, d_chunks.as<uint32_t>(), d_lines.as<uint32_t>(), st));
+        return SPL_OK;
+    }
+    void release() { d_chunks.release(); d_lines.release(); d_work.release(); }
+};
+
+// The first line of a window that the source's rule declined, as its kernels leave it (spl_sam_counts, spl_genome_counts): index << 8 |
+// reason by atomicMin, over NONE, which the caller puts there in front of every window.  line: of the window, from 0.
+struct FirstBad {
+    static constexpr unsigned long long NONE = ~0ull;
+    const bool any; const uint64_t line; const uint32_t reason;
+    explicit FirstBad(unsigned long long v) : any(v != NONE), line(v >> 8), reason((uint32_t)(v & 0xffu)) {}
 };
 } // namespace
 
@@ -1422,16 +1492,7 @@ struct RecordArrays {
     // old array goes back to the pool behind that wait.  The first reservation moves nothing and waits for nothing.
     int reserve(uint64_t want_rec, uint64_t want_ops, hipStream_t st)
     {
-        auto grow = [&](DevBuf &b, size_t elem, uint64_t n, uint64_t used) -> int {
-            DevBuf fresh;
-            HIP_TRY(fresh.get(elem * (size_t)n, st));
-            if (b.p && used) {
-                HIP_TRY(hipMemcpyAsync(fresh.p, b.p, elem * (size_t)used, hipMemcpyDeviceToDevice, st));
-                HIP_TRY(hipStreamSynchronize(st));
-            }
-            std::swap(b.p, fresh.p);
-            return SPL_OK; // (fresh's destructor gives the old array back)
-        };
+        auto grow = [&](DevBuf &b, size_t elem, uint64_t n, uint64_t used) { return regrow(b, elem * (size_t)n, elem * (size_t)used, st); };
         if (want_rec > cap_rec) {
             const bool first = !cig_off.p;
             int rc = grow(pos, 4, want_rec, n_rec);
@@ -2720,15 +2781,14 @@ static int decode_share(spl_ctx *c, spl_bam *bam, const spl_bam_share *share, Sh
 }
 
 // ---- SAM text (spl_sam_open): the same five arrays from the text an aligner writes --------------------------------------
-// Windows of SPL_SAM_WINDOW_BYTES (default 256 MiB) of whole lines -- the host cuts a window behind its last '\n', which it finds
-// in the mapping: text needs no room for an unfinished line, and a line longer than a window declines the file -- go up
-// through the context's staging ring on the copy stream, from a thread of this call, into two device buffers, while the window
-// before is parsed on a stream of its own: line starts (count, prefix sum, fill), the scan (the rule, a lane per line), prefix sums
-// of kept lines and ops, the extraction.  The host waits twice a window, for the number of lines and for the kept lines' and ops'
-// totals (the output arrays are sized from the first window's density and regrown, device to device, when a later one needs
-// more).  Behind the last window: the sort when reference ids or POS ever went down (text is always spl_bam_set_any_order),
-// where each reference's records are, the totals, and the same hand-over as the BAM decode's.  A line the rule does not take ends
-// the decode with the file declined (spl_sam_fail); everything else that goes wrong leaves the file to the host parser.
+// Windows of SPL_SAM_WINDOW_BYTES (default 256 MiB) of whole lines (spl_text_windows.h, STOP: text needs no room for an unfinished
+// line, and a line longer than a window declines the file) go up from a thread of this call (send_window) into two device buffers,
+// while the window before is parsed on a stream of its own: line starts (LineIndex), the scan (the rule, a lane per line), prefix
+// sums of kept lines and ops, the extraction.  The host waits twice a window, for the number of lines and for the kept lines' and
+// ops' totals (the output arrays are sized from the first window's density and regrown, device to device, when a later one needs
+// more).  Behind the last window: the sort when reference ids or POS ever went down (text is always spl_bam_set_any_order), where
+// each reference's records are, the totals, and the same hand-over as the BAM decode's.  A line the rule does not take ends the
+// decode with the file declined (spl_sam_fail); everything else that goes wrong leaves the file to the host parser.
 namespace {
 struct SamDecode {
     spl_ctx *const c;
@@ -2746,10 +2806,10 @@ struct SamDecode {
     spl_sam_names host_names{}, dev_names{};
     size_t blob_bytes = 0;
     // ---- everything the streams touch is declared before them
-    DevBuf d_text[2], d_slots, d_nameoff, d_blob, d_chunks, d_lines, d_kept, d_nops, d_ltid, d_fstat, d_fsum, d_counts, d_work, d_maxend, d_bounds, d_nbounds, d_long;
+    DevBuf d_text[2], d_slots, d_nameoff, d_blob, d_kept, d_nops, d_ltid, d_fstat, d_fsum, d_counts, d_maxend, d_bounds, d_nbounds, d_long;
+    LineIndex lines;
     RecordArrays arrays;
     RecordSort sorter;
-    size_t cap_chunks = 0, cap_lines = 0, cap_work = 0;
     uint64_t n_lines_all = 0, n_drop_flags = 0, n_drop_mapq = 0, n_sorted = 0;
     struct Streams {
         hipStream_t k = nullptr;
@@ -2761,7 +2821,6 @@ struct SamDecode {
         }
     } st;
     // ---- the windows and the thread that sends them
-    struct Window { uint64_t lo, hi; };
     std::vector<Window> windows;
     size_t win_bytes = (size_t)256 << 20;
     uint64_t text_bytes = 0;  // (SPL_BAM_TIMING's line: the bytes of text, the windows they came in, and what kind of file)
@@ -2775,36 +2834,33 @@ struct SamDecode {
     std::thread uploader;
 
     SamDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : c(ctx), bam(b), res(r) { arrays.want_xs = want_xs; arrays.want_keys = want_keys; }
-    ~SamDecode()
+    void stop_uploader() // (before the buffers and streams go that the thread works on)
     {
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            stop = true;
-        }
+        { std::lock_guard<std::mutex> lock(mu); stop = true; }
         cv.notify_all();
         if (uploader.joinable()) uploader.join();
+    }
+    void parsed(size_t w) // (window w's buffer is free for window w + 2)
+    {
+        { std::lock_guard<std::mutex> lock(mu); n_parsed = w + 1; }
+        cv.notify_all();
+    }
+    ~SamDecode()
+    {
+        stop_uploader();
         if (c->copy) (void)hipStreamSynchronize(c->copy);
         c->stages_idle();
     }
 
-    // The file cut into windows of whole lines.  A line longer than a window (its newline counted) fits none: the windows end in
-    // front of it, and the file is declined there once the lines before it have been found good -- the first line the rule does
-    // not take is the one that is reported, as by the host parser, which declines the same line by the same measure.
+    // The file cut into windows of whole lines, which end in front of a line that fits none (long_line): the file is declined there
+    // once the lines before it have been found good -- the first line the rule does not take is the one that is reported, as by the
+    // host parser, which declines the same line by the same measure.
     bool long_line = false;
     int plan()
     {
         (void)spl_bam_text(bam, &begin, &header_lines, &host_names, &blob_bytes);
         win_bytes = spl_sam_window_bytes();
-        for (uint64_t lo = begin; lo < fsize;) {
-            uint64_t hi = std::min<uint64_t>(fsize, lo + win_bytes);
-            if (hi < fsize) {
-                const void *nl = memrchr(image + lo, '\n', (size_t)(hi - lo));
-                if (!nl) { long_line = true; break; }
-                hi = (uint64_t)((const uint8_t *)nl - image) + 1;
-            }
-            windows.push_back(Window{lo, hi});
-            lo = hi;
-        }
+        long_line = spltext::cut_windows(image, begin, fsize, win_bytes, spltext::STOP, windows);
         text_bytes = fsize - begin;
         n_windows = windows.size();
         return SPL_OK;
@@ -2854,9 +2910,7 @@ struct SamDecode {
                 cv.wait(lock, [&]() { return stop || w < n_parsed + 2; });
                 if (stop) return;
             }
-            const uint64_t from = windows[w].lo & ~(uint64_t)15, bytes = windows[w].hi - from;
-            q = ring_send(c, d_text[w % 2].as<char>(), bytes, FileFill{image, spl_bam_fd(bam), from});
-            if (q == hipSuccess) q = hipEventRecord(st.up[w % 2], c->copy);
+            q = send_window(c, image, spl_bam_fd(bam), windows[w], d_text[w % 2], st.up[w % 2]);
             std::lock_guard<std::mutex> lock(mu);
             if (q == hipSuccess) n_sent = w + 1;
             else up_err = q;
@@ -2896,11 +2950,7 @@ struct SamDecode {
         const uint64_t last_end = image[win.hi - 1] == '\n' ? win.hi - 1 : win.hi;
         HIP_TRY(hipStreamWaitEvent(st.k, st.up[w % 2], 0));
         { const int rc = parse_range(text, win, last_end, fsize - win.hi, 0); if (rc) return rc; }
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            n_parsed = w + 1;
-        }
-        cv.notify_all();
+        parsed(w);
         return SPL_OK;
     }
 
@@ -2911,34 +2961,14 @@ struct SamDecode {
     int parse_range(const uint8_t *text, const Window win, uint64_t last_end, uint64_t bytes_left, size_t max_line)
     {
         const uint64_t base = win.lo & ~(uint64_t)15;
-        // ---- line starts
-        const uint32_t n_chunks = spl_sam_chunks(win.lo, win.hi);
-        if (n_chunks > cap_chunks) { d_chunks.release(); HIP_TRY(d_chunks.get(4 * (size_t)n_chunks, st.k)); cap_chunks = n_chunks; }
-        auto work_for = [&](uint64_t n) -> hipError_t {
-            const size_t need = spl_dev_sort_work_bytes(n);
-            if (need <= cap_work) return hipSuccess;
-            d_work.release();
-            cap_work = 0;
-            const hipError_t q = d_work.get(need, st.k);
-            if (q == hipSuccess) cap_work = need;
-            return q;
-        };
-        HIP_TRY(work_for(n_chunks));
-        HIP_TRY((hipError_t)spl_dev_launch_sam_line_count(text, win.lo, win.hi, d_chunks.as<uint32_t>(), st.k));
-        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_chunks.as<uint32_t>(), n_chunks, d_work.p, st.k));
-        uint32_t n_lines = 0;
-        HIP_TRY(hipMemcpyAsync(&n_lines, d_chunks.as<uint32_t>() + (n_chunks - 1), 4, hipMemcpyDeviceToHost, st.k));
-        HIP_TRY(hipStreamSynchronize(st.k));
-        if (n_lines > cap_lines) {
-            d_lines.release(); d_kept.release(); d_nops.release(); d_ltid.release(); d_fstat.release();
-            cap_lines = 0;
-            const size_t n = (size_t)n_lines + (size_t)n_lines / 8;
-            HIP_TRY(d_lines.get(4 * n, st.k)); HIP_TRY(d_kept.get(4 * n, st.k)); HIP_TRY(d_nops.get(4 * n, st.k)); HIP_TRY(d_ltid.get(4 * n, st.k));
-            if (want_stat) HIP_TRY(d_fstat.get(4 * SPL_FS_CATEGORIES * ((n + 63) / 64), st.k));
-            cap_lines = n;
-        }
-        HIP_TRY(work_for(n_lines));
-        HIP_TRY((hipError_t)spl_dev_launch_sam_line_fill(text, win.lo, win.hi, d_chunks.as<uint32_t>(), d_lines.as<uint32_t>(), st.k));
+        // ---- line starts, and the per-line arrays with the room they have
+        { const int rc = lines.find(text, win.lo, win.hi, st.k); if (rc) return rc; }
+        const uint32_t n_lines = lines.n_lines;
+        const DevBuf &d_lines = lines.d_lines, &d_work = lines.d_work;
+        const size_t room = lines.room();
+        HIP_TRY(d_kept.ensure(4 * room, st.k)); HIP_TRY(d_nops.ensure(4 * room, st.k)); HIP_TRY(d_ltid.ensure(4 * room, st.k));
+        if (want_stat) HIP_TRY(d_fstat.ensure(4 * SPL_FS_CATEGORIES * ((room + 63) / 64), st.k));
+        HIP_TRY(lines.scan_work(n_lines, st.k));
         uint32_t first_long = ~0u;
         if (max_line) {
             static const uint32_t no_line = ~0u;
@@ -2948,8 +2978,7 @@ struct SamDecode {
             HIP_TRY(hipMemcpyAsync(&first_long, d_long.p, 4, hipMemcpyDeviceToHost, st.k)); // (back with the scan's counters: no wait of its own)
         }
         // ---- the rule, a lane per line
-        static const unsigned long long none = ~0ull;
-        HIP_TRY(hipMemcpyAsync(d_counts.p, &none, 8, hipMemcpyHostToDevice, st.k));
+        HIP_TRY(hipMemcpyAsync(d_counts.p, &FirstBad::NONE, 8, hipMemcpyHostToDevice, st.k));
         HIP_TRY(hipMemsetAsync(d_counts.as<char>() + 8, 0, 8, st.k)); // (the two drop counters; `unordered` and `overflow` stay)
         HIP_TRY((hipError_t)spl_dev_launch_sam_scan(text, base, d_lines.as<uint32_t>(), n_lines, last_end, &dev_names, opts.filter.min_mapq, opts.filter.require_flags,
                                                     opts.filter.exclude_flags, want_xs ? 1 : 0, d_kept.as<uint32_t>(), d_nops.as<uint32_t>(), d_ltid.as<int32_t>(),
@@ -2964,14 +2993,15 @@ struct SamDecode {
             HIP_TRY(hipMemcpyAsync(&ops_w, d_nops.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st.k));
         }
         HIP_TRY(hipStreamSynchronize(st.k));
-        if (first_long != ~0u && (counts.first_bad == none || first_long <= (counts.first_bad >> 8))) { // (the host parser measures a line before it reads it)
+        const FirstBad declined(counts.first_bad);
+        if (first_long != ~0u && (!declined.any || first_long <= declined.line)) { // (the host parser measures a line before it reads it)
             bad_line = header_lines + n_lines_all + first_long + 1;
             bad_reason = SPL_SAM_LONG_LINE;
             return STOPPED;
         }
-        if (counts.first_bad != none) {
-            bad_line = header_lines + n_lines_all + (counts.first_bad >> 8) + 1;
-            bad_reason = (uint32_t)(counts.first_bad & 0xffu);
+        if (declined.any) {
+            bad_line = header_lines + n_lines_all + declined.line + 1;
+            bad_reason = declined.reason;
             return STOPPED;
         }
         if (arrays.n_rec + kept_w > 0xfffffff0ull || arrays.n_ops + ops_w > 0xfffffff0ull) { // (cig_off is 32 bits wide, and so is the sort's payload)
@@ -3007,7 +3037,7 @@ struct SamDecode {
     void release_buffers()
     {
         for (DevBuf &b : d_text) b.release();
-        d_chunks.release(); d_lines.release(); d_kept.release(); d_nops.release(); d_ltid.release(); d_fstat.release(); d_work.release();
+        lines.release(); d_kept.release(); d_nops.release(); d_ltid.release(); d_fstat.release();
     }
     std::vector<unsigned long long> maxend;
     int sort_records()
@@ -3047,6 +3077,19 @@ struct SamDecode {
             fprintf(stderr, "[spl_bam_decode_device] device %d: %s, %.1f MB in %zu window%s, %llu lines, %llu placed records%s: %.4f s\n", c->device, what, text_bytes / 1e6, n_windows,
                     n_windows == 1 ? "" : "s", (unsigned long long)n_lines_all, (unsigned long long)n_rec, n_sorted ? ", sorted" : "", host_now() - t_begin);
         return SPL_OK;
+    }
+
+    // How a decode of text ends, plain or compressed; rc: what its windows left.  A file that is not declined: as ShareDecode::release_and_publish,
+    // the decode's buffers go back to the pool before the waiters are told (a failed hand-over frees the reads itself: spl_bam_decode_device's `adopt`).
+    int end(int rc, const Publish &publish)
+    {
+        if (rc == STOPPED) { spl_sam_fail(bam, bad_line, bad_reason); return SPL_OK; }
+        if (rc == SPL_OK && long_line) { spl_sam_fail(bam, header_lines + n_lines_all + 1, SPL_SAM_LONG_LINE); return SPL_OK; }
+        if (rc == SPL_OK) rc = finish();
+        if (rc != SPL_OK) return rc;
+        release_buffers();
+        sorter.release();
+        return publish(res);
     }
 };
 
@@ -3093,15 +3136,7 @@ struct SamZDecode : SamDecode {
     uint64_t n_blocks_done = 0;
 
     SamZDecode(spl_ctx *ctx, spl_bam *b, ShareOut &r) : SamDecode(ctx, b, r) {}
-    ~SamZDecode()
-    {
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            stop = true;
-        }
-        cv.notify_all();
-        if (uploader.joinable()) uploader.join(); // (before this object's buffers and stream go: the thread works on them)
-    }
+    ~SamZDecode() { stop_uploader(); } // (before this object's buffers and stream go)
 
     int plan_z()
     {
@@ -3301,11 +3336,7 @@ struct SamZDecode : SamDecode {
             t_parse += host_now() - t0;
             ++n_windows;
             text_bytes += r.hi - r.lo;
-            {
-                std::lock_guard<std::mutex> lock(mu);
-                n_parsed = w + 1;
-            }
-            cv.notify_all();
+            parsed(w);
         }
         if (timing)
             fprintf(stderr, "[spl_bam_decode_device] device %d: %s: upload %.4f s, inflate %.4f s (%llu blocks), parse %.4f s (the producing thread's stages overlap the parsing one's)\n", c->device, what,
@@ -3321,13 +3352,7 @@ static int decode_ztext(spl_ctx *c, spl_bam *bam, ShareOut &res, const Publish &
     int rc = d.plan_z();
     if (rc == SPL_OK) rc = d.set_up_z();
     if (rc == SPL_OK) rc = d.parse_all();
-    if (rc == STOPPED) { spl_sam_fail(bam, d.bad_line, d.bad_reason); return SPL_OK; }
-    if (rc == SPL_OK && d.long_line) { spl_sam_fail(bam, d.header_lines + d.n_lines_all + 1, SPL_SAM_LONG_LINE); return SPL_OK; }
-    if (rc == SPL_OK) rc = d.finish();
-    if (rc != SPL_OK) return rc;
-    d.release_buffers();
-    d.sorter.release();
-    return publish(res);
+    return d.end(rc, publish);
 }
 
 static int decode_text(spl_ctx *c, spl_bam *bam, ShareOut &res, const Publish &publish)
@@ -3338,15 +3363,45 @@ static int decode_text(spl_ctx *c, spl_bam *bam, ShareOut &res, const Publish &p
     int rc = d.plan();
     if (rc == SPL_OK) rc = d.set_up();
     for (size_t w = 0; w < d.windows.size() && rc == SPL_OK; ++w) rc = d.parse_window(w);
-    if (rc == STOPPED) { spl_sam_fail(bam, d.bad_line, d.bad_reason); return SPL_OK; }
-    if (rc == SPL_OK && d.long_line) { spl_sam_fail(bam, d.header_lines + d.n_lines_all + 1, SPL_SAM_LONG_LINE); return SPL_OK; }
-    if (rc == SPL_OK) rc = d.finish();
-    if (rc != SPL_OK) return rc;
-    // as ShareDecode::release_and_publish: the decode's buffers go back to the pool before the waiters are told (a failed
-    // hand-over frees the reads itself: spl_bam_decode_device's `adopt`)
-    d.release_buffers();
-    d.sorter.release();
-    return publish(res);
+    return d.end(rc, publish);
+}
+
+// The window plan on a caller's text (test hook, no GPU): spl_text_windows.h as the decoders call it.
+extern "C" int spl_text_windows_host(const uint8_t *text, int64_t len, int64_t begin, int64_t win_bytes, int rule, int64_t cap, int64_t *cuts, int64_t *n_out, int *long_line_out)
+{
+    if (len < 0 || (len && !text) || begin < 0 || begin > len || win_bytes < 0 || (rule != spltext::STOP && rule != spltext::OWN_WINDOW) || cap < 0 || (cap && !cuts) || !n_out || !long_line_out)
+        return spl_set_error(SPL_ERR_ARG, "spl_text_windows_host: bad argument");
+    std::vector<Window> windows;
+    *long_line_out = spltext::cut_windows(text, (uint64_t)begin, (uint64_t)len, (uint64_t)win_bytes, (spltext::LongLine)rule, windows) ? 1 : 0;
+    *n_out = (int64_t)windows.size();
+    if (windows.size() > (uint64_t)cap) return spl_set_error(SPL_ERR_ARG, "spl_text_windows_host: %zu windows, room for %lld", windows.size(), (long long)cap);
+    for (size_t k = 0; k < windows.size(); ++k) { cuts[2 * k] = (int64_t)windows[k].lo; cuts[2 * k + 1] = (int64_t)windows[k].hi; }
+    return SPL_OK;
+}
+
+// The decoders' line index on a caller's text (test hook): ONE LineIndex over the windows in the order given, so that its buffers are
+// made, reused and outgrown as a decode's are.  A window goes up with a plain copy, newlines behind it to the pad's end (none may count).
+extern "C" int spl_text_line_index(spl_ctx *c, const uint8_t *text, int64_t len, int64_t n_windows, const int64_t *lo, const int64_t *hi, int64_t cap_starts, int64_t *n_lines_out,
+                                   int64_t *room_out, uint32_t *starts_out)
+{
+    if (!c || len < 0 || (len && !text) || n_windows < 0 || (n_windows && (!lo || !hi || !n_lines_out || !room_out)) || cap_starts < 0 || (cap_starts && !starts_out))
+        return spl_set_error(SPL_ERR_ARG, "spl_text_line_index: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf d_text;
+    LineIndex lines;
+    for (int64_t w = 0, at = 0; w < n_windows; at += lines.n_lines, ++w) {
+        if (lo[w] < 0 || lo[w] >= hi[w] || hi[w] > len || hi[w] - lo[w] > 0x7fffff00LL) return spl_set_error(SPL_ERR_ARG, "spl_text_line_index: window %lld is not a window of the text", (long long)w);
+        const uint64_t base = (uint64_t)lo[w] & ~(uint64_t)15, bytes = (uint64_t)hi[w] - base;
+        HIP_TRY(d_text.ensure((size_t)bytes + 16 + SPL_SAM_PAD, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_text.p, text + base, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(d_text.as<char>() + bytes, '\n', 16 + SPL_SAM_PAD, c->stream));
+        { const int rc = lines.find(d_text.as<uint8_t>() - base, (uint64_t)lo[w], (uint64_t)hi[w], c->stream); if (rc) return rc; }
+        n_lines_out[w] = lines.n_lines; room_out[w] = (int64_t)lines.room();
+        if (at + (int64_t)lines.n_lines > cap_starts) return spl_set_error(SPL_ERR_ARG, "spl_text_line_index: more line starts than room for %lld", (long long)cap_starts);
+        HIP_TRY(hipMemcpyAsync(starts_out + at, lines.d_lines.p, 4 * (size_t)lines.n_lines, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream)); // (the text's buffer is the next window's)
+    }
+    return SPL_OK;
 }
 
 // The device's sort on a caller's keys (test hook): exactly the launches sort_records makes for keys of key_bits bits.
@@ -4519,7 +4574,7 @@ int cov_stages(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, i
         splprof::Scope prof("spl_cov_compact", c->stream, 2.0 * 4.0 * (double)length); // (the array read twice; the boundaries are few beside it)
         int rc = spl_dev_launch_cov_count(d_diff.as<uint32_t>(), length, d_tiles.as<uint32_t>(), c->stream);
         if (rc) return spl_set_error(SPL_ERR_HIP, "coverage count kernel launch: %s", hipGetErrorString((hipError_t)rc));
-        HIP_TRY(d_work.get(spl_dev_sort_work_bytes((uint64_t)n_tiles), c->stream));
+        HIP_TRY(d_work.ensure(spl_dev_sort_work_bytes((uint64_t)n_tiles), c->stream));
         HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_tiles.as<uint32_t>(), (uint64_t)n_tiles, d_work.p, c->stream));
         HIP_TRY(hipMemcpyAsync(&n_bound, d_tiles.as<uint32_t>() + (n_tiles - 1), 4, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream)); // (the buffers below are sized from the count)
@@ -4532,7 +4587,7 @@ int cov_stages(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, i
     }
     if (n_bound) {
         splprof::Scope prof("spl_cov_scan", c->stream, 2.0 * 4.0 * (double)n_bound);
-        if (spl_dev_sort_work_bytes(n_bound) > spl_dev_sort_work_bytes((uint64_t)n_tiles)) { d_work.release(); HIP_TRY(d_work.get(spl_dev_sort_work_bytes(n_bound), c->stream)); }
+        HIP_TRY(d_work.ensure(spl_dev_sort_work_bytes(n_bound), c->stream));
         HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_delta.as<uint32_t>(), n_bound, d_work.p, c->stream)); // delta -> the depth behind each boundary
     }
     s.n_bound = n_bound;
@@ -5368,12 +5423,11 @@ extern "C" int spl_sse(spl_ctx *c, const spl_sites *s, const uint32_t *beta1, co
 }
 
 // ---- the genome on the device (spl_genome.hip; the rule is spl_motif_rule.h) ----------------------------------------------------
-// A FASTA's sequences as base codes, two a byte (spl_genome.h: the stored form).  The file is mapped and goes up through the
-// staging ring in windows of whole lines -- cut by the host at the last newline a window's bytes hold, as the plain SAM text's
-// are (a longer line gets a window of its own) --, window w + 1 is sent before window w's launches are queued, so the copy engine
-// works while the kernels do.  Per window: spl_sam.hip's line starts, classify, two prefix sums, headers; the headers come down (a
-// few dozen for a genome), the host closes the sequences they end, checks the names and gives every piece of a sequence its
-// place; the pack kernel stores.  A sequence that spans windows is joined in the one 16-byte word two windows share (spl_genome.h).
+// A FASTA's sequences as base codes, two a byte (spl_genome.h: the stored form).  The file is mapped and goes up in windows of whole
+// lines (spl_text_windows.h, OWN_WINDOW: a line longer than a window gets one of its own; send_window), window w + 1 before window
+// w's launches are queued, so the copy engine works while the kernels do.  Per window: line starts (LineIndex), classify, two prefix
+// sums, headers; the headers come down (a few dozen for a genome), the host closes the sequences they end, checks the names and gives
+// every piece of a sequence its place; the pack kernel stores.  A sequence that spans windows is joined in the one 16-byte word two windows share (spl_genome.h).
 struct spl_genome {
     int device = 0;
     void *store = nullptr;
@@ -5405,10 +5459,9 @@ struct GenomeLoad {
     const uint8_t *image = nullptr;
     size_t fsize = 0;
     int fd = -1;
-    struct Window { uint64_t lo, hi; };
     std::vector<Window> windows;
-    DevBuf d_text[2], d_chunks, d_lines, d_nb, d_hdr, d_headers, d_segs, d_counts, d_work, d_store;
-    size_t cap_chunks = 0, cap_lines = 0, cap_work = 0, cap_headers = 0, cap_segs = 0;
+    DevBuf d_text[2], d_nb, d_hdr, d_headers, d_segs, d_counts, d_store;
+    LineIndex lines;
     hipEvent_t up[2] = {nullptr, nullptr};
     std::vector<hipEvent_t> ev; // per window: copy begin, copy end, kernels begin, kernels end
     // the sequence that is open: its bases so far, where it lies
@@ -5450,46 +5503,26 @@ struct GenomeLoad {
 
     int plan(size_t win_bytes)
     {
-        for (uint64_t lo = 0; lo < fsize;) {
-            uint64_t hi = std::min<uint64_t>(fsize, lo + win_bytes);
-            if (hi < fsize) {
-                const void *nl = memrchr(image + lo, '\n', (size_t)(hi - lo));
-                if (!nl) nl = memchr(image + hi, '\n', fsize - hi); // (a line longer than a window: a window of its own)
-                hi = nl ? (uint64_t)((const uint8_t *)nl - image) + 1 : fsize;
-            }
-            if (hi - lo > 0xffffff00ull) return spl_set_error(SPL_ERR_FORMAT, "%s: a line of more than 4 GiB", path);
-            windows.push_back(Window{lo, hi});
-            lo = hi;
-        }
+        (void)spltext::cut_windows(image, 0, fsize, win_bytes, spltext::OWN_WINDOW, windows); // (a line longer than a window: a window of its own)
+        for (const Window &w : windows)
+            if (w.hi - w.lo > 0xffffff00ull) return spl_set_error(SPL_ERR_FORMAT, "%s: a line of more than 4 GiB", path);
         return SPL_OK;
     }
 
     hipError_t send(size_t w)
     {
-        const uint64_t from = windows[w].lo & ~(uint64_t)15, bytes = windows[w].hi - from;
         hipError_t q = hipEventRecord(ev[4 * w], c->copy);
-        if (q == hipSuccess) q = ring_send(c, d_text[w % 2].as<char>(), bytes, FileFill{image, fd, from});
+        if (q == hipSuccess) q = send_window(c, image, fd, windows[w], d_text[w % 2], up[w % 2]);
         if (q == hipSuccess) q = hipEventRecord(ev[4 * w + 1], c->copy);
-        if (q == hipSuccess) q = hipEventRecord(up[w % 2], c->copy);
         return q;
-    }
-
-    bool name_seen(const std::string &s)
-    {
-        return !seen.insert(s).second;
     }
 
     int room(uint64_t need)
     {
         if (need <= g->cap) return SPL_OK;
         const uint64_t want = align_up((size_t)std::max<uint64_t>(need + need / 4, 4096), 256);
-        DevBuf fresh;
-        HIP_TRY(fresh.get((size_t)want, c->stream));
         // (what the windows before have stored, no more: g->used is already this window's, beyond the old store's end where it grows)
-        if (d_store.p && stored) HIP_TRY(hipMemcpyAsync(fresh.p, d_store.p, (size_t)std::min<uint64_t>(stored, g->cap), hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        d_store.release();
-        d_store.p = fresh.p; fresh.p = nullptr;
+        { const int rc = regrow(d_store, (size_t)want, (size_t)std::min<uint64_t>(stored, g->cap), c->stream); if (rc) return rc; }
         g->cap = want;
         return SPL_OK;
     }
@@ -5503,34 +5536,14 @@ struct GenomeLoad {
         const uint64_t last_end = image[win.hi - 1] == '\n' ? win.hi - 1 : win.hi;
         HIP_TRY(hipStreamWaitEvent(st, up[w % 2], 0));
         HIP_TRY(hipEventRecord(ev[4 * w + 2], st));
-        auto work_for = [&](uint64_t n) -> hipError_t {
-            const size_t need = spl_dev_sort_work_bytes(n);
-            if (need <= cap_work) return hipSuccess;
-            d_work.release(); cap_work = 0;
-            const hipError_t q = d_work.get(need, st);
-            if (q == hipSuccess) cap_work = need;
-            return q;
-        };
-        // ---- line starts
-        const uint32_t n_chunks = spl_sam_chunks(win.lo, win.hi);
-        if (n_chunks > cap_chunks) { d_chunks.release(); cap_chunks = 0; HIP_TRY(d_chunks.get(4 * (size_t)n_chunks, st)); cap_chunks = n_chunks; }
-        HIP_TRY(work_for(n_chunks));
-        HIP_TRY((hipError_t)spl_dev_launch_sam_line_count(text, win.lo, win.hi, d_chunks.as<uint32_t>(), st));
-        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_chunks.as<uint32_t>(), n_chunks, d_work.p, st));
-        uint32_t n_lines = 0;
-        HIP_TRY(hipMemcpyAsync(&n_lines, d_chunks.as<uint32_t>() + (n_chunks - 1), 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (n_lines > cap_lines) {
-            d_lines.release(); d_nb.release(); d_hdr.release(); cap_lines = 0;
-            const size_t n = (size_t)n_lines + (size_t)n_lines / 8;
-            HIP_TRY(d_lines.get(4 * n, st)); HIP_TRY(d_nb.get(4 * n, st)); HIP_TRY(d_hdr.get(4 * n, st));
-            cap_lines = n;
-        }
-        HIP_TRY(work_for(n_lines));
-        HIP_TRY((hipError_t)spl_dev_launch_sam_line_fill(text, win.lo, win.hi, d_chunks.as<uint32_t>(), d_lines.as<uint32_t>(), st));
+        // ---- line starts, and the per-line arrays with the room they have
+        { const int rc = lines.find(text, win.lo, win.hi, st); if (rc) return rc; }
+        const uint32_t n_lines = lines.n_lines;
+        const DevBuf &d_lines = lines.d_lines, &d_work = lines.d_work;
+        HIP_TRY(d_nb.ensure(4 * lines.room(), st)); HIP_TRY(d_hdr.ensure(4 * lines.room(), st));
+        HIP_TRY(lines.scan_work(n_lines, st));
         // ---- what every line is, and the sums
-        static const unsigned long long none = ~0ull;
-        HIP_TRY(hipMemcpyAsync(d_counts.p, &none, 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_counts.p, &FirstBad::NONE, 8, hipMemcpyHostToDevice, st));
         HIP_TRY((hipError_t)spl_dev_launch_genome_classify(text, base, d_lines.as<uint32_t>(), n_lines, last_end, win.hi, d_nb.as<uint32_t>(), d_hdr.as<uint32_t>(),
                                                            d_counts.as<spl_genome_counts>(), st));
         HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_nb.as<uint32_t>(), n_lines, d_work.p, st));
@@ -5539,7 +5552,7 @@ struct GenomeLoad {
         HIP_TRY(hipMemcpyAsync(&n_bases, d_nb.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&n_hdr, d_hdr.as<uint32_t>() + (n_lines - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (n_hdr > cap_headers) { d_headers.release(); cap_headers = 0; HIP_TRY(d_headers.get(sizeof(spl_genome_header) * (size_t)n_hdr, st)); cap_headers = n_hdr; }
+        HIP_TRY(d_headers.ensure(sizeof(spl_genome_header) * (size_t)n_hdr, st));
         HIP_TRY((hipError_t)spl_dev_launch_genome_headers(text, base, d_lines.as<uint32_t>(), n_lines, last_end, win.hi, d_nb.as<uint32_t>(), d_hdr.as<uint32_t>(), seq_open ? 1 : 0,
                                                           d_headers.as<spl_genome_header>(), d_counts.as<spl_genome_counts>(), st));
         headers.resize(n_hdr);
@@ -5548,7 +5561,7 @@ struct GenomeLoad {
         HIP_TRY(hipMemcpyAsync(&counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         // ---- the sequences the headers end and begin; every piece of a sequence in this window is a segment
-        const uint64_t bad_line = counts.first_bad == none ? ~0ull : (counts.first_bad >> 8);
+        const FirstBad declined(counts.first_bad);
         segs.clear();
         uint32_t wb = 0;
         auto piece = [&](uint32_t upto) {
@@ -5557,24 +5570,24 @@ struct GenomeLoad {
             wb = upto;
         };
         for (const spl_genome_header &h : headers) {
-            if ((uint64_t)h.line > bad_line) break; // (the first line the rule declines is the one that is reported)
+            if (declined.any && (uint64_t)h.line > declined.line) break; // (the first line the rule declines is the one that is reported)
             piece(h.bases_before);
             const std::string name((const char *)image + h.name_at, h.name_len);
-            if (h.name_len && name_seen(name)) return bad(SPL_FASTA_REPEATED_NAME, lines_before + h.line + 1);
+            if (h.name_len && !seen.insert(name).second) return bad(SPL_FASTA_REPEATED_NAME, lines_before + h.line + 1);
             if (seq_open) g->used = cur_dst + 16u * ((cur_len + 31u) / 32u);
             seq_open = true;
             cur_len = 0;
             cur_dst = g->used;
             g->names.push_back(name); g->length.push_back(0); g->dst.push_back(cur_dst);
         }
-        if (bad_line != ~0ull) return bad((int)(counts.first_bad & 0xffu), lines_before + bad_line + 1);
+        if (declined.any) return bad((int)declined.reason, lines_before + declined.line + 1);
         piece(n_bases);
         uint32_t n_groups = 0;
         for (spl_genome_segment &s : segs) { s.group_first = n_groups; n_groups += (uint32_t)((s.seq_first + s.n + 31u) / 32u - s.seq_first / 32u); }
         const uint64_t end = seq_open ? cur_dst + 16u * ((cur_len + 31u) / 32u) : 0;
         { const int rc = room(end); if (rc) return rc; }
         if (!segs.empty()) {
-            if (segs.size() > cap_segs) { d_segs.release(); cap_segs = 0; HIP_TRY(d_segs.get(sizeof(spl_genome_segment) * (segs.size() + segs.size() / 8), st)); cap_segs = segs.size() + segs.size() / 8; }
+            if (sizeof(spl_genome_segment) * segs.size() > d_segs.room) HIP_TRY(d_segs.ensure(sizeof(spl_genome_segment) * (segs.size() + segs.size() / 8), st));
             HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), sizeof(spl_genome_segment) * segs.size(), hipMemcpyHostToDevice, st));
             splprof::Scope prof("spl_genome_pack_kernel", st, 1.5 * (double)n_bases); // a byte read and half a byte written a base
             HIP_TRY((hipError_t)spl_dev_launch_genome_pack(text, base, d_lines.as<uint32_t>(), n_lines, d_nb.as<uint32_t>(), d_segs.as<spl_genome_segment>(), (uint32_t)segs.size(),

@@ -6,7 +6,7 @@
 // the nibbles behind a sequence's last base are 0.
 //
 // A WINDOW of the text in device memory holds whole lines (bytes [lo, hi) of the file, `text` indexed with whole-file offsets as
-// in spl_sam.h, whose line-start launchers find the lines).  Then
+// in spl_sam.h; the windows are spl_text_windows.h's, the lines are found by the LineIndex the SAM decoders use).  Then
 //   classify   a lane per line: header, bases or empty (hdr[i] = 1 for a header), the bases of the line (nb[i]), the first line
 //              the rule declines;
 //   (the caller's inclusive prefix sums of nb and hdr: spl_dev_launch_sort_scan)

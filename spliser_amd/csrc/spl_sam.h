@@ -1,8 +1,8 @@
-// spl_sam.h -- SAM text on the device: the launchers of spl_sam.hip and what they exchange with the host (spl_capi.cpp: SamDecode).
+// spl_sam.h -- SAM text on the device: the launchers of spl_sam.hip and what they exchange with the host (spl_capi.cpp: SamDecode; the line starts: LineIndex, for every text source).
 //
 // The second decoder behind spl_bam: where spl_inflate.hip makes POS, FLAG, the CIGAR offsets and words and the strand byte from
 // the inflated BAM stream, these make them from the text an aligner writes, by the one rule of spl_sam_line.h.  Everything works
-// on a WINDOW of the text in device memory that holds whole lines: bytes [lo, hi) of the file, `text` indexed with whole-file
+// on a WINDOW of the text in device memory that holds whole lines (spl_text_windows.h): bytes [lo, hi) of the file, `text` indexed with whole-file
 // offsets (the caller passes the buffer's address minus the offset of its first byte, which is lo rounded down to 16: the
 // kernels' 16-byte loads are aligned in the file and in memory alike).  Loads stay inside [lo & ~15, (hi + 15) & ~15): the
 // buffer is SPL_SAM_PAD bytes longer than the window.

@@ -52,7 +52,7 @@ EXPORTS = [
     "spl_reads_upload", "spl_reads_upload_segments", "spl_reads_begin", "spl_reads_begin_sized", "spl_reads_add", "spl_reads_add2", "spl_reads_add_bam", "spl_reads_add_bam_share", "spl_reads_finish",
     "spl_soa_upload", "spl_soa_upload2", "spl_soa_upload3", "spl_soa_upload4", "spl_reads_has_strand", "spl_reads_has_mate_keys", "spl_soa_free", "spl_reads_add_soa", "spl_reads_relayout", "spl_layout_timing_collect", "spl_reads_layout_bytes", "spl_reads_slots_download",
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
-    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_set_mate_keys", "spl_bam_mate_keys", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
+    "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_set_mate_keys", "spl_bam_mate_keys", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_text_windows_host", "spl_text_line_index", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
     "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_junctions_fragments", "spl_junction_fragment_rule_host", "spl_strand_tally", "spl_strand_rule_host", "spl_genome_open", "spl_genome_n", "spl_genome_name", "spl_genome_bases", "spl_genome_stats", "spl_genome_free", "spl_genome_pack_host", "spl_reads_motif_strand", "spl_motif_read_strand_host", "spl_junction_motifs", "spl_junction_motifs_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_coverage_fragments", "spl_coverage_fragment_totals", "spl_intron_depth_fragments", "spl_coverage_fragment_rule_host", "spl_coverage_cursor_host", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_lanes_plan_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
@@ -1181,6 +1181,33 @@ def sort_keys_device(ctx, keys, key_bits):
     perm = np.zeros(len(keys), np.uint32)
     _check(lib().spl_sort_keys_device(ctx._h, _ptr(keys) if len(keys) else None, ctypes.c_int64(len(keys)), ctypes.c_int(int(key_bits)), _ptr(perm) if len(keys) else None))
     return perm
+
+
+TEXT_WINDOWS_STOP, TEXT_WINDOWS_OWN = 0, 1     # what becomes of a line that fits no window: SAM text's rule, FASTA's
+
+
+def text_windows_host(text, begin, win_bytes, rule):
+    """How the device's text sources cut bytes [begin, len(text)) into windows of whole lines (``spl_text_windows_host``, no GPU)
+    -> ([(lo, hi)], whether a line that fits no window ended the plan)."""
+    buf = np.frombuffer(bytes(text), np.uint8)
+    n, long_line = ctypes.c_int64(0), ctypes.c_int(0)
+    cuts = np.zeros(2 * (buf.size + 1), np.int64)          # (a window holds a byte at least)
+    _check(lib().spl_text_windows_host(_ptr(buf) if buf.size else None, ctypes.c_int64(buf.size), ctypes.c_int64(int(begin)), ctypes.c_int64(int(win_bytes)), ctypes.c_int(int(rule)),
+                                       ctypes.c_int64(buf.size + 1), _ptr(cuts), ctypes.byref(n), ctypes.byref(long_line)))
+    return [(int(cuts[2 * k]), int(cuts[2 * k + 1])) for k in range(n.value)], bool(long_line.value)
+
+
+def text_line_index(ctx, text, windows):
+    """The line starts of ``windows`` [(lo, hi)] of ``text`` by ONE of the decoders' line-index objects, in that order
+    (``spl_text_line_index``) -> per window (line starts as offsets from lo & ~15, uint32; the lines the index then had room for)."""
+    buf = np.frombuffer(bytes(text), np.uint8)
+    lo, hi = _arr([w[0] for w in windows], np.int64), _arr([w[1] for w in windows], np.int64)
+    cap = max(int(sum(h - l for l, h in windows)), 0)              # (a line holds a byte at least, except a window's last)
+    n_lines, room, starts = np.zeros(max(len(windows), 1), np.int64), np.zeros(max(len(windows), 1), np.int64), np.zeros(cap + len(windows) + 1, np.uint32)
+    _check(lib().spl_text_line_index(ctx._h, _ptr(buf) if buf.size else None, ctypes.c_int64(buf.size), ctypes.c_int64(len(windows)), _ptr(lo), _ptr(hi),
+                                     ctypes.c_int64(starts.size), _ptr(n_lines), _ptr(room), _ptr(starts)))
+    ends = np.cumsum(n_lines[:len(windows)])
+    return [(starts[int(e - n):int(e)].copy(), int(r)) for e, n, r in zip(ends, n_lines, room)]
 
 
 def flagstat_add_host(flag, tid, next_tid, mapq, counters=None):
