@@ -115,6 +115,18 @@ def expected(rs, seq, shift=0):
     return out, tally
 
 
+def table_by_strand(rs, bytes_, shift=0):
+    """The mode-3 junction table the strand bytes imply: {(left, right, strand byte or '?'): supporting reads}, from the walk above."""
+    rows, off = {}, rs.cig_off.astype(np.int64)
+    for i in range(rs.n):
+        if rs.flag[i] & 4 or rs.pos[i] < 0:
+            continue
+        for l, r in junctions_of(int(rs.pos[i]) + shift, rs.cigar[off[i]:off[i + 1]]):
+            key = (l, r, int(bytes_[i]) or 63)
+            rows[key] = rows.get(key, 0) + 1
+    return rows
+
+
 def expected_xs_tags(rs, seq):
     """The aux area (``XS:A`` or nothing) the rule gives every read, for ``samio.write_bam(tags=...)``."""
     return [b"XSA+" if b == 43 else b"XSA-" if b == 45 else b"" for b in expected(rs, seq)[0]]

@@ -12,7 +12,18 @@ runs the list in ONE process, writes each case's raw results to ``DIR/<case>.npz
 ``end <case>`` to ``DIR/progress.log`` around it, and at the end the pool's statistics and two probes' bytes (``DIR/pool.json``,
 ``DIR/probes.npz``).  With ``--twice`` it runs the list forward and then once more in reverse order, the second pass under
 ``DIR/second/``.  It computes no expectation: test_gpu_poisoned_memory.py starts it as a child and compares what it left with
-``want_of``; test_poisoncases_host.py checks on the CPU that every yardstick is non-trivial and that ``mismatches`` can fail."""
+``want_of``; test_poisoncases_host.py checks on the CPU that every yardstick is non-trivial and that ``mismatches`` can fail.
+
+The list: the counting pass at its limits, the BAM decode with every switch and in shares, SAM text and BGZF SAM text, one finished set
+under every per-read consumer, the junction table, ``process`` and ``combine`` end to end; and what has been built since the list
+was first written, where buffers are reused, regrown and double-buffered inside ONE call: the genome packed at windows of 0, 65536
+and 4096 bytes in turn (the same ``DevBuf``s at three sizes; sequences joined inside a 16-byte word the windows share) and under a
+store that grows beneath joined sequences (``regrow`` moves what the windows before stored, no more); the motif kernel on one fused
+set whose strand bytes all go up wrong, called twice (a tally buffer that is not cleared shows doubled, or as 0xA5), its table and
+``spl_junction_motifs``; every ``fragments=True`` consumer on one set with name keys and strand bytes; the text cases again at
+``SPL_SAM_WINDOW_BYTES=4096`` -- fifteen windows where the default is one: two text buffers in turn, ``LineIndex`` and the per-line
+arrays regrown, the carry of the compressed readers --, plain gzip besides; ``junctions --strandFromMotif`` with text and FASTA in
+such windows; and two shards' passes side by side on the two lanes of one context, the mode changing every step."""
 import atexit
 import hashlib
 import json
@@ -31,7 +42,9 @@ for _p in (ROOT, HERE):
         sys.path.insert(0, _p)
 
 import covcases as C                      # noqa: E402
+import covfragcases as CF                 # noqa: E402
 import exoncases as E                     # noqa: E402
+import exonfragcases as EF                # noqa: E402
 import filtercases as F                   # noqa: E402
 import flagstatcases as fc                # noqa: E402
 import genecases as G                     # noqa: E402
@@ -39,9 +52,11 @@ import introncases as I                   # noqa: E402
 import junctioncases as J                 # noqa: E402
 import limitcases as L                    # noqa: E402
 import matecases as M                     # noqa: E402
+import motifcases as MO                   # noqa: E402
 import ordercases as O                    # noqa: E402
 import samzcases as Z                     # noqa: E402
 import strandcases as S                   # noqa: E402
+import windowcases as W                   # noqa: E402
 import xscases as X                       # noqa: E402
 from spliser_amd import samio             # noqa: E402
 
@@ -602,6 +617,506 @@ def _combine_nontrivial(inp, w):
     assert len(lines) > 20 and len(lines[0].split("\t")) > 6
 
 
+# ---- the genome on the device: one set of buffers at three window sizes, and a store that grows under joined sequences ----------------
+GENOME_WINDOWS = (0, 65536, 4096)          # in this order, in one process: the same DevBufs are asked for three different sizes
+
+
+def _genome_pack_build(workdir):
+    os.makedirs(workdir, exist_ok=True)
+    path = os.path.join(workdir, "corpus.fa")
+    with open(path, "wb") as fh:
+        fh.write(MO.pack_corpus())
+    return dict(path=path)
+
+
+def _genome_pack_run(ctx, inp, outdir):
+    from spliser_amd import native
+    out = {}
+    for window in GENOME_WINDOWS:
+        tag = "window%d_" % window
+        with native.Genome(ctx, inp["path"], window) as g:
+            out[tag + "names"] = "\n".join(g.names).encode("utf-8", "surrogateescape")
+            out[tag + "lengths"] = np.asarray(g.lengths, np.int64)
+            out[tag + "bases"] = np.concatenate([g.bases(k) for k in range(len(g.names))])
+            out[tag + "device_bytes"] = np.array([g.stats()["device_bytes"]], np.int64)
+    return out
+
+
+def _genome_pack_want(inp):
+    seqs = MO.parse_fasta(open(inp["path"], "rb").read())
+    out = {}
+    for window in GENOME_WINDOWS:
+        tag = "window%d_" % window
+        out[tag + "names"] = b"\n".join(n for n, _ in seqs)
+        out[tag + "lengths"] = np.array([len(c) for _, c in seqs], np.int64)
+        out[tag + "bases"] = np.concatenate([c for _, c in seqs])
+        out[tag + "device_bytes"] = np.array([sum(16 * ((len(c) + 31) // 32) for _, c in seqs)], np.int64)
+    return out
+
+
+def _genome_pack_nontrivial(inp, w):
+    text = open(inp["path"], "rb").read()
+    assert len(text) == 559453 and w["window0_lengths"].shape[0] == 71 and int(np.count_nonzero(w["window0_lengths"] == 0)) >= 1
+    joined = MO.sequences_joined_across(text, 4096)
+    assert len(joined) >= 100 and len({n % 32 for _, n in joined if n % 32}) >= 8          # joins inside a word of the store, at many phases
+    assert len(MO.sequences_joined_across(text, 65536)) >= 5
+
+
+GROW_N, GROW_WINDOW = 300000, 65536
+
+
+def _joined_across(text, window):
+    """``motifcases.sequences_joined_across`` for a text whose only '>' begin its headers, with the sequence's index: the cuts of
+    ``motifcases.window_cuts`` that fall inside a sequence -> [(index, its bases in front of the cut)].  (Parsed from the sequence's
+    own header on, not from the text's first byte: the same answer for a text of 600 000 lines in a second.)"""
+    out = []
+    for cut in MO.window_cuts(text, window):
+        rest = text[cut:].lstrip(b"\r\n")
+        if rest[:1] in (b">", b""):
+            continue
+        out.append((text.count(b">", 0, cut) - 1, len(MO.parse_fasta(text[text.rfind(b">", 0, cut):cut])[-1][1])))
+    return out
+
+
+def _grow_build(workdir):
+    """test_the_store_grows_under_many_short_sequences' recipe -- 300 000 sequences of one or two bases under names of at most four
+    letters, 16 bytes of store each where the store is first given a quarter more than half the file -- with a sequence of a few
+    hundred bases over short lines mixed in every thousand, and one more wherever a window of 64 KiB is about to end: that one the
+    cut falls into, so nearly every window joins a sequence, most of them in a store that has already grown."""
+    os.makedirs(workdir, exist_ok=True)
+    rng = np.random.default_rng(4)
+    names = [np.base_repr(k, 36).lower().encode() for k in range(GROW_N)]
+    bases = MO.random_bases(rng, 2 * GROW_N)
+    t, lo = bytearray(), 0          # lo: where the window that is open began
+    for k in range(GROW_N):
+        if k % 1000 == 500 or len(t) > lo + GROW_WINDOW - 40:
+            t.extend(MO.fasta_text([(names[k], MO.random_bases(rng, int(rng.integers(200, 600)), plain=True))], width=int(rng.integers(5, 20))))
+        else:
+            t.extend(b">" + names[k] + b"\n" + bases[2 * k:2 * k + (2 if k % 31 == 0 else 1)] + b"\n")
+        if len(t) > lo + GROW_WINDOW:
+            lo = t.rfind(b"\n", lo, lo + GROW_WINDOW) + 1
+    text = bytes(t)
+    path = os.path.join(workdir, "short.fa")
+    with open(path, "wb") as fh:
+        fh.write(text)
+    return dict(path=path, joined=np.asarray(_joined_across(text, GROW_WINDOW), np.int64).reshape(-1, 2))
+
+
+def _grow_sampled():
+    return list(range(0, 64)) + list(range(64, GROW_N, 997)) + [GROW_N - 1]
+
+
+def _grow_run(ctx, inp, outdir):
+    from spliser_amd import native
+    out = {}
+    with native.Genome(ctx, inp["path"], GROW_WINDOW) as g:
+        out["n_names"] = np.array([len(g.names)], np.int64)
+        out["lengths"] = np.asarray(g.lengths, np.int64)
+        out["device_bytes"] = np.array([g.stats()["device_bytes"]], np.int64)
+        out["bases_sampled"] = np.concatenate([g.bases(k) for k in _grow_sampled()])
+        out["bases_joined"] = np.concatenate([g.bases(int(k)) for k in inp["joined"][:, 0]])
+    return out
+
+
+def _grow_want(inp):
+    seqs = MO.parse_fasta(open(inp["path"], "rb").read())
+    lengths = np.array([len(c) for _, c in seqs], np.int64)
+    return {"n_names": np.array([len(seqs)], np.int64), "lengths": lengths, "device_bytes": np.array([int((16 * ((lengths + 31) // 32)).sum())], np.int64),
+            "bases_sampled": np.concatenate([seqs[k][1] for k in _grow_sampled()]), "bases_joined": np.concatenate([seqs[int(k)][1] for k in inp["joined"][:, 0]])}
+
+
+def _grow_nontrivial(inp, w):
+    size, lengths, joined = os.path.getsize(inp["path"]), w["lengths"], inp["joined"]
+    assert lengths.shape[0] == GROW_N and 16 * GROW_N > 2 * (size // 2 + 4096) + (2 << 20)          # the store must grow: no rounding of the first allocation holds it
+    need = size // 2 + 4096
+    first = (max(need + need // 4, 4096) + 255) // 256 * 256          # the first allocation, as GenomeLoad::room makes it
+    assert int(w["device_bytes"][0]) > 2 * first
+    place = np.concatenate(([0], np.cumsum(16 * ((lengths + 31) // 32))))          # 16 bytes per 32 bases, cumulative
+    beyond = [(k, n) for k, n in joined.tolist() if n % 32 and place[k] + 16 * (n // 32) >= first]
+    assert len(beyond) >= 5 and len({n % 32 for _, n in beyond}) >= 4, beyond          # joined at a non-zero phase, in a word beyond the first allocation
+    assert any(place[k] + 16 * (n // 32) < first for k, n in joined.tolist())                # ... and before the store grew, too
+    assert all(lengths[k] >= 200 for k, _ in joined.tolist()) and int((lengths >= 200).sum()) >= 300
+
+
+# ---- the motif kernel: one fused set, its strand bytes written over twice, the tally, the table the bytes imply ----------------------------
+MOTIF_CASES = ("planted", "random")
+MOTIF_SHIFT = 700
+
+
+def _motif_extra(n):
+    """The six out-of-range rows of test_junction_motifs_of_a_table for a sequence of n bases."""
+    return [(-5, 40), (-1, 30), (n - 10, n + 1), (n, n + 50), (10, 12), (2147483000, 2147483600)]
+
+
+def _motif_build(workdir):
+    os.makedirs(workdir, exist_ok=True)
+    made = dict(planted=MO.planted_case(), random=MO.random_case(20261021, 5000))
+    path = os.path.join(workdir, "two.fa")
+    with open(path, "wb") as fh:
+        fh.write(MO.fasta_text([(b"planted", made["planted"][0]), (b"none", b""), (b"random", made["random"][0])], width=61))
+    out = dict(fasta=path)
+    for name in MOTIF_CASES:
+        bases, rs, juncs = made[name]
+        right = MO.expected(rs, MO.codes_of(bases))[0]
+        out[name] = dict(bases=bases, rs=rs, juncs=np.asarray(juncs, np.int64), wrong=np.where(right == 45, 43, 45).astype(np.uint8))          # every byte goes up wrong
+    return out
+
+
+def _rows4(table):
+    return np.asarray([r[:4] for r in J.rows(table)], np.int64).reshape(-1, 4)
+
+
+def _motif_run(ctx, inp, outdir):
+    from spliser_amd import native
+    out = {}
+    with native.Genome(ctx, inp["fasta"]) as g:
+        for name in MOTIF_CASES:
+            rs, wrong, juncs = inp[name]["rs"], inp[name]["wrong"], inp[name]["juncs"].tolist()
+            with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, xs=wrong)], with_strand=True) as soa:
+                with ctx.begin_reads() as dr:
+                    dr.add_soa(soa, 0)
+                    dr.finish()
+                    out[name + "_tally"] = dr.motif_strand(g, name)
+                    out[name + "_tally_again"] = dr.motif_strand(g, name)          # (a tally buffer that is not cleared: doubled, or 0xA5)
+                    out[name + "_table"] = _rows4(dr.junctions(native.STRAND_FROM_XS, 0, 0, 0))
+                    out[name + "_strand_tally"] = dr.strand_tally()
+                    out[name + "_record_bytes"] = np.array([dr.layout_bytes()[1]], np.int64)
+            with ctx.upload_soa([native.ReadArrays(rs.pos - MOTIF_SHIFT, rs.flag, rs.cig_off, rs.cigar, xs=wrong)], with_strand=True) as soa:
+                with ctx.begin_reads() as dr:
+                    dr.add_soa(soa, 0, MOTIF_SHIFT)
+                    dr.finish()
+                    out[name + "_shifted_tally"] = dr.motif_strand(g, g.index(name))
+                    out[name + "_shifted_table"] = _rows4(dr.junctions(native.STRAND_FROM_XS, 0, 0, 0))
+            rows = juncs + _motif_extra(len(inp[name]["bases"]))
+            out[name + "_junction_motifs"] = g.junction_motifs(name, [l for l, _ in rows], [r for _, r in rows])
+    return out
+
+
+def _table_of_bytes(rs, bytes_, shift=0):
+    return np.asarray([k + (n,) for k, n in sorted(MO.table_by_strand(rs, bytes_, shift).items())], np.int64).reshape(-1, 4)
+
+
+def _motif_want(inp):
+    out = {}
+    for name in MOTIF_CASES:
+        rs, seq = inp[name]["rs"], MO.codes_of(inp[name]["bases"])
+        bytes_, tally = MO.expected(rs, seq)
+        out[name + "_tally"] = out[name + "_tally_again"] = out[name + "_shifted_tally"] = tally
+        out[name + "_table"] = _table_of_bytes(rs, bytes_)
+        # (the table takes a read by its own POS, which the shift has moved below 1 for the first of them; the motif kernel by POS + shift)
+        out[name + "_shifted_table"] = _table_of_bytes(samio.ReadSet(rs.pos - MOTIF_SHIFT, rs.flag, rs.cig_off, rs.cigar), bytes_, MOTIF_SHIFT)
+        out[name + "_strand_tally"] = np.asarray(S.tally(rs, bytes_), np.int64)
+        out[name + "_record_bytes"] = np.zeros(1, np.int64)          # the set stays fused
+        rows = inp[name]["juncs"].tolist() + _motif_extra(len(seq))
+        out[name + "_junction_motifs"] = np.array([MO.motif_code(seq, l, r)[0] for l, r in rows], np.int64)
+    return out
+
+
+def _motif_nontrivial(inp, w):
+    bytes_ = MO.expected(inp["random"]["rs"], MO.codes_of(inp["random"]["bases"]))[0]
+    t = w["random_tally"]
+    assert min(int((bytes_ == 43).sum()), int((bytes_ == 45).sum()), int(t[9]), int(t[10])) >= 100, t          # +, -, conflicting, no canonical motif
+    for name in MOTIF_CASES:
+        right = MO.expected(inp[name]["rs"], MO.codes_of(inp[name]["bases"]))[0]
+        assert not (inp[name]["wrong"] == right).any()
+        assert {43, 45, 63} == set(w[name + "_table"][:, 2].tolist()) and set(range(7)) == set(w[name + "_junction_motifs"].tolist())
+    assert int(w["planted_tally"][11]) > 0 and int(w["planted_strand_tally"][2:8].sum()) > 0          # a junction beyond the sequence's end
+
+
+# ---- one finished set with name keys and strand bytes: the fragment consumers in turn ----------------------------------------------------
+FRAG_BASES = CF.LENGTH + 200          # (the planted pair past LENGTH ends at LENGTH + 20: the per-base yardsticks of the counts look this far)
+FRAG_GENES = 9
+FRAG_INTRON_LENGTH = CF.LENGTH - 900
+FRAG_CALLS = 22                       # the calls of _fragset_run that are followed by a look at the records' bytes
+
+
+def _fragset_build(workdir):
+    rng = np.random.default_rng(20261022)
+    rs, keys, _ = CF.paired_content(rng)
+    _, xs = X.make_tags(rng, rs)
+    features = G.random_features(rng, CF.LENGTH - 700, FRAG_GENES, 30)
+    return dict(rs=rs, keys=keys, xs=xs, features=features)
+
+
+def _fragset_run(ctx, inp, outdir):
+    from spliser_amd import exoncounts as xc, genecounts as gc, native
+    rs, xs, keys, features = inp["rs"], inp["xs"], inp["keys"], inp["features"]
+    out, records_bytes = {}, []
+    a, _ = gc.gene_maps(*_arrays(features))
+    bin_map, _, (bin_gene, _, _) = xc.exon_maps(*_arrays(features), stranded=False)
+    introns = [x[3] for x in I.introns_of(features, ".", FRAG_INTRON_LENGTH)]
+
+    def seen():
+        records_bytes.append(dr.layout_bytes()[1])
+
+    def coverage(tag, *args, **kw):
+        start, end, depth, t = dr.coverage(CF.LENGTH, *args, **kw)
+        out[tag + "_start"], out[tag + "_end"], out[tag + "_depth"] = start, end, depth
+        out[tag + "_totals"] = np.array([t[k] for k in (native.COVERAGE_FRAGMENT_TOTALS if kw else native.COVERAGE_TOTALS)], np.int64)
+        seen()
+
+    with ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar, xs=xs, name_key=keys)], with_strand=True, with_keys=True) as soa:
+        with ctx.begin_reads() as dr:
+            dr.add_soa(soa, 0)
+            dr.finish()
+            seen()
+            coverage("coverage")
+            coverage("coverage_fragments", fragments=True)
+            coverage("coverage_fragments_fr_plus", 1, "+", fragments=True)
+            for stranded in (0, 1, native.STRAND_FROM_XS):
+                for k, knobs in enumerate(CF.KNOBS):
+                    out["junctions_fragments_s%d_knobs%d" % (stranded, k)] = _rows(J.rows(dr.junctions(stranded, *knobs, fragments=True))); seen()
+            for trim in TRIMS:
+                out["intron_depth_fragments_trim%d" % trim] = dr.intron_depth(FRAG_INTRON_LENGTH, *_tables(introns), trim_percent=trim, fragments=True); seen()
+            out["exon_counts_fragments"] = dr.exon_counts(bin_gene.astype(np.uint32), bin_map, fragments=True); seen()
+            out["exon_counts"] = dr.exon_counts(bin_gene.astype(np.uint32), bin_map); seen()
+            out["gene_counts_fragments"] = dr.gene_counts(FRAG_GENES, a, fragments=True); seen()
+            out["gene_counts"] = dr.gene_counts(FRAG_GENES, a); seen()
+            mate, counts = dr.mate_table(0, rs.n); seen()
+            out["mate"], out["mate_counts"] = mate, np.array([counts[k] for k in native.MATE_COUNTS], np.int64)
+            out["junctions"] = _rows(J.rows(dr.junctions(0))); seen()
+            out["junctions_from_xs"] = _rows(J.rows(dr.junctions(native.STRAND_FROM_XS))); seen()
+            coverage("coverage_again")
+            coverage("coverage_fragments_again", fragments=True)
+    out["record_bytes_after_every_call"] = np.asarray(records_bytes, np.int64)
+    return out
+
+
+def _fragset_want(inp):
+    from spliser_amd import exoncounts as xc
+    oracle = _oracle()
+    rs, xs, keys, features = inp["rs"], inp["xs"], inp["keys"], inp["features"]
+    mate, counts = M.mate_table_of(rs, keys)
+    out = {"mate": np.asarray(mate, np.int64), "mate_counts": np.array([counts[k] for k in ("pairable", "paired", "unpaired_mate_mapped")], np.int64)}
+    depth, totals = C.depth_of(rs, CF.LENGTH)
+    start, end, value = C.runs_of(depth)
+    out["coverage_start"], out["coverage_end"], out["coverage_depth"], out["coverage_totals"] = start, end, value, np.array([start.shape[0]] + totals, np.int64)
+    for tag, args in (("coverage_fragments", ()), ("coverage_fragments_fr_plus", (1, "+"))):
+        (start, end, value), totals = CF.want_of(rs, mate, CF.LENGTH, 0, *args)
+        out[tag + "_start"], out[tag + "_end"], out[tag + "_depth"], out[tag + "_totals"] = start, end, value, np.array(totals, np.int64)
+    for k in ("start", "end", "depth", "totals"):
+        out["coverage_again_" + k], out["coverage_fragments_again_" + k] = out["coverage_" + k], out["coverage_fragments_" + k]
+    for stranded in (0, 1, 3):
+        for k, knobs in enumerate(CF.KNOBS):
+            out["junctions_fragments_s%d_knobs%d" % (stranded, k)] = _rows(CF.table_rows(CF.junction_tables(rs, mate, stranded, knobs, xs=xs if stranded == 3 else None)[0]))
+    introns = [x[3] for x in I.introns_of(features, ".", FRAG_INTRON_LENGTH)]
+    per_fragment = CF.fragment_depth(rs, mate, FRAG_INTRON_LENGTH)[0]
+    for trim in TRIMS:
+        out["intron_depth_fragments_trim%d" % trim] = np.asarray([I.stats_of(per_fragment, pieces, trim) for pieces in introns], np.int64).reshape(-1, 4)
+    labels = E.labels_of_features(features, FRAG_BASES)
+    bins = E.bins_of([labels])
+    _, _, (bin_gene, bin_start, bin_end) = xc.exon_maps(*_arrays(features), stranded=False)
+    assert list(zip(bin_start.tolist(), bin_end.tolist(), bin_gene.tolist())) == bins          # (the product's bins are the yardstick's)
+    number_of = {k: i for i, k in enumerate(bins)}
+    out["exon_counts_fragments"] = np.asarray(EF.counts_of(EF.fragment_results(rs, keys, labels, mate=mate), number_of, len(bins)), np.int64)
+    out["exon_counts"] = np.asarray(E.counts_of(E.reads_of(rs, labels), number_of, len(bins)), np.int64)
+    bases = G.bases_of_features(features, FRAG_BASES)
+    out["gene_counts_fragments"] = np.asarray(M.counts_of(M.fragment_results(rs, keys, bases, mate=mate), FRAG_GENES), np.int64)
+    out["gene_counts"] = np.asarray(G.counts_of(G.results_of(rs, bases), FRAG_GENES), np.int64)
+    out["junctions"] = _rows(oracle.junction_table(rs.pos, rs.flag, rs.cig_off, rs.cigar, 0, 0, 0, 0))
+    out["junctions_from_xs"] = _rows(X.yardstick(rs, xs))
+    out["record_bytes_after_every_call"] = np.zeros(FRAG_CALLS, np.int64)          # the set stays fused: no records are ever written
+    return out
+
+
+def _fragset_nontrivial(inp, w):
+    rs, keys = inp["rs"], inp["keys"]
+    CF.assert_covers(rs, keys)
+    assert w["mate_counts"][1] // 2 > 100 and w["coverage_fragments_totals"][5] == w["mate_counts"][1] // 2          # pairs, and every pair's union taken
+    assert 0 < w["coverage_fragments_fr_plus_totals"][5] < w["coverage_fragments_totals"][5]
+    assert int(w["coverage_fragments_totals"][4]) < int(w["coverage_totals"][4]) and w["coverage_totals"][3] > 0      # fewer covered bases per fragment; reads past the end
+    assert not np.array_equal(C.expand(w["coverage_start"], w["coverage_end"], w["coverage_depth"], CF.LENGTH),
+                              C.expand(w["coverage_fragments_start"], w["coverage_fragments_end"], w["coverage_fragments_depth"], CF.LENGTH))
+    mate = [int(m) for m in w["mate"]]
+    for stranded in (0, 1):
+        for k, knobs in enumerate(CF.KNOBS):
+            frag, read, per_read = CF.junction_tables(rs, mate, stranded, knobs)
+            assert sum(1 for p in per_read if p and p[1]) >= 1, (stranded, knobs)          # a junction both mates support, counted once
+            assert len(frag) > 20 and sum(r[0] for r in frag.values()) < sum(r[0] for r in read.values())
+    assert {43, 45, 63} <= set(w["junctions_fragments_s3_knobs0"][:, 2].tolist())
+    n_bins = w["exon_counts"].shape[0] - 4
+    for k in ("exon_counts", "exon_counts_fragments"):
+        assert min(w[k][n_bins:].tolist()) > 0 and int(np.count_nonzero(w[k][:n_bins])) >= 8, k          # every special counter above zero
+    assert int(w["exon_counts_fragments"][:n_bins].sum()) < int(w["exon_counts"][:n_bins].sum())
+    assert min(w["gene_counts_fragments"][FRAG_GENES:].tolist()) > 0 and int(w["gene_counts_fragments"].sum()) == rs.n - w["mate_counts"][1] // 2
+    for trim in TRIMS:
+        t = w["intron_depth_fragments_trim%d" % trim]
+        assert t.shape[0] > 3 and int(t[:, 1].sum()) > 0
+
+
+# ---- text in many windows: SPL_SAM_WINDOW_BYTES = 4096 over the files of the text cases, and a command whose FASTA goes up so too ----------
+TEXT_WINDOW = 4096
+
+
+def _text_windows_build(workdir):
+    """_text_build's files, a plain-gzip copy of the text, and a BGZF copy in blocks of 1021 bytes: the one block of ``samz`` is one
+    window whatever the variable says, these are four to a window."""
+    inp = _text_build(workdir)
+    text = open(inp["sam"], "rb").read()
+    inp["samgz"], inp["samz_small"] = inp["sam"] + ".plain.gz", inp["sam"] + ".small.gz"
+    with open(inp["samgz"], "wb") as fh:
+        fh.write(Z.gz(text))
+    with open(inp["samz_small"], "wb") as fh:
+        fh.write(Z.bgzf(text))
+    return inp
+
+
+def _in_windows(run):
+    def inner(ctx, inp, outdir):
+        with _env(SPL_SAM_WINDOW_BYTES=TEXT_WINDOW):
+            return run(ctx, inp, outdir)
+    return inner
+
+
+def _fragments_bgzf_windows_run(ctx, inp, outdir):
+    out = _fragments_run("samz")(ctx, inp, outdir)
+    out["genecounts_of_small_blocks.tsv"] = _fragments_run("samz_small")(ctx, inp, outdir)["genecounts.tsv"]
+    return out
+
+
+def _fragments_bgzf_windows_want(inp):
+    text = _fragments_want(inp)["genecounts.tsv"]
+    return {"genecounts.tsv": text, "genecounts_of_small_blocks.tsv": text}
+
+
+def _n_text_windows(inp):
+    text = open(inp["sam"], "rb").read()
+    begin = 0
+    while text[begin:begin + 1] == b"@":
+        begin = text.index(b"\n", begin) + 1
+    plan, stopped = W.window_plan(text, begin, TEXT_WINDOW, W.STOP)
+    assert not stopped and max(len(line) for line in text.split(b"\n")) < TEXT_WINDOW // 8
+    return len(plan)
+
+
+def _text_windows_nontrivial(then):
+    def inner(inp, w):
+        assert _n_text_windows(inp) >= 8
+        import gzip
+        text = open(inp["sam"], "rb").read()
+        assert gzip.decompress(open(inp["samgz"], "rb").read()) == text and gzip.decompress(open(inp["samz_small"], "rb").read()) == text
+        assert open(inp["samz_small"], "rb").read().count(b"\x1f\x8b\x08\x04") > 4 * 8          # (BGZF blocks: many windows of them)
+        then(inp, w)
+    return inner
+
+
+E2E_NAMES = ["c1", "c2", "c3"]
+
+
+def _e2e_motif_build(workdir):
+    os.makedirs(workdir, exist_ok=True)
+    made = [MO.random_case(100 + k, 1200) for k in range(len(E2E_NAMES))]
+    sets = [(c, rs) for c, (_, rs, _) in zip(E2E_NAMES, made)]
+    bases = {c: b for c, (b, _, _) in zip(E2E_NAMES, made)}
+    sam, fasta = os.path.join(workdir, "plain.sam"), os.path.join(workdir, "g.fa")
+    samio.write_sam(sam, E2E_NAMES, [len(bases[c]) for c in E2E_NAMES], sets)
+    with open(fasta, "wb") as fh:          # (in another order than the header's, with a sequence nobody aligned to)
+        fh.write(MO.fasta_text([(b"c3", bases["c3"]), (b"extra", b"ACGTNNNN" * 40), (b"c1", bases["c1"]), (b"c2", bases["c2"])], width=70))
+    return dict(sam=sam, fasta=fasta, sets=sets, bases=[bases[c] for c in E2E_NAMES])
+
+
+def _e2e_motif_run(ctx, inp, outdir):
+    from spliser_amd import cli, process as proc
+    bed = os.path.join(outdir, "motif.bed")
+    with _env(SPL_SAM_WINDOW_BYTES=TEXT_WINDOW):          # (the SAM text's windows and the FASTA's: GenomeLoad's default window is the same variable)
+        if cli.main(["junctions", "-B", inp["sam"], "-o", bed, "--genome", inp["fasta"], "--strandFromMotif", "-a", "0", "-m", "0", "-M", "0"]) != 0:
+            raise RuntimeError("junctions --strandFromMotif failed")
+        proc.wait_deferred_close()
+    rows = []
+    for line in open(bed).read().splitlines()[1:]:
+        c = line.split("\t")
+        sizes = c[10].split(",")
+        rows.append((E2E_NAMES.index(c[0]), int(c[1]) + int(sizes[0]), int(c[2]) - int(sizes[1]), ord(c[5]), int(c[4])))
+    return {"bed_rows": np.asarray(rows, np.int64).reshape(-1, 5)}
+
+
+def _e2e_motif_want(inp):
+    rows = []
+    for k, ((_, rs), bases) in enumerate(zip(inp["sets"], inp["bases"])):
+        rows += [(k,) + tuple(r) for r in _table_of_bytes(rs, MO.expected(rs, MO.codes_of(bases))[0]).tolist()]
+    return {"bed_rows": np.asarray(rows, np.int64).reshape(-1, 5)}
+
+
+def _e2e_motif_nontrivial(inp, w):
+    rows = w["bed_rows"]
+    assert set(rows[:, 0].tolist()) == {0, 1, 2} and {43, 45, 63} == set(rows[:, 3].tolist()) and rows.shape[0] > 150 and int(rows[:, 4].max()) > 3
+    assert len(MO.window_cuts(open(inp["fasta"], "rb").read(), TEXT_WINDOW)) >= 8 and os.path.getsize(inp["sam"]) > 8 * TEXT_WINDOW
+    assert len(MO.sequences_joined_across(open(inp["fasta"], "rb").read(), TEXT_WINDOW)) >= 8
+
+
+# ---- two lanes: two shards' passes side by side on one context -----------------------------------------------------------------------
+LANE_MODES = [(0, 0), (1, 0), (2, 1), (1, 1)]          # (stranded, combine) of the four steps
+LANE_EARLY = 2                                          # the step whose first shard is read down before the barrier
+
+
+def _lanes_build(workdir):
+    return dict(cases=[L.tile_case("class_change_%d" % (L.TILE + 1)), L.window_case(L.WIN)])
+
+
+def _lanes_run(ctx, inp, outdir):
+    from spliser_amd import native
+    out, dev = {}, []
+
+    def results(step, n):
+        ds = dev[n][0]
+        for j, a in enumerate(ds.counters()):
+            out["step%d_shard%d_counter%d" % (step, n, j)] = np.asarray(a)
+        for j, a in enumerate(ds.sse_results()):
+            out["step%d_shard%d_sse%d" % (step, n, j)] = np.asarray(a)
+
+    with _env(SPL_FORCE_CHUNK=L.CHUNK):
+        try:
+            for case in inp["cases"]:
+                soa = ctx.upload_soa([native.ReadArrays(rs.pos, rs.flag, rs.cig_off, rs.cigar) for rs, _ in case.segments])
+                dev.append([None, None, soa])
+                dev[-1][0] = ctx.upload_sites(case.table.sites())
+                dev[-1][1] = ctx.layout_read_segments(soa, [shift for _, shift in case.segments])
+            for step, (stranded, combine) in enumerate(LANE_MODES):
+                for ds, dr, _ in dev:
+                    dr.relayout()
+                    ctx.count_launch(ds, dr, stranded, combine, 0)
+                    ctx.sse_launch(ds, (stranded + combine) % 2 == 0)
+                if step == LANE_EARLY:          # the second shard's pass still queued behind it
+                    results(step, 0)
+                ctx.pass_barrier()
+                for n in range(len(dev)):
+                    if not (step == LANE_EARLY and n == 0):
+                        results(step, n)
+            out["record_bytes"] = np.array([dr.layout_bytes()[1] for _, dr, _ in dev], np.int64)
+        finally:
+            ctx.sync()
+            for ds, dr, soa in dev:
+                for h in (dr, ds, soa):
+                    if h is not None:
+                        h.free()
+    return out
+
+
+def _lanes_want(inp):
+    oracle, out = _oracle(), {}
+    for n, case in enumerate(inp["cases"]):
+        t, r = case.table, case.reads
+        for step, (stranded, combine) in enumerate(LANE_MODES):
+            counts = oracle.check_bam(t.pos, t.strand, t.part_off, t.part_pos, t.comp_off, t.comp_pos, r.pos, r.flag, r.cig_off, r.cigar, stranded, combine)
+            sse = oracle.beta2_sse(t.pos, t.part_off, t.part_pos, t.part_site, t.alpha, t.edge_cnt, counts[0], counts[1], counts[2], (stranded + combine) % 2 == 0)
+            for j, a in enumerate(counts):
+                out["step%d_shard%d_counter%d" % (step, n, j)] = np.asarray(a)
+            for j, a in enumerate(sse):
+                out["step%d_shard%d_sse%d" % (step, n, j)] = np.asarray(a)
+    out["record_bytes"] = np.zeros(len(inp["cases"]), np.int64)          # both sets are fused
+    return out
+
+
+def _lanes_nontrivial(inp, w):
+    tile, window = inp["cases"]
+    assert tile.reads.n > L.CHUNK and tile.reads.n > L.TILE and window.table.n > L.WIN          # more than one chunk and one tile; more than one window
+    assert len(set(LANE_MODES)) == len(LANE_MODES) and all(a != b for a, b in zip(LANE_MODES, LANE_MODES[1:]))
+    for step in range(len(LANE_MODES)):
+        for n in (0, 1):
+            assert int(w["step%d_shard%d_counter0" % (step, n)].sum()) > 0 and int(w["step%d_shard%d_counter1" % (step, n)].sum()) > 0, (step, n)
+    assert any(not np.array_equal(w["step0_shard%d_counter%d" % (n, j)], w["step1_shard%d_counter%d" % (n, j)]) for n in (0, 1) for j in (0, 1, 2))          # the mode matters
+
+
 # ---- the list -----------------------------------------------------------------------------------------------------------------
 def cases():
     out = [_count_case(k, name, make) for k, (name, make) in enumerate(COUNT_CASES)]
@@ -614,6 +1129,18 @@ def cases():
     out += [_junction_case(name) for name in ("record_classes", "wave_merge", "hash")]
     out.append(PCase("end_to_end_process_kat2", lambda workdir: {}, _kat2_run, _kat2_want, _kat2_nontrivial))
     out.append(PCase("end_to_end_combine_a", lambda workdir: {}, _combine_run, _combine_want, _combine_nontrivial))
+    # what came after the list was first written: the genome, the motif kernel, the fragment variants, text in many windows, two lanes
+    out.append(PCase("genome_pack_windows", _genome_pack_build, _genome_pack_run, _genome_pack_want, _genome_pack_nontrivial))
+    out.append(PCase("genome_store_growth", _grow_build, _grow_run, _grow_want, _grow_nontrivial))
+    out.append(PCase("motif_one_set", _motif_build, _motif_run, _motif_want, _motif_nontrivial))
+    out.append(PCase("one_set_fragment_consumers", _fragset_build, _fragset_run, _fragset_want, _fragset_nontrivial))
+    out.append(PCase("text_windows_fragments_sam", _text_windows_build, _in_windows(_fragments_run("sam")), _fragments_want, _text_windows_nontrivial(_fragments_nontrivial)))
+    out.append(PCase("text_windows_fragments_bgzf_sam", _text_windows_build, _in_windows(_fragments_bgzf_windows_run), _fragments_bgzf_windows_want,
+                     _text_windows_nontrivial(_fragments_nontrivial)))
+    out.append(PCase("text_windows_fragments_gzip_sam", _text_windows_build, _in_windows(_fragments_run("samgz")), _fragments_want, _text_windows_nontrivial(_fragments_nontrivial)))
+    out.append(PCase("text_windows_coverage_sam", _text_windows_build, _in_windows(_text_coverage_run), _text_coverage_want, _text_windows_nontrivial(_text_coverage_nontrivial)))
+    out.append(PCase("end_to_end_junctions_from_motif", _e2e_motif_build, _e2e_motif_run, _e2e_motif_want, _e2e_motif_nontrivial))
+    out.append(PCase("lanes_two_shards", _lanes_build, _lanes_run, _lanes_want, _lanes_nontrivial))
     return out
 
 

@@ -141,18 +141,6 @@ def _strands(ctx, genome, seq, rs, shift=0):
             return tally, dr.junctions(XS3, 0, 0, 0), int(dr.strand_tally()[2:8].sum())
 
 
-def _table_by_strand(rs, bytes_, shift=0):
-    """The mode-3 table the bytes imply: (left, right, strand byte) -> supporting reads, from the restatement's walk."""
-    rows, off = {}, rs.cig_off.astype(np.int64)
-    for i in range(rs.n):
-        if rs.flag[i] & 4 or rs.pos[i] < 0:
-            continue
-        for l, r in M.junctions_of(int(rs.pos[i]) + shift, rs.cigar[off[i]:off[i + 1]]):
-            key = (l, r, int(bytes_[i]) or 63)
-            rows[key] = rows.get(key, 0) + 1
-    return rows
-
-
 @pytest.mark.parametrize("name", ["planted", "random"])
 def test_strand_bytes_and_tally_are_the_restatement(ctx, motif_cases, name):
     genome, cases = motif_cases
@@ -162,7 +150,7 @@ def test_strand_bytes_and_tally_are_the_restatement(ctx, motif_cases, name):
     tally, table, tagged = _strands(ctx, genome, name, rs)
     assert tally.tolist() == want_tally.tolist()
     got = {(int(l), int(r), int(s)): int(c) for l, r, s, c in zip(table["left"], table["right"], table["strand"], table["count"])}
-    assert got == _table_by_strand(rs, want)
+    assert got == M.table_by_strand(rs, want)
     assert tagged == int(((want != 0) & ((rs.flag & ELIGIBLE_OFF) == 0)).sum())
     # ... and with the reads moved by a shift
     arrays = native.ReadArrays(rs.pos - 700, rs.flag, rs.cig_off, rs.cigar, xs=np.full(rs.n, 43, np.uint8))

@@ -9,6 +9,11 @@ compared here with the yardsticks of the single suites, exactly.  A child that d
 with the tail of its output and of ``progress.log``, which names the case; the second child is then not started, and nothing is
 run again.
 
+The list covers the counting pass, the decodes, SAM text, every consumer of a finished set -- per read and per fragment --, the
+junction table, the genome on the device (three window sizes on one set of buffers; a store that grows under joined sequences), the
+motif kernel's strand bytes and tally, text, compressed text and FASTA in windows of 4096 bytes, two shards on two lanes, and the
+commands end to end; poisoncases.py says what each case is there for.
+
 Positive controls keep either mode from passing without having happened: the poisoned child's pool says that every buffer was
 poisoned and a probe of 3 MiB + 1 bytes comes back as 4 MiB of 0xA5, a second one -- served from the pool -- again; the other
 child's pool poisoned nothing and served more buffers from what it held during the second pass than before it."""

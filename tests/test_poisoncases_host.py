@@ -17,8 +17,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_names_are_unique_and_the_list_covers_every_path():
     assert len(set(P.NAMES)) == len(P.NAMES)
-    for prefix, n in (("count_", 8), ("decode_", 2), ("text_", 3), ("one_set_", 1), ("junctions_", 3), ("end_to_end_", 2)):
+    for prefix, n in (("count_", 8), ("decode_", 2), ("text_", 7), ("text_windows_", 4), ("one_set_", 2), ("junctions_", 3), ("end_to_end_", 3), ("genome_", 2),
+                      ("motif_", 1), ("lanes_", 1)):
         assert sum(1 for name in P.NAMES if name.startswith(prefix)) == n, prefix
+    assert len(P.NAMES) == 29
     assert all(name.replace("_", "").isalnum() for name in P.NAMES)          # (they are file names)
 
 
@@ -98,8 +100,9 @@ def test_the_comparator_rejects_one_changed_entry_of_every_result(name):
 
 
 def test_the_comparator_on_the_kinds_the_issue_names():
-    """One counter, one run boundary, one mate word, one byte of a file, one word of an SSE -- and what is equal stays equal through
-    the file the driver writes: NaN, uint64 name keys, integers of any width."""
+    """One counter, one run boundary, one mate word, one byte of a file, one word of an SSE, one base code, one counter of the motif
+    tally, one row of a BED -- and what is equal stays equal through the file the driver writes: NaN, uint64 name keys, integers of
+    any width."""
     w = P.want_of("one_set_every_consumer")
     for key in ("gene_counts", "coverage_start", "mate", "strand_tally", "junctions", "record_bytes_after_every_call"):
         got = dict(w)
@@ -126,6 +129,26 @@ def test_the_comparator_on_the_kinds_the_issue_names():
     assert d["a_name_key"].dtype == np.uint64 and int(d["a_name_key"][0]) > 2 ** 63          # (beyond int64: compared as it is)
     got = dict(d, a_name_key=d["a_name_key"] ^ np.uint64(1))
     assert [b.split(":")[0] for b in P.mismatches(got, d)] == ["a_name_key"]
+    # one base code of a packed genome, one counter of the motif tally, one row of a BED (its strand byte, then its score)
+    g = P.want_of("genome_pack_windows")
+    got = dict(g, window4096_bases=g["window4096_bases"].copy())
+    k = int(np.flatnonzero(got["window4096_bases"] == 1)[1000])
+    got["window4096_bases"][k] = 2          # an A read as a C
+    bad = P.mismatches(got, g)
+    assert len(bad) == 1 and bad[0].startswith("window4096_bases: 1 of %d entries differ, the first at %d: 2 where 1 was expected" % (g["window4096_bases"].size, k))
+    m = P.want_of("motif_one_set")
+    for key in ("random_tally", "random_tally_again", "planted_strand_tally"):
+        got = dict(m)
+        got[key] = m[key].copy()
+        got[key][7 if key.endswith("tally_again") else 1] *= 2          # (what a tally buffer that is not cleared gives)
+        assert [b.split(":")[0] for b in P.mismatches(got, m)] == [key]
+    e = P.want_of("end_to_end_junctions_from_motif")
+    for column, other in ((3, 63), (4, 0)):
+        got = {"bed_rows": e["bed_rows"].copy()}
+        row = int(np.flatnonzero(e["bed_rows"][:, 3] == 43)[0])
+        got["bed_rows"][row, column] = other
+        assert len(P.mismatches(got, e)) == 1
+    assert "shape" in P.mismatches({"bed_rows": e["bed_rows"][1:]}, e)[0]
 
 
 def test_results_come_back_from_the_drivers_file_as_they_went_in(tmp_path):
