@@ -4408,7 +4408,7 @@ extern "C" int spl_junction_fragment_rule_host(int64_t n_reads, const int32_t *p
     if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_junction_fragment_rule_host: cigar is null");
     if (min_anchor < 0 || min_intron < 0 || max_intron < 0) return spl_set_error(SPL_ERR_ARG, "spl_junction_fragment_rule_host: negative filter value");
     if (stranded < 0 || stranded > 3 || (stranded == 3 && n_reads && !xs)) return spl_set_error(SPL_ERR_ARG, "spl_junction_fragment_rule_host: stranded must be 0, 1, 2 or 3 (with strand bytes)");
-    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    const spl_read_view reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
     const spljw::Filter filter{(uint32_t)min_anchor, (uint32_t)min_intron, (uint32_t)max_intron};
     struct Keep {
         int stranded; int64_t cap, n, counted, dup; int64_t *rows;
@@ -4668,7 +4668,6 @@ extern "C" int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t
     if ((n_ops && !ops) || !n_out || capacity < 0 || (capacity && (!blk_start || !blk_end))) return spl_set_error(SPL_ERR_ARG, "spl_coverage_rule_host: null argument");
     if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_coverage_rule_host: length must be in 1 .. 2^31 - 2");
     if (!spl_cov_args_fit(stranded, strand)) return spl_set_error(SPL_ERR_ARG, "spl_coverage_rule_host: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2");
-    struct HostOps { const uint32_t *p; uint32_t operator()(uint32_t k) const { return p[k]; } };
     struct Keep {
         int capacity, n; int64_t *s, *e;
         void operator()(int64_t a, int64_t b) { if (n < capacity) { s[n] = a; e[n] = b; } ++n; }
@@ -4676,7 +4675,7 @@ extern "C" int spl_coverage_rule_host(uint32_t flag, int32_t pos, const uint32_t
     uint32_t bits = 0;
     if (spl_cov_eligible(flag, (int64_t)pos, n_ops) && spl_cov_on_track(flag, stranded, strand)) {
         int64_t covered = 0;
-        bits = spl_cov_walk(HostOps{ops}, n_ops, (int64_t)pos - 1 + (int64_t)shift, length, keep, &covered);
+        bits = spl_cov_walk(spl_ops_ptr{ops}, n_ops, (int64_t)pos - 1 + (int64_t)shift, length, keep, &covered);
     }
     *n_out = keep.n;
     if (past_end_out) *past_end_out = (bits & SPL_COV_PAST_END) ? 1 : 0;
@@ -5068,7 +5067,7 @@ extern "C" int spl_coverage_fragment_rule_host(int64_t n_reads, const int32_t *p
     if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_rule_host: cigar is null");
     if (length < 1 || length > SPL_COV_LENGTH_MAX) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_rule_host: length must be in 1 .. 2^31 - 2");
     if (!spl_cov_args_fit(stranded, strand)) return spl_set_error(SPL_ERR_ARG, "spl_coverage_fragment_rule_host: strand must be 0 with stranded = 0, and '+' or '-' with stranded = 1 or 2");
-    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    const spl_read_view reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
     struct Keep {
         int64_t cap, used, n; int64_t *s, *e;
         void operator()(int64_t a, int64_t b) { if (used < cap) { s[used] = a; e[used] = b; ++used; } ++n; }
@@ -5083,7 +5082,7 @@ extern "C" int spl_coverage_fragment_rule_host(int64_t n_reads, const int32_t *p
         if (what != SPL_COVF_LEADS) { status_out[r] = what == SPL_COVF_SILENT ? -4 : -3; continue; }
         keep.n = 0;
         int64_t covered = 0;
-        const uint32_t bits = spl_cov_fragment_walk<spl_gene_ops_ptr>(cigar, lead, other, length, keep, &covered);
+        const uint32_t bits = spl_cov_fragment_walk<spl_ops_ptr>(cigar, lead, other, length, keep, &covered);
         n_iv_out[r] = keep.n;
         status_out[r] = (bits & SPL_COV_CONTRIBUTED) ? 1 : 0;
         if (past_out) past_out[r] = (bits & SPL_COV_PAST_END) ? 1 : 0;
@@ -5108,7 +5107,7 @@ extern "C" int spl_coverage_cursor_host(uint32_t flag, int32_t pos, const uint32
     int n = 0;
     uint32_t bits = 0;
     if (spl_cov_eligible(flag, (int64_t)pos, n_ops) && spl_cov_on_track(flag, stranded, strand)) {
-        spl_cov_cursor<spl_gene_ops_ptr> cursor(spl_gene_ops_ptr{ops}, n_ops, (int64_t)pos - 1 + (int64_t)shift, length);
+        spl_cov_cursor<spl_ops_ptr> cursor(spl_ops_ptr{ops}, n_ops, (int64_t)pos - 1 + (int64_t)shift, length);
         for (int64_t s, e; cursor.next(&s, &e); ++n)
             if (n < capacity) { blk_start[n] = s; blk_end[n] = e; }
         bits = cursor.bits;
@@ -5174,10 +5173,10 @@ extern "C" int spl_gene_fragment_rule_host(int64_t n_reads, const int32_t *pos, 
     if (n_reads < 0 || (n_reads && (!pos || !flag || !cig_off || !mate || !results_out))) return spl_set_error(SPL_ERR_ARG, "spl_gene_fragment_rule_host: null argument");
     if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_gene_fragment_rule_host: cigar is null");
     if (const int rc = gene_maps_fit("spl_gene_fragment_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_genes)) return rc;
-    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    const spl_read_view reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
     const spl_gene_map_flat map_a{n_a, a_start, a_code}, map_b{n_b, b_start, b_code};
     for (int64_t r = 0; r < n_reads; ++r) {
-        const uint32_t v = spl_gene_fragment_result<spl_gene_ops_ptr>(reads, 0, n_reads, r, mate, (int64_t)shift, stranded, map_a, map_b);
+        const uint32_t v = spl_gene_fragment_result<spl_ops_ptr>(reads, 0, n_reads, r, mate, (int64_t)shift, stranded, map_a, map_b);
         results_out[r] = v == SPL_GENE_NO_FEATURE ? -1 : v == SPL_GENE_AMBIGUOUS ? -2 : v == SPL_GENE_NOT_COUNTED ? -3 : v == SPL_GENE_IDLE ? -4 : (int64_t)v;
     }
     return SPL_OK;
@@ -5248,7 +5247,7 @@ extern "C" int spl_exon_fragment_rule_host(int64_t n_reads, const int32_t *pos, 
         return spl_set_error(SPL_ERR_ARG, "spl_exon_fragment_rule_host: null argument");
     if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_exon_fragment_rule_host: cigar is null");
     if (const int rc = exon_maps_fit("spl_exon_fragment_rule_host", stranded, n_a, a_start, a_code, n_b, b_start, b_code, n_bins, bin_gene)) return rc;
-    const spl_mate_reads reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    const spl_read_view reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
     const spl_gene_map_flat map_a{n_a, a_start, a_code}, map_b{n_b, b_start, b_code};
     int64_t used = 0;
     for (int64_t r = 0; r < n_reads; ++r) {
@@ -5342,13 +5341,12 @@ extern "C" int spl_junction_walk_host(const uint32_t *ops, uint32_t n_ops, int32
 {
     if ((n_ops && !ops) || !n_out) return spl_set_error(SPL_ERR_ARG, "spl_junction_walk_host: null argument");
     if (min_anchor < 0 || min_intron < 0 || max_intron < 0) return spl_set_error(SPL_ERR_ARG, "spl_junction_walk_host: negative filter value");
-    struct HostOps { const uint32_t *p; uint32_t operator()(uint32_t k) const { return p[k]; } };
     const spljw::Filter f{(uint32_t)min_anchor, (uint32_t)min_intron, (uint32_t)max_intron};
     spljw::Walk w;
     w.begin(pos);
     spljw::Junction j;
     int n = 0;
-    while (spljw::next(w, HostOps{ops}, n_ops, f, j)) {
+    while (spljw::next(w, spl_ops_ptr{ops}, n_ops, f, j)) {
         if (n < capacity) {
             if (left) left[n] = j.l;
             if (right) right[n] = j.r;
@@ -5778,13 +5776,6 @@ extern "C" int spl_reads_motif_strand(spl_ctx *c, spl_dreads *dr, const spl_geno
     return SPL_OK;
 }
 
-namespace {
-struct HostOps {
-    const uint32_t *p;
-    uint32_t operator()(uint32_t k) const { return p[k]; }
-};
-} // namespace
-
 // The rule over host arrays and a sequence with a code a byte: no GPU involved (test hook).
 extern "C" int spl_motif_read_strand_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, int64_t n_ops_total, int32_t shift,
                                           const uint8_t *codes, int64_t length, uint8_t *strand_out, int64_t *tally_out)
@@ -5793,10 +5784,10 @@ extern "C" int spl_motif_read_strand_host(int64_t n_reads, const int32_t *pos, c
         return spl_set_error(SPL_ERR_ARG, "spl_motif_read_strand_host: bad argument");
     memset(tally_out, 0, 8 * SPL_MOTIF_TALLY);
     for (int64_t i = 0; i < n_reads; ++i) {
-        uint32_t c0, c1;
-        splmotif::ops_span(cig_off, i, n_ops_total, c0, c1);
+        uint32_t c0, n_ops;
+        spl_ops_of(cig_off, i, n_ops_total, &c0, &n_ops);
         splmotif::ReadMotifs m;
-        splmotif::read_motifs((uint32_t)flag[i], (int64_t)pos[i] + shift, HostOps{cigar + c0}, c1 - c0, splmotif::BytePairs{codes}, length, m);
+        splmotif::read_motifs((uint32_t)flag[i], (int64_t)pos[i] + shift, spl_ops_ptr{cigar + c0}, n_ops, splmotif::BytePairs{codes}, length, m);
         strand_out[i] = m.strand;
         for (int k = 0; k < 7; ++k) tally_out[k] += m.walks[k];
         if (m.cls) tally_out[m.cls] += 1;

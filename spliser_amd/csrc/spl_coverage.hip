@@ -8,8 +8,8 @@
 //          a lane, in whatever order the reads are.  A lane walks its read's ops where they lie and adds, per clipped block
 //          [s, e), +1 at diff[s] and -1 at diff[e] -- uint32 words, sums mod 2^32 (exact while the depth is below 2^32), plain
 //          device-scope atomics whose value nobody waits for.  Three predicates a read (seen, contributed, past the end) are
-//          counted by ballot and popcount, lane c of a wave keeping counter c; the covered bases are summed per lane and across
-//          the wave at the end; the waves meet in LDS, and a workgroup ends with one 64-bit atomicAdd per counter.
+//          counted by the predicate tally of spl_tally_dev.h; the covered bases are summed per lane and across the wave at the end, an atomic
+//          a wave.
 // compact  Depth changes exactly where diff[i] != 0, i in [0, length).  Pass 1 counts those words per tile of SPL_COV_POS_TILE
 //          positions, a 16-byte load a lane; the tile counts are scanned (spl_dev_launch_sort_scan: the caller); pass 2 reads
 //          the tiles again and writes (position, delta) in ascending order, a word's place being its tile's offset, the words of
@@ -26,18 +26,13 @@
 #include "spl_coverage.h"
 #include "spl_coverage_rule.h"
 #include "spl_covfragment_rule.h" // a fragment's rule: spl_cov_mark_fragments_kernel
+#include "spl_tally_dev.h"       // PredicateTally, wave_add64; wv::lane
 
 namespace {
 
 constexpr uint32_t WAVES = SPL_COV_TILE / 64;
 static_assert(SPL_COV_POS_TILE == 4 * SPL_COV_TILE, "compact: four positions a lane, SPL_COV_TILE lanes");
 
-__device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-struct DevOps {
-    const uint32_t *p;
-    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return p[k]; }
-};
 struct DiffMark {
     uint32_t *diff;
     __device__ __forceinline__ void operator()(int64_t s, int64_t e) const
@@ -50,13 +45,9 @@ struct DiffMark {
 __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_mark_kernel(const spl_devreads src, int64_t n_ops_total, int64_t first, int64_t n, int32_t shift, int64_t length, int stranded,
                                                                      int strand, uint32_t *diff, unsigned long long *out)
 {
-    __shared__ unsigned long long s_sum[SPL_COV_COUNTERS + 1];
     const uint32_t t = threadIdx.x;
-    const uint32_t lane = lane_id();
-    if (t < SPL_COV_COUNTERS + 1) s_sum[t] = 0ull;
-    __syncthreads();
-    uint32_t mine = 0;          // lane c of a wave: the wave's reads that add to counter c (32 bits hold any read set's share of a wave)
     unsigned long long bases = 0; // this lane's covered bases
+    PredicateTally<SPL_COV_COUNTERS> tally;
     const DiffMark mark{diff};
     for (int64_t base = (int64_t)blockIdx.x * SPL_COV_TILE; base < n; base += (int64_t)gridDim.x * SPL_COV_TILE) { // (uniform over the workgroup)
         const int64_t r = base + t;
@@ -65,28 +56,24 @@ __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_mark_kernel(const spl_de
             const int64_t i = first + r;
             const uint32_t flag = src.flag[i];
             const int64_t pos = (int64_t)src.pos[i];
-            uint32_t c0 = src.cig_off[i], c1 = src.cig_off[i + 1];
-            if (c1 < c0 || (int64_t)c1 > n_ops_total) c1 = c0; // (offsets of the arrays' own ops: said for the memory's sake)
+            uint32_t c0, n_ops;
+            spl_ops_of(src.cig_off, i, n_ops_total, &c0, &n_ops);
             bits = SPL_COV_SEEN;
-            if (spl_cov_eligible(flag, pos, c1 - c0) && spl_cov_on_track(flag, stranded, strand)) {
+            if (spl_cov_eligible(flag, pos, n_ops) && spl_cov_on_track(flag, stranded, strand)) {
                 int64_t covered = 0;
-                bits |= spl_cov_walk(DevOps{src.cigar + c0}, c1 - c0, pos - 1 + (int64_t)shift, length, mark, &covered);
+                bits |= spl_cov_walk(spl_ops_ptr{src.cigar + c0}, n_ops, pos - 1 + (int64_t)shift, length, mark, &covered);
                 bases += (unsigned long long)covered;
             }
         }
-#pragma unroll
-        for (uint32_t c = 0; c < SPL_COV_COUNTERS; ++c) {
-            const unsigned long long b = __ballot((bits >> c) & 1u);
-            if (lane == c) mine += (uint32_t)__popcll(b);
-        }
+        tally.add(bits);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bases += __shfl_xor(bases, d, 64);
-    if (lane < SPL_COV_COUNTERS && mine) atomicAdd(&s_sum[lane], (unsigned long long)mine);
-    if (lane == SPL_COV_COUNTERS && bases) atomicAdd(&s_sum[SPL_COV_COUNTERS], bases);
-    __syncthreads();
-    if (t < SPL_COV_COUNTERS + 1 && s_sum[t]) atomicAdd(&out[t], s_sum[t]);
+    tally.finish(out);
+    wave_add64(&out[SPL_COV_COUNTERS], bases);
 }
+
+struct FragmentSlots { // out: the per-read kernel's four sums where they were, and the pairs behind them
+    __device__ __forceinline__ uint32_t operator()(uint32_t c) const { return c < SPL_COV_COUNTERS ? c : SPL_COV_COUNTERS + 1; }
+};
 
 // Fragments (spl_coverage_fragments): the same launch over the segment with its mate table (spl_mates.hip) beside the arrays, the
 // same diff array and atomics.  A lane first asks whether its read's mate takes part in the call -- a dependent load of the mate's
@@ -96,14 +83,10 @@ __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_mark_kernel(const spl_de
 __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_mark_fragments_kernel(const spl_devreads src, int64_t n_ops_total, int64_t first, int64_t n, int32_t shift, int64_t length,
                                                                                int stranded, int strand, const uint32_t *mate, uint32_t *diff, unsigned long long *out)
 {
-    __shared__ unsigned long long s_sum[SPL_COVF_COUNTERS + 1];
     const uint32_t t = threadIdx.x;
-    const uint32_t lane = lane_id();
-    if (t < SPL_COVF_COUNTERS + 1) s_sum[t] = 0ull;
-    __syncthreads();
-    const spl_mate_reads reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
-    uint32_t mine = 0;            // (as in the per-read kernel)
+    const spl_read_view reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
     unsigned long long bases = 0; // this lane's covered bases
+    PredicateTally<SPL_COVF_COUNTERS> tally;
     DiffMark mark{diff};
     for (int64_t base = (int64_t)blockIdx.x * SPL_COV_TILE; base < n; base += (int64_t)gridDim.x * SPL_COV_TILE) { // (uniform over the workgroup)
         const int64_t r = base + t;
@@ -113,23 +96,14 @@ __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_mark_fragments_kernel(co
             spl_cov_side lead, other;
             if (spl_cov_fragment_sides(reads, first, n, r, mate, (int64_t)shift, stranded, strand, &lead, &other) == SPL_COVF_LEADS) {
                 int64_t covered = 0;
-                bits |= spl_cov_fragment_walk<DevOps>(src.cigar, lead, other, length, mark, &covered);
+                bits |= spl_cov_fragment_walk<spl_ops_ptr>(src.cigar, lead, other, length, mark, &covered);
                 bases += (unsigned long long)covered;
             }
         }
-#pragma unroll
-        for (uint32_t c = 0; c < SPL_COVF_COUNTERS; ++c) {
-            const unsigned long long b = __ballot((bits >> c) & 1u);
-            if (lane == c) mine += (uint32_t)__popcll(b);
-        }
+        tally.add(bits);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bases += __shfl_xor(bases, d, 64);
-    // out: the per-read kernel's four sums where they were, and the pairs behind them
-    if (lane < SPL_COVF_COUNTERS && mine) atomicAdd(&s_sum[lane < SPL_COV_COUNTERS ? lane : SPL_COV_COUNTERS + 1], (unsigned long long)mine);
-    if (lane == SPL_COVF_COUNTERS && bases) atomicAdd(&s_sum[SPL_COV_COUNTERS], bases);
-    __syncthreads();
-    if (t < SPL_COVF_COUNTERS + 1 && s_sum[t]) atomicAdd(&out[t], s_sum[t]);
+    tally.finish(out, FragmentSlots{});
+    wave_add64(&out[SPL_COV_COUNTERS], bases);
 }
 
 // The four words of this lane's load of tile `tile`, those at or beyond `length` as zero: bit k of the result = word k is not zero.
@@ -144,7 +118,7 @@ __device__ __forceinline__ uint32_t load_tile_words(const uint32_t *diff, int64_
 __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_count_kernel(const uint32_t *diff, int64_t length, int64_t n_tiles, uint32_t *tile_count)
 {
     __shared__ uint32_t s_wave[WAVES];
-    const uint32_t t = threadIdx.x, lane = lane_id(), wave = t >> 6;
+    const uint32_t t = threadIdx.x, lane = wv::lane(), wave = t >> 6;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) { // (uniform over the workgroup)
         uint4 w;
         const uint32_t nz = load_tile_words(diff, length, tile, t, w);
@@ -166,7 +140,7 @@ __global__ __launch_bounds__(SPL_COV_TILE) void spl_cov_emit_kernel(const uint32
                                                                      int64_t n_out)
 {
     __shared__ uint32_t s_wave[WAVES];
-    const uint32_t t = threadIdx.x, lane = lane_id(), wave = t >> 6;
+    const uint32_t t = threadIdx.x, lane = wv::lane(), wave = t >> 6;
     const unsigned long long in_front = lane ? (~0ull >> (64u - lane)) : 0ull; // the lanes below this one
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) { // (uniform over the workgroup)
         uint4 w;

@@ -25,6 +25,7 @@
 #define SPL_COV_CONTRIBUTED 2u
 #define SPL_COV_PAST_END 4u
 #define SPL_COV_LENGTH_MAX 2147483646ll // 2^31 - 2: every block end fits an int32, and so does length + 1
+#define SPL_BLOCK_NONE 0x7FFFFFFFFFFFFFFFll // no block is open: above every position a walk reaches
 
 SPL_HD bool spl_cov_eligible(uint32_t flag, int64_t pos, uint32_t n_ops) { return (flag & 0x4u) == 0u && pos >= 1 && n_ops >= 1u; }
 
@@ -37,34 +38,66 @@ SPL_HD bool spl_cov_args_fit(int stranded, int strand)
 
 SPL_HD bool spl_cov_on_track(uint32_t flag, int stranded, int strand) { return stranded == 0 || (int)spl_read_strand(flag, stranded) == strand; }
 
-// The clipped blocks of one read that is eligible and on the track: emit(s, e) for each, 0 <= s < e <= length, ascending.
-// ops(k) = the read's k-th op (BAM form).  -> SPL_COV_* bits without SPL_COV_SEEN; *covered_out = the bases the blocks hold.
+// THE BLOCK WALK, stated once, an op a step: a read's blocks [s, e), ascending, disjoint and not clipped, from p in int64.  Every
+// op that advances either covers or is a gap, so p is always the open block's end: a covering op lengthens the open block or
+// opens one at p, a gap or the read's end closes it.  Whoever walks feeds the read's ops in turn (BAM form) and then its end.
+struct spl_block_walk {
+    int64_t p, bs; // the open block is [bs, p); bs == SPL_BLOCK_NONE: none is open
+    SPL_HD explicit spl_block_walk(int64_t p0) : p(p0), bs(SPL_BLOCK_NONE) {}
+    // at_end: the read's end, `op` is nothing.  -> true: a block ended here, [*s, *e).
+    SPL_HD bool feed(bool at_end, uint32_t op, int64_t *s, int64_t *e)
+    {
+        int64_t len = 0; // (the read's end: a gap of no length)
+        if (!at_end) {
+            len = (int64_t)(op >> 4);
+            if (len == 0 || !((SPL_PROG_MASK >> (op & 15u)) & 1u)) return false;
+            if ((SPL_MAPPED_MASK >> (op & 15u)) & 1u) { // covers: abuts the open block, or opens one
+                if (bs == SPL_BLOCK_NONE) bs = p;
+                p += len;
+                return false;
+            }
+        }
+        const bool ended = bs != SPL_BLOCK_NONE; // the open block ends here
+        if (ended) { *s = bs; *e = p; bs = SPL_BLOCK_NONE; }
+        p += len;
+        return ended;
+    }
+};
+
+// The walk, clipped and resumable: next() gives the read's clipped blocks one by one, 0 <= s < e <= length, ascending and disjoint;
+// bits gathers SPL_COV_PAST_END as the walk meets it (complete once next() has said false).  ops(k) = the read's k-th op.
+template <class Ops>
+struct spl_cov_cursor {
+    Ops ops;
+    uint32_t n_ops, k, bits; // k: the next op (n_ops + 1: the walk is over)
+    int64_t length;
+    spl_block_walk walk;
+    SPL_HD spl_cov_cursor(const Ops &o, uint32_t n, int64_t p0, int64_t len) : ops(o), n_ops(n), k(0u), bits(0u), length(len), walk(p0) {}
+    SPL_HD bool next(int64_t *s, int64_t *e)
+    {
+        while (k <= n_ops) {
+            const uint32_t at = k++;
+            int64_t bs, be;
+            if (!walk.feed(at == n_ops, at < n_ops ? ops(at) : 0u, &bs, &be)) continue;
+            *s = bs < 0 ? 0 : bs;
+            *e = be > length ? length : be;
+            if (*s != bs || *e != be) bits |= SPL_COV_PAST_END; // the clipping took a base
+            if (*e > *s) return true;
+        }
+        return false;
+    }
+};
+
+// The clipped blocks of one read that is eligible and on the track: emit(s, e) for each, ascending.  -> SPL_COV_* bits without
+// SPL_COV_SEEN; *covered_out = the bases the blocks hold.
 template <class Ops, class Emit>
 SPL_HD uint32_t spl_cov_walk(const Ops &ops, uint32_t n_ops, int64_t p, int64_t length, Emit &emit, int64_t *covered_out)
 {
-    uint32_t bits = 0u;
-    int64_t covered = 0, bs = 0, be = 0; // the open block [bs, be); bs == be: none
-    for (uint32_t k = 0; k <= n_ops; ++k) {
-        int64_t len = 0;
-        bool covers = false;
-        if (k < n_ops) {
-            const uint32_t op = ops(k);
-            len = (int64_t)(op >> 4);
-            if (len == 0 || !((SPL_PROG_MASK >> (op & 15u)) & 1u)) continue;
-            covers = ((SPL_MAPPED_MASK >> (op & 15u)) & 1u) != 0u;
-        }
-        if (covers && be > bs && p == be) { be += len; p += len; continue; } // abuts the open block
-        if (be > bs) { // the open block ends here
-            const int64_t s = bs < 0 ? 0 : bs, e = be > length ? length : be;
-            if (s != bs || e != be) bits |= SPL_COV_PAST_END;
-            if (e > s) { emit(s, e); covered += e - s; bits |= SPL_COV_CONTRIBUTED; }
-            bs = be = 0;
-        }
-        if (covers) { bs = p; be = p + len; }
-        p += len;
-    }
+    spl_cov_cursor<Ops> blocks(ops, n_ops, p, length);
+    int64_t covered = 0, s, e;
+    while (blocks.next(&s, &e)) { emit(s, e); covered += e - s; }
     *covered_out = covered;
-    return bits;
+    return blocks.bits | (covered ? SPL_COV_CONTRIBUTED : 0u);
 }
 
 #endif // SPL_COVERAGE_RULE_H

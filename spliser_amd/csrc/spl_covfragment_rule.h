@@ -21,9 +21,9 @@
 //   either read lost a base to the clipping, and its covered bases are the union's length.
 // A read's leader depends on the reads' order; the union does not, nor do the counters: a pair contributes once, whichever leads.
 //
-// NOTHING STORED PER LANE.  One read's clipped blocks ascend and are disjoint (spl_cov_cursor: spl_cov_walk as a resumable cursor,
-// block for block), so a fragment's union is the two-way merge of two block cursors: hold both heads, take the one that starts
-// first, and let it lengthen the open interval or close it.
+// NOTHING STORED PER LANE.  One read's clipped blocks ascend and are disjoint (spl_cov_cursor, spl_coverage_rule.h), so a
+// fragment's union is the two-way merge of two block cursors: hold both heads, take the one that starts first, and let it
+// lengthen the open interval or close it.
 #ifndef SPL_COVFRAGMENT_RULE_H
 #define SPL_COVFRAGMENT_RULE_H
 
@@ -39,43 +39,6 @@
 #define SPL_COVF_SILENT SPL_FRAG_SILENT
 #define SPL_COVF_LEADS SPL_FRAG_LEADS // to be walked: a fragment's leader, or a read without a partner
 
-// spl_cov_walk, resumable: next() gives the read's clipped blocks one by one, 0 <= s < e <= length, ascending and disjoint; bits
-// gathers SPL_COV_PAST_END as the walk meets it (complete once next() has said false).  A read of no op gives nothing.
-template <class Ops>
-struct spl_cov_cursor {
-    Ops ops;
-    uint32_t n_ops, k, bits;
-    int64_t p, length, bs, be; // the open block [bs, be); bs == be: none
-
-    SPL_HD spl_cov_cursor(const Ops &o, uint32_t n, int64_t p0, int64_t len) : ops(o), n_ops(n), k(0u), bits(0u), p(p0), length(len), bs(0), be(0) {}
-
-    SPL_HD bool next(int64_t *s_out, int64_t *e_out)
-    {
-        while (k <= n_ops) {
-            int64_t len = 0;
-            bool covers = false;
-            if (k < n_ops) {
-                const uint32_t op = ops(k);
-                len = (int64_t)(op >> 4);
-                if (len == 0 || !((SPL_PROG_MASK >> (op & 15u)) & 1u)) { ++k; continue; }
-                covers = ((SPL_MAPPED_MASK >> (op & 15u)) & 1u) != 0u;
-            }
-            if (covers && be > bs && p == be) { be += len; p += len; ++k; continue; } // abuts the open block
-            if (be > bs) { // the open block ends here; op k is looked at again by the next turn, with no block open
-                const int64_t s = bs < 0 ? 0 : bs, e = be > length ? length : be;
-                if (s != bs || e != be) bits |= SPL_COV_PAST_END;
-                bs = be = 0;
-                if (e > s) { *s_out = s; *e_out = e; return true; }
-                continue;
-            }
-            if (covers) { bs = p; be = p + len; }
-            p += len;
-            ++k;
-        }
-        return false;
-    }
-};
-
 // The coverage's predicate: a read takes part when it is eligible and on the call's track.
 struct spl_cov_takes {
     int stranded, strand;
@@ -87,7 +50,7 @@ typedef spl_frag_side spl_cov_side;
 
 // What read r of the n reads of a segment is to the call: SPL_COVF_NOT_PARTICIPATING, SPL_COVF_SILENT or SPL_COVF_LEADS
 // (spl_fragment_sides; a mate that does not take part is no partner).
-SPL_HD uint32_t spl_cov_fragment_sides(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, int strand, spl_cov_side *lead,
+SPL_HD uint32_t spl_cov_fragment_sides(const spl_read_view &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, int strand, spl_cov_side *lead,
                                        spl_cov_side *other)
 {
     return spl_fragment_sides<true>(s, first, n, r, mate, shift, spl_cov_takes{stranded, strand}, lead, other);

@@ -23,7 +23,7 @@
 #include "spl_exoncount_rule.h"
 #include "spl_exoncount_wave.h"
 #include "spl_exonfragment_rule.h" // a fragment's rule: spl_exon_count_fragments_kernel
-#include "spl_genemap_dev.h"       // DevMap, DevOps, CountFrame, count_launch_fits
+#include "spl_genemap_dev.h"       // DevMap, CountFrame, count_launch_fits
 
 static_assert(splexon::VERDICTS == SPL_EXON_VERDICTS && splexon::IDLE_VERDICT == SPL_EXON_IDLE && SPL_EXON_COUNTED == 0u && SPL_EXON_NO_FEATURE == 1u && SPL_EXON_AMBIGUOUS == 2u &&
                   SPL_EXON_NOT_COUNTED == 3u,
@@ -34,7 +34,7 @@ namespace {
 
 // A lane's bins for splexon::wave_commit: the second walk of a counted read; a lane without one has no op to walk.
 struct LaneBins {
-    spl_exon_hits<DevOps, DevMap> hits;
+    spl_exon_hits<spl_ops_ptr, DevMap> hits;
     __device__ __forceinline__ uint32_t next() { return spl_exon_next_bin(hits, splexon::NO_BIN); }
 };
 
@@ -51,19 +51,18 @@ __global__ __launch_bounds__(SPL_EXON_TILE) void spl_exon_count_kernel(const spl
             const int64_t i = first + r;
             const uint32_t flag = src.flag[i];
             const int64_t pos = (int64_t)src.pos[i];
-            c0 = src.cig_off[i];
-            uint32_t c1 = src.cig_off[i + 1];
-            if (c1 < c0 || (int64_t)c1 > n_ops_total) c1 = c0; // (offsets of the arrays' own ops: said for the memory's sake)
+            uint32_t its_ops;
+            spl_ops_of(src.cig_off, i, n_ops_total, &c0, &its_ops);
             verdict = SPL_EXON_NOT_COUNTED;
-            if (spl_gene_eligible(flag, pos, c1 - c0)) {
-                n_ops = c1 - c0;
+            if (spl_gene_eligible(flag, pos, its_ops)) {
+                n_ops = its_ops; // (a read that is not eligible is not walked)
                 p = pos - 1 + (int64_t)shift;
                 if (spl_gene_uses_b(flag, stranded)) map = f.map_b;
-                verdict = spl_exon_verdict(DevOps{src.cigar + c0}, n_ops, p, map, bin_gene);
+                verdict = spl_exon_verdict(spl_ops_ptr{src.cigar + c0}, n_ops, p, map, bin_gene);
             }
         }
         splexon::wave_verdicts(verdict, f.mine);
-        LaneBins bins{spl_exon_hits<DevOps, DevMap>(DevOps{src.cigar + c0}, verdict == SPL_EXON_COUNTED ? n_ops : 0u, p, map)};
+        LaneBins bins{spl_exon_hits<spl_ops_ptr, DevMap>(spl_ops_ptr{src.cigar + c0}, verdict == SPL_EXON_COUNTED ? n_ops : 0u, p, map)};
         splexon::wave_commit(bins, n_bins, reinterpret_cast<uint64_t *>(counts));
     }
     f.finish(n_bins, counts);
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(SPL_EXON_TILE) void spl_exon_count_kernel(const spl
 // fourth quarter of a launch of SPL_EXON_GRID_MAX workgroups (four a CU) waits for a second round.  The bound of four waves a SIMD
 // keeps all of them resident (128 registers, DESIGN section 7: what it costs in scratch, and what it gains).
 struct LaneFragmentBins {
-    spl_exon_merge<DevOps, DevMap> merge;
+    spl_exon_merge<spl_ops_ptr, DevMap> merge;
     __device__ __forceinline__ uint32_t next() { return merge.next(); }
 };
 
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(SPL_EXON_TILE, 4) void spl_exon_count_fragments_ker
                                                                                   const spl_count_maps maps, uint32_t n_bins, const uint32_t *bin_gene, const uint32_t *mate,
                                                                                   unsigned long long *counts)
 {
-    const spl_mate_reads reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
+    const spl_read_view reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
     CountFrame<SPL_EXON_TILE, SPL_EXON_TOP, SPL_EXON_VERDICTS> f(maps);
     for (int64_t base = f.first(); base < n; base += f.stride()) { // (uniform over the workgroup)
         const int64_t r = base + threadIdx.x;
@@ -94,11 +93,11 @@ __global__ __launch_bounds__(SPL_EXON_TILE, 4) void spl_exon_count_fragments_ker
         spl_exon_side lead{0u, 0u, 0, false}, other{0u, 0u, 0, false};
         if (r < n) {
             verdict = spl_exon_fragment_sides(reads, first, n, r, mate, (int64_t)shift, stranded, &lead, &other);
-            if (verdict == SPL_EXON_COUNTED) verdict = spl_exon_fragment_verdict<DevOps>(src.cigar, lead, other, f.map_a, f.map_b, bin_gene);
+            if (verdict == SPL_EXON_COUNTED) verdict = spl_exon_fragment_verdict<spl_ops_ptr>(src.cigar, lead, other, f.map_a, f.map_b, bin_gene);
         }
         splexon::wave_verdicts(verdict, f.mine);
         if (verdict != SPL_EXON_COUNTED) lead.n_ops = other.n_ops = 0u; // (no walk: the merge has no bin)
-        LaneFragmentBins bins{spl_exon_merge<DevOps, DevMap>(src.cigar, lead, other, f.map_a, f.map_b)};
+        LaneFragmentBins bins{spl_exon_merge<spl_ops_ptr, DevMap>(src.cigar, lead, other, f.map_a, f.map_b)};
         splexon::wave_commit(bins, n_bins, reinterpret_cast<uint64_t *>(counts));
     }
     f.finish(n_bins, counts);

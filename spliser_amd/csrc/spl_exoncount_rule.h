@@ -19,7 +19,7 @@
 // A BIN MAP has the shape of a gene map (spl_genecount_rule.h): an ascending int32 start[n] with a uint32 code[n], code[k] holding
 // for start[k] <= p < start[k + 1] (the last entry to +infinity; 0 below start[0]): 0 = none, b + 1 = bin b, 0xFFFFFFFF = shared; an
 // entry only where the code changes.  bin_gene[n_bins] is every bin's gene, a uint32 that is only ever compared for equality.
-// A READ.  Eligibility and map are spl_gene_count's (spl_gene_eligible, spl_gene_uses_b).  Its BLOCKS are spl_cov_walk's from
+// A READ.  Eligibility and map are spl_gene_count's (spl_gene_eligible, spl_gene_uses_b).  Its BLOCKS are the block walk's from
 // p = POS - 1 + shift, in int64, nothing clipped.  Its HIT STRETCHES are the stretches of its map that a block overlaps by a base or
 // more, each taken once however many of its blocks overlap it (a deletion or an intron inside one bin gives two blocks in one
 // stretch).  VERDICT: any hit stretch shared, or two hit stretches with bins of different genes -> AMBIGUOUS, and no bin is
@@ -44,40 +44,28 @@
 #define SPL_EXON_NOT_COUNTED 3u
 #define SPL_EXON_IDLE 4u
 
-// The hit stretches of one eligible read over `map`, one by one: spl_cov_walk's loop, stopped at every block, and every block held
-// against the map.  A stretch that consecutive blocks hit is given once: blocks and stretches both ascend, so the index of the
-// last stretch given is all there is to remember.  Stretches of code 0 are hit and passed over: they hold no bin and decide nothing.
+// The hit stretches of one eligible read over `map`, one by one: the block walk (spl_block_walk, spl_coverage_rule.h), not
+// clipped, every block held against the map.  A stretch that consecutive blocks hit is given once: blocks and stretches both
+// ascend, so the index of the last stretch given is all there is to remember.  Stretches of code 0 are hit and passed over: they
+// hold no bin and decide nothing.
 template <class Ops, class Map>
 struct spl_exon_hits {
     const Ops ops;      // (both by value: a few words, and a lane's walk then points at nothing of the caller's)
     uint32_t n_ops;
     const Map map;
     uint32_t k;         // the next op (n_ops + 1: the walk is over)
-    int64_t p, bs, be;  // the walk's position and its open block [bs, be); bs == be: none
+    spl_block_walk walk;
     int64_t s, e;       // the block held against the map, s == e: none
     int64_t j, last;    // the next stretch to look at for [s, e); the last one given (-1: none)
 
-    SPL_HD spl_exon_hits(const Ops &ops_, uint32_t n_ops_, int64_t p_, const Map &map_) : ops(ops_), n_ops(n_ops_), map(map_), k(0u), p(p_), bs(0), be(0), s(0), e(0), j(0), last(-1) {}
+    SPL_HD spl_exon_hits(const Ops &ops_, uint32_t n_ops_, int64_t p_, const Map &map_) : ops(ops_), n_ops(n_ops_), map(map_), k(0u), walk(p_), s(0), e(0), j(0), last(-1) {}
 
-    // The read's next block into [s, e): spl_cov_walk's blocks, not clipped.  -> false: there is none.
+    // The read's next block into [s, e), not clipped.  -> false: there is none.
     SPL_HD bool next_block()
     {
         while (k <= n_ops) {
             const uint32_t at = k++;
-            int64_t len = 0;
-            bool covers = false;
-            if (at < n_ops) {
-                const uint32_t op = ops(at);
-                len = (int64_t)(op >> 4);
-                if (len == 0 || !((SPL_PROG_MASK >> (op & 15u)) & 1u)) continue;
-                covers = ((SPL_MAPPED_MASK >> (op & 15u)) & 1u) != 0u;
-            }
-            if (covers && be > bs && p == be) { be += len; p += len; continue; } // abuts the open block
-            const bool ended = be > bs; // the open block ends here
-            if (ended) { s = bs; e = be; bs = be = 0; }
-            if (covers) { bs = p; be = p + len; }
-            p += len;
-            if (ended) return true;
+            if (walk.feed(at == n_ops, at < n_ops ? ops(at) : 0u, &s, &e)) return true;
         }
         return false;
     }
@@ -138,10 +126,10 @@ SPL_HD uint32_t spl_exon_read_result(uint32_t flag, int64_t pos, const uint32_t 
     *n_hits_out = 0;
     if (!spl_gene_eligible(flag, pos, n_ops)) return SPL_EXON_NOT_COUNTED;
     const spl_gene_map_flat &map = spl_gene_uses_b(flag, stranded) ? b : a;
-    const spl_gene_ops_ptr o{ops};
+    const spl_ops_ptr o{ops};
     const uint32_t verdict = spl_exon_verdict(o, n_ops, pos - 1 + shift, map, bin_gene);
     if (verdict != SPL_EXON_COUNTED) return verdict;
-    spl_exon_hits<spl_gene_ops_ptr, spl_gene_map_flat> hits(o, n_ops, pos - 1 + shift, map);
+    spl_exon_hits<spl_ops_ptr, spl_gene_map_flat> hits(o, n_ops, pos - 1 + shift, map);
     for (uint32_t bin; (bin = spl_exon_next_bin(hits, 0xFFFFFFFFu)) != 0xFFFFFFFFu;) {
         if (*n_hits_out < cap) bins_out[*n_hits_out] = (int64_t)bin;
         ++*n_hits_out;

@@ -47,7 +47,7 @@ struct spl_exon_side {
 // What read r of the n reads of a segment is (spl_fragment_sides, by the table's word): SPL_EXON_NOT_COUNTED, SPL_EXON_IDLE (silent:
 // its leader counts the fragment), or SPL_EXON_COUNTED -- to be walked: *lead is the read itself, *other its mate (n_ops = 0: it
 // has none).  A side's map is settled here, from its read's own flag.
-SPL_HD uint32_t spl_exon_fragment_sides(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, spl_exon_side *lead,
+SPL_HD uint32_t spl_exon_fragment_sides(const spl_read_view &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, spl_exon_side *lead,
                                         spl_exon_side *other)
 {
     spl_frag_side x, y;
@@ -115,16 +115,16 @@ struct spl_exon_merge {
 // The whole rule for read r of a segment from arrays the caller can index as they are (the host's form): -> the verdict, or
 // SPL_EXON_IDLE for a silent read; bins_out[0 .. cap) gets a counted fragment's distinct bins in ascending order, *n_hits_out their
 // number (all of them, also beyond cap); any other verdict has no hit.
-SPL_HD uint32_t spl_exon_fragment_result(const spl_mate_reads &s, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, const spl_gene_map_flat &a,
+SPL_HD uint32_t spl_exon_fragment_result(const spl_read_view &s, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, const spl_gene_map_flat &a,
                                          const spl_gene_map_flat &b, const uint32_t *bin_gene, int64_t *bins_out, int64_t cap, int64_t *n_hits_out)
 {
     *n_hits_out = 0;
     spl_exon_side lead, other;
     const uint32_t what = spl_exon_fragment_sides(s, 0, n, r, mate, shift, stranded, &lead, &other);
     if (what != SPL_EXON_COUNTED) return what;
-    const uint32_t verdict = spl_exon_fragment_verdict<spl_gene_ops_ptr>(s.cigar, lead, other, a, b, bin_gene);
+    const uint32_t verdict = spl_exon_fragment_verdict<spl_ops_ptr>(s.cigar, lead, other, a, b, bin_gene);
     if (verdict != SPL_EXON_COUNTED) return verdict;
-    spl_exon_merge<spl_gene_ops_ptr, spl_gene_map_flat> merge(s.cigar, lead, other, a, b);
+    spl_exon_merge<spl_ops_ptr, spl_gene_map_flat> merge(s.cigar, lead, other, a, b);
     for (uint32_t bin; (bin = merge.next()) != SPL_EXON_NO_BIN;) {
         if (*n_hits_out < cap) bins_out[*n_hits_out] = (int64_t)bin;
         ++*n_hits_out;

@@ -8,9 +8,9 @@
 //
 // The geometry is spl_strand.hip's: one launch per segment of the set, a grid-stride loop over its reads, SPL_GENE_TILE reads a
 // workgroup and step, a read a lane, in whatever order the reads are: the frame of spl_genemap_dev.h (CountFrame), whose loop both
-// kernels here run with a per-step body of their own.  A lane walks its eligible read's ops where they lie (spl_cov_walk) and folds every block
-// over the gene map of its strand.  A map is searched in two steps: its top level -- every stride-th start, at most SPL_GENE_TOP
-// of them -- is in LDS (both maps': 8 KB), the stretch of `stride` entries below the hit is searched where it is, in global
+// kernels here run with a per-step body of their own.  A lane walks its eligible read's ops where they lie (the block walk) and
+// folds every block over the gene map of its strand.  A map is searched in two steps: its top level -- every stride-th start, at
+// most SPL_GENE_TOP of them -- is in LDS (both maps': 8 KB), the stretch of `stride` entries below the hit is searched where it is, in global
 // memory; the stretches a block runs over behind the hit are read in turn.  A map of any size takes this path.
 //
 // The lane's result -- a gene, no feature, ambiguous, not counted -- goes into the counts by splgene::wave_count: one 64-bit
@@ -23,7 +23,7 @@
 #include "spl_genecount.h"
 #include "spl_genecount_rule.h"
 #include "spl_genecount_wave.h"
-#include "spl_genemap_dev.h" // DevMap, DevOps, CountFrame, count_launch_fits
+#include "spl_genemap_dev.h" // DevMap, CountFrame, count_launch_fits
 #include "spl_mate_rule.h"   // the fragment's rule
 
 static_assert(splgene::NO_FEATURE == SPL_GENE_NO_FEATURE && splgene::AMBIGUOUS == SPL_GENE_AMBIGUOUS && splgene::NOT_COUNTED == SPL_GENE_NOT_COUNTED &&
@@ -43,12 +43,12 @@ __global__ __launch_bounds__(SPL_GENE_TILE) void spl_gene_count_kernel(const spl
             const int64_t i = first + r;
             const uint32_t flag = src.flag[i];
             const int64_t pos = (int64_t)src.pos[i];
-            uint32_t c0 = src.cig_off[i], c1 = src.cig_off[i + 1];
-            if (c1 < c0 || (int64_t)c1 > n_ops_total) c1 = c0; // (offsets of the arrays' own ops: said for the memory's sake)
+            uint32_t c0, n_ops;
+            spl_ops_of(src.cig_off, i, n_ops_total, &c0, &n_ops);
             result = SPL_GENE_NOT_COUNTED;
-            if (spl_gene_eligible(flag, pos, c1 - c0)) {
+            if (spl_gene_eligible(flag, pos, n_ops)) {
                 const int64_t p = pos - 1 + (int64_t)shift;
-                result = spl_gene_uses_b(flag, stranded) ? spl_gene_of_blocks(DevOps{src.cigar + c0}, c1 - c0, p, f.map_b) : spl_gene_of_blocks(DevOps{src.cigar + c0}, c1 - c0, p, f.map_a);
+                result = spl_gene_uses_b(flag, stranded) ? spl_gene_of_blocks(spl_ops_ptr{src.cigar + c0}, n_ops, p, f.map_b) : spl_gene_of_blocks(spl_ops_ptr{src.cigar + c0}, n_ops, p, f.map_a);
             }
         }
         splgene::wave_count(result, n_genes, reinterpret_cast<uint64_t *>(counts), f.mine);
@@ -62,12 +62,12 @@ __global__ __launch_bounds__(SPL_GENE_TILE) void spl_gene_count_kernel(const spl
 __global__ __launch_bounds__(SPL_GENE_TILE) void spl_gene_count_fragments_kernel(const spl_devreads src, int64_t n_ops_total, int64_t first, int64_t n, int32_t shift, int stranded,
                                                                                   const spl_count_maps maps, uint32_t n_genes, const uint32_t *mate, unsigned long long *counts)
 {
-    const spl_mate_reads reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
+    const spl_read_view reads{src.pos, src.flag, src.cig_off, src.cigar, n_ops_total};
     CountFrame<SPL_GENE_TILE, SPL_GENE_TOP, SPL_GENE_SPECIALS> f(maps);
     for (int64_t base = f.first(); base < n; base += f.stride()) { // (uniform over the workgroup)
         const int64_t r = base + threadIdx.x;
         uint32_t result = SPL_GENE_IDLE;
-        if (r < n) result = spl_gene_fragment_result<DevOps>(reads, first, n, r, mate, (int64_t)shift, stranded, f.map_a, f.map_b);
+        if (r < n) result = spl_gene_fragment_result<spl_ops_ptr>(reads, first, n, r, mate, (int64_t)shift, stranded, f.map_a, f.map_b);
         splgene::wave_count(result, n_genes, reinterpret_cast<uint64_t *>(counts), f.mine);
     }
     f.finish(n_genes, counts);

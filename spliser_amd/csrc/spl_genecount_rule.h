@@ -12,7 +12,7 @@
 // positions start[k] <= p < start[k + 1] (the last entry to +infinity; 0 below start[0]): 0 = no feature, g + 1 = features of the
 // one gene g only, 0xFFFFFFFF = features of two or more genes.  A read is ELIGIBLE when it is mapped, primary, QC-passed and not
 // supplementary (spl_strand_eligible; duplicates count), POS >= 1 and it has at least one op; any other read is NOT COUNTED.  An
-// eligible read's BLOCKS are those of spl_cov_walk from the 0-based p = POS - 1 + shift, in int64, not clipped to a length: M, =
+// eligible read's BLOCKS are the block walk's (spl_coverage_rule.h) from the 0-based p = POS - 1 + shift, in int64, not clipped: M, =
 // and X cover, D and N are gaps, covering ops that abut are one block.  Its GENE SET is the union, over every stretch of the map
 // that a block overlaps by a base or more, of that stretch's code: empty -> NO FEATURE, exactly one gene -> that gene, anything
 // else -> AMBIGUOUS (htseq-count's --mode union --nonunique none, featureCounts' default, per read).  With stranded = 1 (fr) or 2
@@ -24,6 +24,7 @@
 
 #include "spl_classify.h"
 #include "spl_coverage_rule.h"
+#include "spl_read_view.h"
 #include "spl_strand_rule.h"
 
 #define SPL_GENE_MANY 0xFFFFFFFFu         // a map code: two or more genes
@@ -34,7 +35,6 @@
 #define SPL_GENE_NOT_COUNTED 0xFFFFFFFEu
 #define SPL_GENE_IDLE 0xFFFFFFFFu
 #define SPL_GENE_INDEX_MAX 0xFFFFFFF0u    // n_genes at most: every code g + 1 and every result stays clear of the values above
-#define SPL_GENE_NO_LENGTH 0x3FFFFFFFFFFFFFFFll // the walk's clipping length when nothing is clipped
 
 SPL_HD bool spl_gene_eligible(uint32_t flag, int64_t pos, uint32_t n_ops) { return spl_strand_eligible(flag) && pos >= 1 && n_ops >= 1u; }
 
@@ -49,7 +49,7 @@ struct spl_gene_map_flat {
     SPL_HD uint32_t code_at(int64_t k) const { return code[k]; }
 };
 
-// The fold of a read's blocks over a map: spl_cov_walk's emit.  set: 0 = empty, g + 1 = the one gene g, SPL_GENE_MANY.
+// The fold of a read's blocks over a map: what the block walk's blocks go into.  set: 0 = empty, g + 1 = the one gene g, SPL_GENE_MANY.
 template <class Map>
 struct spl_gene_fold {
     const Map &map;
@@ -69,41 +69,51 @@ struct spl_gene_fold {
     }
 };
 
-// What an ELIGIBLE read with these ops comes to over `map`, p = POS - 1 + shift.  ops(k) = the read's k-th op (BAM form).
-template <class Ops, class Map>
-SPL_HD uint32_t spl_gene_of_blocks(const Ops &ops, uint32_t n_ops, int64_t p, const Map &map)
-{
-    spl_gene_fold<Map> fold{map, 0u};
-    int64_t covered = 0;
-    (void)spl_cov_walk(ops, n_ops, p, SPL_GENE_NO_LENGTH, fold, &covered);
-    return fold.set == 0u ? SPL_GENE_NO_FEATURE : fold.set == SPL_GENE_MANY ? SPL_GENE_AMBIGUOUS : fold.set - 1u;
-}
-
-// The form that CONTINUES a set (a fragment's: spl_mate_rule.h): `set` as a fold has it -> the set with these blocks folded in.
+// The form that CONTINUES a set (a fragment's: spl_mate_rule.h): `set` as a fold has it -> the set with the blocks of these ops
+// folded in, p = POS - 1 + shift.  ops(k) = the read's k-th op (BAM form).
+// THE SECOND STATEMENT OF THE BLOCK WALK, kept on purpose: spl_cov_walk's former loop without the clipping.  Over spl_block_walk's
+// step (spl_coverage_rule.h) spl_gene_count_kernel measured 2.8 and 3.6 % slower than with this loop, beyond the 2 % it was allowed
+// (DESIGN.md, section 3).  A change of the rule changes both; tests/test_blockwalk_host.py holds both to one restatement.
 template <class Ops, class Map>
 SPL_HD uint32_t spl_gene_set_add_blocks(uint32_t set, const Ops &ops, uint32_t n_ops, int64_t p, const Map &map)
 {
     spl_gene_fold<Map> fold{map, set};
-    int64_t covered = 0;
-    (void)spl_cov_walk(ops, n_ops, p, SPL_GENE_NO_LENGTH, fold, &covered);
+    int64_t bs = 0, be = 0; // the open block [bs, be); bs == be: none
+    for (uint32_t k = 0; k <= n_ops; ++k) {
+        int64_t len = 0;
+        bool covers = false;
+        if (k < n_ops) {
+            const uint32_t op = ops(k);
+            len = (int64_t)(op >> 4);
+            if (len == 0 || !((SPL_PROG_MASK >> (op & 15u)) & 1u)) continue;
+            covers = ((SPL_MAPPED_MASK >> (op & 15u)) & 1u) != 0u;
+        }
+        if (covers && be > bs && p == be) { be += len; p += len; continue; } // abuts the open block
+        if (be > bs) { fold(bs, be); bs = be = 0; }
+        if (covers) { bs = p; be = p + len; }
+        p += len;
+    }
     return fold.set;
 }
 // What a finished set comes to.
 SPL_HD uint32_t spl_gene_result_of_set(uint32_t set) { return set == 0u ? SPL_GENE_NO_FEATURE : set == SPL_GENE_MANY ? SPL_GENE_AMBIGUOUS : set - 1u; }
 
+// What an ELIGIBLE read with these ops comes to over `map`.
+template <class Ops, class Map>
+SPL_HD uint32_t spl_gene_of_blocks(const Ops &ops, uint32_t n_ops, int64_t p, const Map &map)
+{
+    return spl_gene_result_of_set(spl_gene_set_add_blocks(0u, ops, n_ops, p, map));
+}
+
 // Map b serves this read (stranded = 1 / 2 and a '-' read); map a every other.
 SPL_HD bool spl_gene_uses_b(uint32_t flag, int stranded) { return stranded != 0 && spl_read_strand(flag, stranded) == (uint8_t)'-'; }
 
 // The whole rule for one read from arrays the caller can index as they are (the host's form).
-struct spl_gene_ops_ptr {
-    const uint32_t *p;
-    SPL_HD uint32_t operator()(uint32_t k) const { return p[k]; }
-};
 SPL_HD uint32_t spl_gene_read_result(uint32_t flag, int64_t pos, const uint32_t *ops, uint32_t n_ops, int64_t shift, int stranded, const spl_gene_map_flat &a,
                                      const spl_gene_map_flat &b)
 {
     if (!spl_gene_eligible(flag, pos, n_ops)) return SPL_GENE_NOT_COUNTED;
-    return spl_gene_of_blocks(spl_gene_ops_ptr{ops}, n_ops, pos - 1 + shift, spl_gene_uses_b(flag, stranded) ? b : a);
+    return spl_gene_of_blocks(spl_ops_ptr{ops}, n_ops, pos - 1 + shift, spl_gene_uses_b(flag, stranded) ? b : a);
 }
 
 // A map as the entries take it: strictly ascending starts, codes 0 .. n_genes or SPL_GENE_MANY.  -> -1 when it is one, else the

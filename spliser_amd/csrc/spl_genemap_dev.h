@@ -6,9 +6,8 @@
 // THE FRAME of a counting kernel (CountFrame): both maps' top levels go into LDS and the special counters' sums are cleared; a
 // grid-stride loop gives every lane of the workgroup a read of the segment per step, or none; a kernel's own per-step body says
 // what a read comes to and commits it wave by wave, gathering the special counters in `mine` (lane c of a wave: the wave's reads
-// that add to special counter c -- at most 64 a step: 32 bits hold any read set's); the waves' sums then meet in LDS and the
-// workgroup ends with one atomic per special counter, behind the kernel's n_codes ordinary counters.  Integer sums: exact,
-// whatever the order.
+// that add to special counter c); the frame ends as the predicate tally does (spl_tally_dev.h: tally_finish), behind the kernel's
+// n_codes ordinary counters.
 #ifndef SPL_GENEMAP_DEV_H
 #define SPL_GENEMAP_DEV_H
 #include <hip/hip_runtime.h>
@@ -17,6 +16,7 @@
 #include "spl_genecount.h" // spl_count_maps
 #include "spl_genecount_rule.h"
 #include "spl_strand_rule.h"
+#include "spl_tally_dev.h" // tally_finish: the frame's ending
 #include "spl_wave.h"
 
 namespace {
@@ -37,11 +37,6 @@ struct DevMap {
     }
     __device__ __forceinline__ int64_t start_at(int64_t k) const { return (int64_t)start[k]; }
     __device__ __forceinline__ uint32_t code_at(int64_t k) const { return code[k]; }
-};
-
-struct DevOps {
-    const uint32_t *p;
-    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return p[k]; }
 };
 
 // The frame.  TILE: the workgroup's lanes (whole waves); TOP: a map's top level at most; SPECIALS: the special counters.  A kernel
@@ -75,10 +70,7 @@ struct CountFrame {
     // the special counters behind the kernel's n_codes ordinary ones
     __device__ __forceinline__ void finish(uint32_t n_codes, unsigned long long *counts)
     {
-        const uint32_t t = threadIdx.x;
-        if (wv::lane() < SPECIALS && mine) atomicAdd(&s_sum[wv::lane()], mine);
-        __syncthreads();
-        if (t < SPECIALS && s_sum[t]) atomicAdd(&counts[(int64_t)n_codes + t], (unsigned long long)s_sum[t]);
+        tally_finish<SPECIALS>(s_sum, mine, counts + n_codes, SlotSame{});
     }
 };
 

@@ -62,16 +62,11 @@ SPL_HD bool carries(const Ops &ops, uint32_t n_ops, int32_t p, const spljw::Filt
     return false;
 }
 
-struct OpsPtr {
-    const uint32_t *p;
-    SPL_HD uint32_t operator()(uint32_t k) const { return p[k]; }
-};
-
 // The whole rule for read r of a segment from arrays the caller can index as they are (the host's form): visit(l, r, strand code,
 // anchor_left, anchor_right, duplicate) for every junction the read supports, in walk order.  xs: the reads' strand bytes (mode 3)
 // or null.  -> false: the read's walk left the coordinate space (what it gave until then was visited).
 template <class Visit>
-SPL_HD bool read_junctions(const spl_mate_reads &s, const uint8_t *xs, int64_t n, int64_t r, const uint32_t *mate, int32_t shift, int stranded, const spljw::Filter &f, Visit &visit)
+SPL_HD bool read_junctions(const spl_read_view &s, const uint8_t *xs, int64_t n, int64_t r, const uint32_t *mate, int32_t shift, int stranded, const spljw::Filter &f, Visit &visit)
 {
     const uint32_t flag = s.flag[r];
     const int64_t pos = (int64_t)s.pos[r];
@@ -87,13 +82,13 @@ SPL_HD bool read_junctions(const spl_mate_reads &s, const uint8_t *xs, int64_t n
         m_p = (int32_t)((int64_t)s.pos[m] + (int64_t)shift);
         if (!walked(s.flag[m], (int64_t)s.pos[m]) || strand_code(s.flag[m], xs ? xs[m] : 0u, stranded) != code) m = -1;
     }
-    const OpsPtr ops{s.cigar + c0};
+    const spl_ops_ptr ops{s.cigar + c0};
     spljw::Walk w;
     w.begin((int32_t)((int64_t)s.pos[r] + (int64_t)shift));
     spljw::Junction j;
     while (spljw::next(w, ops, n_ops, f, j)) {
         if (!j.passes || (stranded == 3 && !spljw::key3_fits(j.l, j.r))) continue;
-        const bool dup = m >= 0 && carries(OpsPtr{s.cigar + m0}, m_ops, m_p, f, j.l, j.r);
+        const bool dup = m >= 0 && carries(spl_ops_ptr{s.cigar + m0}, m_ops, m_p, f, j.l, j.r);
         visit(j.l, j.r, code, j.anchor_left, j.anchor_right, dup);
     }
     return !w.range_error;

@@ -216,7 +216,7 @@ __global__ __launch_bounds__(SPL_JTILE) void spl_junction_fused_kernel(const spl
                     w.range_error = false;
                 }
                 if (XS && have && !spljw::key3_fits(j.l, j.r)) { atomicOr(err, SPL_DEV_ERR_RANGE); have = false; }
-                if (FRAG && have && m_has && spljf::carries(spljf::OpsPtr{src.cigar + m0}, m_ops, m_p, filter, j.l, j.r)) have = false; // a duplicate carry
+                if (FRAG && have && m_has && spljf::carries(spl_ops_ptr{src.cigar + m0}, m_ops, m_p, filter, j.l, j.r)) have = false; // a duplicate carry
                 junction_merge_insert(have, have ? (XS ? spljw::key3_of(j.l, j.r, sbit) : spljw::key_of(j.l, j.r, sbit)) : ~0ull, j.anchor_left, j.anchor_right, lane, keys, vals, mask,
                                       err);
             }

@@ -151,38 +151,8 @@ SPL_HD bool spl_mate_pair_element(const uint64_t *keys, const uint32_t *index, i
 }
 
 // ---- a fragment's sides, and its gene ---------------------------------------------------------------------------------------------
-// One read of a fragment as a walk takes it: its ops (n_ops = 0: there is no such read), p = POS - 1 + shift, and its FLAG (which
-// map serves it: spl_gene_uses_b).
-struct spl_frag_side {
-    uint32_t c0, n_ops;
-    int64_t p;
-    uint32_t flag;
-};
-
-// The arrays of a segment as the rule reads them: read r of the segment is entry first + r; mate[] is the segment's table.
-struct spl_mate_reads {
-    const int32_t *pos;
-    const uint16_t *flag;
-    const uint32_t *cig_off;
-    const uint32_t *cigar;
-    int64_t n_ops_total; // the cigar array's size: no op beyond it is read
-    SPL_HD void ops_of(int64_t i, uint32_t *c0, uint32_t *n) const
-    {
-        uint32_t a = cig_off[i], b = cig_off[i + 1];
-        if (b < a || (int64_t)b > n_ops_total) b = a; // (offsets of the arrays' own ops: said for the memory's sake)
-        *c0 = a; *n = b - a;
-    }
-    // Entry i as a side; -> whether it takes part: takes(flag, POS, n_ops).
-    template <class Takes>
-    SPL_HD bool side_of(int64_t i, int64_t shift, const Takes &takes, spl_frag_side *out) const
-    {
-        const int64_t p1 = (int64_t)pos[i];
-        out->flag = flag[i];
-        ops_of(i, &out->c0, &out->n_ops);
-        out->p = p1 - 1 + shift;
-        return takes(out->flag, p1, out->n_ops);
-    }
-};
+// The arrays of a segment as the rule reads them, and one read of a fragment as a walk takes it (spl_frag_side; its FLAG says
+// which map serves it: spl_gene_uses_b): spl_read_view.h's spl_read_view.  mate[] is the segment's table.
 
 #define SPL_FRAG_OUT 0u
 #define SPL_FRAG_SILENT 1u
@@ -197,7 +167,7 @@ struct spl_gene_takes {
 // a leader's mate (n_ops = 0: it has none).  MateMustTake: the policy above -- false, the table's word; true, a mate that does
 // not take part is no partner.
 template <bool MateMustTake, class Takes>
-SPL_HD uint32_t spl_fragment_sides(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, const Takes &takes, spl_frag_side *lead,
+SPL_HD uint32_t spl_fragment_sides(const spl_read_view &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, const Takes &takes, spl_frag_side *lead,
                                    spl_frag_side *other)
 {
     const spl_frag_side none{0u, 0u, 0, 0u};
@@ -217,7 +187,7 @@ SPL_HD uint32_t spl_fragment_sides(const spl_mate_reads &s, int64_t first, int64
 // What read r of the n reads of a segment adds: a gene, SPL_GENE_NO_FEATURE, SPL_GENE_AMBIGUOUS, SPL_GENE_NOT_COUNTED -- or
 // SPL_GENE_IDLE: nothing, its leader counts the fragment.  Ops: made from a pointer to the read's first op.
 template <class Ops, class Map>
-SPL_HD uint32_t spl_gene_fragment_result(const spl_mate_reads &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, const Map &map_a,
+SPL_HD uint32_t spl_gene_fragment_result(const spl_read_view &s, int64_t first, int64_t n, int64_t r, const uint32_t *mate, int64_t shift, int stranded, const Map &map_a,
                                          const Map &map_b)
 {
     spl_frag_side lead, other;

@@ -13,15 +13,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#define SPL_HD __device__ __forceinline__
 #include "spl_motif.h"
 #include "spl_motif_rule.h"
+#include "spl_read_view.h"
 
 namespace {
-
-struct OpsPtr {
-    const uint32_t *p;
-    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return p[k]; }
-};
 
 __global__ __launch_bounds__(SPL_MOTIF_TILE) void spl_motif_strand_kernel(const spl_devreads src, uint8_t *xs, int64_t n_ops_total, int64_t first, int64_t n, int32_t shift,
                                                                           const uint8_t *packed, int64_t length, unsigned long long *out)
@@ -36,15 +33,14 @@ __global__ __launch_bounds__(SPL_MOTIF_TILE) void spl_motif_strand_kernel(const 
     const splmotif::NibblePairs pairs{packed};
     for (int64_t r = (int64_t)blockIdx.x * SPL_MOTIF_TILE + t; r < n; r += (int64_t)gridDim.x * SPL_MOTIF_TILE) {
         const int64_t i = first + r;
-        uint32_t c0, c1;
-        splmotif::ops_span(src.cig_off, i, n_ops_total, c0, c1);
-        const uint32_t n_ops = c1 - c0;
+        uint32_t c0, n_ops;
+        spl_ops_of(src.cig_off, i, n_ops_total, &c0, &n_ops);
         bool has_n = false;
         for (uint32_t k = 0; k < n_ops; ++k) has_n = has_n || (src.cigar[c0 + k] & 15u) == (uint32_t)SPL_OP_N;
         uint8_t strand = 0;
         if (has_n) {
             splmotif::ReadMotifs m;
-            splmotif::read_motifs((uint32_t)src.flag[i], (int64_t)src.pos[i] + shift, OpsPtr{src.cigar + c0}, n_ops, pairs, length, m);
+            splmotif::read_motifs((uint32_t)src.flag[i], (int64_t)src.pos[i] + shift, spl_ops_ptr{src.cigar + c0}, n_ops, pairs, length, m);
             strand = m.strand;
 #pragma unroll
             for (int c = 0; c < 7; ++c) mine[c] += m.walks[c];

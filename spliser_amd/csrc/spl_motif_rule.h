@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "spl_junction_walk.h"
+#include "spl_read_view.h"
 
 #ifndef SPL_MOTIF_HD
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -122,12 +123,13 @@ struct NibblePairs {
     }
 };
 
-// A read's ops in the arrays: cigar[c0, c1).  Offsets that descend or point beyond the arrays' ops are an empty CIGAR.
-SPL_MOTIF_HD void ops_span(const uint32_t *cig_off, int64_t i, int64_t n_ops_total, uint32_t &c0, uint32_t &c1)
+// A read's ops in the arrays: cigar[c0, c1) (spl_ops_of, spl_read_view.h: offsets that descend or point beyond the arrays' ops are
+// an empty CIGAR).
+SPL_HD void ops_span(const uint32_t *cig_off, int64_t i, int64_t n_ops_total, uint32_t &c0, uint32_t &c1)
 {
-    c0 = cig_off[i];
-    c1 = cig_off[i + 1];
-    if (c1 < c0 || (int64_t)c1 > n_ops_total) c1 = c0;
+    uint32_t n_ops;
+    spl_ops_of(cig_off, i, n_ops_total, &c0, &n_ops);
+    c1 = c0 + n_ops;
 }
 
 // what one read adds to the tally: its walks by code (a read has several), and the read's class

@@ -11,14 +11,15 @@
 // start, at most SPL_STRAND_TOP of them -- is in LDS, the stretch of `stride` entries below the hit is searched where it is, in
 // global memory (one entry when the whole map fits the top level).  A map of any size takes this path; nothing is a limit.
 //
-// Every counter is a 0/1 predicate per read: a ballot and a popcount per wave and step, kept by lane c for counter c; the waves'
-// sums meet in LDS, and a workgroup ends with one 64-bit atomicAdd per counter.  Integer sums: exact, whatever the order.
+// Every counter is a 0/1 predicate per read: the predicate tally of spl_tally_dev.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define SPL_HD __device__ __forceinline__
+#include "spl_read_view.h"
 #include "spl_strand.h"
 #include "spl_strand_rule.h"
+#include "spl_tally_dev.h"
 
 namespace {
 
@@ -28,14 +29,10 @@ __global__ __launch_bounds__(SPL_STRAND_TILE) void spl_strand_tally_kernel(const
                                                                            unsigned long long *out)
 {
     __shared__ int32_t s_top[MAP ? SPL_STRAND_TOP : 1];
-    __shared__ uint32_t s_sum[SPL_STRAND_COUNTERS];
     const uint32_t t = threadIdx.x;
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     if (MAP)
         for (uint32_t j = t; j < n_top; j += SPL_STRAND_TILE) s_top[j] = cover_start[(int64_t)j * stride];
-    if (t < SPL_STRAND_COUNTERS) s_sum[t] = 0u;
-    __syncthreads();
-    uint32_t mine = 0; // lane c of a wave: the wave's reads that add to counter c (at most 64 a step: 32 bits hold any read set's)
+    PredicateTally<SPL_STRAND_COUNTERS> tally; // (its barrier: s_top is filled)
     for (int64_t base = (int64_t)blockIdx.x * SPL_STRAND_TILE; base < n; base += (int64_t)gridDim.x * SPL_STRAND_TILE) { // (uniform over the workgroup)
         const int64_t r = base + t;
         uint32_t bits = 0;
@@ -50,22 +47,16 @@ __global__ __launch_bounds__(SPL_STRAND_TILE) void spl_strand_tally_kernel(const
                 if (j >= 0) {
                     const int64_t lo = j * stride, hi = lo + stride < n_cover ? lo + stride : n_cover;
                     const int64_t k = spl_cover_find(cover_start, lo, hi, pos); // (start[lo] <= pos: k >= lo)
-                    uint32_t c0 = src.cig_off[i], c1 = src.cig_off[i + 1];
-                    if (c1 < c0 || (int64_t)c1 > n_ops_total) c1 = c0; // (offsets of the arrays' own ops: said for the memory's sake)
-                    ann = spl_cover_evidence(k, n_cover, cover_start, cover_code, pos, spl_strand_ref_len(src.cigar + c0, c1 - c0));
+                    uint32_t c0, n_ops;
+                    spl_ops_of(src.cig_off, i, n_ops_total, &c0, &n_ops);
+                    ann = spl_cover_evidence(k, n_cover, cover_start, cover_code, pos, spl_strand_ref_len(src.cigar + c0, n_ops));
                 }
             }
             bits = spl_strand_bits(flag, tag, ann);
         }
-#pragma unroll
-        for (uint32_t c = 0; c < SPL_STRAND_COUNTERS; ++c) {
-            const unsigned long long b = __ballot((bits >> c) & 1u);
-            if (lane == c) mine += (uint32_t)__popcll(b);
-        }
+        tally.add(bits);
     }
-    if (lane < SPL_STRAND_COUNTERS && mine) atomicAdd(&s_sum[lane], mine);
-    __syncthreads();
-    if (t < SPL_STRAND_COUNTERS) atomicAdd(&out[t], (unsigned long long)s_sum[t]);
+    tally.finish(out);
 }
 
 } // namespace
