@@ -12,31 +12,15 @@ import numpy as np
 import pytest
 
 import helpers
-from spliser_amd import cli, combine as cmb, native, process as proc, samio, sites, synth, tsv
+import plancases
+from spliser_amd import cli, combine as cmb, native, process as proc, samio, synth
 
 pytestmark = pytest.mark.gpu
 
 
 def _oracle_tsv(oracle_lib, bed, wl, stranded, cryptic, gff=None):
-    """The .SpliSER.tsv text the reference's rules give for a workload: host Steps 0-2 (golden-pinned) + the oracle."""
-    bins = sites.GeneBins.from_annotation(gff, "gene", "All") if gff else sites.GeneBins()
-    table = sites.SiteTable(bins, is_stranded=bool(stranded))
-    table.add_bed(bed)
-    table.find_competitors()
-    scode = native.STRANDED_CODE[stranded]
-    text = [tsv.HEADER]
-    names = wl.genome.chrom_names
-    for chrom in table.chrom_index:
-        arr = table.chrom_arrays(chrom)
-        if arr.n == 0:
-            continue
-        rd = wl.reads[names.index(chrom)]
-        cnt = oracle_lib.check_bam(arr.pos, arr.strand, arr.part_off, arr.part_pos, arr.comp_off, arr.comp_pos, rd.pos, rd.flag,
-                                   rd.cig_off, rd.cigar, scode, 0)
-        b2s, b2c, b2w, sse = oracle_lib.beta2_sse(arr.pos, arr.part_off, arr.part_pos, arr.part_site, arr.alpha, arr.edge_cnt,
-                                                  cnt[0], cnt[1], cnt[2], cryptic)
-        text.extend(tsv.format_chrom(arr, dict(beta1=cnt[0], beta2_simple=b2s, beta2_cryptic=b2c, beta2_weighted=b2w, sse=sse), cryptic))
-    return "".join(text)
+    """The .SpliSER.tsv text the reference's rules give for a workload (``plancases.oracle_tsv`` over its read sets)."""
+    return plancases.oracle_tsv(oracle_lib, bed, wl.genome.chrom_names, wl.reads, stranded, cryptic, gff)
 
 
 def _files(wl, prefix, seq_mode=0):
