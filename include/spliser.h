@@ -703,6 +703,38 @@ int spl_gene_fragment_rule_host(int64_t n_reads, const int32_t *pos, const uint1
                                 int32_t shift, int stranded, int64_t n_a, const int32_t *a_start, const uint32_t *a_code, int64_t n_b, const int32_t *b_start,
                                 const uint32_t *b_code, int64_t n_genes, int64_t *results_out /* n_reads */);
 
+/* ---- a reproducible fraction of a set's reads ----------------------------------------------------------------------------------
+ * Replaces `samtools view -s SEED.FRAC` in front of another run of the whole pipeline (twenty of them for a saturation curve; RSeQC's
+ * junction_saturation.py makes one of junctions, from a sorted file, in a Python loop).  The reference has no counterpart.  The rule
+ * is csrc/spl_subsample_rule.h, which the kernels and the host hook compile alike.  A read's decision depends on its name and the
+ * seed only:
+ *   k = name key (above);  if k == 0 ("no name"):  k = (uint64)(uint32)POS << 32 | (uint64)FLAG << 16 | (n_ops & 0xffff)
+ *   z = k ^ (seed * 0x9e3779b97f4a7c15)                                                              (mod 2^64)
+ *   z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9;  z = (z ^ z >> 27) * 0x94d049bb133111eb;  z ^= z >> 31
+ *   u = z >> 32;   keep  <=>  u < threshold,   threshold in 0 .. 2^32  (2^32 keeps every read, 0 none)
+ * POS is the file's 1-based position, before any shard shift.  So both mates of a pair, and every secondary and supplementary
+ * record of a name, share one decision; for one seed the kept sets are nested (T1 <= T2: kept(T1) is a subset of kept(T2)); and the
+ * decision depends neither on the reads' order nor on the container.  Parity with samtools' choice of reads is not intended and
+ * would mean nothing for a random subset.
+ * spl_reads_subsample: `dr` is a finished, FUSED read set whose arrays have name keys; *out is a finished, fused set on new arrays
+ * that it owns -- the kept reads in their order (an order-preserving compaction on the device: two launches, a tile of
+ * spl_subsample_tile() reads a wave, a scan of the tiles' totals between them, no atomics: the same words from run to run), the
+ * segments of `dr` with their shifts (a segment that keeps no read is none of *out's, as a chromosome without a read is none of any
+ * set's), strand bytes and name keys carried when `dr` has them.  Whatever takes a finished fused set takes *out, this call
+ * included.  `dr` is untouched and may be freed before or after *out.  kept_per_seg (or null): per segment of `dr` that has reads,
+ * in the order they were added, the reads kept.  kept_index_out (or null; room for every read of `dr`): the number within `dr` of
+ * the i-th read of *out.  A set without a read gives a set without a read, and so does a selection that keeps none.  SPL_ERR_ARG,
+ * after which the context stays usable: a set that is not finished, not fused or without name keys; a threshold beyond 2^32.
+ * Test hooks: spl_subsample_keep_host (no GPU: the rule over one segment's host arrays, keep_out[i] = 1 where read i is kept),
+ * spl_subsample_tile (the kernels' tile).  spl_reads_n_segments: the segments of a set that have reads, in the order they were
+ * added -- the entries kept_per_seg gets, the numbers spl_mate_table takes. */
+int spl_reads_subsample(spl_ctx *ctx, const spl_dreads *dr, uint64_t seed, uint64_t threshold, spl_dreads **out, int64_t *kept_per_seg /* n_seg, or NULL */,
+                        uint32_t *kept_index_out /* or NULL */);
+int spl_subsample_keep_host(int64_t n, const uint64_t *name_key, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, uint64_t seed, uint64_t threshold,
+                            uint8_t *keep_out);
+int spl_subsample_tile(void);
+int spl_reads_n_segments(const spl_dreads *dr, int64_t *out);
+
 /* ---- the lanes of the counting passes (test hook, no GPU) ----------------------------------------------------------------------
  * Which stream a counting pass runs on and which recorded events it waits for is a rule of its own (csrc/spl_lanes.h; INTEGRATION.md,
  * "streams"), which spl_reads_relayout, spl_count_launch, spl_pass_barrier and the joins of every other entry point follow.

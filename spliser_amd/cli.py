@@ -189,8 +189,33 @@ def build_parser(fragment_switches=False):
     j.add_argument("-m", "--minIntron", dest="minIntron", type=int, default=70, help="regtools -m")
     j.add_argument("-M", "--maxIntron", dest="maxIntron", type=int, default=500000, help="regtools -M; 0 = no limit")
     j.add_argument("--anyOrder", dest="anyOrder", default=False, action="store_true", help=ANY_ORDER_HELP)
+    # (default SUPPRESS: without the switches the parsed arguments are what they were, key for key)
+    j.add_argument("--subsample", dest="subsample", type=float, default=argparse.SUPPRESS, metavar="FRAC",
+                   help="(this build only; changes results) the junctions of a fraction of the reads, 0 < FRAC <= 1, chosen on the GPU by a hash of "
+                        "the read's name and --seed: mates stay together, and the same names are kept whatever the file's order or container "
+                        "(not samtools view -s' choice of reads)")
+    j.add_argument("--seed", dest="seed", type=int, default=argparse.SUPPRESS, help="(with --subsample) the seed of the choice, 0 .. 2^64 - 1 - default: 0")
     _filter_flags(j)
     _engine_flags(j)
+    u = sub.add_parser("saturation", help="(this build only) junctions and SpliSER sites at nested subsamples of the reads, from one decode, on the GPU: how many sites "
+                                          "pass -r now, and whether more would with more reads (no samtools view -s, no second run)")
+    u.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    u.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="output prefix: .saturation.tsv is appended")
+    u.add_argument("--steps", dest="steps", type=int, default=20, help="rows of the table: step k of K holds the fraction k / K of the reads, 1..100 - default: 20")
+    u.add_argument("--seed", dest="seed", type=int, default=0, help="the seed of the choice of reads (a hash of the read's name and this), 0 .. 2^64 - 1 - default: 0")
+    u.add_argument("-r", "--minReads", dest="minReads", type=int, default=10,
+                   help="a site passes with alpha_count + beta1_count + beta2Simple_count of at least this (output's and combineShallow's -r), a junction with "
+                        "this score - default: 10")
+    u.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False, help="optional: one chromosome only")
+    u.add_argument("--isStranded", dest="isStranded", default=False, action="store_true")
+    u.add_argument("-s", "--strandedType", dest="strandedType", nargs="?", type=str, required=False,
+                   help='"fr" or "rf" (not "auto": the `strandedness` command tells which)')
+    u.add_argument("-a", "--minAnchor", dest="minAnchor", type=int, default=8, help="as for junctions (regtools -a)")
+    u.add_argument("-m", "--minIntron", dest="minIntron", type=int, default=70, help="regtools -m")
+    u.add_argument("-M", "--maxIntron", dest="maxIntron", type=int, default=500000, help="regtools -M; 0 = no limit")
+    _decode_flags(u)
+    _filter_flags(u)
+    _engine_flags(u)
     s = sub.add_parser("strandedness", help="(this build only) is the library unstranded, fr or rf?  Tallied from the BAM on the GPU: " + AUTO_HELP)
     s.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
     s.add_argument("-A", "--annotationFile", dest="annotationFile", required=False,
@@ -381,11 +406,31 @@ def main(argv=None):
                 parser.error("--genome %s: %s" % (kwargs["genome"], exc.strerror))
             if magic == b"\x1f\x8b":
                 parser.error("--genome %s is compressed: pass the uncompressed FASTA the aligner's index was built from" % kwargs["genome"])
+    if command == "saturation":
+        if kwargs.get("strandedType") == "auto":
+            parser.error("saturation: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
+        if kwargs.get("isStranded") and kwargs.get("strandedType") not in ("fr", "rf"):
+            parser.error("saturation: --isStranded requires --strandedType/-s as fr or rf")
+        if not 1 <= kwargs["steps"] <= 100:
+            parser.error("saturation: --steps must be in 1..100")
+        if kwargs["minReads"] < 1:
+            parser.error("saturation: -r / --minReads must be at least 1")
+        if not 0 <= kwargs["seed"] < 1 << 64:
+            parser.error("saturation: --seed must be in 0 .. 2^64 - 1")
+        if min(kwargs["minAnchor"], kwargs["minIntron"], kwargs["maxIntron"]) < 0:
+            parser.error("--minAnchor / --minIntron / --maxIntron must not be negative")
+    if command == "junctions":
+        if "seed" in kwargs and "subsample" not in kwargs:
+            parser.error("junctions: --seed belongs to --subsample")
+        if "subsample" in kwargs and not 0.0 < kwargs["subsample"] <= 1.0:
+            parser.error("junctions: --subsample must be a fraction in (0, 1]")
+        if "seed" in kwargs and not 0 <= kwargs["seed"] < 1 << 64:
+            parser.error("junctions: --seed must be in 0 .. 2^64 - 1")
     if command in ("process", "junctions", "strandedness") and kwargs.get("minEvidence") is not None and kwargs["minEvidence"] < 0:
         parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts", "exoncounts", "intronretention"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts", "exoncounts", "intronretention", "saturation"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -426,6 +471,9 @@ def main(argv=None):
     elif command == "junctions":
         from .junctions import junctions
         junctions(devices=devices, threads=threads, **kwargs)
+    elif command == "saturation":
+        from .saturation import saturation
+        saturation(devices=devices, threads=threads, **kwargs)
     elif command == "strandedness":
         from .strandedness import strandedness
         strandedness(devices=devices, threads=threads, **kwargs)

@@ -60,6 +60,8 @@
 #include "spl_genome.h"
 #include "spl_motif.h"
 #include "spl_motif_rule.h"
+#include "spl_subsample.h"
+#include "spl_subsample_rule.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -5019,6 +5021,136 @@ extern "C" int spl_mate_table(spl_ctx *c, const spl_dreads *dr, int seg, uint32_
     }
     return SPL_OK;
 }
+
+// ---- a reproducible fraction of a set's reads (spl_subsample.hip; the rule is spl_subsample_rule.h) ------------------------------
+// The read set of the reads of `dr` that the rule keeps under (seed, threshold): new arrays that *out owns, the same segments with
+// the same shifts (a segment that keeps no read is none of *out, as a chromosome without reads is none of any set).  Two launches
+// with the scan of the tiles' totals between them, and ONE wait of the host in the middle, for the sizes of the new arrays.
+extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t seed, uint64_t threshold, spl_dreads **out, int64_t *kept_per_seg, uint32_t *kept_index_out)
+{
+    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: null argument");
+    *out = nullptr;
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: the read set is not finished (spl_reads_finish)");
+    if (threshold > SPL_SUBSAMPLE_ALL) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: threshold %llu is beyond 2^32 (which keeps every read)", (unsigned long long)threshold);
+    if (const int rc = fused_refusal("spl_reads_subsample", dr)) return rc;
+    if (!dr->segs.empty() && !dr->groups[0].src->name_key)
+        return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: the reads have no name keys (spl_bam_set_mate_keys before the decode, or spl_soa_upload4)");
+    HIP_TRY(hipSetDevice(c->device));
+    struct Sets { // (what is made here goes unless it is handed out)
+        spl_ctx *c; spl_dreads *d = nullptr; DeviceReads *dev = nullptr;
+        ~Sets() { if (d) spl_reads_free(c, d); if (dev) free_device_reads(dev); }
+    } made{c};
+    const size_t n_seg = dr->segs.size();
+    std::vector<splsub::Seg> segs(n_seg);
+    uint64_t n_tiles = 0;
+    int64_t base = 0;
+    for (size_t k = 0; k < n_seg; ++k) {
+        const spl_layout_seg &ls = dr->groups[0].segs[dr->segs[k].group_seg];
+        segs[k] = splsub::Seg{ls.first, ls.n_reads, base, n_tiles};
+        n_tiles += (uint64_t)((ls.n_reads + (int64_t)splsub::TILE - 1) / (int64_t)splsub::TILE);
+        base += ls.n_reads;
+        if (kept_per_seg) kept_per_seg[k] = 0;
+    }
+    std::vector<uint32_t> ends(2 * std::max<size_t>(n_seg, 1), 0u);
+    DevBuf d_segs, d_rows, d_ends, d_work, d_index;
+    splsub::Src src{};
+    const uint64_t salt = spl_subsample_salt(seed);
+    if (n_tiles) {
+        const DeviceReads *from = dr->groups[0].src;
+        src = splsub::Src{(const int32_t *)from->pos, (const uint16_t *)from->flag, (const uint32_t *)from->cig_off, (const uint32_t *)from->cigar, (const uint8_t *)from->xs,
+                          (const uint64_t *)from->name_key, from->n_rec, from->n_ops};
+        for (const splsub::Seg &s : segs)
+            if (s.first < 0 || s.n < 0 || s.first + s.n > from->n_rec) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: a segment outside the device arrays");
+        HIP_TRY(d_segs.get(sizeof(splsub::Seg) * n_seg, c->stream));
+        HIP_TRY(d_rows.get(4 * 2 * (size_t)n_tiles, c->stream));
+        HIP_TRY(d_ends.get(4 * 2 * n_seg, c->stream));
+        HIP_TRY(d_work.get(spl_dev_sort_work_bytes(n_tiles), c->stream));
+        HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), sizeof(splsub::Seg) * n_seg, hipMemcpyHostToDevice, c->stream));
+        {
+            // bytes: a read's key and its two CIGAR offsets (POS and FLAG only without a name)
+            splprof::Scope prof("spl_subsample_count_kernel", c->stream, 12.0 * (double)dr->n_reads);
+            HIP_TRY((hipError_t)spl_dev_launch_subsample_count(&src, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, salt, threshold, d_rows.as<uint32_t>(), c->stream));
+        }
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_rows.as<uint32_t>(), n_tiles, d_work.p, c->stream));
+        HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_rows.as<uint32_t>() + n_tiles, n_tiles, d_work.p, c->stream));
+        HIP_TRY((hipError_t)spl_dev_launch_subsample_ends(d_rows.as<uint32_t>(), d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, d_ends.as<uint32_t>(), c->stream));
+        HIP_TRY(hipMemcpyAsync(ends.data(), d_ends.p, 4 * 2 * n_seg, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream)); // (the copy reads `segs` and writes `ends`: both are the host's from here)
+    }
+    const int64_t kept = n_seg ? (int64_t)ends[n_seg - 1] : 0, kept_ops = n_seg ? (int64_t)ends[2 * n_seg - 1] : 0;
+    for (size_t k = 0; k < n_seg; ++k) { // (sums that ascend, and no more than there was: said for the memory's sake)
+        const int64_t r0 = k ? ends[k - 1] : 0, o0 = k ? ends[n_seg + k - 1] : 0;
+        if ((int64_t)ends[k] < r0 || (int64_t)ends[k] - r0 > segs[k].n || (int64_t)ends[n_seg + k] < o0 || kept_ops > src.n_ops)
+            return spl_set_error(SPL_ERR_HIP, "spl_reads_subsample: the scan of the kept reads went wrong");
+    }
+    {
+        const int rc = spl_reads_begin_sized(c, kept, &made.d);
+        if (rc) return rc;
+    }
+    if (kept) {
+        DeviceReads *dev = made.dev = new (std::nothrow) DeviceReads();
+        if (!dev) return spl_set_error(SPL_ERR_NOMEM, "out of host memory");
+        dev->device = c->device;
+        dev->n_rec = kept; dev->n_ops = kept_ops;
+        dev->ref_first.assign(n_seg, 0); dev->ref_n.assign(n_seg, 0); dev->ref_max.assign(n_seg, 0); dev->ref_ops.assign(n_seg, 0);
+        HIP_TRY(devmem::get(&dev->pos, 4 * (size_t)kept + 64, 'b'));
+        HIP_TRY(devmem::get(&dev->flag, 2 * (size_t)kept + 64, 'b'));
+        HIP_TRY(devmem::get(&dev->cig_off, 4 * ((size_t)kept + 1) + 64, 'b'));
+        HIP_TRY(devmem::get(&dev->cigar, 4 * (size_t)kept_ops + 64, 'b'));
+        if (src.xs) HIP_TRY(devmem::get(&dev->xs, (size_t)kept + 64, 'b'));
+        HIP_TRY(devmem::get(&dev->name_key, 8 * (size_t)kept + 64, 'b'));
+        if (kept_index_out) HIP_TRY(d_index.get(4 * (size_t)kept, c->stream));
+        const splsub::Dst dst{(int32_t *)dev->pos, (uint16_t *)dev->flag, (uint32_t *)dev->cig_off, (uint32_t *)dev->cigar, (uint8_t *)dev->xs, (uint64_t *)dev->name_key,
+                              kept_index_out ? d_index.as<uint32_t>() : nullptr, kept, kept_ops};
+        {
+            // bytes: what launch 1 read, and of the kept reads every array read and written, the index beside them
+            splprof::Scope prof("spl_subsample_write_kernel", c->stream, 12.0 * (double)dr->n_reads + (2.0 * (src.xs ? 19.0 : 18.0) + 4.0) * (double)kept + 8.0 * (double)kept_ops);
+            HIP_TRY((hipError_t)spl_dev_launch_subsample_write(&src, &dst, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, salt, threshold, d_rows.as<uint32_t>(), c->stream));
+        }
+        if (kept_index_out) HIP_TRY(hipMemcpyAsync(kept_index_out, d_index.p, 4 * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream)); // (the scratch goes back to the pool behind this, and `dr` may be freed at once)
+        for (size_t k = 0; k < n_seg; ++k) {
+            const int64_t r0 = k ? ends[k - 1] : 0, o0 = k ? ends[n_seg + k - 1] : 0, n_k = (int64_t)ends[k] - r0, ops_k = (int64_t)ends[n_seg + k] - o0;
+            dev->ref_first[k] = r0; dev->ref_n[k] = n_k; dev->ref_ops[k] = ops_k;
+            if (kept_per_seg) kept_per_seg[k] = n_k;
+            const int rc = add_segment_device(c, made.d, dev, r0, n_k, ops_k, dr->segs[k].shift, -1); // (no read ends beyond where one of `dr` ended: its shift was fit for them)
+            if (rc) return rc;
+        }
+    }
+    {
+        const int rc = finish_reads(c, made.d);
+        if (rc) return rc;
+    }
+    *out = made.d;
+    made.d = nullptr; // (the set holds its own reference to the arrays; the one made here goes with `made`)
+    return SPL_OK;
+}
+
+// The rule on the host over one segment's arrays (test hook, no GPU): keep_out[i] = 1 where read i is kept.
+extern "C" int spl_subsample_keep_host(int64_t n, const uint64_t *name_key, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, uint64_t seed, uint64_t threshold,
+                                       uint8_t *keep_out)
+{
+    if (n < 0 || (n && (!name_key || !pos || !flag || !cig_off || !keep_out))) return spl_set_error(SPL_ERR_ARG, "spl_subsample_keep_host: null argument");
+    if (threshold > SPL_SUBSAMPLE_ALL) return spl_set_error(SPL_ERR_ARG, "spl_subsample_keep_host: threshold %llu is beyond 2^32", (unsigned long long)threshold);
+    const uint64_t salt = spl_subsample_salt(seed);
+    const int64_t n_ops_total = n ? (int64_t)cig_off[n] : 0; // (the cigar array's size: a read's ops as the kernels take them, spl_ops_of)
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t c0, n_ops;
+        spl_ops_of(cig_off, i, n_ops_total, &c0, &n_ops);
+        keep_out[i] = spl_subsample_keep(name_key[i], (int64_t)pos[i], flag[i], n_ops, salt, threshold) ? 1 : 0;
+    }
+    return SPL_OK;
+}
+
+// The segments of a read set that have reads, in the order they were added: what spl_mate_table numbers and spl_reads_subsample's kept_per_seg has an entry for.
+extern "C" int spl_reads_n_segments(const spl_dreads *d, int64_t *out)
+{
+    if (!d || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_n_segments: null argument");
+    *out = (int64_t)d->segs.size();
+    return SPL_OK;
+}
+
+extern "C" int spl_subsample_tile(void) { return (int)spl_dev_subsample_tile(); }
 
 // spl_coverage per fragment (the rule is spl_covfragment_rule.h): the arguments are spl_coverage's; the set must have name keys.
 extern "C" int spl_coverage_fragments(spl_ctx *c, const spl_dreads *dr, int64_t length, int stranded, int strand, spl_cov **out)

@@ -70,14 +70,48 @@ def run_plans(plans, job):
         raise errors[0]
 
 
+def subsample_threshold(fraction):
+    """``--subsample FRAC`` -> the rule's threshold (``spl_reads_subsample``): FRAC of 2^32, rounded down; FRAC in (0, 1]."""
+    fraction = float(fraction)
+    if not 0.0 < fraction <= 1.0:
+        raise ValueError("subsample: the fraction must be in (0, 1]")
+    return int(fraction * 4294967296.0)
+
+
+_kept_lock = threading.Lock()
+
+
 @contextlib.contextmanager
-def fused_set(ctx, source, chrom, add, with_keys=False, with_strand=False):
+def _selected(dr, subsample, kept):
+    """``dr`` itself, or -- ``subsample`` = (seed, threshold) -- the set of its reads that the rule keeps, selected on the device and
+    freed on the way out (None when none is kept).  ``kept`` (or None): a list whose two entries get the reads kept and the reads
+    they were selected from added."""
+    if dr is None or subsample is None:
+        yield dr
+        return
+    sel, _ = dr.subsample(*subsample)
+    try:
+        if kept is not None:
+            with _kept_lock:
+                kept[0] += sel.n
+                kept[1] += dr.n
+        yield sel if sel.n else None
+    finally:
+        sel.free()
+
+
+@contextlib.contextmanager
+def fused_set(ctx, source, chrom, add, with_keys=False, with_strand=False, subsample=None, kept=None):
     """One entry of a plan as a finished read set on ``ctx`` -- None when the chromosome has no read --, freed on the way out.  Reads
     on the host (``add`` None) go up as four arrays, ``with_keys`` / ``with_strand``: with their name keys / strand bytes, which the
-    source must have (``DecodeOptions.mate_keys`` / ``aux_strand``)."""
+    source must have (``DecodeOptions.mate_keys`` / ``aux_strand``).  ``subsample`` = (seed, threshold): the set handed out is the
+    one ``DeviceReads.subsample`` selects from it (the source needs name keys; reads on the host go up with theirs), and ``kept`` (a list of two) gets the reads
+    kept and the reads they were selected from added."""
+    with_keys = with_keys or subsample is not None
     if add is not None:
         with ctx.begin_reads() as dr:
-            yield dr.finish() if add(dr) else None
+            with _selected(dr.finish() if add(dr) else None, subsample, kept) as out:
+                yield out
         return
     rs = source.reads(chrom)
     if rs is None or not rs.n:
@@ -91,7 +125,8 @@ def fused_set(ctx, source, chrom, add, with_keys=False, with_strand=False):
     with ctx.upload_soa([arrays], [getattr(rs, "max_end", None)], with_keys=with_keys, with_strand=with_strand) as soa:
         with ctx.begin_reads() as dr:
             dr.add_soa(soa, 0)
-            yield dr.finish()
+            with _selected(dr.finish(), subsample, kept) as out:
+                yield out
 
 
 def over_fused_sets(source, devices, chroms, visit, with_keys=False, with_strand=False):
