@@ -735,6 +735,43 @@ int spl_subsample_keep_host(int64_t n, const uint64_t *name_key, const int32_t *
 int spl_subsample_tile(void);
 int spl_reads_n_segments(const spl_dreads *dr, int64_t *out);
 
+/* ---- PCR duplicates ------------------------------------------------------------------------------------------------------------
+ * Replaces Picard MarkDuplicates / `samtools fixmate` + `samtools markdup` in front of --excludeFlags 0x400: both want a
+ * coordinate-sorted copy of the file and rewrite it.  The reference has no counterpart.  The rule is csrc/spl_dup_rule.h, which
+ * the kernels (csrc/spl_dups.hip) and the host hook compile alike; tests/dupcases.py restates it.  Per segment of a finished,
+ * FUSED set with name keys:
+ *   EXAMINED: mapped, primary, QC-passed, not supplementary, POS >= 1, an op at least (an incoming 0x400 is ignored); every other
+ *   record is never marked.
+ *   FRAGMENTS, over the segment's mate table: an examined read with a mate of higher index LEADS a pair fragment; one without a mate
+ *   leads a single fragment; the other read of a pair belongs to its leader's fragment.  examined = 2 * pairs + singles.
+ *   THE UNCLIPPED 5' END of a read: cl / ct = the sum of the S and H ops before the first / after the last op that is neither
+ *   (every op a clip: cl is their sum, ct = 0), L = the sum of the M, D, N, =, X lengths, o = FLAG bit 0x10;
+ *   u = POS - cl when o = 0, else POS + L - 1 + ct, in 64 bits, clamped to [-2^31, 2^31 - 1].
+ *   THE SIGNATURE: for a pair, end A is the smaller of the two reads' ends by (u, o), on a tie the read with FLAG 0x40; B the other.
+ *     W0 = (uA + 2^31) << 3 | oA << 2 | paired << 1 | (paired && A's read has 0x40)
+ *     W1 = paired ? (uB + 2^31) << 1 | oB : 0
+ *     W2 = the name key (both mates share it; 0 for a nameless read)
+ *   DUPLICATES: fragments of one segment with equal (W0, W1) are a group; the one with the smallest W2 is its representative, ties
+ *   to the lowest leader index; every other fragment is a duplicate, and both of its reads are marked.
+ * The same NAMES are marked whatever the file's order or container -- for named reads only (nameless fragments tie at W2 = 0).
+ * Deliberate differences from Picard and samtools (parity intended and unpinned; yardstick tests/dupcases.py): the representative
+ * is chosen by name hash, not by quality sum (no qualities are decoded); a pair split over two chromosomes or by a decode filter is
+ * two single fragments; singles compete only with singles; secondary, supplementary, QC-failed and unmapped records are never
+ * marked; no optical duplicates, no UMIs.
+ * spl_reads_duplicates: `seg` as for spl_mate_table, and SPL_ERR_ARG where that refuses.  The segment's marks are built at the
+ * first call (the mate table first) and kept with the set, one byte a read.  host_out (or null): a byte per read of the segment, 1 =
+ * duplicate.  counts (or null), seven: reads of the segment, examined, pair fragments, single fragments, duplicate pairs, duplicate
+ * singles, examined reads whose incoming FLAG has 0x400.  hist (or null), 257: groups of 1 .. 255 fragments, of 256 or more, and
+ * the fragments of the groups in that last bin.  Integer atomics only: the same words from run to run.
+ * spl_reads_dedup: spl_reads_subsample's contract with the keep decision "not marked": *out is a finished, fused set on its own
+ * arrays, segments and shifts, strand bytes and name keys carried; `dr` is untouched.
+ * spl_duplicates_host (no GPU, test hook): the rule header over one segment's host arrays and its mate table behind a stable sort
+ * on the host; dup_out: a byte per read; counts: seven; hist: 257, or null. */
+int spl_reads_duplicates(spl_ctx *ctx, const spl_dreads *dr, int seg, uint8_t *host_out, int64_t *counts /* 7, or NULL */, int64_t *hist /* 257, or NULL */);
+int spl_reads_dedup(spl_ctx *ctx, const spl_dreads *dr, spl_dreads **out, int64_t *kept_per_seg /* n_seg, or NULL */, uint32_t *kept_index_out /* or NULL */);
+int spl_duplicates_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint64_t *name_key, const uint32_t *mate,
+                        uint8_t *dup_out, int64_t *counts /* 7 */, int64_t *hist /* 257, or NULL */);
+
 /* ---- the lanes of the counting passes (test hook, no GPU) ----------------------------------------------------------------------
  * Which stream a counting pass runs on and which recorded events it waits for is a rule of its own (csrc/spl_lanes.h; INTEGRATION.md,
  * "streams"), which spl_reads_relayout, spl_count_launch, spl_pass_barrier and the joins of every other entry point follow.

@@ -48,6 +48,10 @@ Extra sub-command ``intronretention -B x.bam -A genes.gtf -o PREFIX [-t exon] [-
 the IR ratio, taken on the GPU from the decode -- IRFinder's measure, without a sorted BAM and a second tool (``intronretention.py``).
 ``--fragments``: depth and splice counts per fragment -- ``coverage --fragments``' depth, and a junction both mates cross counted once.
 ``junctions`` and ``process`` have no such switch: the BED score feeds alpha, which stays per read beside beta1 / beta2.
+Extra sub-command ``duplicates -B x.bam -o PREFIX [-c CHROM]`` writes ``PREFIX.duplicates.tsv`` and ``PREFIX.duplicates.hist.tsv``: per
+chromosome the fragments and the PCR duplicate fragments among them, and the histogram of duplicate group sizes, marked on the GPU
+from the decode -- no sorted copy, no ``fixmate``, no rewritten file (``duplicates.py``).  ``--dedup`` (``junctions``, ``genecounts``,
+``saturation``; changes results): the command runs on the reads that are not marked.
 Not read: CRAM, a pipe, and compressed text that has no ``@`` header line (uncompressed, the Python reader still takes that).
 """
 import argparse
@@ -195,6 +199,7 @@ def build_parser(fragment_switches=False):
                         "the read's name and --seed: mates stay together, and the same names are kept whatever the file's order or container "
                         "(not samtools view -s' choice of reads)")
     j.add_argument("--seed", dest="seed", type=int, default=argparse.SUPPRESS, help="(with --subsample) the seed of the choice, 0 .. 2^64 - 1 - default: 0")
+    j.add_argument("--dedup", dest="dedup", default=argparse.SUPPRESS, action="store_true", help=DEDUP_HELP + "; with --subsample the fraction is chosen first")
     _filter_flags(j)
     _engine_flags(j)
     u = sub.add_parser("saturation", help="(this build only) junctions and SpliSER sites at nested subsamples of the reads, from one decode, on the GPU: how many sites "
@@ -214,8 +219,18 @@ def build_parser(fragment_switches=False):
     u.add_argument("-m", "--minIntron", dest="minIntron", type=int, default=70, help="regtools -m")
     u.add_argument("-M", "--maxIntron", dest="maxIntron", type=int, default=500000, help="regtools -M; 0 = no limit")
     _decode_flags(u)
+    u.add_argument("--dedup", dest="dedup", default=argparse.SUPPRESS, action="store_true",
+                   help=DEDUP_HELP + "; every step's set is deduplicated behind its selection, and the table gets the column reads_before_dedup")
     _filter_flags(u)
     _engine_flags(u)
+    d = sub.add_parser("duplicates", help="(this build only) the library's PCR duplicate rate from the decode, on the GPU: fragments, duplicate fragments and the "
+                                          "histogram of group sizes per chromosome -- no sorted copy, no fixmate, no rewritten file")
+    d.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
+    d.add_argument("-o", "--outputPath", dest="outputPath", required=True, help="output prefix: .duplicates.tsv and .duplicates.hist.tsv are appended")
+    d.add_argument("-c", "--chromosome", dest="qChrom", nargs="?", default="All", type=str, required=False, help="optional: one chromosome only")
+    _decode_flags(d)
+    _filter_flags(d)
+    _engine_flags(d)
     s = sub.add_parser("strandedness", help="(this build only) is the library unstranded, fr or rf?  Tallied from the BAM on the GPU: " + AUTO_HELP)
     s.add_argument("-B", "--BAMFile", dest="inBAM", required=True)
     s.add_argument("-A", "--annotationFile", dest="annotationFile", required=False,
@@ -264,6 +279,7 @@ def build_parser(fragment_switches=False):
     n.add_argument("--fragments", dest="fragments", default=False, action="store_true",
                    help="paired-end: mates are paired on the GPU by a key of their names and a fragment counts once, by both mates' blocks "
                         "(htseq-count's and featureCounts -p --countReadPairs' way); a pair split over two chromosomes or by the read filter counts as two")
+    n.add_argument("--dedup", dest="dedup", default=argparse.SUPPRESS, action="store_true", help=DEDUP_HELP + "; with --fragments the mates are paired behind it")
     _filter_flags(n)
     _engine_flags(n)
     x = sub.add_parser("exoncounts", help="(this build only) reads per exon counting bin for edgeR::diffSpliceDGE / DEXSeq, counted on the GPU from the decode "
@@ -341,6 +357,10 @@ AUTO_HELP = ("every read's strand is held against the XS:A tag of the spliced re
              "source >= 90%% of the reads agreeing with fr means fr, <= 10%% rf, 40..60%% unstranded, anything else (or two sources that differ) "
              "undetermined: a stated policy, not a measurement")
 MIN_EVIDENCE_HELP = "(-s auto, strandedness) reads with evidence a source needs to be heard - default: 1000"
+
+DEDUP_HELP = ("(this build only; changes results) PCR duplicate fragments are marked on the GPU and left out, as after MarkDuplicates and --excludeFlags 0x400 "
+              "without the sorted copy: fragments of one chromosome with the same unclipped 5' ends and orientations are one group, the one with the "
+              "smallest name hash stays (the `duplicates` command reports the rate; Picard's choice by base quality is not made)")
 
 ANY_ORDER_HELP = ("(this build only; changes no result) the BAM may be in any record order, e.g. as the aligner wrote it: its reads are "
                   "coordinate-sorted on the GPU after the decode instead of by samtools sort beforehand")
@@ -430,7 +450,7 @@ def main(argv=None):
         parser.error("--minEvidence must not be negative")
     if command in ("process", "junctions") and kwargs.get("strandFromXS") and kwargs.get("isStranded"):
         parser.error("--strandFromXS and --isStranded are alternatives: the strand of the aligner's tag, or the strand of the read")
-    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts", "exoncounts", "intronretention", "saturation"):
+    if command in ("process", "combine", "combineShallow", "junctions", "flagstat", "strandedness", "coverage", "genecounts", "exoncounts", "intronretention", "saturation", "duplicates"):
         if not 0 <= kwargs["minMapQ"] <= 255:
             parser.error("--minMapQ must be in 0..255")
         if not (0 <= kwargs["requireFlags"] <= 65535 and 0 <= kwargs["excludeFlags"] <= 65535):
@@ -474,6 +494,9 @@ def main(argv=None):
     elif command == "saturation":
         from .saturation import saturation
         saturation(devices=devices, threads=threads, **kwargs)
+    elif command == "duplicates":
+        from .duplicates import duplicates
+        duplicates(devices=devices, threads=threads, **kwargs)
     elif command == "strandedness":
         from .strandedness import strandedness
         strandedness(devices=devices, threads=threads, **kwargs)

@@ -62,6 +62,8 @@
 #include "spl_motif_rule.h"
 #include "spl_subsample.h"
 #include "spl_subsample_rule.h"
+#include "spl_dups.h"
+#include "spl_dup_rule.h"
 
 // ---- error plumbing -------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -506,6 +508,10 @@ struct spl_dreads {
     // read of the arrays, a segment's at its reads' places, the mate as an index within the segment; three counters a segment.
     mutable uint32_t *mates = nullptr;
     mutable std::vector<int64_t> mate_counts;
+    // The duplicate marks of such a set (spl_reads_duplicates): made on first use, kept with the set.  One byte a read of the arrays,
+    // a segment's at its reads' places; seven counters and a histogram of SPL_DUP_HIST sums a segment.
+    mutable uint8_t *dups = nullptr;
+    mutable std::vector<int64_t> dup_counts, dup_hist;
 };
 
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
@@ -4012,6 +4018,7 @@ extern "C" void spl_reads_free(spl_ctx *c, spl_dreads *d)
     for (spl_dreads::Group &g : d->groups) { devmem::put(g.slab); devmem::put(g.d_segs); free_device_reads(g.src); }
     devmem::put(d->ctl);
     devmem::put(d->mates);
+    devmem::put(d->dups);
     delete d;
 }
 
@@ -5026,15 +5033,17 @@ extern "C" int spl_mate_table(spl_ctx *c, const spl_dreads *dr, int seg, uint32_
 // The read set of the reads of `dr` that the rule keeps under (seed, threshold): new arrays that *out owns, the same segments with
 // the same shifts (a segment that keeps no read is none of *out, as a chromosome without reads is none of any set).  Two launches
 // with the scan of the tiles' totals between them, and ONE wait of the host in the middle, for the sizes of the new arrays.
-extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t seed, uint64_t threshold, spl_dreads **out, int64_t *kept_per_seg, uint32_t *kept_index_out)
+// `dup` null: the subsampling rule under (seed, threshold); else the reads whose byte of `dup` (one per entry of the arrays) is 0 (spl_reads_dedup).
+static int reads_compact(spl_ctx *c, const spl_dreads *dr, const char *who, const uint8_t *dup, uint64_t seed, uint64_t threshold, spl_dreads **out, int64_t *kept_per_seg,
+                         uint32_t *kept_index_out)
 {
-    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: null argument");
+    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "%s: null argument", who);
     *out = nullptr;
-    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: the read set is not finished (spl_reads_finish)");
-    if (threshold > SPL_SUBSAMPLE_ALL) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: threshold %llu is beyond 2^32 (which keeps every read)", (unsigned long long)threshold);
-    if (const int rc = fused_refusal("spl_reads_subsample", dr)) return rc;
+    if (!dr->finished) return spl_set_error(SPL_ERR_ARG, "%s: the read set is not finished (spl_reads_finish)", who);
+    if (threshold > SPL_SUBSAMPLE_ALL) return spl_set_error(SPL_ERR_ARG, "%s: threshold %llu is beyond 2^32 (which keeps every read)", who, (unsigned long long)threshold);
+    if (const int rc = fused_refusal(who, dr)) return rc;
     if (!dr->segs.empty() && !dr->groups[0].src->name_key)
-        return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: the reads have no name keys (spl_bam_set_mate_keys before the decode, or spl_soa_upload4)");
+        return spl_set_error(SPL_ERR_ARG, "%s: the reads have no name keys (spl_bam_set_mate_keys before the decode, or spl_soa_upload4)", who);
     HIP_TRY(hipSetDevice(c->device));
     struct Sets { // (what is made here goes unless it is handed out)
         spl_ctx *c; spl_dreads *d = nullptr; DeviceReads *dev = nullptr;
@@ -5060,7 +5069,7 @@ extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t se
         src = splsub::Src{(const int32_t *)from->pos, (const uint16_t *)from->flag, (const uint32_t *)from->cig_off, (const uint32_t *)from->cigar, (const uint8_t *)from->xs,
                           (const uint64_t *)from->name_key, from->n_rec, from->n_ops};
         for (const splsub::Seg &s : segs)
-            if (s.first < 0 || s.n < 0 || s.first + s.n > from->n_rec) return spl_set_error(SPL_ERR_ARG, "spl_reads_subsample: a segment outside the device arrays");
+            if (s.first < 0 || s.n < 0 || s.first + s.n > from->n_rec) return spl_set_error(SPL_ERR_ARG, "%s: a segment outside the device arrays", who);
         HIP_TRY(d_segs.get(sizeof(splsub::Seg) * n_seg, c->stream));
         HIP_TRY(d_rows.get(4 * 2 * (size_t)n_tiles, c->stream));
         HIP_TRY(d_ends.get(4 * 2 * n_seg, c->stream));
@@ -5068,8 +5077,9 @@ extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t se
         HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), sizeof(splsub::Seg) * n_seg, hipMemcpyHostToDevice, c->stream));
         {
             // bytes: a read's key and its two CIGAR offsets (POS and FLAG only without a name)
-            splprof::Scope prof("spl_subsample_count_kernel", c->stream, 12.0 * (double)dr->n_reads);
-            HIP_TRY((hipError_t)spl_dev_launch_subsample_count(&src, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, salt, threshold, d_rows.as<uint32_t>(), c->stream));
+            splprof::Scope prof(dup ? "spl_dedup_count_kernel" : "spl_subsample_count_kernel", c->stream, (dup ? 13.0 : 12.0) * (double)dr->n_reads);
+            HIP_TRY((hipError_t)(dup ? spl_dev_launch_dedup_count(&src, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, dup, d_rows.as<uint32_t>(), c->stream)
+                                     : spl_dev_launch_subsample_count(&src, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, salt, threshold, d_rows.as<uint32_t>(), c->stream)));
         }
         HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_rows.as<uint32_t>(), n_tiles, d_work.p, c->stream));
         HIP_TRY((hipError_t)spl_dev_launch_sort_scan(d_rows.as<uint32_t>() + n_tiles, n_tiles, d_work.p, c->stream));
@@ -5081,7 +5091,7 @@ extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t se
     for (size_t k = 0; k < n_seg; ++k) { // (sums that ascend, and no more than there was: said for the memory's sake)
         const int64_t r0 = k ? ends[k - 1] : 0, o0 = k ? ends[n_seg + k - 1] : 0;
         if ((int64_t)ends[k] < r0 || (int64_t)ends[k] - r0 > segs[k].n || (int64_t)ends[n_seg + k] < o0 || kept_ops > src.n_ops)
-            return spl_set_error(SPL_ERR_HIP, "spl_reads_subsample: the scan of the kept reads went wrong");
+            return spl_set_error(SPL_ERR_HIP, "%s: the scan of the kept reads went wrong", who);
     }
     {
         const int rc = spl_reads_begin_sized(c, kept, &made.d);
@@ -5104,8 +5114,10 @@ extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t se
                               kept_index_out ? d_index.as<uint32_t>() : nullptr, kept, kept_ops};
         {
             // bytes: what launch 1 read, and of the kept reads every array read and written, the index beside them
-            splprof::Scope prof("spl_subsample_write_kernel", c->stream, 12.0 * (double)dr->n_reads + (2.0 * (src.xs ? 19.0 : 18.0) + 4.0) * (double)kept + 8.0 * (double)kept_ops);
-            HIP_TRY((hipError_t)spl_dev_launch_subsample_write(&src, &dst, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, salt, threshold, d_rows.as<uint32_t>(), c->stream));
+            splprof::Scope prof(dup ? "spl_dedup_write_kernel" : "spl_subsample_write_kernel", c->stream,
+                                (dup ? 13.0 : 12.0) * (double)dr->n_reads + (2.0 * (src.xs ? 19.0 : 18.0) + 4.0) * (double)kept + 8.0 * (double)kept_ops);
+            HIP_TRY((hipError_t)(dup ? spl_dev_launch_dedup_write(&src, &dst, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, dup, d_rows.as<uint32_t>(), c->stream)
+                                     : spl_dev_launch_subsample_write(&src, &dst, d_segs.as<splsub::Seg>(), (uint32_t)n_seg, n_tiles, salt, threshold, d_rows.as<uint32_t>(), c->stream)));
         }
         if (kept_index_out) HIP_TRY(hipMemcpyAsync(kept_index_out, d_index.p, 4 * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream)); // (the scratch goes back to the pool behind this, and `dr` may be freed at once)
@@ -5123,6 +5135,208 @@ extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t se
     }
     *out = made.d;
     made.d = nullptr; // (the set holds its own reference to the arrays; the one made here goes with `made`)
+    return SPL_OK;
+}
+
+extern "C" int spl_reads_subsample(spl_ctx *c, const spl_dreads *dr, uint64_t seed, uint64_t threshold, spl_dreads **out, int64_t *kept_per_seg, uint32_t *kept_index_out)
+{
+    return reads_compact(c, dr, "spl_reads_subsample", nullptr, seed, threshold, out, kept_per_seg, kept_index_out);
+}
+
+// ---- PCR duplicates (spl_dups.hip; the rule is spl_dup_rule.h) -------------------------------------------------------------------
+namespace {
+// The digits (of 8 bits, least significant first) a word of `bits` significant bits is sorted by: the others cannot differ.
+uint32_t dup_digits(uint32_t bits) { return (bits + 7u) / 8u; }
+
+// The duplicate marks of every segment of a finished, fused set whose arrays have name keys, made once (dr->dups, dr->dup_counts,
+// dr->dup_hist), behind the set's mate table.  Per segment: the leaders' marks and their scan, ONE wait of the host for the number
+// of fragments, the signatures, the sort by (W0, W1, W2) -- least significant word first, the next word gathered by the
+// permutation between words, 8 + 5 + 5 stable passes --, the marks and the groups' sizes.
+int dups_of(spl_ctx *c, const spl_dreads *dr, const char *who)
+{
+    if (const int rc = mates_of(c, dr, who)) return rc;
+    if (dr->segs.empty() || dr->dups) return SPL_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const spl_dreads::Group &g = dr->groups[0];
+    const size_t n_seg = dr->segs.size();
+    int64_t most = 0;
+    for (const spl_dreads::Segment &seg : dr->segs) most = std::max<int64_t>(most, g.segs[seg.group_seg].n_reads);
+    void *marks = nullptr;
+    HIP_TRY(devmem::get(&marks, (size_t)std::max<int64_t>(g.src->n_rec, 1) + 64, 'b'));
+    struct Put { void *p; ~Put() { devmem::put(p); } } keep{marks};
+    HIP_TRY(hipMemsetAsync(marks, 0, (size_t)std::max<int64_t>(g.src->n_rec, 1), c->stream));
+    const size_t n_sums = (size_t)(SPL_DUP_COUNTERS + SPL_DUP_HIST) * n_seg; // a segment's counters, then its histogram
+    DevBuf d_sums, d_work, d_lead, d_w[3], d_keys[2], d_perm[2], d_leader;
+    HIP_TRY(d_sums.get(8 * n_sums, c->stream));
+    HIP_TRY(hipMemsetAsync(d_sums.p, 0, 8 * n_sums, c->stream));
+    HIP_TRY(d_work.get(spl_dev_sort_work_bytes((uint64_t)std::max<int64_t>(most, 1)), c->stream));
+    HIP_TRY(d_lead.get(4 * (size_t)std::max<int64_t>(most, 1), c->stream));
+    const splsub::Src src{(const int32_t *)g.src->pos, (const uint16_t *)g.src->flag, (const uint32_t *)g.src->cig_off, (const uint32_t *)g.src->cigar, (const uint8_t *)g.src->xs,
+                          (const uint64_t *)g.src->name_key, g.src->n_rec, g.src->n_ops};
+    uint64_t cap = 0; // elements the scratch arrays hold
+    for (size_t k = 0; k < n_seg; ++k) {
+        const spl_layout_seg &ls = g.segs[dr->segs[k].group_seg];
+        const int64_t n = ls.n_reads;
+        if (n <= 0) continue;
+        if (ls.first < 0 || ls.first + n > g.src->n_rec) return spl_set_error(SPL_ERR_ARG, "%s: a segment outside the device arrays", who);
+        const uint32_t *mate = dr->mates + ls.first;
+        unsigned long long *counters = d_sums.as<unsigned long long>() + (size_t)(SPL_DUP_COUNTERS + SPL_DUP_HIST) * k, *hist = counters + SPL_DUP_COUNTERS;
+        uint32_t *lead = d_lead.as<uint32_t>();
+        uint32_t n_el = 0;
+        {
+            // bytes: FLAG, POS and the two CIGAR offsets of a read and of its mate, the table's word, the mark and its scan
+            splprof::Scope prof("spl_dup_lead", c->stream, 40.0 * (double)n);
+            HIP_TRY((hipError_t)spl_dev_launch_dup_lead(&src, ls.first, n, mate, lead, counters, c->stream));
+            HIP_TRY((hipError_t)spl_dev_launch_sort_scan(lead, (uint64_t)n, d_work.p, c->stream));
+            HIP_TRY(hipMemcpyAsync(&n_el, lead + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        if ((int64_t)n_el > n) return spl_set_error(SPL_ERR_HIP, "%s: the scan of the leading reads went wrong", who);
+        if (!n_el) continue;
+        if (n_el > cap) {
+            for (int q = 0; q < 3; ++q) { d_w[q].release(); HIP_TRY(d_w[q].get(8 * (size_t)n_el, c->stream)); }
+            for (int q = 0; q < 2; ++q) {
+                d_keys[q].release(); d_perm[q].release();
+                HIP_TRY(d_keys[q].get(8 * (size_t)n_el, c->stream));
+                HIP_TRY(d_perm[q].get(4 * (size_t)n_el, c->stream));
+            }
+            d_leader.release();
+            HIP_TRY(d_leader.get(4 * (size_t)n_el, c->stream));
+            cap = n_el;
+        }
+        {
+            // bytes: what the lead kernel read, a fragment's ops (two of them here), key and element
+            splprof::Scope prof("spl_dup_signature_kernel", c->stream, 8.0 * (double)n + (32.0 + 8.0 + 28.0) * (double)n_el);
+            HIP_TRY((hipError_t)spl_dev_launch_dup_signature(&src, ls.first, n, mate, lead, (int64_t)n_el, d_w[0].as<uint64_t>(), d_w[1].as<uint64_t>(), d_w[2].as<uint64_t>(),
+                                                             d_leader.as<uint32_t>(), c->stream));
+        }
+        int kcur = 0, pcur = 0; // where the keys and the permutation are
+        bool first_word = true;
+        static const char *const word_name[3] = {"spl_dup_sort_w0", "spl_dup_sort_w1", "spl_dup_sort_w2"};
+        const uint32_t digits[3] = {dup_digits(SPL_DUP_W0_BITS), dup_digits(SPL_DUP_W1_BITS), 8u};
+        for (int w = 2; w >= 0; --w) { // (least significant word first)
+            splprof::Scope prof(word_name[w], c->stream, (double)digits[w] * 2.0 * 12.0 * (double)n_el);
+            const uint64_t *in = d_w[w].as<uint64_t>();
+            if (!first_word) {
+                HIP_TRY((hipError_t)spl_dev_launch_gather_u64(d_perm[pcur].as<uint32_t>(), n_el, in, d_keys[kcur].as<uint64_t>(), c->stream));
+                in = d_keys[kcur].as<uint64_t>();
+            }
+            for (uint32_t d = 0; d < digits[w]; ++d) {
+                const bool identity = first_word && d == 0u;
+                const int kout = (first_word && d == 0u) ? 0 : kcur ^ 1, pout = identity ? 0 : pcur ^ 1;
+                HIP_TRY((hipError_t)spl_dev_launch_sort_pass(in, identity ? nullptr : d_perm[pcur].as<uint32_t>(), n_el, 8u * d, d_keys[kout].as<uint64_t>(), d_perm[pout].as<uint32_t>(),
+                                                             d_work.p, c->stream));
+                kcur = kout; pcur = pout;
+                in = d_keys[kcur].as<uint64_t>();
+            }
+            kcur ^= 1; // (the next word is gathered into the other buffer; behind the last word kcur ^ 1 has W0 in order)
+            first_word = false;
+        }
+        const uint64_t *w0_sorted = d_keys[kcur ^ 1].as<uint64_t>();
+        uint64_t *w1_sorted = d_keys[kcur].as<uint64_t>();
+        {
+            splprof::Scope prof("spl_dup_mark_kernel", c->stream, (8.0 + 4.0 + 16.0) * (double)n_el);
+            HIP_TRY((hipError_t)spl_dev_launch_gather_u64(d_perm[pcur].as<uint32_t>(), n_el, d_w[1].as<uint64_t>(), w1_sorted, c->stream));
+            HIP_TRY((hipError_t)spl_dev_launch_dup_mark(w0_sorted, w1_sorted, d_perm[pcur].as<uint32_t>(), d_leader.as<uint32_t>(), (int64_t)n_el, mate, n, (uint8_t *)marks + ls.first,
+                                                        c->stream));
+        }
+        {
+            splprof::Scope prof("spl_dup_groups_kernel", c->stream, 16.0 * (double)n_el);
+            HIP_TRY((hipError_t)spl_dev_launch_dup_groups(w0_sorted, w1_sorted, (int64_t)n_el, hist, counters, c->stream));
+        }
+    }
+    std::vector<unsigned long long> got(n_sums, 0ull);
+    HIP_TRY(hipMemcpyAsync(got.data(), d_sums.p, 8 * n_sums, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dr->dup_counts.assign((size_t)SPL_DUP_COUNTERS * n_seg, 0);
+    dr->dup_hist.assign((size_t)SPL_DUP_HIST * n_seg, 0);
+    for (size_t k = 0; k < n_seg; ++k) {
+        const unsigned long long *from = got.data() + (size_t)(SPL_DUP_COUNTERS + SPL_DUP_HIST) * k;
+        for (int q = 0; q < SPL_DUP_COUNTERS; ++q) dr->dup_counts[SPL_DUP_COUNTERS * k + (size_t)q] = (int64_t)from[q];
+        dr->dup_counts[SPL_DUP_COUNTERS * k] = g.segs[dr->segs[k].group_seg].n_reads;
+        for (int q = 0; q < SPL_DUP_HIST; ++q) dr->dup_hist[SPL_DUP_HIST * k + (size_t)q] = (int64_t)from[SPL_DUP_COUNTERS + q];
+    }
+    dr->dups = (uint8_t *)marks;
+    keep.p = nullptr;
+    return SPL_OK;
+}
+} // namespace
+
+// The duplicate marks of segment `seg` (numbered as spl_mate_table numbers them) of a finished, fused read set with name keys:
+// host_out (or null) gets a byte per read of the segment, counts (or null) the seven counters, hist (or null) the SPL_DUP_HIST sums.
+// The marks are made at the first call and kept with the set.
+extern "C" int spl_reads_duplicates(spl_ctx *c, const spl_dreads *dr, int seg, uint8_t *host_out, int64_t *counts, int64_t *hist)
+{
+    if (!c || !dr) return spl_set_error(SPL_ERR_ARG, "spl_reads_duplicates: null argument");
+    if (const int rc = dups_of(c, dr, "spl_reads_duplicates")) return rc;
+    if (dr->segs.empty() && seg >= 0) { // (a set without a read has no segment and no marks)
+        if (counts) for (int k = 0; k < SPL_DUP_COUNTERS; ++k) counts[k] = 0;
+        if (hist) for (int k = 0; k < SPL_DUP_HIST; ++k) hist[k] = 0;
+        return SPL_OK;
+    }
+    if (seg < 0 || (size_t)seg >= dr->segs.size()) return spl_set_error(SPL_ERR_ARG, "spl_reads_duplicates: no segment %d", seg);
+    const spl_layout_seg &ls = dr->groups[0].segs[dr->segs[(size_t)seg].group_seg];
+    if (counts) for (int k = 0; k < SPL_DUP_COUNTERS; ++k) counts[k] = dr->dup_counts[SPL_DUP_COUNTERS * (size_t)seg + (size_t)k];
+    if (hist) for (int k = 0; k < SPL_DUP_HIST; ++k) hist[k] = dr->dup_hist[SPL_DUP_HIST * (size_t)seg + (size_t)k];
+    if (host_out && ls.n_reads > 0) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMemcpyAsync(host_out, dr->dups + ls.first, (size_t)ls.n_reads, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return SPL_OK;
+}
+
+// The read set of the reads of `dr` that are no duplicates: spl_reads_subsample's contract, the keep decision the marks'.
+extern "C" int spl_reads_dedup(spl_ctx *c, const spl_dreads *dr, spl_dreads **out, int64_t *kept_per_seg, uint32_t *kept_index_out)
+{
+    if (!c || !dr || !out) return spl_set_error(SPL_ERR_ARG, "spl_reads_dedup: null argument");
+    *out = nullptr;
+    if (const int rc = dups_of(c, dr, "spl_reads_dedup")) return rc;
+    return reads_compact(c, dr, "spl_reads_dedup", dr->dups, 0, SPL_SUBSAMPLE_ALL, out, kept_per_seg, kept_index_out);
+}
+
+// The rule on the host over one segment's arrays and its mate table, behind a stable sort (test hook, no GPU): dup_out[r] = 1 where
+// read r is marked; counts: the seven counters; hist (or null): the SPL_DUP_HIST sums.
+extern "C" int spl_duplicates_host(int64_t n_reads, const int32_t *pos, const uint16_t *flag, const uint32_t *cig_off, const uint32_t *cigar, const uint64_t *name_key,
+                                   const uint32_t *mate, uint8_t *dup_out, int64_t *counts, int64_t *hist)
+{
+    if (n_reads < 0 || n_reads > 0xfffffff0LL || (n_reads && (!pos || !flag || !cig_off || !name_key || !mate || !dup_out)) || !counts)
+        return spl_set_error(SPL_ERR_ARG, "spl_duplicates_host: null argument");
+    if (n_reads && cig_off[n_reads] && !cigar) return spl_set_error(SPL_ERR_ARG, "spl_duplicates_host: cigar is null");
+    const spl_read_view reads{pos, flag, cig_off, cigar, n_reads ? (int64_t)cig_off[n_reads] : 0};
+    for (int k = 0; k < SPL_DUP_COUNTERS; ++k) counts[k] = 0;
+    if (hist) for (int k = 0; k < SPL_DUP_HIST; ++k) hist[k] = 0;
+    counts[0] = n_reads;
+    struct El { spl_dup_sig sig; uint32_t leader; };
+    std::vector<El> el;
+    for (int64_t r = 0; r < n_reads; ++r) {
+        dup_out[r] = 0;
+        spl_frag_side me, its;
+        const uint32_t what = spl_dup_sides(reads, 0, n_reads, r, mate, &me, &its);
+        if (what == SPL_FRAG_OUT) continue;
+        counts[1] += 1;
+        if (me.flag & 0x400u) counts[6] += 1;
+        if (what != SPL_FRAG_LEADS) continue;
+        counts[its.n_ops ? 2 : 3] += 1;
+        el.push_back(El{spl_dup_signature(reads, me, its, name_key[r]), (uint32_t)r});
+    }
+    std::stable_sort(el.begin(), el.end(), [](const El &a, const El &b) {
+        return a.sig.w0 != b.sig.w0 ? a.sig.w0 < b.sig.w0 : a.sig.w1 != b.sig.w1 ? a.sig.w1 < b.sig.w1 : a.sig.w2 < b.sig.w2;
+    });
+    const int64_t n_el = (int64_t)el.size();
+    std::vector<uint64_t> w0((size_t)n_el), w1((size_t)n_el);
+    std::vector<uint32_t> perm((size_t)n_el), leader((size_t)n_el);
+    for (int64_t j = 0; j < n_el; ++j) { w0[(size_t)j] = el[(size_t)j].sig.w0; w1[(size_t)j] = el[(size_t)j].sig.w1; perm[(size_t)j] = (uint32_t)j; leader[(size_t)j] = el[(size_t)j].leader; }
+    for (int64_t j = 0; j < n_el; ++j) {
+        (void)spl_dup_mark_element(w0.data(), w1.data(), perm.data(), leader.data(), n_el, j, mate, n_reads, dup_out);
+        if (j && spl_dup_same(w0.data(), w1.data(), j - 1, j)) continue;
+        const int64_t size = spl_dup_group_end(w0.data(), w1.data(), n_el, j) - j;
+        counts[(w0[(size_t)j] & 2ull) ? 4 : 5] += size - 1;
+        if (hist) {
+            hist[std::min<int64_t>(size, SPL_DUP_BINS) - 1] += 1;
+            if (size >= SPL_DUP_BINS) hist[SPL_DUP_BINS] += size;
+        }
+    }
     return SPL_OK;
 }
 

@@ -43,17 +43,30 @@ WV_DEV void tile_range(const Seg *segs, uint32_t n_seg, uint64_t t, int64_t *lo,
     *base = s.base + (at < s.n ? at : s.n);
 }
 
-// Entry i of the arrays: its key, ops and the decision.  (POS and FLAG are read only for a read without a name.)
-WV_DEV bool keep_at(const Src &s, int64_t i, uint64_t salt, uint64_t threshold, uint64_t *key, uint32_t *c0, uint32_t *n_ops)
+// THE KEEP DECISION is a parameter of the two bodies: keep(s, i, key, n_ops) for entry i of the arrays, whose key and op count the
+// body has loaded.  HashKeep is the subsampling rule (POS and FLAG are read only for a read without a name); spl_dups_wave.h has
+// the second one, a byte a read (spl_reads_dedup).
+struct HashKeep {
+    uint64_t salt, threshold;
+    SPL_HD bool operator()(const Src &s, int64_t i, uint64_t key, uint32_t n_ops) const
+    {
+        if (key != 0ull) return (uint64_t)spl_subsample_draw(key, salt) < threshold;
+        return spl_subsample_keep(0ull, (int64_t)s.pos[i], (uint32_t)s.flag[i], n_ops, salt, threshold);
+    }
+};
+
+// Entry i of the arrays: its key, ops and the decision.
+template <class Keep>
+WV_DEV bool keep_at(const Src &s, int64_t i, const Keep &keep, uint64_t *key, uint32_t *c0, uint32_t *n_ops)
 {
     *key = s.key[i];
     spl_ops_of(s.cig_off, i, s.n_ops, c0, n_ops);
-    if (*key != 0ull) return (uint64_t)spl_subsample_draw(*key, salt) < threshold;
-    return spl_subsample_keep(0ull, (int64_t)s.pos[i], (uint32_t)s.flag[i], *n_ops, salt, threshold);
+    return keep(s, i, *key, *n_ops);
 }
 
 // Launch 1: tile t's totals -> reads_out[t], ops_out[t].
-WV_DEV void tile_count(const Src &s, int64_t lo, int64_t hi, uint64_t salt, uint64_t threshold, uint32_t *reads_out, uint32_t *ops_out)
+template <class Keep>
+WV_DEV void tile_count_by(const Src &s, int64_t lo, int64_t hi, const Keep &keep, uint32_t *reads_out, uint32_t *ops_out)
 {
     const uint32_t lane = wv::lane();
     uint32_t reads = 0u, ops = 0u;
@@ -63,14 +76,20 @@ WV_DEV void tile_count(const Src &s, int64_t lo, int64_t hi, uint64_t salt, uint
         if (i >= hi || i >= s.n_rec) continue; // (i < n_rec always: said for the memory's sake)
         uint64_t key;
         uint32_t c0, n_ops;
-        if (keep_at(s, i, salt, threshold, &key, &c0, &n_ops)) { reads += 1u; ops += n_ops; }
+        if (keep_at(s, i, keep, &key, &c0, &n_ops)) { reads += 1u; ops += n_ops; }
     }
     const uint32_t reads_inc = wv::scan_add(reads), ops_inc = wv::scan_add(ops);
     if (lane == 63u) { *reads_out = reads_inc; *ops_out = ops_inc; }
 }
 
+WV_DEV void tile_count(const Src &s, int64_t lo, int64_t hi, uint64_t salt, uint64_t threshold, uint32_t *reads_out, uint32_t *ops_out)
+{
+    tile_count_by(s, lo, hi, HashKeep{salt, threshold}, reads_out, ops_out);
+}
+
 // Launch 3: the tile's kept reads to the places read0 .. of d, their ops to op0 ..; base: the source set's number of the read at lo.
-WV_DEV void tile_write(const Src &s, const Dst &d, int64_t lo, int64_t hi, int64_t base, uint64_t salt, uint64_t threshold, uint32_t read0, uint32_t op0)
+template <class Keep>
+WV_DEV void tile_write_by(const Src &s, const Dst &d, int64_t lo, int64_t hi, int64_t base, const Keep &keep_rule, uint32_t read0, uint32_t op0)
 {
     const uint32_t lane = wv::lane();
     const uint64_t in_front = lane ? (~0ull >> (64u - lane)) : 0ull; // the lanes below this one
@@ -80,7 +99,7 @@ WV_DEV void tile_write(const Src &s, const Dst &d, int64_t lo, int64_t hi, int64
         const bool have = i < hi && i < s.n_rec;
         uint64_t key = 0ull;
         uint32_t c0 = 0u, n_ops = 0u;
-        const bool keep = have && keep_at(s, i, salt, threshold, &key, &c0, &n_ops);
+        const bool keep = have && keep_at(s, i, keep_rule, &key, &c0, &n_ops);
         const uint64_t kept = wv::ballot(keep);
         const uint32_t mine = keep ? n_ops : 0u;
         const uint32_t ops_inc = wv::scan_add(mine);
@@ -108,6 +127,11 @@ WV_DEV void tile_write(const Src &s, const Dst &d, int64_t lo, int64_t hi, int64
         read0 += wv::popc64(kept);
         op0 += ops_round;
     }
+}
+
+WV_DEV void tile_write(const Src &s, const Dst &d, int64_t lo, int64_t hi, int64_t base, uint64_t salt, uint64_t threshold, uint32_t read0, uint32_t op0)
+{
+    tile_write_by(s, d, lo, hi, base, HashKeep{salt, threshold}, read0, op0);
 }
 
 } // namespace splsub

@@ -186,17 +186,19 @@ def add_row(rows, chrom, row):
         got += row
 
 
-def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None, fragments=False, mates=None):
+def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chrom=None, fragments=False, mates=None, dedup=False, removed=None):
     """``spl_gene_count`` over every chromosome of ``chroms`` -> int64[n_genes + 3], the sums: the genes' reads, then no feature,
     ambiguous, not counted.  On the plan of ``readsets.over_fused_sets``: counts add over reads, so the pieces of a decode in shares are
     counted where they lie and the host adds.  ``maps``: {chrom: (map a, map b)} (``maps_of``); a chromosome without one has no feature.
     ``per_chrom``: a dict that gets, per chromosome with reads, int64[4]: counted, no feature, ambiguous, not counted.
     ``fragments``: ``spl_gene_count_fragments`` -- a pair of mates counts once; the source was decoded with ``mate_keys`` and not in
     shares (an error otherwise).  ``mates``: a dict that then gets, per chromosome with reads, int64[4]: reads, pairable reads, reads
-    with a mate, pairable reads without one whose flag says the mate is mapped."""
+    with a mate, pairable reads without one whose flag says the mate is mapped.  ``dedup``: every set is counted without its
+    duplicate fragments (``readsets.fused_set``: name keys and one device, as for ``fragments``); ``removed``: a list whose two entries
+    get the reads removed and the reads they were removed from added."""
     n_genes = int(n_genes)
     total, lock = np.zeros(n_genes + 3, np.int64), threading.Lock()
-    if fragments:
+    if fragments or dedup:
         readsets.check_fragment_source(source)
 
     def count(dr, chrom):
@@ -209,7 +211,7 @@ def counts_of_source(source, devices, chroms, maps, n_genes, stranded=0, per_chr
             total[:] += t
             add_row(per_chrom, chrom, verdicts)
 
-    readsets.over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments))
+    readsets.over_fused_sets(source, devices, chroms, count, with_keys=bool(fragments or dedup), dedup=bool(dedup), removed=removed)
     return total
 
 
@@ -252,16 +254,18 @@ def write_counts(path, ids, counts, only=None):
 
 
 def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id", qChrom="All", isStranded=False, strandedType=None, devices=(0,), threads=0, log=None,
-               gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False, fragments=False):
+               gpuDecode=None, minMapQ=0, requireFlags=0, excludeFlags=0, anyOrder=False, fragments=False, dedup=False):
     """The ``genecounts`` command: one decode, the annotation read meanwhile, ``<outputPath>.genecounts.tsv``.  ``qChrom``: the reads
     of that chromosome, and the genes with a feature on it.  ``fragments``: a pair of mates counts once (the module's text); the
-    file's format is the same.  -> int64[n_genes + 3], the counts written."""
+    file's format is the same.  ``dedup``: the reads that are no PCR duplicates are counted (``spl_reads_dedup``): what the command
+    writes of a file from which the marked reads have been taken.  -> int64[n_genes + 3], the counts written."""
     log = _process.logger(log)
     if annotationFile is None:
         raise ValueError("genecounts: an annotation file (-A) is required")
     stranded = _process.stranded_code("genecounts", isStranded, strandedType)
-    devices = _process.one_device(devices, log, "--fragments: the alignment file is decoded and counted") if fragments else tuple(devices)
-    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(fragments))
+    devices = (_process.one_device(devices, log, "%s: the alignment file is decoded and counted" % ("--fragments" if fragments else "--dedup")) if fragments or dedup
+               else tuple(devices))
+    options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), any_order=bool(anyOrder), mate_keys=bool(fragments or dedup))
     with _process.decoding(inBAM, devices, gpuDecode, threads, options, log=log) as source:
         t0 = timeit.default_timer()
         features = read_features(annotationFile, aType, idAttr)
@@ -271,8 +275,11 @@ def genecounts(inBAM, annotationFile, outputPath, aType="exon", idAttr="gene_id"
         chroms = _process.chroms_of(source, qChrom)
         maps = maps_of(features, chroms, stranded)
         per_chrom, mates = {}, ({} if fragments else None)
-        counts = counts_of_source(source, devices, chroms, maps, n_genes, stranded, per_chrom, fragments=bool(fragments), mates=mates)
+        n_removed = [0, 0]
+        counts = counts_of_source(source, devices, chroms, maps, n_genes, stranded, per_chrom, fragments=bool(fragments), mates=mates, dedup=bool(dedup), removed=n_removed)
         log_verdicts(chroms, per_chrom, mates, log)
+        if dedup:
+            log("  (dedup: %d of %d reads removed as duplicates)" % (n_removed[0], n_removed[1]))
         _process.log_filter(source, options.read_filter, log)
     only = None if qChrom == "All" else features.genes_on(qChrom)
     path = outputPath + SUFFIX

@@ -156,7 +156,7 @@ def drop_noncanonical(tables, chroms, genome, source, devices, log):
     return out
 
 
-def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, maxIntron, tally=None, motif=None, subsample=None, kept=None):
+def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, maxIntron, tally=None, motif=None, subsample=None, kept=None, dedup=False, removed=None):
     """The junction table of every chromosome of ``chroms`` that has reads, from an alignment source whose decode has been
     started (``process.open_and_decode``): -> {chrom: (reads, table)}.  On the plan of ``readsets``: after a decode on the device
     the read sets are fused and stay so (``spl_junctions`` reads the arrays; nothing is laid out, nothing decoded again by whoever
@@ -171,7 +171,11 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
     made (``spl_reads_motif_strand``) -- the decode's XS walk has left the array, its cost accepted.  ``subsample`` = (seed,
     threshold): every set's table is that of the reads the subsampling rule keeps (``readsets.fused_set``: selected on the device; the
     source must have been opened with ``mate_keys``, and reads on the host go up as arrays with their keys); ``kept``: a list whose
-    two entries get the reads kept and the reads they were selected from added."""
+    two entries get the reads kept and the reads they were selected from added.  ``dedup``: every set's table is that of the set
+    without its duplicate fragments (``readsets.fused_set``; behind ``subsample``), ``removed``: a list whose two entries get the reads
+    removed and the reads they were removed from added."""
+    if dedup:
+        readsets.check_fragment_source(source)
     from_xs = stranded == native.STRAND_FROM_XS
     if motif is not None and not from_xs:
         raise ValueError("strand from motif is the mode of the reads' strand bytes (STRAND_FROM_XS)")
@@ -189,10 +193,10 @@ def tables_of_source(source, devices, chroms, stranded, minAnchor, minIntron, ma
         return rs.n
 
     def job(ctx, chrom, add):
-        if add is None and not from_xs and subsample is None:
+        if add is None and not from_xs and subsample is None and not dedup:
             def add(dr):
                 return add_host(dr, chrom)
-        with readsets.fused_set(ctx, source, chrom, add, with_strand=from_xs, subsample=subsample, kept=kept) as dr:
+        with readsets.fused_set(ctx, source, chrom, add, with_strand=from_xs, subsample=subsample, kept=kept, dedup=dedup, removed=removed) as dr:
             if dr is None:
                 return
             if motif is not None:
@@ -224,7 +228,7 @@ def check_motif_options(genome, strandFromMotif, canonicalOnly, isStranded, stra
 
 def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=8, minIntron=70, maxIntron=500000,
               qChrom="All", devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, strandFromXS=False, anyOrder=False,
-              minEvidence=None, genome=None, strandFromMotif=False, canonicalOnly=False, subsample=None, seed=0):
+              minEvidence=None, genome=None, strandFromMotif=False, canonicalOnly=False, subsample=None, seed=0, dedup=False):
     """Writes ``outputPath`` (a BED12 file) and returns the number of junctions.  ``strandedType="auto"``: the library's strandedness
     is inferred first, from the reads' XS:A tags (``strandedness.py``), and the call goes on as if the verdict had been passed.  ``minMapQ`` / ``requireFlags`` / ``excludeFlags``:
     the read filter of ``process`` (samtools view's -q / -f / -F; changes results) -- the junctions of the reads that pass.
@@ -237,8 +241,12 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
     junctions whose motif is none of the six are not written.  ``subsample`` (this build only; changes results): a fraction in
     (0, 1] -- the junctions of that share of the reads, chosen by name and ``seed`` on the GPU (``spl_reads_subsample``: mates stay
     together, the same names whatever the file's order or container; not samtools view -s' choice of reads): what this command writes
-    of a file that holds exactly those reads."""
+    of a file that holds exactly those reads.  ``dedup`` (this build only; changes results): the junctions of the reads that are no
+    PCR duplicates (``spl_reads_dedup``; the rule is ``csrc/spl_dup_rule.h``), behind ``subsample`` when both are given: what this
+    command writes of a file from which the marked reads have been taken."""
     log = _process.logger(log)
+    if dedup:
+        devices = _process.one_device(devices, log, "--dedup: the alignment file is decoded and deduplicated")
     selection = None if subsample is None else (int(seed), readsets.subsample_threshold(subsample))
     if selection is not None and not 0 <= selection[0] < 1 << 64:
         raise ValueError("seed must be in 0 .. 2^64 - 1")
@@ -255,7 +263,7 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
     if from_bytes:
         stranded = native.STRAND_FROM_XS
     options = _process.DecodeOptions(_process.read_filter(minMapQ, requireFlags, excludeFlags), aux_strand=bool(from_bytes or auto), any_order=bool(anyOrder),
-                                     mate_keys=selection is not None)
+                                     mate_keys=selection is not None or bool(dedup))
     fasta = GenomeOnDevices(genome) if genome is not None else None
     try:
         with _process.decoding(inBAM, devices, None, threads, options, log=log) as source:   # (on the GPU(s), like `process`)
@@ -267,14 +275,16 @@ def junctions(inBAM, outputPath, isStranded=False, strandedType=None, minAnchor=
             if anyOrder:
                 _process.log_any_order(source, log)
             tally = [0, 0, 0] if strandFromXS else None
-            n_kept = [0, 0]
+            n_kept, n_removed = [0, 0], [0, 0]
             tables = tables_of_source(source, tuple(devices), chroms, stranded, minAnchor, minIntron, maxIntron, tally=tally, motif=fasta if strandFromMotif else None,
-                                      subsample=selection, kept=n_kept)
+                                      subsample=selection, kept=n_kept, dedup=bool(dedup), removed=n_removed)
             if isinstance(source, native.BamFile) and not source.wait_all():
                 raise native.SpliserNativeError(-5, "%s is not sorted by reference: sort it (samtools sort) first" % inBAM)
             _process.log_filter(source, options.read_filter, log)
             if selection is not None:
                 log("  (subsample: %d of %d reads kept, fraction %r, seed %d)" % (n_kept[0], n_kept[1], float(subsample), selection[0]))
+            if dedup:
+                log("  (dedup: %d of %d reads removed as duplicates)" % (n_removed[0], n_removed[1]))
             if strandFromXS:
                 log_xs_tally(tally, log)
             if strandFromMotif:

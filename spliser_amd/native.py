@@ -54,7 +54,7 @@ EXPORTS = [
     "spl_pack_host", "spl_reads_free", "spl_count_launch", "spl_sse_launch", "spl_counters_download",
     "spl_sse_download", "spl_count_algorithmic_bytes", "spl_literal_queue_size", "spl_last_launch_info", "spl_bam_open", "spl_bam_open_stream", "spl_bam_open_deferred", "spl_bam_set_filter", "spl_bam_set_aux_strand", "spl_bam_set_mate_keys", "spl_bam_mate_keys", "spl_bam_aux_strand", "spl_bam_aux_strand_host", "spl_bam_filter_counts", "spl_bam_set_flagstat", "spl_bam_flagstat", "spl_flagstat_add_host", "spl_bam_set_any_order", "spl_bam_any_order_sorted", "spl_sort_keys_device", "spl_text_windows_host", "spl_text_line_index", "spl_bam_decode_device", "spl_bam_reserve_device", "spl_bam_share_plan", "spl_bam_share_range", "spl_bam_share_info", "spl_bam_share_count_host", "spl_bam_share_ref", "spl_bam_decode_device_share", "spl_bam_decoded_on_device", "spl_bam_wait_device", "spl_bam_start", "spl_bam_compression_ratio", "spl_bam_sample", "spl_bam_wait_ref", "spl_bam_wait_all", "spl_bam_cancel", "spl_bam_decline_reason", "spl_sam_open", "spl_bam_is_text", "spl_bam_text_compression", "spl_bam_text_blocks", "spl_bam_close",
     "spl_bam_n_ref", "spl_bam_ref_name", "spl_bam_ref_length", "spl_bam_n_records", "spl_bam_reads", "spl_bam_write", "spl_bam_write2",
-    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_junctions_fragments", "spl_junction_fragment_rule_host", "spl_strand_tally", "spl_strand_rule_host", "spl_genome_open", "spl_genome_n", "spl_genome_name", "spl_genome_bases", "spl_genome_stats", "spl_genome_free", "spl_genome_pack_host", "spl_reads_motif_strand", "spl_motif_read_strand_host", "spl_junction_motifs", "spl_junction_motifs_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_coverage_fragments", "spl_coverage_fragment_totals", "spl_intron_depth_fragments", "spl_coverage_fragment_rule_host", "spl_coverage_cursor_host", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_reads_subsample", "spl_subsample_keep_host", "spl_subsample_tile", "spl_reads_n_segments", "spl_lanes_plan_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
+    "spl_gene_search", "spl_junctions", "spl_junctions_get", "spl_junctions_stats", "spl_junction_walk_host", "spl_junctions_fragments", "spl_junction_fragment_rule_host", "spl_strand_tally", "spl_strand_rule_host", "spl_genome_open", "spl_genome_n", "spl_genome_name", "spl_genome_bases", "spl_genome_stats", "spl_genome_free", "spl_genome_pack_host", "spl_reads_motif_strand", "spl_motif_read_strand_host", "spl_junction_motifs", "spl_junction_motifs_host", "spl_coverage", "spl_coverage_totals", "spl_coverage_download", "spl_coverage_free", "spl_coverage_rule_host", "spl_bedgraph_append", "spl_coverage_fragments", "spl_coverage_fragment_totals", "spl_intron_depth_fragments", "spl_coverage_fragment_rule_host", "spl_coverage_cursor_host", "spl_gene_count", "spl_gene_count_rule_host", "spl_mate_table", "spl_gene_count_fragments", "spl_name_key_host", "spl_reads_subsample", "spl_subsample_keep_host", "spl_subsample_tile", "spl_reads_n_segments", "spl_reads_duplicates", "spl_reads_dedup", "spl_duplicates_host", "spl_lanes_plan_host", "spl_mate_table_host", "spl_gene_fragment_rule_host", "spl_exon_count", "spl_exon_count_rule_host", "spl_exon_count_fragments", "spl_exon_fragment_rule_host", "spl_intron_depth", "spl_intron_depth_runs", "spl_intron_depth_host", "spl_simple_span_host", "spl_sites_index_info", "spl_sites_index_download", "spl_tsv_append", "spl_tsv_append_many", "spl_fmt_fixed",
     "spl_bed_open", "spl_gff_open", "spl_text_close", "spl_text_rows", "spl_text_n_chrom", "spl_text_chrom_name", "spl_text_chrom",
     "spl_text_i64", "spl_text_strand", "spl_text_names",
     "spl_combine_open", "spl_combine_close", "spl_combine_rows", "spl_combine_n_texts", "spl_combine_text", "spl_combine_region_runs",
@@ -460,6 +460,30 @@ class DeviceReads(object):
         if not (0 <= seed < 1 << 64 and 0 <= threshold < 1 << 64):
             raise ValueError("seed and threshold are unsigned 64-bit numbers")
         _check(lib().spl_reads_subsample(self.ctx._h, self._h, ctypes.c_uint64(seed), ctypes.c_uint64(threshold), ctypes.byref(h), _ptr(kept), _ptr(index)))
+        kept = kept[:n_seg]
+        total = int(kept.sum())
+        out = DeviceReads(self.ctx, h, total)
+        return (out, kept, index[:total]) if with_index else (out, kept)
+
+    def duplicates(self, seg, n_reads=None):
+        """The duplicate marks of segment ``seg`` of this (finished, fused) set with name keys, made on the device at the first call
+        and kept with the set (``spl_reads_duplicates``; the rule is ``csrc/spl_dup_rule.h``) -> (dup bool[reads of the segment],
+        counts: dict of ``DUP_COUNTS``, hist int64[257]: groups of size 1 .. 255 and 256+, then the fragments of the last bin's
+        groups).  ``seg`` and ``n_reads`` as for ``mate_table``; ``n_reads`` None: no marks come down."""
+        counts, hist = np.zeros(len(DUP_COUNTS), np.int64), np.zeros(DUP_HIST, np.int64)
+        dup = None if n_reads is None else np.zeros(max(int(n_reads), 1), np.uint8)
+        _check(lib().spl_reads_duplicates(self.ctx._h, self._h, ctypes.c_int(int(seg)), _ptr(dup), _ptr(counts), _ptr(hist)))
+        return (None if dup is None else dup[:int(n_reads)].astype(bool)), dict(zip(DUP_COUNTS, counts.tolist())), hist
+
+    def dedup(self, with_index=False):
+        """The read set of the reads of this (finished, fused) set with name keys that are no duplicates, made on the device
+        (``spl_reads_dedup``) -> what ``subsample`` returns: a finished, fused set on arrays of its own and the reads kept per
+        segment; ``with_index``: the number within this set of every kept read too."""
+        h = ctypes.c_void_p()
+        n_seg = self.n_segments()
+        kept = np.zeros(max(n_seg, 1), np.int64)
+        index = np.empty(max(self.n, 1), np.uint32) if with_index else None
+        _check(lib().spl_reads_dedup(self.ctx._h, self._h, ctypes.byref(h), _ptr(kept), _ptr(index)))
         kept = kept[:n_seg]
         total = int(kept.sum())
         out = DeviceReads(self.ctx, h, total)
@@ -1444,6 +1468,23 @@ def subsample_keep_host(name_key, pos, flag, cig_off, seed, threshold):
 def subsample_tile():
     """The reads of a tile of ``spl_reads_subsample``'s kernels (``spl_subsample_tile``): the tests' shapes hang on it."""
     return int(lib().spl_subsample_tile())
+
+
+# spl_reads_duplicates' seven counters; its histogram has DUP_HIST sums (sizes 1 .. 255, 256+, the fragments of the 256+ groups)
+DUP_COUNTS = ("reads", "examined", "pair_fragments", "single_fragments", "duplicate_pairs", "duplicate_singles", "flagged_in_file")
+DUP_HIST = 257
+
+
+def duplicates_host(reads, name_key, mate):
+    """The duplicate rule over one segment's host arrays (``ReadArrays``-like) and its mate table by the rule header behind a
+    stable sort on the host (``spl_duplicates_host``, no GPU) -> (dup bool[n], counts dict, hist int64[257])."""
+    name_key, mate = _arr(name_key, np.uint64), _arr(mate, np.uint32)
+    if name_key.shape[0] != reads.n or mate.shape[0] != reads.n:
+        raise ValueError("name_key and mate must have n_reads entries")
+    dup, counts, hist = np.zeros(max(reads.n, 1), np.uint8), np.zeros(len(DUP_COUNTS), np.int64), np.zeros(DUP_HIST, np.int64)
+    _check(lib().spl_duplicates_host(ctypes.c_int64(reads.n), _ptr(reads.pos), _ptr(reads.flag), _ptr(reads.cig_off), _ptr(reads.cigar) if len(reads.cigar) else None,
+                                     _ptr(name_key), _ptr(mate), _ptr(dup), _ptr(counts), _ptr(hist)))
+    return dup[:reads.n].astype(bool), dict(zip(DUP_COUNTS, counts.tolist())), hist
 
 
 LANE_PLAN_STRIDE = 6 + 4 * 12

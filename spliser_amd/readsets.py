@@ -82,35 +82,54 @@ _kept_lock = threading.Lock()
 
 
 @contextlib.contextmanager
-def _selected(dr, subsample, kept):
-    """``dr`` itself, or -- ``subsample`` = (seed, threshold) -- the set of its reads that the rule keeps, selected on the device and
-    freed on the way out (None when none is kept).  ``kept`` (or None): a list whose two entries get the reads kept and the reads
-    they were selected from added."""
-    if dr is None or subsample is None:
+def _selected(dr, subsample, kept, dedup=False, removed=None):
+    """``dr`` itself, or -- ``subsample`` = (seed, threshold) -- the set of its reads that the rule keeps, selected on the device, or --
+    ``dedup`` -- the set without its duplicate fragments (``DeviceReads.dedup``), or the second of the first: a shallower library
+    is deduplicated as a shallower library would be.  What is made here is freed on the way out (None when no read is left).
+    ``kept`` (or None): a list whose two entries get the reads kept by the selection and the reads they were selected from
+    added; ``removed`` (or None): likewise the duplicate reads removed and the reads they were removed from."""
+    if dr is None or (subsample is None and not dedup):
         yield dr
         return
-    sel, _ = dr.subsample(*subsample)
+    made = []
     try:
-        if kept is not None:
-            with _kept_lock:
-                kept[0] += sel.n
-                kept[1] += dr.n
-        yield sel if sel.n else None
+        if subsample is not None:
+            sel, _ = dr.subsample(*subsample)
+            made.append(sel)
+            if kept is not None:
+                with _kept_lock:
+                    kept[0] += sel.n
+                    kept[1] += dr.n
+            dr = sel
+        if dedup and dr.n:
+            left, _ = dr.dedup()
+            made.append(left)
+            if removed is not None:
+                with _kept_lock:
+                    removed[0] += dr.n - left.n
+                    removed[1] += dr.n
+            if len(made) == 2:          # (the selection has served: the deduplicated set is on arrays of its own)
+                made.pop(0).free()
+            dr = left
+        yield dr if dr.n else None
     finally:
-        sel.free()
+        for s in made:
+            s.free()
 
 
 @contextlib.contextmanager
-def fused_set(ctx, source, chrom, add, with_keys=False, with_strand=False, subsample=None, kept=None):
+def fused_set(ctx, source, chrom, add, with_keys=False, with_strand=False, subsample=None, kept=None, dedup=False, removed=None):
     """One entry of a plan as a finished read set on ``ctx`` -- None when the chromosome has no read --, freed on the way out.  Reads
     on the host (``add`` None) go up as four arrays, ``with_keys`` / ``with_strand``: with their name keys / strand bytes, which the
     source must have (``DecodeOptions.mate_keys`` / ``aux_strand``).  ``subsample`` = (seed, threshold): the set handed out is the
     one ``DeviceReads.subsample`` selects from it (the source needs name keys; reads on the host go up with theirs), and ``kept`` (a list of two) gets the reads
-    kept and the reads they were selected from added."""
-    with_keys = with_keys or subsample is not None
+    kept and the reads they were selected from added.  ``dedup``: the set handed out is without its duplicate fragments
+    (``DeviceReads.dedup``: name keys again, and the file whole on one device -- ``check_fragment_source``), behind ``subsample`` when
+    both are given; ``removed`` (a list of two) gets the reads removed and the reads they were removed from added."""
+    with_keys = with_keys or subsample is not None or bool(dedup)
     if add is not None:
         with ctx.begin_reads() as dr:
-            with _selected(dr.finish() if add(dr) else None, subsample, kept) as out:
+            with _selected(dr.finish() if add(dr) else None, subsample, kept, dedup, removed) as out:
                 yield out
         return
     rs = source.reads(chrom)
@@ -125,15 +144,15 @@ def fused_set(ctx, source, chrom, add, with_keys=False, with_strand=False, subsa
     with ctx.upload_soa([arrays], [getattr(rs, "max_end", None)], with_keys=with_keys, with_strand=with_strand) as soa:
         with ctx.begin_reads() as dr:
             dr.add_soa(soa, 0)
-            with _selected(dr.finish(), subsample, kept) as out:
+            with _selected(dr.finish(), subsample, kept, dedup, removed) as out:
                 yield out
 
 
-def over_fused_sets(source, devices, chroms, visit, with_keys=False, with_strand=False):
+def over_fused_sets(source, devices, chroms, visit, with_keys=False, with_strand=False, dedup=False, removed=None):
     """``visit(dr, chrom)`` for a finished, fused read set per chromosome of ``chroms`` that has a read (per piece of it, after a
-    decode in shares) -- called from one thread per device, so it guards what it adds to."""
+    decode in shares) -- called from one thread per device, so it guards what it adds to.  ``dedup`` / ``removed``: ``fused_set``'s."""
     def job(ctx, chrom, add):
-        with fused_set(ctx, source, chrom, add, with_keys, with_strand) as dr:
+        with fused_set(ctx, source, chrom, add, with_keys, with_strand, dedup=dedup, removed=removed) as dr:
             if dr is not None:
                 visit(dr, chrom)
     run_plans(plans_of(source, devices, chroms), job)

@@ -44,8 +44,20 @@ def check(steps, minReads, strandedType):
         raise ValueError("saturation: -s auto is not taken here: the `strandedness` command tells whether the library is fr or rf")
 
 
-def _row_of_step(ctx, sets, chroms, stranded, isStranded, strandedType, knobs, qChrom, minReads, spent):
-    """One row's six numbers from the step's sets ({chrom: DeviceReads}): the path of ``process`` without ``-b``, without its files."""
+def _row_of_step(ctx, sets, chroms, stranded, isStranded, strandedType, knobs, qChrom, minReads, spent, dedup=False):
+    """One row's six numbers from the step's sets ({chrom: DeviceReads}): the path of ``process`` without ``-b``, without its files.
+    ``dedup``: from the sets without their duplicate fragments, made here and freed here; a seventh number, the reads before."""
+    if dedup:
+        t0 = time.perf_counter()
+        before, left = sum(s.n for s in sets.values()), {}
+        try:
+            for chrom, dr in sets.items():
+                left[chrom] = dr.dedup()[0]
+            spent["selections_s"] += time.perf_counter() - t0
+            return _row_of_step(ctx, {c: s for c, s in left.items() if s.n}, chroms, stranded, isStranded, strandedType, knobs, qChrom, minReads, spent) + (before,)
+        finally:
+            for s in left.values():
+                s.free()
     t0 = time.perf_counter()
     tables = {c: sets[c].junctions(stranded, *knobs) for c in chroms if c in sets}
     t1 = time.perf_counter()
@@ -89,11 +101,14 @@ def _set_or_none(ctx, dr):
 
 
 def saturation(inBAM, outputPath, steps=20, seed=0, minReads=10, qChrom="All", isStranded=False, strandedType=None, minAnchor=8, minIntron=70, maxIntron=500000,
-               anyOrder=False, gpuDecode=None, devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, timings=None):
+               anyOrder=False, gpuDecode=None, devices=(0,), threads=0, log=None, minMapQ=0, requireFlags=0, excludeFlags=0, timings=None, dedup=False):
     """Writes ``<outputPath>.saturation.tsv`` -- a row per step k = 1 .. ``steps``: the fraction k / steps, the placed reads kept, the
     junctions (BED lines), those whose score is at least ``minReads``, the sum of the scores, the sites (rows of ``.SpliSER.tsv``) and
     those with alpha_count + beta1_count + beta2Simple_count >= ``minReads`` -- and returns the rows.  ``timings`` (a dict, or None):
-    gets the seconds of the decode, the selections, the junction tables, the site tables (host) and the counting passes."""
+    gets the seconds of the decode, the selections, the junction tables, the site tables (host) and the counting passes.  ``dedup``:
+    every step's selected set is deduplicated (``DeviceReads.dedup``) before its row is made -- the kept sets are not nested under
+    dedup, so the chain of selections stays as it is and the deduplicated sets live for their step only --, the table gets one more
+    column, ``reads_before_dedup``, and a returned row a seventh number."""
     log = _process.logger(log)
     check(steps, minReads, strandedType)
     steps, seed, minReads = int(steps), int(seed), int(minReads)
@@ -147,15 +162,17 @@ def saturation(inBAM, outputPath, steps=20, seed=0, minReads=10, qChrom="All", i
                         else:
                             sel.free()
                     spent["selections_s"] += time.perf_counter() - t0
-                    rows[k] = _row_of_step(ctx, current, chroms, stranded, isStranded, strandedType, knobs, qChrom, minReads, spent)
+                    rows[k] = _row_of_step(ctx, current, chroms, stranded, isStranded, strandedType, knobs, qChrom, minReads, spent, dedup=bool(dedup))
                     log("step %d of %d (fraction %r): %d reads, %d junctions (%d with at least %d reads), %d sites (%d with at least %d reads)"
                         % (k, steps, k / steps, rows[k][0], rows[k][1], rows[k][2], minReads, rows[k][4], rows[k][5], minReads))
+                    if dedup:
+                        log("  (dedup: %d of %d reads removed as duplicates)" % (rows[k][6] - rows[k][0], rows[k][6]))
             finally:
                 for chrom, dr in current.items():
                     if chrom not in held:          # (a whole set goes with its stack)
                         dr.free()
     with open(outputPath + SUFFIX, "w") as out:
-        out.write(HEADER)
+        out.write(HEADER[:-1] + "\treads_before_dedup\n" if dedup else HEADER)
         for k in range(1, steps + 1):
             out.write("%d\t%r\t%s\n" % (k, k / steps, "\t".join("%d" % v for v in rows[k])))
     if steps % 2 == 0:
